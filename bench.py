@@ -15,11 +15,17 @@ collective runs inside the denoiser.  No torch anywhere: `python bench.py --gpus
 workers (from a parent that never touches the GPU); under `python -m torch.distributed.run` the ranks
 it created are used as they are (RANK / LOCAL_RANK / WORLD_SIZE), torch itself is never imported.
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live (HIP events on the library's stream around
-the dominant kernel class during the timed steps).  N = 1 adds: `cpu_baseline` (the NumPy oracle on
-the host cores, bounded sample), `f32_exact` (the same workload on the exact-f32 MFMA kernels),
-`rollout` (30-step autoregressive forecast wall-clock) and `one_degree` (BASELINE configs[3]: 1 deg
-grid, full GenCast widths, its own dominant kernel and roofline).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`); nothing else is measured.  `--full` adds what needs runs of its own: `roofline`
+(an untimed pre-pass per kernel class, then HIP events on the library's stream around the dominant class
+during the timed steps) and, N = 1: `cpu_baseline` (the NumPy oracle on the host cores, bounded sample),
+`f32_exact` (the same workload on the exact-f32 MFMA kernels), `rollout` (30-step autoregressive forecast
+wall-clock) and `one_degree` (BASELINE configs[3]: 1 deg grid, full GenCast widths, its own dominant
+kernel and roofline).
+
+`--dump-outputs DIR`: after the timed steps every rank writes the sample its last timed step computed
+(what `download_sample` hands a caller) as DIR/sample.npy (rank 0) or DIR/sample_rank<r>.npy, float32.
+The inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -38,11 +44,17 @@ PEAK_HBM_GBS = 8000.0
 CALLS_PER_STEP = 39
 
 
-def parse_args():
+def parse_args(argv=None):
   p = argparse.ArgumentParser()
   p.add_argument("--gpus", type=int, default=1)
-  p.add_argument("--steps", type=int, default=5)
+  p.add_argument("--steps", type=int, default=5, help="timed steps (one step = one 39-call sample)")
   p.add_argument("--warmup", type=int, default=1)
+  p.add_argument("--full", action="store_true",
+                 help="also measure the roofline and, N = 1, the extras below (cpu_baseline, f32_exact, fp16_features, "
+                      "three_members_in_flight, graph_replay, rollout, one_degree), as chosen by --no-cpu-baseline, "
+                      "--cpu-baseline-calls, --rollout-steps, --no-extras and --extra-steps")
+  p.add_argument("--dump-outputs", metavar="DIR",
+                 help="write the sample of the last timed step to DIR/sample.npy (float32; other ranks: sample_rank<r>.npy)")
   p.add_argument("--no-cpu-baseline", action="store_true")
   p.add_argument("--cpu-baseline-calls", type=int, default=6)   # ~12 s of host work
   p.add_argument("--cpu-threads", type=int, default=16)
@@ -55,7 +67,10 @@ def parse_args():
                  help="N > 1: if RCCL cannot span all ranks (e.g. two ranks rehearsing on one GPU), time the host-file "
                       "fallback instead of exiting non-zero; the line then says broadcast: host-file")
   p.add_argument("--extra-steps", type=int, default=5, help="timed steps of the N = 1 extra objects (f32_exact, ...)")
-  return p.parse_args()
+  args = p.parse_args(argv)
+  if args.steps < 1:
+    p.error("--steps must be at least 1")
+  return args
 
 
 def time_rollout(steps, arch, params, lat, lon, device_id, *, graph=None, options=None, device_noise=False,
@@ -477,23 +492,24 @@ def main():
   exchange()
   nd.sync()
 
-  # ---- pick the dominant kernel class (untimed pre-pass) ---------------------------------------
-  classes = nd.kernel_classes()
   for _ in range(max(args.warmup, 1)):
     one_step()
   nd.sync()
-  per_class = class_profile(nd, sigmas, classes) if rank == 0 else {}
+  # ---- --full: pick the dominant kernel class (untimed pre-pass) ---------------------------------
+  classes = nd.kernel_classes()
+  profiled = args.full and rank == 0
+  per_class = class_profile(nd, sigmas, classes) if profiled else {}
   dominant = max(per_class, key=lambda k: per_class[k][1]) if per_class else classes[0]
   dom_idx = classes.index(dominant)
 
   # ---- timed region: exactly K steps between barriers -------------------------------------------
-  # Every rank enqueues the timed steps EAGERLY (sampler graphs off): rank 0 brackets the dominant class's launches
-  # with HIP events, which a replayed graph cannot carry, and the ranks' per-rank figures must come from one path
-  # (ADVICE r3).  Device time is the same either way (graph replay changes host time only: `graph_replay` below).
+  # Every rank enqueues the timed steps EAGERLY (sampler graphs off): with --full rank 0 brackets the dominant class's
+  # launches with HIP events, which a replayed graph cannot carry, and the ranks' per-rank figures must come from one
+  # path.  Device time is the same either way (graph replay changes host time only: `graph_replay` below).
   graphs_wanted = os.environ.get("GC_TUNE_GRAPH", "1") != "0"      # the library's default, restored after the timed region
   nd.set_option("graphs", "off")
-  if rank == 0:
-    nd.profile_set_stride(sampling_stride(per_class, dominant) if per_class else 8)   # ~1 launch in 8: keeps the event records out of the way
+  if profiled:
+    nd.profile_set_stride(sampling_stride(per_class, dominant))   # ~1 launch in 8: keeps the event records out of the way
     nd.profile_enable(dom_idx)
   barrier()
   t0 = time.perf_counter()
@@ -502,10 +518,14 @@ def main():
   nd.sync()
   barrier()
   elapsed = time.perf_counter() - t0
-  dom_launches, dom_ms = nd.profile_read() if rank == 0 else (0, 0.0)
-  if rank == 0:
+  dom_launches, dom_ms = nd.profile_read() if profiled else (0, 0.0)
+  if profiled:
     nd.profile_enable(-1)
     nd.profile_set_stride(1)
+  if args.dump_outputs:                               # before anything else runs on the handle's sample buffer
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "sample.npy" if rank == 0 else f"sample_rank{rank}.npy"),
+            nd.download_sample())
   nd.set_option("graphs", "on" if graphs_wanted else "off")       # (an A/B run with GC_TUNE_GRAPH=0 keeps its extras eager)
   own_elapsed = elapsed
   fastest = elapsed
@@ -514,7 +534,7 @@ def main():
     fastest = -allreduce_max(-own_elapsed)            # MIN over ranks
   # what the exchange costs on its own (outside the timed region): broadcast + re-pack, waited for
   bcast_ms = None
-  if use_comm:
+  if use_comm and args.full:
     barrier()
     tb = time.perf_counter()
     for _ in range(3):
@@ -530,35 +550,39 @@ def main():
     precision = os.environ.get("GC_PRECISION", "f16x3")
     total_calls = world * args.steps * CALLS_PER_STEP
     value = total_calls / elapsed
-    roofline = roofline_of(nd, graph, dims, per_class, dominant, dom_launches, dom_ms, precision, value / world)
-    # Figures that need the profiler come from the committed rocprofv3 passes of tools/profile_round.sh -- and only
-    # when those passes were made on THIS tree's kernels (profiles/profile_meta.json records the source hash);
-    # otherwise they are left out rather than quoted next to numbers they do not belong to.
-    prof = profile_figures(dominant)
-    roofline["traffic"] = prof["traffic"]
-    roofline["mfma_busy"] = prof["mfma_busy"]
-    roofline["inter_kernel_gaps"] = prof["inter_kernel_gaps"]
-    roofline["from_profile"] = prof["from_profile"]
-    roofline["note"] = (
-        "achieved = algorithmic f32 FLOPs of one launch / live HIP-event duration. peak: f16x3 mode executes every "
-        "product as 3 fp16 MFMAs, so the MFMA ceiling in algorithmic FLOPs is the dense fp16 peak / 3 (2516.6 / 3 "
-        "TFLOP/s); f32 mode: the dense f32 matrix peak 157.3. traffic / mfma_busy / inter_kernel_gaps = memory-side bytes "
-        "per launch, SQ_VALU_MFMA_BUSY_CYCLES share and device-timeline gaps from the committed rocprofv3 passes of "
-        "tools/profile_round.sh (from_profile says which, and that they were made on this tree's kernels)")
+    roofline = None
+    if args.full:
+      roofline = roofline_of(nd, graph, dims, per_class, dominant, dom_launches, dom_ms, precision, value / world)
+      # Figures that need the profiler come from the committed rocprofv3 passes of tools/profile_round.sh -- and only
+      # when those passes were made on THIS tree's kernels (profiles/profile_meta.json records the source hash);
+      # otherwise they are left out rather than quoted next to numbers they do not belong to.
+      prof = profile_figures(dominant)
+      roofline["traffic"] = prof["traffic"]
+      roofline["mfma_busy"] = prof["mfma_busy"]
+      roofline["inter_kernel_gaps"] = prof["inter_kernel_gaps"]
+      roofline["from_profile"] = prof["from_profile"]
+      roofline["note"] = (
+          "achieved = algorithmic f32 FLOPs of one launch / live HIP-event duration. peak: f16x3 mode executes every "
+          "product as 3 fp16 MFMAs, so the MFMA ceiling in algorithmic FLOPs is the dense fp16 peak / 3 (2516.6 / 3 "
+          "TFLOP/s); f32 mode: the dense f32 matrix peak 157.3. traffic / mfma_busy / inter_kernel_gaps = memory-side "
+          "bytes per launch, SQ_VALU_MFMA_BUSY_CYCLES share and device-timeline gaps from the committed rocprofv3 passes "
+          "of tools/profile_round.sh (from_profile says which, and that they were made on this tree's kernels)")
     range_fallbacks = nd.counter("range_fallbacks")
+    launches_per_call = int(nd.counter("launches_per_call"))
 
+    extras = world == 1 and args.full and not args.no_extras
     xs = max(1, args.extra_steps)
     # the same workload through the replayed HIP graph of the sample (what a rollout driver runs): host enqueue time
     # per sample falls from ~25 ms to ~0.1 ms, device time does not change
     graph_replay = None
-    if world == 1 and not args.no_extras:
+    if extras:
       c0, r0 = nd.counter("graph_captures"), nd.counter("graph_replays")
       time_samples(nd, sigmas, 2)                                  # eager, then capture + first replay
       dtg = time_samples(nd, sigmas, xs)
       graph_replay = {"value": round(xs * CALLS_PER_STEP / dtg, 2), "unit": "calls/s", "steps": xs,
                       "graph_captures": nd.counter("graph_captures") - c0, "graph_replays": nd.counter("graph_replays") - r0}
     f32_exact = None
-    if world == 1 and not args.no_extras and precision == "f16x3":
+    if extras and precision == "f16x3":
       nd.set_option("precision", "f32")
       time_samples(nd, sigmas, 1)
       pc32 = class_profile(nd, sigmas, classes)
@@ -578,7 +602,7 @@ def main():
                            "gc_set_option(precision, f32); roofline.peak = the dense f32 matrix peak"}
 
     fp16_features = None
-    if world == 1 and not args.no_extras and precision == "f16x3":
+    if extras and precision == "f16x3":
       nd.set_option("features", "f16")                # BASELINE configs[4]'s arithmetic on the configs[1] workload
       nd.upload_cond(cond)
       nd.upload_noise(noise)
@@ -595,7 +619,7 @@ def main():
       nd.upload_noise(noise)
 
     members3 = None
-    if world == 1 and not args.no_extras and precision == "f16x3":
+    if extras and precision == "f16x3":
       # ensemble throughput of ONE GPU: 3 members in flight on 3 handles (= 3 HIP streams); `value` above stays
       # the 1-member figure BASELINE configs[1] names
       lanes = [nd]
@@ -632,7 +656,7 @@ def main():
         ln.close()
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
       from oracle import gencast_oracle as O  # the CPU baseline leg is the ONLY oracle use here
       import dataclasses
       gd = dataclasses.asdict(graph)
@@ -656,11 +680,11 @@ def main():
     if not getattr(nd, "comm_stuck", False):
       nd.close()
     rollout_info = None
-    if world == 1 and args.rollout_steps > 0:
+    if world == 1 and args.full and args.rollout_steps > 0:
       # second half of BASELINE.json's metric: rollout wall-clock (one member, context resident in HBM)
       rollout_info = time_rollout(args.rollout_steps, arch, params, lat, lon, device_id, device_noise=True)
     one_degree = one_degree_rollout = None
-    if world == 1 and not args.no_extras:
+    if extras:
       one_degree, one_degree_rollout = one_degree_objects(device_id, precision, args.rollout_steps, xs)
     line = {
         "metric": "denoiser-calls/sec", "value": round(value, 2), "unit": "calls/s", "n_gpus": world,
@@ -681,14 +705,16 @@ def main():
                    "per_rank_calls_per_sec": {"min": round(args.steps * CALLS_PER_STEP / elapsed, 2),
                                               "max": round(args.steps * CALLS_PER_STEP / fastest, 2)},
                    "precision": precision,
-                   "timed_path": "eager launches on every rank (sampler graphs off; rank 0 brackets the dominant class with HIP events)",
+                   "timed_path": "eager launches on every rank (sampler graphs off" + (
+                       "; rank 0 brackets the dominant class with HIP events)" if args.full else ")"),
                    "graphs_outside_timed_region": "on" if graphs_wanted else "off (GC_TUNE_GRAPH=0)",
                    "library_sources": library_source_hash(), "library_built_from_this_tree": library_source_hash() == source_hash(),
                    "launcher": os.environ.get("GC_BENCH_LAUNCHER", "env" if "WORLD_SIZE" in os.environ else "single"),
                    "torch_imported": "torch" in sys.modules},
         "sample_seconds": round(elapsed / args.steps, 4),
-        "launches_per_call": roofline["launches_per_call"], "range_fallbacks": range_fallbacks,
-        "roofline": roofline, "cpu_baseline": cpu, "f32_exact": f32_exact, "fp16_features": fp16_features, "three_members_in_flight": members3, "graph_replay": graph_replay, "rollout": rollout_info,
+        "launches_per_call": launches_per_call, "range_fallbacks": range_fallbacks,
+        # null unless --full
+        "full": args.full, "roofline": roofline, "cpu_baseline": cpu, "f32_exact": f32_exact, "fp16_features": fp16_features, "three_members_in_flight": members3, "graph_replay": graph_replay, "rollout": rollout_info,
         "one_degree": one_degree, "one_degree_rollout_fp16_features": one_degree_rollout,
     }
     if cpu:
