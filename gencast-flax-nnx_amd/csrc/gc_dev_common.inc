@@ -1,4 +1,4 @@
-// Device-side helpers shared by the kernel translation units (gc_kernels.hip, compiled twice, and gc_gemm_lt.hip):
+// Device-side helpers of the library's kernels (gc_kernels.hip, compiled twice: gc and gc_a16; tools/gemm_lt reuses them):
 // vector typedefs, 16-byte loads / stores, the f16x3 split, MFMA wrappers, fast activations.  Included INSIDE the
 // including file's namespace (no include guard).
 
@@ -9,12 +9,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-// Write-through 16-byte store (`sc1`): the line goes to memory now and is dropped from this XCD's L2 instead of
-// staying dirty until the end-of-kernel write-back.  Measured on the fused FFW's slabs and the fused MLPs'
-// outputs (GC_TUNE_WT_STORES): slower / neutral -- see DESIGN.md section 5, dead ends.
-__device__ __forceinline__ void st4_wt(float* p, f32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
-}
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -30,7 +24,8 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr float kLoScale = 2048.0f;
 // value of a split-product accumulator pair: hi + lo / 2048 as ONE explicit fused multiply-add.  Written `hi + lo *
 // (1 / 2048)` hipcc (-ffp-contract=fast) contracted some unrolled instances and not others, so a row's last bit depended
-// on which 32-row MFMA tile of the workgroup it sat in (found in round 5: tests/gpu_debug_tri2.py).
+// on which 32-row MFMA tile of the workgroup it sat in (found in round 5; guarded by
+// tests/test_gpu_parity.py::test_a_rows_result_does_not_depend_on_where_it_sits_in_the_launch and tools/position_dependence_probe.py).
 __device__ __forceinline__ float hilo(float hi, float lo) { return __builtin_fmaf(lo, 1.0f / kLoScale, hi); }
 
 __device__ __forceinline__ f32x16 mfma16(f32x4 a, f32x4 b, f32x16 c) {
@@ -49,7 +44,7 @@ constexpr float kF16Max = 65504.0f;
 // x is itself a product (x = a * b: swish, gelu, a conditioning scale) the compiler may fuse it into the subtraction --
 // lo = f16(fma(a, b, -hi) * 2048), the residual of the UNROUNDED product -- and it did so for some unrolled instances and
 // not for others, so a row's last bits depended on which 32-row MFMA tile of a workgroup it sat in (found in round 5 from
-// the ISA: v_pk_fma_f32 ... neg_lo behind v_cvt_pk_f16_f32; tests/gpu_debug_tri3.py).  Both forms are within the split's
+// the ISA: v_pk_fma_f32 ... neg_lo behind v_cvt_pk_f16_f32; same test and probe).  Both forms are within the split's
 // 2^-22; only one of them is a function of x alone.
 __device__ __forceinline__ void split16(float x, _Float16& hi, _Float16& lo) {
 #pragma clang fp contract(off)

@@ -1154,8 +1154,7 @@ __device__ __forceinline__ void gc_mlp_ws_body(const MlpArgs& a, const int bid) 
             if (c + e < n) as_h16(a.out)[(size_t)orow * a.ldo + c + e] = (_Float16)v[e];
         }
       } else if (vec_io) {
-        if (a.wt) st4_wt(a.out + (size_t)orow * a.ldo + c, v);
-        else st4(a.out + (size_t)orow * a.ldo + c, v);
+        st4(a.out + (size_t)orow * a.ldo + c, v);
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -1278,95 +1277,53 @@ static hipError_t launch_mlp_t(hipStream_t s, const MlpArgs& a) {
   return hipGetLastError();
 }
 
+// hidden 256 from this many rows on: 64-row tiles (measured at nano: they win only on the 31.5k-edge MLP); below it
+// 8 column waves x 32 rows, two workgroups (16 waves) per CU -- 1-6 us faster per launch than 4 waves x 32 rows
+constexpr int kMlpMt2Rows = 24000;
+
+// The one rule for the MLP kernel form: launch_mlp dispatches on it, and gc_api asks it before it relies on a form.
+// Weight-streaming whenever weight images are given (WF16: f16x3, WF32: exact f32) and the shape has a form -- hidden
+// 128 / 256 with n_out_pad <= hidden, hidden 512 with n_out_pad 512 or 128 -- else the LDS-staged kernel.
 bool mlp_runs_weight_streaming(const MlpArgs& a) {
   const int nt1 = a.hidden / 128, nt2 = a.n_out_pad / 128;
   if (a.hidden % 128 || a.n_out_pad % 128 || a.n_out_pad > a.hidden || !((a.f16 || a.f32w) && a.w1f)) return false;
   if (nt1 <= 2) return nt2 <= nt1;
-  const char* e = getenv("GC_TUNE_MLP_WS512");
-  return nt1 == 4 && !(e && *e && atoi(e) == 0) && (nt2 == 4 || nt2 == 1);
+  return nt1 == 4 && (nt2 == 4 || nt2 == 1);
 }
 
 hipError_t launch_mlp(hipStream_t s, const MlpArgs& a) {
   const int nt1 = a.hidden / 128, nt2 = a.n_out_pad / 128;
   if (a.hidden % 128 || a.n_out_pad % 128 || a.n_out_pad > a.hidden) return hipErrorInvalidValue;
-  // 64-row tiles once there are enough rows to keep every CU busy with them (f16x3 only: the f32
-  // path is MFMA-bound and prefers more, smaller tiles)
-  static int big_rows = -1;
-  if (big_rows < 0) {
-    const char* e = getenv("GC_TUNE_MLP_BIG_ROWS");
-    big_rows = (e && *e) ? atoi(e) : (1 << 30);   // measured neutral at nano: off by default
-  }
-  // weight-streaming form; hidden = 512 runs it with 8 column waves (GC_TUNE_MLP_WS512=0: LDS-staged kernel)
-  static int ws512 = -1;
-  if (ws512 < 0) {
-    const char* e = getenv("GC_TUNE_MLP_WS512");
-    ws512 = (e && *e) ? atoi(e) : 2;             // != 0: 64-row tiles (1-degree config: 3.1 ms per call; LDS-staged 7.1)
-  }
-  const bool ws_ok = (a.f16 || a.f32w) && a.w1f;   // weight-streaming form: f16x3 (WF16 images) or exact f32 (WF32)
-  if (ws_ok && nt1 == 4 && ws512) {
-    if (nt2 == 4) return launch_mlp_ws_t<2, 2, 2, 1, 8, 8>(s, a);   // (the 32-row forms: 3.9 vs 3.1 ms per 1-degree call, removed in round 5)
-    if (nt2 == 1) return launch_mlp_ws_t<2, 1, 2, 1, 8, 4>(s, a);
-  }
-  // hidden = 256 below the 64-row threshold: 8 column waves x 32 rows, two workgroups (16 waves) per
-  // CU -- measured 1-6 us faster per launch than 4 waves x 32 rows (GC_TUNE_MLP_WS8=0 for the latter)
-  static int ws8 = -1, ws8_rows = -1;
-  if (ws8 < 0) {
-    const char* e = getenv("GC_TUNE_MLP_WS8");
-    ws8 = (e && *e) ? atoi(e) : 1;
-    const char* r = getenv("GC_TUNE_MLP_MT2_ROWS");
-    ws8_rows = (r && *r) ? atoi(r) : 24000;
-  }
-  if (ws_ok && nt1 == 2 && ws8 && a.rows < ws8_rows) {
-    if (nt2 == 2) return launch_mlp_ws_t<1, 1, 1, 1, 8, 8>(s, a);
-    if (nt2 == 1) return launch_mlp_ws_t<1, 1, 1, 1, 8, 4>(s, a);
-  }
-  if (ws_ok && nt1 <= 2) {
-    static int mt2_rows = -1;                   // 64-row tiles from this many rows on (GC_TUNE_MLP_MT2_ROWS)
-    if (mt2_rows < 0) {
-      const char* e = getenv("GC_TUNE_MLP_MT2_ROWS");
-      mt2_rows = (e && *e) ? atoi(e) : 24000;   // measured at nano: 64-row tiles win only on the 31.5k-edge MLP
-    }
+  if (mlp_runs_weight_streaming(a)) {
+    // hidden 512: 8 column waves x 64 rows (1-degree config: 3.1 ms per call; 32-row forms 3.9, LDS-staged 7.1)
+    if (nt1 == 4) return nt2 == 4 ? launch_mlp_ws_t<2, 2, 2, 1, 8, 8>(s, a) : launch_mlp_ws_t<2, 1, 2, 1, 8, 4>(s, a);
     // (128-row tiles with one workgroup per CU were measured slower than 64-row ones -- 84 vs 77 us on the nano
     //  mesh2grid edge MLP -- and left the build in round 5 together with the NT1 = 4 four-wave forms no dispatch reached)
-    const bool mt2 = a.rows >= mt2_rows;
-#define GC_MLP_WS(A_, B_)                                                                \
-  if (nt1 == A_ && nt2 == B_) {                                                          \
-    if (mt2) return launch_mlp_ws_t<A_, B_, 2, 1>(s, a);                                 \
-    return launch_mlp_ws_t<A_, B_, 1, 1>(s, a);                                          \
+    const bool mt2 = a.rows >= kMlpMt2Rows;
+    if (nt1 == 2 && !mt2) return nt2 == 2 ? launch_mlp_ws_t<1, 1, 1, 1, 8, 8>(s, a) : launch_mlp_ws_t<1, 1, 1, 1, 8, 4>(s, a);
+    if (nt1 == 2) return nt2 == 2 ? launch_mlp_ws_t<2, 2, 2, 1>(s, a) : launch_mlp_ws_t<2, 1, 2, 1>(s, a);
+    return mt2 ? launch_mlp_ws_t<1, 1, 2, 1>(s, a) : launch_mlp_ws_t<1, 1, 1, 1>(s, a);
   }
-    GC_MLP_WS(1, 1) GC_MLP_WS(2, 2) GC_MLP_WS(2, 1)
-#undef GC_MLP_WS
-    return hipErrorInvalidValue;
-  }
-  // from here on: the LDS-staged kernels, which read and write float32 arrays only.  With physical fp16 storage
-  // (a.a16: halfs behind the float* fields) that would be silently wrong values -- e.g. GC_TUNE_MLP_WS512=0 at hidden
-  // 512 while gc_api's store16_ok() looks at the other switches only -- so it is an error instead
-  if (a.a16 || a.tri) return hipErrorInvalidValue;   // (the triple epilogue exists in the weight-streaming kernel only)
-  const bool big = a.f16 && a.rows >= big_rows && nt1 <= 2;
-#define GC_MLP(A_, B_)                                                                   \
-  if (nt1 == A_ && nt2 == B_) {                                                          \
-    if (!a.f16) return launch_mlp_t<A_, B_, false, 1>(s, a);                             \
-    if constexpr (A_ <= 2) { if (big) return launch_mlp_t<A_, B_, true, 2>(s, a); }      \
-    return launch_mlp_t<A_, B_, true, 1>(s, a);                                          \
-  }
+  // from here on: the LDS-staged kernel, exact f32 on float32 arrays only.  f16x3 always has its WF16 images, so it
+  // never lands here; physical fp16 storage (a.a16: halfs behind the float* fields) would be silently wrong values and
+  // the triple epilogue exists in the weight-streaming kernel only.  The kernel dereferences w1t and every add-term
+  // index (the weight-streaming kernel takes a null index as "the row itself"), so those are checked too.
+  if (a.f16 || a.a16 || a.tri || !a.w1t || a.nadd < 0 || a.nadd > 2) return hipErrorInvalidValue;
+  for (int i = 0; i < a.nadd; ++i)
+    if (!a.add[i].index) return hipErrorInvalidValue;
+#define GC_MLP(A_, B_) \
+  if (nt1 == A_ && nt2 == B_) return launch_mlp_t<A_, B_, false, 1>(s, a);
   GC_MLP(1, 1) GC_MLP(2, 2) GC_MLP(2, 1) GC_MLP(4, 4) GC_MLP(4, 1)
 #undef GC_MLP
   return hipErrorInvalidValue;
 }
 
-// Both MLPs on the 8-wave x 32-row weight-streaming form of hidden 256 (what launch_mlp picks below 24 000 rows), same
-// precision family, no triple epilogue: then one launch can run them side by side.
+// Both MLPs on the 8-wave weight-streaming form launch_mlp picks for them -- hidden 256 below kMlpMt2Rows rows (32-row
+// tiles) or latent 512 (64-row tiles) --, same precision family, no triple epilogue: then one launch runs them side by side.
 bool mlp_pair_supported(const MlpArgs& a, const MlpArgs& b) {
   auto ok = [](const MlpArgs& m) {
-    if (!((m.f16 || m.f32w) && m.w1f) || m.tri) return false;
-    if (m.hidden == 512 && m.n_out_pad == 512) {          // the 8-wave x 64-row form of latent 512
-      const char* e = getenv("GC_TUNE_MLP_WS512");
-      return !(e && *e && atoi(e) == 0);
-    }
-    const char* e8 = getenv("GC_TUNE_MLP_WS8");
-    const char* r8 = getenv("GC_TUNE_MLP_MT2_ROWS");
-    const int ws8_rows = (r8 && *r8) ? atoi(r8) : 24000;
-    return m.hidden == 256 && m.n_out_pad == 256 && !(e8 && *e8 && atoi(e8) == 0) && m.rows < ws8_rows;
+    if (!mlp_runs_weight_streaming(m) || m.tri || m.n_out_pad != m.hidden) return false;
+    return m.hidden == 512 || (m.hidden == 256 && m.rows < kMlpMt2Rows);
   };
   return ok(a) && ok(b) && a.hidden == b.hidden && a.f16 == b.f16 && a.f32w == b.f32w && a.a16 == b.a16;
 }
@@ -1781,44 +1738,31 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && MT == 1) ? 3 : 2) vo
 }
 
 template <int CLS>
-static hipError_t launch_gemm_c(hipStream_t s, const GemmArgs& g_in, int shape, int splits, int epi, bool f16) {
-  // shape 1: 32x128 tile, 2: 64x128 tile (256 threads)
-  if (shape < 1 || shape > 2) return hipErrorInvalidValue;
+static hipError_t launch_gemm_c(hipStream_t s, const GemmArgs& g_in, int splits, int epi, bool f16) {
+  // 32x128 tiles, 256 threads
   if (g_in.n % 128 || g_in.k_slice % kBK || g_in.lda % 4 || g_in.ldw % 4) return hipErrorInvalidValue;
   if (epi < 0 || epi > 1) return hipErrorInvalidValue;
-  const int bm = shape == 1 ? 32 : 64;
-  const int total = ((g_in.rows + bm - 1) / bm) * (g_in.n / 128) * splits;
-  // Persistent grid: as many workgroups as can be co-resident (LDS-limited: 3 / 2 / 2 per CU),
+  const int total = ((g_in.rows + 31) / 32) * (g_in.n / 128) * splits;
+  // Persistent grid: as many workgroups as can be co-resident (LDS-limited: 3 per CU),
   // and every workgroup gets the same number of output tiles.
-  static int cap_override = -1;
-  if (cap_override < 0) {
-    const char* e = getenv("GC_TUNE_GEMM_BLOCKS");
-    cap_override = (e && *e) ? atoi(e) : 0;
-  }
-  const int cap = cap_override > 0 ? cap_override : 256 * (shape == 1 ? 3 : 2);
+  const int cap = 256 * 3;
   const int rounds = (total + cap - 1) / cap;
   int nblk = (total + rounds - 1) / rounds;
   if (rounds > 1) nblk = (nblk + 7) & ~7;     // keep blockIdx % 8 == tile % 8 for the XCD-aware order
   dim3 grid(nblk, 1, 1);
   GemmArgs g = g_in;
   g.splits = splits;
-  if (g.att_S > 0) {                          // out-projection fed by attention partials (shape 1, slabs)
-    if (shape != 1 || epi != 1 || g.att_S > kMaxAttnSplits) return hipErrorInvalidValue;
+  if (g.att_S > 0) {                          // out-projection fed by attention partials (slabs)
+    if (epi != 1 || g.att_S > kMaxAttnSplits) return hipErrorInvalidValue;
     if (f16) hipLaunchKernelGGL((gc_gemm_kernel<1, 4, 1, 1, 1, CLS, true, 1>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((gc_gemm_kernel<1, 4, 1, 1, 1, CLS, false, 1>), grid, dim3(256), 0, s, g);
     return hipGetLastError();
   }
-#define GC_LAUNCH(WM_, WN_, MT_, NT_, EPI_, F16_) \
-  hipLaunchKernelGGL((gc_gemm_kernel<WM_, WN_, MT_, NT_, EPI_, CLS, F16_, 0>), grid, dim3(64 * WM_ * WN_), 0, s, g)
-#define GC_SHAPES(EPI_, F16_)                                   \
-  if (shape == 1) GC_LAUNCH(1, 4, 1, 1, EPI_, F16_);            \
-  else GC_LAUNCH(1, 4, 2, 1, EPI_, F16_);
-  if (epi == 0 && !f16) { GC_SHAPES(0, false) }
-  else if (epi == 0 && f16) { GC_SHAPES(0, true) }
-  else if (epi == 1 && !f16) { GC_SHAPES(1, false) }
-  else if (epi == 1 && f16) { GC_SHAPES(1, true) }
-  else return hipErrorInvalidValue;
-#undef GC_SHAPES
+#define GC_LAUNCH(EPI_, F16_) hipLaunchKernelGGL((gc_gemm_kernel<1, 4, 1, 1, EPI_, CLS, F16_, 0>), grid, dim3(256), 0, s, g)
+  if (epi == 0 && !f16) GC_LAUNCH(0, false);
+  else if (epi == 0) GC_LAUNCH(0, true);
+  else if (!f16) GC_LAUNCH(1, false);
+  else GC_LAUNCH(1, true);
 #undef GC_LAUNCH
   return hipGetLastError();
 }
@@ -1863,8 +1807,7 @@ hipError_t set_gemm_ws_stamp_buffer(unsigned long long* p) {
 // GEMMs -7 %, FFW-1 +-0 at the 1-degree size.  With float32 features the split arithmetic moves into the product
 // loop and the loop grows by MORE than the phase it replaces (stamps, profiles/r03_stamps_gemm_ws_pipe.txt: loops
 // 18.9k -> 28.1k cycles per wave for a 7.0k staging phase, wave lifetime 36.7k -> 39.8k): a SIMD's three waves do
-// not hide one another's split VALU work under their MFMAs, so that form stays unpipelined (GC_TUNE_WS_PIPE=1
-// forces it on for measurements).
+// not hide one another's split VALU work under their MFMAs, so that form stays unpipelined.
 // F32 (exact-f32 family): g.wt is the WF32 image, the LDS tile holds plain float32, a k16 step is 8
 // v_mfma_f32_32x32x2_f32 into one accumulator (no PIPE / A16 / epilogue-3 forms).
 template <int MT, int EPI, int CLS, int AMODE, int kWsPD /* W fragments (k16 steps) in flight per wave */,
@@ -2319,11 +2262,11 @@ __global__ __launch_bounds__(256, OCC) void gc_gemm_ws_kernel(GemmArgs g) {
 
 template <int CLS>
 static hipError_t launch_gemm_ws_c(hipStream_t s, const GemmArgs& g_in, int mt, int splits, int epi) {
-  if ((mt != 1 && mt != 2 && mt != 4) || epi < 0 || (epi > 1 && epi != 3)) return hipErrorInvalidValue;
+  if ((mt != 1 && mt != 2) || epi < 0 || (epi > 1 && epi != 3)) return hipErrorInvalidValue;
   if (epi == 3 && (CLS != KC_GEMM_QKV || !g_in.kv16 || g_in.kv_d % 32 || g_in.n != 3 * g_in.kv_d || splits != 1 ||
                    g_in.att_S > 0 || g_in.bias))
     return hipErrorInvalidValue;
-  const int KC = (mt == 1) ? 256 : (mt == 2 ? 128 : 64);
+  const int KC = mt == 1 ? 256 : 128;
   const int kc = g_in.k_slice < KC ? g_in.k_slice : KC;
   if (g_in.n % 128 || kc % 64 || g_in.k_slice % 128 || g_in.k_slice % kc || g_in.lda % 4 || g_in.ldw % 16 || splits < 1)
     return hipErrorInvalidValue;
@@ -2335,24 +2278,13 @@ static hipError_t launch_gemm_ws_c(hipStream_t s, const GemmArgs& g_in, int mt, 
   dim3 grid((total + 7) / 8 * 8), block(256);   // padded: the kernel maps XCD-contiguous ranges
   // ring of 4 k16 steps, registers held to 3 workgroups per CU: the best of {ring 8 / 2 per CU,
   // ring 4 / 4 (spills), ring 4 / 3, ring 8 / 3 (spills)} at the nano shapes (tools/bench_kernels ws)
-  static int pipe_env = -1;
-  if (pipe_env < 0) {
-    const char* e = getenv("GC_TUNE_WS_PIPE");
-    pipe_env = (e && *e) ? (atoi(e) != 0) : 2;   // 2: the default rule
-  }
-  const bool pipe = pipe_env == 2 ? (kTuA16 && mt == 2) : pipe_env != 0;
-#define GC_WS(MT_, EPI_, AM_)                                                                                         \
-  {                                                                                                                   \
-    if (pipe && AM_ == 0 && MT_ <= 2)                                                                                 \
-      hipLaunchKernelGGL((gc_gemm_ws_kernel<MT_, EPI_, CLS, AM_, 4, (MT_ >= 4 ? 2 : 3), kTuA16, (AM_ == 0 && MT_ <= 2)>), \
-                         grid, block, 0, s, g);                                                                       \
-    else                                                                                                              \
-      hipLaunchKernelGGL((gc_gemm_ws_kernel<MT_, EPI_, CLS, AM_, 4, (MT_ >= 4 ? 2 : 3), kTuA16, false>), grid, block, 0, s, g); \
-  }
+  // PIPE: the gc_a16 build's plain 64-row form (see the kernel)
+#define GC_WS(MT_, EPI_, AM_) \
+  hipLaunchKernelGGL((gc_gemm_ws_kernel<MT_, EPI_, CLS, AM_, 4, 3, kTuA16, (kTuA16 && AM_ == 0 && MT_ == 2)>), grid, block, 0, s, g);
   if constexpr (!kTuA16) {
     if (g.f32w) {                                // exact-f32 family: plain tiles only (32 / 64 rows), epilogues 0 and 1
 #define GC_WS32(MT_, EPI_, AM_) hipLaunchKernelGGL((gc_gemm_ws_kernel<MT_, EPI_, CLS, AM_, 4, 3, false, false, true>), grid, block, 0, s, g);
-      if (epi == 3 || mt == 4) return hipErrorInvalidValue;
+      if (epi == 3) return hipErrorInvalidValue;
       if (g.att_S > 0) {
         if (mt != 1 || epi != 1 || g.att_S > kMaxAttnSplits) return hipErrorInvalidValue;
         GC_WS32(1, 1, 1)
@@ -2369,14 +2301,12 @@ static hipError_t launch_gemm_ws_c(hipStream_t s, const GemmArgs& g_in, int mt, 
     GC_WS(1, 1, 1)
   } else if (epi == 3) {
     if constexpr (CLS == KC_GEMM_QKV) {
-      if (mt == 1) { GC_WS(1, 3, 0) } else if (mt == 2) { GC_WS(2, 3, 0) } else { GC_WS(4, 3, 0) }
+      if (mt == 1) { GC_WS(1, 3, 0) } else { GC_WS(2, 3, 0) }
     }
   } else if (mt == 1 && epi == 0) { GC_WS(1, 0, 0) }
-  else if (mt == 1 && epi == 1) { GC_WS(1, 1, 0) }
-  else if (mt == 2 && epi == 0) { GC_WS(2, 0, 0) }
-  else if (mt == 2) { GC_WS(2, 1, 0) }
-  else if (epi == 0) { GC_WS(4, 0, 0) }
-  else { GC_WS(4, 1, 0) }
+  else if (mt == 1) { GC_WS(1, 1, 0) }
+  else if (epi == 0) { GC_WS(2, 0, 0) }
+  else { GC_WS(2, 1, 0) }
 #undef GC_WS
   return hipGetLastError();
 }
@@ -2752,15 +2682,9 @@ static hipError_t launch_gemm_rowop_c(hipStream_t s, const GemmArgs& g, const Ro
   const int nthr = (D / (32 * nt)) * 64;       // 256 (d = 128) or 512 threads
   // 16-row workgroups while 32-row ones would leave more than half of the 256 CUs idle; 48-row workgroups when the
   // 32-row tiles would need a partly filled extra round of workgroups and 48-row ones do not (see the kernel)
-  static int rh_env = -1;
-  if (rh_env < 0) {
-    const char* e = getenv("GC_TUNE_OUT_RH");
-    rh_env = (e && *e) ? atoi(e) : 0;
-  }
   const int t32 = (g.rows + 31) / 32, t48 = (g.rows + 47) / 48;
   int rh = t32 <= 128 ? 16 : 32;
   if (t32 > 256 && (t32 + 255) / 256 > (t48 + 255) / 256 && nthr == 512 && g.att_S == 0) rh = 48;
-  if (rh_env == 16 || rh_env == 32 || (rh_env == 48 && nthr == 512 && g.att_S == 0)) rh = rh_env;
   const size_t lds = (size_t)(rh > 32 ? 64 : 32) * (D + 4) * sizeof(float);
   const int grid = (g.rows + rh - 1) / rh;
   if (grid <= 0) return hipSuccess;
@@ -2819,16 +2743,7 @@ __global__ __launch_bounds__(64 * NWC, NWC == 8 ? 2 : ((ND <= 2 && MT == 1) ? 3 
   float* Ut = smem;                             // [BM][LDU]  S16: takes over a's space after phase 1
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, hh = lane >> 5;
   const int S = g.f / FS;
-  int z = blockIdx.x % S, mtile = blockIdx.x / S;
-  if (g.xcd_tiles) {
-    // (experiment, GC_TUNE_FFW_XCD=1) the S hidden slices of a row tile on ONE XCD: blocks with
-    // equal blockIdx.x % 8 share an XCD, so XCD x takes row tiles x, x + 8, ...; its L2 then holds all S slabs of its
-    // rows (the row pass is mapped the same way) and streams every weight slice instead of keeping one
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    mtile = (j / S) * 8 + xcd;
-    z = j - (j / S) * S;
-    if (mtile * BM >= g.rows) return;
-  }
+  const int z = blockIdx.x % S, mtile = blockIdx.x / S;
 #ifdef GC_STAMPS
   unsigned long long stamp_v[8];
   int stamp_n = 0;
@@ -3022,8 +2937,7 @@ __global__ __launch_bounds__(64 * NWC, NWC == 8 ? 2 : ((ND <= 2 && MT == 1) ? 3 
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = hilo(acc2[mt][nt][4 * j + e], accx2[mt][nt][4 * j + e]);
-        if (g.wt) st4_wt(orow + cbase + 8 * j, v);
-        else st4(orow + cbase + 8 * j, v);
+        st4(orow + cbase + 8 * j, v);
       }
     }
   }
@@ -3040,8 +2954,7 @@ __global__ __launch_bounds__(64 * NWC, NWC == 8 ? 2 : ((ND <= 2 && MT == 1) ? 3 
 template <int ND, int MT, int NWC = 4>
 static hipError_t launch_ffw_fused_t(hipStream_t s, const FfwArgs& g) {
   const size_t lds = (size_t)(32 * MT * ((ND > 2 ? 128 * ND : 256) + 4)) * sizeof(float);
-  const int n_mt = (g.rows + 32 * MT - 1) / (32 * MT);
-  const int grid = g.xcd_tiles ? 8 * ((n_mt + 7) / 8) * (g.f / 256) : n_mt * (g.f / 256);
+  const int grid = ((g.rows + 32 * MT - 1) / (32 * MT)) * (g.f / 256);
   if (grid <= 0) return hipSuccess;
   if constexpr (!kTuA16) {
     if (g.f32w) {                                // exact-f32 family: WF32 images
@@ -3057,30 +2970,20 @@ static hipError_t launch_ffw_fused_t(hipStream_t s, const FfwArgs& g) {
   return hipGetLastError();
 }
 
+// d_model 128 / 256 only: at 512 the kernel's accumulators leave one workgroup per CU and the two-launch form is
+// faster (2.98 vs 3.32 ms per call on the 1-degree config)
 hipError_t launch_ffw_fused(hipStream_t s, const FfwArgs& g) {
-  if (g.d % 128 || g.d > 512 || g.f % 256 || g.f < 256) return hipErrorInvalidValue;
+  if ((g.d != 128 && g.d != 256) || g.f % 256 || g.f < 256) return hipErrorInvalidValue;
   // 64-row tiles halve the weight traffic (the kernel streams both slices per tile and is bound by
   // the L2 -> CU rate); used once they still give more than one workgroup per CU
-  static int mt2 = -1;
-  if (mt2 < 0) {
-    const char* e = getenv("GC_TUNE_FFW_MT");
-    mt2 = e ? atoi(e) : 0;
-  }
-  const bool big = mt2 == 2 || (mt2 == 0 && ((g.rows + 63) / 64) * (g.f / 256) >= 300);
-  switch (g.d / 128) {
-    case 1: return big ? launch_ffw_fused_t<1, 2>(s, g) : launch_ffw_fused_t<1, 1>(s, g);
-    case 2: {
-      // 96-row tiles on 8 waves when that gives one balanced wave of workgroups (between half a chip and
-      // a chip: 27 x 8 = 216 at the nano size).  With 64-row tiles 328 workgroups land two on some CUs and
-      // one on the others, and the kernel lasts as long as the doubly loaded CUs (32.2 vs 29.2 us).
-      const int b96 = ((g.rows + 95) / 96) * (g.f / 256);
-      if (mt2 == 38 || (mt2 == 0 && b96 > 128 && b96 <= 256)) return launch_ffw_fused_t<2, 3, 8>(s, g);
-      if (mt2 == 28) return launch_ffw_fused_t<2, 2, 8>(s, g);
-      return big ? launch_ffw_fused_t<2, 2>(s, g) : launch_ffw_fused_t<2, 1>(s, g);
-    }
-    case 4: return launch_ffw_fused_t<4, 1>(s, g);
-    default: return hipErrorInvalidValue;
-  }
+  const bool big = ((g.rows + 63) / 64) * (g.f / 256) >= 300;
+  if (g.d == 128) return big ? launch_ffw_fused_t<1, 2>(s, g) : launch_ffw_fused_t<1, 1>(s, g);
+  // 96-row tiles on 8 waves when that gives one balanced wave of workgroups (between half a chip and
+  // a chip: 27 x 8 = 216 at the nano size).  With 64-row tiles 328 workgroups land two on some CUs and
+  // one on the others, and the kernel lasts as long as the doubly loaded CUs (32.2 vs 29.2 us).
+  const int b96 = ((g.rows + 95) / 96) * (g.f / 256);
+  if (b96 > 128 && b96 <= 256) return launch_ffw_fused_t<2, 3, 8>(s, g);
+  return big ? launch_ffw_fused_t<2, 2>(s, g) : launch_ffw_fused_t<2, 1>(s, g);
 }
 
 hipError_t launch_gemm_ws(hipStream_t s, int cls, const GemmArgs& g, int mt, int splits, int epi) {
@@ -3094,13 +2997,13 @@ hipError_t launch_gemm_ws(hipStream_t s, int cls, const GemmArgs& g, int mt, int
   }
 }
 
-hipError_t launch_gemm(hipStream_t s, int cls, const GemmArgs& g, int shape, int splits, int epi, bool f16) {
+hipError_t launch_gemm(hipStream_t s, int cls, const GemmArgs& g, int splits, int epi, bool f16) {
   switch (cls) {
-    case KC_GEMM_QKV: return launch_gemm_c<KC_GEMM_QKV>(s, g, shape, splits, epi, f16);
-    case KC_GEMM_OUT: return launch_gemm_c<KC_GEMM_OUT>(s, g, shape, splits, epi, f16);
-    case KC_GEMM_FFW1: return launch_gemm_c<KC_GEMM_FFW1>(s, g, shape, splits, epi, f16);
-    case KC_GEMM_FFW2: return launch_gemm_c<KC_GEMM_FFW2>(s, g, shape, splits, epi, f16);
-    case KC_GEMM_NODE: return launch_gemm_c<KC_GEMM_NODE>(s, g, shape, splits, epi, f16);
+    case KC_GEMM_QKV: return launch_gemm_c<KC_GEMM_QKV>(s, g, splits, epi, f16);
+    case KC_GEMM_OUT: return launch_gemm_c<KC_GEMM_OUT>(s, g, splits, epi, f16);
+    case KC_GEMM_FFW1: return launch_gemm_c<KC_GEMM_FFW1>(s, g, splits, epi, f16);
+    case KC_GEMM_FFW2: return launch_gemm_c<KC_GEMM_FFW2>(s, g, splits, epi, f16);
+    case KC_GEMM_NODE: return launch_gemm_c<KC_GEMM_NODE>(s, g, splits, epi, f16);
     default: return hipErrorInvalidValue;
   }
 }
@@ -3119,12 +3022,8 @@ __global__ __launch_bounds__(256) void gc_rowop_kernel(float* __restrict__ x,
                                                         const float* __restrict__ partials, int n_slabs,
                                                         int rows, int d, int B,
                                                         const float* __restrict__ cond, int cond_stride,
-                                                        float* __restrict__ h, int h_s16, int round16, int xcd_tile_rows) {
-  int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (xcd_tile_rows) {                          // (GC_TUNE_FFW_XCD=1) rows of fused-FFW row tile t on the XCD that wrote its slabs: t % 8
-    const int bpt = xcd_tile_rows >> 2, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    row = ((j / bpt) * 8 + xcd) * xcd_tile_rows + (j % bpt) * 4 + (threadIdx.x >> 6);
-  }
+                                                        float* __restrict__ h, int h_s16, int round16) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
   const size_t slab = (size_t)rows * d;
@@ -3208,15 +3107,14 @@ __global__ __launch_bounds__(256) void gc_rowop_kernel(float* __restrict__ x,
 
 hipError_t launch_rowop(hipStream_t s, float* x, const float* bias, const float* partials, int n_slabs,
                         int rows, int d, int B, const float* cond, int cond_stride, float* h, int h_s16,
-                        bool round16, bool h16, int xcd_tile_rows) {
+                        bool round16, bool h16) {
   if (d > 512 || d % 4 || h_s16 < 0 || h_s16 > 1 || (h_s16 && d % 32) || (h16 && h_s16 == 1)) return hipErrorInvalidValue;
-  if (xcd_tile_rows % 4) return hipErrorInvalidValue;
-  const int n_blocks = xcd_tile_rows ? 8 * (((rows + xcd_tile_rows - 1) / xcd_tile_rows + 7) / 8) * (xcd_tile_rows / 4) : (rows + 3) / 4;
+  const int n_blocks = (rows + 3) / 4;
 #define GC_ROWOP_NS(NS_)                                                                                   \
   if (h16) hipLaunchKernelGGL((gc_rowop_kernel<NS_, true>), dim3(n_blocks), dim3(256), 0, s, x, bias, partials, n_slabs, \
-                     rows, d, B, cond, cond_stride, h, h_s16, 1, xcd_tile_rows);                           \
+                     rows, d, B, cond, cond_stride, h, h_s16, 1);                           \
   else hipLaunchKernelGGL((gc_rowop_kernel<NS_, false>), dim3(n_blocks), dim3(256), 0, s, x, bias, partials, n_slabs, \
-                     rows, d, B, cond, cond_stride, h, h_s16, round16 ? 1 : 0, xcd_tile_rows)
+                     rows, d, B, cond, cond_stride, h, h_s16, round16 ? 1 : 0)
   switch (n_slabs) {                             // the counts the forward pass uses; anything else: generic
     case 1: GC_ROWOP_NS(1); break;
     case 2: GC_ROWOP_NS(2); break;
@@ -3518,9 +3416,6 @@ __global__ __launch_bounds__(DH >= 128 ? 256 : 512) void gc_attention_v2_kernel(
   const int base_cnt = n_pairs >> 3, extra = n_pairs & 7;
   if (jj >= base_cnt + (xcd < extra ? 1 : 0)) return;
   const int lin = xcd * base_cnt + (xcd < extra ? xcd : extra) + jj;
-#if defined(GC_EXP_ATT_256)      // timing-only ablation: one round of workgroups (the first 32 pairs of every XCD)
-  if (jj >= 32) return;
-#endif
   int t, sp, it_lo = 0, it_hi = 0, it_slot = -1;
   if constexpr (ITEMS) {
     t = items[4 * lin];
@@ -3637,15 +3532,6 @@ __global__ __launch_bounds__(DH >= 128 ? 256 : 512) void gc_attention_v2_kernel(
 
   // V piece i of this lane: key vkey[i] of the chunk, 16-byte chunk vc8[i] of its row
   auto v_issue = [&](int c, f32x4 (&vr)[NP][NPV]) __attribute__((always_inline)) {
-#if defined(GC_EXP_ATT_NOV)      // timing-only ablation: no V gathers at all
-#pragma unroll
-    for (int i = 0; i < NPV; ++i)
-#pragma unroll
-      for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) vr[pl][i][j] = __int_as_float(0x3c003c00 + c + i + j);
-    return;
-#endif
 #pragma unroll
     for (int i = 0; i < NPV; ++i) {
       const int p = lane + 64 * i, key = p / CPR, c8 = p - key * CPR;
@@ -3664,25 +3550,6 @@ __global__ __launch_bounds__(DH >= 128 ? 256 : 512) void gc_attention_v2_kernel(
     }
   };
   auto k_issue = [&](int c, f32x4 (&kh)[KS], f32x4 (&kl)[KS]) __attribute__((always_inline)) {
-    // GC_EXP_ATT_*: TIMING-ONLY ablations (wrong values) for tools/build_variant.sh + tools/exp_att_gather.sh; never defined
-    // in the product build (profiles/r04_attention_gather_ablation.txt)
-#if defined(GC_EXP_ATT_NOK)      // no K gathers at all: the operand registers are filled with constants
-#pragma unroll
-    for (int s8 = 0; s8 < KS; ++s8)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { kh[s8][j] = __int_as_float(0x3c003c00 + c + s8 + j); kl[s8][j] = __int_as_float(0x1c001c00 + c + s8 + j); }
-    return;
-#elif defined(GC_EXP_ATT_KCOAL)  // the same K bytes fetched quad-coalesced (4 lanes = 64 contiguous bytes)
-    const _Float16* kb = kv16 + (size_t)b * 4 * D + head * DH;
-#pragma unroll
-    for (int s8 = 0; s8 < KS; ++s8) {
-      const int key = (16 * (s8 & 1) + (lane >> 2)) & 31, piece = (4 * (s8 >> 1) + (lane & 3)) % (DH / 8);
-      const _Float16* kq = kb + (size_t)(unsigned)s_idx[(c - lo) * 32 + key] * rstride + 8 * piece;
-      kh[s8] = ld4(reinterpret_cast<const float*>(kq));
-      if constexpr (!FEAT16) kl[s8] = ld4(reinterpret_cast<const float*>(kq + D));
-    }
-    return;
-#endif
     const _Float16* kp = kplane + (size_t)(unsigned)s_idx[(c - lo) * 32 + r] * rstride;
 #pragma unroll
     for (int s8 = 0; s8 < KS; ++s8) {
@@ -3906,48 +3773,10 @@ hipError_t launch_attention_v2(hipStream_t s, const float* qkv, const void* kv16
   return hipGetLastError();
 }
 
-// Merges the S partial (m, l, O) triples of every (node, head):
-//   O = sum_s e^{m_s - m*} O_s / sum_s e^{m_s - m*} l_s,  m* = max_s m_s.
-__global__ __launch_bounds__(256) void gc_attn_combine_kernel(const float* __restrict__ part_o,
-                                                               const float* __restrict__ part_ml,
-                                                               int M, int B, int D, int H, int S,
-                                                               float* __restrict__ o, int out_s16, int round16) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);   // node * B + b
-  const int lane = threadIdx.x & 63;
-  if (row >= M * B) return;
-  const int node = row / B, b = row - node * B;
-  const int t = node / kTileM, q = node - t * kTileM;
-  const int DH = D / H;
-  for (int c = 4 * lane; c < D; c += 256) {
-    const int head = c / DH, dv = c - head * DH;
-    float mstar = -1e30f;
-    for (int s = 0; s < S; ++s) {
-      const size_t slot = (((size_t)t * S + s) * B + b) * H + head;
-      mstar = fmaxf(mstar, part_ml[slot * (kTileM * 2) + q * 2]);
-    }
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    float lsum = 0.f;
-    for (int s = 0; s < S; ++s) {
-      const size_t slot = (((size_t)t * S + s) * B + b) * H + head;
-      const float m = part_ml[slot * (kTileM * 2) + q * 2];
-      const float l = part_ml[slot * (kTileM * 2) + q * 2 + 1];
-      const float w = (l != 0.f) ? expf(m - mstar) : 0.f;
-      const float4 v = *reinterpret_cast<const float4*>(part_o + slot * (kTileM * DH) + q * DH + dv);
-      acc.x += w * v.x; acc.y += w * v.y; acc.z += w * v.z; acc.w += w * v.w;
-      lsum += w * l;
-    }
-    const float il = (lsum != 0.f) ? 1.0f / lsum : 0.f;
-    float4 ov = make_float4(acc.x * il, acc.y * il, acc.z * il, acc.w * il);
-    if (round16) { ov.x = r16(ov.x); ov.y = r16(ov.y); ov.z = r16(ov.z); ov.w = r16(ov.w); }
-    if (out_s16) store4_s16(o, (size_t)row, D, c, ov.x, ov.y, ov.z, ov.w);
-    else *reinterpret_cast<float4*>(o + (size_t)row * D + c) = ov;
-  }
-}
-
 hipError_t launch_attention(hipStream_t s, const float* qkv, float* o, float* part_o, float* part_ml,
                             int M, int B, int D, int H, int S, bool out_s16, const int* tile_chunk_start,
-                            const int* union_idx, const unsigned* mask_bits, int n_tiles, bool f16, int max_chunks,
-                            bool feat16, const int* items, int n_items) {
+                            const int* union_idx, const unsigned* mask_bits, int n_tiles, bool feat16,
+                            const int* items, int n_items) {
   const int os = out_s16 ? 1 : 0;
   if (H < 1 || D % H || S < 1) return hipErrorInvalidValue;
   const int dh = D / H;
@@ -3955,9 +3784,7 @@ hipError_t launch_attention(hipStream_t s, const float* qkv, float* o, float* pa
   if (items && (S != 1 || n_items < 8 || n_items % 8 || out_s16)) return hipErrorInvalidValue;
   if (!items) n_items = 0;
   dim3 grid(items ? n_items : n_tiles, S, B), block(64 * H);
-  // (round 1's f16x3 form of this kernel, gc_attention16, re-split K and V per tile; it served only A/B switches since
-  //  gc_attention_v2 and left the build in round 5: `f16` is accepted and ignored, this is the exact-f32 attention)
-  (void)f16; (void)max_chunks;
+  // (the exact-f32 attention; f16x3 runs gc_attention_v2)
   if (dh == 32)
     hipLaunchKernelGGL((gc_attention_kernel<32>), grid, block, 0, s, qkv, o, part_o, part_ml, M, B, D, S, os,
                        tile_chunk_start, union_idx, mask_bits, feat16 ? 1 : 0, items, n_items);
@@ -3969,13 +3796,6 @@ hipError_t launch_attention(hipStream_t s, const float* qkv, float* o, float* pa
                        tile_chunk_start, union_idx, mask_bits, feat16 ? 1 : 0, items, n_items);
   else
     return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
-hipError_t launch_attn_combine(hipStream_t s, const float* part_o, const float* part_ml, int M, int B,
-                               int D, int H, int S, float* o, bool out_s16, bool round16) {
-  hipLaunchKernelGGL(gc_attn_combine_kernel, dim3((M * B + 3) / 4), dim3(256), 0, s, part_o, part_ml, M,
-                     B, D, H, S, o, out_s16 ? 1 : 0, round16 ? 1 : 0);
   return hipGetLastError();
 }
 

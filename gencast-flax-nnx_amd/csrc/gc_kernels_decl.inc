@@ -15,7 +15,7 @@ enum KernelClass : int {
   KC_ROWOP,         // residual add (+ split-K slab sum) + LayerNorm + cond of the mesh rows
   KC_GEMM_QKV,      // QKV projection
   KC_ATTN,          // k-hop sparse attention
-  KC_ATTN_COMBINE,  // merge of the attention key-splits
+  KC_ATTN_COMBINE,  // (no kernel is filed under it: the out-projection's loader merges the key splits; kept for the ABI)
   KC_GEMM_OUT,      // attention out-projection (slab)
   KC_GEMM_FFW1,     // FFW layer 1 + gelu
   KC_GEMM_FFW2,     // FFW layer 2 (split-K slabs)
@@ -74,7 +74,6 @@ struct MlpArgs {
   // "fp16 node features" mode (gc_set_option features=f16; rounding points: DESIGN.md section 3b):
   int round16;         // 1: staged inputs, the hidden activation and the second Linear's output are rounded to fp16
   int round_out;       // 1: the LayerNorm + conditioning output and the residual sum are rounded to fp16
-  int wt;              // 1: the output rows leave as write-through (sc1) stores (A/B switch GC_TUNE_WT_STORES & 2)
   int a16;             // 1 (only with round16): staged inputs and hidden tile are exact fp16 -- the CALLER then launches
                        // the gc_a16 build of the kernel (2 MFMAs per product: the lo planes are zero); identical bits
   // gc_a16 build only (physical fp16 activation storage): segment sources, `residual` and `out` are _Float16
@@ -87,7 +86,8 @@ struct MlpArgs {
   // rounded to fp16 first when round_out) -- the mesh2grid edge update with jraph.segment_sum folded in (no residual)
   int tri;
 };
-// true when launch_mlp would run `a` on the weight-streaming kernel (the only one with the triple epilogue, MlpArgs::tri)
+// true when launch_mlp runs `a` on the weight-streaming kernel (the only one with the triple epilogue, MlpArgs::tri);
+// launch_mlp and mlp_pair_supported decide by it
 bool mlp_runs_weight_streaming(const MlpArgs& a);
 
 hipError_t launch_cond(hipStream_t s, const float* sigma_dev, float sigma_scalar, int B,
@@ -106,7 +106,8 @@ hipError_t launch_cond_multi(hipStream_t s, const SigmaList& sl, int ncalls, int
 
 hipError_t launch_mlp(hipStream_t s, const MlpArgs& a);
 // Two independent MLPs in ONE launch (workgroups [0, tiles(a)) run a, the rest b), when both take the same kernel form
-// (mlp_pair_supported: hidden 256 below 24 000 rows, one precision family, no triple epilogue)
+// (mlp_pair_supported: 8-wave weight-streaming form -- hidden 256 below 24 000 rows, or hidden 512 --, one precision
+// family, no triple epilogue)
 bool mlp_pair_supported(const MlpArgs& a, const MlpArgs& b);
 hipError_t launch_mlp_pair(hipStream_t s, const MlpArgs& a, const MlpArgs& b);
 
@@ -120,7 +121,7 @@ struct GemmArgs {
   int lda;
   int a_f32;           // f16 mode only: 1 = A holds plain float32 and is split to S16 while staging
   // att_S > 0: A is the attention output merged on the fly from att_S key-split partials
-  // (launch_attention's part_o / part_ml); `a` is then unused.  Only with shape 1, epi 1.
+  // (launch_attention's part_o / part_ml); `a` is then unused.  Only with 32-row tiles, epi 1.
   const float* att_po;
   const float* att_pml;
   int att_S, att_B, att_H, att_DH;
@@ -147,14 +148,14 @@ struct GemmArgs {
   int out_f32;         // gc_a16 build, epi 0: `out` is float32 (the per-node pre-activation terms of a split edge MLP)
   int f32w;            // weight-streaming forms: 1 = exact-f32 family -- wt is a WF32 image, products on v_mfma_f32_32x32x2_f32
 };
-// shape: 1 -> 32x128 tiles, 2 -> 64x128 tiles (256 threads);
+// LDS-staged form: 32x128 tiles (256 threads);
 // epi 0: bias/act f32 store, 1: raw split-K slabs (f32),
 // 2: bias/act store in S16 split-fp16 layout (f16 only).  f16: A and W^T are S16-encoded and the
 // product runs as 3 fp16 MFMAs per k-step (f32-equivalent accuracy, see gc_kernels.hip).
-hipError_t launch_gemm(hipStream_t s, int cls, const GemmArgs& g, int shape, int splits, int epi, bool f16);
+hipError_t launch_gemm(hipStream_t s, int cls, const GemmArgs& g, int splits, int epi, bool f16);
 // Weight-streaming f16x3 form: g.wt is the WF16 fragment-order image of W^T (gc_api.hip
 // encode_wf16), g.ldw the full contraction length K; a is plain float32 (or attention partials).
-// Tile (32*mt) x 128; needs n % 128 == 0 and k_slice a multiple of 128.  epi 0 | 1 as launch_gemm;
+// Tile (32*mt) x 128, mt 1 or 2; needs n % 128 == 0 and k_slice a multiple of 128.  epi 0 | 1 as launch_gemm;
 // epi 3 = QKV projection with pre-split K / V planes (g.kv16, g.kv_d).
 hipError_t launch_gemm_ws(hipStream_t s, int cls, const GemmArgs& g, int mt, int splits, int epi);
 #ifdef GC_STAMPS
@@ -165,18 +166,16 @@ hipError_t set_gemm_ws_stamp_buffer(unsigned long long* p);     // diagnostic bu
 // for hidden slices Fz of 256 columns; the hidden activations never leave LDS.  f16x3, WF16 weights.
 struct FfwArgs {
   const float* a;      // [rows][d] float32 (the normed + conditioned residual stream)
-  int rows, d, f;      // d % 128 == 0 (<= 512), f % 256 == 0
+  int rows, d, f;      // d = 128 or 256, f % 256 == 0
   const float* w1f;    // WF16 image of W1^T [f][d]
   const float* b1;     // [f]
   const float* w2f;    // WF16 image of W2^T [d][f]
   float* out;          // [f/256][rows][d] partial sums, one slab per hidden slice
   int round16;         // fp16-feature mode: the hidden activation is rounded to fp16
-  int wt;              // 1: the slabs leave as write-through (sc1) stores (A/B switch GC_TUNE_WT_STORES & 1)
   int a16;             // 1 (only with round16): a and the hidden tile are exact fp16 -- the caller launches the gc_a16 build
   // diagnostic builds only (-DGC_STAMPS, tools/stamp_ffw.cpp): 8 s_memtime stamps per wave, or nullptr
   unsigned long long* stamps;
   int f32w;            // 1: exact-f32 family -- w1f / w2f are WF32 images (gc_api.hip encode_wf32), products on v_mfma_f32_32x32x2_f32
-  int xcd_tiles;       // 1 (GC_TUNE_FFW_XCD=1): the hidden slices of a row tile run on one XCD (see the kernel)
 };
 hipError_t launch_ffw_fused(hipStream_t s, const FfwArgs& g);
 
@@ -201,14 +200,14 @@ hipError_t set_gemm_rowop_stamp_buffer(unsigned long long* p);   // diagnostic b
 hipError_t launch_rowop(hipStream_t s, float* x, const float* bias, const float* partials, int n_slabs,
                         int rows, int d, int B, const float* cond, int cond_stride, float* h,
                         int h_s16 /* 0: [rows][d]; 1: S16 */,
-                        bool round16 = false, bool h16 = false /* x and h are _Float16 arrays (implies rounding) */,
-                        int xcd_tile_rows = 0 /* != 0: rows of row tile t (that many rows) run on the XCD of blocks t % 8 */);
+                        bool round16 = false, bool h16 = false /* x and h are _Float16 arrays (implies rounding) */);
 
-// S == 1: writes o directly; S > 1: writes partial (m, l, O) per key split for launch_attn_combine
+// Exact-f32 attention.  S == 1: writes o directly; S > 1: writes partial (m, l, O) per key split, merged by the
+// out-projection's A loader (GemmArgs::att_S)
 hipError_t launch_attention(hipStream_t s, const float* qkv, float* o, float* part_o, float* part_ml,
                             int M, int B, int D, int H, int S, bool out_s16,
                             const int* tile_chunk_start, const int* union_idx, const unsigned* mask_bits,
-                            int n_tiles, bool f16 = false, int max_chunks_per_tile = 0, bool feat16 = false,
+                            int n_tiles, bool feat16 = false,
                             const int* items = nullptr /* work-item list, as launch_attention_v2 (S == 1) */, int n_items = 0);
 // Attention on pre-split K / V planes (kv16 as written by launch_gemm_ws epi 3); q from qkv (f32).
 // Always writes per-split partials when S > 1, o when S == 1 (as launch_attention).
@@ -223,8 +222,6 @@ hipError_t launch_attention_v2(hipStream_t s, const float* qkv, const void* kv16
 #ifdef GC_STAMPS
 hipError_t set_attention_stamp_buffer(unsigned long long* p);   // diagnostic builds: 12 words per wave
 #endif
-hipError_t launch_attn_combine(hipStream_t s, const float* part_o, const float* part_ml, int M, int B,
-                               int D, int H, int S, float* o, bool out_s16, bool round16 = false);
 
 // grid input packing: xp[rows][kp] = [struct(3) | feats(c_in) | 0...]
 hipError_t launch_pack_full(hipStream_t s, const float* grid_struct, const float* feats, int G, int B,

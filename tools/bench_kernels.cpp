@@ -64,14 +64,14 @@ int main(int argc, char** argv) {
   if (f16) { h = dev_rand_s16((size_t)M * D); u = dev_rand_s16((size_t)M * F); wqkv = dev_rand_s16((size_t)3 * D * D);
              w1 = dev_rand_s16((size_t)F * D); w2 = dev_rand_s16((size_t)D * F); }
   auto gemm = [&](const char* name, int cls, const float* a, int lda, const float* wt, int ldw, int n, int k,
-                  int splits, const float* bias, int act, float* o, int ldo, int mt, int epi) {
+                  int splits, const float* bias, int act, float* o, int ldo, int epi) {
     g_af32 = getenv("BK_AF32") ? 1 : 0;
     gc::GemmArgs g{};
     g.a = a; g.lda = lda; g.a_f32 = g_af32; g.wt = wt; g.ldw = ldw; g.rows = M; g.n = n; g.k_slice = k / splits;
     g.bias = bias; g.act = act; g.out = o; g.ldo = ldo;
-    float us = time_it(s, iters, [&] { return gc::launch_gemm(s, cls, g, mt, splits, epi, f16); });
+    float us = time_it(s, iters, [&] { return gc::launch_gemm(s, cls, g, splits, epi, f16); });
     double fl = 2.0 * M * n * k;
-    printf("%-34s mt=%d splits=%d  %8.2f us  %6.1f TF/s\n", name, mt, splits, us, fl / us * 1e-6);
+    printf("%-34s splits=%d  %8.2f us  %6.1f TF/s\n", name, splits, us, fl / us * 1e-6);
   };
   if (argc <= 1) {  // attention with synthetic tiles: 81 tiles x 13 chunks, ~50 % mask density, clustered keys
     const int T = (M + 31) / 32, CH = 13, H = 4;
@@ -94,9 +94,8 @@ int main(int argc, char** argv) {
     float* pml = dev_rand((size_t)T * 8 * H * 32 * 2);
     for (int S : {1, 2, 3, 4, 6, 8}) {
       float us = time_it(s, iters, [&] { return gc::launch_attention(s, qkv, att, po, pml, M, 1, D, H, S, false, d_ts, d_un, d_mk, T); });
-      float us2 = S > 1 ? time_it(s, iters, [&] { return gc::launch_attn_combine(s, po, pml, M, 1, D, H, S, att, false); }) : 0.f;
       double fl = 4.0 * T * CH * 32 * 32 * D;   // dense tile flops actually executed
-      printf("attention S=%d  %8.2f us (+combine %5.2f us)  %6.1f TF/s executed\n", S, us, us2, fl / us * 1e-6);
+      printf("attention S=%d  %8.2f us  %6.1f TF/s executed\n", S, us, fl / us * 1e-6);
     }
   }
   const char* only = argc > 1 ? argv[1] : nullptr;
@@ -122,32 +121,29 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  if (only) {   // single-config mode for rocprofv3 counter runs: bench_kernels ffw1 <mt> [iters]
-    const int mt = argc > 2 ? atoi(argv[2]) : 1;
+  if (only) {   // single-config mode for rocprofv3 counter runs: bench_kernels ffw1|ffw2|floor <unused> [iters]
     if (std::string(only) == "floor") {
       for (int kk : {32, 64, 128, 256}) {
         char nm[64]; snprintf(nm, 64, "ffw1-shape K=%d (no gelu)", kk);
-        gemm(nm, gc::KC_GEMM_FFW1, h, D, w1, D, F, kk, 1, b1, 0, out, F, mt, 0);
+        gemm(nm, gc::KC_GEMM_FFW1, h, D, w1, D, F, kk, 1, b1, 0, out, F, 0);
         snprintf(nm, 64, "ffw1-shape K=%d slabs", kk);
-        gemm(nm, gc::KC_GEMM_FFW1, h, D, w1, D, F, kk, 1, nullptr, 0, out, F, mt, 1);
+        gemm(nm, gc::KC_GEMM_FFW1, h, D, w1, D, F, kk, 1, nullptr, 0, out, F, 1);
         snprintf(nm, 64, "qkv-shape K=%d", kk);
-        gemm(nm, gc::KC_GEMM_QKV, h, D, wqkv, D, 3 * D, kk, 1, nullptr, 0, out, 3 * D, mt, 0);
+        gemm(nm, gc::KC_GEMM_QKV, h, D, wqkv, D, 3 * D, kk, 1, nullptr, 0, out, 3 * D, 0);
         snprintf(nm, 64, "out-shape K=%d", kk);
-        gemm(nm, gc::KC_GEMM_OUT, h, D, wqkv, D, D, kk, 1, nullptr, 0, out, D, mt, 1);
+        gemm(nm, gc::KC_GEMM_OUT, h, D, wqkv, D, D, kk, 1, nullptr, 0, out, D, 1);
       }
     }
-    if (std::string(only) == "ffw1") gemm("ffw1 (no gelu)", gc::KC_GEMM_FFW1, h, D, w1, D, F, D, 1, b1, 0, out, F, mt, 0);
-    if (std::string(only) == "ffw2") gemm("ffw2 splits 4", gc::KC_GEMM_FFW2, u, F, w2, F, D, F, 4, nullptr, 0, part, D, mt, 1);
+    if (std::string(only) == "ffw1") gemm("ffw1 (no gelu)", gc::KC_GEMM_FFW1, h, D, w1, D, F, D, 1, b1, 0, out, F, 0);
+    if (std::string(only) == "ffw2") gemm("ffw2 splits 4", gc::KC_GEMM_FFW2, u, F, w2, F, D, F, 4, nullptr, 0, part, D, 1);
     return 0;
   }
-  for (int mt = 1; mt <= 2; ++mt) {
-    gemm("qkv   [2562x256]x[256x768]", gc::KC_GEMM_QKV, h, D, wqkv, D, 3 * D, D, 1, nullptr, 0, out, 3 * D, mt, 0);
-    gemm("ffw1  [2562x256]x[256x2048] +gelu", gc::KC_GEMM_FFW1, h, D, w1, D, F, D, 1, b1, 1, out, F, mt, 0);
-    gemm("ffw1  (no gelu)", gc::KC_GEMM_FFW1, h, D, w1, D, F, D, 1, b1, 0, out, F, mt, 0);
-    for (int sp : {1, 2, 4, 8})
-      gemm("ffw2  [2562x2048]x[2048x256]", gc::KC_GEMM_FFW2, u, F, w2, F, D, F, sp, nullptr, 0, part, D, mt, 1);
-    for (int sp : {1, 2})
-      gemm("out   [2562x256]x[256x256]", gc::KC_GEMM_OUT, h, D, wqkv, D, D, D, sp, nullptr, 0, part, D, mt, 1);
-  }
+  gemm("qkv   [2562x256]x[256x768]", gc::KC_GEMM_QKV, h, D, wqkv, D, 3 * D, D, 1, nullptr, 0, out, 3 * D, 0);
+  gemm("ffw1  [2562x256]x[256x2048] +gelu", gc::KC_GEMM_FFW1, h, D, w1, D, F, D, 1, b1, 1, out, F, 0);
+  gemm("ffw1  (no gelu)", gc::KC_GEMM_FFW1, h, D, w1, D, F, D, 1, b1, 0, out, F, 0);
+  for (int sp : {1, 2, 4, 8})
+    gemm("ffw2  [2562x2048]x[2048x256]", gc::KC_GEMM_FFW2, u, F, w2, F, D, F, sp, nullptr, 0, part, D, 1);
+  for (int sp : {1, 2})
+    gemm("out   [2562x256]x[256x256]", gc::KC_GEMM_OUT, h, D, wqkv, D, D, D, sp, nullptr, 0, part, D, 1);
   return 0;
 }

@@ -4,7 +4,6 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # repo root (this file lives in tools/)
 from tests import helpers
 os.environ["GC_TUNE_M2G_FUSE_SUM"] = "0"
-os.environ["GC_TUNE_SPLIT_EDGE"] = "0"
 for prec in ("f16x3", "f32"):
   gr, dims, params, x, sigma = helpers.tiny_setup(batch=1, seed=13, latent=512, heads=4, ffw=256, layers=1, mesh_size=3, k_hop=2, n_lat=19, n_lon=36)
   E = len(gr.m2g_senders) - 1                     # drop one edge: not "3 per grid node", so the library keeps the caller's order
