@@ -95,6 +95,11 @@ SIGNATURES = {
     "gc_noise_draw": (ctypes.c_int, [_hp]),
     "gc_download_noise": (ctypes.c_int, [_hp, _f32p]),
     "gc_set_churn": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, ctypes.c_float]),
+    "gc_loss_set_weights": (ctypes.c_int, [_hp, _f32p, _f32p, _i32p, ctypes.c_int32, _f32p]),
+    "gc_upload_targets": (ctypes.c_int, [_hp, _f32p]),
+    "gc_loss_resident": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p]),
+    "gc_download_denoised": (ctypes.c_int, [_hp, _f32p]),
+    "gc_loss": (ctypes.c_int, [_hp, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -182,6 +187,7 @@ class NativeDenoiser:
         raise
     self.num_grid_nodes = None
     self.num_mesh_nodes = None
+    self._loss_groups = 0                      # groups of the loss weights this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
   def _check(self, rc):
@@ -419,6 +425,71 @@ class NativeDenoiser:
     r = _f32(rates).reshape(-1)
     self._check(self._lib.gc_set_churn(self._h, _ptr(r, _f32p), len(r), float(noise_level_inflation_factor)))
 
+  # -- denoising loss (forward only) ----------------------------------------------------------------
+  def loss_set_weights(self, node_weight, channel_weight, channel_group, group_weight) -> None:
+    """Flat loss weights (gc_loss_set_weights; `losses.loss_plan` builds them): node_weight [G], channel_weight and
+    channel_group [c_out], group_weight [n_groups]."""
+    nw, cw, gw = _f32(node_weight), _f32(channel_weight), _f32(group_weight)
+    cg = _i32(channel_group)
+    if nw.shape != (self.num_grid_nodes,):
+      raise ValueError(f"node_weight must have shape ({self.num_grid_nodes},)")
+    if cw.shape != (self.cfg.c_out,) or cg.shape != (self.cfg.c_out,):
+      raise ValueError(f"channel_weight / channel_group must have shape ({self.cfg.c_out},)")
+    if gw.ndim != 1:
+      raise ValueError("group_weight must be one-dimensional")
+    self._check(self._lib.gc_loss_set_weights(self._h, _ptr(nw, _f32p), _ptr(cw, _f32p), _ptr(cg, _i32p), len(gw),
+                                              _ptr(gw, _f32p)))
+    self._loss_groups = len(gw)
+
+  def _need_loss_groups(self) -> int:
+    """The result buffers are sized by the group count: the weights must have gone through `loss_set_weights`."""
+    if not self._loss_groups:
+      raise GencastHipError("libgencast_hip error 4: no loss weights (loss_set_weights has not been called on this object)")
+    return self._loss_groups
+
+  def upload_targets(self, targets) -> None:
+    t = _f32(targets)
+    if t.shape != self._shape_out():
+      raise ValueError(f"targets must be {self._shape_out()}, got {t.shape}")
+    self._check(self._lib.gc_upload_targets(self._h, _ptr(t, _f32p)))
+
+  def loss_resident(self, sigmas, draw_noise: bool = False):
+    """`sigmas` [n_eval, B] (or [B]: one evaluation) -> (loss [n_eval, B], per_group [n_eval, B, n_groups]) on the
+    resident conditioning and targets (gc_loss_resident)."""
+    sg = _f32(sigmas)
+    sg = sg.reshape(1, -1) if sg.ndim == 1 else sg
+    if sg.ndim != 2 or sg.shape[1] != self.cfg.batch or sg.shape[0] < 1:
+      raise ValueError("noise_levels expected to be shape (n_eval, batch).")
+    ng = self._need_loss_groups()
+    loss = np.empty((sg.shape[0], self.cfg.batch), dtype=np.float32)
+    per_group = np.empty((sg.shape[0], self.cfg.batch, ng), dtype=np.float32)
+    self._check(self._lib.gc_loss_resident(self._h, _ptr(sg, _f32p), sg.shape[0], int(bool(draw_noise)),
+                                           _ptr(loss, _f32p), _ptr(per_group, _f32p)))
+    return loss, per_group
+
+  def download_denoised(self) -> np.ndarray:
+    """The preconditioned prediction D of the last loss evaluation (gc_download_denoised)."""
+    out = np.empty(self._shape_out(), dtype=np.float32)
+    self._check(self._lib.gc_download_denoised(self._h, _ptr(out, _f32p)))
+    return out
+
+  def loss(self, cond_feats, targets, noise, sigma, want_denoised: bool = False):
+    """One evaluation from host arrays (gc_loss) -> (loss [B], per_group [B, n_groups][, D [G, B, c_out]])."""
+    c, t, z, sg = _f32(cond_feats), _f32(targets), _f32(noise), _f32(sigma).reshape(-1)
+    if c.shape != self._shape_in():
+      raise ValueError(f"cond_feats must be {self._shape_in()}, got {c.shape}")
+    if t.shape != self._shape_out() or z.shape != self._shape_out():
+      raise ValueError(f"targets and noise must be {self._shape_out()}")
+    if sg.shape != (self.cfg.batch,):
+      raise ValueError("noise_levels expected to be shape (batch,).")
+    ng = self._need_loss_groups()
+    loss = np.empty((self.cfg.batch,), dtype=np.float32)
+    per_group = np.empty((self.cfg.batch, ng), dtype=np.float32)
+    den = np.empty(self._shape_out(), dtype=np.float32) if want_denoised else None
+    self._check(self._lib.gc_loss(self._h, _ptr(c, _f32p), _ptr(t, _f32p), _ptr(z, _f32p), _ptr(sg, _f32p),
+                                  _ptr(loss, _f32p), _ptr(per_group, _f32p), None if den is None else _ptr(den, _f32p)))
+    return (loss, per_group, den) if want_denoised else (loss, per_group)
+
   # -- ensemble exchange (RCCL inside the library) -------------------------------------------------
   def comm_init(self, unique_id: bytes, rank: int, world_size: int) -> None:
     if len(unique_id) != COMM_ID_BYTES:
@@ -444,7 +515,7 @@ class NativeDenoiser:
     self._check(self._lib.gc_comm_destroy(self._h))
 
   def counter(self, name: str) -> int:
-    """Named counters: range_fallbacks, launches_per_call, weights_f16_unsafe (gc_get_counter)."""
+    """Named counters: range_fallbacks, launches_per_call, weights_f16_unsafe, loss_evaluations, ... (gc_get_counter)."""
     v = ctypes.c_int64()
     self._check(self._lib.gc_get_counter(self._h, name.encode(), ctypes.byref(v)))
     return v.value

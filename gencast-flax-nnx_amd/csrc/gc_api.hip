@@ -189,6 +189,18 @@ struct gc_handle {
   std::vector<float> churn_rates;      // per solver step; empty = no churn
   float churn_inflation = 1.0f;
 
+  // denoising loss (gc_loss_*): forward-only evaluation of the training objective on resident conditioning + targets
+  bool has_loss_weights = false, has_targets = false, has_denoised = false;
+  int loss_groups = 0;
+  float *d_lw_node = nullptr, *d_lw_chan = nullptr, *d_lw_group = nullptr;   // [G], [c_out], [kLossMaxGroups]
+  int* d_l_group = nullptr;                                                   // channel -> group [c_out]
+  float *d_targets = nullptr, *d_lx = nullptr, *d_lden = nullptr;            // targets, noisy targets x, denoised D: [G, B, c_out]
+  double* d_lpart = nullptr;                                                  // [loss_reduce_blocks][B][c_out] per-block column sums
+  float *d_lsig = nullptr, *d_lloss = nullptr, *d_lpg = nullptr;             // per evaluation: sigma [B], loss [B], per_group [B][n_groups]
+  int loss_cap = 0;                                                           // evaluations those three (and pin_lguard) hold
+  unsigned* pin_lguard = nullptr;                                             // domain-guard counter as it stood after each evaluation
+  int64_t loss_evaluations = 0, loss_device_us = 0;
+
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {
     std::vector<float> sigmas;
@@ -1482,6 +1494,39 @@ int check_ready(gc_handle* h) {
 }
 
 
+// One evaluation of the denoising objective on the resident conditioning and targets (gc_loss_resident): optionally a
+// fresh noise field into the initial-noise buffer, x = t + sigma n and its scaled copy into the packed input, the forward
+// in the every-column form of gc_denoise (no embed cache, never captured), the reduction into slot `e` of the result
+// arrays.  `sig` = this evaluation's noise levels on the device.
+int loss_eval(gc_handle* h, int e, const float* sig, bool draw_noise, bool want_den) {
+  const gc_config& c = h->cfg;
+  const int G = h->hg.G, B = c.batch, ng = h->loss_groups;
+  hipStream_t s = h->stream;
+  int rc;
+  if (draw_noise) {
+    if ((rc = noise_field(h, nullptr, 1.0f, h->d_noise))) return rc;
+    h->has_noise = true;
+  }
+  if ((rc = launch(h, gc::KC_PACK, [&] {
+         return gc::launch_loss_noisy(s, h->d_targets, h->d_noise, sig, h->d_slots, G * B, B, c.c_out, h->kp, h->d_lx, h->d_xp);
+       })))
+    return rc;
+  float* const sigma_own = h->d_sigma;           // forward(h, -1) reads the noise levels from h->d_sigma
+  h->d_sigma = const_cast<float*>(sig);
+  rc = forward(h, -1.0f);
+  h->d_sigma = sigma_own;
+  if (rc) return rc;
+  if ((rc = launch(h, gc::KC_PACK, [&] {
+         return gc::launch_loss_reduce(s, h->d_y, h->d_targets, h->d_noise, h->d_lx, sig, h->d_lw_node, G, B, c.c_out,
+                                       h->d_lpart, want_den ? h->d_lden : nullptr);
+       })))
+    return rc;
+  return launch(h, gc::KC_PACK, [&] {
+    return gc::launch_loss_finish(s, h->d_lpart, gc::loss_reduce_blocks(G, B, c.c_out), sig, h->d_lw_chan, h->d_l_group,
+                                  h->d_lw_group, B, c.c_out, ng, h->d_lloss + (size_t)e * B, h->d_lpg + (size_t)e * B * ng);
+  });
+}
+
 // ---- RCCL, bound at run time ----------------------------------------------------------------------
 // The denoiser itself never communicates; only the ensemble driver's one exchange per forecast step
 // does.  librccl is therefore not a link-time dependency: a single-GPU user (or a CPU-only box that
@@ -1682,7 +1727,8 @@ static void destroy_impl(gc_handle* h) {
   if (h->comm) (void)rccl().CommDestroy(h->comm);
   for (void* p : h->allocs) (void)hipFree(p);
   if (h->d_nonfinite) (void)hipFree(h->d_nonfinite);
-  for (void* p : {(void*)h->h_nonfinite, (void*)h->pin_cond, (void*)h->pin_noise, (void*)h->pin_forc})
+  for (void* p : {(void*)h->h_nonfinite, (void*)h->pin_cond, (void*)h->pin_noise, (void*)h->pin_forc,
+                  (void*)h->pin_lguard})
     if (p) (void)hipHostFree(p);
   if (h->ev_pin) (void)hipEventDestroy(h->ev_pin);
   if (h->ev_stash) (void)hipEventDestroy(h->ev_stash);
@@ -2484,6 +2530,8 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "embed_cache") *value = h->embed_cache_samples;
   else if (n == "graph_replays") *value = h->graph_replays;
   else if (n == "graph_captures") *value = h->graph_captures;
+  else if (n == "loss_evaluations") *value = h->loss_evaluations;
+  else if (n == "loss_device_us") *value = h->loss_device_us;
   else return fail(h, GC_ERR_INVALID_ARGUMENT, "unknown counter: " + n);
   return GC_OK;
   });
@@ -2573,6 +2621,178 @@ int gc_set_churn(gc_handle* h, const float* rates, int32_t n, float noise_level_
   else h->churn_rates.clear();
   h->churn_inflation = noise_level_inflation_factor;
   return GC_OK;
+  });
+}
+
+// ---- denoising loss (include/gencast_hip.h) -----------------------------------------------------------
+int gc_loss_set_weights(gc_handle* h, const float* node_weight, const float* channel_weight, const int32_t* channel_group,
+                        int32_t n_groups, const float* group_weight) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  if (!node_weight || !channel_weight || !channel_group || !group_weight) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_groups < 1 || n_groups > gc::kLossMaxGroups) return fail(h, GC_ERR_INVALID_ARGUMENT, "n_groups must be in 1..64");
+  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  const gc_config& c = h->cfg;
+  for (int i = 0; i < c.c_out; ++i)
+    if (channel_group[i] < 0 || channel_group[i] >= n_groups)
+      return fail(h, GC_ERR_INVALID_ARGUMENT, "channel_group holds an index outside [0, n_groups)");
+  if ((size_t)(c.batch * c.c_out + c.batch * gc::kLossMaxGroups) * sizeof(double) > gc::kLossMaxLds)
+    return fail(h, GC_ERR_UNSUPPORTED, "batch x c_out too large for the loss reduction's finishing kernel");
+  GC_HIP(h, hipSetDevice(h->device));
+  int rc;
+  const int G = h->hg.G;
+  if (!h->d_lw_node) {
+    if ((rc = dev_alloc(h, &h->d_lw_node, (size_t)G)) || (rc = dev_alloc(h, &h->d_lw_chan, (size_t)c.c_out)) ||
+        (rc = dev_alloc(h, &h->d_l_group, (size_t)c.c_out)) || (rc = dev_alloc(h, &h->d_lw_group, (size_t)gc::kLossMaxGroups)) ||
+        (rc = dev_alloc(h, &h->d_lpart, (size_t)gc::loss_reduce_blocks(G, c.batch, c.c_out) * c.batch * c.c_out)))
+      return rc;
+  }
+  // on the handle's stream (ordered behind whatever still runs there), then waited for: the arrays are the caller's again
+  GC_HIP(h, hipMemcpyAsync(h->d_lw_node, node_weight, (size_t)G * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  GC_HIP(h, hipMemcpyAsync(h->d_lw_chan, channel_weight, c.c_out * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  GC_HIP(h, hipMemcpyAsync(h->d_l_group, channel_group, c.c_out * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  GC_HIP(h, hipMemcpyAsync(h->d_lw_group, group_weight, n_groups * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  GC_HIP(h, hipStreamSynchronize(h->stream));
+  h->loss_groups = n_groups;
+  h->has_loss_weights = true;
+  return GC_OK;
+  });
+}
+
+int gc_upload_targets(gc_handle* h, const float* targets) {
+  return guarded(h, [&]() -> int {
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!targets) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  GC_HIP(h, hipSetDevice(h->device));
+  if (h->guard_pending && (rc = resolve_guard(h))) return rc;
+  const size_t n = (size_t)h->hg.G * h->cfg.batch * h->cfg.c_out;
+  if (!h->d_targets) {
+    if ((rc = dev_alloc(h, &h->d_targets, n)) || (rc = dev_alloc(h, &h->d_lx, n)) || (rc = dev_alloc(h, &h->d_lden, n))) return rc;
+  }
+  if ((rc = staged_upload(h, h->pin_noise, h->d_targets, targets, n))) return rc;   // (same size as the noise staging buffer)
+  h->has_targets = true;
+  h->has_denoised = false;
+  return GC_OK;
+  });
+}
+
+int gc_loss_resident(gc_handle* h, const float* sigmas, int32_t n_eval, int32_t draw_noise, float* loss, float* per_group) {
+  return guarded(h, [&]() -> int {
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!sigmas || !loss || !per_group) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_eval < 1 || n_eval > (1 << 20)) return fail(h, GC_ERR_INVALID_ARGUMENT, "n_eval must be in 1..2^20");
+  const gc_config& c = h->cfg;
+  const int B = c.batch;
+  for (int64_t i = 0; i < (int64_t)n_eval * B; ++i)
+    if (!(sigmas[i] > 0.f)) return fail(h, GC_ERR_INVALID_ARGUMENT, "noise levels must be > 0");
+  if (!h->has_slots) return fail(h, GC_ERR_STATE, "gc_set_noisy_slots has not been called");
+  if (!h->has_loss_weights) return fail(h, GC_ERR_STATE, "no loss weights (gc_loss_set_weights)");
+  if (!h->has_targets) return fail(h, GC_ERR_STATE, "no targets uploaded (gc_upload_targets)");
+  if (!h->has_cond) return fail(h, GC_ERR_STATE, "no conditioning uploaded (gc_upload_cond)");
+  if (draw_noise && h->nz_L == 0) return fail(h, GC_ERR_STATE, "gc_noise_set_tables has not been called");
+  if (!draw_noise && !h->has_noise) return fail(h, GC_ERR_STATE, "no noise on the device (gc_upload_noise / gc_noise_draw)");
+  GC_HIP(h, hipSetDevice(h->device));
+  // a resident sample whose domain check is pending is resolved first: the evaluations share its guard counter, and a
+  // re-run of that sample must still find its noise (draw_noise overwrites the initial-noise buffer, like gc_noise_draw)
+  if ((rc = resolve_guard(h))) return rc;
+  const int ng = h->loss_groups;
+  if (n_eval > h->loss_cap) {                    // (earlier, smaller buffers stay owned by the handle)
+    const int cap = std::max(n_eval, 2 * h->loss_cap);
+    if ((rc = dev_alloc(h, &h->d_lsig, (size_t)cap * B)) || (rc = dev_alloc(h, &h->d_lloss, (size_t)cap * B)) ||
+        (rc = dev_alloc(h, &h->d_lpg, (size_t)cap * B * gc::kLossMaxGroups)))
+      return rc;
+    unsigned* pin = nullptr;                     // the new block first: a failure leaves the old one and loss_cap = 0
+    h->loss_cap = 0;
+    GC_HIP(h, hipHostMalloc((void**)&pin, (size_t)cap * sizeof(unsigned), hipHostMallocDefault));
+    if (h->pin_lguard) (void)hipHostFree(h->pin_lguard);
+    h->pin_lguard = pin;
+    h->loss_cap = cap;
+  }
+  hipStream_t s = h->stream;
+  GC_HIP(h, hipMemcpyAsync(h->d_lsig, sigmas, (size_t)n_eval * B * sizeof(float), hipMemcpyHostToDevice, s));
+  const bool guard = use_f16(h);
+  const unsigned long long stream0 = h->nz_stream;
+  GC_HIP(h, hipEventRecord(h->ev0, s));
+  for (int e = 0; e < n_eval; ++e) {
+    if ((rc = loss_eval(h, e, h->d_lsig + (size_t)e * B, draw_noise != 0, e == n_eval - 1))) return rc;
+    if (guard) {                                 // NaN / Inf in F: counted on the device, the count kept per evaluation
+      if ((rc = launch(h, gc::KC_PACK, [&] {
+             return gc::launch_finite_check(s, h->d_y, (size_t)h->hg.G * B * c.c_out, h->d_nonfinite);
+           })))
+        return rc;
+      GC_HIP(h, hipMemcpyAsync(h->pin_lguard + e, h->d_nonfinite, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    }
+  }
+  GC_HIP(h, hipEventRecord(h->ev1, s));
+  GC_HIP(h, hipStreamSynchronize(s));
+  {
+    float ms = 0.f;
+    GC_HIP(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    h->loss_device_us = (int64_t)(ms * 1000.0f);
+  }
+  h->loss_evaluations += n_eval;
+  h->has_denoised = true;
+  if (guard) {
+    // An evaluation that left the f16x3 domain runs again on the exact-f32 kernels, from the same noise: the field in
+    // the initial-noise buffer, or the same Philox stream drawn again (x = t + sigma n is then the same, bit for bit).
+    unsigned seen = h->nonfinite_seen;
+    int last_rerun = -1;
+    for (int e = 0; e < n_eval; ++e) {
+      const bool tripped = h->pin_lguard[e] != seen;
+      seen = h->pin_lguard[e];
+      if (!tripped) continue;
+      ++h->range_fallbacks;
+      h->in_fallback = true;
+      h->nz_stream = stream0 + (unsigned long long)e;
+      rc = loss_eval(h, e, h->d_lsig + (size_t)e * B, draw_noise != 0, e == n_eval - 1);
+      h->in_fallback = false;
+      if (rc) return rc;
+      last_rerun = e;
+    }
+    if (draw_noise) {
+      if (last_rerun >= 0 && last_rerun != n_eval - 1) {   // the buffer holds the LAST evaluation's field again
+        h->nz_stream = stream0 + (unsigned long long)(n_eval - 1);
+        if ((rc = noise_field(h, nullptr, 1.0f, h->d_noise))) return rc;
+      }
+      h->nz_stream = stream0 + (unsigned long long)n_eval;
+    }
+    h->nonfinite_seen = seen;
+    *h->h_nonfinite = seen;
+  }
+  GC_HIP(h, hipMemcpyAsync(loss, h->d_lloss, (size_t)n_eval * B * sizeof(float), hipMemcpyDeviceToHost, s));
+  GC_HIP(h, hipMemcpyAsync(per_group, h->d_lpg, (size_t)n_eval * B * ng * sizeof(float), hipMemcpyDeviceToHost, s));
+  GC_HIP(h, hipStreamSynchronize(s));
+  return GC_OK;
+  });
+}
+
+int gc_download_denoised(gc_handle* h, float* out) {
+  return guarded(h, [&]() -> int {
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!out) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!h->has_denoised) return fail(h, GC_ERR_STATE, "no loss evaluation on the device (gc_loss_resident)");
+  GC_HIP(h, hipSetDevice(h->device));
+  const size_t n = (size_t)h->hg.G * h->cfg.batch * h->cfg.c_out;
+  GC_HIP(h, hipMemcpyAsync(out, h->d_lden, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  GC_HIP(h, hipStreamSynchronize(h->stream));
+  return GC_OK;
+  });
+}
+
+int gc_loss(gc_handle* h, const float* cond_feats, const float* targets, const float* noise, const float* sigma, float* loss,
+            float* per_group, float* denoised) {
+  return guarded(h, [&]() -> int {
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!cond_feats || !targets || !noise || !sigma || !loss || !per_group) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if ((rc = gc_upload_cond(h, cond_feats))) return rc;
+  if ((rc = gc_upload_targets(h, targets))) return rc;
+  if ((rc = gc_upload_noise(h, noise))) return rc;
+  if ((rc = gc_loss_resident(h, sigma, 1, 0, loss, per_group))) return rc;
+  return denoised ? gc_download_denoised(h, denoised) : GC_OK;
   });
 }
 

@@ -4024,6 +4024,163 @@ hipError_t launch_rollout_advance(hipStream_t s, const float* old_feats, const f
   return hipGetLastError();
 }
 
+// ----------------------------------------------------------------------------
+// Denoising loss (gencast/gencast.py:229-280, common/losses.py:58-180), forward only.
+//   gc_loss_noisy_kernel    x = t + sigma_b n, and c_in(sigma_b) x into the noisy slots of the packed grid input
+//   gc_loss_reduce_kernel  per-column weighted sums of (F + c_in (n - sigma t))^2 = lambda (D - t)^2, in double
+//   gc_loss_finish_kernel  blocks in index order -> columns -> groups -> loss, per_group (float32)
+// sigma is per batch member and comes from a device array.  No atomics: every partial has one writer and every
+// sum a fixed order, so the result does not depend on how the launch was scheduled.
+// ----------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gc_loss_noisy_kernel(const float* __restrict__ t, const float* __restrict__ nz,
+                                                                  const float* __restrict__ sigma, const int* __restrict__ slots,
+                                                                  int rows, int B, int c_out, int kp, float* __restrict__ x,
+                                                                  float* __restrict__ xp) {
+  const size_t total = (size_t)rows * c_out;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t row = i / c_out;
+    const int c = (int)(i - row * c_out);
+    const float sg = sigma[row % B];
+    const float v = t[i] + sg * nz[i];
+    x[i] = v;
+    xp[row * kp + 3 + slots[c]] = (1.0f / sqrtf(sg * sg + 1.0f)) * v;
+  }
+}
+
+// Thread layout: a grid node's B rows are W = B c_out consecutive floats.  grid.y cuts W into column tiles of at most
+// 256; inside a tile of wt columns thread t owns column t % wt (one (b, c) pair: one sigma, one group, ONE accumulator)
+// of node lane t / wt, q = 256 / wt lanes -- so the active threads of a block read q whole consecutive nodes, a wave
+// 64 consecutive floats.  Block x walks the contiguous node range [x per, (x + 1) per) in steps of q.  The q lanes of a
+// column are added in lane order through LDS, and the block's column sums go out as plain stores:
+// part[block x][W] (double).
+__global__ __launch_bounds__(256) void gc_loss_reduce_kernel(const float* __restrict__ y, const float* __restrict__ t,
+                                                                   const float* __restrict__ nz, const float* __restrict__ x,
+                                                                   const float* __restrict__ sigma,
+                                                                   const float* __restrict__ node_w, int G, int B, int c_out,
+                                                                   int per, double* __restrict__ part,
+                                                                   float* __restrict__ den) {
+  __shared__ double lane_sum[256];
+  const int W = B * c_out;
+  const int col0 = blockIdx.y * 256;
+  const int wt = min(256, W - col0);
+  const int q = 256 / wt;
+  const int tid = threadIdx.x;
+  const int lane = tid / wt;
+  const int col = col0 + (tid - lane * wt);
+  const bool active = lane < q;
+  double acc = 0.0;
+  if (active) {
+    const float sgf = sigma[col / c_out];
+    const double sg = (double)sgf;
+    const double c_in = 1.0 / sqrt(sg * sg + 1.0);
+    const float co_f = sgf / sqrtf(sgf * sgf + 1.0f), cs_f = 1.0f / (sgf * sgf + 1.0f);
+    const int n_end = min(G, (int)(blockIdx.x + 1) * per);
+#pragma unroll 4
+    for (int n = blockIdx.x * per + lane; n < n_end; n += q) {
+      const size_t i = (size_t)n * W + col;
+      const float yv = y[i];
+      const double r = (double)yv + c_in * ((double)nz[i] - sg * (double)t[i]);
+      acc += (double)node_w[n] * (r * r);
+      if (den) den[i] = yv * co_f + x[i] * cs_f;
+    }
+  }
+  lane_sum[tid] = acc;
+  __syncthreads();
+  if (tid < wt) {
+    double s = lane_sum[tid];
+    for (int l = 1; l < q; ++l) s += lane_sum[l * wt + tid];
+    part[(size_t)blockIdx.x * W + col] = s;
+  }
+}
+
+// One workgroup.  Dynamic LDS: double[W + B n_groups].  The blocks of a column are added the way the reduce pass adds
+// nodes: in tiles of at most 256 columns, thread t owns column t % wt and the contiguous block range of lane t / wt, the
+// lanes are combined in lane order -- a fixed order, ascending in the block index.
+__global__ __launch_bounds__(256) void gc_loss_finish_kernel(const double* __restrict__ part, int blocks,
+                                                                   const float* __restrict__ sigma,
+                                                                   const float* __restrict__ chan_w,
+                                                                   const int* __restrict__ chan_group,
+                                                                   const float* __restrict__ group_w, int B, int c_out,
+                                                                   int n_groups, float* __restrict__ loss,
+                                                                   float* __restrict__ per_group) {
+  extern __shared__ double fin_lds[];
+  __shared__ double lane_sum[256];
+  const int W = B * c_out;
+  double* col_sum = fin_lds;
+  double* grp = fin_lds + W;
+  for (int col0 = 0; col0 < W; col0 += 256) {
+    const int wt = min(256, W - col0);
+    const int q = 256 / wt;
+    const int lane = threadIdx.x / wt;
+    const int j = col0 + (threadIdx.x - lane * wt);
+    const int per = (blocks + q - 1) / q;
+    double s = 0.0;
+    if (lane < q) {
+      const int k_end = min(blocks, (lane + 1) * per);
+#pragma unroll 8
+      for (int k = lane * per; k < k_end; ++k) s += part[(size_t)k * W + j];
+    }
+    lane_sum[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x < wt) {
+      double tot = lane_sum[threadIdx.x];
+      for (int l = 1; l < q; ++l) tot += lane_sum[l * wt + threadIdx.x];
+      col_sum[j] = tot * (double)chan_w[j % c_out];
+    }
+    __syncthreads();
+  }
+  for (int j = threadIdx.x; j < B * n_groups; j += 256) {
+    const int b = j / n_groups, g = j - b * n_groups;
+    double s = 0.0;
+    for (int c = 0; c < c_out; ++c)
+      if (chan_group[c] == g) s += col_sum[b * c_out + c];
+    const double sg = (double)sigma[b];
+    s *= sg * sg / (sg * sg + 1.0);            // mean of (D - t)^2 = c_out(sigma)^2 x mean of lambda (D - t)^2
+    grp[j] = s;
+    per_group[j] = (float)s;
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < B; b += 256) {
+    double s = 0.0;
+    for (int g = 0; g < n_groups; ++g) s += (double)group_w[g] * grp[b * n_groups + g];
+    const double sg = (double)sigma[b];
+    loss[b] = (float)(s * ((sg * sg + 1.0) / (sg * sg)));   // lambda = c_out(sigma)^-2
+  }
+}
+
+hipError_t launch_loss_noisy(hipStream_t s, const float* t, const float* nz, const float* sigma, const int* slots, int rows,
+                             int B, int c_out, int kp, float* x, float* xp) {
+  hipLaunchKernelGGL(gc_loss_noisy_kernel, dim3(ew_grid((size_t)rows * c_out)), dim3(256), 0, s, t, nz, sigma, slots,
+                     rows, B, c_out, kp, x, xp);
+  return hipGetLastError();
+}
+
+int loss_reduce_blocks(int G, int B, int c_out) {
+  const int W = B * c_out;
+  const int q = 256 / std::min(256, W);            // node lanes of a full column tile
+  return std::max(1, std::min(kLossMaxBlocks, (G + 8 * q - 1) / (8 * q)));   // 8 nodes per thread, or more
+}
+
+hipError_t launch_loss_reduce(hipStream_t s, const float* y, const float* t, const float* nz, const float* x,
+                              const float* sigma, const float* node_w, int G, int B, int c_out, double* part, float* den) {
+  const int W = B * c_out;
+  const int blocks = loss_reduce_blocks(G, B, c_out);
+  const int per = (G + blocks - 1) / blocks;
+  hipLaunchKernelGGL(gc_loss_reduce_kernel, dim3(blocks, (W + 255) / 256), dim3(256), 0, s, y, t, nz, x, sigma, node_w,
+                     G, B, c_out, per, part, den);
+  return hipGetLastError();
+}
+
+hipError_t launch_loss_finish(hipStream_t s, const double* part, int blocks, const float* sigma, const float* chan_w,
+                              const int* chan_group, const float* group_w, int B, int c_out, int n_groups, float* loss,
+                              float* per_group) {
+  const size_t lds = (size_t)(B * c_out + B * n_groups) * sizeof(double);
+  if (lds > kLossMaxLds) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gc_loss_finish_kernel, dim3(1), dim3(256), lds, s, part, blocks, sigma, chan_w, chan_group,
+                     group_w, B, c_out, n_groups, loss, per_group);
+  return hipGetLastError();
+}
+
 const char* kernel_class_name(int cls) {
   static const char* names[KC_COUNT] = {"gc_cond",      "gc_pack",       "gc_mlp",       "gc_segsum",
                                         "gc_rowop",     "gc_gemm_qkv",   "gc_attention", "gc_attn_combine",

@@ -268,6 +268,24 @@ hipError_t launch_dpm_first(hipStream_t s, const float* y, const float* x, float
 hipError_t launch_dpm_second(hipStream_t s, const float* y, const float* xmid, float c_out,
                              float c_skip, float a_next, size_t n, float* x, const NoisyWrite& nw = NoisyWrite());
 
+// Denoising loss, forward only (gencast/gencast.py:229-280, common/losses.py:58-180); sigma [B] is a DEVICE array.
+//   launch_loss_noisy   x = t + sigma_b nz;  xp[row][3 + slots[c]] = c_in(sigma_b) x
+//   launch_loss_reduce  part[block][B][c_out] (double) = sum over the block's nodes of node_w (y + c_in (nz - sigma t))^2,
+//                       loss_reduce_blocks(G, B, c_out) blocks; den != nullptr: also den = c_out y + c_skip x (else x is unused)
+//   launch_loss_finish  blocks added in index order, times chan_w, folded into groups by chan_group:
+//                       per_group[b][g] = c_out(sigma_b)^2 (...), loss[b] = lambda(sigma_b) sum_g group_w[g] per_group[b][g]
+constexpr int kLossMaxBlocks = 2048;          // 8 workgroups of 4 waves per CU: a memory-bound pass wants the waves
+constexpr int kLossMaxGroups = 64;
+constexpr size_t kLossMaxLds = 32 * 1024;      // launch_loss_finish: (B c_out + B n_groups) doubles
+int loss_reduce_blocks(int G, int B, int c_out);
+hipError_t launch_loss_noisy(hipStream_t s, const float* t, const float* nz, const float* sigma, const int* slots, int rows,
+                             int B, int c_out, int kp, float* x, float* xp);
+hipError_t launch_loss_reduce(hipStream_t s, const float* y, const float* t, const float* nz, const float* x,
+                              const float* sigma, const float* node_w, int G, int B, int c_out, double* part, float* den);
+hipError_t launch_loss_finish(hipStream_t s, const double* part, int blocks, const float* sigma, const float* chan_w,
+                              const int* chan_group, const float* group_w, int B, int c_out, int n_groups, float* loss,
+                              float* per_group);
+
 // Spherical white noise (gc_noise.hip): `count` N(0,1) values from Philox4x32-10 (key, stream), and the
 // two-step synthesis out = (base ? base : 0) + scale * field, field [n_lat * n_lon][N] from coef [2][L][L][N].
 hipError_t launch_noise_normals(hipStream_t s, float* out, size_t count, unsigned long long key,

@@ -202,6 +202,15 @@ def like_inputs(out: Dataset, template, *others):
   return to_xarray(out, template if is_xarray(template) else None)
 
 
+def loss_like_inputs(loss, diagnostics, *given):
+  """`like_inputs` for a (loss, diagnostics) pair: an `xarray.DataArray` and an `xarray.Dataset` when any of the
+  arguments of the call was an xarray object (common/losses.py:26 `LossAndDiagnostics`), else `Variable` / `Dataset`."""
+  if not any(is_xarray(o) for o in given) or is_xarray(diagnostics):
+    return loss, diagnostics
+  import xarray  # pylint: disable=import-outside-toplevel
+  return xarray.DataArray(loss.data, dims=loss.dims), to_xarray(diagnostics)
+
+
 def as_dataset(obj) -> Dataset:
   if isinstance(obj, Dataset):
     return obj

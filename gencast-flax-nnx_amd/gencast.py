@@ -8,7 +8,9 @@ noise_encoder_config), `num_outputs` inference (:158-169), the sampler singleton
 Known reference defect NOT copied: `GenCast.__call__` forwards `forcings`
 positionally into the denoiser's `noise_levels` slot (gencast.py:282-287 vs
 denoiser.py:172-178).  Here `__call__` takes `noise_levels` explicitly.
-`loss` / `loss_and_predictions` are training-only and out of scope.
+`loss` / `loss_and_predictions` (gencast.py:221-280) keep raising NotImplementedError: training is out of scope.
+The diffusion objective itself is available forward-only as `denoising_loss` /
+`denoising_loss_and_predictions` (a harness that only evaluates may alias them: INTEGRATION.md).
 """
 from __future__ import annotations
 
@@ -18,8 +20,24 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import config as cfg
+from . import datasets, losses
+from .datasets import Dataset, Variable
 from .denoiser import Denoiser
-from .sampler import Sampler
+from .sampler import Sampler, rho_inverse_cdf
+
+
+def _generator(rngs) -> np.random.Generator:
+  """A numpy Generator from whatever `rngs` is, the way `Sampler` consumes it: a Generator is used (and advanced) as
+  it is, an int seeds a fresh one, an object with `.noise()` seeds one from the key it hands out."""
+  if rngs is None:
+    raise ValueError("Must pass rngs (a numpy Generator, an int seed, or an object with .noise())")
+  if isinstance(rngs, np.random.Generator):
+    return rngs
+  if isinstance(rngs, (int, np.integer)):
+    return np.random.default_rng(int(rngs))
+  if hasattr(rngs, "noise"):
+    return np.random.default_rng(datasets.key_words(rngs.noise()).tolist())
+  raise TypeError(f"unsupported rngs: {type(rngs)}")
 
 
 class GenCast:
@@ -70,10 +88,136 @@ class GenCast:
       return self._sampler(inputs, targets_template, forcings, rngs=rng, **optional_kwargs)
     return predictor_fn
 
+  # -- the diffusion objective, forward only -----------------------------------------------------------------
+  def _denoising_eval(self, inputs, targets, forcings, rngs, noise_levels, noise, num_noise_draws, per_variable_weights):
+    """-> (loss [K, B], per_variable [K, B, V], names, D [G, B, c_out] of the last draw, grid_shape, targets Dataset)."""
+    inputs, targets, forcings = (datasets.as_dataset(x) for x in (inputs, targets, forcings))
+    if noise_levels is None and self._noise_config is None:
+      raise ValueError("Noise config must be specified to train GenCast.")
+    draws = 1 if num_noise_draws is None else int(num_noise_draws)
+    if draws < 1:
+      raise ValueError("num_noise_draws must be >= 1")
+    cond, grid_shape, slots = self.denoiser.init_for(inputs, targets, forcings)
+    native = self.denoiser.native
+    native.set_noisy_slots(slots)
+    batch = cond.shape[1]
+    shape = (cond.shape[0], batch, self.denoiser.dims.c_out)
+    stacked = np.transpose(datasets.dataset_to_stacked(targets, targets.sizes), (1, 2, 0, 3))
+    plan = losses.loss_plan(targets, per_variable_weights)
+    native.loss_set_weights(plan.node_weight, plan.channel_weight, plan.channel_group, plan.group_weight)
+    native.upload_cond(cond)
+    native.upload_targets(stacked.reshape(shape))
+    if noise_levels is not None:
+      sigmas = np.asarray(getattr(noise_levels, "data", noise_levels), dtype=np.float32)
+      sigmas = sigmas.reshape(1, -1) if sigmas.ndim == 1 else sigmas
+      if sigmas.shape != (draws, batch):
+        raise ValueError("noise_levels expected to be shape (batch,).")
+    gen = None
+    if noise_levels is None or noise is None:
+      gen = _generator(self.rngs if rngs is None else rngs)
+    if noise is not None:
+      noise = np.asarray(noise, dtype=np.float32)
+      if noise.shape != shape:
+        raise ValueError(f"noise must have shape {shape}")
+    nc = self._noise_config
+    sampler = self._sampler
+    on_device = noise is None and sampler.device_noise and sampler.noise_kind != "white"
+    loss = np.empty((draws, batch), np.float32)
+    per_var = np.empty((draws, batch, len(plan.names)), np.float32)
+    if on_device:                       # every draw a fresh device field: ONE native call for all of them
+      sampler.ensure_device_noise(native, targets)
+      native.noise_seed(sampler.seed_from(gen), 0)      # the key first, then the levels: draw 0 is the single call's draw
+      if noise_levels is None:
+        sigmas = np.stack([rho_inverse_cdf(nc.training_min_noise_level, nc.training_max_noise_level, nc.training_noise_level_rho,
+                                           gen.random(batch, dtype=np.float32)) for _ in range(draws)]).astype(np.float32)
+      loss, per_var = native.loss_resident(sigmas, draw_noise=True)
+    else:
+      for k in range(draws):            # per draw: noise levels first, then the field (the reference's order, gencast.py:238-253)
+        if noise_levels is None:
+          sg = rho_inverse_cdf(nc.training_min_noise_level, nc.training_max_noise_level, nc.training_noise_level_rho,
+                               gen.random(batch, dtype=np.float32)).astype(np.float32)
+        else:
+          sg = sigmas[k]
+        native.upload_noise(noise if noise is not None else sampler.draw_noise(gen, shape, targets))
+        loss[k], per_var[k] = (a[0] for a in native.loss_resident(sg))
+    return loss, per_var, plan.names, native, grid_shape, targets
+
+  @staticmethod
+  def _loss_outputs(loss, per_var, names, squeeze, given):
+    dims = ("batch",) if squeeze else ("draw", "batch")
+    if squeeze:
+      loss, per_var = loss[0], per_var[0]
+    total = Variable(dims, loss)
+    diagnostics = Dataset({name: Variable(dims, np.ascontiguousarray(per_var[..., g])) for g, name in enumerate(names)})
+    return datasets.loss_like_inputs(total, diagnostics, *given)
+
+  def denoising_loss(self, inputs, targets, forcings=None, *, rngs=None, noise_levels=None, noise=None,
+                     num_noise_draws=None, per_variable_weights=None):
+    """The value of `GenCast.loss` (gencast/gencast.py:229-280), evaluated forward-only on the GPU: per batch member
+    a noise level sigma, x = targets + sigma * noise, the preconditioned denoiser D(x; sigma), the latitude- and
+    level-weighted MSE of D against the targets summed over variables (`losses.DEFAULT_PER_VARIABLE_WEIGHTS`) and times
+    lambda(sigma) = c_out(sigma)^-2.  Returns (loss, diagnostics) with dims ('batch',): diagnostics are the unweighted
+    per-variable means.
+
+    `noise_levels` [batch]: given levels; None draws them as rho_inverse_cdf(NoiseConfig, uniform) from `rngs` (from
+    `self.rngs` when that is None too), consumed the way `Sampler` consumes it.  `noise` [G, batch, c_out]: a given
+    unit-variance field; None draws spherical white noise on a qualifying grid, else white noise (`Sampler.draw_noise`;
+    on the device with the sampler's `device_noise`).  The reference's random stream (jax's `uniform`, dinosaur's
+    coefficient order) is not reproduced, as for sampling: equal `rngs` give equal results HERE.
+    `num_noise_draws=K` evaluates K independent (levels, field) draws on the conditioning and targets uploaded once and
+    returns dims ('draw', 'batch') (`validation_loss`)."""
+    loss, per_var, names, *_ = self._denoising_eval(inputs, targets, forcings, rngs, noise_levels, noise, num_noise_draws,
+                                                    per_variable_weights)
+    return self._loss_outputs(loss, per_var, names, num_noise_draws is None, (targets, inputs, forcings))
+
+  def denoising_loss_and_predictions(self, inputs, targets, forcings=None, *, rngs=None, noise_levels=None, noise=None,
+                                     num_noise_draws=None, per_variable_weights=None):
+    """((loss, diagnostics), predictions) with predictions = the preconditioned D(x; sigma) of THAT evaluation (of the
+    last draw with `num_noise_draws`).  The reference's `loss_and_predictions` (gencast.py:221-227) takes its
+    predictions from a second call through its `__call__`, which passes `forcings` where the denoiser expects noise
+    levels -- the defect this module already declines to copy -- so there is no reference value to match; D is what
+    the loss was computed from."""
+    loss, per_var, names, native, grid_shape, tds = self._denoising_eval(
+        inputs, targets, forcings, rngs, noise_levels, noise, num_noise_draws, per_variable_weights)
+    preds = Denoiser.unpack_outputs(native.download_denoised(), grid_shape, tds)
+    given = (targets, inputs, forcings)
+    return self._loss_outputs(loss, per_var, names, num_noise_draws is None, given), datasets.like_inputs(preds, *given)
+
   def loss(self, *args, **kwargs):
-    raise NotImplementedError("training (loss) is outside the sampling hot path")
+    raise NotImplementedError("training (loss) is outside the sampling hot path; the forward-only value of the "
+                              "objective is GenCast.denoising_loss / denoising_loss_and_predictions")
 
   loss_and_predictions = loss
+
+
+def compute_loss(model, inputs, targets, forcings=None, **kwargs):
+  """training/train_helpers.py:221-236: (mean loss over the batch, {variable: batch mean}) of `model.denoising_loss`."""
+  loss, diagnostics = model.denoising_loss(inputs, targets, forcings, **kwargs)
+  vals = lambda v: np.asarray(getattr(v, "values", getattr(v, "data", v)), dtype=np.float64)
+  return float(vals(loss).mean()), {k: float(vals(diagnostics[k]).mean()) for k in diagnostics.keys()}
+
+
+def validation_loss(model, batches, noise_levels_per_batch: int = 1, rngs=0):
+  """A checkpoint's validation loss (what training/train_helpers.py:276-290 `eval_step_packed` is looped for): for every
+  (inputs, targets, forcings) of `batches` the conditioning and targets go up once and `noise_levels_per_batch`
+  independent (noise levels, noise field) draws are evaluated on them (`gc_loss_resident`).  `model`: a `GenCast` or a
+  wrapper stack around one.  Returns (mean loss, {variable: mean}) over all batches, draws and batch members.  One
+  generator made from `rngs` runs through all of them.  With host-drawn noise (the default) the result equals the mean of
+  the single `denoising_loss(..., rngs=generator)` calls in the same order; with the sampler's `device_noise` a batch's K
+  draws are ONE native call on Philox streams 0..K-1 of one key (draw 0 is what a single call would draw, the others
+  are not)."""
+  gen = _generator(rngs)
+  total, per_var, count = 0.0, {}, 0
+  for inputs, targets, forcings in batches:
+    loss, diagnostics = model.denoising_loss(inputs, targets, forcings, rngs=gen, num_noise_draws=int(noise_levels_per_batch))
+    vals = lambda v: np.asarray(getattr(v, "values", getattr(v, "data", v)), dtype=np.float64)
+    total += float(vals(loss).sum())
+    count += vals(loss).size
+    for k in diagnostics.keys():
+      per_var[k] = per_var.get(k, 0.0) + float(vals(diagnostics[k]).sum())
+  if count == 0:
+    raise ValueError("validation_loss: no batches")
+  return total / count, {k: v / count for k, v in per_var.items()}
 
 
 def create_gencast_model(task_config: cfg.TaskConfig = cfg.TASK, *, mesh_size: int = 3,

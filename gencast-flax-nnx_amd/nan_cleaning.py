@@ -1,7 +1,8 @@
 """`NaNCleaner`: predictor wrapper that fills NaNs of one variable before the wrapped predictor sees
 them and (optionally) puts them back into the predictions.
 
-Mirrors gencast/nan_cleaning.py:27-156 (`__call__`, `full_sampling`; `loss` is training-only).  With
+Mirrors gencast/nan_cleaning.py:27-156 (`__call__`, `full_sampling`; `loss` is training-only, its forward-only
+value is `denoising_loss` / `denoising_loss_and_predictions`, :87-126).  With
 this repo's TASK the cleaned variable (`sea_surface_temperature`, training/train_helpers.py:170-178)
 is absent, so the wrapper is a pass-through at run time -- it exists so that the reference's model
 stack `NaNCleaner(InputsAndResiduals(GenCast))` can be assembled unchanged.  It also keeps NaNs
@@ -79,7 +80,34 @@ class NaNCleaner:
   def full_sampling(self, inputs, targets_template, forcings: Optional[Dataset] = None, **kwargs):
     return self._wrap(self.predictor.full_sampling, inputs, targets_template, forcings, **kwargs)
 
+  def _clean_all(self, inputs, targets, forcings):
+    inputs, targets = datasets.as_dataset(inputs), datasets.as_dataset(targets)
+    forcings = None if forcings is None else datasets.as_dataset(forcings)
+    if self._var_to_clean in inputs.keys():
+      inputs = self._clean(inputs)
+    if self._var_to_clean in targets.keys():
+      targets = self._clean(targets)
+    if forcings is not None and self._var_to_clean in forcings.keys():
+      forcings = self._clean(forcings)
+    return inputs, targets, forcings
+
+  def denoising_loss(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """nan_cleaning.py:87-102 on the forward-only objective: inputs, targets and forcings are cleaned."""
+    out = self.predictor.denoising_loss(*self._clean_all(inputs, targets, forcings), **kwargs)
+    return datasets.loss_like_inputs(*out, targets, inputs, forcings)
+
+  def denoising_loss_and_predictions(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """nan_cleaning.py:104-126: as above; NaNs go back into the predictions when `reintroduce_nans`."""
+    given = (targets, inputs, forcings)
+    original = datasets.as_dataset(inputs)
+    loss, preds = self.predictor.denoising_loss_and_predictions(*self._clean_all(inputs, targets, forcings), **kwargs)
+    preds = datasets.as_dataset(preds)
+    if self._reintroduce_nans:
+      preds = self._maybe_reintroduce_nans(original, preds)
+    return datasets.loss_like_inputs(*loss, *given), datasets.like_inputs(preds, *given)
+
   def loss(self, *args, **kwargs):
-    raise NotImplementedError("training (loss) is outside the sampling hot path")
+    raise NotImplementedError("training (loss) is outside the sampling hot path; the forward-only value of the "
+                              "objective is denoising_loss / denoising_loss_and_predictions")
 
   loss_and_predictions = loss

@@ -155,6 +155,28 @@ class InputsAndResiduals:
     """common/normalization.py:200-238."""
     return self._wrap("full_sampling", inputs, targets_template, forcings, **kwargs)
 
+  def _normalized_loss_args(self, inputs, targets, forcings):
+    inputs, targets, forcings = (datasets.as_dataset(x) for x in (inputs, targets, forcings))
+    norm_targets = Dataset({k: self._subtract_input_and_normalize_target(inputs, k, v) for k, v in targets.items()},
+                           targets.coords)
+    return (inputs, normalize(inputs, self._scales, self._locations), norm_targets,
+            normalize(forcings, self._scales, self._locations))
+
+  def denoising_loss(self, inputs, targets, forcings=None, **kwargs):
+    """common/normalization.py:163-176 on the forward-only objective: the loss of the wrapped predictor on normalised
+    inputs and forcings and residual-normalised targets."""
+    _, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    return datasets.loss_like_inputs(*self.predictor.denoising_loss(ni, nt, forcings=nf, **kwargs), targets, inputs, forcings)
+
+  def denoising_loss_and_predictions(self, inputs, targets, forcings=None, **kwargs):
+    """common/normalization.py:178-197: the same loss, with the predictions un-normalised (residuals added back)."""
+    given = (targets, inputs, forcings)
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    loss, norm_pred = self.predictor.denoising_loss_and_predictions(ni, nt, forcings=nf, **kwargs)
+    norm_pred = datasets.as_dataset(norm_pred)
+    preds = Dataset({k: self._unnormalize_prediction_and_add_input(raw, k, v) for k, v in norm_pred.items()}, norm_pred.coords)
+    return datasets.loss_like_inputs(*loss, *given), datasets.like_inputs(preds, *given)
+
 
 def _broadcast_last(last: Variable, like: Variable) -> np.ndarray:
   """The last input frame (no time axis) broadcast against a time=1 variable."""

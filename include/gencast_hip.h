@@ -233,7 +233,8 @@ int gc_sample(gc_handle* h, const float* cond_feats, const float* init_noise,
  * initial noise is double-buffered -- so "sample, upload the next member's noise, download" pipelines without a
  * wait.  Every other entry point that changes sampler inputs (gc_upload_cond, gc_upload_cond_dev, gc_commit_cond,
  * gc_comm_broadcast_cond, gc_set_noisy_slots, gc_set_churn, gc_noise_seed) first resolves the pending check, i.e.
- * waits for the stream.  A second gc_sample_resident before any of these discards the first sample's check with
+ * waits for the stream; so do gc_upload_targets and gc_loss_resident (the targets are an input of the loss evaluations,
+ * which share the guard and, with draw_noise, overwrite the initial-noise buffer).  A second gc_sample_resident before any of these discards the first sample's check with
  * its result.
  */
 int gc_upload_cond(gc_handle* h, const float* cond_feats);
@@ -291,6 +292,50 @@ int gc_noise_seed(gc_handle* h, uint64_t seed, uint64_t stream);
 int gc_noise_draw(gc_handle* h);
 int gc_download_noise(gc_handle* h, float* out);
 int gc_set_churn(gc_handle* h, const float* rates, int32_t n, float noise_level_inflation_factor);
+
+/*
+ * Denoising loss, forward only: "what is this checkpoint's loss on this batch at these noise levels".
+ * Replaces: GenCast.loss (gencast/gencast.py:229-280) with losses.weighted_mse_per_level
+ * (common/losses.py:58-180), at the flat-array level; no backward pass.  For batch member b with noise level s_b:
+ *   x = t + s_b n;   F = network(cond with c_in(s_b) x in the noisy slots; s_b);   D = c_out(s_b) F + c_skip(s_b) x
+ *   per_group[b][g] = sum over nodes i and the channels c of group g of node_weight[i] channel_weight[c] (D - t)^2
+ *   loss[b]         = c_out(s_b)^-2  sum_g group_weight[g] per_group[b][g]
+ * (the reference's per-variable mean: node_weight = unit-mean latitude weight / G, channel_weight = level weight /
+ * channels of the variable, one group per variable -- gencast-flax-nnx_amd/losses.py loss_plan builds them).
+ * The device evaluates lambda (D - t)^2 as (F + c_in (n - s t))^2, the same quantity without the cancellation at small
+ * s, forms and adds every term in double in a fixed order (no atomics: results are bit-reproducible) and rounds once,
+ * to the float32 results.
+ *   gc_loss_set_weights   node_weight [G], channel_weight [c_out], channel_group [c_out] (values in [0, n_groups)),
+ *                         n_groups in 1..64, group_weight [n_groups].  GC_ERR_UNSUPPORTED when
+ *                         batch * (c_out + 64) * 8 bytes exceed 32 KiB (batch > 28 at c_out = 82): the finishing kernel is
+ *                         one workgroup that keeps every column and group sum in LDS
+ *   gc_upload_targets     targets [G, B, c_out] into the handle (H2D; the caller's buffer is free on return)
+ *   gc_loss_resident      n_eval evaluations back to back on the resident conditioning (gc_upload_cond*) and targets;
+ *                         sigmas [n_eval][B] (> 0).  draw_noise = 1: every evaluation draws a fresh spherical field into
+ *                         the initial-noise buffer (gc_noise_seed streams, one stream per field); draw_noise = 0: every
+ *                         evaluation uses the field that buffer holds (gc_upload_noise / gc_noise_draw).  Synchronous:
+ *                         loss [n_eval][B] and per_group [n_eval][B][n_groups] come back in one download at the end.
+ *                         n_eval <= 2^20; the per-evaluation device buffers (B * 66 floats per evaluation) grow by
+ *                         doubling and, like every device buffer of a handle, are released by gc_destroy only.
+ *                         Each evaluation is one forward in gc_denoise's form, enqueued eagerly (never captured, the
+ *                         per-sample embedding cache is not engaged); conditioning, the last sample, captured sample
+ *                         graphs and (with draw_noise = 0) the initial noise are left as they were.
+ *   gc_download_denoised  D [G, B, c_out] of the LAST evaluation of the last gc_loss_resident / gc_loss
+ *   gc_loss               host-pointer convenience for one evaluation: gc_upload_cond + gc_upload_targets +
+ *                         gc_upload_noise + gc_loss_resident(n_eval = 1, draw_noise = 0) (+ gc_download_denoised when
+ *                         `denoised` is not NULL)
+ * GC_ERR_STATE before gc_finalize, gc_set_noisy_slots, the weights, the targets, the conditioning or the noise are in
+ * place.  f16x3 domain guard as in gc_denoise: an evaluation whose F holds NaN / Inf is run again on the exact-f32
+ * kernels from the same noise and counted in "range_fallbacks".
+ */
+int gc_loss_set_weights(gc_handle* h, const float* node_weight, const float* channel_weight,
+                        const int32_t* channel_group, int32_t n_groups, const float* group_weight);
+int gc_upload_targets(gc_handle* h, const float* targets);
+int gc_loss_resident(gc_handle* h, const float* sigmas, int32_t n_eval, int32_t draw_noise,
+                     float* loss, float* per_group);
+int gc_download_denoised(gc_handle* h, float* out);
+int gc_loss(gc_handle* h, const float* cond_feats, const float* targets, const float* noise, const float* sigma,
+            float* loss, float* per_group, float* denoised /* NULL allowed */);
 
 /*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
@@ -372,7 +417,9 @@ int gc_algorithmic_work(gc_handle* h, double* flops, double* bytes);
  * jraph.segment_sum of common/typed_graph_net.py:175-182 without storing the edges; 0: edge update + a segment-sum launch, the form
  * any mesh2grid edge set with other in-degrees than 3 takes), "embed_cache" (samples so far whose grid embedding ran on the cached
  * per-sample-constant part of its first layer: only the c_out noisy-target columns are multiplied per call, the other 3 + c_in - c_out
- * once per sample -- dpm_solver_plus_plus_2s.py:107-112 closes over them; float32 node features, hidden_layers = 1). */
+ * once per sample -- dpm_solver_plus_plus_2s.py:107-112 closes over them; float32 node features, hidden_layers = 1),
+ * "loss_evaluations" (denoising-loss evaluations so far: gc_loss_resident / gc_loss), "loss_device_us" (HIP-event time of
+ * the evaluations of the last gc_loss_resident call, microseconds). */
 int gc_get_counter(gc_handle* h, const char* name, int64_t* value);
 
 #ifdef __cplusplus
