@@ -1,0 +1,346 @@
+// Internals shared by the host translation units of libgencast_hip.so: the handle, the device-side weight layout,
+// the route of a forward, and the allocation / launch helpers.  gc_weights.hip lays the weights out, gc_forward.hip
+// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include <rccl/rccl.h>   // types and enums only: librccl.so.1 is dlopen'ed on first use (gc_comm_*)
+
+#include "../../include/gencast_hip.h"
+#include "../../include/gencast_hip_debug.h"
+#include "gc_graph.h"
+#include "gc_kernels.h"
+
+namespace gci {
+
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// Every decision of one denoiser forward, taken once from the handle's state (make_route, gc_forward.hip); the
+// launches read nothing else.
+struct Route {
+  bool f16 = false;         // GEMM-shaped kernels run f16x3 (3 fp16 MFMAs per product); else exact f32
+  bool x32 = false;         // exact f32 on the weight-streaming / fused kernels (WF32 images, v_mfma_f32_32x32x2_f32)
+  bool st16 = false;        // PHYSICAL fp16 activation storage: every kernel is the gc_a16 build (halfs in HBM)
+  int ffw_slabs = 0;        // > 0: both FFW layers in one launch with this many hidden slices
+  bool v2 = false;          // the QKV projection writes K / V as fp16 planes (they live in d_kv16 only) for attention v2
+  int att_items = 0;        // work items of the attention launch (0: the plain (tile, split) launch)
+  bool fuse_row = false;    // out-projection with the row pass in its epilogue
+  bool node_ws = false;     // the per-node GEMMs of a split edge MLP stream their weights (WF16 only: no WF32 image)
+  bool m2g_fused = false;   // the mesh2grid edge MLP sums each grid node's three edges: f1 is not stored
+  bool split_edge = false;  // edge MLPs with the first layer split by input block
+  bool try_pair = false;    // the grid2mesh edge and grid-node updates may go out as one launch
+  bool embed_cache = false; // inside a sample that runs the grid embedding on the cache (d_xn / d_pstat)
+  // the weight-streaming GEMM (WF16 / WF32 weights) whenever the K slice is a multiple of 128
+  bool ws(int n, int k, int splits) const { return (f16 || x32) && n % 128 == 0 && (k / splits) % 128 == 0; }
+};
+
+// One matrix W^T [n][k] on the device, in every image a kernel form reads it from.
+struct Weight {
+  float* t = nullptr;   // float32, row-major, row stride ld   (LDS-staged kernels, exact f32)
+  float* s = nullptr;   // S16 (split-fp16) encoding of t      (LDS-staged kernels, f16x3)
+  float* f = nullptr;   // WF16 (MFMA fragment order), K = kf  (weight-streaming kernels, f16x3)
+  float* x = nullptr;   // WF32, K = kf                        (weight-streaming kernels, exact f32; only with f32_ws)
+  int ld = 0, kf = 0;   // kf: K of the streaming images, zero-padded to a multiple of 64
+};
+enum class Form { Staged, Streaming };
+inline const float* pick(const Weight& w, const Route& r, Form form) {
+  if (form == Form::Streaming) return r.x32 ? w.x : w.f;
+  return r.f16 ? w.s : w.t;
+}
+
+struct DevMlp {        // device-side layout of one MLPWithNormConditioning
+  Weight w1, w2;       // [hidden][K padded], [n_out_pad][hidden]
+  // edge MLPs only: first layer split by input block [e | sender | receiver] (each L rows of W1; the per-node blocks
+  // have no WF32 image).  w1e is also the noisy-columns block of the grid embedding (build_embed_cache: streaming
+  // images only, ld = the compact array's row stride)
+  Weight w1e, w1snd, w1rcv;
+  float *b1 = nullptr, *b2 = nullptr;
+  int n_out = 0, n_out_pad = 0;
+  int cond_off = -1;   // offset of [scale | offset] in the conditioning buffer
+  // hidden_layers >= 2 (common/mlp.py:166-183): the leading (Linear -> activation) layers, each run as a launch of
+  // the same fused kernel with an identity second layer and no LayerNorm; this struct then holds the LAST hidden
+  // Linear as its first layer and the output Linear as its second
+  std::vector<DevMlp> pre;
+};
+
+struct DevLayer {      // one transformer block
+  Weight wqkv, wo, w1, w2;   // [3D][D], [D][D], [F][D], [D][F]
+  float *bo = nullptr, *b1 = nullptr, *b2 = nullptr;
+  int cond_attn = -1, cond_ffw = -1;
+};
+
+}  // namespace gci
+
+struct gc_handle {
+  gc_config cfg{};
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipStream_t stream2 = nullptr;             // side stream of the stash download (gc_stash_sample)
+  std::string err;
+  bool has_graph = false, finalized = false, has_slots = false, has_cond = false, has_noise = false;
+  bool finalized_weights = false;            // gc_finalize ran on the weights now loaded (gc_load_weight clears it)
+  gc::HostGraph hg;
+
+  std::map<std::string, std::vector<int64_t>> specs;  // expected shapes
+  std::map<std::string, std::vector<float>> weights;  // host copies as loaded
+  // device buffers by owner (all freed in destroy): made once per handle; by gc_finalize, freed by the next one
+  // (free_weights); by build_embed_cache, freed by the next one
+  std::vector<void*> allocs, weight_allocs, cache_allocs;
+
+  // graph (device)
+  int *d_g2m_snd = nullptr, *d_g2m_rcv = nullptr, *d_m2g_snd = nullptr, *d_m2g_rcv = nullptr;
+  int *d_g2m_ptr = nullptr, *d_g2m_eid = nullptr, *d_m2g_ptr = nullptr, *d_m2g_eid = nullptr;
+  int *d_tile_start = nullptr, *d_union = nullptr;
+  // work-item list of the attention launch (1.25 rounds of tiles -> one round of whole tiles + one round of pieces):
+  // build_attention_items
+  int *d_att_items = nullptr, *d_att_tiles = nullptr;
+  int att_n_items = 0;
+  unsigned* d_mask = nullptr;
+  float *d_grid_struct = nullptr, *d_mesh_struct16 = nullptr, *d_e1_struct16 = nullptr,
+        *d_e2_struct16 = nullptr;
+
+  // weights (device)
+  gci::DevMlp g2m_embed_grid, g2m_embed_mesh, g2m_embed_edge, g2m_edge, g2m_mesh, g2m_grid;
+  gci::DevMlp m2g_embed_edge, m2g_edge, m2g_grid, m2g_dec;
+  std::vector<gci::DevLayer> layers;
+  int cond_final = -1;
+  int cond_total = 0;
+  std::map<std::string, std::pair<int, int>> cond_sites;   // conditioning linear (parameter path) -> (offset, width) in d_cond
+  float *d_nw0t = nullptr, *d_nb0 = nullptr, *d_nw1t = nullptr, *d_nb1 = nullptr;
+  float *d_wc_all = nullptr, *d_bc_all = nullptr;
+
+  // static embeddings (LayerNorm output, before conditioning)
+  float *d_m0_hat = nullptr, *d_e0_hat = nullptr, *d_f0_hat = nullptr;
+
+  // activations
+  int kp = 0;
+  float *d_sigma = nullptr, *d_condvec = nullptr, *d_cond = nullptr;
+  float* d_cond_all = nullptr;               // sampler: conditioning of every call of the sample [calls][B][total]
+  size_t cond_all_cap = 0;
+  const float* cond_cur = nullptr;           // conditioning vectors the current forward() reads
+  float *d_feats = nullptr, *d_xp = nullptr, *d_g0 = nullptr, *d_g1 = nullptr, *d_m0 = nullptr,
+        *d_x = nullptr, *d_e1 = nullptr, *d_agg1 = nullptr, *d_qkv = nullptr, *d_att = nullptr,
+        *d_u = nullptr, *d_m2 = nullptr, *d_f1 = nullptr, *d_agg2 = nullptr, *d_g2 = nullptr,
+        *d_y = nullptr, *d_h = nullptr, *d_part = nullptr, *d_apart_o = nullptr, *d_apart_ml = nullptr,
+        *d_pg = nullptr, *d_pm = nullptr;     // per-node first-layer products of the edge MLPs
+  // Grid embedding with its per-sample-constant part cached (dpm_solver_plus_plus_2s.py:107-112,
+  // denoiser.py:654-659): inside one sample only the c_out noisy-target channels of the packed grid input change from
+  // call to call.  At the start of a sample P = W1[static rows]^T [struct | inputs | forcings] is computed once
+  // ([G B, L] float32, the noisy columns' weights zeroed); each call's embedding MLP then multiplies only the compact
+  // noisy array xn [G B, c_out padded to 32] and adds P next to the bias (the add-term path of the split edge MLPs).
+  bool mlp_pair = true;                      // GC_TUNE_MLP_PAIR=0: the grid2mesh edge update and the grid-node update as two launches
+  bool embed_cache = true;                   // GC_TUNE_EMBED_CACHE=0: every call multiplies all 3 + c_in columns
+  bool embed_cache_ready = false;            // the split weight images below match the current weights and slots
+  bool embed_cache_live = false;             // inside a sample: the forwards may run on the cache (Route::embed_cache)
+  int nwp = 0;                               // noisy columns padded to a multiple of 32
+  float *d_xn = nullptr, *d_pstat = nullptr;
+  float *w1st_t = nullptr, *w1st_s = nullptr;   // static first layer [L][kp]: float32 and S16, noisy columns zero
+  gci::DevMlp g2m_embed_grid_n;                   // g2m_embed_grid with the noisy-columns block as its first layer (+ P as add term)
+  std::vector<int> h_slots;
+  int64_t embed_cache_samples = 0;           // samples that ran on the cache (gc_get_counter "embed_cache")
+  bool m2g_fuse_sum = true;                  // GC_TUNE_M2G_FUSE_SUM=0: mesh2grid edge update + a segment-sum launch (the form every
+                                             // graph with other in-degrees than 3 takes anyway)
+  float *d_ones = nullptr, *d_zeros = nullptr;   // identity affine for gc_mlp_ws
+  int hidden_layers = 1;                         // gc_set_option("hidden_layers"): hidden layers of every GNN MLP (denoiser.py:135)
+  float* d_mlp_tmp[2] = {nullptr, nullptr};      // hidden_layers >= 2: [max rows][latent] hand-over between the launches of one MLP
+  // autoregressive context update (gc_rollout_plan / gc_rollout_advance)
+  float *d_feats2 = nullptr, *d_ro_a = nullptr, *d_ro_b = nullptr, *d_ro_forc = nullptr;
+  int *d_ro_kind = nullptr, *d_ro_src = nullptr, *d_ro_sidx = nullptr;
+  int ro_nforc = -1, ro_forc_cap = 0;
+  bool has_sample = false;
+  int max_tile_chunks = 0;                   // largest number of 32-key chunks of any attention tile
+  int ffw_fused_slabs = 0;                   // > 0: gc_ffw_fused with this many hidden slices (= slabs)
+  void* d_kv16 = nullptr;                    // K / V as fp16 hi / lo planes, written by the QKV projection
+  bool f32_ws = true;                        // exact-f32 family on the weight-streaming / fused kernels (WF32 images): the shapes allow it
+  bool split_edge = false;                   // the split edge MLPs (latent >= 512, hidden_layers == 1)
+  // launch geometry (chosen in gc_set_graph)
+  int attn_splits = 1, out_splits = 1, ffw2_splits = 1;
+  gci::Route route;                          // of the launches being enqueued (forward, compute_static_embeddings)
+  gci::Route last_route;                     // of the last forward (gc_debug_fetch, gc_get_counter)
+  bool a16 = true;                           // GC_TUNE_A16=0: fp16-feature mode on float32 containers with 3 MFMAs per product (A/B, bit-identical)
+  bool attn_items = true;                    // GC_TUNE_ATTN_ITEMS=0: the plain (tile, split) attention launch
+  bool graph_serialize = false;              // GC_TUNE_GRAPH_SERIALIZE=1: every hipGraphLaunch also takes the capture mutex (run_sampler)
+  bool graph_verbose = false;                // GC_TUNE_GRAPH_VERBOSE=1: graph capture progress on stderr
+  // sampler state
+  int* d_slots = nullptr;
+  float *d_sx = nullptr, *d_sden = nullptr, *d_smid = nullptr, *d_noise = nullptr;
+  // The initial noise is double-buffered: a resident sample whose f16x3 domain check is still pending may have to be
+  // re-run from ITS noise, so an upload / draw for the next member that arrives before the check is resolved goes to
+  // the other buffer (d_noise always = the buffer the next sample will read; last_noise = the pending sample's).
+  float *d_noise_alt = nullptr, *last_noise = nullptr;
+  float* d_stash = nullptr;            // gc_stash_sample: snapshot of a sample, downloaded on the side stream
+  hipEvent_t ev_stash = nullptr;
+  bool has_stash = false;
+
+  // spherical white noise on the device + stochastic churn (gc_noise_*, gc_set_churn)
+  int nz_L = 0, nz_lat = 0, nz_lon = 0;
+  float *d_nz_leg = nullptr, *d_nz_cos = nullptr, *d_nz_sin = nullptr, *d_nz_coef = nullptr, *d_nz_f = nullptr;
+  unsigned long long nz_key = 0, nz_stream = 0;
+  std::vector<float> churn_rates;      // per solver step; empty = no churn
+  float churn_inflation = 1.0f;
+
+  // denoising loss (gc_loss_*): forward-only evaluation of the training objective on resident conditioning + targets
+  bool has_loss_weights = false, has_targets = false, has_denoised = false;
+  int loss_groups = 0;
+  float *d_lw_node = nullptr, *d_lw_chan = nullptr, *d_lw_group = nullptr;   // [G], [c_out], [kLossMaxGroups]
+  int* d_l_group = nullptr;                                                   // channel -> group [c_out]
+  float *d_targets = nullptr, *d_lx = nullptr, *d_lden = nullptr;            // targets, noisy targets x, denoised D: [G, B, c_out]
+  double* d_lpart = nullptr;                                                  // [loss_reduce_blocks][B][c_out] per-block column sums
+  float *d_lsig = nullptr, *d_lloss = nullptr, *d_lpg = nullptr;             // per evaluation: sigma [B], loss [B], per_group [B][n_groups]
+  int loss_cap = 0;                                                           // evaluations those three (and pin_lguard) hold
+  unsigned* pin_lguard = nullptr;                                             // domain-guard counter as it stood after each evaluation
+  int64_t loss_evaluations = 0, loss_device_us = 0;
+
+  // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
+  struct SampleGraph {
+    std::vector<float> sigmas;
+    int skip_dead = 1;
+    const float* noise = nullptr;      // the initial-noise buffer baked into the graph (it is double-buffered)
+    bool feat16 = false;
+    gci::Route route;                  // signature: f16, st16; whole once captured (a replay restores last_route)
+    hipGraph_t graph = nullptr;
+    // null until the signature has been seen twice; TWO executables of the one captured graph, launched alternately,
+    // each with an event recorded behind its last launch: an executable is never launched while its previous
+    // instance may still be running (the host waits for that event first, outside any lock)
+    hipGraphExec_t exec = nullptr, exec2 = nullptr;
+    hipEvent_t done[2] = {nullptr, nullptr};
+    int next = 0;
+    int calls = 0;
+    int64_t launches_per_call = 0, launches = 0;
+    uint64_t last_use = 0;
+  };
+  bool use_graphs = true;              // GC_TUNE_GRAPH=0 / gc_set_option(h, "graphs", "off"): always enqueue eagerly
+  std::vector<SampleGraph> sample_graphs;
+  uint64_t graph_clock = 0;
+  int64_t graph_replays = 0, graph_captures = 0;
+  int debug_layer_limit = -1;  // gc_debug_set_layer_limit
+  int debug_stop_layer = -1, debug_stop_phase = -1;   // gc_debug_set_stop: forward() returns inside this block
+  bool f16x3 = true;           // GEMM-shaped kernels run as 3 fp16 MFMAs per product (gc_set_option)
+  float g2m_agg_norm = 0.f;    // "grid2mesh_aggregate_normalization": the grid2mesh edge sums are divided by it (0: not)
+  bool feat16 = false;         // "features" = "f16": activations rounded to fp16 where stored (BASELINE configs[4])
+  // f16x3 domain guard: operands outside fp16 range poison the output with
+  // NaN / Inf (no clamp anywhere); the output is checked on the device once per call and a poisoned
+  // call is re-run on the exact-f32 kernels, which treat NaN / Inf / huge inputs like the reference.
+  bool weights_f16_unsafe = false;   // a weight is non-finite or beyond fp16 range: f32 kernels only
+  bool in_fallback = false;          // forward() is running the f32 re-run of a poisoned call
+  unsigned* d_nonfinite = nullptr;   // device counter bumped by gc_finite_check
+  unsigned* h_nonfinite = nullptr;   // pinned host copy
+  unsigned nonfinite_seen = 0;
+  int64_t range_fallbacks = 0;       // calls re-run in f32 (gc_get_counter "range_fallbacks")
+  bool guard_pending = false;        // a resident sample has not been checked yet
+  std::vector<float> last_sigmas;    // arguments of that sample, for the re-run
+  int last_skip_dead = 1;
+  unsigned long long last_stream0 = 0;
+  int64_t launches_last_call = 0, launch_count = 0;   // kernel launches of the last denoiser forward
+  // pinned staging buffers of the asynchronous uploads (caller buffers are free on return)
+  float *pin_cond = nullptr, *pin_noise = nullptr, *pin_forc = nullptr;
+  size_t pin_forc_cap = 0;
+  hipEvent_t ev_pin = nullptr;       // last H2D copy out of a staging buffer
+  // ensemble exchange (gc_comm_*): one RCCL communicator per handle, collectives on h->stream
+  ncclComm_t comm = nullptr;
+  int comm_rank = 0, comm_world = 1;
+  double* d_comm_scalar = nullptr;
+
+  // profiling
+  int prof_cls = -1;
+  int prof_stride = 1;
+  unsigned prof_seen = 0;
+  std::vector<hipEvent_t> prof_events;
+  size_t prof_used = 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+namespace gci {
+
+#define GC_HIP(h, call)                                                                     \
+  do {                                                                                      \
+    hipError_t e__ = (call);                                                                \
+    if (e__ != hipSuccess) {                                                                \
+      (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                        \
+      return GC_ERR_HIP;                                                                    \
+    }                                                                                       \
+  } while (0)
+
+inline int fail(gc_handle* h, int code, const std::string& msg) {
+  h->err = msg;
+  return code;
+}
+
+// owner: the list that frees the buffer (default h->allocs: freed in destroy)
+template <typename T>
+int dev_alloc(gc_handle* h, T** p, size_t count, std::vector<void*>* owner = nullptr) {
+  void* q = nullptr;
+  GC_HIP(h, hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+  (owner ? owner : &h->allocs)->push_back(q);
+  *p = reinterpret_cast<T*>(q);
+  return GC_OK;
+}
+
+template <typename T>
+int dev_upload(gc_handle* h, T** p, const std::vector<T>& v, std::vector<void*>* owner = nullptr) {
+  int rc = dev_alloc(h, p, v.size(), owner);
+  if (rc) return rc;
+  if (!v.empty()) GC_HIP(h, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return GC_OK;
+}
+
+inline void free_allocs(std::vector<void*>* owner) {
+  for (void* p : *owner) (void)hipFree(p);
+  owner->clear();
+}
+
+// ---- launch wrapper with optional per-class event bracketing --------------------------------
+template <typename F>
+int launch(gc_handle* h, int cls, F&& f) {
+  ++h->launch_count;
+  bool prof = (h->prof_cls == cls) && (h->prof_used + 2 <= h->prof_events.size());
+  if (prof && h->prof_stride > 1) prof = ((h->prof_seen++ % (unsigned)h->prof_stride) == 0);
+  if (prof) GC_HIP(h, hipEventRecord(h->prof_events[h->prof_used], h->stream));
+  hipError_t e = f();
+  if (e != hipSuccess) {
+    h->err = std::string("launch ") + gc::kernel_class_name(cls) + ": " + hipGetErrorString(e);
+    return GC_ERR_HIP;
+  }
+  if (prof) {
+    GC_HIP(h, hipEventRecord(h->prof_events[h->prof_used + 1], h->stream));
+    h->prof_used += 2;
+  }
+  return GC_OK;
+}
+
+// gc_weights.hip
+extern const char* const P_M2G;
+void build_specs(gc_handle* h);
+float f16_bits_to_f32(uint16_t h);
+void free_weights(gc_handle* h);
+int finalize_weights(gc_handle* h);
+int build_embed_cache(gc_handle* h);
+// gc_forward.hip
+Route make_route(const gc_handle* h);
+bool build_attention_items(const gc::HostGraph& g, std::vector<int>* items, std::vector<int>* tiles);
+int run_m2g_edge(gc_handle* h, const float* cond, bool fused);
+int forward(gc_handle* h, float sigma_scalar, const float* cond_ready = nullptr);
+int compute_static_embeddings(gc_handle* h);
+// gc_sampler.hip
+int guard_enqueue(gc_handle* h, const float* p, size_t n);
+bool guard_tripped(gc_handle* h);
+int noise_field(gc_handle* h, const float* base, float scale, float* out);
+int run_sampler(gc_handle* h, const float* sigmas, int n, int skip_dead, gc_sample_stats* stats);
+int resolve_guard(gc_handle* h);
+void destroy_sample_graph(gc_handle::SampleGraph& g);
+void drop_sample_graphs(gc_handle* h);
+int loss_eval(gc_handle* h, int e, const float* sig, bool draw_noise, bool want_den);
+
+}  // namespace gci

@@ -153,7 +153,7 @@ struct GemmArgs {
 // 2: bias/act store in S16 split-fp16 layout (f16 only).  f16: A and W^T are S16-encoded and the
 // product runs as 3 fp16 MFMAs per k-step (f32-equivalent accuracy, see gc_kernels.hip).
 hipError_t launch_gemm(hipStream_t s, int cls, const GemmArgs& g, int splits, int epi, bool f16);
-// Weight-streaming f16x3 form: g.wt is the WF16 fragment-order image of W^T (gc_api.hip
+// Weight-streaming f16x3 form: g.wt is the WF16 fragment-order image of W^T (gc_weights.hip
 // encode_wf16), g.ldw the full contraction length K; a is plain float32 (or attention partials).
 // Tile (32*mt) x 128, mt 1 or 2; needs n % 128 == 0 and k_slice a multiple of 128.  epi 0 | 1 as launch_gemm;
 // epi 3 = QKV projection with pre-split K / V planes (g.kv16, g.kv_d).
@@ -175,7 +175,7 @@ struct FfwArgs {
   int a16;             // 1 (only with round16): a and the hidden tile are exact fp16 -- the caller launches the gc_a16 build
   // diagnostic builds only (-DGC_STAMPS, tools/stamp_ffw.cpp): 8 s_memtime stamps per wave, or nullptr
   unsigned long long* stamps;
-  int f32w;            // 1: exact-f32 family -- w1f / w2f are WF32 images (gc_api.hip encode_wf32), products on v_mfma_f32_32x32x2_f32
+  int f32w;            // 1: exact-f32 family -- w1f / w2f are WF32 images (gc_weights.hip encode_wf32), products on v_mfma_f32_32x32x2_f32
 };
 hipError_t launch_ffw_fused(hipStream_t s, const FfwArgs& g);
 
@@ -243,7 +243,7 @@ hipError_t launch_finite_check(hipStream_t s, const float* p, size_t n, unsigned
 // Optional second output of the three sampler-state kernels below: the value also goes, times `scale` (the NEXT denoiser
 // call's c_in), into the noisy-target slots of the packed grid input -- xp[row][3 + slots[c]] = scale * v, what
 // launch_write_noisy does as a launch of its own.  xp == nullptr: off.
-constexpr int kItemPieces = 4;   // most key-range pieces an attention tile is cut into by a work-item list (gc_api.hip build_attention_items)
+constexpr int kItemPieces = 4;   // most key-range pieces an attention tile is cut into by a work-item list (gc_forward.hip build_attention_items)
 struct NoisyWrite {
   const int* slots = nullptr;
   int c_out = 1, kp = 0;

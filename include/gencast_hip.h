@@ -420,6 +420,7 @@ int gc_algorithmic_work(gc_handle* h, double* flops, double* bytes);
  * once per sample -- dpm_solver_plus_plus_2s.py:107-112 closes over them; float32 node features, hidden_layers = 1),
  * "loss_evaluations" (denoising-loss evaluations so far: gc_loss_resident / gc_loss), "loss_device_us" (HIP-event time of
  * the evaluations of the last gc_loss_resident call, microseconds). */
+/* ... and "device_allocations" (device buffers the handle holds now: gc_finalize and gc_set_noisy_slots replace theirs, they do not add). */
 int gc_get_counter(gc_handle* h, const char* name, int64_t* value);
 
 #ifdef __cplusplus

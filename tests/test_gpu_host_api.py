@@ -586,6 +586,48 @@ def test_sampler_graph_replay_is_bit_identical_to_eager_launches():
     nd.close()
 
 
+def test_refinalize_replaces_the_weight_buffers():
+  """gc_finalize owns what it allocates: loading the same weights and finalizing again frees the previous images, so
+  the handle's device allocation count stays where the first gc_finalize left it and gc_denoise repeats bit for bit."""
+  gr, dims, params, x, sigma = helpers.tiny_setup(batch=2, seed=3)
+  nd = helpers.make_native(gr, dims, params, 2)
+  try:
+    n0 = nd.counter("device_allocations")
+    y0 = nd.denoise(x, sigma)
+    assert n0 > 0
+    for _ in range(2):
+      nd.load_weights(params)
+      nd.finalize()
+      assert nd.counter("device_allocations") == n0
+      np.testing.assert_array_equal(nd.denoise(x, sigma), y0)
+  finally:
+    nd.close()
+
+
+def test_changing_the_noisy_slots_replaces_the_embed_cache_images():
+  """gc_set_noisy_slots with other slots rebuilds the split grid-embedding images in place of the old ones: slots,
+  reversed slots, slots again, a sample after each -- as many device allocations after the third sample as after the
+  first, and the first and third samples equal bit for bit."""
+  gr, dims, params, x, sigma = helpers.tiny_setup(batch=2, seed=3)
+  nd = helpers.make_native(gr, dims, params, 2)
+  try:
+    slots = np.arange(dims.c_in - dims.c_out, dims.c_in, dtype=np.int32)
+    noise = np.random.default_rng(9).standard_normal((gr.num_grid_nodes, 2, dims.c_out)).astype(np.float32)
+    sig = O.noise_schedule(80.0, 0.03, 4, 7.0).astype(np.float32)
+    nd.set_noisy_slots(slots)
+    first = nd.sample(x, noise, sig)[0]
+    n1 = nd.counter("device_allocations")
+    assert nd.counter("embed_cache") == 1
+    nd.set_noisy_slots(slots[::-1].copy())
+    nd.sample(x, noise, sig)
+    nd.set_noisy_slots(slots)
+    third = nd.sample(x, noise, sig)[0]
+    assert nd.counter("device_allocations") == n1
+    np.testing.assert_array_equal(third, first)
+  finally:
+    nd.close()
+
+
 def test_concurrent_members_are_bit_identical_to_sequential_ones():
   """EnsembleSampler(concurrent_members=3): three members in flight on three handles (three HIP streams) of
   one GPU -- every member equals the one-at-a-time result bit for bit (no shared scratch between handles)."""

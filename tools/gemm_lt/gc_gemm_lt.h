@@ -4,7 +4,7 @@
 // Operand images ("fragment order": what a lane feeds to v_mfma_f32_32x32x16_f16 is 16 contiguous bytes, a wave's
 // operand 1 KB, so global -> LDS is a linear copy by global_load_lds_dwordx4 and LDS -> register a linear,
 // conflict-free ds_read_b128):
-//   WF16  weights, built once by gc_finalize (gc_api.hip encode_wf16): [32-column tile][k16 step][hi | lo][lane][8 halfs]
+//   WF16  weights, built once by gc_finalize (gc_weights.hip encode_wf16): [32-column tile][k16 step][hi | lo][lane][8 halfs]
 //   AF16  activations, written by their producers: [32-row tile][k16 step][hi | lo][lane][8 halfs]  (hi only when the
 //         activation is exact fp16: "fp16 node features", the A16 kernel variants)
 // Inside a k16 step lane (r, hk) (r = lane & 31 = row / column of the tile, hk = lane >> 5) holds the 8 values
