@@ -100,6 +100,13 @@ SIGNATURES = {
     "gc_loss_resident": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p]),
     "gc_download_denoised": (ctypes.c_int, [_hp, _f32p]),
     "gc_loss": (ctypes.c_int, [_hp, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "gc_ens_reserve": (ctypes.c_int, [_hp, ctypes.c_int32]),
+    "gc_ens_set_node_weight": (ctypes.c_int, [_hp, _f32p]),
+    "gc_ens_push": (ctypes.c_int, [_hp, ctypes.c_int32, _hp]),
+    "gc_ens_push_host": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
+    "gc_ens_score": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
+                                    ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_download_fields": (ctypes.c_int, [_hp, _f32p, _f32p]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -188,6 +195,7 @@ class NativeDenoiser:
     self.num_grid_nodes = None
     self.num_mesh_nodes = None
     self._loss_groups = 0                      # groups of the loss weights this object handed to the handle
+    self._ens_members = 0                      # slots of the member store this object reserved on the handle
 
   # -- plumbing ------------------------------------------------------------------------------
   def _check(self, rc):
@@ -489,6 +497,53 @@ class NativeDenoiser:
     self._check(self._lib.gc_loss(self._h, _ptr(c, _f32p), _ptr(t, _f32p), _ptr(z, _f32p), _ptr(sg, _f32p),
                                   _ptr(loss, _f32p), _ptr(per_group, _f32p), None if den is None else _ptr(den, _f32p)))
     return (loss, per_group, den) if want_denoised else (loss, per_group)
+
+  # -- ensemble verification (scored on the device) -------------------------------------------------
+  def ens_reserve(self, n_members: int) -> None:
+    """A store of `n_members` (2..64) member fields on the handle; empties an earlier one (gc_ens_reserve)."""
+    self._check(self._lib.gc_ens_reserve(self._h, int(n_members)))
+    self._ens_members = int(n_members)
+
+  def ens_set_node_weight(self, node_weight) -> None:
+    w = _f32(node_weight)
+    if w.shape != (self.num_grid_nodes,):
+      raise ValueError(f"node_weight must have shape ({self.num_grid_nodes},)")
+    self._check(self._lib.gc_ens_set_node_weight(self._h, _ptr(w, _f32p)))
+
+  def ens_push(self, slot: int, src: Optional["NativeDenoiser"] = None) -> None:
+    """Slot <- the last sample of `src` (None: of this handle), device to device (gc_ens_push)."""
+    self._check(self._lib.gc_ens_push(self._h, int(slot), None if src is None else src._h))  # pylint: disable=protected-access
+
+  def ens_push_host(self, slot: int, field) -> None:
+    x = _f32(field)
+    if x.shape != self._shape_out():
+      raise ValueError(f"field must be {self._shape_out()}, got {x.shape}")
+    self._check(self._lib.gc_ens_push_host(self._h, int(slot), _ptr(x, _f32p)))
+
+  def ens_score(self, truth=None, want_fields: bool = False):
+    """-> (sums [B, c_out, 6] float64, rank_hist [B, c_out, M + 1] uint64): the raw, additive sums of gc_ens_score
+    (`verification.EnsembleScores` derives the scores).  `truth` [G, B, c_out], or None = the truth uploaded last."""
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    t = None
+    if truth is not None:
+      t = _f32(truth)
+      if t.shape != self._shape_out():
+        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    B, C = self.cfg.batch, self.cfg.c_out
+    sums = np.empty((6, B, C), dtype=np.float64)
+    hist = np.empty((B, C, self._ens_members + 1), dtype=np.uint64)
+    self._check(self._lib.gc_ens_score(self._h, None if t is None else _ptr(t, _f32p), int(bool(want_fields)),
+                                       _ptr(sums, ctypes.POINTER(ctypes.c_double)),
+                                       _ptr(hist, ctypes.POINTER(ctypes.c_uint64))))
+    return np.ascontiguousarray(np.moveaxis(sums, 0, -1)), hist
+
+  def ens_download_fields(self):
+    """(mean, variance) [G, B, c_out] of the last `ens_score(want_fields=True)` (gc_ens_download_fields)."""
+    mean = np.empty(self._shape_out(), dtype=np.float32)
+    var = np.empty(self._shape_out(), dtype=np.float32)
+    self._check(self._lib.gc_ens_download_fields(self._h, _ptr(mean, _f32p), _ptr(var, _f32p)))
+    return mean, var
 
   # -- ensemble exchange (RCCL inside the library) -------------------------------------------------
   def comm_init(self, unique_id: bytes, rank: int, world_size: int) -> None:

@@ -8,20 +8,9 @@ using namespace gci;
 
 namespace {
 
-thread_local std::string g_create_error;
-
 // Entry points that overwrite the initial noise while a sample's domain check is pending write the OTHER buffer.
 void protect_pending_noise(gc_handle* h) {
   if (h->guard_pending && h->d_noise == h->last_noise) std::swap(h->d_noise, h->d_noise_alt);
-}
-
-// Asynchronous H2D through a handle-owned pinned buffer: the caller's buffer is free on return.
-int staged_upload(gc_handle* h, float* pinned, float* dev, const float* src, size_t count) {
-  GC_HIP(h, hipEventSynchronize(h->ev_pin));       // the previous copy out of a staging buffer is done
-  std::memcpy(pinned, src, count * sizeof(float));
-  GC_HIP(h, hipMemcpyAsync(dev, pinned, count * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  GC_HIP(h, hipEventRecord(h->ev_pin, h->stream));
-  return GC_OK;
 }
 
 int check_ready(gc_handle* h) {
@@ -87,29 +76,6 @@ Rccl& rccl() {
       return GC_ERR_COMM;                                                                   \
     }                                                                                       \
   } while (0)
-
-// No C++ exception crosses the C ABI: every entry point runs inside this wrapper.
-template <typename F>
-int guarded(gc_handle* h, F&& f) noexcept {
-  const char* what = "unknown C++ exception";
-  try {
-    return f();
-  } catch (const std::bad_alloc&) {
-    what = "out of host memory (std::bad_alloc)";
-  } catch (const std::exception& e) {
-    try {
-      (h ? h->err : g_create_error) = std::string("C++ exception: ") + e.what();
-      return GC_ERR_INTERNAL;
-    } catch (...) {
-    }
-  } catch (...) {
-  }
-  try {
-    (h ? h->err : g_create_error) = what;
-  } catch (...) {
-  }
-  return GC_ERR_INTERNAL;
-}
 
 }  // namespace
 
@@ -228,13 +194,15 @@ static void destroy_impl(gc_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   drop_sample_graphs(h);
   if (h->comm) (void)rccl().CommDestroy(h->comm);
-  for (std::vector<void*>* l : {&h->allocs, &h->weight_allocs, &h->cache_allocs}) free_allocs(l);
+  for (std::vector<void*>* l : {&h->allocs, &h->weight_allocs, &h->cache_allocs, &h->ens_allocs}) free_allocs(l);
   if (h->d_nonfinite) (void)hipFree(h->d_nonfinite);
   for (void* p : {(void*)h->h_nonfinite, (void*)h->pin_cond, (void*)h->pin_noise, (void*)h->pin_forc,
                   (void*)h->pin_lguard})
     if (p) (void)hipHostFree(p);
   if (h->ev_pin) (void)hipEventDestroy(h->ev_pin);
   if (h->ev_stash) (void)hipEventDestroy(h->ev_stash);
+  for (hipEvent_t e : {h->ev_ens_free, h->ev_ens_done, h->ev_ens0, h->ev_ens1})
+    if (e) (void)hipEventDestroy(e);
   if (h->stream2) {
     (void)hipStreamSynchronize(h->stream2);
     (void)hipStreamDestroy(h->stream2);
@@ -887,7 +855,11 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "graph_captures") *value = h->graph_captures;
   else if (n == "loss_evaluations") *value = h->loss_evaluations;
   else if (n == "loss_device_us") *value = h->loss_device_us;
-  else if (n == "device_allocations") *value = (int64_t)(h->allocs.size() + h->weight_allocs.size() + h->cache_allocs.size());
+  else if (n == "ens_scores") *value = h->ens_scores;
+  else if (n == "ens_score_device_us") *value = h->ens_score_device_us;
+  else if (n == "ens_invalid_points") *value = h->ens_invalid_points;
+  else if (n == "device_allocations")
+    *value = (int64_t)(h->allocs.size() + h->weight_allocs.size() + h->cache_allocs.size() + h->ens_allocs.size());
   else return fail(h, GC_ERR_INVALID_ARGUMENT, "unknown counter: " + n);
   return GC_OK;
   });

@@ -1,0 +1,398 @@
+// Ensemble verification on the device (include/gencast_hip.h, gc_ens_*): a store of M member fields on the handle and
+// one scoring pass over it -- CRPS terms, error and spread of the ensemble mean, the rank histogram, and on request
+// the mean and variance fields.  Kernels and their host code live together here; DESIGN.md section 8c has the
+// definitions and the error bound the tests assert.
+//
+// Per point (g, b, c), from the float32 members x_0 .. x_{M-1} and the truth y, in double:
+//   m  = (sum_i x_i) / M                       ascending slot order
+//   s2 = sum_i (x_i - m)^2 / (M - 1)           two passes, ascending slot order
+//   ae = (sum_i |x_i - y|) / M
+//   d  = sum_{i<j} |x_i - x_j| / (M (M-1) / 2)
+//   r  = #{i : x_i < y}                        ties are not randomised: a member equal to y is not below it
+// A point counts when y and all M members are finite.  Per column (b, c), over the counted nodes, w = node weight:
+//   S0 = sum w, S1 = sum w (m - y), S2 = sum w (m - y)^2, S3 = sum w s2, S4 = sum w ae, S5 = sum w d,  H[r] += 1
+// No atomics on floats: every partial has one writer and every sum a fixed order, so the result does not depend on how
+// the launch was scheduled.  The rank counts are integers; their LDS atomics commute.
+#include "gc_handle.h"
+
+// the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
+#pragma clang fp contract(off)
+
+namespace gc {
+
+constexpr int kEnsMinMembers = 2, kEnsMaxMembers = 64;
+
+// Thread layout of gc_loss_reduce_kernel: a grid node's B rows are W = B c_out consecutive floats; grid.y cuts W into
+// column tiles of at most 256; inside a tile of wt columns thread t owns column t % wt (ONE accumulator set) of node
+// lane t / wt, q = 256 / wt lanes; block x walks the contiguous node range [x per, (x + 1) per) in steps of q.
+// The M values of a point are read once from HBM (M loads of stride `field`, each coalesced across the wave) into the
+// thread's own column of an LDS tile [M][256]; the second pass and the O(M^2) pair loop read them from there.
+// Dynamic LDS: float[M][256], then unsigned[wt][M + 1] rank counts of the block.
+// Out, as plain stores: part[block x][6][W] (double), hpart[block x][W][M + 1], ipart[block x][tile] (points skipped).
+__global__ __launch_bounds__(256) void gc_ens_score_kernel(const float* __restrict__ mem, size_t field, int M,
+                                                            const float* __restrict__ truth,
+                                                            const float* __restrict__ node_w, int G, int W, int per,
+                                                            double* __restrict__ part, unsigned* __restrict__ hpart,
+                                                            unsigned* __restrict__ ipart, float* __restrict__ mean,
+                                                            float* __restrict__ var) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ens_lds[];
+  __shared__ double lane_sum[256];
+  __shared__ unsigned skipped;
+  float* const tile = reinterpret_cast<float*>(ens_lds);
+  unsigned* const hist = reinterpret_cast<unsigned*>(tile + (size_t)M * 256);
+  const int col0 = blockIdx.y * 256;
+  const int wt = min(256, W - col0);
+  const int q = 256 / wt;
+  const int tid = threadIdx.x;
+  const int lane = tid / wt;
+  const int cl = tid - lane * wt;
+  const int col = col0 + cl;
+  const int bins = M + 1;
+  for (int i = tid; i < wt * bins; i += 256) hist[i] = 0u;
+  if (tid == 0) skipped = 0u;
+  __syncthreads();
+  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  unsigned inv = 0;
+  if (lane < q) {
+    float* const my = tile + tid;                  // x_k at my[k * 256]: a bank of its own for every lane
+    const double dM = (double)M, pairs = 0.5 * dM * (dM - 1.0);
+    const int n_end = min(G, (int)(blockIdx.x + 1) * per);
+    for (int n = blockIdx.x * per + lane; n < n_end; n += q) {
+      const size_t i = (size_t)n * W + col;
+      const float y = truth[i];
+      bool xfin = true;
+      double sum = 0.0;
+#pragma unroll 4
+      for (int k = 0; k < M; ++k) {
+        const float x = mem[(size_t)k * field + i];
+        my[k * 256] = x;
+        xfin = xfin && isfinite(x);
+        sum += (double)x;
+      }
+      const double m = sum / dM;
+      const bool ok = xfin && isfinite(y);
+      double s2 = 0.0, ae = 0.0;
+      int r = 0;
+      if (xfin) {
+        const double yd = (double)y;
+#pragma unroll 4
+        for (int k = 0; k < M; ++k) {
+          const float x = my[k * 256];
+          const double dx = (double)x - m;
+          s2 += dx * dx;
+          ae += fabs((double)x - yd);
+          r += x < y ? 1 : 0;
+        }
+        s2 /= dM - 1.0;
+      }
+      if (mean) {
+        mean[i] = xfin ? (float)m : __builtin_nanf("");
+        var[i] = xfin ? (float)s2 : __builtin_nanf("");
+      }
+      if (!ok) {
+        ++inv;
+        continue;
+      }
+      double d0 = 0.0, d1 = 0.0;                    // two chains: the pair sum has no prescribed order
+      for (int a = 0; a + 1 < M; ++a) {
+        const double xa = (double)my[a * 256];
+        int b = a + 1;
+        for (; b + 1 < M; b += 2) {
+          d0 += fabs(xa - (double)my[b * 256]);
+          d1 += fabs(xa - (double)my[(b + 1) * 256]);
+        }
+        if (b < M) d0 += fabs(xa - (double)my[b * 256]);
+      }
+      const double w = (double)node_w[n], e = m - (double)y;
+      s[0] += w;
+      s[1] += w * e;
+      s[2] += w * (e * e);
+      s[3] += w * s2;
+      s[4] += w * (ae / dM);
+      s[5] += w * ((d0 + d1) / pairs);
+      atomicAdd(&hist[cl * bins + r], 1u);
+    }
+  }
+  if (inv) atomicAdd(&skipped, inv);
+  // the q lanes of a column, added in lane order
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    lane_sum[tid] = s[k];
+    __syncthreads();
+    if (tid < wt) {
+      double t = lane_sum[tid];
+      for (int l = 1; l < q; ++l) t += lane_sum[l * wt + tid];
+      part[((size_t)blockIdx.x * 6 + k) * W + col] = t;
+    }
+    __syncthreads();
+  }
+  unsigned* const hp = hpart + ((size_t)blockIdx.x * W + col0) * bins;
+  for (int i = tid; i < wt * bins; i += 256) hp[i] = hist[i];
+  if (tid == 0) ipart[(size_t)blockIdx.x * gridDim.y + blockIdx.y] = skipped;
+}
+
+// One workgroup per column tile.  The blocks of a column are added the way gc_loss_finish_kernel adds them: thread t
+// owns column t % wt and the contiguous block range of lane t / wt, the lanes are combined in lane order -- a fixed
+// order, ascending in the block index.  sums [6][W]; hist [W][M + 1] then one word: the points the call skipped.
+__global__ __launch_bounds__(256) void gc_ens_finish_kernel(const double* __restrict__ part,
+                                                             const unsigned* __restrict__ hpart,
+                                                             const unsigned* __restrict__ ipart, int blocks, int W, int M,
+                                                             double* __restrict__ sums,
+                                                             unsigned long long* __restrict__ hist) {
+  __shared__ double lane_sum[256];
+  __shared__ unsigned long long skipped;
+  const int col0 = blockIdx.x * 256;
+  const int wt = min(256, W - col0);
+  const int q = 256 / wt;
+  const int tid = threadIdx.x;
+  const int lane = tid / wt;
+  const int col = col0 + (tid - lane * wt);
+  const int bper = (blocks + q - 1) / q;
+  const int bins = M + 1;
+  if (tid == 0) skipped = 0ull;
+  for (int k = 0; k < 6; ++k) {
+    double t = 0.0;
+    if (lane < q) {
+      const int b_end = min(blocks, (lane + 1) * bper);
+#pragma unroll 8
+      for (int b = lane * bper; b < b_end; ++b) t += part[((size_t)b * 6 + k) * W + col];
+    }
+    lane_sum[tid] = t;
+    __syncthreads();
+    if (tid < wt) {
+      double tot = lane_sum[tid];
+      for (int l = 1; l < q; ++l) tot += lane_sum[l * wt + tid];
+      sums[(size_t)k * W + col] = tot;
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < wt * bins; e += 256) {
+    unsigned long long t = 0ull;
+    for (int b = 0; b < blocks; ++b) t += hpart[((size_t)b * W + col0) * bins + e];
+    hist[(size_t)col0 * bins + e] = t;
+  }
+  if (blockIdx.x == 0) {
+    unsigned long long t = 0ull;
+    for (int i = tid; i < blocks * (int)gridDim.x; i += 256) t += ipart[i];
+    if (t) atomicAdd(&skipped, t);
+    __syncthreads();
+    if (tid == 0) hist[(size_t)W * bins] = skipped;
+  }
+}
+
+static size_t ens_score_lds(int M, int W) { return (size_t)M * 256 * sizeof(float) + (size_t)std::min(256, W) * (M + 1) * sizeof(unsigned); }
+
+static hipError_t launch_ens_score(hipStream_t s, const float* mem, size_t field, int M, const float* truth, const float* node_w,
+                                   int G, int B, int c_out, double* part, unsigned* hpart, unsigned* ipart, float* mean, float* var) {
+  const int W = B * c_out;
+  const int blocks = loss_reduce_blocks(G, B, c_out);
+  const int per = (G + blocks - 1) / blocks;
+  const size_t lds = ens_score_lds(M, W);
+  if (lds > 64 * 1024) {                           // (a per-device property of the kernel; setting it again is harmless)
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gc_ens_score_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(gc_ens_score_kernel, dim3(blocks, (W + 255) / 256), dim3(256), lds, s, mem, field, M, truth, node_w, G, W,
+                     per, part, hpart, ipart, mean, var);
+  return hipGetLastError();
+}
+
+static hipError_t launch_ens_finish(hipStream_t s, const double* part, const unsigned* hpart, const unsigned* ipart, int blocks,
+                                    int W, int M, double* sums, unsigned long long* hist) {
+  hipLaunchKernelGGL(gc_ens_finish_kernel, dim3((W + 255) / 256), dim3(256), 0, s, part, hpart, ipart, blocks, W, M, sums, hist);
+  return hipGetLastError();
+}
+
+}  // namespace gc
+
+using namespace gci;
+
+namespace {
+
+size_t ens_field(const gc_handle* h) { return (size_t)h->hg.G * h->cfg.batch * h->cfg.c_out; }
+
+// the entries that need G only: no weights, no gc_finalize
+int ens_ready(gc_handle* h, bool need_store) {
+  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (need_store && h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
+  return GC_OK;
+}
+
+int ens_slot(gc_handle* h, int32_t slot) {
+  if (slot < 0 || slot >= h->ens_members) return fail(h, GC_ERR_INVALID_ARGUMENT, "slot outside [0, n_members)");
+  return GC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gc_ens_reserve(gc_handle* h, int32_t n_members) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ens_ready(h, false);
+  if (rc) return rc;
+  if (n_members < gc::kEnsMinMembers || n_members > gc::kEnsMaxMembers)
+    return fail(h, GC_ERR_UNSUPPORTED, "n_members must be in 2..64");
+  GC_HIP(h, hipSetDevice(h->device));
+  GC_HIP(h, hipStreamSynchronize(h->stream));      // every push into the old store has landed (pushes from other handles are ordered into this stream)
+  free_allocs(&h->ens_allocs);
+  h->ens_members = 0;
+  h->ens_filled.clear();
+  h->has_ens_fields = false;
+  h->d_ens = nullptr;
+  const gc_config& c = h->cfg;
+  const int G = h->hg.G, W = c.batch * c.c_out, M = n_members;
+  const size_t blocks = (size_t)gc::loss_reduce_blocks(G, c.batch, c.c_out), tiles = (size_t)(W + 255) / 256;
+  if ((rc = dev_alloc(h, &h->d_ens, (size_t)M * ens_field(h), &h->ens_allocs)) ||
+      (rc = dev_alloc(h, &h->d_ens_part, blocks * 6 * W, &h->ens_allocs)) ||
+      (rc = dev_alloc(h, &h->d_ens_hpart, blocks * W * (M + 1) + blocks * tiles, &h->ens_allocs)) ||
+      (rc = dev_alloc(h, &h->d_ens_sums, (size_t)6 * W, &h->ens_allocs)) ||
+      (rc = dev_alloc(h, &h->d_ens_hist, (size_t)W * (M + 1) + 1, &h->ens_allocs))) {
+    free_allocs(&h->ens_allocs);
+    return rc;
+  }
+  for (hipEvent_t* e : {&h->ev_ens_free, &h->ev_ens_done})
+    if (!*e) GC_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
+  for (hipEvent_t* e : {&h->ev_ens0, &h->ev_ens1})
+    if (!*e) GC_HIP(h, hipEventCreate(e));
+  h->ens_filled.assign((size_t)M, 0);
+  h->ens_members = M;
+  return GC_OK;
+  });
+}
+
+int gc_ens_set_node_weight(gc_handle* h, const float* w) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ens_ready(h, false);
+  if (rc) return rc;
+  if (!w) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  GC_HIP(h, hipSetDevice(h->device));
+  if (!h->d_ens_w && (rc = dev_alloc(h, &h->d_ens_w, (size_t)h->hg.G))) return rc;
+  // on the handle's stream (ordered behind whatever still runs there), then waited for: the array is the caller's again
+  GC_HIP(h, hipMemcpyAsync(h->d_ens_w, w, (size_t)h->hg.G * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  GC_HIP(h, hipStreamSynchronize(h->stream));
+  h->has_ens_w = true;
+  return GC_OK;
+  });
+}
+
+int gc_ens_push(gc_handle* h, int32_t slot, gc_handle* src) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ens_ready(h, true);
+  if (rc || (rc = ens_slot(h, slot))) return rc;
+  if (!src) src = h;
+  if (src->device != h->device) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle is on another device");
+  if (!src->has_graph || src->hg.G != h->hg.G || src->cfg.batch != h->cfg.batch || src->cfg.c_out != h->cfg.c_out)
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle has other dimensions (G, batch, c_out)");
+  if (!src->finalized || !src->has_sample) return fail(h, GC_ERR_STATE, "no sample on the source handle (gc_sample_resident)");
+  GC_HIP(h, hipSetDevice(h->device));
+  if ((rc = resolve_guard(src))) {                 // the member is the CHECKED sample (exact-f32 re-run included)
+    if (src != h) h->err = "source handle: " + src->err;
+    return rc;
+  }
+  float* const dst = h->d_ens + (size_t)slot * ens_field(h);
+  const size_t bytes = ens_field(h) * sizeof(float);
+  if (src == h) {
+    GC_HIP(h, hipMemcpyAsync(dst, h->d_sx, bytes, hipMemcpyDeviceToDevice, h->stream));
+  } else {
+    // the copy runs on the SOURCE's stream, in front of that handle's next sample; the two streams are ordered by
+    // events, both ways: the store is no longer being read when the copy starts, and is complete before this
+    // handle's stream goes on
+    GC_HIP(h, hipEventRecord(h->ev_ens_free, h->stream));
+    GC_HIP(h, hipStreamWaitEvent(src->stream, h->ev_ens_free, 0));
+    GC_HIP(h, hipMemcpyAsync(dst, src->d_sx, bytes, hipMemcpyDeviceToDevice, src->stream));
+    GC_HIP(h, hipEventRecord(h->ev_ens_done, src->stream));
+    GC_HIP(h, hipStreamWaitEvent(h->stream, h->ev_ens_done, 0));
+  }
+  h->ens_filled[(size_t)slot] = 1;
+  return GC_OK;
+  });
+}
+
+int gc_ens_push_host(gc_handle* h, int32_t slot, const float* field) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ens_ready(h, true);
+  if (rc || (rc = ens_slot(h, slot))) return rc;
+  if (!field) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  GC_HIP(h, hipSetDevice(h->device));
+  if ((rc = staged_upload(h, h->pin_noise, h->d_ens + (size_t)slot * ens_field(h), field, ens_field(h)))) return rc;
+  h->ens_filled[(size_t)slot] = 1;
+  return GC_OK;
+  });
+}
+
+int gc_ens_score(gc_handle* h, const float* truth, int32_t want_fields, double* sums, uint64_t* rank_hist) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ens_ready(h, true);
+  if (rc) return rc;
+  if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  const int M = h->ens_members;
+  for (int i = 0; i < M; ++i)
+    if (!h->ens_filled[(size_t)i]) return fail(h, GC_ERR_STATE, "member slot " + std::to_string(i) + " has not been pushed");
+  if (!h->has_ens_w) return fail(h, GC_ERR_STATE, "no node weights (gc_ens_set_node_weight)");
+  if (!truth && !h->has_ens_truth) return fail(h, GC_ERR_STATE, "no truth on the device (pass one to gc_ens_score)");
+  GC_HIP(h, hipSetDevice(h->device));
+  const gc_config& c = h->cfg;
+  const int G = h->hg.G, B = c.batch, W = B * c.c_out;
+  const size_t field = ens_field(h);
+  if (truth) {
+    if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
+    if ((rc = staged_upload(h, h->pin_noise, h->d_ens_truth, truth, field))) return rc;
+    h->has_ens_truth = true;
+  }
+  if (want_fields && !h->d_ens_mean) {
+    if ((rc = dev_alloc(h, &h->d_ens_mean, field)) || (rc = dev_alloc(h, &h->d_ens_var, field))) return rc;
+  }
+  hipStream_t s = h->stream;
+  const int blocks = gc::loss_reduce_blocks(G, B, c.c_out);
+  unsigned* const ipart = h->d_ens_hpart + (size_t)blocks * W * (M + 1);
+  GC_HIP(h, hipEventRecord(h->ev_ens0, s));
+  if ((rc = launch(h, gc::KC_PACK, [&] {
+         return gc::launch_ens_score(s, h->d_ens, field, M, h->d_ens_truth, h->d_ens_w, G, B, c.c_out, h->d_ens_part,
+                                     h->d_ens_hpart, ipart, want_fields ? h->d_ens_mean : nullptr,
+                                     want_fields ? h->d_ens_var : nullptr);
+       })))
+    return rc;
+  if ((rc = launch(h, gc::KC_PACK, [&] {
+         return gc::launch_ens_finish(s, h->d_ens_part, h->d_ens_hpart, ipart, blocks, W, M, h->d_ens_sums, h->d_ens_hist);
+       })))
+    return rc;
+  GC_HIP(h, hipEventRecord(h->ev_ens1, s));
+  if (want_fields) h->has_ens_fields = true;
+  std::vector<unsigned long long> hist((size_t)W * (M + 1) + 1);
+  GC_HIP(h, hipMemcpyAsync(sums, h->d_ens_sums, (size_t)6 * W * sizeof(double), hipMemcpyDeviceToHost, s));
+  GC_HIP(h, hipMemcpyAsync(hist.data(), h->d_ens_hist, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  GC_HIP(h, hipStreamSynchronize(s));
+  float ms = 0.f;
+  GC_HIP(h, hipEventElapsedTime(&ms, h->ev_ens0, h->ev_ens1));
+  h->ens_score_device_us = (int64_t)(ms * 1000.0f);
+  h->ens_invalid_points = (int64_t)hist.back();
+  ++h->ens_scores;
+  if (rank_hist)
+    for (size_t i = 0; i + 1 < hist.size(); ++i) rank_hist[i] = hist[i];
+  return GC_OK;
+  });
+}
+
+int gc_ens_download_fields(gc_handle* h, float* mean, float* variance) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ens_ready(h, true);
+  if (rc) return rc;
+  if (!h->has_ens_fields) return fail(h, GC_ERR_STATE, "no mean / variance fields on the device (gc_ens_score with want_fields)");
+  GC_HIP(h, hipSetDevice(h->device));
+  const size_t bytes = ens_field(h) * sizeof(float);
+  if (mean) GC_HIP(h, hipMemcpyAsync(mean, h->d_ens_mean, bytes, hipMemcpyDeviceToHost, h->stream));
+  if (variance) GC_HIP(h, hipMemcpyAsync(variance, h->d_ens_var, bytes, hipMemcpyDeviceToHost, h->stream));
+  GC_HIP(h, hipStreamSynchronize(h->stream));
+  return GC_OK;
+  });
+}
+
+}  // extern "C"

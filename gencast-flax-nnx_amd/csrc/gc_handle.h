@@ -1,6 +1,6 @@
 // Internals shared by the host translation units of libgencast_hip.so: the handle, the device-side weight layout,
 // the route of a forward, and the allocation / launch helpers.  gc_weights.hip lays the weights out, gc_forward.hip
-// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI.
+// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* entries).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -203,6 +203,22 @@ struct gc_handle {
   unsigned* pin_lguard = nullptr;                                             // domain-guard counter as it stood after each evaluation
   int64_t loss_evaluations = 0, loss_device_us = 0;
 
+  // ensemble verification (gc_ens_*, gc_ensemble.hip): a store of M member fields and the sums scored from it
+  std::vector<void*> ens_allocs;                 // everything sized by M: freed and replaced by gc_ens_reserve
+  int ens_members = 0;                           // M (0: nothing reserved)
+  std::vector<char> ens_filled;                  // per slot: pushed since the last gc_ens_reserve
+  float* d_ens = nullptr;                        // [M][G, B, c_out] member fields
+  double* d_ens_part = nullptr;                  // [blocks][6][B c_out] per-block column sums
+  unsigned* d_ens_hpart = nullptr;               // [blocks][B c_out][M + 1] per-block rank counts, then [blocks][tiles] skipped points
+  double* d_ens_sums = nullptr;                  // [6][B][c_out]
+  unsigned long long* d_ens_hist = nullptr;      // [B][c_out][M + 1], then the skipped points of the call
+  float *d_ens_w = nullptr, *d_ens_truth = nullptr;            // [G], [G, B, c_out]: made once, kept across reserves
+  float *d_ens_mean = nullptr, *d_ens_var = nullptr;           // [G, B, c_out] each: made by the first call that asks for fields
+  bool has_ens_w = false, has_ens_truth = false, has_ens_fields = false;
+  hipEvent_t ev_ens_free = nullptr, ev_ens_done = nullptr;     // stream order of a push from another handle
+  hipEvent_t ev_ens0 = nullptr, ev_ens1 = nullptr;             // brackets of the last scoring call
+  int64_t ens_scores = 0, ens_score_device_us = 0, ens_invalid_points = 0;
+
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {
     std::vector<float> sigmas;
@@ -318,6 +334,41 @@ int launch(gc_handle* h, int cls, F&& f) {
     h->prof_used += 2;
   }
   return GC_OK;
+}
+
+// what gc_last_error(nullptr) returns: the failure of an entry point that has no handle yet (gc_create)
+inline thread_local std::string g_create_error;
+
+// Asynchronous H2D through a handle-owned pinned buffer: the caller's buffer is free on return.
+inline int staged_upload(gc_handle* h, float* pinned, float* dev, const float* src, size_t count) {
+  GC_HIP(h, hipEventSynchronize(h->ev_pin));       // the previous copy out of a staging buffer is done
+  std::memcpy(pinned, src, count * sizeof(float));
+  GC_HIP(h, hipMemcpyAsync(dev, pinned, count * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  GC_HIP(h, hipEventRecord(h->ev_pin, h->stream));
+  return GC_OK;
+}
+
+// No C++ exception crosses the C ABI: every entry point runs inside this wrapper.
+template <typename F>
+int guarded(gc_handle* h, F&& f) noexcept {
+  const char* what = "unknown C++ exception";
+  try {
+    return f();
+  } catch (const std::bad_alloc&) {
+    what = "out of host memory (std::bad_alloc)";
+  } catch (const std::exception& e) {
+    try {
+      (h ? h->err : g_create_error) = std::string("C++ exception: ") + e.what();
+      return GC_ERR_INTERNAL;
+    } catch (...) {
+    }
+  } catch (...) {
+  }
+  try {
+    (h ? h->err : g_create_error) = what;
+  } catch (...) {
+  }
+  return GC_ERR_INTERNAL;
 }
 
 // gc_weights.hip

@@ -14,7 +14,7 @@ from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
-from . import datasets
+from . import datasets, verification
 from .denoiser import Denoiser
 from .sampler import Sampler
 
@@ -68,6 +68,22 @@ class EnsembleSampler:
 
   def __call__(self, inputs, targets_template, forcings, num_members: int
                ) -> List[Tuple[int, datasets.Dataset]]:
+    return self._run(inputs, targets_template, forcings, num_members, None)
+
+  def scores(self, inputs, targets, forcings, num_members: int, *, fields: bool = False):
+    """Runs the members as `__call__` does and scores them against `targets` on the device: every finished member
+    goes into lane 0's member store by a device-to-device copy (`ens_push(slot, src=lane)`), none is downloaded,
+    and one `ens_score` reduces them.  Returns `verification.EnsembleScores` in the units of `targets` (NaN targets
+    are skipped point by point); with `fields=True` also the ensemble mean and variance as Datasets shaped like
+    `targets` (xarray in, xarray out).  Node weights: `verification.node_weights(targets)`.
+    One rank only: the pair term of the CRPS needs all members at every point."""
+    if self.world_size > 1:
+      raise ValueError("EnsembleSampler.scores needs all members on one rank (world_size == 1): bring the other "
+                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    return self._run(inputs, targets, forcings, num_members, bool(fields))
+
+  def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool]):
+    """`score_fields` None: members come back as Datasets (`__call__`); else they are scored (`scores`)."""
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
     cond, grid_shape, slots = self._denoiser.init_for(inputs, template, forcings)
@@ -93,6 +109,10 @@ class EnsembleSampler:
       for lane in lanes[1:]:
         lane.set_noisy_slots(slots)
         lane.upload_cond_dev(ptr)                          # device-to-device, on the lane's own stream
+    scoring = score_fields is not None
+    if scoring:
+      native.ens_reserve(num_members)
+      native.ens_set_node_weight(verification.node_weights(template))
     out = []
     for g0 in range(0, len(mine), len(lanes)):
       group = mine[g0:g0 + len(lanes)]
@@ -100,6 +120,18 @@ class EnsembleSampler:
         lane.upload_noise(self.member_noise(m, shape, template))
         lane.sample_resident(sigmas, skip_dead_call=True, want_stats=False)
       for lane, m in zip(lanes, group):
-        out.append((m, datasets.like_inputs(Denoiser.unpack_outputs(lane.download_sample(), grid_shape, template),
-                                            targets_template, inputs, forcings)))
-    return out
+        if scoring:
+          native.ens_push(m, src=lane)
+        else:
+          out.append((m, datasets.like_inputs(Denoiser.unpack_outputs(lane.download_sample(), grid_shape, template),
+                                              targets_template, inputs, forcings)))
+    if not scoring:
+      return out
+    truth = np.transpose(datasets.dataset_to_stacked(template, template.sizes), (1, 2, 0, 3)).reshape(shape)
+    sums, hist = native.ens_score(truth, want_fields=score_fields)
+    result = verification.EnsembleScores(sums, hist, num_members)
+    if not score_fields:
+      return result
+    given = (targets_template, inputs, forcings)
+    return (result,) + tuple(datasets.like_inputs(Denoiser.unpack_outputs(f, grid_shape, template), *given)
+                             for f in native.ens_download_fields())

@@ -88,6 +88,18 @@ class GenCast:
       return self._sampler(inputs, targets_template, forcings, rngs=rng, **optional_kwargs)
     return predictor_fn
 
+  def ensemble_scores(self, inputs, targets, forcings=None, *, num_members, rngs=0, concurrent_members=1, fields=False):
+    """Samples `num_members` (2..64) members for (inputs, forcings) and scores them against `targets` on the GPU:
+    `verification.EnsembleScores` (CRPS, RMSE of the ensemble mean, spread, rank histogram, per batch member and
+    channel, latitude-weighted), with `fields=True` also the ensemble mean and variance as Datasets.  No member
+    leaves the device.  `rngs`: the base seed of the members' noise streams (`ensemble.member_seed`), so member m
+    is the member m of `EnsembleSampler(base_seed=rngs)`; `concurrent_members` as there."""
+    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
+    if not isinstance(rngs, (int, np.integer)):
+      rngs = Sampler.seed_from(rngs)
+    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    return runner.scores(inputs, targets, forcings, num_members, fields=fields)
+
   # -- the diffusion objective, forward only -----------------------------------------------------------------
   def _denoising_eval(self, inputs, targets, forcings, rngs, noise_levels, noise, num_noise_draws, per_variable_weights):
     """-> (loss [K, B], per_variable [K, B, V], names, D [G, B, c_out] of the last draw, grid_shape, targets Dataset)."""

@@ -106,6 +106,21 @@ class NaNCleaner:
       preds = self._maybe_reintroduce_nans(original, preds)
     return datasets.loss_like_inputs(*loss, *given), datasets.like_inputs(preds, *given)
 
+  def ensemble_scores(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """Inputs and forcings are cleaned; the targets pass through unchanged: their NaNs (land points of the cleaned
+    variable) are the points the device skips, so the scores are over the valid points only."""
+    given = (targets, inputs, forcings)
+    inputs = datasets.as_dataset(inputs)
+    forcings = None if forcings is None else datasets.as_dataset(forcings)
+    if self._var_to_clean in inputs.keys():
+      inputs = self._clean(inputs)
+    if forcings is not None and self._var_to_clean in forcings.keys():
+      forcings = self._clean(forcings)
+    out = self.predictor.ensemble_scores(inputs, datasets.as_dataset(targets), forcings, **kwargs)
+    if not isinstance(out, tuple):
+      return out
+    return (out[0],) + tuple(datasets.like_inputs(datasets.as_dataset(f), *given) for f in out[1:])
+
   def loss(self, *args, **kwargs):
     raise NotImplementedError("training (loss) is outside the sampling hot path; the forward-only value of the "
                               "objective is denoising_loss / denoising_loss_and_predictions")

@@ -178,6 +178,29 @@ class InputsAndResiduals:
     return datasets.loss_like_inputs(*loss, *given), datasets.like_inputs(preds, *given)
 
 
+  def ensemble_scores(self, inputs, targets, forcings=None, **kwargs):
+    """`ensemble_scores` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets,
+    returned in physical units: the member-to-physical map is x -> a x + b per channel (a: the residual scale of a
+    variable that is also an input, else its plain scale; b cancels in every score), so the raw sums are rescaled
+    (`EnsembleScores.scaled`), nothing is recomputed.  With `fields=True` the mean is un-normalised like a
+    prediction (last input frame added back for residual variables) and the variance is multiplied by a^2."""
+    given = (targets, inputs, forcings)
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    tds = datasets.as_dataset(targets)
+    scale = []
+    for name, _, _ in datasets.channel_layout(tds):
+      stat = self._residual_scales if name in raw else self._scales
+      scale.append(_per_channel_stat(stat, name, tds[name], 1.0))
+    out = self.predictor.ensemble_scores(ni, nt, forcings=nf, **kwargs)
+    if not isinstance(out, tuple):
+      return out.scaled(np.concatenate(scale))
+    scores, mean, var = out[0], datasets.as_dataset(out[1]), datasets.as_dataset(out[2])
+    mean = Dataset({k: self._unnormalize_prediction_and_add_input(raw, k, v) for k, v in mean.items()}, mean.coords)
+    squared = {True: self._residual_scales.map(np.square), False: self._scales.map(np.square)}
+    var = Dataset({k: unnormalize(Dataset({k: v}), squared[k in raw], None)[k] for k, v in var.items()}, var.coords)
+    return scores.scaled(np.concatenate(scale)), datasets.like_inputs(mean, *given), datasets.like_inputs(var, *given)
+
+
 def _broadcast_last(last: Variable, like: Variable) -> np.ndarray:
   """The last input frame (no time axis) broadcast against a time=1 variable."""
   shape = [1] * len(like.dims)

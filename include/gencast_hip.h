@@ -338,6 +338,54 @@ int gc_loss(gc_handle* h, const float* cond_feats, const float* targets, const f
             float* loss, float* per_group, float* denoised /* NULL allowed */);
 
 /*
+ * Ensemble verification: score M members against one truth on the device.  The reference
+ * project has no verification metrics; the yardstick is the closed-form definition in float64.
+ * Members x_0 .. x_{M-1} and the truth y are [G, B, c_out] float32 in the sample layout; w [G] is a node weight.
+ * A point (g, b, c) counts when y and all M members are finite there; other points contribute nothing (NaN truth
+ * over land).  Per counted point, in double from the float32 values:
+ *   m  = (sum_i x_i) / M  (ascending slot order),   s2 = sum_i (x_i - m)^2 / (M - 1)  (two passes),
+ *   ae = (sum_i |x_i - y|) / M,   d = sum_{i<j} |x_i - x_j| / (M (M-1) / 2),
+ *   r  = #{i : x_i < y} in 0..M   (ties are not randomised: a member equal to y is not below it)
+ * Per column (b, c), over the counted nodes g:
+ *   sums[0] = sum w, [1] = sum w (m - y), [2] = sum w (m - y)^2, [3] = sum w s2, [4] = sum w ae, [5] = sum w d,
+ *   rank_hist[b][c][r] = points of rank r (unweighted: they add up to the counted nodes of the column).
+ * The sums are raw and additive (batches, dates, ranks merge by addition); rmse = sqrt(S2/S0), spread = sqrt(S3/S0),
+ * fair CRPS = (S4 - S5/2)/S0, ensemble CRPS = (S4 - (M-1)/M S5/2)/S0, bias = S1/S0 are formed by the caller
+ * (gencast-flax-nnx_amd/verification.py).  Every term is formed and added in double, in a fixed order, with no atomics
+ * on floats: a call's results are bit-reproducible.
+ *   gc_ens_reserve          a store of n_members fields on the handle, n_members in 2..64 (else GC_ERR_UNSUPPORTED);
+ *                           frees and replaces an earlier store and everything sized by it, and empties every slot
+ *                           (also the mean / variance fields count as not computed again)
+ *   gc_ens_set_node_weight  w [G] (H2D; the caller's array is free on return); kept across gc_ens_reserve
+ *   gc_ens_push             slot <- the last sample of `src` (NULL: of h itself): one stream-ordered device-to-device
+ *                           copy.  The source's pending f16x3 domain check is resolved first, as in gc_stash_sample (the
+ *                           member is the checked sample).  With another handle the copy runs on the source's stream and
+ *                           the two streams are ordered by events, not by a host wait for the copy.
+ *                           GC_ERR_INVALID_ARGUMENT: slot outside [0, n_members); src on another device or with other
+ *                           G / batch / c_out.  GC_ERR_STATE: src holds no sample.
+ *   gc_ens_push_host        slot <- field [G, B, c_out] from the host through pinned staging (the caller's buffer is
+ *                           free on return): a member that was produced elsewhere (another rank, a rollout step)
+ *   gc_ens_score            truth: host [G, B, c_out], uploaded and kept, or NULL = the truth uploaded last.
+ *                           sums [6][B][c_out] doubles; rank_hist [B][c_out][M + 1] (NULL allowed).  want_fields != 0:
+ *                           the pass also writes m and s2 of every point into two handle-owned float32 fields (from the
+ *                           members alone; NaN where a member is not finite).  Synchronous.
+ *                           GC_ERR_STATE: a slot not pushed since gc_ens_reserve, no node weights, no truth.
+ *   gc_ens_download_fields  mean and / or variance [G, B, c_out] of the last gc_ens_score that asked for them (either
+ *                           pointer may be NULL); GC_ERR_STATE when none did since gc_ens_reserve
+ * Everything except gc_ens_push needs gc_set_graph only (no weights, no gc_finalize).  None of these entries touches the
+ * conditioning, the last sample, the stash, the loss buffers or the captured sample graphs.  Counters: "ens_scores"
+ * (scoring calls so far), "ens_score_device_us" (HIP-event time of the last call's two kernels), "ens_invalid_points"
+ * (points the last call skipped).
+ */
+int gc_ens_reserve(gc_handle* h, int32_t n_members);
+int gc_ens_set_node_weight(gc_handle* h, const float* w /* [G] */);
+int gc_ens_push(gc_handle* h, int32_t slot, gc_handle* src /* NULL = h */);
+int gc_ens_push_host(gc_handle* h, int32_t slot, const float* field /* [G,B,c_out] */);
+int gc_ens_score(gc_handle* h, const float* truth /* NULL = the truth uploaded last */, int32_t want_fields,
+                 double* sums /* [6][B][c_out] */, uint64_t* rank_hist /* [B][c_out][M+1], NULL allowed */);
+int gc_ens_download_fields(gc_handle* h, float* mean, float* variance);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
