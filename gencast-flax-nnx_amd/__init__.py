@@ -13,11 +13,13 @@ Public surface (mirrors the reference's call contracts):
   EnsembleSampler     common/rollout.py:78-176 (members sharded one per GPU)
   verification        EnsembleScores: CRPS, RMSE, spread, rank histogram from sums reduced on the GPU (no reference
                       counterpart: GenCast.ensemble_scores / EnsembleSampler.scores)
+  spectra             SphericalAnalysis, EnsembleSpectra: spherical-harmonic power per total wavenumber of a sample or an
+                      ensemble, analysed on the GPU (no reference counterpart: GenCast.ensemble_spectra)
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM
 """
-from . import config, datasets, geometry, launch, losses, rollout, synthetic, verification, weights  # noqa: F401
+from . import config, datasets, geometry, launch, losses, rollout, spectra, synthetic, verification, weights  # noqa: F401
 from .config import (DenoiserArchitectureConfig, NoiseConfig, NoiseEncoderConfig,  # noqa: F401
                      SamplerConfig, SparseTransformerConfig, TASK, TaskConfig)
 from .denoiser import Denoiser  # noqa: F401
@@ -26,9 +28,11 @@ from .gencast import GenCast, compute_loss, create_gencast_model, validation_los
 from .nan_cleaning import NaNCleaner  # noqa: F401
 from .rollout import DeviceRollout, InputsAndResiduals, autoregressive_rollout  # noqa: F401
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
+from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
 from .verification import EnsembleScores  # noqa: F401
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
            "InputsAndResiduals", "autoregressive_rollout", "DeviceRollout", "NaNCleaner", "launch", "losses",
-           "compute_loss", "validation_loss", "verification", "EnsembleScores"]
+           "compute_loss", "validation_loss", "verification", "EnsembleScores", "spectra", "EnsembleSpectra",
+           "SphericalAnalysis"]

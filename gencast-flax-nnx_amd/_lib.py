@@ -107,6 +107,9 @@ SIGNATURES = {
     "gc_ens_score": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
                                     ctypes.POINTER(ctypes.c_uint64)]),
     "gc_ens_download_fields": (ctypes.c_int, [_hp, _f32p, _f32p]),
+    "gc_spec_set_tables": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p, _f32p]),
+    "gc_spec_field": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_spectrum": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -196,6 +199,7 @@ class NativeDenoiser:
     self.num_mesh_nodes = None
     self._loss_groups = 0                      # groups of the loss weights this object handed to the handle
     self._ens_members = 0                      # slots of the member store this object reserved on the handle
+    self._spec_lmax = 0                        # band limit of the analysis tables this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
   def _check(self, rc):
@@ -544,6 +548,55 @@ class NativeDenoiser:
     var = np.empty(self._shape_out(), dtype=np.float32)
     self._check(self._lib.gc_ens_download_fields(self._h, _ptr(mean, _f32p), _ptr(var, _f32p)))
     return mean, var
+
+  # -- spherical-harmonic power spectra (analysed on the device) -------------------------------------
+  def spec_set_tables(self, legendre_analysis, cos_a, sin_a) -> None:
+    """`spectra.SphericalAnalysis.device_tables()`: legendre_analysis [lmax, lmax, n_lat], cos_a / sin_a [lmax, n_lon]
+    (gc_spec_set_tables; needs `set_graph` only)."""
+    q, c, s = _f32(legendre_analysis), _f32(cos_a), _f32(sin_a)
+    if q.ndim != 3 or q.shape[0] != q.shape[1] or c.ndim != 2 or c.shape != s.shape or c.shape[0] != q.shape[0]:
+      raise ValueError(f"tables must be [lmax, lmax, n_lat], [lmax, n_lon], [lmax, n_lon]; got {q.shape}, {c.shape}, {s.shape}")
+    self._check(self._lib.gc_spec_set_tables(self._h, q.shape[2], c.shape[1], q.shape[0], _ptr(q, _f32p), _ptr(c, _f32p),
+                                             _ptr(s, _f32p)))
+    self._spec_lmax = int(q.shape[0])
+
+  def _spec_need_tables(self):
+    if not self._spec_lmax:
+      raise GencastHipError("libgencast_hip error 4: no analysis tables (spec_set_tables has not been called on this object)")
+
+  def spec_field(self, field=None) -> np.ndarray:
+    """-> power [B, c_out, lmax] float64 of `field` [G, B, c_out], or of the last resident sample (None): gc_spec_field."""
+    self._spec_need_tables()
+    x = None
+    if field is not None:
+      x = _f32(field)
+      if x.shape != self._shape_out():
+        raise ValueError(f"field must be {self._shape_out()}, got {x.shape}")
+    power = np.empty((self.cfg.batch, self.cfg.c_out, self._spec_lmax), dtype=np.float64)
+    self._check(self._lib.gc_spec_field(self._h, None if x is None else _ptr(x, _f32p),
+                                        _ptr(power, ctypes.POINTER(ctypes.c_double))))
+    return power
+
+  def ens_spectrum(self, truth=None, want_member_power: bool = False):
+    """-> sums [B, c_out, lmax, 6] float64, the raw additive sums of gc_ens_spectrum over the member store
+    (`spectra.EnsembleSpectra` derives the rest); with `want_member_power` also [M, B, c_out, lmax].
+    `truth` [G, B, c_out], or None = the truth uploaded last (shared with `ens_score`)."""
+    self._spec_need_tables()
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    t = None
+    if truth is not None:
+      t = _f32(truth)
+      if t.shape != self._shape_out():
+        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    B, C, L = self.cfg.batch, self.cfg.c_out, self._spec_lmax
+    dp = ctypes.POINTER(ctypes.c_double)
+    sums = np.empty((6, B, C, L), dtype=np.float64)
+    mp = np.empty((self._ens_members, B, C, L), dtype=np.float64) if want_member_power else None
+    self._check(self._lib.gc_ens_spectrum(self._h, None if t is None else _ptr(t, _f32p), _ptr(sums, dp),
+                                          None if mp is None else _ptr(mp, dp)))
+    sums = np.ascontiguousarray(np.moveaxis(sums, 0, -1))
+    return (sums, mp) if want_member_power else sums
 
   # -- ensemble exchange (RCCL inside the library) -------------------------------------------------
   def comm_init(self, unique_id: bytes, rank: int, world_size: int) -> None:

@@ -194,14 +194,15 @@ static void destroy_impl(gc_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   drop_sample_graphs(h);
   if (h->comm) (void)rccl().CommDestroy(h->comm);
-  for (std::vector<void*>* l : {&h->allocs, &h->weight_allocs, &h->cache_allocs, &h->ens_allocs}) free_allocs(l);
+  for (std::vector<void*>* l : {&h->allocs, &h->weight_allocs, &h->cache_allocs, &h->ens_allocs, &h->spec_allocs, &h->spec_work_allocs})
+    free_allocs(l);
   if (h->d_nonfinite) (void)hipFree(h->d_nonfinite);
   for (void* p : {(void*)h->h_nonfinite, (void*)h->pin_cond, (void*)h->pin_noise, (void*)h->pin_forc,
                   (void*)h->pin_lguard})
     if (p) (void)hipHostFree(p);
   if (h->ev_pin) (void)hipEventDestroy(h->ev_pin);
   if (h->ev_stash) (void)hipEventDestroy(h->ev_stash);
-  for (hipEvent_t e : {h->ev_ens_free, h->ev_ens_done, h->ev_ens0, h->ev_ens1})
+  for (hipEvent_t e : {h->ev_ens_free, h->ev_ens_done, h->ev_ens0, h->ev_ens1, h->ev_sp0, h->ev_sp1})
     if (e) (void)hipEventDestroy(e);
   if (h->stream2) {
     (void)hipStreamSynchronize(h->stream2);
@@ -858,8 +859,12 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "ens_scores") *value = h->ens_scores;
   else if (n == "ens_score_device_us") *value = h->ens_score_device_us;
   else if (n == "ens_invalid_points") *value = h->ens_invalid_points;
+  else if (n == "spec_calls") *value = h->spec_calls;
+  else if (n == "spec_device_us") *value = h->spec_device_us;
+  else if (n == "spec_invalid_columns") *value = h->spec_invalid_columns;
   else if (n == "device_allocations")
-    *value = (int64_t)(h->allocs.size() + h->weight_allocs.size() + h->cache_allocs.size() + h->ens_allocs.size());
+    *value = (int64_t)(h->allocs.size() + h->weight_allocs.size() + h->cache_allocs.size() + h->ens_allocs.size() +
+                       h->spec_allocs.size() + h->spec_work_allocs.size());
   else return fail(h, GC_ERR_INVALID_ARGUMENT, "unknown counter: " + n);
   return GC_OK;
   });

@@ -1,6 +1,6 @@
 // Internals shared by the host translation units of libgencast_hip.so: the handle, the device-side weight layout,
 // the route of a forward, and the allocation / launch helpers.  gc_weights.hip lays the weights out, gc_forward.hip
-// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* entries).
+// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* entries, gc_spectrum.hip gc_spec_* and gc_ens_spectrum).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -218,6 +218,20 @@ struct gc_handle {
   hipEvent_t ev_ens_free = nullptr, ev_ens_done = nullptr;     // stream order of a push from another handle
   hipEvent_t ev_ens0 = nullptr, ev_ens1 = nullptr;             // brackets of the last scoring call
   int64_t ens_scores = 0, ens_score_device_us = 0, ens_invalid_points = 0;
+
+  // spherical-harmonic power spectra (gc_spec_*, gc_ens_spectrum, gc_spectrum.hip)
+  std::vector<void*> spec_allocs;                // sized by the tables: freed and replaced by gc_spec_set_tables
+  std::vector<void*> spec_work_allocs;           // sized by the coefficient sets a call keeps: replaced when a call needs more
+  int sp_L = 0, sp_lat = 0, sp_lon = 0;          // lmax (0: no tables), n_lat, n_lon
+  int sp_sets = 0;                               // coefficient sets d_sp_coef holds
+  float *d_sp_q = nullptr, *d_sp_tab = nullptr;  // [L m][L l][n_lat] Legendre analysis, [2 L][n_lon] cosine rows then sine rows
+  float* d_sp_field = nullptr;                   // [G, B, c_out]: a field handed over from the host
+  double* d_sp_F = nullptr;                      // [2][L][n_lat][B c_out]: Fourier step of the field in flight
+  double* d_sp_coef = nullptr;                   // [sp_sets][2][L m][L l][B c_out]
+  double* d_sp_out = nullptr;                    // [6 + sp_sets][B c_out][L]: the sums, then the member powers
+  unsigned* d_sp_flags = nullptr;                // [B c_out]: a value of the column was not finite
+  hipEvent_t ev_sp0 = nullptr, ev_sp1 = nullptr; // brackets of the last spectrum call
+  int64_t spec_calls = 0, spec_device_us = 0, spec_invalid_columns = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

@@ -1,0 +1,362 @@
+// Spherical-harmonic power spectra on the device (include/gencast_hip.h, gc_spec_* / gc_ens_spectrum): the analysis
+// direction of the transform gc_noise.hip synthesises with, and the reductions on top of it.  Kernels and their host code
+// live together here; DESIGN.md section 8d has the definitions and the error bound the tests assert.
+//
+// A field is [n_lat][n_lon][N] float32, N = B c_out independent columns.  With the float32 tables T (cosine and sine rows,
+// amp_m / n_lon folded in) and Q (the pseudo-inverse of the Legendre synthesis matrix of every m, zero for l < m):
+//   Fourier step   F[part][m][lat][n] = sum_j   T[part][m][j] f[lat][j][n]          j ascending
+//   Legendre step  a[part][m][l][n]   = sum_lat Q[m][l][lat] F[part][m][lat][n]     lat ascending
+//   power          p[n][l]            = (sum_m a[0][m][l][n]^2 + a[1][m][l][n]^2) / (4 pi)   m ascending, cosine then sine
+// Every product and sum is binary64.  The Fourier products are exact (float32 x float32), so fused and unfused
+// multiply-adds give the same bits there; the Legendre step uses fused multiply-adds (one rounding per term); the
+// squares of the power step are rounded before they are added.  Every sum has one writer and a fixed order; the only
+// atomics are integer ORs into the per-column "not finite" flags, which commute.  Both products run on the vector ALUs
+// (as gc_noise_* do): a wave keeps 16 output rows of one 64-column group in registers, its table values are
+// wave-uniform and come through the scalar cache.
+#include "gc_handle.h"
+
+namespace gc {
+
+constexpr int kSpecRows = 16;                    // output rows (wavenumbers) a wave accumulates
+constexpr int kSpecBlockRows = 4 * kSpecRows;    // per workgroup of 4 waves
+constexpr double kFourPi = 12.566370614359172;   // 4 pi, as the host's 4.0 * pi rounds
+
+// Fourier step.  grid = (n_lat, ceil(2 L / 64), ceil(N / 64)); lane = column.  Row r < L is the cosine row of m = r,
+// row L + m the sine row.  The workgroups of row block 0 also note a value that is not finite in flags[n].
+__global__ __launch_bounds__(256) void gc_spec_fourier_kernel(const float* __restrict__ f,      // [n_lat][n_lon][N]
+                                                               const float* __restrict__ tab,    // [2 L][n_lon]
+                                                               int L, int n_lat, int n_lon, int N,
+                                                               double* __restrict__ F,           // [2 L][n_lat][N]
+                                                               unsigned* __restrict__ flags) {   // [N]
+  const int lat = blockIdx.x, R = 2 * L;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int n = blockIdx.z * 64 + lane;
+  const int r0 = blockIdx.y * kSpecBlockRows + wave * kSpecRows;
+  if (r0 >= R) return;
+  const float* trow[kSpecRows];
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k) trow[k] = tab + (size_t)min(r0 + k, R - 1) * n_lon;
+  double acc[kSpecRows];
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k) acc[k] = 0.0;
+  const float* frow = f + (size_t)lat * n_lon * N + min(n, N - 1);
+  bool bad = false;
+  for (int j = 0; j < n_lon; ++j) {
+    const float xf = frow[(size_t)j * N];
+    bad = bad || !isfinite(xf);
+    const double x = (double)xf;
+#pragma unroll
+    for (int k = 0; k < kSpecRows; ++k) acc[k] = fma((double)trow[k][j], x, acc[k]);
+  }
+  if (n >= N) return;
+  if (bad && r0 == 0) atomicOr(&flags[n], 1u);
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k)
+    if (r0 + k < R) F[((size_t)(r0 + k) * n_lat + lat) * N + n] = acc[k];
+}
+
+// Legendre step.  grid = (L, 2 ceil(L / 64), ceil(N / 64)): blockIdx.x = m, blockIdx.y = part + 2 (block of 64 l).  A wave
+// whose 16 l are all below m has nothing to do (those coefficients do not exist and are never read).
+__global__ __launch_bounds__(256) void gc_spec_legendre_kernel(const float* __restrict__ Q,      // [L m][L l][n_lat]
+                                                                const double* __restrict__ F,     // [2][L][n_lat][N]
+                                                                int L, int n_lat, int N,
+                                                                double* __restrict__ coef) {      // [2][L m][L l][N]
+  const int m = blockIdx.x, part = blockIdx.y & 1;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int n = blockIdx.z * 64 + lane;
+  const int l0 = (blockIdx.y >> 1) * kSpecBlockRows + wave * kSpecRows;
+  if (l0 >= L || l0 + kSpecRows <= m) return;
+  const float* qrow[kSpecRows];
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k) qrow[k] = Q + ((size_t)m * L + min(l0 + k, L - 1)) * n_lat;
+  double acc[kSpecRows];
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k) acc[k] = 0.0;
+  const double* fcol = F + ((size_t)part * L + m) * n_lat * N + min(n, N - 1);
+  for (int lat = 0; lat < n_lat; ++lat) {
+    const double x = fcol[(size_t)lat * N];
+#pragma unroll
+    for (int k = 0; k < kSpecRows; ++k) acc[k] = fma((double)qrow[k][lat], x, acc[k]);
+  }
+  if (n >= N) return;
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k)
+    if (l0 + k < L) coef[(((size_t)part * L + m) * L + l0 + k) * N + n] = acc[k];
+}
+
+#pragma clang fp contract(off)   // from here on a square is rounded before it is added: the order the header states
+
+// sum_m (c^2 + s^2) / (4 pi) of the coefficients u - v (v may be null), m ascending, cosine before sine
+__device__ __forceinline__ double spec_power_of(const double* __restrict__ u, const double* __restrict__ v, int L, int N,
+                                                int l, int n) {
+  const size_t part = (size_t)L * L * N, step = (size_t)L * N;
+  size_t e = (size_t)l * N + n;
+  double s = 0.0;
+  for (int m = 0; m <= l; ++m, e += step) {
+    const double c = v ? u[e] - v[e] : u[e];
+    const double d = v ? u[part + e] - v[part + e] : u[part + e];
+    s += c * c;
+    s += d * d;
+  }
+  return s / kFourPi;
+}
+
+// One thread per (l, n).  out [N][L]: the power of one coefficient set; NaN for a flagged column.
+__global__ __launch_bounds__(256) void gc_spec_power_kernel(const double* __restrict__ coef, const unsigned* __restrict__ flags,
+                                                             int L, int N, double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= L * N) return;
+  const int l = i / N, n = i - l * N;
+  out[(size_t)n * L + l] = flags[n] ? __builtin_nan("") : spec_power_of(coef, nullptr, L, N, l, n);
+}
+
+// Mean coefficients: mean = (sum_i set_i) / M, members in ascending slot order, on every (part, m, l >= m, n).
+__global__ __launch_bounds__(256) void gc_spec_mean_kernel(const double* __restrict__ members, size_t set, int M, int L, int N,
+                                                            double* __restrict__ mean) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= set) return;
+  const int l = (int)((e / N) % L), m = (int)((e / ((size_t)N * L)) % L);
+  double s = 0.0;
+  if (l >= m) {
+    for (int i = 0; i < M; ++i) s += members[(size_t)i * set + e];
+    s /= (double)M;
+  }
+  mean[e] = s;
+}
+
+// The six ensemble sums of one (l, n), from the coefficient sets [truth | member 0 .. M-1 | mean]:
+//   P0 = p(y)  P1 = sum_i p(x_i)  P2 = p(mean)  P3 = sum_i p(x_i - y)  P4 = p(mean - y)  P5 = sum_i p(x_i - mean)
+// each p() complete (divided by 4 pi) before it is added, members in ascending slot order; differences on the
+// coefficients.  sums [6][N][L]; member_power [M][N][L] (may be null): p(x_i).
+__global__ __launch_bounds__(256) void gc_spec_ens_kernel(const double* __restrict__ sets, size_t set, int M,
+                                                           const unsigned* __restrict__ flags, int L, int N,
+                                                           double* __restrict__ sums, double* __restrict__ member_power) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= L * N) return;
+  const int l = i / N, n = i - l * N;
+  const size_t o = (size_t)n * L + l, plane = (size_t)N * L;
+  const bool bad = flags[n] != 0u;
+  const double qnan = __builtin_nan("");
+  const double* y = sets;
+  const double* mean = sets + (size_t)(M + 1) * set;
+  double p[6] = {qnan, qnan, qnan, qnan, qnan, qnan};
+  if (!bad) {
+    p[0] = spec_power_of(y, nullptr, L, N, l, n);
+    p[2] = spec_power_of(mean, nullptr, L, N, l, n);
+    p[4] = spec_power_of(mean, y, L, N, l, n);
+    p[1] = p[3] = p[5] = 0.0;
+  }
+  for (int k = 0; k < M; ++k) {
+    const double* x = sets + (size_t)(k + 1) * set;
+    double px = qnan;
+    if (!bad) {
+      px = spec_power_of(x, nullptr, L, N, l, n);
+      p[1] += px;
+      p[3] += spec_power_of(x, y, L, N, l, n);
+      p[5] += spec_power_of(x, mean, L, N, l, n);
+    }
+    if (member_power) member_power[(size_t)k * plane + o] = px;
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) sums[(size_t)k * plane + o] = p[k];
+}
+
+static bool spec_grid_ok(int L, int n_lat, int N) {
+  return L >= 1 && n_lat >= 1 && N >= 1 && n_lat <= 65535 && (N + 63) / 64 <= 65535 &&
+         2 * ((L + kSpecBlockRows - 1) / kSpecBlockRows) <= 65535 && (long long)L * N < (1ll << 31) - 256;
+}
+
+// field -> coefficient set (F is the scratch of the Fourier step)
+static hipError_t launch_spec_analysis(hipStream_t s, const float* field, const float* tab, const float* Q, int L, int n_lat,
+                                       int n_lon, int N, double* F, double* coef, unsigned* flags) {
+  if (!spec_grid_ok(L, n_lat, N)) return hipErrorInvalidValue;
+  const unsigned cols = (unsigned)((N + 63) / 64);
+  hipLaunchKernelGGL(gc_spec_fourier_kernel, dim3(n_lat, (2 * L + kSpecBlockRows - 1) / kSpecBlockRows, cols), dim3(256), 0, s,
+                     field, tab, L, n_lat, n_lon, N, F, flags);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(gc_spec_legendre_kernel, dim3(L, 2 * ((L + kSpecBlockRows - 1) / kSpecBlockRows), cols), dim3(256), 0, s, Q, F,
+                     L, n_lat, N, coef);
+  return hipGetLastError();
+}
+
+static hipError_t launch_spec_power(hipStream_t s, const double* coef, const unsigned* flags, int L, int N, double* out) {
+  hipLaunchKernelGGL(gc_spec_power_kernel, dim3((L * N + 255) / 256), dim3(256), 0, s, coef, flags, L, N, out);
+  return hipGetLastError();
+}
+
+static hipError_t launch_spec_ens(hipStream_t s, double* sets, size_t set, int M, const unsigned* flags, int L, int N, double* sums,
+                                  double* member_power) {
+  hipLaunchKernelGGL(gc_spec_mean_kernel, dim3((unsigned)((set + 255) / 256)), dim3(256), 0, s, sets + set, set, M, L, N,
+                     sets + (size_t)(M + 1) * set);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(gc_spec_ens_kernel, dim3((L * N + 255) / 256), dim3(256), 0, s, sets, set, M, flags, L, N, sums, member_power);
+  return hipGetLastError();
+}
+
+}  // namespace gc
+
+using namespace gci;
+
+namespace {
+
+size_t spec_field_len(const gc_handle* h) { return (size_t)h->hg.G * h->cfg.batch * h->cfg.c_out; }
+size_t spec_set_len(const gc_handle* h) { return (size_t)2 * h->sp_L * h->sp_L * h->cfg.batch * h->cfg.c_out; }
+
+int spec_ready(gc_handle* h) {
+  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (h->sp_L == 0) return fail(h, GC_ERR_STATE, "no analysis tables (gc_spec_set_tables)");
+  return GC_OK;
+}
+
+// The buffers sized by the number of coefficient sets a call keeps: made again when a call needs more than there are.
+int spec_reserve_sets(gc_handle* h, int sets) {
+  if (sets <= h->sp_sets) return GC_OK;
+  GC_HIP(h, hipStreamSynchronize(h->stream));
+  free_allocs(&h->spec_work_allocs);
+  h->sp_sets = 0;
+  const size_t out = (size_t)h->cfg.batch * h->cfg.c_out * h->sp_L;
+  int rc;
+  if ((rc = dev_alloc(h, &h->d_sp_coef, (size_t)sets * spec_set_len(h), &h->spec_work_allocs)) ||
+      (rc = dev_alloc(h, &h->d_sp_out, (size_t)(6 + sets) * out, &h->spec_work_allocs))) {
+    free_allocs(&h->spec_work_allocs);
+    return rc;
+  }
+  h->sp_sets = sets;
+  return GC_OK;
+}
+
+int spec_finish(gc_handle* h, const std::vector<unsigned>& flags) {
+  float ms = 0.f;
+  GC_HIP(h, hipEventElapsedTime(&ms, h->ev_sp0, h->ev_sp1));
+  h->spec_device_us = (int64_t)(ms * 1000.0f);
+  int64_t bad = 0;
+  for (unsigned f : flags) bad += f ? 1 : 0;
+  h->spec_invalid_columns = bad;
+  ++h->spec_calls;
+  return GC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gc_spec_set_tables(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t lmax, const float* legendre_analysis,
+                       const float* cos_a, const float* sin_a) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (!legendre_analysis || !cos_a || !sin_a) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_lat < 2 || n_lon < 2 || (int64_t)n_lat * n_lon != h->hg.G)
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "n_lat * n_lon must equal the number of grid nodes");
+  if (lmax < 1 || 2 * (int64_t)lmax > n_lon) return fail(h, GC_ERR_INVALID_ARGUMENT, "lmax must be in 1 .. n_lon / 2");
+  const int N = h->cfg.batch * h->cfg.c_out;
+  if (!gc::spec_grid_ok(lmax, n_lat, N)) return fail(h, GC_ERR_UNSUPPORTED, "grid too large for the spectrum kernels");
+  GC_HIP(h, hipSetDevice(h->device));
+  GC_HIP(h, hipStreamSynchronize(h->stream));      // nothing reads the old tables any more
+  free_allocs(&h->spec_allocs);
+  free_allocs(&h->spec_work_allocs);
+  h->sp_L = h->sp_sets = 0;
+  const size_t L = (size_t)lmax;
+  std::vector<float> tab(2 * L * n_lon);
+  std::copy(cos_a, cos_a + L * n_lon, tab.begin());
+  std::copy(sin_a, sin_a + L * n_lon, tab.begin() + L * n_lon);
+  int rc;
+  if ((rc = dev_upload(h, &h->d_sp_q, std::vector<float>(legendre_analysis, legendre_analysis + L * L * n_lat), &h->spec_allocs)) ||
+      (rc = dev_upload(h, &h->d_sp_tab, tab, &h->spec_allocs)) ||
+      (rc = dev_alloc(h, &h->d_sp_F, 2 * L * n_lat * N, &h->spec_allocs)) ||
+      (rc = dev_alloc(h, &h->d_sp_field, spec_field_len(h), &h->spec_allocs)) ||
+      (rc = dev_alloc(h, &h->d_sp_flags, (size_t)N, &h->spec_allocs))) {
+    free_allocs(&h->spec_allocs);
+    return rc;
+  }
+  for (hipEvent_t* e : {&h->ev_sp0, &h->ev_sp1})
+    if (!*e) GC_HIP(h, hipEventCreate(e));
+  h->sp_L = lmax; h->sp_lat = n_lat; h->sp_lon = n_lon;
+  return GC_OK;
+  });
+}
+
+int gc_spec_field(gc_handle* h, const float* field, double* power) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = spec_ready(h);
+  if (rc) return rc;
+  if (!power) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!field && (!h->finalized || !h->has_sample)) return fail(h, GC_ERR_STATE, "no sample on the device (gc_sample_resident)");
+  GC_HIP(h, hipSetDevice(h->device));
+  if (!field && (rc = resolve_guard(h))) return rc;   // the spectrum is of the CHECKED sample (exact-f32 re-run included)
+  if ((rc = spec_reserve_sets(h, 1))) return rc;
+  if (field && (rc = staged_upload(h, h->pin_noise, h->d_sp_field, field, spec_field_len(h)))) return rc;
+  const int L = h->sp_L, N = h->cfg.batch * h->cfg.c_out;
+  hipStream_t s = h->stream;
+  const float* src = field ? h->d_sp_field : h->d_sx;
+  GC_HIP(h, hipEventRecord(h->ev_sp0, s));
+  GC_HIP(h, hipMemsetAsync(h->d_sp_flags, 0, (size_t)N * sizeof(unsigned), s));
+  if ((rc = launch(h, gc::KC_PACK, [&] {
+         return gc::launch_spec_analysis(s, src, h->d_sp_tab, h->d_sp_q, L, h->sp_lat, h->sp_lon, N, h->d_sp_F, h->d_sp_coef,
+                                         h->d_sp_flags);
+       })))
+    return rc;
+  if ((rc = launch(h, gc::KC_PACK, [&] { return gc::launch_spec_power(s, h->d_sp_coef, h->d_sp_flags, L, N, h->d_sp_out); })))
+    return rc;
+  GC_HIP(h, hipEventRecord(h->ev_sp1, s));
+  std::vector<unsigned> flags((size_t)N);
+  GC_HIP(h, hipMemcpyAsync(power, h->d_sp_out, (size_t)N * L * sizeof(double), hipMemcpyDeviceToHost, s));
+  GC_HIP(h, hipMemcpyAsync(flags.data(), h->d_sp_flags, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  GC_HIP(h, hipStreamSynchronize(s));
+  return spec_finish(h, flags);
+  });
+}
+
+int gc_ens_spectrum(gc_handle* h, const float* truth, double* sums, double* member_power) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = spec_ready(h);
+  if (rc) return rc;
+  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
+  if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  const int M = h->ens_members;
+  for (int i = 0; i < M; ++i)
+    if (!h->ens_filled[(size_t)i]) return fail(h, GC_ERR_STATE, "member slot " + std::to_string(i) + " has not been pushed");
+  if (!truth && !h->has_ens_truth) return fail(h, GC_ERR_STATE, "no truth on the device (pass one to gc_ens_spectrum)");
+  GC_HIP(h, hipSetDevice(h->device));
+  const size_t field = spec_field_len(h), set = spec_set_len(h);
+  if (truth) {
+    if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
+    if ((rc = staged_upload(h, h->pin_noise, h->d_ens_truth, truth, field))) return rc;
+    h->has_ens_truth = true;
+  }
+  if ((rc = spec_reserve_sets(h, M + 2))) return rc;
+  const int L = h->sp_L, N = h->cfg.batch * h->cfg.c_out;
+  const size_t plane = (size_t)N * L;
+  hipStream_t s = h->stream;
+  double* const d_sums = h->d_sp_out;
+  double* const d_mp = h->d_sp_out + 6 * plane;
+  GC_HIP(h, hipEventRecord(h->ev_sp0, s));
+  GC_HIP(h, hipMemsetAsync(h->d_sp_flags, 0, (size_t)N * sizeof(unsigned), s));
+  // one field at a time through the Fourier scratch; set 0 = truth, 1 + i = member i, M + 1 = the mean coefficients
+  for (int k = 0; k <= M; ++k) {
+    const float* src = k == 0 ? h->d_ens_truth : h->d_ens + (size_t)(k - 1) * field;
+    if ((rc = launch(h, gc::KC_PACK, [&] {
+           return gc::launch_spec_analysis(s, src, h->d_sp_tab, h->d_sp_q, L, h->sp_lat, h->sp_lon, N, h->d_sp_F,
+                                           h->d_sp_coef + (size_t)k * set, h->d_sp_flags);
+         })))
+      return rc;
+  }
+  if ((rc = launch(h, gc::KC_PACK, [&] {
+         return gc::launch_spec_ens(s, h->d_sp_coef, set, M, h->d_sp_flags, L, N, d_sums, member_power ? d_mp : nullptr);
+       })))
+    return rc;
+  GC_HIP(h, hipEventRecord(h->ev_sp1, s));
+  std::vector<unsigned> flags((size_t)N);
+  GC_HIP(h, hipMemcpyAsync(sums, d_sums, 6 * plane * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (member_power) GC_HIP(h, hipMemcpyAsync(member_power, d_mp, (size_t)M * plane * sizeof(double), hipMemcpyDeviceToHost, s));
+  GC_HIP(h, hipMemcpyAsync(flags.data(), h->d_sp_flags, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  GC_HIP(h, hipStreamSynchronize(s));
+  return spec_finish(h, flags);
+  });
+}
+
+}  // extern "C"

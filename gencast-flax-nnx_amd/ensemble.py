@@ -14,7 +14,7 @@ from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
-from . import datasets, verification
+from . import datasets, spectra as _spectra, verification
 from .denoiser import Denoiser
 from .sampler import Sampler
 
@@ -82,8 +82,29 @@ class EnsembleSampler:
                        "ranks' members over and push them with NativeDenoiser.ens_push_host")
     return self._run(inputs, targets, forcings, num_members, bool(fields))
 
-  def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool]):
-    """`score_fields` None: members come back as Datasets (`__call__`); else they are scored (`scores`)."""
+  def spectra(self, inputs, targets, forcings, num_members: int, *, lmax: Optional[int] = None):
+    """Runs the members as `scores` does and analyses them on the device: `spectra.EnsembleSpectra` (power per total
+    wavenumber of the truth, the members, the ensemble mean, the errors and the spread, per batch member and channel)
+    in the units of `targets`.  No member is downloaded.  `lmax`: the band limit (default n_lon / 2).  `targets` must
+    be finite: a column with a NaN has no transform and comes back NaN."""
+    return self._spectral(inputs, targets, forcings, num_members, None, lmax)
+
+  def scores_and_spectra(self, inputs, targets, forcings, num_members: int, *, fields: bool = False,
+                         lmax: Optional[int] = None):
+    """`scores(...)` and `spectra(...)` of the same members, sampled once: -> (scores, spectra), with `fields=True`
+    (scores, mean, variance, spectra)."""
+    return self._spectral(inputs, targets, forcings, num_members, bool(fields), lmax)
+
+  def _spectral(self, inputs, targets, forcings, num_members, score_fields, lmax):
+    if self.world_size > 1:
+      raise ValueError("EnsembleSampler.spectra needs all members on one rank (world_size == 1): bring the other "
+                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
+
+  def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,
+           lmax: Optional[int] = None):
+    """`score_fields` None: members come back as Datasets (`__call__`) or, with `spectral`, only their spectra are
+    formed; else they are scored (`scores`), with `spectral` both."""
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
     cond, grid_shape, slots = self._denoiser.init_for(inputs, template, forcings)
@@ -110,9 +131,12 @@ class EnsembleSampler:
         lane.set_noisy_slots(slots)
         lane.upload_cond_dev(ptr)                          # device-to-device, on the lane's own stream
     scoring = score_fields is not None
-    if scoring:
+    if scoring or spectral:
       native.ens_reserve(num_members)
+    if scoring:
       native.ens_set_node_weight(verification.node_weights(template))
+    if spectral:
+      _spectra.ensure_tables(native, template, lmax)
     out = []
     for g0 in range(0, len(mine), len(lanes)):
       group = mine[g0:g0 + len(lanes)]
@@ -120,18 +144,22 @@ class EnsembleSampler:
         lane.upload_noise(self.member_noise(m, shape, template))
         lane.sample_resident(sigmas, skip_dead_call=True, want_stats=False)
       for lane, m in zip(lanes, group):
-        if scoring:
+        if scoring or spectral:
           native.ens_push(m, src=lane)
         else:
           out.append((m, datasets.like_inputs(Denoiser.unpack_outputs(lane.download_sample(), grid_shape, template),
                                               targets_template, inputs, forcings)))
-    if not scoring:
+    if not scoring and not spectral:
       return out
     truth = np.transpose(datasets.dataset_to_stacked(template, template.sizes), (1, 2, 0, 3)).reshape(shape)
+    if not scoring:
+      return _spectra.EnsembleSpectra(native.ens_spectrum(truth), num_members)
     sums, hist = native.ens_score(truth, want_fields=score_fields)
-    result = verification.EnsembleScores(sums, hist, num_members)
-    if not score_fields:
-      return result
-    given = (targets_template, inputs, forcings)
-    return (result,) + tuple(datasets.like_inputs(Denoiser.unpack_outputs(f, grid_shape, template), *given)
-                             for f in native.ens_download_fields())
+    result = (verification.EnsembleScores(sums, hist, num_members),)
+    if score_fields:
+      given = (targets_template, inputs, forcings)
+      result += tuple(datasets.like_inputs(Denoiser.unpack_outputs(f, grid_shape, template), *given)
+                      for f in native.ens_download_fields())
+    if spectral:
+      result += (_spectra.EnsembleSpectra(native.ens_spectrum(None), num_members),)   # the truth is on the device already
+    return result if len(result) > 1 else result[0]

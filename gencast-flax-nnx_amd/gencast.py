@@ -100,6 +100,20 @@ class GenCast:
     runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
     return runner.scores(inputs, targets, forcings, num_members, fields=fields)
 
+  def ensemble_spectra(self, inputs, targets, forcings=None, *, num_members, rngs=0, concurrent_members=1, lmax=None,
+                       scores=False):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and analyses them against `targets` on the GPU:
+    `spectra.EnsembleSpectra` -- spherical-harmonic power per total wavenumber l < `lmax` (default n_lon / 2) of the
+    truth, the members, the ensemble mean, their errors and the spread, per batch member and channel.  No member
+    leaves the device.  `scores=True`: -> (EnsembleScores, EnsembleSpectra) from the same members, sampled once."""
+    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
+    if not isinstance(rngs, (int, np.integer)):
+      rngs = Sampler.seed_from(rngs)
+    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    if scores:
+      return runner.scores_and_spectra(inputs, targets, forcings, num_members, lmax=lmax)
+    return runner.spectra(inputs, targets, forcings, num_members, lmax=lmax)
+
   # -- the diffusion objective, forward only -----------------------------------------------------------------
   def _denoising_eval(self, inputs, targets, forcings, rngs, noise_levels, noise, num_noise_draws, per_variable_weights):
     """-> (loss [K, B], per_variable [K, B, V], names, D [G, B, c_out] of the last draw, grid_shape, targets Dataset)."""

@@ -121,6 +121,21 @@ class NaNCleaner:
       return out
     return (out[0],) + tuple(datasets.like_inputs(datasets.as_dataset(f), *given) for f in out[1:])
 
+  def ensemble_spectra(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """Inputs and forcings are cleaned, and so are the targets: a transform cannot skip points, so the spectrum of the
+    cleaned variable is that of the field with its NaNs (land points) replaced by the fill value, truth and members
+    alike."""
+    inputs = datasets.as_dataset(inputs)
+    targets = datasets.as_dataset(targets)
+    forcings = None if forcings is None else datasets.as_dataset(forcings)
+    if self._var_to_clean in inputs.keys():
+      inputs = self._clean(inputs)
+    if self._var_to_clean in targets.keys():
+      targets = self._clean(targets)
+    if forcings is not None and self._var_to_clean in forcings.keys():
+      forcings = self._clean(forcings)
+    return self.predictor.ensemble_spectra(inputs, targets, forcings, **kwargs)
+
   def loss(self, *args, **kwargs):
     raise NotImplementedError("training (loss) is outside the sampling hot path; the forward-only value of the "
                               "objective is denoising_loss / denoising_loss_and_predictions")

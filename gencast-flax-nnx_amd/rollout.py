@@ -201,6 +201,26 @@ class InputsAndResiduals:
     return scores.scaled(np.concatenate(scale)), datasets.like_inputs(mean, *given), datasets.like_inputs(var, *given)
 
 
+  def ensemble_spectra(self, inputs, targets, forcings=None, **kwargs):
+    """`ensemble_spectra` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets,
+    in physical units: every power is multiplied by a^2 per channel (`EnsembleSpectra.scaled`; a: the residual scale of
+    a variable that is also an input, else its plain scale).  This is the spectrum of the predicted INCREMENT without
+    its location offset (for a residual variable the last input frame, else the mean): adding a field back is not a
+    rescaling of sums.  The error and spread spectra do not depend on that offset.  With `scores=True` the scores are
+    rescaled as `ensemble_scores` does."""
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    tds = datasets.as_dataset(targets)
+    scale = []
+    for name, _, _ in datasets.channel_layout(tds):
+      stat = self._residual_scales if name in raw else self._scales
+      scale.append(_per_channel_stat(stat, name, tds[name], 1.0))
+    scale = np.concatenate(scale)
+    out = self.predictor.ensemble_spectra(ni, nt, forcings=nf, **kwargs)
+    if not isinstance(out, tuple):
+      return out.scaled(scale)
+    return tuple(o.scaled(scale) for o in out)
+
+
 def _broadcast_last(last: Variable, like: Variable) -> np.ndarray:
   """The last input frame (no time axis) broadcast against a time=1 variable."""
   shape = [1] * len(like.dims)

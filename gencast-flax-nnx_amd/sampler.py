@@ -90,6 +90,7 @@ class Sampler:
     self._tables_on = None                    # the native handle that holds the noise tables
     self.sigma_data = 1.0
     self.last_stats = None
+    self._last_template = None
 
   @property
   def noise_levels(self) -> np.ndarray:
@@ -151,6 +152,7 @@ class Sampler:
     cond, grid_shape, slots = self._denoiser.init_for(inputs, template, forcings)
     native = self._denoiser.native
     native.set_noisy_slots(slots)
+    self._last_template = template                              # the grid of the resident sample (sample_spectrum)
     shape = (cond.shape[0], cond.shape[1], self._denoiser.dims.c_out)
     on_device = init_noise is None and self.device_noise and self.noise_kind != "white"
     if self._stochastic_churn or on_device:
@@ -175,3 +177,14 @@ class Sampler:
     out = native.download_sample()
     # xarray in -> xarray out: the harness concatenates what this returns with xr.concat (train_helpers.py:569-624)
     return datasets.like_inputs(Denoiser.unpack_outputs(out, grid_shape, template), targets_template, inputs, forcings)
+
+  def sample_spectrum(self, lmax: Optional[int] = None) -> np.ndarray:
+    """Power per total wavenumber [B, c_out, lmax] (float64) of the sample the last `__call__` left on the device,
+    analysed where it lies (`gc_spec_field`; spectra.py): nothing is downloaded but the spectrum.
+    In the units the denoiser works in; `lmax` defaults to n_lon / 2."""
+    from . import spectra as _spectra
+    if self._last_template is None:
+      raise ValueError("sample_spectrum: no sample yet (call the sampler first)")
+    native = self._denoiser.native
+    _spectra.ensure_tables(native, self._last_template, lmax)
+    return native.spec_field(None)

@@ -386,6 +386,51 @@ int gc_ens_score(gc_handle* h, const float* truth /* NULL = the truth uploaded l
 int gc_ens_download_fields(gc_handle* h, float* mean, float* variance);
 
 /*
+ * Spherical-harmonic power spectra of fields and ensembles on the device: the analysis direction
+ * of the transform gc_noise_* synthesises with.  The reference project has no spectral diagnostics; the yardstick is the
+ * definition below in float64 (tests/spectrum_reference.py).
+ * Grid: n_lat x n_lon nodes, node = lat_i n_lon + lon_j, latitudes ascending with the poles, phi_j = 2 pi j / n_lon (the
+ * grid of gc_noise_set_tables).  Basis: the real orthonormal Y_lm of noise.py.  Band limit 0 <= m <= l < lmax <= n_lon / 2.
+ * A field is [G, B, c_out] float32: N = B c_out independent columns.  amp_0 = 1, amp_m = sqrt(2):
+ *   Fourier    Fc[m][lat] = sum_j f(lat, j) cos_a[m][j],  cos_a[m][j] = amp_m cos(m phi_j) / n_lon   (Fs: sin_a), j ascending
+ *   Legendre   a_lm = sum_lat Q[m][l][lat] Fc[m][lat]  (b_lm from Fs), lat ascending; Q_m = pinv(A_m),
+ *              A_m[lat][l] = N_lm P_l^m(sin lat), l = m .. lmax-1: least squares, not quadrature (the latitudes with poles
+ *              cannot integrate degree 2 lmax); a field band-limited below lmax is recovered exactly
+ *   power      power[l] = (sum_m a_lm^2 + b_lm^2) / (4 pi), m ascending, the cosine term before the sine term; each square is
+ *              rounded before it is added.  For a band-limited field sum_l power[l] is the area mean of f^2.
+ * The tables are float32 (built in float64 on the host: spectra.py); every product and sum on the device is binary64, the
+ * Legendre step with fused multiply-adds.  Every sum has one writer and a fixed order (j, lat, m, members ascending) and
+ * there are no atomics on floats: the same call twice returns identical bytes.
+ * Ensemble spectra, of the members x_0 .. x_{M-1} of the gc_ens_* store and a truth y: the mean has the coefficients
+ * (sum_i a_i) / M, formed on the coefficients in double, ascending slot order.  Per (b, c, l), six raw sums, additive over dates:
+ *   sums[0] = power(y)            sums[1] = sum_i power(x_i)   sums[2] = power(mean)
+ *   sums[3] = sum_i power(x_i-y)  sums[4] = power(mean - y)    sums[5] = sum_i power(x_i - mean)
+ * every difference taken on the coefficients before squaring, every power() complete before it is added, members ascending.
+ * A column (b, c) in which the truth or any member holds a value that is not finite is NaN in every output (a transform
+ * cannot skip points); counter "spec_invalid_columns" counts those columns of the last call.
+ *   gc_spec_set_tables  legendre_analysis [lmax m][lmax l][n_lat] (zero for l < m), cos_a / sin_a [lmax][n_lon].  Needs
+ *                       gc_set_graph only.  GC_ERR_INVALID_ARGUMENT: n_lat n_lon != G, lmax outside 1 .. n_lon / 2.  Replaces
+ *                       earlier tables and every buffer sized by them.
+ *   gc_spec_field       power [B][c_out][lmax] of one field: host [G, B, c_out] (through pinned staging; the caller's buffer
+ *                       is free on return), or NULL = the handle's last sample, where it lies, after its pending f16x3 domain
+ *                       check is resolved as in gc_stash_sample.  Synchronous.  GC_ERR_STATE: no tables; NULL and no sample.
+ *   gc_ens_spectrum     truth: host [G, B, c_out], uploaded and kept, or NULL = the truth uploaded last (shared with
+ *                       gc_ens_score).  sums [6][B][c_out][lmax]; member_power [M][B][c_out][lmax] (NULL allowed): power(x_i).
+ *                       Synchronous.  GC_ERR_STATE: no tables, no member store, a slot not pushed since gc_ens_reserve, no truth.
+ * The Fourier step of one field ([2][lmax][n_lat][N] doubles) and the coefficient sets ([2][lmax][lmax][N] doubles each: one
+ * for gc_spec_field, M + 2 for gc_ens_spectrum) live in handle-owned buffers: made again when the tables change or a call
+ * needs more sets than there are, freed by gc_destroy.  None of these entries touches the conditioning, the last sample, the
+ * stash, the loss buffers, the member store's contents or the captured sample graphs.  Counters: "spec_calls" (calls so
+ * far), "spec_device_us" (HIP-event time of the last call), "spec_invalid_columns".
+ */
+int gc_spec_set_tables(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t lmax,
+                       const float* legendre_analysis /* [lmax][lmax][n_lat] */, const float* cos_a /* [lmax][n_lon] */,
+                       const float* sin_a /* [lmax][n_lon] */);
+int gc_spec_field(gc_handle* h, const float* field /* [G,B,c_out], NULL = the last sample */, double* power /* [B][c_out][lmax] */);
+int gc_ens_spectrum(gc_handle* h, const float* truth /* NULL = the truth uploaded last */, double* sums /* [6][B][c_out][lmax] */,
+                    double* member_power /* [M][B][c_out][lmax], NULL allowed */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are

@@ -1,17 +1,18 @@
 #!/usr/bin/env python3
-"""Register / scratch census of the gfx950 kernels: compiles csrc/gc_kernels.hip with
--Rpass-analysis=kernel-resource-usage and prints one line per kernel (VGPRs, AGPRs, spilled VGPRs, scratch bytes,
-waves per SIMD).  usage: tools/kernel_resources.py [-DGC_TU_A16] [regex]"""
+"""Register / scratch census of the gfx950 kernels: compiles csrc/gc_kernels.hip (or the translation unit named with
+--src=, e.g. --src=gc_spectrum.hip) with -Rpass-analysis=kernel-resource-usage and prints one line per kernel (VGPRs,
+AGPRs, spilled VGPRs, scratch bytes, waves per SIMD).  usage: tools/kernel_resources.py [--src=FILE] [-DGC_TU_A16] [regex]"""
 import os
 import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-flags = [a for a in sys.argv[1:] if a.startswith("-")]
+src = ([a[6:] for a in sys.argv[1:] if a.startswith("--src=")] or ["gc_kernels.hip"])[-1]
+flags = [a for a in sys.argv[1:] if a.startswith("-") and not a.startswith("--src=")]
 pats = [a for a in sys.argv[1:] if not a.startswith("-")]
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function", *flags,
-       "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "gencast-flax-nnx_amd", "csrc", "gc_kernels.hip"),
+       "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "gencast-flax-nnx_amd", "csrc", src),
        "-o", "/tmp/kernel_resources_probe.o"]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
