@@ -17,7 +17,9 @@ Public surface (mirrors the reference's call contracts):
                       ensemble, analysed on the GPU (no reference counterpart: GenCast.ensemble_spectra)
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
-                      (autoregressive_rollout); DeviceRollout keeps the context in HBM
+                      (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
+                      context per member there and scores the member states at every lead time (no reference
+                      counterpart: GenCast.ensemble_rollout)
 """
 from . import config, datasets, geometry, launch, losses, rollout, spectra, synthetic, verification, weights  # noqa: F401
 from .config import (DenoiserArchitectureConfig, NoiseConfig, NoiseEncoderConfig,  # noqa: F401
@@ -26,7 +28,8 @@ from .denoiser import Denoiser  # noqa: F401
 from .ensemble import EnsembleSampler, member_seed, member_shard  # noqa: F401
 from .gencast import GenCast, compute_loss, create_gencast_model, validation_loss  # noqa: F401
 from .nan_cleaning import NaNCleaner  # noqa: F401
-from .rollout import DeviceRollout, InputsAndResiduals, autoregressive_rollout  # noqa: F401
+from .rollout import (DeviceRollout, EnsembleRollout, EnsembleRolloutResult, InputsAndResiduals,  # noqa: F401
+                      autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
 from .verification import EnsembleScores  # noqa: F401
@@ -35,4 +38,4 @@ __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
            "InputsAndResiduals", "autoregressive_rollout", "DeviceRollout", "NaNCleaner", "launch", "losses",
            "compute_loss", "validation_loss", "verification", "EnsembleScores", "spectra", "EnsembleSpectra",
-           "SphericalAnalysis"]
+           "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels"]

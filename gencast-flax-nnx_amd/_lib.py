@@ -107,6 +107,12 @@ SIGNATURES = {
     "gc_ens_score": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
                                     ctypes.POINTER(ctypes.c_uint64)]),
     "gc_ens_download_fields": (ctypes.c_int, [_hp, _f32p, _f32p]),
+    "gc_ctx_reserve": (ctypes.c_int, [_hp, ctypes.c_int32]),
+    "gc_ctx_save": (ctypes.c_int, [_hp, ctypes.c_int32, _hp]),
+    "gc_ctx_load": (ctypes.c_int, [_hp, ctypes.c_int32, _hp]),
+    "gc_ctx_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
+    "gc_ens_push_state": (ctypes.c_int, [_hp, ctypes.c_int32, _hp, _i32p]),
+    "gc_ens_download_member": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
     "gc_spec_set_tables": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p, _f32p]),
     "gc_spec_field": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double)]),
     "gc_ens_spectrum": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
@@ -548,6 +554,38 @@ class NativeDenoiser:
     var = np.empty(self._shape_out(), dtype=np.float32)
     self._check(self._lib.gc_ens_download_fields(self._h, _ptr(mean, _f32p), _ptr(var, _f32p)))
     return mean, var
+
+  def ens_push_state(self, slot: int, state_src, src: Optional["NativeDenoiser"] = None) -> None:
+    """Slot <- the STATE of `src` (None: of this handle): channel j from conditioning channel `state_src[j]` of the
+    advanced context, from the sample where `state_src[j] < 0` (gc_ens_push_state; `rollout.state_channels`)."""
+    t = _i32(state_src)
+    if t.shape != (self.cfg.c_out,):
+      raise ValueError(f"state_src must have shape ({self.cfg.c_out},)")
+    self._check(self._lib.gc_ens_push_state(self._h, int(slot), None if src is None else src._h, _ptr(t, _i32p)))  # pylint: disable=protected-access
+
+  def ens_download_member(self, slot: int) -> np.ndarray:
+    """One stored member [G, B, c_out] (gc_ens_download_member)."""
+    out = np.empty(self._shape_out(), dtype=np.float32)
+    self._check(self._lib.gc_ens_download_member(self._h, int(slot), _ptr(out, _f32p)))
+    return out
+
+  # -- context store: one resident conditioning per ensemble member ----------------------------------
+  def ctx_reserve(self, n: int) -> None:
+    """A store of `n` (1..64) conditioning arrays on the handle; empties an earlier one (gc_ctx_reserve)."""
+    self._check(self._lib.gc_ctx_reserve(self._h, int(n)))
+
+  def ctx_save(self, slot: int, src: Optional["NativeDenoiser"] = None) -> None:
+    """Slot <- the current conditioning of `src` (None: of this handle), device to device (gc_ctx_save)."""
+    self._check(self._lib.gc_ctx_save(self._h, int(slot), None if src is None else src._h))  # pylint: disable=protected-access
+
+  def ctx_load(self, slot: int, dst: Optional["NativeDenoiser"] = None) -> None:
+    """The conditioning of `dst` (None: of this handle) <- slot, re-packed like `upload_cond_dev` (gc_ctx_load)."""
+    self._check(self._lib.gc_ctx_load(self._h, int(slot), None if dst is None else dst._h))  # pylint: disable=protected-access
+
+  def ctx_download(self, slot: int) -> np.ndarray:
+    out = np.empty(self._shape_in(), dtype=np.float32)
+    self._check(self._lib.gc_ctx_download(self._h, int(slot), _ptr(out, _f32p)))
+    return out
 
   # -- spherical-harmonic power spectra (analysed on the device) -------------------------------------
   def spec_set_tables(self, legendre_analysis, cos_a, sin_a) -> None:

@@ -1,7 +1,8 @@
 // Ensemble verification on the device (include/gencast_hip.h, gc_ens_*): a store of M member fields on the handle and
 // one scoring pass over it -- CRPS terms, error and spread of the ensemble mean, the rank histogram, and on request
 // the mean and variance fields.  Kernels and their host code live together here; DESIGN.md section 8c has the
-// definitions and the error bound the tests assert.
+// definitions and the error bound the tests assert.  Below them: the member STATE gather (gc_ens_push_state) and the
+// context store (gc_ctx_*) that let a multi-step ensemble forecast stay on the device.
 //
 // Per point (g, b, c), from the float32 members x_0 .. x_{M-1} and the truth y, in double:
 //   m  = (sum_i x_i) / M                       ascending slot order
@@ -204,6 +205,39 @@ static hipError_t launch_ens_finish(hipStream_t s, const double* part, const uns
   return hipGetLastError();
 }
 
+// Member state (gc_ens_push_state): output channel j of a member is conditioning channel state_src[j] of the ADVANCED
+// context, or sample channel j where the target has no input channel (state_src[j] < 0).  A gather, no arithmetic: the
+// stored value is bit for bit the value the next forecast step is conditioned on.  Thread layout of the kernels above:
+// thread t owns column t % wt = (b, j) of node lane t / wt, so the active threads of a block store q whole consecutive
+// member rows; the reads are a fixed permutation inside the node's B c_in conditioning floats.
+__global__ __launch_bounds__(256) void gc_ens_state_kernel(const float* __restrict__ cond, const float* __restrict__ sample,
+                                                            const int* __restrict__ state_src, int G, int B, int c_in,
+                                                            int c_out, float* __restrict__ member) {
+  const int W = B * c_out;
+  const int col0 = blockIdx.y * 256;
+  const int wt = min(256, W - col0);
+  const int q = 256 / wt;
+  const int lane = threadIdx.x / wt;
+  if (lane >= q) return;
+  const int col = col0 + ((int)threadIdx.x - lane * wt);
+  const int b = col / c_out;
+  const int sc = state_src[col - b * c_out];
+  const float* const from = sc >= 0 ? cond + (size_t)b * c_in + sc : sample + col;
+  const size_t stride = sc >= 0 ? (size_t)B * c_in : (size_t)W;
+  for (size_t n = (size_t)blockIdx.x * q + lane; n < (size_t)G; n += (size_t)gridDim.x * q)
+    member[n * W + col] = from[n * stride];
+}
+
+static hipError_t launch_ens_state(hipStream_t s, const float* cond, const float* sample, const int* state_src, int G, int B,
+                                   int c_in, int c_out, float* member) {
+  const int W = B * c_out;
+  const int q = 256 / std::min(256, W);
+  const int blocks = std::max(1, std::min(1024, (G + q - 1) / q));
+  hipLaunchKernelGGL(gc_ens_state_kernel, dim3(blocks, (W + 255) / 256), dim3(256), 0, s, cond, sample, state_src, G, B, c_in,
+                     c_out, member);
+  return hipGetLastError();
+}
+
 }  // namespace gc
 
 using namespace gci;
@@ -224,6 +258,30 @@ int ens_slot(gc_handle* h, int32_t slot) {
   return GC_OK;
 }
 
+size_t ctx_field(const gc_handle* h) { return (size_t)h->hg.G * h->cfg.batch * h->cfg.c_in; }
+
+int ctx_ready(gc_handle* h, int32_t slot) {
+  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (h->ctx_slots == 0) return fail(h, GC_ERR_STATE, "no context store (gc_ctx_reserve)");
+  if (slot < 0 || slot >= h->ctx_slots) return fail(h, GC_ERR_INVALID_ARGUMENT, "slot outside [0, n)");
+  return GC_OK;
+}
+
+// the handle on the other side of a context copy: same device, same [G, B, c_in], finalized
+int ctx_peer(gc_handle* h, const gc_handle* o) {
+  if (o->device != h->device) return fail(h, GC_ERR_INVALID_ARGUMENT, "the other handle is on another device");
+  if (!o->has_graph || o->hg.G != h->hg.G || o->cfg.batch != h->cfg.batch || o->cfg.c_in != h->cfg.c_in)
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "the other handle has other dimensions (G, batch, c_in)");
+  if (!o->finalized) return fail(h, GC_ERR_STATE, "gc_finalize has not been called on the other handle");
+  return GC_OK;
+}
+
+// a failure inside a call made on another handle is reported on the handle the caller asked
+int from_peer(gc_handle* h, gc_handle* o, int rc, const char* who) {
+  if (rc && o != h) h->err = std::string(who) + " handle: " + o->err;
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -242,6 +300,7 @@ int gc_ens_reserve(gc_handle* h, int32_t n_members) {
   h->ens_filled.clear();
   h->has_ens_fields = false;
   h->d_ens = nullptr;
+  h->d_ens_state_src = nullptr;
   const gc_config& c = h->cfg;
   const int G = h->hg.G, W = c.batch * c.c_out, M = n_members;
   const size_t blocks = (size_t)gc::loss_reduce_blocks(G, c.batch, c.c_out), tiles = (size_t)(W + 255) / 256;
@@ -249,10 +308,12 @@ int gc_ens_reserve(gc_handle* h, int32_t n_members) {
       (rc = dev_alloc(h, &h->d_ens_part, blocks * 6 * W, &h->ens_allocs)) ||
       (rc = dev_alloc(h, &h->d_ens_hpart, blocks * W * (M + 1) + blocks * tiles, &h->ens_allocs)) ||
       (rc = dev_alloc(h, &h->d_ens_sums, (size_t)6 * W, &h->ens_allocs)) ||
-      (rc = dev_alloc(h, &h->d_ens_hist, (size_t)W * (M + 1) + 1, &h->ens_allocs))) {
+      (rc = dev_alloc(h, &h->d_ens_hist, (size_t)W * (M + 1) + 1, &h->ens_allocs)) ||
+      (rc = dev_alloc(h, &h->d_ens_state_src, (size_t)c.c_out, &h->ens_allocs))) {
     free_allocs(&h->ens_allocs);
     return rc;
   }
+  h->ens_state_src.clear();
   for (hipEvent_t* e : {&h->ev_ens_free, &h->ev_ens_done})
     if (!*e) GC_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
   for (hipEvent_t* e : {&h->ev_ens0, &h->ev_ens1})
@@ -391,6 +452,158 @@ int gc_ens_download_fields(gc_handle* h, float* mean, float* variance) {
   if (mean) GC_HIP(h, hipMemcpyAsync(mean, h->d_ens_mean, bytes, hipMemcpyDeviceToHost, h->stream));
   if (variance) GC_HIP(h, hipMemcpyAsync(variance, h->d_ens_var, bytes, hipMemcpyDeviceToHost, h->stream));
   GC_HIP(h, hipStreamSynchronize(h->stream));
+  return GC_OK;
+  });
+}
+
+int gc_ens_push_state(gc_handle* h, int32_t slot, gc_handle* src, const int32_t* state_src) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ens_ready(h, true);
+  if (rc || (rc = ens_slot(h, slot))) return rc;
+  if (!state_src) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!src) src = h;
+  const gc_config& c = h->cfg;
+  if (src->device != h->device) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle is on another device");
+  if (!src->has_graph || src->hg.G != h->hg.G || src->cfg.batch != c.batch || src->cfg.c_out != c.c_out || src->cfg.c_in != c.c_in)
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle has other dimensions (G, batch, c_in, c_out)");
+  if (!src->finalized || !src->has_sample) return fail(h, GC_ERR_STATE, "no sample on the source handle (gc_sample_resident)");
+  if (!src->has_cond) return fail(h, GC_ERR_STATE, "no conditioning on the source handle (gc_upload_cond)");
+  for (int j = 0; j < c.c_out; ++j) {
+    if (state_src[j] >= c.c_in) return fail(h, GC_ERR_INVALID_ARGUMENT, "state_src: conditioning channel out of range");
+    if (state_src[j] >= 0 && std::find(src->h_slots.begin(), src->h_slots.end(), state_src[j]) != src->h_slots.end())
+      return fail(h, GC_ERR_INVALID_ARGUMENT, "state_src: a noisy slot holds no state");
+  }
+  GC_HIP(h, hipSetDevice(h->device));
+  if ((rc = from_peer(h, src, resolve_guard(src), "source"))) return rc;   // the state comes from the CHECKED sample
+  if (h->ens_state_src.size() != (size_t)c.c_out || !std::equal(state_src, state_src + c.c_out, h->ens_state_src.begin())) {
+    // every earlier gather is ordered into this stream (ev_ens_done): after the wait none reads the old table
+    GC_HIP(h, hipStreamSynchronize(h->stream));
+    GC_HIP(h, hipMemcpyAsync(h->d_ens_state_src, state_src, c.c_out * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    GC_HIP(h, hipStreamSynchronize(h->stream));      // `state_src` is the caller's again, and every stream sees the table
+    h->ens_state_src.assign(state_src, state_src + c.c_out);
+  }
+  float* const dst = h->d_ens + (size_t)slot * ens_field(h);
+  auto gather = [&] {
+    return gc::launch_ens_state(src->stream, src->d_feats, src->d_sx, h->d_ens_state_src, h->hg.G, c.batch, c.c_in, c.c_out, dst);
+  };
+  if (src == h) {
+    if ((rc = launch(h, gc::KC_PACK, gather))) return rc;
+  } else {
+    // on the SOURCE's stream, ordered against this handle's stream by events both ways, as in gc_ens_push
+    GC_HIP(h, hipEventRecord(h->ev_ens_free, h->stream));
+    GC_HIP(h, hipStreamWaitEvent(src->stream, h->ev_ens_free, 0));
+    if ((rc = from_peer(h, src, launch(src, gc::KC_PACK, gather), "source"))) return rc;
+    GC_HIP(h, hipEventRecord(h->ev_ens_done, src->stream));
+    GC_HIP(h, hipStreamWaitEvent(h->stream, h->ev_ens_done, 0));
+  }
+  h->ens_filled[(size_t)slot] = 1;
+  return GC_OK;
+  });
+}
+
+int gc_ens_download_member(gc_handle* h, int32_t slot, float* out) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ens_ready(h, true);
+  if (rc || (rc = ens_slot(h, slot))) return rc;
+  if (!out) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (!h->ens_filled[(size_t)slot]) return fail(h, GC_ERR_STATE, "member slot " + std::to_string(slot) + " has not been pushed");
+  GC_HIP(h, hipSetDevice(h->device));
+  // (every push, whichever stream made it, is ordered into this one)
+  GC_HIP(h, hipMemcpyAsync(out, h->d_ens + (size_t)slot * ens_field(h), ens_field(h) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  GC_HIP(h, hipStreamSynchronize(h->stream));
+  return GC_OK;
+  });
+}
+
+// ---- context store (include/gencast_hip.h, gc_ctx_*) ------------------------------------------------------------------
+// A slot is written and read on the stream of whichever handle's conditioning is copied, so a copy lies in stream order
+// with that handle's samples and context updates and waits for nothing else.  Order between streams is per slot: ev_w
+// is recorded behind the last write, ev_r behind the last read; a write waits for both, a read for the write and (so
+// that ev_r stands for ALL earlier reads) for the read before it.  The host never waits for a copy.
+
+int gc_ctx_reserve(gc_handle* h, int32_t n) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (n < 1 || n > 64) return fail(h, GC_ERR_UNSUPPORTED, "n must be in 1..64");
+  GC_HIP(h, hipSetDevice(h->device));
+  for (gc_handle::CtxSlot& c : h->ctx) {             // no copy into or out of the old store is still running
+    if (c.saved) GC_HIP(h, hipEventSynchronize(c.ev_w));
+    if (c.read) GC_HIP(h, hipEventSynchronize(c.ev_r));
+    c.saved = c.read = false;
+  }
+  free_allocs(&h->ctx_allocs);
+  h->ctx_slots = 0;
+  h->d_ctx = nullptr;
+  int rc;
+  if ((rc = dev_alloc(h, &h->d_ctx, (size_t)n * ctx_field(h), &h->ctx_allocs))) return rc;
+  if (h->ctx.size() < (size_t)n) h->ctx.resize((size_t)n);
+  for (int i = 0; i < n; ++i)
+    for (hipEvent_t* e : {&h->ctx[(size_t)i].ev_w, &h->ctx[(size_t)i].ev_r})
+      if (!*e) GC_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
+  h->ctx_slots = n;
+  return GC_OK;
+  });
+}
+
+int gc_ctx_save(gc_handle* h, int32_t slot, gc_handle* src) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ctx_ready(h, slot);
+  if (rc) return rc;
+  if (!src) src = h;
+  if ((rc = ctx_peer(h, src))) return rc;
+  if (!src->has_cond) return fail(h, GC_ERR_STATE, "no conditioning on the source handle (gc_upload_cond)");
+  GC_HIP(h, hipSetDevice(h->device));
+  if (src->guard_pending && (rc = from_peer(h, src, resolve_guard(src), "source"))) return rc;
+  gc_handle::CtxSlot& c = h->ctx[(size_t)slot];
+  if (c.saved) GC_HIP(h, hipStreamWaitEvent(src->stream, c.ev_w, 0));
+  if (c.read) GC_HIP(h, hipStreamWaitEvent(src->stream, c.ev_r, 0));
+  GC_HIP(h, hipMemcpyAsync(h->d_ctx + (size_t)slot * ctx_field(h), src->d_feats, ctx_field(h) * sizeof(float),
+                           hipMemcpyDeviceToDevice, src->stream));
+  GC_HIP(h, hipEventRecord(c.ev_w, src->stream));
+  c.saved = true;
+  c.read = false;                                    // (this write waited for the reads: ev_w now stands for them too)
+  return GC_OK;
+  });
+}
+
+int gc_ctx_load(gc_handle* h, int32_t slot, gc_handle* dst) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ctx_ready(h, slot);
+  if (rc) return rc;
+  if (!dst) dst = h;
+  if ((rc = ctx_peer(h, dst))) return rc;
+  gc_handle::CtxSlot& c = h->ctx[(size_t)slot];
+  if (!c.saved) return fail(h, GC_ERR_STATE, "context slot " + std::to_string(slot) + " has not been saved");
+  GC_HIP(h, hipSetDevice(h->device));
+  // a pending re-run needs the conditioning it sampled with (gc_upload_cond_dev)
+  if (dst->guard_pending && (rc = from_peer(h, dst, resolve_guard(dst), "destination"))) return rc;
+  GC_HIP(h, hipStreamWaitEvent(dst->stream, c.ev_w, 0));
+  if (c.read) GC_HIP(h, hipStreamWaitEvent(dst->stream, c.ev_r, 0));
+  GC_HIP(h, hipMemcpyAsync(dst->d_feats, h->d_ctx + (size_t)slot * ctx_field(h), ctx_field(h) * sizeof(float),
+                           hipMemcpyDeviceToDevice, dst->stream));
+  GC_HIP(h, hipEventRecord(c.ev_r, dst->stream));
+  c.read = true;
+  return from_peer(h, dst, gc_commit_cond(dst), "destination");
+  });
+}
+
+int gc_ctx_download(gc_handle* h, int32_t slot, float* out) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = ctx_ready(h, slot);
+  if (rc) return rc;
+  if (!out) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  gc_handle::CtxSlot& c = h->ctx[(size_t)slot];
+  if (!c.saved) return fail(h, GC_ERR_STATE, "context slot " + std::to_string(slot) + " has not been saved");
+  GC_HIP(h, hipSetDevice(h->device));
+  GC_HIP(h, hipStreamWaitEvent(h->stream, c.ev_w, 0));
+  GC_HIP(h, hipMemcpyAsync(out, h->d_ctx + (size_t)slot * ctx_field(h), ctx_field(h) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  GC_HIP(h, hipStreamSynchronize(h->stream));        // (complete on return: no read event to leave behind)
   return GC_OK;
   });
 }

@@ -1,6 +1,6 @@
 // Internals shared by the host translation units of libgencast_hip.so: the handle, the device-side weight layout,
 // the route of a forward, and the allocation / launch helpers.  gc_weights.hip lays the weights out, gc_forward.hip
-// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* entries, gc_spectrum.hip gc_spec_* and gc_ens_spectrum).
+// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* and gc_ctx_* entries, gc_spectrum.hip gc_spec_* and gc_ens_spectrum).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -218,6 +218,21 @@ struct gc_handle {
   hipEvent_t ev_ens_free = nullptr, ev_ens_done = nullptr;     // stream order of a push from another handle
   hipEvent_t ev_ens0 = nullptr, ev_ens1 = nullptr;             // brackets of the last scoring call
   int64_t ens_scores = 0, ens_score_device_us = 0, ens_invalid_points = 0;
+  // member STATES (gc_ens_push_state): output channel j of a member comes from conditioning channel ens_state_src[j]
+  // (-1: from the sample); the device copy is uploaded again only when the table changes
+  std::vector<int32_t> ens_state_src;
+  int* d_ens_state_src = nullptr;                // [c_out], made once
+
+  // context store (gc_ctx_*, gc_ensemble.hip): n conditioning arrays beside the member store, one per ensemble member
+  std::vector<void*> ctx_allocs;                 // the store: freed and replaced by gc_ctx_reserve
+  int ctx_slots = 0;                             // n (0: nothing reserved)
+  float* d_ctx = nullptr;                        // [n][G, B, c_in]
+  struct CtxSlot {
+    bool saved = false;                          // written since the last gc_ctx_reserve
+    bool read = false;                           // ev_r has been recorded since then
+    hipEvent_t ev_w = nullptr, ev_r = nullptr;   // behind the last write / the last read, on whichever stream made it
+  };
+  std::vector<CtxSlot> ctx;                      // (events are kept across reserves and destroyed with the handle)
 
   // spherical-harmonic power spectra (gc_spec_*, gc_ens_spectrum, gc_spectrum.hip)
   std::vector<void*> spec_allocs;                // sized by the tables: freed and replaced by gc_spec_set_tables

@@ -60,6 +60,7 @@ class GenCast:
     spread over GPUs by `EnsembleSampler` / `launch.py`.  `rngs`: an int seed, a numpy Generator, or an
     nnx.Rngs-like object whose `.noise()` returns key words (kept as it is: the sampler draws its keys from it)."""
     del gpu_mesh
+    self.task_config = task_config
     if isinstance(rngs, np.random.Generator) or hasattr(rngs, "noise"):
       self.rngs = rngs
     else:
@@ -113,6 +114,21 @@ class GenCast:
     if scores:
       return runner.scores_and_spectra(inputs, targets, forcings, num_members, lmax=lmax)
     return runner.spectra(inputs, targets, forcings, num_members, lmax=lmax)
+
+  def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, *, rngs=0, norm=None, concurrent_members=1,
+                       device_noise=None, **kwargs):
+    """Rolls `num_members` (2..64) members out `horizon` autoregressive steps with every member's context resident on
+    the GPU and scores their states against `targets[k]` at every lead time: `rollout.EnsembleRolloutResult` (per lead
+    time `EnsembleScores`, with `spectra=True` also `EnsembleSpectra`, with `fields=True` the mean and variance).  No
+    member leaves the device.  `rngs`: the base seed (member m is `DeviceRollout(...).run(rngs=member_seed(rngs, m))`);
+    `norm`: an `InputsAndResiduals` whose statistics apply (its own `ensemble_rollout` passes itself); `device_noise`
+    defaults to the sampler's; other keywords as `rollout.EnsembleRollout.run`."""
+    from .rollout import EnsembleRollout  # pylint: disable=import-outside-toplevel
+    if not isinstance(rngs, (int, np.integer)):
+      rngs = Sampler.seed_from(rngs)
+    runner = EnsembleRollout(self, norm, self.task_config, base_seed=int(rngs), concurrent_members=concurrent_members,
+                             device_noise=self._sampler.device_noise if device_noise is None else device_noise)
+    return runner.run(inputs, targets, forcings, horizon, num_members, **kwargs)
 
   # -- the diffusion objective, forward only -----------------------------------------------------------------
   def _denoising_eval(self, inputs, targets, forcings, rngs, noise_levels, noise, num_noise_draws, per_variable_weights):

@@ -136,6 +136,26 @@ class NaNCleaner:
       forcings = self._clean(forcings)
     return self.predictor.ensemble_spectra(inputs, targets, forcings, **kwargs)
 
+  def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, **kwargs):
+    """Inputs and forcings are cleaned.  The targets pass through unchanged (their NaNs are the points the device
+    skips) unless `spectra=True`: a transform cannot skip points, so they are then cleaned too, as `ensemble_spectra`
+    does, and the scores of the same call are over the filled field."""
+    given = (targets, inputs, forcings)
+    inputs = datasets.as_dataset(inputs)
+    targets = datasets.as_dataset(targets)
+    forcings = datasets.as_dataset(forcings)
+    if self._var_to_clean in inputs.keys():
+      inputs = self._clean(inputs)
+    if self._var_to_clean in forcings.keys():
+      forcings = self._clean(forcings)
+    if kwargs.get("spectra") and self._var_to_clean in targets.keys():
+      targets = self._clean(targets)
+    out = self.predictor.ensemble_rollout(inputs, targets, forcings, horizon, num_members, **kwargs)
+    if out.mean is not None and any(datasets.is_xarray(g) for g in given):   # xarray in -> xarray out
+      like = given[0].isel(time=slice(0, horizon)) if datasets.is_xarray(given[0]) else None
+      out.mean, out.variance = (datasets.to_xarray(datasets.as_dataset(f), like) for f in (out.mean, out.variance))
+    return out
+
   def loss(self, *args, **kwargs):
     raise NotImplementedError("training (loss) is outside the sampling hot path; the forward-only value of the "
                               "objective is denoising_loss / denoising_loss_and_predictions")

@@ -201,6 +201,12 @@ class InputsAndResiduals:
     return scores.scaled(np.concatenate(scale)), datasets.like_inputs(mean, *given), datasets.like_inputs(var, *given)
 
 
+  def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, **kwargs):
+    """`ensemble_rollout` of the wrapped predictor with this wrapper as its normalisation (`EnsembleRollout(norm=self)`):
+    the inputs go in RAW -- the device rollout normalises them itself and folds the residual arithmetic into its
+    per-channel context update -- and scores, spectra and fields come back in physical units."""
+    return self.predictor.ensemble_rollout(inputs, targets, forcings, horizon, num_members, norm=self, **kwargs)
+
   def ensemble_spectra(self, inputs, targets, forcings=None, **kwargs):
     """`ensemble_spectra` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets,
     in physical units: every power is multiplied by a^2 per channel (`EnsembleSpectra.scaled`; a: the residual scale of
@@ -504,3 +510,274 @@ class DeviceRollout:
     if datasets.is_xarray(given[0]):                        # predictions on the targets' time axis, like the harness's xr.concat
       return datasets.to_xarray(out, given[0].isel(time=slice(0, horizon)))
     return datasets.like_inputs(out, None, *given[1:])
+
+
+# ---------------------------------------------------------------------------------------------
+# ensemble rollout: every member's context resident on the device, scored at every lead time
+# ---------------------------------------------------------------------------------------------
+def state_channels(plan, c_out: int) -> np.ndarray:
+  """`state_src` [c_out] int32 for `gc_ens_push_state`: the conditioning channel that holds target channel j after
+  `gc_rollout_advance`, i.e. the channel c the plan fills from the sample (`kind[c]` 2 or 4) with `sidx[c] == j` --
+  the newest input frame of a variable that is both predicted and fed back.  -1: the target channel has no input
+  channel (its state is the sample itself).  Two conditioning channels claiming one j raise ValueError."""
+  kind, sidx = np.asarray(plan["kind"]), np.asarray(plan["sidx"])
+  out = np.full(int(c_out), -1, np.int32)
+  for c in np.flatnonzero((kind == 2) | (kind == 4)):
+    j = int(sidx[c])
+    if not 0 <= j < c_out:
+      raise ValueError(f"plan: sample index {j} of channel {c} is outside [0, {c_out})")
+    if out[j] >= 0:
+      raise ValueError(f"plan: conditioning channels {out[j]} and {c} both take target channel {j}")
+    out[j] = c
+  return out
+
+
+class _MemberNoise:
+  """The noise of one ensemble member over a whole rollout: ONE generator, seeded by (base_seed, member) only and
+  consumed in step order exactly as `DeviceRollout.run(..., rngs=member_seed(base_seed, member))` consumes its own --
+  the Philox key first (once, when anything is drawn on the device), then one host field per step unless the initial
+  states are drawn on the device or given."""
+
+  def __init__(self, sampler, base_seed: int, member: int, *, needs_key: bool, host_fields: bool):
+    from .ensemble import member_seed  # pylint: disable=import-outside-toplevel
+    self._sampler = sampler
+    self._gen = np.random.default_rng(member_seed(base_seed, member))
+    self.key = sampler.seed_from(self._gen) if needs_key else None
+    self.stream = 0                                       # Philox stream of the member's next device field
+    self._host_fields = host_fields
+
+  def host_field(self, shape, template) -> Optional[np.ndarray]:
+    if not self._host_fields:
+      return None
+    return np.asarray(self._sampler.draw_noise(self._gen, shape, template), np.float32)
+
+
+class EnsembleRolloutResult:
+  """What `EnsembleRollout.run` returns.  `scores`: one `verification.EnsembleScores` per lead time; `spectra`: one
+  `spectra.EnsembleSpectra` per lead time, or None; `mean` / `variance`: the ensemble mean and variance fields on the
+  targets' time axis (physical units), or None; `members`: `[horizon][M]` arrays [G, B, c_out] in the members' own
+  units (normalised with the input statistics under a normalisation wrapper), or None; `n_members`.
+  `scores_normalized` / `spectra_normalized`: the same lists as the device returned them, in the members' units
+  (`scores[k]` is `scores_normalized[k].scaled(s)`)."""
+
+  def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
+               scores_normalized=None, spectra_normalized=None):
+    self.scores = list(scores)
+    self.spectra = None if spectra is None else list(spectra)
+    self.scores_normalized = None if scores_normalized is None else list(scores_normalized)
+    self.spectra_normalized = None if spectra_normalized is None else list(spectra_normalized)
+    self.mean, self.variance, self.members = mean, variance, members
+    self.n_members = int(n_members if n_members is not None else self.scores[0].n_members)
+    if self.spectra is not None and len(self.spectra) != len(self.scores):
+      raise ValueError("scores and spectra must cover the same lead times")
+
+  @property
+  def horizon(self) -> int:
+    return len(self.scores)
+
+  def merge(self, other: "EnsembleRolloutResult") -> "EnsembleRolloutResult":
+    """The result over the union of the start dates, lead time by lead time (`EnsembleScores.merge`,
+    `EnsembleSpectra.merge`: raw sums add).  Fields and members belong to one date and are dropped."""
+    from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
+    if other.horizon != self.horizon:
+      raise ValueError(f"merge: horizons differ ({self.horizon} and {other.horizon})")
+    if other.n_members != self.n_members:
+      raise ValueError(f"merge: member counts differ ({self.n_members} and {other.n_members})")
+    if (self.spectra is None) != (other.spectra is None):
+      raise ValueError("merge: only one of the two results carries spectra")
+    def both(cls, a, b):
+      return None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
+
+    S, P = verification.EnsembleScores, _spectra.EnsembleSpectra
+    return EnsembleRolloutResult(both(S, self.scores, other.scores), both(P, self.spectra, other.spectra),
+                                 n_members=self.n_members,
+                                 scores_normalized=both(S, self.scores_normalized, other.scores_normalized),
+                                 spectra_normalized=both(P, self.spectra_normalized, other.spectra_normalized))
+
+
+class EnsembleRollout:
+  """M members rolled out `horizon` steps with every member's conditioning resident in HBM, scored at every lead time
+  on the device.  What is scored is each member's STATE -- the channels of its advanced context
+  (`state_channels`) -- not its sample: under `InputsAndResiduals` a sample is a residual relative to that member's own
+  previous frame and is not comparable between members from the second step on.
+
+  Member m is exactly `DeviceRollout(model, norm).run(..., rngs=member_seed(base_seed, m))`, bit for bit, however many
+  lanes (`concurrent_members`, `Denoiser.member_lanes`) are used and however the members fall into groups: its context
+  travels with it through the context store (`gc_ctx_save` / `gc_ctx_load`), its noise through `_MemberNoise` and, for
+  fields drawn on the device, the library's own stream counter ("noise_stream")."""
+
+  def __init__(self, model, norm: Optional[InputsAndResiduals] = None, task: cfg.TaskConfig = cfg.TASK, *,
+               base_seed: int = 0, concurrent_members: int = 1, device_noise: bool = False,
+               rank: int = 0, world_size: int = 1):
+    if concurrent_members < 1:
+      raise ValueError("concurrent_members must be >= 1")
+    self.model = model                                    # a GenCast (its sampler drives the native handles)
+    self.norm = norm
+    self.task = task
+    self.base_seed = int(base_seed)
+    self.concurrent_members = int(concurrent_members)
+    self.device_noise = bool(device_noise)
+    self.rank, self.world_size = int(rank), int(world_size)
+    self.last_lead_ms: List[float] = []
+
+  def member_noise(self, member: int, *, given: bool = False) -> _MemberNoise:
+    """The noise source of one member; `given`: the initial states come from `init_noise`."""
+    sampler = self.model._sampler  # pylint: disable=protected-access
+    on_device = self.device_noise and not given
+    churn = bool(getattr(sampler, "_stochastic_churn", False))
+    return _MemberNoise(sampler, self.base_seed, member, needs_key=on_device or churn,
+                        host_fields=not on_device and not given)
+
+  @staticmethod
+  def next_forcings(forcings: Dataset, k: int, horizon: int) -> Dataset:
+    """The forcing frame `gc_rollout_advance` takes after step k: frame k + 1.  After the LAST step the frame `horizon`
+    is used when `forcings` carries one; else frame `horizon - 1` is used again -- no sample ever reads those channels
+    (the rollout ends there) and no state channel is a forcing channel, so the scores cannot depend on them."""
+    del horizon                                           # (frame k + 1 can only be missing after the last step)
+    t = k + 1 if k + 1 < forcings.sizes.get("time", 0) else k
+    return isel_time(forcings, slice(t, t + 1))
+
+  def _stat(self, stat, template: Dataset, default: float) -> np.ndarray:
+    return np.concatenate([_per_channel_stat(stat, name, template[name], default)
+                           for name, _, _ in datasets.channel_layout(template)])
+
+  def run(self, inputs, targets, forcings, horizon: int, num_members: int, *, context_steps: int = 2,
+          init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
+          keep_members: bool = False) -> EnsembleRolloutResult:
+    """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
+    k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
+    spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
+    variance as Datasets on the targets' time axis.  `keep_members`: also every member state, downloaded.
+
+    Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
+    `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
+    error and spread spectra.  `truth_power`, `member_power` and `mean_power` are those of (x - l) s / s = x - l: a
+    constant offset moves l = 0 only, through a cross term the sums do not hold, so at l = 0 they
+    are the power of the field minus its climatological location, at l > 0 the field's own.  Fields are un-normalised
+    with s and l.  A NaN in `targets` is a point the device skips (`ens_invalid_points`).
+
+    After the last step the context is advanced once more to form the state; see `next_forcings` for the forcing frame
+    that update takes."""
+    import time as _time
+    from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
+    if self.world_size > 1:
+      raise ValueError("EnsembleRollout needs all members on one rank (world_size == 1): bring the other "
+                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    given = (targets, inputs, forcings)
+    inputs, targets, forcings = (datasets.as_dataset(x) for x in (inputs, targets, forcings))
+    M = int(num_members)
+    if horizon < 1 or targets.sizes.get("time", 0) < horizon:
+      raise ValueError(f"targets carry {targets.sizes.get('time', 0)} time steps (need horizon = {horizon})")
+    if init_noise is not None and (len(init_noise) != M or any(len(z) < horizon for z in init_noise)):
+      raise ValueError("init_noise must be [num_members][horizon] fields")
+    context = isel_time(inputs, slice(-context_steps, None))
+    template0 = isel_time(targets, slice(0, 1)).map(np.zeros_like)
+    forc0 = isel_time(forcings, slice(0, 1))
+    sampler = self.model._sampler  # pylint: disable=protected-access
+    den: Denoiser = self.model.denoiser
+    norm = self.norm
+    if norm is not None:
+      n_in = normalize(context, norm._scales, norm._locations)
+      n_fo = normalize(forc0, norm._scales, norm._locations)
+    else:
+      n_in, n_fo = context, forc0
+    cond, grid_shape, slots = den.init_for(n_in, template0, n_fo)
+    native = den.native
+    plan, forcing_cols = build_rollout_plan(context, forc0, template0, self.task, norm)
+    state_src = state_channels(plan, den.dims.c_out)
+    lanes = [native]
+    n_lanes = min(self.concurrent_members, M)
+    if n_lanes > 1:
+      lanes += list(den.member_lanes(n_lanes - 1))
+    for lane in lanes:
+      lane.set_noisy_slots(slots)
+      lane.rollout_plan(**plan)
+    native.upload_cond(cond)
+    native.ctx_reserve(M)
+    for m in range(M):                                    # every member starts from the initial conditioning
+      native.ctx_save(m)
+    native.ens_reserve(M)
+    native.ens_set_node_weight(verification.node_weights(template0))
+    if spectra:
+      _spectra.ensure_tables(native, template0, lmax)
+
+    given_noise = init_noise is not None
+    noise = [self.member_noise(m, given=given_noise) for m in range(M)]
+    churn = bool(getattr(sampler, "_stochastic_churn", False))
+    on_device = self.device_noise and not given_noise
+    if on_device or churn:
+      sampler.ensure_device_noise(native, template0)
+      key = (len(template0.coords["lat"]), len(template0.coords["lon"]))
+      for lane in lanes[1:]:                              # (the sampler remembers lane 0 only)
+        if getattr(lane, "_noise_tables_key", None) != key:
+          lane.noise_set_tables(*key, *sampler._noise_gen.device_tables())  # pylint: disable=protected-access
+          lane._noise_tables_key = key  # pylint: disable=protected-access
+    for lane in lanes:
+      lane.set_churn(sampler._per_step_churn_rates if churn else None,  # pylint: disable=protected-access
+                     getattr(sampler, "_noise_level_inflation_factor", 1.0))
+
+    sigmas = np.asarray(sampler.noise_levels, np.float32)
+    shape = (cond.shape[0], cond.shape[1], den.dims.c_out)
+    sizes = dict(forc0.sizes)
+    sizes.update(context.sizes)
+    rows_of = DeviceRollout(self.model, norm, self.task)._forcing_rows  # pylint: disable=protected-access
+    scale = self._stat(None if norm is None else norm._scales, template0, 1.0)
+    loc = self._stat(None if norm is None else norm._locations, template0, 0.0)
+
+    scores, spec, means, variances = [], ([] if spectra else None), [], []
+    raw_scores, raw_spec = [], ([] if spectra else None)
+    members = [] if keep_members else None
+    self.last_lead_ms = []
+    for k in range(horizon):
+      t0 = _time.perf_counter()
+      frows = (rows_of(self.next_forcings(forcings, k, horizon), forcing_cols, sizes, grid_shape)
+               if plan["n_forcing"] else None)
+      for g0 in range(0, M, len(lanes)):
+        group = list(zip(lanes, range(g0, min(M, g0 + len(lanes)))))
+        for lane, m in group:                             # enqueue only: every lane's sample is in flight after this
+          native.ctx_load(m, dst=lane)
+          if noise[m].key is not None:
+            lane.noise_seed(noise[m].key, noise[m].stream)
+          if on_device:
+            lane.noise_draw()
+          else:
+            z = np.asarray(init_noise[m][k], np.float32) if given_noise else noise[m].host_field(shape, template0)
+            lane.upload_noise(z)
+          lane.sample_resident(sigmas, skip_dead_call=True, want_stats=False)
+          if noise[m].key is not None:
+            noise[m].stream = lane.counter("noise_stream")   # churn fields drew too: the library is the one that knows
+        for lane, m in group:
+          lane.rollout_advance(frows)                     # resolves the lane's domain check, then advances ITS context
+          native.ctx_save(m, src=lane)
+          native.ens_push_state(m, state_src, src=lane)
+      # the truth of lead k in the members' units: (y - l) / s in float64, rounded once
+      tk = isel_time(targets, slice(k, k + 1))
+      y = np.transpose(datasets.dataset_to_stacked(tk, tk.sizes), (1, 2, 0, 3)).reshape(shape)
+      truth = y.astype(np.float32) if norm is None else \
+          ((y.astype(np.float64) - loc[None, None, :]) / scale[None, None, :]).astype(np.float32)
+      sums, hist = native.ens_score(truth, want_fields=fields)
+      raw_scores.append(verification.EnsembleScores(sums, hist, M))
+      scores.append(raw_scores[-1].scaled(scale))
+      if fields:
+        mean, var = native.ens_download_fields()
+        mean = (mean.astype(np.float64) * scale + loc).astype(np.float32)
+        var = (var.astype(np.float64) * scale * scale).astype(np.float32)
+        tmpl = tk.map(np.zeros_like)
+        means.append(Denoiser.unpack_outputs(mean, grid_shape, tmpl))
+        variances.append(Denoiser.unpack_outputs(var, grid_shape, tmpl))
+      if spectra:
+        raw_spec.append(_spectra.EnsembleSpectra(native.ens_spectrum(None), M))   # the truth is on the device already
+        spec.append(raw_spec[-1].scaled(scale))
+      if keep_members:
+        members.append([native.ens_download_member(m) for m in range(M)])
+      self.last_lead_ms.append(1e3 * (_time.perf_counter() - t0))
+
+    def on_time_axis(parts):
+      out = concat_time(parts)
+      if datasets.is_xarray(given[0]):
+        return datasets.to_xarray(out, given[0].isel(time=slice(0, horizon)))
+      return datasets.like_inputs(out, None, *given[1:])
+
+    return EnsembleRolloutResult(scores, spec, on_time_axis(means) if fields else None,
+                                 on_time_axis(variances) if fields else None, members, M,
+                                 scores_normalized=raw_scores, spectra_normalized=raw_spec)
