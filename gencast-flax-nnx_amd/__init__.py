@@ -32,10 +32,10 @@ from .rollout import (DeviceRollout, EnsembleRollout, EnsembleRolloutResult, Inp
                       autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
-from .verification import EnsembleScores  # noqa: F401
+from .verification import EnsembleScores, EventScores, EventSpec  # noqa: F401
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
            "InputsAndResiduals", "autoregressive_rollout", "DeviceRollout", "NaNCleaner", "launch", "losses",
            "compute_loss", "validation_loss", "verification", "EnsembleScores", "spectra", "EnsembleSpectra",
-           "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels"]
+           "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec"]

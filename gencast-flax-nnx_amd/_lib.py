@@ -116,6 +116,10 @@ SIGNATURES = {
     "gc_spec_set_tables": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p, _f32p]),
     "gc_spec_field": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double)]),
     "gc_ens_spectrum": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_event_set": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p, _i32p, ctypes.POINTER(ctypes.c_uint32)]),
+    "gc_ens_event_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_event_download": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8)]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -206,6 +210,7 @@ class NativeDenoiser:
     self._loss_groups = 0                      # groups of the loss weights this object handed to the handle
     self._ens_members = 0                      # slots of the member store this object reserved on the handle
     self._spec_lmax = 0                        # band limit of the analysis tables this object handed to the handle
+    self._event_thresholds = 0                 # threshold fields this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
   def _check(self, rc):
@@ -568,6 +573,56 @@ class NativeDenoiser:
     out = np.empty(self._shape_out(), dtype=np.float32)
     self._check(self._lib.gc_ens_download_member(self._h, int(slot), _ptr(out, _f32p)))
     return out
+
+  # -- ensemble event verification (exceedance tables formed on the device) ---------------------------
+  def ens_event_set(self, thresholds, directions, node_weight_q) -> None:
+    """`thresholds` [T, G, B, c_out] float32 (T in 1..8; NaN = not evaluated there), `directions` [T] (> 0: the event is
+    `value > threshold`, < 0: `value < threshold`), `node_weight_q` [G] uint32 (`verification.quantize_node_weights`):
+    gc_ens_event_set; needs `set_graph` only and survives `ens_reserve`."""
+    thr = _f32(thresholds)
+    if thr.ndim != 4 or thr.shape[1:] != self._shape_out():
+      raise ValueError(f"thresholds must be [T, {', '.join(str(n) for n in self._shape_out())}], got {thr.shape}")
+    d = _i32(directions)
+    if d.shape != (thr.shape[0],):
+      raise ValueError(f"directions must have shape ({thr.shape[0]},)")
+    w = np.asarray(node_weight_q)
+    if w.shape != (self.num_grid_nodes,) or w.dtype.kind not in "ui" or (w.size and (w.min() < 0 or w.max() > 0xFFFFFFFF)):
+      raise ValueError(f"node_weight_q must be unsigned 32-bit integers of shape ({self.num_grid_nodes},)")
+    w = np.ascontiguousarray(w, dtype=np.uint32)
+    self._check(self._lib.gc_ens_event_set(self._h, thr.shape[0], _ptr(thr, _f32p), _ptr(d, _i32p),
+                                           _ptr(w, ctypes.POINTER(ctypes.c_uint32))))
+    self._event_thresholds = int(thr.shape[0])
+
+  def ens_event_score(self, truth=None):
+    """-> (weighted [T, B, c_out, 2, M + 1] uint64, counts (same shape), invalid [T] uint64): the integer tables of
+    gc_ens_event_score over the member store (`verification.EventScores` derives the scores).  `truth` [G, B, c_out], or
+    None = the truth uploaded last (shared with `ens_score` / `ens_spectrum`)."""
+    if not self._event_thresholds:
+      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_event_set has not been called on this object)")
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    t = None
+    if truth is not None:
+      t = _f32(truth)
+      if t.shape != self._shape_out():
+        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    T, B, C = self._event_thresholds, self.cfg.batch, self.cfg.c_out
+    u64 = ctypes.POINTER(ctypes.c_uint64)
+    weighted = np.empty((T, B, C, 2, self._ens_members + 1), dtype=np.uint64)
+    counts = np.empty_like(weighted)
+    invalid = np.empty(T, dtype=np.uint64)
+    self._check(self._lib.gc_ens_event_score(self._h, None if t is None else _ptr(t, _f32p), _ptr(weighted, u64),
+                                             _ptr(counts, u64), _ptr(invalid, u64)))
+    return weighted, counts, invalid
+
+  def ens_event_codes(self, t: int) -> np.ndarray:
+    """uint8 [G, B, c_out] of threshold `t` from the last `ens_event_score`: k | (o << 7), 255 where the point did not
+    count (gc_ens_event_download; `verification.event_probability` decodes)."""
+    if not self._event_thresholds:
+      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_event_set has not been called on this object)")
+    code = np.empty(self._shape_out(), dtype=np.uint8)
+    self._check(self._lib.gc_ens_event_download(self._h, int(t), _ptr(code, ctypes.POINTER(ctypes.c_uint8))))
+    return code
 
   # -- context store: one resident conditioning per ensemble member ----------------------------------
   def ctx_reserve(self, n: int) -> None:

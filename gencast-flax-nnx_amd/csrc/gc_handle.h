@@ -1,6 +1,6 @@
 // Internals shared by the host translation units of libgencast_hip.so: the handle, the device-side weight layout,
 // the route of a forward, and the allocation / launch helpers.  gc_weights.hip lays the weights out, gc_forward.hip
-// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* and gc_ctx_* entries, gc_spectrum.hip gc_spec_* and gc_ens_spectrum).
+// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* and gc_ctx_* entries, gc_spectrum.hip gc_spec_* and gc_ens_spectrum, gc_events.hip gc_ens_event_*).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -247,6 +247,20 @@ struct gc_handle {
   unsigned* d_sp_flags = nullptr;                // [B c_out]: a value of the column was not finite
   hipEvent_t ev_sp0 = nullptr, ev_sp1 = nullptr; // brackets of the last spectrum call
   int64_t spec_calls = 0, spec_device_us = 0, spec_invalid_columns = 0;
+
+  // ensemble event verification (gc_ens_event_*, gc_events.hip): threshold fields and the tables scored from the member store
+  std::vector<void*> evt_allocs;                 // sized by T: thresholds, codes, weights; kept across gc_ens_reserve
+  std::vector<void*> evt_table_allocs;           // sized by T and M: made again by the scoring call that finds either changed
+  int evt_T = 0;                                 // thresholds set (0: none)
+  unsigned evt_dir_up = 0;                       // bit t: the event of threshold t is `value > thr`
+  int evt_table_T = 0, evt_table_M = 0;          // what d_evt_table is sized for
+  float* d_evt_thr = nullptr;                    // [T][G, B, c_out]
+  unsigned char* d_evt_code = nullptr;           // [T][G, B, c_out]: k | o << 7, 255 = not counted
+  unsigned* d_evt_wq = nullptr;                  // [G] integer node weights
+  unsigned long long* d_evt_table = nullptr;     // weighted [T][B c_out][2][M + 1], counts (same), invalid [T]
+  bool evt_scored = false;                       // a scoring call ran since gc_ens_event_set / gc_ens_reserve
+  hipEvent_t ev_evt0 = nullptr, ev_evt1 = nullptr;   // brackets of the last scoring call
+  int64_t evt_calls = 0, evt_device_us = 0, evt_invalid_points = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

@@ -95,6 +95,17 @@ class EnsembleSampler:
     (scores, mean, variance, spectra)."""
     return self._spectral(inputs, targets, forcings, num_members, bool(fields), lmax)
 
+  def events(self, inputs, targets, forcings, num_members: int, spec):
+    """Runs the members as `scores` does and counts, on the device, the events of `spec` (a `verification.EventSpec`:
+    thresholds per variable in the units of `targets`, one direction per event) among the members and in the truth:
+    `verification.EventScores` (Brier score and its decomposition, reliability curve, ROC, economic value, per event,
+    batch member and channel).  No member is downloaded.  Node weights:
+    `verification.quantize_node_weights(verification.node_weights(targets))`."""
+    if self.world_size > 1:
+      raise ValueError("EnsembleSampler.events needs all members on one rank (world_size == 1): bring the other "
+                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    return self._run(inputs, targets, forcings, num_members, None, events=spec)
+
   def _spectral(self, inputs, targets, forcings, num_members, score_fields, lmax):
     if self.world_size > 1:
       raise ValueError("EnsembleSampler.spectra needs all members on one rank (world_size == 1): bring the other "
@@ -102,9 +113,10 @@ class EnsembleSampler:
     return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
 
   def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,
-           lmax: Optional[int] = None):
+           lmax: Optional[int] = None, events=None):
     """`score_fields` None: members come back as Datasets (`__call__`) or, with `spectral`, only their spectra are
-    formed; else they are scored (`scores`), with `spectral` both."""
+    formed, or, with `events` (an EventSpec), only their event tables; else they are scored (`scores`), with `spectral`
+    both."""
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
     cond, grid_shape, slots = self._denoiser.init_for(inputs, template, forcings)
@@ -131,7 +143,7 @@ class EnsembleSampler:
         lane.set_noisy_slots(slots)
         lane.upload_cond_dev(ptr)                          # device-to-device, on the lane's own stream
     scoring = score_fields is not None
-    if scoring or spectral:
+    if scoring or spectral or events is not None:
       native.ens_reserve(num_members)
     if scoring:
       native.ens_set_node_weight(verification.node_weights(template))
@@ -144,14 +156,19 @@ class EnsembleSampler:
         lane.upload_noise(self.member_noise(m, shape, template))
         lane.sample_resident(sigmas, skip_dead_call=True, want_stats=False)
       for lane, m in zip(lanes, group):
-        if scoring or spectral:
+        if scoring or spectral or events is not None:
           native.ens_push(m, src=lane)
         else:
           out.append((m, datasets.like_inputs(Denoiser.unpack_outputs(lane.download_sample(), grid_shape, template),
                                               targets_template, inputs, forcings)))
-    if not scoring and not spectral:
+    if not scoring and not spectral and events is None:
       return out
     truth = np.transpose(datasets.dataset_to_stacked(template, template.sizes), (1, 2, 0, 3)).reshape(shape)
+    if events is not None:
+      wq, scale = verification.quantize_node_weights(verification.node_weights(template))
+      native.ens_event_set(events.packed(template), events.directions, wq)
+      weighted, counts, invalid = native.ens_event_score(truth)
+      return verification.EventScores(weighted, counts, num_members, events.directions, scale, invalid)
     if not scoring:
       return _spectra.EnsembleSpectra(native.ens_spectrum(truth), num_members)
     sums, hist = native.ens_score(truth, want_fields=score_fields)

@@ -115,11 +115,23 @@ class GenCast:
       return runner.scores_and_spectra(inputs, targets, forcings, num_members, lmax=lmax)
     return runner.spectra(inputs, targets, forcings, num_members, lmax=lmax)
 
+  def ensemble_events(self, inputs, targets, forcings=None, *, num_members, spec, rngs=0, concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and counts the events of `spec`
+    (`verification.EventSpec`: thresholds per variable in the units of `targets`, a direction per event) among them and
+    in `targets`, on the GPU: `verification.EventScores` -- Brier score with its decomposition, reliability curve, ROC
+    area, relative economic value, per event, batch member and channel.  No member leaves the device."""
+    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
+    if not isinstance(rngs, (int, np.integer)):
+      rngs = Sampler.seed_from(rngs)
+    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    return runner.events(inputs, targets, forcings, num_members, spec)
+
   def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, *, rngs=0, norm=None, concurrent_members=1,
                        device_noise=None, **kwargs):
     """Rolls `num_members` (2..64) members out `horizon` autoregressive steps with every member's context resident on
     the GPU and scores their states against `targets[k]` at every lead time: `rollout.EnsembleRolloutResult` (per lead
-    time `EnsembleScores`, with `spectra=True` also `EnsembleSpectra`, with `fields=True` the mean and variance).  No
+    time `EnsembleScores`, with `spectra=True` also `EnsembleSpectra`, with `fields=True` the mean and variance, with
+    `events=EventSpec` also `EventScores`).  No
     member leaves the device.  `rngs`: the base seed (member m is `DeviceRollout(...).run(rngs=member_seed(rngs, m))`);
     `norm`: an `InputsAndResiduals` whose statistics apply (its own `ensemble_rollout` passes itself); `device_noise`
     defaults to the sampler's; other keywords as `rollout.EnsembleRollout.run`."""

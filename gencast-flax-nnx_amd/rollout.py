@@ -201,6 +201,16 @@ class InputsAndResiduals:
     return scores.scaled(np.concatenate(scale)), datasets.like_inputs(mean, *given), datasets.like_inputs(var, *given)
 
 
+  def ensemble_events(self, inputs, targets, forcings=None, *, spec, **kwargs):
+    """`ensemble_events` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.
+    The thresholds of `spec` (physical units) go through the SAME map as the targets
+    (`_subtract_input_and_normalize_target`: for a residual variable the last input frame is subtracted, per batch
+    member -- which is why thresholds are full fields).  Scales are positive, so no direction flips; the tables are
+    integers and carry no unit."""
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    nspec = spec.mapped(datasets.as_dataset(targets), lambda name, v: self._subtract_input_and_normalize_target(raw, name, v))
+    return self.predictor.ensemble_events(ni, nt, forcings=nf, spec=nspec, **kwargs)
+
   def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, **kwargs):
     """`ensemble_rollout` of the wrapped predictor with this wrapper as its normalisation (`EnsembleRollout(norm=self)`):
     the inputs go in RAW -- the device rollout normalises them itself and folds the residual arithmetic into its
@@ -558,11 +568,15 @@ class EnsembleRolloutResult:
   targets' time axis (physical units), or None; `members`: `[horizon][M]` arrays [G, B, c_out] in the members' own
   units (normalised with the input statistics under a normalisation wrapper), or None; `n_members`.
   `scores_normalized` / `spectra_normalized`: the same lists as the device returned them, in the members' units
-  (`scores[k]` is `scores_normalized[k].scaled(s)`)."""
+  (`scores[k]` is `scores_normalized[k].scaled(s)`).  `events`: one `verification.EventScores` per lead time, or None
+  (integer tables: no unit, nothing to rescale)."""
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
-               scores_normalized=None, spectra_normalized=None):
+               scores_normalized=None, spectra_normalized=None, events=None):
     self.scores = list(scores)
+    self.events = None if events is None else list(events)
+    if self.events is not None and len(self.events) != len(self.scores):
+      raise ValueError("scores and events must cover the same lead times")
     self.spectra = None if spectra is None else list(spectra)
     self.scores_normalized = None if scores_normalized is None else list(scores_normalized)
     self.spectra_normalized = None if spectra_normalized is None else list(spectra_normalized)
@@ -585,6 +599,8 @@ class EnsembleRolloutResult:
       raise ValueError(f"merge: member counts differ ({self.n_members} and {other.n_members})")
     if (self.spectra is None) != (other.spectra is None):
       raise ValueError("merge: only one of the two results carries spectra")
+    if (self.events is None) != (other.events is None):
+      raise ValueError("merge: only one of the two results carries events")
     def both(cls, a, b):
       return None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
 
@@ -592,7 +608,8 @@ class EnsembleRolloutResult:
     return EnsembleRolloutResult(both(S, self.scores, other.scores), both(P, self.spectra, other.spectra),
                                  n_members=self.n_members,
                                  scores_normalized=both(S, self.scores_normalized, other.scores_normalized),
-                                 spectra_normalized=both(P, self.spectra_normalized, other.spectra_normalized))
+                                 spectra_normalized=both(P, self.spectra_normalized, other.spectra_normalized),
+                                 events=both(verification.EventScores, self.events, other.events))
 
 
 class EnsembleRollout:
@@ -643,11 +660,15 @@ class EnsembleRollout:
 
   def run(self, inputs, targets, forcings, horizon: int, num_members: int, *, context_steps: int = 2,
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
-          keep_members: bool = False) -> EnsembleRolloutResult:
+          keep_members: bool = False, events=None) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
     variance as Datasets on the targets' time axis.  `keep_members`: also every member state, downloaded.
+    `events`: a `verification.EventSpec` (thresholds in the physical units of `targets`), or a sequence of `horizon` of
+    them with equal directions (a climatology that moves with the lead time): also the event tables per lead time,
+    `EnsembleRolloutResult.events`, counted right after the scores on the truth already on the device.  The thresholds
+    take the map of the truth, (thr - l) / s in float64, rounded once; s > 0, so no direction flips.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -700,6 +721,12 @@ class EnsembleRollout:
     native.ens_set_node_weight(verification.node_weights(template0))
     if spectra:
       _spectra.ensure_tables(native, template0, lmax)
+    event_specs = None
+    if events is not None:
+      event_specs = list(events) if isinstance(events, (list, tuple)) else [events]
+      if len(event_specs) not in (1, horizon) or any(s.directions != event_specs[0].directions for s in event_specs):
+        raise ValueError(f"events must be one EventSpec or {horizon} of them with equal directions")
+      wq, wq_scale = verification.quantize_node_weights(verification.node_weights(template0))
 
     given_noise = init_noise is not None
     noise = [self.member_noise(m, given=given_noise) for m in range(M)]
@@ -727,6 +754,16 @@ class EnsembleRollout:
     scores, spec, means, variances = [], ([] if spectra else None), [], []
     raw_scores, raw_spec = [], ([] if spectra else None)
     members = [] if keep_members else None
+    event_scores = None if event_specs is None else []
+
+    def set_events(spec):
+      thr = spec.packed(template0)
+      if norm is not None:
+        thr = ((thr.astype(np.float64) - loc) / scale).astype(np.float32)
+      native.ens_event_set(thr, spec.directions, wq)
+
+    if event_specs is not None and len(event_specs) == 1:
+      set_events(event_specs[0])                          # uploaded once: they survive the store and every lead time
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -758,6 +795,11 @@ class EnsembleRollout:
       sums, hist = native.ens_score(truth, want_fields=fields)
       raw_scores.append(verification.EnsembleScores(sums, hist, M))
       scores.append(raw_scores[-1].scaled(scale))
+      if event_specs is not None:
+        if len(event_specs) > 1:
+          set_events(event_specs[k])
+        ew, ec, ei = native.ens_event_score(None)          # the truth is on the device already
+        event_scores.append(verification.EventScores(ew, ec, M, event_specs[0].directions, wq_scale, ei))
       if fields:
         mean, var = native.ens_download_fields()
         mean = (mean.astype(np.float64) * scale + loc).astype(np.float32)
@@ -780,4 +822,4 @@ class EnsembleRollout:
 
     return EnsembleRolloutResult(scores, spec, on_time_axis(means) if fields else None,
                                  on_time_axis(variances) if fields else None, members, M,
-                                 scores_normalized=raw_scores, spectra_normalized=raw_spec)
+                                 scores_normalized=raw_scores, spectra_normalized=raw_spec, events=event_scores)

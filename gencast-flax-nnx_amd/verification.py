@@ -13,10 +13,18 @@ additive -- batches, initial dates and ranks merge by `merge` -- and derives eve
   fair CRPS = (S4 - S5/2)/S0      ensemble CRPS = (S4 - (M-1)/M S5/2)/S0
 
 There is no NumPy implementation of the metrics in here: the per-point work exists on the device only.
+
+Events (`gc_ens_event_score`): for T threshold fields with a direction each, the device counts at
+every valid point k = the members inside the event and o = whether the truth is, and hands back per (threshold, batch,
+channel) the integer table `weighted[o][k]` = sum of the quantised node weights (`quantize_node_weights`) and `counts[o][k]`.
+`EventScores` keeps the tables raw (they add over dates, exactly) and derives the Brier score with its decomposition,
+the reliability curve, the ROC and the relative economic value; `EventSpec` carries thresholds given per variable in
+physical units down to the packed fields; `event_probability` decodes the per-point bytes the device keeps.
 """
 from __future__ import annotations
 
-from typing import Dict, Sequence
+import math
+from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -135,3 +143,280 @@ def node_weights(template) -> np.ndarray:
   if "lat" not in sizes or "lon" not in sizes:
     raise ValueError("template must have 'lat' and 'lon' dimensions")
   return np.repeat(losses.normalized_latitude_weights(template), sizes["lon"]).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------
+# events: exceedance probabilities against thresholds (gc_ens_event_*)
+# ---------------------------------------------------------------------------------------------
+_U32_MAX = 4294967295
+
+
+def quantize_node_weights(w) -> Tuple[np.ndarray, float]:
+  """-> (wq [G] uint32, scale): wq = rint(w scale) in float64, scale = 2^e with e the largest integer for which
+  max(w) 2^e <= 2^32 - 1.  The device adds wq as integers, so sums are exact and have no order; a column total is at most
+  G (2^32 - 1), below 2^53 for G <= 2^21, so `total / scale` in float64 is exact too.  `w` must be finite, >= 0 and not
+  all zero (ValueError)."""
+  w = np.asarray(w, dtype=np.float64).reshape(-1)
+  if w.size == 0 or not np.all(np.isfinite(w)) or np.any(w < 0.0) or not np.any(w > 0.0):
+    raise ValueError("node weights must be finite, >= 0 and not all zero")
+  top = float(w.max())
+  e = int(math.floor(math.log2(_U32_MAX / top)))
+  while math.ldexp(top, e + 1) <= _U32_MAX:               # (ldexp by a power of two is exact: the comparisons are)
+    e += 1
+  while math.ldexp(top, e) > _U32_MAX:
+    e -= 1
+  scale = math.ldexp(1.0, e)
+  return np.rint(w * scale).astype(np.uint32), scale
+
+
+def event_probability(code, n_members: int) -> Tuple[np.ndarray, np.ndarray]:
+  """The per-point bytes of `NativeDenoiser.ens_event_codes` -> (probability k / M as float32, NaN where the point did
+  not count; observed flag as bool, False there)."""
+  code = np.asarray(code, dtype=np.uint8)
+  valid = code != 255
+  k = (code & 127).astype(np.float32)
+  prob = np.where(valid, k / np.float32(n_members), np.float32(np.nan)).astype(np.float32)
+  return prob, valid & ((code >> 7) == 1)
+
+
+class EventSpec:
+  """Thresholds of T events, per target variable and in the physical units of the targets, with one direction per
+  event (> 0: the event is `value > threshold`, < 0: `value < threshold`; both strict).
+
+  `thresholds`: {variable: array}, leading axis T; the remaining axes broadcast, right-aligned, against the variable's
+  dims other than batch and time (a scalar per event: shape (T,); per level: (T, level, 1, 1); a climatological map:
+  (T, lat, lon)).  An array with one axis per dim of the variable after the leading one (batch and time included) is
+  taken as the full field it is.  A target variable left out is NaN: not evaluated.  Values are cast to the dtype of the
+  target variable, so a threshold and a target of equal value stay equal through every map both go through."""
+
+  def __init__(self, thresholds: Mapping[str, np.ndarray], directions: Sequence[int]):
+    self.directions = tuple(int(np.sign(d)) for d in directions)
+    if not self.directions or any(d == 0 for d in self.directions):
+      raise ValueError("directions must be non-empty and non-zero")
+    self.thresholds = {k: np.asarray(v, dtype=np.float64) for k, v in thresholds.items()}
+    for k, v in self.thresholds.items():
+      if v.ndim < 1 or v.shape[0] != len(self.directions):
+        raise ValueError(f"thresholds[{k!r}] must have a leading axis of length {len(self.directions)}, got {v.shape}")
+
+  @property
+  def n_thresholds(self) -> int:
+    return len(self.directions)
+
+  def fields(self, template) -> List[datasets.Dataset]:
+    """T Datasets shaped like `template` (one per event), NaN for a variable without thresholds."""
+    template = datasets.as_dataset(template)
+    for name in self.thresholds:
+      if name not in template:
+        raise ValueError(f"thresholds given for {name!r}, which is not a target variable")
+    out: List[Dict[str, datasets.Variable]] = [{} for _ in self.directions]
+    for name, var in template.items():
+      shape, dtype = np.shape(var.data), np.asarray(var.data).dtype
+      thr = self.thresholds.get(name)
+      if thr is None:
+        full = np.full((self.n_thresholds,) + shape, np.nan, dtype)
+      else:
+        rest = [d for d in var.dims if d not in ("batch", "time")]
+        if thr.ndim - 1 == len(var.dims) and len(var.dims) > len(rest):
+          view = thr
+        else:
+          if thr.ndim - 1 > len(rest):
+            raise ValueError(f"thresholds[{name!r}] has shape {thr.shape}: more axes than {tuple(rest)}")
+          tail = (1,) * (len(rest) - (thr.ndim - 1)) + thr.shape[1:]
+          sizes = dict(zip(rest, tail))
+          view = thr.reshape((thr.shape[0],) + tuple(sizes.get(d, 1) for d in var.dims))
+        full = np.broadcast_to(view, (self.n_thresholds,) + shape).astype(dtype)
+      for t in range(self.n_thresholds):
+        out[t][name] = datasets.Variable(var.dims, full[t])
+    return [datasets.Dataset(v, template.coords) for v in out]
+
+  def mapped(self, template, fn) -> "EventSpec":
+    """The spec with every threshold field sent through `fn(name, Variable) -> Variable` (the map the targets go
+    through under a normalisation wrapper); the result holds full fields."""
+    fields = self.fields(template)
+    names = list(datasets.as_dataset(template).keys())
+    return EventSpec({name: np.stack([np.asarray(fn(name, f[name]).data) for f in fields]) for name in names},
+                     self.directions)
+
+  def packed(self, template) -> np.ndarray:
+    """[T, G, B, c_out] float32 in the channel order of `datasets.channel_layout` (node = lat_i n_lon + lon_j)."""
+    template = datasets.as_dataset(template)
+    sizes = template.sizes
+    out = []
+    for f in self.fields(template):
+      st = np.transpose(datasets.dataset_to_stacked(f, sizes), (1, 2, 0, 3))
+      out.append(st.reshape((st.shape[0] * st.shape[1],) + st.shape[2:]))
+    return np.ascontiguousarray(np.stack(out), dtype=np.float32)
+
+
+class EventScores:
+  """The integer tables of `gc_ens_event_score`: `weighted` and `counts` [T, B, c_out, 2, M + 1] uint64 (axis -2: the
+  truth outside / inside the event, axis -1: k members inside), `invalid` [T] points skipped, with the member count M,
+  the directions [T] and the `scale` of the quantised node weights.  Every derived score is [T, B, c_out] float64 (curves
+  carry one more axis); a ratio whose denominator is zero -- the event never or always observed -- is NaN, not an error.
+
+  With n_k = (weighted[0][k] + weighted[1][k]) / scale, o_k = weighted[1][k] / scale, N = sum n_k, O = sum o_k, s = O / N
+  and p_k = k / M.  The bins are the distinct forecast values, so brier = reliability - resolution + uncertainty holds
+  exactly in exact arithmetic."""
+
+  def __init__(self, weighted, counts, n_members: int, directions: Sequence[int], scale: float, invalid=None):
+    self.weighted = np.asarray(weighted, dtype=np.uint64)
+    self.counts = np.asarray(counts, dtype=np.uint64)
+    self.n_members = int(n_members)
+    self.directions = tuple(int(np.sign(d)) for d in directions)
+    self.scale = float(scale)
+    if self.n_members < 2:
+      raise ValueError("n_members must be >= 2")
+    if self.weighted.ndim != 5 or self.weighted.shape[-2:] != (2, self.n_members + 1):
+      raise ValueError(f"weighted must be [T, batch, channels, 2, {self.n_members + 1}], got {self.weighted.shape}")
+    if self.counts.shape != self.weighted.shape:
+      raise ValueError(f"counts must be {self.weighted.shape}, got {self.counts.shape}")
+    if len(self.directions) != self.weighted.shape[0] or any(d == 0 for d in self.directions):
+      raise ValueError(f"directions must be {self.weighted.shape[0]} non-zero signs")
+    if not (self.scale > 0.0 and math.isfinite(self.scale)):
+      raise ValueError("scale must be positive and finite")
+    self.invalid = (np.zeros(self.weighted.shape[0], np.uint64) if invalid is None
+                    else np.asarray(invalid, dtype=np.uint64).reshape(self.weighted.shape[0]))
+
+  # -- the table in float64 (exact: see quantize_node_weights) -------------------------------------------------
+  @property
+  def _n(self) -> np.ndarray:
+    return (self.weighted[..., 0, :] + self.weighted[..., 1, :]).astype(np.float64) / self.scale
+
+  @property
+  def _o(self) -> np.ndarray:
+    return self.weighted[..., 1, :].astype(np.float64) / self.scale
+
+  @property
+  def _p(self) -> np.ndarray:
+    return np.arange(self.n_members + 1, dtype=np.float64) / float(self.n_members)
+
+  @staticmethod
+  def _ratio(a, b) -> np.ndarray:
+    a, b = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64))
+    out = np.full(a.shape, np.nan)
+    np.divide(a, b, out=out, where=b != 0.0)
+    return out
+
+  @property
+  def valid_weight(self) -> np.ndarray:
+    """N: the node weight of the points that counted."""
+    return self._n.sum(axis=-1)
+
+  @property
+  def valid_points(self) -> np.ndarray:
+    return self.counts.sum(axis=(-1, -2))
+
+  @property
+  def base_rate(self) -> np.ndarray:
+    return self._ratio(self._o.sum(axis=-1), self._n.sum(axis=-1))
+
+  @property
+  def brier(self) -> np.ndarray:
+    n, o, p = self._n, self._o, self._p
+    return self._ratio(((n - o) * p ** 2 + o * (1.0 - p) ** 2).sum(axis=-1), n.sum(axis=-1))
+
+  @property
+  def brier_fair(self) -> np.ndarray:
+    """Ferro's fair Brier score: unbiased for the score of the distribution the members were drawn from."""
+    m = float(self.n_members)
+    k = np.arange(self.n_members + 1, dtype=np.float64)
+    n = self._n
+    return self.brier - self._ratio((n * (k * (m - k) / (m * m * (m - 1.0)))).sum(axis=-1), n.sum(axis=-1))
+
+  @property
+  def reliability(self) -> np.ndarray:
+    n, o, p = self._n, self._o, self._p
+    obar = np.where(n > 0.0, self._ratio(o, n), 0.0)
+    return self._ratio((n * (p - obar) ** 2).sum(axis=-1), n.sum(axis=-1))    # (an empty bin has n = 0: it adds 0)
+
+  @property
+  def resolution(self) -> np.ndarray:
+    n, o = self._n, self._o
+    s = self.base_rate[..., None]
+    obar = np.where(n > 0.0, self._ratio(o, n), 0.0)
+    return self._ratio(np.where(n > 0.0, n * (obar - s) ** 2, 0.0).sum(axis=-1), n.sum(axis=-1))
+
+  @property
+  def uncertainty(self) -> np.ndarray:
+    s = self.base_rate
+    return s * (1.0 - s)
+
+  @property
+  def brier_skill(self) -> np.ndarray:
+    return 1.0 - self._ratio(self.brier, self.uncertainty)
+
+  @property
+  def reliability_curve(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(p_k [M + 1], observed frequency o_k / n_k [T, B, c_out, M + 1] (NaN for an empty bin), n_k (same shape))."""
+    return self._p, self._ratio(self._o, self._n), self._n
+
+  def _hits_and_false_alarms(self) -> Tuple[np.ndarray, np.ndarray]:
+    """H_j, F_j for the decision levels j = 0 .. M + 1 ("warn when k >= j"): [T, B, c_out, M + 2]."""
+    n, o = self._n, self._o
+    zero = np.zeros(n.shape[:-1] + (1,))
+    tail = lambda a: np.concatenate([np.cumsum(a[..., ::-1], axis=-1)[..., ::-1], zero], axis=-1)
+    return tail(o), tail(n - o)
+
+  @property
+  def hit_rate(self) -> np.ndarray:
+    h, _ = self._hits_and_false_alarms()
+    return self._ratio(h, self._o.sum(axis=-1)[..., None])
+
+  @property
+  def false_alarm_rate(self) -> np.ndarray:
+    _, f = self._hits_and_false_alarms()
+    return self._ratio(f, (self._n.sum(axis=-1) - self._o.sum(axis=-1))[..., None])
+
+  @property
+  def roc_area(self) -> np.ndarray:
+    """The trapezoid rule through the M + 2 points (false_alarm_rate_j, hit_rate_j)."""
+    h, f = self.hit_rate, self.false_alarm_rate
+    return (0.5 * (f[..., :-1] - f[..., 1:]) * (h[..., :-1] + h[..., 1:])).sum(axis=-1)
+
+  def economic_value(self, alpha) -> np.ndarray:
+    """The relative economic value at cost/loss ratios `alpha` in (0, 1): [T, B, c_out] + alpha.shape.  Per decision
+    level E_j = alpha (H_j + F_j) / N + (O - H_j) / N; value = max_j (E_clim - E_j) / (E_clim - E_perf) with
+    E_clim = min(alpha, s), E_perf = alpha s."""
+    alpha = np.asarray(alpha, dtype=np.float64)
+    if np.any(alpha <= 0.0) or np.any(alpha >= 1.0):
+      raise ValueError("alpha must lie in (0, 1)")
+    h, f = self._hits_and_false_alarms()
+    big_n, big_o = self._n.sum(axis=-1), self._o.sum(axis=-1)
+    extra = (None,) * alpha.ndim
+    lev = lambda a: a[(Ellipsis,) + extra]                 # [T, B, c_out, M + 2] -> [..., M + 2, alpha...]
+    col = lambda a: a[(Ellipsis, None) + extra]            # [T, B, c_out]        -> [..., 1, alpha...]
+    e = self._ratio(alpha * lev(h + f), col(big_n)) + self._ratio(col(big_o) - lev(h), col(big_n))
+    s = col(self.base_rate)
+    e_clim, e_perf = np.minimum(alpha, s), alpha * s
+    value = self._ratio(e_clim - e, e_clim - e_perf)
+    return np.max(value, axis=3)                           # (the denominators do not depend on j: NaN at all levels or none)
+
+  @staticmethod
+  def merge(parts: Sequence["EventScores"]) -> "EventScores":
+    """Scores over the union of what the parts covered (other nodes, other dates): the integer tables add."""
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    for p in parts[1:]:
+      if (p.n_members != first.n_members or p.directions != first.directions or p.scale != first.scale
+          or p.weighted.shape != first.weighted.shape):
+        raise ValueError("merge: the parts differ in members, directions, scale or shape")
+    weighted, counts, invalid = first.weighted.copy(), first.counts.copy(), first.invalid.copy()
+    for p in parts[1:]:
+      weighted += p.weighted
+      counts += p.counts
+      invalid += p.invalid
+    return EventScores(weighted, counts, first.n_members, first.directions, first.scale, invalid)
+
+  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
+    """{score: {variable: [T, batch, channels of the variable]}} in the channel order of `datasets.channel_layout`."""
+    layout = datasets.channel_layout(datasets.as_dataset(template))
+    if sum(n for _, _, n in layout) != self.weighted.shape[2]:
+      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.weighted.shape[2]}")
+    out: Dict[str, Dict[str, np.ndarray]] = {}
+    for score in ("base_rate", "brier", "brier_fair", "reliability", "resolution", "uncertainty", "brier_skill", "roc_area",
+                  "valid_weight", "valid_points"):
+      values = getattr(self, score)
+      out[score] = {name: values[:, :, off:off + n] for name, off, n in layout}
+    return out

@@ -479,6 +479,52 @@ int gc_ens_spectrum(gc_handle* h, const float* truth /* NULL = the truth uploade
                     double* member_power /* [M][B][c_out][lmax], NULL allowed */);
 
 /*
+ * Ensemble event verification on the device: the exceedance events of the members of the gc_ens_*
+ * store -- "10 m wind above the 99th percentile" -- counted against what the truth did, as the joint table the Brier score,
+ * the reliability curve, the ROC and the relative economic value are formed from (gencast-flax-nnx_amd/verification.py
+ * EventScores).  The reference project has no verification metrics; the yardstick is the definition below, restated in
+ * tests/event_reference.py.  Everything the device returns is an INTEGER: results are compared with ==.
+ * Members x_0 .. x_{M-1} (2 <= M <= 64) and the truth y are [G, B, c_out] float32.  T threshold fields thr_t (1 <= T <= 8),
+ * each [G, B, c_out] float32 -- a climatological percentile varies per node and channel, and under the residual normalisation
+ * of a single-step sample per batch member too -- with a direction dir_t:
+ *   dir_t > 0: the event is value > thr_t;   dir_t < 0: value < thr_t.   Both strict, on the float32 values: a value equal
+ *   to the threshold is not an event.  dir_t == 0 is an invalid argument.
+ * A point (g, b, c) counts for threshold t when y, all M members and thr_t are finite there; other points contribute nothing
+ * (a NaN threshold: "this channel or point is not evaluated").  Per counted point:
+ *   k = #{i : x_i in the event} in 0..M,   o = [y in the event].
+ * wq [G] uint32 are integer node weights (verification.quantize_node_weights: rint(w 2^e) in float64, 2^e the largest power
+ * of two with max(w) 2^e <= 2^32 - 1); the device never sees a float weight here.  Per (t, b, c), over the counted nodes g:
+ *   weighted[t][b][c][o][k] = sum wq[g],   counts[t][b][c][o][k] = sum 1,   invalid[t] = points skipped.
+ * All uint64 and additive over dates and batches.  Integer addition has no order: the results are bit-reproducible however
+ * the launch is scheduled.  A column total is at most G (2^32 - 1): for G <= 2^21 below 2^53, so the conversion to float64
+ * and the division by 2^e are exact.  Per point and threshold the device keeps one byte, code = k | (o << 7), or 255 where the
+ * point does not count: the exceedance-probability map k / M with the observed flag (verification.event_probability).
+ *   gc_ens_event_set       T threshold fields, their directions and the integer node weights, through pinned staging (the
+ *                          caller's arrays are free on return).  Needs gc_set_graph only.  Thresholds, directions, weights
+ *                          and the code buffers do not depend on M and survive gc_ens_reserve; the tables, sized by M and
+ *                          T, are made again by the scoring call that finds either changed.  Repeated calls replace, they
+ *                          do not add ("device_allocations" stays flat).  Released by gc_destroy.
+ *                          GC_ERR_UNSUPPORTED: T outside 1..8.  GC_ERR_INVALID_ARGUMENT: a zero direction, a null pointer.
+ *   gc_ens_event_score     truth: host [G, B, c_out], uploaded and kept, or NULL = the truth uploaded last (the buffer
+ *                          gc_ens_score and gc_ens_spectrum use).  weighted [T][B][c_out][2][M + 1]; counts (same shape)
+ *                          and invalid [T] may be NULL.  Two launches: a code pass that streams the M members once, and a
+ *                          table pass over the code bytes.  Synchronous.
+ *                          GC_ERR_STATE: no thresholds set, no member store, a slot not pushed since gc_ens_reserve, no truth.
+ *   gc_ens_event_download  the codes [G, B, c_out] of threshold t from the last scoring call.  GC_ERR_STATE: none ran since
+ *                          gc_ens_event_set / gc_ens_reserve.  GC_ERR_INVALID_ARGUMENT: t outside [0, T).
+ * None of these entries touches the conditioning, the last sample, the stash, the loss or spectrum buffers, the member
+ * store's contents or the captured sample graphs.  Counters: "ens_event_calls" (scoring calls so far),
+ * "ens_event_device_us" (HIP-event time of the last call's kernels), "ens_event_invalid_points" (sum over the thresholds of
+ * the last call).
+ */
+int gc_ens_event_set(gc_handle* h, int32_t n_thresholds, const float* thresholds /* [T][G,B,c_out] */,
+                     const int32_t* direction /* [T] */, const uint32_t* node_weight_q /* [G] */);
+int gc_ens_event_score(gc_handle* h, const float* truth /* NULL = the truth uploaded last */,
+                       uint64_t* weighted /* [T][B][c_out][2][M+1] */, uint64_t* counts /* same, NULL allowed */,
+                       uint64_t* invalid /* [T], NULL allowed */);
+int gc_ens_event_download(gc_handle* h, int32_t threshold, uint8_t* code /* [G,B,c_out] */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
