@@ -15,6 +15,8 @@ Public surface (mirrors the reference's call contracts):
                       counterpart: GenCast.ensemble_scores / EnsembleSampler.scores)
   spectra             SphericalAnalysis, EnsembleSpectra: spherical-harmonic power per total wavenumber of a sample or an
                       ensemble, analysed on the GPU (no reference counterpart: GenCast.ensemble_spectra)
+                      DerivedSpec: wind speed and spatially pooled fields formed on the GPU in front of every scorer
+                      (GenCast.ensemble_derived, EnsembleRollout.run(derived=...))
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
@@ -28,14 +30,15 @@ from .denoiser import Denoiser  # noqa: F401
 from .ensemble import EnsembleSampler, member_seed, member_shard  # noqa: F401
 from .gencast import GenCast, compute_loss, create_gencast_model, validation_loss  # noqa: F401
 from .nan_cleaning import NaNCleaner  # noqa: F401
-from .rollout import (DeviceRollout, EnsembleRollout, EnsembleRolloutResult, InputsAndResiduals,  # noqa: F401
+from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, EnsembleRolloutResult, InputsAndResiduals,  # noqa: F401
                       autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
-from .verification import EnsembleScores, EventScores, EventSpec  # noqa: F401
+from .verification import DerivedSpec, EnsembleScores, EventScores, EventSpec  # noqa: F401
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
            "InputsAndResiduals", "autoregressive_rollout", "DeviceRollout", "NaNCleaner", "launch", "losses",
            "compute_loss", "validation_loss", "verification", "EnsembleScores", "spectra", "EnsembleSpectra",
-           "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec"]
+           "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec",
+           "DerivedSpec", "DerivedRolloutResult"]

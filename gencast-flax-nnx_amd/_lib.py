@@ -120,6 +120,9 @@ SIGNATURES = {
     "gc_ens_event_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint64)]),
     "gc_ens_event_download": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8)]),
+    "gc_ens_derive_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_derive": (ctypes.c_int, [_hp, _hp, _f32p]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -211,6 +214,7 @@ class NativeDenoiser:
     self._ens_members = 0                      # slots of the member store this object reserved on the handle
     self._spec_lmax = 0                        # band limit of the analysis tables this object handed to the handle
     self._event_thresholds = 0                 # threshold fields this object handed to the handle
+    self._derive_c_src = 0                     # source channels of the derive plan this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
   def _check(self, rc):
@@ -623,6 +627,69 @@ class NativeDenoiser:
     code = np.empty(self._shape_out(), dtype=np.uint8)
     self._check(self._lib.gc_ens_event_download(self._h, int(t), _ptr(code, ctypes.POINTER(ctypes.c_uint8))))
     return code
+
+  # -- derived and pooled ensemble fields (formed on the device, into this handle's member store) -------
+  def ens_derive_set(self, c_src: int, op, src_a, src_b, affine, pool: int = 0, n_lat: Optional[int] = None,
+                     n_lon: Optional[int] = None, r_lat: int = 0, r_lon=None, row_weight=None) -> None:
+    """The plan of `ens_derive` for this handle's c_out = c_d derived channels (gc_ens_derive_set; needs `set_graph` only,
+    survives `ens_reserve`).  `op` [c_d]: 0 copy of source channel `src_a[j]`, 1 norm2 = sqrt(u^2 + v^2) in double with
+    u = x[src_a[j]] sa + la, v = x[src_b[j]] sb + lb and `affine[j]` = (sa, la, sb, lb).  `pool`: 0 none, 1 max, 2 min,
+    3 mean over the window of `r_lat` rows either side and `r_lon[i']` longitudes either side in row i' (wrapping), the mean
+    weighted with `row_weight[i']`; `n_lat` x `n_lon` is the grid (node = lat_i n_lon + lon_j).  `verification.DerivedSpec`
+    builds these arrays from variable names."""
+    c_d = self.cfg.c_out
+    if int(c_src) < 1:
+      raise ValueError("c_src must be positive")
+    o, a, b = _i32(op), _i32(src_a), _i32(src_b)
+    if o.shape != (c_d,) or a.shape != (c_d,) or b.shape != (c_d,):
+      raise ValueError(f"op, src_a and src_b must have shape ({c_d},)")
+    if np.any((o != 0) & (o != 1)):
+      raise ValueError("op must be 0 (copy) or 1 (norm2)")
+    if np.any((a < 0) | (a >= c_src)) or np.any((o == 1) & ((b < 0) | (b >= c_src))):
+      raise ValueError(f"a source channel lies outside [0, {int(c_src)})")
+    aff = np.ascontiguousarray(affine, dtype=np.float64)
+    if aff.shape != (c_d, 4):
+      raise ValueError(f"affine must have shape ({c_d}, 4)")
+    if int(pool) not in (0, 1, 2, 3):
+      raise ValueError("pool must be 0 (none), 1 (max), 2 (min) or 3 (mean)")
+    if n_lat is None or n_lon is None or int(n_lat) * int(n_lon) != self.num_grid_nodes:
+      raise ValueError(f"n_lat * n_lon must equal the number of grid nodes ({self.num_grid_nodes})")
+    if int(r_lat) < 0:
+      raise ValueError("r_lat must be >= 0")
+    dp = ctypes.POINTER(ctypes.c_double)
+    r = w = None
+    if int(pool) != 0:
+      if r_lon is None or row_weight is None:
+        raise ValueError("a pooled plan needs r_lon and row_weight")
+      r = _i32(r_lon)
+      w = np.ascontiguousarray(row_weight, dtype=np.float64)
+      if r.shape != (int(n_lat),) or w.shape != (int(n_lat),):
+        raise ValueError(f"r_lon and row_weight must have shape ({int(n_lat)},)")
+      if np.any((r < 0) | (r > (int(n_lon) - 1) // 2)):
+        raise ValueError(f"r_lon must lie in 0 .. {(int(n_lon) - 1) // 2}")
+      if not np.all(np.isfinite(w) & (w > 0.0)):
+        raise ValueError("row_weight must be finite and > 0")
+    self._check(self._lib.gc_ens_derive_set(self._h, int(c_src), _ptr(o, _i32p), _ptr(a, _i32p), _ptr(b, _i32p), _ptr(aff, dp),
+                                            int(pool), int(n_lat), int(n_lon), int(r_lat),
+                                            None if r is None else _ptr(r, _i32p), None if w is None else _ptr(w, dp)))
+    self._derive_c_src = int(c_src)
+
+  def ens_derive(self, src: "NativeDenoiser", truth=None) -> None:
+    """Every slot of this handle's member store <- the derived (and pooled) member of `src`'s store, this handle's truth <-
+    the derived truth of `src` (gc_ens_derive): afterwards `ens_score(None)`, `ens_event_score(None)`, `ens_spectrum(None)`
+    and `ens_download_member` of THIS handle see the derived fields.  `truth` [G, B, c_src] is uploaded into `src`, or
+    None = the truth `src` holds."""
+    if not self._derive_c_src:
+      raise GencastHipError("libgencast_hip error 4: no plan (ens_derive_set has not been called on this object)")
+    if not isinstance(src, NativeDenoiser) or src is self:
+      raise ValueError("src must be another NativeDenoiser")
+    t = None
+    if truth is not None:
+      t = _f32(truth)
+      want = (self.num_grid_nodes, self.cfg.batch, self._derive_c_src)
+      if t.shape != want:
+        raise ValueError(f"truth must be {want}, got {t.shape}")
+    self._check(self._lib.gc_ens_derive(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
 
   # -- context store: one resident conditioning per ensemble member ----------------------------------
   def ctx_reserve(self, n: int) -> None:

@@ -1,0 +1,475 @@
+// Derived and pooled ensemble fields on the device (include/gencast_hip.h, gc_ens_derive_*): the members and the truth of
+// one handle's gc_ens_* store become, in the store of a second handle, fields of derived channels (a copy of a source
+// channel, or the norm of two: wind speed) pooled over a latitude-adaptive window (max, min or an area-weighted mean).
+// Every scorer of the library then works on that store as it is.  Kernels and their host code live together here;
+// DESIGN.md section 8g has the definitions.
+//
+// Three passes per call, fields z = 0 .. M (the M members, then the truth):
+//   derive   d = x[src_a] (the same bits), or (float) sqrt(u u + v v) with u = (double) x[src_a] sa + la (v likewise), into
+//            the destination slot.  With pool == NONE this is the whole call.
+//   row      one latitude row i' of d pooled along the longitude over |t| <= r_lon[i'], wrapping, non-finite values
+//            skipped, into an intermediate: one float per point (max; min is max of the negated values), or a double sum
+//            and an int32 count of the finite values (mean).
+//   column   per point the intermediates of the rows |i' - i| <= r_lat (clipped at the poles) combined -- the mean with
+//            row_weight[i'] -- and written over the centre; NaN where the centre itself is not finite.
+// No atomics: every output has one writer and every sum a fixed order, so two calls give the same bytes.
+#include "gc_handle.h"
+
+// the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
+#pragma clang fp contract(off)
+
+namespace gc {
+
+enum { kDrvCopy = 0, kDrvNorm2 = 1 };
+enum { kPoolNone = 0, kPoolMax = 1, kPoolMin = 2, kPoolMean = 3 };
+constexpr int kDrvChunk = 8;                     // fields the intermediate holds: the M + 1 fields go through it in chunks
+constexpr size_t kDrvRowLds = 64 * 1024;         // the staged row tile of a workgroup: 2 workgroups per CU (160 KB)
+constexpr int kDrvMaxTile = 32;                  // columns of a row tile: 32 lanes x 4 bytes = one 128-byte line per longitude
+constexpr int kDrvRegs = 64;                     // max pass: tile elements per thread (kDrvRowLds / 4 / 256)
+constexpr int kDrvMeanBytes = 12;                // mean pass: a double prefix sum and an int32 prefix count per tile element
+
+// field z of a store: member z, or the truth behind the last member
+__device__ inline const float* drv_field(const float* mem, const float* truth, size_t field, int M, int z) {
+  return z < M ? mem + (size_t)z * field : truth;
+}
+__device__ inline float* drv_field(float* mem, float* truth, size_t field, int M, int z) {
+  return z < M ? mem + (size_t)z * field : truth;
+}
+
+// Derive pass.  Thread layout of gc_ens_state_kernel: thread t owns derived column t % wt = (b, j) of node lane t / wt, so
+// its row of the table (op, the two source channels, the affine) sits in registers for the whole node loop; the active
+// threads of a block store q whole consecutive destination rows.  grid = (node blocks, column tiles of 256, M + 1).
+__global__ __launch_bounds__(256) void gc_ens_derive_kernel(const float* __restrict__ smem, const float* __restrict__ struth,
+                                                             float* __restrict__ dmem, float* __restrict__ dtruth, int M,
+                                                             int G, int B, int c_src, int c_d, const int* __restrict__ op,
+                                                             const int* __restrict__ src_a, const int* __restrict__ src_b,
+                                                             const double* __restrict__ affine) {
+  const int W = B * c_d, Ws = B * c_src;
+  const int col0 = blockIdx.y * 256;
+  const int wt = min(256, W - col0);
+  const int q = 256 / wt;
+  const int lane = threadIdx.x / wt;
+  if (lane >= q) return;
+  const int col = col0 + ((int)threadIdx.x - lane * wt);
+  const int b = col / c_d, j = col - b * c_d;
+  const int z = blockIdx.z;
+  const unsigned* const from = reinterpret_cast<const unsigned*>(drv_field(smem, struth, (size_t)G * Ws, M, z)) + (size_t)b * c_src;
+  unsigned* const to = reinterpret_cast<unsigned*>(drv_field(dmem, dtruth, (size_t)G * W, M, z)) + col;
+  const int ca = src_a[j];
+  if (op[j] == kDrvCopy) {                         // the same bits: a NaN keeps its payload
+    for (size_t n = (size_t)blockIdx.x * q + lane; n < (size_t)G; n += (size_t)gridDim.x * q) to[n * W] = from[n * Ws + ca];
+    return;
+  }
+  const int cb = src_b[j];
+  const double sa = affine[4 * j], la = affine[4 * j + 1], sb = affine[4 * j + 2], lb = affine[4 * j + 3];
+  for (size_t n = (size_t)blockIdx.x * q + lane; n < (size_t)G; n += (size_t)gridDim.x * q) {
+    const double u = (double)__uint_as_float(from[n * Ws + ca]) * sa + la;
+    const double v = (double)__uint_as_float(from[n * Ws + cb]) * sb + lb;
+    to[n * W] = __float_as_uint((float)sqrt(u * u + v * v));
+  }
+}
+
+// Row pass, max (and min, on the negated values).  grid = (column tiles of wt, n_lat, fields of the chunk); wt is a power
+// of two that divides 256.  Thread t owns column t % wt of longitude lane t / wt (q = 256 / wt lanes): the lanes of a wave
+// own different columns at the same longitude, so their LDS addresses are consecutive.  The row tile [n_lon][wt] is staged
+// once, non-finite values as -inf, and doubled IN PLACE over power-of-two spans, S_k[j] = max x[j .. j + 2^k - 1] (circular):
+// every thread reads its (at most kDrvRegs) elements and their partners at distance 2^(k-1) into registers, a barrier, then
+// writes.  A window of w = 2 r + 1 longitudes is the max of the two spans of length 2^k <= w that cover it: floor(log2 w)
+// doubling steps of two LDS reads and a write per element, then two reads per output, whatever r is -- near the poles the
+// window is the whole row.  (The prefix / suffix form of van Herk needs two more arrays and a row extended past the wrap;
+// the doubling form needs the staged tile only.)  out [chunk][G][W]: the pooled row in the max domain, -inf where no
+// finite value.
+__global__ __launch_bounds__(256) void gc_ens_pool_row_max_kernel(const float* __restrict__ mem, const float* __restrict__ truth,
+                                                                   size_t field, int M, int z0, int n_lon, int W, int wt,
+                                                                   const int* __restrict__ r_lon, int negate,
+                                                                   float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char drv_lds[];
+  float* const S = reinterpret_cast<float*>(drv_lds);
+  const int q = 256 / wt;
+  const int tid = threadIdx.x;
+  const int lane = tid / wt;
+  const int cl = tid - lane * wt;
+  const int col = blockIdx.x * wt + cl;
+  const bool live = col < W;
+  const int i = blockIdx.y;
+  const float* const row = drv_field(mem, truth, field, M, z0 + (int)blockIdx.z) + (size_t)i * n_lon * W + col;
+  const float ninf = -__builtin_inff();
+  for (int j = lane; j < n_lon; j += q) {
+    float x = live ? row[(size_t)j * W] : ninf;
+    if (negate) x = -x;
+    S[j * wt + cl] = isfinite(x) ? x : ninf;
+  }
+  __syncthreads();
+  const int r = r_lon[i], w = 2 * r + 1;
+  int span = 1;
+  while (2 * span <= w) {                          // S_k -> S_(k+1), span = 2^k
+    float v[kDrvRegs];
+#pragma unroll
+    for (int e = 0; e < kDrvRegs; ++e) {
+      const int j = lane + e * q;
+      if (j < n_lon) {
+        int j2 = j + span;
+        if (j2 >= n_lon) j2 -= n_lon;
+        v[e] = fmaxf(S[j * wt + cl], S[j2 * wt + cl]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < kDrvRegs; ++e) {
+      const int j = lane + e * q;
+      if (j < n_lon) S[j * wt + cl] = v[e];
+    }
+    __syncthreads();
+    span *= 2;
+  }
+  if (!live) return;
+  float* const o = out + ((size_t)blockIdx.z * gridDim.y + i) * n_lon * W + col;
+  for (int j = lane; j < n_lon; j += q) {
+    int a = j - r;
+    if (a < 0) a += n_lon;
+    int b = j + r - span + 1;                      // in (-n_lon, n_lon): span <= w <= n_lon
+    if (b < 0) b += n_lon;
+    o[(size_t)j * W] = fmaxf(S[a * wt + cl], S[b * wt + cl]);
+  }
+}
+
+// Row pass, mean.  The same grid and thread layout.  Dynamic LDS: double P[n_lon][wt], the inclusive prefix sum of the
+// finite values along the row, then int C[n_lon][wt], the prefix count.  Lane l scans its contiguous segment of
+// ceil(n_lon / q) longitudes, reads the totals of the segments in front of it (ascending: a fixed order), a barrier, and
+// adds them to its segment.  A window is the difference of two prefix values (three where it wraps): the cost per output
+// does not depend on r.  sum [chunk][G][W] double, cnt [chunk][G][W] int.
+__global__ __launch_bounds__(256) void gc_ens_pool_row_mean_kernel(const float* __restrict__ mem, const float* __restrict__ truth,
+                                                                    size_t field, int M, int z0, int n_lon, int W, int wt,
+                                                                    const int* __restrict__ r_lon, double* __restrict__ sum,
+                                                                    int* __restrict__ cnt) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char drv_lds[];
+  double* const P = reinterpret_cast<double*>(drv_lds);
+  int* const C = reinterpret_cast<int*>(P + (size_t)n_lon * wt);
+  const int q = 256 / wt;
+  const int tid = threadIdx.x;
+  const int lane = tid / wt;
+  const int cl = tid - lane * wt;
+  const int col = blockIdx.x * wt + cl;
+  const bool live = col < W;
+  const int i = blockIdx.y;
+  const float* const row = drv_field(mem, truth, field, M, z0 + (int)blockIdx.z) + (size_t)i * n_lon * W + col;
+  const int seg = (n_lon + q - 1) / q;
+  const int j0 = min(n_lon, lane * seg), j1 = min(n_lon, j0 + seg);
+  double s = 0.0;
+  int c = 0;
+  for (int j = j0; j < j1; ++j) {
+    const float x = live ? row[(size_t)j * W] : 0.f;
+    if (isfinite(x)) {
+      s += (double)x;
+      ++c;
+    }
+    P[j * wt + cl] = s;
+    C[j * wt + cl] = c;
+  }
+  __syncthreads();
+  double ps = 0.0;
+  int pc = 0;
+  for (int l = 0; l < lane; ++l) {                 // the segments in front of this one, ascending
+    const int e = min(n_lon, (l + 1) * seg);
+    if (e > l * seg) {
+      ps += P[(e - 1) * wt + cl];
+      pc += C[(e - 1) * wt + cl];
+    }
+  }
+  __syncthreads();
+  for (int j = j0; j < j1; ++j) {
+    P[j * wt + cl] += ps;
+    C[j * wt + cl] += pc;
+  }
+  __syncthreads();
+  if (!live) return;
+  const int r = r_lon[i];
+  const size_t base = ((size_t)blockIdx.z * gridDim.y + i) * n_lon * W + col;
+  const double tot = P[(n_lon - 1) * wt + cl];
+  const int ctot = C[(n_lon - 1) * wt + cl];
+  for (int j = lane; j < n_lon; j += q) {
+    const int lo = j - r, hi = j + r;              // 2 r + 1 <= n_lon: the window wraps at one end at the most
+    double ws;
+    int wc;
+    if (lo < 0) {
+      ws = (tot - P[(lo + n_lon - 1) * wt + cl]) + P[hi * wt + cl];
+      wc = (ctot - C[(lo + n_lon - 1) * wt + cl]) + C[hi * wt + cl];
+    } else if (hi >= n_lon) {
+      ws = (tot - P[(lo - 1) * wt + cl]) + P[(hi - n_lon) * wt + cl];
+      wc = (ctot - C[(lo - 1) * wt + cl]) + C[(hi - n_lon) * wt + cl];
+    } else {
+      ws = P[hi * wt + cl] - (lo > 0 ? P[(lo - 1) * wt + cl] : 0.0);
+      wc = C[hi * wt + cl] - (lo > 0 ? C[(lo - 1) * wt + cl] : 0);
+    }
+    sum[base + (size_t)j * W] = ws;
+    cnt[base + (size_t)j * W] = wc;
+  }
+}
+
+// Column pass: a stream over the points of the chunk's fields, one thread per point.  The at most 2 r_lat + 1 intermediates
+// above and below lie n_lon W elements apart (coalesced across the wave, L2 hits between neighbouring rows); the centre is
+// read from, and the result written over, the thread's own element of the destination field.
+template <int POOL>
+__global__ __launch_bounds__(256) void gc_ens_pool_col_kernel(float* __restrict__ mem, float* __restrict__ truth, size_t field,
+                                                               int M, int z0, int n_lat, size_t rowlen, int r_lat,
+                                                               const float* __restrict__ rmax, const double* __restrict__ rsum,
+                                                               const int* __restrict__ rcnt,
+                                                               const double* __restrict__ row_weight) {
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= field) return;
+  float* const f = drv_field(mem, truth, field, M, z0 + (int)blockIdx.y);
+  const int i = (int)(p / rowlen);
+  const int i0 = max(0, i - r_lat), i1 = min(n_lat - 1, i + r_lat);
+  const size_t at = (size_t)blockIdx.y * field + p - (size_t)(i - i0) * rowlen;
+  float out;
+  if constexpr (POOL == kPoolMean) {
+    double num = 0.0, den = 0.0;
+    for (int k = i0; k <= i1; ++k) {
+      const size_t e = at + (size_t)(k - i0) * rowlen;
+      const double w = row_weight[k];
+      num += w * rsum[e];
+      den += w * (double)rcnt[e];
+    }
+    out = (float)(num / den);
+  } else {
+    float m = -__builtin_inff();
+    for (int k = i0; k <= i1; ++k) m = fmaxf(m, rmax[at + (size_t)(k - i0) * rowlen]);
+    out = POOL == kPoolMin ? -m : m;
+  }
+  if (!isfinite(f[p])) out = __builtin_nanf("");
+  f[p] = out;
+}
+
+static int drv_pow2_floor(int v) {
+  int p = 1;
+  while (2 * p <= v) p *= 2;
+  return p;
+}
+
+// columns of a row tile: a power of two, within the LDS budget, no wider than the field needs; 0: the row does not fit
+static int drv_tile(int pool, int n_lon, int W) {
+  const size_t per = (size_t)n_lon * (pool == kPoolMean ? kDrvMeanBytes : 4);
+  if (per > kDrvRowLds) return 0;
+  int wt = std::min(kDrvMaxTile, drv_pow2_floor((int)(kDrvRowLds / per)));
+  while (wt / 2 >= W) wt /= 2;
+  return wt;
+}
+
+static hipError_t launch_ens_derive(hipStream_t s, const float* smem, const float* struth, float* dmem, float* dtruth, int M,
+                                    int G, int B, int c_src, int c_d, const int* op, const int* src_a, const int* src_b,
+                                    const double* affine) {
+  const int W = B * c_d;
+  const int q = 256 / std::min(256, W);
+  const int blocks = std::max(1, std::min(1024, (G + q - 1) / q));
+  hipLaunchKernelGGL(gc_ens_derive_kernel, dim3(blocks, (W + 255) / 256, M + 1), dim3(256), 0, s, smem, struth, dmem, dtruth, M,
+                     G, B, c_src, c_d, op, src_a, src_b, affine);
+  return hipGetLastError();
+}
+
+static hipError_t launch_ens_pool_row(hipStream_t s, int pool, const float* mem, const float* truth, size_t field, int M, int z0,
+                                      int nz, int n_lat, int n_lon, int W, const int* r_lon, void* inter) {
+  const int wt = drv_tile(pool, n_lon, W);
+  const dim3 grid((W + wt - 1) / wt, n_lat, nz);
+  if (pool == kPoolMean) {
+    double* const sum = reinterpret_cast<double*>(inter);
+    int* const cnt = reinterpret_cast<int*>(sum + (size_t)kDrvChunk * field);
+    hipLaunchKernelGGL(gc_ens_pool_row_mean_kernel, grid, dim3(256), (size_t)n_lon * wt * kDrvMeanBytes, s, mem, truth, field, M,
+                       z0, n_lon, W, wt, r_lon, sum, cnt);
+  } else {
+    hipLaunchKernelGGL(gc_ens_pool_row_max_kernel, grid, dim3(256), (size_t)n_lon * wt * sizeof(float), s, mem, truth, field, M,
+                       z0, n_lon, W, wt, r_lon, pool == kPoolMin ? 1 : 0, reinterpret_cast<float*>(inter));
+  }
+  return hipGetLastError();
+}
+
+static hipError_t launch_ens_pool_col(hipStream_t s, int pool, float* mem, float* truth, size_t field, int M, int z0, int nz,
+                                      int n_lat, int n_lon, int W, int r_lat, void* inter, const double* row_weight) {
+  const dim3 grid((unsigned)((field + 255) / 256), nz);
+  const size_t rowlen = (size_t)n_lon * W;
+  float* const rmax = reinterpret_cast<float*>(inter);
+  double* const rsum = reinterpret_cast<double*>(inter);
+  int* const rcnt = reinterpret_cast<int*>(rsum + (size_t)kDrvChunk * field);
+  if (pool == kPoolMean)
+    hipLaunchKernelGGL((gc_ens_pool_col_kernel<kPoolMean>), grid, dim3(256), 0, s, mem, truth, field, M, z0, n_lat, rowlen, r_lat,
+                       nullptr, rsum, rcnt, row_weight);
+  else if (pool == kPoolMin)
+    hipLaunchKernelGGL((gc_ens_pool_col_kernel<kPoolMin>), grid, dim3(256), 0, s, mem, truth, field, M, z0, n_lat, rowlen, r_lat,
+                       rmax, nullptr, nullptr, row_weight);
+  else
+    hipLaunchKernelGGL((gc_ens_pool_col_kernel<kPoolMax>), grid, dim3(256), 0, s, mem, truth, field, M, z0, n_lat, rowlen, r_lat,
+                       rmax, nullptr, nullptr, row_weight);
+  return hipGetLastError();
+}
+
+}  // namespace gc
+
+using namespace gci;
+
+namespace {
+
+size_t drv_field_len(const gc_handle* h) { return (size_t)h->hg.G * h->cfg.batch * h->cfg.c_out; }
+
+// through the pinned staging buffer of the noise upload ([G, B, c_out] floats), in pieces where the table is longer
+int drv_staged_upload(gc_handle* h, void* dev, const void* src, size_t bytes) {
+  const size_t cap = drv_field_len(h) * sizeof(float);
+  for (size_t off = 0; off < bytes; off += cap) {
+    const size_t n = std::min(cap, bytes - off);
+    GC_HIP(h, hipEventSynchronize(h->ev_pin));
+    std::memcpy(h->pin_noise, static_cast<const char*>(src) + off, n);
+    GC_HIP(h, hipMemcpyAsync(static_cast<char*>(dev) + off, h->pin_noise, n, hipMemcpyHostToDevice, h->stream));
+    GC_HIP(h, hipEventRecord(h->ev_pin, h->stream));
+  }
+  return GC_OK;
+}
+
+// a failure inside a call made on the source handle is reported on the handle the caller asked
+int drv_from_src(gc_handle* h, gc_handle* src, int rc) {
+  if (rc) h->err = "source handle: " + src->err;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gc_ens_derive_set(gc_handle* h, int32_t c_src, const int32_t* op, const int32_t* src_a, const int32_t* src_b,
+                      const double* affine, int32_t pool, int32_t n_lat, int32_t n_lon, int32_t r_lat, const int32_t* r_lon,
+                      const double* row_weight) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (pool < gc::kPoolNone || pool > gc::kPoolMean) return fail(h, GC_ERR_UNSUPPORTED, "pool must be 0 (none), 1 (max), 2 (min) or 3 (mean)");
+  if (!op || !src_a || !src_b || !affine || (pool != gc::kPoolNone && (!r_lon || !row_weight)))
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (c_src < 1) return fail(h, GC_ERR_INVALID_ARGUMENT, "c_src must be positive");
+  if (n_lat < 1 || n_lon < 1 || (int64_t)n_lat * n_lon != (int64_t)h->hg.G)
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "n_lat * n_lon must equal the number of grid nodes");
+  const int c_d = h->cfg.c_out, W = h->cfg.batch * c_d;
+  for (int j = 0; j < c_d; ++j) {
+    if (op[j] != gc::kDrvCopy && op[j] != gc::kDrvNorm2) return fail(h, GC_ERR_UNSUPPORTED, "op " + std::to_string(j) + " is neither 0 (copy) nor 1 (norm2)");
+    if (src_a[j] < 0 || src_a[j] >= c_src || (op[j] == gc::kDrvNorm2 && (src_b[j] < 0 || src_b[j] >= c_src)))
+      return fail(h, GC_ERR_INVALID_ARGUMENT, "derived channel " + std::to_string(j) + ": source channel outside [0, c_src)");
+  }
+  if (r_lat < 0) return fail(h, GC_ERR_INVALID_ARGUMENT, "r_lat is negative");
+  if (pool != gc::kPoolNone) {
+    for (int i = 0; i < n_lat; ++i) {
+      if (r_lon[i] < 0 || r_lon[i] > (n_lon - 1) / 2) return fail(h, GC_ERR_INVALID_ARGUMENT, "r_lon[" + std::to_string(i) + "] outside 0 .. (n_lon - 1) / 2");
+      if (!(std::isfinite(row_weight[i]) && row_weight[i] > 0.0)) return fail(h, GC_ERR_INVALID_ARGUMENT, "row_weight[" + std::to_string(i) + "] is not finite and positive");
+    }
+    if (gc::drv_tile(pool, n_lon, W) == 0) return fail(h, GC_ERR_UNSUPPORTED, "n_lon is too large for the row tile of this pool (64 KB of LDS)");
+  }
+  GC_HIP(h, hipSetDevice(h->device));
+  // one blob: affine [c_d][4] and row_weight [n_lat] doubles, then op, src_a, src_b [c_d] and r_lon [n_lat] int32
+  const size_t n_d = (size_t)4 * c_d + n_lat, n_i = (size_t)3 * c_d + n_lat;
+  std::vector<double> blob(n_d + (n_i + 1) / 2);
+  std::copy(affine, affine + 4 * c_d, blob.begin());
+  for (int i = 0; i < n_lat; ++i) blob[(size_t)4 * c_d + i] = pool != gc::kPoolNone ? row_weight[i] : 1.0;
+  int32_t* const ib = reinterpret_cast<int32_t*>(blob.data() + n_d);
+  for (int j = 0; j < c_d; ++j) {
+    ib[j] = op[j];
+    ib[c_d + j] = src_a[j];
+    ib[2 * c_d + j] = op[j] == gc::kDrvNorm2 ? src_b[j] : src_a[j];
+  }
+  for (int i = 0; i < n_lat; ++i) ib[3 * c_d + i] = pool != gc::kPoolNone ? r_lon[i] : 0;
+  GC_HIP(h, hipStreamSynchronize(h->stream));        // nothing reads the old plan any more
+  free_allocs(&h->drv_allocs);
+  h->drv_set = false;
+  int rc;
+  double* d_blob = nullptr;
+  if ((rc = dev_alloc(h, &d_blob, blob.size(), &h->drv_allocs))) return rc;
+  for (hipEvent_t* e : {&h->ev_drv0, &h->ev_drv1})
+    if (!*e) GC_HIP(h, hipEventCreate(e));
+  if (!h->ev_drv_src) GC_HIP(h, hipEventCreateWithFlags(&h->ev_drv_src, hipEventDisableTiming));
+  if ((rc = drv_staged_upload(h, d_blob, blob.data(), blob.size() * sizeof(double)))) return rc;
+  h->d_drv_affine = d_blob;
+  h->d_drv_roww = d_blob + (size_t)4 * c_d;
+  h->d_drv_op = reinterpret_cast<int*>(d_blob + n_d);
+  h->d_drv_a = h->d_drv_op + c_d;
+  h->d_drv_b = h->d_drv_a + c_d;
+  h->d_drv_rlon = h->d_drv_b + c_d;
+  h->drv_c_src = c_src;
+  h->drv_pool = pool;
+  h->drv_n_lat = n_lat;
+  h->drv_n_lon = n_lon;
+  h->drv_r_lat = r_lat;
+  h->drv_set = true;
+  return GC_OK;
+  });
+}
+
+int gc_ens_derive(gc_handle* h, gc_handle* src, const float* truth) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  if (!src || src == h) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source must be another handle");
+  if (src->device != h->device) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle is on another device");
+  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (!h->drv_set) return fail(h, GC_ERR_STATE, "no plan (gc_ens_derive_set)");
+  if (!src->has_graph || src->hg.G != h->hg.G || src->cfg.batch != h->cfg.batch || src->cfg.c_out != h->drv_c_src)
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle has other dimensions (G, batch, c_out == c_src of the plan)");
+  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
+  if (src->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store on the source handle (gc_ens_reserve)");
+  if (src->ens_members != h->ens_members) return fail(h, GC_ERR_STATE, "the two member stores hold different numbers of members");
+  const int M = h->ens_members;
+  for (int i = 0; i < M; ++i)
+    if (!src->ens_filled[(size_t)i]) return fail(h, GC_ERR_STATE, "source member slot " + std::to_string(i) + " has not been pushed");
+  if (!truth && !src->has_ens_truth) return fail(h, GC_ERR_STATE, "no truth on the source handle (pass one to gc_ens_derive)");
+  GC_HIP(h, hipSetDevice(h->device));
+  const gc_config& c = h->cfg;
+  const int G = h->hg.G, B = c.batch, c_d = c.c_out, W = B * c_d, pool = h->drv_pool;
+  const size_t field = drv_field_len(h), sfield = (size_t)G * B * src->cfg.c_out;
+  int rc;
+  if (truth) {                                     // into the source's truth buffer, as gc_ens_score(src, truth, ...) would
+    if (!src->d_ens_truth && (rc = drv_from_src(h, src, dev_alloc(src, &src->d_ens_truth, sfield)))) return rc;
+    if ((rc = drv_from_src(h, src, staged_upload(src, src->pin_noise, src->d_ens_truth, truth, sfield)))) return rc;
+    src->has_ens_truth = true;
+  }
+  if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
+  const int chunk = std::min(gc::kDrvChunk, M + 1);
+  const size_t need = pool == gc::kPoolNone ? 0 : (size_t)gc::kDrvChunk * field * (pool == gc::kPoolMean ? gc::kDrvMeanBytes : 4);
+  if (need && need != h->drv_work_bytes) {         // sized by the pool kind and the field: made again only when they change
+    GC_HIP(h, hipStreamSynchronize(h->stream));
+    free_allocs(&h->drv_work_allocs);
+    h->drv_work_bytes = 0;
+    if ((rc = dev_alloc(h, &h->d_drv_work, need, &h->drv_work_allocs))) return rc;
+    h->drv_work_bytes = need;
+  }
+  hipStream_t s = h->stream;
+  // the source's store and truth are complete on ITS stream: this handle's stream goes on behind them
+  GC_HIP(h, hipEventRecord(h->ev_drv_src, src->stream));
+  GC_HIP(h, hipStreamWaitEvent(s, h->ev_drv_src, 0));
+  h->evt_scored = false;
+  h->has_ens_fields = false;
+  GC_HIP(h, hipEventRecord(h->ev_drv0, s));
+  if ((rc = launch(h, gc::KC_PACK, [&] {
+         return gc::launch_ens_derive(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out, c_d,
+                                      h->d_drv_op, h->d_drv_a, h->d_drv_b, h->d_drv_affine);
+       })))
+    return rc;
+  if (pool != gc::kPoolNone) {
+    for (int z0 = 0; z0 <= M; z0 += chunk) {
+      const int nz = std::min(chunk, M + 1 - z0);
+      if ((rc = launch(h, gc::KC_PACK, [&] {
+             return gc::launch_ens_pool_row(s, pool, h->d_ens, h->d_ens_truth, field, M, z0, nz, h->drv_n_lat, h->drv_n_lon, W,
+                                            h->d_drv_rlon, h->d_drv_work);
+           })))
+        return rc;
+      if ((rc = launch(h, gc::KC_PACK, [&] {
+             return gc::launch_ens_pool_col(s, pool, h->d_ens, h->d_ens_truth, field, M, z0, nz, h->drv_n_lat, h->drv_n_lon, W,
+                                            h->drv_r_lat, h->d_drv_work, h->d_drv_roww);
+           })))
+        return rc;
+    }
+  }
+  GC_HIP(h, hipEventRecord(h->ev_drv1, s));
+  GC_HIP(h, hipStreamSynchronize(s));
+  float ms = 0.f;
+  GC_HIP(h, hipEventElapsedTime(&ms, h->ev_drv0, h->ev_drv1));
+  h->drv_device_us = (int64_t)(ms * 1000.0f);
+  std::fill(h->ens_filled.begin(), h->ens_filled.end(), 1);
+  h->has_ens_truth = true;
+  ++h->drv_calls;
+  return GC_OK;
+  });
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // Internals shared by the host translation units of libgencast_hip.so: the handle, the device-side weight layout,
 // the route of a forward, and the allocation / launch helpers.  gc_weights.hip lays the weights out, gc_forward.hip
-// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* and gc_ctx_* entries, gc_spectrum.hip gc_spec_* and gc_ens_spectrum, gc_events.hip gc_ens_event_*).
+// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* and gc_ctx_* entries, gc_spectrum.hip gc_spec_* and gc_ens_spectrum, gc_events.hip gc_ens_event_*, gc_derive.hip gc_ens_derive_*).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -261,6 +261,19 @@ struct gc_handle {
   bool evt_scored = false;                       // a scoring call ran since gc_ens_event_set / gc_ens_reserve
   hipEvent_t ev_evt0 = nullptr, ev_evt1 = nullptr;   // brackets of the last scoring call
   int64_t evt_calls = 0, evt_device_us = 0, evt_invalid_points = 0;
+
+  // derived and pooled ensemble fields (gc_ens_derive_*, gc_derive.hip): the plan, and the intermediate of the pooling passes
+  std::vector<void*> drv_allocs;                 // the plan's tables, one buffer: freed and replaced by gc_ens_derive_set
+  std::vector<void*> drv_work_allocs;            // the intermediate: made again by the call that finds its size changed
+  bool drv_set = false;                          // a plan has been set
+  int drv_c_src = 0, drv_pool = 0, drv_n_lat = 0, drv_n_lon = 0, drv_r_lat = 0;
+  double *d_drv_affine = nullptr, *d_drv_roww = nullptr;       // [c_out][4] (sa, la, sb, lb), [n_lat]
+  int *d_drv_op = nullptr, *d_drv_a = nullptr, *d_drv_b = nullptr, *d_drv_rlon = nullptr;   // [c_out] x 3, [n_lat]
+  unsigned char* d_drv_work = nullptr;           // 8 fields of row-pooled values: a float (max, min), or a double and an int32 (mean), per point
+  size_t drv_work_bytes = 0;
+  hipEvent_t ev_drv0 = nullptr, ev_drv1 = nullptr;             // brackets of the last call
+  hipEvent_t ev_drv_src = nullptr;                             // stream order behind the source handle
+  int64_t drv_calls = 0, drv_device_us = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

@@ -155,6 +155,40 @@ class Denoiser:
       lanes.append(nd)
     return lanes[:count]
 
+  def view_handle(self, c_d: int) -> _lib.NativeDenoiser:
+    """A library handle on the same GPU that knows this denoiser's graph and nothing else (no weights, no `finalize`;
+    the smallest network configuration, so that it holds next to nothing), with `c_out = c_d`: the destination of
+    `NativeDenoiser.ens_derive`, whose member store then holds derived fields of `c_d` channels (wind speed, pooled
+    fields) for every scorer of the library.  One per `c_d`, created once and kept; `close` releases them."""
+    if not self._initialized:
+      raise RuntimeError("view_handle: the denoiser has not been initialised by a first call / init_for")
+    c_d = int(c_d)
+    if c_d < 1:
+      raise ValueError("c_d must be positive")
+    views = getattr(self, "_views", None)
+    if views is None:
+      views = self._views = {}
+    nd = views.get(c_d)
+    if nd is None or nd.closed:
+      nd = _lib.NativeDenoiser(latent_size=128, d_model=128, num_heads=2, ffw_hidden=256, num_layers=1, c_in=c_d, c_out=c_d,
+                               batch=self._batch, device_id=self._device_id)
+      try:
+        nd.set_graph(self.graph)
+      except Exception:
+        nd.close()
+        raise
+      views[c_d] = nd
+    return nd
+
+  def close(self) -> None:
+    """Releases every library handle this denoiser made: the view handles, the member lanes and `native`."""
+    for nd in list((getattr(self, "_views", None) or {}).values()) + list(getattr(self, "_lanes", None) or []):
+      nd.close()
+    self._views, self._lanes = {}, []
+    if self.native is not None:
+      self.native.close()
+    self._initialized = False
+
   @staticmethod
   def pack_inputs(inputs: datasets.Dataset, forcings: datasets.Dataset):
     """Datasets -> ([G,B,C] float32, (n_lat, n_lon), lat, lon, C_inputs).

@@ -106,6 +106,19 @@ class EnsembleSampler:
                        "ranks' members over and push them with NativeDenoiser.ens_push_host")
     return self._run(inputs, targets, forcings, num_members, None, events=spec)
 
+  def derived(self, inputs, targets, forcings, num_members: int, spec, events=None):
+    """Runs the members as `scores` does, sends them and `targets` through `spec` (a `verification.DerivedSpec`: wind speed
+    from two components, fields pooled over a neighbourhood) on the device and scores the derived fields there:
+    `verification.EnsembleScores` over the derived channels (`spec.template(targets)` names them), with `events` (an
+    `EventSpec` keyed by the derived names) -> (EnsembleScores, EventScores).  No member is downloaded.  The members are
+    taken as they are sampled, scale 1 and location 0: under a normalisation wrapper (`InputsAndResiduals`, `NaNCleaner`
+    around one) a single-step sample is a normalised RESIDUAL, and the norm of two residuals is no wind speed -- the wrappers
+    therefore have no such method; `EnsembleRollout.run(derived=...)` derives from member STATES, which are fields."""
+    if self.world_size > 1:
+      raise ValueError("EnsembleSampler.derived needs all members on one rank (world_size == 1): bring the other "
+                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    return self._run(inputs, targets, forcings, num_members, None, derived=(spec, events))
+
   def _spectral(self, inputs, targets, forcings, num_members, score_fields, lmax):
     if self.world_size > 1:
       raise ValueError("EnsembleSampler.spectra needs all members on one rank (world_size == 1): bring the other "
@@ -113,7 +126,7 @@ class EnsembleSampler:
     return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
 
   def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,
-           lmax: Optional[int] = None, events=None):
+           lmax: Optional[int] = None, events=None, derived=None):
     """`score_fields` None: members come back as Datasets (`__call__`) or, with `spectral`, only their spectra are
     formed, or, with `events` (an EventSpec), only their event tables; else they are scored (`scores`), with `spectral`
     both."""
@@ -143,7 +156,7 @@ class EnsembleSampler:
         lane.set_noisy_slots(slots)
         lane.upload_cond_dev(ptr)                          # device-to-device, on the lane's own stream
     scoring = score_fields is not None
-    if scoring or spectral or events is not None:
+    if scoring or spectral or events is not None or derived is not None:
       native.ens_reserve(num_members)
     if scoring:
       native.ens_set_node_weight(verification.node_weights(template))
@@ -156,14 +169,30 @@ class EnsembleSampler:
         lane.upload_noise(self.member_noise(m, shape, template))
         lane.sample_resident(sigmas, skip_dead_call=True, want_stats=False)
       for lane, m in zip(lanes, group):
-        if scoring or spectral or events is not None:
+        if scoring or spectral or events is not None or derived is not None:
           native.ens_push(m, src=lane)
         else:
           out.append((m, datasets.like_inputs(Denoiser.unpack_outputs(lane.download_sample(), grid_shape, template),
                                               targets_template, inputs, forcings)))
-    if not scoring and not spectral and events is None:
+    if not scoring and not spectral and events is None and derived is None:
       return out
     truth = np.transpose(datasets.dataset_to_stacked(template, template.sizes), (1, 2, 0, 3)).reshape(shape)
+    if derived is not None:
+      dspec, dev = derived
+      plan = dspec.plan(template)
+      view = self._denoiser.view_handle(len(plan["op"]))
+      view.ens_derive_set(**plan)
+      view.ens_reserve(num_members)
+      view.ens_set_node_weight(verification.node_weights(template))
+      view.ens_derive(native, truth)
+      sums, hist = view.ens_score(None)
+      scores = verification.EnsembleScores(sums, hist, num_members)
+      if dev is None:
+        return scores
+      wq, scale = verification.quantize_node_weights(verification.node_weights(template))
+      view.ens_event_set(dev.packed(dspec.template(template)), dev.directions, wq)
+      weighted, counts, invalid = view.ens_event_score(None)
+      return scores, verification.EventScores(weighted, counts, num_members, dev.directions, scale, invalid)
     if events is not None:
       wq, scale = verification.quantize_node_weights(verification.node_weights(template))
       native.ens_event_set(events.packed(template), events.directions, wq)

@@ -126,6 +126,20 @@ class GenCast:
     runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
     return runner.events(inputs, targets, forcings, num_members, spec)
 
+  def ensemble_derived(self, inputs, targets, forcings=None, *, num_members, spec, events=None, rngs=0, concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and scores, on the GPU, what `spec`
+    (`verification.DerivedSpec`) makes of them and of `targets`: wind speed from two components, fields max-, min- or
+    mean-pooled over a neighbourhood.  -> `verification.EnsembleScores` over the derived channels, with `events` (an
+    `EventSpec` keyed by the derived names) -> (EnsembleScores, EventScores).  No member leaves the device.  The members
+    are taken in the units they are sampled in; the normalisation wrappers have no such method, because under them a
+    single-step sample is a normalised residual and the norm of two residuals is no wind speed (`ensemble_rollout(...,
+    derived=...)` derives from member states instead)."""
+    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
+    if not isinstance(rngs, (int, np.integer)):
+      rngs = Sampler.seed_from(rngs)
+    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    return runner.derived(inputs, targets, forcings, num_members, spec, events)
+
   def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, *, rngs=0, norm=None, concurrent_members=1,
                        device_noise=None, **kwargs):
     """Rolls `num_members` (2..64) members out `horizon` autoregressive steps with every member's context resident on

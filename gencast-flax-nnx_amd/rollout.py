@@ -562,6 +562,29 @@ class _MemberNoise:
     return np.asarray(self._sampler.draw_noise(self._gen, shape, template), np.float32)
 
 
+class DerivedRolloutResult:
+  """The part of an `EnsembleRolloutResult` that belongs to one entry of `EnsembleRollout.run(derived=...)`: per lead time
+  `scores[k]` (`verification.EnsembleScores` in the units of the derived variables: `scores_normalized[k].scaled(scale_d)`
+  with `DerivedSpec.channel_stats`), `scores_normalized[k]` (as the device returned them), `events[k]`
+  (`verification.EventScores`, or None without an EventSpec) and `members[k]` (`[M]` arrays [G, B, c_d] in the members' own
+  units, or None); `template`: the Dataset of the derived variables (`DerivedSpec.template`) for `per_variable`."""
+
+  def __init__(self, scores, scores_normalized, events=None, members=None, template=None):
+    self.scores, self.scores_normalized = list(scores), list(scores_normalized)
+    self.events = None if events is None else list(events)
+    self.members, self.template = members, template
+
+  def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
+    from . import verification  # pylint: disable=import-outside-toplevel
+    if (self.events is None) != (other.events is None):
+      raise ValueError("merge: only one of the two derived results carries events")
+    S, E = verification.EnsembleScores, verification.EventScores
+    return DerivedRolloutResult([S.merge([a, b]) for a, b in zip(self.scores, other.scores)],
+                                [S.merge([a, b]) for a, b in zip(self.scores_normalized, other.scores_normalized)],
+                                None if self.events is None else [E.merge([a, b]) for a, b in zip(self.events, other.events)],
+                                template=self.template)
+
+
 class EnsembleRolloutResult:
   """What `EnsembleRollout.run` returns.  `scores`: one `verification.EnsembleScores` per lead time; `spectra`: one
   `spectra.EnsembleSpectra` per lead time, or None; `mean` / `variance`: the ensemble mean and variance fields on the
@@ -569,11 +592,13 @@ class EnsembleRolloutResult:
   units (normalised with the input statistics under a normalisation wrapper), or None; `n_members`.
   `scores_normalized` / `spectra_normalized`: the same lists as the device returned them, in the members' units
   (`scores[k]` is `scores_normalized[k].scaled(s)`).  `events`: one `verification.EventScores` per lead time, or None
-  (integer tables: no unit, nothing to rescale)."""
+  (integer tables: no unit, nothing to rescale).  `derived`: {name: `DerivedRolloutResult`} for the entries of
+  `run(derived=...)`, or None."""
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
-               scores_normalized=None, spectra_normalized=None, events=None):
+               scores_normalized=None, spectra_normalized=None, events=None, derived=None):
     self.scores = list(scores)
+    self.derived = None if derived is None else dict(derived)
     self.events = None if events is None else list(events)
     if self.events is not None and len(self.events) != len(self.scores):
       raise ValueError("scores and events must cover the same lead times")
@@ -601,6 +626,12 @@ class EnsembleRolloutResult:
       raise ValueError("merge: only one of the two results carries spectra")
     if (self.events is None) != (other.events is None):
       raise ValueError("merge: only one of the two results carries events")
+    if (self.derived is None) != (other.derived is None):
+      raise ValueError("merge: only one of the two results carries derived scores")
+    if self.derived is not None and sorted(self.derived) != sorted(other.derived):
+      raise ValueError(f"merge: the derived names differ ({sorted(self.derived)} and {sorted(other.derived)})")
+    derived = None if self.derived is None else {k: v.merge(other.derived[k]) for k, v in self.derived.items()}
+
     def both(cls, a, b):
       return None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
 
@@ -609,7 +640,7 @@ class EnsembleRolloutResult:
                                  n_members=self.n_members,
                                  scores_normalized=both(S, self.scores_normalized, other.scores_normalized),
                                  spectra_normalized=both(P, self.spectra_normalized, other.spectra_normalized),
-                                 events=both(verification.EventScores, self.events, other.events))
+                                 events=both(verification.EventScores, self.events, other.events), derived=derived)
 
 
 class EnsembleRollout:
@@ -660,7 +691,7 @@ class EnsembleRollout:
 
   def run(self, inputs, targets, forcings, horizon: int, num_members: int, *, context_steps: int = 2,
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
-          keep_members: bool = False, events=None) -> EnsembleRolloutResult:
+          keep_members: bool = False, events=None, derived=None) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -669,6 +700,12 @@ class EnsembleRollout:
     them with equal directions (a climatology that moves with the lead time): also the event tables per lead time,
     `EnsembleRolloutResult.events`, counted right after the scores on the truth already on the device.  The thresholds
     take the map of the truth, (thr - l) / s in float64, rounded once; s > 0, so no direction flips.
+    `derived`: {name: `verification.DerivedSpec`, or (DerivedSpec, EventSpec)}: per lead time, after the scores, the member
+    states and the truth go through `gc_ens_derive` into the store of a view handle (`Denoiser.view_handle`) -- wind speed
+    in physical units from the normalised components, fields pooled over a neighbourhood -- and are scored there with the
+    same node weights: `EnsembleRolloutResult.derived[name]`.  The thresholds of such an EventSpec are keyed by the derived
+    names, in physical units, and take the map of `DerivedSpec.channel_stats`.  With `keep_members` the derived members
+    are downloaded too.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -764,6 +801,33 @@ class EnsembleRollout:
 
     if event_specs is not None and len(event_specs) == 1:
       set_events(event_specs[0])                          # uploaded once: they survive the store and every lead time
+    views = {}
+    dwq = dwq_scale = None
+    for name, entry in (derived or {}).items():
+      dspec, dev = entry if isinstance(entry, (tuple, list)) else (entry, None)
+      dplan = dspec.plan(template0, scale, loc)
+      dtemplate = dspec.template(template0)
+      dscale, dloc = dspec.channel_stats(template0, scale, loc)
+      dthr = None
+      if dev is not None:
+        dthr = dev.packed(dtemplate)
+        if norm is not None:
+          dthr = ((dthr.astype(np.float64) - dloc) / dscale).astype(np.float32)
+        if dwq is None:
+          dwq, dwq_scale = verification.quantize_node_weights(verification.node_weights(template0))
+      views[name] = dict(view=den.view_handle(len(dplan["op"])), plan=dplan, scale=dscale, thr=dthr, events=dev,
+                         template=dtemplate, scores=[], raw=[], ev=None if dev is None else [],
+                         members=[] if keep_members else None)
+    for v in views.values():
+      view = v["view"]
+      # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
+      v["shared"] = sum(1 for o in views.values() if o["view"] is view) > 1
+      view.ens_reserve(M)
+      view.ens_set_node_weight(verification.node_weights(template0))
+      if not v["shared"]:
+        view.ens_derive_set(**v["plan"])
+        if v["events"] is not None:
+          view.ens_event_set(v["thr"], v["events"].directions, dwq)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -812,6 +876,21 @@ class EnsembleRollout:
         spec.append(raw_spec[-1].scaled(scale))
       if keep_members:
         members.append([native.ens_download_member(m) for m in range(M)])
+      for v in views.values():
+        view = v["view"]
+        if v["shared"]:
+          view.ens_derive_set(**v["plan"])
+        view.ens_derive(native)                           # members and truth, device to device
+        dsums, dhist = view.ens_score(None, want_fields=False)
+        v["raw"].append(verification.EnsembleScores(dsums, dhist, M))
+        v["scores"].append(v["raw"][-1].scaled(v["scale"]))
+        if v["events"] is not None:
+          if v["shared"]:
+            view.ens_event_set(v["thr"], v["events"].directions, dwq)
+          ew, ec, ei = view.ens_event_score(None)
+          v["ev"].append(verification.EventScores(ew, ec, M, v["events"].directions, dwq_scale, ei))
+        if keep_members:
+          v["members"].append([view.ens_download_member(m) for m in range(M)])
       self.last_lead_ms.append(1e3 * (_time.perf_counter() - t0))
 
     def on_time_axis(parts):
@@ -822,4 +901,7 @@ class EnsembleRollout:
 
     return EnsembleRolloutResult(scores, spec, on_time_axis(means) if fields else None,
                                  on_time_axis(variances) if fields else None, members, M,
-                                 scores_normalized=raw_scores, spectra_normalized=raw_spec, events=event_scores)
+                                 scores_normalized=raw_scores, spectra_normalized=raw_spec, events=event_scores,
+                                 derived=None if derived is None else {
+                                     k: DerivedRolloutResult(v["scores"], v["raw"], v["ev"], v["members"], v["template"])
+                                     for k, v in views.items()})

@@ -20,6 +20,11 @@ channel) the integer table `weighted[o][k]` = sum of the quantised node weights 
 `EventScores` keeps the tables raw (they add over dates, exactly) and derives the Brier score with its decomposition,
 the reliability curve, the ROC and the relative economic value; `EventSpec` carries thresholds given per variable in
 physical units down to the packed fields; `event_probability` decodes the per-point bytes the device keeps.
+
+Derived fields (`gc_ens_derive`): `DerivedSpec` names variables that are no model channels (wind speed:
+the norm of two components, in physical units) and one spatial pooling (max, min or area-weighted mean over a neighbourhood
+of fixed great-circle radius); the device forms them from a member store into the store of a second handle, where every
+scorer above works unchanged.
 """
 from __future__ import annotations
 
@@ -420,3 +425,165 @@ class EventScores:
       values = getattr(self, score)
       out[score] = {name: values[:, :, off:off + n] for name, off, n in layout}
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# derived and pooled fields: wind speed, neighbourhood maxima, area means (gc_ens_derive_*)
+# ---------------------------------------------------------------------------------------------
+_KM_PER_DEGREE = 111.195                                   # one degree of a great circle on the mean Earth radius 6371 km
+_POOLS = {None: 0, "none": 0, "max": 1, "min": 2, "mean": 3}
+
+
+class DerivedSpec:
+  """What `gc_ens_derive` makes of a member store: an ordered list of derived variables, then one
+  spatial pooling for all of them.
+
+  `outputs`: `("copy", name)` keeps a target variable; `("norm2", new_name, name_a, name_b)` is sqrt(a^2 + b^2) of two
+  target variables IN PHYSICAL UNITS, channel by channel (10 m wind speed from the two 10 m components: one channel; wind
+  speed on 13 levels from the two components on levels: 13) -- `name_a` and `name_b` must have equal channel counts.  The
+  derived channels are packed like every Dataset here, in sorted-name order (`datasets.channel_layout(self.template(...))`).
+  `pool`: None, "max", "min" or "mean" over a window of `r_lat` rows either side (clipped at the poles) and `r_lon[i']`
+  longitudes either side in row i' (wrapping) -- given as they are, or as `radius_km` (`window`).  The mean is weighted with
+  `losses.normalized_latitude_weights`."""
+
+  def __init__(self, outputs, pool: Optional[str] = None, radius_km: Optional[float] = None, r_lat: Optional[int] = None,
+               r_lon: Optional[Sequence[int]] = None):
+    self.outputs = [tuple(o) for o in outputs]
+    if not self.outputs:
+      raise ValueError("outputs must name at least one derived variable")
+    names = []
+    for o in self.outputs:
+      if len(o) == 2 and o[0] == "copy":
+        names.append(o[1])
+      elif len(o) == 4 and o[0] == "norm2":
+        names.append(o[1])
+      else:
+        raise ValueError(f"an output must be ('copy', name) or ('norm2', new_name, name_a, name_b), got {o!r}")
+    if len(set(names)) != len(names):
+      raise ValueError(f"derived variable names must be distinct, got {names}")
+    if pool not in _POOLS:
+      raise ValueError(f"pool must be None, 'max', 'min' or 'mean', got {pool!r}")
+    self.pool = None if pool in (None, "none") else pool
+    explicit = r_lat is not None or r_lon is not None
+    if self.pool is None:
+      if radius_km is not None or explicit:
+        raise ValueError("a window (radius_km, or r_lat and r_lon) needs a pool")
+    else:
+      if (radius_km is not None) == explicit:
+        raise ValueError("a pool needs either radius_km or r_lat and r_lon")
+      if explicit and (r_lat is None or r_lon is None):
+        raise ValueError("r_lat and r_lon must be given together")
+      if radius_km is not None and not (float(radius_km) >= 0.0 and math.isfinite(float(radius_km))):
+        raise ValueError("radius_km must be finite and >= 0")
+      if explicit and int(r_lat) < 0:
+        raise ValueError("r_lat must be >= 0")
+    self.radius_km = None if radius_km is None else float(radius_km)
+    self.r_lat = None if r_lat is None else int(r_lat)
+    self.r_lon = None if r_lon is None else np.asarray(r_lon, dtype=np.int64).reshape(-1)
+
+  @property
+  def names(self) -> List[str]:
+    return [o[1] for o in self.outputs]
+
+  def _sources(self, template0):
+    """{derived name: (op, [(offset, n) of each source])} with the channel counts checked."""
+    template0 = datasets.as_dataset(template0)
+    where = {name: (off, n) for name, off, n in datasets.channel_layout(template0)}
+    out = {}
+    for o in self.outputs:
+      srcs = o[1:] if o[0] == "copy" else o[2:]
+      for s in srcs:
+        if s not in where:
+          raise ValueError(f"{s!r} is not a target variable")
+      if o[0] == "norm2" and where[srcs[0]][1] != where[srcs[1]][1]:
+        raise ValueError(f"{srcs[0]!r} has {where[srcs[0]][1]} channels, {srcs[1]!r} {where[srcs[1]][1]}: the norm is taken "
+                         "channel by channel")
+      out[o[1]] = (o[0], [where[s] for s in srcs])
+    return out
+
+  def template(self, template0) -> datasets.Dataset:
+    """A Dataset of the derived variables (zeros) with the dims of their (first) source variable and the source's
+    coordinates: `EventSpec.packed`, `EnsembleScores.per_variable` and `EventScores.per_variable` work on it unchanged."""
+    template0 = datasets.as_dataset(template0)
+    self._sources(template0)
+    out = {}
+    for o in self.outputs:
+      src = template0[o[1] if o[0] == "copy" else o[2]]
+      out[o[1]] = datasets.Variable(src.dims, np.zeros_like(np.asarray(src.data)))
+    return datasets.Dataset(out, template0.coords)
+
+  def _per_channel(self, template0):
+    """[(op, channel of source a, channel of source b)] per derived channel, in the packed order of `template`."""
+    srcs = self._sources(template0)
+    rows = []
+    for name, _, n in datasets.channel_layout(self.template(template0)):
+      op, where = srcs[name]
+      for k in range(n):
+        rows.append((op, where[0][0] + k, where[-1][0] + k))
+    return rows
+
+  @staticmethod
+  def window(lat, lon, radius_km: float) -> Tuple[int, np.ndarray]:
+    """(r_lat, r_lon [n_lat]) of a great-circle radius on an equiangular grid: r_lat = rint(radius / (111.195 dlat)),
+    r_lon[i] = min((n_lon - 1) // 2, floor(radius / (111.195 dlon cos lat_i))); the pole rows take the cap (the whole row)."""
+    lat, lon = np.asarray(lat, np.float64).reshape(-1), np.asarray(lon, np.float64).reshape(-1)
+    if lat.size < 2 or lon.size < 2:
+      raise ValueError("window needs at least two latitudes and two longitudes")
+    dlat, dlon = abs(float(lat[1] - lat[0])), abs(float(lon[1] - lon[0]))
+    cap = (lon.size - 1) // 2
+    coslat = np.cos(np.deg2rad(lat))
+    r_lon = np.full(lat.size, cap, np.int64)
+    inside = np.abs(lat) < 90.0 - 1e-9
+    with np.errstate(divide="ignore", over="ignore"):
+      r_lon[inside] = np.minimum(float(cap), np.floor(float(radius_km) / (_KM_PER_DEGREE * dlon * coslat[inside]))).astype(np.int64)
+    return int(np.rint(float(radius_km) / (_KM_PER_DEGREE * dlat))), r_lon.astype(np.int32)
+
+  def plan(self, template0, scale=None, loc=None) -> Dict[str, object]:
+    """The keyword arguments of `NativeDenoiser.ens_derive_set`.  `scale`, `loc` [c_src]: the members hold (x - loc) / scale
+    per source channel (None: 1 and 0), so a norm2 channel gets (sa, la, sb, lb) = the sources' scale and location and
+    comes out in physical units."""
+    template0 = datasets.as_dataset(template0)
+    c_src = sum(n for _, _, n in datasets.channel_layout(template0))
+    scale = np.ones(c_src) if scale is None else np.asarray(scale, np.float64).reshape(-1)
+    loc = np.zeros(c_src) if loc is None else np.asarray(loc, np.float64).reshape(-1)
+    if scale.shape != (c_src,) or loc.shape != (c_src,):
+      raise ValueError(f"scale and loc must have shape ({c_src},)")
+    rows = self._per_channel(template0)
+    op = np.array([1 if r[0] == "norm2" else 0 for r in rows], np.int32)
+    src_a = np.array([r[1] for r in rows], np.int32)
+    src_b = np.array([r[2] for r in rows], np.int32)
+    affine = np.tile(np.array([1.0, 0.0, 1.0, 0.0]), (len(rows), 1))
+    for j, r in enumerate(rows):
+      if r[0] == "norm2":
+        affine[j] = (scale[r[1]], loc[r[1]], scale[r[2]], loc[r[2]])
+    sizes = template0.sizes
+    if "lat" not in sizes or "lon" not in sizes:
+      raise ValueError("template must have 'lat' and 'lon' dimensions")
+    n_lat, n_lon = int(sizes["lat"]), int(sizes["lon"])
+    out = dict(c_src=c_src, op=op, src_a=src_a, src_b=src_b, affine=affine, pool=_POOLS[self.pool], n_lat=n_lat, n_lon=n_lon,
+               r_lat=0, r_lon=None, row_weight=None)
+    if self.pool is not None:
+      if self.radius_km is not None:
+        r_lat, r_lon = self.window(template0.coords["lat"], template0.coords["lon"], self.radius_km)
+      else:
+        r_lat, r_lon = self.r_lat, self.r_lon
+      r_lon = np.asarray(r_lon, np.int64)
+      if r_lon.shape != (n_lat,):
+        raise ValueError(f"r_lon must have one entry per latitude row ({n_lat}), got {r_lon.shape}")
+      if np.any((r_lon < 0) | (r_lon > (n_lon - 1) // 2)):
+        raise ValueError(f"r_lon must lie in 0 .. {(n_lon - 1) // 2}")
+      out.update(r_lat=int(r_lat), r_lon=r_lon.astype(np.int32),
+                 row_weight=np.asarray(losses.normalized_latitude_weights(template0), np.float64))
+    return out
+
+  def channel_stats(self, template0, scale=None, loc=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(scale_d, loc_d) [c_d]: a copy channel keeps its source's, a norm2 channel is in physical units already: (1, 0)."""
+    template0 = datasets.as_dataset(template0)
+    c_src = sum(n for _, _, n in datasets.channel_layout(template0))
+    scale = np.ones(c_src) if scale is None else np.asarray(scale, np.float64).reshape(-1)
+    loc = np.zeros(c_src) if loc is None else np.asarray(loc, np.float64).reshape(-1)
+    if scale.shape != (c_src,) or loc.shape != (c_src,):
+      raise ValueError(f"scale and loc must have shape ({c_src},)")
+    rows = self._per_channel(template0)
+    return (np.array([1.0 if r[0] == "norm2" else scale[r[1]] for r in rows]),
+            np.array([0.0 if r[0] == "norm2" else loc[r[1]] for r in rows]))

@@ -525,6 +525,57 @@ int gc_ens_event_score(gc_handle* h, const float* truth /* NULL = the truth uplo
 int gc_ens_event_download(gc_handle* h, int32_t threshold, uint8_t* code /* [G,B,c_out] */);
 
 /*
+ * Derived and pooled ensemble fields on the device: 10 m wind speed, which is no model channel, and
+ * spatially pooled fields -- "the maximum within r km", the area mean over a region -- formed from the members and the truth
+ * of one handle's gc_ens_* store and left in the member store of a SECOND handle, on which every scorer of this library
+ * (gc_ens_score, gc_ens_spectrum, gc_ens_event_*, gc_ens_download_member, gc_ens_download_fields) then works as it is.  The
+ * reference project has no verification code; the yardstick is the definition below, restated in tests/derive_reference.py.
+ * Source handle `src`: a full store of M members and a truth y, each [G, B, c_src] float32, G = n_lat n_lon, node =
+ * lat_i n_lon + lon_j (the grid of gc_spec_set_tables).  Destination handle `dst`: the same device, G and batch; its own
+ * c_out = c_d is the number of derived channels.  It needs gc_set_graph only.
+ * Step 1, per derived channel j, with op[j], src_a[j], src_b[j] and affine[j] = (sa, la, sb, lb):
+ *   COPY  (0)  d = x[src_a], the same bits, no arithmetic; src_b and affine are ignored
+ *   NORM2 (1)  d = (float) sqrt(u u + v v) in double, u = (double) x[src_a] sa + la, v = (double) x[src_b] sb + lb, rounded
+ *              once: wind speed in physical units from normalised components
+ * Step 2, pool in {NONE 0, MAX 1, MIN 2, MEAN 3} of the float32 field d over the latitude-adaptive window
+ *   Win(i, j) = {(i', (j + t) mod n_lon) : max(0, i - r_lat) <= i' <= min(n_lat - 1, i + r_lat), |t| <= r_lon[i']}
+ * The longitude wraps, the latitude is clipped (nothing crosses a pole), and the width of a row is that of the row i', not
+ * of the centre row: the window approximates a fixed distance on the sphere and is separable.  Per (b, channel) the output
+ * at (i, j) is NaN iff the centre d(i, j) is not finite; else the window points that are not finite (NaN, +-inf) are skipped:
+ *   MAX / MIN  the extreme of the finite window values (exact)
+ *   MEAN       sum row_weight[i'] d / sum row_weight[i'] over the finite window points, in double, rounded once
+ *   NONE       d
+ * The truth goes through the same map.
+ *   gc_ens_derive_set  the plan: op, src_a, src_b [c_d], affine [c_d][4], pool, the grid, r_lat >= 0, r_lon [n_lat] with
+ *                      0 <= r_lon[i] <= (n_lon - 1) / 2, row_weight [n_lat] finite and > 0 (r_lon and row_weight may be
+ *                      NULL when pool == 0).  Needs gc_set_graph only.  Through pinned staging: the caller's arrays are
+ *                      free on return.  Replaces an earlier plan ("device_allocations" stays flat), survives
+ *                      gc_ens_reserve, released by gc_destroy.  GC_ERR_STATE: no graph.  GC_ERR_INVALID_ARGUMENT: a null
+ *                      pointer, n_lat n_lon != G, a source channel outside [0, c_src), r_lat < 0, r_lon[i] out of range, a
+ *                      row_weight that is not finite and > 0.  GC_ERR_UNSUPPORTED: an unknown op or pool; a row that
+ *                      does not fit the 64 KB row tile of the pooling pass (n_lon > 16384; with MEAN, n_lon > 5461).
+ *   gc_ens_derive      every slot of dst's store becomes the derived member and counts as pushed; dst's truth buffer
+ *                      becomes the derived truth, so truth = NULL works in every scorer of dst; dst's event codes and mean
+ *                      / variance fields count as not computed.  truth: host [G, B, c_src], uploaded into and kept in
+ *                      src's truth buffer as gc_ens_score(src, truth, ...) would, or NULL = src's last truth.  The
+ *                      kernels run on dst's stream, ordered behind src's stream by an event.  Synchronous.
+ *                      GC_ERR_INVALID_ARGUMENT: src is NULL, dst itself or on another device; src has no graph, another
+ *                      G or batch, or c_out != c_src of the plan.  GC_ERR_STATE: no plan, no store on dst, no store on
+ *                      src, the two stores differ in M, a src slot not pushed since its gc_ens_reserve, no truth.
+ * Launches: a derive pass (the whole call with pool == 0), then per chunk of at most 8 of the M + 1 fields a row pass
+ * (one latitude row pooled along the longitude in LDS, at a cost per output that does not grow with r_lon) and a column
+ * pass over a handle-owned intermediate (8 fields of a float, or a double and an int32, per point: made again only when
+ * its size changes).  No atomics: the same call twice returns identical bytes.  Nothing else on either handle is
+ * touched: not the conditioning, the last sample, the stash, the loss or spectrum buffers, src's store contents or the
+ * captured sample graphs.  Counters: "ens_derive_calls" (calls so far), "ens_derive_device_us" (HIP-event time of the
+ * last call's launches).
+ */
+int gc_ens_derive_set(gc_handle* dst, int32_t c_src, const int32_t* op, const int32_t* src_a, const int32_t* src_b,
+                      const double* affine /* [c_out][4] */, int32_t pool, int32_t n_lat, int32_t n_lon, int32_t r_lat,
+                      const int32_t* r_lon /* [n_lat] */, const double* row_weight /* [n_lat] */);
+int gc_ens_derive(gc_handle* dst, gc_handle* src, const float* truth /* [G,B,c_src] host, NULL = src's last truth */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
