@@ -24,14 +24,17 @@ PY
 FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DGC_SOURCE_HASH="\"$SRC_HASH\"" "$@")
 OBJ=$(mktemp -d)
 trap 'rm -rf "$OBJ"' EXIT
+mapfile -t UNITS < <(grep -v '^#' SOURCES)          # the translation units: one list, shared with tools/build_variant.sh
 pids=()
-for src in gc_kernels.hip gc_api.hip gc_weights.hip gc_forward.hip gc_sampler.hip gc_noise.hip gc_ensemble.hip gc_spectrum.hip gc_events.hip gc_derive.hip gc_graph.cpp; do
+objs=("$OBJ/gc_kernels_a16.o")
+for src in "${UNITS[@]}"; do
   "$HIPCC" "${FLAGS[@]}" -c "$src" -o "$OBJ/${src%.*}.o" &
   pids+=($!)
+  objs+=("$OBJ/${src%.*}.o")
 done
 # the same kernels again as namespace gc_a16: 2-MFMA variants for exact-fp16 activations (gc_kernels.hip, top)
 "$HIPCC" "${FLAGS[@]}" -DGC_TU_A16 -c gc_kernels.hip -o "$OBJ/gc_kernels_a16.o" &
 pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done
-"$HIPCC" --offload-arch=gfx950 -fPIC -shared "$OBJ"/gc_kernels.o "$OBJ"/gc_kernels_a16.o "$OBJ"/gc_api.o "$OBJ"/gc_weights.o "$OBJ"/gc_forward.o "$OBJ"/gc_sampler.o "$OBJ"/gc_noise.o "$OBJ"/gc_ensemble.o "$OBJ"/gc_spectrum.o "$OBJ"/gc_events.o "$OBJ"/gc_derive.o "$OBJ"/gc_graph.o -o "$OUT"
+"$HIPCC" --offload-arch=gfx950 -fPIC -shared "${objs[@]}" -o "$OUT"
 echo "built $(pwd)/$OUT (sources $SRC_HASH)"

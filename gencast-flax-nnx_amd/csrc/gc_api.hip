@@ -198,18 +198,15 @@ static void destroy_impl(gc_handle* h) {
     if (c.saved) (void)hipEventSynchronize(c.ev_w);
     if (c.read) (void)hipEventSynchronize(c.ev_r);
   }
-  for (std::vector<void*>* l : {&h->allocs, &h->weight_allocs, &h->cache_allocs, &h->ens_allocs, &h->ctx_allocs, &h->spec_allocs, &h->spec_work_allocs,
-                                &h->evt_allocs, &h->evt_table_allocs, &h->drv_allocs, &h->drv_work_allocs})
-    free_allocs(l);
+  for (BufferGroup* g : h->groups) g->free();
   if (h->d_nonfinite) (void)hipFree(h->d_nonfinite);
   for (void* p : {(void*)h->h_nonfinite, (void*)h->pin_cond, (void*)h->pin_noise, (void*)h->pin_forc,
                   (void*)h->pin_lguard})
     if (p) (void)hipHostFree(p);
   if (h->ev_pin) (void)hipEventDestroy(h->ev_pin);
   if (h->ev_stash) (void)hipEventDestroy(h->ev_stash);
-  for (hipEvent_t e : {h->ev_ens_free, h->ev_ens_done, h->ev_ens0, h->ev_ens1, h->ev_sp0, h->ev_sp1, h->ev_evt0, h->ev_evt1,
-                       h->ev_drv0, h->ev_drv1, h->ev_drv_src})
-    if (e) (void)hipEventDestroy(e);
+  for (Event* e : h->events)
+    if (e->e) (void)hipEventDestroy(e->e);
   for (gc_handle::CtxSlot& c : h->ctx)
     for (hipEvent_t e : {c.ev_w, c.ev_r})
       if (e) (void)hipEventDestroy(e);
@@ -877,10 +874,10 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "ens_derive_calls") *value = h->drv_calls;
   else if (n == "ens_derive_device_us") *value = h->drv_device_us;
   else if (n == "noise_stream") *value = (int64_t)h->nz_stream;
-  else if (n == "device_allocations")
-    *value = (int64_t)(h->allocs.size() + h->weight_allocs.size() + h->cache_allocs.size() + h->ens_allocs.size() +
-                       h->ctx_allocs.size() + h->spec_allocs.size() + h->spec_work_allocs.size() + h->evt_allocs.size() +
-                       h->evt_table_allocs.size() + h->drv_allocs.size() + h->drv_work_allocs.size());
+  else if (n == "device_allocations") {
+    *value = 0;
+    for (const BufferGroup* g : h->groups) *value += (int64_t)g->ptrs.size();
+  }
   else return fail(h, GC_ERR_INVALID_ARGUMENT, "unknown counter: " + n);
   return GC_OK;
   });

@@ -13,7 +13,7 @@
 //   column   per point the intermediates of the rows |i' - i| <= r_lat (clipped at the poles) combined -- the mean with
 //            row_weight[i'] -- and written over the centre; NaN where the centre itself is not finite.
 // No atomics: every output has one writer and every sum a fixed order, so two calls give the same bytes.
-#include "gc_handle.h"
+#include "gc_store.h"
 
 // the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
 #pragma clang fp contract(off)
@@ -305,31 +305,6 @@ static hipError_t launch_ens_pool_col(hipStream_t s, int pool, float* mem, float
 
 using namespace gci;
 
-namespace {
-
-size_t drv_field_len(const gc_handle* h) { return (size_t)h->hg.G * h->cfg.batch * h->cfg.c_out; }
-
-// through the pinned staging buffer of the noise upload ([G, B, c_out] floats), in pieces where the table is longer
-int drv_staged_upload(gc_handle* h, void* dev, const void* src, size_t bytes) {
-  const size_t cap = drv_field_len(h) * sizeof(float);
-  for (size_t off = 0; off < bytes; off += cap) {
-    const size_t n = std::min(cap, bytes - off);
-    GC_HIP(h, hipEventSynchronize(h->ev_pin));
-    std::memcpy(h->pin_noise, static_cast<const char*>(src) + off, n);
-    GC_HIP(h, hipMemcpyAsync(static_cast<char*>(dev) + off, h->pin_noise, n, hipMemcpyHostToDevice, h->stream));
-    GC_HIP(h, hipEventRecord(h->ev_pin, h->stream));
-  }
-  return GC_OK;
-}
-
-// a failure inside a call made on the source handle is reported on the handle the caller asked
-int drv_from_src(gc_handle* h, gc_handle* src, int rc) {
-  if (rc) h->err = "source handle: " + src->err;
-  return rc;
-}
-
-}  // namespace
-
 extern "C" {
 
 int gc_ens_derive_set(gc_handle* h, int32_t c_src, const int32_t* op, const int32_t* src_a, const int32_t* src_b,
@@ -371,16 +346,14 @@ int gc_ens_derive_set(gc_handle* h, int32_t c_src, const int32_t* op, const int3
     ib[2 * c_d + j] = op[j] == gc::kDrvNorm2 ? src_b[j] : src_a[j];
   }
   for (int i = 0; i < n_lat; ++i) ib[3 * c_d + i] = pool != gc::kPoolNone ? r_lon[i] : 0;
-  GC_HIP(h, hipStreamSynchronize(h->stream));        // nothing reads the old plan any more
-  free_allocs(&h->drv_allocs);
+  GC_HIP(h, h->drv_allocs.drop(h->stream));          // nothing reads the old plan any more
   h->drv_set = false;
   int rc;
   double* d_blob = nullptr;
   if ((rc = dev_alloc(h, &d_blob, blob.size(), &h->drv_allocs))) return rc;
-  for (hipEvent_t* e : {&h->ev_drv0, &h->ev_drv1})
-    if (!*e) GC_HIP(h, hipEventCreate(e));
-  if (!h->ev_drv_src) GC_HIP(h, hipEventCreateWithFlags(&h->ev_drv_src, hipEventDisableTiming));
-  if ((rc = drv_staged_upload(h, d_blob, blob.data(), blob.size() * sizeof(double)))) return rc;
+  GC_HIP(h, h->drv_time.ensure());
+  GC_HIP(h, h->ev_drv_src.ensure());
+  if ((rc = store_upload(h, d_blob, blob.data(), blob.size() * sizeof(double)))) return rc;
   h->d_drv_affine = d_blob;
   h->d_drv_roww = d_blob + (size_t)4 * c_d;
   h->d_drv_op = reinterpret_cast<int*>(d_blob + n_d);
@@ -401,45 +374,34 @@ int gc_ens_derive(gc_handle* h, gc_handle* src, const float* truth) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
   if (!src || src == h) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source must be another handle");
-  if (src->device != h->device) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle is on another device");
   if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
   if (!h->drv_set) return fail(h, GC_ERR_STATE, "no plan (gc_ens_derive_set)");
-  if (!src->has_graph || src->hg.G != h->hg.G || src->cfg.batch != h->cfg.batch || src->cfg.c_out != h->drv_c_src)
-    return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle has other dimensions (G, batch, c_out == c_src of the plan)");
+  int rc = check_peer(h, src, "source", false, h->drv_c_src, "c_out == c_src of the plan");
+  if (rc) return rc;
   if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
   if (src->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store on the source handle (gc_ens_reserve)");
   if (src->ens_members != h->ens_members) return fail(h, GC_ERR_STATE, "the two member stores hold different numbers of members");
-  const int M = h->ens_members;
-  for (int i = 0; i < M; ++i)
-    if (!src->ens_filled[(size_t)i]) return fail(h, GC_ERR_STATE, "source member slot " + std::to_string(i) + " has not been pushed");
-  if (!truth && !src->has_ens_truth) return fail(h, GC_ERR_STATE, "no truth on the source handle (pass one to gc_ens_derive)");
+  if ((rc = store_complete(h, src, "source "))) return rc;
   GC_HIP(h, hipSetDevice(h->device));
+  if ((rc = take_truth(h, src, truth, "gc_ens_derive"))) return rc;   // into the source's truth buffer, as gc_ens_score(src, truth, ...) would
   const gc_config& c = h->cfg;
-  const int G = h->hg.G, B = c.batch, c_d = c.c_out, W = B * c_d, pool = h->drv_pool;
-  const size_t field = drv_field_len(h), sfield = (size_t)G * B * src->cfg.c_out;
-  int rc;
-  if (truth) {                                     // into the source's truth buffer, as gc_ens_score(src, truth, ...) would
-    if (!src->d_ens_truth && (rc = drv_from_src(h, src, dev_alloc(src, &src->d_ens_truth, sfield)))) return rc;
-    if ((rc = drv_from_src(h, src, staged_upload(src, src->pin_noise, src->d_ens_truth, truth, sfield)))) return rc;
-    src->has_ens_truth = true;
-  }
+  const int G = h->hg.G, B = c.batch, c_d = c.c_out, W = B * c_d, pool = h->drv_pool, M = h->ens_members;
+  const size_t field = field_len(h);
   if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
   const int chunk = std::min(gc::kDrvChunk, M + 1);
   const size_t need = pool == gc::kPoolNone ? 0 : (size_t)gc::kDrvChunk * field * (pool == gc::kPoolMean ? gc::kDrvMeanBytes : 4);
   if (need && need != h->drv_work_bytes) {         // sized by the pool kind and the field: made again only when they change
-    GC_HIP(h, hipStreamSynchronize(h->stream));
-    free_allocs(&h->drv_work_allocs);
+    GC_HIP(h, h->drv_work_allocs.drop(h->stream));
     h->drv_work_bytes = 0;
     if ((rc = dev_alloc(h, &h->d_drv_work, need, &h->drv_work_allocs))) return rc;
     h->drv_work_bytes = need;
   }
   hipStream_t s = h->stream;
   // the source's store and truth are complete on ITS stream: this handle's stream goes on behind them
-  GC_HIP(h, hipEventRecord(h->ev_drv_src, src->stream));
-  GC_HIP(h, hipStreamWaitEvent(s, h->ev_drv_src, 0));
+  if ((rc = order_behind(h, h->ev_drv_src, src->stream, s))) return rc;
   h->evt_scored = false;
   h->has_ens_fields = false;
-  GC_HIP(h, hipEventRecord(h->ev_drv0, s));
+  GC_HIP(h, h->drv_time.begin(s));
   if ((rc = launch(h, gc::KC_PACK, [&] {
          return gc::launch_ens_derive(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out, c_d,
                                       h->d_drv_op, h->d_drv_a, h->d_drv_b, h->d_drv_affine);
@@ -460,11 +422,9 @@ int gc_ens_derive(gc_handle* h, gc_handle* src, const float* truth) {
         return rc;
     }
   }
-  GC_HIP(h, hipEventRecord(h->ev_drv1, s));
+  GC_HIP(h, h->drv_time.end(s));
   GC_HIP(h, hipStreamSynchronize(s));
-  float ms = 0.f;
-  GC_HIP(h, hipEventElapsedTime(&ms, h->ev_drv0, h->ev_drv1));
-  h->drv_device_us = (int64_t)(ms * 1000.0f);
+  GC_HIP(h, h->drv_time.microseconds(&h->drv_device_us));
   std::fill(h->ens_filled.begin(), h->ens_filled.end(), 1);
   h->has_ens_truth = true;
   ++h->drv_calls;

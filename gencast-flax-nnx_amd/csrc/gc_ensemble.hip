@@ -14,7 +14,7 @@
 //   S0 = sum w, S1 = sum w (m - y), S2 = sum w (m - y)^2, S3 = sum w s2, S4 = sum w ae, S5 = sum w d,  H[r] += 1
 // No atomics on floats: every partial has one writer and every sum a fixed order, so the result does not depend on how
 // the launch was scheduled.  The rank counts are integers; their LDS atomics commute.
-#include "gc_handle.h"
+#include "gc_store.h"
 
 // the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
 #pragma clang fp contract(off)
@@ -244,8 +244,6 @@ using namespace gci;
 
 namespace {
 
-size_t ens_field(const gc_handle* h) { return (size_t)h->hg.G * h->cfg.batch * h->cfg.c_out; }
-
 // the entries that need G only: no weights, no gc_finalize
 int ens_ready(gc_handle* h, bool need_store) {
   if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
@@ -258,8 +256,6 @@ int ens_slot(gc_handle* h, int32_t slot) {
   return GC_OK;
 }
 
-size_t ctx_field(const gc_handle* h) { return (size_t)h->hg.G * h->cfg.batch * h->cfg.c_in; }
-
 int ctx_ready(gc_handle* h, int32_t slot) {
   if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
   if (h->ctx_slots == 0) return fail(h, GC_ERR_STATE, "no context store (gc_ctx_reserve)");
@@ -269,17 +265,16 @@ int ctx_ready(gc_handle* h, int32_t slot) {
 
 // the handle on the other side of a context copy: same device, same [G, B, c_in], finalized
 int ctx_peer(gc_handle* h, const gc_handle* o) {
-  if (o->device != h->device) return fail(h, GC_ERR_INVALID_ARGUMENT, "the other handle is on another device");
-  if (!o->has_graph || o->hg.G != h->hg.G || o->cfg.batch != h->cfg.batch || o->cfg.c_in != h->cfg.c_in)
-    return fail(h, GC_ERR_INVALID_ARGUMENT, "the other handle has other dimensions (G, batch, c_in)");
+  if (int rc = check_peer(h, o, "other", true)) return rc;
   if (!o->finalized) return fail(h, GC_ERR_STATE, "gc_finalize has not been called on the other handle");
   return GC_OK;
 }
 
-// a failure inside a call made on another handle is reported on the handle the caller asked
-int from_peer(gc_handle* h, gc_handle* o, int rc, const char* who) {
-  if (rc && o != h) h->err = std::string(who) + " handle: " + o->err;
-  return rc;
+// the handle a member is pushed from: same device, same [G, B, c_out] (and c_in for a state), a checked sample on it
+int push_source(gc_handle* h, gc_handle* src, bool c_in) {
+  if (int rc = check_peer(h, src, "source", c_in, h->cfg.c_out)) return rc;
+  if (!src->finalized || !src->has_sample) return fail(h, GC_ERR_STATE, "no sample on the source handle (gc_sample_resident)");
+  return GC_OK;
 }
 
 }  // namespace
@@ -294,8 +289,7 @@ int gc_ens_reserve(gc_handle* h, int32_t n_members) {
   if (n_members < gc::kEnsMinMembers || n_members > gc::kEnsMaxMembers)
     return fail(h, GC_ERR_UNSUPPORTED, "n_members must be in 2..64");
   GC_HIP(h, hipSetDevice(h->device));
-  GC_HIP(h, hipStreamSynchronize(h->stream));      // every push into the old store has landed (pushes from other handles are ordered into this stream)
-  free_allocs(&h->ens_allocs);
+  GC_HIP(h, h->ens_allocs.drop(h->stream));         // every push into the old store has landed (pushes from other handles are ordered into this stream)
   h->ens_members = 0;
   h->ens_filled.clear();
   h->has_ens_fields = false;
@@ -305,20 +299,19 @@ int gc_ens_reserve(gc_handle* h, int32_t n_members) {
   const gc_config& c = h->cfg;
   const int G = h->hg.G, W = c.batch * c.c_out, M = n_members;
   const size_t blocks = (size_t)gc::loss_reduce_blocks(G, c.batch, c.c_out), tiles = (size_t)(W + 255) / 256;
-  if ((rc = dev_alloc(h, &h->d_ens, (size_t)M * ens_field(h), &h->ens_allocs)) ||
+  if ((rc = dev_alloc(h, &h->d_ens, (size_t)M * field_len(h), &h->ens_allocs)) ||
       (rc = dev_alloc(h, &h->d_ens_part, blocks * 6 * W, &h->ens_allocs)) ||
       (rc = dev_alloc(h, &h->d_ens_hpart, blocks * W * (M + 1) + blocks * tiles, &h->ens_allocs)) ||
       (rc = dev_alloc(h, &h->d_ens_sums, (size_t)6 * W, &h->ens_allocs)) ||
       (rc = dev_alloc(h, &h->d_ens_hist, (size_t)W * (M + 1) + 1, &h->ens_allocs)) ||
       (rc = dev_alloc(h, &h->d_ens_state_src, (size_t)c.c_out, &h->ens_allocs))) {
-    free_allocs(&h->ens_allocs);
+    h->ens_allocs.free();
     return rc;
   }
   h->ens_state_src.clear();
-  for (hipEvent_t* e : {&h->ev_ens_free, &h->ev_ens_done})
-    if (!*e) GC_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
-  for (hipEvent_t* e : {&h->ev_ens0, &h->ev_ens1})
-    if (!*e) GC_HIP(h, hipEventCreate(e));
+  GC_HIP(h, h->ev_ens_free.ensure());
+  GC_HIP(h, h->ev_ens_done.ensure());
+  GC_HIP(h, h->ens_time.ensure());
   h->ens_filled.assign((size_t)M, 0);
   h->ens_members = M;
   return GC_OK;
@@ -347,29 +340,17 @@ int gc_ens_push(gc_handle* h, int32_t slot, gc_handle* src) {
   int rc = ens_ready(h, true);
   if (rc || (rc = ens_slot(h, slot))) return rc;
   if (!src) src = h;
-  if (src->device != h->device) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle is on another device");
-  if (!src->has_graph || src->hg.G != h->hg.G || src->cfg.batch != h->cfg.batch || src->cfg.c_out != h->cfg.c_out)
-    return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle has other dimensions (G, batch, c_out)");
-  if (!src->finalized || !src->has_sample) return fail(h, GC_ERR_STATE, "no sample on the source handle (gc_sample_resident)");
+  if ((rc = push_source(h, src, false))) return rc;
   GC_HIP(h, hipSetDevice(h->device));
-  if ((rc = resolve_guard(src))) {                 // the member is the CHECKED sample (exact-f32 re-run included)
-    if (src != h) h->err = "source handle: " + src->err;
-    return rc;
-  }
-  float* const dst = h->d_ens + (size_t)slot * ens_field(h);
-  const size_t bytes = ens_field(h) * sizeof(float);
-  if (src == h) {
-    GC_HIP(h, hipMemcpyAsync(dst, h->d_sx, bytes, hipMemcpyDeviceToDevice, h->stream));
-  } else {
-    // the copy runs on the SOURCE's stream, in front of that handle's next sample; the two streams are ordered by
-    // events, both ways: the store is no longer being read when the copy starts, and is complete before this
-    // handle's stream goes on
-    GC_HIP(h, hipEventRecord(h->ev_ens_free, h->stream));
-    GC_HIP(h, hipStreamWaitEvent(src->stream, h->ev_ens_free, 0));
+  if ((rc = relay(h, src, resolve_guard(src), "source"))) return rc;   // the member is the CHECKED sample (exact-f32 re-run included)
+  float* const dst = h->d_ens + (size_t)slot * field_len(h);
+  const size_t bytes = field_len(h) * sizeof(float);
+  // on the SOURCE's stream, in front of that handle's next sample
+  auto copy = [&]() -> int {
     GC_HIP(h, hipMemcpyAsync(dst, src->d_sx, bytes, hipMemcpyDeviceToDevice, src->stream));
-    GC_HIP(h, hipEventRecord(h->ev_ens_done, src->stream));
-    GC_HIP(h, hipStreamWaitEvent(h->stream, h->ev_ens_done, 0));
-  }
+    return GC_OK;
+  };
+  if ((rc = src == h ? copy() : on_peer_stream(h, src, copy))) return rc;
   h->ens_filled[(size_t)slot] = 1;
   return GC_OK;
   });
@@ -382,7 +363,7 @@ int gc_ens_push_host(gc_handle* h, int32_t slot, const float* field) {
   if (rc || (rc = ens_slot(h, slot))) return rc;
   if (!field) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   GC_HIP(h, hipSetDevice(h->device));
-  if ((rc = staged_upload(h, h->pin_noise, h->d_ens + (size_t)slot * ens_field(h), field, ens_field(h)))) return rc;
+  if ((rc = staged_upload(h, h->pin_noise, h->d_ens + (size_t)slot * field_len(h), field, field_len(h)))) return rc;
   h->ens_filled[(size_t)slot] = 1;
   return GC_OK;
   });
@@ -394,27 +375,20 @@ int gc_ens_score(gc_handle* h, const float* truth, int32_t want_fields, double* 
   int rc = ens_ready(h, true);
   if (rc) return rc;
   if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  const int M = h->ens_members;
-  for (int i = 0; i < M; ++i)
-    if (!h->ens_filled[(size_t)i]) return fail(h, GC_ERR_STATE, "member slot " + std::to_string(i) + " has not been pushed");
+  if ((rc = store_complete(h, h))) return rc;
   if (!h->has_ens_w) return fail(h, GC_ERR_STATE, "no node weights (gc_ens_set_node_weight)");
-  if (!truth && !h->has_ens_truth) return fail(h, GC_ERR_STATE, "no truth on the device (pass one to gc_ens_score)");
   GC_HIP(h, hipSetDevice(h->device));
+  if ((rc = take_truth(h, h, truth, "gc_ens_score"))) return rc;
   const gc_config& c = h->cfg;
-  const int G = h->hg.G, B = c.batch, W = B * c.c_out;
-  const size_t field = ens_field(h);
-  if (truth) {
-    if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
-    if ((rc = staged_upload(h, h->pin_noise, h->d_ens_truth, truth, field))) return rc;
-    h->has_ens_truth = true;
-  }
+  const int G = h->hg.G, B = c.batch, W = B * c.c_out, M = h->ens_members;
+  const size_t field = field_len(h);
   if (want_fields && !h->d_ens_mean) {
     if ((rc = dev_alloc(h, &h->d_ens_mean, field)) || (rc = dev_alloc(h, &h->d_ens_var, field))) return rc;
   }
   hipStream_t s = h->stream;
   const int blocks = gc::loss_reduce_blocks(G, B, c.c_out);
   unsigned* const ipart = h->d_ens_hpart + (size_t)blocks * W * (M + 1);
-  GC_HIP(h, hipEventRecord(h->ev_ens0, s));
+  GC_HIP(h, h->ens_time.begin(s));
   if ((rc = launch(h, gc::KC_PACK, [&] {
          return gc::launch_ens_score(s, h->d_ens, field, M, h->d_ens_truth, h->d_ens_w, G, B, c.c_out, h->d_ens_part,
                                      h->d_ens_hpart, ipart, want_fields ? h->d_ens_mean : nullptr,
@@ -425,15 +399,13 @@ int gc_ens_score(gc_handle* h, const float* truth, int32_t want_fields, double* 
          return gc::launch_ens_finish(s, h->d_ens_part, h->d_ens_hpart, ipart, blocks, W, M, h->d_ens_sums, h->d_ens_hist);
        })))
     return rc;
-  GC_HIP(h, hipEventRecord(h->ev_ens1, s));
+  GC_HIP(h, h->ens_time.end(s));
   if (want_fields) h->has_ens_fields = true;
   std::vector<unsigned long long> hist((size_t)W * (M + 1) + 1);
   GC_HIP(h, hipMemcpyAsync(sums, h->d_ens_sums, (size_t)6 * W * sizeof(double), hipMemcpyDeviceToHost, s));
   GC_HIP(h, hipMemcpyAsync(hist.data(), h->d_ens_hist, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   GC_HIP(h, hipStreamSynchronize(s));
-  float ms = 0.f;
-  GC_HIP(h, hipEventElapsedTime(&ms, h->ev_ens0, h->ev_ens1));
-  h->ens_score_device_us = (int64_t)(ms * 1000.0f);
+  GC_HIP(h, h->ens_time.microseconds(&h->ens_score_device_us));
   h->ens_invalid_points = (int64_t)hist.back();
   ++h->ens_scores;
   if (rank_hist)
@@ -449,7 +421,7 @@ int gc_ens_download_fields(gc_handle* h, float* mean, float* variance) {
   if (rc) return rc;
   if (!h->has_ens_fields) return fail(h, GC_ERR_STATE, "no mean / variance fields on the device (gc_ens_score with want_fields)");
   GC_HIP(h, hipSetDevice(h->device));
-  const size_t bytes = ens_field(h) * sizeof(float);
+  const size_t bytes = field_len(h) * sizeof(float);
   if (mean) GC_HIP(h, hipMemcpyAsync(mean, h->d_ens_mean, bytes, hipMemcpyDeviceToHost, h->stream));
   if (variance) GC_HIP(h, hipMemcpyAsync(variance, h->d_ens_var, bytes, hipMemcpyDeviceToHost, h->stream));
   GC_HIP(h, hipStreamSynchronize(h->stream));
@@ -465,10 +437,7 @@ int gc_ens_push_state(gc_handle* h, int32_t slot, gc_handle* src, const int32_t*
   if (!state_src) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   if (!src) src = h;
   const gc_config& c = h->cfg;
-  if (src->device != h->device) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle is on another device");
-  if (!src->has_graph || src->hg.G != h->hg.G || src->cfg.batch != c.batch || src->cfg.c_out != c.c_out || src->cfg.c_in != c.c_in)
-    return fail(h, GC_ERR_INVALID_ARGUMENT, "the source handle has other dimensions (G, batch, c_in, c_out)");
-  if (!src->finalized || !src->has_sample) return fail(h, GC_ERR_STATE, "no sample on the source handle (gc_sample_resident)");
+  if ((rc = push_source(h, src, true))) return rc;
   if (!src->has_cond) return fail(h, GC_ERR_STATE, "no conditioning on the source handle (gc_upload_cond)");
   for (int j = 0; j < c.c_out; ++j) {
     if (state_src[j] >= c.c_in) return fail(h, GC_ERR_INVALID_ARGUMENT, "state_src: conditioning channel out of range");
@@ -476,7 +445,7 @@ int gc_ens_push_state(gc_handle* h, int32_t slot, gc_handle* src, const int32_t*
       return fail(h, GC_ERR_INVALID_ARGUMENT, "state_src: a noisy slot holds no state");
   }
   GC_HIP(h, hipSetDevice(h->device));
-  if ((rc = from_peer(h, src, resolve_guard(src), "source"))) return rc;   // the state comes from the CHECKED sample
+  if ((rc = relay(h, src, resolve_guard(src), "source"))) return rc;   // the state comes from the CHECKED sample
   if (h->ens_state_src.size() != (size_t)c.c_out || !std::equal(state_src, state_src + c.c_out, h->ens_state_src.begin())) {
     // every earlier gather is ordered into this stream (ev_ens_done): after the wait none reads the old table
     GC_HIP(h, hipStreamSynchronize(h->stream));
@@ -484,20 +453,14 @@ int gc_ens_push_state(gc_handle* h, int32_t slot, gc_handle* src, const int32_t*
     GC_HIP(h, hipStreamSynchronize(h->stream));      // `state_src` is the caller's again, and every stream sees the table
     h->ens_state_src.assign(state_src, state_src + c.c_out);
   }
-  float* const dst = h->d_ens + (size_t)slot * ens_field(h);
+  float* const dst = h->d_ens + (size_t)slot * field_len(h);
+  // on the SOURCE's stream, as the copy of gc_ens_push
   auto gather = [&] {
-    return gc::launch_ens_state(src->stream, src->d_feats, src->d_sx, h->d_ens_state_src, h->hg.G, c.batch, c.c_in, c.c_out, dst);
+    return relay(h, src, launch(src, gc::KC_PACK, [&] {
+      return gc::launch_ens_state(src->stream, src->d_feats, src->d_sx, h->d_ens_state_src, h->hg.G, c.batch, c.c_in, c.c_out, dst);
+    }), "source");
   };
-  if (src == h) {
-    if ((rc = launch(h, gc::KC_PACK, gather))) return rc;
-  } else {
-    // on the SOURCE's stream, ordered against this handle's stream by events both ways, as in gc_ens_push
-    GC_HIP(h, hipEventRecord(h->ev_ens_free, h->stream));
-    GC_HIP(h, hipStreamWaitEvent(src->stream, h->ev_ens_free, 0));
-    if ((rc = from_peer(h, src, launch(src, gc::KC_PACK, gather), "source"))) return rc;
-    GC_HIP(h, hipEventRecord(h->ev_ens_done, src->stream));
-    GC_HIP(h, hipStreamWaitEvent(h->stream, h->ev_ens_done, 0));
-  }
+  if ((rc = src == h ? gather() : on_peer_stream(h, src, gather))) return rc;
   h->ens_filled[(size_t)slot] = 1;
   return GC_OK;
   });
@@ -512,7 +475,7 @@ int gc_ens_download_member(gc_handle* h, int32_t slot, float* out) {
   if (!h->ens_filled[(size_t)slot]) return fail(h, GC_ERR_STATE, "member slot " + std::to_string(slot) + " has not been pushed");
   GC_HIP(h, hipSetDevice(h->device));
   // (every push, whichever stream made it, is ordered into this one)
-  GC_HIP(h, hipMemcpyAsync(out, h->d_ens + (size_t)slot * ens_field(h), ens_field(h) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  GC_HIP(h, hipMemcpyAsync(out, h->d_ens + (size_t)slot * field_len(h), field_len(h) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   GC_HIP(h, hipStreamSynchronize(h->stream));
   return GC_OK;
   });
@@ -535,11 +498,11 @@ int gc_ctx_reserve(gc_handle* h, int32_t n) {
     if (c.read) GC_HIP(h, hipEventSynchronize(c.ev_r));
     c.saved = c.read = false;
   }
-  free_allocs(&h->ctx_allocs);
+  h->ctx_allocs.free();
   h->ctx_slots = 0;
   h->d_ctx = nullptr;
   int rc;
-  if ((rc = dev_alloc(h, &h->d_ctx, (size_t)n * ctx_field(h), &h->ctx_allocs))) return rc;
+  if ((rc = dev_alloc(h, &h->d_ctx, (size_t)n * cond_len(h), &h->ctx_allocs))) return rc;
   if (h->ctx.size() < (size_t)n) h->ctx.resize((size_t)n);
   for (int i = 0; i < n; ++i)
     for (hipEvent_t* e : {&h->ctx[(size_t)i].ev_w, &h->ctx[(size_t)i].ev_r})
@@ -558,11 +521,11 @@ int gc_ctx_save(gc_handle* h, int32_t slot, gc_handle* src) {
   if ((rc = ctx_peer(h, src))) return rc;
   if (!src->has_cond) return fail(h, GC_ERR_STATE, "no conditioning on the source handle (gc_upload_cond)");
   GC_HIP(h, hipSetDevice(h->device));
-  if (src->guard_pending && (rc = from_peer(h, src, resolve_guard(src), "source"))) return rc;
+  if (src->guard_pending && (rc = relay(h, src, resolve_guard(src), "source"))) return rc;
   gc_handle::CtxSlot& c = h->ctx[(size_t)slot];
   if (c.saved) GC_HIP(h, hipStreamWaitEvent(src->stream, c.ev_w, 0));
   if (c.read) GC_HIP(h, hipStreamWaitEvent(src->stream, c.ev_r, 0));
-  GC_HIP(h, hipMemcpyAsync(h->d_ctx + (size_t)slot * ctx_field(h), src->d_feats, ctx_field(h) * sizeof(float),
+  GC_HIP(h, hipMemcpyAsync(h->d_ctx + (size_t)slot * cond_len(h), src->d_feats, cond_len(h) * sizeof(float),
                            hipMemcpyDeviceToDevice, src->stream));
   GC_HIP(h, hipEventRecord(c.ev_w, src->stream));
   c.saved = true;
@@ -582,14 +545,14 @@ int gc_ctx_load(gc_handle* h, int32_t slot, gc_handle* dst) {
   if (!c.saved) return fail(h, GC_ERR_STATE, "context slot " + std::to_string(slot) + " has not been saved");
   GC_HIP(h, hipSetDevice(h->device));
   // a pending re-run needs the conditioning it sampled with (gc_upload_cond_dev)
-  if (dst->guard_pending && (rc = from_peer(h, dst, resolve_guard(dst), "destination"))) return rc;
+  if (dst->guard_pending && (rc = relay(h, dst, resolve_guard(dst), "destination"))) return rc;
   GC_HIP(h, hipStreamWaitEvent(dst->stream, c.ev_w, 0));
   if (c.read) GC_HIP(h, hipStreamWaitEvent(dst->stream, c.ev_r, 0));
-  GC_HIP(h, hipMemcpyAsync(dst->d_feats, h->d_ctx + (size_t)slot * ctx_field(h), ctx_field(h) * sizeof(float),
+  GC_HIP(h, hipMemcpyAsync(dst->d_feats, h->d_ctx + (size_t)slot * cond_len(h), cond_len(h) * sizeof(float),
                            hipMemcpyDeviceToDevice, dst->stream));
   GC_HIP(h, hipEventRecord(c.ev_r, dst->stream));
   c.read = true;
-  return from_peer(h, dst, gc_commit_cond(dst), "destination");
+  return relay(h, dst, gc_commit_cond(dst), "destination");
   });
 }
 
@@ -603,7 +566,7 @@ int gc_ctx_download(gc_handle* h, int32_t slot, float* out) {
   if (!c.saved) return fail(h, GC_ERR_STATE, "context slot " + std::to_string(slot) + " has not been saved");
   GC_HIP(h, hipSetDevice(h->device));
   GC_HIP(h, hipStreamWaitEvent(h->stream, c.ev_w, 0));
-  GC_HIP(h, hipMemcpyAsync(out, h->d_ctx + (size_t)slot * ctx_field(h), ctx_field(h) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  GC_HIP(h, hipMemcpyAsync(out, h->d_ctx + (size_t)slot * cond_len(h), cond_len(h) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   GC_HIP(h, hipStreamSynchronize(h->stream));        // (complete on return: no read event to leave behind)
   return GC_OK;
   });

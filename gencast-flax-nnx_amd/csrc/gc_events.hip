@@ -13,7 +13,7 @@
 // per point and threshold (k | o << 7, 255 = not counted: the exceedance-probability map), the table pass reads those
 // bytes and the weights.  Fusing them would need [T][W][2 (M + 1)] 64-bit bins per workgroup (268 KB at T = 4, W = 82,
 // M = 50), which no workgroup has.
-#include "gc_handle.h"
+#include "gc_store.h"
 
 namespace gc {
 
@@ -202,19 +202,8 @@ using namespace gci;
 
 namespace {
 
-size_t evt_field(const gc_handle* h) { return (size_t)h->hg.G * h->cfg.batch * h->cfg.c_out; }
-
 // words of one table [T][W][2][M + 1]
 size_t evt_table_len(const gc_handle* h, int T, int M) { return (size_t)T * h->cfg.batch * h->cfg.c_out * 2 * (M + 1); }
-
-// through the pinned staging buffer of the noise upload ([G, B, c_out] floats: at least `bytes`), as staged_upload
-int evt_staged_upload(gc_handle* h, void* dev, const void* src, size_t bytes) {
-  GC_HIP(h, hipEventSynchronize(h->ev_pin));
-  std::memcpy(h->pin_noise, src, bytes);
-  GC_HIP(h, hipMemcpyAsync(dev, h->pin_noise, bytes, hipMemcpyHostToDevice, h->stream));
-  GC_HIP(h, hipEventRecord(h->ev_pin, h->stream));
-  return GC_OK;
-}
 
 }  // namespace
 
@@ -234,28 +223,26 @@ int gc_ens_event_set(gc_handle* h, int32_t n_thresholds, const float* thresholds
   }
   GC_HIP(h, hipSetDevice(h->device));
   const int T = n_thresholds;
-  const size_t field = evt_field(h);
+  const size_t field = field_len(h);
   int rc;
   h->evt_scored = false;
   if (T != h->evt_T) {
-    GC_HIP(h, hipStreamSynchronize(h->stream));      // nothing reads the old buffers any more
-    free_allocs(&h->evt_allocs);
-    free_allocs(&h->evt_table_allocs);
+    GC_HIP(h, h->evt_allocs.drop(h->stream));        // nothing reads the old buffers any more
+    h->evt_table_allocs.free();
     h->evt_T = h->evt_table_T = h->evt_table_M = 0;
     if ((rc = dev_alloc(h, &h->d_evt_thr, (size_t)T * field, &h->evt_allocs)) ||
         (rc = dev_alloc(h, &h->d_evt_code, (size_t)T * field, &h->evt_allocs)) ||
         (rc = dev_alloc(h, &h->d_evt_wq, (size_t)h->hg.G, &h->evt_allocs))) {
-      free_allocs(&h->evt_allocs);
+      h->evt_allocs.free();
       return rc;
     }
-    for (hipEvent_t* e : {&h->ev_evt0, &h->ev_evt1})
-      if (!*e) GC_HIP(h, hipEventCreate(e));
+    GC_HIP(h, h->evt_time.ensure());
   }
   // on the handle's stream, behind whatever still reads the old values; the caller's arrays are free on return
   for (int t = 0; t < T; ++t)
-    if ((rc = evt_staged_upload(h, h->d_evt_thr + (size_t)t * field, thresholds + (size_t)t * field, field * sizeof(float))))
+    if ((rc = store_upload(h, h->d_evt_thr + (size_t)t * field, thresholds + (size_t)t * field, field * sizeof(float))))
       return rc;
-  if ((rc = evt_staged_upload(h, h->d_evt_wq, node_weight_q, (size_t)h->hg.G * sizeof(uint32_t)))) return rc;
+  if ((rc = store_upload(h, h->d_evt_wq, node_weight_q, (size_t)h->hg.G * sizeof(uint32_t)))) return rc;
   h->evt_dir_up = up;
   h->evt_T = T;
   return GC_OK;
@@ -269,23 +256,15 @@ int gc_ens_event_score(gc_handle* h, const float* truth, uint64_t* weighted, uin
   if (h->evt_T == 0) return fail(h, GC_ERR_STATE, "no thresholds (gc_ens_event_set)");
   if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
   if (!weighted) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  const int M = h->ens_members, T = h->evt_T;
-  for (int i = 0; i < M; ++i)
-    if (!h->ens_filled[(size_t)i]) return fail(h, GC_ERR_STATE, "member slot " + std::to_string(i) + " has not been pushed");
-  if (!truth && !h->has_ens_truth) return fail(h, GC_ERR_STATE, "no truth on the device (pass one to gc_ens_event_score)");
+  int rc = store_complete(h, h);
+  if (rc) return rc;
   GC_HIP(h, hipSetDevice(h->device));
+  if ((rc = take_truth(h, h, truth, "gc_ens_event_score"))) return rc;
   const gc_config& c = h->cfg;
-  const int G = h->hg.G, W = c.batch * c.c_out;
-  const size_t field = evt_field(h), len = evt_table_len(h, T, M);
-  int rc;
-  if (truth) {
-    if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
-    if ((rc = staged_upload(h, h->pin_noise, h->d_ens_truth, truth, field))) return rc;
-    h->has_ens_truth = true;
-  }
+  const int G = h->hg.G, W = c.batch * c.c_out, M = h->ens_members, T = h->evt_T;
+  const size_t field = field_len(h), len = evt_table_len(h, T, M);
   if (h->evt_table_T != T || h->evt_table_M != M) {   // sized by M: made again when M or T changed
-    GC_HIP(h, hipStreamSynchronize(h->stream));
-    free_allocs(&h->evt_table_allocs);
+    GC_HIP(h, h->evt_table_allocs.drop(h->stream));
     h->evt_table_T = h->evt_table_M = 0;
     if ((rc = dev_alloc(h, &h->d_evt_table, 2 * len + (size_t)T, &h->evt_table_allocs))) return rc;
     h->evt_table_T = T;
@@ -295,7 +274,7 @@ int gc_ens_event_score(gc_handle* h, const float* truth, uint64_t* weighted, uin
   unsigned long long* const d_w = h->d_evt_table;
   unsigned long long* const d_c = d_w + len;
   unsigned long long* const d_inv = d_c + len;
-  GC_HIP(h, hipEventRecord(h->ev_evt0, s));
+  GC_HIP(h, h->evt_time.begin(s));
   GC_HIP(h, hipMemsetAsync(d_w, 0, (2 * len + (size_t)T) * sizeof(unsigned long long), s));
   if ((rc = launch(h, gc::KC_PACK, [&] {
          return gc::launch_ens_event_code(s, h->d_ens, field, M, h->d_ens_truth, T, h->d_evt_thr, h->evt_dir_up, h->d_evt_code);
@@ -305,16 +284,14 @@ int gc_ens_event_score(gc_handle* h, const float* truth, uint64_t* weighted, uin
          return gc::launch_ens_event_table(s, h->d_evt_code, field, h->d_evt_wq, G, W, M, T, d_w, d_c, d_inv);
        })))
     return rc;
-  GC_HIP(h, hipEventRecord(h->ev_evt1, s));
+  GC_HIP(h, h->evt_time.end(s));
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the tables are copied out as they lie");
   std::vector<unsigned long long> inv((size_t)T);
   GC_HIP(h, hipMemcpyAsync(weighted, d_w, len * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   if (counts) GC_HIP(h, hipMemcpyAsync(counts, d_c, len * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   GC_HIP(h, hipMemcpyAsync(inv.data(), d_inv, inv.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   GC_HIP(h, hipStreamSynchronize(s));
-  float ms = 0.f;
-  GC_HIP(h, hipEventElapsedTime(&ms, h->ev_evt0, h->ev_evt1));
-  h->evt_device_us = (int64_t)(ms * 1000.0f);
+  GC_HIP(h, h->evt_time.microseconds(&h->evt_device_us));
   int64_t total = 0;
   for (int t = 0; t < T; ++t) {
     total += (int64_t)inv[(size_t)t];
@@ -336,7 +313,7 @@ int gc_ens_event_download(gc_handle* h, int32_t threshold, uint8_t* code) {
   if (threshold < 0 || threshold >= h->evt_T) return fail(h, GC_ERR_INVALID_ARGUMENT, "threshold outside [0, n_thresholds)");
   if (!h->evt_scored) return fail(h, GC_ERR_STATE, "no event codes on the device (gc_ens_event_score)");
   GC_HIP(h, hipSetDevice(h->device));
-  const size_t field = evt_field(h);
+  const size_t field = field_len(h);
   GC_HIP(h, hipMemcpyAsync(code, h->d_evt_code + (size_t)threshold * field, field, hipMemcpyDeviceToHost, h->stream));
   GC_HIP(h, hipStreamSynchronize(h->stream));
   return GC_OK;

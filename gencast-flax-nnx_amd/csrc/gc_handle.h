@@ -1,6 +1,18 @@
 // Internals shared by the host translation units of libgencast_hip.so: the handle, the device-side weight layout,
-// the route of a forward, and the allocation / launch helpers.  gc_weights.hip lays the weights out, gc_forward.hip
-// enqueues one denoiser forward, gc_sampler.hip the sampler and the loss around it, gc_api.hip is the C ABI (gc_ensemble.hip holds its gc_ens_* and gc_ctx_* entries, gc_spectrum.hip gc_spec_* and gc_ens_spectrum, gc_events.hip gc_ens_event_*, gc_derive.hip gc_ens_derive_*).
+// the route of a forward, and the allocation / launch helpers.
+//   gc_weights.hip   lays the weights out
+//   gc_forward.hip   enqueues one denoiser forward
+//   gc_sampler.hip   the sampler and the loss around it
+//   gc_api.hip       the C ABI, but for the entries of the four units below
+//   gc_ensemble.hip  gc_ens_* (the member store and its scores) and gc_ctx_*
+//   gc_spectrum.hip  gc_spec_* and gc_ens_spectrum
+//   gc_events.hip    gc_ens_event_*
+//   gc_derive.hip    gc_ens_derive_*
+// The last four are scorers over the member store of gc_ens_reserve.  What they share -- field length, upload through
+// the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
+// relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
+// are a BufferGroup and its events an Event or a Bracket (below); declaring one as a member of the handle is all it takes
+// for gc_destroy to release it and for the "device_allocations" counter to see it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,9 +93,56 @@ struct DevLayer {      // one transformer block
   int cond_attn = -1, cond_ffw = -1;
 };
 
+// Device buffers that are freed and replaced together.  A member of the handle enters the handle's list: gc_destroy
+// and the "device_allocations" counter walk that list.
+struct BufferGroup {
+  std::vector<void*> ptrs;
+  explicit BufferGroup(std::vector<BufferGroup*>& of_handle) { of_handle.push_back(this); }
+  BufferGroup(const BufferGroup&) = delete;
+  void free() {                          // (the caller knows that nothing on the device uses the buffers any more)
+    for (void* p : ptrs) (void)hipFree(p);
+    ptrs.clear();
+  }
+  hipError_t drop(hipStream_t s) {       // synchronise the stream that used them, free, forget
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) free();
+    return e;
+  }
+};
+
+// An event the handle owns: created on first use, destroyed by gc_destroy through the handle's list.
+struct Event {
+  hipEvent_t e = nullptr;
+  explicit Event(std::vector<Event*>& of_handle) { of_handle.push_back(this); }
+  Event(const Event&) = delete;
+  hipError_t ensure(bool timing = false) {
+    return e ? hipSuccess : timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming);
+  }
+};
+
+// The two timing events around the device work of a feature's last call.
+struct Bracket {
+  Event e0, e1;
+  explicit Bracket(std::vector<Event*>& of_handle) : e0(of_handle), e1(of_handle) {}
+  hipError_t ensure() {
+    const hipError_t e = e0.ensure(true);
+    return e != hipSuccess ? e : e1.ensure(true);
+  }
+  hipError_t begin(hipStream_t s) { return hipEventRecord(e0.e, s); }
+  hipError_t end(hipStream_t s) { return hipEventRecord(e1.e, s); }
+  hipError_t microseconds(int64_t* us) {           // (after the stream has been synchronised)
+    float ms = 0.f;
+    const hipError_t e = hipEventElapsedTime(&ms, e0.e, e1.e);
+    *us = (int64_t)(ms * 1000.0f);
+    return e;
+  }
+};
+
 }  // namespace gci
 
 struct gc_handle {
+  std::vector<gci::BufferGroup*> groups;     // every BufferGroup / Event member below, in declaration order
+  std::vector<gci::Event*> events;
   gc_config cfg{};
   int device = 0;
   hipStream_t stream = nullptr;
@@ -97,7 +156,7 @@ struct gc_handle {
   std::map<std::string, std::vector<float>> weights;  // host copies as loaded
   // device buffers by owner (all freed in destroy): made once per handle; by gc_finalize, freed by the next one
   // (free_weights); by build_embed_cache, freed by the next one
-  std::vector<void*> allocs, weight_allocs, cache_allocs;
+  gci::BufferGroup allocs{groups}, weight_allocs{groups}, cache_allocs{groups};
 
   // graph (device)
   int *d_g2m_snd = nullptr, *d_g2m_rcv = nullptr, *d_m2g_snd = nullptr, *d_m2g_rcv = nullptr;
@@ -204,7 +263,7 @@ struct gc_handle {
   int64_t loss_evaluations = 0, loss_device_us = 0;
 
   // ensemble verification (gc_ens_*, gc_ensemble.hip): a store of M member fields and the sums scored from it
-  std::vector<void*> ens_allocs;                 // everything sized by M: freed and replaced by gc_ens_reserve
+  gci::BufferGroup ens_allocs{groups};               // everything sized by M: freed and replaced by gc_ens_reserve
   int ens_members = 0;                           // M (0: nothing reserved)
   std::vector<char> ens_filled;                  // per slot: pushed since the last gc_ens_reserve
   float* d_ens = nullptr;                        // [M][G, B, c_out] member fields
@@ -215,8 +274,8 @@ struct gc_handle {
   float *d_ens_w = nullptr, *d_ens_truth = nullptr;            // [G], [G, B, c_out]: made once, kept across reserves
   float *d_ens_mean = nullptr, *d_ens_var = nullptr;           // [G, B, c_out] each: made by the first call that asks for fields
   bool has_ens_w = false, has_ens_truth = false, has_ens_fields = false;
-  hipEvent_t ev_ens_free = nullptr, ev_ens_done = nullptr;     // stream order of a push from another handle
-  hipEvent_t ev_ens0 = nullptr, ev_ens1 = nullptr;             // brackets of the last scoring call
+  gci::Event ev_ens_free{events}, ev_ens_done{events};         // stream order of a push from another handle
+  gci::Bracket ens_time{events};                               // of the last scoring call
   int64_t ens_scores = 0, ens_score_device_us = 0, ens_invalid_points = 0;
   // member STATES (gc_ens_push_state): output channel j of a member comes from conditioning channel ens_state_src[j]
   // (-1: from the sample); the device copy is uploaded again only when the table changes
@@ -224,7 +283,7 @@ struct gc_handle {
   int* d_ens_state_src = nullptr;                // [c_out], made once
 
   // context store (gc_ctx_*, gc_ensemble.hip): n conditioning arrays beside the member store, one per ensemble member
-  std::vector<void*> ctx_allocs;                 // the store: freed and replaced by gc_ctx_reserve
+  gci::BufferGroup ctx_allocs{groups};               // the store: freed and replaced by gc_ctx_reserve
   int ctx_slots = 0;                             // n (0: nothing reserved)
   float* d_ctx = nullptr;                        // [n][G, B, c_in]
   struct CtxSlot {
@@ -235,8 +294,8 @@ struct gc_handle {
   std::vector<CtxSlot> ctx;                      // (events are kept across reserves and destroyed with the handle)
 
   // spherical-harmonic power spectra (gc_spec_*, gc_ens_spectrum, gc_spectrum.hip)
-  std::vector<void*> spec_allocs;                // sized by the tables: freed and replaced by gc_spec_set_tables
-  std::vector<void*> spec_work_allocs;           // sized by the coefficient sets a call keeps: replaced when a call needs more
+  gci::BufferGroup spec_allocs{groups};           // sized by the tables: freed and replaced by gc_spec_set_tables
+  gci::BufferGroup spec_work_allocs{groups};      // sized by the coefficient sets a call keeps: replaced when a call needs more
   int sp_L = 0, sp_lat = 0, sp_lon = 0;          // lmax (0: no tables), n_lat, n_lon
   int sp_sets = 0;                               // coefficient sets d_sp_coef holds
   float *d_sp_q = nullptr, *d_sp_tab = nullptr;  // [L m][L l][n_lat] Legendre analysis, [2 L][n_lon] cosine rows then sine rows
@@ -245,12 +304,12 @@ struct gc_handle {
   double* d_sp_coef = nullptr;                   // [sp_sets][2][L m][L l][B c_out]
   double* d_sp_out = nullptr;                    // [6 + sp_sets][B c_out][L]: the sums, then the member powers
   unsigned* d_sp_flags = nullptr;                // [B c_out]: a value of the column was not finite
-  hipEvent_t ev_sp0 = nullptr, ev_sp1 = nullptr; // brackets of the last spectrum call
+  gci::Bracket spec_time{events};                // of the last spectrum call
   int64_t spec_calls = 0, spec_device_us = 0, spec_invalid_columns = 0;
 
   // ensemble event verification (gc_ens_event_*, gc_events.hip): threshold fields and the tables scored from the member store
-  std::vector<void*> evt_allocs;                 // sized by T: thresholds, codes, weights; kept across gc_ens_reserve
-  std::vector<void*> evt_table_allocs;           // sized by T and M: made again by the scoring call that finds either changed
+  gci::BufferGroup evt_allocs{groups};            // sized by T: thresholds, codes, weights; kept across gc_ens_reserve
+  gci::BufferGroup evt_table_allocs{groups};      // sized by T and M: made again by the scoring call that finds either changed
   int evt_T = 0;                                 // thresholds set (0: none)
   unsigned evt_dir_up = 0;                       // bit t: the event of threshold t is `value > thr`
   int evt_table_T = 0, evt_table_M = 0;          // what d_evt_table is sized for
@@ -259,20 +318,20 @@ struct gc_handle {
   unsigned* d_evt_wq = nullptr;                  // [G] integer node weights
   unsigned long long* d_evt_table = nullptr;     // weighted [T][B c_out][2][M + 1], counts (same), invalid [T]
   bool evt_scored = false;                       // a scoring call ran since gc_ens_event_set / gc_ens_reserve
-  hipEvent_t ev_evt0 = nullptr, ev_evt1 = nullptr;   // brackets of the last scoring call
+  gci::Bracket evt_time{events};                 // of the last scoring call
   int64_t evt_calls = 0, evt_device_us = 0, evt_invalid_points = 0;
 
   // derived and pooled ensemble fields (gc_ens_derive_*, gc_derive.hip): the plan, and the intermediate of the pooling passes
-  std::vector<void*> drv_allocs;                 // the plan's tables, one buffer: freed and replaced by gc_ens_derive_set
-  std::vector<void*> drv_work_allocs;            // the intermediate: made again by the call that finds its size changed
+  gci::BufferGroup drv_allocs{groups};            // the plan's tables, one buffer: freed and replaced by gc_ens_derive_set
+  gci::BufferGroup drv_work_allocs{groups};       // the intermediate: made again by the call that finds its size changed
   bool drv_set = false;                          // a plan has been set
   int drv_c_src = 0, drv_pool = 0, drv_n_lat = 0, drv_n_lon = 0, drv_r_lat = 0;
   double *d_drv_affine = nullptr, *d_drv_roww = nullptr;       // [c_out][4] (sa, la, sb, lb), [n_lat]
   int *d_drv_op = nullptr, *d_drv_a = nullptr, *d_drv_b = nullptr, *d_drv_rlon = nullptr;   // [c_out] x 3, [n_lat]
   unsigned char* d_drv_work = nullptr;           // 8 fields of row-pooled values: a float (max, min), or a double and an int32 (mean), per point
   size_t drv_work_bytes = 0;
-  hipEvent_t ev_drv0 = nullptr, ev_drv1 = nullptr;             // brackets of the last call
-  hipEvent_t ev_drv_src = nullptr;                             // stream order behind the source handle
+  gci::Bracket drv_time{events};                               // of the last call
+  gci::Event ev_drv_src{events};                               // stream order behind the source handle
   int64_t drv_calls = 0, drv_device_us = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
@@ -352,25 +411,20 @@ inline int fail(gc_handle* h, int code, const std::string& msg) {
 
 // owner: the list that frees the buffer (default h->allocs: freed in destroy)
 template <typename T>
-int dev_alloc(gc_handle* h, T** p, size_t count, std::vector<void*>* owner = nullptr) {
+int dev_alloc(gc_handle* h, T** p, size_t count, BufferGroup* owner = nullptr) {
   void* q = nullptr;
   GC_HIP(h, hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-  (owner ? owner : &h->allocs)->push_back(q);
+  (owner ? owner : &h->allocs)->ptrs.push_back(q);
   *p = reinterpret_cast<T*>(q);
   return GC_OK;
 }
 
 template <typename T>
-int dev_upload(gc_handle* h, T** p, const std::vector<T>& v, std::vector<void*>* owner = nullptr) {
+int dev_upload(gc_handle* h, T** p, const std::vector<T>& v, BufferGroup* owner = nullptr) {
   int rc = dev_alloc(h, p, v.size(), owner);
   if (rc) return rc;
   if (!v.empty()) GC_HIP(h, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return GC_OK;
-}
-
-inline void free_allocs(std::vector<void*>* owner) {
-  for (void* p : *owner) (void)hipFree(p);
-  owner->clear();
 }
 
 // ---- launch wrapper with optional per-class event bracketing --------------------------------
@@ -395,13 +449,23 @@ int launch(gc_handle* h, int cls, F&& f) {
 // what gc_last_error(nullptr) returns: the failure of an entry point that has no handle yet (gc_create)
 inline thread_local std::string g_create_error;
 
-// Asynchronous H2D through a handle-owned pinned buffer: the caller's buffer is free on return.
-inline int staged_upload(gc_handle* h, float* pinned, float* dev, const float* src, size_t count) {
-  GC_HIP(h, hipEventSynchronize(h->ev_pin));       // the previous copy out of a staging buffer is done
-  std::memcpy(pinned, src, count * sizeof(float));
-  GC_HIP(h, hipMemcpyAsync(dev, pinned, count * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  GC_HIP(h, hipEventRecord(h->ev_pin, h->stream));
+// Asynchronous H2D through a handle-owned pinned buffer of `cap` bytes, in pieces where the payload is longer: the
+// caller's buffer is free on return.
+inline int staged_upload_bytes(gc_handle* h, void* pinned, size_t cap, void* dev, const void* src, size_t bytes) {
+  size_t off = 0;
+  do {
+    const size_t n = std::min(cap, bytes - off);
+    GC_HIP(h, hipEventSynchronize(h->ev_pin));     // the previous copy out of a staging buffer is done
+    std::memcpy(pinned, static_cast<const char*>(src) + off, n);
+    GC_HIP(h, hipMemcpyAsync(static_cast<char*>(dev) + off, pinned, n, hipMemcpyHostToDevice, h->stream));
+    GC_HIP(h, hipEventRecord(h->ev_pin, h->stream));
+    off += n;
+  } while (off < bytes);
   return GC_OK;
+}
+// `count` floats that fit the buffer
+inline int staged_upload(gc_handle* h, float* pinned, float* dev, const float* src, size_t count) {
+  return staged_upload_bytes(h, pinned, count * sizeof(float), dev, src, count * sizeof(float));
 }
 
 // No C++ exception crosses the C ABI: every entry point runs inside this wrapper.

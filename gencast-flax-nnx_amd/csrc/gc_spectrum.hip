@@ -13,7 +13,7 @@
 // atomics are integer ORs into the per-column "not finite" flags, which commute.  Both products run on the vector ALUs
 // (as gc_noise_* do): a wave keeps 16 output rows of one 64-column group in registers, its table values are
 // wave-uniform and come through the scalar cache.
-#include "gc_handle.h"
+#include "gc_store.h"
 
 namespace gc {
 
@@ -201,7 +201,6 @@ using namespace gci;
 
 namespace {
 
-size_t spec_field_len(const gc_handle* h) { return (size_t)h->hg.G * h->cfg.batch * h->cfg.c_out; }
 size_t spec_set_len(const gc_handle* h) { return (size_t)2 * h->sp_L * h->sp_L * h->cfg.batch * h->cfg.c_out; }
 
 int spec_ready(gc_handle* h) {
@@ -213,14 +212,13 @@ int spec_ready(gc_handle* h) {
 // The buffers sized by the number of coefficient sets a call keeps: made again when a call needs more than there are.
 int spec_reserve_sets(gc_handle* h, int sets) {
   if (sets <= h->sp_sets) return GC_OK;
-  GC_HIP(h, hipStreamSynchronize(h->stream));
-  free_allocs(&h->spec_work_allocs);
+  GC_HIP(h, h->spec_work_allocs.drop(h->stream));
   h->sp_sets = 0;
   const size_t out = (size_t)h->cfg.batch * h->cfg.c_out * h->sp_L;
   int rc;
   if ((rc = dev_alloc(h, &h->d_sp_coef, (size_t)sets * spec_set_len(h), &h->spec_work_allocs)) ||
       (rc = dev_alloc(h, &h->d_sp_out, (size_t)(6 + sets) * out, &h->spec_work_allocs))) {
-    free_allocs(&h->spec_work_allocs);
+    h->spec_work_allocs.free();
     return rc;
   }
   h->sp_sets = sets;
@@ -228,9 +226,7 @@ int spec_reserve_sets(gc_handle* h, int sets) {
 }
 
 int spec_finish(gc_handle* h, const std::vector<unsigned>& flags) {
-  float ms = 0.f;
-  GC_HIP(h, hipEventElapsedTime(&ms, h->ev_sp0, h->ev_sp1));
-  h->spec_device_us = (int64_t)(ms * 1000.0f);
+  GC_HIP(h, h->spec_time.microseconds(&h->spec_device_us));
   int64_t bad = 0;
   for (unsigned f : flags) bad += f ? 1 : 0;
   h->spec_invalid_columns = bad;
@@ -254,9 +250,8 @@ int gc_spec_set_tables(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t lmax,
   const int N = h->cfg.batch * h->cfg.c_out;
   if (!gc::spec_grid_ok(lmax, n_lat, N)) return fail(h, GC_ERR_UNSUPPORTED, "grid too large for the spectrum kernels");
   GC_HIP(h, hipSetDevice(h->device));
-  GC_HIP(h, hipStreamSynchronize(h->stream));      // nothing reads the old tables any more
-  free_allocs(&h->spec_allocs);
-  free_allocs(&h->spec_work_allocs);
+  GC_HIP(h, h->spec_allocs.drop(h->stream));       // nothing reads the old tables any more
+  h->spec_work_allocs.free();
   h->sp_L = h->sp_sets = 0;
   const size_t L = (size_t)lmax;
   std::vector<float> tab(2 * L * n_lon);
@@ -266,13 +261,12 @@ int gc_spec_set_tables(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t lmax,
   if ((rc = dev_upload(h, &h->d_sp_q, std::vector<float>(legendre_analysis, legendre_analysis + L * L * n_lat), &h->spec_allocs)) ||
       (rc = dev_upload(h, &h->d_sp_tab, tab, &h->spec_allocs)) ||
       (rc = dev_alloc(h, &h->d_sp_F, 2 * L * n_lat * N, &h->spec_allocs)) ||
-      (rc = dev_alloc(h, &h->d_sp_field, spec_field_len(h), &h->spec_allocs)) ||
+      (rc = dev_alloc(h, &h->d_sp_field, field_len(h), &h->spec_allocs)) ||
       (rc = dev_alloc(h, &h->d_sp_flags, (size_t)N, &h->spec_allocs))) {
-    free_allocs(&h->spec_allocs);
+    h->spec_allocs.free();
     return rc;
   }
-  for (hipEvent_t* e : {&h->ev_sp0, &h->ev_sp1})
-    if (!*e) GC_HIP(h, hipEventCreate(e));
+  GC_HIP(h, h->spec_time.ensure());
   h->sp_L = lmax; h->sp_lat = n_lat; h->sp_lon = n_lon;
   return GC_OK;
   });
@@ -288,11 +282,11 @@ int gc_spec_field(gc_handle* h, const float* field, double* power) {
   GC_HIP(h, hipSetDevice(h->device));
   if (!field && (rc = resolve_guard(h))) return rc;   // the spectrum is of the CHECKED sample (exact-f32 re-run included)
   if ((rc = spec_reserve_sets(h, 1))) return rc;
-  if (field && (rc = staged_upload(h, h->pin_noise, h->d_sp_field, field, spec_field_len(h)))) return rc;
+  if (field && (rc = staged_upload(h, h->pin_noise, h->d_sp_field, field, field_len(h)))) return rc;
   const int L = h->sp_L, N = h->cfg.batch * h->cfg.c_out;
   hipStream_t s = h->stream;
   const float* src = field ? h->d_sp_field : h->d_sx;
-  GC_HIP(h, hipEventRecord(h->ev_sp0, s));
+  GC_HIP(h, h->spec_time.begin(s));
   GC_HIP(h, hipMemsetAsync(h->d_sp_flags, 0, (size_t)N * sizeof(unsigned), s));
   if ((rc = launch(h, gc::KC_PACK, [&] {
          return gc::launch_spec_analysis(s, src, h->d_sp_tab, h->d_sp_q, L, h->sp_lat, h->sp_lon, N, h->d_sp_F, h->d_sp_coef,
@@ -301,7 +295,7 @@ int gc_spec_field(gc_handle* h, const float* field, double* power) {
     return rc;
   if ((rc = launch(h, gc::KC_PACK, [&] { return gc::launch_spec_power(s, h->d_sp_coef, h->d_sp_flags, L, N, h->d_sp_out); })))
     return rc;
-  GC_HIP(h, hipEventRecord(h->ev_sp1, s));
+  GC_HIP(h, h->spec_time.end(s));
   std::vector<unsigned> flags((size_t)N);
   GC_HIP(h, hipMemcpyAsync(power, h->d_sp_out, (size_t)N * L * sizeof(double), hipMemcpyDeviceToHost, s));
   GC_HIP(h, hipMemcpyAsync(flags.data(), h->d_sp_flags, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
@@ -317,24 +311,18 @@ int gc_ens_spectrum(gc_handle* h, const float* truth, double* sums, double* memb
   if (rc) return rc;
   if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
   if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  const int M = h->ens_members;
-  for (int i = 0; i < M; ++i)
-    if (!h->ens_filled[(size_t)i]) return fail(h, GC_ERR_STATE, "member slot " + std::to_string(i) + " has not been pushed");
-  if (!truth && !h->has_ens_truth) return fail(h, GC_ERR_STATE, "no truth on the device (pass one to gc_ens_spectrum)");
+  if ((rc = store_complete(h, h))) return rc;
   GC_HIP(h, hipSetDevice(h->device));
-  const size_t field = spec_field_len(h), set = spec_set_len(h);
-  if (truth) {
-    if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
-    if ((rc = staged_upload(h, h->pin_noise, h->d_ens_truth, truth, field))) return rc;
-    h->has_ens_truth = true;
-  }
+  if ((rc = take_truth(h, h, truth, "gc_ens_spectrum"))) return rc;
+  const int M = h->ens_members;
+  const size_t field = field_len(h), set = spec_set_len(h);
   if ((rc = spec_reserve_sets(h, M + 2))) return rc;
   const int L = h->sp_L, N = h->cfg.batch * h->cfg.c_out;
   const size_t plane = (size_t)N * L;
   hipStream_t s = h->stream;
   double* const d_sums = h->d_sp_out;
   double* const d_mp = h->d_sp_out + 6 * plane;
-  GC_HIP(h, hipEventRecord(h->ev_sp0, s));
+  GC_HIP(h, h->spec_time.begin(s));
   GC_HIP(h, hipMemsetAsync(h->d_sp_flags, 0, (size_t)N * sizeof(unsigned), s));
   // one field at a time through the Fourier scratch; set 0 = truth, 1 + i = member i, M + 1 = the mean coefficients
   for (int k = 0; k <= M; ++k) {
@@ -349,7 +337,7 @@ int gc_ens_spectrum(gc_handle* h, const float* truth, double* sums, double* memb
          return gc::launch_spec_ens(s, h->d_sp_coef, set, M, h->d_sp_flags, L, N, d_sums, member_power ? d_mp : nullptr);
        })))
     return rc;
-  GC_HIP(h, hipEventRecord(h->ev_sp1, s));
+  GC_HIP(h, h->spec_time.end(s));
   std::vector<unsigned> flags((size_t)N);
   GC_HIP(h, hipMemcpyAsync(sums, d_sums, 6 * plane * sizeof(double), hipMemcpyDeviceToHost, s));
   if (member_power) GC_HIP(h, hipMemcpyAsync(member_power, d_mp, (size_t)M * plane * sizeof(double), hipMemcpyDeviceToHost, s));

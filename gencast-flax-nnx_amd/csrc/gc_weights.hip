@@ -200,7 +200,7 @@ struct CondPacker {
 // family runs on the weight-streaming kernels (wf32) -- WF32 with K zero-padded to kf (a multiple of 64: the ring walks
 // 4 k16 steps).  The only caller of the encoders besides build_embed_cache.
 int upload_weight(gc_handle* h, const std::vector<float>& m, int n, int k, int kf, bool wf32, Weight* w) {
-  std::vector<void*>* own = &h->weight_allocs;
+  BufferGroup* own = &h->weight_allocs;
   *w = Weight{};
   w->ld = k; w->kf = kf;
   int rc;
@@ -271,8 +271,8 @@ int build_embed_cache(gc_handle* h) {
   const auto& k1 = h->weights.at(p);                          // [node_in][L]
   int rc;
   drop_sample_graphs(h);                                      // captured samples bake these images' addresses
-  free_allocs(&h->cache_allocs);                              // (callers have synchronised the stream)
-  std::vector<void*>* own = &h->cache_allocs;
+  h->cache_allocs.free();                                     // (callers have synchronised the stream)
+  BufferGroup* own = &h->cache_allocs;
   auto wst = transpose_pad(k1, node_in, L, 0, node_in, kp, L);   // [L][kp]
   for (int o = 0; o < L; ++o)
     for (int cc = 0; cc < c.c_out; ++cc) wst[(size_t)o * kp + 3 + h->h_slots[cc]] = 0.f;
@@ -301,7 +301,7 @@ int build_embed_cache(gc_handle* h) {
 
 // Frees what finalize_weights allocated (the stream is idle and no captured sample is left: gc_finalize, destroy).
 void free_weights(gc_handle* h) {
-  free_allocs(&h->weight_allocs);
+  h->weight_allocs.free();
   h->finalized = h->finalized_weights = h->embed_cache_ready = false;
   h->cond_cur = nullptr;                        // (it may point into the d_cond just freed)
 }
@@ -311,7 +311,7 @@ int finalize_weights(gc_handle* h) {
   const gc_config& c = h->cfg;
   const int L = c.latent_size, D = c.d_model, F = c.ffw_hidden;
   const std::string g = P_G2M, m = P_M2G, t = P_TR, nz = P_NOISE;
-  std::vector<void*>* own = &h->weight_allocs;
+  BufferGroup* own = &h->weight_allocs;
   CondPacker cp;
   int rc;
   const int node_in = 3 + c.c_in;

@@ -156,10 +156,16 @@ class EnsembleSampler:
         lane.set_noisy_slots(slots)
         lane.upload_cond_dev(ptr)                          # device-to-device, on the lane's own stream
     scoring = score_fields is not None
+    main = None                                            # lane 0's member store, where anything is scored at all
     if scoring or spectral or events is not None or derived is not None:
-      native.ens_reserve(num_members)
-    if scoring:
-      native.ens_set_node_weight(verification.node_weights(template))
+      dspec, dev = derived if derived is not None else (None, None)
+      weights = None if spectral and not scoring else verification.node_weights(template)
+      wq = None if events is None and dev is None else verification.quantize_node_weights(weights)
+      # (scored once: the thresholds are set by that call, after the members are in)
+      main = verification.ScoredStore(native, num_members, weights if scoring else None, events=events,
+                                      thresholds=None if events is None else events.packed(template), weight_q=wq,
+                                      set_per_score=True)
+      main.setup()
     if spectral:
       _spectra.ensure_tables(native, template, lmax)
     out = []
@@ -169,39 +175,27 @@ class EnsembleSampler:
         lane.upload_noise(self.member_noise(m, shape, template))
         lane.sample_resident(sigmas, skip_dead_call=True, want_stats=False)
       for lane, m in zip(lanes, group):
-        if scoring or spectral or events is not None or derived is not None:
+        if main is not None:
           native.ens_push(m, src=lane)
         else:
           out.append((m, datasets.like_inputs(Denoiser.unpack_outputs(lane.download_sample(), grid_shape, template),
                                               targets_template, inputs, forcings)))
-    if not scoring and not spectral and events is None and derived is None:
+    if main is None:
       return out
     truth = np.transpose(datasets.dataset_to_stacked(template, template.sizes), (1, 2, 0, 3)).reshape(shape)
     if derived is not None:
-      dspec, dev = derived
       plan = dspec.plan(template)
-      view = self._denoiser.view_handle(len(plan["op"]))
-      view.ens_derive_set(**plan)
-      view.ens_reserve(num_members)
-      view.ens_set_node_weight(verification.node_weights(template))
-      view.ens_derive(native, truth)
-      sums, hist = view.ens_score(None)
-      scores = verification.EnsembleScores(sums, hist, num_members)
-      if dev is None:
-        return scores
-      wq, scale = verification.quantize_node_weights(verification.node_weights(template))
-      view.ens_event_set(dev.packed(dspec.template(template)), dev.directions, wq)
-      weighted, counts, invalid = view.ens_event_score(None)
-      return scores, verification.EventScores(weighted, counts, num_members, dev.directions, scale, invalid)
+      view = verification.ScoredStore(self._denoiser.view_handle(len(plan["op"])), num_members, weights, events=dev,
+                                      thresholds=None if dev is None else dev.packed(dspec.template(template)), weight_q=wq,
+                                      plan=plan, source=native, set_per_score=True)
+      view.setup()
+      scores, event_scores = view.score(truth)
+      return scores if dev is None else (scores, event_scores)
     if events is not None:
-      wq, scale = verification.quantize_node_weights(verification.node_weights(template))
-      native.ens_event_set(events.packed(template), events.directions, wq)
-      weighted, counts, invalid = native.ens_event_score(truth)
-      return verification.EventScores(weighted, counts, num_members, events.directions, scale, invalid)
+      return main.score_events(truth)
     if not scoring:
       return _spectra.EnsembleSpectra(native.ens_spectrum(truth), num_members)
-    sums, hist = native.ens_score(truth, want_fields=score_fields)
-    result = (verification.EnsembleScores(sums, hist, num_members),)
+    result = (main.score(truth, want_fields=score_fields)[0],)
     if score_fields:
       given = (targets_template, inputs, forcings)
       result += tuple(datasets.like_inputs(Denoiser.unpack_outputs(f, grid_shape, template), *given)

@@ -18,6 +18,7 @@ Three layers, each mirroring the reference at the array level:
 """
 from __future__ import annotations
 
+import time as _time
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -406,6 +407,14 @@ def build_rollout_plan(inputs: Dataset, forcings: Dataset, template: Dataset, ta
   return dict(kind=kind, src=src, sidx=sidx, a=a, b=b, n_forcing=nf), forcing_cols
 
 
+def _on_time_axis(parts: Sequence[Dataset], given, horizon: int):
+  """`parts` joined on the targets' time axis, like the harness's xr.concat; `given` = (targets, inputs, forcings) as passed."""
+  out = concat_time(parts)
+  if datasets.is_xarray(given[0]):
+    return datasets.to_xarray(out, given[0].isel(time=slice(0, horizon)))
+  return datasets.like_inputs(out, None, *given[1:])
+
+
 class DeviceRollout:
   """AR rollout with the conditioning resident in HBM (one `gc_rollout_advance` per step)."""
 
@@ -432,7 +441,6 @@ class DeviceRollout:
   def run(self, inputs: Dataset, targets: Dataset, forcings: Dataset, horizon: int, *,
           context_steps: int = 2, init_noise: Optional[Sequence[np.ndarray]] = None, rngs=0):
     """Returns the predictions (physical units, time = horizon) like `autoregressive_rollout`."""
-    import time as _time
     given = (targets, inputs, forcings)
     inputs, targets, forcings = (datasets.as_dataset(x) for x in (inputs, targets, forcings))
     context = isel_time(inputs, slice(-context_steps, None))
@@ -516,10 +524,7 @@ class DeviceRollout:
       pending = k
       self.last_step_ms.append(1e3 * (_time.perf_counter() - t0))
     finish(pending, native.download_stash())
-    out = concat_time(preds)
-    if datasets.is_xarray(given[0]):                        # predictions on the targets' time axis, like the harness's xr.concat
-      return datasets.to_xarray(out, given[0].isel(time=slice(0, horizon)))
-    return datasets.like_inputs(out, None, *given[1:])
+    return _on_time_axis(preds, given, horizon)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -643,6 +648,30 @@ class EnsembleRolloutResult:
                                  events=both(verification.EventScores, self.events, other.events), derived=derived)
 
 
+class _DerivedView:
+  """One entry of `EnsembleRollout.run(derived=...)`: its store (`verification.ScoredStore`), the scale and the template of
+  its channels, and what the lead times have yielded so far."""
+
+  def __init__(self, store, scale, template, keep_members: bool):
+    self.store, self.scale, self.template = store, scale, template
+    self.scores, self.raw = [], []
+    self.events = None if store.events is None else []
+    self.members = [] if keep_members else None
+
+  def result(self) -> DerivedRolloutResult:
+    return DerivedRolloutResult(self.scores, self.raw, self.events, self.members, self.template)
+
+
+class _EnsembleRun:
+  """The state of one `EnsembleRollout.run`: what `_setup` made (handles, plan, noise sources, the main store and the
+  derived views) and the per-lead results `_score_lead` appends."""
+
+  def __init__(self):
+    self.scores, self.raw_scores, self.means, self.variances = [], [], [], []
+    self.thresholds = None                                # per EventSpec, in the members' units
+    self.views: Dict[str, _DerivedView] = {}
+
+
 class EnsembleRollout:
   """M members rolled out `horizon` steps with every member's conditioning resident in HBM, scored at every lead time
   on the device.  What is scored is each member's STATE -- the channels of its advanced context
@@ -716,8 +745,6 @@ class EnsembleRollout:
 
     After the last step the context is advanced once more to form the state; see `next_forcings` for the forcing frame
     that update takes."""
-    import time as _time
-    from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
     if self.world_size > 1:
       raise ValueError("EnsembleRollout needs all members on one rank (world_size == 1): bring the other "
                        "ranks' members over and push them with NativeDenoiser.ens_push_host")
@@ -728,6 +755,24 @@ class EnsembleRollout:
       raise ValueError(f"targets carry {targets.sizes.get('time', 0)} time steps (need horizon = {horizon})")
     if init_noise is not None and (len(init_noise) != M or any(len(z) < horizon for z in init_noise)):
       raise ValueError("init_noise must be [num_members][horizon] fields")
+    run = self._setup(inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields,
+                      keep_members, events, derived)
+    self.last_lead_ms = []
+    for k in range(horizon):
+      t0 = _time.perf_counter()
+      self._sample_lead(run, k, forcings, horizon)
+      self._score_lead(run, k, targets)
+      self.last_lead_ms.append(1e3 * (_time.perf_counter() - t0))
+    return EnsembleRolloutResult(run.scores, run.spectra, _on_time_axis(run.means, given, horizon) if fields else None,
+                                 _on_time_axis(run.variances, given, horizon) if fields else None, run.members, M,
+                                 scores_normalized=run.raw_scores, spectra_normalized=run.raw_spectra, events=run.events,
+                                 derived=None if derived is None else {k: v.result() for k, v in run.views.items()})
+
+  def _setup(self, inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields, keep_members,
+             events, derived) -> "_EnsembleRun":
+    """Everything `run` does before the first sample: lanes, context store, the main store and the derived views."""
+    from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
+    run = _EnsembleRun()
     context = isel_time(inputs, slice(-context_steps, None))
     template0 = isel_time(targets, slice(0, 1)).map(np.zeros_like)
     forc0 = isel_time(forcings, slice(0, 1))
@@ -739,37 +784,54 @@ class EnsembleRollout:
       n_fo = normalize(forc0, norm._scales, norm._locations)
     else:
       n_in, n_fo = context, forc0
-    cond, grid_shape, slots = den.init_for(n_in, template0, n_fo)
+    cond, run.grid_shape, slots = den.init_for(n_in, template0, n_fo)
     native = den.native
-    plan, forcing_cols = build_rollout_plan(context, forc0, template0, self.task, norm)
-    state_src = state_channels(plan, den.dims.c_out)
+    run.plan, run.forcing_cols = build_rollout_plan(context, forc0, template0, self.task, norm)
+    run.state_src = state_channels(run.plan, den.dims.c_out)
     lanes = [native]
     n_lanes = min(self.concurrent_members, M)
     if n_lanes > 1:
       lanes += list(den.member_lanes(n_lanes - 1))
     for lane in lanes:
       lane.set_noisy_slots(slots)
-      lane.rollout_plan(**plan)
+      lane.rollout_plan(**run.plan)
     native.upload_cond(cond)
     native.ctx_reserve(M)
     for m in range(M):                                    # every member starts from the initial conditioning
       native.ctx_save(m)
-    native.ens_reserve(M)
-    native.ens_set_node_weight(verification.node_weights(template0))
+    scale = self._stat(None if norm is None else norm._scales, template0, 1.0)
+    loc = self._stat(None if norm is None else norm._locations, template0, 0.0)
+
+    def packed(spec, template, s, l):
+      """The thresholds in the members' units: the map of the truth, (thr - l) / s in float64, rounded once."""
+      thr = spec.packed(template)
+      return thr if norm is None else ((thr.astype(np.float64) - l) / s).astype(np.float32)
+
+    entries = {name: entry if isinstance(entry, (tuple, list)) else (entry, None) for name, entry in (derived or {}).items()}
+    weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
+    wq = None
+    if events is not None or any(dev is not None for _, dev in entries.values()):
+      wq = verification.quantize_node_weights(weights)
+    specs = None
+    if events is not None:
+      specs = list(events) if isinstance(events, (list, tuple)) else [events]
+      if len(specs) not in (1, horizon) or any(s.directions != specs[0].directions for s in specs):
+        raise ValueError(f"events must be one EventSpec or {horizon} of them with equal directions")
+      run.thresholds = [packed(s, template0, scale, loc) for s in specs]
+    # one spec: uploaded once, it survives the store and every lead time; else the one of the lead, before it is scored
+    run.main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
+                                        thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
+                                        set_per_score=specs is not None and len(specs) > 1)
+    run.main.reserve()
     if spectra:
       _spectra.ensure_tables(native, template0, lmax)
-    event_specs = None
-    if events is not None:
-      event_specs = list(events) if isinstance(events, (list, tuple)) else [events]
-      if len(event_specs) not in (1, horizon) or any(s.directions != event_specs[0].directions for s in event_specs):
-        raise ValueError(f"events must be one EventSpec or {horizon} of them with equal directions")
-      wq, wq_scale = verification.quantize_node_weights(verification.node_weights(template0))
 
-    given_noise = init_noise is not None
-    noise = [self.member_noise(m, given=given_noise) for m in range(M)]
+    run.given_noise = init_noise is not None
+    run.init_noise = init_noise
+    run.noise = [self.member_noise(m, given=run.given_noise) for m in range(M)]
     churn = bool(getattr(sampler, "_stochastic_churn", False))
-    on_device = self.device_noise and not given_noise
-    if on_device or churn:
+    run.on_device = self.device_noise and not run.given_noise
+    if run.on_device or churn:
       sampler.ensure_device_noise(native, template0)
       key = (len(template0.coords["lat"]), len(template0.coords["lon"]))
       for lane in lanes[1:]:                              # (the sampler remembers lane 0 only)
@@ -780,128 +842,94 @@ class EnsembleRollout:
       lane.set_churn(sampler._per_step_churn_rates if churn else None,  # pylint: disable=protected-access
                      getattr(sampler, "_noise_level_inflation_factor", 1.0))
 
-    sigmas = np.asarray(sampler.noise_levels, np.float32)
-    shape = (cond.shape[0], cond.shape[1], den.dims.c_out)
-    sizes = dict(forc0.sizes)
-    sizes.update(context.sizes)
-    rows_of = DeviceRollout(self.model, norm, self.task)._forcing_rows  # pylint: disable=protected-access
-    scale = self._stat(None if norm is None else norm._scales, template0, 1.0)
-    loc = self._stat(None if norm is None else norm._locations, template0, 0.0)
+    run.M, run.lanes, run.native, run.template0 = M, lanes, native, template0
+    run.sigmas = np.asarray(sampler.noise_levels, np.float32)
+    run.shape = (cond.shape[0], cond.shape[1], den.dims.c_out)
+    run.sizes = dict(forc0.sizes)
+    run.sizes.update(context.sizes)
+    run.rows_of = DeviceRollout(self.model, norm, self.task)._forcing_rows  # pylint: disable=protected-access
+    run.scale, run.loc, run.normalized = scale, loc, norm is not None
+    run.want_fields, run.want_spectra = bool(fields), bool(spectra)
+    run.spectra, run.raw_spectra = ([], []) if spectra else (None, None)
+    run.members = [] if keep_members else None
+    run.events = None if specs is None else []
+    if not run.main.set_per_score:
+      run.main.configure()
 
-    scores, spec, means, variances = [], ([] if spectra else None), [], []
-    raw_scores, raw_spec = [], ([] if spectra else None)
-    members = [] if keep_members else None
-    event_scores = None if event_specs is None else []
-
-    def set_events(spec):
-      thr = spec.packed(template0)
-      if norm is not None:
-        thr = ((thr.astype(np.float64) - loc) / scale).astype(np.float32)
-      native.ens_event_set(thr, spec.directions, wq)
-
-    if event_specs is not None and len(event_specs) == 1:
-      set_events(event_specs[0])                          # uploaded once: they survive the store and every lead time
-    views = {}
-    dwq = dwq_scale = None
-    for name, entry in (derived or {}).items():
-      dspec, dev = entry if isinstance(entry, (tuple, list)) else (entry, None)
+    for name, (dspec, dev) in entries.items():
       dplan = dspec.plan(template0, scale, loc)
       dtemplate = dspec.template(template0)
       dscale, dloc = dspec.channel_stats(template0, scale, loc)
-      dthr = None
-      if dev is not None:
-        dthr = dev.packed(dtemplate)
-        if norm is not None:
-          dthr = ((dthr.astype(np.float64) - dloc) / dscale).astype(np.float32)
-        if dwq is None:
-          dwq, dwq_scale = verification.quantize_node_weights(verification.node_weights(template0))
-      views[name] = dict(view=den.view_handle(len(dplan["op"])), plan=dplan, scale=dscale, thr=dthr, events=dev,
-                         template=dtemplate, scores=[], raw=[], ev=None if dev is None else [],
-                         members=[] if keep_members else None)
-    for v in views.values():
-      view = v["view"]
+      store = verification.ScoredStore(den.view_handle(len(dplan["op"])), M, weights, events=dev,
+                                       thresholds=None if dev is None else packed(dev, dtemplate, dscale, dloc), weight_q=wq,
+                                       plan=dplan, source=native)
+      run.views[name] = _DerivedView(store, dscale, dtemplate, keep_members)
+    for store in (v.store for v in run.views.values()):
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
-      v["shared"] = sum(1 for o in views.values() if o["view"] is view) > 1
-      view.ens_reserve(M)
-      view.ens_set_node_weight(verification.node_weights(template0))
-      if not v["shared"]:
-        view.ens_derive_set(**v["plan"])
-        if v["events"] is not None:
-          view.ens_event_set(v["thr"], v["events"].directions, dwq)
-    self.last_lead_ms = []
-    for k in range(horizon):
-      t0 = _time.perf_counter()
-      frows = (rows_of(self.next_forcings(forcings, k, horizon), forcing_cols, sizes, grid_shape)
-               if plan["n_forcing"] else None)
-      for g0 in range(0, M, len(lanes)):
-        group = list(zip(lanes, range(g0, min(M, g0 + len(lanes)))))
-        for lane, m in group:                             # enqueue only: every lane's sample is in flight after this
-          native.ctx_load(m, dst=lane)
-          if noise[m].key is not None:
-            lane.noise_seed(noise[m].key, noise[m].stream)
-          if on_device:
-            lane.noise_draw()
-          else:
-            z = np.asarray(init_noise[m][k], np.float32) if given_noise else noise[m].host_field(shape, template0)
-            lane.upload_noise(z)
-          lane.sample_resident(sigmas, skip_dead_call=True, want_stats=False)
-          if noise[m].key is not None:
-            noise[m].stream = lane.counter("noise_stream")   # churn fields drew too: the library is the one that knows
-        for lane, m in group:
-          lane.rollout_advance(frows)                     # resolves the lane's domain check, then advances ITS context
-          native.ctx_save(m, src=lane)
-          native.ens_push_state(m, state_src, src=lane)
-      # the truth of lead k in the members' units: (y - l) / s in float64, rounded once
-      tk = isel_time(targets, slice(k, k + 1))
-      y = np.transpose(datasets.dataset_to_stacked(tk, tk.sizes), (1, 2, 0, 3)).reshape(shape)
-      truth = y.astype(np.float32) if norm is None else \
-          ((y.astype(np.float64) - loc[None, None, :]) / scale[None, None, :]).astype(np.float32)
-      sums, hist = native.ens_score(truth, want_fields=fields)
-      raw_scores.append(verification.EnsembleScores(sums, hist, M))
-      scores.append(raw_scores[-1].scaled(scale))
-      if event_specs is not None:
-        if len(event_specs) > 1:
-          set_events(event_specs[k])
-        ew, ec, ei = native.ens_event_score(None)          # the truth is on the device already
-        event_scores.append(verification.EventScores(ew, ec, M, event_specs[0].directions, wq_scale, ei))
-      if fields:
-        mean, var = native.ens_download_fields()
-        mean = (mean.astype(np.float64) * scale + loc).astype(np.float32)
-        var = (var.astype(np.float64) * scale * scale).astype(np.float32)
-        tmpl = tk.map(np.zeros_like)
-        means.append(Denoiser.unpack_outputs(mean, grid_shape, tmpl))
-        variances.append(Denoiser.unpack_outputs(var, grid_shape, tmpl))
-      if spectra:
-        raw_spec.append(_spectra.EnsembleSpectra(native.ens_spectrum(None), M))   # the truth is on the device already
-        spec.append(raw_spec[-1].scaled(scale))
-      if keep_members:
-        members.append([native.ens_download_member(m) for m in range(M)])
-      for v in views.values():
-        view = v["view"]
-        if v["shared"]:
-          view.ens_derive_set(**v["plan"])
-        view.ens_derive(native)                           # members and truth, device to device
-        dsums, dhist = view.ens_score(None, want_fields=False)
-        v["raw"].append(verification.EnsembleScores(dsums, dhist, M))
-        v["scores"].append(v["raw"][-1].scaled(v["scale"]))
-        if v["events"] is not None:
-          if v["shared"]:
-            view.ens_event_set(v["thr"], v["events"].directions, dwq)
-          ew, ec, ei = view.ens_event_score(None)
-          v["ev"].append(verification.EventScores(ew, ec, M, v["events"].directions, dwq_scale, ei))
-        if keep_members:
-          v["members"].append([view.ens_download_member(m) for m in range(M)])
-      self.last_lead_ms.append(1e3 * (_time.perf_counter() - t0))
+      store.set_per_score = sum(1 for v in run.views.values() if v.store.handle is store.handle) > 1
+      store.setup()
+    return run
 
-    def on_time_axis(parts):
-      out = concat_time(parts)
-      if datasets.is_xarray(given[0]):
-        return datasets.to_xarray(out, given[0].isel(time=slice(0, horizon)))
-      return datasets.like_inputs(out, None, *given[1:])
+  @staticmethod
+  def _sample_lead(run: "_EnsembleRun", k: int, forcings, horizon: int) -> None:
+    """The member loop of lead time k: every member sampled from its own context, advanced, and its state pushed."""
+    native, lanes, M, noise = run.native, run.lanes, run.M, run.noise
+    frows = (run.rows_of(EnsembleRollout.next_forcings(forcings, k, horizon), run.forcing_cols, run.sizes, run.grid_shape)
+             if run.plan["n_forcing"] else None)
+    for g0 in range(0, M, len(lanes)):
+      group = list(zip(lanes, range(g0, min(M, g0 + len(lanes)))))
+      for lane, m in group:                               # enqueue only: every lane's sample is in flight after this
+        native.ctx_load(m, dst=lane)
+        if noise[m].key is not None:
+          lane.noise_seed(noise[m].key, noise[m].stream)
+        if run.on_device:
+          lane.noise_draw()
+        else:
+          z = np.asarray(run.init_noise[m][k], np.float32) if run.given_noise else \
+              noise[m].host_field(run.shape, run.template0)
+          lane.upload_noise(z)
+        lane.sample_resident(run.sigmas, skip_dead_call=True, want_stats=False)
+        if noise[m].key is not None:
+          noise[m].stream = lane.counter("noise_stream")   # churn fields drew too: the library is the one that knows
+      for lane, m in group:
+        lane.rollout_advance(frows)                       # resolves the lane's domain check, then advances ITS context
+        native.ctx_save(m, src=lane)
+        native.ens_push_state(m, run.state_src, src=lane)
 
-    return EnsembleRolloutResult(scores, spec, on_time_axis(means) if fields else None,
-                                 on_time_axis(variances) if fields else None, members, M,
-                                 scores_normalized=raw_scores, spectra_normalized=raw_spec, events=event_scores,
-                                 derived=None if derived is None else {
-                                     k: DerivedRolloutResult(v["scores"], v["raw"], v["ev"], v["members"], v["template"])
-                                     for k, v in views.items()})
+  @staticmethod
+  def _score_lead(run: "_EnsembleRun", k: int, targets) -> None:
+    """Lead time k scored on the device: the main store against `targets[k]`, then every derived view."""
+    from . import spectra as _spectra  # pylint: disable=import-outside-toplevel
+    native, M, scale, loc = run.native, run.M, run.scale, run.loc
+    # the truth of lead k in the members' units: (y - l) / s in float64, rounded once
+    tk = isel_time(targets, slice(k, k + 1))
+    y = np.transpose(datasets.dataset_to_stacked(tk, tk.sizes), (1, 2, 0, 3)).reshape(run.shape)
+    truth = ((y.astype(np.float64) - loc[None, None, :]) / scale[None, None, :]).astype(np.float32) if run.normalized \
+        else y.astype(np.float32)
+    if run.main.set_per_score:
+      run.main.thresholds = run.thresholds[k]
+    raw, ev = run.main.score(truth, want_fields=run.want_fields)   # (the events: on the truth already on the device)
+    run.raw_scores.append(raw)
+    run.scores.append(raw.scaled(scale))
+    if ev is not None:
+      run.events.append(ev)
+    if run.want_fields:
+      mean, var = native.ens_download_fields()
+      mean = (mean.astype(np.float64) * scale + loc).astype(np.float32)
+      var = (var.astype(np.float64) * scale * scale).astype(np.float32)
+      tmpl = tk.map(np.zeros_like)
+      run.means.append(Denoiser.unpack_outputs(mean, run.grid_shape, tmpl))
+      run.variances.append(Denoiser.unpack_outputs(var, run.grid_shape, tmpl))
+    if run.want_spectra:
+      run.raw_spectra.append(_spectra.EnsembleSpectra(native.ens_spectrum(None), M))   # the truth is on the device already
+      run.spectra.append(run.raw_spectra[-1].scaled(scale))
+    if run.members is not None:
+      run.members.append([native.ens_download_member(m) for m in range(M)])
+    for v in run.views.values():
+      raw, ev = v.store.score(None)                       # members and truth, device to device
+      v.raw.append(raw)
+      v.scores.append(raw.scaled(v.scale))
+      if ev is not None:
+        v.events.append(ev)
+      if v.members is not None:
+        v.members.append([v.store.handle.ens_download_member(m) for m in range(M)])

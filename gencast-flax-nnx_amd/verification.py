@@ -587,3 +587,71 @@ class DerivedSpec:
     rows = self._per_channel(template0)
     return (np.array([1.0 if r[0] == "norm2" else scale[r[1]] for r in rows]),
             np.array([0.0 if r[0] == "norm2" else loc[r[1]] for r in rows]))
+
+
+# ---------------------------------------------------------------------------------------------
+# a member store that gets scored
+# ---------------------------------------------------------------------------------------------
+class ScoredStore:
+  """The member store of one handle and everything that is scored from it: the M members it holds, the node weights
+  (None: `ens_score` is not used on it), optionally the events counted on it -- an `EventSpec`, its packed `thresholds`
+  in the members' units and `weight_q` = `quantize_node_weights(...)` -- and optionally the `plan` (`DerivedSpec.plan`) that
+  fills it from the store of a `source` handle (`ens_derive`).  `EnsembleSampler` and `EnsembleRollout` use one for the
+  main store and one per derived view.
+
+  `set_per_score`: the plan and the thresholds are not set once by `setup` but by every `score` -- two stores that share
+  a handle, or thresholds that change from call to call (assign `thresholds` before the call)."""
+
+  def __init__(self, handle, n_members: int, node_weight=None, *, events: Optional["EventSpec"] = None, thresholds=None,
+               weight_q: Optional[Tuple[np.ndarray, float]] = None, plan=None, source=None, set_per_score: bool = False):
+    if events is not None and weight_q is None:
+      raise ValueError("events need the quantised node weights (quantize_node_weights)")
+    if (plan is None) != (source is None):
+      raise ValueError("a derive plan and its source handle go together")
+    self.handle, self.n_members, self.node_weight = handle, int(n_members), node_weight
+    self.events, self.thresholds, self.weight_q = events, thresholds, weight_q
+    self.plan, self.source, self.set_per_score = plan, source, bool(set_per_score)
+
+  def reserve(self) -> None:
+    self.handle.ens_reserve(self.n_members)
+    if self.node_weight is not None:
+      self.handle.ens_set_node_weight(self.node_weight)
+
+  def _set_plan(self) -> None:
+    if self.plan is not None:
+      self.handle.ens_derive_set(**self.plan)
+
+  def _set_events(self) -> None:
+    if self.events is not None:
+      self.handle.ens_event_set(self.thresholds, self.events.directions, self.weight_q[0])
+
+  def configure(self) -> None:
+    """The plan and the thresholds: both survive `ens_reserve` and every score."""
+    self._set_plan()
+    self._set_events()
+
+  def setup(self) -> None:
+    self.reserve()
+    if not self.set_per_score:
+      self.configure()
+
+  def score_events(self, truth=None) -> Optional["EventScores"]:
+    """The event tables of the store (None without an EventSpec); `truth` None: the truth already on the device."""
+    if self.events is None:
+      return None
+    if self.set_per_score:
+      self._set_events()
+    weighted, counts, invalid = self.handle.ens_event_score(truth)
+    return EventScores(weighted, counts, self.n_members, self.events.directions, self.weight_q[1], invalid)
+
+  def score(self, truth=None, want_fields: bool = False) -> Tuple[EnsembleScores, Optional["EventScores"]]:
+    """-> (raw `EnsembleScores`, `EventScores` or None).  `truth` [G, B, c_out] in the members' units, None: the truth
+    already on the device; with a plan the store is first filled from the source's (members and truth, device to
+    device) and `truth` [G, B, c_src] is the SOURCE's."""
+    if self.plan is not None:
+      if self.set_per_score:
+        self._set_plan()
+      self.handle.ens_derive(self.source, truth)
+      truth = None
+    sums, hist = self.handle.ens_score(truth, want_fields=want_fields)
+    return EnsembleScores(sums, hist, self.n_members), self.score_events(None)

@@ -61,3 +61,19 @@ def khop16_setup():
   """SURVEY.md 8d stress case: mesh 5 with k_hop = 16 (up to 799 keys per query), heads of 128."""
   return tiny_setup(batch=1, seed=5, mesh_size=5, k_hop=16, latent=256, heads=2, ffw=256, layers=2, c_in=20,
                     c_out=6, n_lat=73, n_lon=144)
+
+
+def small_graph(n_lat=13, n_lon=24, mesh_size=2, k_hop=2):
+  """The graph of a small equiangular grid, poles included (G = n_lat * n_lon)."""
+  lat = np.linspace(-90, 90, n_lat)
+  lon = np.arange(n_lon) * (360.0 / n_lon)
+  return geometry.build_denoiser_graph(grid_lat=lat, grid_lon=lon, mesh_size=mesh_size, attention_k_hop=k_hop)
+
+
+def graph_handle(gr, batch, c_out, latent=128, heads=2, ffw=256):
+  """A handle that knows its graph and nothing else: no weights, no gc_finalize."""
+  from gencast_flax_nnx_amd import _lib
+  nd = _lib.NativeDenoiser(latent_size=latent, d_model=latent, num_heads=heads, ffw_hidden=ffw, num_layers=1,
+                           c_in=c_out + 4, c_out=c_out, batch=batch)
+  nd.set_graph(gr)
+  return nd

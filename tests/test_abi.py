@@ -30,6 +30,20 @@ def test_every_declared_symbol_is_exported_and_bound():
   assert b"gfx950" in lib.gc_build_info()
 
 
+def test_both_build_scripts_take_the_translation_units_from_one_list():
+  """csrc/SOURCES names every translation unit under csrc/ once; csrc/build.sh and tools/build_variant.sh read it and
+  name no unit themselves but gc_kernels.hip, which both compile a second time with other flags."""
+  csrc = os.path.join(ROOT, "gencast-flax-nnx_amd", "csrc")
+  listed = [l.strip() for l in open(os.path.join(csrc, "SOURCES")) if l.strip() and not l.startswith("#")]
+  on_disk = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".cpp")))
+  assert sorted(listed) == on_disk and len(set(listed)) == len(listed)
+  for script in (os.path.join(csrc, "build.sh"), os.path.join(ROOT, "tools", "build_variant.sh")):
+    text = open(script).read()
+    assert re.search(r"<\s*<\(grep -v '\^#' SOURCES\)", text), f"{script} does not read csrc/SOURCES"
+    named = set(re.findall(r"\bgc_\w+\.(?:hip|cpp)\b", text))
+    assert named <= {"gc_kernels.hip"}, f"{script} names translation units of its own: {sorted(named)}"
+
+
 def test_kernel_class_table():
   lib = _lib.load_library()
   n = lib.gc_num_kernel_classes()

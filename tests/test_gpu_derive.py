@@ -20,6 +20,7 @@ from gencast_flax_nnx_amd.verification import quantize_node_weights
 from tests import derive_reference as R
 from tests import event_reference as ER
 from tests import helpers
+from tests.helpers import graph_handle as _handle
 
 pytestmark = pytest.mark.gpu
 
@@ -36,14 +37,6 @@ def _grid(which):
   gr = geometry.build_denoiser_graph(grid_lat=lat, grid_lon=lon, mesh_size=2, attention_k_hop=2)
   assert gr.num_grid_nodes == n_lat * n_lon
   return gr, lat, lon, np.asarray(losses.normalized_latitude_weights(lat), np.float64)
-
-
-def _handle(gr, batch, c_out):
-  """A handle that knows its graph and nothing else: no weights, no gc_finalize."""
-  nd = _lib.NativeDenoiser(latent_size=128, d_model=128, num_heads=2, ffw_hidden=256, num_layers=1, c_in=c_out + 4, c_out=c_out,
-                           batch=batch)
-  nd.set_graph(gr)
-  return nd
 
 
 def _push_all(nd, members):

@@ -9,32 +9,19 @@ multiple of 4, the one-point-per-thread form of the code pass."""
 import numpy as np
 import pytest
 
-from gencast_flax_nnx_amd import (EnsembleSampler, EventScores, EventSpec, GenCast, _lib, config, datasets, geometry, rollout,
-                                  synthetic, verification, weights)
+from gencast_flax_nnx_amd import (EnsembleSampler, EventScores, EventSpec, GenCast, _lib, config, datasets, rollout, synthetic,
+                                  verification, weights)
 from gencast_flax_nnx_amd.denoiser import dims_from_arch
 from gencast_flax_nnx_amd.verification import event_probability, quantize_node_weights
 from tests import event_reference as R
 from tests import helpers
+from tests.helpers import graph_handle as _handle, small_graph as _graph
 from tests.test_gpu_host_api import _small_arch
 from tests.test_rollout import _stats
 
 pytestmark = pytest.mark.gpu
 
 ALPHAS = np.array([0.05, 0.2, 0.5, 0.9])
-
-
-def _graph(n_lat=13, n_lon=24, mesh_size=2, k_hop=2):
-  lat = np.linspace(-90, 90, n_lat)
-  lon = np.arange(n_lon) * (360.0 / n_lon)
-  return geometry.build_denoiser_graph(grid_lat=lat, grid_lon=lon, mesh_size=mesh_size, attention_k_hop=k_hop)
-
-
-def _handle(gr, batch, c_out, latent=128, heads=2, ffw=256):
-  """A handle that knows its graph and nothing else: no weights, no gc_finalize."""
-  nd = _lib.NativeDenoiser(latent_size=latent, d_model=latent, num_heads=heads, ffw_hidden=ffw, num_layers=1,
-                           c_in=c_out + 4, c_out=c_out, batch=batch)
-  nd.set_graph(gr)
-  return nd
 
 
 def _push_all(nd, members):

@@ -14,6 +14,7 @@ import pytest
 
 from gencast_flax_nnx_amd import EnsembleSpectra, SphericalAnalysis, _lib, geometry
 from tests import helpers
+from tests.helpers import graph_handle as _handle, small_graph as _graph
 from tests import spectrum_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -21,19 +22,6 @@ pytestmark = pytest.mark.gpu
 
 def _latlon(n_lat, n_lon):
   return np.linspace(-90, 90, n_lat), np.arange(n_lon) * (360.0 / n_lon)
-
-
-def _graph(n_lat=13, n_lon=24, mesh_size=2, k_hop=2):
-  lat, lon = _latlon(n_lat, n_lon)
-  return geometry.build_denoiser_graph(grid_lat=lat, grid_lon=lon, mesh_size=mesh_size, attention_k_hop=k_hop)
-
-
-def _handle(gr, batch, c_out, latent=128, heads=2, ffw=256):
-  """A handle that knows its graph and nothing else: no weights, no gc_finalize."""
-  nd = _lib.NativeDenoiser(latent_size=latent, d_model=latent, num_heads=heads, ffw_hidden=ffw, num_layers=1,
-                           c_in=c_out + 4, c_out=c_out, batch=batch)
-  nd.set_graph(gr)
-  return nd
 
 
 def _data(M, G, B, C, seed, scale):

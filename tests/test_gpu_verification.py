@@ -10,23 +10,10 @@ import pytest
 from gencast_flax_nnx_amd import _lib, geometry, verification
 from gencast_flax_nnx_amd.verification import EnsembleScores
 from tests import helpers
+from tests.helpers import graph_handle as _handle, small_graph as _graph
 from tests import verification_reference as R
 
 pytestmark = pytest.mark.gpu
-
-
-def _graph(n_lat=13, n_lon=24, mesh_size=2, k_hop=2):
-  lat = np.linspace(-90, 90, n_lat)
-  lon = np.arange(n_lon) * (360.0 / n_lon)
-  return geometry.build_denoiser_graph(grid_lat=lat, grid_lon=lon, mesh_size=mesh_size, attention_k_hop=k_hop)
-
-
-def _handle(gr, batch, c_out, latent=128, heads=2, ffw=256):
-  """A handle that knows its graph and nothing else: no weights, no gc_finalize."""
-  nd = _lib.NativeDenoiser(latent_size=latent, d_model=latent, num_heads=heads, ffw_hidden=ffw, num_layers=1,
-                           c_in=c_out + 4, c_out=c_out, batch=batch)
-  nd.set_graph(gr)
-  return nd
 
 
 def _data(M, G, B, C, seed, scale=None):
@@ -440,3 +427,67 @@ def test_state_and_argument_errors():
     other.close()
     if full is not None:
       full.close()
+
+
+# ---- the truth of the store: uploaded by one scorer, used by all ----------------------------------------------------------
+def test_truth_uploaded_by_one_scorer_is_the_truth_of_the_others():
+  """gc_ens_score, gc_ens_spectrum and gc_ens_event_score take the truth through one path into one buffer: whichever of
+  them uploads it, the other two given None score against it, bit for bit as if it had been passed to them; a truth that
+  gc_ens_derive uploads goes into the SOURCE handle's buffer and is there for the source's own scorers."""
+  from gencast_flax_nnx_amd import SphericalAnalysis
+  from gencast_flax_nnx_amd.verification import quantize_node_weights
+  gr = _graph()
+  G, B, C, M, T, lmax = gr.num_grid_nodes, 2, 3, 3, 2, 6
+  members, truth, w = _data(M, G, B, C, seed=31, scale=np.ones(C))
+  rng = np.random.default_rng(32)
+  thr = rng.standard_normal((T, G, B, C)).astype(np.float32)
+  wq, _ = quantize_node_weights(w)
+  tabs = SphericalAnalysis(np.linspace(-90, 90, 13), np.arange(24) * 15.0, lmax=lmax).device_tables()
+
+  def fresh():
+    nd = _handle(gr, B, C)
+    _push_all(nd, members, w)
+    nd.spec_set_tables(*tabs)
+    nd.ens_event_set(thr, [1, -1], wq)
+    return nd
+
+  scorers = {"score": lambda nd, t: nd.ens_score(t), "spectrum": lambda nd, t: (nd.ens_spectrum(t),),
+             "events": lambda nd, t: nd.ens_event_score(t)}
+  nd = fresh()
+  try:
+    explicit = {name: f(nd, truth) for name, f in scorers.items()}
+  finally:
+    nd.close()
+  assert all(np.isfinite(a).all() for a in explicit["score"][:1] + explicit["spectrum"])
+
+  def same(tag, got, want):
+    assert len(got) == len(want)
+    for i, (a, b) in enumerate(zip(got, want)):
+      assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), f"{tag}: output {i} differs"
+
+  for uploader in scorers:
+    nd = fresh()
+    try:
+      for name, f in scorers.items():
+        if name != uploader:
+          with pytest.raises(_lib.GencastHipError, match="truth"):   # nothing uploaded yet
+            f(nd, None)
+      same(f"{uploader} uploads", scorers[uploader](nd, truth), explicit[uploader])
+      for name, f in scorers.items():
+        same(f"{uploader} uploaded, {name} given None", f(nd, None), explicit[name])
+    finally:
+      nd.close()
+
+  src, view = fresh(), _handle(gr, B, 2)
+  try:
+    view.ens_derive_set(c_src=C, op=[0, 1], src_a=[0, 1], src_b=[0, 2], affine=np.tile([1.0, 0.0, 1.0, 0.0], (2, 1)),
+                        n_lat=13, n_lon=24)
+    view.ens_reserve(M)
+    with pytest.raises(_lib.GencastHipError, match="no truth on the source handle"):
+      view.ens_derive(src)
+    view.ens_derive(src, truth)
+    same("derive uploaded, source score given None", src.ens_score(None), explicit["score"])
+    same("derive uploaded, source score given the truth", src.ens_score(truth), explicit["score"])
+  finally:
+    view.close()
+    src.close()

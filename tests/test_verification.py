@@ -191,8 +191,9 @@ def test_new_entries_are_declared_bound_and_exported():
       ["num_members", "rngs", "concurrent_members", "fields"]
   assert callable(rollout.InputsAndResiduals.ensemble_scores) and callable(NaNCleaner.ensemble_scores)
   # the new translation unit is in both build lists, and the product does not import the tests' reference
+  assert "gc_ensemble.hip" in open(os.path.join(ROOT, "gencast-flax-nnx_amd/csrc/SOURCES")).read().split()
   for script in ("gencast-flax-nnx_amd/csrc/build.sh", "tools/build_variant.sh"):
-    assert "gc_ensemble.hip" in open(os.path.join(ROOT, script)).read(), script
+    assert "< <(grep -v '^#' SOURCES)" in open(os.path.join(ROOT, script)).read(), script
   assert "verification_reference" not in open(os.path.join(ROOT, "gencast-flax-nnx_amd", "verification.py")).read()
 
 

@@ -23,8 +23,12 @@ OBJ=/tmp/gc_variant_obj/$TREE_HASH
 mkdir -p "$OBJ" variants
 SRC_HASH=variant-$name
 BASE=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DGC_SOURCE_HASH="\"$SRC_HASH\"")
+mapfile -t UNITS < <(grep -v '^#' SOURCES)          # the translation units: the list csrc/build.sh reads
 pids=()
-for src in gc_api.hip gc_weights.hip gc_forward.hip gc_sampler.hip gc_noise.hip gc_ensemble.hip gc_spectrum.hip gc_graph.cpp; do
+objs=("$OBJ/gc_kernels_$name.o" "$OBJ/gc_kernels_a16.o")
+for src in "${UNITS[@]}"; do
+  [ "$src" = gc_kernels.hip ] && continue             # (compiled below: once with the flags given, once as the fp16-feature TU)
+  objs+=("$OBJ/${src%.*}.o")
   if [ ! -f "$OBJ/${src%.*}.o" ] || [ "$src" -nt "$OBJ/${src%.*}.o" ]; then
     "$HIPCC" "${BASE[@]}" -c "$src" -o "$OBJ/${src%.*}.o" & pids+=($!)
   fi
@@ -34,5 +38,5 @@ if [ ! -f "$OBJ/gc_kernels_a16.o" ] || [ gc_kernels.hip -nt "$OBJ/gc_kernels_a16
 fi
 "$HIPCC" "${BASE[@]}" "$@" -c gc_kernels.hip -o "$OBJ/gc_kernels_$name.o" & pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done
-"$HIPCC" --offload-arch=gfx950 -fPIC -shared "$OBJ/gc_kernels_$name.o" "$OBJ"/gc_kernels_a16.o "$OBJ"/gc_api.o "$OBJ"/gc_weights.o "$OBJ"/gc_forward.o "$OBJ"/gc_sampler.o "$OBJ"/gc_noise.o "$OBJ"/gc_ensemble.o "$OBJ"/gc_spectrum.o "$OBJ"/gc_graph.o -o "variants/libgencast_hip_$name.so"
+"$HIPCC" --offload-arch=gfx950 -fPIC -shared "${objs[@]}" -o "variants/libgencast_hip_$name.so"
 echo "built variants/libgencast_hip_$name.so"
