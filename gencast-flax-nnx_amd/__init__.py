@@ -17,6 +17,8 @@ Public surface (mirrors the reference's call contracts):
                       ensemble, analysed on the GPU (no reference counterpart: GenCast.ensemble_spectra)
                       DerivedSpec: wind speed and spatially pooled fields formed on the GPU in front of every scorer
                       (GenCast.ensemble_derived, EnsembleRollout.run(derived=...))
+                      OrderScores: quantile fields and the reliability / potential split of the CRPS from members sorted
+                      on the GPU (GenCast.ensemble_order, EnsembleRollout.run(order=...))
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
@@ -34,11 +36,11 @@ from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, Ense
                       autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
-from .verification import DerivedSpec, EnsembleScores, EventScores, EventSpec  # noqa: F401
+from .verification import DerivedSpec, EnsembleScores, EventScores, EventSpec, OrderScores  # noqa: F401
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
            "InputsAndResiduals", "autoregressive_rollout", "DeviceRollout", "NaNCleaner", "launch", "losses",
            "compute_loss", "validation_loss", "verification", "EnsembleScores", "spectra", "EnsembleSpectra",
            "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec",
-           "DerivedSpec", "DerivedRolloutResult"]
+           "DerivedSpec", "DerivedRolloutResult", "OrderScores"]

@@ -123,6 +123,12 @@ SIGNATURES = {
     "gc_ens_derive_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int32,
                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.POINTER(ctypes.c_double)]),
     "gc_ens_derive": (ctypes.c_int, [_hp, _hp, _f32p]),
+    "gc_ens_order_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_order_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_order_fields": (ctypes.c_int, [_hp]),
+    "gc_ens_order_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -215,6 +221,7 @@ class NativeDenoiser:
     self._spec_lmax = 0                        # band limit of the analysis tables this object handed to the handle
     self._event_thresholds = 0                 # threshold fields this object handed to the handle
     self._derive_c_src = 0                     # source channels of the derive plan this object handed to the handle
+    self._order_quantiles = None               # probabilities this object handed to the handle (None: ens_order_set not called)
 
   # -- plumbing ------------------------------------------------------------------------------
   def _check(self, rc):
@@ -690,6 +697,61 @@ class NativeDenoiser:
       if t.shape != want:
         raise ValueError(f"truth must be {want}, got {t.shape}")
     self._check(self._lib.gc_ens_derive(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
+
+  # -- ensemble order statistics (members sorted on the device) ----------------------------------------
+  def ens_order_set(self, probs) -> None:
+    """`probs` [Q] in [0, 1], Q in 0..8: the quantile fields `ens_order_score` / `ens_order_fields` leave on the device
+    (gc_ens_order_set; needs `set_graph` only and survives `ens_reserve`).  Q = 0: the bin sums only."""
+    p = np.ascontiguousarray([] if probs is None else probs, dtype=np.float64)
+    if p.ndim != 1 or p.shape[0] > 8:
+      raise ValueError(f"probs must be a sequence of at most 8 probabilities, got shape {p.shape}")
+    if not np.all((p >= 0.0) & (p <= 1.0)):                # (NaN fails both comparisons)
+      raise ValueError("probs must lie in [0, 1]")
+    self._check(self._lib.gc_ens_order_set(self._h, p.shape[0],
+                                           _ptr(p, ctypes.POINTER(ctypes.c_double)) if p.shape[0] else None))
+    self._order_quantiles = int(p.shape[0])
+
+  def _order_need_set(self) -> int:
+    if self._order_quantiles is None:
+      raise GencastHipError("libgencast_hip error 4: no probabilities (ens_order_set has not been called on this object)")
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    return self._order_quantiles
+
+  def ens_order_score(self, truth=None):
+    """-> (bins [B, c_out, M + 1, 2], extra [B, c_out, 3], pinball [B, c_out, Q] float64, counts [B, c_out, Q + 1] uint64,
+    invalid int): the raw, additive sums of gc_ens_order_score over the member store (`verification.OrderScores` derives
+    the scores); the Q quantile fields stay on the device (`ens_order_quantile`).  `truth` [G, B, c_out], or None = the
+    truth uploaded last (shared with `ens_score`)."""
+    Q = self._order_need_set()
+    t = None
+    if truth is not None:
+      t = _f32(truth)
+      if t.shape != self._shape_out():
+        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    B, C, M = self.cfg.batch, self.cfg.c_out, self._ens_members
+    dp, u64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)
+    bins = np.empty((B, C, M + 1, 2), dtype=np.float64)
+    extra = np.empty((B, C, 3), dtype=np.float64)
+    pinball = np.empty((B, C, Q), dtype=np.float64)
+    counts = np.empty((B, C, Q + 1), dtype=np.uint64)
+    invalid = np.zeros(1, dtype=np.uint64)
+    self._check(self._lib.gc_ens_order_score(self._h, None if t is None else _ptr(t, _f32p), _ptr(bins, dp), _ptr(extra, dp),
+                                             _ptr(pinball, dp) if Q else None, _ptr(counts, u64), _ptr(invalid, u64)))
+    return bins, extra, pinball, counts, int(invalid[0])
+
+  def ens_order_fields(self) -> None:
+    """The quantile fields of the member store, without truth and without weights (gc_ens_order_fields)."""
+    self._order_need_set()
+    self._check(self._lib.gc_ens_order_fields(self._h))
+
+  def ens_order_quantile(self, q: int) -> np.ndarray:
+    """Quantile field `q` [G, B, c_out] of the last `ens_order_score` / `ens_order_fields` (gc_ens_order_download)."""
+    if self._order_quantiles is None:
+      raise GencastHipError("libgencast_hip error 4: no probabilities (ens_order_set has not been called on this object)")
+    out = np.empty(self._shape_out(), dtype=np.float32)
+    self._check(self._lib.gc_ens_order_download(self._h, int(q), _ptr(out, _f32p)))
+    return out
 
   # -- context store: one resident conditioning per ensemble member ----------------------------------
   def ctx_reserve(self, n: int) -> None:

@@ -401,6 +401,7 @@ int gc_ens_derive(gc_handle* h, gc_handle* src, const float* truth) {
   if ((rc = order_behind(h, h->ev_drv_src, src->stream, s))) return rc;
   h->evt_scored = false;
   h->has_ens_fields = false;
+  h->ord_ready = false;
   GC_HIP(h, h->drv_time.begin(s));
   if ((rc = launch(h, gc::KC_PACK, [&] {
          return gc::launch_ens_derive(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out, c_d,

@@ -8,7 +8,8 @@
 //   gc_spectrum.hip  gc_spec_* and gc_ens_spectrum
 //   gc_events.hip    gc_ens_event_*
 //   gc_derive.hip    gc_ens_derive_*
-// The last four are scorers over the member store of gc_ens_reserve.  What they share -- field length, upload through
+//   gc_order.hip     gc_ens_order_*
+// The last five are scorers over the member store of gc_ens_reserve.  What they share -- field length, upload through
 // the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
 // relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
 // are a BufferGroup and its events an Event or a Bracket (below); declaring one as a member of the handle is all it takes
@@ -333,6 +334,22 @@ struct gc_handle {
   gci::Bracket drv_time{events};                               // of the last call
   gci::Event ev_drv_src{events};                               // stream order behind the source handle
   int64_t drv_calls = 0, drv_device_us = 0;
+
+  // ensemble order statistics (gc_ens_order_*, gc_order.hip): quantile fields and the bin sums of the CRPS decomposition
+  gci::BufferGroup ord_allocs{groups};            // sized by Q: the quantile fields; kept across gc_ens_reserve
+  gci::BufferGroup ord_work_allocs{groups};       // sized by M and Q: made again by the scoring call that finds either changed
+  bool ord_set = false;                          // probabilities have been set (Q = 0 is a setting)
+  int ord_Q = 0;
+  double ord_p[8] = {};                          // the probabilities: lo, hi and f are formed per call from the current M
+  int ord_work_M = 0, ord_work_Q = -1;           // what the partial and result buffers are sized for
+  float* d_ord_q = nullptr;                      // [Q][G, B, c_out] quantile fields
+  double* d_ord_part = nullptr;                  // [blocks][2 (M + 1) + 3 + Q][B c_out] per-block column sums
+  unsigned* d_ord_cpart = nullptr;               // [blocks][Q + 1][B c_out] per-block counts, then [blocks][tiles] skipped points
+  double* d_ord_out = nullptr;                   // bins [B c_out][M + 1][2], extra [B c_out][3], pinball [B c_out][Q]
+  unsigned long long* d_ord_outc = nullptr;      // counts [B c_out][Q + 1], then the skipped points of the call
+  bool ord_ready = false;                        // an order call ran since gc_ens_order_set / gc_ens_reserve / gc_ens_derive
+  gci::Bracket ord_time{events};                 // of the last call
+  int64_t ord_calls = 0, ord_device_us = 0, ord_invalid_points = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

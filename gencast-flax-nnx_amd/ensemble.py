@@ -119,6 +119,17 @@ class EnsembleSampler:
                        "ranks' members over and push them with NativeDenoiser.ens_push_host")
     return self._run(inputs, targets, forcings, num_members, None, derived=(spec, events))
 
+  def order(self, inputs, targets, forcings, num_members: int, probs=(), *, quantile_fields: bool = False):
+    """Runs the members as `scores` does and sorts them, point by point, on the device: `verification.OrderScores` in the
+    units of `targets` -- the reliability / potential split of the ensemble CRPS (Hersbach 2000), the outlier frequencies
+    and, for the probabilities `probs` (at most 8), the pinball loss and the coverage of the quantile fields.  With
+    `quantile_fields=True` also those fields (the median, a p10 / p90 band) as Datasets shaped like `targets`; they need no
+    truth and exist wherever all members are finite.  No member is downloaded."""
+    if self.world_size > 1:
+      raise ValueError("EnsembleSampler.order needs all members on one rank (world_size == 1): bring the other "
+                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    return self._run(inputs, targets, forcings, num_members, None, order=(tuple(probs), bool(quantile_fields)))
+
   def _spectral(self, inputs, targets, forcings, num_members, score_fields, lmax):
     if self.world_size > 1:
       raise ValueError("EnsembleSampler.spectra needs all members on one rank (world_size == 1): bring the other "
@@ -126,10 +137,10 @@ class EnsembleSampler:
     return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
 
   def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,
-           lmax: Optional[int] = None, events=None, derived=None):
+           lmax: Optional[int] = None, events=None, derived=None, order=None):
     """`score_fields` None: members come back as Datasets (`__call__`) or, with `spectral`, only their spectra are
-    formed, or, with `events` (an EventSpec), only their event tables; else they are scored (`scores`), with `spectral`
-    both."""
+    formed, or, with `events` (an EventSpec), only their event tables, or, with `order` (probabilities, want fields), only
+    their order statistics; else they are scored (`scores`), with `spectral` both."""
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
     cond, grid_shape, slots = self._denoiser.init_for(inputs, template, forcings)
@@ -157,14 +168,14 @@ class EnsembleSampler:
         lane.upload_cond_dev(ptr)                          # device-to-device, on the lane's own stream
     scoring = score_fields is not None
     main = None                                            # lane 0's member store, where anything is scored at all
-    if scoring or spectral or events is not None or derived is not None:
+    if scoring or spectral or events is not None or derived is not None or order is not None:
       dspec, dev = derived if derived is not None else (None, None)
       weights = None if spectral and not scoring else verification.node_weights(template)
       wq = None if events is None and dev is None else verification.quantize_node_weights(weights)
       # (scored once: the thresholds are set by that call, after the members are in)
-      main = verification.ScoredStore(native, num_members, weights if scoring else None, events=events,
+      main = verification.ScoredStore(native, num_members, weights if scoring or order is not None else None, events=events,
                                       thresholds=None if events is None else events.packed(template), weight_q=wq,
-                                      set_per_score=True)
+                                      set_per_score=True, order=None if order is None else order[0])
       main.setup()
     if spectral:
       _spectra.ensure_tables(native, template, lmax)
@@ -193,6 +204,13 @@ class EnsembleSampler:
       return scores if dev is None else (scores, event_scores)
     if events is not None:
       return main.score_events(truth)
+    if order is not None:
+      scores = main.score_order(truth)
+      if not order[1]:
+        return scores
+      given = (targets_template, inputs, forcings)
+      return scores, [datasets.like_inputs(Denoiser.unpack_outputs(f, grid_shape, template), *given)
+                      for f in main.quantile_fields()]
     if not scoring:
       return _spectra.EnsembleSpectra(native.ens_spectrum(truth), num_members)
     result = (main.score(truth, want_fields=score_fields)[0],)

@@ -126,6 +126,20 @@ class GenCast:
     runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
     return runner.events(inputs, targets, forcings, num_members, spec)
 
+  def ensemble_order(self, inputs, targets, forcings=None, *, num_members, probs=(), quantile_fields=False, rngs=0,
+                     concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and sorts them point by point on the GPU:
+    `verification.OrderScores` -- the ensemble CRPS split into its reliability and potential parts (Hersbach 2000), the
+    outlier frequencies, and for the probabilities `probs` (at most 8) the pinball loss and coverage of the quantile
+    fields -- per batch member and channel, latitude-weighted.  `quantile_fields=True`: -> (OrderScores, [Q Datasets]),
+    the quantile fields (median, p10 / p90 band) shaped like `targets`.  No member leaves the device.  The uncertainty and
+    resolution parts of Hersbach's decomposition need a climatology of the observations and are not formed."""
+    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
+    if not isinstance(rngs, (int, np.integer)):
+      rngs = Sampler.seed_from(rngs)
+    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    return runner.order(inputs, targets, forcings, num_members, probs, quantile_fields=quantile_fields)
+
   def ensemble_derived(self, inputs, targets, forcings=None, *, num_members, spec, events=None, rngs=0, concurrent_members=1):
     """Samples `num_members` (2..64) members as `ensemble_scores` does and scores, on the GPU, what `spec`
     (`verification.DerivedSpec`) makes of them and of `targets`: wind speed from two components, fields max-, min- or

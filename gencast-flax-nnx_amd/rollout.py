@@ -202,6 +202,30 @@ class InputsAndResiduals:
     return scores.scaled(np.concatenate(scale)), datasets.like_inputs(mean, *given), datasets.like_inputs(var, *given)
 
 
+  def ensemble_order(self, inputs, targets, forcings=None, **kwargs):
+    """`ensemble_order` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets, in
+    physical units: the bin and pinball sums are rescaled as `ensemble_scores` rescales its sums (`OrderScores.scaled`).
+    With `quantile_fields=True` every field is un-normalised like a prediction (last input frame added back for residual
+    variables).  That is valid because the member-to-physical map x -> a x + b(point) has a > 0 and a b that is the same
+    for all members of a point: it is monotone, so it keeps the order of the members, and affine, so it commutes with the
+    linear interpolation between two of them -- the quantile of the mapped members is the mapped quantile."""
+    given = (targets, inputs, forcings)
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    tds = datasets.as_dataset(targets)
+    scale = []
+    for name, _, _ in datasets.channel_layout(tds):
+      stat = self._residual_scales if name in raw else self._scales
+      scale.append(_per_channel_stat(stat, name, tds[name], 1.0))
+    out = self.predictor.ensemble_order(ni, nt, forcings=nf, **kwargs)
+    if not isinstance(out, tuple):
+      return out.scaled(np.concatenate(scale))
+    fields = []
+    for f in out[1]:
+      f = datasets.as_dataset(f)
+      fields.append(datasets.like_inputs(Dataset({k: self._unnormalize_prediction_and_add_input(raw, k, v)
+                                                  for k, v in f.items()}, f.coords), *given))
+    return out[0].scaled(np.concatenate(scale)), fields
+
   def ensemble_events(self, inputs, targets, forcings=None, *, spec, **kwargs):
     """`ensemble_events` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.
     The thresholds of `spec` (physical units) go through the SAME map as the targets
@@ -572,22 +596,35 @@ class DerivedRolloutResult:
   `scores[k]` (`verification.EnsembleScores` in the units of the derived variables: `scores_normalized[k].scaled(scale_d)`
   with `DerivedSpec.channel_stats`), `scores_normalized[k]` (as the device returned them), `events[k]`
   (`verification.EventScores`, or None without an EventSpec) and `members[k]` (`[M]` arrays [G, B, c_d] in the members' own
-  units, or None); `template`: the Dataset of the derived variables (`DerivedSpec.template`) for `per_variable`."""
+  units, or None); `template`: the Dataset of the derived variables (`DerivedSpec.template`) for `per_variable`.  With
+  `run(order=...)` also `order[k]` / `order_normalized[k]` (`verification.OrderScores`, as `scores`) and, when asked for,
+  `quantiles[k]` (`[Q]` arrays [G, B, c_d] in the members' own units)."""
 
-  def __init__(self, scores, scores_normalized, events=None, members=None, template=None):
+  def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, order=None,
+               order_normalized=None, quantiles=None):
     self.scores, self.scores_normalized = list(scores), list(scores_normalized)
     self.events = None if events is None else list(events)
     self.members, self.template = members, template
+    self.order = None if order is None else list(order)
+    self.order_normalized = None if order_normalized is None else list(order_normalized)
+    self.quantiles = quantiles
 
   def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
     from . import verification  # pylint: disable=import-outside-toplevel
     if (self.events is None) != (other.events is None):
       raise ValueError("merge: only one of the two derived results carries events")
-    S, E = verification.EnsembleScores, verification.EventScores
+    if (self.order is None) != (other.order is None):
+      raise ValueError("merge: only one of the two derived results carries order statistics")
+    S, E, O = verification.EnsembleScores, verification.EventScores, verification.OrderScores
+
+    def both(a, b):
+      return None if a is None or b is None else [O.merge([x, y]) for x, y in zip(a, b)]
+
     return DerivedRolloutResult([S.merge([a, b]) for a, b in zip(self.scores, other.scores)],
                                 [S.merge([a, b]) for a, b in zip(self.scores_normalized, other.scores_normalized)],
                                 None if self.events is None else [E.merge([a, b]) for a, b in zip(self.events, other.events)],
-                                template=self.template)
+                                template=self.template, order=both(self.order, other.order),
+                                order_normalized=both(self.order_normalized, other.order_normalized))
 
 
 class EnsembleRolloutResult:
@@ -598,11 +635,19 @@ class EnsembleRolloutResult:
   `scores_normalized` / `spectra_normalized`: the same lists as the device returned them, in the members' units
   (`scores[k]` is `scores_normalized[k].scaled(s)`).  `events`: one `verification.EventScores` per lead time, or None
   (integer tables: no unit, nothing to rescale).  `derived`: {name: `DerivedRolloutResult`} for the entries of
-  `run(derived=...)`, or None."""
+  `run(derived=...)`, or None.  `order` / `order_normalized`: one `verification.OrderScores` per lead time (as `scores` /
+  `scores_normalized`), or None; `quantiles`: `[horizon][Q]` arrays [G, B, c_out] in the members' own units (as `members`),
+  or None."""
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
-               scores_normalized=None, spectra_normalized=None, events=None, derived=None):
+               scores_normalized=None, spectra_normalized=None, events=None, derived=None, order=None,
+               order_normalized=None, quantiles=None):
     self.scores = list(scores)
+    self.order = None if order is None else list(order)
+    self.order_normalized = None if order_normalized is None else list(order_normalized)
+    self.quantiles = quantiles
+    if self.order is not None and len(self.order) != len(self.scores):
+      raise ValueError("scores and order statistics must cover the same lead times")
     self.derived = None if derived is None else dict(derived)
     self.events = None if events is None else list(events)
     if self.events is not None and len(self.events) != len(self.scores):
@@ -621,7 +666,8 @@ class EnsembleRolloutResult:
 
   def merge(self, other: "EnsembleRolloutResult") -> "EnsembleRolloutResult":
     """The result over the union of the start dates, lead time by lead time (`EnsembleScores.merge`,
-    `EnsembleSpectra.merge`: raw sums add).  Fields and members belong to one date and are dropped."""
+    `EnsembleSpectra.merge`, `OrderScores.merge`: raw sums add).  Fields, members and quantile fields belong to one date
+    and are dropped."""
     from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
     if other.horizon != self.horizon:
       raise ValueError(f"merge: horizons differ ({self.horizon} and {other.horizon})")
@@ -631,6 +677,8 @@ class EnsembleRolloutResult:
       raise ValueError("merge: only one of the two results carries spectra")
     if (self.events is None) != (other.events is None):
       raise ValueError("merge: only one of the two results carries events")
+    if (self.order is None) != (other.order is None):
+      raise ValueError("merge: only one of the two results carries order statistics")
     if (self.derived is None) != (other.derived is None):
       raise ValueError("merge: only one of the two results carries derived scores")
     if self.derived is not None and sorted(self.derived) != sorted(other.derived):
@@ -645,7 +693,9 @@ class EnsembleRolloutResult:
                                  n_members=self.n_members,
                                  scores_normalized=both(S, self.scores_normalized, other.scores_normalized),
                                  spectra_normalized=both(P, self.spectra_normalized, other.spectra_normalized),
-                                 events=both(verification.EventScores, self.events, other.events), derived=derived)
+                                 events=both(verification.EventScores, self.events, other.events), derived=derived,
+                                 order=both(verification.OrderScores, self.order, other.order),
+                                 order_normalized=both(verification.OrderScores, self.order_normalized, other.order_normalized))
 
 
 class _DerivedView:
@@ -657,9 +707,12 @@ class _DerivedView:
     self.scores, self.raw = [], []
     self.events = None if store.events is None else []
     self.members = [] if keep_members else None
+    self.order, self.raw_order = ([], []) if store.order is not None else (None, None)
+    self.quantiles = None
 
   def result(self) -> DerivedRolloutResult:
-    return DerivedRolloutResult(self.scores, self.raw, self.events, self.members, self.template)
+    return DerivedRolloutResult(self.scores, self.raw, self.events, self.members, self.template, order=self.order,
+                                order_normalized=self.raw_order, quantiles=self.quantiles)
 
 
 class _EnsembleRun:
@@ -720,7 +773,8 @@ class EnsembleRollout:
 
   def run(self, inputs, targets, forcings, horizon: int, num_members: int, *, context_steps: int = 2,
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
-          keep_members: bool = False, events=None, derived=None) -> EnsembleRolloutResult:
+          keep_members: bool = False, events=None, derived=None, order=None,
+          keep_quantiles: bool = False) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -735,6 +789,11 @@ class EnsembleRollout:
     same node weights: `EnsembleRolloutResult.derived[name]`.  The thresholds of such an EventSpec are keyed by the derived
     names, in physical units, and take the map of `DerivedSpec.channel_stats`.  With `keep_members` the derived members
     are downloaded too.
+    `order`: probabilities (at most 8; an empty sequence: none): per lead time, after the scores, the member states are
+    sorted point by point on the device (`gc_ens_order_score`, on the truth already there): `EnsembleRolloutResult.order`
+    (`verification.OrderScores`: the reliability / potential split of the ensemble CRPS, pinball loss and coverage of the
+    quantiles), and the same for every `derived` entry on its derived members.  `keep_quantiles`: also the quantile
+    fields, downloaded, in the members' units (`EnsembleRolloutResult.quantiles`).  Without `order` nothing changes.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -756,7 +815,7 @@ class EnsembleRollout:
     if init_noise is not None and (len(init_noise) != M or any(len(z) < horizon for z in init_noise)):
       raise ValueError("init_noise must be [num_members][horizon] fields")
     run = self._setup(inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields,
-                      keep_members, events, derived)
+                      keep_members, events, derived, order, keep_quantiles)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -766,10 +825,11 @@ class EnsembleRollout:
     return EnsembleRolloutResult(run.scores, run.spectra, _on_time_axis(run.means, given, horizon) if fields else None,
                                  _on_time_axis(run.variances, given, horizon) if fields else None, run.members, M,
                                  scores_normalized=run.raw_scores, spectra_normalized=run.raw_spectra, events=run.events,
-                                 derived=None if derived is None else {k: v.result() for k, v in run.views.items()})
+                                 derived=None if derived is None else {k: v.result() for k, v in run.views.items()},
+                                 order=run.order, order_normalized=run.raw_order, quantiles=run.quantiles)
 
   def _setup(self, inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields, keep_members,
-             events, derived) -> "_EnsembleRun":
+             events, derived, order=None, keep_quantiles=False) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views."""
     from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
     run = _EnsembleRun()
@@ -821,7 +881,7 @@ class EnsembleRollout:
     # one spec: uploaded once, it survives the store and every lead time; else the one of the lead, before it is scored
     run.main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
                                         thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
-                                        set_per_score=specs is not None and len(specs) > 1)
+                                        set_per_score=specs is not None and len(specs) > 1, order=order)
     run.main.reserve()
     if spectra:
       _spectra.ensure_tables(native, template0, lmax)
@@ -853,6 +913,8 @@ class EnsembleRollout:
     run.spectra, run.raw_spectra = ([], []) if spectra else (None, None)
     run.members = [] if keep_members else None
     run.events = None if specs is None else []
+    run.order, run.raw_order = ([], []) if order is not None else (None, None)
+    run.quantiles = [] if order is not None and keep_quantiles else None
     if not run.main.set_per_score:
       run.main.configure()
 
@@ -862,8 +924,10 @@ class EnsembleRollout:
       dscale, dloc = dspec.channel_stats(template0, scale, loc)
       store = verification.ScoredStore(den.view_handle(len(dplan["op"])), M, weights, events=dev,
                                        thresholds=None if dev is None else packed(dev, dtemplate, dscale, dloc), weight_q=wq,
-                                       plan=dplan, source=native)
+                                       plan=dplan, source=native, order=order)
       run.views[name] = _DerivedView(store, dscale, dtemplate, keep_members)
+      if run.quantiles is not None:
+        run.views[name].quantiles = []
     for store in (v.store for v in run.views.values()):
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
       store.set_per_score = sum(1 for v in run.views.values() if v.store.handle is store.handle) > 1
@@ -923,6 +987,11 @@ class EnsembleRollout:
     if run.want_spectra:
       run.raw_spectra.append(_spectra.EnsembleSpectra(native.ens_spectrum(None), M))   # the truth is on the device already
       run.spectra.append(run.raw_spectra[-1].scaled(scale))
+    if run.order is not None:
+      run.raw_order.append(run.main.score_order(None))    # (the truth is on the device already)
+      run.order.append(run.raw_order[-1].scaled(scale))
+      if run.quantiles is not None:
+        run.quantiles.append(run.main.quantile_fields())
     if run.members is not None:
       run.members.append([native.ens_download_member(m) for m in range(M)])
     for v in run.views.values():
@@ -931,5 +1000,10 @@ class EnsembleRollout:
       v.scores.append(raw.scaled(v.scale))
       if ev is not None:
         v.events.append(ev)
+      if v.order is not None:
+        v.raw_order.append(v.store.score_order(None))
+        v.order.append(v.raw_order[-1].scaled(v.scale))
+        if v.quantiles is not None:
+          v.quantiles.append(v.store.quantile_fields())
       if v.members is not None:
         v.members.append([v.store.handle.ens_download_member(m) for m in range(M)])

@@ -25,6 +25,11 @@ Derived fields (`gc_ens_derive`): `DerivedSpec` names vari
 the norm of two components, in physical units) and one spatial pooling (max, min or area-weighted mean over a neighbourhood
 of fixed great-circle radius); the device forms them from a member store into the store of a second handle, where every
 scorer above works unchanged.
+
+Order statistics (`gc_ens_order_score`): the device sorts the M members of every point and hands back,
+per (batch, channel), the bin sums `bins[k] = (sum w alpha_k, sum w beta_k)` of Hersbach's (2000) decomposition of the
+ensemble CRPS, the outlier weights, and for Q probabilities the pinball-loss sums and below-quantile counts of the quantile
+fields it leaves on the device.  `OrderScores` keeps them raw and derives reliability and potential CRPS.
 """
 from __future__ import annotations
 
@@ -148,6 +153,158 @@ def node_weights(template) -> np.ndarray:
   if "lat" not in sizes or "lon" not in sizes:
     raise ValueError("template must have 'lat' and 'lon' dimensions")
   return np.repeat(losses.normalized_latitude_weights(template), sizes["lon"]).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------
+# order statistics: quantiles and the reliability / potential split of the CRPS (gc_ens_order_*)
+# ---------------------------------------------------------------------------------------------
+class OrderScores:
+  """The raw sums of `gc_ens_order_score`: `bins` [B, c_out, M + 1, 2] float64 (A_k = sum w alpha_k, B_k = sum w beta_k),
+  `extra` [B, c_out, 3] (S0 = sum w, O_lo = sum w [y < x_(1)], O_hi = sum w [y > x_(M)]), `pinball` [B, c_out, Q],
+  `counts` [B, c_out, Q + 1] uint64 (points with y < Q_q; last: the counted points), with the member count M and the
+  probabilities [Q].  With p_k = k / M (Hersbach 2000):
+
+    g_k = (A_k + B_k) / S0,  o_k = B_k / (A_k + B_k)                 0 < k < M
+    o_0 = O_lo / S0,  g_0 = B_0 / O_lo;    o_M = 1 - O_hi / S0,  g_M = A_M / O_hi        (a zero denominator: g = 0)
+    reliability = sum g_k (o_k - p_k)^2      crps_potential = sum g_k o_k (1 - o_k)
+    crps_ensemble = sum (A_k p_k^2 + B_k (1 - p_k)^2) / S0 = reliability + crps_potential
+
+  `crps_ensemble` is `EnsembleScores.crps_ensemble` of the same store.  Hersbach's further split of the potential CRPS into
+  uncertainty and resolution needs the climatological distribution of the observations, which is not additive over dates:
+  it is not formed here."""
+
+  def __init__(self, bins, extra, pinball, counts, n_members: int, probs):
+    self.bins = np.asarray(bins, dtype=np.float64)
+    self.extra = np.asarray(extra, dtype=np.float64)
+    self.n_members = int(n_members)
+    self.probs = tuple(float(p) for p in np.asarray([] if probs is None else probs, dtype=np.float64).reshape(-1))
+    if self.n_members < 2:
+      raise ValueError("n_members must be >= 2")
+    if self.bins.ndim != 4 or self.bins.shape[-2:] != (self.n_members + 1, 2):
+      raise ValueError(f"bins must be [batch, channels, {self.n_members + 1}, 2], got {self.bins.shape}")
+    lead, nq = self.bins.shape[:2], len(self.probs)
+    if self.extra.shape != lead + (3,):
+      raise ValueError(f"extra must be {lead + (3,)}, got {self.extra.shape}")
+    self.pinball = np.asarray(pinball, dtype=np.float64).reshape(lead + (nq,)) if nq == 0 else np.asarray(pinball, dtype=np.float64)
+    self.counts = np.asarray(counts, dtype=np.uint64)
+    if self.pinball.shape != lead + (nq,):
+      raise ValueError(f"pinball must be {lead + (nq,)}, got {self.pinball.shape}")
+    if self.counts.shape != lead + (nq + 1,):
+      raise ValueError(f"counts must be {lead + (nq + 1,)}, got {self.counts.shape}")
+
+  @staticmethod
+  def _ratio0(a, b) -> np.ndarray:
+    """a / b, zero where b is zero."""
+    a, b = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64))
+    out = np.zeros(a.shape)
+    np.divide(a, b, out=out, where=b != 0.0)
+    return out
+
+  @property
+  def _p(self) -> np.ndarray:
+    return np.arange(self.n_members + 1, dtype=np.float64) / float(self.n_members)
+
+  @property
+  def valid_weight(self) -> np.ndarray:
+    """S0: the node weight of the points that counted, per (batch, channel)."""
+    return self.extra[..., 0]
+
+  @property
+  def valid_points(self) -> np.ndarray:
+    return self.counts[..., -1]
+
+  @property
+  def outlier_low(self) -> np.ndarray:
+    """The weighted frequency of a truth below every member."""
+    return self.extra[..., 1] / self.extra[..., 0]
+
+  @property
+  def outlier_high(self) -> np.ndarray:
+    return self.extra[..., 2] / self.extra[..., 0]
+
+  @property
+  def bin_width(self) -> np.ndarray:
+    """g_k [B, c_out, M + 1]: the mean width of bin k (for the two end bins: the mean distance of an outlier)."""
+    a, b = self.bins[..., 0], self.bins[..., 1]
+    g = (a + b) / self.extra[..., 0:1]
+    g[..., 0] = self._ratio0(b[..., 0], self.extra[..., 1])
+    g[..., -1] = self._ratio0(a[..., -1], self.extra[..., 2])
+    return g
+
+  @property
+  def bin_frequency(self) -> np.ndarray:
+    """o_k [B, c_out, M + 1]: how often the truth lay below the middle of bin k -- p_k = k / M for a reliable ensemble."""
+    a, b = self.bins[..., 0], self.bins[..., 1]
+    o = self._ratio0(b, a + b)
+    o[..., 0] = self.extra[..., 1] / self.extra[..., 0]
+    o[..., -1] = 1.0 - self.extra[..., 2] / self.extra[..., 0]
+    return o
+
+  @property
+  def reliability(self) -> np.ndarray:
+    return (self.bin_width * (self.bin_frequency - self._p) ** 2).sum(axis=-1)
+
+  @property
+  def crps_potential(self) -> np.ndarray:
+    o = self.bin_frequency
+    return (self.bin_width * o * (1.0 - o)).sum(axis=-1)
+
+  @property
+  def crps_ensemble(self) -> np.ndarray:
+    """The CRPS of the M-member empirical distribution, from the bin sums: reliability + crps_potential."""
+    p = self._p
+    return (self.bins[..., 0] * p ** 2 + self.bins[..., 1] * (1.0 - p) ** 2).sum(axis=-1) / self.extra[..., 0]
+
+  @property
+  def quantile_score(self) -> np.ndarray:
+    """[B, c_out, Q]: the mean pinball loss of quantile field q."""
+    return self.pinball / self.extra[..., 0:1]
+
+  @property
+  def quantile_coverage(self) -> np.ndarray:
+    """[B, c_out, Q]: the fraction of counted points with the truth below quantile field q (p_q when reliable)."""
+    return self.counts[..., :-1].astype(np.float64) / self.counts[..., -1:].astype(np.float64)
+
+  def scaled(self, channel_scale) -> "OrderScores":
+    """The scores of a x + b in place of x (members and truth alike), a = channel_scale [c_out] > 0, any b: the bin sums and
+    the pinball sums scale with a; weights and counts do not change.  (a < 0 would reverse the order of the members.)"""
+    a = np.asarray(channel_scale, dtype=np.float64).reshape(-1)
+    if a.shape != (self.bins.shape[1],):
+      raise ValueError(f"channel_scale must have shape ({self.bins.shape[1]},)")
+    if not np.all(np.isfinite(a) & (a > 0.0)):
+      raise ValueError("channel_scale must be finite and > 0")
+    return OrderScores(self.bins * a[None, :, None, None], self.extra, self.pinball * a[None, :, None], self.counts,
+                       self.n_members, self.probs)
+
+  @staticmethod
+  def merge(parts: Sequence["OrderScores"]) -> "OrderScores":
+    """Scores over the union of what the parts covered (other nodes, other dates): raw sums and counts add."""
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    for p in parts[1:]:
+      if p.n_members != first.n_members or p.probs != first.probs or p.bins.shape != first.bins.shape:
+        raise ValueError("merge: the parts differ in members, probabilities or shape")
+    bins, extra, pinball, counts = first.bins.copy(), first.extra.copy(), first.pinball.copy(), first.counts.copy()
+    for p in parts[1:]:
+      bins += p.bins
+      extra += p.extra
+      pinball += p.pinball
+      counts += p.counts
+    return OrderScores(bins, extra, pinball, counts, first.n_members, first.probs)
+
+  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
+    """{score: {variable: [batch, channels of the variable, ...]}} in the channel order of `datasets.channel_layout`."""
+    layout = datasets.channel_layout(datasets.as_dataset(template))
+    if sum(n for _, _, n in layout) != self.bins.shape[1]:
+      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.bins.shape[1]}")
+    out: Dict[str, Dict[str, np.ndarray]] = {}
+    for score in ("crps_ensemble", "reliability", "crps_potential", "outlier_low", "outlier_high", "bin_width", "bin_frequency",
+                  "quantile_score", "quantile_coverage", "valid_weight", "valid_points"):
+      values = getattr(self, score)
+      out[score] = {name: values[:, off:off + n] for name, off, n in layout}
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -596,14 +753,16 @@ class ScoredStore:
   """The member store of one handle and everything that is scored from it: the M members it holds, the node weights
   (None: `ens_score` is not used on it), optionally the events counted on it -- an `EventSpec`, its packed `thresholds`
   in the members' units and `weight_q` = `quantize_node_weights(...)` -- and optionally the `plan` (`DerivedSpec.plan`) that
-  fills it from the store of a `source` handle (`ens_derive`).  `EnsembleSampler` and `EnsembleRollout` use one for the
-  main store and one per derived view.
+  fills it from the store of a `source` handle (`ens_derive`), and optionally `order`: the probabilities of the quantile
+  fields `score_order` leaves on the device next to its `OrderScores`.  `EnsembleSampler` and `EnsembleRollout` use one for
+  the main store and one per derived view.
 
   `set_per_score`: the plan and the thresholds are not set once by `setup` but by every `score` -- two stores that share
   a handle, or thresholds that change from call to call (assign `thresholds` before the call)."""
 
   def __init__(self, handle, n_members: int, node_weight=None, *, events: Optional["EventSpec"] = None, thresholds=None,
-               weight_q: Optional[Tuple[np.ndarray, float]] = None, plan=None, source=None, set_per_score: bool = False):
+               weight_q: Optional[Tuple[np.ndarray, float]] = None, plan=None, source=None, set_per_score: bool = False,
+               order=None):
     if events is not None and weight_q is None:
       raise ValueError("events need the quantised node weights (quantize_node_weights)")
     if (plan is None) != (source is None):
@@ -611,6 +770,7 @@ class ScoredStore:
     self.handle, self.n_members, self.node_weight = handle, int(n_members), node_weight
     self.events, self.thresholds, self.weight_q = events, thresholds, weight_q
     self.plan, self.source, self.set_per_score = plan, source, bool(set_per_score)
+    self.order = None if order is None else tuple(float(p) for p in np.asarray(order, dtype=np.float64).reshape(-1))
 
   def reserve(self) -> None:
     self.handle.ens_reserve(self.n_members)
@@ -625,10 +785,15 @@ class ScoredStore:
     if self.events is not None:
       self.handle.ens_event_set(self.thresholds, self.events.directions, self.weight_q[0])
 
+  def _set_order(self) -> None:
+    if self.order is not None:
+      self.handle.ens_order_set(self.order)
+
   def configure(self) -> None:
-    """The plan and the thresholds: both survive `ens_reserve` and every score."""
+    """The plan, the thresholds and the probabilities: all survive `ens_reserve` and every score."""
     self._set_plan()
     self._set_events()
+    self._set_order()
 
   def setup(self) -> None:
     self.reserve()
@@ -643,6 +808,21 @@ class ScoredStore:
       self._set_events()
     weighted, counts, invalid = self.handle.ens_event_score(truth)
     return EventScores(weighted, counts, self.n_members, self.events.directions, self.weight_q[1], invalid)
+
+  def score_order(self, truth=None) -> Optional["OrderScores"]:
+    """The order statistics of the store (None without `order`); `truth` None: the truth already on the device.  On a
+    derived view (a store with a plan) the DERIVED members are scored: call it after `score`, which fills the view, and
+    leave `truth` None."""
+    if self.order is None:
+      return None
+    if self.set_per_score:
+      self._set_order()
+    bins, extra, pinball, counts, _ = self.handle.ens_order_score(truth)
+    return OrderScores(bins, extra, pinball, counts, self.n_members, self.order)
+
+  def quantile_fields(self) -> List[np.ndarray]:
+    """The Q quantile fields [G, B, c_out] of the last `score_order`, downloaded."""
+    return [self.handle.ens_order_quantile(q) for q in range(len(self.order or ()))]
 
   def score(self, truth=None, want_fields: bool = False) -> Tuple[EnsembleScores, Optional["EventScores"]]:
     """-> (raw `EnsembleScores`, `EventScores` or None).  `truth` [G, B, c_out] in the members' units, None: the truth

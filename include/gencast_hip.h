@@ -576,6 +576,60 @@ int gc_ens_derive_set(gc_handle* dst, int32_t c_src, const int32_t* op, const in
 int gc_ens_derive(gc_handle* dst, gc_handle* src, const float* truth /* [G,B,c_src] host, NULL = src's last truth */);
 
 /*
+ * Ensemble order statistics on the device: the M members of every point of the gc_ens_* store in
+ * ascending order, and what follows from that order -- quantile fields (the median, a p10 / p90 band) and the bin sums of
+ * Hersbach's (2000) decomposition of the ensemble CRPS into a reliability and a potential part (gencast-flax-nnx_amd/
+ * verification.py OrderScores).  The reference project has no verification code; the yardstick is the definition below,
+ * restated in float64 in tests/order_reference.py.
+ * Members x_0 .. x_{M-1} (2 <= M <= 64) and the truth y are [G, B, c_out] float32, w [G] the node weights of
+ * gc_ens_set_node_weight; per point x_(1) <= .. <= x_(M) are the member values in ascending order.  A point is member-valid
+ * when all M members are finite, and counted when it is member-valid and y is finite (the rule of gc_ens_score).
+ * Quantile fields, for Q probabilities p_q in [0, 1] (0 <= Q <= 8): the HOST forms h = p_q (M - 1), lo = min(floor(h), M - 1),
+ * hi = min(lo + 1, M - 1), f = h - lo in double, per call from the current M, and the device computes at a member-valid point
+ *   Q_q = (float)((double)x_(lo+1) + f ((double)x_(hi+1) - (double)x_(lo+1)))       no fused multiply-add; NaN elsewhere
+ * -- NumPy's "linear" rule; p = 0 and p = 1 give the minimum and the maximum bit for bit.
+ * Bin terms per counted point, in double (differences of float32 values are formed in double):
+ *   0 < k < M:  c = min(max(y, x_(k)), x_(k+1)),  alpha_k = c - x_(k),  beta_k = x_(k+1) - c
+ *   alpha_0 = 0,  beta_0 = max(x_(1) - y, 0);     alpha_M = max(y - x_(M), 0),  beta_M = 0
+ * Per column (b, c), over the counted nodes g:
+ *   bins[b][c][k] = (sum w alpha_k, sum w beta_k)       extra[b][c] = (sum w, sum w [y < x_(1)], sum w [y > x_(M)])
+ *   pinball[b][c][q] = sum w u (p_q - [u < 0]),  u = (double)y - (double)Q_q (the stored float32 field value)
+ *   counts[b][c][q] = #{y < Q_q} for q < Q,  counts[b][c][Q] = counted points          invalid = points not counted
+ * Every term is formed and added in double; every partial sum has one writer and the order of addition is fixed (no atomics
+ * on floats), so the same call twice returns identical bytes.  All outputs are raw and additive over batches and dates.
+ * Hersbach's uncertainty and resolution need the climatological distribution of the observations, which is not additive
+ * over dates: they are not formed here.
+ *   gc_ens_order_set       the probabilities.  Needs gc_set_graph only; survives gc_ens_reserve (they do not depend on M);
+ *                          replaces an earlier setting ("device_allocations" stays flat); released by gc_destroy.
+ *                          GC_ERR_UNSUPPORTED: Q outside 0..8.  GC_ERR_INVALID_ARGUMENT: a probability that is NaN or
+ *                          outside [0, 1]; probs NULL with Q > 0.
+ *   gc_ens_order_score     truth: host [G, B, c_out], uploaded and kept, or NULL = the truth uploaded last (the buffer
+ *                          gc_ens_score, gc_ens_spectrum and gc_ens_event_score use).  bins [B][c_out][M + 1][2] and extra
+ *                          [B][c_out][3] are required; pinball [B][c_out][Q], counts [B][c_out][Q + 1] and invalid [1] may
+ *                          be NULL.  Also leaves the Q quantile fields on the device.  Two launches: a pass that reads the
+ *                          M members of a point once and sorts them in registers with a bitonic network, and a finish that
+ *                          adds the per-block partials in block order.  Synchronous.
+ *                          GC_ERR_STATE: no gc_ens_order_set, no member store, a slot not pushed since gc_ens_reserve, no
+ *                          node weights, no truth.
+ *   gc_ens_order_fields    the quantile fields only: the same pass without its truth-dependent half.  Needs neither
+ *                          weights nor truth.  Synchronous.
+ *   gc_ens_order_download  quantile field q [G, B, c_out] of the last order call.  GC_ERR_STATE: none ran since
+ *                          gc_ens_order_set / gc_ens_reserve (/ gc_ens_derive into this handle).
+ *                          GC_ERR_INVALID_ARGUMENT: q outside [0, Q).
+ * None of these entries touches the conditioning, the last sample, the stash, the loss, spectrum, event or derive buffers,
+ * the member store's contents, the mean and variance fields or the captured sample graphs.  Counters: "ens_order_calls"
+ * (calls so far), "ens_order_device_us" (HIP-event time of the last call's launches), "ens_order_invalid_points" (of the
+ * last scoring call).
+ */
+int gc_ens_order_set(gc_handle* h, int32_t n_quantiles, const double* probs /* [Q], NULL when Q = 0 */);
+int gc_ens_order_score(gc_handle* h, const float* truth /* NULL = the truth uploaded last */,
+                       double* bins /* [B][c_out][M+1][2] */, double* extra /* [B][c_out][3] */,
+                       double* pinball /* [B][c_out][Q], NULL allowed */, uint64_t* counts /* [B][c_out][Q+1], NULL allowed */,
+                       uint64_t* invalid /* [1], NULL allowed */);
+int gc_ens_order_fields(gc_handle* h);                    /* quantile fields only: no truth read, no sums */
+int gc_ens_order_download(gc_handle* h, int32_t q, float* field /* [G,B,c_out] */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
