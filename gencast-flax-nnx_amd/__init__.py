@@ -19,6 +19,8 @@ Public surface (mirrors the reference's call contracts):
                       (GenCast.ensemble_derived, EnsembleRollout.run(derived=...))
                       OrderScores: quantile fields and the reliability / potential split of the CRPS from members sorted
                       on the GPU (GenCast.ensemble_order, EnsembleRollout.run(order=...))
+                      ClimatologyScores: anomaly correlation and CRPS skill score of an ensemble against K climatological
+                      samples held by a second handle (GenCast.ensemble_climatology, EnsembleRollout.run(climatology=...))
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
@@ -36,11 +38,11 @@ from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, Ense
                       autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
-from .verification import DerivedSpec, EnsembleScores, EventScores, EventSpec, OrderScores  # noqa: F401
+from .verification import ClimatologyScores, DerivedSpec, EnsembleScores, EventScores, EventSpec, OrderScores  # noqa: F401
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
            "InputsAndResiduals", "autoregressive_rollout", "DeviceRollout", "NaNCleaner", "launch", "losses",
            "compute_loss", "validation_loss", "verification", "EnsembleScores", "spectra", "EnsembleSpectra",
            "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec",
-           "DerivedSpec", "DerivedRolloutResult", "OrderScores"]
+           "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores"]

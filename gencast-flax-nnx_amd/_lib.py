@@ -129,6 +129,8 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_uint64)]),
     "gc_ens_order_fields": (ctypes.c_int, [_hp]),
     "gc_ens_order_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
+    "gc_ens_clim_score": (ctypes.c_int, [_hp, _hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
+                                         ctypes.POINTER(ctypes.c_uint64)]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -752,6 +754,33 @@ class NativeDenoiser:
     out = np.empty(self._shape_out(), dtype=np.float32)
     self._check(self._lib.gc_ens_order_download(self._h, int(q), _ptr(out, _f32p)))
     return out
+
+  # -- an ensemble against a climatology (two member stores, one pass) -----------------------------------
+  def ens_clim_score(self, clim: "NativeDenoiser", truth=None):
+    """-> (sums [B, c_out, 12] float64, counts [B, c_out] uint64, invalid int): the raw, additive sums of
+    gc_ens_clim_score over this handle's member store and the K climatological samples in the store of `clim`, another
+    handle with the same graph, batch and c_out (`Denoiser.climatology_handle`; filled with `ens_reserve(K)` and
+    `ens_push_host`).  `verification.ClimatologyScores` derives ACC, CRPSS and the rest.  `truth` [G, B, c_out], or None =
+    the truth uploaded last (shared with `ens_score`)."""
+    if not isinstance(clim, NativeDenoiser):
+      raise TypeError("clim must be a NativeDenoiser")
+    if clim is self:
+      raise ValueError("the climatology must be another handle")
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    t = None
+    if truth is not None:
+      t = _f32(truth)
+      if t.shape != self._shape_out():
+        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    B, C = self.cfg.batch, self.cfg.c_out
+    sums = np.empty((B, C, 12), dtype=np.float64)
+    counts = np.empty((B, C), dtype=np.uint64)
+    invalid = np.zeros(1, dtype=np.uint64)
+    u64 = ctypes.POINTER(ctypes.c_uint64)
+    self._check(self._lib.gc_ens_clim_score(self._h, clim._h, None if t is None else _ptr(t, _f32p),  # pylint: disable=protected-access
+                                            _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(counts, u64), _ptr(invalid, u64)))
+    return sums, counts, int(invalid[0])
 
   # -- context store: one resident conditioning per ensemble member ----------------------------------
   def ctx_reserve(self, n: int) -> None:

@@ -876,6 +876,9 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "ens_order_calls") *value = h->ord_calls;
   else if (n == "ens_order_device_us") *value = h->ord_device_us;
   else if (n == "ens_order_invalid_points") *value = h->ord_invalid_points;
+  else if (n == "ens_clim_calls") *value = h->clim_calls;
+  else if (n == "ens_clim_device_us") *value = h->clim_device_us;
+  else if (n == "ens_clim_invalid_points") *value = h->clim_invalid_points;
   else if (n == "noise_stream") *value = (int64_t)h->nz_stream;
   else if (n == "device_allocations") {
     *value = 0;

@@ -9,7 +9,8 @@
 //   gc_events.hip    gc_ens_event_*
 //   gc_derive.hip    gc_ens_derive_*
 //   gc_order.hip     gc_ens_order_*
-// The last five are scorers over the member store of gc_ens_reserve.  What they share -- field length, upload through
+//   gc_clim.hip      gc_ens_clim_score
+// The last six are scorers over the member store of gc_ens_reserve.  What they share -- field length, upload through
 // the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
 // relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
 // are a BufferGroup and its events an Event or a Bracket (below); declaring one as a member of the handle is all it takes
@@ -350,6 +351,16 @@ struct gc_handle {
   bool ord_ready = false;                        // an order call ran since gc_ens_order_set / gc_ens_reserve / gc_ens_derive
   gci::Bracket ord_time{events};                 // of the last call
   int64_t ord_calls = 0, ord_device_us = 0, ord_invalid_points = 0;
+
+  // an ensemble against a climatology (gc_ens_clim_score, gc_clim.hip): the sums of a pass over this handle's store and another's
+  gci::BufferGroup clim_allocs{groups};           // sized by G, B and c_out alone: made by the first call, kept
+  double* d_clim_part = nullptr;                 // [blocks][12][B c_out] per-block column sums
+  unsigned* d_clim_cpart = nullptr;              // [blocks][B c_out] per-block counted points, then [blocks][tiles] skipped points
+  double* d_clim_out = nullptr;                  // [B c_out][12]
+  unsigned long long* d_clim_outc = nullptr;     // [B c_out] counted points, then the skipped points of the call
+  gci::Bracket clim_time{events};                // of the last call
+  gci::Event ev_clim_src{events};                // stream order behind the climatology handle
+  int64_t clim_calls = 0, clim_device_us = 0, clim_invalid_points = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

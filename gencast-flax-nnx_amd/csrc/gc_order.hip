@@ -13,6 +13,7 @@
 //   pinball[q] = sum w u (p_q - [u < 0]), u = y - Q_q          counts[q] = #{y < Q_q}, counts[Q] = counted points
 // No atomics on floats: every accumulator has one writer and every sum a fixed order (a thread's nodes ascending, the
 // node lanes of a column in lane order, the blocks in index order), so the same call twice returns identical bytes.
+#include "gc_sort.h"
 #include "gc_store.h"
 
 // the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
@@ -45,9 +46,6 @@ static int ord_blocks(int G, int W, int M, int Q) {
   return std::max(1, std::min({(G + 8 * q - 1) / (8 * q), 1024, 2 * kOrdCuCount * per_cu}));
 }
 
-template <int P>
-struct OrdLog { static constexpr int value = P == 2 ? 1 : P == 4 ? 2 : P == 8 ? 3 : P == 16 ? 4 : P == 32 ? 5 : 6; };
-
 // v[idx] for a wave-uniform idx in [0, P): a tree of selects on the bits of idx, lowest first, over compile-time
 // indices -- P - 1 selects on log2 P conditions, and the array stays in registers
 template <int P>
@@ -65,31 +63,6 @@ __device__ inline float ord_pick(const float (&v)[P], int idx) {
     }
   }
   return t[0];
-}
-
-// Bitonic network over P = 2^n registers, ascending: P/2 compare-exchanges per stage, n (n + 1) / 2 stages, every index
-// a compile-time constant.  No branch depends on the data.
-template <int P>
-__device__ inline void ord_sort(float (&v)[P]) {
-  constexpr int kLog = OrdLog<P>::value;
-  static_assert(P == 1 << kLog, "P is a power of two in 2..64");
-#pragma unroll
-  for (int s = 1; s <= kLog; ++s) {                // merges of runs of 2^s
-#pragma unroll
-    for (int t = s - 1; t >= 0; --t) {             // compare-exchange at distance 2^t
-#pragma unroll
-      for (int i = 0; i < P; ++i) {
-        const int l = i ^ (1 << t);
-        if (l > i) {
-          const float a = v[i], b = v[l];
-          const float lo = fminf(a, b), hi = fmaxf(a, b);
-          const bool up = (i & (1 << s)) == 0;
-          v[i] = up ? lo : hi;
-          v[l] = up ? hi : lo;
-        }
-      }
-    }
-  }
 }
 
 // The pass.  Thread layout of gc_ens_score_kernel, on column tiles of tile_w <= cap columns: inside a tile of wt columns

@@ -180,11 +180,39 @@ class Denoiser:
       views[c_d] = nd
     return nd
 
+  def climatology_handle(self, c_d: int, *, view: bool = False) -> _lib.NativeDenoiser:
+    """A graph-only handle like `view_handle`'s, kept apart from those (a view of `c_d` channels and the climatology it is
+    scored against are two stores): its member store takes the K climatological samples of `c_d` channels that
+    `NativeDenoiser.ens_clim_score` reads next to the members -- pushed with `ens_push_host`, or derived from another
+    climatology handle with `ens_derive` (`view=True`: the handle of such derived samples, apart from the plain one of the
+    same width).  One per (`c_d`, `view`), created once and kept; `close` releases them."""
+    if not self._initialized:
+      raise RuntimeError("climatology_handle: the denoiser has not been initialised by a first call / init_for")
+    c_d = int(c_d)
+    if c_d < 1:
+      raise ValueError("c_d must be positive")
+    clims = getattr(self, "_climatologies", None)
+    if clims is None:
+      clims = self._climatologies = {}
+    nd = clims.get((c_d, bool(view)))
+    if nd is None or nd.closed:
+      nd = _lib.NativeDenoiser(latent_size=128, d_model=128, num_heads=2, ffw_hidden=256, num_layers=1, c_in=c_d, c_out=c_d,
+                               batch=self._batch, device_id=self._device_id)
+      try:
+        nd.set_graph(self.graph)
+      except Exception:
+        nd.close()
+        raise
+      clims[(c_d, bool(view))] = nd
+    return nd
+
   def close(self) -> None:
-    """Releases every library handle this denoiser made: the view handles, the member lanes and `native`."""
-    for nd in list((getattr(self, "_views", None) or {}).values()) + list(getattr(self, "_lanes", None) or []):
+    """Releases every library handle this denoiser made: the view and climatology handles, the member lanes and
+    `native`."""
+    for nd in (list((getattr(self, "_views", None) or {}).values()) + list((getattr(self, "_climatologies", None) or {}).values())
+               + list(getattr(self, "_lanes", None) or [])):
       nd.close()
-    self._views, self._lanes = {}, []
+    self._views, self._climatologies, self._lanes = {}, {}, []
     if self.native is not None:
       self.native.close()
     self._initialized = False

@@ -130,6 +130,21 @@ class EnsembleSampler:
                        "ranks' members over and push them with NativeDenoiser.ens_push_host")
     return self._run(inputs, targets, forcings, num_members, None, order=(tuple(probs), bool(quantile_fields)))
 
+  def climatology(self, inputs, targets, forcings, num_members: int, climatology):
+    """Runs the members as `scores` does and scores them, on the device, against `climatology`: K (2..64) Datasets shaped
+    like `targets` -- past states for the same calendar date; a plain climatological mean is given twice.  Returns
+    `verification.ClimatologyScores` in the units of `targets`: the anomaly correlation of the ensemble mean, the CRPS
+    skill score against the climatological ensemble, the mean-square skill score.  The K fields are uploaded into the
+    store of a second handle (`Denoiser.climatology_handle`); no member is downloaded.  NaNs in `targets` or in a sample
+    are points the device does not count."""
+    if self.world_size > 1:
+      raise ValueError("EnsembleSampler.climatology needs all members on one rank (world_size == 1): bring the other "
+                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    climatology = list(climatology)
+    if not 2 <= len(climatology) <= 64:
+      raise ValueError(f"climatology must be 2..64 Datasets shaped like the targets, got {len(climatology)}")
+    return self._run(inputs, targets, forcings, num_members, None, climatology=climatology)
+
   def _spectral(self, inputs, targets, forcings, num_members, score_fields, lmax):
     if self.world_size > 1:
       raise ValueError("EnsembleSampler.spectra needs all members on one rank (world_size == 1): bring the other "
@@ -137,10 +152,11 @@ class EnsembleSampler:
     return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
 
   def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,
-           lmax: Optional[int] = None, events=None, derived=None, order=None):
+           lmax: Optional[int] = None, events=None, derived=None, order=None, climatology=None):
     """`score_fields` None: members come back as Datasets (`__call__`) or, with `spectral`, only their spectra are
     formed, or, with `events` (an EventSpec), only their event tables, or, with `order` (probabilities, want fields), only
-    their order statistics; else they are scored (`scores`), with `spectral` both."""
+    their order statistics, or, with `climatology` (K Datasets), only their skill against it; else they are scored
+    (`scores`), with `spectral` both."""
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
     cond, grid_shape, slots = self._denoiser.init_for(inputs, template, forcings)
@@ -168,14 +184,17 @@ class EnsembleSampler:
         lane.upload_cond_dev(ptr)                          # device-to-device, on the lane's own stream
     scoring = score_fields is not None
     main = None                                            # lane 0's member store, where anything is scored at all
-    if scoring or spectral or events is not None or derived is not None or order is not None:
+    if scoring or spectral or events is not None or derived is not None or order is not None or climatology is not None:
       dspec, dev = derived if derived is not None else (None, None)
       weights = None if spectral and not scoring else verification.node_weights(template)
       wq = None if events is None and dev is None else verification.quantize_node_weights(weights)
       # (scored once: the thresholds are set by that call, after the members are in)
-      main = verification.ScoredStore(native, num_members, weights if scoring or order is not None else None, events=events,
-                                      thresholds=None if events is None else events.packed(template), weight_q=wq,
-                                      set_per_score=True, order=None if order is None else order[0])
+      main = verification.ScoredStore(native, num_members,
+                                      weights if scoring or order is not None or climatology is not None else None,
+                                      events=events, thresholds=None if events is None else events.packed(template), weight_q=wq,
+                                      set_per_score=True, order=None if order is None else order[0],
+                                      climatology=None if climatology is None
+                                      else self._denoiser.climatology_handle(self._denoiser.dims.c_out))
       main.setup()
     if spectral:
       _spectra.ensure_tables(native, template, lmax)
@@ -204,6 +223,10 @@ class EnsembleSampler:
       return scores if dev is None else (scores, event_scores)
     if events is not None:
       return main.score_events(truth)
+    if climatology is not None:
+      pack = lambda ds: np.transpose(datasets.dataset_to_stacked(datasets.as_dataset(ds), template.sizes),
+                                     (1, 2, 0, 3)).reshape(shape)
+      return main.score_climatology([pack(c) for c in climatology], truth)
     if order is not None:
       scores = main.score_order(truth)
       if not order[1]:

@@ -140,6 +140,18 @@ class GenCast:
     runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
     return runner.order(inputs, targets, forcings, num_members, probs, quantile_fields=quantile_fields)
 
+  def ensemble_climatology(self, inputs, targets, forcings=None, *, num_members, climatology, rngs=0, concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and scores them on the GPU against `climatology`,
+    K (2..64) Datasets shaped like `targets` (past states for the same calendar date; a climatological mean is given
+    twice): `verification.ClimatologyScores` -- the anomaly correlation coefficient of the ensemble mean (`acc`), the CRPS
+    skill score against the climatological ensemble (`crpss`), `msss` -- per batch member and channel, latitude-weighted.
+    No member leaves the device."""
+    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
+    if not isinstance(rngs, (int, np.integer)):
+      rngs = Sampler.seed_from(rngs)
+    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    return runner.climatology(inputs, targets, forcings, num_members, climatology)
+
   def ensemble_derived(self, inputs, targets, forcings=None, *, num_members, spec, events=None, rngs=0, concurrent_members=1):
     """Samples `num_members` (2..64) members as `ensemble_scores` does and scores, on the GPU, what `spec`
     (`verification.DerivedSpec`) makes of them and of `targets`: wind speed from two components, fields max-, min- or

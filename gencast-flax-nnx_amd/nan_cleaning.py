@@ -136,6 +136,17 @@ class NaNCleaner:
       return out
     return out[0], [datasets.like_inputs(datasets.as_dataset(f), *given) for f in out[1]]
 
+  def ensemble_climatology(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """Inputs and forcings are cleaned; the targets and the climatology pass through unchanged: their NaNs are points
+    the device does not count (`ClimatologyScores.invalid`)."""
+    inputs = datasets.as_dataset(inputs)
+    forcings = None if forcings is None else datasets.as_dataset(forcings)
+    if self._var_to_clean in inputs.keys():
+      inputs = self._clean(inputs)
+    if forcings is not None and self._var_to_clean in forcings.keys():
+      forcings = self._clean(forcings)
+    return self.predictor.ensemble_climatology(inputs, datasets.as_dataset(targets), forcings, **kwargs)
+
   def ensemble_events(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """Inputs and forcings are cleaned; the targets pass through unchanged, as in `ensemble_scores`: their NaNs are
     points the device does not count (`EventScores.invalid`)."""

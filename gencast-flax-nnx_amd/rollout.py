@@ -226,6 +226,24 @@ class InputsAndResiduals:
                                                   for k, v in f.items()}, f.coords), *given))
     return out[0].scaled(np.concatenate(scale)), fields
 
+  def ensemble_climatology(self, inputs, targets, forcings=None, *, climatology, **kwargs):
+    """`ensemble_climatology` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.
+    Every climatological sample (physical units) goes through the SAME map as the targets
+    (`_subtract_input_and_normalize_target`: for a residual variable the last input frame is subtracted, per batch member),
+    so members, samples and truth differ from their physical values by one affine map x -> a x + b(point) per channel; the
+    raw sums are scaled back (`ClimatologyScores.scaled`: b drops out of every term), nothing is recomputed."""
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    tds = datasets.as_dataset(targets)
+    scale = []
+    for name, _, _ in datasets.channel_layout(tds):
+      stat = self._residual_scales if name in raw else self._scales
+      scale.append(_per_channel_stat(stat, name, tds[name], 1.0))
+    nclim = []
+    for c in climatology:
+      c = datasets.as_dataset(c)
+      nclim.append(Dataset({k: self._subtract_input_and_normalize_target(raw, k, v) for k, v in c.items()}, c.coords))
+    return self.predictor.ensemble_climatology(ni, nt, forcings=nf, climatology=nclim, **kwargs).scaled(np.concatenate(scale))
+
   def ensemble_events(self, inputs, targets, forcings=None, *, spec, **kwargs):
     """`ensemble_events` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.
     The thresholds of `spec` (physical units) go through the SAME map as the targets
@@ -598,16 +616,20 @@ class DerivedRolloutResult:
   (`verification.EventScores`, or None without an EventSpec) and `members[k]` (`[M]` arrays [G, B, c_d] in the members' own
   units, or None); `template`: the Dataset of the derived variables (`DerivedSpec.template`) for `per_variable`.  With
   `run(order=...)` also `order[k]` / `order_normalized[k]` (`verification.OrderScores`, as `scores`) and, when asked for,
-  `quantiles[k]` (`[Q]` arrays [G, B, c_d] in the members' own units)."""
+  `quantiles[k]` (`[Q]` arrays [G, B, c_d] in the members' own units).  With `run(climatology=...)` also `climatology[k]` /
+  `climatology_normalized[k]` (`verification.ClimatologyScores`, as `scores`): the derived members against the derived
+  climatological samples."""
 
   def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, order=None,
-               order_normalized=None, quantiles=None):
+               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None):
     self.scores, self.scores_normalized = list(scores), list(scores_normalized)
     self.events = None if events is None else list(events)
     self.members, self.template = members, template
     self.order = None if order is None else list(order)
     self.order_normalized = None if order_normalized is None else list(order_normalized)
     self.quantiles = quantiles
+    self.climatology = None if climatology is None else list(climatology)
+    self.climatology_normalized = None if climatology_normalized is None else list(climatology_normalized)
 
   def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
     from . import verification  # pylint: disable=import-outside-toplevel
@@ -615,16 +637,20 @@ class DerivedRolloutResult:
       raise ValueError("merge: only one of the two derived results carries events")
     if (self.order is None) != (other.order is None):
       raise ValueError("merge: only one of the two derived results carries order statistics")
-    S, E, O = verification.EnsembleScores, verification.EventScores, verification.OrderScores
+    if (self.climatology is None) != (other.climatology is None):
+      raise ValueError("merge: only one of the two derived results carries climatology scores")
+    S, E, O, C = verification.EnsembleScores, verification.EventScores, verification.OrderScores, verification.ClimatologyScores
 
-    def both(a, b):
-      return None if a is None or b is None else [O.merge([x, y]) for x, y in zip(a, b)]
+    def both(a, b, cls=O):
+      return None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
 
     return DerivedRolloutResult([S.merge([a, b]) for a, b in zip(self.scores, other.scores)],
                                 [S.merge([a, b]) for a, b in zip(self.scores_normalized, other.scores_normalized)],
                                 None if self.events is None else [E.merge([a, b]) for a, b in zip(self.events, other.events)],
                                 template=self.template, order=both(self.order, other.order),
-                                order_normalized=both(self.order_normalized, other.order_normalized))
+                                order_normalized=both(self.order_normalized, other.order_normalized),
+                                climatology=both(self.climatology, other.climatology, C),
+                                climatology_normalized=both(self.climatology_normalized, other.climatology_normalized, C))
 
 
 class EnsembleRolloutResult:
@@ -637,12 +663,17 @@ class EnsembleRolloutResult:
   (integer tables: no unit, nothing to rescale).  `derived`: {name: `DerivedRolloutResult`} for the entries of
   `run(derived=...)`, or None.  `order` / `order_normalized`: one `verification.OrderScores` per lead time (as `scores` /
   `scores_normalized`), or None; `quantiles`: `[horizon][Q]` arrays [G, B, c_out] in the members' own units (as `members`),
-  or None."""
+  or None.  `climatology` / `climatology_normalized`: one `verification.ClimatologyScores` per lead time (as `scores` /
+  `scores_normalized`) -- anomaly correlation and CRPS skill score against the samples of `run(climatology=...)` -- or None."""
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
                scores_normalized=None, spectra_normalized=None, events=None, derived=None, order=None,
-               order_normalized=None, quantiles=None):
+               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None):
     self.scores = list(scores)
+    self.climatology = None if climatology is None else list(climatology)
+    self.climatology_normalized = None if climatology_normalized is None else list(climatology_normalized)
+    if self.climatology is not None and len(self.climatology) != len(self.scores):
+      raise ValueError("scores and climatology scores must cover the same lead times")
     self.order = None if order is None else list(order)
     self.order_normalized = None if order_normalized is None else list(order_normalized)
     self.quantiles = quantiles
@@ -666,7 +697,7 @@ class EnsembleRolloutResult:
 
   def merge(self, other: "EnsembleRolloutResult") -> "EnsembleRolloutResult":
     """The result over the union of the start dates, lead time by lead time (`EnsembleScores.merge`,
-    `EnsembleSpectra.merge`, `OrderScores.merge`: raw sums add).  Fields, members and quantile fields belong to one date
+    `EnsembleSpectra.merge`, `OrderScores.merge`, `ClimatologyScores.merge`: raw sums add).  Fields, members and quantile fields belong to one date
     and are dropped."""
     from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
     if other.horizon != self.horizon:
@@ -679,6 +710,8 @@ class EnsembleRolloutResult:
       raise ValueError("merge: only one of the two results carries events")
     if (self.order is None) != (other.order is None):
       raise ValueError("merge: only one of the two results carries order statistics")
+    if (self.climatology is None) != (other.climatology is None):
+      raise ValueError("merge: only one of the two results carries climatology scores")
     if (self.derived is None) != (other.derived is None):
       raise ValueError("merge: only one of the two results carries derived scores")
     if self.derived is not None and sorted(self.derived) != sorted(other.derived):
@@ -695,7 +728,10 @@ class EnsembleRolloutResult:
                                  spectra_normalized=both(P, self.spectra_normalized, other.spectra_normalized),
                                  events=both(verification.EventScores, self.events, other.events), derived=derived,
                                  order=both(verification.OrderScores, self.order, other.order),
-                                 order_normalized=both(verification.OrderScores, self.order_normalized, other.order_normalized))
+                                 order_normalized=both(verification.OrderScores, self.order_normalized, other.order_normalized),
+                                 climatology=both(verification.ClimatologyScores, self.climatology, other.climatology),
+                                 climatology_normalized=both(verification.ClimatologyScores, self.climatology_normalized,
+                                                             other.climatology_normalized))
 
 
 class _DerivedView:
@@ -709,10 +745,12 @@ class _DerivedView:
     self.members = [] if keep_members else None
     self.order, self.raw_order = ([], []) if store.order is not None else (None, None)
     self.quantiles = None
+    self.clim, self.raw_clim = ([], []) if store.climatology is not None else (None, None)
 
   def result(self) -> DerivedRolloutResult:
     return DerivedRolloutResult(self.scores, self.raw, self.events, self.members, self.template, order=self.order,
-                                order_normalized=self.raw_order, quantiles=self.quantiles)
+                                order_normalized=self.raw_order, quantiles=self.quantiles, climatology=self.clim,
+                                climatology_normalized=self.raw_clim)
 
 
 class _EnsembleRun:
@@ -774,7 +812,7 @@ class EnsembleRollout:
   def run(self, inputs, targets, forcings, horizon: int, num_members: int, *, context_steps: int = 2,
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
           keep_members: bool = False, events=None, derived=None, order=None,
-          keep_quantiles: bool = False) -> EnsembleRolloutResult:
+          keep_quantiles: bool = False, climatology=None) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -794,6 +832,14 @@ class EnsembleRollout:
     (`verification.OrderScores`: the reliability / potential split of the ensemble CRPS, pinball loss and coverage of the
     quantiles), and the same for every `derived` entry on its derived members.  `keep_quantiles`: also the quantile
     fields, downloaded, in the members' units (`EnsembleRolloutResult.quantiles`).  Without `order` nothing changes.
+    `climatology`: a sequence of `horizon` entries, or a callable of the lead time k, giving the K (2..64) climatological
+    samples of lead k -- Datasets shaped like `targets[k]` in physical units, past states for that calendar date; a plain
+    climatological mean is given twice.  Per lead time, after the scores, they take the map of the truth, go into the store
+    of a second handle (`Denoiser.climatology_handle`) and the member states are scored against them
+    (`gc_ens_clim_score`, on the truth already there): `EnsembleRolloutResult.climatology` (`verification.ClimatologyScores`:
+    anomaly correlation of the ensemble mean, CRPS skill score).  For every `derived` entry the samples go through the
+    entry's plan as the members do (`gc_ens_derive` from the climatology handle into a climatology view) and the derived
+    members are scored against them.  A NaN in a sample is a point the device skips.  Without `climatology` nothing changes.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -815,7 +861,7 @@ class EnsembleRollout:
     if init_noise is not None and (len(init_noise) != M or any(len(z) < horizon for z in init_noise)):
       raise ValueError("init_noise must be [num_members][horizon] fields")
     run = self._setup(inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields,
-                      keep_members, events, derived, order, keep_quantiles)
+                      keep_members, events, derived, order, keep_quantiles, climatology)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -826,10 +872,11 @@ class EnsembleRollout:
                                  _on_time_axis(run.variances, given, horizon) if fields else None, run.members, M,
                                  scores_normalized=run.raw_scores, spectra_normalized=run.raw_spectra, events=run.events,
                                  derived=None if derived is None else {k: v.result() for k, v in run.views.items()},
-                                 order=run.order, order_normalized=run.raw_order, quantiles=run.quantiles)
+                                 order=run.order, order_normalized=run.raw_order, quantiles=run.quantiles,
+                                 climatology=run.clim, climatology_normalized=run.raw_clim)
 
   def _setup(self, inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields, keep_members,
-             events, derived, order=None, keep_quantiles=False) -> "_EnsembleRun":
+             events, derived, order=None, keep_quantiles=False, climatology=None) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views."""
     from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
     run = _EnsembleRun()
@@ -878,10 +925,15 @@ class EnsembleRollout:
       if len(specs) not in (1, horizon) or any(s.directions != specs[0].directions for s in specs):
         raise ValueError(f"events must be one EventSpec or {horizon} of them with equal directions")
       run.thresholds = [packed(s, template0, scale, loc) for s in specs]
+    if climatology is not None and not callable(climatology) and len(climatology) < horizon:
+      raise ValueError(f"climatology must give the samples of {horizon} lead times, got {len(climatology)}")
+    run.climatology = climatology
+    clim_handle = None if climatology is None else den.climatology_handle(den.dims.c_out)
     # one spec: uploaded once, it survives the store and every lead time; else the one of the lead, before it is scored
     run.main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
                                         thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
-                                        set_per_score=specs is not None and len(specs) > 1, order=order)
+                                        set_per_score=specs is not None and len(specs) > 1, order=order,
+                                        climatology=clim_handle)
     run.main.reserve()
     if spectra:
       _spectra.ensure_tables(native, template0, lmax)
@@ -915,6 +967,7 @@ class EnsembleRollout:
     run.events = None if specs is None else []
     run.order, run.raw_order = ([], []) if order is not None else (None, None)
     run.quantiles = [] if order is not None and keep_quantiles else None
+    run.clim, run.raw_clim = ([], []) if climatology is not None else (None, None)
     if not run.main.set_per_score:
       run.main.configure()
 
@@ -924,7 +977,10 @@ class EnsembleRollout:
       dscale, dloc = dspec.channel_stats(template0, scale, loc)
       store = verification.ScoredStore(den.view_handle(len(dplan["op"])), M, weights, events=dev,
                                        thresholds=None if dev is None else packed(dev, dtemplate, dscale, dloc), weight_q=wq,
-                                       plan=dplan, source=native, order=order)
+                                       plan=dplan, source=native, order=order,
+                                       climatology=None if clim_handle is None
+                                       else den.climatology_handle(len(dplan["op"]), view=True),
+                                       climatology_source=clim_handle)
       run.views[name] = _DerivedView(store, dscale, dtemplate, keep_members)
       if run.quantiles is not None:
         run.views[name].quantiles = []
@@ -992,6 +1048,20 @@ class EnsembleRollout:
       run.order.append(run.raw_order[-1].scaled(scale))
       if run.quantiles is not None:
         run.quantiles.append(run.main.quantile_fields())
+    n_samples = 0
+    if run.clim is not None:
+      samples = list(run.climatology(k) if callable(run.climatology) else run.climatology[k])
+      if not 2 <= len(samples) <= 64:
+        raise ValueError(f"climatology of lead time {k}: 2..64 Datasets shaped like the targets, got {len(samples)}")
+      n_samples = len(samples)
+      packed = []
+      for c in samples:                                   # the map of the truth: (c - l) / s in float64, rounded once
+        c = datasets.as_dataset(c)
+        f = np.transpose(datasets.dataset_to_stacked(c, c.sizes), (1, 2, 0, 3)).reshape(run.shape)
+        packed.append(((f.astype(np.float64) - loc[None, None, :]) / scale[None, None, :]).astype(np.float32)
+                      if run.normalized else f.astype(np.float32))
+      run.raw_clim.append(run.main.score_climatology(packed, None))   # (the truth is on the device already)
+      run.clim.append(run.raw_clim[-1].scaled(scale))
     if run.members is not None:
       run.members.append([native.ens_download_member(m) for m in range(M)])
     for v in run.views.values():
@@ -1005,5 +1075,9 @@ class EnsembleRollout:
         v.order.append(v.raw_order[-1].scaled(v.scale))
         if v.quantiles is not None:
           v.quantiles.append(v.store.quantile_fields())
+      if v.clim is not None:
+        # the samples in the main climatology handle's store, through the view's plan; that handle has no truth of its own
+        v.raw_clim.append(v.store.score_climatology(None, None, n_samples=n_samples, source_truth=truth))
+        v.clim.append(v.raw_clim[-1].scaled(v.scale))
       if v.members is not None:
         v.members.append([v.store.handle.ens_download_member(m) for m in range(M)])

@@ -30,6 +30,10 @@ Order statistics (`gc_ens_order_score`): the device sorts 
 per (batch, channel), the bin sums `bins[k] = (sum w alpha_k, sum w beta_k)` of Hersbach's (2000) decomposition of the
 ensemble CRPS, the outlier weights, and for Q probabilities the pinball-loss sums and below-quantile counts of the quantile
 fields it leaves on the device.  `OrderScores` keeps them raw and derives reliability and potential CRPS.
+
+Skill against a climatology (`gc_ens_clim_score`): the device reads the M members and, from the store
+of a second handle, K climatological samples of every point, and hands back twelve raw sums per (batch, channel).
+`ClimatologyScores` keeps them raw and derives the anomaly correlation of the ensemble mean and the CRPS skill score.
 """
 from __future__ import annotations
 
@@ -302,6 +306,169 @@ class OrderScores:
     out: Dict[str, Dict[str, np.ndarray]] = {}
     for score in ("crps_ensemble", "reliability", "crps_potential", "outlier_low", "outlier_high", "bin_width", "bin_frequency",
                   "quantile_score", "quantile_coverage", "valid_weight", "valid_points"):
+      values = getattr(self, score)
+      out[score] = {name: values[:, off:off + n] for name, off, n in layout}
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# skill against a climatology: anomaly correlation and CRPS skill score (gc_ens_clim_score)
+# ---------------------------------------------------------------------------------------------
+class ClimatologyScores:
+  """The raw sums of `gc_ens_clim_score`: `sums` [B, c_out, 12] float64 and `counts` [B, c_out] uint64 (counted points),
+  with the member count M, the number K of climatological samples and the points `invalid` that did not count.  With m
+  the ensemble mean, cbar the mean of the K samples, fa = m - cbar, oa = y - cbar, ae the mean |. - y| and d the mean
+  absolute difference over the pairs, of the members (x) and of the samples (c):
+
+    sums[..., 0:8]  = A0 .. A7 = sum w (1, fa, oa, fa oa, fa^2, oa^2, mean_i (x_i - cbar)^2, (m - y)^2)
+    sums[..., 8:12] = F4, F5, C4, C5 = sum w (ae_x, d_x, ae_c, d_c)
+
+  Every derived score is [B, c_out]; a zero denominator gives NaN, not an error."""
+
+  N_SUMS = 12
+
+  def __init__(self, sums, counts, n_members: int, n_climatology: int, invalid: int = 0):
+    self.sums = np.asarray(sums, dtype=np.float64)
+    self.counts = np.asarray(counts, dtype=np.uint64)
+    self.n_members, self.n_climatology, self.invalid = int(n_members), int(n_climatology), int(invalid)
+    if self.n_members < 2 or self.n_climatology < 2:
+      raise ValueError("n_members and n_climatology must be >= 2")
+    if self.sums.ndim != 3 or self.sums.shape[-1] != self.N_SUMS:
+      raise ValueError(f"sums must be [batch, channels, {self.N_SUMS}], got {self.sums.shape}")
+    if self.counts.shape != self.sums.shape[:2]:
+      raise ValueError(f"counts must be {self.sums.shape[:2]}, got {self.counts.shape}")
+
+  def _s(self, k: int) -> np.ndarray:
+    return self.sums[..., k]
+
+  @staticmethod
+  def _ratio(a, b) -> np.ndarray:
+    """a / b, NaN where b is zero (or not a number)."""
+    a, b = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64))
+    out = np.full(a.shape, np.nan)
+    np.divide(a, b, out=out, where=(b != 0.0) & ~np.isnan(b))
+    return out
+
+  @classmethod
+  def _root(cls, a) -> np.ndarray:
+    """sqrt(a), NaN where a < 0 (a variance that rounding made negative)."""
+    a = np.asarray(a, np.float64)
+    return np.sqrt(np.where(a >= 0.0, a, np.nan))
+
+  @property
+  def valid_weight(self) -> np.ndarray:
+    """A0: the node weight of the points that counted, per (batch, channel)."""
+    return self._s(0)
+
+  @property
+  def valid_points(self) -> np.ndarray:
+    return self.counts
+
+  @property
+  def acc(self) -> np.ndarray:
+    """The anomaly correlation coefficient of the ensemble mean, uncentred (the form WeatherBench uses):
+    sum w fa oa / sqrt(sum w fa^2 sum w oa^2)."""
+    return self._ratio(self._s(3), self._root(self._s(4) * self._s(5)))
+
+  @property
+  def acc_centred(self) -> np.ndarray:
+    """The anomaly correlation with the weighted mean anomalies removed from both sides."""
+    a0 = self._s(0)
+    mf, mo = self._ratio(self._s(1), a0), self._ratio(self._s(2), a0)
+    cov = self._ratio(self._s(3), a0) - mf * mo
+    vf, vo = self._ratio(self._s(4), a0) - mf * mf, self._ratio(self._s(5), a0) - mo * mo
+    return self._ratio(cov, self._root(vf * vo))
+
+  @property
+  def acc_members(self) -> np.ndarray:
+    """The anomaly correlation with the mean square member anomaly in place of the square of the mean anomaly: what a
+    single member scores on average, where `acc` gains from the averaging."""
+    return self._ratio(self._s(3), self._root(self._s(6) * self._s(5)))
+
+  @property
+  def crps(self) -> np.ndarray:
+    """The fair CRPS of the forecast (`EnsembleScores.crps` of the same store)."""
+    return self._ratio(self._s(8) - 0.5 * self._s(9), self._s(0))
+
+  @property
+  def crps_ensemble(self) -> np.ndarray:
+    """The CRPS of the M-member empirical distribution (pair term times (M - 1) / M)."""
+    m = float(self.n_members)
+    return self._ratio(self._s(8) - 0.5 * (m - 1.0) / m * self._s(9), self._s(0))
+
+  @property
+  def crps_climatology(self) -> np.ndarray:
+    """The fair CRPS of the K climatological samples taken as a forecast."""
+    return self._ratio(self._s(10) - 0.5 * self._s(11), self._s(0))
+
+  @property
+  def crps_climatology_ensemble(self) -> np.ndarray:
+    """The CRPS of the K-sample empirical distribution (pair term times (K - 1) / K)."""
+    k = float(self.n_climatology)
+    return self._ratio(self._s(10) - 0.5 * (k - 1.0) / k * self._s(11), self._s(0))
+
+  @property
+  def crpss(self) -> np.ndarray:
+    """The CRPS skill score 1 - crps / crps_climatology: 1 perfect, 0 no better than the climatology."""
+    return 1.0 - self._ratio(self.crps, self.crps_climatology)
+
+  @property
+  def crpss_ensemble(self) -> np.ndarray:
+    return 1.0 - self._ratio(self.crps_ensemble, self.crps_climatology_ensemble)
+
+  @property
+  def msss(self) -> np.ndarray:
+    """The mean-square skill score of the ensemble mean against the climatological mean, 1 - A7 / A5."""
+    return 1.0 - self._ratio(self._s(7), self._s(5))
+
+  @property
+  def rmse(self) -> np.ndarray:
+    """Of the ensemble mean (`EnsembleScores.rmse` of the same store where the climatology is finite)."""
+    return self._root(self._ratio(self._s(7), self._s(0)))
+
+  @property
+  def rmse_climatology(self) -> np.ndarray:
+    """Of the climatological mean taken as a forecast."""
+    return self._root(self._ratio(self._s(5), self._s(0)))
+
+  def scaled(self, channel_scale) -> "ClimatologyScores":
+    """The sums of a x + b in place of x (members, samples and truth alike), a = channel_scale [c_out], any b(point): A1
+    and A2 scale with a, F4, F5, C4 and C5 with |a|, A3 .. A7 with a^2; b drops out of every term."""
+    a = np.asarray(channel_scale, dtype=np.float64).reshape(-1)
+    if a.shape != (self.sums.shape[1],):
+      raise ValueError(f"channel_scale must have shape ({self.sums.shape[1]},)")
+    if np.any(a == 0.0) or not np.all(np.isfinite(a)):
+      raise ValueError("channel_scale must be finite and non-zero")
+    one, sq, ab = np.ones_like(a), a * a, np.abs(a)
+    f = np.stack([one, a, a, sq, sq, sq, sq, sq, ab, ab, ab, ab], axis=-1)
+    return ClimatologyScores(self.sums * f[None], self.counts, self.n_members, self.n_climatology, self.invalid)
+
+  @staticmethod
+  def merge(parts: Sequence["ClimatologyScores"]) -> "ClimatologyScores":
+    """Scores over the union of what the parts covered (other nodes, other dates): raw sums and counts add."""
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    for p in parts[1:]:
+      if (p.n_members != first.n_members or p.n_climatology != first.n_climatology or p.sums.shape != first.sums.shape):
+        raise ValueError("merge: the parts differ in members, climatological samples or shape")
+    sums, counts, invalid = first.sums.copy(), first.counts.copy(), first.invalid
+    for p in parts[1:]:
+      sums += p.sums
+      counts += p.counts
+      invalid += p.invalid
+    return ClimatologyScores(sums, counts, first.n_members, first.n_climatology, invalid)
+
+  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
+    """{score: {variable: [batch, channels of the variable]}} in the channel order of `datasets.channel_layout`."""
+    layout = datasets.channel_layout(datasets.as_dataset(template))
+    if sum(n for _, _, n in layout) != self.sums.shape[1]:
+      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.sums.shape[1]}")
+    out: Dict[str, Dict[str, np.ndarray]] = {}
+    for score in ("acc", "acc_centred", "acc_members", "crps", "crps_climatology", "crpss", "crps_ensemble",
+                  "crps_climatology_ensemble", "crpss_ensemble", "msss", "rmse", "rmse_climatology", "valid_weight",
+                  "valid_points"):
       values = getattr(self, score)
       out[score] = {name: values[:, off:off + n] for name, off, n in layout}
     return out
@@ -754,15 +921,20 @@ class ScoredStore:
   (None: `ens_score` is not used on it), optionally the events counted on it -- an `EventSpec`, its packed `thresholds`
   in the members' units and `weight_q` = `quantize_node_weights(...)` -- and optionally the `plan` (`DerivedSpec.plan`) that
   fills it from the store of a `source` handle (`ens_derive`), and optionally `order`: the probabilities of the quantile
-  fields `score_order` leaves on the device next to its `OrderScores`.  `EnsembleSampler` and `EnsembleRollout` use one for
-  the main store and one per derived view.
+  fields `score_order` leaves on the device next to its `OrderScores`, and optionally `climatology`: a second handle of the
+  same graph, batch and c_out (`Denoiser.climatology_handle`) whose member store takes the K climatological samples
+  `score_climatology` scores the members against -- on a derived view together with `climatology_source`, the handle whose
+  store holds the samples the view's plan is applied to.  `EnsembleSampler` and `EnsembleRollout` use one for the main
+  store and one per derived view.
 
   `set_per_score`: the plan and the thresholds are not set once by `setup` but by every `score` -- two stores that share
   a handle, or thresholds that change from call to call (assign `thresholds` before the call)."""
 
   def __init__(self, handle, n_members: int, node_weight=None, *, events: Optional["EventSpec"] = None, thresholds=None,
                weight_q: Optional[Tuple[np.ndarray, float]] = None, plan=None, source=None, set_per_score: bool = False,
-               order=None):
+               order=None, climatology=None, climatology_source=None):
+    if climatology_source is not None and (climatology is None or plan is None):
+      raise ValueError("a climatology source goes with a climatology handle and a derive plan")
     if events is not None and weight_q is None:
       raise ValueError("events need the quantised node weights (quantize_node_weights)")
     if (plan is None) != (source is None):
@@ -771,6 +943,9 @@ class ScoredStore:
     self.events, self.thresholds, self.weight_q = events, thresholds, weight_q
     self.plan, self.source, self.set_per_score = plan, source, bool(set_per_score)
     self.order = None if order is None else tuple(float(p) for p in np.asarray(order, dtype=np.float64).reshape(-1))
+    self.climatology, self.climatology_source = climatology, climatology_source
+    self._clim_reserved = 0                      # K of the store this object reserved on the climatology handle
+    self._clim_plan_set = False                  # the plan has been handed to the climatology handle (a derived view)
 
   def reserve(self) -> None:
     self.handle.ens_reserve(self.n_members)
@@ -819,6 +994,38 @@ class ScoredStore:
       self._set_order()
     bins, extra, pinball, counts, _ = self.handle.ens_order_score(truth)
     return OrderScores(bins, extra, pinball, counts, self.n_members, self.order)
+
+  def _reserve_climatology(self, K: int) -> None:
+    if K != self._clim_reserved:
+      self.climatology.ens_reserve(K)
+      self._clim_reserved = K
+
+  def score_climatology(self, fields=None, truth=None, *, n_samples: Optional[int] = None,
+                        source_truth=None) -> Optional["ClimatologyScores"]:
+    """The members against a climatology (None without a climatology handle).  `fields`: the K (2..64) samples
+    [G, B, c_out] in the members' units, pushed into the climatology handle's store with `ens_push_host` (its store is
+    reserved again only when K changes); None: the samples already there.  `truth` None: the truth already on the device.
+    On a derived view with a `climatology_source` the samples are instead made by `ens_derive` -- the view's plan applied
+    to the `n_samples` samples in the source's store, with `source_truth` [G, B, c_src] (the truth in the source's units:
+    the climatology handle has none of its own) -- and the DERIVED members are scored: call it after `score`."""
+    if self.climatology is None:
+      return None
+    if self.climatology_source is not None:
+      K = int(n_samples)
+      self._reserve_climatology(K)
+      if self.set_per_score or not self._clim_plan_set:
+        self.climatology.ens_derive_set(**self.plan)
+        self._clim_plan_set = True
+      self.climatology.ens_derive(self.climatology_source, source_truth)
+    elif fields is not None:
+      K = len(fields)
+      self._reserve_climatology(K)
+      for j, f in enumerate(fields):
+        self.climatology.ens_push_host(j, f)
+    else:
+      K = self._clim_reserved
+    sums, counts, invalid = self.handle.ens_clim_score(self.climatology, truth)
+    return ClimatologyScores(sums, counts, self.n_members, K, invalid)
 
   def quantile_fields(self) -> List[np.ndarray]:
     """The Q quantile fields [G, B, c_out] of the last `score_order`, downloaded."""

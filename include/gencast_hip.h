@@ -630,6 +630,45 @@ int gc_ens_order_fields(gc_handle* h);                    /* quantile fields onl
 int gc_ens_order_download(gc_handle* h, int32_t q, float* field /* [G,B,c_out] */);
 
 /*
+ * An ensemble scored against a climatology on the device: the raw sums of the anomaly correlation
+ * coefficient (ACC) of the ensemble mean and of the CRPS skill score (CRPSS) against a climatological ensemble
+ * (gencast-flax-nnx_amd/verification.py ClimatologyScores).  The reference project has no verification code; the yardstick
+ * is the definition below, restated in float64 in tests/clim_reference.py.
+ * Members x_0 .. x_{M-1} come from the store of `h`, climatological samples c_0 .. c_{K-1} (past states for the same
+ * calendar date) from the store of `clim`, a second handle -- graph-only will do -- on the same device with the same G,
+ * batch and c_out, filled with gc_ens_reserve(clim, K) and gc_ens_push_host; 2 <= M, K <= 64, and a plain climatological
+ * mean field is pushed twice.  The truth y and w [G], the node weights, are those of `h`.  All fields are [G, B, c_out]
+ * float32.  A point is counted when y, all M members and all K samples are finite; every other point adds to `invalid`
+ * and to nothing else.  Per counted point, in double from the float32 values, no fused multiply-add:
+ *   m    = (sum_i x_i) / M,  cbar = (sum_j c_j) / K         ascending slot order (m is the m of gc_ens_score)
+ *   fa = m - cbar,  oa = y - cbar
+ *   ae_x = (sum_i |x_i - y|) / M,   ae_c = (sum_j |c_j - y|) / K
+ *   d_x  = sum_{k=1}^{M-1} k (M - k) (x_(k+1) - x_(k)) / (M (M - 1) / 2)     over the members sorted ascending: the mean of
+ *          |x_i - x_j| over the pairs, every term >= 0;   d_c the same over the sorted samples
+ *   q_x  = (sum_i (x_i - cbar)^2) / M
+ * Per column (b, c), over the counted nodes g, sums[b][c][0..11] in this order:
+ *   A0 = sum w     A1 = sum w fa     A2 = sum w oa     A3 = sum w fa oa     A4 = sum w fa^2     A5 = sum w oa^2
+ *   A6 = sum w q_x A7 = sum w (m - y)^2                F4 = sum w ae_x      F5 = sum w d_x
+ *   C4 = sum w ae_c                  C5 = sum w d_c
+ * counts[b][c] = counted points, invalid = points not counted.  Every partial sum has one writer and the order of addition
+ * is fixed (no atomics on floats), so the same call twice returns identical bytes.  All outputs are raw and additive over
+ * batches and dates; ACC = A3 / sqrt(A4 A5), CRPSS = 1 - (F4 - F5/2) / (C4 - C5/2) and the rest are formed on the host.
+ *   truth: host [G, B, c_out], uploaded and kept, or NULL = the truth uploaded last (the buffer gc_ens_score uses).
+ *   sums [B][c_out][12] is required; counts [B][c_out] and invalid [1] may be NULL.  Two launches on h's stream, ordered
+ *   behind clim's stream by an event: a pass that reads the K samples and the M members of a point once each and sorts each
+ *   in registers (the network of gc_ens_order_score), and a finish that adds the per-block partials in block order.
+ *   Synchronous.
+ *   GC_ERR_STATE: no gc_set_graph, no member store on either handle, a slot of either not pushed since its gc_ens_reserve
+ *   (of clim's: "climatology member slot ..."), no node weights, no truth.
+ *   GC_ERR_INVALID_ARGUMENT: clim NULL or == h, sums NULL, clim on another device or with another G, batch or c_out.
+ * The call touches nothing of either handle but its own buffers and the shared truth buffer of h.  Counters (on h):
+ * "ens_clim_calls", "ens_clim_device_us" (HIP-event time of the last call's launches), "ens_clim_invalid_points".
+ */
+int gc_ens_clim_score(gc_handle* h, gc_handle* clim, const float* truth /* NULL = the truth uploaded last */,
+                      double* sums /* [B][c_out][12] */, uint64_t* counts /* [B][c_out], NULL allowed */,
+                      uint64_t* invalid /* [1], NULL allowed */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
