@@ -21,6 +21,8 @@ Public surface (mirrors the reference's call contracts):
                       on the GPU (GenCast.ensemble_order, EnsembleRollout.run(order=...))
                       ClimatologyScores: anomaly correlation and CRPS skill score of an ensemble against K climatological
                       samples held by a second handle (GenCast.ensemble_climatology, EnsembleRollout.run(climatology=...))
+                      WindowSpec: accumulations, means, changes and extremes over the last lead times of a rollout, formed
+                      on the GPU from a ring of member stores (EnsembleRollout.run(windows=...))
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
@@ -35,14 +37,15 @@ from .ensemble import EnsembleSampler, member_seed, member_shard  # noqa: F401
 from .gencast import GenCast, compute_loss, create_gencast_model, validation_loss  # noqa: F401
 from .nan_cleaning import NaNCleaner  # noqa: F401
 from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, EnsembleRolloutResult, InputsAndResiduals,  # noqa: F401
-                      autoregressive_rollout, state_channels)
+                      WindowRolloutResult, autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
-from .verification import ClimatologyScores, DerivedSpec, EnsembleScores, EventScores, EventSpec, OrderScores  # noqa: F401
+from .verification import ClimatologyScores, DerivedSpec, EnsembleScores, EventScores, EventSpec, OrderScores, WindowSpec  # noqa: F401
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
            "InputsAndResiduals", "autoregressive_rollout", "DeviceRollout", "NaNCleaner", "launch", "losses",
            "compute_loss", "validation_loss", "verification", "EnsembleScores", "spectra", "EnsembleSpectra",
            "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec",
-           "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores"]
+           "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores",
+           "WindowSpec", "WindowRolloutResult"]

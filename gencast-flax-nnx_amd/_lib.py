@@ -131,6 +131,10 @@ SIGNATURES = {
     "gc_ens_order_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
     "gc_ens_clim_score": (ctypes.c_int, [_hp, _hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
                                          ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_window_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_window_push": (ctypes.c_int, [_hp, _hp, _f32p]),
+    "gc_ens_window_emit": (ctypes.c_int, [_hp]),
+    "gc_ens_window_reset": (ctypes.c_int, [_hp]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -224,6 +228,7 @@ class NativeDenoiser:
     self._event_thresholds = 0                 # threshold fields this object handed to the handle
     self._derive_c_src = 0                     # source channels of the derive plan this object handed to the handle
     self._order_quantiles = None               # probabilities this object handed to the handle (None: ens_order_set not called)
+    self._window_length = 0                    # length of the window plan this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
   def _check(self, rc):
@@ -781,6 +786,59 @@ class NativeDenoiser:
     self._check(self._lib.gc_ens_clim_score(self._h, clim._h, None if t is None else _ptr(t, _f32p),  # pylint: disable=protected-access
                                             _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(counts, u64), _ptr(invalid, u64)))
     return sums, counts, int(invalid[0])
+
+  # -- time-window ensemble fields (a ring of the last lead times, reduced into this handle's member store) --
+  def ens_window_set(self, kind: int, length: int, coef=None) -> None:
+    """The plan of `ens_window_emit` (gc_ens_window_set; needs `set_graph` only): `kind` 0 linear, 1 max, 2 min over the last
+    `length` (1..64) pushes; `coef` [length] float64, oldest push first, for a linear window (sum: ones; mean: 1 / length;
+    change: -1, 0, .., 0, +1) and None otherwise.  A new plan clears the push count.  `verification.WindowSpec` builds these
+    arguments."""
+    kind, length = int(kind), int(length)
+    if kind not in (0, 1, 2):
+      raise ValueError("kind must be 0 (linear), 1 (max) or 2 (min)")
+    if not 1 <= length <= 64:
+      raise ValueError("length must lie in 1 .. 64")
+    a = None
+    if kind == 0:
+      if coef is None:
+        raise ValueError("a linear window needs its coefficients")
+      a = np.ascontiguousarray(coef, dtype=np.float64)
+      if a.shape != (length,):
+        raise ValueError(f"coef must have shape ({length},)")
+      if not np.all(np.isfinite(a)):
+        raise ValueError("coef must be finite")
+    elif coef is not None:
+      raise ValueError("only a linear window takes coefficients")
+    self._check(self._lib.gc_ens_window_set(self._h, kind, length,
+                                            None if a is None else _ptr(a, ctypes.POINTER(ctypes.c_double))))
+    self._window_length = length
+
+  def ens_window_push(self, src: "NativeDenoiser", truth=None) -> None:
+    """The ring of this handle <- the M members and the truth of `src`'s store as they stand, device to device
+    (gc_ens_window_push).  `truth` [G, B, c_out] is uploaded into `src`, or None = the truth `src` holds.  On return `src`'s
+    store may be overwritten."""
+    if not self._window_length:
+      raise GencastHipError("libgencast_hip error 4: no plan (ens_window_set has not been called on this object)")
+    if not isinstance(src, NativeDenoiser) or src is self:
+      raise ValueError("src must be another NativeDenoiser")
+    t = None
+    if truth is not None:
+      t = _f32(truth)
+      if t.shape != self._shape_out():
+        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    self._check(self._lib.gc_ens_window_push(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
+
+  def ens_window_emit(self) -> None:
+    """Every slot of this handle's member store and its truth <- the window over the last `length` pushes
+    (gc_ens_window_emit): afterwards `ens_score(None)`, `ens_event_score(None)`, `ens_order_score(None)` and
+    `ens_download_member` of THIS handle see the windowed fields.  The ring is unchanged."""
+    if not self._window_length:
+      raise GencastHipError("libgencast_hip error 4: no plan (ens_window_set has not been called on this object)")
+    self._check(self._lib.gc_ens_window_emit(self._h))
+
+  def ens_window_reset(self) -> None:
+    """Forgets the pushes; the plan and the ring's memory stay (gc_ens_window_reset)."""
+    self._check(self._lib.gc_ens_window_reset(self._h))
 
   # -- context store: one resident conditioning per ensemble member ----------------------------------
   def ctx_reserve(self, n: int) -> None:

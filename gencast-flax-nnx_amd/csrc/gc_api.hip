@@ -879,6 +879,11 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "ens_clim_calls") *value = h->clim_calls;
   else if (n == "ens_clim_device_us") *value = h->clim_device_us;
   else if (n == "ens_clim_invalid_points") *value = h->clim_invalid_points;
+  else if (n == "ens_window_pushes") *value = h->win_pushes;
+  else if (n == "ens_window_emits") *value = h->win_emits;
+  else if (n == "ens_window_device_us") *value = h->win_device_us;
+  else if (n == "ens_window_ring_bytes")
+    *value = (int64_t)((size_t)h->win_ring_L * (((size_t)(h->win_ring_M + 1) * h->hg.G * h->cfg.batch * h->cfg.c_out + 3) / 4 * 4) * sizeof(float));
   else if (n == "noise_stream") *value = (int64_t)h->nz_stream;
   else if (n == "device_allocations") {
     *value = 0;

@@ -10,7 +10,9 @@
 //   gc_derive.hip    gc_ens_derive_*
 //   gc_order.hip     gc_ens_order_*
 //   gc_clim.hip      gc_ens_clim_score
-// The last six are scorers over the member store of gc_ens_reserve.  What they share -- field length, upload through
+//   gc_window.hip    gc_ens_window_*
+// The last seven are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
+// lead times of another).  What they share -- field length, upload through
 // the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
 // relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
 // are a BufferGroup and its events an Event or a Bracket (below); declaring one as a member of the handle is all it takes
@@ -361,6 +363,18 @@ struct gc_handle {
   gci::Bracket clim_time{events};                // of the last call
   gci::Event ev_clim_src{events};                // stream order behind the climatology handle
   int64_t clim_calls = 0, clim_device_us = 0, clim_invalid_points = 0;
+
+  // time-window ensemble fields (gc_ens_window_*, gc_window.hip): the plan, and the ring of the last L pushed lead times
+  gci::BufferGroup win_allocs{groups};            // the ring, one buffer: made again by the push that finds L or M changed
+  bool win_set = false;                          // a plan has been set
+  int win_kind = 0, win_L = 0;                   // 0 linear, 1 max, 2 min; the window length
+  int win_ring_L = 0, win_ring_M = 0;            // what d_win_ring is sized for (0: no ring)
+  float* d_win_ring = nullptr;                   // [L][(M + 1) [G, B, c_out] padded to whole float4s]: M members, then the truth
+  double* d_win_coef = nullptr;                  // [64] coefficients of a linear window, oldest first: made once
+  int64_t win_pushes = 0;                        // pushes since the last gc_ens_window_set / _reset: the next goes to slot win_pushes % L
+  gci::Bracket win_time{events};                 // of the last emit
+  gci::Event ev_win_src{events};                 // stream order behind the source handle
+  int64_t win_emits = 0, win_device_us = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

@@ -206,13 +206,38 @@ class Denoiser:
       clims[(c_d, bool(view))] = nd
     return nd
 
+  def window_handle(self, c_d: int, key: str) -> _lib.NativeDenoiser:
+    """A graph-only handle like `view_handle`'s with `c_out = c_d`, for ONE entry of `EnsembleRollout.run(windows=...)`:
+    it owns the ring of the last lead times `NativeDenoiser.ens_window_push` fills, and its member store takes what
+    `ens_window_emit` makes of them.  One per (`c_d`, `key`) -- two entries never share one, each has a ring of its own --
+    created once and kept; `close` releases them."""
+    if not self._initialized:
+      raise RuntimeError("window_handle: the denoiser has not been initialised by a first call / init_for")
+    c_d = int(c_d)
+    if c_d < 1:
+      raise ValueError("c_d must be positive")
+    windows = getattr(self, "_windows", None)
+    if windows is None:
+      windows = self._windows = {}
+    nd = windows.get((c_d, str(key)))
+    if nd is None or nd.closed:
+      nd = _lib.NativeDenoiser(latent_size=128, d_model=128, num_heads=2, ffw_hidden=256, num_layers=1, c_in=c_d, c_out=c_d,
+                               batch=self._batch, device_id=self._device_id)
+      try:
+        nd.set_graph(self.graph)
+      except Exception:
+        nd.close()
+        raise
+      windows[(c_d, str(key))] = nd
+    return nd
+
   def close(self) -> None:
-    """Releases every library handle this denoiser made: the view and climatology handles, the member lanes and
+    """Releases every library handle this denoiser made: the view, climatology and window handles, the member lanes and
     `native`."""
     for nd in (list((getattr(self, "_views", None) or {}).values()) + list((getattr(self, "_climatologies", None) or {}).values())
-               + list(getattr(self, "_lanes", None) or [])):
+               + list((getattr(self, "_windows", None) or {}).values()) + list(getattr(self, "_lanes", None) or [])):
       nd.close()
-    self._views, self._climatologies, self._lanes = {}, {}, []
+    self._views, self._climatologies, self._windows, self._lanes = {}, {}, {}, []
     if self.native is not None:
       self.native.close()
     self._initialized = False

@@ -653,6 +653,46 @@ class DerivedRolloutResult:
                                 climatology_normalized=both(self.climatology_normalized, other.climatology_normalized, C))
 
 
+class WindowRolloutResult:
+  """The part of an `EnsembleRolloutResult` that belongs to one entry of `EnsembleRollout.run(windows=...)`.  `leads`: the
+  lead times that end a window (`WindowSpec.leads`), `steps`: the window length; per window i, ending at `leads[i]`,
+  `scores[i]` (`verification.EnsembleScores` in physical units: `scores_normalized[i].scaled(scale)` with
+  `WindowSpec.channel_stats`), `scores_normalized[i]` (as the device returned them), `events[i]` (`verification.EventScores`,
+  or None without an EventSpec), `order[i]` / `order_normalized[i]` (`verification.OrderScores`, or None without
+  `run(order=...)`) and `members[i]` (`[M]` arrays [G, B, c] of the windowed members in the members' own units, or None);
+  `template`: the Dataset of the source's variables for `per_variable`."""
+
+  def __init__(self, leads, steps: int, scores, scores_normalized, events=None, order=None, members=None, template=None, *,
+               order_normalized=None):
+    self.leads, self.steps = [int(k) for k in leads], int(steps)
+    self.scores, self.scores_normalized = list(scores), list(scores_normalized)
+    if len(self.scores) != len(self.leads) or len(self.scores_normalized) != len(self.leads):
+      raise ValueError("a window result needs one score per window lead time")
+    self.events = None if events is None else list(events)
+    self.order = None if order is None else list(order)
+    self.order_normalized = None if order_normalized is None else list(order_normalized)
+    self.members, self.template = members, template
+
+  def merge(self, other: "WindowRolloutResult") -> "WindowRolloutResult":
+    """The result over the union of the start dates, window by window: raw sums add; members belong to one date."""
+    from . import verification  # pylint: disable=import-outside-toplevel
+    if self.leads != other.leads or self.steps != other.steps:
+      raise ValueError(f"merge: the windows differ (steps {self.steps} and {other.steps}, leads {self.leads} and {other.leads})")
+    if (self.events is None) != (other.events is None):
+      raise ValueError("merge: only one of the two window results carries events")
+    if (self.order is None) != (other.order is None):
+      raise ValueError("merge: only one of the two window results carries order statistics")
+    S, E, O = verification.EnsembleScores, verification.EventScores, verification.OrderScores
+
+    def both(a, b, cls):
+      return None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
+
+    return WindowRolloutResult(self.leads, self.steps, both(self.scores, other.scores, S),
+                               both(self.scores_normalized, other.scores_normalized, S), both(self.events, other.events, E),
+                               both(self.order, other.order, O), template=self.template,
+                               order_normalized=both(self.order_normalized, other.order_normalized, O))
+
+
 class EnsembleRolloutResult:
   """What `EnsembleRollout.run` returns.  `scores`: one `verification.EnsembleScores` per lead time; `spectra`: one
   `spectra.EnsembleSpectra` per lead time, or None; `mean` / `variance`: the ensemble mean and variance fields on the
@@ -664,12 +704,14 @@ class EnsembleRolloutResult:
   `run(derived=...)`, or None.  `order` / `order_normalized`: one `verification.OrderScores` per lead time (as `scores` /
   `scores_normalized`), or None; `quantiles`: `[horizon][Q]` arrays [G, B, c_out] in the members' own units (as `members`),
   or None.  `climatology` / `climatology_normalized`: one `verification.ClimatologyScores` per lead time (as `scores` /
-  `scores_normalized`) -- anomaly correlation and CRPS skill score against the samples of `run(climatology=...)` -- or None."""
+  `scores_normalized`) -- anomaly correlation and CRPS skill score against the samples of `run(climatology=...)` -- or None.
+  `windows`: {name: `WindowRolloutResult`} for the entries of `run(windows=...)`, or None."""
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
                scores_normalized=None, spectra_normalized=None, events=None, derived=None, order=None,
-               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None):
+               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, windows=None):
     self.scores = list(scores)
+    self.windows = None if windows is None else dict(windows)
     self.climatology = None if climatology is None else list(climatology)
     self.climatology_normalized = None if climatology_normalized is None else list(climatology_normalized)
     if self.climatology is not None and len(self.climatology) != len(self.scores):
@@ -717,6 +759,11 @@ class EnsembleRolloutResult:
     if self.derived is not None and sorted(self.derived) != sorted(other.derived):
       raise ValueError(f"merge: the derived names differ ({sorted(self.derived)} and {sorted(other.derived)})")
     derived = None if self.derived is None else {k: v.merge(other.derived[k]) for k, v in self.derived.items()}
+    if (self.windows is None) != (other.windows is None):
+      raise ValueError("merge: only one of the two results carries windows")
+    if self.windows is not None and sorted(self.windows) != sorted(other.windows):
+      raise ValueError(f"merge: the window names differ ({sorted(self.windows)} and {sorted(other.windows)})")
+    windows = None if self.windows is None else {k: v.merge(other.windows[k]) for k, v in self.windows.items()}
 
     def both(cls, a, b):
       return None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
@@ -731,7 +778,7 @@ class EnsembleRolloutResult:
                                  order_normalized=both(verification.OrderScores, self.order_normalized, other.order_normalized),
                                  climatology=both(verification.ClimatologyScores, self.climatology, other.climatology),
                                  climatology_normalized=both(verification.ClimatologyScores, self.climatology_normalized,
-                                                             other.climatology_normalized))
+                                                             other.climatology_normalized), windows=windows)
 
 
 class _DerivedView:
@@ -753,6 +800,49 @@ class _DerivedView:
                                 climatology_normalized=self.raw_clim)
 
 
+class _WindowEntry:
+  """One entry of `EnsembleRollout.run(windows=...)`: its window handle as a `verification.ScoredStore` (the ring lives on
+  that handle), the handle its pushes come from, and what the window lead times have yielded so far."""
+
+  def __init__(self, spec, store, source, scale, template, horizon: int, keep_members: bool):
+    self.spec, self.store, self.source, self.scale, self.template = spec, store, source, scale, template
+    self.leads = spec.leads(horizon)
+    self.scores, self.raw = [], []
+    self.events = None if store.events is None else []
+    self.order, self.raw_order = ([], []) if store.order is not None else (None, None)
+    self.members = [] if keep_members else None
+
+  def start(self) -> None:
+    """Before the first lead time: the store, what is scored on it, the plan, and an empty ring."""
+    self.store.setup()
+    self.store.handle.ens_window_set(**self.spec.plan())
+    self.store.handle.ens_window_reset()
+
+  def push(self) -> None:
+    """The source's members and truth as they stand (the truth of the lead is on the device already) into the ring."""
+    self.store.handle.ens_window_push(self.source, None)
+
+  def finish_lead(self, k: int) -> None:
+    """At a lead time that ends a window: the window into the store, scored there like any other store."""
+    if k not in self.leads:
+      return
+    self.store.handle.ens_window_emit()
+    raw, ev = self.store.score(None)
+    self.raw.append(raw)
+    self.scores.append(raw.scaled(self.scale))
+    if ev is not None:
+      self.events.append(ev)
+    if self.order is not None:
+      self.raw_order.append(self.store.score_order(None))
+      self.order.append(self.raw_order[-1].scaled(self.scale))
+    if self.members is not None:
+      self.members.append([self.store.handle.ens_download_member(m) for m in range(self.store.n_members)])
+
+  def result(self) -> WindowRolloutResult:
+    return WindowRolloutResult(self.leads, self.spec.steps, self.scores, self.raw, self.events, self.order, self.members,
+                               self.template, order_normalized=self.raw_order)
+
+
 class _EnsembleRun:
   """The state of one `EnsembleRollout.run`: what `_setup` made (handles, plan, noise sources, the main store and the
   derived views) and the per-lead results `_score_lead` appends."""
@@ -761,6 +851,7 @@ class _EnsembleRun:
     self.scores, self.raw_scores, self.means, self.variances = [], [], [], []
     self.thresholds = None                                # per EventSpec, in the members' units
     self.views: Dict[str, _DerivedView] = {}
+    self.windows: Dict[str, _WindowEntry] = {}
 
 
 class EnsembleRollout:
@@ -812,7 +903,7 @@ class EnsembleRollout:
   def run(self, inputs, targets, forcings, horizon: int, num_members: int, *, context_steps: int = 2,
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
           keep_members: bool = False, events=None, derived=None, order=None,
-          keep_quantiles: bool = False, climatology=None) -> EnsembleRolloutResult:
+          keep_quantiles: bool = False, climatology=None, windows=None) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -840,6 +931,15 @@ class EnsembleRollout:
     anomaly correlation of the ensemble mean, CRPS skill score).  For every `derived` entry the samples go through the
     entry's plan as the members do (`gc_ens_derive` from the climatology handle into a climatology view) and the derived
     members are scored against them.  A NaN in a sample is a point the device skips.  Without `climatology` nothing changes.
+    `windows`: {name: `verification.WindowSpec`, or (WindowSpec, EventSpec)}: per lead time, after the scores, the member
+    states and the truth of the entry's source -- the main store, or the view of a `derived` entry -- are copied into a ring
+    on a window handle (`Denoiser.window_handle`, one per entry); at the lead times that end a window (`WindowSpec.leads`)
+    the last `steps` of them become one field per member and for the truth (`gc_ens_window_emit`: an accumulation, a mean,
+    a change, the extreme over time) and are scored there with the same node weights, with `order` where given:
+    `EnsembleRolloutResult.windows[name]` (`WindowRolloutResult`).  The thresholds of such an EventSpec are keyed by the
+    source's variable names, in physical units, and take the map of `WindowSpec.channel_stats`.  With `keep_members` the
+    windowed members are downloaded too.  `climatology` does not reach the windows: skill of a windowed field needs the
+    window of every climatological sample, which is not built.  Without `windows` nothing changes.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -853,6 +953,10 @@ class EnsembleRollout:
     if self.world_size > 1:
       raise ValueError("EnsembleRollout needs all members on one rank (world_size == 1): bring the other "
                        "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    for name, entry in (windows or {}).items():
+      wspec = entry[0] if isinstance(entry, (tuple, list)) else entry
+      if wspec.source is not None and wspec.source not in (derived or {}):
+        raise ValueError(f"window {name!r}: its source {wspec.source!r} names no entry of `derived` ({sorted(derived or {})})")
     given = (targets, inputs, forcings)
     inputs, targets, forcings = (datasets.as_dataset(x) for x in (inputs, targets, forcings))
     M = int(num_members)
@@ -861,7 +965,7 @@ class EnsembleRollout:
     if init_noise is not None and (len(init_noise) != M or any(len(z) < horizon for z in init_noise)):
       raise ValueError("init_noise must be [num_members][horizon] fields")
     run = self._setup(inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields,
-                      keep_members, events, derived, order, keep_quantiles, climatology)
+                      keep_members, events, derived, order, keep_quantiles, climatology, windows)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -873,10 +977,11 @@ class EnsembleRollout:
                                  scores_normalized=run.raw_scores, spectra_normalized=run.raw_spectra, events=run.events,
                                  derived=None if derived is None else {k: v.result() for k, v in run.views.items()},
                                  order=run.order, order_normalized=run.raw_order, quantiles=run.quantiles,
-                                 climatology=run.clim, climatology_normalized=run.raw_clim)
+                                 climatology=run.clim, climatology_normalized=run.raw_clim,
+                                 windows=None if windows is None else {k: v.result() for k, v in run.windows.items()})
 
   def _setup(self, inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields, keep_members,
-             events, derived, order=None, keep_quantiles=False, climatology=None) -> "_EnsembleRun":
+             events, derived, order=None, keep_quantiles=False, climatology=None, windows=None) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views."""
     from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
     run = _EnsembleRun()
@@ -915,9 +1020,11 @@ class EnsembleRollout:
       return thr if norm is None else ((thr.astype(np.float64) - l) / s).astype(np.float32)
 
     entries = {name: entry if isinstance(entry, (tuple, list)) else (entry, None) for name, entry in (derived or {}).items()}
+    wentries = {name: entry if isinstance(entry, (tuple, list)) else (entry, None) for name, entry in (windows or {}).items()}
     weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
     wq = None
-    if events is not None or any(dev is not None for _, dev in entries.values()):
+    if (events is not None or any(dev is not None for _, dev in entries.values())
+        or any(wev is not None for _, wev in wentries.values())):
       wq = verification.quantize_node_weights(weights)
     specs = None
     if events is not None:
@@ -988,6 +1095,21 @@ class EnsembleRollout:
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
       store.set_per_score = sum(1 for v in run.views.values() if v.store.handle is store.handle) > 1
       store.setup()
+
+    for name, (wspec, wev) in wentries.items():
+      # the source's channels, their statistics and their names; the window maps the statistics once more
+      if wspec.source is None:
+        source, stemplate, sscale, sloc = native, template0, scale, loc
+      else:
+        dspec = entries[wspec.source][0]
+        source, stemplate = run.views[wspec.source].store.handle, dspec.template(template0)
+        sscale, sloc = dspec.channel_stats(template0, scale, loc)
+      wscale, wloc = wspec.channel_stats(sscale, sloc)
+      store = verification.ScoredStore(den.window_handle(len(wscale), name), M, weights, events=wev,
+                                       thresholds=None if wev is None else packed(wev, stemplate, wscale, wloc), weight_q=wq,
+                                       order=order)
+      run.windows[name] = _WindowEntry(wspec, store, source, wscale, stemplate, horizon, keep_members)
+      run.windows[name].start()
     return run
 
   @staticmethod
@@ -1064,7 +1186,10 @@ class EnsembleRollout:
       run.clim.append(run.raw_clim[-1].scaled(scale))
     if run.members is not None:
       run.members.append([native.ens_download_member(m) for m in range(M)])
-    for v in run.views.values():
+    for w in run.windows.values():
+      if w.spec.source is None:
+        w.push()
+    for vname, v in run.views.items():
       raw, ev = v.store.score(None)                       # members and truth, device to device
       v.raw.append(raw)
       v.scores.append(raw.scaled(v.scale))
@@ -1081,3 +1206,8 @@ class EnsembleRollout:
         v.clim.append(v.raw_clim[-1].scaled(v.scale))
       if v.members is not None:
         v.members.append([v.store.handle.ens_download_member(m) for m in range(M)])
+      for w in run.windows.values():                      # (two views may share a handle: the view's fields are there NOW)
+        if w.spec.source == vname:
+          w.push()
+    for w in run.windows.values():
+      w.finish_lead(k)

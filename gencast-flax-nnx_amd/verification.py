@@ -914,6 +914,84 @@ class DerivedSpec:
 
 
 # ---------------------------------------------------------------------------------------------
+# time windows: accumulations, means, changes and extremes over lead times (gc_ens_window_*)
+# ---------------------------------------------------------------------------------------------
+_WINDOW_KINDS = {"sum": 0, "mean": 0, "change": 0, "linear": 0, "max": 1, "min": 2}
+
+
+class WindowSpec:
+  """What `gc_ens_window_emit` makes of the last `steps` lead times of a member store: per member,
+  and for the truth, one field over time.
+
+  `kind`: "sum" (an accumulation: 24 h precipitation from two 12 h steps), "mean", "max", "min", "change" (newest minus
+  oldest; `steps` >= 2) or "linear" with `coef` [steps], oldest lead time first.  sum, mean and change are linear windows
+  with coefficients 1, 1 / steps and (-1, 0, .., 0, +1).  `steps`: 1..64 lead times.  `stride`: lead times between the ends of
+  two windows; `steps` (the default) gives windows that tile the rollout, 1 a window ending at every lead time from the
+  first full one on.  `source`: None, the main store, or the name of an entry of `derived` ("the highest pooled wind speed
+  within three days").  Variable names and the template are the source's.  A lead time at which any of the `steps` values
+  is not finite gives NaN: an accumulation with a missing step is not an accumulation."""
+
+  def __init__(self, kind: str, steps: int, stride: Optional[int] = None, source: Optional[str] = None, coef=None):
+    if kind not in _WINDOW_KINDS:
+      raise ValueError(f"kind must be one of {sorted(_WINDOW_KINDS)}, got {kind!r}")
+    if isinstance(steps, bool) or int(steps) != steps or not 1 <= int(steps) <= 64:
+      raise ValueError(f"steps must be an integer in 1 .. 64, got {steps!r}")
+    self.kind, self.steps = kind, int(steps)
+    if kind == "change" and self.steps < 2:
+      raise ValueError("a change needs steps >= 2")
+    if stride is not None and (isinstance(stride, bool) or int(stride) != stride or int(stride) < 1):
+      raise ValueError(f"stride must be a positive integer, got {stride!r}")
+    self.stride = self.steps if stride is None else int(stride)
+    if source is not None and not isinstance(source, str):
+      raise ValueError("source must be None (the main store) or the name of a derived entry")
+    self.source = source
+    if kind == "linear":
+      if coef is None:
+        raise ValueError("a linear window needs coef")
+      c = np.asarray(coef, dtype=np.float64).reshape(-1)
+      if c.shape != (self.steps,):
+        raise ValueError(f"coef must have {self.steps} entries, got {c.shape[0]}")
+      if not np.all(np.isfinite(c)):
+        raise ValueError("coef must be finite")
+      self.coef = c.copy()
+    else:
+      if coef is not None:
+        raise ValueError("only kind 'linear' takes coef")
+      self.coef = None
+
+  def coefficients(self) -> Optional[np.ndarray]:
+    """a [steps] float64, oldest lead time first, of a linear window; None for max and min."""
+    L = self.steps
+    if self.kind == "sum":
+      return np.ones(L)
+    if self.kind == "mean":
+      return np.full(L, 1.0 / L)
+    if self.kind == "change":
+      a = np.zeros(L)
+      a[0], a[-1] = -1.0, 1.0
+      return a
+    return None if self.coef is None else self.coef.copy()
+
+  def plan(self) -> Dict[str, object]:
+    """The keyword arguments of `NativeDenoiser.ens_window_set`."""
+    return dict(kind=_WINDOW_KINDS[self.kind], length=self.steps, coef=self.coefficients())
+
+  def leads(self, horizon: int) -> List[int]:
+    """The lead times k < horizon that end a window: k + 1 >= steps and (k + 1 - steps) % stride == 0."""
+    return [k for k in range(int(horizon)) if k + 1 >= self.steps and (k + 1 - self.steps) % self.stride == 0]
+
+  def channel_stats(self, scale, loc) -> Tuple[np.ndarray, np.ndarray]:
+    """(scale_w, loc_w): the affine map from a windowed value of members that hold (x - loc) / scale to physical units.  A
+    linear window of x is scale * (the window of the members) + loc * sum(a): (scale, loc * sum(a)); the extreme of x is
+    scale * (the extreme of the members) + loc: (scale, loc)."""
+    scale, loc = np.asarray(scale, np.float64).reshape(-1), np.asarray(loc, np.float64).reshape(-1)
+    if scale.shape != loc.shape:
+      raise ValueError("scale and loc must have the same shape")
+    a = self.coefficients()
+    return scale.copy(), loc.copy() if a is None else loc * float(np.sum(a))
+
+
+# ---------------------------------------------------------------------------------------------
 # a member store that gets scored
 # ---------------------------------------------------------------------------------------------
 class ScoredStore:

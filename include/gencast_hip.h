@@ -669,6 +669,51 @@ int gc_ens_clim_score(gc_handle* h, gc_handle* clim, const float* truth /* NULL 
                       uint64_t* invalid /* [1], NULL allowed */);
 
 /*
+ * Time-window ensemble fields on the device: accumulations, means, changes and extremes over the
+ * last L lead times of a rollout -- 24 h precipitation from 12 h steps, a weekly mean, the highest wind speed within three
+ * days -- formed from the members and the truths that one handle's gc_ens_* store held at those lead times and left in the
+ * member store of a SECOND handle, on which every scorer of this library then works as it is.  The reference project has
+ * no verification code; the yardstick is the definition below, restated in tests/window_reference.py, bit for bit.
+ * Source handle `src`: a complete store of M members and a truth, each [G, B, c] float32 -- a handle that samples, or the
+ * destination of gc_ens_derive.  Window handle `win`: the same device, G and batch, c_out == c; it needs gc_set_graph only.
+ * It owns a RING of the last L pushes; a push is a copy of src's M members and truth as they stand.
+ * Plan: kind in {LINEAR 0, MAX 1, MIN 2}, 1 <= L <= 64 and, for LINEAR, coefficients a[0 .. L-1], finite doubles.  With
+ * x_t, t = 0 (oldest) .. L - 1 (newest), the float32 values of one element of one field over the last L pushes, for every
+ * element of each of the M + 1 fields (the truth is field M):
+ *   any x_t not finite (NaN, +-inf) gives NaN, for every kind and also where a_t == 0
+ *   LINEAR     acc = 0.0, then for t ascending acc = acc + a_t (double) x_t: the product is rounded, then the sum (no fused
+ *              multiply-add); the output is (float) acc, rounded once -- a finite double beyond float32 range becomes +-inf
+ *   MAX / MIN  m = x_0, then for t ascending m = x_t where x_t > m (MIN: x_t < m): exact, one of the inputs' bits, the
+ *              older one on a tie (so also between +0 and -0)
+ *   gc_ens_window_set    the plan.  coef [L] doubles, oldest first (NULL unless LINEAR).  Needs gc_set_graph only.  A new
+ *                        plan clears the push count; the ring is freed and made again only by the push that finds L or M
+ *                        changed ("device_allocations" stays flat).  GC_ERR_STATE: no graph.  GC_ERR_INVALID_ARGUMENT:
+ *                        length < 1, LINEAR with coef NULL, a coefficient that is not finite.  GC_ERR_UNSUPPORTED: an
+ *                        unknown kind, length > 64.
+ *   gc_ens_window_push   src's M members and truth, device to device, into ring slot pushes % L; then pushes += 1.  truth:
+ *                        host [G, B, c], uploaded into and kept in src's truth buffer as gc_ens_score(src, truth, ...)
+ *                        would, or NULL = src's last truth.  The copies run on win's stream, ordered behind src's stream
+ *                        by an event.  Synchronous: after the call src's store may be overwritten without changing the ring.
+ *                        GC_ERR_INVALID_ARGUMENT: src is NULL, win itself or on another device; src has no graph, another
+ *                        G, batch or c_out.  GC_ERR_STATE: no plan, no store on src, a src slot not pushed since its
+ *                        gc_ens_reserve, no truth, an M other than the ring's while pushes > 0 (gc_ens_window_reset first).
+ *   gc_ens_window_emit   pushes - L .. pushes - 1, in that order, reduced into every slot of win's member store and into
+ *                        win's truth buffer: afterwards every slot counts as pushed and truth = NULL works in every scorer
+ *                        of win; win's event codes, mean / variance fields and order results count as not computed.  One
+ *                        launch.  Synchronous.  The ring is unchanged: an emit after every push gives sliding windows.
+ *                        GC_ERR_STATE: no plan, pushes < L, no store on win, a store whose M differs from the ring's.
+ *   gc_ens_window_reset  pushes = 0; the plan and the ring's memory stay.
+ * No atomics: the same emit twice returns identical bytes.  The calls touch nothing on src but its truth buffer, and on win
+ * only the ring, the member store and the truth.  Counters (on win): "ens_window_pushes" (pushes since the last set / reset),
+ * "ens_window_emits" (emits so far), "ens_window_device_us" (HIP-event time of the last emit's launch),
+ * "ens_window_ring_bytes" (the ring as it stands: L slots of (M + 1) fields, each slot padded to 16 bytes).
+ */
+int gc_ens_window_set(gc_handle* win, int32_t kind, int32_t length, const double* coef /* [length], NULL unless LINEAR */);
+int gc_ens_window_push(gc_handle* win, gc_handle* src, const float* truth /* [G,B,c] host, NULL = src's last truth */);
+int gc_ens_window_emit(gc_handle* win);
+int gc_ens_window_reset(gc_handle* win);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
