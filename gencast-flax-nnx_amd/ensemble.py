@@ -66,6 +66,12 @@ class EnsembleSampler:
       return gen.standard_normal(shape, dtype=np.float32)
     return np.asarray(draw(gen, shape, template), np.float32)
 
+  def _one_rank(self, what: str) -> None:
+    """Refuses what needs all members at every point (the pair term of the CRPS, a sort, a count) on more than one rank."""
+    if self.world_size > 1:
+      raise ValueError(f"EnsembleSampler.{what} needs all members on one rank (world_size == 1): bring the other "
+                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+
   def __call__(self, inputs, targets_template, forcings, num_members: int
                ) -> List[Tuple[int, datasets.Dataset]]:
     return self._run(inputs, targets_template, forcings, num_members, None)
@@ -77,9 +83,7 @@ class EnsembleSampler:
     are skipped point by point); with `fields=True` also the ensemble mean and variance as Datasets shaped like
     `targets` (xarray in, xarray out).  Node weights: `verification.node_weights(targets)`.
     One rank only: the pair term of the CRPS needs all members at every point."""
-    if self.world_size > 1:
-      raise ValueError("EnsembleSampler.scores needs all members on one rank (world_size == 1): bring the other "
-                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    self._one_rank("scores")
     return self._run(inputs, targets, forcings, num_members, bool(fields))
 
   def spectra(self, inputs, targets, forcings, num_members: int, *, lmax: Optional[int] = None):
@@ -101,9 +105,7 @@ class EnsembleSampler:
     `verification.EventScores` (Brier score and its decomposition, reliability curve, ROC, economic value, per event,
     batch member and channel).  No member is downloaded.  Node weights:
     `verification.quantize_node_weights(verification.node_weights(targets))`."""
-    if self.world_size > 1:
-      raise ValueError("EnsembleSampler.events needs all members on one rank (world_size == 1): bring the other "
-                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    self._one_rank("events")
     return self._run(inputs, targets, forcings, num_members, None, events=spec)
 
   def derived(self, inputs, targets, forcings, num_members: int, spec, events=None):
@@ -114,9 +116,7 @@ class EnsembleSampler:
     taken as they are sampled, scale 1 and location 0: under a normalisation wrapper (`InputsAndResiduals`, `NaNCleaner`
     around one) a single-step sample is a normalised RESIDUAL, and the norm of two residuals is no wind speed -- the wrappers
     therefore have no such method; `EnsembleRollout.run(derived=...)` derives from member STATES, which are fields."""
-    if self.world_size > 1:
-      raise ValueError("EnsembleSampler.derived needs all members on one rank (world_size == 1): bring the other "
-                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    self._one_rank("derived")
     return self._run(inputs, targets, forcings, num_members, None, derived=(spec, events))
 
   def order(self, inputs, targets, forcings, num_members: int, probs=(), *, quantile_fields: bool = False):
@@ -125,9 +125,7 @@ class EnsembleSampler:
     and, for the probabilities `probs` (at most 8), the pinball loss and the coverage of the quantile fields.  With
     `quantile_fields=True` also those fields (the median, a p10 / p90 band) as Datasets shaped like `targets`; they need no
     truth and exist wherever all members are finite.  No member is downloaded."""
-    if self.world_size > 1:
-      raise ValueError("EnsembleSampler.order needs all members on one rank (world_size == 1): bring the other "
-                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    self._one_rank("order")
     return self._run(inputs, targets, forcings, num_members, None, order=(tuple(probs), bool(quantile_fields)))
 
   def climatology(self, inputs, targets, forcings, num_members: int, climatology):
@@ -137,18 +135,14 @@ class EnsembleSampler:
     skill score against the climatological ensemble, the mean-square skill score.  The K fields are uploaded into the
     store of a second handle (`Denoiser.climatology_handle`); no member is downloaded.  NaNs in `targets` or in a sample
     are points the device does not count."""
-    if self.world_size > 1:
-      raise ValueError("EnsembleSampler.climatology needs all members on one rank (world_size == 1): bring the other "
-                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    self._one_rank("climatology")
     climatology = list(climatology)
     if not 2 <= len(climatology) <= 64:
       raise ValueError(f"climatology must be 2..64 Datasets shaped like the targets, got {len(climatology)}")
     return self._run(inputs, targets, forcings, num_members, None, climatology=climatology)
 
   def _spectral(self, inputs, targets, forcings, num_members, score_fields, lmax):
-    if self.world_size > 1:
-      raise ValueError("EnsembleSampler.spectra needs all members on one rank (world_size == 1): bring the other "
-                       "ranks' members over and push them with NativeDenoiser.ens_push_host")
+    self._one_rank("spectra")
     return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
 
   def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,

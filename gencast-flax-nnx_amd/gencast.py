@@ -40,6 +40,11 @@ def _generator(rngs) -> np.random.Generator:
   raise TypeError(f"unsupported rngs: {type(rngs)}")
 
 
+def _base_seed(rngs) -> int:
+  """The base seed of an ensemble: an int as it is, anything else through `Sampler.seed_from`."""
+  return int(rngs if isinstance(rngs, (int, np.integer)) else Sampler.seed_from(rngs))
+
+
 class GenCast:
 
   def __init__(self,
@@ -89,16 +94,18 @@ class GenCast:
       return self._sampler(inputs, targets_template, forcings, rngs=rng, **optional_kwargs)
     return predictor_fn
 
+  def _ensemble_sampler(self, rngs, concurrent_members):
+    """The `EnsembleSampler` of the `ensemble_*` methods: all members on this rank, `rngs` as the base seed."""
+    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
+    return EnsembleSampler(self._sampler, base_seed=_base_seed(rngs), concurrent_members=concurrent_members)
+
   def ensemble_scores(self, inputs, targets, forcings=None, *, num_members, rngs=0, concurrent_members=1, fields=False):
     """Samples `num_members` (2..64) members for (inputs, forcings) and scores them against `targets` on the GPU:
     `verification.EnsembleScores` (CRPS, RMSE of the ensemble mean, spread, rank histogram, per batch member and
     channel, latitude-weighted), with `fields=True` also the ensemble mean and variance as Datasets.  No member
     leaves the device.  `rngs`: the base seed of the members' noise streams (`ensemble.member_seed`), so member m
     is the member m of `EnsembleSampler(base_seed=rngs)`; `concurrent_members` as there."""
-    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
-    if not isinstance(rngs, (int, np.integer)):
-      rngs = Sampler.seed_from(rngs)
-    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.scores(inputs, targets, forcings, num_members, fields=fields)
 
   def ensemble_spectra(self, inputs, targets, forcings=None, *, num_members, rngs=0, concurrent_members=1, lmax=None,
@@ -107,10 +114,7 @@ class GenCast:
     `spectra.EnsembleSpectra` -- spherical-harmonic power per total wavenumber l < `lmax` (default n_lon / 2) of the
     truth, the members, the ensemble mean, their errors and the spread, per batch member and channel.  No member
     leaves the device.  `scores=True`: -> (EnsembleScores, EnsembleSpectra) from the same members, sampled once."""
-    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
-    if not isinstance(rngs, (int, np.integer)):
-      rngs = Sampler.seed_from(rngs)
-    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    runner = self._ensemble_sampler(rngs, concurrent_members)
     if scores:
       return runner.scores_and_spectra(inputs, targets, forcings, num_members, lmax=lmax)
     return runner.spectra(inputs, targets, forcings, num_members, lmax=lmax)
@@ -120,10 +124,7 @@ class GenCast:
     (`verification.EventSpec`: thresholds per variable in the units of `targets`, a direction per event) among them and
     in `targets`, on the GPU: `verification.EventScores` -- Brier score with its decomposition, reliability curve, ROC
     area, relative economic value, per event, batch member and channel.  No member leaves the device."""
-    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
-    if not isinstance(rngs, (int, np.integer)):
-      rngs = Sampler.seed_from(rngs)
-    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.events(inputs, targets, forcings, num_members, spec)
 
   def ensemble_order(self, inputs, targets, forcings=None, *, num_members, probs=(), quantile_fields=False, rngs=0,
@@ -134,10 +135,7 @@ class GenCast:
     fields -- per batch member and channel, latitude-weighted.  `quantile_fields=True`: -> (OrderScores, [Q Datasets]),
     the quantile fields (median, p10 / p90 band) shaped like `targets`.  No member leaves the device.  The uncertainty and
     resolution parts of Hersbach's decomposition need a climatology of the observations and are not formed."""
-    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
-    if not isinstance(rngs, (int, np.integer)):
-      rngs = Sampler.seed_from(rngs)
-    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.order(inputs, targets, forcings, num_members, probs, quantile_fields=quantile_fields)
 
   def ensemble_climatology(self, inputs, targets, forcings=None, *, num_members, climatology, rngs=0, concurrent_members=1):
@@ -146,10 +144,7 @@ class GenCast:
     twice): `verification.ClimatologyScores` -- the anomaly correlation coefficient of the ensemble mean (`acc`), the CRPS
     skill score against the climatological ensemble (`crpss`), `msss` -- per batch member and channel, latitude-weighted.
     No member leaves the device."""
-    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
-    if not isinstance(rngs, (int, np.integer)):
-      rngs = Sampler.seed_from(rngs)
-    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.climatology(inputs, targets, forcings, num_members, climatology)
 
   def ensemble_derived(self, inputs, targets, forcings=None, *, num_members, spec, events=None, rngs=0, concurrent_members=1):
@@ -160,10 +155,7 @@ class GenCast:
     are taken in the units they are sampled in; the normalisation wrappers have no such method, because under them a
     single-step sample is a normalised residual and the norm of two residuals is no wind speed (`ensemble_rollout(...,
     derived=...)` derives from member states instead)."""
-    from .ensemble import EnsembleSampler  # pylint: disable=import-outside-toplevel
-    if not isinstance(rngs, (int, np.integer)):
-      rngs = Sampler.seed_from(rngs)
-    runner = EnsembleSampler(self._sampler, base_seed=int(rngs), concurrent_members=concurrent_members)
+    runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.derived(inputs, targets, forcings, num_members, spec, events)
 
   def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, *, rngs=0, norm=None, concurrent_members=1,
@@ -176,9 +168,7 @@ class GenCast:
     `norm`: an `InputsAndResiduals` whose statistics apply (its own `ensemble_rollout` passes itself); `device_noise`
     defaults to the sampler's; other keywords as `rollout.EnsembleRollout.run`."""
     from .rollout import EnsembleRollout  # pylint: disable=import-outside-toplevel
-    if not isinstance(rngs, (int, np.integer)):
-      rngs = Sampler.seed_from(rngs)
-    runner = EnsembleRollout(self, norm, self.task_config, base_seed=int(rngs), concurrent_members=concurrent_members,
+    runner = EnsembleRollout(self, norm, self.task_config, base_seed=_base_seed(rngs), concurrent_members=concurrent_members,
                              device_noise=self._sampler.device_noise if device_noise is None else device_noise)
     return runner.run(inputs, targets, forcings, horizon, num_members, **kwargs)
 

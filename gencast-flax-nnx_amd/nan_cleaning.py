@@ -80,16 +80,20 @@ class NaNCleaner:
   def full_sampling(self, inputs, targets_template, forcings: Optional[Dataset] = None, **kwargs):
     return self._wrap(self.predictor.full_sampling, inputs, targets_template, forcings, **kwargs)
 
-  def _clean_all(self, inputs, targets, forcings):
+  def _cleaned(self, inputs, targets, forcings, clean_targets: bool):
+    """Inputs and forcings as Datasets with the variable cleaned; the targets as a Dataset, cleaned only when asked."""
     inputs, targets = datasets.as_dataset(inputs), datasets.as_dataset(targets)
     forcings = None if forcings is None else datasets.as_dataset(forcings)
     if self._var_to_clean in inputs.keys():
       inputs = self._clean(inputs)
-    if self._var_to_clean in targets.keys():
+    if clean_targets and self._var_to_clean in targets.keys():
       targets = self._clean(targets)
     if forcings is not None and self._var_to_clean in forcings.keys():
       forcings = self._clean(forcings)
     return inputs, targets, forcings
+
+  def _clean_all(self, inputs, targets, forcings):
+    return self._cleaned(inputs, targets, forcings, True)
 
   def denoising_loss(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """nan_cleaning.py:87-102 on the forward-only objective: inputs, targets and forcings are cleaned."""
@@ -110,13 +114,7 @@ class NaNCleaner:
     """Inputs and forcings are cleaned; the targets pass through unchanged: their NaNs (land points of the cleaned
     variable) are the points the device skips, so the scores are over the valid points only."""
     given = (targets, inputs, forcings)
-    inputs = datasets.as_dataset(inputs)
-    forcings = None if forcings is None else datasets.as_dataset(forcings)
-    if self._var_to_clean in inputs.keys():
-      inputs = self._clean(inputs)
-    if forcings is not None and self._var_to_clean in forcings.keys():
-      forcings = self._clean(forcings)
-    out = self.predictor.ensemble_scores(inputs, datasets.as_dataset(targets), forcings, **kwargs)
+    out = self.predictor.ensemble_scores(*self._cleaned(inputs, targets, forcings, False), **kwargs)
     if not isinstance(out, tuple):
       return out
     return (out[0],) + tuple(datasets.like_inputs(datasets.as_dataset(f), *given) for f in out[1:])
@@ -125,13 +123,7 @@ class NaNCleaner:
     """Inputs and forcings are cleaned; the targets pass through unchanged, as in `ensemble_scores`: their NaNs are
     points the device does not count.  The quantile fields need no truth and are finite there."""
     given = (targets, inputs, forcings)
-    inputs = datasets.as_dataset(inputs)
-    forcings = None if forcings is None else datasets.as_dataset(forcings)
-    if self._var_to_clean in inputs.keys():
-      inputs = self._clean(inputs)
-    if forcings is not None and self._var_to_clean in forcings.keys():
-      forcings = self._clean(forcings)
-    out = self.predictor.ensemble_order(inputs, datasets.as_dataset(targets), forcings, **kwargs)
+    out = self.predictor.ensemble_order(*self._cleaned(inputs, targets, forcings, False), **kwargs)
     if not isinstance(out, tuple):
       return out
     return out[0], [datasets.like_inputs(datasets.as_dataset(f), *given) for f in out[1]]
@@ -139,55 +131,26 @@ class NaNCleaner:
   def ensemble_climatology(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """Inputs and forcings are cleaned; the targets and the climatology pass through unchanged: their NaNs are points
     the device does not count (`ClimatologyScores.invalid`)."""
-    inputs = datasets.as_dataset(inputs)
-    forcings = None if forcings is None else datasets.as_dataset(forcings)
-    if self._var_to_clean in inputs.keys():
-      inputs = self._clean(inputs)
-    if forcings is not None and self._var_to_clean in forcings.keys():
-      forcings = self._clean(forcings)
-    return self.predictor.ensemble_climatology(inputs, datasets.as_dataset(targets), forcings, **kwargs)
+    return self.predictor.ensemble_climatology(*self._cleaned(inputs, targets, forcings, False), **kwargs)
 
   def ensemble_events(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """Inputs and forcings are cleaned; the targets pass through unchanged, as in `ensemble_scores`: their NaNs are
     points the device does not count (`EventScores.invalid`)."""
-    inputs = datasets.as_dataset(inputs)
-    forcings = None if forcings is None else datasets.as_dataset(forcings)
-    if self._var_to_clean in inputs.keys():
-      inputs = self._clean(inputs)
-    if forcings is not None and self._var_to_clean in forcings.keys():
-      forcings = self._clean(forcings)
-    return self.predictor.ensemble_events(inputs, datasets.as_dataset(targets), forcings, **kwargs)
+    return self.predictor.ensemble_events(*self._cleaned(inputs, targets, forcings, False), **kwargs)
 
   def ensemble_spectra(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """Inputs and forcings are cleaned, and so are the targets: a transform cannot skip points, so the spectrum of the
     cleaned variable is that of the field with its NaNs (land points) replaced by the fill value, truth and members
     alike."""
-    inputs = datasets.as_dataset(inputs)
-    targets = datasets.as_dataset(targets)
-    forcings = None if forcings is None else datasets.as_dataset(forcings)
-    if self._var_to_clean in inputs.keys():
-      inputs = self._clean(inputs)
-    if self._var_to_clean in targets.keys():
-      targets = self._clean(targets)
-    if forcings is not None and self._var_to_clean in forcings.keys():
-      forcings = self._clean(forcings)
-    return self.predictor.ensemble_spectra(inputs, targets, forcings, **kwargs)
+    return self.predictor.ensemble_spectra(*self._clean_all(inputs, targets, forcings), **kwargs)
 
   def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, **kwargs):
     """Inputs and forcings are cleaned.  The targets pass through unchanged (their NaNs are the points the device
     skips) unless `spectra=True`: a transform cannot skip points, so they are then cleaned too, as `ensemble_spectra`
     does, and the scores of the same call are over the filled field."""
     given = (targets, inputs, forcings)
-    inputs = datasets.as_dataset(inputs)
-    targets = datasets.as_dataset(targets)
-    forcings = datasets.as_dataset(forcings)
-    if self._var_to_clean in inputs.keys():
-      inputs = self._clean(inputs)
-    if self._var_to_clean in forcings.keys():
-      forcings = self._clean(forcings)
-    if kwargs.get("spectra") and self._var_to_clean in targets.keys():
-      targets = self._clean(targets)
-    out = self.predictor.ensemble_rollout(inputs, targets, forcings, horizon, num_members, **kwargs)
+    cleaned = self._cleaned(inputs, targets, datasets.as_dataset(forcings), bool(kwargs.get("spectra")))
+    out = self.predictor.ensemble_rollout(*cleaned, horizon, num_members, **kwargs)
     if out.mean is not None and any(datasets.is_xarray(g) for g in given):   # xarray in -> xarray out
       like = given[0].isel(time=slice(0, horizon)) if datasets.is_xarray(given[0]) else None
       out.mean, out.variance = (datasets.to_xarray(datasets.as_dataset(f), like) for f in (out.mean, out.variance))

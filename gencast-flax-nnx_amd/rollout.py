@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import config as cfg
-from . import datasets
+from . import datasets, spectra as _spectra, verification
 from .datasets import Dataset, Variable
 from .denoiser import Denoiser
 
@@ -178,6 +178,13 @@ class InputsAndResiduals:
     preds = Dataset({k: self._unnormalize_prediction_and_add_input(raw, k, v) for k, v in norm_pred.items()}, norm_pred.coords)
     return datasets.loss_like_inputs(*loss, *given), datasets.like_inputs(preds, *given)
 
+  def _target_scale(self, raw_inputs: Dataset, targets) -> np.ndarray:
+    """Per target channel, the a of the member-to-physical map x -> a x + b: the residual scale of a variable that is also
+    an input, else its plain scale."""
+    tds = datasets.as_dataset(targets)
+    return np.concatenate([_per_channel_stat(self._residual_scales if name in raw_inputs else self._scales, name, tds[name], 1.0)
+                           for name, _, _ in datasets.channel_layout(tds)])
+
 
   def ensemble_scores(self, inputs, targets, forcings=None, **kwargs):
     """`ensemble_scores` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets,
@@ -187,19 +194,15 @@ class InputsAndResiduals:
     prediction (last input frame added back for residual variables) and the variance is multiplied by a^2."""
     given = (targets, inputs, forcings)
     raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
-    tds = datasets.as_dataset(targets)
-    scale = []
-    for name, _, _ in datasets.channel_layout(tds):
-      stat = self._residual_scales if name in raw else self._scales
-      scale.append(_per_channel_stat(stat, name, tds[name], 1.0))
+    scale = self._target_scale(raw, targets)
     out = self.predictor.ensemble_scores(ni, nt, forcings=nf, **kwargs)
     if not isinstance(out, tuple):
-      return out.scaled(np.concatenate(scale))
+      return out.scaled(scale)
     scores, mean, var = out[0], datasets.as_dataset(out[1]), datasets.as_dataset(out[2])
     mean = Dataset({k: self._unnormalize_prediction_and_add_input(raw, k, v) for k, v in mean.items()}, mean.coords)
     squared = {True: self._residual_scales.map(np.square), False: self._scales.map(np.square)}
     var = Dataset({k: unnormalize(Dataset({k: v}), squared[k in raw], None)[k] for k, v in var.items()}, var.coords)
-    return scores.scaled(np.concatenate(scale)), datasets.like_inputs(mean, *given), datasets.like_inputs(var, *given)
+    return scores.scaled(scale), datasets.like_inputs(mean, *given), datasets.like_inputs(var, *given)
 
 
   def ensemble_order(self, inputs, targets, forcings=None, **kwargs):
@@ -211,20 +214,16 @@ class InputsAndResiduals:
     linear interpolation between two of them -- the quantile of the mapped members is the mapped quantile."""
     given = (targets, inputs, forcings)
     raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
-    tds = datasets.as_dataset(targets)
-    scale = []
-    for name, _, _ in datasets.channel_layout(tds):
-      stat = self._residual_scales if name in raw else self._scales
-      scale.append(_per_channel_stat(stat, name, tds[name], 1.0))
+    scale = self._target_scale(raw, targets)
     out = self.predictor.ensemble_order(ni, nt, forcings=nf, **kwargs)
     if not isinstance(out, tuple):
-      return out.scaled(np.concatenate(scale))
+      return out.scaled(scale)
     fields = []
     for f in out[1]:
       f = datasets.as_dataset(f)
       fields.append(datasets.like_inputs(Dataset({k: self._unnormalize_prediction_and_add_input(raw, k, v)
                                                   for k, v in f.items()}, f.coords), *given))
-    return out[0].scaled(np.concatenate(scale)), fields
+    return out[0].scaled(scale), fields
 
   def ensemble_climatology(self, inputs, targets, forcings=None, *, climatology, **kwargs):
     """`ensemble_climatology` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.
@@ -233,16 +232,12 @@ class InputsAndResiduals:
     so members, samples and truth differ from their physical values by one affine map x -> a x + b(point) per channel; the
     raw sums are scaled back (`ClimatologyScores.scaled`: b drops out of every term), nothing is recomputed."""
     raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
-    tds = datasets.as_dataset(targets)
-    scale = []
-    for name, _, _ in datasets.channel_layout(tds):
-      stat = self._residual_scales if name in raw else self._scales
-      scale.append(_per_channel_stat(stat, name, tds[name], 1.0))
+    scale = self._target_scale(raw, targets)
     nclim = []
     for c in climatology:
       c = datasets.as_dataset(c)
       nclim.append(Dataset({k: self._subtract_input_and_normalize_target(raw, k, v) for k, v in c.items()}, c.coords))
-    return self.predictor.ensemble_climatology(ni, nt, forcings=nf, climatology=nclim, **kwargs).scaled(np.concatenate(scale))
+    return self.predictor.ensemble_climatology(ni, nt, forcings=nf, climatology=nclim, **kwargs).scaled(scale)
 
   def ensemble_events(self, inputs, targets, forcings=None, *, spec, **kwargs):
     """`ensemble_events` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.
@@ -268,12 +263,7 @@ class InputsAndResiduals:
     rescaling of sums.  The error and spread spectra do not depend on that offset.  With `scores=True` the scores are
     rescaled as `ensemble_scores` does."""
     raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
-    tds = datasets.as_dataset(targets)
-    scale = []
-    for name, _, _ in datasets.channel_layout(tds):
-      stat = self._residual_scales if name in raw else self._scales
-      scale.append(_per_channel_stat(stat, name, tds[name], 1.0))
-    scale = np.concatenate(scale)
+    scale = self._target_scale(raw, targets)
     out = self.predictor.ensemble_spectra(ni, nt, forcings=nf, **kwargs)
     if not isinstance(out, tuple):
       return out.scaled(scale)
@@ -609,7 +599,50 @@ class _MemberNoise:
     return np.asarray(self._sampler.draw_noise(self._gen, shape, template), np.float32)
 
 
-class DerivedRolloutResult:
+# (attribute, score class, the word for it in an error message -- None: the raw twin of the row before it, or the scores
+# themselves: never checked on its own).  A new scorer adds its two rows here.
+_SERIES = (("scores", verification.EnsembleScores, None), ("scores_normalized", verification.EnsembleScores, None),
+           ("spectra", _spectra.EnsembleSpectra, "spectra"), ("spectra_normalized", _spectra.EnsembleSpectra, None),
+           ("events", verification.EventScores, "events"),
+           ("order", verification.OrderScores, "order statistics"), ("order_normalized", verification.OrderScores, None),
+           ("climatology", verification.ClimatologyScores, "climatology scores"),
+           ("climatology_normalized", verification.ClimatologyScores, None))
+
+
+class _SeriesResult:
+  """What the three results share: the rows of `_SERIES` a result carries (`_carries`), each a list with one entry per
+  lead time or None, and their merge."""
+  _carries: Sequence[str] = ()
+  _kind = "results"                                       # (as the merge's error messages name the two operands)
+
+  def _set_series(self, **series) -> None:
+    """Copies the series into lists (the scores first) and checks that the others cover the lead times of the scores."""
+    for name, _, word in _SERIES:
+      if name in self._carries:
+        setattr(self, name, None if series[name] is None else list(series[name]))
+        if word is not None and series[name] is not None and len(getattr(self, name)) != len(self.scores):
+          raise ValueError(f"scores and {word} must cover the same lead times")
+
+  def _merged_series(self, other) -> Dict[str, Optional[list]]:
+    """{attribute: the series of both results merged entry by entry (raw sums add), None where either has none}."""
+    rows = [row for row in _SERIES if row[0] in self._carries]
+    for name, _, word in rows:
+      if word is not None and (getattr(self, name) is None) != (getattr(other, name) is None):
+        raise ValueError(f"merge: only one of the two {self._kind} carries {word}")
+    both = lambda cls, a, b: None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
+    return {name: both(cls, getattr(self, name), getattr(other, name)) for name, cls, _ in rows}
+
+
+def _merge_named(a, b, word: str, names: str):
+  """The merge of two {name: result} parts of an `EnsembleRolloutResult` (None: the result has no such part)."""
+  if (a is None) != (b is None):
+    raise ValueError(f"merge: only one of the two results carries {word}")
+  if a is not None and sorted(a) != sorted(b):
+    raise ValueError(f"merge: the {names} names differ ({sorted(a)} and {sorted(b)})")
+  return None if a is None else {k: v.merge(b[k]) for k, v in a.items()}
+
+
+class DerivedRolloutResult(_SeriesResult):
   """The part of an `EnsembleRolloutResult` that belongs to one entry of `EnsembleRollout.run(derived=...)`: per lead time
   `scores[k]` (`verification.EnsembleScores` in the units of the derived variables: `scores_normalized[k].scaled(scale_d)`
   with `DerivedSpec.channel_stats`), `scores_normalized[k]` (as the device returned them), `events[k]`
@@ -620,40 +653,20 @@ class DerivedRolloutResult:
   `climatology_normalized[k]` (`verification.ClimatologyScores`, as `scores`): the derived members against the derived
   climatological samples."""
 
+  _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "climatology", "climatology_normalized")
+  _kind = "derived results"
+
   def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, order=None,
                order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None):
-    self.scores, self.scores_normalized = list(scores), list(scores_normalized)
-    self.events = None if events is None else list(events)
-    self.members, self.template = members, template
-    self.order = None if order is None else list(order)
-    self.order_normalized = None if order_normalized is None else list(order_normalized)
-    self.quantiles = quantiles
-    self.climatology = None if climatology is None else list(climatology)
-    self.climatology_normalized = None if climatology_normalized is None else list(climatology_normalized)
+    self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
+                     order_normalized=order_normalized, climatology=climatology, climatology_normalized=climatology_normalized)
+    self.members, self.template, self.quantiles = members, template, quantiles
 
   def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
-    from . import verification  # pylint: disable=import-outside-toplevel
-    if (self.events is None) != (other.events is None):
-      raise ValueError("merge: only one of the two derived results carries events")
-    if (self.order is None) != (other.order is None):
-      raise ValueError("merge: only one of the two derived results carries order statistics")
-    if (self.climatology is None) != (other.climatology is None):
-      raise ValueError("merge: only one of the two derived results carries climatology scores")
-    S, E, O, C = verification.EnsembleScores, verification.EventScores, verification.OrderScores, verification.ClimatologyScores
-
-    def both(a, b, cls=O):
-      return None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
-
-    return DerivedRolloutResult([S.merge([a, b]) for a, b in zip(self.scores, other.scores)],
-                                [S.merge([a, b]) for a, b in zip(self.scores_normalized, other.scores_normalized)],
-                                None if self.events is None else [E.merge([a, b]) for a, b in zip(self.events, other.events)],
-                                template=self.template, order=both(self.order, other.order),
-                                order_normalized=both(self.order_normalized, other.order_normalized),
-                                climatology=both(self.climatology, other.climatology, C),
-                                climatology_normalized=both(self.climatology_normalized, other.climatology_normalized, C))
+    return DerivedRolloutResult(template=self.template, **self._merged_series(other))
 
 
-class WindowRolloutResult:
+class WindowRolloutResult(_SeriesResult):
   """The part of an `EnsembleRolloutResult` that belongs to one entry of `EnsembleRollout.run(windows=...)`.  `leads`: the
   lead times that end a window (`WindowSpec.leads`), `steps`: the window length; per window i, ending at `leads[i]`,
   `scores[i]` (`verification.EnsembleScores` in physical units: `scores_normalized[i].scaled(scale)` with
@@ -662,38 +675,26 @@ class WindowRolloutResult:
   `run(order=...)`) and `members[i]` (`[M]` arrays [G, B, c] of the windowed members in the members' own units, or None);
   `template`: the Dataset of the source's variables for `per_variable`."""
 
+  _carries = ("scores", "scores_normalized", "events", "order", "order_normalized")
+  _kind = "window results"
+
   def __init__(self, leads, steps: int, scores, scores_normalized, events=None, order=None, members=None, template=None, *,
                order_normalized=None):
     self.leads, self.steps = [int(k) for k in leads], int(steps)
-    self.scores, self.scores_normalized = list(scores), list(scores_normalized)
+    self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
+                     order_normalized=order_normalized)
     if len(self.scores) != len(self.leads) or len(self.scores_normalized) != len(self.leads):
       raise ValueError("a window result needs one score per window lead time")
-    self.events = None if events is None else list(events)
-    self.order = None if order is None else list(order)
-    self.order_normalized = None if order_normalized is None else list(order_normalized)
     self.members, self.template = members, template
 
   def merge(self, other: "WindowRolloutResult") -> "WindowRolloutResult":
     """The result over the union of the start dates, window by window: raw sums add; members belong to one date."""
-    from . import verification  # pylint: disable=import-outside-toplevel
     if self.leads != other.leads or self.steps != other.steps:
       raise ValueError(f"merge: the windows differ (steps {self.steps} and {other.steps}, leads {self.leads} and {other.leads})")
-    if (self.events is None) != (other.events is None):
-      raise ValueError("merge: only one of the two window results carries events")
-    if (self.order is None) != (other.order is None):
-      raise ValueError("merge: only one of the two window results carries order statistics")
-    S, E, O = verification.EnsembleScores, verification.EventScores, verification.OrderScores
-
-    def both(a, b, cls):
-      return None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
-
-    return WindowRolloutResult(self.leads, self.steps, both(self.scores, other.scores, S),
-                               both(self.scores_normalized, other.scores_normalized, S), both(self.events, other.events, E),
-                               both(self.order, other.order, O), template=self.template,
-                               order_normalized=both(self.order_normalized, other.order_normalized, O))
+    return WindowRolloutResult(self.leads, self.steps, template=self.template, **self._merged_series(other))
 
 
-class EnsembleRolloutResult:
+class EnsembleRolloutResult(_SeriesResult):
   """What `EnsembleRollout.run` returns.  `scores`: one `verification.EnsembleScores` per lead time; `spectra`: one
   `spectra.EnsembleSpectra` per lead time, or None; `mean` / `variance`: the ensemble mean and variance fields on the
   targets' time axis (physical units), or None; `members`: `[horizon][M]` arrays [G, B, c_out] in the members' own
@@ -707,31 +708,18 @@ class EnsembleRolloutResult:
   `scores_normalized`) -- anomaly correlation and CRPS skill score against the samples of `run(climatology=...)` -- or None.
   `windows`: {name: `WindowRolloutResult`} for the entries of `run(windows=...)`, or None."""
 
+  _carries = tuple(row[0] for row in _SERIES)
+
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
                scores_normalized=None, spectra_normalized=None, events=None, derived=None, order=None,
                order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, windows=None):
-    self.scores = list(scores)
-    self.windows = None if windows is None else dict(windows)
-    self.climatology = None if climatology is None else list(climatology)
-    self.climatology_normalized = None if climatology_normalized is None else list(climatology_normalized)
-    if self.climatology is not None and len(self.climatology) != len(self.scores):
-      raise ValueError("scores and climatology scores must cover the same lead times")
-    self.order = None if order is None else list(order)
-    self.order_normalized = None if order_normalized is None else list(order_normalized)
-    self.quantiles = quantiles
-    if self.order is not None and len(self.order) != len(self.scores):
-      raise ValueError("scores and order statistics must cover the same lead times")
+    self._set_series(scores=scores, scores_normalized=scores_normalized, spectra=spectra, spectra_normalized=spectra_normalized,
+                     events=events, order=order, order_normalized=order_normalized, climatology=climatology,
+                     climatology_normalized=climatology_normalized)
     self.derived = None if derived is None else dict(derived)
-    self.events = None if events is None else list(events)
-    if self.events is not None and len(self.events) != len(self.scores):
-      raise ValueError("scores and events must cover the same lead times")
-    self.spectra = None if spectra is None else list(spectra)
-    self.scores_normalized = None if scores_normalized is None else list(scores_normalized)
-    self.spectra_normalized = None if spectra_normalized is None else list(spectra_normalized)
-    self.mean, self.variance, self.members = mean, variance, members
+    self.windows = None if windows is None else dict(windows)
+    self.mean, self.variance, self.members, self.quantiles = mean, variance, members, quantiles
     self.n_members = int(n_members if n_members is not None else self.scores[0].n_members)
-    if self.spectra is not None and len(self.spectra) != len(self.scores):
-      raise ValueError("scores and spectra must cover the same lead times")
 
   @property
   def horizon(self) -> int:
@@ -741,117 +729,116 @@ class EnsembleRolloutResult:
     """The result over the union of the start dates, lead time by lead time (`EnsembleScores.merge`,
     `EnsembleSpectra.merge`, `OrderScores.merge`, `ClimatologyScores.merge`: raw sums add).  Fields, members and quantile fields belong to one date
     and are dropped."""
-    from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
     if other.horizon != self.horizon:
       raise ValueError(f"merge: horizons differ ({self.horizon} and {other.horizon})")
     if other.n_members != self.n_members:
       raise ValueError(f"merge: member counts differ ({self.n_members} and {other.n_members})")
-    if (self.spectra is None) != (other.spectra is None):
-      raise ValueError("merge: only one of the two results carries spectra")
-    if (self.events is None) != (other.events is None):
-      raise ValueError("merge: only one of the two results carries events")
-    if (self.order is None) != (other.order is None):
-      raise ValueError("merge: only one of the two results carries order statistics")
-    if (self.climatology is None) != (other.climatology is None):
-      raise ValueError("merge: only one of the two results carries climatology scores")
-    if (self.derived is None) != (other.derived is None):
-      raise ValueError("merge: only one of the two results carries derived scores")
-    if self.derived is not None and sorted(self.derived) != sorted(other.derived):
-      raise ValueError(f"merge: the derived names differ ({sorted(self.derived)} and {sorted(other.derived)})")
-    derived = None if self.derived is None else {k: v.merge(other.derived[k]) for k, v in self.derived.items()}
-    if (self.windows is None) != (other.windows is None):
-      raise ValueError("merge: only one of the two results carries windows")
-    if self.windows is not None and sorted(self.windows) != sorted(other.windows):
-      raise ValueError(f"merge: the window names differ ({sorted(self.windows)} and {sorted(other.windows)})")
-    windows = None if self.windows is None else {k: v.merge(other.windows[k]) for k, v in self.windows.items()}
-
-    def both(cls, a, b):
-      return None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
-
-    S, P = verification.EnsembleScores, _spectra.EnsembleSpectra
-    return EnsembleRolloutResult(both(S, self.scores, other.scores), both(P, self.spectra, other.spectra),
-                                 n_members=self.n_members,
-                                 scores_normalized=both(S, self.scores_normalized, other.scores_normalized),
-                                 spectra_normalized=both(P, self.spectra_normalized, other.spectra_normalized),
-                                 events=both(verification.EventScores, self.events, other.events), derived=derived,
-                                 order=both(verification.OrderScores, self.order, other.order),
-                                 order_normalized=both(verification.OrderScores, self.order_normalized, other.order_normalized),
-                                 climatology=both(verification.ClimatologyScores, self.climatology, other.climatology),
-                                 climatology_normalized=both(verification.ClimatologyScores, self.climatology_normalized,
-                                                             other.climatology_normalized), windows=windows)
+    series = self._merged_series(other)
+    return EnsembleRolloutResult(n_members=self.n_members, **series,
+                                 derived=_merge_named(self.derived, other.derived, "derived scores", "derived"),
+                                 windows=_merge_named(self.windows, other.windows, "windows", "window"))
 
 
-class _DerivedView:
-  """One entry of `EnsembleRollout.run(derived=...)`: its store (`verification.ScoredStore`), the scale and the template of
-  its channels, and what the lead times have yielded so far."""
+class _StoreSeries:
+  """One scored store of an `EnsembleRollout.run` -- the main store, the view of a `derived` entry or the store of a window --
+  as a `verification.ScoredStore`, the scale and the template of its channels, and what the lead times have yielded so far:
+  every series the store and the `keep_*` flags call for is a list, the others are None."""
 
-  def __init__(self, store, scale, template, keep_members: bool):
+  def __init__(self, store, scale, template, *, keep_members: bool = False, keep_quantiles: bool = False):
     self.store, self.scale, self.template = store, scale, template
     self.scores, self.raw = [], []
     self.events = None if store.events is None else []
-    self.members = [] if keep_members else None
     self.order, self.raw_order = ([], []) if store.order is not None else (None, None)
-    self.quantiles = None
+    self.quantiles = [] if store.order is not None and keep_quantiles else None
     self.clim, self.raw_clim = ([], []) if store.climatology is not None else (None, None)
+    self.members = [] if keep_members else None
 
-  def result(self) -> DerivedRolloutResult:
+  def score_lead(self, truth=None, *, want_fields: bool = False, after_score=None, clim_fields=None, n_samples=None,
+                 source_truth=None) -> None:
+    """Scores the store as it stands and appends to every series: the scores (the events ride with them), the order
+    statistics and their quantile fields, the climatology scores, the members -- in that order on the device.  `truth`,
+    `want_fields`: as `ScoredStore.score`; `after_score()`: what the caller downloads between the scores and the rest;
+    `clim_fields`, or `n_samples` and `source_truth`: as `ScoredStore.score_climatology`.  A new scorer adds its step here."""
+    raw, ev = self.store.score(truth, want_fields=want_fields)   # (the events: on the truth already on the device)
+    self.raw.append(raw)
+    self.scores.append(raw.scaled(self.scale))
+    if ev is not None:
+      self.events.append(ev)
+    if after_score is not None:
+      after_score()
+    if self.order is not None:
+      self.raw_order.append(self.store.score_order(None))  # (the truth is on the device already)
+      self.order.append(self.raw_order[-1].scaled(self.scale))
+      if self.quantiles is not None:
+        self.quantiles.append(self.store.quantile_fields())
+    if self.clim is not None:
+      self.raw_clim.append(self.store.score_climatology(clim_fields, None, n_samples=n_samples, source_truth=source_truth))
+      self.clim.append(self.raw_clim[-1].scaled(self.scale))
+    if self.members is not None:
+      self.members.append([self.store.handle.ens_download_member(m) for m in range(self.store.n_members)])
+
+  def derived_result(self) -> DerivedRolloutResult:
     return DerivedRolloutResult(self.scores, self.raw, self.events, self.members, self.template, order=self.order,
                                 order_normalized=self.raw_order, quantiles=self.quantiles, climatology=self.clim,
                                 climatology_normalized=self.raw_clim)
 
 
 class _WindowEntry:
-  """One entry of `EnsembleRollout.run(windows=...)`: its window handle as a `verification.ScoredStore` (the ring lives on
-  that handle), the handle its pushes come from, and what the window lead times have yielded so far."""
+  """One entry of `EnsembleRollout.run(windows=...)`: its window handle's store as a `_StoreSeries` (the ring lives on that
+  handle) and the handle its pushes come from."""
 
-  def __init__(self, spec, store, source, scale, template, horizon: int, keep_members: bool):
-    self.spec, self.store, self.source, self.scale, self.template = spec, store, source, scale, template
+  def __init__(self, spec, series: _StoreSeries, source, horizon: int):
+    self.spec, self.series, self.source = spec, series, source
     self.leads = spec.leads(horizon)
-    self.scores, self.raw = [], []
-    self.events = None if store.events is None else []
-    self.order, self.raw_order = ([], []) if store.order is not None else (None, None)
-    self.members = [] if keep_members else None
 
   def start(self) -> None:
     """Before the first lead time: the store, what is scored on it, the plan, and an empty ring."""
-    self.store.setup()
-    self.store.handle.ens_window_set(**self.spec.plan())
-    self.store.handle.ens_window_reset()
+    self.series.store.setup()
+    self.series.store.handle.ens_window_set(**self.spec.plan())
+    self.series.store.handle.ens_window_reset()
 
   def push(self) -> None:
     """The source's members and truth as they stand (the truth of the lead is on the device already) into the ring."""
-    self.store.handle.ens_window_push(self.source, None)
+    self.series.store.handle.ens_window_push(self.source, None)
 
   def finish_lead(self, k: int) -> None:
     """At a lead time that ends a window: the window into the store, scored there like any other store."""
-    if k not in self.leads:
-      return
-    self.store.handle.ens_window_emit()
-    raw, ev = self.store.score(None)
-    self.raw.append(raw)
-    self.scores.append(raw.scaled(self.scale))
-    if ev is not None:
-      self.events.append(ev)
-    if self.order is not None:
-      self.raw_order.append(self.store.score_order(None))
-      self.order.append(self.raw_order[-1].scaled(self.scale))
-    if self.members is not None:
-      self.members.append([self.store.handle.ens_download_member(m) for m in range(self.store.n_members)])
+    if k in self.leads:
+      self.series.store.handle.ens_window_emit()
+      self.series.score_lead()
 
   def result(self) -> WindowRolloutResult:
-    return WindowRolloutResult(self.leads, self.spec.steps, self.scores, self.raw, self.events, self.order, self.members,
-                               self.template, order_normalized=self.raw_order)
+    s = self.series
+    return WindowRolloutResult(self.leads, self.spec.steps, s.scores, s.raw, s.events, s.order, s.members, s.template,
+                               order_normalized=s.raw_order)
 
 
 class _EnsembleRun:
-  """The state of one `EnsembleRollout.run`: what `_setup` made (handles, plan, noise sources, the main store and the
-  derived views) and the per-lead results `_score_lead` appends."""
+  """The state of one `EnsembleRollout.run`: what `_setup` made (handles, plan, noise sources, the main store `main`, the
+  derived `views` and the `windows`) and the fields and spectra `_score_lead` appends next to the main store's series."""
 
   def __init__(self):
-    self.scores, self.raw_scores, self.means, self.variances = [], [], [], []
+    self.means, self.variances = [], []
     self.thresholds = None                                # per EventSpec, in the members' units
-    self.views: Dict[str, _DerivedView] = {}
+    self.views: Dict[str, _StoreSeries] = {}
     self.windows: Dict[str, _WindowEntry] = {}
+
+
+def _to_members_units(x: np.ndarray, scale, loc, normalized: bool) -> np.ndarray:
+  """[..., c] physical values in the members' units: (x - l) / s in float64, rounded once; without a norm one plain cast."""
+  return ((x.astype(np.float64) - loc) / scale).astype(np.float32) if normalized else x.astype(np.float32)
+
+
+def _members_units(ds, shape, scale, loc, normalized: bool) -> np.ndarray:
+  """A Dataset as [G, B, c] in the members' units (`_to_members_units`)."""
+  ds = datasets.as_dataset(ds)
+  x = np.transpose(datasets.dataset_to_stacked(ds, ds.sizes), (1, 2, 0, 3)).reshape(shape)
+  return _to_members_units(x, scale, loc, normalized)
+
+
+def _spec_entries(entries) -> Dict[str, tuple]:
+  """The entries of `derived=` / `windows=` as {name: (spec, EventSpec or None)}."""
+  return {name: tuple(entry) if isinstance(entry, (tuple, list)) else (entry, None) for name, entry in (entries or {}).items()}
 
 
 class EnsembleRollout:
@@ -953,8 +940,7 @@ class EnsembleRollout:
     if self.world_size > 1:
       raise ValueError("EnsembleRollout needs all members on one rank (world_size == 1): bring the other "
                        "ranks' members over and push them with NativeDenoiser.ens_push_host")
-    for name, entry in (windows or {}).items():
-      wspec = entry[0] if isinstance(entry, (tuple, list)) else entry
+    for name, (wspec, _) in _spec_entries(windows).items():
       if wspec.source is not None and wspec.source not in (derived or {}):
         raise ValueError(f"window {name!r}: its source {wspec.source!r} names no entry of `derived` ({sorted(derived or {})})")
     given = (targets, inputs, forcings)
@@ -972,18 +958,18 @@ class EnsembleRollout:
       self._sample_lead(run, k, forcings, horizon)
       self._score_lead(run, k, targets)
       self.last_lead_ms.append(1e3 * (_time.perf_counter() - t0))
-    return EnsembleRolloutResult(run.scores, run.spectra, _on_time_axis(run.means, given, horizon) if fields else None,
-                                 _on_time_axis(run.variances, given, horizon) if fields else None, run.members, M,
-                                 scores_normalized=run.raw_scores, spectra_normalized=run.raw_spectra, events=run.events,
-                                 derived=None if derived is None else {k: v.result() for k, v in run.views.items()},
-                                 order=run.order, order_normalized=run.raw_order, quantiles=run.quantiles,
-                                 climatology=run.clim, climatology_normalized=run.raw_clim,
+    main = run.main
+    return EnsembleRolloutResult(main.scores, run.spectra, _on_time_axis(run.means, given, horizon) if fields else None,
+                                 _on_time_axis(run.variances, given, horizon) if fields else None, main.members, M,
+                                 scores_normalized=main.raw, spectra_normalized=run.raw_spectra, events=main.events,
+                                 derived=None if derived is None else {k: v.derived_result() for k, v in run.views.items()},
+                                 order=main.order, order_normalized=main.raw_order, quantiles=main.quantiles,
+                                 climatology=main.clim, climatology_normalized=main.raw_clim,
                                  windows=None if windows is None else {k: v.result() for k, v in run.windows.items()})
 
   def _setup(self, inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields, keep_members,
              events, derived, order=None, keep_quantiles=False, climatology=None, windows=None) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views."""
-    from . import spectra as _spectra, verification  # pylint: disable=import-outside-toplevel
     run = _EnsembleRun()
     context = isel_time(inputs, slice(-context_steps, None))
     template0 = isel_time(targets, slice(0, 1)).map(np.zeros_like)
@@ -1015,12 +1001,10 @@ class EnsembleRollout:
     loc = self._stat(None if norm is None else norm._locations, template0, 0.0)
 
     def packed(spec, template, s, l):
-      """The thresholds in the members' units: the map of the truth, (thr - l) / s in float64, rounded once."""
-      thr = spec.packed(template)
-      return thr if norm is None else ((thr.astype(np.float64) - l) / s).astype(np.float32)
+      """The thresholds [T, G, B, c] in the members' units: the map of the truth."""
+      return _to_members_units(spec.packed(template), s, l, norm is not None)
 
-    entries = {name: entry if isinstance(entry, (tuple, list)) else (entry, None) for name, entry in (derived or {}).items()}
-    wentries = {name: entry if isinstance(entry, (tuple, list)) else (entry, None) for name, entry in (windows or {}).items()}
+    entries, wentries = _spec_entries(derived), _spec_entries(windows)
     weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
     wq = None
     if (events is not None or any(dev is not None for _, dev in entries.values())
@@ -1037,11 +1021,11 @@ class EnsembleRollout:
     run.climatology = climatology
     clim_handle = None if climatology is None else den.climatology_handle(den.dims.c_out)
     # one spec: uploaded once, it survives the store and every lead time; else the one of the lead, before it is scored
-    run.main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
-                                        thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
-                                        set_per_score=specs is not None and len(specs) > 1, order=order,
-                                        climatology=clim_handle)
-    run.main.reserve()
+    main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
+                                    thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
+                                    set_per_score=specs is not None and len(specs) > 1, order=order, climatology=clim_handle)
+    run.main = _StoreSeries(main, scale, template0, keep_members=keep_members, keep_quantiles=keep_quantiles)
+    main.reserve()
     if spectra:
       _spectra.ensure_tables(native, template0, lmax)
 
@@ -1070,13 +1054,8 @@ class EnsembleRollout:
     run.scale, run.loc, run.normalized = scale, loc, norm is not None
     run.want_fields, run.want_spectra = bool(fields), bool(spectra)
     run.spectra, run.raw_spectra = ([], []) if spectra else (None, None)
-    run.members = [] if keep_members else None
-    run.events = None if specs is None else []
-    run.order, run.raw_order = ([], []) if order is not None else (None, None)
-    run.quantiles = [] if order is not None and keep_quantiles else None
-    run.clim, run.raw_clim = ([], []) if climatology is not None else (None, None)
-    if not run.main.set_per_score:
-      run.main.configure()
+    if not main.set_per_score:
+      main.configure()
 
     for name, (dspec, dev) in entries.items():
       dplan = dspec.plan(template0, scale, loc)
@@ -1088,9 +1067,7 @@ class EnsembleRollout:
                                        climatology=None if clim_handle is None
                                        else den.climatology_handle(len(dplan["op"]), view=True),
                                        climatology_source=clim_handle)
-      run.views[name] = _DerivedView(store, dscale, dtemplate, keep_members)
-      if run.quantiles is not None:
-        run.views[name].quantiles = []
+      run.views[name] = _StoreSeries(store, dscale, dtemplate, keep_members=keep_members, keep_quantiles=keep_quantiles)
     for store in (v.store for v in run.views.values()):
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
       store.set_per_score = sum(1 for v in run.views.values() if v.store.handle is store.handle) > 1
@@ -1108,7 +1085,7 @@ class EnsembleRollout:
       store = verification.ScoredStore(den.window_handle(len(wscale), name), M, weights, events=wev,
                                        thresholds=None if wev is None else packed(wev, stemplate, wscale, wloc), weight_q=wq,
                                        order=order)
-      run.windows[name] = _WindowEntry(wspec, store, source, wscale, stemplate, horizon, keep_members)
+      run.windows[name] = _WindowEntry(wspec, _StoreSeries(store, wscale, stemplate, keep_members=keep_members), source, horizon)
       run.windows[name].start()
     return run
 
@@ -1140,72 +1117,40 @@ class EnsembleRollout:
 
   @staticmethod
   def _score_lead(run: "_EnsembleRun", k: int, targets) -> None:
-    """Lead time k scored on the device: the main store against `targets[k]`, then every derived view."""
-    from . import spectra as _spectra  # pylint: disable=import-outside-toplevel
-    native, M, scale, loc = run.native, run.M, run.scale, run.loc
-    # the truth of lead k in the members' units: (y - l) / s in float64, rounded once
+    """Lead time k scored on the device: the main store against `targets[k]`, then every derived view, then the windows that
+    end here (`_StoreSeries.score_lead` each)."""
+    native, scale, loc = run.native, run.scale, run.loc
     tk = isel_time(targets, slice(k, k + 1))
-    y = np.transpose(datasets.dataset_to_stacked(tk, tk.sizes), (1, 2, 0, 3)).reshape(run.shape)
-    truth = ((y.astype(np.float64) - loc[None, None, :]) / scale[None, None, :]).astype(np.float32) if run.normalized \
-        else y.astype(np.float32)
-    if run.main.set_per_score:
-      run.main.thresholds = run.thresholds[k]
-    raw, ev = run.main.score(truth, want_fields=run.want_fields)   # (the events: on the truth already on the device)
-    run.raw_scores.append(raw)
-    run.scores.append(raw.scaled(scale))
-    if ev is not None:
-      run.events.append(ev)
-    if run.want_fields:
-      mean, var = native.ens_download_fields()
-      mean = (mean.astype(np.float64) * scale + loc).astype(np.float32)
-      var = (var.astype(np.float64) * scale * scale).astype(np.float32)
-      tmpl = tk.map(np.zeros_like)
-      run.means.append(Denoiser.unpack_outputs(mean, run.grid_shape, tmpl))
-      run.variances.append(Denoiser.unpack_outputs(var, run.grid_shape, tmpl))
-    if run.want_spectra:
-      run.raw_spectra.append(_spectra.EnsembleSpectra(native.ens_spectrum(None), M))   # the truth is on the device already
-      run.spectra.append(run.raw_spectra[-1].scaled(scale))
-    if run.order is not None:
-      run.raw_order.append(run.main.score_order(None))    # (the truth is on the device already)
-      run.order.append(run.raw_order[-1].scaled(scale))
-      if run.quantiles is not None:
-        run.quantiles.append(run.main.quantile_fields())
-    n_samples = 0
-    if run.clim is not None:
+    truth = _members_units(tk, run.shape, scale, loc, run.normalized)
+    if run.main.store.set_per_score:
+      run.main.store.thresholds = run.thresholds[k]
+
+    def fields_and_spectra():
+      if run.want_fields:
+        mean, var = native.ens_download_fields()
+        mean = (mean.astype(np.float64) * scale + loc).astype(np.float32)
+        var = (var.astype(np.float64) * scale * scale).astype(np.float32)
+        tmpl = tk.map(np.zeros_like)
+        run.means.append(Denoiser.unpack_outputs(mean, run.grid_shape, tmpl))
+        run.variances.append(Denoiser.unpack_outputs(var, run.grid_shape, tmpl))
+      if run.want_spectra:
+        run.raw_spectra.append(_spectra.EnsembleSpectra(native.ens_spectrum(None), run.M))   # the truth is on the device already
+        run.spectra.append(run.raw_spectra[-1].scaled(scale))
+
+    samples = None
+    if run.main.clim is not None:
       samples = list(run.climatology(k) if callable(run.climatology) else run.climatology[k])
       if not 2 <= len(samples) <= 64:
         raise ValueError(f"climatology of lead time {k}: 2..64 Datasets shaped like the targets, got {len(samples)}")
-      n_samples = len(samples)
-      packed = []
-      for c in samples:                                   # the map of the truth: (c - l) / s in float64, rounded once
-        c = datasets.as_dataset(c)
-        f = np.transpose(datasets.dataset_to_stacked(c, c.sizes), (1, 2, 0, 3)).reshape(run.shape)
-        packed.append(((f.astype(np.float64) - loc[None, None, :]) / scale[None, None, :]).astype(np.float32)
-                      if run.normalized else f.astype(np.float32))
-      run.raw_clim.append(run.main.score_climatology(packed, None))   # (the truth is on the device already)
-      run.clim.append(run.raw_clim[-1].scaled(scale))
-    if run.members is not None:
-      run.members.append([native.ens_download_member(m) for m in range(M)])
+      samples = [_members_units(c, run.shape, scale, loc, run.normalized) for c in samples]
+    run.main.score_lead(truth, want_fields=run.want_fields, after_score=fields_and_spectra, clim_fields=samples)
     for w in run.windows.values():
       if w.spec.source is None:
         w.push()
     for vname, v in run.views.items():
-      raw, ev = v.store.score(None)                       # members and truth, device to device
-      v.raw.append(raw)
-      v.scores.append(raw.scaled(v.scale))
-      if ev is not None:
-        v.events.append(ev)
-      if v.order is not None:
-        v.raw_order.append(v.store.score_order(None))
-        v.order.append(v.raw_order[-1].scaled(v.scale))
-        if v.quantiles is not None:
-          v.quantiles.append(v.store.quantile_fields())
-      if v.clim is not None:
-        # the samples in the main climatology handle's store, through the view's plan; that handle has no truth of its own
-        v.raw_clim.append(v.store.score_climatology(None, None, n_samples=n_samples, source_truth=truth))
-        v.clim.append(v.raw_clim[-1].scaled(v.scale))
-      if v.members is not None:
-        v.members.append([v.store.handle.ens_download_member(m) for m in range(M)])
+      # members and truth, device to device; the climatology: the samples in the main climatology handle's store, through the
+      # view's plan -- that handle has no truth of its own
+      v.score_lead(None, n_samples=None if samples is None else len(samples), source_truth=truth)
       for w in run.windows.values():                      # (two views may share a handle: the view's fields are there NOW)
         if w.spec.source == vname:
           w.push()

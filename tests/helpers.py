@@ -70,6 +70,107 @@ def small_graph(n_lat=13, n_lon=24, mesh_size=2, k_hop=2):
   return geometry.build_denoiser_graph(grid_lat=lat, grid_lon=lon, mesh_size=mesh_size, attention_k_hop=k_hop)
 
 
+class RecordingHandle:
+  """A stand-in for `_lib.NativeDenoiser` that needs no device: every call appends `(name, call, *details)` to the shared
+  list `log` and returns arrays of the shapes the library returns -- `G` nodes, batch `B`, `C` channels, `M` members --
+  filled with the number of times that call has been made on this handle (1.0 the first time), so two results that were
+  appended in another order are not equal.  `details` is what the host-side tests assert on: the scalars, `truth is None`,
+  the name of another handle.  With `full=True` the remaining arguments follow them, so that the log pins every value
+  handed to the device, and a method the class does not define is logged by its name and arguments (without `full` it is an
+  AttributeError: a binding call the test did not expect)."""
+
+  def __init__(self, name, log, M=4, B=2, C=3, G=4, Q=0, full=False):
+    self.name, self.calls, self.M, self.B, self.C, self.G, self.full = name, log, M, B, C, G, full
+    self.Q, self.T = Q, 0                                   # quantile probabilities (until `ens_order_set`) / events set
+    self._made = {}
+
+  def _log(self, call, *details, full=()):
+    self.calls.append((self.name, call) + details + (tuple(full) if self.full else ()))
+    self._made[call] = self._made.get(call, 0) + 1
+
+  def _filled(self, call, shape, dtype=np.float64):
+    return np.full(shape, self._made[call], dtype)
+
+  def __getattr__(self, call):
+    if call.startswith("_") or not self.full:               # (without `full`, a call no test expects is an error)
+      raise AttributeError(call)
+    return lambda *args, **kwargs: self._log(call, full=args + tuple(sorted(kwargs.items())))
+
+  def cond_device_ptr(self):
+    self._log("cond_device_ptr")
+    return self.name + ".cond", 0
+
+  def ens_reserve(self, n):
+    self._log("reserve", n)
+
+  def ens_set_node_weight(self, w):
+    self._log("weight", full=(w,))
+
+  def ens_push(self, slot, src=None):
+    self._log("push", slot, getattr(src, "name", None))
+
+  def ens_push_host(self, slot, field):
+    self._log("push_host", slot, float(np.asarray(field).ravel()[0]), full=(field,))
+
+  def ens_event_set(self, thr, directions, wq):
+    self.T = len(directions)
+    self._log("event_set", np.asarray(thr).copy(), full=(directions, wq))
+
+  def ens_order_set(self, probs):
+    self.Q = len(probs)
+    self._log("order_set", tuple(probs))
+
+  def ens_derive_set(self, **plan):
+    self._log("derive_set", full=sorted(plan.items()))
+
+  def ens_derive(self, src, truth):
+    self._log("derive", getattr(src, "name", None), truth)
+
+  def ens_score(self, truth, want_fields=False):
+    self._log("score", truth is None, full=(truth, want_fields))
+    return self._filled("score", (self.B, self.C, 6)), self._filled("score", (self.B, self.C, self.M + 1), np.uint64)
+
+  def ens_download_fields(self):
+    self._log("download_fields")
+    return (self._filled("download_fields", (self.G, self.B, self.C), np.float32),
+            2 * self._filled("download_fields", (self.G, self.B, self.C), np.float32))
+
+  def ens_event_score(self, truth):
+    self._log("event_score", truth is None, full=(truth,))
+    table = self._filled("event_score", (self.T, self.B, self.C, 2, self.M + 1), np.uint64)
+    return table, table.copy(), np.zeros(self.T, np.uint64)
+
+  def ens_order_score(self, truth):
+    self._log("order_score", truth is None, full=(truth,))
+    return (self._filled("order_score", (self.B, self.C, self.M + 1, 2)), self._filled("order_score", (self.B, self.C, 3)),
+            self._filled("order_score", (self.B, self.C, self.Q)),
+            self._filled("order_score", (self.B, self.C, self.Q + 1), np.uint64), 0)
+
+  def ens_order_quantile(self, q):
+    self._log("quantile", q)
+    return np.full((self.G, self.B, self.C), float(q), np.float32)
+
+  def ens_clim_score(self, clim, truth):
+    self._log("clim_score", clim.name, truth is None, full=(truth,))
+    return self._filled("clim_score", (self.B, self.C, 12)), np.full((self.B, self.C), 5, np.uint64), 7
+
+  def ens_download_member(self, m):
+    self._log("download", m)
+    return np.full((self.G, self.B, self.C), float(m), np.float32)
+
+  def ens_window_set(self, kind, length, coef):
+    self._log("window_set", kind, length, None if coef is None else tuple(coef))
+
+  def ens_window_push(self, src, truth):
+    self._log("window_push", src.name, truth is None, full=(truth,))
+
+  def ens_window_emit(self):
+    self._log("window_emit")
+
+  def ens_window_reset(self):
+    self._log("window_reset")
+
+
 def graph_handle(gr, batch, c_out, latent=128, heads=2, ffw=256):
   """A handle that knows its graph and nothing else: no weights, no gc_finalize."""
   from gencast_flax_nnx_amd import _lib

@@ -7,6 +7,7 @@ import pytest
 from gencast_flax_nnx_amd import _lib, datasets, rollout, verification
 from gencast_flax_nnx_amd.verification import ClimatologyScores, EnsembleScores
 from tests import clim_reference as R
+from tests.helpers import RecordingHandle
 
 
 def _data(M, K, G=60, B=2, C=3, seed=0, offset=0.0):
@@ -179,37 +180,9 @@ def test_the_binding_checks_its_arguments_before_the_call():
 
 
 # ---- ScoredStore(climatology=...) with a handle that records ------------------------------------------------------------------
-class _FakeHandle:
-  def __init__(self, name, log, M=4, B=2, C=3):
-    self.name, self.calls, self.M, self.B, self.C = name, log, M, B, C
-
-  def ens_reserve(self, n):
-    self.calls.append((self.name, "reserve", n))
-
-  def ens_set_node_weight(self, w):
-    self.calls.append((self.name, "weight"))
-
-  def ens_push_host(self, slot, field):
-    self.calls.append((self.name, "push_host", slot, float(np.asarray(field).ravel()[0])))
-
-  def ens_derive_set(self, **plan):
-    self.calls.append((self.name, "derive_set"))
-
-  def ens_derive(self, src, truth):
-    self.calls.append((self.name, "derive", src.name, truth))
-
-  def ens_score(self, truth, want_fields=False):
-    self.calls.append((self.name, "score", truth is None))
-    return np.ones((self.B, self.C, 6)), np.ones((self.B, self.C, self.M + 1), np.uint64)
-
-  def ens_clim_score(self, clim, truth):
-    self.calls.append((self.name, "clim_score", clim.name, truth is None))
-    return np.ones((self.B, self.C, 12)), np.full((self.B, self.C), 5, np.uint64), 7
-
-
 def test_scored_store_pushes_the_samples_and_scores():
   log = []
-  h, c = _FakeHandle("main", log), _FakeHandle("clim", log)
+  h, c = RecordingHandle("main", log), RecordingHandle("clim", log)
   st = verification.ScoredStore(h, 4, np.ones(6, np.float32), climatology=c)
   st.setup()
   assert log == [("main", "reserve", 4), ("main", "weight")]             # the climatology's store: sized by the first K
@@ -236,7 +209,7 @@ def test_scored_store_pushes_the_samples_and_scores():
 
 def test_a_derived_view_derives_its_climatology_from_the_source_climatology():
   log = []
-  src, view, csrc, cview = (_FakeHandle(n, log) for n in ("src", "view", "csrc", "cview"))
+  src, view, csrc, cview = (RecordingHandle(n, log) for n in ("src", "view", "csrc", "cview"))
   st = verification.ScoredStore(view, 4, np.ones(6, np.float32), plan={"op": [0]}, source=src, climatology=cview,
                                 climatology_source=csrc)
   st.setup()

@@ -8,6 +8,7 @@ import pytest
 from gencast_flax_nnx_amd import _lib, rollout, verification
 from gencast_flax_nnx_amd.verification import EnsembleScores, OrderScores
 from tests import order_reference as R
+from tests.helpers import RecordingHandle
 
 PROBS = (0.0, 0.1, 0.5, 0.9, 1.0)
 
@@ -198,70 +199,36 @@ def test_binding_rejects_bad_probabilities_before_the_c_call():
 
 
 # ---- ScoredStore(order=...) with a handle that records ----------------------------------------------------------------------
-class _FakeHandle:
-  def __init__(self, M, B=2, C=3, Q=2):
-    self.calls, self.M, self.B, self.C, self.Q = [], M, B, C, Q
-
-  def ens_reserve(self, n):
-    self.calls.append(("reserve", n))
-
-  def ens_set_node_weight(self, w):
-    self.calls.append(("weight",))
-
-  def ens_derive_set(self, **plan):
-    self.calls.append(("derive_set",))
-
-  def ens_derive(self, src, truth):
-    self.calls.append(("derive", truth is None))
-
-  def ens_order_set(self, probs):
-    self.calls.append(("order_set", tuple(probs)))
-    self.Q = len(probs)
-
-  def ens_score(self, truth, want_fields=False):
-    self.calls.append(("score", truth is None))
-    return np.ones((self.B, self.C, 6)), np.ones((self.B, self.C, self.M + 1), np.uint64)
-
-  def ens_order_score(self, truth):
-    self.calls.append(("order_score", truth is None))
-    return (np.ones((self.B, self.C, self.M + 1, 2)), np.ones((self.B, self.C, 3)), np.ones((self.B, self.C, self.Q)),
-            np.ones((self.B, self.C, self.Q + 1), np.uint64), 0)
-
-  def ens_order_quantile(self, q):
-    self.calls.append(("quantile", q))
-    return np.full((4, self.B, self.C), float(q), np.float32)
-
-
 def test_scored_store_sets_the_probabilities_and_scores_the_order():
-  h = _FakeHandle(8)
+  h = RecordingHandle("h", [], M=8)
   st = verification.ScoredStore(h, 8, np.ones(4, np.float32), order=[0.1, 0.9])
   st.setup()
-  assert h.calls == [("reserve", 8), ("weight",), ("order_set", (0.1, 0.9))]
+  assert h.calls == [("h", "reserve", 8), ("h", "weight"), ("h", "order_set", (0.1, 0.9))]
   out = st.score_order("truth")
   assert isinstance(out, OrderScores) and out.n_members == 8 and out.probs == (0.1, 0.9)
-  assert h.calls[-1] == ("order_score", False)
+  assert h.calls[-1] == ("h", "order_score", False)
   assert [f[0, 0, 0] for f in st.quantile_fields()] == [0.0, 1.0]
   # without `order` nothing of it is touched
-  h2 = _FakeHandle(8)
+  h2 = RecordingHandle("h2", [], M=8)
   plain = verification.ScoredStore(h2, 8, np.ones(4, np.float32))
   plain.setup()
   assert plain.score_order(None) is None and plain.order is None
-  assert all(c[0] not in ("order_set", "order_score") for c in h2.calls)
+  assert all(c[1] not in ("order_set", "order_score") for c in h2.calls)
   # set per score: the setting is made again by every scoring call, not by setup
-  h3 = _FakeHandle(8)
+  h3 = RecordingHandle("h3", [], M=8)
   per = verification.ScoredStore(h3, 8, np.ones(4, np.float32), order=(), set_per_score=True)
   per.setup()
-  assert ("order_set", ()) not in h3.calls
+  assert ("h3", "order_set", ()) not in h3.calls
   assert per.score_order(None).pinball.shape == (2, 3, 0)
-  assert h3.calls[-2:] == [("order_set", ()), ("order_score", True)]
+  assert h3.calls[-2:] == [("h3", "order_set", ()), ("h3", "order_score", True)]
   # a derived view: filled by `score`, then sorted on the truth already there
-  h4 = _FakeHandle(8)
+  h4 = RecordingHandle("h4", [], M=8)
   view = verification.ScoredStore(h4, 8, np.ones(4, np.float32), plan={"op": [0]}, source=object(), order=(0.5,))
   view.setup()
   view.score("source truth")
   view.score_order(None)
-  assert [c[0] for c in h4.calls] == ["reserve", "weight", "derive_set", "order_set", "derive", "score", "order_score"]
-  assert h4.calls[-1] == ("order_score", True)
+  assert [c[1] for c in h4.calls] == ["reserve", "weight", "derive_set", "order_set", "derive", "score", "order_score"]
+  assert h4.calls[-1] == ("h4", "order_score", True)
 
 
 # ---- rollout results --------------------------------------------------------------------------------------------------------

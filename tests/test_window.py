@@ -10,6 +10,7 @@ import pytest
 from gencast_flax_nnx_amd import _lib, datasets, rollout, verification
 from gencast_flax_nnx_amd.verification import EnsembleScores, EventScores, EventSpec, WindowSpec
 from tests import window_reference as R
+from tests.helpers import RecordingHandle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ["gc_ens_window_set", "gc_ens_window_push", "gc_ens_window_emit", "gc_ens_window_reset"]
@@ -150,58 +151,8 @@ def test_the_binding_checks_its_arguments_before_the_call():
 G, B, C, M = 6, 1, 2, 3
 
 
-class _FakeHandle:
-  def __init__(self, name, log):
-    self.name, self.calls = name, log
-
-  def _log(self, *what):
-    self.calls.append((self.name,) + what)
-
-  def ens_reserve(self, n):
-    self._log("reserve", n)
-
-  def ens_set_node_weight(self, w):
-    self._log("weight")
-
-  def ens_event_set(self, thr, directions, wq):
-    self._log("event_set", np.asarray(thr).copy())
-
-  def ens_order_set(self, probs):
-    self._log("order_set", tuple(probs))
-
-  def ens_derive_set(self, **plan):
-    self._log("derive_set")
-
-  def ens_derive(self, src, truth):
-    self._log("derive", src.name)
-
-  def ens_score(self, truth, want_fields=False):
-    self._log("score", truth is None)
-    return np.ones((B, C, 6)), np.ones((B, C, M + 1), np.uint64)
-
-  def ens_event_score(self, truth):
-    self._log("event_score", truth is None)
-    return np.ones((1, B, C, 2, M + 1), np.uint64), np.ones((1, B, C, 2, M + 1), np.uint64), np.zeros(1, np.uint64)
-
-  def ens_order_score(self, truth):
-    self._log("order_score", truth is None)
-    return np.ones((B, C, M + 1, 2)), np.ones((B, C, 3)), np.ones((B, C, 1)), np.ones((B, C, 2), np.uint64), 0
-
-  def ens_download_member(self, m):
-    self._log("download", m)
-    return np.full((G, B, C), float(m), np.float32)
-
-  def ens_window_set(self, kind, length, coef):
-    self._log("window_set", kind, length, None if coef is None else tuple(coef))
-
-  def ens_window_push(self, src, truth):
-    self._log("window_push", src.name, truth is None)
-
-  def ens_window_emit(self):
-    self._log("window_emit")
-
-  def ens_window_reset(self):
-    self._log("window_reset")
+def _FakeHandle(name, log):
+  return RecordingHandle(name, log, M=M, B=B, C=C, G=G, Q=1)      # (the hand-made main store and view are never set up)
 
 
 def _targets(horizon):
@@ -220,19 +171,19 @@ def _run(horizon, windows, log, order=None, keep_members=True):
   run = rollout._EnsembleRun()
   main, view = _FakeHandle("main", log), _FakeHandle("view", log)
   run.native, run.M, run.scale, run.loc, run.shape, run.normalized = main, M, np.ones(C), np.zeros(C), (G, B, C), False
-  run.main = verification.ScoredStore(main, M, w, order=order)
+  run.main = rollout._StoreSeries(verification.ScoredStore(main, M, w, order=order), np.ones(C), None, keep_members=keep_members)
+  run.scores = run.main.scores                           # (the tests below read the main store's scores as `run.scores`)
   run.want_fields = run.want_spectra = False
-  run.events, run.clim, run.raw_clim, run.members = None, None, None, [] if keep_members else None
-  run.order, run.raw_order, run.quantiles = ([], [], None) if order is not None else (None, None, None)
   vstore = verification.ScoredStore(view, M, w, plan={"op": [0, 0]}, source=main, order=order)
-  run.views["view"] = rollout._DerivedView(vstore, np.ones(C), None, keep_members)
+  run.views["view"] = rollout._StoreSeries(vstore, np.ones(C), None, keep_members=keep_members)
   template = rollout.isel_time(_targets(1), slice(0, 1))
   for name, entry in windows.items():
     spec, ev = entry if isinstance(entry, tuple) else (entry, None)
     source = main if spec.source is None else view
     store = verification.ScoredStore(_FakeHandle(name, log), M, w, events=ev, weight_q=wq, order=order,
                                      thresholds=None if ev is None else ev.packed(template))
-    run.windows[name] = rollout._WindowEntry(spec, store, source, np.ones(C), template, horizon, keep_members)
+    series = rollout._StoreSeries(store, np.ones(C), template, keep_members=keep_members)
+    run.windows[name] = rollout._WindowEntry(spec, series, source, horizon)
     run.windows[name].start()
   return run
 
