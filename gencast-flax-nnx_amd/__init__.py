@@ -23,6 +23,9 @@ Public surface (mirrors the reference's call contracts):
                       samples held by a second handle (GenCast.ensemble_climatology, EnsembleRollout.run(climatology=...))
                       WindowSpec: accumulations, means, changes and extremes over the last lead times of a rollout, formed
                       on the GPU from a ring of member stores (EnsembleRollout.run(windows=...))
+                      EnergySpec / VariogramSpec: the energy score over groups of variables and the variogram score over
+                      grid offsets, from pair sums formed on the GPU (GenCast.ensemble_multivariate,
+                      EnsembleRollout.run(energy=..., variogram=...))
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
@@ -40,7 +43,8 @@ from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, Ense
                       WindowRolloutResult, autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
-from .verification import ClimatologyScores, DerivedSpec, EnsembleScores, EventScores, EventSpec, OrderScores, WindowSpec  # noqa: F401
+from .verification import (ClimatologyScores, DerivedSpec, EnergyScores, EnergySpec, EnsembleScores, EventScores,  # noqa: F401
+                           EventSpec, OrderScores, VariogramScores, VariogramSpec, WindowSpec)
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
@@ -48,4 +52,4 @@ __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_
            "compute_loss", "validation_loss", "verification", "EnsembleScores", "spectra", "EnsembleSpectra",
            "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec",
            "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores",
-           "WindowSpec", "WindowRolloutResult"]
+           "WindowSpec", "WindowRolloutResult", "EnergySpec", "EnergyScores", "VariogramSpec", "VariogramScores"]

@@ -135,6 +135,11 @@ SIGNATURES = {
     "gc_ens_window_push": (ctypes.c_int, [_hp, _hp, _f32p]),
     "gc_ens_window_emit": (ctypes.c_int, [_hp]),
     "gc_ens_window_reset": (ctypes.c_int, [_hp]),
+    "gc_ens_energy_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_energy_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_variogram_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.c_double]),
+    "gc_ens_variogram_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -228,6 +233,8 @@ class NativeDenoiser:
     self._event_thresholds = 0                 # threshold fields this object handed to the handle
     self._derive_c_src = 0                     # source channels of the derive plan this object handed to the handle
     self._order_quantiles = None               # probabilities this object handed to the handle (None: ens_order_set not called)
+    self._energy_groups = None                 # groups of the energy plan this object set (None: ens_energy_set not called)
+    self._variogram_offsets = None             # offsets of the variogram plan this object set (None: ens_variogram_set not called)
     self._window_length = 0                    # length of the window plan this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
@@ -786,6 +793,85 @@ class NativeDenoiser:
     self._check(self._lib.gc_ens_clim_score(self._h, clim._h, None if t is None else _ptr(t, _f32p),  # pylint: disable=protected-access
                                             _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(counts, u64), _ptr(invalid, u64)))
     return sums, counts, int(invalid[0])
+
+  # -- multivariate ensemble scores (energy over channel groups, variogram over grid offsets) -----------
+  def _truth_arg(self, truth):
+    if truth is None:
+      return None
+    t = _f32(truth)
+    if t.shape != self._shape_out():
+      raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    return t
+
+  def ens_energy_set(self, n_groups: int, group, scale) -> None:
+    """The plan of `ens_energy_score` (gc_ens_energy_set; needs `set_graph` only and survives `ens_reserve`): `group` [c_out]
+    int, the group 0 .. n_groups - 1 of every channel or -1 for none; `scale` [c_out] float64, a[c] > 0 of the grouped
+    channels.  `verification.EnergySpec` builds these arguments."""
+    K = int(n_groups)
+    g = np.ascontiguousarray(group, dtype=np.int32)
+    a = np.ascontiguousarray(scale, dtype=np.float64)
+    C = self.cfg.c_out
+    if g.shape != (C,) or a.shape != (C,):
+      raise ValueError(f"group and scale must be [{C}], got {g.shape} and {a.shape}")
+    if not 1 <= K <= 32:
+      raise ValueError("n_groups must be in 1..32")
+    if g.min() < -1 or g.max() >= K or set(range(K)) - set(g.tolist()):
+      raise ValueError("group must map every channel to -1 or 0 .. n_groups - 1 and leave no group empty")
+    if not np.all(np.isfinite(a[g >= 0]) & (a[g >= 0] > 0.0)):
+      raise ValueError("scale must be finite and > 0 for grouped channels")
+    self._check(self._lib.gc_ens_energy_set(self._h, K, _ptr(g, _i32p), _ptr(a, ctypes.POINTER(ctypes.c_double))))
+    self._energy_groups = K
+
+  def ens_energy_score(self, truth=None):
+    """-> (d2 [B, K, P] float64, s0 [B, K] float64, invalid int): the raw sums of gc_ens_energy_score over the member store,
+    P = M (M + 1) / 2 pairs (i < j, index j (j - 1) / 2 + i, slot M the truth); `verification.EnergyScores` derives the
+    scores.  `truth` [G, B, c_out], or None = the truth uploaded last (shared with `ens_score`)."""
+    if self._energy_groups is None:
+      raise GencastHipError("libgencast_hip error 4: no plan (ens_energy_set has not been called on this object)")
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    t = self._truth_arg(truth)
+    B, K, M = self.cfg.batch, self._energy_groups, self._ens_members
+    dp, u64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)
+    d2 = np.empty((B, K, M * (M + 1) // 2), dtype=np.float64)
+    s0 = np.empty((B, K), dtype=np.float64)
+    invalid = np.zeros(1, dtype=np.uint64)
+    self._check(self._lib.gc_ens_energy_score(self._h, None if t is None else _ptr(t, _f32p), _ptr(d2, dp), _ptr(s0, dp),
+                                              _ptr(invalid, u64)))
+    return d2, s0, int(invalid[0])
+
+  def ens_variogram_set(self, n_lat: int, n_lon: int, offsets, p: float) -> None:
+    """The plan of `ens_variogram_score` (gc_ens_variogram_set; needs `set_graph` only and survives `ens_reserve`): the grid
+    `n_lat` x `n_lon` (node = i n_lon + j), `offsets` [O, 2] int (di, dj), O in 1..16, and the order `p` in {0.5, 1, 2}."""
+    o = np.ascontiguousarray(offsets, dtype=np.int32)
+    if o.ndim != 2 or o.shape[1] != 2 or not 1 <= o.shape[0] <= 16:
+      raise ValueError(f"offsets must be [O, 2] with O in 1..16, got {o.shape}")
+    if float(p) not in (0.5, 1.0, 2.0):
+      raise ValueError("p must be 0.5, 1 or 2")
+    n_lat, n_lon = int(n_lat), int(n_lon)
+    if n_lat * n_lon != self.num_grid_nodes:
+      raise ValueError(f"n_lat * n_lon must be the number of grid nodes {self.num_grid_nodes}")
+    if np.any((o == 0).all(axis=1)) or np.any(np.abs(o[:, 0]) >= n_lat) or np.any(np.abs(o[:, 1]) >= n_lon):
+      raise ValueError("an offset is (0, 0) or reaches beyond the grid")
+    self._check(self._lib.gc_ens_variogram_set(self._h, n_lat, n_lon, o.shape[0], _ptr(o, _i32p), float(p)))
+    self._variogram_offsets = int(o.shape[0])
+
+  def ens_variogram_score(self, truth=None):
+    """-> (sums [4, B, c_out, O] float64: V0 .. V3, counts [B, c_out, O] uint64): the raw, additive sums of
+    gc_ens_variogram_score over the member store; `verification.VariogramScores` derives the scores.  `truth` [G, B, c_out],
+    or None = the truth uploaded last (shared with `ens_score`)."""
+    if self._variogram_offsets is None:
+      raise GencastHipError("libgencast_hip error 4: no plan (ens_variogram_set has not been called on this object)")
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    t = self._truth_arg(truth)
+    B, C, O = self.cfg.batch, self.cfg.c_out, self._variogram_offsets
+    sums = np.empty((4, B, C, O), dtype=np.float64)
+    counts = np.empty((B, C, O), dtype=np.uint64)
+    self._check(self._lib.gc_ens_variogram_score(self._h, None if t is None else _ptr(t, _f32p),
+                                                 _ptr(sums, ctypes.POINTER(ctypes.c_double)),
+                                                 _ptr(counts, ctypes.POINTER(ctypes.c_uint64))))
+    return sums, counts
 
   # -- time-window ensemble fields (a ring of the last lead times, reduced into this handle's member store) --
   def ens_window_set(self, kind: int, length: int, coef=None) -> None:

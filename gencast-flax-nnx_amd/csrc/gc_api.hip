@@ -879,6 +879,11 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "ens_clim_calls") *value = h->clim_calls;
   else if (n == "ens_clim_device_us") *value = h->clim_device_us;
   else if (n == "ens_clim_invalid_points") *value = h->clim_invalid_points;
+  else if (n == "ens_energy_calls") *value = h->en_calls;
+  else if (n == "ens_energy_device_us") *value = h->en_device_us;
+  else if (n == "ens_energy_invalid_points") *value = h->en_invalid_points;
+  else if (n == "ens_variogram_calls") *value = h->vg_calls;
+  else if (n == "ens_variogram_device_us") *value = h->vg_device_us;
   else if (n == "ens_window_pushes") *value = h->win_pushes;
   else if (n == "ens_window_emits") *value = h->win_emits;
   else if (n == "ens_window_device_us") *value = h->win_device_us;

@@ -11,7 +11,8 @@
 //   gc_order.hip     gc_ens_order_*
 //   gc_clim.hip      gc_ens_clim_score
 //   gc_window.hip    gc_ens_window_*
-// The last seven are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
+//   gc_multivar.hip  gc_ens_energy_*, gc_ens_variogram_*
+// The last eight are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
 // lead times of another).  What they share -- field length, upload through
 // the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
 // relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
@@ -375,6 +376,31 @@ struct gc_handle {
   gci::Bracket win_time{events};                 // of the last emit
   gci::Event ev_win_src{events};                 // stream order behind the source handle
   int64_t win_emits = 0, win_device_us = 0;
+
+  // multivariate ensemble scores (gc_ens_energy_*, gc_ens_variogram_*, gc_multivar.hip): the two plans and their sums
+  gci::BufferGroup en_allocs{groups};             // the energy plan's tables: freed and replaced by gc_ens_energy_set
+  gci::BufferGroup en_work_allocs{groups};        // sized by M and the plan: made again by the scoring call that finds either changed
+  bool en_set = false;                           // an energy plan has been set
+  int en_K = 0, en_nc_max = 0;                   // groups; channels of the largest
+  int *d_en_gchan = nullptr, *d_en_goff = nullptr;   // the channels of the groups, group after group; [K + 1] where each starts
+  double* d_en_scale = nullptr;                  // [c_out] a[c]
+  int en_work_M = 0, en_work_K = 0, en_work_blocks = 0;   // what the partial and result buffers are sized for
+  double* d_en_part = nullptr;                   // [blocks][B K][P] per-block pair sums, then [blocks][B K] per-block S0
+  unsigned* d_en_ipart = nullptr;                // [blocks][B K] skipped points
+  double* d_en_out = nullptr;                    // D2 [B][K][P], then S0 [B][K]
+  unsigned long long* d_en_outc = nullptr;       // the skipped points of the call
+  gci::Bracket en_time{events};                  // of the last energy call
+  int64_t en_calls = 0, en_device_us = 0, en_invalid_points = 0;
+  gci::BufferGroup vg_allocs{groups};             // the variogram plan and the buffers sized by it: replaced by gc_ens_variogram_set
+  bool vg_set = false;                           // a variogram plan has been set
+  int vg_O = 0, vg_pk = 0, vg_n_lat = 0, vg_n_lon = 0;   // offsets; order 0 (p = 0.5), 1, 2; the grid
+  int* d_vg_offs = nullptr;                      // [O][2] (di, dj)
+  double* d_vg_part = nullptr;                   // [blocks][O][4][B c_out] per-block column sums
+  unsigned* d_vg_cpart = nullptr;                // [blocks][O][B c_out] per-block valid pairs
+  double* d_vg_out = nullptr;                    // [4][B c_out][O]
+  unsigned long long* d_vg_outc = nullptr;       // [B c_out][O]
+  gci::Bracket vg_time{events};                  // of the last variogram call
+  int64_t vg_calls = 0, vg_device_us = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

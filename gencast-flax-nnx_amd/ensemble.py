@@ -141,15 +141,27 @@ class EnsembleSampler:
       raise ValueError(f"climatology must be 2..64 Datasets shaped like the targets, got {len(climatology)}")
     return self._run(inputs, targets, forcings, num_members, None, climatology=climatology)
 
+  def multivariate(self, inputs, targets, forcings, num_members: int, energy=None, variogram=None):
+    """Runs the members as `scores` does and forms, on the device, the two proper scores of a JOINT forecast: with `energy`
+    (a `verification.EnergySpec`: groups of variables) the energy score of every group, with `variogram` (a
+    `verification.VariogramSpec`: grid offsets and an order) the variogram score of every channel at every offset.
+    -> (`verification.EnergyScores` or None, `verification.VariogramScores` or None), both in the units of `targets`.
+    No member is downloaded."""
+    self._one_rank("multivariate")
+    if energy is None and variogram is None:
+      raise ValueError("multivariate needs an EnergySpec, a VariogramSpec or both")
+    return self._run(inputs, targets, forcings, num_members, None, multivariate=(energy, variogram))
+
   def _spectral(self, inputs, targets, forcings, num_members, score_fields, lmax):
     self._one_rank("spectra")
     return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
 
   def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,
-           lmax: Optional[int] = None, events=None, derived=None, order=None, climatology=None):
+           lmax: Optional[int] = None, events=None, derived=None, order=None, climatology=None, multivariate=None):
     """`score_fields` None: members come back as Datasets (`__call__`) or, with `spectral`, only their spectra are
     formed, or, with `events` (an EventSpec), only their event tables, or, with `order` (probabilities, want fields), only
-    their order statistics, or, with `climatology` (K Datasets), only their skill against it; else they are scored
+    their order statistics, or, with `climatology` (K Datasets), only their skill against it, or, with `multivariate` (an
+    EnergySpec or None, a VariogramSpec or None), only their energy and variogram scores; else they are scored
     (`scores`), with `spectral` both."""
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
@@ -178,17 +190,23 @@ class EnsembleSampler:
         lane.upload_cond_dev(ptr)                          # device-to-device, on the lane's own stream
     scoring = score_fields is not None
     main = None                                            # lane 0's member store, where anything is scored at all
-    if scoring or spectral or events is not None or derived is not None or order is not None or climatology is not None:
+    if (scoring or spectral or events is not None or derived is not None or order is not None or climatology is not None or
+        multivariate is not None):
       dspec, dev = derived if derived is not None else (None, None)
       weights = None if spectral and not scoring else verification.node_weights(template)
       wq = None if events is None and dev is None else verification.quantize_node_weights(weights)
       # (scored once: the thresholds are set by that call, after the members are in)
       main = verification.ScoredStore(native, num_members,
-                                      weights if scoring or order is not None or climatology is not None else None,
+                                      weights if scoring or order is not None or climatology is not None or
+                                      multivariate is not None else None,
                                       events=events, thresholds=None if events is None else events.packed(template), weight_q=wq,
                                       set_per_score=True, order=None if order is None else order[0],
                                       climatology=None if climatology is None
-                                      else self._denoiser.climatology_handle(self._denoiser.dims.c_out))
+                                      else self._denoiser.climatology_handle(self._denoiser.dims.c_out),
+                                      energy=None if multivariate is None or multivariate[0] is None
+                                      else multivariate[0].plan(template),
+                                      variogram=None if multivariate is None or multivariate[1] is None
+                                      else multivariate[1].plan(template))
       main.setup()
     if spectral:
       _spectra.ensure_tables(native, template, lmax)
@@ -221,6 +239,9 @@ class EnsembleSampler:
       pack = lambda ds: np.transpose(datasets.dataset_to_stacked(datasets.as_dataset(ds), template.sizes),
                                      (1, 2, 0, 3)).reshape(shape)
       return main.score_climatology([pack(c) for c in climatology], truth)
+    if multivariate is not None:
+      en = main.score_energy(truth)
+      return en, main.score_variogram(truth if en is None else None)      # (the truth is on the device after the first)
     if order is not None:
       scores = main.score_order(truth)
       if not order[1]:

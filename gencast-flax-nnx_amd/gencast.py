@@ -138,6 +138,16 @@ class GenCast:
     runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.order(inputs, targets, forcings, num_members, probs, quantile_fields=quantile_fields)
 
+  def ensemble_multivariate(self, inputs, targets, forcings=None, *, num_members, energy=None, variogram=None, rngs=0,
+                            concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and forms on the GPU the two standard proper scores of
+    a joint forecast, which no marginal score sees: with `energy` (`verification.EnergySpec`: groups of variables, e.g. the
+    two wind components, or a whole field) the energy score of every group, with `variogram` (`verification.VariogramSpec`:
+    grid offsets and an order p) the variogram score per batch member, channel and offset, latitude-weighted.
+    -> (`verification.EnergyScores` or None, `verification.VariogramScores` or None).  No member leaves the device."""
+    runner = self._ensemble_sampler(rngs, concurrent_members)
+    return runner.multivariate(inputs, targets, forcings, num_members, energy, variogram)
+
   def ensemble_climatology(self, inputs, targets, forcings=None, *, num_members, climatology, rngs=0, concurrent_members=1):
     """Samples `num_members` (2..64) members as `ensemble_scores` does and scores them on the GPU against `climatology`,
     K (2..64) Datasets shaped like `targets` (past states for the same calendar date; a climatological mean is given

@@ -128,6 +128,11 @@ class NaNCleaner:
       return out
     return out[0], [datasets.like_inputs(datasets.as_dataset(f), *given) for f in out[1]]
 
+  def ensemble_multivariate(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """Inputs and forcings are cleaned; the targets pass through unchanged, as in `ensemble_scores`: their NaNs are
+    points the device skips (`EnergyScores.invalid`) and ends of pairs it does not count."""
+    return self.predictor.ensemble_multivariate(*self._cleaned(inputs, targets, forcings, False), **kwargs)
+
   def ensemble_climatology(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """Inputs and forcings are cleaned; the targets and the climatology pass through unchanged: their NaNs are points
     the device does not count (`ClimatologyScores.invalid`)."""

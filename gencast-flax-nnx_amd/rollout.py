@@ -225,6 +225,16 @@ class InputsAndResiduals:
                                                   for k, v in f.items()}, f.coords), *given))
     return out[0].scaled(scale), fields
 
+  def ensemble_multivariate(self, inputs, targets, forcings=None, **kwargs):
+    """`ensemble_multivariate` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.
+    The variogram sums are scaled back to physical units (`VariogramScores.scaled`: the location drops out of every
+    difference).  The energy score STAYS in normalised residual units: a norm over several variables has a meaning only
+    where they are comparable, and there is no single factor that would take it back."""
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    scale = self._target_scale(raw, targets)
+    en, vg = self.predictor.ensemble_multivariate(ni, nt, forcings=nf, **kwargs)
+    return en, None if vg is None else vg.scaled(scale)
+
   def ensemble_climatology(self, inputs, targets, forcings=None, *, climatology, **kwargs):
     """`ensemble_climatology` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.
     Every climatological sample (physical units) goes through the SAME map as the targets
@@ -600,13 +610,19 @@ class _MemberNoise:
 
 
 # (attribute, score class, the word for it in an error message -- None: the raw twin of the row before it, or the scores
-# themselves: never checked on its own).  A new scorer adds its two rows here.
+# themselves: never checked on its own).  A new scorer adds its rows here AND its names to `_SeriesResult._optional`: a result
+# that was not given such a series keeps no instance attribute for it, so `vars(result)` of a run that does not use the scorer
+# is what it was before the scorer existed (tests/golden/rollout_call_sequence.json records it).  The rows up to
+# "climatology_normalized" predate that rule and are always set.
 _SERIES = (("scores", verification.EnsembleScores, None), ("scores_normalized", verification.EnsembleScores, None),
            ("spectra", _spectra.EnsembleSpectra, "spectra"), ("spectra_normalized", _spectra.EnsembleSpectra, None),
            ("events", verification.EventScores, "events"),
            ("order", verification.OrderScores, "order statistics"), ("order_normalized", verification.OrderScores, None),
            ("climatology", verification.ClimatologyScores, "climatology scores"),
-           ("climatology_normalized", verification.ClimatologyScores, None))
+           ("climatology_normalized", verification.ClimatologyScores, None),
+           ("energy", verification.EnergyScores, "energy scores"),
+           ("variogram", verification.VariogramScores, "variogram scores"),
+           ("variogram_normalized", verification.VariogramScores, None))
 
 
 class _SeriesResult:
@@ -614,11 +630,16 @@ class _SeriesResult:
   lead time or None, and their merge."""
   _carries: Sequence[str] = ()
   _kind = "results"                                       # (as the merge's error messages name the two operands)
+  # series that exist on an instance only when the run asked for them; the class holds their None (see `_SERIES`)
+  _optional = ("energy", "variogram", "variogram_normalized")
+  energy = variogram = variogram_normalized = None
 
   def _set_series(self, **series) -> None:
     """Copies the series into lists (the scores first) and checks that the others cover the lead times of the scores."""
     for name, _, word in _SERIES:
       if name in self._carries:
+        if series[name] is None and name in self._optional:
+          continue                                        # (the class's None stands)
         setattr(self, name, None if series[name] is None else list(series[name]))
         if word is not None and series[name] is not None and len(getattr(self, name)) != len(self.scores):
           raise ValueError(f"scores and {word} must cover the same lead times")
@@ -651,15 +672,20 @@ class DerivedRolloutResult(_SeriesResult):
   `run(order=...)` also `order[k]` / `order_normalized[k]` (`verification.OrderScores`, as `scores`) and, when asked for,
   `quantiles[k]` (`[Q]` arrays [G, B, c_d] in the members' own units).  With `run(climatology=...)` also `climatology[k]` /
   `climatology_normalized[k]` (`verification.ClimatologyScores`, as `scores`): the derived members against the derived
-  climatological samples."""
+  climatological samples.  With `run(energy=...)` / `run(variogram=...)` also `energy[k]` (`verification.EnergyScores` over the
+  groups whose variables are all derived variables of this entry, in the members' own units; None where no group is) and
+  `variogram[k]` / `variogram_normalized[k]` (`verification.VariogramScores`, as `scores`)."""
 
-  _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "climatology", "climatology_normalized")
+  _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "climatology", "climatology_normalized",
+              "energy", "variogram", "variogram_normalized")
   _kind = "derived results"
 
   def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, order=None,
-               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None):
+               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, energy=None,
+               variogram=None, variogram_normalized=None):
     self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
-                     order_normalized=order_normalized, climatology=climatology, climatology_normalized=climatology_normalized)
+                     order_normalized=order_normalized, climatology=climatology, climatology_normalized=climatology_normalized,
+                     energy=energy, variogram=variogram, variogram_normalized=variogram_normalized)
     self.members, self.template, self.quantiles = members, template, quantiles
 
   def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
@@ -673,16 +699,20 @@ class WindowRolloutResult(_SeriesResult):
   `WindowSpec.channel_stats`), `scores_normalized[i]` (as the device returned them), `events[i]` (`verification.EventScores`,
   or None without an EventSpec), `order[i]` / `order_normalized[i]` (`verification.OrderScores`, or None without
   `run(order=...)`) and `members[i]` (`[M]` arrays [G, B, c] of the windowed members in the members' own units, or None);
-  `template`: the Dataset of the source's variables for `per_variable`."""
+  `template`: the Dataset of the source's variables for `per_variable`.  With `run(energy=...)` / `run(variogram=...)` also
+  `energy[i]` (`verification.EnergyScores` of the windowed fields, in the members' own units; None where no group names
+  variables of the source) and `variogram[i]` / `variogram_normalized[i]` (`verification.VariogramScores`, as `scores`)."""
 
-  _carries = ("scores", "scores_normalized", "events", "order", "order_normalized")
+  _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "energy", "variogram",
+              "variogram_normalized")
   _kind = "window results"
 
   def __init__(self, leads, steps: int, scores, scores_normalized, events=None, order=None, members=None, template=None, *,
-               order_normalized=None):
+               order_normalized=None, energy=None, variogram=None, variogram_normalized=None):
     self.leads, self.steps = [int(k) for k in leads], int(steps)
     self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
-                     order_normalized=order_normalized)
+                     order_normalized=order_normalized, energy=energy, variogram=variogram,
+                     variogram_normalized=variogram_normalized)
     if len(self.scores) != len(self.leads) or len(self.scores_normalized) != len(self.leads):
       raise ValueError("a window result needs one score per window lead time")
     self.members, self.template = members, template
@@ -706,16 +736,21 @@ class EnsembleRolloutResult(_SeriesResult):
   `scores_normalized`), or None; `quantiles`: `[horizon][Q]` arrays [G, B, c_out] in the members' own units (as `members`),
   or None.  `climatology` / `climatology_normalized`: one `verification.ClimatologyScores` per lead time (as `scores` /
   `scores_normalized`) -- anomaly correlation and CRPS skill score against the samples of `run(climatology=...)` -- or None.
-  `windows`: {name: `WindowRolloutResult`} for the entries of `run(windows=...)`, or None."""
+  `windows`: {name: `WindowRolloutResult`} for the entries of `run(windows=...)`, or None.  `energy`: one
+  `verification.EnergyScores` per lead time -- the energy score of the groups of `run(energy=...)`, in the members' own units
+  (normalised under a normalisation wrapper: what makes a norm over several variables meaningful) -- or None; `variogram` /
+  `variogram_normalized`: one `verification.VariogramScores` per lead time (as `scores` / `scores_normalized`), or None."""
 
   _carries = tuple(row[0] for row in _SERIES)
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
                scores_normalized=None, spectra_normalized=None, events=None, derived=None, order=None,
-               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, windows=None):
+               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, windows=None,
+               energy=None, variogram=None, variogram_normalized=None):
     self._set_series(scores=scores, scores_normalized=scores_normalized, spectra=spectra, spectra_normalized=spectra_normalized,
                      events=events, order=order, order_normalized=order_normalized, climatology=climatology,
-                     climatology_normalized=climatology_normalized)
+                     climatology_normalized=climatology_normalized, energy=energy, variogram=variogram,
+                     variogram_normalized=variogram_normalized)
     self.derived = None if derived is None else dict(derived)
     self.windows = None if windows is None else dict(windows)
     self.mean, self.variance, self.members, self.quantiles = mean, variance, members, quantiles
@@ -727,8 +762,8 @@ class EnsembleRolloutResult(_SeriesResult):
 
   def merge(self, other: "EnsembleRolloutResult") -> "EnsembleRolloutResult":
     """The result over the union of the start dates, lead time by lead time (`EnsembleScores.merge`,
-    `EnsembleSpectra.merge`, `OrderScores.merge`, `ClimatologyScores.merge`: raw sums add).  Fields, members and quantile fields belong to one date
-    and are dropped."""
+    `EnsembleSpectra.merge`, `OrderScores.merge`, `ClimatologyScores.merge`, `VariogramScores.merge`: raw sums add;
+    `EnergyScores.merge`: the forecasts of both).  Fields, members and quantile fields belong to one date and are dropped."""
     if other.horizon != self.horizon:
       raise ValueError(f"merge: horizons differ ({self.horizon} and {other.horizon})")
     if other.n_members != self.n_members:
@@ -751,12 +786,15 @@ class _StoreSeries:
     self.order, self.raw_order = ([], []) if store.order is not None else (None, None)
     self.quantiles = [] if store.order is not None and keep_quantiles else None
     self.clim, self.raw_clim = ([], []) if store.climatology is not None else (None, None)
+    self.energy = None if store.energy is None else []
+    self.variogram, self.raw_variogram = ([], []) if store.variogram is not None else (None, None)
     self.members = [] if keep_members else None
 
   def score_lead(self, truth=None, *, want_fields: bool = False, after_score=None, clim_fields=None, n_samples=None,
                  source_truth=None) -> None:
     """Scores the store as it stands and appends to every series: the scores (the events ride with them), the order
-    statistics and their quantile fields, the climatology scores, the members -- in that order on the device.  `truth`,
+    statistics and their quantile fields, the climatology scores, the energy and variogram scores, the members -- in that
+    order on the device.  `truth`,
     `want_fields`: as `ScoredStore.score`; `after_score()`: what the caller downloads between the scores and the rest;
     `clim_fields`, or `n_samples` and `source_truth`: as `ScoredStore.score_climatology`.  A new scorer adds its step here."""
     raw, ev = self.store.score(truth, want_fields=want_fields)   # (the events: on the truth already on the device)
@@ -774,13 +812,19 @@ class _StoreSeries:
     if self.clim is not None:
       self.raw_clim.append(self.store.score_climatology(clim_fields, None, n_samples=n_samples, source_truth=source_truth))
       self.clim.append(self.raw_clim[-1].scaled(self.scale))
+    if self.energy is not None:
+      self.energy.append(self.store.score_energy(None))    # (in the store's own units: there is no `scaled`)
+    if self.variogram is not None:
+      self.raw_variogram.append(self.store.score_variogram(None))
+      self.variogram.append(self.raw_variogram[-1].scaled(self.scale))
     if self.members is not None:
       self.members.append([self.store.handle.ens_download_member(m) for m in range(self.store.n_members)])
 
   def derived_result(self) -> DerivedRolloutResult:
     return DerivedRolloutResult(self.scores, self.raw, self.events, self.members, self.template, order=self.order,
                                 order_normalized=self.raw_order, quantiles=self.quantiles, climatology=self.clim,
-                                climatology_normalized=self.raw_clim)
+                                climatology_normalized=self.raw_clim, energy=self.energy, variogram=self.variogram,
+                                variogram_normalized=self.raw_variogram)
 
 
 class _WindowEntry:
@@ -810,7 +854,8 @@ class _WindowEntry:
   def result(self) -> WindowRolloutResult:
     s = self.series
     return WindowRolloutResult(self.leads, self.spec.steps, s.scores, s.raw, s.events, s.order, s.members, s.template,
-                               order_normalized=s.raw_order)
+                               order_normalized=s.raw_order, energy=s.energy, variogram=s.variogram,
+                               variogram_normalized=s.raw_variogram)
 
 
 class _EnsembleRun:
@@ -890,7 +935,8 @@ class EnsembleRollout:
   def run(self, inputs, targets, forcings, horizon: int, num_members: int, *, context_steps: int = 2,
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
           keep_members: bool = False, events=None, derived=None, order=None,
-          keep_quantiles: bool = False, climatology=None, windows=None) -> EnsembleRolloutResult:
+          keep_quantiles: bool = False, climatology=None, windows=None, energy=None,
+          variogram=None) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -927,6 +973,16 @@ class EnsembleRollout:
     source's variable names, in physical units, and take the map of `WindowSpec.channel_stats`.  With `keep_members` the
     windowed members are downloaded too.  `climatology` does not reach the windows: skill of a windowed field needs the
     window of every climatological sample, which is not built.  Without `windows` nothing changes.
+    `energy`: a `verification.EnergySpec` (groups of variables, e.g. the two components of the 10 m wind, or every level of
+    the geopotential): per lead time, after the scores, the energy score of every group over the member states
+    (`gc_ens_energy_score`, on the truth already there): `EnsembleRolloutResult.energy` (`verification.EnergyScores`), in the
+    members' own units -- normalised under a normalisation wrapper, which is what makes a norm over several variables
+    meaningful.  A store is scored over the groups whose variables it all has: the main store and the windows on it by the
+    names of `targets`, a `derived` entry and the windows on it by its derived names; a group that fits no store is an
+    error.  `variogram`: a `verification.VariogramSpec` (grid offsets, an order p): per lead time the variogram score of
+    every channel at every offset (`gc_ens_variogram_score`): `EnsembleRolloutResult.variogram` in physical units
+    (`VariogramScores.scaled`), `variogram_normalized` as the device returned it, and the same for every `derived` entry
+    and every window.  Without them nothing changes.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -948,10 +1004,18 @@ class EnsembleRollout:
     M = int(num_members)
     if horizon < 1 or targets.sizes.get("time", 0) < horizon:
       raise ValueError(f"targets carry {targets.sizes.get('time', 0)} time steps (need horizon = {horizon})")
+    if energy is not None:                                # every group must fit a store: the main one or a derived view
+      template0 = isel_time(targets, slice(0, 1)).map(np.zeros_like)
+      fitted = set()
+      for template in [template0] + [dspec.template(template0) for dspec, _ in _spec_entries(derived).values()]:
+        part = energy.restricted(template)
+        fitted.update(() if part is None else part.names)
+      if set(energy.names) - fitted:
+        raise ValueError(f"energy: the groups {sorted(set(energy.names) - fitted)} name variables that no scored store has all of")
     if init_noise is not None and (len(init_noise) != M or any(len(z) < horizon for z in init_noise)):
       raise ValueError("init_noise must be [num_members][horizon] fields")
     run = self._setup(inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields,
-                      keep_members, events, derived, order, keep_quantiles, climatology, windows)
+                      keep_members, events, derived, order, keep_quantiles, climatology, windows, energy, variogram)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -965,10 +1029,12 @@ class EnsembleRollout:
                                  derived=None if derived is None else {k: v.derived_result() for k, v in run.views.items()},
                                  order=main.order, order_normalized=main.raw_order, quantiles=main.quantiles,
                                  climatology=main.clim, climatology_normalized=main.raw_clim,
-                                 windows=None if windows is None else {k: v.result() for k, v in run.windows.items()})
+                                 windows=None if windows is None else {k: v.result() for k, v in run.windows.items()},
+                                 energy=main.energy, variogram=main.variogram, variogram_normalized=main.raw_variogram)
 
   def _setup(self, inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields, keep_members,
-             events, derived, order=None, keep_quantiles=False, climatology=None, windows=None) -> "_EnsembleRun":
+             events, derived, order=None, keep_quantiles=False, climatology=None, windows=None, energy=None,
+             variogram=None) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views."""
     run = _EnsembleRun()
     context = isel_time(inputs, slice(-context_steps, None))
@@ -1005,6 +1071,13 @@ class EnsembleRollout:
       return _to_members_units(spec.packed(template), s, l, norm is not None)
 
     entries, wentries = _spec_entries(derived), _spec_entries(windows)
+    # the multivariate plans: the offsets are the grid's, the same for every store; the groups go by a store's variable names
+    vplan = None if variogram is None else variogram.plan(template0)
+
+    def eplan(template):
+      part = None if energy is None else energy.restricted(template)
+      return None if part is None else part.plan(template)
+
     weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
     wq = None
     if (events is not None or any(dev is not None for _, dev in entries.values())
@@ -1023,7 +1096,8 @@ class EnsembleRollout:
     # one spec: uploaded once, it survives the store and every lead time; else the one of the lead, before it is scored
     main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
                                     thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
-                                    set_per_score=specs is not None and len(specs) > 1, order=order, climatology=clim_handle)
+                                    set_per_score=specs is not None and len(specs) > 1, order=order, climatology=clim_handle,
+                                    energy=eplan(template0), variogram=vplan)
     run.main = _StoreSeries(main, scale, template0, keep_members=keep_members, keep_quantiles=keep_quantiles)
     main.reserve()
     if spectra:
@@ -1063,7 +1137,7 @@ class EnsembleRollout:
       dscale, dloc = dspec.channel_stats(template0, scale, loc)
       store = verification.ScoredStore(den.view_handle(len(dplan["op"])), M, weights, events=dev,
                                        thresholds=None if dev is None else packed(dev, dtemplate, dscale, dloc), weight_q=wq,
-                                       plan=dplan, source=native, order=order,
+                                       plan=dplan, source=native, order=order, energy=eplan(dtemplate), variogram=vplan,
                                        climatology=None if clim_handle is None
                                        else den.climatology_handle(len(dplan["op"]), view=True),
                                        climatology_source=clim_handle)
@@ -1084,7 +1158,7 @@ class EnsembleRollout:
       wscale, wloc = wspec.channel_stats(sscale, sloc)
       store = verification.ScoredStore(den.window_handle(len(wscale), name), M, weights, events=wev,
                                        thresholds=None if wev is None else packed(wev, stemplate, wscale, wloc), weight_q=wq,
-                                       order=order)
+                                       order=order, energy=eplan(stemplate), variogram=vplan)
       run.windows[name] = _WindowEntry(wspec, _StoreSeries(store, wscale, stemplate, keep_members=keep_members), source, horizon)
       run.windows[name].start()
     return run

@@ -34,6 +34,12 @@ fields it leaves on the device.  `OrderScores` keeps them raw and derives reliab
 Skill against a climatology (`gc_ens_clim_score`): the device reads the M members and, from the store
 of a second handle, K climatological samples of every point, and hands back twelve raw sums per (batch, channel).
 `ClimatologyScores` keeps them raw and derives the anomaly correlation of the ensemble mean and the CRPS skill score.
+
+Multivariate scores (`gc_ens_energy_score`, `gc_ens_variogram_score`): every score above is marginal.
+For `EnergySpec` groups of channels the device hands back the weighted squared distances D2 between every pair of the
+M + 1 fields (members and truth) and `EnergyScores` derives the energy score; for `VariogramSpec` grid offsets it hands
+back four additive sums per (batch, channel, offset) and `VariogramScores` derives the variogram score and the roughness
+of the members against the truth's.
 """
 from __future__ import annotations
 
@@ -992,6 +998,276 @@ class WindowSpec:
 
 
 # ---------------------------------------------------------------------------------------------
+# multivariate scores: energy over channel groups, variogram over grid offsets (gc_ens_energy_*, gc_ens_variogram_*)
+# ---------------------------------------------------------------------------------------------
+class EnergySpec:
+  """Groups of target variables whose joint forecast the energy score judges: `groups` {group name: [variable, ..]}, 1 to
+  32 of them, every variable in at most one group; a variable brings all its channels (levels).  `weights` {variable:
+  a scalar or one value per channel of the variable}, finite and > 0 (default 1): the a[c] of the norm -- level or variable
+  weights.  The score is formed in the units of the member store (normalised residuals under the usual wrappers), which is
+  what makes a norm over several variables meaningful."""
+
+  def __init__(self, groups: Mapping[str, Sequence[str]], weights: Optional[Mapping[str, object]] = None):
+    self.groups = {str(k): tuple(str(v) for v in vs) for k, vs in groups.items()}
+    self.weights = {str(k): np.asarray(v, dtype=np.float64) for k, v in (weights or {}).items()}
+    if not 1 <= len(self.groups) <= 32:
+      raise ValueError("an EnergySpec has 1 to 32 groups")
+    seen = set()
+    for g, vs in self.groups.items():
+      if not vs:
+        raise ValueError(f"group {g!r} is empty")
+      for v in vs:
+        if v in seen:
+          raise ValueError(f"variable {v!r} is in more than one group")
+        seen.add(v)
+    for v, w in self.weights.items():
+      if v not in seen:
+        raise ValueError(f"a weight is given for {v!r}, which is in no group")
+      if not np.all(np.isfinite(w) & (w > 0.0)):
+        raise ValueError(f"weights[{v!r}] must be finite and > 0")
+
+  @property
+  def names(self) -> Tuple[str, ...]:
+    return tuple(self.groups)
+
+  def restricted(self, template) -> Optional["EnergySpec"]:
+    """The spec of the groups whose variables are all variables of `template` (None: there is no such group)."""
+    have = set(datasets.as_dataset(template).keys())
+    groups = {g: vs for g, vs in self.groups.items() if set(vs) <= have}
+    if not groups:
+      return None
+    used = {v for vs in groups.values() for v in vs}
+    return EnergySpec(groups, {v: w for v, w in self.weights.items() if v in used})
+
+  def plan(self, template) -> Dict[str, object]:
+    """The arguments of `NativeDenoiser.ens_energy_set` in the channel order of `datasets.channel_layout(template)`, with
+    the group `names`."""
+    layout = {name: (off, n) for name, off, n in datasets.channel_layout(datasets.as_dataset(template))}
+    C = sum(n for _, n in layout.values())
+    group = np.full(C, -1, dtype=np.int32)
+    scale = np.ones(C, dtype=np.float64)
+    for k, vs in enumerate(self.groups.values()):
+      for v in vs:
+        if v not in layout:
+          raise ValueError(f"{v!r} is not a target variable")
+        off, n = layout[v]
+        group[off:off + n] = k
+        if v in self.weights:
+          w = self.weights[v].reshape(-1)
+          if w.shape[0] not in (1, n):
+            raise ValueError(f"weights[{v!r}] must be a scalar or have {n} values, got {w.shape[0]}")
+          scale[off:off + n] = w
+    return {"n_groups": len(self.groups), "group": group, "scale": scale, "names": self.names}
+
+
+class EnergyScores:
+  """The energy score of F forecasts over K groups: `err` and `pair` [F, K] float64 with the member count M, where for one
+  forecast, D[i][j] = sqrt(D2 / S0) the weighted root-mean-square distance between fields i and j (slot M: the truth),
+
+    err = mean_i D[i][M]      pair = mean_{i<j<M} D[i][j]
+    fair ES = err - pair / 2      ensemble ES = err - (M - 1) / M pair / 2
+
+  -- the pairing of the fair and ensemble CRPS, to which both reduce for a group of one point.  ES is not additive in the
+  raw sums, so the terms are kept per forecast (a batch member counts as a forecast); `merge` concatenates and the scores
+  are means over forecasts.  A group without a valid point (S0 = 0) is NaN.  Units are the member store's own."""
+
+  def __init__(self, err, pair, n_members: int, names: Optional[Sequence[str]] = None, invalid: int = 0):
+    self.err = np.asarray(err, dtype=np.float64)
+    self.pair = np.asarray(pair, dtype=np.float64)
+    self.n_members = int(n_members)
+    self.invalid = int(invalid)
+    if self.n_members < 2:
+      raise ValueError("n_members must be >= 2")
+    if self.err.ndim != 2 or self.pair.shape != self.err.shape:
+      raise ValueError(f"err and pair must be [forecasts, groups], got {self.err.shape} and {self.pair.shape}")
+    self.names = tuple(f"group{k}" for k in range(self.err.shape[1])) if names is None else tuple(str(n) for n in names)
+    if len(self.names) != self.err.shape[1]:
+      raise ValueError(f"{len(self.names)} names for {self.err.shape[1]} groups")
+
+  @staticmethod
+  def pair_index(i: int, j: int) -> int:
+    """The index of the pair i < j in the last axis of D2."""
+    if not 0 <= i < j:
+      raise ValueError("pair_index needs 0 <= i < j")
+    return j * (j - 1) // 2 + i
+
+  @classmethod
+  def from_sums(cls, d2, s0, n_members: int, names: Optional[Sequence[str]] = None, invalid: int = 0) -> "EnergyScores":
+    """From the raw sums of `gc_ens_energy_score`: `d2` [B, K, P], `s0` [B, K]."""
+    M = int(n_members)
+    d2, s0 = np.asarray(d2, dtype=np.float64), np.asarray(s0, dtype=np.float64)
+    if d2.ndim != 3 or d2.shape[-1] != M * (M + 1) // 2 or s0.shape != d2.shape[:2]:
+      raise ValueError(f"d2 must be [batch, groups, {M * (M + 1) // 2}] and s0 [batch, groups], got {d2.shape} and {s0.shape}")
+    with np.errstate(invalid="ignore", divide="ignore"):
+      D = np.sqrt(d2 / s0[..., None])
+    truth = np.arange(M * (M - 1) // 2, M * (M + 1) // 2)        # the pairs (i, M)
+    return cls(D[..., truth].mean(axis=-1), D[..., :truth[0]].mean(axis=-1), M, names, invalid)
+
+  @property
+  def n_forecasts(self) -> int:
+    return self.err.shape[0]
+
+  @property
+  def per_forecast(self) -> np.ndarray:
+    """[F, K]: the fair energy score of every forecast."""
+    return self.err - 0.5 * self.pair
+
+  @property
+  def per_forecast_ensemble(self) -> np.ndarray:
+    m = float(self.n_members)
+    return self.err - 0.5 * (m - 1.0) / m * self.pair
+
+  @property
+  def energy_score(self) -> np.ndarray:
+    """[K]: the fair energy score, the mean over the forecasts."""
+    return self.per_forecast.mean(axis=0)
+
+  @property
+  def energy_score_ensemble(self) -> np.ndarray:
+    """[K]: the energy score of the M-member empirical distribution."""
+    return self.per_forecast_ensemble.mean(axis=0)
+
+  @property
+  def error_term(self) -> np.ndarray:
+    return self.err.mean(axis=0)
+
+  @property
+  def pair_term(self) -> np.ndarray:
+    return self.pair.mean(axis=0)
+
+  @staticmethod
+  def merge(parts: Sequence["EnergyScores"]) -> "EnergyScores":
+    """The forecasts of all parts (other dates), one after the other."""
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    for p in parts[1:]:
+      if p.n_members != first.n_members or p.names != first.names:
+        raise ValueError("merge: the parts differ in members or groups")
+    return EnergyScores(np.concatenate([p.err for p in parts]), np.concatenate([p.pair for p in parts]), first.n_members,
+                        first.names, sum(p.invalid for p in parts))
+
+  def per_group(self) -> Dict[str, Dict[str, float]]:
+    """{score: {group name: value}}."""
+    return {score: {n: float(v) for n, v in zip(self.names, getattr(self, score))}
+            for score in ("energy_score", "energy_score_ensemble", "error_term", "pair_term")}
+
+
+class VariogramSpec:
+  """Pairs of grid points a fixed offset apart: `offsets` 1 to 16 pairs (di, dj) in rows and columns of the lat-lon grid,
+  none (0, 0) -- the partner of (i, j) is (i + di, (j + dj) mod n_lon), and a pair whose partner row lies beyond a pole is
+  left out -- and the order `p` in {0.5, 1, 2} of the variogram (0.5: Scheuerer and Hamill 2015)."""
+
+  def __init__(self, offsets: Sequence[Tuple[int, int]], p: float = 0.5):
+    o = np.asarray(offsets)
+    if o.ndim != 2 or o.shape[1] != 2 or not 1 <= o.shape[0] <= 16 or not np.all(o == np.round(o)):
+      raise ValueError("offsets must be 1 to 16 pairs of integers (di, dj)")
+    self.offsets = tuple((int(a), int(b)) for a, b in o)
+    if any(a == 0 and b == 0 for a, b in self.offsets):
+      raise ValueError("the offset (0, 0) pairs a point with itself")
+    self.p = float(p)
+    if self.p not in (0.5, 1.0, 2.0):
+      raise ValueError("p must be 0.5, 1 or 2")
+
+  def plan(self, template) -> Dict[str, object]:
+    """The arguments of `NativeDenoiser.ens_variogram_set` for the grid of `template`."""
+    sizes = datasets.as_dataset(template).sizes
+    if "lat" not in sizes or "lon" not in sizes:
+      raise ValueError("template must have 'lat' and 'lon' dimensions")
+    return self.grid_plan(int(sizes["lat"]), int(sizes["lon"]))
+
+  def grid_plan(self, n_lat: int, n_lon: int) -> Dict[str, object]:
+    for di, dj in self.offsets:
+      if abs(di) >= n_lat or abs(dj) >= n_lon:
+        raise ValueError(f"offset {(di, dj)} reaches beyond the {n_lat} x {n_lon} grid")
+    return {"n_lat": int(n_lat), "n_lon": int(n_lon), "offsets": np.asarray(self.offsets, dtype=np.int32), "p": self.p}
+
+
+class VariogramScores:
+  """The raw sums of `gc_ens_variogram_score`: `sums` [4, B, c_out, O] float64 -- V0 = sum omega, V1 = sum omega (vy - vx)^2,
+  V2 = sum omega vx, V3 = sum omega vy over the valid pairs, v(u) = |u_g - u_g'|^p, vx the members' mean of it, vy the
+  truth's -- and `counts` [B, c_out, O] uint64 (valid pairs), with the member count, the offsets [O] and p.  The sums are
+  additive.  Every score is [B, c_out, O]."""
+
+  def __init__(self, sums, counts, n_members: int, offsets, p: float):
+    self.sums = np.asarray(sums, dtype=np.float64)
+    self.counts = np.asarray(counts, dtype=np.uint64)
+    self.n_members = int(n_members)
+    self.offsets = tuple((int(a), int(b)) for a, b in offsets)
+    self.p = float(p)
+    if self.sums.ndim != 4 or self.sums.shape[0] != 4 or self.sums.shape[-1] != len(self.offsets):
+      raise ValueError(f"sums must be [4, batch, channels, {len(self.offsets)}], got {self.sums.shape}")
+    if self.counts.shape != self.sums.shape[1:]:
+      raise ValueError(f"counts must be {self.sums.shape[1:]}, got {self.counts.shape}")
+
+  @property
+  def valid_weight(self) -> np.ndarray:
+    return self.sums[0]
+
+  @property
+  def valid_pairs(self) -> np.ndarray:
+    return self.counts
+
+  @property
+  def variogram_score(self) -> np.ndarray:
+    """V1 / V0: the weighted mean squared difference between the truth's variogram term and the ensemble's."""
+    return self.sums[1] / self.sums[0]
+
+  @property
+  def ensemble_variogram(self) -> np.ndarray:
+    return self.sums[2] / self.sums[0]
+
+  @property
+  def truth_variogram(self) -> np.ndarray:
+    return self.sums[3] / self.sums[0]
+
+  @property
+  def roughness_ratio(self) -> np.ndarray:
+    """V2 / V3: below 1 the members are smoother than the truth at that separation."""
+    return self.sums[2] / self.sums[3]
+
+  def scaled(self, channel_scale) -> "VariogramScores":
+    """The scores of a x + b in place of x (members and truth alike), a = channel_scale [c_out], any b: V1 scales with
+    |a|^(2p), V2 and V3 with |a|^p; weights and counts do not change."""
+    a = np.asarray(channel_scale, dtype=np.float64).reshape(-1)
+    if a.shape != (self.sums.shape[2],):
+      raise ValueError(f"channel_scale must have shape ({self.sums.shape[2]},)")
+    if np.any(a == 0.0) or not np.all(np.isfinite(a)):
+      raise ValueError("channel_scale must be finite and non-zero")
+    ap = np.abs(a) ** self.p
+    f = np.stack([np.ones_like(a), ap * ap, ap, ap])[:, None, :, None]
+    return VariogramScores(self.sums * f, self.counts, self.n_members, self.offsets, self.p)
+
+  @staticmethod
+  def merge(parts: Sequence["VariogramScores"]) -> "VariogramScores":
+    """Scores over the union of what the parts covered (other dates): raw sums and counts add."""
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    for q in parts[1:]:
+      if q.n_members != first.n_members or q.offsets != first.offsets or q.p != first.p or q.sums.shape != first.sums.shape:
+        raise ValueError("merge: the parts differ in members, offsets, order or shape")
+    sums, counts = first.sums.copy(), first.counts.copy()
+    for q in parts[1:]:
+      sums += q.sums
+      counts += q.counts
+    return VariogramScores(sums, counts, first.n_members, first.offsets, first.p)
+
+  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
+    """{score: {variable: [batch, channels of the variable, O]}} in the channel order of `datasets.channel_layout`."""
+    layout = datasets.channel_layout(datasets.as_dataset(template))
+    if sum(n for _, _, n in layout) != self.sums.shape[2]:
+      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.sums.shape[2]}")
+    out: Dict[str, Dict[str, np.ndarray]] = {}
+    for score in ("variogram_score", "ensemble_variogram", "truth_variogram", "roughness_ratio", "valid_weight", "valid_pairs"):
+      values = getattr(self, score)
+      out[score] = {name: values[:, off:off + n] for name, off, n in layout}
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # a member store that gets scored
 # ---------------------------------------------------------------------------------------------
 class ScoredStore:
@@ -999,7 +1275,8 @@ class ScoredStore:
   (None: `ens_score` is not used on it), optionally the events counted on it -- an `EventSpec`, its packed `thresholds`
   in the members' units and `weight_q` = `quantize_node_weights(...)` -- and optionally the `plan` (`DerivedSpec.plan`) that
   fills it from the store of a `source` handle (`ens_derive`), and optionally `order`: the probabilities of the quantile
-  fields `score_order` leaves on the device next to its `OrderScores`, and optionally `climatology`: a second handle of the
+  fields `score_order` leaves on the device next to its `OrderScores`, optionally `energy` and `variogram`: the plans
+  (`EnergySpec.plan`, `VariogramSpec.plan`) of `score_energy` and `score_variogram`, and optionally `climatology`: a second handle of the
   same graph, batch and c_out (`Denoiser.climatology_handle`) whose member store takes the K climatological samples
   `score_climatology` scores the members against -- on a derived view together with `climatology_source`, the handle whose
   store holds the samples the view's plan is applied to.  `EnsembleSampler` and `EnsembleRollout` use one for the main
@@ -1010,7 +1287,7 @@ class ScoredStore:
 
   def __init__(self, handle, n_members: int, node_weight=None, *, events: Optional["EventSpec"] = None, thresholds=None,
                weight_q: Optional[Tuple[np.ndarray, float]] = None, plan=None, source=None, set_per_score: bool = False,
-               order=None, climatology=None, climatology_source=None):
+               order=None, climatology=None, climatology_source=None, energy=None, variogram=None):
     if climatology_source is not None and (climatology is None or plan is None):
       raise ValueError("a climatology source goes with a climatology handle and a derive plan")
     if events is not None and weight_q is None:
@@ -1022,6 +1299,7 @@ class ScoredStore:
     self.plan, self.source, self.set_per_score = plan, source, bool(set_per_score)
     self.order = None if order is None else tuple(float(p) for p in np.asarray(order, dtype=np.float64).reshape(-1))
     self.climatology, self.climatology_source = climatology, climatology_source
+    self.energy, self.variogram = energy, variogram          # the plans (`EnergySpec.plan`, `VariogramSpec.plan`) or None
     self._clim_reserved = 0                      # K of the store this object reserved on the climatology handle
     self._clim_plan_set = False                  # the plan has been handed to the climatology handle (a derived view)
 
@@ -1042,11 +1320,22 @@ class ScoredStore:
     if self.order is not None:
       self.handle.ens_order_set(self.order)
 
+  def _set_energy(self) -> None:
+    if self.energy is not None:
+      self.handle.ens_energy_set(self.energy["n_groups"], self.energy["group"], self.energy["scale"])
+
+  def _set_variogram(self) -> None:
+    if self.variogram is not None:
+      v = self.variogram
+      self.handle.ens_variogram_set(v["n_lat"], v["n_lon"], v["offsets"], v["p"])
+
   def configure(self) -> None:
-    """The plan, the thresholds and the probabilities: all survive `ens_reserve` and every score."""
+    """The plan, the thresholds, the probabilities and the multivariate plans: all survive `ens_reserve` and every score."""
     self._set_plan()
     self._set_events()
     self._set_order()
+    self._set_energy()
+    self._set_variogram()
 
   def setup(self) -> None:
     self.reserve()
@@ -1072,6 +1361,26 @@ class ScoredStore:
       self._set_order()
     bins, extra, pinball, counts, _ = self.handle.ens_order_score(truth)
     return OrderScores(bins, extra, pinball, counts, self.n_members, self.order)
+
+  def score_energy(self, truth=None) -> Optional["EnergyScores"]:
+    """The energy score of the store over the groups of `energy` (None without it), in the store's own units; `truth` None:
+    the truth already on the device.  On a derived view the DERIVED members are scored: call it after `score`."""
+    if self.energy is None:
+      return None
+    if self.set_per_score:
+      self._set_energy()
+    d2, s0, invalid = self.handle.ens_energy_score(truth)
+    return EnergyScores.from_sums(d2, s0, self.n_members, self.energy.get("names"), invalid)
+
+  def score_variogram(self, truth=None) -> Optional["VariogramScores"]:
+    """The raw variogram sums of the store at the offsets of `variogram` (None without it), in the store's own units;
+    `truth` None: the truth already on the device.  On a derived view call it after `score`."""
+    if self.variogram is None:
+      return None
+    if self.set_per_score:
+      self._set_variogram()
+    sums, counts = self.handle.ens_variogram_score(truth)
+    return VariogramScores(sums, counts, self.n_members, self.variogram["offsets"], self.variogram["p"])
 
   def _reserve_climatology(self, K: int) -> None:
     if K != self._clim_reserved:

@@ -714,6 +714,61 @@ int gc_ens_window_emit(gc_handle* win);
 int gc_ens_window_reset(gc_handle* win);
 
 /*
+ * Multivariate ensemble scores on the device: the raw sums of the energy score over groups of
+ * channels and whole fields, and of the variogram score over pairs of grid points a fixed offset apart
+ * (gencast-flax-nnx_amd/verification.py EnergyScores, VariogramScores).  Every other score of this library is marginal: it
+ * looks at one point and one channel at a time.  The reference project has no verification code; the yardstick is the
+ * definition below, restated in float64 in tests/multivar_reference.py.
+ * Members x_0 .. x_{M-1} and the truth y are [G, B, c_out] float32, w[g] the node weight of gc_ens_set_node_weight.  A
+ * point (g, b, c) is valid iff y and all M members are finite there.  Write x_M = y.
+ * Energy.  The plan gives K groups (1 <= K <= 32) and a per-channel scale: group[c] in {-1, 0 .. K-1}, where -1 means
+ * the channel is in no group; every group is non-empty; a[c] is finite and > 0 for grouped channels.  Per batch member b,
+ * group k and pair 0 <= i < j <= M, with pair index p = j (j - 1) / 2 + i and P = M (M + 1) / 2:
+ *   D2[b][k][p] = sum omega (d d) over the valid points of the group
+ *                 omega = (double)w[g] a[c];  d = (double)x_i - (double)x_j, which is exact; each product and each addition
+ *                 is a rounded double operation with no contraction
+ *   S0[b][k]    = sum omega over the same points         invalid = the number of skipped points of grouped channels
+ * Invalid points are skipped, not multiplied by zero.  On the host D[i][j] = sqrt(D2 / S0), err = mean_i D[i][M],
+ * pair = mean_{i<j<M} D[i][j], fair ES = err - pair / 2, ensemble ES = err - (M - 1) / M pair / 2 -- the pairing of the
+ * fair and ensemble CRPS of gc_ens_score.  A group with S0 = 0 gives NaN.  ES is not additive in the raw sums: a result
+ * keeps err and pair per forecast.  Units are the store's own; a[c] carries level or variable weights.
+ * Variogram.  The plan gives the grid n_lat n_lon = G with node = i n_lon + j (as in gc_ens_derive_set), O offsets (di, dj)
+ * with 1 <= O <= 16, not (0, 0), |di| < n_lat, |dj| < n_lon, and an order p in {0.5, 1, 2}: formed with sqrt, identity and
+ * a product, no pow.  The partner of (i, j) is (i + di, (j + dj) mod n_lon).  The pair is skipped when i + di leaves
+ * [0, n_lat), and when either end is invalid.  Per valid pair, in double:
+ *   omega = (w[g] + w[g']) / 2      v(u) = |u_g - u_g'|^p      vx = (sum_i v(x_i)) / M in ascending slot order      vy = v(y)
+ * Per (b, c, o):  V0 = sum omega,  V1 = sum omega (vy - vx)^2,  V2 = sum omega vx,  V3 = sum omega vy, and a uint64 pair
+ * count.  These sums are additive; variogram score = V1 / V0, roughness ratio = V2 / V3 on the host.
+ *   gc_ens_energy_set       the plan: group [c_out], scale [c_out].  Needs gc_set_graph only; survives gc_ens_reserve;
+ *                           replaces an earlier plan ("device_allocations" stays flat); released by gc_destroy.
+ *                           GC_ERR_UNSUPPORTED: K outside 1..32.  GC_ERR_INVALID_ARGUMENT: a NULL array, a group index
+ *                           outside -1 .. K - 1, an empty group, a scale of a grouped channel that is not finite and > 0.
+ *   gc_ens_energy_score     truth: host [G, B, c_out], uploaded and kept, or NULL = the truth uploaded last (the buffer
+ *                           gc_ens_score uses).  d2 [B][K][P] and s0 [B][K] are required, invalid [1] may be NULL.  Two
+ *                           launches: a pass in which a workgroup takes one (b, k) and a node range, stages tiles of 256
+ *                           points of the M + 1 fields in LDS and keeps the P pair sums in registers, spread over its
+ *                           threads; and a finish that adds the per-block partials in block order.  Synchronous.
+ *   gc_ens_variogram_set    the plan.  Needs gc_set_graph only; survives gc_ens_reserve; replaces an earlier plan
+ *                           ("device_allocations" stays flat).  GC_ERR_UNSUPPORTED: O outside 1..16, p not 0.5, 1 or 2.
+ *                           GC_ERR_INVALID_ARGUMENT: offsets NULL, n_lat n_lon != G, an offset (0, 0) or beyond the grid.
+ *   gc_ens_variogram_score  sums [4][B][c_out][O] (V0 .. V3) is required, counts [B][c_out][O] may be NULL.  Two launches:
+ *                           a pass with one thread per column of a node lane and one offset per workgroup, and the
+ *                           finish.  Synchronous.
+ * Both scoring entries: GC_ERR_STATE for no plan, no member store, a slot not pushed since gc_ens_reserve, no node weights,
+ * no truth; GC_ERR_INVALID_ARGUMENT for a required array that is NULL.  No atomics on floats and a fixed order of every
+ * sum: the same call twice returns identical bytes.  Nothing else on the handle is touched.  Counters: "ens_energy_calls",
+ * "ens_energy_device_us" (HIP-event time of the last call's launches), "ens_energy_invalid_points" (of the last call),
+ * "ens_variogram_calls", "ens_variogram_device_us".
+ */
+int gc_ens_energy_set(gc_handle* h, int32_t n_groups, const int32_t* group /* [c_out] */, const double* scale /* [c_out] */);
+int gc_ens_energy_score(gc_handle* h, const float* truth /* NULL = the truth uploaded last */, double* d2 /* [B][K][P] */,
+                        double* s0 /* [B][K] */, uint64_t* invalid /* [1], NULL allowed */);
+int gc_ens_variogram_set(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t n_offsets, const int32_t* offsets /* [O][2] */,
+                         double p);
+int gc_ens_variogram_score(gc_handle* h, const float* truth /* NULL = the truth uploaded last */,
+                           double* sums /* [4][B][c_out][O] */, uint64_t* counts /* [B][c_out][O], NULL allowed */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
