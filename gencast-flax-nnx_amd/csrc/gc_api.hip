@@ -851,6 +851,7 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   if (!name || !value) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   const std::string n(name);
   if (n == "range_fallbacks") *value = h->range_fallbacks;
+  else if (n == "static_embedding_fallbacks") *value = h->static_embedding_fallbacks;
   else if (n == "launches_per_call") *value = h->launches_last_call;
   else if (n == "weights_f16_unsafe") *value = h->weights_f16_unsafe ? 1 : 0;
   else if (n == "fp16_storage") *value = h->last_route.st16 ? 1 : 0;

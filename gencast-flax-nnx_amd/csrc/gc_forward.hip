@@ -473,19 +473,48 @@ int forward(gc_handle* h, float sigma_scalar, const float* cond_ready) {
 
 // Static embeddings: LayerNorm(MLP(static features)) in the precision currently selected; the
 // per-call conditioning is applied where they are consumed.  Re-run when the precision changes.
+// f16x3 domain guard: every call reads them, the exact-f32 re-run of a poisoned call included, so a hidden activation
+// beyond fp16 range in here (every weight inside it: weights_f16_unsafe does not see that) would leave NaN in them for
+// the life of the handle, and the re-run of every call would return NaN too.  They are checked where they are made and
+// made again on the exact-f32 kernels when poisoned; nothing is added to a call.
 int compute_static_embeddings(gc_handle* h) {
   const gc::HostGraph& hg = h->hg;
   const int L = h->cfg.latent_size;
-  h->route = make_route(h);      // same kernel build as the forward will use; float32 in (structural features) and out
   const struct { const DevMlp& w; const float* in; int items; float* out; } embeds[] = {
       {h->g2m_embed_mesh, h->d_mesh_struct16, hg.M, h->d_m0_hat},
       {h->g2m_embed_edge, h->d_e1_struct16, hg.E1, h->d_e0_hat},
       {h->m2g_embed_edge, h->d_e2_struct16, hg.E2, h->d_f0_hat}};
-  for (const auto& e : embeds) {
-    MlpCall c = mlp_call({seg(e.in, nullptr, nullptr, 32, 32, 1)}, e.items, 1, e.out, L);
-    c.cond = c.round_out = false; c.seg0_f32 = c.out_f32 = true;
-    if (int rc = run_mlp(h, e.w, c)) return rc;
-  }
+  auto run = [&]() -> int {
+    h->route = make_route(h);    // same kernel build as the forward will use; float32 in (structural features) and out
+    for (const auto& e : embeds) {
+      MlpCall c = mlp_call({seg(e.in, nullptr, nullptr, 32, 32, 1)}, e.items, 1, e.out, L);
+      c.cond = c.round_out = false; c.seg0_f32 = c.out_f32 = true;
+      if (int rc = run_mlp(h, e.w, c)) return rc;
+    }
+    return GC_OK;
+  };
+  if (int rc = run()) return rc;
+  GC_HIP(h, hipStreamSynchronize(h->stream));
+  // (fp16 features: an overflow in there is the mode's own arithmetic, the exact-f32 kernels round to the same Inf)
+  if (!h->route.f16 || h->feat16) return GC_OK;
+  // The counter is shared with the calls' checks.  Both gc_set_option callers resolve a pending sample's check first and
+  // gc_finalize has no sample to keep; should one be unresolved all the same, its count reached the host copy with the
+  // synchronisation above (guard_enqueue queued that copy behind the sample), so `before` holds it and only what these
+  // three launches add is taken off as theirs.
+  const unsigned before = *h->h_nonfinite;
+  for (const auto& e : embeds)
+    if (int rc = launch(h, gc::KC_PACK, [&] { return gc::launch_finite_check(h->stream, e.out, (size_t)e.items * L, h->d_nonfinite); }))
+      return rc;
+  GC_HIP(h, hipMemcpyAsync(h->h_nonfinite, h->d_nonfinite, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+  GC_HIP(h, hipStreamSynchronize(h->stream));
+  const unsigned hits = *h->h_nonfinite - before;
+  if (!hits) return GC_OK;
+  h->nonfinite_seen += hits;
+  ++h->static_embedding_fallbacks;
+  h->in_fallback = true;
+  const int rc = run();
+  h->in_fallback = false;
+  if (rc) return rc;
   GC_HIP(h, hipStreamSynchronize(h->stream));
   return GC_OK;
 }

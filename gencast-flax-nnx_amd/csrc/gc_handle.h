@@ -438,6 +438,7 @@ struct gc_handle {
   unsigned* h_nonfinite = nullptr;   // pinned host copy
   unsigned nonfinite_seen = 0;
   int64_t range_fallbacks = 0;       // calls re-run in f32 (gc_get_counter "range_fallbacks")
+  int64_t static_embedding_fallbacks = 0;   // times the static embeddings were made again in f32 (compute_static_embeddings)
   bool guard_pending = false;        // a resident sample has not been checked yet
   std::vector<float> last_sigmas;    // arguments of that sample, for the re-run
   int last_skip_dead = 1;

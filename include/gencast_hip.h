@@ -102,6 +102,7 @@ void gc_destroy(gc_handle* h);
  *   propagate).  gc_get_counter("range_fallbacks") counts those re-runs.  For the resident
  *   (asynchronous) sampler the check is resolved by the next gc_download_sample / gc_sync /
  *   gc_rollout_advance.  Weights beyond the domain switch the handle to f32 kernels for good.
+ *   The static embeddings, which gc_finalize makes once for every call to read, are checked and re-made the same way.
  *   "features" = "f32" (default) | "f16"   -- BASELINE.json configs[4], "fp16 node features":
  *       every activation is rounded to fp16 (round to nearest even) where it is produced -- grid
  *       input features, MLP hidden and output, LayerNorm + conditioning outputs, residual sums,
@@ -838,6 +839,9 @@ int gc_profile_read(gc_handle* h, int32_t* launches, float* total_ms);
  * handle's configuration (formulas in DESIGN.md). */
 int gc_algorithmic_work(gc_handle* h, double* flops, double* bytes);
 /* Named counters: "range_fallbacks" (calls re-run on the f32 kernels by the f16x3 domain guard),
+ * "static_embedding_fallbacks" (times the static embeddings -- made in gc_finalize and when "precision" or "features"
+ * changes -- left the f16x3 domain and were made again on the f32 kernels; calls are not affected; not checked with
+ * "features" = "f16", where an overflow to Inf is that mode's defined arithmetic),
  * "launches_per_call" (kernel launches of the last denoiser forward), "weights_f16_unsafe",
  * "graph_captures" / "graph_replays" (sampler graphs captured / samples launched as one hipGraphLaunch),
  * "fp16_storage" (1 when the last forward kept its activations as 2-byte fp16 arrays in HBM: features = f16 on the

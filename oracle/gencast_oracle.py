@@ -95,8 +95,24 @@ def feature_rounding(dtype, skip_calls=()):
     _R = saved
 
 
+# ---- operand magnitudes (denoiser_forward(operand_max=...)) -------------------------------------------
+# `_REC`: the dict being filled, or None (off: `_note` returns at once, nothing else differs).  A left operand of a
+# matrix product is keyed by the parameter path of the kernel it multiplies; `_REC_NAMES` maps id(kernel array) to that
+# path for the arrays of the forward that is running.  Only max |value| is read off arrays the forward has made anyway.
+_REC = None
+_REC_NAMES = {}
+
+
+def _note(key, a):
+  if _REC is None or key is None:
+    return
+  with np.errstate(invalid="ignore"):
+    _REC[key] = max(_REC.get(key, 0.0), float(np.abs(a).max()))
+
+
 def linear(x, kernel, bias=None):
   """flax.nnx.Linear: y = x @ kernel + bias, kernel (in, out) (mlp.py:51-57,175-199)."""
+  _note(_REC_NAMES.get(id(kernel)), x)
   y = (x.reshape(-1, x.shape[-1]) @ kernel).reshape(x.shape[:-1] + (kernel.shape[-1],))  # one GEMM
   return _R(y if bias is None else y + bias)
 
@@ -141,6 +157,7 @@ def noise_level_encoding(params, noise_levels, *, base_period=16.0, num_frequenc
 
 def _cond_linear(cond, kernel, bias):
   """The conditioning path (noise encoder -> [scale | offset]) stays float32 in every mode."""
+  _note(_REC_NAMES.get(id(kernel)), cond)
   return (cond.reshape(-1, cond.shape[-1]) @ kernel).reshape(cond.shape[:-1] + (kernel.shape[-1],)) + bias
 
 
@@ -360,6 +377,7 @@ def attention_triblockdiag(q, k, v, mask_csr, block_size, masks=None):
 # ----------------------------------------------------------------------------
 
 def _linear_f32(x, kernel, bias=None):
+  _note(_REC_NAMES.get(id(kernel)), x)
   y = (x.reshape(-1, x.shape[-1]) @ kernel).reshape(x.shape[:-1] + (kernel.shape[-1],))
   return y if bias is None else y + bias
 
@@ -379,16 +397,22 @@ def transformer_block(params, i, x, cond, attn_fn, num_heads):
   q = linear(hcond, params[f"{p}.attn_module.q_proj.linear.kernel"]).reshape(b, m, num_heads, dh)
   k = linear(hcond, params[f"{p}.attn_module.k_proj.linear.kernel"]).reshape(b, m, num_heads, dh)
   v = linear(hcond, params[f"{p}.attn_module.v_proj.linear.kernel"]).reshape(b, m, num_heads, dh)
+  _note(f"{p}.q", q)
+  _note(f"{p}.k", k)
+  _note(f"{p}.v", v)
   a = attn_fn(q, k, v).reshape(b, m, d)
   # (in the fp16-feature mode the projection is NOT rounded on its own: the kernels accumulate it in
   #  float32 straight into the residual sum, which is rounded once)
   x = _R(x + _linear_f32(a, params[f"{p}.attn_module.final_linear.kernel"],
                          params[f"{p}.attn_module.final_linear.bias"]))
+  _note(f"{p}.x", x)
   h2 = cond_bf(layer_norm(x), "norm_cond_ffw")
   f = _R(gelu_tanh(_linear_f32(h2, params[f"{p}.ffw_module.mlp.layers.0.kernel"],
                                params[f"{p}.ffw_module.mlp.layers.0.bias"])))
-  return _R(x + _linear_f32(f, params[f"{p}.ffw_module.mlp.layers.2.kernel"],
-                            params[f"{p}.ffw_module.mlp.layers.2.bias"]))
+  x = _R(x + _linear_f32(f, params[f"{p}.ffw_module.mlp.layers.2.kernel"],
+                         params[f"{p}.ffw_module.mlp.layers.2.bias"]))
+  _note(f"{p}.x", x)
+  return x
 
 
 def mesh_transformer(params, x_mbd, cond, *, num_layers, num_heads, attn_fn):
@@ -441,19 +465,26 @@ def make_attention_fn(graph, formulation: str):
 
 def denoiser_forward(params, graph, grid_feats, noise_levels, *, num_layers, num_heads,
                      attention="neighbour", dtype=np.float64, return_intermediates=False,
-                     feature_dtype=None, g2m_aggregate_normalization=None):
+                     feature_dtype=None, g2m_aggregate_normalization=None, operand_max=None):
   """See `_denoiser_forward`.  `feature_dtype=np.float16` evaluates the "fp16 node features" mode
-  (rounding points listed at the top of this file) in `dtype` arithmetic."""
-  global _R
-  saved = _R
+  (rounding points listed at the top of this file) in `dtype` arithmetic.
+
+  `operand_max`: a dict to fill, in forward order, with the largest |value| of every left operand of a matrix product
+  of this forward, keyed by the parameter path of the kernel it multiplies (the conditioning path included; an MLP's
+  hidden activation is the operand of its `layers.2.kernel`, the static embedders' among them), and besides, per
+  transformer block `b`, `b.q` / `b.k` / `b.v` after projection and `b.x`, the residual stream (the larger of its two
+  states in the block; it is no operand).  Magnitudes only: the arithmetic and the result are the same with and without it."""
+  global _R, _REC, _REC_NAMES
+  saved = _R, _REC, _REC_NAMES
   _R = _round_to(feature_dtype)
+  _REC, _REC_NAMES = operand_max, {}
   try:
     return _denoiser_forward(params, graph, grid_feats, noise_levels, num_layers=num_layers,
                              num_heads=num_heads, attention=attention, dtype=dtype,
                              return_intermediates=return_intermediates,
                              g2m_aggregate_normalization=g2m_aggregate_normalization)
   finally:
-    _R = saved
+    _R, _REC, _REC_NAMES = saved
 
 
 def _denoiser_forward(params, graph, grid_feats, noise_levels, *, num_layers, num_heads,
@@ -469,6 +500,8 @@ def _denoiser_forward(params, graph, grid_feats, noise_levels, *, num_layers, nu
   """
   dt = np.dtype(dtype)
   params = {k: np.asarray(v, dtype=dt) for k, v in params.items()}
+  if _REC is not None:
+    _REC_NAMES.update({id(v): k for k, v in params.items() if k.endswith(".kernel")})
   x = np.asarray(grid_feats, dtype=dt)
   sig = np.asarray(noise_levels, dtype=dt)
   g, b, _ = x.shape
