@@ -140,6 +140,9 @@ SIGNATURES = {
                                            ctypes.POINTER(ctypes.c_uint64)]),
     "gc_ens_variogram_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.c_double]),
     "gc_ens_variogram_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_tail_set": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p, _i32p]),
+    "gc_ens_tail_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
+                                         ctypes.POINTER(ctypes.c_uint64)]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -235,6 +238,7 @@ class NativeDenoiser:
     self._order_quantiles = None               # probabilities this object handed to the handle (None: ens_order_set not called)
     self._energy_groups = None                 # groups of the energy plan this object set (None: ens_energy_set not called)
     self._variogram_offsets = None             # offsets of the variogram plan this object set (None: ens_variogram_set not called)
+    self._tail_thresholds = 0                  # tail threshold fields this object handed to the handle
     self._window_length = 0                    # length of the window plan this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
@@ -872,6 +876,42 @@ class NativeDenoiser:
                                                  _ptr(sums, ctypes.POINTER(ctypes.c_double)),
                                                  _ptr(counts, ctypes.POINTER(ctypes.c_uint64))))
     return sums, counts
+
+  # -- threshold-weighted CRPS (one sort of the members per point, T thresholds) -------------------------
+  def ens_tail_set(self, thresholds, directions) -> None:
+    """`thresholds` [T, G, B, c_out] float32 (T in 1..8; NaN = not evaluated there), `directions` [T] (> 0: the upper tail,
+    weight 1{z >= threshold}; < 0: the lower tail, 1{z <= threshold}): gc_ens_tail_set; needs `set_graph` only, survives
+    `ens_reserve` and is independent of `ens_event_set`."""
+    thr = _f32(thresholds)
+    if thr.ndim != 4 or thr.shape[1:] != self._shape_out():
+      raise ValueError(f"thresholds must be [T, {', '.join(str(n) for n in self._shape_out())}], got {thr.shape}")
+    if not 1 <= thr.shape[0] <= 8:
+      raise ValueError(f"thresholds must hold 1..8 fields, got {thr.shape[0]}")
+    d = _i32(directions)
+    if d.shape != (thr.shape[0],):
+      raise ValueError(f"directions must have shape ({thr.shape[0]},)")
+    if np.any(d == 0):
+      raise ValueError("directions must be non-zero")
+    self._check(self._lib.gc_ens_tail_set(self._h, thr.shape[0], _ptr(thr, _f32p), _ptr(d, _i32p)))
+    self._tail_thresholds = int(thr.shape[0])
+
+  def ens_tail_score(self, truth=None):
+    """-> (sums [T, B, c_out, 4] float64: sum w, sum w ae, sum w d, sum w o; counts [T, B, c_out] uint64; invalid [T] uint64):
+    the raw, additive sums of gc_ens_tail_score over the member store (`verification.TailScores` derives the scores).
+    `truth` [G, B, c_out], or None = the truth uploaded last (shared with `ens_score`)."""
+    if not self._tail_thresholds:
+      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_tail_set has not been called on this object)")
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    t = self._truth_arg(truth)
+    T, B, C = self._tail_thresholds, self.cfg.batch, self.cfg.c_out
+    u64 = ctypes.POINTER(ctypes.c_uint64)
+    sums = np.empty((T, B, C, 4), dtype=np.float64)
+    counts = np.empty((T, B, C), dtype=np.uint64)
+    invalid = np.empty(T, dtype=np.uint64)
+    self._check(self._lib.gc_ens_tail_score(self._h, None if t is None else _ptr(t, _f32p),
+                                            _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(counts, u64), _ptr(invalid, u64)))
+    return sums, counts, invalid
 
   # -- time-window ensemble fields (a ring of the last lead times, reduced into this handle's member store) --
   def ens_window_set(self, kind: int, length: int, coef=None) -> None:

@@ -12,7 +12,8 @@
 //   gc_clim.hip      gc_ens_clim_score
 //   gc_window.hip    gc_ens_window_*
 //   gc_multivar.hip  gc_ens_energy_*, gc_ens_variogram_*
-// The last eight are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
+//   gc_tail.hip      gc_ens_tail_*
+// The last nine are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
 // lead times of another).  What they share -- field length, upload through
 // the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
 // relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
@@ -401,6 +402,20 @@ struct gc_handle {
   unsigned long long* d_vg_outc = nullptr;       // [B c_out][O]
   gci::Bracket vg_time{events};                  // of the last variogram call
   int64_t vg_calls = 0, vg_device_us = 0;
+
+  // threshold-weighted CRPS (gc_ens_tail_*, gc_tail.hip): threshold fields of its own and the sums of one sort per point
+  gci::BufferGroup tail_allocs{groups};           // sized by T: the thresholds; kept across gc_ens_reserve
+  gci::BufferGroup tail_work_allocs{groups};      // sized by T: made again by the scoring call that finds it changed
+  int tail_T = 0;                                // thresholds set (0: none)
+  unsigned tail_dir_up = 0;                      // bit t: threshold t is the upper tail, weight 1{z >= thr}
+  int tail_work_T = 0;                           // what the partial and result buffers are sized for
+  float* d_tail_thr = nullptr;                   // [T][G, B, c_out]
+  double* d_tail_part = nullptr;                 // [blocks][T][4][B c_out] per-block column sums
+  unsigned* d_tail_cpart = nullptr;              // [blocks][T][B c_out] per-block counted points
+  double* d_tail_out = nullptr;                  // [T][B c_out][4]
+  unsigned long long* d_tail_outc = nullptr;     // [T][B c_out] counted points
+  gci::Bracket tail_time{events};                // of the last call
+  int64_t tail_calls = 0, tail_device_us = 0, tail_invalid_points = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

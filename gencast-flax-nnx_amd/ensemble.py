@@ -152,16 +152,27 @@ class EnsembleSampler:
       raise ValueError("multivariate needs an EnergySpec, a VariogramSpec or both")
     return self._run(inputs, targets, forcings, num_members, None, multivariate=(energy, variogram))
 
+  def tails(self, inputs, targets, forcings, num_members: int, spec):
+    """Runs the members as `scores` does and forms, on the device, the threshold-weighted CRPS at the thresholds of `spec`
+    (a `verification.EventSpec`: thresholds per variable in the units of `targets`; direction > 0: the upper tail, weight
+    1{z >= threshold}, < 0: the lower tail): `verification.TailScores` -- the CRPS of members and truth clamped at the
+    threshold, fair and of the empirical distribution, per threshold, batch member and channel.  The members of a point are
+    sorted once for all thresholds.  No member is downloaded."""
+    self._one_rank("tails")
+    return self._run(inputs, targets, forcings, num_members, None, tails=spec)
+
   def _spectral(self, inputs, targets, forcings, num_members, score_fields, lmax):
     self._one_rank("spectra")
     return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
 
   def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,
-           lmax: Optional[int] = None, events=None, derived=None, order=None, climatology=None, multivariate=None):
+           lmax: Optional[int] = None, events=None, derived=None, order=None, climatology=None, multivariate=None,
+           tails=None):
     """`score_fields` None: members come back as Datasets (`__call__`) or, with `spectral`, only their spectra are
     formed, or, with `events` (an EventSpec), only their event tables, or, with `order` (probabilities, want fields), only
     their order statistics, or, with `climatology` (K Datasets), only their skill against it, or, with `multivariate` (an
-    EnergySpec or None, a VariogramSpec or None), only their energy and variogram scores; else they are scored
+    EnergySpec or None, a VariogramSpec or None), only their energy and variogram scores, or, with `tails` (an EventSpec), only
+    their threshold-weighted CRPS sums; else they are scored
     (`scores`), with `spectral` both."""
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
@@ -191,14 +202,14 @@ class EnsembleSampler:
     scoring = score_fields is not None
     main = None                                            # lane 0's member store, where anything is scored at all
     if (scoring or spectral or events is not None or derived is not None or order is not None or climatology is not None or
-        multivariate is not None):
+        multivariate is not None or tails is not None):
       dspec, dev = derived if derived is not None else (None, None)
       weights = None if spectral and not scoring else verification.node_weights(template)
       wq = None if events is None and dev is None else verification.quantize_node_weights(weights)
       # (scored once: the thresholds are set by that call, after the members are in)
       main = verification.ScoredStore(native, num_members,
                                       weights if scoring or order is not None or climatology is not None or
-                                      multivariate is not None else None,
+                                      multivariate is not None or tails is not None else None,
                                       events=events, thresholds=None if events is None else events.packed(template), weight_q=wq,
                                       set_per_score=True, order=None if order is None else order[0],
                                       climatology=None if climatology is None
@@ -206,7 +217,8 @@ class EnsembleSampler:
                                       energy=None if multivariate is None or multivariate[0] is None
                                       else multivariate[0].plan(template),
                                       variogram=None if multivariate is None or multivariate[1] is None
-                                      else multivariate[1].plan(template))
+                                      else multivariate[1].plan(template),
+                                      tails=tails, tail_thresholds=None if tails is None else tails.packed(template))
       main.setup()
     if spectral:
       _spectra.ensure_tables(native, template, lmax)
@@ -239,6 +251,8 @@ class EnsembleSampler:
       pack = lambda ds: np.transpose(datasets.dataset_to_stacked(datasets.as_dataset(ds), template.sizes),
                                      (1, 2, 0, 3)).reshape(shape)
       return main.score_climatology([pack(c) for c in climatology], truth)
+    if tails is not None:
+      return main.score_tails(truth)
     if multivariate is not None:
       en = main.score_energy(truth)
       return en, main.score_variogram(truth if en is None else None)      # (the truth is on the device after the first)

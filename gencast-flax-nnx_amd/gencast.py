@@ -127,6 +127,15 @@ class GenCast:
     runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.events(inputs, targets, forcings, num_members, spec)
 
+  def ensemble_tails(self, inputs, targets, forcings=None, *, num_members, spec, rngs=0, concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and forms on the GPU the threshold-weighted CRPS
+    (Gneiting & Ranjan 2011) at the thresholds of `spec` (`verification.EventSpec`: thresholds per variable in the units of
+    `targets`; direction > 0: the upper tail, weight 1{z >= threshold}, < 0: the lower tail): `verification.TailScores` --
+    `.twcrps` (fair), `.twcrps_ensemble`, `.abs_error`, `.pair_distance`, `.base_rate` per threshold, batch member and
+    channel, latitude-weighted.  The members of a point are sorted once for all thresholds.  No member leaves the device."""
+    runner = self._ensemble_sampler(rngs, concurrent_members)
+    return runner.tails(inputs, targets, forcings, num_members, spec)
+
   def ensemble_order(self, inputs, targets, forcings=None, *, num_members, probs=(), quantile_fields=False, rngs=0,
                      concurrent_members=1):
     """Samples `num_members` (2..64) members as `ensemble_scores` does and sorts them point by point on the GPU:
@@ -173,7 +182,7 @@ class GenCast:
     """Rolls `num_members` (2..64) members out `horizon` autoregressive steps with every member's context resident on
     the GPU and scores their states against `targets[k]` at every lead time: `rollout.EnsembleRolloutResult` (per lead
     time `EnsembleScores`, with `spectra=True` also `EnsembleSpectra`, with `fields=True` the mean and variance, with
-    `events=EventSpec` also `EventScores`).  No
+    `events=EventSpec` also `EventScores`, with `tails=EventSpec` also `TailScores`).  No
     member leaves the device.  `rngs`: the base seed (member m is `DeviceRollout(...).run(rngs=member_seed(rngs, m))`);
     `norm`: an `InputsAndResiduals` whose statistics apply (its own `ensemble_rollout` passes itself); `device_noise`
     defaults to the sampler's; other keywords as `rollout.EnsembleRollout.run`."""

@@ -19,7 +19,7 @@ Three layers, each mirroring the reference at the array level:
 from __future__ import annotations
 
 import time as _time
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Mapping, Optional, Sequence
 
 import numpy as np
 
@@ -258,6 +258,16 @@ class InputsAndResiduals:
     raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
     nspec = spec.mapped(datasets.as_dataset(targets), lambda name, v: self._subtract_input_and_normalize_target(raw, name, v))
     return self.predictor.ensemble_events(ni, nt, forcings=nf, spec=nspec, **kwargs)
+
+  def ensemble_tails(self, inputs, targets, forcings=None, *, spec, **kwargs):
+    """`ensemble_tails` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.  The
+    thresholds of `spec` (physical units) go through the SAME map as the targets, exactly as in `ensemble_events`; the map
+    x -> a x + b(point) has a > 0, so clamping commutes with it and no tail flips, and the sums are scaled back to physical
+    units (`TailScores.scaled`: b drops out of every difference)."""
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    scale = self._target_scale(raw, targets)
+    nspec = spec.mapped(datasets.as_dataset(targets), lambda name, v: self._subtract_input_and_normalize_target(raw, name, v))
+    return self.predictor.ensemble_tails(ni, nt, forcings=nf, spec=nspec, **kwargs).scaled(scale)
 
   def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, **kwargs):
     """`ensemble_rollout` of the wrapped predictor with this wrapper as its normalisation (`EnsembleRollout(norm=self)`):
@@ -622,7 +632,8 @@ _SERIES = (("scores", verification.EnsembleScores, None), ("scores_normalized", 
            ("climatology_normalized", verification.ClimatologyScores, None),
            ("energy", verification.EnergyScores, "energy scores"),
            ("variogram", verification.VariogramScores, "variogram scores"),
-           ("variogram_normalized", verification.VariogramScores, None))
+           ("variogram_normalized", verification.VariogramScores, None),
+           ("tails", verification.TailScores, "tail scores"), ("tails_normalized", verification.TailScores, None))
 
 
 class _SeriesResult:
@@ -631,8 +642,8 @@ class _SeriesResult:
   _carries: Sequence[str] = ()
   _kind = "results"                                       # (as the merge's error messages name the two operands)
   # series that exist on an instance only when the run asked for them; the class holds their None (see `_SERIES`)
-  _optional = ("energy", "variogram", "variogram_normalized")
-  energy = variogram = variogram_normalized = None
+  _optional = ("energy", "variogram", "variogram_normalized", "tails", "tails_normalized")
+  energy = variogram = variogram_normalized = tails = tails_normalized = None
 
   def _set_series(self, **series) -> None:
     """Copies the series into lists (the scores first) and checks that the others cover the lead times of the scores."""
@@ -674,18 +685,20 @@ class DerivedRolloutResult(_SeriesResult):
   `climatology_normalized[k]` (`verification.ClimatologyScores`, as `scores`): the derived members against the derived
   climatological samples.  With `run(energy=...)` / `run(variogram=...)` also `energy[k]` (`verification.EnergyScores` over the
   groups whose variables are all derived variables of this entry, in the members' own units; None where no group is) and
-  `variogram[k]` / `variogram_normalized[k]` (`verification.VariogramScores`, as `scores`)."""
+  `variogram[k]` / `variogram_normalized[k]` (`verification.VariogramScores`, as `scores`).  With `run(tails={name: spec})`
+  also `tails[k]` / `tails_normalized[k]` (`verification.TailScores`, as `scores`)."""
 
   _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "climatology", "climatology_normalized",
-              "energy", "variogram", "variogram_normalized")
+              "energy", "variogram", "variogram_normalized", "tails", "tails_normalized")
   _kind = "derived results"
 
   def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, order=None,
                order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, energy=None,
-               variogram=None, variogram_normalized=None):
+               variogram=None, variogram_normalized=None, tails=None, tails_normalized=None):
     self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
                      order_normalized=order_normalized, climatology=climatology, climatology_normalized=climatology_normalized,
-                     energy=energy, variogram=variogram, variogram_normalized=variogram_normalized)
+                     energy=energy, variogram=variogram, variogram_normalized=variogram_normalized, tails=tails,
+                     tails_normalized=tails_normalized)
     self.members, self.template, self.quantiles = members, template, quantiles
 
   def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
@@ -701,18 +714,20 @@ class WindowRolloutResult(_SeriesResult):
   `run(order=...)`) and `members[i]` (`[M]` arrays [G, B, c] of the windowed members in the members' own units, or None);
   `template`: the Dataset of the source's variables for `per_variable`.  With `run(energy=...)` / `run(variogram=...)` also
   `energy[i]` (`verification.EnergyScores` of the windowed fields, in the members' own units; None where no group names
-  variables of the source) and `variogram[i]` / `variogram_normalized[i]` (`verification.VariogramScores`, as `scores`)."""
+  variables of the source) and `variogram[i]` / `variogram_normalized[i]` (`verification.VariogramScores`, as `scores`).  With
+  `run(tails={name: spec})` also `tails[i]` / `tails_normalized[i]` (`verification.TailScores`, as `scores`)."""
 
   _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "energy", "variogram",
-              "variogram_normalized")
+              "variogram_normalized", "tails", "tails_normalized")
   _kind = "window results"
 
   def __init__(self, leads, steps: int, scores, scores_normalized, events=None, order=None, members=None, template=None, *,
-               order_normalized=None, energy=None, variogram=None, variogram_normalized=None):
+               order_normalized=None, energy=None, variogram=None, variogram_normalized=None, tails=None,
+               tails_normalized=None):
     self.leads, self.steps = [int(k) for k in leads], int(steps)
     self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
                      order_normalized=order_normalized, energy=energy, variogram=variogram,
-                     variogram_normalized=variogram_normalized)
+                     variogram_normalized=variogram_normalized, tails=tails, tails_normalized=tails_normalized)
     if len(self.scores) != len(self.leads) or len(self.scores_normalized) != len(self.leads):
       raise ValueError("a window result needs one score per window lead time")
     self.members, self.template = members, template
@@ -739,18 +754,20 @@ class EnsembleRolloutResult(_SeriesResult):
   `windows`: {name: `WindowRolloutResult`} for the entries of `run(windows=...)`, or None.  `energy`: one
   `verification.EnergyScores` per lead time -- the energy score of the groups of `run(energy=...)`, in the members' own units
   (normalised under a normalisation wrapper: what makes a norm over several variables meaningful) -- or None; `variogram` /
-  `variogram_normalized`: one `verification.VariogramScores` per lead time (as `scores` / `scores_normalized`), or None."""
+  `variogram_normalized`: one `verification.VariogramScores` per lead time (as `scores` / `scores_normalized`), or None.
+  `tails` / `tails_normalized`: one `verification.TailScores` per lead time (as `scores` / `scores_normalized`) -- the
+  threshold-weighted CRPS at the thresholds of `run(tails=...)` -- or None."""
 
   _carries = tuple(row[0] for row in _SERIES)
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
                scores_normalized=None, spectra_normalized=None, events=None, derived=None, order=None,
                order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, windows=None,
-               energy=None, variogram=None, variogram_normalized=None):
+               energy=None, variogram=None, variogram_normalized=None, tails=None, tails_normalized=None):
     self._set_series(scores=scores, scores_normalized=scores_normalized, spectra=spectra, spectra_normalized=spectra_normalized,
                      events=events, order=order, order_normalized=order_normalized, climatology=climatology,
                      climatology_normalized=climatology_normalized, energy=energy, variogram=variogram,
-                     variogram_normalized=variogram_normalized)
+                     variogram_normalized=variogram_normalized, tails=tails, tails_normalized=tails_normalized)
     self.derived = None if derived is None else dict(derived)
     self.windows = None if windows is None else dict(windows)
     self.mean, self.variance, self.members, self.quantiles = mean, variance, members, quantiles
@@ -762,8 +779,8 @@ class EnsembleRolloutResult(_SeriesResult):
 
   def merge(self, other: "EnsembleRolloutResult") -> "EnsembleRolloutResult":
     """The result over the union of the start dates, lead time by lead time (`EnsembleScores.merge`,
-    `EnsembleSpectra.merge`, `OrderScores.merge`, `ClimatologyScores.merge`, `VariogramScores.merge`: raw sums add;
-    `EnergyScores.merge`: the forecasts of both).  Fields, members and quantile fields belong to one date and are dropped."""
+    `EnsembleSpectra.merge`, `OrderScores.merge`, `ClimatologyScores.merge`, `VariogramScores.merge`, `TailScores.merge`: raw
+    sums add; `EnergyScores.merge`: the forecasts of both).  Fields, members and quantile fields belong to one date and are dropped."""
     if other.horizon != self.horizon:
       raise ValueError(f"merge: horizons differ ({self.horizon} and {other.horizon})")
     if other.n_members != self.n_members:
@@ -788,13 +805,14 @@ class _StoreSeries:
     self.clim, self.raw_clim = ([], []) if store.climatology is not None else (None, None)
     self.energy = None if store.energy is None else []
     self.variogram, self.raw_variogram = ([], []) if store.variogram is not None else (None, None)
+    self.tails, self.raw_tails = ([], []) if store.tails is not None else (None, None)
     self.members = [] if keep_members else None
 
   def score_lead(self, truth=None, *, want_fields: bool = False, after_score=None, clim_fields=None, n_samples=None,
                  source_truth=None) -> None:
     """Scores the store as it stands and appends to every series: the scores (the events ride with them), the order
-    statistics and their quantile fields, the climatology scores, the energy and variogram scores, the members -- in that
-    order on the device.  `truth`,
+    statistics and their quantile fields, the climatology scores, the energy and variogram scores, the tail scores, the
+    members -- in that order on the device.  `truth`,
     `want_fields`: as `ScoredStore.score`; `after_score()`: what the caller downloads between the scores and the rest;
     `clim_fields`, or `n_samples` and `source_truth`: as `ScoredStore.score_climatology`.  A new scorer adds its step here."""
     raw, ev = self.store.score(truth, want_fields=want_fields)   # (the events: on the truth already on the device)
@@ -817,6 +835,9 @@ class _StoreSeries:
     if self.variogram is not None:
       self.raw_variogram.append(self.store.score_variogram(None))
       self.variogram.append(self.raw_variogram[-1].scaled(self.scale))
+    if self.tails is not None:
+      self.raw_tails.append(self.store.score_tails(None))   # (the truth is on the device already)
+      self.tails.append(self.raw_tails[-1].scaled(self.scale))
     if self.members is not None:
       self.members.append([self.store.handle.ens_download_member(m) for m in range(self.store.n_members)])
 
@@ -824,7 +845,7 @@ class _StoreSeries:
     return DerivedRolloutResult(self.scores, self.raw, self.events, self.members, self.template, order=self.order,
                                 order_normalized=self.raw_order, quantiles=self.quantiles, climatology=self.clim,
                                 climatology_normalized=self.raw_clim, energy=self.energy, variogram=self.variogram,
-                                variogram_normalized=self.raw_variogram)
+                                variogram_normalized=self.raw_variogram, tails=self.tails, tails_normalized=self.raw_tails)
 
 
 class _WindowEntry:
@@ -855,7 +876,7 @@ class _WindowEntry:
     s = self.series
     return WindowRolloutResult(self.leads, self.spec.steps, s.scores, s.raw, s.events, s.order, s.members, s.template,
                                order_normalized=s.raw_order, energy=s.energy, variogram=s.variogram,
-                               variogram_normalized=s.raw_variogram)
+                               variogram_normalized=s.raw_variogram, tails=s.tails, tails_normalized=s.raw_tails)
 
 
 class _EnsembleRun:
@@ -936,7 +957,7 @@ class EnsembleRollout:
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
           keep_members: bool = False, events=None, derived=None, order=None,
           keep_quantiles: bool = False, climatology=None, windows=None, energy=None,
-          variogram=None) -> EnsembleRolloutResult:
+          variogram=None, tails=None) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -983,6 +1004,14 @@ class EnsembleRollout:
     every channel at every offset (`gc_ens_variogram_score`): `EnsembleRolloutResult.variogram` in physical units
     (`VariogramScores.scaled`), `variogram_normalized` as the device returned it, and the same for every `derived` entry
     and every window.  Without them nothing changes.
+    `tails`: a `verification.EventSpec` read as tails (direction > 0: the upper tail, weight 1{z >= threshold}; < 0: the lower
+    tail) for the main store, or a mapping {None: spec, name: spec, ...} whose other keys name entries of `derived` /
+    `windows` (an unknown key is a ValueError), with thresholds keyed by that store's variable names in physical units.  Per
+    lead time, after the variogram, the members of every point are sorted once and the threshold-weighted CRPS sums of all
+    thresholds are formed (`gc_ens_tail_score`, on the truth already there): `EnsembleRolloutResult.tails`
+    (`verification.TailScores` in physical units, `TailScores.scaled`), `tails_normalized` as the device returned them, and
+    the same on the results of the named entries.  The thresholds reach the members' units by the path of the thresholds of
+    `events`.  Without `tails` nothing changes.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -1014,8 +1043,13 @@ class EnsembleRollout:
         raise ValueError(f"energy: the groups {sorted(set(energy.names) - fitted)} name variables that no scored store has all of")
     if init_noise is not None and (len(init_noise) != M or any(len(z) < horizon for z in init_noise)):
       raise ValueError("init_noise must be [num_members][horizon] fields")
+    if tails is not None:
+      tails = dict(tails) if isinstance(tails, Mapping) else {None: tails}
+      known = set(derived or {}) | set(windows or {})
+      if set(tails) - known - {None}:
+        raise ValueError(f"tails: {sorted(set(tails) - known - {None})} name no entry of `derived` or `windows` ({sorted(known)})")
     run = self._setup(inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields,
-                      keep_members, events, derived, order, keep_quantiles, climatology, windows, energy, variogram)
+                      keep_members, events, derived, order, keep_quantiles, climatology, windows, energy, variogram, tails)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -1030,11 +1064,12 @@ class EnsembleRollout:
                                  order=main.order, order_normalized=main.raw_order, quantiles=main.quantiles,
                                  climatology=main.clim, climatology_normalized=main.raw_clim,
                                  windows=None if windows is None else {k: v.result() for k, v in run.windows.items()},
-                                 energy=main.energy, variogram=main.variogram, variogram_normalized=main.raw_variogram)
+                                 energy=main.energy, variogram=main.variogram, variogram_normalized=main.raw_variogram,
+                                 tails=main.tails, tails_normalized=main.raw_tails)
 
   def _setup(self, inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields, keep_members,
              events, derived, order=None, keep_quantiles=False, climatology=None, windows=None, energy=None,
-             variogram=None) -> "_EnsembleRun":
+             variogram=None, tails=None) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views."""
     run = _EnsembleRun()
     context = isel_time(inputs, slice(-context_steps, None))
@@ -1078,6 +1113,11 @@ class EnsembleRollout:
       part = None if energy is None else energy.restricted(template)
       return None if part is None else part.plan(template)
 
+    def tail_args(name, template, s, l):
+      """`tails=` / `tail_thresholds=` of the store `name` (None: the main store): its spec, thresholds in the members' units."""
+      spec = (tails or {}).get(name)
+      return {} if spec is None else {"tails": spec, "tail_thresholds": packed(spec, template, s, l)}
+
     weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
     wq = None
     if (events is not None or any(dev is not None for _, dev in entries.values())
@@ -1097,7 +1137,7 @@ class EnsembleRollout:
     main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
                                     thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
                                     set_per_score=specs is not None and len(specs) > 1, order=order, climatology=clim_handle,
-                                    energy=eplan(template0), variogram=vplan)
+                                    energy=eplan(template0), variogram=vplan, **tail_args(None, template0, scale, loc))
     run.main = _StoreSeries(main, scale, template0, keep_members=keep_members, keep_quantiles=keep_quantiles)
     main.reserve()
     if spectra:
@@ -1140,7 +1180,7 @@ class EnsembleRollout:
                                        plan=dplan, source=native, order=order, energy=eplan(dtemplate), variogram=vplan,
                                        climatology=None if clim_handle is None
                                        else den.climatology_handle(len(dplan["op"]), view=True),
-                                       climatology_source=clim_handle)
+                                       climatology_source=clim_handle, **tail_args(name, dtemplate, dscale, dloc))
       run.views[name] = _StoreSeries(store, dscale, dtemplate, keep_members=keep_members, keep_quantiles=keep_quantiles)
     for store in (v.store for v in run.views.values()):
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
@@ -1158,7 +1198,8 @@ class EnsembleRollout:
       wscale, wloc = wspec.channel_stats(sscale, sloc)
       store = verification.ScoredStore(den.window_handle(len(wscale), name), M, weights, events=wev,
                                        thresholds=None if wev is None else packed(wev, stemplate, wscale, wloc), weight_q=wq,
-                                       order=order, energy=eplan(stemplate), variogram=vplan)
+                                       order=order, energy=eplan(stemplate), variogram=vplan,
+                                       **tail_args(name, stemplate, wscale, wloc))
       run.windows[name] = _WindowEntry(wspec, _StoreSeries(store, wscale, stemplate, keep_members=keep_members), source, horizon)
       run.windows[name].start()
     return run

@@ -40,6 +40,11 @@ For `EnergySpec` groups of channels the device hands back the weighted squared d
 M + 1 fields (members and truth) and `EnergyScores` derives the energy score; for `VariogramSpec` grid offsets it hands
 back four additive sums per (batch, channel, offset) and `VariogramScores` derives the variogram score and the roughness
 of the members against the truth's.
+
+Tail skill (`gc_ens_tail_score`): the threshold-weighted CRPS of Gneiting & Ranjan (2011) in the
+chaining form of Allen et al. (2023) -- the plain CRPS of members and truth clamped at a threshold from one side.  The
+thresholds and directions are an `EventSpec`; the device sorts the members of a point once and hands back four raw sums per
+(threshold, batch, channel).  `TailScores` keeps them raw and derives the fair and the ensemble twCRPS.
 """
 from __future__ import annotations
 
@@ -757,6 +762,111 @@ class EventScores:
     return out
 
 
+class TailScores:
+  """The raw sums of `gc_ens_tail_score`: `sums` [T, B, c_out, 4] float64 -- S0 = sum w, S1 = sum w ae, S2 = sum w d,
+  S3 = sum w o over the counted nodes, with ae the mean absolute difference between the clamped members and the clamped
+  truth, d the mean absolute difference between two clamped members (the Gini mean difference) and o whether the truth lies
+  in the event -- `counts` [T, B, c_out] uint64 (counted points) and `invalid` [T] points skipped, with the member count M
+  and the directions [T] (> 0: the upper tail, weight 1{z >= threshold}; < 0: the lower tail).  The sums are additive.
+  Every score is [T, B, c_out] float64; where nothing counted (S0 = 0: a NaN threshold) it is NaN, not an error."""
+
+  def __init__(self, sums, counts, n_members: int, directions: Sequence[int], invalid=None):
+    self.sums = np.asarray(sums, dtype=np.float64)
+    self.counts = np.asarray(counts, dtype=np.uint64)
+    self.n_members = int(n_members)
+    self.directions = tuple(int(np.sign(d)) for d in directions)
+    if self.n_members < 2:
+      raise ValueError("n_members must be >= 2")
+    if self.sums.ndim != 4 or self.sums.shape[-1] != 4:
+      raise ValueError(f"sums must be [T, batch, channels, 4], got {self.sums.shape}")
+    if self.counts.shape != self.sums.shape[:3]:
+      raise ValueError(f"counts must be {self.sums.shape[:3]}, got {self.counts.shape}")
+    if len(self.directions) != self.sums.shape[0] or any(d == 0 for d in self.directions):
+      raise ValueError(f"directions must be {self.sums.shape[0]} non-zero signs")
+    self.invalid = (np.zeros(self.sums.shape[0], np.uint64) if invalid is None
+                    else np.asarray(invalid, dtype=np.uint64).reshape(self.sums.shape[0]))
+
+  def _over_weight(self, a) -> np.ndarray:
+    out = np.full(self.sums.shape[:3], np.nan)
+    np.divide(a, self.sums[..., 0], out=out, where=self.sums[..., 0] != 0.0)
+    return out
+
+  @property
+  def valid_weight(self) -> np.ndarray:
+    """S0: the node weight of the points that counted."""
+    return self.sums[..., 0]
+
+  @property
+  def valid_points(self) -> np.ndarray:
+    return self.counts
+
+  @property
+  def abs_error(self) -> np.ndarray:
+    """S1 / S0: the mean absolute difference between a clamped member and the clamped truth."""
+    return self._over_weight(self.sums[..., 1])
+
+  @property
+  def pair_distance(self) -> np.ndarray:
+    """S2 / S0: the mean absolute difference between two clamped members."""
+    return self._over_weight(self.sums[..., 2])
+
+  @property
+  def twcrps(self) -> np.ndarray:
+    """The fair threshold-weighted CRPS: unbiased for that of the distribution the members were drawn from."""
+    return self._over_weight(self.sums[..., 1] - 0.5 * self.sums[..., 2])
+
+  @property
+  def twcrps_ensemble(self) -> np.ndarray:
+    """The threshold-weighted CRPS of the M-member empirical distribution (pair term normalised by M^2)."""
+    m = float(self.n_members)
+    return self._over_weight(self.sums[..., 1] - 0.5 * (m - 1.0) / m * self.sums[..., 2])
+
+  @property
+  def base_rate(self) -> np.ndarray:
+    """S3 / S0: how often the truth lay in the event."""
+    return self._over_weight(self.sums[..., 3])
+
+  def scaled(self, channel_scale) -> "TailScores":
+    """The scores of a x + b in place of x (members, truth and thresholds alike), a = channel_scale [c_out] > 0, any b: S1
+    and S2 scale with a; weights, base rates and counts do not change.  a <= 0 is a ValueError: a negative scale swaps the
+    tails."""
+    a = np.asarray(channel_scale, dtype=np.float64).reshape(-1)
+    if a.shape != (self.sums.shape[2],):
+      raise ValueError(f"channel_scale must have shape ({self.sums.shape[2]},)")
+    if not np.all(np.isfinite(a) & (a > 0.0)):
+      raise ValueError("channel_scale must be finite and > 0 (a negative scale swaps the tails)")
+    f = np.stack([np.ones_like(a), a, a, np.ones_like(a)], axis=-1)
+    return TailScores(self.sums * f[None, None], self.counts, self.n_members, self.directions, self.invalid)
+
+  @staticmethod
+  def merge(parts: Sequence["TailScores"]) -> "TailScores":
+    """Scores over the union of what the parts covered (other nodes, other dates): raw sums and counts add."""
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    for p in parts[1:]:
+      if p.n_members != first.n_members or p.directions != first.directions or p.sums.shape != first.sums.shape:
+        raise ValueError("merge: the parts differ in members, directions or shape")
+    sums, counts, invalid = first.sums.copy(), first.counts.copy(), first.invalid.copy()
+    for p in parts[1:]:
+      sums += p.sums
+      counts += p.counts
+      invalid += p.invalid
+    return TailScores(sums, counts, first.n_members, first.directions, invalid)
+
+  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
+    """{score: {variable: [T, batch, channels of the variable]}} in the channel order of `datasets.channel_layout`."""
+    layout = datasets.channel_layout(datasets.as_dataset(template))
+    if sum(n for _, _, n in layout) != self.sums.shape[2]:
+      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.sums.shape[2]}")
+    out: Dict[str, Dict[str, np.ndarray]] = {}
+    for score in ("twcrps", "twcrps_ensemble", "abs_error", "pair_distance", "base_rate", "valid_weight", "valid_points"):
+      values = getattr(self, score)
+      out[score] = {name: values[:, :, off:off + n] for name, off, n in layout}
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # derived and pooled fields: wind speed, neighbourhood maxima, area means (gc_ens_derive_*)
 # ---------------------------------------------------------------------------------------------
@@ -1279,7 +1389,8 @@ class ScoredStore:
   (`EnergySpec.plan`, `VariogramSpec.plan`) of `score_energy` and `score_variogram`, and optionally `climatology`: a second handle of the
   same graph, batch and c_out (`Denoiser.climatology_handle`) whose member store takes the K climatological samples
   `score_climatology` scores the members against -- on a derived view together with `climatology_source`, the handle whose
-  store holds the samples the view's plan is applied to.  `EnsembleSampler` and `EnsembleRollout` use one for the main
+  store holds the samples the view's plan is applied to, and optionally `tails`: an `EventSpec` read as tails (direction
+  > 0: the upper tail) with its packed `tail_thresholds` in the members' units, for `score_tails`.  `EnsembleSampler` and `EnsembleRollout` use one for the main
   store and one per derived view.
 
   `set_per_score`: the plan and the thresholds are not set once by `setup` but by every `score` -- two stores that share
@@ -1287,7 +1398,8 @@ class ScoredStore:
 
   def __init__(self, handle, n_members: int, node_weight=None, *, events: Optional["EventSpec"] = None, thresholds=None,
                weight_q: Optional[Tuple[np.ndarray, float]] = None, plan=None, source=None, set_per_score: bool = False,
-               order=None, climatology=None, climatology_source=None, energy=None, variogram=None):
+               order=None, climatology=None, climatology_source=None, energy=None, variogram=None,
+               tails: Optional["EventSpec"] = None, tail_thresholds=None):
     if climatology_source is not None and (climatology is None or plan is None):
       raise ValueError("a climatology source goes with a climatology handle and a derive plan")
     if events is not None and weight_q is None:
@@ -1300,6 +1412,7 @@ class ScoredStore:
     self.order = None if order is None else tuple(float(p) for p in np.asarray(order, dtype=np.float64).reshape(-1))
     self.climatology, self.climatology_source = climatology, climatology_source
     self.energy, self.variogram = energy, variogram          # the plans (`EnergySpec.plan`, `VariogramSpec.plan`) or None
+    self.tails, self.tail_thresholds = tails, tail_thresholds
     self._clim_reserved = 0                      # K of the store this object reserved on the climatology handle
     self._clim_plan_set = False                  # the plan has been handed to the climatology handle (a derived view)
 
@@ -1329,13 +1442,19 @@ class ScoredStore:
       v = self.variogram
       self.handle.ens_variogram_set(v["n_lat"], v["n_lon"], v["offsets"], v["p"])
 
+  def _set_tails(self) -> None:
+    if self.tails is not None:
+      self.handle.ens_tail_set(self.tail_thresholds, self.tails.directions)
+
   def configure(self) -> None:
-    """The plan, the thresholds, the probabilities and the multivariate plans: all survive `ens_reserve` and every score."""
+    """The plan, the thresholds, the probabilities, the multivariate plans and the tails: all survive `ens_reserve` and
+    every score."""
     self._set_plan()
     self._set_events()
     self._set_order()
     self._set_energy()
     self._set_variogram()
+    self._set_tails()
 
   def setup(self) -> None:
     self.reserve()
@@ -1381,6 +1500,16 @@ class ScoredStore:
       self._set_variogram()
     sums, counts = self.handle.ens_variogram_score(truth)
     return VariogramScores(sums, counts, self.n_members, self.variogram["offsets"], self.variogram["p"])
+
+  def score_tails(self, truth=None) -> Optional["TailScores"]:
+    """The raw threshold-weighted CRPS sums of the store at the thresholds of `tails` (None without it), in the store's own
+    units; `truth` None: the truth already on the device.  On a derived view call it after `score`."""
+    if self.tails is None:
+      return None
+    if self.set_per_score:
+      self._set_tails()
+    sums, counts, invalid = self.handle.ens_tail_score(truth)
+    return TailScores(sums, counts, self.n_members, self.tails.directions, invalid)
 
   def _reserve_climatology(self, K: int) -> None:
     if K != self._clim_reserved:

@@ -770,6 +770,52 @@ int gc_ens_variogram_score(gc_handle* h, const float* truth /* NULL = the truth 
                            double* sums /* [4][B][c_out][O] */, uint64_t* counts /* [B][c_out][O], NULL allowed */);
 
 /*
+ * Threshold-weighted CRPS on the device: how good the forecast distribution of the gc_ens_* store is
+ * in one tail (Gneiting & Ranjan 2011), in the chaining form of Allen et al. (2023): for the weight 1{z >= t} the twCRPS is
+ * the plain CRPS of the clamped values max(z, t), for 1{z <= t} of min(z, t).  Clamping keeps the order of the members, so a
+ * point is sorted once and every threshold costs O(M) (gencast-flax-nnx_amd/verification.py TailScores).  The reference
+ * project has no verification code; the yardstick is the definition below, restated in float64 in tests/tail_reference.py.
+ * Members x_0..x_{M-1} (2 <= M <= 64) and truth y are [G,B,c_out] float32 in the sample layout.  w[g] are the float node
+ * weights of gc_ens_set_node_weight.  There are T threshold fields thr_t (1 <= T <= 8), each [G,B,c_out] float32, with a
+ * direction dir_t != 0.  This is the convention of gc_ens_event_set.
+ * A point counts for threshold t when y, all M members and thr_t are finite there.  A NaN threshold means "not evaluated"
+ * for that t only.
+ * Per counted point, with x_(0) <= ... <= x_(M-1) the members in ascending order:
+ *   v(z) = fmaxf(z, thr_t) when dir_t > 0.  This is the upper tail, weight 1{z >= thr}.
+ *   v(z) = fminf(z, thr_t) when dir_t < 0.  Both are exact in float32.
+ *   u_k = v(x_(k)), which is still ascending.
+ *   AE = sum_{k=0}^{M-1} |(double)u_k - (double)v(y)|, added in ascending k.  ae = AE / M.
+ *   PD = sum_{k=1}^{M-1} (double)(k (M-k)) ((double)u_k - (double)u_{k-1}), added in ascending k.  d = PD / (M(M-1)/2).
+ *     This "gap form" equals sum_{i<j} |u_i - u_j|.  Every term is non-negative, so there is no cancellation.
+ *   o = [y in the event], strict as in section 8f: y > thr_t for dir_t > 0, y < thr_t for dir_t < 0.
+ * Every operation is a rounded double operation with no contraction.
+ * Per (t, b, c), over the counted nodes:
+ *   sums[t][b][c][0..3] = sum w, sum w ae, sum w d, sum w o
+ *   counts[t][b][c] = counted points (uint64)
+ *   invalid[t] = points skipped
+ * All of these are raw and additive over batches and dates.  On the host, with S0..S3 the four sums: fair twCRPS =
+ * (S1 - S2/2)/S0, ensemble twCRPS = (S1 - (M-1)/M S2/2)/S0 (the pairing of gc_ens_score's sums 4 and 5: d is the same Gini
+ * mean difference), base rate = S3/S0.
+ *   gc_ens_tail_set    the threshold fields and directions.  Needs gc_set_graph only; buffers of its own, independent of
+ *                      gc_ens_event_set (both may be set, with different T); survives gc_ens_reserve; a repeated call
+ *                      replaces ("device_allocations" stays flat); released by gc_destroy.  GC_ERR_UNSUPPORTED: T outside
+ *                      1..8.  GC_ERR_INVALID_ARGUMENT: a zero direction or a null pointer.  GC_ERR_STATE: before gc_set_graph.
+ *   gc_ens_tail_score  truth: host [G, B, c_out], uploaded and kept, or NULL = the truth uploaded last (the buffer
+ *                      gc_ens_score uses).  sums is required, counts and invalid may be NULL.  Two launches: a pass that
+ *                      reads the M members of a point once, sorts them in registers and walks the T thresholds, and a
+ *                      finish that adds the per-block partials in block order.  Synchronous.  GC_ERR_STATE: no thresholds,
+ *                      no member store, a slot not pushed since gc_ens_reserve, no node weights, no truth.
+ * No atomics on floats and a fixed order of every sum: the same call twice returns identical bytes.  Nothing else on the
+ * handle is touched.  Counters: "ens_tail_calls", "ens_tail_device_us" (HIP-event time of the last call's launches),
+ * "ens_tail_invalid_points" (of the last call, over all thresholds).
+ */
+int gc_ens_tail_set(gc_handle* h, int32_t n_thresholds, const float* thresholds /* [T][G,B,c_out] */,
+                    const int32_t* direction /* [T] */);
+int gc_ens_tail_score(gc_handle* h, const float* truth /* NULL = the truth uploaded last */,
+                      double* sums /* [T][B][c_out][4] */, uint64_t* counts /* [T][B][c_out], NULL allowed */,
+                      uint64_t* invalid /* [T], NULL allowed */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
