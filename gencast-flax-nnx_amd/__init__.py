@@ -28,6 +28,9 @@ Public surface (mirrors the reference's call contracts):
                       EnsembleRollout.run(energy=..., variogram=...))
                       TailScores: the threshold-weighted CRPS at the thresholds of an EventSpec, from members sorted once
                       per point on the GPU (GenCast.ensemble_tails, EnsembleRollout.run(tails=...))
+                      RegionSpec / RegionScores: the ensemble scores per region of the grid (tropics, extratropics, land,
+                      sea, boxes), every region from one pass on the GPU (GenCast.ensemble_regions,
+                      EnsembleRollout.run(regions=...))
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
@@ -46,7 +49,8 @@ from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, Ense
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
 from .verification import (ClimatologyScores, DerivedSpec, EnergyScores, EnergySpec, EnsembleScores, EventScores,  # noqa: F401
-                           EventSpec, OrderScores, TailScores, VariogramScores, VariogramSpec, WindowSpec)
+                           EventSpec, OrderScores, RegionScores, RegionSpec, TailScores, VariogramScores, VariogramSpec,
+                           WindowSpec)
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
@@ -54,4 +58,5 @@ __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_
            "compute_loss", "validation_loss", "verification", "EnsembleScores", "spectra", "EnsembleSpectra",
            "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec",
            "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores",
-           "WindowSpec", "WindowRolloutResult", "EnergySpec", "EnergyScores", "VariogramSpec", "VariogramScores", "TailScores"]
+           "WindowSpec", "WindowRolloutResult", "EnergySpec", "EnergyScores", "VariogramSpec", "VariogramScores", "TailScores",
+           "RegionSpec", "RegionScores"]

@@ -143,6 +143,9 @@ SIGNATURES = {
     "gc_ens_tail_set": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p, _i32p]),
     "gc_ens_tail_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
                                          ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_region_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
+    "gc_ens_region_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_uint64)]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -239,6 +242,7 @@ class NativeDenoiser:
     self._energy_groups = None                 # groups of the energy plan this object set (None: ens_energy_set not called)
     self._variogram_offsets = None             # offsets of the variogram plan this object set (None: ens_variogram_set not called)
     self._tail_thresholds = 0                  # tail threshold fields this object handed to the handle
+    self._regions = 0                          # regions of the plan this object handed to the handle (0: ens_region_set not called)
     self._window_length = 0                    # length of the window plan this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
@@ -912,6 +916,41 @@ class NativeDenoiser:
     self._check(self._lib.gc_ens_tail_score(self._h, None if t is None else _ptr(t, _f32p),
                                             _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(counts, u64), _ptr(invalid, u64)))
     return sums, counts, invalid
+
+  # -- regional ensemble scores (the sums of ens_score per region of grid nodes, from one pass) ---------
+  def ens_region_set(self, node_bits, n_regions: int) -> None:
+    """`node_bits` [G] uint32, bit r set = grid node g belongs to region r < `n_regions` (1..32); regions may overlap, a node
+    with no bit is never read: gc_ens_region_set; needs `set_graph` only and survives `ens_reserve`.  At most 256 distinct
+    non-zero values.  `verification.RegionSpec.node_bits` builds the argument."""
+    R = int(n_regions)
+    if not 1 <= R <= 32:
+      raise ValueError(f"n_regions must be in 1..32, got {R}")
+    raw = np.asarray(node_bits)
+    if raw.shape != (self.num_grid_nodes,):
+      raise ValueError(f"node_bits must have shape ({self.num_grid_nodes},), got {raw.shape}")
+    if raw.dtype.kind not in "ui" or (raw.size and (int(raw.min()) < 0 or int(raw.max()) >> R)):
+      raise ValueError(f"node_bits must be unsigned integers below 2^{R}")
+    bits = np.ascontiguousarray(raw, dtype=np.uint32)
+    self._check(self._lib.gc_ens_region_set(self._h, R, _ptr(bits, ctypes.POINTER(ctypes.c_uint32))))
+    self._regions = R
+
+  def ens_region_score(self, truth=None):
+    """-> (sums [R, B, c_out, 6] float64, hist [R, B, c_out, M + 1] uint64, invalid [R] uint64): per region the raw, additive
+    sums, rank histogram and skipped points of `ens_score` restricted to the region's nodes (gc_ens_region_score;
+    `verification.RegionScores` derives the scores).  `truth` [G, B, c_out], or None = the truth uploaded last."""
+    if not self._regions:
+      raise GencastHipError("libgencast_hip error 4: no regions (ens_region_set has not been called on this object)")
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    t = self._truth_arg(truth)
+    R, B, C = self._regions, self.cfg.batch, self.cfg.c_out
+    u64 = ctypes.POINTER(ctypes.c_uint64)
+    sums = np.empty((R, 6, B, C), dtype=np.float64)
+    hist = np.empty((R, B, C, self._ens_members + 1), dtype=np.uint64)
+    invalid = np.empty(R, dtype=np.uint64)
+    self._check(self._lib.gc_ens_region_score(self._h, None if t is None else _ptr(t, _f32p),
+                                              _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(hist, u64), _ptr(invalid, u64)))
+    return np.ascontiguousarray(np.moveaxis(sums, 1, -1)), hist, invalid
 
   # -- time-window ensemble fields (a ring of the last lead times, reduced into this handle's member store) --
   def ens_window_set(self, kind: int, length: int, coef=None) -> None:

@@ -13,7 +13,8 @@
 //   gc_window.hip    gc_ens_window_*
 //   gc_multivar.hip  gc_ens_energy_*, gc_ens_variogram_*
 //   gc_tail.hip      gc_ens_tail_*
-// The last nine are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
+//   gc_region.hip    gc_ens_region_*
+// The last ten are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
 // lead times of another).  What they share -- field length, upload through
 // the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
 // relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
@@ -416,6 +417,20 @@ struct gc_handle {
   unsigned long long* d_tail_outc = nullptr;     // [T][B c_out] counted points
   gci::Bracket tail_time{events};                // of the last call
   int64_t tail_calls = 0, tail_device_us = 0, tail_invalid_points = 0;
+
+  // regional ensemble scores (gc_ens_region_*, gc_region.hip): the plan on the host, its device copy and the sums of one pass
+  gci::BufferGroup reg_allocs{groups};            // the plan's device copy and everything sized by it and by M: replaced as a whole
+  int reg_R = 0;                                 // regions set (0: no plan)
+  int reg_listed = 0, reg_blocks = 0;            // nodes that belong to a region; entries of the block table
+  std::vector<int> reg_plan;                     // order [listed], {begin, end} [blocks], atom bits [blocks]: kept across gc_ens_reserve
+  int reg_dev_M = 0;                             // M the device buffers are sized for (0: none)
+  int* d_reg_plan = nullptr;                     // reg_plan as it lies
+  double* d_reg_part = nullptr;                  // [blocks][6][B c_out] per-block column sums
+  unsigned* d_reg_hpart = nullptr;               // [blocks][B c_out][M + 1] per-block rank counts, then [blocks][tiles] skipped points
+  double* d_reg_sums = nullptr;                  // [R][6][B][c_out]
+  unsigned long long* d_reg_hist = nullptr;      // [R][B][c_out][M + 1], then [R] skipped points
+  gci::Bracket reg_time{events};                 // of the last call
+  int64_t reg_calls = 0, reg_device_us = 0, reg_invalid_points = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

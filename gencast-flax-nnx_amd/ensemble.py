@@ -161,18 +161,25 @@ class EnsembleSampler:
     self._one_rank("tails")
     return self._run(inputs, targets, forcings, num_members, None, tails=spec)
 
+  def regions(self, inputs, targets, forcings, num_members: int, spec):
+    """Runs the members as `scores` does and forms, on the device, the sums of `scores` for every region of `spec` (a
+    `verification.RegionSpec`) from one pass over the nodes of all regions: `verification.RegionScores`, whose `[name]` is the
+    region's `EnsembleScores`.  No member is downloaded."""
+    self._one_rank("regions")
+    return self._run(inputs, targets, forcings, num_members, None, regions=spec)
+
   def _spectral(self, inputs, targets, forcings, num_members, score_fields, lmax):
     self._one_rank("spectra")
     return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
 
   def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,
            lmax: Optional[int] = None, events=None, derived=None, order=None, climatology=None, multivariate=None,
-           tails=None):
+           tails=None, regions=None):
     """`score_fields` None: members come back as Datasets (`__call__`) or, with `spectral`, only their spectra are
     formed, or, with `events` (an EventSpec), only their event tables, or, with `order` (probabilities, want fields), only
     their order statistics, or, with `climatology` (K Datasets), only their skill against it, or, with `multivariate` (an
     EnergySpec or None, a VariogramSpec or None), only their energy and variogram scores, or, with `tails` (an EventSpec), only
-    their threshold-weighted CRPS sums; else they are scored
+    their threshold-weighted CRPS sums, or, with `regions` (a RegionSpec), only their sums per region; else they are scored
     (`scores`), with `spectral` both."""
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
@@ -202,14 +209,14 @@ class EnsembleSampler:
     scoring = score_fields is not None
     main = None                                            # lane 0's member store, where anything is scored at all
     if (scoring or spectral or events is not None or derived is not None or order is not None or climatology is not None or
-        multivariate is not None or tails is not None):
+        multivariate is not None or tails is not None or regions is not None):
       dspec, dev = derived if derived is not None else (None, None)
       weights = None if spectral and not scoring else verification.node_weights(template)
       wq = None if events is None and dev is None else verification.quantize_node_weights(weights)
       # (scored once: the thresholds are set by that call, after the members are in)
       main = verification.ScoredStore(native, num_members,
                                       weights if scoring or order is not None or climatology is not None or
-                                      multivariate is not None or tails is not None else None,
+                                      multivariate is not None or tails is not None or regions is not None else None,
                                       events=events, thresholds=None if events is None else events.packed(template), weight_q=wq,
                                       set_per_score=True, order=None if order is None else order[0],
                                       climatology=None if climatology is None
@@ -218,7 +225,8 @@ class EnsembleSampler:
                                       else multivariate[0].plan(template),
                                       variogram=None if multivariate is None or multivariate[1] is None
                                       else multivariate[1].plan(template),
-                                      tails=tails, tail_thresholds=None if tails is None else tails.packed(template))
+                                      tails=tails, tail_thresholds=None if tails is None else tails.packed(template),
+                                      regions=regions, region_bits=None if regions is None else regions.node_bits(template))
       main.setup()
     if spectral:
       _spectra.ensure_tables(native, template, lmax)
@@ -253,6 +261,8 @@ class EnsembleSampler:
       return main.score_climatology([pack(c) for c in climatology], truth)
     if tails is not None:
       return main.score_tails(truth)
+    if regions is not None:
+      return main.score_regions(truth)
     if multivariate is not None:
       en = main.score_energy(truth)
       return en, main.score_variogram(truth if en is None else None)      # (the truth is on the device after the first)

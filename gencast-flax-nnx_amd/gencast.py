@@ -136,6 +136,14 @@ class GenCast:
     runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.tails(inputs, targets, forcings, num_members, spec)
 
+  def ensemble_regions(self, inputs, targets, forcings=None, *, num_members, spec, rngs=0, concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and forms on the GPU the sums of `ensemble_scores` for
+    every region of `spec` (`verification.RegionSpec`: named boolean masks over the grid, overlapping or not) from ONE pass
+    over the nodes that belong to any region: `verification.RegionScores`, whose `[name]` is an `EnsembleScores` -- `.crps`,
+    `.rmse`, `.spread_skill_ratio`, `.rank_histogram` of that region, latitude-weighted.  No member leaves the device."""
+    runner = self._ensemble_sampler(rngs, concurrent_members)
+    return runner.regions(inputs, targets, forcings, num_members, spec)
+
   def ensemble_order(self, inputs, targets, forcings=None, *, num_members, probs=(), quantile_fields=False, rngs=0,
                      concurrent_members=1):
     """Samples `num_members` (2..64) members as `ensemble_scores` does and sorts them point by point on the GPU:
@@ -182,7 +190,8 @@ class GenCast:
     """Rolls `num_members` (2..64) members out `horizon` autoregressive steps with every member's context resident on
     the GPU and scores their states against `targets[k]` at every lead time: `rollout.EnsembleRolloutResult` (per lead
     time `EnsembleScores`, with `spectra=True` also `EnsembleSpectra`, with `fields=True` the mean and variance, with
-    `events=EventSpec` also `EventScores`, with `tails=EventSpec` also `TailScores`).  No
+    `events=EventSpec` also `EventScores`, with `tails=EventSpec` also `TailScores`, with `regions=RegionSpec` also
+    `RegionScores`).  No
     member leaves the device.  `rngs`: the base seed (member m is `DeviceRollout(...).run(rngs=member_seed(rngs, m))`);
     `norm`: an `InputsAndResiduals` whose statistics apply (its own `ensemble_rollout` passes itself); `device_noise`
     defaults to the sampler's; other keywords as `rollout.EnsembleRollout.run`."""

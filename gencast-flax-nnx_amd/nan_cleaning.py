@@ -148,6 +148,11 @@ class NaNCleaner:
     points the device does not count (`TailScores.invalid`)."""
     return self.predictor.ensemble_tails(*self._cleaned(inputs, targets, forcings, False), **kwargs)
 
+  def ensemble_regions(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """Inputs and forcings are cleaned; the targets pass through unchanged, as in `ensemble_scores`: their NaNs are
+    points the device does not count (`RegionScores.invalid`, per region)."""
+    return self.predictor.ensemble_regions(*self._cleaned(inputs, targets, forcings, False), **kwargs)
+
   def ensemble_spectra(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """Inputs and forcings are cleaned, and so are the targets: a transform cannot skip points, so the spectrum of the
     cleaned variable is that of the field with its NaNs (land points) replaced by the fill value, truth and members

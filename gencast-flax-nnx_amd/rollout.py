@@ -269,6 +269,13 @@ class InputsAndResiduals:
     nspec = spec.mapped(datasets.as_dataset(targets), lambda name, v: self._subtract_input_and_normalize_target(raw, name, v))
     return self.predictor.ensemble_tails(ni, nt, forcings=nf, spec=nspec, **kwargs).scaled(scale)
 
+  def ensemble_regions(self, inputs, targets, forcings=None, **kwargs):
+    """`ensemble_regions` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets, returned
+    in physical units: every region's raw sums are rescaled as in `ensemble_scores` (`RegionScores.scaled`)."""
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    scale = self._target_scale(raw, targets)
+    return self.predictor.ensemble_regions(ni, nt, forcings=nf, **kwargs).scaled(scale)
+
   def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, **kwargs):
     """`ensemble_rollout` of the wrapped predictor with this wrapper as its normalisation (`EnsembleRollout(norm=self)`):
     the inputs go in RAW -- the device rollout normalises them itself and folds the residual arithmetic into its
@@ -633,7 +640,8 @@ _SERIES = (("scores", verification.EnsembleScores, None), ("scores_normalized", 
            ("energy", verification.EnergyScores, "energy scores"),
            ("variogram", verification.VariogramScores, "variogram scores"),
            ("variogram_normalized", verification.VariogramScores, None),
-           ("tails", verification.TailScores, "tail scores"), ("tails_normalized", verification.TailScores, None))
+           ("tails", verification.TailScores, "tail scores"), ("tails_normalized", verification.TailScores, None),
+           ("regions", verification.RegionScores, "region scores"), ("regions_normalized", verification.RegionScores, None))
 
 
 class _SeriesResult:
@@ -642,8 +650,8 @@ class _SeriesResult:
   _carries: Sequence[str] = ()
   _kind = "results"                                       # (as the merge's error messages name the two operands)
   # series that exist on an instance only when the run asked for them; the class holds their None (see `_SERIES`)
-  _optional = ("energy", "variogram", "variogram_normalized", "tails", "tails_normalized")
-  energy = variogram = variogram_normalized = tails = tails_normalized = None
+  _optional = ("energy", "variogram", "variogram_normalized", "tails", "tails_normalized", "regions", "regions_normalized")
+  energy = variogram = variogram_normalized = tails = tails_normalized = regions = regions_normalized = None
 
   def _set_series(self, **series) -> None:
     """Copies the series into lists (the scores first) and checks that the others cover the lead times of the scores."""
@@ -686,19 +694,21 @@ class DerivedRolloutResult(_SeriesResult):
   climatological samples.  With `run(energy=...)` / `run(variogram=...)` also `energy[k]` (`verification.EnergyScores` over the
   groups whose variables are all derived variables of this entry, in the members' own units; None where no group is) and
   `variogram[k]` / `variogram_normalized[k]` (`verification.VariogramScores`, as `scores`).  With `run(tails={name: spec})`
-  also `tails[k]` / `tails_normalized[k]` (`verification.TailScores`, as `scores`)."""
+  also `tails[k]` / `tails_normalized[k]` (`verification.TailScores`, as `scores`).  With `run(regions={name: spec})` also
+  `regions[k]` / `regions_normalized[k]` (`verification.RegionScores`, as `scores`)."""
 
   _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "climatology", "climatology_normalized",
-              "energy", "variogram", "variogram_normalized", "tails", "tails_normalized")
+              "energy", "variogram", "variogram_normalized", "tails", "tails_normalized", "regions", "regions_normalized")
   _kind = "derived results"
 
   def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, order=None,
                order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, energy=None,
-               variogram=None, variogram_normalized=None, tails=None, tails_normalized=None):
+               variogram=None, variogram_normalized=None, tails=None, tails_normalized=None, regions=None,
+               regions_normalized=None):
     self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
                      order_normalized=order_normalized, climatology=climatology, climatology_normalized=climatology_normalized,
                      energy=energy, variogram=variogram, variogram_normalized=variogram_normalized, tails=tails,
-                     tails_normalized=tails_normalized)
+                     tails_normalized=tails_normalized, regions=regions, regions_normalized=regions_normalized)
     self.members, self.template, self.quantiles = members, template, quantiles
 
   def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
@@ -715,19 +725,21 @@ class WindowRolloutResult(_SeriesResult):
   `template`: the Dataset of the source's variables for `per_variable`.  With `run(energy=...)` / `run(variogram=...)` also
   `energy[i]` (`verification.EnergyScores` of the windowed fields, in the members' own units; None where no group names
   variables of the source) and `variogram[i]` / `variogram_normalized[i]` (`verification.VariogramScores`, as `scores`).  With
-  `run(tails={name: spec})` also `tails[i]` / `tails_normalized[i]` (`verification.TailScores`, as `scores`)."""
+  `run(tails={name: spec})` also `tails[i]` / `tails_normalized[i]` (`verification.TailScores`, as `scores`).  With
+  `run(regions={name: spec})` also `regions[i]` / `regions_normalized[i]` (`verification.RegionScores`, as `scores`)."""
 
   _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "energy", "variogram",
-              "variogram_normalized", "tails", "tails_normalized")
+              "variogram_normalized", "tails", "tails_normalized", "regions", "regions_normalized")
   _kind = "window results"
 
   def __init__(self, leads, steps: int, scores, scores_normalized, events=None, order=None, members=None, template=None, *,
                order_normalized=None, energy=None, variogram=None, variogram_normalized=None, tails=None,
-               tails_normalized=None):
+               tails_normalized=None, regions=None, regions_normalized=None):
     self.leads, self.steps = [int(k) for k in leads], int(steps)
     self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
                      order_normalized=order_normalized, energy=energy, variogram=variogram,
-                     variogram_normalized=variogram_normalized, tails=tails, tails_normalized=tails_normalized)
+                     variogram_normalized=variogram_normalized, tails=tails, tails_normalized=tails_normalized,
+                     regions=regions, regions_normalized=regions_normalized)
     if len(self.scores) != len(self.leads) or len(self.scores_normalized) != len(self.leads):
       raise ValueError("a window result needs one score per window lead time")
     self.members, self.template = members, template
@@ -756,18 +768,22 @@ class EnsembleRolloutResult(_SeriesResult):
   (normalised under a normalisation wrapper: what makes a norm over several variables meaningful) -- or None; `variogram` /
   `variogram_normalized`: one `verification.VariogramScores` per lead time (as `scores` / `scores_normalized`), or None.
   `tails` / `tails_normalized`: one `verification.TailScores` per lead time (as `scores` / `scores_normalized`) -- the
-  threshold-weighted CRPS at the thresholds of `run(tails=...)` -- or None."""
+  threshold-weighted CRPS at the thresholds of `run(tails=...)` -- or None.  `regions` / `regions_normalized`: one
+  `verification.RegionScores` per lead time (as `scores` / `scores_normalized`) -- the scores of every region of
+  `run(regions=...)`, `regions[k][name]` an `EnsembleScores` -- or None."""
 
   _carries = tuple(row[0] for row in _SERIES)
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
                scores_normalized=None, spectra_normalized=None, events=None, derived=None, order=None,
                order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, windows=None,
-               energy=None, variogram=None, variogram_normalized=None, tails=None, tails_normalized=None):
+               energy=None, variogram=None, variogram_normalized=None, tails=None, tails_normalized=None, regions=None,
+               regions_normalized=None):
     self._set_series(scores=scores, scores_normalized=scores_normalized, spectra=spectra, spectra_normalized=spectra_normalized,
                      events=events, order=order, order_normalized=order_normalized, climatology=climatology,
                      climatology_normalized=climatology_normalized, energy=energy, variogram=variogram,
-                     variogram_normalized=variogram_normalized, tails=tails, tails_normalized=tails_normalized)
+                     variogram_normalized=variogram_normalized, tails=tails, tails_normalized=tails_normalized,
+                     regions=regions, regions_normalized=regions_normalized)
     self.derived = None if derived is None else dict(derived)
     self.windows = None if windows is None else dict(windows)
     self.mean, self.variance, self.members, self.quantiles = mean, variance, members, quantiles
@@ -779,8 +795,8 @@ class EnsembleRolloutResult(_SeriesResult):
 
   def merge(self, other: "EnsembleRolloutResult") -> "EnsembleRolloutResult":
     """The result over the union of the start dates, lead time by lead time (`EnsembleScores.merge`,
-    `EnsembleSpectra.merge`, `OrderScores.merge`, `ClimatologyScores.merge`, `VariogramScores.merge`, `TailScores.merge`: raw
-    sums add; `EnergyScores.merge`: the forecasts of both).  Fields, members and quantile fields belong to one date and are dropped."""
+    `EnsembleSpectra.merge`, `OrderScores.merge`, `ClimatologyScores.merge`, `VariogramScores.merge`, `TailScores.merge`,
+    `RegionScores.merge`: raw sums add; `EnergyScores.merge`: the forecasts of both).  Fields, members and quantile fields belong to one date and are dropped."""
     if other.horizon != self.horizon:
       raise ValueError(f"merge: horizons differ ({self.horizon} and {other.horizon})")
     if other.n_members != self.n_members:
@@ -806,13 +822,14 @@ class _StoreSeries:
     self.energy = None if store.energy is None else []
     self.variogram, self.raw_variogram = ([], []) if store.variogram is not None else (None, None)
     self.tails, self.raw_tails = ([], []) if store.tails is not None else (None, None)
+    self.regions, self.raw_regions = ([], []) if store.regions is not None else (None, None)
     self.members = [] if keep_members else None
 
   def score_lead(self, truth=None, *, want_fields: bool = False, after_score=None, clim_fields=None, n_samples=None,
                  source_truth=None) -> None:
     """Scores the store as it stands and appends to every series: the scores (the events ride with them), the order
     statistics and their quantile fields, the climatology scores, the energy and variogram scores, the tail scores, the
-    members -- in that order on the device.  `truth`,
+    region scores, the members -- in that order on the device.  `truth`,
     `want_fields`: as `ScoredStore.score`; `after_score()`: what the caller downloads between the scores and the rest;
     `clim_fields`, or `n_samples` and `source_truth`: as `ScoredStore.score_climatology`.  A new scorer adds its step here."""
     raw, ev = self.store.score(truth, want_fields=want_fields)   # (the events: on the truth already on the device)
@@ -838,6 +855,9 @@ class _StoreSeries:
     if self.tails is not None:
       self.raw_tails.append(self.store.score_tails(None))   # (the truth is on the device already)
       self.tails.append(self.raw_tails[-1].scaled(self.scale))
+    if self.regions is not None:
+      self.raw_regions.append(self.store.score_regions(None))   # (the truth is on the device already)
+      self.regions.append(self.raw_regions[-1].scaled(self.scale))
     if self.members is not None:
       self.members.append([self.store.handle.ens_download_member(m) for m in range(self.store.n_members)])
 
@@ -845,7 +865,8 @@ class _StoreSeries:
     return DerivedRolloutResult(self.scores, self.raw, self.events, self.members, self.template, order=self.order,
                                 order_normalized=self.raw_order, quantiles=self.quantiles, climatology=self.clim,
                                 climatology_normalized=self.raw_clim, energy=self.energy, variogram=self.variogram,
-                                variogram_normalized=self.raw_variogram, tails=self.tails, tails_normalized=self.raw_tails)
+                                variogram_normalized=self.raw_variogram, tails=self.tails, tails_normalized=self.raw_tails,
+                                regions=self.regions, regions_normalized=self.raw_regions)
 
 
 class _WindowEntry:
@@ -876,7 +897,8 @@ class _WindowEntry:
     s = self.series
     return WindowRolloutResult(self.leads, self.spec.steps, s.scores, s.raw, s.events, s.order, s.members, s.template,
                                order_normalized=s.raw_order, energy=s.energy, variogram=s.variogram,
-                               variogram_normalized=s.raw_variogram, tails=s.tails, tails_normalized=s.raw_tails)
+                               variogram_normalized=s.raw_variogram, tails=s.tails, tails_normalized=s.raw_tails,
+                               regions=s.regions, regions_normalized=s.raw_regions)
 
 
 class _EnsembleRun:
@@ -957,7 +979,7 @@ class EnsembleRollout:
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
           keep_members: bool = False, events=None, derived=None, order=None,
           keep_quantiles: bool = False, climatology=None, windows=None, energy=None,
-          variogram=None, tails=None) -> EnsembleRolloutResult:
+          variogram=None, tails=None, regions=None) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -1012,6 +1034,13 @@ class EnsembleRollout:
     (`verification.TailScores` in physical units, `TailScores.scaled`), `tails_normalized` as the device returned them, and
     the same on the results of the named entries.  The thresholds reach the members' units by the path of the thresholds of
     `events`.  Without `tails` nothing changes.
+    `regions`: a `verification.RegionSpec` (named masks over the grid nodes, overlapping or not) for the main store, or a
+    mapping {None: spec, name: spec, ...} whose other keys name entries of `derived` / `windows` (an unknown key is a
+    ValueError; every store lives on the same grid nodes).  Per lead time, after the tails, ONE pass over the nodes that belong
+    to any region forms the sums of `scores` for every region (`gc_ens_region_score`, on the truth already there):
+    `EnsembleRolloutResult.regions` (`verification.RegionScores` in physical units, `regions[k][name]` an `EnsembleScores`),
+    `regions_normalized` as the device returned them, and the same on the results of the named entries.  Without `regions`
+    nothing changes.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -1048,8 +1077,14 @@ class EnsembleRollout:
       known = set(derived or {}) | set(windows or {})
       if set(tails) - known - {None}:
         raise ValueError(f"tails: {sorted(set(tails) - known - {None})} name no entry of `derived` or `windows` ({sorted(known)})")
+    if regions is not None:
+      regions = dict(regions) if isinstance(regions, Mapping) else {None: regions}
+      known = set(derived or {}) | set(windows or {})
+      if set(regions) - known - {None}:
+        raise ValueError(f"regions: {sorted(set(regions) - known - {None})} name no entry of `derived` or `windows` ({sorted(known)})")
     run = self._setup(inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields,
-                      keep_members, events, derived, order, keep_quantiles, climatology, windows, energy, variogram, tails)
+                      keep_members, events, derived, order, keep_quantiles, climatology, windows, energy, variogram, tails,
+                      regions)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -1065,11 +1100,12 @@ class EnsembleRollout:
                                  climatology=main.clim, climatology_normalized=main.raw_clim,
                                  windows=None if windows is None else {k: v.result() for k, v in run.windows.items()},
                                  energy=main.energy, variogram=main.variogram, variogram_normalized=main.raw_variogram,
-                                 tails=main.tails, tails_normalized=main.raw_tails)
+                                 tails=main.tails, tails_normalized=main.raw_tails, regions=main.regions,
+                                 regions_normalized=main.raw_regions)
 
   def _setup(self, inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields, keep_members,
              events, derived, order=None, keep_quantiles=False, climatology=None, windows=None, energy=None,
-             variogram=None, tails=None) -> "_EnsembleRun":
+             variogram=None, tails=None, regions=None) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views."""
     run = _EnsembleRun()
     context = isel_time(inputs, slice(-context_steps, None))
@@ -1118,6 +1154,11 @@ class EnsembleRollout:
       spec = (tails or {}).get(name)
       return {} if spec is None else {"tails": spec, "tail_thresholds": packed(spec, template, s, l)}
 
+    def region_args(name):
+      """`regions=` / `region_bits=` of the store `name` (None: the main store): every store has the grid nodes of `template0`."""
+      spec = (regions or {}).get(name)
+      return {} if spec is None else {"regions": spec, "region_bits": spec.node_bits(template0)}
+
     weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
     wq = None
     if (events is not None or any(dev is not None for _, dev in entries.values())
@@ -1137,7 +1178,8 @@ class EnsembleRollout:
     main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
                                     thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
                                     set_per_score=specs is not None and len(specs) > 1, order=order, climatology=clim_handle,
-                                    energy=eplan(template0), variogram=vplan, **tail_args(None, template0, scale, loc))
+                                    energy=eplan(template0), variogram=vplan, **tail_args(None, template0, scale, loc),
+                                    **region_args(None))
     run.main = _StoreSeries(main, scale, template0, keep_members=keep_members, keep_quantiles=keep_quantiles)
     main.reserve()
     if spectra:
@@ -1180,7 +1222,8 @@ class EnsembleRollout:
                                        plan=dplan, source=native, order=order, energy=eplan(dtemplate), variogram=vplan,
                                        climatology=None if clim_handle is None
                                        else den.climatology_handle(len(dplan["op"]), view=True),
-                                       climatology_source=clim_handle, **tail_args(name, dtemplate, dscale, dloc))
+                                       climatology_source=clim_handle, **tail_args(name, dtemplate, dscale, dloc),
+                                       **region_args(name))
       run.views[name] = _StoreSeries(store, dscale, dtemplate, keep_members=keep_members, keep_quantiles=keep_quantiles)
     for store in (v.store for v in run.views.values()):
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
@@ -1199,7 +1242,7 @@ class EnsembleRollout:
       store = verification.ScoredStore(den.window_handle(len(wscale), name), M, weights, events=wev,
                                        thresholds=None if wev is None else packed(wev, stemplate, wscale, wloc), weight_q=wq,
                                        order=order, energy=eplan(stemplate), variogram=vplan,
-                                       **tail_args(name, stemplate, wscale, wloc))
+                                       **tail_args(name, stemplate, wscale, wloc), **region_args(name))
       run.windows[name] = _WindowEntry(wspec, _StoreSeries(store, wscale, stemplate, keep_members=keep_members), source, horizon)
       run.windows[name].start()
     return run

@@ -45,6 +45,10 @@ Tail skill (`gc_ens_tail_score`): the threshold-weighted C
 chaining form of Allen et al. (2023) -- the plain CRPS of members and truth clamped at a threshold from one side.  The
 thresholds and directions are an `EventSpec`; the device sorts the members of a point once and hands back four raw sums per
 (threshold, batch, channel).  `TailScores` keeps them raw and derives the fair and the ensemble twCRPS.
+
+Regions (`gc_ens_region_score`): the sums of `EnsembleScores` per named set of grid nodes -- tropics,
+extratropics, land, sea, boxes -- every region from one pass over the nodes that belong to any.  `RegionSpec` holds the masks
+and builds boxes from bounds; `RegionScores[name]` is the region's `EnsembleScores`.
 """
 from __future__ import annotations
 
@@ -868,6 +872,144 @@ class TailScores:
 
 
 # ---------------------------------------------------------------------------------------------
+# regions: the ensemble scores per set of grid nodes, every region from one pass (gc_ens_region_*)
+# ---------------------------------------------------------------------------------------------
+class RegionSpec:
+  """Named regions of the grid: an ordered {name: mask}, at most 32.  A mask is boolean, [lat, lon] or [G] with
+  node = lat_i * n_lon + lon_j; regions may overlap, and a node in no mask is never read by the device.  `masks` exposes the
+  plain arrays, so a caller can combine them with a land-sea mask before building another spec."""
+
+  MAX_REGIONS = 32
+
+  def __init__(self, regions: Mapping[str, np.ndarray]):
+    self.masks: Dict[str, np.ndarray] = {}
+    for name, mask in regions.items():
+      m = np.asarray(mask)
+      if m.dtype != np.bool_ or m.ndim not in (1, 2):
+        raise ValueError(f"region {name!r}: a mask is a boolean [lat, lon] or [G] array, got {m.dtype} {m.shape}")
+      self.masks[name] = m
+    if not 1 <= len(self.masks) <= self.MAX_REGIONS:
+      raise ValueError(f"a RegionSpec holds 1..{self.MAX_REGIONS} regions, got {len(self.masks)}")
+    if len({m.size for m in self.masks.values()}) != 1:
+      raise ValueError("the masks cover grids of different sizes")
+
+  @property
+  def names(self) -> Tuple[str, ...]:
+    return tuple(self.masks)
+
+  @property
+  def n_regions(self) -> int:
+    return len(self.masks)
+
+  @classmethod
+  def from_bounds(cls, template, bounds: Mapping[str, Mapping[str, Tuple[float, float]]]) -> "RegionSpec":
+    """Latitude-longitude boxes on the template's own `lat` / `lon` coordinates: {name: dict(lat=(lat0, lat1), lon=(lon0,
+    lon1))}, either key optional (absent: all of them).  Bounds are inclusive.  Longitudes are taken modulo 360; a box
+    wraps through 0 degrees when lon0 > lon1 after that (`lon=(-12.5, 42.5)` is 347.5 .. 360 and 0 .. 42.5); a span of 360
+    degrees or more is the whole circle."""
+    coords = datasets.as_dataset(template).coords
+    if "lat" not in coords or "lon" not in coords:
+      raise ValueError("template must have 'lat' and 'lon' coordinates")
+    lat = np.asarray(coords["lat"], dtype=np.float64)
+    lon = np.mod(np.asarray(coords["lon"], dtype=np.float64), 360.0)
+    masks = {}
+    for name, box in bounds.items():
+      if set(box) - {"lat", "lon"}:
+        raise ValueError(f"region {name!r}: bounds are given by 'lat' and 'lon', got {sorted(box)}")
+      in_lat = np.ones(lat.shape, bool)
+      if box.get("lat") is not None:
+        lat0, lat1 = (float(v) for v in box["lat"])
+        if lat0 > lat1:
+          raise ValueError(f"region {name!r}: lat bounds must be ascending, got {(lat0, lat1)}")
+        in_lat = (lat >= lat0) & (lat <= lat1)
+      in_lon = np.ones(lon.shape, bool)
+      if box.get("lon") is not None:
+        lon0, lon1 = (float(v) for v in box["lon"])
+        if lon1 - lon0 < 360.0:
+          lon0, lon1 = lon0 % 360.0, lon1 % 360.0
+          in_lon = (lon >= lon0) & (lon <= lon1) if lon0 <= lon1 else (lon >= lon0) | (lon <= lon1)
+      masks[name] = in_lat[:, None] & in_lon[None, :]
+    return cls(masks)
+
+  def node_bits(self, template) -> np.ndarray:
+    """[G] uint32 for `NativeDenoiser.ens_region_set`: bit r set = the node belongs to the r-th region.  The masks must fit
+    the template's grid."""
+    sizes = datasets.as_dataset(template).sizes
+    if "lat" not in sizes or "lon" not in sizes:
+      raise ValueError("template must have 'lat' and 'lon' dimensions")
+    n_lat, n_lon = int(sizes["lat"]), int(sizes["lon"])
+    bits = np.zeros(n_lat * n_lon, np.uint32)
+    for r, (name, m) in enumerate(self.masks.items()):
+      if m.shape not in ((n_lat, n_lon), (n_lat * n_lon,)):
+        raise ValueError(f"region {name!r}: mask {m.shape} does not fit the {n_lat} x {n_lon} grid")
+      bits |= m.reshape(-1).astype(np.uint32) << np.uint32(r)
+    return bits
+
+
+class RegionScores:
+  """The results of `gc_ens_region_score`: per region r the raw sums [R, B, c_out, 6] float64, rank histogram [R, B, c_out,
+  M + 1] uint64 and skipped points `invalid` [R] of `EnsembleScores`, restricted to the region's nodes.  `scores[name]` is the
+  region's `EnsembleScores` (`.crps`, `.rmse`, `.spread_skill_ratio`, `.rank_histogram`, ...: no formula of its own); a region
+  in which nothing counted has NaN scores."""
+
+  def __init__(self, names: Sequence[str], sums, hist, n_members: int, invalid=None):
+    self.names = tuple(names)
+    self.sums = np.asarray(sums, dtype=np.float64)
+    self.rank_histogram = np.asarray(hist, dtype=np.uint64)
+    self.n_members = int(n_members)
+    R = len(self.names)
+    if len(set(self.names)) != R:
+      raise ValueError("region names must be distinct")
+    if self.sums.ndim != 4 or self.sums.shape[0] != R or self.sums.shape[-1] != 6:
+      raise ValueError(f"sums must be [{R}, batch, channels, 6], got {self.sums.shape}")
+    if self.rank_histogram.shape != self.sums.shape[:3] + (self.n_members + 1,):
+      raise ValueError(f"hist must be {self.sums.shape[:3] + (self.n_members + 1,)}, got {self.rank_histogram.shape}")
+    self.invalid = np.zeros(R, np.uint64) if invalid is None else np.asarray(invalid, dtype=np.uint64).reshape(R)
+
+  def __getitem__(self, name: str) -> EnsembleScores:
+    r = self.names.index(name) if name in self.names else None
+    if r is None:
+      raise KeyError(name)
+    return EnsembleScores(self.sums[r], self.rank_histogram[r], self.n_members)
+
+  def __len__(self) -> int:
+    return len(self.names)
+
+  def __iter__(self):
+    return iter(self.names)
+
+  def items(self):
+    return [(name, self[name]) for name in self.names]
+
+  def scaled(self, channel_scale) -> "RegionScores":
+    """`EnsembleScores.scaled` of every region."""
+    parts = [self[name].scaled(channel_scale) for name in self.names]
+    return RegionScores(self.names, np.stack([p.sums for p in parts]), np.stack([p.rank_histogram for p in parts]),
+                        self.n_members, self.invalid)
+
+  @staticmethod
+  def merge(parts: Sequence["RegionScores"]) -> "RegionScores":
+    """Scores over the union of what the parts covered (other dates): raw sums and counts add, region by region."""
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    for p in parts[1:]:
+      if p.names != first.names or p.n_members != first.n_members or p.sums.shape != first.sums.shape:
+        raise ValueError("merge: the parts differ in region names, members or shape")
+    sums, hist, invalid = first.sums.copy(), first.rank_histogram.copy(), first.invalid.copy()
+    for p in parts[1:]:
+      sums += p.sums
+      hist += p.rank_histogram
+      invalid += p.invalid
+    return RegionScores(first.names, sums, hist, first.n_members, invalid)
+
+  def per_variable(self, template) -> Dict[str, Dict[str, Dict[str, np.ndarray]]]:
+    """{region: `EnsembleScores.per_variable(template)`}."""
+    return {name: self[name].per_variable(template) for name in self.names}
+
+
+# ---------------------------------------------------------------------------------------------
 # derived and pooled fields: wind speed, neighbourhood maxima, area means (gc_ens_derive_*)
 # ---------------------------------------------------------------------------------------------
 _KM_PER_DEGREE = 111.195                                   # one degree of a great circle on the mean Earth radius 6371 km
@@ -1390,8 +1532,9 @@ class ScoredStore:
   same graph, batch and c_out (`Denoiser.climatology_handle`) whose member store takes the K climatological samples
   `score_climatology` scores the members against -- on a derived view together with `climatology_source`, the handle whose
   store holds the samples the view's plan is applied to, and optionally `tails`: an `EventSpec` read as tails (direction
-  > 0: the upper tail) with its packed `tail_thresholds` in the members' units, for `score_tails`.  `EnsembleSampler` and `EnsembleRollout` use one for the main
-  store and one per derived view.
+  > 0: the upper tail) with its packed `tail_thresholds` in the members' units, for `score_tails`, and optionally `regions`: a
+  `RegionSpec` with `region_bits` = `regions.node_bits(template)`, for `score_regions`.  `EnsembleSampler` and `EnsembleRollout`
+  use one for the main store and one per derived view.
 
   `set_per_score`: the plan and the thresholds are not set once by `setup` but by every `score` -- two stores that share
   a handle, or thresholds that change from call to call (assign `thresholds` before the call)."""
@@ -1399,7 +1542,10 @@ class ScoredStore:
   def __init__(self, handle, n_members: int, node_weight=None, *, events: Optional["EventSpec"] = None, thresholds=None,
                weight_q: Optional[Tuple[np.ndarray, float]] = None, plan=None, source=None, set_per_score: bool = False,
                order=None, climatology=None, climatology_source=None, energy=None, variogram=None,
-               tails: Optional["EventSpec"] = None, tail_thresholds=None):
+               tails: Optional["EventSpec"] = None, tail_thresholds=None, regions: Optional["RegionSpec"] = None,
+               region_bits=None):
+    if regions is not None and region_bits is None:
+      raise ValueError("regions need their node bits (RegionSpec.node_bits)")
     if climatology_source is not None and (climatology is None or plan is None):
       raise ValueError("a climatology source goes with a climatology handle and a derive plan")
     if events is not None and weight_q is None:
@@ -1413,6 +1559,7 @@ class ScoredStore:
     self.climatology, self.climatology_source = climatology, climatology_source
     self.energy, self.variogram = energy, variogram          # the plans (`EnergySpec.plan`, `VariogramSpec.plan`) or None
     self.tails, self.tail_thresholds = tails, tail_thresholds
+    self.regions, self.region_bits = regions, region_bits
     self._clim_reserved = 0                      # K of the store this object reserved on the climatology handle
     self._clim_plan_set = False                  # the plan has been handed to the climatology handle (a derived view)
 
@@ -1446,15 +1593,20 @@ class ScoredStore:
     if self.tails is not None:
       self.handle.ens_tail_set(self.tail_thresholds, self.tails.directions)
 
+  def _set_regions(self) -> None:
+    if self.regions is not None:
+      self.handle.ens_region_set(self.region_bits, self.regions.n_regions)
+
   def configure(self) -> None:
-    """The plan, the thresholds, the probabilities, the multivariate plans and the tails: all survive `ens_reserve` and
-    every score."""
+    """The plan, the thresholds, the probabilities, the multivariate plans, the tails and the regions: all survive
+    `ens_reserve` and every score."""
     self._set_plan()
     self._set_events()
     self._set_order()
     self._set_energy()
     self._set_variogram()
     self._set_tails()
+    self._set_regions()
 
   def setup(self) -> None:
     self.reserve()
@@ -1510,6 +1662,16 @@ class ScoredStore:
       self._set_tails()
     sums, counts, invalid = self.handle.ens_tail_score(truth)
     return TailScores(sums, counts, self.n_members, self.tails.directions, invalid)
+
+  def score_regions(self, truth=None) -> Optional["RegionScores"]:
+    """The raw sums of `score` per region of `regions` (None without it), from one pass over the nodes of all regions, in the
+    store's own units; `truth` None: the truth already on the device.  On a derived view call it after `score`."""
+    if self.regions is None:
+      return None
+    if self.set_per_score:
+      self._set_regions()
+    sums, hist, invalid = self.handle.ens_region_score(truth)
+    return RegionScores(self.regions.names, sums, hist, self.n_members, invalid)
 
   def _reserve_climatology(self, K: int) -> None:
     if K != self._clim_reserved:

@@ -816,6 +816,42 @@ int gc_ens_tail_score(gc_handle* h, const float* truth /* NULL = the truth uploa
                       uint64_t* invalid /* [T], NULL allowed */);
 
 /*
+ * Regional ensemble scores on the device: the sums of gc_ens_score for R regions of grid nodes --
+ * tropics, extratropics, land, sea, boxes -- from ONE scoring pass over the nodes that belong to any region
+ * (gencast-flax-nnx_amd/verification.py RegionSpec, RegionScores).  The reference project has no verification code; the
+ * yardstick is tests/verification_reference.py on each region's node subset (tests/region_reference.py).
+ * node_bits[g] is a uint32 per grid node: bit r set = node g belongs to region r (r < R <= 32).  Regions may overlap.  A node
+ * with node_bits == 0 belongs to nothing: it is not read, and it is counted in no invalid[r].  A region without a node is
+ * legal: its sums and counts are zero.
+ * Per region r, over the nodes with bit r set and with the node weights of gc_ens_set_node_weight, sums S0..S5, the rank
+ * histogram and the skipped points are exactly those of gc_ens_score (section 8c): the validity rule (y and all M members
+ * finite), the tie rule (a member equal to y is not below it), the ascending slot order of the mean, the second pass for s2
+ * and rounded double operations without contraction carry over.
+ *   gc_ens_region_set    builds the plan on the host.  An ATOM is a distinct non-zero value of node_bits; the listed nodes
+ *                        are grouped by atom (ascending atom value, ascending node index inside an atom) and cut into node
+ *                        ranges that each lie inside one atom: an atom of n_a nodes gets ceil(n_a / per) workgroups, per as
+ *                        gc_ens_score would cut the listed nodes.  Needs gc_set_graph only; survives gc_ens_reserve and every
+ *                        score; a repeated call replaces ("device_allocations" stays flat); released by gc_destroy.
+ *                        GC_ERR_UNSUPPORTED: R outside 1..32, or more than 256 atoms (the previous plan stays in force).
+ *                        GC_ERR_INVALID_ARGUMENT: a null pointer, or a bit at or above R.  GC_ERR_STATE: before gc_set_graph.
+ *   gc_ens_region_score  truth: host [G, B, c_out], uploaded and kept, or NULL = the truth uploaded last (the buffer
+ *                        gc_ens_score uses).  sums is required, hist and invalid may be NULL.  Two launches: the pass of
+ *                        gc_ens_score over the listed nodes, whose per-workgroup partials belong to one atom each, and a
+ *                        finish over (column tile, region) that adds the partials of the atoms with bit r in ascending
+ *                        workgroup order.  The cost is one scoring pass over the listed nodes, whatever R is.  Synchronous.
+ *                        GC_ERR_STATE: no plan, no member store, a slot not pushed since gc_ens_reserve, no node weights,
+ *                        no truth.
+ * No atomics on floats and a fixed order of every sum: the same call twice returns identical bytes.  Nothing else on the
+ * handle is touched.  Counters: "ens_region_calls", "ens_region_device_us" (HIP-event time of the last call's launches),
+ * "ens_region_invalid_points" (of the last call, summed over the regions).
+ */
+int gc_ens_region_set(gc_handle* h, int32_t n_regions /* R, 1..32 */,
+                      const uint32_t* node_bits /* [G]: bit r set = node g belongs to region r */);
+int gc_ens_region_score(gc_handle* h, const float* truth /* NULL = the truth uploaded last */,
+                        double* sums /* [R][6][B][c_out] */, uint64_t* hist /* [R][B][c_out][M + 1], NULL allowed */,
+                        uint64_t* invalid /* [R], NULL allowed */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
