@@ -173,14 +173,17 @@ class EnsembleSampler:
     return self._run(inputs, targets, forcings, num_members, score_fields, spectral=True, lmax=lmax)
 
   def _run(self, inputs, targets_template, forcings, num_members: int, score_fields: Optional[bool], spectral: bool = False,
-           lmax: Optional[int] = None, events=None, derived=None, order=None, climatology=None, multivariate=None,
-           tails=None, regions=None):
+           lmax: Optional[int] = None, **asked):
     """`score_fields` None: members come back as Datasets (`__call__`) or, with `spectral`, only their spectra are
     formed, or, with `events` (an EventSpec), only their event tables, or, with `order` (probabilities, want fields), only
     their order statistics, or, with `climatology` (K Datasets), only their skill against it, or, with `multivariate` (an
     EnergySpec or None, a VariogramSpec or None), only their energy and variogram scores, or, with `tails` (an EventSpec), only
-    their threshold-weighted CRPS sums, or, with `regions` (a RegionSpec), only their sums per region; else they are scored
-    (`scores`), with `spectral` both."""
+    their threshold-weighted CRPS sums, or, with `regions` (a RegionSpec), only their sums per region, or, with `derived` (a
+    DerivedSpec, an EventSpec or None), only the scores of the derived fields; else they are scored (`scores`), with
+    `spectral` both.  `asked`: at most one of these keywords (one that is None was not asked for)."""
+    asked = {what: arg for what, arg in asked.items() if arg is not None}
+    events, order, climatology, tails, regions = (asked.get(k) for k in ("events", "order", "climatology", "tails", "regions"))
+    (dspec, dev), (energy, variogram) = asked.get("derived", (None, None)), asked.get("multivariate", (None, None))
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
     cond, grid_shape, slots = self._denoiser.init_for(inputs, template, forcings)
@@ -208,23 +211,18 @@ class EnsembleSampler:
         lane.upload_cond_dev(ptr)                          # device-to-device, on the lane's own stream
     scoring = score_fields is not None
     main = None                                            # lane 0's member store, where anything is scored at all
-    if (scoring or spectral or events is not None or derived is not None or order is not None or climatology is not None or
-        multivariate is not None or tails is not None or regions is not None):
-      dspec, dev = derived if derived is not None else (None, None)
+    if scoring or spectral or asked:
       weights = None if spectral and not scoring else verification.node_weights(template)
       wq = None if events is None and dev is None else verification.quantize_node_weights(weights)
-      # (scored once: the thresholds are set by that call, after the members are in)
-      main = verification.ScoredStore(native, num_members,
-                                      weights if scoring or order is not None or climatology is not None or
-                                      multivariate is not None or tails is not None or regions is not None else None,
+      # (scored once: the thresholds are set by that call, after the members are in; events and derived fields alone need no
+      # node weights on the main store)
+      main = verification.ScoredStore(native, num_members, weights if scoring or asked.keys() - {"events", "derived"} else None,
                                       events=events, thresholds=None if events is None else events.packed(template), weight_q=wq,
                                       set_per_score=True, order=None if order is None else order[0],
                                       climatology=None if climatology is None
                                       else self._denoiser.climatology_handle(self._denoiser.dims.c_out),
-                                      energy=None if multivariate is None or multivariate[0] is None
-                                      else multivariate[0].plan(template),
-                                      variogram=None if multivariate is None or multivariate[1] is None
-                                      else multivariate[1].plan(template),
+                                      energy=None if energy is None else energy.plan(template),
+                                      variogram=None if variogram is None else variogram.plan(template),
                                       tails=tails, tail_thresholds=None if tails is None else tails.packed(template),
                                       regions=regions, region_bits=None if regions is None else regions.node_bits(template))
       main.setup()
@@ -244,8 +242,12 @@ class EnsembleSampler:
                                               targets_template, inputs, forcings)))
     if main is None:
       return out
-    truth = np.transpose(datasets.dataset_to_stacked(template, template.sizes), (1, 2, 0, 3)).reshape(shape)
-    if derived is not None:
+    pack =lambda ds: np.transpose(datasets.dataset_to_stacked(datasets.as_dataset(ds), template.sizes), (1, 2, 0, 3)).reshape(shape)
+    truth = pack(template)
+    as_given = lambda fields: [datasets.like_inputs(Denoiser.unpack_outputs(f, grid_shape, template), targets_template, inputs,
+                                                    forcings) for f in fields]
+
+    def derived_scores():
       plan = dspec.plan(template)
       view = verification.ScoredStore(self._denoiser.view_handle(len(plan["op"])), num_members, weights, events=dev,
                                       thresholds=None if dev is None else dev.packed(dspec.template(template)), weight_q=wq,
@@ -253,33 +255,25 @@ class EnsembleSampler:
       view.setup()
       scores, event_scores = view.score(truth)
       return scores if dev is None else (scores, event_scores)
-    if events is not None:
-      return main.score_events(truth)
-    if climatology is not None:
-      pack = lambda ds: np.transpose(datasets.dataset_to_stacked(datasets.as_dataset(ds), template.sizes),
-                                     (1, 2, 0, 3)).reshape(shape)
-      return main.score_climatology([pack(c) for c in climatology], truth)
-    if tails is not None:
-      return main.score_tails(truth)
-    if regions is not None:
-      return main.score_regions(truth)
-    if multivariate is not None:
+
+    def multivariate_scores():
       en = main.score_energy(truth)
       return en, main.score_variogram(truth if en is None else None)      # (the truth is on the device after the first)
-    if order is not None:
+
+    def order_scores():
       scores = main.score_order(truth)
-      if not order[1]:
-        return scores
-      given = (targets_template, inputs, forcings)
-      return scores, [datasets.like_inputs(Denoiser.unpack_outputs(f, grid_shape, template), *given)
-                      for f in main.quantile_fields()]
+      return (scores, as_given(main.quantile_fields())) if order[1] else scores
+
+    if asked:                                              # (what was asked for is scored alone)
+      return {"derived": derived_scores, "events": lambda: main.score_events(truth),
+              "climatology": lambda: main.score_climatology([pack(c) for c in climatology], truth),
+              "tails": lambda: main.score_tails(truth), "regions": lambda: main.score_regions(truth),
+              "multivariate": multivariate_scores, "order": order_scores}[next(iter(asked))]()
     if not scoring:
       return _spectra.EnsembleSpectra(native.ens_spectrum(truth), num_members)
     result = (main.score(truth, want_fields=score_fields)[0],)
     if score_fields:
-      given = (targets_template, inputs, forcings)
-      result += tuple(datasets.like_inputs(Denoiser.unpack_outputs(f, grid_shape, template), *given)
-                      for f in native.ens_download_fields())
+      result += tuple(as_given(native.ens_download_fields()))
     if spectral:
       result += (_spectra.EnsembleSpectra(native.ens_spectrum(None), num_members),)   # the truth is on the device already
     return result if len(result) > 1 else result[0]

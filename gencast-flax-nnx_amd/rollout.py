@@ -626,51 +626,49 @@ class _MemberNoise:
     return np.asarray(self._sampler.draw_noise(self._gen, shape, template), np.float32)
 
 
-# (attribute, score class, the word for it in an error message -- None: the raw twin of the row before it, or the scores
-# themselves: never checked on its own).  A new scorer adds its rows here AND its names to `_SeriesResult._optional`: a result
-# that was not given such a series keeps no instance attribute for it, so `vars(result)` of a run that does not use the scorer
-# is what it was before the scorer existed (tests/golden/rollout_call_sequence.json records it).  The rows up to
-# "climatology_normalized" predate that rule and are always set.
-_SERIES = (("scores", verification.EnsembleScores, None), ("scores_normalized", verification.EnsembleScores, None),
-           ("spectra", _spectra.EnsembleSpectra, "spectra"), ("spectra_normalized", _spectra.EnsembleSpectra, None),
-           ("events", verification.EventScores, "events"),
-           ("order", verification.OrderScores, "order statistics"), ("order_normalized", verification.OrderScores, None),
-           ("climatology", verification.ClimatologyScores, "climatology scores"),
-           ("climatology_normalized", verification.ClimatologyScores, None),
-           ("energy", verification.EnergyScores, "energy scores"),
-           ("variogram", verification.VariogramScores, "variogram scores"),
-           ("variogram_normalized", verification.VariogramScores, None),
-           ("tails", verification.TailScores, "tail scores"), ("tails_normalized", verification.TailScores, None),
-           ("regions", verification.RegionScores, "region scores"), ("regions_normalized", verification.RegionScores, None))
-
-
 class _SeriesResult:
-  """What the three results share: the rows of `_SERIES` a result carries (`_carries`), each a list with one entry per
-  lead time or None, and their merge."""
-  _carries: Sequence[str] = ()
+  """What the three results share: the series of the rows of `verification.SCORERS` that name the result's kind
+  (`_carried_as`), each a list with one entry per lead time or None, and their merge.  A result that was not given a series of
+  an `optional` row keeps no instance attribute for it (it reads as None), so `vars(result)` of a run that does not use the
+  scorer is what it was before the scorer existed (tests/golden/rollout_call_sequence.json records it)."""
+  _carried_as = "none"
   _kind = "results"                                       # (as the merge's error messages name the two operands)
-  # series that exist on an instance only when the run asked for them; the class holds their None (see `_SERIES`)
-  _optional = ("energy", "variogram", "variogram_normalized", "tails", "tails_normalized", "regions", "regions_normalized")
-  energy = variogram = variogram_normalized = tails = tails_normalized = regions = regions_normalized = None
 
-  def _set_series(self, **series) -> None:
-    """Copies the series into lists (the scores first) and checks that the others cover the lead times of the scores."""
-    for name, _, word in _SERIES:
-      if name in self._carries:
-        if series[name] is None and name in self._optional:
-          continue                                        # (the class's None stands)
-        setattr(self, name, None if series[name] is None else list(series[name]))
-        if word is not None and series[name] is not None and len(getattr(self, name)) != len(self.scores):
-          raise ValueError(f"scores and {word} must cover the same lead times")
+  @classmethod
+  def _rows(cls) -> List[verification.Scorer]:
+    return [row for row in verification.SCORERS if cls._carried_as in row.carried_by]
+
+  @classmethod
+  def _carries(cls) -> List[str]:
+    return [name for row in cls._rows() for name in row.series]
+
+  def __getattr__(self, name):
+    if any(row.optional and name in row.series for row in self._rows()):
+      return None
+    raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+  def _set_series(self, named, series) -> None:
+    """Copies the series into lists (the scores first) and checks that the others cover the lead times of the scores.
+    `named`: the constructor's own parameters by name; `series`: its other keywords, each a series the result carries."""
+    unknown = [name for name in series if name not in self._carries()]
+    if unknown:
+      raise TypeError(f"{type(self).__name__}() got an unexpected keyword argument {unknown[0]!r}")
+    for row in self._rows():
+      for name in row.series:
+        given = series.get(name, named.get(name))
+        if given is None and row.optional:
+          continue                                        # (it reads as None)
+        setattr(self, name, None if given is None else list(given))
+        if name == row.name and row.word is not None and given is not None and len(getattr(self, name)) != len(self.scores):
+          raise ValueError(f"scores and {row.word} must cover the same lead times")
 
   def _merged_series(self, other) -> Dict[str, Optional[list]]:
     """{attribute: the series of both results merged entry by entry (raw sums add), None where either has none}."""
-    rows = [row for row in _SERIES if row[0] in self._carries]
-    for name, _, word in rows:
-      if word is not None and (getattr(self, name) is None) != (getattr(other, name) is None):
-        raise ValueError(f"merge: only one of the two {self._kind} carries {word}")
-    both = lambda cls, a, b: None if a is None or b is None else [cls.merge([x, y]) for x, y in zip(a, b)]
-    return {name: both(cls, getattr(self, name), getattr(other, name)) for name, cls, _ in rows}
+    for row in self._rows():
+      if row.word is not None and (getattr(self, row.name) is None) != (getattr(other, row.name) is None):
+        raise ValueError(f"merge: only one of the two {self._kind} carries {row.word}")
+    both = lambda a, b: None if a is None or b is None else [type(x).merge([x, y]) for x, y in zip(a, b)]
+    return {name: both(getattr(self, name), getattr(other, name)) for name in self._carries()}
 
 
 def _merge_named(a, b, word: str, names: str):
@@ -697,18 +695,10 @@ class DerivedRolloutResult(_SeriesResult):
   also `tails[k]` / `tails_normalized[k]` (`verification.TailScores`, as `scores`).  With `run(regions={name: spec})` also
   `regions[k]` / `regions_normalized[k]` (`verification.RegionScores`, as `scores`)."""
 
-  _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "climatology", "climatology_normalized",
-              "energy", "variogram", "variogram_normalized", "tails", "tails_normalized", "regions", "regions_normalized")
-  _kind = "derived results"
+  _carried_as, _kind = "derived", "derived results"
 
-  def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, order=None,
-               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, energy=None,
-               variogram=None, variogram_normalized=None, tails=None, tails_normalized=None, regions=None,
-               regions_normalized=None):
-    self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
-                     order_normalized=order_normalized, climatology=climatology, climatology_normalized=climatology_normalized,
-                     energy=energy, variogram=variogram, variogram_normalized=variogram_normalized, tails=tails,
-                     tails_normalized=tails_normalized, regions=regions, regions_normalized=regions_normalized)
+  def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, quantiles=None, **series):
+    self._set_series(locals(), series)
     self.members, self.template, self.quantiles = members, template, quantiles
 
   def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
@@ -728,18 +718,12 @@ class WindowRolloutResult(_SeriesResult):
   `run(tails={name: spec})` also `tails[i]` / `tails_normalized[i]` (`verification.TailScores`, as `scores`).  With
   `run(regions={name: spec})` also `regions[i]` / `regions_normalized[i]` (`verification.RegionScores`, as `scores`)."""
 
-  _carries = ("scores", "scores_normalized", "events", "order", "order_normalized", "energy", "variogram",
-              "variogram_normalized", "tails", "tails_normalized", "regions", "regions_normalized")
-  _kind = "window results"
+  _carried_as, _kind = "window", "window results"
 
-  def __init__(self, leads, steps: int, scores, scores_normalized, events=None, order=None, members=None, template=None, *,
-               order_normalized=None, energy=None, variogram=None, variogram_normalized=None, tails=None,
-               tails_normalized=None, regions=None, regions_normalized=None):
+  def __init__(self, leads, steps: int, scores, scores_normalized, events=None, order=None, members=None, template=None,
+               **series):
     self.leads, self.steps = [int(k) for k in leads], int(steps)
-    self._set_series(scores=scores, scores_normalized=scores_normalized, events=events, order=order,
-                     order_normalized=order_normalized, energy=energy, variogram=variogram,
-                     variogram_normalized=variogram_normalized, tails=tails, tails_normalized=tails_normalized,
-                     regions=regions, regions_normalized=regions_normalized)
+    self._set_series(locals(), series)
     if len(self.scores) != len(self.leads) or len(self.scores_normalized) != len(self.leads):
       raise ValueError("a window result needs one score per window lead time")
     self.members, self.template = members, template
@@ -772,18 +756,11 @@ class EnsembleRolloutResult(_SeriesResult):
   `verification.RegionScores` per lead time (as `scores` / `scores_normalized`) -- the scores of every region of
   `run(regions=...)`, `regions[k][name]` an `EnsembleScores` -- or None."""
 
-  _carries = tuple(row[0] for row in _SERIES)
+  _carried_as = "ensemble"
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
-               scores_normalized=None, spectra_normalized=None, events=None, derived=None, order=None,
-               order_normalized=None, quantiles=None, climatology=None, climatology_normalized=None, windows=None,
-               energy=None, variogram=None, variogram_normalized=None, tails=None, tails_normalized=None, regions=None,
-               regions_normalized=None):
-    self._set_series(scores=scores, scores_normalized=scores_normalized, spectra=spectra, spectra_normalized=spectra_normalized,
-                     events=events, order=order, order_normalized=order_normalized, climatology=climatology,
-                     climatology_normalized=climatology_normalized, energy=energy, variogram=variogram,
-                     variogram_normalized=variogram_normalized, tails=tails, tails_normalized=tails_normalized,
-                     regions=regions, regions_normalized=regions_normalized)
+               derived=None, quantiles=None, windows=None, **series):
+    self._set_series(locals(), series)
     self.derived = None if derived is None else dict(derived)
     self.windows = None if windows is None else dict(windows)
     self.mean, self.variance, self.members, self.quantiles = mean, variance, members, quantiles
@@ -814,59 +791,60 @@ class _StoreSeries:
 
   def __init__(self, store, scale, template, *, keep_members: bool = False, keep_quantiles: bool = False):
     self.store, self.scale, self.template = store, scale, template
-    self.scores, self.raw = [], []
-    self.events = None if store.events is None else []
-    self.order, self.raw_order = ([], []) if store.order is not None else (None, None)
+    # {series, by the name a result has it under: its list} of the scores and of every row the store has switched on
+    self.lists = {name: [] for row in verification.SCORERS
+                  if row.name == "scores" or getattr(store, row.name, None) is not None for name in row.series}
     self.quantiles = [] if store.order is not None and keep_quantiles else None
-    self.clim, self.raw_clim = ([], []) if store.climatology is not None else (None, None)
-    self.energy = None if store.energy is None else []
-    self.variogram, self.raw_variogram = ([], []) if store.variogram is not None else (None, None)
-    self.tails, self.raw_tails = ([], []) if store.tails is not None else (None, None)
-    self.regions, self.raw_regions = ([], []) if store.regions is not None else (None, None)
     self.members = [] if keep_members else None
+
+  def __getattr__(self, name):
+    """`series.tails`, `series.raw_tails`, `series.raw`, `series.clim`, ...: a list of `lists` by its short name (None: the
+    store does not have the scorer switched on)."""
+    short = {"raw": "raw_scores", "clim": "climatology", "raw_clim": "raw_climatology"}.get(name, name)
+    key = short[4:] + "_normalized" if short.startswith("raw_") else short
+    if name != "lists" and any(key in row.series for row in verification.SCORERS):
+      return self.lists.get(key)
+    raise AttributeError(name)
 
   def score_lead(self, truth=None, *, want_fields: bool = False, after_score=None, clim_fields=None, n_samples=None,
                  source_truth=None) -> None:
-    """Scores the store as it stands and appends to every series: the scores (the events ride with them), the order
-    statistics and their quantile fields, the climatology scores, the energy and variogram scores, the tail scores, the
-    region scores, the members -- in that order on the device.  `truth`,
-    `want_fields`: as `ScoredStore.score`; `after_score()`: what the caller downloads between the scores and the rest;
-    `clim_fields`, or `n_samples` and `source_truth`: as `ScoredStore.score_climatology`.  A new scorer adds its step here."""
+    """Scores the store as it stands and appends to every series: the scores (the events ride with them), then, after
+    `after_score()`, every other row of `verification.SCORERS` the store has switched on -- the order statistics and their
+    quantile fields, the climatology scores, the energy and variogram scores, the tail scores, the region scores -- then the
+    members, in that order on the device.  `truth`, `want_fields`: as `ScoredStore.score`; `after_score()`: what the caller
+    downloads between the scores and the rest; `clim_fields`, or `n_samples` and `source_truth`: as
+    `ScoredStore.score_climatology`."""
+    lists = self.lists
     raw, ev = self.store.score(truth, want_fields=want_fields)   # (the events: on the truth already on the device)
-    self.raw.append(raw)
-    self.scores.append(raw.scaled(self.scale))
+    lists["scores_normalized"].append(raw)
+    lists["scores"].append(raw.scaled(self.scale))
     if ev is not None:
-      self.events.append(ev)
+      lists["events"].append(ev)
     if after_score is not None:
       after_score()
-    if self.order is not None:
-      self.raw_order.append(self.store.score_order(None))  # (the truth is on the device already)
-      self.order.append(self.raw_order[-1].scaled(self.scale))
-      if self.quantiles is not None:
+    for row in verification.SCORERS:
+      if row.name in ("scores", "events") or row.name not in lists:
+        continue
+      if row.name == "climatology":
+        raw = self.store.score_climatology(clim_fields, None, n_samples=n_samples, source_truth=source_truth)
+      else:
+        raw = self.store._score(row, None)                  # (the truth is on the device already)  pylint: disable=protected-access
+      if row.scaled:
+        lists[row.name + "_normalized"].append(raw)
+        raw = raw.scaled(self.scale)
+      lists[row.name].append(raw)                           # (without `scaled`: in the store's own units)
+      if row.name == "order" and self.quantiles is not None:
         self.quantiles.append(self.store.quantile_fields())
-    if self.clim is not None:
-      self.raw_clim.append(self.store.score_climatology(clim_fields, None, n_samples=n_samples, source_truth=source_truth))
-      self.clim.append(self.raw_clim[-1].scaled(self.scale))
-    if self.energy is not None:
-      self.energy.append(self.store.score_energy(None))    # (in the store's own units: there is no `scaled`)
-    if self.variogram is not None:
-      self.raw_variogram.append(self.store.score_variogram(None))
-      self.variogram.append(self.raw_variogram[-1].scaled(self.scale))
-    if self.tails is not None:
-      self.raw_tails.append(self.store.score_tails(None))   # (the truth is on the device already)
-      self.tails.append(self.raw_tails[-1].scaled(self.scale))
-    if self.regions is not None:
-      self.raw_regions.append(self.store.score_regions(None))   # (the truth is on the device already)
-      self.regions.append(self.raw_regions[-1].scaled(self.scale))
     if self.members is not None:
       self.members.append([self.store.handle.ens_download_member(m) for m in range(self.store.n_members)])
 
+  def carried(self, result) -> Dict[str, list]:
+    """The series of the store that a result of class `result` carries, as the keywords of its constructor."""
+    return {name: series for name, series in self.lists.items() if name in result._carries()}  # pylint: disable=protected-access
+
   def derived_result(self) -> DerivedRolloutResult:
-    return DerivedRolloutResult(self.scores, self.raw, self.events, self.members, self.template, order=self.order,
-                                order_normalized=self.raw_order, quantiles=self.quantiles, climatology=self.clim,
-                                climatology_normalized=self.raw_clim, energy=self.energy, variogram=self.variogram,
-                                variogram_normalized=self.raw_variogram, tails=self.tails, tails_normalized=self.raw_tails,
-                                regions=self.regions, regions_normalized=self.raw_regions)
+    return DerivedRolloutResult(members=self.members, template=self.template, quantiles=self.quantiles,
+                                **self.carried(DerivedRolloutResult))
 
 
 class _WindowEntry:
@@ -895,10 +873,8 @@ class _WindowEntry:
 
   def result(self) -> WindowRolloutResult:
     s = self.series
-    return WindowRolloutResult(self.leads, self.spec.steps, s.scores, s.raw, s.events, s.order, s.members, s.template,
-                               order_normalized=s.raw_order, energy=s.energy, variogram=s.variogram,
-                               variogram_normalized=s.raw_variogram, tails=s.tails, tails_normalized=s.raw_tails,
-                               regions=s.regions, regions_normalized=s.raw_regions)
+    return WindowRolloutResult(self.leads, self.spec.steps, members=s.members, template=s.template,
+                               **s.carried(WindowRolloutResult))
 
 
 class _EnsembleRun:
@@ -927,6 +903,17 @@ def _members_units(ds, shape, scale, loc, normalized: bool) -> np.ndarray:
 def _spec_entries(entries) -> Dict[str, tuple]:
   """The entries of `derived=` / `windows=` as {name: (spec, EventSpec or None)}."""
   return {name: tuple(entry) if isinstance(entry, (tuple, list)) else (entry, None) for name, entry in (entries or {}).items()}
+
+
+def _per_store(arg: str, given, known) -> Optional[dict]:
+  """An argument of `run` that is a spec for the main store, or {None: spec, name: spec, ...}, as that mapping (None stays
+  None); a name that is not among `known`, the entries of `derived` and `windows`, is a ValueError."""
+  if given is None:
+    return None
+  given = dict(given) if isinstance(given, Mapping) else {None: given}
+  if set(given) - known - {None}:
+    raise ValueError(f"{arg}: {sorted(set(given) - known - {None})} name no entry of `derived` or `windows` ({sorted(known)})")
+  return given
 
 
 class EnsembleRollout:
@@ -1072,19 +1059,12 @@ class EnsembleRollout:
         raise ValueError(f"energy: the groups {sorted(set(energy.names) - fitted)} name variables that no scored store has all of")
     if init_noise is not None and (len(init_noise) != M or any(len(z) < horizon for z in init_noise)):
       raise ValueError("init_noise must be [num_members][horizon] fields")
-    if tails is not None:
-      tails = dict(tails) if isinstance(tails, Mapping) else {None: tails}
-      known = set(derived or {}) | set(windows or {})
-      if set(tails) - known - {None}:
-        raise ValueError(f"tails: {sorted(set(tails) - known - {None})} name no entry of `derived` or `windows` ({sorted(known)})")
-    if regions is not None:
-      regions = dict(regions) if isinstance(regions, Mapping) else {None: regions}
-      known = set(derived or {}) | set(windows or {})
-      if set(regions) - known - {None}:
-        raise ValueError(f"regions: {sorted(set(regions) - known - {None})} name no entry of `derived` or `windows` ({sorted(known)})")
-    run = self._setup(inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields,
-                      keep_members, events, derived, order, keep_quantiles, climatology, windows, energy, variogram, tails,
-                      regions)
+    known = set(derived or {}) | set(windows or {})
+    per_store = {arg: _per_store(arg, spec, known) for arg, spec in (("tails", tails), ("regions", regions))}
+    run = self._setup(inputs, targets, forcings, horizon, M, context_steps=context_steps, init_noise=init_noise,
+                      spectra=spectra, lmax=lmax, fields=fields, keep_members=keep_members, events=events, derived=derived,
+                      order=order, keep_quantiles=keep_quantiles, climatology=climatology, windows=windows, energy=energy,
+                      variogram=variogram, per_store=per_store)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -1092,21 +1072,17 @@ class EnsembleRollout:
       self._score_lead(run, k, targets)
       self.last_lead_ms.append(1e3 * (_time.perf_counter() - t0))
     main = run.main
-    return EnsembleRolloutResult(main.scores, run.spectra, _on_time_axis(run.means, given, horizon) if fields else None,
-                                 _on_time_axis(run.variances, given, horizon) if fields else None, main.members, M,
-                                 scores_normalized=main.raw, spectra_normalized=run.raw_spectra, events=main.events,
+    return EnsembleRolloutResult(mean=_on_time_axis(run.means, given, horizon) if fields else None,
+                                 variance=_on_time_axis(run.variances, given, horizon) if fields else None,
+                                 members=main.members, n_members=M, quantiles=main.quantiles,
                                  derived=None if derived is None else {k: v.derived_result() for k, v in run.views.items()},
-                                 order=main.order, order_normalized=main.raw_order, quantiles=main.quantiles,
-                                 climatology=main.clim, climatology_normalized=main.raw_clim,
                                  windows=None if windows is None else {k: v.result() for k, v in run.windows.items()},
-                                 energy=main.energy, variogram=main.variogram, variogram_normalized=main.raw_variogram,
-                                 tails=main.tails, tails_normalized=main.raw_tails, regions=main.regions,
-                                 regions_normalized=main.raw_regions)
+                                 spectra=run.spectra, spectra_normalized=run.raw_spectra, **main.carried(EnsembleRolloutResult))
 
-  def _setup(self, inputs, targets, forcings, horizon, M, context_steps, init_noise, spectra, lmax, fields, keep_members,
-             events, derived, order=None, keep_quantiles=False, climatology=None, windows=None, energy=None,
-             variogram=None, tails=None, regions=None) -> "_EnsembleRun":
-    """Everything `run` does before the first sample: lanes, context store, the main store and the derived views."""
+  def _setup(self, inputs, targets, forcings, horizon, M, *, context_steps, init_noise, spectra, lmax, fields, keep_members,
+             events, derived, order, keep_quantiles, climatology, windows, energy, variogram, per_store) -> "_EnsembleRun":
+    """Everything `run` does before the first sample: lanes, context store, the main store and the derived views.  The
+    keywords are `run`'s own; `per_store`: {argument given per store ("tails", "regions"): {store name: spec} or None}."""
     run = _EnsembleRun()
     context = isel_time(inputs, slice(-context_steps, None))
     template0 = isel_time(targets, slice(0, 1)).map(np.zeros_like)
@@ -1149,15 +1125,15 @@ class EnsembleRollout:
       part = None if energy is None else energy.restricted(template)
       return None if part is None else part.plan(template)
 
-    def tail_args(name, template, s, l):
-      """`tails=` / `tail_thresholds=` of the store `name` (None: the main store): its spec, thresholds in the members' units."""
-      spec = (tails or {}).get(name)
-      return {} if spec is None else {"tails": spec, "tail_thresholds": packed(spec, template, s, l)}
-
-    def region_args(name):
-      """`regions=` / `region_bits=` of the store `name` (None: the main store): every store has the grid nodes of `template0`."""
-      spec = (regions or {}).get(name)
-      return {} if spec is None else {"regions": spec, "region_bits": spec.node_bits(template0)}
+    def per_store_args(name, template, s, l):
+      """The `ScoredStore` keywords of the store `name` (None: the main store) for what is given per store: the spec and the
+      settings its row makes of it (`Scorer.from_spec`; thresholds come in the members' units)."""
+      out = {}
+      for arg, specs in per_store.items():
+        spec = (specs or {}).get(name)
+        if spec is not None:
+          out.update({arg: spec}, **verification.scorer(arg).from_spec(spec, template, lambda sp, t: packed(sp, t, s, l)))
+      return out
 
     weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
     wq = None
@@ -1178,8 +1154,7 @@ class EnsembleRollout:
     main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
                                     thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
                                     set_per_score=specs is not None and len(specs) > 1, order=order, climatology=clim_handle,
-                                    energy=eplan(template0), variogram=vplan, **tail_args(None, template0, scale, loc),
-                                    **region_args(None))
+                                    energy=eplan(template0), variogram=vplan, **per_store_args(None, template0, scale, loc))
     run.main = _StoreSeries(main, scale, template0, keep_members=keep_members, keep_quantiles=keep_quantiles)
     main.reserve()
     if spectra:
@@ -1222,8 +1197,7 @@ class EnsembleRollout:
                                        plan=dplan, source=native, order=order, energy=eplan(dtemplate), variogram=vplan,
                                        climatology=None if clim_handle is None
                                        else den.climatology_handle(len(dplan["op"]), view=True),
-                                       climatology_source=clim_handle, **tail_args(name, dtemplate, dscale, dloc),
-                                       **region_args(name))
+                                       climatology_source=clim_handle, **per_store_args(name, dtemplate, dscale, dloc))
       run.views[name] = _StoreSeries(store, dscale, dtemplate, keep_members=keep_members, keep_quantiles=keep_quantiles)
     for store in (v.store for v in run.views.values()):
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
@@ -1242,7 +1216,7 @@ class EnsembleRollout:
       store = verification.ScoredStore(den.window_handle(len(wscale), name), M, weights, events=wev,
                                        thresholds=None if wev is None else packed(wev, stemplate, wscale, wloc), weight_q=wq,
                                        order=order, energy=eplan(stemplate), variogram=vplan,
-                                       **tail_args(name, stemplate, wscale, wloc), **region_args(name))
+                                       **per_store_args(name, stemplate, wscale, wloc))
       run.windows[name] = _WindowEntry(wspec, _StoreSeries(store, wscale, stemplate, keep_members=keep_members), source, horizon)
       run.windows[name].start()
     return run
@@ -1296,7 +1270,7 @@ class EnsembleRollout:
         run.spectra.append(run.raw_spectra[-1].scaled(scale))
 
     samples = None
-    if run.main.clim is not None:
+    if "climatology" in run.main.lists:
       samples = list(run.climatology(k) if callable(run.climatology) else run.climatology[k])
       if not 2 <= len(samples) <= 64:
         raise ValueError(f"climatology of lead time {k}: 2..64 Datasets shaped like the targets, got {len(samples)}")

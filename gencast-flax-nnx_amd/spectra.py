@@ -19,12 +19,13 @@ tests/spectrum_reference.py).
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional
 
 import numpy as np
 
 from . import datasets
 from .noise import _normalized_legendre
+from .verification import AdditiveScores
 
 MAX_CONDITION = 1e3
 
@@ -101,11 +102,15 @@ def ensure_tables(native, template, lmax: Optional[int] = None) -> int:
   return want
 
 
-class EnsembleSpectra:
-  """Raw sums [B, c_out, lmax, 6] float64, the member count M and the number of dates merged."""
+class EnsembleSpectra(AdditiveScores):
+  """Raw sums [B, c_out, lmax, 6] float64, the member count M and the number of dates merged (`merge`: spectra over the union
+  of the dates the parts covered: raw sums and date counts add)."""
 
   NAMES = ("truth_power", "member_power", "mean_power", "power_ratio", "error_power", "mean_error_power", "spread_power",
            "spectral_spread_skill")
+  _adds = ("sums", "n_dates")
+  _listed = NAMES
+  _what = "spectra"
 
   def __init__(self, sums, n_members: int, n_dates: int = 1):
     self.sums = np.asarray(sums, dtype=np.float64)
@@ -175,30 +180,8 @@ class EnsembleSpectra:
       raise ValueError("channel_scale must be finite and non-zero")
     return EnsembleSpectra(self.sums * (a * a)[None, :, None, None], self.n_members, self.n_dates)
 
-  @staticmethod
-  def merge(parts: Sequence["EnsembleSpectra"]) -> "EnsembleSpectra":
-    """Spectra over the union of the dates the parts covered: raw sums and date counts add."""
-    parts = list(parts)
-    if not parts:
-      raise ValueError("merge: nothing to merge")
-    first = parts[0]
-    for p in parts[1:]:
-      if p.n_members != first.n_members or p.sums.shape != first.sums.shape:
-        raise ValueError("merge: the parts differ in members or shape")
-    sums = first.sums.copy()
-    for p in parts[1:]:
-      sums += p.sums
-    return EnsembleSpectra(sums, first.n_members, sum(p.n_dates for p in parts))
-
   def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
     """{spectrum: {variable: [batch, channels of the variable, lmax]}} in the channel order of
     `datasets.channel_layout`."""
-    layout = datasets.channel_layout(datasets.as_dataset(template))
-    if sum(n for _, _, n in layout) != self.sums.shape[1]:
-      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the spectra {self.sums.shape[1]}")
-    out: Dict[str, Dict[str, np.ndarray]] = {}
-    for name in self.NAMES:
-      with np.errstate(divide="ignore", invalid="ignore"):
-        values = getattr(self, name)
-      out[name] = {var: values[:, off:off + n] for var, off, n in layout}
-    return out
+    with np.errstate(divide="ignore", invalid="ignore"):
+      return super().per_variable(template)

@@ -53,15 +53,61 @@ and builds boxes from bounds; `RegionScores[name]` is the region's `EnsembleScor
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Mapping, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import datasets, losses
 
 
-class EnsembleScores:
+class AdditiveScores:
+  """What the score classes made of raw, additive sums share.  A class states `_adds`: the attributes that add (the first of
+  them the array whose shape the parts must share and whose `_channel_axis` is the channel axis), `_same`: {attribute that must
+  be equal across parts: the word for it in the message}, and `_listed`: the properties `per_variable` lists.  The constructor
+  takes all of them by these names."""
+  _adds: Tuple[str, ...] = ()
+  _same: Mapping[str, str] = {"n_members": "members"}
+  _listed: Tuple[str, ...] = ()
+  _channel_axis = 1
+  _what = "scores"
+
+  @classmethod
+  def merge(cls, parts):
+    """Scores over the union of what the parts covered (other nodes, other dates): raw sums and counts add."""
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    for p in parts[1:]:
+      if (any(getattr(p, f) != getattr(first, f) for f in cls._same)
+          or getattr(p, cls._adds[0]).shape != getattr(first, cls._adds[0]).shape):
+        raise ValueError(f"merge: the parts differ in {', '.join(cls._same.values())} or shape")
+    total = {a: np.copy(getattr(first, a)) for a in cls._adds}
+    for p in parts[1:]:
+      for a in cls._adds:
+        total[a] += getattr(p, a)
+    return cls(**total, **{f: getattr(first, f) for f in cls._same})
+
+  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
+    """{score: {variable: [leading axes, channels of the variable, ...]}} in the channel order of `datasets.channel_layout`
+    (`EnsembleScores`, for a variable with levels and one time step: (batch, level)); the leading axes are batch, after the
+    thresholds where the class has them."""
+    layout = datasets.channel_layout(datasets.as_dataset(template))
+    channels = getattr(self, self._adds[0]).shape[self._channel_axis]
+    if sum(n for _, _, n in layout) != channels:
+      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the {self._what} {channels}")
+    lead = (slice(None),) * self._channel_axis
+    out: Dict[str, Dict[str, np.ndarray]] = {}
+    for score in self._listed:
+      values = getattr(self, score)
+      out[score] = {name: values[lead + (slice(off, off + n),)] for name, off, n in layout}
+    return out
+
+
+class EnsembleScores(AdditiveScores):
   """Raw sums [B, c_out, 6] float64, rank histogram [B, c_out, M + 1] uint64 and the member count M."""
+  _adds = ("sums", "rank_histogram")
+  _listed = ("rmse", "spread", "spread_skill_ratio", "crps", "crps_ensemble", "bias", "valid_weight", "rank_histogram")
 
   def __init__(self, sums, rank_histogram, n_members: int):
     self.sums = np.asarray(sums, dtype=np.float64)
@@ -130,36 +176,6 @@ class EnsembleScores:
     return EnsembleScores(self.sums * f[None], hist, self.n_members)
 
   @staticmethod
-  def merge(parts: Sequence["EnsembleScores"]) -> "EnsembleScores":
-    """Scores over the union of what the parts covered (other nodes, other dates): raw sums and counts add."""
-    parts = list(parts)
-    if not parts:
-      raise ValueError("merge: nothing to merge")
-    first = parts[0]
-    for p in parts[1:]:
-      if p.n_members != first.n_members or p.sums.shape != first.sums.shape:
-        raise ValueError("merge: the parts differ in members or shape")
-    sums = first.sums.copy()
-    hist = first.rank_histogram.copy()
-    for p in parts[1:]:
-      sums += p.sums
-      hist += p.rank_histogram
-    return EnsembleScores(sums, hist, first.n_members)
-
-  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
-    """{score: {variable: [batch, channels of the variable]}} in the channel order of `datasets.channel_layout`
-    (for a variable with levels and one time step: (batch, level))."""
-    layout = datasets.channel_layout(datasets.as_dataset(template))
-    if sum(n for _, _, n in layout) != self.sums.shape[1]:
-      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.sums.shape[1]}")
-    out: Dict[str, Dict[str, np.ndarray]] = {}
-    for score in ("rmse", "spread", "spread_skill_ratio", "crps", "crps_ensemble", "bias", "valid_weight"):
-      values = getattr(self, score)
-      out[score] = {name: values[:, off:off + n] for name, off, n in layout}
-    out["rank_histogram"] = {name: self.rank_histogram[:, off:off + n] for name, off, n in layout}
-    return out
-
-  @staticmethod
   def node_weights(template) -> np.ndarray:
     return node_weights(template)
 
@@ -177,7 +193,7 @@ def node_weights(template) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------
 # order statistics: quantiles and the reliability / potential split of the CRPS (gc_ens_order_*)
 # ---------------------------------------------------------------------------------------------
-class OrderScores:
+class OrderScores(AdditiveScores):
   """The raw sums of `gc_ens_order_score`: `bins` [B, c_out, M + 1, 2] float64 (A_k = sum w alpha_k, B_k = sum w beta_k),
   `extra` [B, c_out, 3] (S0 = sum w, O_lo = sum w [y < x_(1)], O_hi = sum w [y > x_(M)]), `pinball` [B, c_out, Q],
   `counts` [B, c_out, Q + 1] uint64 (points with y < Q_q; last: the counted points), with the member count M and the
@@ -191,6 +207,10 @@ class OrderScores:
   `crps_ensemble` is `EnsembleScores.crps_ensemble` of the same store.  Hersbach's further split of the potential CRPS into
   uncertainty and resolution needs the climatological distribution of the observations, which is not additive over dates:
   it is not formed here."""
+  _adds = ("bins", "extra", "pinball", "counts")
+  _same = {"n_members": "members", "probs": "probabilities"}
+  _listed = ("crps_ensemble", "reliability", "crps_potential", "outlier_low", "outlier_high", "bin_width", "bin_frequency",
+             "quantile_score", "quantile_coverage", "valid_weight", "valid_points")
 
   def __init__(self, bins, extra, pinball, counts, n_members: int, probs):
     self.bins = np.asarray(bins, dtype=np.float64)
@@ -295,41 +315,11 @@ class OrderScores:
     return OrderScores(self.bins * a[None, :, None, None], self.extra, self.pinball * a[None, :, None], self.counts,
                        self.n_members, self.probs)
 
-  @staticmethod
-  def merge(parts: Sequence["OrderScores"]) -> "OrderScores":
-    """Scores over the union of what the parts covered (other nodes, other dates): raw sums and counts add."""
-    parts = list(parts)
-    if not parts:
-      raise ValueError("merge: nothing to merge")
-    first = parts[0]
-    for p in parts[1:]:
-      if p.n_members != first.n_members or p.probs != first.probs or p.bins.shape != first.bins.shape:
-        raise ValueError("merge: the parts differ in members, probabilities or shape")
-    bins, extra, pinball, counts = first.bins.copy(), first.extra.copy(), first.pinball.copy(), first.counts.copy()
-    for p in parts[1:]:
-      bins += p.bins
-      extra += p.extra
-      pinball += p.pinball
-      counts += p.counts
-    return OrderScores(bins, extra, pinball, counts, first.n_members, first.probs)
-
-  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
-    """{score: {variable: [batch, channels of the variable, ...]}} in the channel order of `datasets.channel_layout`."""
-    layout = datasets.channel_layout(datasets.as_dataset(template))
-    if sum(n for _, _, n in layout) != self.bins.shape[1]:
-      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.bins.shape[1]}")
-    out: Dict[str, Dict[str, np.ndarray]] = {}
-    for score in ("crps_ensemble", "reliability", "crps_potential", "outlier_low", "outlier_high", "bin_width", "bin_frequency",
-                  "quantile_score", "quantile_coverage", "valid_weight", "valid_points"):
-      values = getattr(self, score)
-      out[score] = {name: values[:, off:off + n] for name, off, n in layout}
-    return out
-
 
 # ---------------------------------------------------------------------------------------------
 # skill against a climatology: anomaly correlation and CRPS skill score (gc_ens_clim_score)
 # ---------------------------------------------------------------------------------------------
-class ClimatologyScores:
+class ClimatologyScores(AdditiveScores):
   """The raw sums of `gc_ens_clim_score`: `sums` [B, c_out, 12] float64 and `counts` [B, c_out] uint64 (counted points),
   with the member count M, the number K of climatological samples and the points `invalid` that did not count.  With m
   the ensemble mean, cbar the mean of the K samples, fa = m - cbar, oa = y - cbar, ae the mean |. - y| and d the mean
@@ -341,6 +331,10 @@ class ClimatologyScores:
   Every derived score is [B, c_out]; a zero denominator gives NaN, not an error."""
 
   N_SUMS = 12
+  _adds = ("sums", "counts", "invalid")
+  _same = {"n_members": "members", "n_climatology": "climatological samples"}
+  _listed = ("acc", "acc_centred", "acc_members", "crps", "crps_climatology", "crpss", "crps_ensemble",
+             "crps_climatology_ensemble", "crpss_ensemble", "msss", "rmse", "rmse_climatology", "valid_weight", "valid_points")
 
   def __init__(self, sums, counts, n_members: int, n_climatology: int, invalid: int = 0):
     self.sums = np.asarray(sums, dtype=np.float64)
@@ -458,36 +452,6 @@ class ClimatologyScores:
     f = np.stack([one, a, a, sq, sq, sq, sq, sq, ab, ab, ab, ab], axis=-1)
     return ClimatologyScores(self.sums * f[None], self.counts, self.n_members, self.n_climatology, self.invalid)
 
-  @staticmethod
-  def merge(parts: Sequence["ClimatologyScores"]) -> "ClimatologyScores":
-    """Scores over the union of what the parts covered (other nodes, other dates): raw sums and counts add."""
-    parts = list(parts)
-    if not parts:
-      raise ValueError("merge: nothing to merge")
-    first = parts[0]
-    for p in parts[1:]:
-      if (p.n_members != first.n_members or p.n_climatology != first.n_climatology or p.sums.shape != first.sums.shape):
-        raise ValueError("merge: the parts differ in members, climatological samples or shape")
-    sums, counts, invalid = first.sums.copy(), first.counts.copy(), first.invalid
-    for p in parts[1:]:
-      sums += p.sums
-      counts += p.counts
-      invalid += p.invalid
-    return ClimatologyScores(sums, counts, first.n_members, first.n_climatology, invalid)
-
-  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
-    """{score: {variable: [batch, channels of the variable]}} in the channel order of `datasets.channel_layout`."""
-    layout = datasets.channel_layout(datasets.as_dataset(template))
-    if sum(n for _, _, n in layout) != self.sums.shape[1]:
-      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.sums.shape[1]}")
-    out: Dict[str, Dict[str, np.ndarray]] = {}
-    for score in ("acc", "acc_centred", "acc_members", "crps", "crps_climatology", "crpss", "crps_ensemble",
-                  "crps_climatology_ensemble", "crpss_ensemble", "msss", "rmse", "rmse_climatology", "valid_weight",
-                  "valid_points"):
-      values = getattr(self, score)
-      out[score] = {name: values[:, off:off + n] for name, off, n in layout}
-    return out
-
 
 # ---------------------------------------------------------------------------------------------
 # events: exceedance probabilities against thresholds (gc_ens_event_*)
@@ -592,7 +556,7 @@ class EventSpec:
     return np.ascontiguousarray(np.stack(out), dtype=np.float32)
 
 
-class EventScores:
+class EventScores(AdditiveScores):
   """The integer tables of `gc_ens_event_score`: `weighted` and `counts` [T, B, c_out, 2, M + 1] uint64 (axis -2: the
   truth outside / inside the event, axis -1: k members inside), `invalid` [T] points skipped, with the member count M,
   the directions [T] and the `scale` of the quantised node weights.  Every derived score is [T, B, c_out] float64 (curves
@@ -601,6 +565,11 @@ class EventScores:
   With n_k = (weighted[0][k] + weighted[1][k]) / scale, o_k = weighted[1][k] / scale, N = sum n_k, O = sum o_k, s = O / N
   and p_k = k / M.  The bins are the distinct forecast values, so brier = reliability - resolution + uncertainty holds
   exactly in exact arithmetic."""
+  _adds = ("weighted", "counts", "invalid")
+  _same = {"n_members": "members", "directions": "directions", "scale": "scale"}
+  _listed = ("base_rate", "brier", "brier_fair", "reliability", "resolution", "uncertainty", "brier_skill", "roc_area",
+             "valid_weight", "valid_points")
+  _channel_axis = 2
 
   def __init__(self, weighted, counts, n_members: int, directions: Sequence[int], scale: float, invalid=None):
     self.weighted = np.asarray(weighted, dtype=np.uint64)
@@ -735,44 +704,18 @@ class EventScores:
     value = self._ratio(e_clim - e, e_clim - e_perf)
     return np.max(value, axis=3)                           # (the denominators do not depend on j: NaN at all levels or none)
 
-  @staticmethod
-  def merge(parts: Sequence["EventScores"]) -> "EventScores":
-    """Scores over the union of what the parts covered (other nodes, other dates): the integer tables add."""
-    parts = list(parts)
-    if not parts:
-      raise ValueError("merge: nothing to merge")
-    first = parts[0]
-    for p in parts[1:]:
-      if (p.n_members != first.n_members or p.directions != first.directions or p.scale != first.scale
-          or p.weighted.shape != first.weighted.shape):
-        raise ValueError("merge: the parts differ in members, directions, scale or shape")
-    weighted, counts, invalid = first.weighted.copy(), first.counts.copy(), first.invalid.copy()
-    for p in parts[1:]:
-      weighted += p.weighted
-      counts += p.counts
-      invalid += p.invalid
-    return EventScores(weighted, counts, first.n_members, first.directions, first.scale, invalid)
 
-  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
-    """{score: {variable: [T, batch, channels of the variable]}} in the channel order of `datasets.channel_layout`."""
-    layout = datasets.channel_layout(datasets.as_dataset(template))
-    if sum(n for _, _, n in layout) != self.weighted.shape[2]:
-      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.weighted.shape[2]}")
-    out: Dict[str, Dict[str, np.ndarray]] = {}
-    for score in ("base_rate", "brier", "brier_fair", "reliability", "resolution", "uncertainty", "brier_skill", "roc_area",
-                  "valid_weight", "valid_points"):
-      values = getattr(self, score)
-      out[score] = {name: values[:, :, off:off + n] for name, off, n in layout}
-    return out
-
-
-class TailScores:
+class TailScores(AdditiveScores):
   """The raw sums of `gc_ens_tail_score`: `sums` [T, B, c_out, 4] float64 -- S0 = sum w, S1 = sum w ae, S2 = sum w d,
   S3 = sum w o over the counted nodes, with ae the mean absolute difference between the clamped members and the clamped
   truth, d the mean absolute difference between two clamped members (the Gini mean difference) and o whether the truth lies
   in the event -- `counts` [T, B, c_out] uint64 (counted points) and `invalid` [T] points skipped, with the member count M
   and the directions [T] (> 0: the upper tail, weight 1{z >= threshold}; < 0: the lower tail).  The sums are additive.
   Every score is [T, B, c_out] float64; where nothing counted (S0 = 0: a NaN threshold) it is NaN, not an error."""
+  _adds = ("sums", "counts", "invalid")
+  _same = {"n_members": "members", "directions": "directions"}
+  _listed = ("twcrps", "twcrps_ensemble", "abs_error", "pair_distance", "base_rate", "valid_weight", "valid_points")
+  _channel_axis = 2
 
   def __init__(self, sums, counts, n_members: int, directions: Sequence[int], invalid=None):
     self.sums = np.asarray(sums, dtype=np.float64)
@@ -841,34 +784,6 @@ class TailScores:
       raise ValueError("channel_scale must be finite and > 0 (a negative scale swaps the tails)")
     f = np.stack([np.ones_like(a), a, a, np.ones_like(a)], axis=-1)
     return TailScores(self.sums * f[None, None], self.counts, self.n_members, self.directions, self.invalid)
-
-  @staticmethod
-  def merge(parts: Sequence["TailScores"]) -> "TailScores":
-    """Scores over the union of what the parts covered (other nodes, other dates): raw sums and counts add."""
-    parts = list(parts)
-    if not parts:
-      raise ValueError("merge: nothing to merge")
-    first = parts[0]
-    for p in parts[1:]:
-      if p.n_members != first.n_members or p.directions != first.directions or p.sums.shape != first.sums.shape:
-        raise ValueError("merge: the parts differ in members, directions or shape")
-    sums, counts, invalid = first.sums.copy(), first.counts.copy(), first.invalid.copy()
-    for p in parts[1:]:
-      sums += p.sums
-      counts += p.counts
-      invalid += p.invalid
-    return TailScores(sums, counts, first.n_members, first.directions, invalid)
-
-  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
-    """{score: {variable: [T, batch, channels of the variable]}} in the channel order of `datasets.channel_layout`."""
-    layout = datasets.channel_layout(datasets.as_dataset(template))
-    if sum(n for _, _, n in layout) != self.sums.shape[2]:
-      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.sums.shape[2]}")
-    out: Dict[str, Dict[str, np.ndarray]] = {}
-    for score in ("twcrps", "twcrps_ensemble", "abs_error", "pair_distance", "base_rate", "valid_weight", "valid_points"):
-      values = getattr(self, score)
-      out[score] = {name: values[:, :, off:off + n] for name, off, n in layout}
-    return out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1436,11 +1351,14 @@ class VariogramSpec:
     return {"n_lat": int(n_lat), "n_lon": int(n_lon), "offsets": np.asarray(self.offsets, dtype=np.int32), "p": self.p}
 
 
-class VariogramScores:
+class VariogramScores(AdditiveScores):
   """The raw sums of `gc_ens_variogram_score`: `sums` [4, B, c_out, O] float64 -- V0 = sum omega, V1 = sum omega (vy - vx)^2,
   V2 = sum omega vx, V3 = sum omega vy over the valid pairs, v(u) = |u_g - u_g'|^p, vx the members' mean of it, vy the
   truth's -- and `counts` [B, c_out, O] uint64 (valid pairs), with the member count, the offsets [O] and p.  The sums are
   additive.  Every score is [B, c_out, O]."""
+  _adds = ("counts", "sums")                                # (the counts first: they have the shape of a score)
+  _same = {"n_members": "members", "offsets": "offsets", "p": "order"}
+  _listed = ("variogram_score", "ensemble_variogram", "truth_variogram", "roughness_ratio", "valid_weight", "valid_pairs")
 
   def __init__(self, sums, counts, n_members: int, offsets, p: float):
     self.sums = np.asarray(sums, dtype=np.float64)
@@ -1491,32 +1409,82 @@ class VariogramScores:
     f = np.stack([np.ones_like(a), ap * ap, ap, ap])[:, None, :, None]
     return VariogramScores(self.sums * f, self.counts, self.n_members, self.offsets, self.p)
 
-  @staticmethod
-  def merge(parts: Sequence["VariogramScores"]) -> "VariogramScores":
-    """Scores over the union of what the parts covered (other dates): raw sums and counts add."""
-    parts = list(parts)
-    if not parts:
-      raise ValueError("merge: nothing to merge")
-    first = parts[0]
-    for q in parts[1:]:
-      if q.n_members != first.n_members or q.offsets != first.offsets or q.p != first.p or q.sums.shape != first.sums.shape:
-        raise ValueError("merge: the parts differ in members, offsets, order or shape")
-    sums, counts = first.sums.copy(), first.counts.copy()
-    for q in parts[1:]:
-      sums += q.sums
-      counts += q.counts
-    return VariogramScores(sums, counts, first.n_members, first.offsets, first.p)
 
-  def per_variable(self, template) -> Dict[str, Dict[str, np.ndarray]]:
-    """{score: {variable: [batch, channels of the variable, O]}} in the channel order of `datasets.channel_layout`."""
-    layout = datasets.channel_layout(datasets.as_dataset(template))
-    if sum(n for _, _, n in layout) != self.sums.shape[2]:
-      raise ValueError(f"template has {sum(n for _, _, n in layout)} channels, the scores {self.sums.shape[2]}")
-    out: Dict[str, Dict[str, np.ndarray]] = {}
-    for score in ("variogram_score", "ensemble_variogram", "truth_variogram", "roughness_ratio", "valid_weight", "valid_pairs"):
-      values = getattr(self, score)
-      out[score] = {name: values[:, off:off + n] for name, off, n in layout}
-    return out
+# ---------------------------------------------------------------------------------------------
+# the scorers of a member store, each declared once
+# ---------------------------------------------------------------------------------------------
+class Scorer(NamedTuple):
+  """One row of `SCORERS`: everything `ScoredStore`, the rollout's results and its per-lead loop know about a scorer."""
+  name: str                                   # the series on a result; with `score`, the `ScoredStore` keyword that switches it on
+  word: Optional[str]                         # what an error message calls it (None: the scores themselves, never checked alone)
+  settings: Tuple[str, ...] = ()              # the companion keywords and attributes of `ScoredStore`
+  set: Optional[Callable] = None              # set(store): hands the settings to `store.handle`; they survive every score
+  score: Optional[Callable] = None            # score(store, truth) -> the score object (None: not scored through `_score`)
+  scaled: bool = True                         # the scores have a `scaled(scale)` twin: the raw series is `<name>_normalized`
+  optional: bool = True                       # absent from `vars(result)` unless the run asked for it
+  carried_by: Tuple[str, ...] = ("ensemble", "derived", "window")   # the results (`_SeriesResult._carried_as`) that hold it
+  from_spec: Optional[Callable] = None        # from_spec(spec, template, pack) -> {setting: value} for a spec given per store
+
+  @property
+  def series(self) -> Tuple[str, ...]:
+    return (self.name, self.name + "_normalized") if self.scaled else (self.name,)
+
+
+def _score_events(store, truth):
+  weighted, counts, invalid = store.handle.ens_event_score(truth)
+  return EventScores(weighted, counts, store.n_members, store.events.directions, store.weight_q[1], invalid)
+
+
+def _score_order(store, truth):
+  bins, extra, pinball, counts, _ = store.handle.ens_order_score(truth)
+  return OrderScores(bins, extra, pinball, counts, store.n_members, store.order)
+
+
+def _score_energy(store, truth):
+  d2, s0, invalid = store.handle.ens_energy_score(truth)
+  return EnergyScores.from_sums(d2, s0, store.n_members, store.energy.get("names"), invalid)
+
+
+def _score_variogram(store, truth):
+  sums, counts = store.handle.ens_variogram_score(truth)
+  return VariogramScores(sums, counts, store.n_members, store.variogram["offsets"], store.variogram["p"])
+
+
+def _score_tails(store, truth):
+  sums, counts, invalid = store.handle.ens_tail_score(truth)
+  return TailScores(sums, counts, store.n_members, store.tails.directions, invalid)
+
+
+def _score_regions(store, truth):
+  sums, hist, invalid = store.handle.ens_region_score(truth)
+  return RegionScores(store.regions.names, sums, hist, store.n_members, invalid)
+
+
+# In the order in which a store is configured and a lead time is scored, which is the order of the series on a result.  The
+# scores, the spectra (the main handle only) and the climatology (a second handle: `ScoredStore.score_climatology`) are rows for
+# what a row can say of them.  The rows up to the climatology predate the `optional` rule: their series are always set.
+SCORERS = [
+    Scorer("scores", None, optional=False),
+    Scorer("spectra", "spectra", optional=False, carried_by=("ensemble",)),
+    Scorer("events", "events", ("thresholds", "weight_q"), scaled=False, optional=False, score=_score_events,
+           set=lambda s: s.handle.ens_event_set(s.thresholds, s.events.directions, s.weight_q[0])),
+    Scorer("order", "order statistics", optional=False, score=_score_order, set=lambda s: s.handle.ens_order_set(s.order)),
+    Scorer("climatology", "climatology scores", optional=False, carried_by=("ensemble", "derived")),
+    Scorer("energy", "energy scores", scaled=False, score=_score_energy,         # (in the store's own units: no `scaled`)
+           set=lambda s: s.handle.ens_energy_set(s.energy["n_groups"], s.energy["group"], s.energy["scale"])),
+    Scorer("variogram", "variogram scores", score=_score_variogram,
+           set=lambda s: s.handle.ens_variogram_set(*(s.variogram[k] for k in ("n_lat", "n_lon", "offsets", "p")))),
+    Scorer("tails", "tail scores", ("tail_thresholds",), score=_score_tails,
+           set=lambda s: s.handle.ens_tail_set(s.tail_thresholds, s.tails.directions),
+           from_spec=lambda spec, template, pack: {"tail_thresholds": pack(spec, template)}),
+    Scorer("regions", "region scores", ("region_bits",), score=_score_regions,
+           set=lambda s: s.handle.ens_region_set(s.region_bits, s.regions.n_regions),
+           from_spec=lambda spec, template, pack: {"region_bits": spec.node_bits(template)}),
+]
+
+
+def scorer(name: str) -> Scorer:
+  return next(row for row in SCORERS if row.name == name)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1539,27 +1507,27 @@ class ScoredStore:
   `set_per_score`: the plan and the thresholds are not set once by `setup` but by every `score` -- two stores that share
   a handle, or thresholds that change from call to call (assign `thresholds` before the call)."""
 
-  def __init__(self, handle, n_members: int, node_weight=None, *, events: Optional["EventSpec"] = None, thresholds=None,
-               weight_q: Optional[Tuple[np.ndarray, float]] = None, plan=None, source=None, set_per_score: bool = False,
-               order=None, climatology=None, climatology_source=None, energy=None, variogram=None,
-               tails: Optional["EventSpec"] = None, tail_thresholds=None, regions: Optional["RegionSpec"] = None,
-               region_bits=None):
-    if regions is not None and region_bits is None:
+  def __init__(self, handle, n_members: int, node_weight=None, *, plan=None, source=None, set_per_score: bool = False,
+               climatology=None, climatology_source=None, **scorers):
+    """`scorers`: per row of `SCORERS` with a `score`, its name (what switches it on) and its settings, None by default."""
+    for row in (r for r in SCORERS if r.score is not None):
+      for key in (row.name,) + row.settings:
+        setattr(self, key, scorers.pop(key, None))
+    if scorers:
+      raise TypeError(f"ScoredStore() got an unexpected keyword argument {next(iter(scorers))!r}")
+    if self.regions is not None and self.region_bits is None:
       raise ValueError("regions need their node bits (RegionSpec.node_bits)")
     if climatology_source is not None and (climatology is None or plan is None):
       raise ValueError("a climatology source goes with a climatology handle and a derive plan")
-    if events is not None and weight_q is None:
+    if self.events is not None and self.weight_q is None:
       raise ValueError("events need the quantised node weights (quantize_node_weights)")
     if (plan is None) != (source is None):
       raise ValueError("a derive plan and its source handle go together")
     self.handle, self.n_members, self.node_weight = handle, int(n_members), node_weight
-    self.events, self.thresholds, self.weight_q = events, thresholds, weight_q
     self.plan, self.source, self.set_per_score = plan, source, bool(set_per_score)
-    self.order = None if order is None else tuple(float(p) for p in np.asarray(order, dtype=np.float64).reshape(-1))
+    if self.order is not None:
+      self.order = tuple(float(p) for p in np.asarray(self.order, dtype=np.float64).reshape(-1))
     self.climatology, self.climatology_source = climatology, climatology_source
-    self.energy, self.variogram = energy, variogram          # the plans (`EnergySpec.plan`, `VariogramSpec.plan`) or None
-    self.tails, self.tail_thresholds = tails, tail_thresholds
-    self.regions, self.region_bits = regions, region_bits
     self._clim_reserved = 0                      # K of the store this object reserved on the climatology handle
     self._clim_plan_set = False                  # the plan has been handed to the climatology handle (a derived view)
 
@@ -1572,106 +1540,56 @@ class ScoredStore:
     if self.plan is not None:
       self.handle.ens_derive_set(**self.plan)
 
-  def _set_events(self) -> None:
-    if self.events is not None:
-      self.handle.ens_event_set(self.thresholds, self.events.directions, self.weight_q[0])
-
-  def _set_order(self) -> None:
-    if self.order is not None:
-      self.handle.ens_order_set(self.order)
-
-  def _set_energy(self) -> None:
-    if self.energy is not None:
-      self.handle.ens_energy_set(self.energy["n_groups"], self.energy["group"], self.energy["scale"])
-
-  def _set_variogram(self) -> None:
-    if self.variogram is not None:
-      v = self.variogram
-      self.handle.ens_variogram_set(v["n_lat"], v["n_lon"], v["offsets"], v["p"])
-
-  def _set_tails(self) -> None:
-    if self.tails is not None:
-      self.handle.ens_tail_set(self.tail_thresholds, self.tails.directions)
-
-  def _set_regions(self) -> None:
-    if self.regions is not None:
-      self.handle.ens_region_set(self.region_bits, self.regions.n_regions)
-
   def configure(self) -> None:
-    """The plan, the thresholds, the probabilities, the multivariate plans, the tails and the regions: all survive
-    `ens_reserve` and every score."""
+    """The plan, then every scorer that is switched on, in the order of `SCORERS` -- the thresholds, the probabilities, the
+    multivariate plans, the tails and the regions: all survive `ens_reserve` and every score."""
     self._set_plan()
-    self._set_events()
-    self._set_order()
-    self._set_energy()
-    self._set_variogram()
-    self._set_tails()
-    self._set_regions()
+    for row in SCORERS:
+      if row.set is not None and getattr(self, row.name) is not None:
+        row.set(self)
 
   def setup(self) -> None:
     self.reserve()
     if not self.set_per_score:
       self.configure()
 
-  def score_events(self, truth=None) -> Optional["EventScores"]:
-    """The event tables of the store (None without an EventSpec); `truth` None: the truth already on the device."""
-    if self.events is None:
+  def _score(self, row: Scorer, truth=None):
+    """The scores of one row of `SCORERS` (None where the store does not have it switched on)."""
+    if getattr(self, row.name) is None:
       return None
     if self.set_per_score:
-      self._set_events()
-    weighted, counts, invalid = self.handle.ens_event_score(truth)
-    return EventScores(weighted, counts, self.n_members, self.events.directions, self.weight_q[1], invalid)
+      row.set(self)
+    return row.score(self, truth)
+
+  def score_events(self, truth=None) -> Optional["EventScores"]:
+    """The event tables of the store (None without an EventSpec); `truth` None: the truth already on the device."""
+    return self._score(scorer("events"), truth)
 
   def score_order(self, truth=None) -> Optional["OrderScores"]:
     """The order statistics of the store (None without `order`); `truth` None: the truth already on the device.  On a
     derived view (a store with a plan) the DERIVED members are scored: call it after `score`, which fills the view, and
     leave `truth` None."""
-    if self.order is None:
-      return None
-    if self.set_per_score:
-      self._set_order()
-    bins, extra, pinball, counts, _ = self.handle.ens_order_score(truth)
-    return OrderScores(bins, extra, pinball, counts, self.n_members, self.order)
+    return self._score(scorer("order"), truth)
 
   def score_energy(self, truth=None) -> Optional["EnergyScores"]:
     """The energy score of the store over the groups of `energy` (None without it), in the store's own units; `truth` None:
     the truth already on the device.  On a derived view the DERIVED members are scored: call it after `score`."""
-    if self.energy is None:
-      return None
-    if self.set_per_score:
-      self._set_energy()
-    d2, s0, invalid = self.handle.ens_energy_score(truth)
-    return EnergyScores.from_sums(d2, s0, self.n_members, self.energy.get("names"), invalid)
+    return self._score(scorer("energy"), truth)
 
   def score_variogram(self, truth=None) -> Optional["VariogramScores"]:
     """The raw variogram sums of the store at the offsets of `variogram` (None without it), in the store's own units;
     `truth` None: the truth already on the device.  On a derived view call it after `score`."""
-    if self.variogram is None:
-      return None
-    if self.set_per_score:
-      self._set_variogram()
-    sums, counts = self.handle.ens_variogram_score(truth)
-    return VariogramScores(sums, counts, self.n_members, self.variogram["offsets"], self.variogram["p"])
+    return self._score(scorer("variogram"), truth)
 
   def score_tails(self, truth=None) -> Optional["TailScores"]:
     """The raw threshold-weighted CRPS sums of the store at the thresholds of `tails` (None without it), in the store's own
     units; `truth` None: the truth already on the device.  On a derived view call it after `score`."""
-    if self.tails is None:
-      return None
-    if self.set_per_score:
-      self._set_tails()
-    sums, counts, invalid = self.handle.ens_tail_score(truth)
-    return TailScores(sums, counts, self.n_members, self.tails.directions, invalid)
+    return self._score(scorer("tails"), truth)
 
   def score_regions(self, truth=None) -> Optional["RegionScores"]:
     """The raw sums of `score` per region of `regions` (None without it), from one pass over the nodes of all regions, in the
     store's own units; `truth` None: the truth already on the device.  On a derived view call it after `score`."""
-    if self.regions is None:
-      return None
-    if self.set_per_score:
-      self._set_regions()
-    sums, hist, invalid = self.handle.ens_region_score(truth)
-    return RegionScores(self.regions.names, sums, hist, self.n_members, invalid)
+    return self._score(scorer("regions"), truth)
 
   def _reserve_climatology(self, K: int) -> None:
     if K != self._clim_reserved:
