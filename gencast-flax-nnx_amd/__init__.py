@@ -31,6 +31,9 @@ Public surface (mirrors the reference's call contracts):
                       RegionSpec / RegionScores: the ensemble scores per region of the grid (tropics, extratropics, land,
                       sea, boxes), every region from one pass on the GPU (GenCast.ensemble_regions,
                       EnsembleRollout.run(regions=...))
+                      FeatureSpec / FeatureScores / link_tracks: cyclone centres per member found on the GPU (a local
+                      extremum with a depth test), their strike-probability map scored like any field, tracks linked on
+                      the host (GenCast.ensemble_features, EnsembleRollout.run(features=...))
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
@@ -44,13 +47,13 @@ from .denoiser import Denoiser  # noqa: F401
 from .ensemble import EnsembleSampler, member_seed, member_shard  # noqa: F401
 from .gencast import GenCast, compute_loss, create_gencast_model, validation_loss  # noqa: F401
 from .nan_cleaning import NaNCleaner  # noqa: F401
-from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, EnsembleRolloutResult, InputsAndResiduals,  # noqa: F401
-                      WindowRolloutResult, autoregressive_rollout, state_channels)
+from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, EnsembleRolloutResult, FeatureRolloutResult,  # noqa: F401
+                      InputsAndResiduals, WindowRolloutResult, autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
 from .verification import (ClimatologyScores, DerivedSpec, EnergyScores, EnergySpec, EnsembleScores, EventScores,  # noqa: F401
-                           EventSpec, OrderScores, RegionScores, RegionSpec, TailScores, VariogramScores, VariogramSpec,
-                           WindowSpec)
+                           EventSpec, FeatureScores, FeatureSpec, OrderScores, RegionScores, RegionSpec, TailScores,
+                           VariogramScores, VariogramSpec, WindowSpec, link_tracks)
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
@@ -59,4 +62,4 @@ __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_
            "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec",
            "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores",
            "WindowSpec", "WindowRolloutResult", "EnergySpec", "EnergyScores", "VariogramSpec", "VariogramScores", "TailScores",
-           "RegionSpec", "RegionScores"]
+           "RegionSpec", "RegionScores", "FeatureSpec", "FeatureScores", "FeatureRolloutResult", "link_tracks"]

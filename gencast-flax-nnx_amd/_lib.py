@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 import sys
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -146,6 +146,11 @@ SIGNATURES = {
     "gc_ens_region_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
     "gc_ens_region_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_feature_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, ctypes.c_int32,
+                                          ctypes.c_int32, _i32p, _i32p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double), _i32p, _i32p,
+                                          ctypes.c_int32]),
+    "gc_ens_feature": (ctypes.c_int, [_hp, _hp, _f32p]),
+    "gc_ens_feature_centres": (ctypes.c_int, [_hp, _i32p, _i32p, _f32p]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
@@ -238,6 +243,9 @@ class NativeDenoiser:
     self._spec_lmax = 0                        # band limit of the analysis tables this object handed to the handle
     self._event_thresholds = 0                 # threshold fields this object handed to the handle
     self._derive_c_src = 0                     # source channels of the derive plan this object handed to the handle
+    self._feature_c_src = 0                    # source channels of the feature plan, and the size of its lists
+    self._feature_max = 0
+    self._feature_members = -1                 # M of the last ens_feature (-1: none since the plan was set)
     self._order_quantiles = None               # probabilities this object handed to the handle (None: ens_order_set not called)
     self._energy_groups = None                 # groups of the energy plan this object set (None: ens_energy_set not called)
     self._variogram_offsets = None             # offsets of the variogram plan this object set (None: ens_variogram_set not called)
@@ -719,6 +727,87 @@ class NativeDenoiser:
       if t.shape != want:
         raise ValueError(f"truth must be {want}, got {t.shape}")
     self._check(self._lib.gc_ens_derive(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
+
+  # -- ensemble feature detection (centres and strike fields, into this handle's member store) -------------
+  def ens_feature_set(self, c_src: int, channel, direction, use_threshold, threshold, n_lat: int, n_lon: int, r_lat, r_lon,
+                      ring_lat, ring_lon, depth, strike_lat, strike_lon, max_centres: int = 64) -> None:
+    """The plan of `ens_feature` for this handle's c_out = D detectors (gc_ens_feature_set; needs `set_graph` only, survives
+    `ens_reserve`).  Per detector: the source `channel`, `direction` (< 0 a minimum, > 0 a maximum), `use_threshold` and
+    `threshold` (the members' units), the extremum window `r_lat`, `r_lon` [D, n_lat], the ring `ring_lat` (0: no ring test),
+    `ring_lon` [D, n_lat] and its `depth` (the members' units), the strike window `strike_lat`, `strike_lon` [D, n_lat];
+    `max_centres` (1..1024) entries per list.  `verification.FeatureSpec` builds these arrays from variable names."""
+    D = self.cfg.c_out
+    if not 1 <= D <= 8:
+      raise ValueError(f"a feature plan needs a handle with c_out in 1 .. 8, got {D}")
+    if int(c_src) < 1:
+      raise ValueError("c_src must be positive")
+    if n_lat is None or n_lon is None or int(n_lat) * int(n_lon) != self.num_grid_nodes:
+      raise ValueError(f"n_lat * n_lon must equal the number of grid nodes ({self.num_grid_nodes})")
+    n_lat, n_lon = int(n_lat), int(n_lon)
+    ch, di, ut = _i32(channel), _i32(direction), _i32(use_threshold)
+    rl, gl, sl = _i32(r_lat), _i32(ring_lat), _i32(strike_lat)
+    th, de = _f32(threshold), np.ascontiguousarray(depth, dtype=np.float64)
+    for name, a in (("channel", ch), ("direction", di), ("use_threshold", ut), ("threshold", th), ("r_lat", rl), ("ring_lat", gl),
+                    ("depth", de), ("strike_lat", sl)):
+      if a.shape != (D,):
+        raise ValueError(f"{name} must have shape ({D},), got {a.shape}")
+    if np.any((ch < 0) | (ch >= int(c_src))):
+      raise ValueError(f"a source channel lies outside [0, {int(c_src)})")
+    if np.any(di == 0):
+      raise ValueError("direction must be < 0 (a minimum) or > 0 (a maximum)")
+    if not np.all(np.isfinite(th[ut != 0])):
+      raise ValueError("a threshold in use must be finite")
+    if np.any(rl < 0) or np.any(gl < 0) or np.any(sl < 0):
+      raise ValueError("r_lat, ring_lat and strike_lat must be >= 0")
+    if not np.all(np.isfinite(de[gl > 0])):
+      raise ValueError("the depth of a ring in use must be finite")
+    lons = []
+    for name, a in (("r_lon", r_lon), ("ring_lon", ring_lon), ("strike_lon", strike_lon)):
+      a = _i32(a)
+      if a.shape != (D, n_lat):
+        raise ValueError(f"{name} must have shape ({D}, {n_lat}), got {a.shape}")
+      if np.any((a < 0) | (a > (n_lon - 1) // 2)):
+        raise ValueError(f"{name} must lie in 0 .. {(n_lon - 1) // 2}")
+      lons.append(a)
+    if isinstance(max_centres, bool) or int(max_centres) != max_centres or not 1 <= int(max_centres) <= 1024:
+      raise ValueError(f"max_centres must be an integer in 1 .. 1024, got {max_centres!r}")
+    self._check(self._lib.gc_ens_feature_set(self._h, int(c_src), D, _ptr(ch, _i32p), _ptr(di, _i32p), _ptr(ut, _i32p), _ptr(th, _f32p),
+                                             n_lat, n_lon, _ptr(rl, _i32p), _ptr(lons[0], _i32p), _ptr(gl, _i32p), _ptr(lons[1], _i32p),
+                                             _ptr(de, ctypes.POINTER(ctypes.c_double)), _ptr(sl, _i32p), _ptr(lons[2], _i32p),
+                                             int(max_centres)))
+    self._feature_c_src, self._feature_max, self._feature_members = int(c_src), int(max_centres), -1
+
+  def ens_feature(self, src: "NativeDenoiser", truth=None) -> None:
+    """Every slot of this handle's member store <- the strike fields of the centres found in the member of `src`'s store,
+    this handle's truth <- those of the truth of `src` (gc_ens_feature): afterwards every scorer of THIS handle sees the
+    0 / 1 fields (truth None) and `ens_feature_centres` returns the lists.  `truth` [G, B, c_src] is uploaded into `src`, or
+    None = the truth `src` holds."""
+    if not self._feature_c_src:
+      raise GencastHipError("libgencast_hip error 4: no plan (ens_feature_set has not been called on this object)")
+    if not isinstance(src, NativeDenoiser) or src is self:
+      raise ValueError("src must be another NativeDenoiser")
+    t = None
+    if truth is not None:
+      t = _f32(truth)
+      want = (self.num_grid_nodes, self.cfg.batch, self._feature_c_src)
+      if t.shape != want:
+        raise ValueError(f"truth must be {want}, got {t.shape}")
+    self._check(self._lib.gc_ens_feature(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
+    self._feature_members = self._ens_members
+
+  def ens_feature_centres(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """-> (count [M + 1, B, D] int32, node [M + 1, B, D, max_centres] int32, value [M + 1, B, D, max_centres] float32) of the
+    last `ens_feature` (gc_ens_feature_centres): field M is the truth; `count` is the true number of centres, of which the
+    first min(count, max_centres) in ascending node index are listed (`value`: the source value, the same bits); the entries
+    behind them read node -1, value 0."""
+    if self._feature_members < 0:
+      raise GencastHipError("libgencast_hip error 4: no centre lists (ens_feature has not run since ens_feature_set)")
+    shape = (self._feature_members + 1, self.cfg.batch, self.cfg.c_out)
+    count = np.empty(shape, np.int32)
+    node = np.empty(shape + (self._feature_max,), np.int32)
+    value = np.empty(shape + (self._feature_max,), np.float32)
+    self._check(self._lib.gc_ens_feature_centres(self._h, _ptr(count, _i32p), _ptr(node, _i32p), _ptr(value, _f32p)))
+    return count, node, value
 
   # -- ensemble order statistics (members sorted on the device) ----------------------------------------
   def ens_order_set(self, probs) -> None:

@@ -14,8 +14,9 @@
 //   gc_multivar.hip  gc_ens_energy_*, gc_ens_variogram_*
 //   gc_tail.hip      gc_ens_tail_*
 //   gc_region.hip    gc_ens_region_*
-// The last ten are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
-// lead times of another).  What they share -- field length, upload through
+//   gc_feature.hip   gc_ens_feature_*
+// The last eleven are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
+// lead times of another, gc_feature.hip with the strike fields of the centres it finds in another).  What they share -- field length, upload through
 // the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
 // relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
 // are a BufferGroup and its events an Event or a Bracket (below); declaring one as a member of the handle is all it takes
@@ -431,6 +432,22 @@ struct gc_handle {
   unsigned long long* d_reg_hist = nullptr;      // [R][B][c_out][M + 1], then [R] skipped points
   gci::Bracket reg_time{events};                 // of the last call
   int64_t reg_calls = 0, reg_device_us = 0, reg_invalid_points = 0;
+
+  // ensemble feature detection (gc_ens_feature_*, gc_feature.hip): the plan, the work of a chunk of fields, the centre lists
+  gci::BufferGroup feat_allocs{groups};           // the plan's tables, one buffer: freed and replaced by gc_ens_feature_set
+  gci::BufferGroup feat_work_allocs{groups};      // the work buffers and the lists: made again by the call that finds their size changed
+  bool feat_set = false;                         // a plan has been set
+  bool feat_listed = false;                      // the lists are those of a call under the current plan
+  int feat_c_src = 0, feat_n_lat = 0, feat_n_lon = 0, feat_max = 0, feat_list_M = 0;
+  double* d_feat_depth = nullptr;                // [c_out]
+  int* d_feat_tab = nullptr;                     // [7][c_out] per-detector tables, then r_lon, ring_lon, strike_lon [c_out][n_lat]
+  unsigned char* d_feat_work = nullptr;          // 8 fields of keys, row minima, flags and block counts; then the lists
+  size_t feat_work_bytes = 0;
+  int *d_feat_count = nullptr, *d_feat_node = nullptr;   // [M + 1][B][c_out], [M + 1][B][c_out][max_centres]: inside d_feat_work
+  float* d_feat_value = nullptr;                 // [M + 1][B][c_out][max_centres]
+  gci::Bracket feat_time{events};                // of the last call
+  gci::Event ev_feat_src{events};                // stream order behind the source handle
+  int64_t feat_calls = 0, feat_device_us = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

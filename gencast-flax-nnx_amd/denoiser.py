@@ -231,6 +231,13 @@ class Denoiser:
       windows[(c_d, str(key))] = nd
     return nd
 
+  def feature_handle(self, c_d: int, key: str) -> _lib.NativeDenoiser:
+    """A graph-only handle like `view_handle`'s with `c_out = c_d` detectors, for ONE `verification.FeatureSpec` (an entry of
+    `EnsembleRollout.run(features=...)`): the destination of `NativeDenoiser.ens_feature`, whose member store then holds the
+    strike fields and which keeps the lists of centres of its last call.  Kept with the window handles, one per (`c_d`,
+    `key`): two entries never share one."""
+    return self.window_handle(c_d, "feature:" + str(key))
+
   def close(self) -> None:
     """Releases every library handle this denoiser made: the view, climatology and window handles, the member lanes and
     `native`."""

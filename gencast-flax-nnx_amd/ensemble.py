@@ -119,6 +119,16 @@ class EnsembleSampler:
     self._one_rank("derived")
     return self._run(inputs, targets, forcings, num_members, None, derived=(spec, events))
 
+  def features(self, inputs, targets, forcings, num_members: int, spec):
+    """Runs the members as `scores` does and looks, on the device, for the features of `spec` (a `verification.FeatureSpec`:
+    cyclone centres as local extrema with a depth test) in every member and in `targets`: `verification.FeatureScores` -- the
+    centres per member and of the truth, the strike-probability map (the ensemble mean of the 0 / 1 strike fields), the
+    `EnsembleScores` of the strike store and its `EventScores` at threshold 0.5.  Only the lists of centres and the
+    probability map are downloaded, no member.  The members are taken as they are sampled, scale 1 and location 0, as in
+    `derived`; `EnsembleRollout.run(features=...)` detects on member STATES, which are fields."""
+    self._one_rank("features")
+    return self._run(inputs, targets, forcings, num_members, None, features=spec)
+
   def order(self, inputs, targets, forcings, num_members: int, probs=(), *, quantile_fields: bool = False):
     """Runs the members as `scores` does and sorts them, point by point, on the device: `verification.OrderScores` in the
     units of `targets` -- the reliability / potential split of the ensemble CRPS (Hersbach 2000), the outlier frequencies
@@ -179,10 +189,12 @@ class EnsembleSampler:
     their order statistics, or, with `climatology` (K Datasets), only their skill against it, or, with `multivariate` (an
     EnergySpec or None, a VariogramSpec or None), only their energy and variogram scores, or, with `tails` (an EventSpec), only
     their threshold-weighted CRPS sums, or, with `regions` (a RegionSpec), only their sums per region, or, with `derived` (a
-    DerivedSpec, an EventSpec or None), only the scores of the derived fields; else they are scored (`scores`), with
+    DerivedSpec, an EventSpec or None), only the scores of the derived fields, or, with `features` (a FeatureSpec), only the
+    centres and the scores of their strike fields; else they are scored (`scores`), with
     `spectral` both.  `asked`: at most one of these keywords (one that is None was not asked for)."""
     asked = {what: arg for what, arg in asked.items() if arg is not None}
     events, order, climatology, tails, regions = (asked.get(k) for k in ("events", "order", "climatology", "tails", "regions"))
+    fspec = asked.get("features")
     (dspec, dev), (energy, variogram) = asked.get("derived", (None, None)), asked.get("multivariate", (None, None))
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
@@ -213,10 +225,10 @@ class EnsembleSampler:
     main = None                                            # lane 0's member store, where anything is scored at all
     if scoring or spectral or asked:
       weights = None if spectral and not scoring else verification.node_weights(template)
-      wq = None if events is None and dev is None else verification.quantize_node_weights(weights)
+      wq = None if events is None and dev is None and fspec is None else verification.quantize_node_weights(weights)
       # (scored once: the thresholds are set by that call, after the members are in; events and derived fields alone need no
       # node weights on the main store)
-      main = verification.ScoredStore(native, num_members, weights if scoring or asked.keys() - {"events", "derived"} else None,
+      main = verification.ScoredStore(native, num_members, weights if scoring or asked.keys() - {"events", "derived", "features"} else None,
                                       events=events, thresholds=None if events is None else events.packed(template), weight_q=wq,
                                       set_per_score=True, order=None if order is None else order[0],
                                       climatology=None if climatology is None
@@ -256,6 +268,18 @@ class EnsembleSampler:
       scores, event_scores = view.score(truth)
       return scores if dev is None else (scores, event_scores)
 
+    def feature_scores():
+      plan, ftemplate, fev = fspec.plan(template), fspec.template(template), fspec.event_spec()
+      view = verification.ScoredStore(self._denoiser.feature_handle(len(plan["channel"]), "single"), num_members, weights,
+                                      events=fev, thresholds=fev.packed(ftemplate), weight_q=wq, feature_plan=plan, source=native,
+                                      set_per_score=True)
+      view.setup()
+      scores, event_scores = view.score(truth, want_fields=True)
+      mean = view.handle.ens_download_fields()[0]
+      members, of_truth = verification.split_centres(view.centres())
+      probability = datasets.like_inputs(Denoiser.unpack_outputs(mean, grid_shape, ftemplate), targets_template, inputs, forcings)
+      return verification.FeatureScores(scores, event_scores, members, of_truth, probability, ftemplate)
+
     def multivariate_scores():
       en = main.score_energy(truth)
       return en, main.score_variogram(truth if en is None else None)      # (the truth is on the device after the first)
@@ -265,7 +289,7 @@ class EnsembleSampler:
       return (scores, as_given(main.quantile_fields())) if order[1] else scores
 
     if asked:                                              # (what was asked for is scored alone)
-      return {"derived": derived_scores, "events": lambda: main.score_events(truth),
+      return {"derived": derived_scores, "features": feature_scores, "events": lambda: main.score_events(truth),
               "climatology": lambda: main.score_climatology([pack(c) for c in climatology], truth),
               "tails": lambda: main.score_tails(truth), "regions": lambda: main.score_regions(truth),
               "multivariate": multivariate_scores, "order": order_scores}[next(iter(asked))]()

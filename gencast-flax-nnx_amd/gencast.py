@@ -185,6 +185,19 @@ class GenCast:
     runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.derived(inputs, targets, forcings, num_members, spec, events)
 
+  def ensemble_features(self, inputs, targets, forcings=None, *, num_members, spec, rngs=0, concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and finds, on the GPU, the features of `spec`
+    (`verification.FeatureSpec`: named detectors, each a local minimum or maximum of one variable over a great-circle
+    radius, with a threshold and a closed-contour depth test) in every member and in `targets`:
+    `verification.FeatureScores` -- `.centres` / `.truth_centres` (lat, lon, value per member and of the truth),
+    `.strike_probability` (the fraction of members with a centre within the strike radius of a place, a Dataset), `.scores`
+    (the `EnsembleScores` of the 0 / 1 strike fields) and `.events` (their `EventScores` at 0.5: Brier score, reliability,
+    ROC area, economic value of the strike probability).  Only the lists and the map leave the device.  The members are
+    taken in the units they are sampled in, as in `ensemble_derived`; under `InputsAndResiduals` a single-step sample is a
+    normalised residual, and that wrapper detects on the member STATES of a one-step `ensemble_rollout` instead."""
+    runner = self._ensemble_sampler(rngs, concurrent_members)
+    return runner.features(inputs, targets, forcings, num_members, spec)
+
   def ensemble_rollout(self, inputs, targets, forcings, horizon, num_members, *, rngs=0, norm=None, concurrent_members=1,
                        device_noise=None, **kwargs):
     """Rolls `num_members` (2..64) members out `horizon` autoregressive steps with every member's context resident on

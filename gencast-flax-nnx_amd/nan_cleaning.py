@@ -153,6 +153,16 @@ class NaNCleaner:
     points the device does not count (`RegionScores.invalid`, per region)."""
     return self.predictor.ensemble_regions(*self._cleaned(inputs, targets, forcings, False), **kwargs)
 
+  def ensemble_features(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """Inputs and forcings are cleaned; the targets pass through unchanged, as in `ensemble_scores`: a NaN of the detection
+    variable is a node that is no centre, is skipped as a neighbour, and is NaN in the strike field (a point the scorers do
+    not count)."""
+    given = (targets, inputs, forcings)
+    out = self.predictor.ensemble_features(*self._cleaned(inputs, targets, forcings, False), **kwargs)
+    if out.strike_probability is not None:
+      out.strike_probability = datasets.like_inputs(datasets.as_dataset(out.strike_probability), *given)
+    return out
+
   def ensemble_spectra(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """Inputs and forcings are cleaned, and so are the targets: a transform cannot skip points, so the spectrum of the
     cleaned variable is that of the field with its NaNs (land points) replaced by the fill value, truth and members

@@ -282,6 +282,17 @@ class InputsAndResiduals:
     per-channel context update -- and scores, spectra and fields come back in physical units."""
     return self.predictor.ensemble_rollout(inputs, targets, forcings, horizon, num_members, norm=self, **kwargs)
 
+  def ensemble_features(self, inputs, targets, forcings=None, *, num_members, spec, **kwargs):
+    """The features of `spec` (`verification.FeatureSpec`, thresholds and depths in physical units) in the members and in
+    `targets`: `verification.FeatureScores`.  A single-step sample is a normalised RESIDUAL here, in which a pressure
+    minimum is no minimum, so the detector runs on the member STATES of a one-step `ensemble_rollout` under this
+    normalisation (`EnsembleRollout.run(features=...)`): the members hold (x - l) / s of the field itself, a monotone map per
+    channel, and thresholds and depths take it."""
+    res = self.ensemble_rollout(inputs, targets, forcings, 1, num_members, features={"features": spec}, **kwargs)
+    part = res.features["features"]
+    members, of_truth = verification.split_centres(part.centres[0])
+    return verification.FeatureScores(part.scores[0], part.events[0], members, of_truth, part.strike_probability[0], part.template)
+
   def ensemble_spectra(self, inputs, targets, forcings=None, **kwargs):
     """`ensemble_spectra` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets,
     in physical units: every power is multiplied by a^2 per channel (`EnsembleSpectra.scaled`; a: the residual scale of
@@ -705,6 +716,29 @@ class DerivedRolloutResult(_SeriesResult):
     return DerivedRolloutResult(template=self.template, **self._merged_series(other))
 
 
+class FeatureRolloutResult(_SeriesResult):
+  """The part of an `EnsembleRolloutResult` that belongs to one entry of `EnsembleRollout.run(features=...)`: per lead time
+  `scores[k]` / `scores_normalized[k]` (`verification.EnsembleScores` of the 0 / 1 strike fields: the same numbers, a strike
+  field has no unit), `events[k]` (`verification.EventScores` at threshold 0.5: Brier score, reliability curve, ROC area and
+  economic value of the strike probability), `centres[k]` ({detector: [B][M + 1] entries} as `verification.unpack_centres`
+  gives them, field M the truth, in physical units), `strike_probability[k]` (a Dataset, one variable per detector: the
+  ensemble mean of the strike fields) and `members[k]` (`[M]` arrays [G, B, D], the strike fields, or None); `template`: the
+  Dataset of the detectors (`FeatureSpec.template`) for `per_variable`.  `order`, `tails` and `regions` as on a
+  `DerivedRolloutResult`."""
+
+  _carried_as, _kind = "derived", "feature results"
+
+  def __init__(self, scores, scores_normalized, events=None, centres=None, strike_probability=None, members=None, template=None,
+               *, quantiles=None, **series):
+    self._set_series(locals(), series)
+    self.centres, self.strike_probability = centres, strike_probability
+    self.members, self.template, self.quantiles = members, template, quantiles
+
+  def merge(self, other: "FeatureRolloutResult") -> "FeatureRolloutResult":
+    """Raw sums and tables add; centres, probability maps and members belong to one date and are dropped."""
+    return FeatureRolloutResult(template=self.template, **self._merged_series(other))
+
+
 class WindowRolloutResult(_SeriesResult):
   """The part of an `EnsembleRolloutResult` that belongs to one entry of `EnsembleRollout.run(windows=...)`.  `leads`: the
   lead times that end a window (`WindowSpec.leads`), `steps`: the window length; per window i, ending at `leads[i]`,
@@ -759,16 +793,23 @@ class EnsembleRolloutResult(_SeriesResult):
   _carried_as = "ensemble"
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
-               derived=None, quantiles=None, windows=None, **series):
+               derived=None, quantiles=None, windows=None, features=None, **series):
     self._set_series(locals(), series)
     self.derived = None if derived is None else dict(derived)
     self.windows = None if windows is None else dict(windows)
+    if features is not None:                              # (as an optional series: absent from `vars(result)` unless asked for)
+      self.features = dict(features)
     self.mean, self.variance, self.members, self.quantiles = mean, variance, members, quantiles
     self.n_members = int(n_members if n_members is not None else self.scores[0].n_members)
 
   @property
   def horizon(self) -> int:
     return len(self.scores)
+
+  def __getattr__(self, name):
+    if name == "features":                                # {name: `FeatureRolloutResult`} of `run(features=...)`, else None
+      return None
+    return super().__getattr__(name)
 
   def merge(self, other: "EnsembleRolloutResult") -> "EnsembleRolloutResult":
     """The result over the union of the start dates, lead time by lead time (`EnsembleScores.merge`,
@@ -781,7 +822,8 @@ class EnsembleRolloutResult(_SeriesResult):
     series = self._merged_series(other)
     return EnsembleRolloutResult(n_members=self.n_members, **series,
                                  derived=_merge_named(self.derived, other.derived, "derived scores", "derived"),
-                                 windows=_merge_named(self.windows, other.windows, "windows", "window"))
+                                 windows=_merge_named(self.windows, other.windows, "windows", "window"),
+                                 features=_merge_named(self.features, other.features, "features", "feature"))
 
 
 class _StoreSeries:
@@ -796,6 +838,8 @@ class _StoreSeries:
                   if row.name == "scores" or getattr(store, row.name, None) is not None for name in row.series}
     self.quantiles = [] if store.order is not None and keep_quantiles else None
     self.members = [] if keep_members else None
+    # a store with a feature plan: per lead time the centres and the strike-probability map
+    self.centres, self.probabilities = ([], []) if getattr(store, "feature_plan", None) is not None else (None, None)
 
   def __getattr__(self, name):
     """`series.tails`, `series.raw_tails`, `series.raw`, `series.clim`, ...: a list of `lists` by its short name (None: the
@@ -842,6 +886,10 @@ class _StoreSeries:
     """The series of the store that a result of class `result` carries, as the keywords of its constructor."""
     return {name: series for name, series in self.lists.items() if name in result._carries()}  # pylint: disable=protected-access
 
+  def feature_result(self) -> FeatureRolloutResult:
+    return FeatureRolloutResult(centres=self.centres, strike_probability=self.probabilities, members=self.members,
+                                template=self.template, quantiles=self.quantiles, **self.carried(FeatureRolloutResult))
+
   def derived_result(self) -> DerivedRolloutResult:
     return DerivedRolloutResult(members=self.members, template=self.template, quantiles=self.quantiles,
                                 **self.carried(DerivedRolloutResult))
@@ -885,6 +933,7 @@ class _EnsembleRun:
     self.means, self.variances = [], []
     self.thresholds = None                                # per EventSpec, in the members' units
     self.views: Dict[str, _StoreSeries] = {}
+    self.features: Dict[str, _StoreSeries] = {}
     self.windows: Dict[str, _WindowEntry] = {}
 
 
@@ -966,7 +1015,7 @@ class EnsembleRollout:
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
           keep_members: bool = False, events=None, derived=None, order=None,
           keep_quantiles: bool = False, climatology=None, windows=None, energy=None,
-          variogram=None, tails=None, regions=None) -> EnsembleRolloutResult:
+          variogram=None, tails=None, regions=None, features=None) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -1028,6 +1077,15 @@ class EnsembleRollout:
     `EnsembleRolloutResult.regions` (`verification.RegionScores` in physical units, `regions[k][name]` an `EnsembleScores`),
     `regions_normalized` as the device returned them, and the same on the results of the named entries.  Without `regions`
     nothing changes.
+    `features`: {name: `verification.FeatureSpec`}: per lead time, after the derived entries, the member states and the truth
+    go through `gc_ens_feature` into the store of a handle of the entry's own (`Denoiser.feature_handle`) -- the centres of
+    every detector (cyclone centres: a local extremum with a threshold and a closed-contour depth test, in physical units)
+    as lists, and as 0 / 1 strike fields, which are scored there like a `derived` entry with the same node weights and with
+    the event `strike > 0.5`: `EnsembleRolloutResult.features[name]` (`FeatureRolloutResult`: `scores[k]`, `events[k]`,
+    `centres[k]`, `strike_probability[k]`).  `order`, and `tails` / `regions` under the entry's name, reach it; `energy`,
+    `variogram` and `climatology` do not.  A window may name it as its source: `WindowSpec("max", L, source=name)` is a strike
+    within L steps, the track-probability map.  `verification.link_tracks` links the centres of a member over the lead times.
+    Without `features` nothing changes.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -1042,8 +1100,11 @@ class EnsembleRollout:
       raise ValueError("EnsembleRollout needs all members on one rank (world_size == 1): bring the other "
                        "ranks' members over and push them with NativeDenoiser.ens_push_host")
     for name, (wspec, _) in _spec_entries(windows).items():
-      if wspec.source is not None and wspec.source not in (derived or {}):
-        raise ValueError(f"window {name!r}: its source {wspec.source!r} names no entry of `derived` ({sorted(derived or {})})")
+      if wspec.source is not None and wspec.source not in (derived or {}) and wspec.source not in (features or {}):
+        raise ValueError(f"window {name!r}: its source {wspec.source!r} names no entry of `derived` ({sorted(derived or {})})"
+                         + (f" or `features` ({sorted(features)})" if features else ""))
+    if set(derived or {}) & set(features or {}):
+      raise ValueError(f"derived and features share the names {sorted(set(derived or {}) & set(features or {}))}")
     given = (targets, inputs, forcings)
     inputs, targets, forcings = (datasets.as_dataset(x) for x in (inputs, targets, forcings))
     M = int(num_members)
@@ -1059,12 +1120,12 @@ class EnsembleRollout:
         raise ValueError(f"energy: the groups {sorted(set(energy.names) - fitted)} name variables that no scored store has all of")
     if init_noise is not None and (len(init_noise) != M or any(len(z) < horizon for z in init_noise)):
       raise ValueError("init_noise must be [num_members][horizon] fields")
-    known = set(derived or {}) | set(windows or {})
+    known = set(derived or {}) | set(windows or {}) | set(features or {})
     per_store = {arg: _per_store(arg, spec, known) for arg, spec in (("tails", tails), ("regions", regions))}
     run = self._setup(inputs, targets, forcings, horizon, M, context_steps=context_steps, init_noise=init_noise,
                       spectra=spectra, lmax=lmax, fields=fields, keep_members=keep_members, events=events, derived=derived,
                       order=order, keep_quantiles=keep_quantiles, climatology=climatology, windows=windows, energy=energy,
-                      variogram=variogram, per_store=per_store)
+                      variogram=variogram, per_store=per_store, features=features)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -1077,10 +1138,12 @@ class EnsembleRollout:
                                  members=main.members, n_members=M, quantiles=main.quantiles,
                                  derived=None if derived is None else {k: v.derived_result() for k, v in run.views.items()},
                                  windows=None if windows is None else {k: v.result() for k, v in run.windows.items()},
+                                 features=None if features is None else {k: v.feature_result() for k, v in run.features.items()},
                                  spectra=run.spectra, spectra_normalized=run.raw_spectra, **main.carried(EnsembleRolloutResult))
 
   def _setup(self, inputs, targets, forcings, horizon, M, *, context_steps, init_noise, spectra, lmax, fields, keep_members,
-             events, derived, order, keep_quantiles, climatology, windows, energy, variogram, per_store) -> "_EnsembleRun":
+             events, derived, order, keep_quantiles, climatology, windows, energy, variogram, per_store,
+             features=None) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views.  The
     keywords are `run`'s own; `per_store`: {argument given per store ("tails", "regions"): {store name: spec} or None}."""
     run = _EnsembleRun()
@@ -1137,7 +1200,7 @@ class EnsembleRollout:
 
     weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
     wq = None
-    if (events is not None or any(dev is not None for _, dev in entries.values())
+    if (events is not None or features or any(dev is not None for _, dev in entries.values())
         or any(wev is not None for _, wev in wentries.values())):
       wq = verification.quantize_node_weights(weights)
     specs = None
@@ -1204,10 +1267,24 @@ class EnsembleRollout:
       store.set_per_score = sum(1 for v in run.views.values() if v.store.handle is store.handle) > 1
       store.setup()
 
+    for name, fspec in (features or {}).items():
+      # a handle of its own per entry (it keeps the lists of its last call); the strike fields are 0 / 1: scale 1, location 0
+      fplan, ftemplate, fev = fspec.plan(template0, scale, loc), fspec.template(template0), fspec.event_spec()
+      fscale, floc = fspec.channel_stats(template0, scale, loc)
+      store = verification.ScoredStore(den.feature_handle(len(fplan["channel"]), name), M, weights, events=fev,
+                                       thresholds=fev.packed(ftemplate), weight_q=wq, feature_plan=fplan, source=native,
+                                       order=order, **per_store_args(name, ftemplate, fscale, floc))
+      run.features[name] = _StoreSeries(store, fscale, ftemplate, keep_members=keep_members, keep_quantiles=keep_quantiles)
+      store.setup()
+
     for name, (wspec, wev) in wentries.items():
       # the source's channels, their statistics and their names; the window maps the statistics once more
       if wspec.source is None:
         source, stemplate, sscale, sloc = native, template0, scale, loc
+      elif wspec.source in run.features:
+        fspec = features[wspec.source]
+        source, stemplate = run.features[wspec.source].store.handle, fspec.template(template0)
+        sscale, sloc = fspec.channel_stats(template0, scale, loc)
       else:
         dspec = entries[wspec.source][0]
         source, stemplate = run.views[wspec.source].store.handle, dspec.template(template0)
@@ -1285,6 +1362,18 @@ class EnsembleRollout:
       v.score_lead(None, n_samples=None if samples is None else len(samples), source_truth=truth)
       for w in run.windows.values():                      # (two views may share a handle: the view's fields are there NOW)
         if w.spec.source == vname:
+          w.push()
+    for fname, f in run.features.items():
+      # members and truth, device to device; then the lists of centres and the ensemble mean of the strike fields
+
+      def centres_and_probability(f=f):
+        f.centres.append(f.store.centres())
+        mean = f.store.handle.ens_download_fields()[0]
+        f.probabilities.append(Denoiser.unpack_outputs(mean, run.grid_shape, f.template))
+
+      f.score_lead(None, want_fields=True, after_score=centres_and_probability)
+      for w in run.windows.values():
+        if w.spec.source == fname:
           w.push()
     for w in run.windows.values():
       w.finish_lead(k)

@@ -1087,6 +1087,279 @@ class DerivedSpec:
 
 
 # ---------------------------------------------------------------------------------------------
+# feature detection: cyclone centres, strike fields, tracks (gc_ens_feature_*)
+# ---------------------------------------------------------------------------------------------
+_EARTH_RADIUS_KM = 6371.0
+_FEATURE_KEYS = ("variable", "level", "kind", "radius_km", "threshold", "ring_km", "depth", "strike_km")
+
+
+class FeaturePlan(dict):
+  """The keyword arguments of `NativeDenoiser.ens_feature_set` (a dict), and beside them what turns a list of centres into
+  physical units: `names` [D] (the detectors in channel order), `lat`, `lon` (the grid's coordinates) and `scale`, `loc` [D]
+  (a listed value x is `x * scale + loc` in physical units)."""
+  names: Tuple[str, ...] = ()
+  lat = lon = scale = loc = None
+
+
+class FeatureSpec:
+  """What `gc_ens_feature` looks for in a member store: named detectors, each a local extremum of one
+  channel with a depth test, whose centres come back as lists and as 0 / 1 strike fields -- one derived variable per
+  detector, named like it, which every scorer reads as it is (its ensemble mean is the strike probability).
+
+  `detectors`: {name: dict(variable=, level=None, kind="min" | "max", radius_km=, threshold=None, ring_km=None, depth=None,
+  strike_km=)}, 1 to 8 of them.  `variable`: a target variable; `level`: the index of its level (None: a surface variable).
+  `radius_km`: the centre is the extremum of the window of that great-circle radius (`DerivedSpec.window`); `ring_km`,
+  `depth`: the smallest value on the boundary of the window of radius `ring_km` lies at least `depth` above the centre (for
+  a maximum: below) -- a closed low; `threshold`: the centre's value is at most (for a maximum: at least) this;
+  `strike_km`: a node is struck by a centre within this radius.  Every radius is a number of km, or the window itself as
+  (r_lat, r_lon) with r_lon one integer or one per latitude row.  Thresholds and depths are in physical units.
+  `max_centres` (1..1024): the entries a list keeps; the count and the strike field see all centres."""
+
+  def __init__(self, detectors: Mapping[str, Mapping[str, object]], max_centres: int = 64):
+    self.detectors = {str(k): dict(v) for k, v in detectors.items()}
+    if not 1 <= len(self.detectors) <= 8:
+      raise ValueError(f"a FeatureSpec holds 1 to 8 detectors, got {len(self.detectors)}")
+    if isinstance(max_centres, bool) or int(max_centres) != max_centres or not 1 <= int(max_centres) <= 1024:
+      raise ValueError(f"max_centres must be an integer in 1 .. 1024, got {max_centres!r}")
+    self.max_centres = int(max_centres)
+    for name, det in self.detectors.items():
+      unknown = set(det) - set(_FEATURE_KEYS)
+      if unknown:
+        raise ValueError(f"detector {name!r}: unknown keys {sorted(unknown)} (known: {list(_FEATURE_KEYS)})")
+      if "variable" not in det:
+        raise ValueError(f"detector {name!r} names no variable")
+      det.setdefault("kind", "min")
+      if det["kind"] not in ("min", "max"):
+        raise ValueError(f"detector {name!r}: kind must be 'min' or 'max', got {det['kind']!r}")
+      for key in ("radius_km", "strike_km"):
+        if det.get(key) is None:
+          raise ValueError(f"detector {name!r} needs {key}")
+      for key in ("radius_km", "strike_km", "ring_km"):
+        r = det.get(key)
+        if r is not None and not isinstance(r, (tuple, list)) and not (math.isfinite(float(r)) and float(r) >= 0.0):
+          raise ValueError(f"detector {name!r}: {key} must be finite and >= 0")
+        if isinstance(r, (tuple, list)) and (len(r) != 2 or int(r[0]) < 0):
+          raise ValueError(f"detector {name!r}: {key} as a window is (r_lat >= 0, r_lon)")
+      if det.get("depth") is not None and det.get("ring_km") is None:
+        raise ValueError(f"detector {name!r}: a depth needs ring_km")
+      if det.get("ring_km") is not None and det.get("depth") is None:
+        raise ValueError(f"detector {name!r}: ring_km needs a depth")
+      for key in ("threshold", "depth"):
+        if det.get(key) is not None and not math.isfinite(float(det[key])):
+          raise ValueError(f"detector {name!r}: {key} must be finite")
+      ring, radius = det.get("ring_km"), det["radius_km"]
+      if ring is not None and not isinstance(ring, (tuple, list)) and not isinstance(radius, (tuple, list)) and float(ring) <= float(radius):
+        raise ValueError(f"detector {name!r}: the ring ({ring} km) must be larger than the extremum radius ({radius} km)")
+
+  @property
+  def names(self) -> List[str]:
+    """The detectors in the channel order of the strike store: sorted, as every Dataset here is packed."""
+    return sorted(self.detectors)
+
+  def _channel(self, template0, name: str) -> int:
+    """The source channel of detector `name` in the packed order of `template0`."""
+    det = self.detectors[name]
+    where = {v: (off, n) for v, off, n in datasets.channel_layout(template0)}
+    if det["variable"] not in where:
+      raise ValueError(f"detector {name!r}: {det['variable']!r} is not a target variable")
+    off, n = where[det["variable"]]
+    level = det.get("level")
+    if level is None:
+      if n != 1:
+        raise ValueError(f"detector {name!r}: {det['variable']!r} has {n} levels: name one (level=index)")
+      return off
+    if isinstance(level, bool) or int(level) != level or not 0 <= int(level) < n:
+      raise ValueError(f"detector {name!r}: level {level!r} outside 0 .. {n - 1}")
+    return off + int(level)
+
+  def template(self, template0) -> datasets.Dataset:
+    """A Dataset with one variable per detector (zeros), with the dims of a surface variable -- the source's without its
+    level -- and the source's coordinates: `EventSpec.packed` and every `per_variable` work on it unchanged."""
+    template0 = datasets.as_dataset(template0)
+    out = {}
+    for name in self.names:
+      self._channel(template0, name)
+      src = template0[self.detectors[name]["variable"]]
+      data = np.asarray(src.data)
+      if "level" in src.dims:
+        data = np.take(data, 0, axis=src.dims.index("level"))
+      out[name] = datasets.Variable(tuple(d for d in src.dims if d != "level"), np.zeros_like(data))
+    return datasets.Dataset(out, template0.coords)
+
+  @staticmethod
+  def _window(given, lat, lon) -> Tuple[int, np.ndarray]:
+    if not isinstance(given, (tuple, list)):
+      return DerivedSpec.window(lat, lon, float(given))
+    r_lon = np.asarray(given[1], dtype=np.int64)
+    r_lon = np.full(len(lat), int(r_lon), np.int64) if r_lon.ndim == 0 else r_lon.reshape(-1)
+    if r_lon.shape != (len(lat),):
+      raise ValueError(f"r_lon must be one integer or one per latitude row ({len(lat)}), got {r_lon.shape}")
+    if np.any((r_lon < 0) | (r_lon > (len(lon) - 1) // 2)):
+      raise ValueError(f"r_lon must lie in 0 .. {(len(lon) - 1) // 2}")
+    return int(given[0]), r_lon.astype(np.int32)
+
+  def plan(self, template0, scale=None, loc=None) -> FeaturePlan:
+    """The keyword arguments of `NativeDenoiser.ens_feature_set`, as a `FeaturePlan`.  `scale`, `loc` [c_src]: the members
+    hold (x - loc) / scale per source channel (None: 1 and 0); a threshold t becomes (t - loc) / scale and a depth
+    depth / scale of the detector's channel (scale > 0: a minimum stays a minimum)."""
+    template0 = datasets.as_dataset(template0)
+    c_src = sum(n for _, _, n in datasets.channel_layout(template0))
+    scale = np.ones(c_src) if scale is None else np.asarray(scale, np.float64).reshape(-1)
+    loc = np.zeros(c_src) if loc is None else np.asarray(loc, np.float64).reshape(-1)
+    if scale.shape != (c_src,) or loc.shape != (c_src,):
+      raise ValueError(f"scale and loc must have shape ({c_src},)")
+    if not np.all(scale > 0.0):
+      raise ValueError("scale must be positive")
+    sizes = template0.sizes
+    if "lat" not in sizes or "lon" not in sizes:
+      raise ValueError("template must have 'lat' and 'lon' dimensions")
+    lat, lon = np.asarray(template0.coords["lat"], np.float64), np.asarray(template0.coords["lon"], np.float64)
+    n_lat, n_lon = int(sizes["lat"]), int(sizes["lon"])
+    names = self.names
+    D = len(names)
+    zeros = np.zeros(n_lat, np.int32)
+    out = FeaturePlan(c_src=c_src, channel=np.zeros(D, np.int32), direction=np.zeros(D, np.int32),
+                      use_threshold=np.zeros(D, np.int32), threshold=np.zeros(D, np.float32), n_lat=n_lat, n_lon=n_lon,
+                      r_lat=np.zeros(D, np.int32), r_lon=np.zeros((D, n_lat), np.int32), ring_lat=np.zeros(D, np.int32),
+                      ring_lon=np.zeros((D, n_lat), np.int32), depth=np.zeros(D, np.float64), strike_lat=np.zeros(D, np.int32),
+                      strike_lon=np.zeros((D, n_lat), np.int32), max_centres=self.max_centres)
+    for d, name in enumerate(names):
+      det = self.detectors[name]
+      ch = self._channel(template0, name)
+      out["channel"][d] = ch
+      out["direction"][d] = -1 if det["kind"] == "min" else 1
+      if det.get("threshold") is not None:
+        out["use_threshold"][d] = 1
+        out["threshold"][d] = np.float32((float(det["threshold"]) - loc[ch]) / scale[ch])
+      out["r_lat"][d], out["r_lon"][d] = self._window(det["radius_km"], lat, lon)
+      out["strike_lat"][d], out["strike_lon"][d] = self._window(det["strike_km"], lat, lon)
+      if det.get("ring_km") is not None:
+        ring_lat, ring_lon = self._window(det["ring_km"], lat, lon)
+        if ring_lat <= int(out["r_lat"][d]):
+          raise ValueError(f"detector {name!r}: the ring (r_lat {ring_lat}) is not larger than the extremum radius "
+                           f"(r_lat {int(out['r_lat'][d])}) on this grid")
+        out["ring_lat"][d], out["ring_lon"][d] = ring_lat, ring_lon
+        out["depth"][d] = float(det["depth"]) / scale[ch]
+      else:
+        out["ring_lon"][d] = zeros
+    out.names, out.lat, out.lon = tuple(names), lat, lon
+    out.scale, out.loc = scale[out["channel"]], loc[out["channel"]]
+    return out
+
+  def channel_stats(self, template0=None, scale=None, loc=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(scale_d, loc_d) [D]: a strike field is 0 / 1 whatever the units of its source: (1, 0)."""
+    del template0, scale, loc
+    return np.ones(len(self.detectors)), np.zeros(len(self.detectors))
+
+  def event_spec(self) -> "EventSpec":
+    """The one event of every strike field, `value > 0.5`: the Brier score, reliability curve, ROC area and economic value
+    of the strike probability."""
+    return EventSpec({name: np.array([0.5]) for name in self.names}, [1])
+
+
+def unpack_centres(count, node, value, plan=None) -> Dict[str, list]:
+  """The arrays of `NativeDenoiser.ens_feature_centres` as {detector: [B][M + 1] entries}, field M the truth; an entry is
+  dict(count=the true number, node=, lat=, lon=, value=) over the listed centres, ascending in node.  With a `FeaturePlan`
+  lat, lon and value are physical (degrees; `x * scale + loc`); with a plain plan they are the row, the column and the
+  value in the members' units."""
+  count, node, value = np.asarray(count), np.asarray(node), np.asarray(value)
+  n_lon = int(plan["n_lon"]) if plan is not None else None
+  names = getattr(plan, "names", None) or tuple(str(d) for d in range(count.shape[2]))
+  physical = getattr(plan, "lat", None) is not None
+  out = {}
+  for d, name in enumerate(names):
+    out[name] = []
+    for b in range(count.shape[1]):
+      row = []
+      for z in range(count.shape[0]):
+        k = min(int(count[z, b, d]), node.shape[-1])
+        at, x = node[z, b, d, :k].astype(np.int64), value[z, b, d, :k]
+        i, j = (at // n_lon, at % n_lon) if n_lon else (at, np.zeros_like(at))
+        if physical:
+          entry = dict(lat=plan.lat[i], lon=plan.lon[j], value=x.astype(np.float64) * plan.scale[d] + plan.loc[d])
+        else:
+          entry = dict(lat=i, lon=j, value=x.copy())
+        row.append(dict(count=int(count[z, b, d]), node=at, **entry))
+      out[name].append(row)
+  return out
+
+
+def great_circle_km(lat_a, lon_a, lat_b, lon_b) -> np.ndarray:
+  """The great-circle distance (haversine, mean Earth radius 6371 km) between points in degrees; broadcasts."""
+  pa, pb = np.deg2rad(np.asarray(lat_a, np.float64)), np.deg2rad(np.asarray(lat_b, np.float64))
+  dl = np.deg2rad(np.asarray(lon_b, np.float64) - np.asarray(lon_a, np.float64))
+  h = np.sin((pb - pa) / 2.0) ** 2 + np.cos(pa) * np.cos(pb) * np.sin(dl / 2.0) ** 2
+  return 2.0 * _EARTH_RADIUS_KM * np.arcsin(np.sqrt(np.clip(h, 0.0, 1.0)))
+
+
+def link_tracks(centres_per_lead, max_km: float) -> List[List[Tuple[int, float, float, float]]]:
+  """Greedy linking of the centres of ONE member (or the truth) and ONE detector over lead times into tracks, on the host.
+  `centres_per_lead[k]`: dict(lat=, lon=, value=[, node=]) of lead k (an entry of `unpack_centres`; without `node` the
+  position in the list stands in).  Between every two consecutive leads all pairs within `max_km` great-circle distance
+  are formed and taken in ascending distance -- ties by ascending node index of the earlier centre, then of the later --
+  each centre being used at most once on either side.  -> the tracks, each a list of (lead, lat, lon, value), in the order
+  of their first centre (lead, then node).  Pure NumPy, deterministic."""
+  if not (float(max_km) >= 0.0 and math.isfinite(float(max_km))):
+    raise ValueError("max_km must be finite and >= 0")
+  leads = []
+  for c in centres_per_lead:
+    lat, lon = np.asarray(c["lat"], np.float64).reshape(-1), np.asarray(c["lon"], np.float64).reshape(-1)
+    val = np.asarray(c["value"], np.float64).reshape(-1)
+    node = np.asarray(c["node"], np.int64).reshape(-1) if c.get("node") is not None else np.arange(lat.size)
+    if not lat.size == lon.size == val.size == node.size:
+      raise ValueError("lat, lon, value and node of a lead must have equal lengths")
+    leads.append((lat, lon, val, node))
+  nxt = [np.full(l[0].size, -1, np.int64) for l in leads]          # per centre: its successor at the next lead
+  has_prev = [np.zeros(l[0].size, bool) for l in leads]
+  for k in range(len(leads) - 1):
+    (la, lo, _, na), (lb, lob, _, nb) = leads[k], leads[k + 1]
+    if la.size == 0 or lb.size == 0:
+      continue
+    dist = great_circle_km(la[:, None], lo[:, None], lb[None, :], lob[None, :])
+    a, b = np.nonzero(dist <= float(max_km))
+    for p in np.lexsort((nb[b], na[a], dist[a, b])):               # distance, then the earlier node, then the later
+      if nxt[k][a[p]] < 0 and not has_prev[k + 1][b[p]]:
+        nxt[k][a[p]] = b[p]
+        has_prev[k + 1][b[p]] = True
+  tracks = []
+  for k, (lat, lon, val, node) in enumerate(leads):
+    for c in np.argsort(node, kind="stable"):
+      if has_prev[k][c]:
+        continue
+      track, kk, cc = [], k, int(c)
+      while cc >= 0:
+        track.append((kk, float(leads[kk][0][cc]), float(leads[kk][1][cc]), float(leads[kk][2][cc])))
+        cc, kk = int(nxt[kk][cc]), kk + 1
+      tracks.append(track)
+  return tracks
+
+
+class FeatureScores:
+  """What `GenCast.ensemble_features` returns.  `centres`: {detector: [B][M] entries}, `truth_centres`: {detector: [B]
+  entries}, an entry dict(count=, node=, lat=, lon=, value=) (`unpack_centres`); `strike_probability`: a Dataset with one
+  variable per detector, the fraction of members that put a centre within the strike radius of a node (NaN where a source
+  value is not finite); `scores`: the `EnsembleScores` of the strike store; `events`: its `EventScores` at threshold 0.5 --
+  Brier score, reliability curve, ROC area and `economic_value` of the strike probability against where the truth had one;
+  `template`: the Dataset of the detectors for `per_variable`."""
+
+  def __init__(self, scores, events, centres=None, truth_centres=None, strike_probability=None, template=None):
+    self.scores, self.events, self.template = scores, events, template
+    self.centres, self.truth_centres, self.strike_probability = centres, truth_centres, strike_probability
+
+  @classmethod
+  def merge(cls, parts: Sequence["FeatureScores"]) -> "FeatureScores":
+    """Over several dates: the raw sums and the tables add; centres and the probability map belong to one date."""
+    parts = list(parts)
+    return cls(EnsembleScores.merge([p.scores for p in parts]), EventScores.merge([p.events for p in parts]),
+               template=parts[0].template)
+
+
+def split_centres(unpacked: Dict[str, list]) -> Tuple[Dict[str, list], Dict[str, list]]:
+  """{detector: [B][M + 1]} -> ({detector: [B][M]} of the members, {detector: [B]} of the truth)."""
+  return ({k: [row[:-1] for row in v] for k, v in unpacked.items()}, {k: [row[-1] for row in v] for k, v in unpacked.items()})
+
+
+# ---------------------------------------------------------------------------------------------
 # time windows: accumulations, means, changes and extremes over lead times (gc_ens_window_*)
 # ---------------------------------------------------------------------------------------------
 _WINDOW_KINDS = {"sum": 0, "mean": 0, "change": 0, "linear": 0, "max": 1, "min": 2}
@@ -1494,7 +1767,8 @@ class ScoredStore:
   """The member store of one handle and everything that is scored from it: the M members it holds, the node weights
   (None: `ens_score` is not used on it), optionally the events counted on it -- an `EventSpec`, its packed `thresholds`
   in the members' units and `weight_q` = `quantize_node_weights(...)` -- and optionally the `plan` (`DerivedSpec.plan`) that
-  fills it from the store of a `source` handle (`ens_derive`), and optionally `order`: the probabilities of the quantile
+  fills it from the store of a `source` handle (`ens_derive`), or instead the `feature_plan` (`FeatureSpec.plan`) that fills
+  it with the strike fields of the centres found in the source's store (`ens_feature`; `centres()` has the lists), and optionally `order`: the probabilities of the quantile
   fields `score_order` leaves on the device next to its `OrderScores`, optionally `energy` and `variogram`: the plans
   (`EnergySpec.plan`, `VariogramSpec.plan`) of `score_energy` and `score_variogram`, and optionally `climatology`: a second handle of the
   same graph, batch and c_out (`Denoiser.climatology_handle`) whose member store takes the K climatological samples
@@ -1508,7 +1782,7 @@ class ScoredStore:
   a handle, or thresholds that change from call to call (assign `thresholds` before the call)."""
 
   def __init__(self, handle, n_members: int, node_weight=None, *, plan=None, source=None, set_per_score: bool = False,
-               climatology=None, climatology_source=None, **scorers):
+               climatology=None, climatology_source=None, feature_plan=None, **scorers):
     """`scorers`: per row of `SCORERS` with a `score`, its name (what switches it on) and its settings, None by default."""
     for row in (r for r in SCORERS if r.score is not None):
       for key in (row.name,) + row.settings:
@@ -1521,10 +1795,13 @@ class ScoredStore:
       raise ValueError("a climatology source goes with a climatology handle and a derive plan")
     if self.events is not None and self.weight_q is None:
       raise ValueError("events need the quantised node weights (quantize_node_weights)")
-    if (plan is None) != (source is None):
-      raise ValueError("a derive plan and its source handle go together")
+    if plan is not None and feature_plan is not None:
+      raise ValueError("a store is filled by a derive plan or by a feature plan, not both")
+    if (plan is None and feature_plan is None) != (source is None):
+      raise ValueError("a derive plan (or a feature plan) and its source handle go together")
     self.handle, self.n_members, self.node_weight = handle, int(n_members), node_weight
     self.plan, self.source, self.set_per_score = plan, source, bool(set_per_score)
+    self.feature_plan = feature_plan
     if self.order is not None:
       self.order = tuple(float(p) for p in np.asarray(self.order, dtype=np.float64).reshape(-1))
     self.climatology, self.climatology_source = climatology, climatology_source
@@ -1539,6 +1816,8 @@ class ScoredStore:
   def _set_plan(self) -> None:
     if self.plan is not None:
       self.handle.ens_derive_set(**self.plan)
+    if self.feature_plan is not None:
+      self.handle.ens_feature_set(**self.feature_plan)
 
   def configure(self) -> None:
     """The plan, then every scorer that is switched on, in the order of `SCORERS` -- the thresholds, the probabilities, the
@@ -1623,18 +1902,30 @@ class ScoredStore:
     sums, counts, invalid = self.handle.ens_clim_score(self.climatology, truth)
     return ClimatologyScores(sums, counts, self.n_members, K, invalid)
 
+  def centres(self) -> Dict[str, list]:
+    """The centres the last `score` found on a store with a `feature_plan` (`ens_feature_centres`), as `unpack_centres`
+    gives them: {detector: [B][M + 1] entries}, field M the truth; with a `FeaturePlan` in physical units."""
+    if self.feature_plan is None:
+      raise ValueError("centres: the store has no feature plan")
+    return unpack_centres(*self.handle.ens_feature_centres(), self.feature_plan)
+
   def quantile_fields(self) -> List[np.ndarray]:
     """The Q quantile fields [G, B, c_out] of the last `score_order`, downloaded."""
     return [self.handle.ens_order_quantile(q) for q in range(len(self.order or ()))]
 
   def score(self, truth=None, want_fields: bool = False) -> Tuple[EnsembleScores, Optional["EventScores"]]:
     """-> (raw `EnsembleScores`, `EventScores` or None).  `truth` [G, B, c_out] in the members' units, None: the truth
-    already on the device; with a plan the store is first filled from the source's (members and truth, device to
-    device) and `truth` [G, B, c_src] is the SOURCE's."""
+    already on the device; with a plan (or a feature plan) the store is first filled from the source's (members and truth,
+    device to device) and `truth` [G, B, c_src] is the SOURCE's."""
     if self.plan is not None:
       if self.set_per_score:
         self._set_plan()
       self.handle.ens_derive(self.source, truth)
+      truth = None
+    if self.feature_plan is not None:
+      if self.set_per_score:
+        self._set_plan()
+      self.handle.ens_feature(self.source, truth)
       truth = None
     sums, hist = self.handle.ens_score(truth, want_fields=want_fields)
     return EnsembleScores(sums, hist, self.n_members), self.score_events(None)

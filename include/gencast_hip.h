@@ -852,6 +852,57 @@ int gc_ens_region_score(gc_handle* h, const float* truth /* NULL = the truth upl
                         uint64_t* invalid /* [R], NULL allowed */);
 
 /*
+ * Ensemble feature detection on the device: where each member, and the truth, puts a weather
+ * system.  Per field of the store of a source handle `src` and per detector d < D, the CENTRES -- local extrema of one
+ * source channel that pass a threshold and a ring (depth) test -- as a sparse list, and as a dense 0 / 1 STRIKE field in
+ * the store of the destination handle `dst` (c_out == D, the same device, G and batch; it needs gc_set_graph only), which
+ * every scorer of the library reads as it is: its ensemble mean is the strike-probability map.  The reference project
+ * has no tracker; the yardstick is the definition below, restated in tests/feature_reference.py.
+ * Per field z (a member, or the truth), batch entry b and detector d, on the grid node = lat_i n_lon + lon_j:
+ *   signed value  x = the source value at channel[d]; s = x for direction[d] < 0 (a minimum), s = -x for direction[d] > 0
+ *   window        window(n; r_lat, r_lon) = Win(i, j) of gc_ens_derive_set: rows |i' - i| <= r_lat clipped at the poles,
+ *                 circular |j' - j| <= r_lon[i'] in row i'
+ *   extremum      s[n] is finite, and for every other n' of window(n; r_lat[d], r_lon[d]) with finite s[n']: s[n] < s[n'],
+ *                 or s[n] == s[n'] and n < n' (IEEE comparison: -0.0 == +0.0); non-finite neighbours are skipped
+ *   threshold     where use_threshold[d]: s[n] <= t, t = threshold[d] for a minimum, -threshold[d] for a maximum
+ *   ring          where ring_lat[d] > 0: the boundary of window(n; ring_lat[d], ring_lon[d]) -- the rows i +- ring_lat that
+ *                 exist over all |t| <= ring_lon[i'], and in every row strictly between them the two nodes t = +-ring_lon[i'] --
+ *                 holds a finite value and (double) min_finite_ring(s) - (double) s[n] >= depth[d] (one double subtraction)
+ *   centre        an extremum that passes the tests that are enabled
+ *   list          the centres in ascending node index; count is their true number, the first max_centres are kept (node,
+ *                 and value = x, the same bits); entries past the last centre read node -1, value 0
+ *   strike field  dst channel d at node n: 1.0f if any centre (listed or not) lies in window(n; strike_lat[d],
+ *                 strike_lon[d]), else 0.0f; NaN where the source value at n is not finite
+ *   gc_ens_feature_set      the plan on dst.  D must equal dst's c_out, 1 <= D <= 8; max_centres in 1..1024; thresholds and
+ *                           depths in the members' units.  Needs gc_set_graph only; through pinned staging; replaces an
+ *                           earlier plan ("device_allocations" stays flat), survives gc_ens_reserve, released by gc_destroy.
+ *                           GC_ERR_STATE: no graph.  GC_ERR_INVALID_ARGUMENT: a null pointer, c_src < 1, D, n_lat n_lon != G,
+ *                           max_centres, a channel outside [0, c_src), direction 0, a threshold in use or a depth of a ring
+ *                           in use that is not finite, a negative r_lat / ring_lat / strike_lat, a *_lon outside
+ *                           0 .. (n_lon - 1) / 2.  GC_ERR_UNSUPPORTED: a row that does not fit the 64 KB of LDS of the row
+ *                           pass (n_lon > 4096).
+ *   gc_ens_feature          every slot of dst's store becomes the member's strike fields and counts as pushed, dst's truth
+ *                           buffer the truth's; dst's event codes, mean / variance fields and order statistics count as
+ *                           not computed.  truth, the stream order and every error as gc_ens_derive.  Synchronous.
+ *   gc_ens_feature_centres  the lists of the last gc_ens_feature, field M = the truth.  GC_ERR_STATE: no call since the
+ *                           plan was set.
+ * Launches per chunk of at most 8 of the M + 1 fields: a gather of the detection channel into dense 64-bit keys (value
+ * order above node index), a row pass (window minimum along the longitude in LDS), a column pass (extremum, threshold, ring,
+ * strike rectangles) and a list pass.  Integer comparisons and one double subtraction, no float atomics: the same call
+ * twice returns identical bytes.  Nothing else on either handle is touched.  Counters: "ens_feature_calls",
+ * "ens_feature_device_us" (HIP-event time of the last call's launches).
+ */
+int gc_ens_feature_set(gc_handle* dst, int32_t c_src, int32_t D, const int32_t* channel /* [D] */,
+                       const int32_t* direction /* [D] < 0 minimum, > 0 maximum */, const int32_t* use_threshold /* [D] */,
+                       const float* threshold /* [D] */, int32_t n_lat, int32_t n_lon, const int32_t* r_lat /* [D] */,
+                       const int32_t* r_lon /* [D][n_lat] */, const int32_t* ring_lat /* [D], 0 = no ring test */,
+                       const int32_t* ring_lon /* [D][n_lat] */, const double* depth /* [D] */,
+                       const int32_t* strike_lat /* [D] */, const int32_t* strike_lon /* [D][n_lat] */, int32_t max_centres);
+int gc_ens_feature(gc_handle* dst, gc_handle* src, const float* truth /* [G,B,c_src] host, NULL = src's last truth */);
+int gc_ens_feature_centres(gc_handle* dst, int32_t* count /* [M + 1][B][D] */, int32_t* node /* [M + 1][B][D][max_centres] */,
+                           float* value /* [M + 1][B][D][max_centres] */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
