@@ -108,7 +108,7 @@ int gc_device_pci_bus_id(int32_t device_id, char* out, int64_t cap) {
 const char* gc_last_error(const gc_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 // The environment switches, all read here, once per handle (gc_create).  GC_PRECISION and GC_TUNE_GRAPH set the
-// defaults of gc_set_option's "precision" and "graphs"; M2G_FUSE_SUM, EMBED_CACHE, ATTN_ITEMS, MLP_PAIR and A16 select
+// defaults of gc_set_option's "precision" and "graphs"; M2G_FUSE_SUM, EMBED_CACHE, ATTN_ITEMS, MLP_PAIR, EDGE_TERMS and A16 select
 // the other form of a fused path (the tests' bit-identity references); GRAPH_SERIALIZE and GRAPH_VERBOSE are the
 // graph-replay safety valve and its diagnostics (run_sampler).
 static void read_switches(gc_handle* h) {
@@ -121,6 +121,7 @@ static void read_switches(gc_handle* h) {
   h->embed_cache = !off("GC_TUNE_EMBED_CACHE");
   h->attn_items = !off("GC_TUNE_ATTN_ITEMS");
   h->mlp_pair = !off("GC_TUNE_MLP_PAIR");
+  h->edge_terms = !off("GC_TUNE_EDGE_TERMS");
   h->a16 = !off("GC_TUNE_A16");
   h->graph_serialize = on("GC_TUNE_GRAPH_SERIALIZE");
   h->graph_verbose = on("GC_TUNE_GRAPH_VERBOSE");
@@ -276,6 +277,17 @@ int gc_set_option(gc_handle* h, const char* key, const char* value) {
     h->g2m_agg_norm = f;
     drop_sample_graphs(h);                       // the constant is a kernel argument baked into captured samples
     return GC_OK;
+  }
+  if (k == "edge_term_cache_mb") {
+    // cap of the edge-term cache (gc_handle::EdgeTerms): a noise-level list whose terms need more keeps the products
+    char* end = nullptr;
+    const long long mb = std::strtoll(v.c_str(), &end, 10);
+    if (v.empty() || (end && *end) || mb < 0 || mb > (1ll << 24)) return fail(h, GC_ERR_INVALID_ARGUMENT, "edge_term_cache_mb must be a number of MiB, 0 .. 2^24");
+    if (mb == h->edge_term_cap_mb) return GC_OK;
+    if (int rc = settle()) return rc;
+    h->edge_term_cap_mb = mb;
+    drop_sample_graphs(h);                       // captured samples bake the route
+    return drop_edge_terms(h);                   // the next sample decides again
   }
   if (k == "graphs") {
     if (v == "on") h->use_graphs = true;
@@ -859,6 +871,8 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "attention_items") *value = h->last_route.att_items;
   else if (n == "m2g_fused_sum") *value = h->last_route.m2g_fused ? 1 : 0;
   else if (n == "embed_cache") *value = h->embed_cache_samples;
+  else if (n == "edge_term_samples") *value = h->edge_term_samples;
+  else if (n == "edge_term_cache_bytes") *value = h->terms.ready ? h->terms.bytes : 0;
   else if (n == "graph_replays") *value = h->graph_replays;
   else if (n == "graph_captures") *value = h->graph_captures;
   else if (n == "loss_evaluations") *value = h->loss_evaluations;
@@ -1279,7 +1293,7 @@ int gc_debug_fetch(gc_handle* h, const char* name, float* out, int64_t capacity,
   struct Ent { const char* n; const float* p; int64_t items; int64_t w; int mesh; int batched; int act; };
   const Ent table[] = {
       {"cond", h->d_condvec, 1, gc::kCondDim, 0, 1, 0},
-      {"g0", h->d_g0, g.G, L, 0, 1, 1},        {"m0", h->d_m0, g.M, L, 1, 1, 1},
+      {"g0", h->d_g0, g.G, L, 0, 1, 1},        {"m0", h->m0_cur ? h->m0_cur : h->d_m0, g.M, L, 1, 1, 1},
       {"e1", h->d_e1, g.E1, L, 0, 1, 1},       {"agg1", h->d_agg1, g.M, L, 1, 1, 1},
       {"m1", h->d_x, g.M, L, 1, 1, 1},         {"x", h->d_x, g.M, L, 1, 1, 1},
       {"g1", h->d_g1, g.G, L, 0, 1, 1},        {"qkv", h->d_qkv, g.M, 3 * L, 1, 1, 0},

@@ -42,7 +42,19 @@ Route make_route(const gc_handle* h) {
   // inside a sample (embed_cache_live): the noisy block on the weight-streaming kernel; fp16 node features round the
   // staged inputs and keep the one-launch form
   r.embed_cache = h->embed_cache_live && h->embed_cache_ready && !h->feat16 && h->hidden_layers == 1 && streams;
+  // inside a sample whose noise levels have their terms cached (ensure_edge_terms built them for this very list)
+  r.edge_terms = h->embed_cache_live && h->terms.ready && edge_terms_possible(h) && r.f16;
   return r;
+}
+
+// What the edge-term route needs of the handle, whatever the noise levels: f16x3 (the exact-f32 family -- precision = f32,
+// the re-run of the domain guard -- keeps the products), float32 features, one hidden layer, latent 256 (the forms the
+// product-free first layer is built in), batch 1, the reference's mesh2grid edge set (3 edges per grid node; their sum in
+// the edge MLP's epilogue or, GC_TUNE_M2G_FUSE_SUM=0, as a launch of its own: the same bits).  GC_TUNE_EDGE_TERMS=0
+// switches it off.
+bool edge_terms_possible(const gc_handle* h) {
+  return h->edge_terms && h->f16x3 && !h->weights_f16_unsafe && !h->in_fallback && !h->feat16 && h->hidden_layers == 1 &&
+         h->cfg.latent_size == 256 && h->cfg.batch == 1 && h->hg.m2g_tri;
 }
 
 static gc::Segment seg(const float* ptr, const int* index, const float* affine, int width, int ld, int bcast) {
@@ -54,7 +66,7 @@ static gc::Segment seg(const float* ptr, const int* index, const float* affine, 
 // One MLP of the GNNs as the caller describes it; what the route and the weights add is build_mlp_args' business.
 struct MlpCall {
   gc::Segment seg[3] = {};             // input column blocks, concatenated along K
-  gc::AddTerm add[2] = {};             // per-node products added to the first layer (split edge MLP, embed cache)
+  gc::AddTerm add[3] = {};             // products added to the first layer (split edge MLP, embed cache, edge terms)
   int nseg = 0, nadd = 0, rows = 0, B = 1, ldo = 0;
   bool ln = true, cond = true;         // LayerNorm; conditioning (where the MLP has one)
   const float* residual = nullptr;
@@ -272,12 +284,25 @@ static MlpCall edge_call(gc_handle* h, const float* e_hat, const float* e_affine
   else c.segments({seg(nsnd, snd, nullptr, L, L, 0), seg(nrcv, rcv, nullptr, L, L, 0)});
   return c;
 }
+// The same update on the edge-term route: no segment, no product -- the first layer is the noise level's edge term (one
+// row per edge), the senders' product and the receivers' product, added in that order, then b1 (MlpArgs::nseg == 0).
+static MlpCall edge_terms_call(gc_handle* h, const float* T, int E, const int* snd, const int* rcv, const float* psnd,
+                               const float* prcv, float* out) {
+  const int B = h->cfg.batch, L = h->cfg.latent_size;
+  MlpCall c = mlp_call({}, E * B, B, out, L);
+  c.seg0_f32 = true;
+  return c.add_terms({{T, nullptr}, {psnd, snd}, {prcv, rcv}});
+}
 
 // mesh2grid edge update f1 = MLPc([f0 | m2[senders] | g1[receivers]]) (typed_graph_net.py:295-305; split_edge: the
 // per-node products are in d_pm / d_pg by then).  fused: the kernel's epilogue adds each grid node's three results and
 // writes agg2 [G, L] instead of f1 [E2, L].  Runs on h->route (gc_debug_fetch re-runs it unfused).
 int run_m2g_edge(gc_handle* h, const float* cond, bool fused) {
-  MlpCall c = edge_call(h, h->d_f0_hat, cond + h->m2g_embed_edge.cond_off, h->hg.E2, h->d_m2g_snd, h->d_m2g_rcv,
+  const size_t slot_rows = (size_t)std::max(h->term_slot, 0) * h->hg.E2 * h->cfg.latent_size;
+  MlpCall c = h->route.edge_terms
+                  ? edge_terms_call(h, h->terms.T2 + slot_rows, h->hg.E2, h->d_m2g_snd, h->d_m2g_rcv, h->d_pm, h->d_pg,
+                                    fused ? h->d_agg2 : h->d_f1)
+                  : edge_call(h, h->d_f0_hat, cond + h->m2g_embed_edge.cond_off, h->hg.E2, h->d_m2g_snd, h->d_m2g_rcv,
                         h->d_m2, h->d_g1, h->d_pm, h->d_pg, fused ? h->d_agg2 : h->d_f1);
   c.tri = fused;
   return run_mlp(h, h->m2g_edge, c);
@@ -345,7 +370,13 @@ int forward(gc_handle* h, float sigma_scalar, const float* cond_ready) {
     if (r.embed_cache) embed.add_terms({{h->d_pstat, nullptr}});
     if ((rc = run_mlp(h, r.embed_cache ? h->g2m_embed_grid_n : h->g2m_embed_grid, embed))) return rc;
   }
-  if ((rc = launch(h, gc::KC_PACK, [&] {
+  // m0 = affine(m0_hat; cond): a launch of the call, or (edge terms) the noise level's slot of the cache
+  const size_t ML = (size_t)g.M * L;
+  if (r.edge_terms && (h->term_slot < 0 || !h->terms.ready))
+    return fail(h, GC_ERR_INTERNAL, "edge terms: the forward has no slot of the cache");
+  const float* const m0 = r.edge_terms ? h->terms.m0 + h->term_slot * ML : h->d_m0;
+  h->m0_cur = m0;
+  if (!r.edge_terms && (rc = launch(h, gc::KC_PACK, [&] {
          return gc::launch_affine_rows(s, h->d_m0_hat, cond + h->g2m_embed_mesh.cond_off, cs, g.M, B, L,
                                        h->d_m0, h->feat16, r.st16);
        })))
@@ -354,8 +385,13 @@ int forward(gc_handle* h, float sigma_scalar, const float* cond_ready) {
   // (typed_graph_net.py:134-195): when both take the same kernel form they go out as ONE launch (gc_mlp_ws_pair_kernel) --
   // at nano the edge update's 526 row tiles are a round of 512 workgroups and a round of 14 that lasts as long again, and
   // the node update's 329 tiles fill that second round instead of a launch of their own (GC_TUNE_MLP_PAIR=0: two launches).
-  const MlpCall edge = edge_call(h, h->d_e0_hat, cond + h->g2m_embed_edge.cond_off, g.E1, h->d_g2m_snd, h->d_g2m_rcv,
-                                 h->d_g0, h->d_m0, h->d_pg, h->d_pm, h->d_e1);
+  // edge terms: the senders' product g0 @ W1snd is the one per-call product of this update (the receivers' is Pm[slot])
+  if (r.edge_terms && (rc = node_gemm(h, h->d_g0, g.G * B, h->g2m_edge.w1snd, h->d_pg))) return rc;
+  const MlpCall edge = r.edge_terms
+                           ? edge_terms_call(h, h->terms.T1 + (size_t)h->term_slot * g.E1 * L, g.E1, h->d_g2m_snd, h->d_g2m_rcv,
+                                             h->d_pg, h->terms.Pm + h->term_slot * ML, h->d_e1)
+                           : edge_call(h, h->d_e0_hat, cond + h->g2m_embed_edge.cond_off, g.E1, h->d_g2m_snd, h->d_g2m_rcv,
+                                       h->d_g0, h->d_m0, h->d_pg, h->d_pm, h->d_e1);
   const MlpCall node = mlp_call({seg(h->d_g0, nullptr, nullptr, L, L, 0)}, g.G * B, B, h->d_g1, L, h->d_g0);
   gc::MlpArgs ea{}, na{};
   bool paired = false;
@@ -371,8 +407,8 @@ int forward(gc_handle* h, float sigma_scalar, const float* cond_ready) {
                                   h->g2m_agg_norm);
        })))
     return rc;
-  if ((rc = run_mlp(h, h->g2m_mesh, mlp_call({seg(h->d_m0, nullptr, nullptr, L, L, 0), seg(h->d_agg1, nullptr, nullptr, L, L, 0)},
-                                             g.M * B, B, h->d_x, L, h->d_m0))))
+  if ((rc = run_mlp(h, h->g2m_mesh, mlp_call({seg(m0, nullptr, nullptr, L, L, 0), seg(h->d_agg1, nullptr, nullptr, L, L, 0)},
+                                             g.M * B, B, h->d_x, L, m0))))
     return rc;
   if (!paired && (rc = run_mlp(h, h->g2m_grid, node))) return rc;
 
@@ -451,7 +487,7 @@ int forward(gc_handle* h, float sigma_scalar, const float* cond_ready) {
   if ((rc = rowop(pend_bias, pend_slabs, h->cond_final, h->d_m2))) return rc;
 
   // ---- mesh2grid + decoder (denoiser.py:730-768) ----
-  if (r.split_edge && (rc = edge_node_products(h, h->m2g_edge, h->d_m2, g.M * B, h->d_pm, h->d_g1, g.G * B, h->d_pg)))
+  if ((r.split_edge || r.edge_terms) && (rc = edge_node_products(h, h->m2g_edge, h->d_m2, g.M * B, h->d_pm, h->d_g1, g.G * B, h->d_pg)))
     return rc;
   // The edge update, and the sum of every grid node's 3 updated edges (typed_graph_net.py:175-182): ONE launch when the
   // route says so (Route::m2g_fused) -- f1 [E2, L] is neither stored nor read back.  Other in-degrees (injected graphs),
@@ -484,6 +520,7 @@ int compute_static_embeddings(gc_handle* h) {
       {h->g2m_embed_mesh, h->d_mesh_struct16, hg.M, h->d_m0_hat},
       {h->g2m_embed_edge, h->d_e1_struct16, hg.E1, h->d_e0_hat},
       {h->m2g_embed_edge, h->d_e2_struct16, hg.E2, h->d_f0_hat}};
+  if (int rc = drop_edge_terms(h)) return rc;   // the edge terms are made from these embeddings
   auto run = [&]() -> int {
     h->route = make_route(h);    // same kernel build as the forward will use; float32 in (structural features) and out
     for (const auto& e : embeds) {
@@ -516,6 +553,88 @@ int compute_static_embeddings(gc_handle* h) {
   h->in_fallback = false;
   if (rc) return rc;
   GC_HIP(h, hipStreamSynchronize(h->stream));
+  return GC_OK;
+}
+
+// ---- edge terms (gc_handle::EdgeTerms) ----
+// Forgets the cache: waits for the stream that may still read it, frees it, and drops the captured samples, which bake
+// its addresses.  Called wherever something the terms are made from changes (weights, precision, feature mode, the static
+// embeddings, the cap) and by ensure_edge_terms for a new noise-level list.
+int drop_edge_terms(gc_handle* h) {
+  if (h->terms.sigmas.empty() && h->term_allocs.ptrs.empty()) return GC_OK;
+  if (!h->term_allocs.ptrs.empty()) {
+    GC_HIP(h, hipStreamSynchronize(h->stream));
+    drop_sample_graphs(h);
+    h->term_allocs.free();
+  }
+  h->terms = gc_handle::EdgeTerms{};
+  h->term_slot = -1;
+  return GC_OK;
+}
+
+// Makes the cache hold the terms of this sample's noise levels (one per denoiser call, in call order), outside any
+// stream capture: a no-op when it already does -- every sample after the first of a sampler configuration.  Otherwise the
+// cache of the previous list goes and, if the new one fits the cap, is built on the handle's stream with the kernels
+// every call used so far: the conditioning of all levels in one launch, then per distinct level the affine pass over
+// each static embedding and the weight-streaming GEMM with the block of W1 it meets.  Over the cap (or more levels than
+// one conditioning launch takes) nothing is built and the sample keeps the route with the products.
+int ensure_edge_terms(gc_handle* h, const std::vector<float>& call_sigma) {
+  if (!edge_terms_possible(h)) return GC_OK;    // (the cache, if any, stays: the exact-f32 re-run of a sample must not cost the next one its terms)
+  gc_handle::EdgeTerms& t = h->terms;
+  if (t.sigmas.size() == call_sigma.size() &&
+      !std::memcmp(t.sigmas.data(), call_sigma.data(), call_sigma.size() * sizeof(float)))
+    return GC_OK;                               // built, or found too large, for this very list
+  if (int rc = drop_edge_terms(h)) return rc;
+  t.sigmas = call_sigma;
+  std::vector<float> distinct;
+  for (float sg : call_sigma) {
+    size_t k = 0;
+    while (k < distinct.size() && std::memcmp(&distinct[k], &sg, sizeof(float))) ++k;
+    if (k == distinct.size()) distinct.push_back(sg);
+    t.call_slot.push_back((int)k);
+  }
+  const gc::HostGraph& g = h->hg;
+  const gc_config& c = h->cfg;
+  const size_t L = c.latent_size, n = distinct.size();
+  const size_t per_slot = ((size_t)g.E1 + g.E2 + 2 * (size_t)g.M) * L;
+  t.bytes = (int64_t)(n * per_slot * sizeof(float));
+  if (n == 0 || n > (size_t)gc::kMaxSigmaList || t.bytes > h->edge_term_cap_mb * (int64_t)(1 << 20) ||
+      n * (size_t)c.batch * h->cond_total > h->cond_all_cap) {
+    t.bytes = 0;
+    return GC_OK;
+  }
+  int rc;
+  BufferGroup* own = &h->term_allocs;
+  if ((rc = dev_alloc(h, &t.T1, n * g.E1 * L, own)) || (rc = dev_alloc(h, &t.T2, n * g.E2 * L, own)) ||
+      (rc = dev_alloc(h, &t.m0, n * g.M * L, own)) || (rc = dev_alloc(h, &t.Pm, n * g.M * L, own)))
+    return rc;
+  hipStream_t s = h->stream;
+  h->route = make_route(h);                     // f16x3 on float32 arrays (edge_terms_possible): the node GEMM's form
+  gc::SigmaList sl{};
+  for (size_t i = 0; i < n; ++i) sl.v[i] = distinct[i];
+  if ((rc = launch(h, gc::KC_COND, [&] {
+         return gc::launch_cond_multi(s, sl, (int)n, c.batch, h->d_nw0t, h->d_nb0, h->d_nw1t, h->d_nb1, c.noise_num_frequencies,
+                                      c.noise_hidden, c.noise_base_period, h->d_wc_all, h->d_bc_all, h->cond_total, h->d_cond_all);
+       })))
+    return rc;
+  // d_e1 / d_f1 ([E1][L], [E2][L] at batch 1) hold the conditioned edge embeddings of the level in hand: every call
+  // overwrites them anyway
+  const int cs = h->cond_total;
+  for (size_t i = 0; i < n; ++i) {
+    const float* cond = h->d_cond_all + i * (size_t)c.batch * cs;
+    const struct { const float* hat; int cond_off, items; float* staged; const Weight* w; float* out; } passes[] = {
+        {h->d_e0_hat, h->g2m_embed_edge.cond_off, g.E1, h->d_e1, &h->g2m_edge.w1e, t.T1 + i * g.E1 * L},
+        {h->d_f0_hat, h->m2g_embed_edge.cond_off, g.E2, h->d_f1, &h->m2g_edge.w1e, t.T2 + i * g.E2 * L},
+        {h->d_m0_hat, h->g2m_embed_mesh.cond_off, g.M, t.m0 + i * g.M * L, &h->g2m_edge.w1rcv, t.Pm + i * g.M * L}};
+    for (const auto& p : passes) {
+      if ((rc = launch(h, gc::KC_PACK, [&] {
+             return gc::launch_affine_rows(s, p.hat, cond + p.cond_off, cs, p.items, 1, (int)L, p.staged, false, false);
+           })))
+        return rc;
+      if ((rc = node_gemm(h, p.staged, p.items, *p.w, p.out))) return rc;
+    }
+  }
+  t.ready = true;
   return GC_OK;
 }
 

@@ -62,6 +62,8 @@ struct Route {
   bool split_edge = false;  // edge MLPs with the first layer split by input block
   bool try_pair = false;    // the grid2mesh edge and grid-node updates may go out as one launch
   bool embed_cache = false; // inside a sample that runs the grid embedding on the cache (d_xn / d_pstat)
+  bool edge_terms = false;  // inside a sample whose noise levels have their edge terms cached (gc_handle::EdgeTerms): the
+                            // two edge MLPs' first layer is T(sigma)[e] + P_snd[snd] + P_rcv[rcv] + b1, no product
   // the weight-streaming GEMM (WF16 / WF32 weights) whenever the K slice is a multiple of 128
   bool ws(int n, int k, int splits) const { return (f16 || x32) && n % 128 == 0 && (k / splits) % 128 == 0; }
 };
@@ -219,6 +221,31 @@ struct gc_handle {
   int64_t embed_cache_samples = 0;           // samples that ran on the cache (gc_get_counter "embed_cache")
   bool m2g_fuse_sum = true;                  // GC_TUNE_M2G_FUSE_SUM=0: mesh2grid edge update + a segment-sum launch (the form every
                                              // graph with other in-degrees than 3 takes anyway)
+  // Edge terms ("edge terms").  The first layer of an edge MLP is [e | n_snd | n_rcv] @ W1 =
+  // e @ W1e + (n_snd @ W1snd)[snd] + (n_rcv @ W1rcv)[rcv].  Inside a sample e = affine(e_hat; cond(sigma)) depends on
+  // the noise level alone (static embedding under a conditioning affine), and so do m0 = affine(m0_hat; sigma) and its
+  // product with the grid2mesh receiver block.  A sampler runs ONE sigma list for every sample of every member, so
+  // these are made once per list, one slot per distinct noise level:
+  //   T1 [slots][E1][L] = affine(e0_hat) @ W1e(g2m)      T2 [slots][E2][L] = affine(f0_hat) @ W1e(m2g)
+  //   m0 [slots][M][L]                                   Pm [slots][M][L]  = m0 @ W1rcv(g2m)
+  // Call i of a sample reads slot call_slot[i].  Key: the sigma list of the calls; weights, precision, feature mode
+  // and the static embeddings are covered by dropping the cache where they change (free_weights,
+  // compute_static_embeddings).  Batch 1 only (the sampler's conditioning is the same for every batch element, but m0
+  // is also a residual with a batch axis): batch > 1 keeps the route with the products.
+  struct EdgeTerms {
+    bool ready = false;                          // built for `sigmas`, within the cap
+    std::vector<float> sigmas;                   // noise level of every denoiser call of the sample it was built for
+    std::vector<int> call_slot;                  // call -> slot (equal noise levels share one)
+    float *T1 = nullptr, *T2 = nullptr, *m0 = nullptr, *Pm = nullptr;
+    int64_t bytes = 0;
+  };
+  bool edge_terms = true;                        // GC_TUNE_EDGE_TERMS=0: every call multiplies the whole first layer
+  int64_t edge_term_cap_mb = 4096;               // gc_set_option("edge_term_cache_mb"): a list that needs more keeps the products
+  EdgeTerms terms;
+  gci::BufferGroup term_allocs{groups};
+  int term_slot = -1;                            // slot of the forward being enqueued / of the last one (gc_debug_fetch)
+  const float* m0_cur = nullptr;                 // the conditioned mesh embedding the last forward read (d_m0 or a slot)
+  int64_t edge_term_samples = 0;                 // samples that ran on the cache (gc_get_counter)
   float *d_ones = nullptr, *d_zeros = nullptr;   // identity affine for gc_mlp_ws
   int hidden_layers = 1;                         // gc_set_option("hidden_layers"): hidden layers of every GNN MLP (denoiser.py:135)
   float* d_mlp_tmp[2] = {nullptr, nullptr};      // hidden_layers >= 2: [max rows][latent] hand-over between the launches of one MLP
@@ -618,6 +645,9 @@ int build_embed_cache(gc_handle* h);
 Route make_route(const gc_handle* h);
 bool build_attention_items(const gc::HostGraph& g, std::vector<int>* items, std::vector<int>* tiles);
 int run_m2g_edge(gc_handle* h, const float* cond, bool fused);
+bool edge_terms_possible(const gc_handle* h);
+int drop_edge_terms(gc_handle* h);
+int ensure_edge_terms(gc_handle* h, const std::vector<float>& call_sigma);
 int forward(gc_handle* h, float sigma_scalar, const float* cond_ready = nullptr);
 int compute_static_embeddings(gc_handle* h);
 // gc_sampler.hip

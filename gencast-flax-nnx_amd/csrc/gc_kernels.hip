@@ -636,9 +636,13 @@ constexpr int mlp_ws_occ() { return NWC >= 8 ? (NT1 == 1 ? 4 : 2) : ((WM >= 2 ||
 // The kernel body, with the workgroup's tile index as a parameter: gc_mlp_ws_kernel runs it on blockIdx.x,
 // gc_mlp_ws_pair_kernel runs TWO independent MLPs of the same shape in one launch (blocks [0, na) the first, the rest the
 // second), so that their partly filled last rounds of workgroups share the chip.
-template <int NT1, int NT2, int MT, int WM, int NWC, int NW2, int OCC, bool A16, bool F32>
+// TERMS (MlpArgs::nseg == 0): the first layer has NO product -- the pre-activation of a row is b1 plus up to three add
+// terms (an edge MLP whose edge block was multiplied once per noise level and whose node blocks once per node:
+// gc_handle "edge terms").  Nothing is staged and no W1 is streamed; the hidden tile is written straight from the sums.
+template <int NT1, int NT2, int MT, int WM, int NWC, int NW2, int OCC, bool A16, bool F32, bool TERMS = false>
 __device__ __forceinline__ void gc_mlp_ws_body(const MlpArgs& a, const int bid) {
   static_assert(!(A16 && F32), "one or the other");
+  static_assert(!TERMS || (!A16 && !F32 && (NT1 * 32 * NWC) % 256 == 0 && (32 * MT) % (4 * NWC) == 0), "terms form: f16x3, whole 1 KB rows per wave");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int HID = NT1 * 32 * NWC, NPAD = NT2 * 32 * NW2, BM = 32 * MT * WM, NTHR = 64 * NWC * WM;
   // K chunk of the gathered input resident in LDS (double-buffered), and weight ring depth.
@@ -675,7 +679,26 @@ __device__ __forceinline__ void gc_mlp_ws_body(const MlpArgs& a, const int bid) 
   const float *p0 = a.seg[0].ptr, *p1 = a.seg[1].ptr, *p2 = a.seg[2].ptr;
   const float *f0 = a.seg[0].affine, *f1 = a.nseg > 1 ? a.seg[1].affine : nullptr,
               *f2 = a.nseg > 2 ? a.seg[2].affine : nullptr;
-  {
+  if constexpr (TERMS) {                       // element offset of each row's term rows, [3][BM] where the segments' offsets lie otherwise
+    const int *ax0 = a.add[0].index, *ax1 = a.add[1].index, *ax2 = a.add[2].index;
+    for (int idx = tid; idx < a.nadd * BM; idx += NTHR) {
+      const int t = idx / BM, i = idx - t * BM;
+      int grow = row0 + i;
+      if (grow >= a.rows) grow = a.rows - 1;
+      int item = grow / a.B, b = grow - item * a.B;
+      if (tri) {                               // (as below: padding rows and units beyond the end repeat a valid row)
+        const int j = i / 3;
+        int u = unit0 + j;
+        if (u >= units) u = units - 1;
+        const int gi = u / a.B;
+        b = u - gi * a.B;
+        item = 3 * gi + (i - 3 * j);
+      }
+      const int* ax = pick3(t, ax0, ax1, ax2);
+      srcoff[idx] = ((ax ? ax[item] : item) * a.B + b) * HID;
+    }
+  }
+  if constexpr (!TERMS) {
     const int *ix0 = a.seg[0].index, *ix1 = a.seg[1].index, *ix2 = a.seg[2].index;
     const int bc0 = a.seg[0].bcast, bc1 = a.seg[1].bcast, bc2 = a.seg[2].bcast;
     const int ld0 = a.seg[0].ld, ld1 = a.seg[1].ld, ld2 = a.seg[2].ld;
@@ -821,7 +844,36 @@ __device__ __forceinline__ void gc_mlp_ws_body(const MlpArgs& a, const int bid) 
   const int steps1 = kpad / 16;
   const float* wf1 = a.w1f + (size_t)(wave * NT1) * steps1 * 512 + lane * 4;
   const size_t cts1 = (size_t)steps1 * 512;
-  {
+  if constexpr (TERMS) {
+    // hidden = swish(((T + sender) + receiver) + b1), float32, in that order.  Wave w takes rows w RPW .. + RPW - 1; a
+    // lane owns 4 consecutive columns per 256, so every term row is one coalesced 1 KB read of the wave.
+    constexpr int RPW = BM / (NWC * WM);
+    const float *t0 = a.add[0].ptr, *t1 = a.add[1].ptr, *t2 = a.add[2].ptr;
+    const int nadd = a.nadd;
+#pragma unroll
+    for (int cg = 0; cg < HID / 256; ++cg) {
+      const int c = 4 * lane + 256 * cg;
+      const f32x4 bv = ld4(a.b1 + c);
+#pragma unroll
+      for (int i0 = 0; i0 < RPW; i0 += 4) {
+        f32x4 v0[4], v1[4], v2[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {          // the four rows' gathers are in flight together
+          const int row = wave_all * RPW + i0 + k;
+          v0[k] = ld4(t0 + srcoff[row] + c);
+          v1[k] = v2[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (nadd > 1) v1[k] = ld4(t1 + srcoff[BM + row] + c);
+          if (nadd > 2) v2[k] = ld4(t2 + srcoff[2 * BM + row] + c);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const f32x4 x = ((v0[k] + v1[k]) + v2[k]) + bv;
+          store4_s16(region, (size_t)(wave_all * RPW + i0 + k), LDH, c, swish(x[0]), swish(x[1]), swish(x[2]), swish(x[3]));
+        }
+      }
+    }
+  }
+  if constexpr (!TERMS) {
     f32x16 acc[MT][NT1], accx[MT][NT1];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -1167,18 +1219,18 @@ __device__ __forceinline__ void gc_mlp_ws_body(const MlpArgs& a, const int bid) 
 
 template <int NT1, int NT2, int MT, int WM, int NWC = 4, int NW2 = NWC,
           int OCC = mlp_ws_occ<NT1, WM, NWC>() /* waves per SIMD the registers are held to */, bool A16 = false,
-          bool F32 = false>
+          bool F32 = false, bool TERMS = false>
 __global__ __launch_bounds__(64 * NWC * WM, OCC) void gc_mlp_ws_kernel(MlpArgs a) {
-  gc_mlp_ws_body<NT1, NT2, MT, WM, NWC, NW2, OCC, A16, F32>(a, (int)blockIdx.x);
+  gc_mlp_ws_body<NT1, NT2, MT, WM, NWC, NW2, OCC, A16, F32, TERMS>(a, (int)blockIdx.x);
 }
 
 // Two independent fused MLPs of one shape in one launch (the grid2mesh edge update and the grid-node update both read
 // only g0 / m0: typed_graph_net.py:134-195).  At nano the edge update's 526 tiles are one round of 512 workgroups plus a
 // round of 14 that costs as much again; the node update's 329 tiles fill that second round instead of a launch of their own.
 template <int NT1, int NT2, int MT, int WM, int NWC = 4, int NW2 = NWC,
-          int OCC = mlp_ws_occ<NT1, WM, NWC>(), bool A16 = false, bool F32 = false>
+          int OCC = mlp_ws_occ<NT1, WM, NWC>(), bool A16 = false, bool F32 = false, bool TERMS_A = false /* the first MLP in the terms form */>
 __global__ __launch_bounds__(64 * NWC * WM, OCC) void gc_mlp_ws_pair_kernel(MlpArgs a, MlpArgs b, int na) {
-  if ((int)blockIdx.x < na) gc_mlp_ws_body<NT1, NT2, MT, WM, NWC, NW2, OCC, A16, F32>(a, (int)blockIdx.x);
+  if ((int)blockIdx.x < na) gc_mlp_ws_body<NT1, NT2, MT, WM, NWC, NW2, OCC, A16, F32, TERMS_A>(a, (int)blockIdx.x);
   else gc_mlp_ws_body<NT1, NT2, MT, WM, NWC, NW2, OCC, A16, F32>(b, (int)blockIdx.x - na);
 }
 
@@ -1190,15 +1242,19 @@ static hipError_t mlp_ws_geometry(const MlpArgs& a, int* grid_out, size_t* lds_o
   constexpr int region = (abuf > BM * (HID + 4)) ? abuf : BM * (HID + 4);
   static_assert(BM * (NPAD + 4) <= region, "output tile must fit the shared region");
   *lds_out = (size_t)(6 * BM + region) * sizeof(float);
-  if (a.nadd < 0 || a.nadd > 2 || (a.nadd > 0 && !a.add[0].ptr) || (a.nadd > 1 && !a.add[1].ptr))
+  if (a.nadd < 0 || a.nadd > 3 || (a.nadd > 0 && !a.add[0].ptr) || (a.nadd > 1 && !a.add[1].ptr) || (a.nadd > 2 && !a.add[2].ptr))
     return hipErrorInvalidValue;
+  if (a.nseg != 0 && a.nadd > 2) return hipErrorInvalidValue;   // the product forms gather two terms
   int ksum = 0;
   for (int i = 0; i < a.nseg; ++i) {
     if (a.seg[i].width % 32 || a.seg[i].ld % 4) return hipErrorInvalidValue;
     ksum += a.seg[i].width;
   }
-  if (a.k1f % 64 || a.k1f < ksum || a.k1f - ksum >= 64 || !a.w2f || !a.ones || !a.zeros || ksum > 512 * 3)
+  if (a.nseg == 0) {                            // terms form: f16x3 on float32 arrays, nothing staged
+    if (a.nadd < 1 || !a.f16 || a.f32w || a.a16 || a.round16 || !a.w2f) return hipErrorInvalidValue;
+  } else if (a.k1f % 64 || a.k1f < ksum || a.k1f - ksum >= 64 || !a.w2f || !a.ones || !a.zeros || ksum > 512 * 3) {
     return hipErrorInvalidValue;
+  }
   if (kTuA16) {                                 // fp16-stored segments: 16-byte pieces of 8 halfs, one segment per K chunk
     constexpr int KCc = BM >= 128 ? 64 : 128;
     for (int i = 0; i < a.nseg; ++i) {
@@ -1218,13 +1274,24 @@ static hipError_t mlp_ws_geometry(const MlpArgs& a, int* grid_out, size_t* lds_o
   return hipSuccess;
 }
 
-template <int NT1, int NT2, int MT, int WM, int NWC = 4, int NW2 = NWC>
+template <int NT1, int NT2, int MT, int WM, int NWC = 4, int NW2 = NWC, bool TERMS_A = false>
 static hipError_t launch_mlp_ws_pair_t(hipStream_t s, const MlpArgs& a, const MlpArgs& b) {
   int ga = 0, gb = 0;
   size_t lds = 0;
   if (hipError_t e = mlp_ws_geometry<NT1, NT2, MT, WM, NWC, NW2>(a, &ga, &lds)) return e;
   if (hipError_t e = mlp_ws_geometry<NT1, NT2, MT, WM, NWC, NW2>(b, &gb, &lds)) return e;
   constexpr int OCC = mlp_ws_occ<NT1, WM, NWC>();
+  if ((a.nseg == 0) != TERMS_A || b.nseg == 0) return hipErrorInvalidValue;
+  if constexpr (TERMS_A) {
+    if constexpr (kTuA16) return hipErrorInvalidValue;
+    else {
+      static DynLdsOnce once_t;
+      if (hipError_t e = once_t.ensure((const void*)gc_mlp_ws_pair_kernel<NT1, NT2, MT, WM, NWC, NW2, OCC, false, false, true>, (int)lds)) return e;
+      hipLaunchKernelGGL((gc_mlp_ws_pair_kernel<NT1, NT2, MT, WM, NWC, NW2, OCC, false, false, true>), dim3(ga + gb),
+                         dim3(64 * NWC * WM), lds, s, a, b, ga);
+      return hipGetLastError();
+    }
+  }
   if constexpr (!kTuA16) {
     if (a.f32w) {
       static DynLdsOnce once32;
@@ -1241,12 +1308,23 @@ static hipError_t launch_mlp_ws_pair_t(hipStream_t s, const MlpArgs& a, const Ml
   return hipGetLastError();
 }
 
-template <int NT1, int NT2, int MT, int WM, int NWC = 4, int NW2 = NWC>
+template <int NT1, int NT2, int MT, int WM, int NWC = 4, int NW2 = NWC, bool TERMS = false>
 static hipError_t launch_mlp_ws_t(hipStream_t s, const MlpArgs& a) {
   int grid = 0;
   size_t lds = 0;
   if (hipError_t e = mlp_ws_geometry<NT1, NT2, MT, WM, NWC, NW2>(a, &grid, &lds)) return e;
   constexpr int OCC = mlp_ws_occ<NT1, WM, NWC>();
+  if ((a.nseg == 0) != TERMS) return hipErrorInvalidValue;
+  if constexpr (TERMS) {
+    if constexpr (kTuA16) return hipErrorInvalidValue;
+    else {
+      static DynLdsOnce once_t;
+      if (hipError_t e = once_t.ensure((const void*)gc_mlp_ws_kernel<NT1, NT2, MT, WM, NWC, NW2, OCC, false, false, true>, (int)lds)) return e;
+      hipLaunchKernelGGL((gc_mlp_ws_kernel<NT1, NT2, MT, WM, NWC, NW2, OCC, false, false, true>), dim3(grid),
+                         dim3(64 * NWC * WM), lds, s, a);
+      return hipGetLastError();
+    }
+  }
   if constexpr (!kTuA16) {
     if (a.f32w) {
       static DynLdsOnce once32;
@@ -1295,6 +1373,11 @@ hipError_t launch_mlp(hipStream_t s, const MlpArgs& a) {
   const int nt1 = a.hidden / 128, nt2 = a.n_out_pad / 128;
   if (a.hidden % 128 || a.n_out_pad % 128 || a.n_out_pad > a.hidden) return hipErrorInvalidValue;
   if (mlp_runs_weight_streaming(a)) {
+    // no first-layer product (nseg == 0): the forms the nano edge updates take -- hidden 256 to 256
+    if (a.nseg == 0) {
+      if (nt1 != 2 || nt2 != 2) return hipErrorInvalidValue;
+      return a.rows >= kMlpMt2Rows ? launch_mlp_ws_t<2, 2, 2, 1, 4, 4, true>(s, a) : launch_mlp_ws_t<1, 1, 1, 1, 8, 8, true>(s, a);
+    }
     // hidden 512: 8 column waves x 64 rows (1-degree config: 3.1 ms per call; 32-row forms 3.9, LDS-staged 7.1)
     if (nt1 == 4) return nt2 == 4 ? launch_mlp_ws_t<2, 2, 2, 1, 8, 8>(s, a) : launch_mlp_ws_t<2, 1, 2, 1, 8, 4>(s, a);
     // (128-row tiles with one workgroup per CU were measured slower than 64-row ones -- 84 vs 77 us on the nano
@@ -1308,7 +1391,7 @@ hipError_t launch_mlp(hipStream_t s, const MlpArgs& a) {
   // never lands here; physical fp16 storage (a.a16: halfs behind the float* fields) would be silently wrong values and
   // the triple epilogue exists in the weight-streaming kernel only.  The kernel dereferences w1t and every add-term
   // index (the weight-streaming kernel takes a null index as "the row itself"), so those are checked too.
-  if (a.f16 || a.a16 || a.tri || !a.w1t || a.nadd < 0 || a.nadd > 2) return hipErrorInvalidValue;
+  if (a.f16 || a.a16 || a.tri || !a.w1t || a.nadd < 0 || a.nadd > 2 || a.nseg == 0) return hipErrorInvalidValue;
   for (int i = 0; i < a.nadd; ++i)
     if (!a.add[i].index) return hipErrorInvalidValue;
 #define GC_MLP(A_, B_) \
@@ -1325,11 +1408,14 @@ bool mlp_pair_supported(const MlpArgs& a, const MlpArgs& b) {
     if (!mlp_runs_weight_streaming(m) || m.tri || m.n_out_pad != m.hidden) return false;
     return m.hidden == 512 || (m.hidden == 256 && m.rows < kMlpMt2Rows);
   };
+  // (the first may be in the terms form, nseg == 0, at hidden 256: the pair is instantiated for that combination)
+  if (b.nseg == 0 || (a.nseg == 0 && a.hidden != 256)) return false;
   return ok(a) && ok(b) && a.hidden == b.hidden && a.f16 == b.f16 && a.f32w == b.f32w && a.a16 == b.a16;
 }
 hipError_t launch_mlp_pair(hipStream_t s, const MlpArgs& a, const MlpArgs& b) {
   if (!mlp_pair_supported(a, b)) return hipErrorInvalidValue;
   if (a.hidden == 512) return launch_mlp_ws_pair_t<2, 2, 2, 1, 8, 8>(s, a, b);
+  if (a.nseg == 0) return launch_mlp_ws_pair_t<1, 1, 1, 1, 8, 8, true>(s, a, b);
   return launch_mlp_ws_pair_t<1, 1, 1, 1, 8, 8>(s, a, b);
 }
 

@@ -38,6 +38,8 @@ struct Segment {
 };
 
 // A per-node product gathered per row and added to the first layer's pre-activation.
+// The three of a first layer without a product (MlpArgs::nseg == 0) are added in float32 in this order: add[0] (the
+// per-noise-level edge term T), add[1] (sender), add[2] (receiver), then b1.
 struct AddTerm {
   const float* ptr;    // [nodes * B][hidden] float32
   const int* index;    // per-item node index; nullptr: the item itself (a per-ROW term, e.g. the cached static part of the grid embedding)
@@ -45,8 +47,8 @@ struct AddTerm {
 
 struct MlpArgs {
   Segment seg[3];
-  int nseg;
-  AddTerm add[2];
+  int nseg;            // 0 (weight-streaming form, f16x3, hidden 256): no first-layer product, pre-activation = add terms + b1
+  AddTerm add[3];
   int nadd;
   int rows;            // items * B
   int B;

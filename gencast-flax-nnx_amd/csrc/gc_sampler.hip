@@ -70,6 +70,13 @@ int sampler_body(gc_handle* h, const float* sigmas, int n, int skip_dead, const 
     if ((rc = launch(h, gc::KC_GEMM_NODE, [&] { return gc::launch_gemm(s, gc::KC_GEMM_NODE, ga, 1, 0, route.f16); }))) return rc;
     ++h->embed_cache_samples;
   }
+  // edge terms: every call reads the slot of its noise level (run_sampler made the cache hold this sample's list)
+  if (route.edge_terms) {
+    if (!multi || h->terms.call_slot.size() != call_sigma.size() ||
+        std::memcmp(h->terms.sigmas.data(), call_sigma.data(), call_sigma.size() * sizeof(float)))
+      return fail(h, GC_ERR_INTERNAL, "sampler: the edge-term cache was built for another noise-level list");
+    ++h->edge_term_samples;
+  }
   auto noisy_write = [&](float sigma_next_call) {
     gc::NoisyWrite nw;
     nw.slots = h->d_slots; nw.c_out = c.c_out; nw.kp = h->kp; nw.scale = f_c_in(std::max(sigma_next_call, 1e-6f));
@@ -112,6 +119,7 @@ int sampler_body(gc_handle* h, const float* sigmas, int n, int skip_dead, const 
         return fail(h, GC_ERR_INTERNAL, "sampler: noise-level list out of step with the loop");
       ready = h->d_cond_all + (size_t)calls * cond_call;
     }
+    h->term_slot = route.edge_terms ? h->terms.call_slot[calls] : -1;
     ++calls;
     return forward(h, ss, ready);
   };
@@ -190,6 +198,8 @@ int run_sampler(gc_handle* h, const float* sigmas, int n, int skip_dead, gc_samp
     if ((rc = dev_alloc(h, &h->d_cond_all, call_sigma.size() * cond_call))) return rc;
     h->cond_all_cap = call_sigma.size() * cond_call;
   }
+  // the edge terms of this list of noise levels: built by the first sample that brings it, outside any capture
+  if ((rc = multi ? ensure_edge_terms(h, call_sigma) : drop_edge_terms(h))) return rc;
 
   // ---- HIP-graph replay (the reference runs its whole sampler as ONE compiled program: the jax.lax.fori_loop of
   // dpm_solver_plus_plus_2s.py:157-158).  One sample is ~3 500 kernel launches that cost the host ~25 ms to enqueue
@@ -258,6 +268,7 @@ int run_sampler(gc_handle* h, const float* sigmas, int n, int skip_dead, gc_samp
     calls = sg->calls;
     h->launches_last_call = sg->launches_per_call;
     h->route = h->last_route = sg->route;
+    if (sg->route.edge_terms) ++h->edge_term_samples;
     ++h->graph_replays;
   } else if (sg) {
     const int64_t l0 = h->launch_count;

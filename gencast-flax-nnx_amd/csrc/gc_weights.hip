@@ -301,6 +301,7 @@ int build_embed_cache(gc_handle* h) {
 
 // Frees what finalize_weights allocated (the stream is idle and no captured sample is left: gc_finalize, destroy).
 void free_weights(gc_handle* h) {
+  (void)drop_edge_terms(h);                     // made from these weights
   h->weight_allocs.free();
   h->finalized = h->finalized_weights = h->embed_cache_ready = false;
   h->cond_cur = nullptr;                        // (it may point into the d_cond just freed)

@@ -132,6 +132,11 @@ void gc_destroy(gc_handle* h);
  *       of fp16 values); the reference trains with 1 (training/train_helpers.py:137), the tuned one-launch-per-MLP path.
  *   "grid2mesh_aggregate_normalization" = "none" (default) | "<positive constant>"   -- the summed grid2mesh edge
  *       messages of every mesh node are divided by it (common/deep_typed_graph_net.py:396-410; gencast/denoiser.py:123,138).
+ *   "edge_term_cache_mb" = "4096" (default) | "<MiB>"   -- cap of the per-noise-level cache the sampler keeps at latent
+ *       256, batch 1, f16x3, float32 features: the edge block of the two edge MLPs' first layer times the
+ *       conditioned static edge embeddings, and the conditioned mesh embedding, one slot per distinct noise level of the
+ *       sampler's list, built by the first sample that brings the list.  A list whose terms need more than the cap (and
+ *       "0") keeps the per-call products: same samples to float32 rounding.
  */
 int gc_set_option(gc_handle* h, const char* key, const char* value);
 
@@ -986,6 +991,8 @@ int gc_algorithmic_work(gc_handle* h, double* flops, double* bytes);
  * any mesh2grid edge set with other in-degrees than 3 takes), "embed_cache" (samples so far whose grid embedding ran on the cached
  * per-sample-constant part of its first layer: only the c_out noisy-target columns are multiplied per call, the other 3 + c_in - c_out
  * once per sample -- dpm_solver_plus_plus_2s.py:107-112 closes over them; float32 node features, hidden_layers = 1),
+ * "edge_term_samples" (samples so far whose edge MLPs read their first layer's edge block from the per-noise-level cache:
+ * gc_set_option "edge_term_cache_mb"), "edge_term_cache_bytes" (device bytes that cache holds now; 0: not built),
  * "loss_evaluations" (denoising-loss evaluations so far: gc_loss_resident / gc_loss), "loss_device_us" (HIP-event time of
  * the evaluations of the last gc_loss_resident call, microseconds). */
 /* ... and "device_allocations" (device buffers the handle holds now: gc_finalize and gc_set_noisy_slots replace theirs, they do not add),
