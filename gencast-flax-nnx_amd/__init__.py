@@ -28,6 +28,8 @@ Public surface (mirrors the reference's call contracts):
                       EnsembleRollout.run(energy=..., variogram=...))
                       TailScores: the threshold-weighted CRPS at the thresholds of an EventSpec, from members sorted once
                       per point on the GPU (GenCast.ensemble_tails, EnsembleRollout.run(tails=...))
+                      FractionsScores: the fractions skill score of the neighbourhood ensemble probability at the
+                      `scales_km` of an EventSpec, from the event codes on the GPU (`EventScores.fractions`)
                       RegionSpec / RegionScores: the ensemble scores per region of the grid (tropics, extratropics, land,
                       sea, boxes), every region from one pass on the GPU (GenCast.ensemble_regions,
                       EnsembleRollout.run(regions=...))
@@ -52,8 +54,8 @@ from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, Ense
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
 from .verification import (ClimatologyScores, DerivedSpec, EnergyScores, EnergySpec, EnsembleScores, EventScores,  # noqa: F401
-                           EventSpec, FeatureScores, FeatureSpec, OrderScores, RegionScores, RegionSpec, TailScores,
-                           VariogramScores, VariogramSpec, WindowSpec, link_tracks)
+                           EventSpec, FeatureScores, FeatureSpec, FractionsScores, OrderScores, RegionScores, RegionSpec,
+                           TailScores, VariogramScores, VariogramSpec, WindowSpec, link_tracks)
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
@@ -62,4 +64,5 @@ __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_
            "SphericalAnalysis", "EnsembleRollout", "EnsembleRolloutResult", "state_channels", "EventScores", "EventSpec",
            "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores",
            "WindowSpec", "WindowRolloutResult", "EnergySpec", "EnergyScores", "VariogramSpec", "VariogramScores", "TailScores",
-           "RegionSpec", "RegionScores", "FeatureSpec", "FeatureScores", "FeatureRolloutResult", "link_tracks"]
+           "RegionSpec", "RegionScores", "FeatureSpec", "FeatureScores", "FeatureRolloutResult", "link_tracks",
+           "FractionsScores"]

@@ -120,6 +120,10 @@ SIGNATURES = {
     "gc_ens_event_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                           ctypes.POINTER(ctypes.c_uint64)]),
     "gc_ens_event_download": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8)]),
+    "gc_ens_fss_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p,
+                                      ctypes.POINTER(ctypes.c_uint32)]),
+    "gc_ens_fss_score": (ctypes.c_int, [_hp, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_fss_fields": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p]),
     "gc_ens_derive_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int32,
                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.POINTER(ctypes.c_double)]),
     "gc_ens_derive": (ctypes.c_int, [_hp, _hp, _f32p]),
@@ -242,6 +246,7 @@ class NativeDenoiser:
     self._ens_members = 0                      # slots of the member store this object reserved on the handle
     self._spec_lmax = 0                        # band limit of the analysis tables this object handed to the handle
     self._event_thresholds = 0                 # threshold fields this object handed to the handle
+    self._fss_scales = 0                       # scales of the fractions plan this object handed to the handle
     self._derive_c_src = 0                     # source channels of the derive plan this object handed to the handle
     self._feature_c_src = 0                    # source channels of the feature plan, and the size of its lists
     self._feature_max = 0
@@ -664,6 +669,62 @@ class NativeDenoiser:
     code = np.empty(self._shape_out(), dtype=np.uint8)
     self._check(self._lib.gc_ens_event_download(self._h, int(t), _ptr(code, ctypes.POINTER(ctypes.c_uint8))))
     return code
+
+  # -- fractions skill score (neighbourhood fractions of the event codes, S scales from one pass) -------
+  def ens_fss_set(self, r_lat, r_lon, row_wq, n_lon: Optional[int] = None) -> None:
+    """The plan of `ens_fss_score` (gc_ens_fss_set; needs `set_graph` only, survives `ens_reserve`): per scale s the window of
+    `r_lat[s]` rows either side and `r_lon[s, i']` longitudes either side in row i' (wrapping), as in `ens_derive_set`;
+    `r_lat` [S], `r_lon` [S, n_lat], S in 1..8; `row_wq` [n_lat] integer row weights in 1 .. 2^24 - 1
+    (`verification.quantize_row_weights`); the grid is n_lat x `n_lon` (None: G / n_lat), node = lat_i n_lon + lon_j.
+    `verification.EventSpec.windows` builds these arrays from `scales_km`."""
+    rl, ro = _i32(r_lat), _i32(r_lon)
+    if rl.ndim != 1 or not 1 <= rl.shape[0] <= 8:
+      raise ValueError(f"r_lat must hold 1..8 scales, got shape {rl.shape}")
+    if ro.ndim != 2 or ro.shape[0] != rl.shape[0] or ro.shape[1] < 1:
+      raise ValueError(f"r_lon must have shape ({rl.shape[0]}, n_lat), got {ro.shape}")
+    n_lat = int(ro.shape[1])
+    n_lon = self.num_grid_nodes // n_lat if n_lon is None else int(n_lon)
+    if n_lon < 1 or n_lat * n_lon != self.num_grid_nodes:
+      raise ValueError(f"n_lat * n_lon = {n_lat} * {n_lon} must equal the number of grid nodes {self.num_grid_nodes}")
+    if np.any(rl < 0):
+      raise ValueError("r_lat must be >= 0")
+    if np.any((ro < 0) | (ro > (n_lon - 1) // 2)):
+      raise ValueError(f"r_lon must lie in 0 .. {(n_lon - 1) // 2}")
+    w = np.asarray(row_wq)
+    if w.shape != (n_lat,) or w.dtype.kind not in "ui" or np.any(w < 1) or np.any(w > 2 ** 24 - 1):
+      raise ValueError(f"row_wq must be integers in 1 .. 2^24 - 1 of shape ({n_lat},)")
+    w = np.ascontiguousarray(w, dtype=np.uint32)
+    self._check(self._lib.gc_ens_fss_set(self._h, rl.shape[0], n_lat, n_lon, _ptr(rl, _i32p), _ptr(ro, _i32p),
+                                         _ptr(w, ctypes.POINTER(ctypes.c_uint32))))
+    self._fss_scales = int(rl.shape[0])
+
+  def ens_fss_score(self) -> np.ndarray:
+    """-> sums [T, S, B, c_out, 4] float64 of gc_ens_fss_score: sum w (P - O)^2, sum w (P^2 + O^2), sum w P, sum w O over the
+    counted centres, from the event codes the last `ens_event_score` left on the device (`verification.FractionsScores`
+    derives the scores)."""
+    if not self._fss_scales:
+      raise GencastHipError("libgencast_hip error 4: no plan (ens_fss_set has not been called on this object)")
+    if not self._event_thresholds:
+      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_event_set has not been called on this object)")
+    sums = np.empty((self._event_thresholds, self._fss_scales, self.cfg.batch, self.cfg.c_out, 4), dtype=np.float64)
+    self._check(self._lib.gc_ens_fss_score(self._h, _ptr(sums, ctypes.POINTER(ctypes.c_double))))
+    return sums
+
+  def ens_fss_fields(self, t: int, s: int):
+    """-> (prob, obs), float32 [G, B, c_out] each: the neighbourhood ensemble probability P and the observed fraction O of
+    threshold `t` at scale `s`, NaN where the point did not count (gc_ens_fss_fields)."""
+    if not self._fss_scales:
+      raise GencastHipError("libgencast_hip error 4: no plan (ens_fss_set has not been called on this object)")
+    if not self._event_thresholds:
+      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_event_set has not been called on this object)")
+    if not 0 <= int(t) < self._event_thresholds:
+      raise ValueError(f"t must lie in [0, {self._event_thresholds})")
+    if not 0 <= int(s) < self._fss_scales:
+      raise ValueError(f"s must lie in [0, {self._fss_scales})")
+    prob = np.empty(self._shape_out(), dtype=np.float32)
+    obs = np.empty(self._shape_out(), dtype=np.float32)
+    self._check(self._lib.gc_ens_fss_fields(self._h, int(t), int(s), _ptr(prob, _f32p), _ptr(obs, _f32p)))
+    return prob, obs
 
   # -- derived and pooled ensemble fields (formed on the device, into this handle's member store) -------
   def ens_derive_set(self, c_src: int, op, src_a, src_b, affine, pool: int = 0, n_lat: Optional[int] = None,

@@ -907,6 +907,8 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "ens_feature_calls") *value = h->feat_calls;
   else if (n == "ens_feature_device_us") *value = h->feat_device_us;
   else if (n == "ens_region_invalid_points") *value = h->reg_invalid_points;
+  else if (n == "ens_fss_calls") *value = h->fss_calls;
+  else if (n == "ens_fss_device_us") *value = h->fss_device_us;
   else if (n == "ens_window_pushes") *value = h->win_pushes;
   else if (n == "ens_window_emits") *value = h->win_emits;
   else if (n == "ens_window_device_us") *value = h->win_device_us;

@@ -15,7 +15,7 @@
 //   gc_tail.hip      gc_ens_tail_*
 //   gc_region.hip    gc_ens_region_*
 //   gc_feature.hip   gc_ens_feature_*
-// The last eleven are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
+// The last twelve are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
 // lead times of another, gc_feature.hip with the strike fields of the centres it finds in another).  What they share -- field length, upload through
 // the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
 // relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
@@ -475,6 +475,21 @@ struct gc_handle {
   gci::Bracket feat_time{events};                // of the last call
   gci::Event ev_feat_src{events};                // stream order behind the source handle
   int64_t feat_calls = 0, feat_device_us = 0;
+
+  // fractions skill score (gc_ens_fss_*, gc_fss.hip): the plan of the scales, and the row sums of a chunk of columns
+  gci::BufferGroup fss_allocs{groups};            // the plan's tables, one buffer: freed and replaced by gc_ens_fss_set; kept across gc_ens_reserve
+  gci::BufferGroup fss_work_allocs{groups};       // the work buffer, the partials and the sums: made again by the call that finds a size changed
+  int fss_S = 0;                                 // scales set (0: no plan)
+  int fss_n_lat = 0, fss_n_lon = 0;
+  std::vector<int32_t> fss_rlat;                 // [S], as on the device (gc_ens_fss_fields passes one by value)
+  int *d_fss_rlat = nullptr, *d_fss_rlon = nullptr;   // [S], [S][n_lat]
+  unsigned* d_fss_roww = nullptr;                // [n_lat] integer row weights
+  uint2* d_fss_work = nullptr;                   // [S + 1][G][chunk columns]: (k sum, o | counts << 16) of the row windows; last slab: two float fields
+  double* d_fss_part = nullptr;                  // [blocks][S][4][chunk columns] per-block column sums
+  double* d_fss_out = nullptr;                   // [T][S][B c_out][4]
+  size_t fss_work_len = 0, fss_part_len = 0, fss_out_len = 0;   // what the three are sized for
+  gci::Bracket fss_time{events};                 // of the last scoring call
+  int64_t fss_calls = 0, fss_device_us = 0;
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {

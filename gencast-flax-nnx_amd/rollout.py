@@ -1208,6 +1208,8 @@ class EnsembleRollout:
       specs = list(events) if isinstance(events, (list, tuple)) else [events]
       if len(specs) not in (1, horizon) or any(s.directions != specs[0].directions for s in specs):
         raise ValueError(f"events must be one EventSpec or {horizon} of them with equal directions")
+      if any(s.scales_km != specs[0].scales_km for s in specs):
+        raise ValueError("the EventSpecs of the lead times must have equal scales_km")
       run.thresholds = [packed(s, template0, scale, loc) for s in specs]
     if climatology is not None and not callable(climatology) and len(climatology) < horizon:
       raise ValueError(f"climatology must give the samples of {horizon} lead times, got {len(climatology)}")

@@ -46,6 +46,11 @@ chaining form of Allen et al. (2023) -- the plain CRPS of members and truth clam
 thresholds and directions are an `EventSpec`; the device sorts the members of a point once and hands back four raw sums per
 (threshold, batch, channel).  `TailScores` keeps them raw and derives the fair and the ensemble twCRPS.
 
+Fractions (`gc_ens_fss_score`): every event score above is point-wise.  An `EventSpec` with `scales_km`
+also gets, from the code bytes of the events, the neighbourhood ensemble probability against the observed fraction at up to
+eight radii; `FractionsScores` keeps the four raw sums per (threshold, scale, batch, channel) and derives the fractions skill
+score and the smallest skilful scale.  It rides on `EventScores.fractions`.
+
 Regions (`gc_ens_region_score`): the sums of `EnsembleScores` per named set of grid nodes -- tropics,
 extratropics, land, sea, boxes -- every region from one pass over the nodes that belong to any.  `RegionSpec` holds the masks
 and builds boxes from bounds; `RegionScores[name]` is the region's `EnsembleScores`.
@@ -477,6 +482,25 @@ def quantize_node_weights(w) -> Tuple[np.ndarray, float]:
   return np.rint(w * scale).astype(np.uint32), scale
 
 
+def quantize_row_weights(w, bits: int = 24) -> np.ndarray:
+  """-> row_wq [n_lat] uint32: max(1, rint(w 2^e)) in float64 with e the largest integer for which max(w) 2^e <= 2^bits - 1:
+  the integer latitude weights of the fractions windows (`gc_ens_fss_set`).  A row whose weight rounds to 0 -- the poles of
+  an equiangular grid -- keeps 1: a counted centre always has a window of positive weight.  `w` must be finite, >= 0 and not
+  all zero (ValueError), as in `quantize_node_weights`."""
+  w = np.asarray(w, dtype=np.float64).reshape(-1)
+  if w.size == 0 or not np.all(np.isfinite(w)) or np.any(w < 0.0) or not np.any(w > 0.0):
+    raise ValueError("row weights must be finite, >= 0 and not all zero")
+  if not 1 <= int(bits) <= 32:
+    raise ValueError("bits must lie in 1..32")
+  top, cap = float(w.max()), float(2 ** int(bits) - 1)
+  e = int(math.floor(math.log2(cap / top)))
+  while math.ldexp(top, e + 1) <= cap:                    # (ldexp by a power of two is exact: the comparisons are)
+    e += 1
+  while math.ldexp(top, e) > cap:
+    e -= 1
+  return np.maximum(1.0, np.rint(w * math.ldexp(1.0, e))).astype(np.uint32)
+
+
 def event_probability(code, n_members: int) -> Tuple[np.ndarray, np.ndarray]:
   """The per-point bytes of `NativeDenoiser.ens_event_codes` -> (probability k / M as float32, NaN where the point did
   not count; observed flag as bool, False there)."""
@@ -495,12 +519,25 @@ class EventSpec:
   dims other than batch and time (a scalar per event: shape (T,); per level: (T, level, 1, 1); a climatological map:
   (T, lat, lon)).  An array with one axis per dim of the variable after the leading one (batch and time included) is
   taken as the full field it is.  A target variable left out is NaN: not evaluated.  Values are cast to the dtype of the
-  target variable, so a threshold and a target of equal value stay equal through every map both go through."""
+  target variable, so a threshold and a target of equal value stay equal through every map both go through.
 
-  def __init__(self, thresholds: Mapping[str, np.ndarray], directions: Sequence[int]):
+  `scales_km`: None, or 1..8 neighbourhood radii in km, ascending (0: the point itself; in a pole row, whose nodes are one
+  point, the whole row, as `DerivedSpec.window` has it).  With them every `EventScores` of
+  the spec carries `.fractions` (`FractionsScores`): the fractions skill score of the neighbourhood ensemble probability at
+  each scale, over the great-circle windows of `DerivedSpec.window`."""
+
+  def __init__(self, thresholds: Mapping[str, np.ndarray], directions: Sequence[int], scales_km: Optional[Sequence[float]] = None):
     self.directions = tuple(int(np.sign(d)) for d in directions)
     if not self.directions or any(d == 0 for d in self.directions):
       raise ValueError("directions must be non-empty and non-zero")
+    self.scales_km = None
+    self.fractions_plan = None                             # `windows(template)` of the last `packed(template)`
+    if scales_km is not None:
+      scales = tuple(float(r) for r in np.asarray(scales_km, dtype=np.float64).reshape(-1))
+      if (not 1 <= len(scales) <= 8 or not all(math.isfinite(r) and r >= 0.0 for r in scales)
+          or any(b <= a for a, b in zip(scales, scales[1:]))):
+        raise ValueError("scales_km must be 1..8 finite radii >= 0 in ascending order")
+      self.scales_km = scales
     self.thresholds = {k: np.asarray(v, dtype=np.float64) for k, v in thresholds.items()}
     for k, v in self.thresholds.items():
       if v.ndim < 1 or v.shape[0] != len(self.directions):
@@ -543,11 +580,26 @@ class EventSpec:
     fields = self.fields(template)
     names = list(datasets.as_dataset(template).keys())
     return EventSpec({name: np.stack([np.asarray(fn(name, f[name]).data) for f in fields]) for name in names},
-                     self.directions)
+                     self.directions, self.scales_km)
+
+  def windows(self, template) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(r_lat [S] int32, r_lon [S, n_lat] int32, row_wq [n_lat] uint32): the arguments of `NativeDenoiser.ens_fss_set` --
+    `DerivedSpec.window` of every scale on the grid of `template`, and its latitude weights
+    (`losses.normalized_latitude_weights`) through `quantize_row_weights`."""
+    if self.scales_km is None:
+      raise ValueError("windows: the spec has no scales_km")
+    coords = datasets.as_dataset(template).coords
+    lat, lon = np.asarray(coords["lat"], np.float64), np.asarray(coords["lon"], np.float64)
+    per_scale = [DerivedSpec.window(lat, lon, r) for r in self.scales_km]
+    return (np.array([w[0] for w in per_scale], np.int32), np.stack([w[1] for w in per_scale]).astype(np.int32),
+            quantize_row_weights(losses.normalized_latitude_weights(lat)))
 
   def packed(self, template) -> np.ndarray:
-    """[T, G, B, c_out] float32 in the channel order of `datasets.channel_layout` (node = lat_i n_lon + lon_j)."""
+    """[T, G, B, c_out] float32 in the channel order of `datasets.channel_layout` (node = lat_i n_lon + lon_j).  With
+    `scales_km` the windows of the same grid are kept as `fractions_plan`, for the store that counts the events."""
     template = datasets.as_dataset(template)
+    if self.scales_km is not None:
+      self.fractions_plan = self.windows(template)
     sizes = template.sizes
     out = []
     for f in self.fields(template):
@@ -570,8 +622,12 @@ class EventScores(AdditiveScores):
   _listed = ("base_rate", "brier", "brier_fair", "reliability", "resolution", "uncertainty", "brier_skill", "roc_area",
              "valid_weight", "valid_points")
   _channel_axis = 2
+  fractions: Optional["FractionsScores"] = None            # the neighbourhood scores of an `EventSpec` with `scales_km`
 
-  def __init__(self, weighted, counts, n_members: int, directions: Sequence[int], scale: float, invalid=None):
+  def __init__(self, weighted, counts, n_members: int, directions: Sequence[int], scale: float, invalid=None, *,
+               fractions: Optional["FractionsScores"] = None):
+    if fractions is not None:                              # (absent from `vars(scores)` unless the spec had `scales_km`)
+      self.fractions = fractions
     self.weighted = np.asarray(weighted, dtype=np.uint64)
     self.counts = np.asarray(counts, dtype=np.uint64)
     self.n_members = int(n_members)
@@ -589,6 +645,18 @@ class EventScores(AdditiveScores):
       raise ValueError("scale must be positive and finite")
     self.invalid = (np.zeros(self.weighted.shape[0], np.uint64) if invalid is None
                     else np.asarray(invalid, dtype=np.uint64).reshape(self.weighted.shape[0]))
+
+  @classmethod
+  def merge(cls, parts):
+    """The tables add; `fractions` merge with them (`FractionsScores.merge`), and every part carries them or none does."""
+    parts = list(parts)
+    total = super().merge(parts)
+    carrying = [p.fractions for p in parts if p.fractions is not None]
+    if carrying:
+      if len(carrying) != len(parts):
+        raise ValueError("merge: only some of the event scores carry fractions scores")
+      total.fractions = FractionsScores.merge(carrying)
+    return total
 
   # -- the table in float64 (exact: see quantize_node_weights) -------------------------------------------------
   @property
@@ -703,6 +771,84 @@ class EventScores(AdditiveScores):
     e_clim, e_perf = np.minimum(alpha, s), alpha * s
     value = self._ratio(e_clim - e, e_clim - e_perf)
     return np.max(value, axis=3)                           # (the denominators do not depend on j: NaN at all levels or none)
+
+
+class FractionsScores(AdditiveScores):
+  """The raw sums of `gc_ens_fss_score`: `sums` [T, S, B, c_out, 4] float64 -- over the counted centres, with P the
+  neighbourhood ensemble probability, O the observed fraction of the neighbourhood and w the quantised node weight,
+  sum w (P - O)^2, sum w (P^2 + O^2), sum w P, sum w O -- and `weight` [T, B, c_out] uint64, the valid weight of the event
+  table (quantised, the same at every scale), with the member count M, the directions [T], the radii `scales_km` [S] and the
+  `scale` of the quantised node weights.  The sums are additive: the FSS over several dates is 1 - sum S0 / sum S1, never a
+  mean of scores.  Every score is [T, S, B, c_out] float64; a ratio whose denominator is zero is NaN, not an error."""
+  _adds = ("sums", "weight")
+  _same = {"n_members": "members", "directions": "directions", "scales_km": "scales", "scale": "scale"}
+  _listed = ("fss", "fbs", "fss_uniform", "forecast_fraction", "observed_fraction", "frequency_bias")
+  _channel_axis = 3
+  _what = "fractions scores"
+
+  def __init__(self, sums, weight, n_members: int, directions: Sequence[int], scales_km: Sequence[float], scale: float):
+    self.sums = np.asarray(sums, dtype=np.float64)
+    self.weight = np.asarray(weight, dtype=np.uint64)
+    self.n_members = int(n_members)
+    self.directions = tuple(int(np.sign(d)) for d in directions)
+    self.scales_km = tuple(float(r) for r in scales_km)
+    self.scale = float(scale)
+    if self.n_members < 2:
+      raise ValueError("n_members must be >= 2")
+    if self.sums.ndim != 5 or self.sums.shape[-1] != 4:
+      raise ValueError(f"sums must be [T, S, batch, channels, 4], got {self.sums.shape}")
+    if self.weight.shape != self.sums.shape[:1] + self.sums.shape[2:4]:
+      raise ValueError(f"weight must be {self.sums.shape[:1] + self.sums.shape[2:4]}, got {self.weight.shape}")
+    if len(self.directions) != self.sums.shape[0] or any(d == 0 for d in self.directions):
+      raise ValueError(f"directions must be {self.sums.shape[0]} non-zero signs")
+    if len(self.scales_km) != self.sums.shape[1]:
+      raise ValueError(f"scales_km must hold {self.sums.shape[1]} radii")
+    if not (self.scale > 0.0 and math.isfinite(self.scale)):
+      raise ValueError("scale must be positive and finite")
+
+  @property
+  def _w(self) -> np.ndarray:
+    """W [T, 1, B, c_out]: the valid weight in the units of the sums (the quantised weights as they are)."""
+    return self.weight.astype(np.float64)[:, None]
+
+  @property
+  def valid_weight(self) -> np.ndarray:
+    """[T, B, c_out]: the node weight of the points that counted, as `EventScores.valid_weight`."""
+    return self.weight.astype(np.float64) / self.scale
+
+  @property
+  def fss(self) -> np.ndarray:
+    return 1.0 - EventScores._ratio(self.sums[..., 0], self.sums[..., 1])
+
+  @property
+  def fbs(self) -> np.ndarray:
+    """The fractions Brier score: the weighted mean of (P - O)^2."""
+    return EventScores._ratio(self.sums[..., 0], self._w)
+
+  @property
+  def forecast_fraction(self) -> np.ndarray:
+    return EventScores._ratio(self.sums[..., 2], self._w)
+
+  @property
+  def observed_fraction(self) -> np.ndarray:
+    return EventScores._ratio(self.sums[..., 3], self._w)
+
+  @property
+  def fss_uniform(self) -> np.ndarray:
+    """0.5 + f0 / 2: the FSS of a uniform forecast of the observed fraction, the usual bar for "skilful"."""
+    return 0.5 + self.observed_fraction / 2.0
+
+  @property
+  def frequency_bias(self) -> np.ndarray:
+    return EventScores._ratio(self.sums[..., 2], self.sums[..., 3])
+
+  @property
+  def skilful_scale_km(self) -> np.ndarray:
+    """[T, B, c_out]: the smallest of `scales_km` at which fss >= fss_uniform, NaN if none."""
+    with np.errstate(invalid="ignore"):
+      ok = self.fss >= self.fss_uniform                    # (NaN compares False)
+    radii = np.asarray(self.scales_km, np.float64)[None, :, None, None]
+    return np.where(ok.any(axis=1), np.min(np.where(ok, radii, np.inf), axis=1), np.nan)
 
 
 class TailScores(AdditiveScores):
@@ -1113,10 +1259,13 @@ class FeatureSpec:
   a maximum: below) -- a closed low; `threshold`: the centre's value is at most (for a maximum: at least) this;
   `strike_km`: a node is struck by a centre within this radius.  Every radius is a number of km, or the window itself as
   (r_lat, r_lon) with r_lon one integer or one per latitude row.  Thresholds and depths are in physical units.
-  `max_centres` (1..1024): the entries a list keeps; the count and the strike field see all centres."""
+  `max_centres` (1..1024): the entries a list keeps; the count and the strike field see all centres.
+  `scales_km`: the neighbourhood radii of `event_spec()` (None: none) -- the fractions skill score of the strikes."""
 
-  def __init__(self, detectors: Mapping[str, Mapping[str, object]], max_centres: int = 64):
+  def __init__(self, detectors: Mapping[str, Mapping[str, object]], max_centres: int = 64,
+               scales_km: Optional[Sequence[float]] = None):
     self.detectors = {str(k): dict(v) for k, v in detectors.items()}
+    self.scales_km = EventSpec({}, [1], scales_km).scales_km   # (validated as an EventSpec's)
     if not 1 <= len(self.detectors) <= 8:
       raise ValueError(f"a FeatureSpec holds 1 to 8 detectors, got {len(self.detectors)}")
     if isinstance(max_centres, bool) or int(max_centres) != max_centres or not 1 <= int(max_centres) <= 1024:
@@ -1254,7 +1403,7 @@ class FeatureSpec:
   def event_spec(self) -> "EventSpec":
     """The one event of every strike field, `value > 0.5`: the Brier score, reliability curve, ROC area and economic value
     of the strike probability."""
-    return EventSpec({name: np.array([0.5]) for name in self.names}, [1])
+    return EventSpec({name: np.array([0.5]) for name in self.names}, [1], self.scales_km)
 
 
 def unpack_centres(count, node, value, plan=None) -> Dict[str, list]:
@@ -1703,9 +1852,30 @@ class Scorer(NamedTuple):
     return (self.name, self.name + "_normalized") if self.scaled else (self.name,)
 
 
+def _fractions_plan(store):
+  """The windows of the store's EventSpec (None without `scales_km`): made by `EventSpec.packed` for the store's own grid."""
+  spec = store.events
+  if getattr(spec, "scales_km", None) is None:
+    return None
+  if spec.fractions_plan is None:
+    raise ValueError("an EventSpec with scales_km needs its windows: call packed(template) (or windows) for the store's grid")
+  return spec.fractions_plan
+
+
+def _set_events(store):
+  store.handle.ens_event_set(store.thresholds, store.events.directions, store.weight_q[0])
+  plan = _fractions_plan(store)
+  if plan is not None:
+    store.handle.ens_fss_set(*plan)
+
+
 def _score_events(store, truth):
   weighted, counts, invalid = store.handle.ens_event_score(truth)
-  return EventScores(weighted, counts, store.n_members, store.events.directions, store.weight_q[1], invalid)
+  scores = EventScores(weighted, counts, store.n_members, store.events.directions, store.weight_q[1], invalid)
+  if _fractions_plan(store) is not None:
+    scores.fractions = FractionsScores(store.handle.ens_fss_score(), scores.weighted.sum(axis=(-1, -2)), store.n_members,
+                                       store.events.directions, store.events.scales_km, store.weight_q[1])
+  return scores
 
 
 def _score_order(store, truth):
@@ -1740,7 +1910,7 @@ SCORERS = [
     Scorer("scores", None, optional=False),
     Scorer("spectra", "spectra", optional=False, carried_by=("ensemble",)),
     Scorer("events", "events", ("thresholds", "weight_q"), scaled=False, optional=False, score=_score_events,
-           set=lambda s: s.handle.ens_event_set(s.thresholds, s.events.directions, s.weight_q[0])),
+           set=_set_events),                                                   # (the fractions of the events ride on this row)
     Scorer("order", "order statistics", optional=False, score=_score_order, set=lambda s: s.handle.ens_order_set(s.order)),
     Scorer("climatology", "climatology scores", optional=False, carried_by=("ensemble", "derived")),
     Scorer("energy", "energy scores", scaled=False, score=_score_energy,         # (in the store's own units: no `scaled`)

@@ -908,6 +908,47 @@ int gc_ens_feature_centres(gc_handle* dst, int32_t* count /* [M + 1][B][D] */, i
                            float* value /* [M + 1][B][D][max_centres] */);
 
 /*
+ * Fractions skill score on the device: every event score above is point-wise, so a sharp forecast that
+ * puts a maximum two grid points beside the analysis is punished twice.  The fractions skill score (Roberts & Lean 2008) of
+ * the neighbourhood ensemble probability (Schwartz et al. 2010) compares the fraction of a neighbourhood in the event,
+ * forecast against observed, at up to 8 neighbourhood sizes from one pass over the code bytes gc_ens_event_score left on the
+ * device.  The reference project has no verification code; the yardstick is the definition below, restated in
+ * tests/fss_reference.py.
+ * Inputs, on a handle whose last gc_ens_event_score is still valid: the codes code_t [G, B, c_out] for t < T, the member
+ * count M they were made with, the node weights wq [G] of gc_ens_event_set.  A point counts iff code != 255; there
+ * k = code & 127 and o = code >> 7.  The plan: S scales (1 <= S <= 8), the grid n_lat n_lon = G (node = lat_i n_lon + lon_j),
+ * per scale r_lat[s] >= 0 and r_lon[s][i] in 0 .. (n_lon - 1) / 2, integer row weights 1 <= row_wq[i] <= 2^24 - 1.  Win_s(i, j)
+ * is the window of gc_ens_derive: latitude clipped, longitude wrapping, the width of a row that of the row i'.
+ * Per counted centre p = (i, j), over the counted q in Win_s(p), in integers:
+ *   A = sum row_wq[i'] k(q),   B = sum row_wq[i'] o(q),   N = sum row_wq[i']       (below 2^51 for G <= 2^21, M <= 64)
+ * then in double, each operation rounded once and nothing contracted:
+ *   P = (double) A / ((double) M (double) N),   O = (double) B / (double) N        (N >= row_wq[i] >= 1)
+ * Per (t, s, b, c) four double sums over the counted centres, w = (double) wq[g]:
+ *   sums[0] = sum w ((P - O)(P - O)),  sums[1] = sum w (P P + O O),  sums[2] = sum w P,  sums[3] = sum w O
+ * formed without float atomics and in a fixed order: two calls give the same bytes.  A column with no counted point gives
+ * four zeros.  FSS = 1 - sums[0] / sums[1]; over several dates 1 - sum sums[0] / sum sums[1]: the sums add, scores do not.
+ *   gc_ens_fss_set     the plan, through pinned staging (the caller's arrays are free on return).  Needs gc_set_graph only.
+ *                      Replaces an earlier plan ("device_allocations" stays flat), survives gc_ens_reserve, released by
+ *                      gc_destroy.  GC_ERR_STATE: no graph.  GC_ERR_UNSUPPORTED: S outside 1..8, n_lon > 16384.
+ *                      GC_ERR_INVALID_ARGUMENT: a null pointer, n_lat n_lon != G, r_lat[s] < 0, an r_lon out of range, a
+ *                      row_wq of 0 or above 2^24 - 1.
+ *   gc_ens_fss_score   sums [T][S][B][c_out][4].  Per threshold and chunk of columns a row pass (prefix sums of one latitude
+ *                      row in LDS, the row-window sums of every scale from that one prefix), a column pass with a block
+ *                      reduction and a finish pass, over a handle-owned work buffer of at most max(256 MiB,
+ *                      8 (S + 1) G tile) bytes.  Synchronous.
+ *   gc_ens_fss_fields  for one (t, s): prob = (float) P and obs = (float) O, each [G, B, c_out], NaN where the point does
+ *                      not count.  GC_ERR_INVALID_ARGUMENT: t outside [0, T), s outside [0, S), a null pointer.
+ * Both: GC_ERR_STATE without a graph, a plan, or valid codes -- a gc_ens_event_set, gc_ens_reserve, gc_ens_derive,
+ * gc_ens_window_emit or gc_ens_feature since the last gc_ens_event_score invalidates them.
+ * None of these entries touches the sampler state, the member store, the codes, the event tables or the captured sample
+ * graphs.  Counters: "ens_fss_calls" (scoring calls so far), "ens_fss_device_us" (HIP-event time of the last call's launches).
+ */
+int gc_ens_fss_set(gc_handle* h, int32_t n_scales, int32_t n_lat, int32_t n_lon, const int32_t* r_lat /* [S] */,
+                   const int32_t* r_lon /* [S][n_lat] */, const uint32_t* row_wq /* [n_lat] */);
+int gc_ens_fss_score(gc_handle* h, double* sums /* [T][S][B][c_out][4] */);
+int gc_ens_fss_fields(gc_handle* h, int32_t threshold, int32_t scale, float* prob /* [G,B,c_out] */, float* obs /* [G,B,c_out] */);
+
+/*
  * Ensemble exchange.  Replaces: the replication of inputs / forcings over the local
  * devices in chunked_prediction_generator_multiple_runs (common/rollout.py:41-75 `_replicate_dataset`,
  * :123-139 `device_put_sharded`); members then run independently, one per GPU (:312-322), and are
