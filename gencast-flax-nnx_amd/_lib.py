@@ -126,6 +126,11 @@ SIGNATURES = {
     "gc_ens_fss_fields": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p]),
     "gc_ens_derive_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int32,
                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_derive_set_expr": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _i32p, ctypes.c_int32,
+                                              ctypes.POINTER(ctypes.c_double), _i32p, _i32p, ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_double, _i32p]),
     "gc_ens_derive": (ctypes.c_int, [_hp, _hp, _f32p]),
     "gc_ens_order_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
     "gc_ens_order_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -728,22 +733,38 @@ class NativeDenoiser:
 
   # -- derived and pooled ensemble fields (formed on the device, into this handle's member store) -------
   def ens_derive_set(self, c_src: int, op, src_a, src_b, affine, pool: int = 0, n_lat: Optional[int] = None,
-                     n_lon: Optional[int] = None, r_lat: int = 0, r_lon=None, row_weight=None) -> None:
+                     n_lon: Optional[int] = None, r_lat: int = 0, r_lon=None, row_weight=None, *, scale=None, loc=None,
+                     term_start=None, term_coef=None, term_a=None, term_b=None, coslat=None, inv_rcos=None, inv_dphi=None,
+                     inv_2dlam=None, pole_row=None) -> None:
     """The plan of `ens_derive` for this handle's c_out = c_d derived channels (gc_ens_derive_set; needs `set_graph` only,
     survives `ens_reserve`).  `op` [c_d]: 0 copy of source channel `src_a[j]`, 1 norm2 = sqrt(u^2 + v^2) in double with
     u = x[src_a[j]] sa + la, v = x[src_b[j]] sb + lb and `affine[j]` = (sa, la, sb, lb).  `pool`: 0 none, 1 max, 2 min,
     3 mean over the window of `r_lat` rows either side and `r_lon[i']` longitudes either side in row i' (wrapping), the mean
     weighted with `row_weight[i']`; `n_lat` x `n_lon` is the grid (node = lat_i n_lon + lon_j).  `verification.DerivedSpec`
-    builds these arrays from variable names."""
+    builds these arrays from variable names.
+
+    With `scale` and `loc` [c_src] the plan goes through gc_ens_derive_set_expr and `op` may also be 2 sum, 3 norm (term
+    lists: `term_start` [c_d, 3], `term_coef`, `term_a`, `term_b` [n_terms]), 4 vorticity and 5 divergence of u = `src_a[j]`,
+    v = `src_b[j]` (row tables `coslat`, `inv_rcos`, `inv_dphi`, `pole_row` [n_lat] and `inv_2dlam`); include/gencast_hip.h
+    has the definitions.  Without them the call is gc_ens_derive_set, as before."""
     c_d = self.cfg.c_out
     if int(c_src) < 1:
       raise ValueError("c_src must be positive")
     o, a, b = _i32(op), _i32(src_a), _i32(src_b)
     if o.shape != (c_d,) or a.shape != (c_d,) or b.shape != (c_d,):
       raise ValueError(f"op, src_a and src_b must have shape ({c_d},)")
-    if np.any((o != 0) & (o != 1)):
-      raise ValueError("op must be 0 (copy) or 1 (norm2)")
-    if np.any((a < 0) | (a >= c_src)) or np.any((o == 1) & ((b < 0) | (b >= c_src))):
+    expr = scale is not None or loc is not None
+    if not expr:
+      given = dict(term_start=term_start, term_coef=term_coef, term_a=term_a, term_b=term_b, coslat=coslat, inv_rcos=inv_rcos,
+                   inv_dphi=inv_dphi, inv_2dlam=inv_2dlam, pole_row=pole_row)
+      if any(v is not None for v in given.values()):
+        raise ValueError(f"{sorted(k for k, v in given.items() if v is not None)} need scale and loc")
+      if np.any((o != 0) & (o != 1)):
+        raise ValueError("op must be 0 (copy) or 1 (norm2)")
+    elif np.any((o < 0) | (o > 5)):
+      raise ValueError("op must be 0 (copy), 1 (norm2), 2 (sum), 3 (norm), 4 (vorticity) or 5 (divergence)")
+    lists = (o == 2) | (o == 3)
+    if np.any(~lists & ((a < 0) | (a >= c_src))) or np.any(~lists & (o != 0) & ((b < 0) | (b >= c_src))):
       raise ValueError(f"a source channel lies outside [0, {int(c_src)})")
     aff = np.ascontiguousarray(affine, dtype=np.float64)
     if aff.shape != (c_d, 4):
@@ -767,9 +788,50 @@ class NativeDenoiser:
         raise ValueError(f"r_lon must lie in 0 .. {(int(n_lon) - 1) // 2}")
       if not np.all(np.isfinite(w) & (w > 0.0)):
         raise ValueError("row_weight must be finite and > 0")
-    self._check(self._lib.gc_ens_derive_set(self._h, int(c_src), _ptr(o, _i32p), _ptr(a, _i32p), _ptr(b, _i32p), _ptr(aff, dp),
-                                            int(pool), int(n_lat), int(n_lon), int(r_lat),
-                                            None if r is None else _ptr(r, _i32p), None if w is None else _ptr(w, dp)))
+    if not expr:
+      self._check(self._lib.gc_ens_derive_set(self._h, int(c_src), _ptr(o, _i32p), _ptr(a, _i32p), _ptr(b, _i32p), _ptr(aff, dp),
+                                              int(pool), int(n_lat), int(n_lon), int(r_lat),
+                                              None if r is None else _ptr(r, _i32p), None if w is None else _ptr(w, dp)))
+      self._derive_c_src = int(c_src)
+      return
+    if scale is None or loc is None:
+      raise ValueError("scale and loc go together")
+    sc, lo = (np.ascontiguousarray(v, dtype=np.float64) for v in (scale, loc))
+    if sc.shape != (int(c_src),) or lo.shape != (int(c_src),) or not (np.isfinite(sc).all() and np.isfinite(lo).all()):
+      raise ValueError(f"scale and loc must be finite and have shape ({int(c_src)},)")
+    tc = np.ascontiguousarray(np.zeros(0) if term_coef is None else term_coef, dtype=np.float64).reshape(-1)
+    ta, tb = (_i32(np.zeros(0, np.int32) if v is None else v).reshape(-1) for v in (term_a, term_b))
+    if not tc.shape == ta.shape == tb.shape:
+      raise ValueError("term_coef, term_a and term_b must have one entry per term")
+    if not np.isfinite(tc).all():
+      raise ValueError("a term coefficient is not finite")
+    if np.any((ta < 0) | (ta >= c_src) | (tb < -1) | (tb >= c_src)):
+      raise ValueError(f"a term's source channel lies outside [0, {int(c_src)}) (term_b: -1 for none)")
+    ts = None
+    if lists.any():
+      if term_start is None:
+        raise ValueError("a sum or norm channel needs term_start")
+      ts = _i32(term_start)
+      if ts.shape != (c_d, 3):
+        raise ValueError(f"term_start must have shape ({c_d}, 3)")
+      s0, s1, s2 = ts[lists].T
+      if np.any((s0 < 0) | (s1 <= s0) | (s2 < s1) | (s2 > tc.size) | ((s2 > s1) != (o[lists] == 3))):
+        raise ValueError("term_start: a sum takes one list of terms inside the table, a norm two, none of them empty")
+    rows = [None] * 4
+    if np.any(o >= 4):
+      if any(v is None for v in (coslat, inv_rcos, inv_dphi, inv_2dlam, pole_row)):
+        raise ValueError("vorticity and divergence need coslat, inv_rcos, inv_dphi, inv_2dlam and pole_row")
+      if int(n_lon) < 3 or int(n_lat) < 2:
+        raise ValueError("vorticity and divergence need n_lon >= 3 and n_lat >= 2")
+      rows = [np.ascontiguousarray(v, dtype=np.float64) for v in (coslat, inv_rcos, inv_dphi)] + [_i32(pole_row)]
+      if any(v.shape != (int(n_lat),) for v in rows):
+        raise ValueError(f"coslat, inv_rcos, inv_dphi and pole_row must have shape ({int(n_lat)},)")
+    self._check(self._lib.gc_ens_derive_set_expr(
+        self._h, int(c_src), _ptr(o, _i32p), _ptr(a, _i32p), _ptr(b, _i32p), _ptr(aff, dp), int(pool), int(n_lat), int(n_lon),
+        int(r_lat), None if r is None else _ptr(r, _i32p), None if w is None else _ptr(w, dp), _ptr(sc, dp), _ptr(lo, dp),
+        None if ts is None else _ptr(ts, _i32p), int(tc.size), _ptr(tc, dp), _ptr(ta, _i32p), _ptr(tb, _i32p),
+        *(None if v is None else _ptr(v, dp) for v in rows[:3]), 0.0 if inv_2dlam is None else float(inv_2dlam),
+        None if rows[3] is None else _ptr(rows[3], _i32p)))
     self._derive_c_src = int(c_src)
 
   def ens_derive(self, src: "NativeDenoiser", truth=None) -> None:

@@ -13,6 +13,12 @@
 //   column   per point the intermediates of the rows |i' - i| <= r_lat (clipped at the poles) combined -- the mean with
 //            row_weight[i'] -- and written over the centre; NaN where the centre itself is not finite.
 // No atomics: every output has one writer and every sum a fixed order, so two calls give the same bytes.
+//
+// A plan set through gc_ens_derive_set_expr has four more derive ops, all in physical units
+// p(c) = (double) x[c] scale[c] + loc[c] and rounded to float32 once: SUM and NORM of term lists sum_t coef_t p(a_t) [p(b_t)]
+// (thickness, shear, column integrals, IVT), and VORTICITY and DIVERGENCE of a (u, v) pair by centred differences on the
+// sphere.  Its derive pass is gc_ens_derive_expr_kernel, followed -- where the grid has pole rows and the plan one of the
+// last two ops -- by gc_ens_derive_pole_kernel; the pooling passes behind them are the same.
 #include "gc_store.h"
 
 // the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
@@ -20,13 +26,17 @@
 
 namespace gc {
 
-enum { kDrvCopy = 0, kDrvNorm2 = 1 };
+enum { kDrvCopy = 0, kDrvNorm2 = 1, kDrvSum = 2, kDrvNorm = 3, kDrvVort = 4, kDrvDiv = 5 };
 enum { kPoolNone = 0, kPoolMax = 1, kPoolMin = 2, kPoolMean = 3 };
 constexpr int kDrvChunk = 8;                     // fields the intermediate holds: the M + 1 fields go through it in chunks
 constexpr size_t kDrvRowLds = 64 * 1024;         // the staged row tile of a workgroup: 2 workgroups per CU (160 KB)
 constexpr int kDrvMaxTile = 32;                  // columns of a row tile: 32 lanes x 4 bytes = one 128-byte line per longitude
 constexpr int kDrvRegs = 64;                     // max pass: tile elements per thread (kDrvRowLds / 4 / 256)
 constexpr int kDrvMeanBytes = 12;                // mean pass: a double prefix sum and an int32 prefix count per tile element
+constexpr int kDrvListTerms = 64;                // terms of one list (37 ERA5 levels fit), and of a whole plan: the term table
+constexpr int kDrvPlanTerms = 1024;              // is staged in LDS at kDrvTermBytes a term, 48 KB at the most
+constexpr int kDrvTermBytes = 48;                // coef, sa, la, sb, lb (double), a, b (int32)
+constexpr int kDrvPoleLon = 8191;                // pole pass: n_lon + 1 doubles of LDS, 64 KB at the most
 
 // field z of a store: member z, or the truth behind the last member
 __device__ inline const float* drv_field(const float* mem, const float* truth, size_t field, int M, int z) {
@@ -67,6 +77,155 @@ __global__ __launch_bounds__(256) void gc_ens_derive_kernel(const float* __restr
     const double v = (double)__uint_as_float(from[n * Ws + cb]) * sb + lb;
     to[n * W] = __float_as_uint((float)sqrt(u * u + v * v));
   }
+}
+
+// ---- the ops of gc_ens_derive_set_expr ---------------------------------------------------------------------------------------
+// the tables of such a plan, all in device memory (one blob: gc_ens_derive_set_expr)
+struct DrvExpr {
+  const int *op, *src_a, *src_b;                   // [c_d]; VORTICITY / DIVERGENCE: the u and the v channel
+  const double* affine;                            // [c_d][4]: NORM2 as given; VORTICITY / DIVERGENCE (su, lu, sv, lv)
+  const int* tstart;                               // [c_d][3]: list 1 is [s0, s1), list 2 [s1, s2) of the term table
+  const double* tq;                                // [5][n_terms]: coef, scale[a], loc[a], scale[b], loc[b]
+  const int *ta, *tb;                              // [n_terms]; tb = -1: no second factor
+  const double *coslat, *inv_rcos, *inv_dphi;      // [n_lat]
+  const int* pole;                                 // [n_lat]
+  double inv_2dlam;
+  int n_terms, n_lat, n_lon;
+};
+
+// S = sum_t coef_t p(a_t) [p(b_t)] over the terms [t0, t1), ascending; q, ta, tb: the staged term table; row: the thread's
+// (node, b) row of source channels
+__device__ inline double drv_term_sum(const unsigned* __restrict__ row, int t0, int t1, const double* q, const int* ta,
+                                      const int* tb, int nT) {
+  double S = 0.0;
+  for (int t = t0; t < t1; ++t) {
+    double term = q[t] * ((double)__uint_as_float(row[ta[t]]) * q[nT + t] + q[2 * nT + t]);
+    const int b = tb[t];
+    if (b >= 0) term = term * ((double)__uint_as_float(row[b]) * q[3 * nT + t] + q[4 * nT + t]);
+    S = S + term;
+  }
+  return S;
+}
+
+// The double result of VORTICITY (vort) or DIVERGENCE at row i (not a pole row), longitude l.  from: the field's batch b.
+// One field is differenced along the longitude (v for the vorticity, u for the divergence), the other, times cos(lat),
+// along the latitude over the rows i- = max(i - 1, 0) and i+ = min(i + 1, n_lat - 1).
+__device__ inline double drv_curl(const unsigned* __restrict__ from, size_t Ws, int i, int l, bool vort, int cu, int cv,
+                                  double su, double lu, double sv, double lv, const DrvExpr& g) {
+  const int lm = l == 0 ? g.n_lon - 1 : l - 1, lp = l + 1 == g.n_lon ? 0 : l + 1;
+  const int im = max(i - 1, 0), ip = min(i + 1, g.n_lat - 1);
+  const int ca = vort ? cv : cu, cb = vort ? cu : cv;
+  const double sa = vort ? sv : su, la = vort ? lv : lu, sb = vort ? su : sv, lb = vort ? lu : lv;
+  const size_t r = (size_t)i * g.n_lon;
+  const double ap = (double)__uint_as_float(from[(r + lp) * Ws + ca]) * sa + la;
+  const double am = (double)__uint_as_float(from[(r + lm) * Ws + ca]) * sa + la;
+  const double bp = (double)__uint_as_float(from[((size_t)ip * g.n_lon + l) * Ws + cb]) * sb + lb;
+  const double bm = (double)__uint_as_float(from[((size_t)im * g.n_lon + l) * Ws + cb]) * sb + lb;
+  const double x = ap - am;
+  const double y = bp * g.coslat[ip] - bm * g.coslat[im];
+  const double t1 = x * g.inv_2dlam, t2 = y * g.inv_dphi[i];
+  return (vort ? t1 - t2 : t1 + t2) * g.inv_rcos[i];
+}
+
+// Derive pass of a gc_ens_derive_set_expr plan: grid and thread layout of gc_ens_derive_kernel.  The term table is staged
+// in LDS once per workgroup (dynamic, kDrvTermBytes a term): the lanes of a wave own different derived columns and walk
+// different lists, which LDS serves at a few cycles a step where a global table would cost a cache line each.  The source
+// row of a node is read straight from global memory by the c_d threads of its (node, b): with few derived columns the lanes
+// of a wave sit on different rows and every load touches a line per lane, which is what bounds a long list (DESIGN.md
+// section 8p has the measurement).  A pole row of VORTICITY / DIVERGENCE is left to gc_ens_derive_pole_kernel.
+__global__ __launch_bounds__(256) void gc_ens_derive_expr_kernel(const float* __restrict__ smem, const float* __restrict__ struth,
+                                                                  float* __restrict__ dmem, float* __restrict__ dtruth, int M,
+                                                                  int G, int B, int c_src, int c_d, DrvExpr g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char drv_lds[];
+  const int nT = g.n_terms;
+  double* const q = reinterpret_cast<double*>(drv_lds);
+  int* const ta = reinterpret_cast<int*>(q + (size_t)5 * nT);
+  int* const tb = ta + nT;
+  for (int t = threadIdx.x; t < 5 * nT; t += 256) q[t] = g.tq[t];
+  for (int t = threadIdx.x; t < nT; t += 256) {
+    ta[t] = g.ta[t];
+    tb[t] = g.tb[t];
+  }
+  __syncthreads();
+  const int W = B * c_d, Ws = B * c_src;
+  const int col0 = blockIdx.y * 256;
+  const int wt = min(256, W - col0);
+  const int nq = 256 / wt;
+  const int lane = threadIdx.x / wt;
+  if (lane >= nq) return;
+  const int col = col0 + ((int)threadIdx.x - lane * wt);
+  const int b = col / c_d, j = col - b * c_d;
+  const int z = blockIdx.z;
+  const unsigned* const from = reinterpret_cast<const unsigned*>(drv_field(smem, struth, (size_t)G * Ws, M, z)) + (size_t)b * c_src;
+  unsigned* const to = reinterpret_cast<unsigned*>(drv_field(dmem, dtruth, (size_t)G * W, M, z)) + col;
+  const int o = g.op[j];
+  const size_t n0 = (size_t)blockIdx.x * nq + lane, dn = (size_t)gridDim.x * nq;
+  if (o == kDrvCopy) {                             // the same bits: a NaN keeps its payload
+    const int ca = g.src_a[j];
+    for (size_t n = n0; n < (size_t)G; n += dn) to[n * W] = from[n * Ws + ca];
+    return;
+  }
+  if (o == kDrvSum || o == kDrvNorm) {
+    const int s0 = g.tstart[3 * j], s1 = g.tstart[3 * j + 1], s2 = g.tstart[3 * j + 2];
+    for (size_t n = n0; n < (size_t)G; n += dn) {
+      const unsigned* const row = from + n * Ws;
+      double S = drv_term_sum(row, s0, s1, q, ta, tb, nT);
+      if (o == kDrvNorm) {
+        const double S2 = drv_term_sum(row, s1, s2, q, ta, tb, nT);
+        S = sqrt(S * S + S2 * S2);
+      }
+      to[n * W] = __float_as_uint((float)S);
+    }
+    return;
+  }
+  const int ca = g.src_a[j], cb = g.src_b[j];
+  const double sa = g.affine[4 * j], la = g.affine[4 * j + 1], sb = g.affine[4 * j + 2], lb = g.affine[4 * j + 3];
+  if (o == kDrvNorm2) {
+    for (size_t n = n0; n < (size_t)G; n += dn) {
+      const double u = (double)__uint_as_float(from[n * Ws + ca]) * sa + la;
+      const double v = (double)__uint_as_float(from[n * Ws + cb]) * sb + lb;
+      to[n * W] = __float_as_uint((float)sqrt(u * u + v * v));
+    }
+    return;
+  }
+  for (size_t n = n0; n < (size_t)G; n += dn) {      // VORTICITY, DIVERGENCE
+    const int i = (int)(n / g.n_lon), l = (int)(n - (size_t)i * g.n_lon);
+    if (g.pole[i]) continue;
+    to[n * W] = __float_as_uint((float)drv_curl(from, Ws, i, l, o == kDrvVort, ca, cb, sa, la, sb, lb, g));
+  }
+}
+
+// Pole pass of VORTICITY / DIVERGENCE: a pole is one point, so every longitude of a pole row gets the zonal mean of the
+// adjacent row's double results, summed in ascending longitude by one thread (a fixed order) and divided by n_lon.
+// grid = (derived columns, the two end rows, M + 1); a workgroup whose column has another op, or whose row is no pole row,
+// returns at once.  Dynamic LDS: n_lon + 1 doubles.
+__global__ __launch_bounds__(256) void gc_ens_derive_pole_kernel(const float* __restrict__ smem, const float* __restrict__ struth,
+                                                                  float* __restrict__ dmem, float* __restrict__ dtruth, int M,
+                                                                  int G, int B, int c_src, int c_d, DrvExpr g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char drv_lds[];
+  double* const val = reinterpret_cast<double*>(drv_lds);
+  const int col = blockIdx.x;
+  const int b = col / c_d, j = col - b * c_d;
+  const int o = g.op[j];
+  const int i = blockIdx.y ? g.n_lat - 1 : 0;
+  if ((o != kDrvVort && o != kDrvDiv) || !g.pole[i]) return;
+  const int ia = i == 0 ? 1 : g.n_lat - 2;         // n_lat >= 2, and the row next to a pole row is no pole row: the plan
+  const int W = B * c_d, Ws = B * c_src;
+  const int z = blockIdx.z;
+  const unsigned* const from = reinterpret_cast<const unsigned*>(drv_field(smem, struth, (size_t)G * Ws, M, z)) + (size_t)b * c_src;
+  unsigned* const to = reinterpret_cast<unsigned*>(drv_field(dmem, dtruth, (size_t)G * W, M, z)) + col;
+  const int ca = g.src_a[j], cb = g.src_b[j];
+  const double sa = g.affine[4 * j], la = g.affine[4 * j + 1], sb = g.affine[4 * j + 2], lb = g.affine[4 * j + 3];
+  for (int l = threadIdx.x; l < g.n_lon; l += 256) val[l] = drv_curl(from, Ws, ia, l, o == kDrvVort, ca, cb, sa, la, sb, lb, g);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int l = 0; l < g.n_lon; ++l) s = s + val[l];
+    val[g.n_lon] = s / (double)g.n_lon;
+  }
+  __syncthreads();
+  const unsigned out = __float_as_uint((float)val[g.n_lon]);
+  for (int l = threadIdx.x; l < g.n_lon; l += 256) to[((size_t)i * g.n_lon + l) * W] = out;
 }
 
 // Row pass, max (and min, on the negated values).  grid = (column tiles of wt, n_lat, fields of the chunk); wt is a power
@@ -266,6 +425,24 @@ static hipError_t launch_ens_derive(hipStream_t s, const float* smem, const floa
   return hipGetLastError();
 }
 
+static hipError_t launch_ens_derive_expr(hipStream_t s, const float* smem, const float* struth, float* dmem, float* dtruth, int M,
+                                         int G, int B, int c_src, int c_d, const DrvExpr& g) {
+  const int W = B * c_d;
+  const int q = 256 / std::min(256, W);
+  const int blocks = std::max(1, std::min(1024, (G + q - 1) / q));
+  hipLaunchKernelGGL(gc_ens_derive_expr_kernel, dim3(blocks, (W + 255) / 256, M + 1), dim3(256), (size_t)g.n_terms * kDrvTermBytes,
+                     s, smem, struth, dmem, dtruth, M, G, B, c_src, c_d, g);
+  return hipGetLastError();
+}
+
+static hipError_t launch_ens_derive_pole(hipStream_t s, const float* smem, const float* struth, float* dmem, float* dtruth, int M,
+                                         int G, int B, int c_src, int c_d, const DrvExpr& g) {
+  const int W = B * c_d;
+  hipLaunchKernelGGL(gc_ens_derive_pole_kernel, dim3(W, 2, M + 1), dim3(256), (size_t)(g.n_lon + 1) * sizeof(double), s, smem,
+                     struth, dmem, dtruth, M, G, B, c_src, c_d, g);
+  return hipGetLastError();
+}
+
 static hipError_t launch_ens_pool_row(hipStream_t s, int pool, const float* mem, const float* truth, size_t field, int M, int z0,
                                       int nz, int n_lat, int n_lon, int W, const int* r_lon, void* inter) {
   const int wt = drv_tile(pool, n_lon, W);
@@ -365,6 +542,155 @@ int gc_ens_derive_set(gc_handle* h, int32_t c_src, const int32_t* op, const int3
   h->drv_n_lat = n_lat;
   h->drv_n_lon = n_lon;
   h->drv_r_lat = r_lat;
+  h->drv_expr = false;
+  h->drv_set = true;
+  return GC_OK;
+  });
+}
+
+int gc_ens_derive_set_expr(gc_handle* h, int32_t c_src, const int32_t* op, const int32_t* src_a, const int32_t* src_b,
+                           const double* affine, int32_t pool, int32_t n_lat, int32_t n_lon, int32_t r_lat, const int32_t* r_lon,
+                           const double* row_weight, const double* scale, const double* loc, const int32_t* term_start,
+                           int32_t n_terms, const double* term_coef, const int32_t* term_a, const int32_t* term_b,
+                           const double* coslat, const double* inv_rcos, const double* inv_dphi, double inv_2dlam,
+                           const int32_t* pole_row) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (pool < gc::kPoolNone || pool > gc::kPoolMean) return fail(h, GC_ERR_UNSUPPORTED, "pool must be 0 (none), 1 (max), 2 (min) or 3 (mean)");
+  if (!op || !src_a || !src_b || !affine || !scale || !loc || (pool != gc::kPoolNone && (!r_lon || !row_weight)))
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (c_src < 1) return fail(h, GC_ERR_INVALID_ARGUMENT, "c_src must be positive");
+  if (n_lat < 1 || n_lon < 1 || (int64_t)n_lat * n_lon != (int64_t)h->hg.G)
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "n_lat * n_lon must equal the number of grid nodes");
+  for (int c = 0; c < c_src; ++c)
+    if (!std::isfinite(scale[c]) || !std::isfinite(loc[c])) return fail(h, GC_ERR_INVALID_ARGUMENT, "scale / loc of source channel " + std::to_string(c) + " is not finite");
+  if (n_terms < 0) return fail(h, GC_ERR_INVALID_ARGUMENT, "n_terms is negative");
+  if (n_terms > gc::kDrvPlanTerms) return fail(h, GC_ERR_UNSUPPORTED, "more than " + std::to_string(gc::kDrvPlanTerms) + " terms in one plan");
+  if (n_terms > 0 && (!term_coef || !term_a || !term_b)) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  for (int t = 0; t < n_terms; ++t) {
+    if (!std::isfinite(term_coef[t])) return fail(h, GC_ERR_INVALID_ARGUMENT, "the coefficient of term " + std::to_string(t) + " is not finite");
+    if (term_a[t] < 0 || term_a[t] >= c_src || term_b[t] < -1 || term_b[t] >= c_src)
+      return fail(h, GC_ERR_INVALID_ARGUMENT, "term " + std::to_string(t) + ": source channel outside [0, c_src)");
+  }
+  const int c_d = h->cfg.c_out, W = h->cfg.batch * c_d;
+  bool curl = false;
+  for (int j = 0; j < c_d; ++j) {
+    const std::string who = "derived channel " + std::to_string(j);
+    if (op[j] < gc::kDrvCopy || op[j] > gc::kDrvDiv)
+      return fail(h, GC_ERR_UNSUPPORTED, "op " + std::to_string(j) + " is none of 0 (copy), 1 (norm2), 2 (sum), 3 (norm), 4 (vorticity), 5 (divergence)");
+    if (op[j] == gc::kDrvSum || op[j] == gc::kDrvNorm) {
+      if (!term_start) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+      const int s0 = term_start[3 * j], s1 = term_start[3 * j + 1], s2 = term_start[3 * j + 2];
+      if (s0 < 0 || s1 <= s0 || s2 < s1 || s2 > n_terms || (s2 > s1) != (op[j] == gc::kDrvNorm))
+        return fail(h, GC_ERR_INVALID_ARGUMENT, who + ": a sum takes one list of terms inside the table, a norm two, none of them empty");
+      if (s1 - s0 > gc::kDrvListTerms || s2 - s1 > gc::kDrvListTerms)
+        return fail(h, GC_ERR_UNSUPPORTED, who + ": more than " + std::to_string(gc::kDrvListTerms) + " terms in one list");
+      continue;
+    }
+    curl = curl || op[j] >= gc::kDrvVort;
+    if (src_a[j] < 0 || src_a[j] >= c_src || (op[j] != gc::kDrvCopy && (src_b[j] < 0 || src_b[j] >= c_src)))
+      return fail(h, GC_ERR_INVALID_ARGUMENT, who + ": source channel outside [0, c_src)");
+  }
+  bool poles = false;
+  if (curl) {
+    if (!coslat || !inv_rcos || !inv_dphi || !pole_row) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_lon < 3 || n_lat < 2) return fail(h, GC_ERR_INVALID_ARGUMENT, "vorticity and divergence need n_lon >= 3 and n_lat >= 2");
+    if (!(std::isfinite(inv_2dlam) && inv_2dlam != 0.0)) return fail(h, GC_ERR_INVALID_ARGUMENT, "1 / (2 dlambda) is not finite and non-zero");
+    for (int i = 0; i < n_lat; ++i) {
+      const std::string row = "row " + std::to_string(i);
+      if (!std::isfinite(coslat[i]) || !(std::isfinite(inv_dphi[i]) && inv_dphi[i] != 0.0))
+        return fail(h, GC_ERR_INVALID_ARGUMENT, row + ": cos(lat) or 1 / dphi is not finite (or 1 / dphi is zero)");
+      if (pole_row[i]) {
+        const int next = i == 0 ? 1 : n_lat - 2;
+        if ((i != 0 && i != n_lat - 1) || coslat[i] != 0.0 || pole_row[next])
+          return fail(h, GC_ERR_INVALID_ARGUMENT, row + ": a pole row is an end row with cos(lat) = 0 next to a row that is none");
+        poles = true;
+      } else if (!std::isfinite(inv_rcos[i])) {
+        return fail(h, GC_ERR_INVALID_ARGUMENT, row + ": 1 / (R cos(lat)) is not finite");
+      }
+    }
+    if (poles && n_lon > gc::kDrvPoleLon) return fail(h, GC_ERR_UNSUPPORTED, "n_lon is too large for the pole pass (64 KB of LDS)");
+  }
+  if (r_lat < 0) return fail(h, GC_ERR_INVALID_ARGUMENT, "r_lat is negative");
+  if (pool != gc::kPoolNone) {
+    for (int i = 0; i < n_lat; ++i) {
+      if (r_lon[i] < 0 || r_lon[i] > (n_lon - 1) / 2) return fail(h, GC_ERR_INVALID_ARGUMENT, "r_lon[" + std::to_string(i) + "] outside 0 .. (n_lon - 1) / 2");
+      if (!(std::isfinite(row_weight[i]) && row_weight[i] > 0.0)) return fail(h, GC_ERR_INVALID_ARGUMENT, "row_weight[" + std::to_string(i) + "] is not finite and positive");
+    }
+    if (gc::drv_tile(pool, n_lon, W) == 0) return fail(h, GC_ERR_UNSUPPORTED, "n_lon is too large for the row tile of this pool (64 KB of LDS)");
+  }
+  GC_HIP(h, hipSetDevice(h->device));
+  // one blob.  doubles: affine [c_d][4], row_weight [n_lat], the term table [5][n_terms], the row tables [3][n_lat];
+  // int32: op, src_a, src_b [c_d], r_lon [n_lat], term_start [c_d][3], term_a, term_b [n_terms], pole_row [n_lat]
+  const size_t nT = (size_t)n_terms;
+  const size_t o_roww = (size_t)4 * c_d, o_tq = o_roww + n_lat, o_rows = o_tq + 5 * nT, n_d = o_rows + (size_t)3 * n_lat;
+  const size_t i_rlon = (size_t)3 * c_d, i_ts = i_rlon + n_lat, i_ta = i_ts + (size_t)3 * c_d, i_tb = i_ta + nT, i_pole = i_tb + nT,
+               n_i = i_pole + n_lat;
+  std::vector<double> blob(n_d + (n_i + 1) / 2);
+  int32_t* const ib = reinterpret_cast<int32_t*>(blob.data() + n_d);
+  for (int j = 0; j < c_d; ++j) {
+    const bool pair = op[j] == gc::kDrvNorm2 || op[j] >= gc::kDrvVort, list = op[j] == gc::kDrvSum || op[j] == gc::kDrvNorm;
+    const int a = list ? 0 : src_a[j], b = pair ? src_b[j] : a;
+    ib[j] = op[j];
+    ib[c_d + j] = a;
+    ib[2 * c_d + j] = b;
+    for (int k = 0; k < 3; ++k) ib[i_ts + 3 * j + k] = list ? term_start[3 * j + k] : 0;
+    double* const aff = blob.data() + 4 * j;
+    if (op[j] >= gc::kDrvVort) {                     // (su, lu, sv, lv): the components in physical units
+      aff[0] = scale[a], aff[1] = loc[a], aff[2] = scale[b], aff[3] = loc[b];
+    } else {
+      std::copy(affine + 4 * j, affine + 4 * j + 4, aff);
+    }
+  }
+  for (int i = 0; i < n_lat; ++i) {
+    blob[o_roww + i] = pool != gc::kPoolNone ? row_weight[i] : 1.0;
+    ib[i_rlon + i] = pool != gc::kPoolNone ? r_lon[i] : 0;
+    blob[o_rows + i] = curl ? coslat[i] : 0.0;
+    blob[o_rows + n_lat + i] = curl && !pole_row[i] ? inv_rcos[i] : 0.0;
+    blob[o_rows + 2 * (size_t)n_lat + i] = curl ? inv_dphi[i] : 0.0;
+    ib[i_pole + i] = curl && pole_row[i] ? 1 : 0;
+  }
+  for (size_t t = 0; t < nT; ++t) {
+    const int a = term_a[t], b = term_b[t];
+    blob[o_tq + t] = term_coef[t];
+    blob[o_tq + nT + t] = scale[a];
+    blob[o_tq + 2 * nT + t] = loc[a];
+    blob[o_tq + 3 * nT + t] = b >= 0 ? scale[b] : 1.0;
+    blob[o_tq + 4 * nT + t] = b >= 0 ? loc[b] : 0.0;
+    ib[i_ta + t] = a;
+    ib[i_tb + t] = b;
+  }
+  GC_HIP(h, h->drv_allocs.drop(h->stream));          // nothing reads the old plan any more
+  h->drv_set = false;
+  int rc;
+  double* d_blob = nullptr;
+  if ((rc = dev_alloc(h, &d_blob, blob.size(), &h->drv_allocs))) return rc;
+  GC_HIP(h, h->drv_time.ensure());
+  GC_HIP(h, h->ev_drv_src.ensure());
+  if ((rc = store_upload(h, d_blob, blob.data(), blob.size() * sizeof(double)))) return rc;
+  int* const d_ib = reinterpret_cast<int*>(d_blob + n_d);
+  h->d_drv_affine = d_blob;
+  h->d_drv_roww = d_blob + o_roww;
+  h->d_drv_tq = d_blob + o_tq;
+  h->d_drv_rows = d_blob + o_rows;
+  h->d_drv_op = d_ib;
+  h->d_drv_a = d_ib + c_d;
+  h->d_drv_b = d_ib + 2 * c_d;
+  h->d_drv_rlon = d_ib + i_rlon;
+  h->d_drv_tstart = d_ib + i_ts;
+  h->d_drv_ta = d_ib + i_ta;
+  h->d_drv_tb = d_ib + i_tb;
+  h->d_drv_pole = d_ib + i_pole;
+  h->drv_n_terms = n_terms;
+  h->drv_inv_2dlam = curl ? inv_2dlam : 0.0;
+  h->drv_poles = poles;
+  h->drv_c_src = c_src;
+  h->drv_pool = pool;
+  h->drv_n_lat = n_lat;
+  h->drv_n_lon = n_lon;
+  h->drv_r_lat = r_lat;
+  h->drv_expr = true;
   h->drv_set = true;
   return GC_OK;
   });
@@ -403,9 +729,21 @@ int gc_ens_derive(gc_handle* h, gc_handle* src, const float* truth) {
   h->has_ens_fields = false;
   h->ord_ready = false;
   GC_HIP(h, h->drv_time.begin(s));
+  const int n_lat = h->drv_n_lat;
+  const gc::DrvExpr g{h->d_drv_op, h->d_drv_a, h->d_drv_b, h->d_drv_affine, h->d_drv_tstart, h->d_drv_tq, h->d_drv_ta, h->d_drv_tb,
+                      h->d_drv_rows, h->d_drv_rows + n_lat, h->d_drv_rows + 2 * (size_t)n_lat, h->d_drv_pole, h->drv_inv_2dlam,
+                      h->drv_n_terms, n_lat, h->drv_n_lon};      // read by the plans of gc_ens_derive_set_expr only
   if ((rc = launch(h, gc::KC_PACK, [&] {
+         if (h->drv_expr)
+           return gc::launch_ens_derive_expr(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out,
+                                             c_d, g);
          return gc::launch_ens_derive(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out, c_d,
                                       h->d_drv_op, h->d_drv_a, h->d_drv_b, h->d_drv_affine);
+       })))
+    return rc;
+  if (h->drv_expr && h->drv_poles &&
+      (rc = launch(h, gc::KC_PACK, [&] {
+         return gc::launch_ens_derive_pole(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out, c_d, g);
        })))
     return rc;
   if (pool != gc::kPoolNone) {

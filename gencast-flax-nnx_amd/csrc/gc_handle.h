@@ -363,6 +363,13 @@ struct gc_handle {
   int drv_c_src = 0, drv_pool = 0, drv_n_lat = 0, drv_n_lon = 0, drv_r_lat = 0;
   double *d_drv_affine = nullptr, *d_drv_roww = nullptr;       // [c_out][4] (sa, la, sb, lb), [n_lat]
   int *d_drv_op = nullptr, *d_drv_a = nullptr, *d_drv_b = nullptr, *d_drv_rlon = nullptr;   // [c_out] x 3, [n_lat]
+  // a plan of gc_ens_derive_set_expr: its further tables lie in the same buffer of drv_allocs and go with it
+  bool drv_expr = false;                         // the plan in force came through gc_ens_derive_set_expr
+  bool drv_poles = false;                        // ... and has a vorticity / divergence channel on a grid with a pole row
+  int drv_n_terms = 0;
+  double drv_inv_2dlam = 0.0;
+  double *d_drv_tq = nullptr, *d_drv_rows = nullptr;           // [5][n_terms] (coef, sa, la, sb, lb), [3][n_lat] (cos, 1 / (R cos), 1 / dphi)
+  int *d_drv_tstart = nullptr, *d_drv_ta = nullptr, *d_drv_tb = nullptr, *d_drv_pole = nullptr;   // [c_out][3], [n_terms] x 2, [n_lat]
   unsigned char* d_drv_work = nullptr;           // 8 fields of row-pooled values: a float (max, min), or a double and an int32 (mean), per point
   size_t drv_work_bytes = 0;
   gci::Bracket drv_time{events};                               // of the last call

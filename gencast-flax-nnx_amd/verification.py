@@ -24,7 +24,9 @@ physical units down to the packed fields; `event_probability` decodes the per-po
 Derived fields (`gc_ens_derive`): `DerivedSpec` names variables that are no model channels (wind speed:
 the norm of two components, in physical units) and one spatial pooling (max, min or area-weighted mean over a neighbourhood
 of fixed great-circle radius); the device forms them from a member store into the store of a second handle, where every
-scorer above works unchanged.
+scorer above works unchanged.  The same spec forms combinations across pressure levels (sums and norms of terms coef a b:
+thickness, shear, column integrals, integrated vapour transport, one level of a variable) and horizontal derivatives on the
+sphere (relative vorticity, divergence), through `gc_ens_derive_set_expr`.
 
 Order statistics (`gc_ens_order_score`): the device sorts the M members of every point and hands back,
 per (batch, channel), the bin sums `bins[k] = (sum w alpha_k, sum w beta_k)` of Hersbach's (2000) decomposition of the
@@ -1075,19 +1077,32 @@ class RegionScores:
 # ---------------------------------------------------------------------------------------------
 _KM_PER_DEGREE = 111.195                                   # one degree of a great circle on the mean Earth radius 6371 km
 _POOLS = {None: 0, "none": 0, "max": 1, "min": 2, "mean": 3}
+_DERIVE_OPS = {"copy": 0, "norm2": 1, "sum": 2, "norm": 3, "vorticity": 4, "divergence": 5}
 
 
 class DerivedSpec:
-  """What `gc_ens_derive` makes of a member store: an ordered list of derived variables, then one
-  spatial pooling for all of them.
+  """What `gc_ens_derive` makes of a member store (DESIGN.md sections 8g and 8p): an ordered list of derived variables, then
+  one spatial pooling for all of them.
 
   `outputs`: `("copy", name)` keeps a target variable; `("norm2", new_name, name_a, name_b)` is sqrt(a^2 + b^2) of two
   target variables IN PHYSICAL UNITS, channel by channel (10 m wind speed from the two 10 m components: one channel; wind
-  speed on 13 levels from the two components on levels: 13) -- `name_a` and `name_b` must have equal channel counts.  The
-  derived channels are packed like every Dataset here, in sorted-name order (`datasets.channel_layout(self.template(...))`).
+  speed on 13 levels from the two components on levels: 13) -- `name_a` and `name_b` must have equal channel counts.
+
+  Across levels, in physical units (section 8p): `("sum", new_name, terms)` is sum_t coef_t a_t [b_t] and `("norm", new_name,
+  terms_1, terms_2)` the norm of two such sums.  A term is `(coef, (variable, level))` or `(coef, (variable, level), (variable,
+  level))`, the level by INDEX as in `FeatureSpec`, None only for a variable of one channel; at most 64 terms in a list.  The
+  result is one channel with the dims of the first source without `level`.  `select`, `thickness`, `shear`,
+  `column_integral` and `ivt` build such tuples.  Along the grid: `("vorticity", new_name, u, v[, level])` and `("divergence",
+  ...)` by centred differences on the sphere -- without a level channel by channel like norm2, with one a single channel
+  without the `level` dim.  They need an equiangular grid of at least 3 longitudes round the whole circle.
+
+  The derived channels are packed like every Dataset here, in sorted-name order (`datasets.channel_layout(self.template(...))`).
   `pool`: None, "max", "min" or "mean" over a window of `r_lat` rows either side (clipped at the poles) and `r_lon[i']`
   longitudes either side in row i' (wrapping) -- given as they are, or as `radius_km` (`window`).  The mean is weighted with
   `losses.normalized_latitude_weights`."""
+
+  MAX_LIST_TERMS, MAX_PLAN_TERMS = 64, 1024              # the caps of gc_ens_derive_set_expr
+  EARTH_RADIUS_M = 6371000.0
 
   def __init__(self, outputs, pool: Optional[str] = None, radius_km: Optional[float] = None, r_lat: Optional[int] = None,
                r_lon: Optional[Sequence[int]] = None):
@@ -1095,13 +1110,23 @@ class DerivedSpec:
     if not self.outputs:
       raise ValueError("outputs must name at least one derived variable")
     names = []
-    for o in self.outputs:
+    for k, o in enumerate(self.outputs):
       if len(o) == 2 and o[0] == "copy":
-        names.append(o[1])
+        pass
       elif len(o) == 4 and o[0] == "norm2":
-        names.append(o[1])
+        pass
+      elif len(o) == 3 and o[0] == "sum":
+        self.outputs[k] = o[:2] + (self._terms(o[1], o[2]),)
+      elif len(o) == 4 and o[0] == "norm":
+        self.outputs[k] = o[:2] + (self._terms(o[1], o[2]), self._terms(o[1], o[3]))
+      elif len(o) in (4, 5) and o[0] in ("vorticity", "divergence"):
+        if len(o) == 5 and o[4] is not None and (isinstance(o[4], bool) or int(o[4]) != o[4]):
+          raise ValueError(f"{o[1]!r}: the level must be an index or None, got {o[4]!r}")
       else:
-        raise ValueError(f"an output must be ('copy', name) or ('norm2', new_name, name_a, name_b), got {o!r}")
+        raise ValueError("an output must be ('copy', name), ('norm2', new_name, name_a, name_b), ('sum', new_name, terms), "
+                         "('norm', new_name, terms_1, terms_2) or ('vorticity' | 'divergence', new_name, u_name, v_name[, level]), "
+                         f"got {o!r}")
+      names.append(o[1])
     if len(set(names)) != len(names):
       raise ValueError(f"derived variable names must be distinct, got {names}")
     if pool not in _POOLS:
@@ -1124,45 +1149,146 @@ class DerivedSpec:
     self.r_lat = None if r_lat is None else int(r_lat)
     self.r_lon = None if r_lon is None else np.asarray(r_lon, dtype=np.int64).reshape(-1)
 
+  @classmethod
+  def _terms(cls, name, terms):
+    """One term list, checked and normalised to ((coef, (variable, level), (variable, level) or None), ...)."""
+    try:
+      terms = [tuple(t) for t in terms]
+    except TypeError:
+      raise ValueError(f"{name!r}: a term list is a sequence of (coef, (variable, level)[, (variable, level)])") from None
+    if not 1 <= len(terms) <= cls.MAX_LIST_TERMS:
+      raise ValueError(f"{name!r}: a term list has 1 .. {cls.MAX_LIST_TERMS} terms, got {len(terms)}")
+    out = []
+    for t in terms:
+      if len(t) not in (2, 3):
+        raise ValueError(f"{name!r}: a term is (coef, (variable, level)) or (coef, (variable, level), (variable, level)), got {t!r}")
+      if isinstance(t[0], (str, bytes)) or not math.isfinite(float(t[0])):
+        raise ValueError(f"{name!r}: the coefficient of {t!r} is not a finite number")
+      factors = []
+      for f in t[1:]:
+        if isinstance(f, str) or len(tuple(f)) != 2 or not isinstance(f[0], str) or \
+           not (f[1] is None or (not isinstance(f[1], bool) and int(f[1]) == f[1])):
+          raise ValueError(f"{name!r}: a factor is (variable, level index or None), got {f!r}")
+        factors.append((f[0], None if f[1] is None else int(f[1])))
+      out.append((float(t[0]), factors[0], factors[1] if len(factors) == 2 else None))
+    return tuple(out)
+
+  # ---- helpers that only build output tuples --------------------------------------------------------------------------
+  @staticmethod
+  def select(name, var, level):
+    """One level of a multi-level variable as a variable of its own, in physical units."""
+    return ("sum", name, [(1.0, (var, level))])
+
+  @staticmethod
+  def thickness(name, var, upper, lower, g: float = 9.80665):
+    """(var[upper] - var[lower]) / g: the thickness in metres of the layer between two levels of the geopotential."""
+    return ("sum", name, [(1.0 / g, (var, upper)), (-1.0 / g, (var, lower))])
+
+  @staticmethod
+  def shear(name, u, v, upper, lower):
+    """|(u, v)[upper] - (u, v)[lower]|: the vertical wind shear between two levels."""
+    return ("norm", name, [(1.0, (u, upper)), (-1.0, (u, lower))], [(1.0, (v, upper)), (-1.0, (v, lower))])
+
+  @staticmethod
+  def pressure_weights(levels_hPa, g: float = 9.80665) -> np.ndarray:
+    """The trapezoid weights dp / g of a column integral, dp in Pa: half the distance between the neighbouring levels, half
+    intervals at the two ends.  Either order of the levels."""
+    p = 100.0 * np.asarray(levels_hPa, np.float64).reshape(-1)
+    if p.size < 2 or not np.isfinite(p).all() or np.any(np.diff(p) == 0) or np.any(np.sign(np.diff(p)) != np.sign(p[1] - p[0])):
+      raise ValueError("levels_hPa must be at least two finite pressures in ascending or descending order")
+    d = np.abs(np.diff(p))
+    return np.concatenate([[d[0]], d[:-1] + d[1:], [d[-1]]]) / (2.0 * g)
+
+  @staticmethod
+  def column_integral(name, var, levels_hPa):
+    """(1 / g) int var dp over all levels of `var` (total column water vapour from the specific humidity)."""
+    return ("sum", name, [(float(w), (var, k)) for k, w in enumerate(DerivedSpec.pressure_weights(levels_hPa))])
+
+  @staticmethod
+  def ivt(name, q, u, v, levels_hPa):
+    """|(1 / g) int q (u, v) dp|: the integrated vapour transport."""
+    w = DerivedSpec.pressure_weights(levels_hPa)
+    return ("norm", name, [(float(x), (q, k), (u, k)) for k, x in enumerate(w)], [(float(x), (q, k), (v, k)) for k, x in enumerate(w)])
+
   @property
   def names(self) -> List[str]:
     return [o[1] for o in self.outputs]
 
+  @property
+  def legacy(self) -> bool:
+    """Only copy / norm2 outputs: the plan of gc_ens_derive_set."""
+    return all(o[0] in ("copy", "norm2") for o in self.outputs)
+
+  @staticmethod
+  def _channel(where, who, var, level) -> int:
+    """The source channel of (variable, level index or None) in the packed order `where`."""
+    if var not in where:
+      raise ValueError(f"{var!r} is not a target variable")
+    off, n = where[var]
+    if level is None:
+      if n != 1:
+        raise ValueError(f"{who!r}: {var!r} has {n} levels: name one (level index)")
+      return off
+    if not 0 <= level < n:
+      raise ValueError(f"{who!r}: level {level!r} of {var!r} outside 0 .. {n - 1}")
+    return off + level
+
   def _sources(self, template0):
-    """{derived name: (op, [(offset, n) of each source])} with the channel counts checked."""
+    """{derived name: (op, [(offset, n) of each source] | the term lists with channels | (u, v) first channels, count)},
+    with the variables, levels and channel counts checked."""
     template0 = datasets.as_dataset(template0)
     where = {name: (off, n) for name, off, n in datasets.channel_layout(template0)}
     out = {}
     for o in self.outputs:
-      srcs = o[1:] if o[0] == "copy" else o[2:]
+      if o[0] in ("sum", "norm"):
+        out[o[1]] = (o[0], [[(c, self._channel(where, o[1], *fa), -1 if fb is None else self._channel(where, o[1], *fb))
+                             for c, fa, fb in terms] for terms in o[2:]])
+        continue
+      srcs = o[1:] if o[0] == "copy" else o[2:4]
       for s in srcs:
         if s not in where:
           raise ValueError(f"{s!r} is not a target variable")
-      if o[0] == "norm2" and where[srcs[0]][1] != where[srcs[1]][1]:
-        raise ValueError(f"{srcs[0]!r} has {where[srcs[0]][1]} channels, {srcs[1]!r} {where[srcs[1]][1]}: the norm is taken "
-                         "channel by channel")
+      if o[0] in ("vorticity", "divergence") and len(o) == 5 and o[4] is not None:
+        out[o[1]] = (o[0], [(self._channel(where, o[1], s, int(o[4])), 1) for s in srcs])
+        continue
+      if o[0] != "copy" and where[srcs[0]][1] != where[srcs[1]][1]:
+        raise ValueError(f"{srcs[0]!r} has {where[srcs[0]][1]} channels, {srcs[1]!r} {where[srcs[1]][1]}: the "
+                         f"{'norm' if o[0] == 'norm2' else o[0]} is taken channel by channel")
       out[o[1]] = (o[0], [where[s] for s in srcs])
     return out
 
   def template(self, template0) -> datasets.Dataset:
-    """A Dataset of the derived variables (zeros) with the dims of their (first) source variable and the source's
-    coordinates: `EventSpec.packed`, `EnsembleScores.per_variable` and `EventScores.per_variable` work on it unchanged."""
+    """A Dataset of the derived variables (zeros) with the dims of their (first) source variable -- without `level` where the
+    output is one channel formed across or at a level -- and the source's coordinates: `EventSpec.packed`,
+    `EnsembleScores.per_variable` and `EventScores.per_variable` work on it unchanged."""
     template0 = datasets.as_dataset(template0)
     self._sources(template0)
     out = {}
     for o in self.outputs:
-      src = template0[o[1] if o[0] == "copy" else o[2]]
-      out[o[1]] = datasets.Variable(src.dims, np.zeros_like(np.asarray(src.data)))
+      flat = o[0] in ("sum", "norm") or (o[0] in ("vorticity", "divergence") and len(o) == 5 and o[4] is not None)
+      src = template0[o[1] if o[0] == "copy" else o[2][0][1][0] if o[0] in ("sum", "norm") else o[2]]
+      data = np.asarray(src.data)
+      if flat and "level" in src.dims:
+        data = np.take(data, 0, axis=src.dims.index("level"))
+        out[o[1]] = datasets.Variable(tuple(d for d in src.dims if d != "level"), np.zeros_like(data))
+      else:
+        out[o[1]] = datasets.Variable(src.dims, np.zeros_like(data))
     return datasets.Dataset(out, template0.coords)
 
   def _per_channel(self, template0):
-    """[(op, channel of source a, channel of source b)] per derived channel, in the packed order of `template`."""
+    """[(op, channel of source a, channel of source b, term lists or None)] per derived channel, in the packed order of
+    `template`."""
     srcs = self._sources(template0)
     rows = []
     for name, _, n in datasets.channel_layout(self.template(template0)):
       op, where = srcs[name]
+      if op in ("sum", "norm"):
+        if n != 1:
+          raise ValueError(f"{name!r}: its first source has dims beyond 'level': a {op} is one channel")
+        rows.append((op, 0, 0, where))
+        continue
       for k in range(n):
-        rows.append((op, where[0][0] + k, where[-1][0] + k))
+        rows.append((op, where[0][0] + k, where[-1][0] + k, None))
     return rows
 
   @staticmethod
@@ -1192,7 +1318,7 @@ class DerivedSpec:
     if scale.shape != (c_src,) or loc.shape != (c_src,):
       raise ValueError(f"scale and loc must have shape ({c_src},)")
     rows = self._per_channel(template0)
-    op = np.array([1 if r[0] == "norm2" else 0 for r in rows], np.int32)
+    op = np.array([_DERIVE_OPS[r[0]] for r in rows], np.int32)
     src_a = np.array([r[1] for r in rows], np.int32)
     src_b = np.array([r[2] for r in rows], np.int32)
     affine = np.tile(np.array([1.0, 0.0, 1.0, 0.0]), (len(rows), 1))
@@ -1205,6 +1331,8 @@ class DerivedSpec:
     n_lat, n_lon = int(sizes["lat"]), int(sizes["lon"])
     out = dict(c_src=c_src, op=op, src_a=src_a, src_b=src_b, affine=affine, pool=_POOLS[self.pool], n_lat=n_lat, n_lon=n_lon,
                r_lat=0, r_lon=None, row_weight=None)
+    if not self.legacy:
+      out.update(self._expr_tables(template0, rows, scale, loc))
     if self.pool is not None:
       if self.radius_km is not None:
         r_lat, r_lon = self.window(template0.coords["lat"], template0.coords["lon"], self.radius_km)
@@ -1219,8 +1347,51 @@ class DerivedSpec:
                  row_weight=np.asarray(losses.normalized_latitude_weights(template0), np.float64))
     return out
 
+  def _expr_tables(self, template0, rows, scale, loc) -> Dict[str, object]:
+    """The further keywords of a plan with a sum, norm, vorticity or divergence channel (gc_ens_derive_set_expr): the
+    statistics, the term table, and for the last two ops the row tables of the grid."""
+    starts, coef, ta, tb = np.zeros((len(rows), 3), np.int32), [], [], []
+    for j, r in enumerate(rows):
+      if r[3] is not None:
+        starts[j, 0] = len(coef)
+        for k, terms in enumerate(r[3]):
+          coef += [t[0] for t in terms]
+          ta += [t[1] for t in terms]
+          tb += [t[2] for t in terms]
+          starts[j, k + 1:] = len(coef)
+    if len(coef) > self.MAX_PLAN_TERMS:
+      raise ValueError(f"the plan has {len(coef)} terms: at most {self.MAX_PLAN_TERMS}")
+    out = dict(scale=scale.copy(), loc=loc.copy(), term_start=starts, term_coef=np.asarray(coef, np.float64),
+               term_a=np.asarray(ta, np.int32), term_b=np.asarray(tb, np.int32), coslat=None, inv_rcos=None, inv_dphi=None,
+               inv_2dlam=None, pole_row=None)
+    if not any(r[0] in ("vorticity", "divergence") for r in rows):
+      return out
+    if "lat" not in template0.coords or "lon" not in template0.coords:
+      raise ValueError("vorticity and divergence need the template's 'lat' and 'lon' coordinates")
+    lat, lon = (np.asarray(template0.coords[k], np.float64).reshape(-1) for k in ("lat", "lon"))
+    if lon.size < 3:
+      raise ValueError(f"vorticity and divergence need at least 3 longitudes, got {lon.size}")
+    if lat.size < 2:
+      raise ValueError(f"vorticity and divergence need at least 2 latitudes, got {lat.size}")
+    dlat, dlon = np.diff(lat), np.diff(lon)
+    if dlat[0] == 0 or not np.allclose(dlat, dlat[0], rtol=1e-6, atol=0.0):
+      raise ValueError("vorticity and divergence need equally spaced latitudes (the centred difference is second order only there)")
+    if dlon[0] == 0 or not np.allclose(dlon, dlon[0], rtol=1e-6, atol=0.0) or not np.isclose(abs(dlon[0]) * lon.size, 360.0, rtol=1e-6):
+      raise ValueError("vorticity and divergence need equally spaced longitudes round the whole circle")
+    pole = np.abs(lat) >= 90.0 - 1e-9
+    if pole[1:-1].any() or (pole[0] and pole[1]) or (pole[-1] and pole[-2]):
+      raise ValueError("only an end row of the grid can be a pole row, next to a row that is none")
+    phi = np.deg2rad(lat)
+    cos = np.where(pole, 0.0, np.cos(phi))
+    idx = np.arange(lat.size)
+    with np.errstate(divide="ignore"):
+      inv_rcos = np.where(pole, 0.0, 1.0 / (self.EARTH_RADIUS_M * np.where(pole, 1.0, cos)))
+    out.update(coslat=cos, inv_rcos=inv_rcos, inv_dphi=1.0 / (phi[np.minimum(idx + 1, lat.size - 1)] - phi[np.maximum(idx - 1, 0)]),
+               inv_2dlam=float(1.0 / (2.0 * np.deg2rad(dlon[0]))), pole_row=pole.astype(np.int32))
+    return out
+
   def channel_stats(self, template0, scale=None, loc=None) -> Tuple[np.ndarray, np.ndarray]:
-    """(scale_d, loc_d) [c_d]: a copy channel keeps its source's, a norm2 channel is in physical units already: (1, 0)."""
+    """(scale_d, loc_d) [c_d]: a copy channel keeps its source's, every other channel is in physical units already: (1, 0)."""
     template0 = datasets.as_dataset(template0)
     c_src = sum(n for _, _, n in datasets.channel_layout(template0))
     scale = np.ones(c_src) if scale is None else np.asarray(scale, np.float64).reshape(-1)
@@ -1228,8 +1399,8 @@ class DerivedSpec:
     if scale.shape != (c_src,) or loc.shape != (c_src,):
       raise ValueError(f"scale and loc must have shape ({c_src},)")
     rows = self._per_channel(template0)
-    return (np.array([1.0 if r[0] == "norm2" else scale[r[1]] for r in rows]),
-            np.array([0.0 if r[0] == "norm2" else loc[r[1]] for r in rows]))
+    return (np.array([scale[r[1]] if r[0] == "copy" else 1.0 for r in rows]),
+            np.array([loc[r[1]] if r[0] == "copy" else 0.0 for r in rows]))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -582,6 +582,48 @@ int gc_ens_derive_set(gc_handle* dst, int32_t c_src, const int32_t* op, const in
 int gc_ens_derive(gc_handle* dst, gc_handle* src, const float* truth /* [G,B,c_src] host, NULL = src's last truth */);
 
 /*
+ * Derived fields across levels and along the grid: a plan with four more ops for step 1 of
+ * gc_ens_derive.  gc_ens_derive_set_expr takes everything gc_ens_derive_set takes, with the same meaning and the same
+ * errors, plus the tables below; gc_ens_derive runs whichever plan was set last, and everything behind step 1 (pooling,
+ * the truth, the stream order, the scorers of dst) is unchanged.  gc_ens_derive_set itself is unchanged.
+ * In the new ops a source channel c enters in physical units, p(c) = (double) x[c] scale[c] + loc[c], with scale, loc
+ * [c_src] finite.  All arithmetic is in double without fused multiply-adds, the result is rounded to float32 once, no
+ * atomics are used and two calls give the same bytes; non-finite inputs propagate by IEEE rules.
+ *   SUM  (2)   d = (float) S1,                       S = sum_t coef_t p(a_t) (b_t >= 0 ? p(b_t) : 1), the terms of a list
+ *   NORM (3)   d = (float) sqrt(S1 S1 + S2 S2)       added in ascending t, each term formed as (coef p(a)) p(b)
+ *              term_start [c_out][3] = (s0, s1, s2): list 1 is the terms [s0, s1) and list 2 [s1, s2) of the table term_coef,
+ *              term_a, term_b [n_terms]; SUM has s2 == s1.  Read for SUM and NORM channels only.  Geopotential thickness,
+ *              wind shear, one level of a variable, column integrals, integrated vapour transport.
+ *   VORTICITY (4), DIVERGENCE (5) of u = p(src_a), v = p(src_b) on the grid node = i n_lon + j.  The host passes per row
+ *              i: coslat[i] = cos(lat_i), inv_rcos[i] = 1 / (R cos(lat_i)) with R = 6 371 000 m, inv_dphi[i] =
+ *              1 / (lat_i+ - lat_i-) in radians with i- = max(i - 1, 0), i+ = min(i + 1, n_lat - 1) (one-sided at the end
+ *              rows; either latitude order), pole_row[i] != 0 where |lat_i| >= 90 - 1e-9, there with coslat[i] = 0 exactly;
+ *              and inv_2dlam = 1 / (2 dlambda).  On a row that is no pole row, the longitude wrapping:
+ *                zeta  = ((v[i,j+1] - v[i,j-1]) inv_2dlam - (u[i+,j] coslat[i+] - u[i-,j] coslat[i-]) inv_dphi[i]) inv_rcos[i]
+ *                delta = ((u[i,j+1] - u[i,j-1]) inv_2dlam + (v[i+,j] coslat[i+] - v[i-,j] coslat[i-]) inv_dphi[i]) inv_rcos[i]
+ *              On a pole row every j gets the mean over j of the adjacent row's double results, summed in ascending j and
+ *              divided by n_lon: a pole is one point.  affine is ignored for these ops (and for SUM, NORM, COPY).
+ * Caps: 64 terms in a list, 1024 in a plan (the table is staged in LDS); with a pole row, n_lon <= 8191.
+ * GC_ERR_INVALID_ARGUMENT beyond those of gc_ens_derive_set: scale or loc NULL or not finite; n_terms < 0; a term table
+ * pointer NULL with n_terms > 0, term_start NULL with a SUM / NORM channel; a term channel outside [0, c_src) (term_b: -1
+ * allowed); a coefficient that is not finite; a term_start row that is not 0 <= s0 < s1 <= s2 <= n_terms, with s2 > s1 for
+ * NORM and s2 == s1 for SUM; with a VORTICITY / DIVERGENCE channel: a row table NULL, n_lon < 3, n_lat < 2, a coslat or
+ * inv_dphi that is not finite, inv_dphi or inv_2dlam zero, inv_rcos not finite on a row that is no pole row, a pole row
+ * that is no end row, has coslat != 0, or lies next to another pole row.  GC_ERR_UNSUPPORTED: an op outside 0 .. 5, a list or
+ * a plan beyond the caps, n_lon beyond the cap of the pole pass.  The row tables may be NULL without such a channel.
+ * Launches: one derive pass, and with a pole row and a VORTICITY / DIVERGENCE channel a pole pass of a workgroup per
+ * (derived column, end row, field).  The tables live in the plan's one buffer and are released with it.
+ */
+int gc_ens_derive_set_expr(gc_handle* dst, int32_t c_src, const int32_t* op, const int32_t* src_a, const int32_t* src_b,
+                           const double* affine /* [c_out][4] */, int32_t pool, int32_t n_lat, int32_t n_lon, int32_t r_lat,
+                           const int32_t* r_lon /* [n_lat] */, const double* row_weight /* [n_lat] */,
+                           const double* scale /* [c_src] */, const double* loc /* [c_src] */,
+                           const int32_t* term_start /* [c_out][3] */, int32_t n_terms, const double* term_coef,
+                           const int32_t* term_a, const int32_t* term_b /* [n_terms] */, const double* coslat,
+                           const double* inv_rcos, const double* inv_dphi /* [n_lat] */, double inv_2dlam,
+                           const int32_t* pole_row /* [n_lat] */);
+
+/*
  * Ensemble order statistics on the device: the M members of every point of the gc_ens_* store in
  * ascending order, and what follows from that order -- quantile fields (the median, a p10 / p90 band) and the bin sums of
  * Hersbach's (2000) decomposition of the ensemble CRPS into a reliability and a potential part (gencast-flax-nnx_amd/
