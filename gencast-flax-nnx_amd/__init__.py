@@ -36,6 +36,9 @@ Public surface (mirrors the reference's call contracts):
                       FeatureSpec / FeatureScores / link_tracks: cyclone centres per member found on the GPU (a local
                       extremum with a depth test), their strike-probability map scored like any field, tracks linked on
                       the host (GenCast.ensemble_features, EnsembleRollout.run(features=...))
+                      BandSpec: the members and the truth low-, band- or high-pass filtered per total wavenumber on
+                      the GPU (analysis, a response per wavenumber, synthesis) in front of every scorer: scores scale by
+                      scale (GenCast.ensemble_derived, EnsembleRollout.run(derived=...))
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
@@ -53,7 +56,7 @@ from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, Ense
                       InputsAndResiduals, WindowRolloutResult, autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
-from .verification import (ClimatologyScores, DerivedSpec, EnergyScores, EnergySpec, EnsembleScores, EventScores,  # noqa: F401
+from .verification import (BandSpec, ClimatologyScores, DerivedSpec, EnergyScores, EnergySpec, EnsembleScores, EventScores,  # noqa: F401
                            EventSpec, FeatureScores, FeatureSpec, FractionsScores, OrderScores, RegionScores, RegionSpec,
                            TailScores, VariogramScores, VariogramSpec, WindowSpec, link_tracks)
 
@@ -65,4 +68,4 @@ __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_
            "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores",
            "WindowSpec", "WindowRolloutResult", "EnergySpec", "EnergyScores", "VariogramSpec", "VariogramScores", "TailScores",
            "RegionSpec", "RegionScores", "FeatureSpec", "FeatureScores", "FeatureRolloutResult", "link_tracks",
-           "FractionsScores"]
+           "FractionsScores", "BandSpec"]

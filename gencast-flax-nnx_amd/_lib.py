@@ -132,6 +132,9 @@ SIGNATURES = {
                                               ctypes.POINTER(ctypes.c_double), _i32p, _i32p, ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_double, _i32p]),
     "gc_ens_derive": (ctypes.c_int, [_hp, _hp, _f32p]),
+    "gc_ens_band_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), _i32p, _i32p, _i32p,
+                                       _f32p, _f32p, _f32p]),
+    "gc_ens_band": (ctypes.c_int, [_hp, _hp, _f32p]),
     "gc_ens_order_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
     "gc_ens_order_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
@@ -253,6 +256,7 @@ class NativeDenoiser:
     self._event_thresholds = 0                 # threshold fields this object handed to the handle
     self._fss_scales = 0                       # scales of the fractions plan this object handed to the handle
     self._derive_c_src = 0                     # source channels of the derive plan this object handed to the handle
+    self._band_c_src = 0                       # source channels of the band plan this object handed to the handle
     self._feature_c_src = 0                    # source channels of the feature plan, and the size of its lists
     self._feature_max = 0
     self._feature_members = -1                 # M of the last ens_feature (-1: none since the plan was set)
@@ -851,6 +855,62 @@ class NativeDenoiser:
         raise ValueError(f"truth must be {want}, got {t.shape}")
     self._check(self._lib.gc_ens_derive(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
 
+  # -- spectral band views (band-limited members and truth, into this handle's member store) -----------------
+  def ens_band_set(self, c_src: int, response, complement, src_channel, band, legendre_synthesis, cos_s, sin_s) -> None:
+    """The plan of `ens_band` for this handle's c_out = c_d derived channels (gc_ens_band_set; needs `set_graph` and
+    `spec_set_tables`, survives `ens_reserve`, dropped by the next `spec_set_tables`).  `response` [K, lmax] float64 (K in
+    1..8): the weight of every total wavenumber in band k; `complement` [K]: the band's field is f - synth(w a) instead of
+    synth(w a); derived channel j is band `band[j]` of source channel `src_channel[j]`.  `legendre_synthesis` [lmax, n_lat,
+    lmax], `cos_s`, `sin_s` [lmax, n_lon]: `spectra.SphericalAnalysis.synthesis_tables()`.  `verification.BandSpec` builds
+    these arrays from variable names."""
+    if not self._spec_lmax:
+      raise GencastHipError("libgencast_hip error 4: no analysis tables (spec_set_tables has not been called on this object)")
+    c_d, L = self.cfg.c_out, self._spec_lmax
+    if int(c_src) < 1:
+      raise ValueError("c_src must be positive")
+    w = np.ascontiguousarray(response, dtype=np.float64)
+    if w.ndim != 2 or not 1 <= w.shape[0] <= 8 or w.shape[1] != L:
+      raise ValueError(f"response must be [K, {L}] with K in 1..8, got {w.shape}")
+    if not np.isfinite(w).all():
+      raise ValueError("a response value is not finite")
+    comp = _i32(np.asarray(complement).astype(np.int32))
+    if comp.shape != (w.shape[0],):
+      raise ValueError(f"complement must have shape ({w.shape[0]},)")
+    ch, bd = _i32(src_channel), _i32(band)
+    if ch.shape != (c_d,) or bd.shape != (c_d,):
+      raise ValueError(f"src_channel and band must have shape ({c_d},)")
+    if np.any((ch < 0) | (ch >= int(c_src))):
+      raise ValueError(f"a source channel lies outside [0, {int(c_src)})")
+    if np.any((bd < 0) | (bd >= w.shape[0])):
+      raise ValueError(f"a band index lies outside [0, {w.shape[0]})")
+    leg, cs, sn = _f32(legendre_synthesis), _f32(cos_s), _f32(sin_s)
+    if leg.ndim != 3 or leg.shape[0] != L or leg.shape[2] != L or leg.shape[1] * cs.shape[-1] != self.num_grid_nodes:
+      raise ValueError(f"legendre_synthesis must be [{L}, n_lat, {L}] with n_lat * n_lon = {self.num_grid_nodes}, got {leg.shape}")
+    if cs.shape != (L, cs.shape[-1]) or sn.shape != cs.shape:
+      raise ValueError(f"cos_s and sin_s must be [{L}, n_lon], got {cs.shape} and {sn.shape}")
+    self._check(self._lib.gc_ens_band_set(self._h, int(c_src), int(w.shape[0]), _ptr(w, ctypes.POINTER(ctypes.c_double)),
+                                          _ptr(comp, _i32p), _ptr(ch, _i32p), _ptr(bd, _i32p), _ptr(leg, _f32p), _ptr(cs, _f32p),
+                                          _ptr(sn, _f32p)))
+    self._band_c_src = int(c_src)
+
+  def ens_band(self, src: "NativeDenoiser", truth=None) -> None:
+    """Every slot of this handle's member store <- the band fields of the member of `src`'s store, this handle's truth <- the
+    band fields of the truth of `src` (gc_ens_band): afterwards every scorer of THIS handle sees the band-limited fields.
+    `truth` [G, B, c_src] is uploaded into `src`, or None = the truth `src` holds.  A band is linear: a view of `x s + l` is
+    `s view(x) + l w[0]` (`l (1 - w[0])` with complement); with float32 tables a constant comes back within a few 1e-7
+    relative."""
+    if not self._band_c_src:
+      raise GencastHipError("libgencast_hip error 4: no plan (ens_band_set has not been called on this object)")
+    if not isinstance(src, NativeDenoiser) or src is self:
+      raise ValueError("src must be another NativeDenoiser")
+    t = None
+    if truth is not None:
+      t = _f32(truth)
+      want = (self.num_grid_nodes, self.cfg.batch, self._band_c_src)
+      if t.shape != want:
+        raise ValueError(f"truth must be {want}, got {t.shape}")
+    self._check(self._lib.gc_ens_band(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
+
   # -- ensemble feature detection (centres and strike fields, into this handle's member store) -------------
   def ens_feature_set(self, c_src: int, channel, direction, use_threshold, threshold, n_lat: int, n_lon: int, r_lat, r_lon,
                       ring_lat, ring_lon, depth, strike_lat, strike_lon, max_centres: int = 64) -> None:
@@ -1245,6 +1305,7 @@ class NativeDenoiser:
     self._check(self._lib.gc_spec_set_tables(self._h, q.shape[2], c.shape[1], q.shape[0], _ptr(q, _f32p), _ptr(c, _f32p),
                                              _ptr(s, _f32p)))
     self._spec_lmax = int(q.shape[0])
+    self._band_c_src = 0                       # (a band plan goes with the tables it was made for)
 
   def _spec_need_tables(self):
     if not self._spec_lmax:

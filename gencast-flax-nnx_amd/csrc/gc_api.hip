@@ -888,6 +888,9 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "ens_event_invalid_points") *value = h->evt_invalid_points;
   else if (n == "ens_derive_calls") *value = h->drv_calls;
   else if (n == "ens_derive_device_us") *value = h->drv_device_us;
+  else if (n == "ens_band_calls") *value = h->band_calls;
+  else if (n == "ens_band_device_us") *value = h->band_device_us;
+  else if (n == "ens_band_invalid_columns") *value = h->band_invalid_columns;
   else if (n == "ens_order_calls") *value = h->ord_calls;
   else if (n == "ens_order_device_us") *value = h->ord_device_us;
   else if (n == "ens_order_invalid_points") *value = h->ord_invalid_points;

@@ -5,7 +5,7 @@
 //   gc_sampler.hip   the sampler and the loss around it
 //   gc_api.hip       the C ABI, but for the entries of the four units below
 //   gc_ensemble.hip  gc_ens_* (the member store and its scores) and gc_ctx_*
-//   gc_spectrum.hip  gc_spec_* and gc_ens_spectrum
+//   gc_spectrum.hip  gc_spec_*, gc_ens_spectrum and gc_ens_band_*
 //   gc_events.hip    gc_ens_event_*
 //   gc_derive.hip    gc_ens_derive_*
 //   gc_order.hip     gc_ens_order_*
@@ -341,6 +341,24 @@ struct gc_handle {
   unsigned* d_sp_flags = nullptr;                // [B c_out]: a value of the column was not finite
   gci::Bracket spec_time{events};                // of the last spectrum call
   int64_t spec_calls = 0, spec_device_us = 0, spec_invalid_columns = 0;
+
+  // spectral band views (gc_ens_band_*, gc_spectrum.hip): the plan, and the scratch of the one field in flight
+  gci::BufferGroup band_allocs{groups};           // the plan's tables, one buffer: freed and replaced by gc_ens_band_set, dropped by gc_spec_set_tables
+  gci::BufferGroup band_work_allocs{groups};      // the scratch and the flags: made again by the call that finds their size changed
+  bool band_set = false;                         // a plan has been set
+  int band_c_src = 0, band_K = 0, band_nu = 0;   // source channels, bands, DISTINCT source channels the plan reads
+  double* d_band_resp = nullptr;                 // [K][L] responses
+  float *d_band_leg = nullptr, *d_band_tab = nullptr;   // [L m][n_lat][L l] Legendre synthesis; [n_lon][L m][2] (cos_s, sin_s)
+  int *d_band_comp = nullptr, *d_band_chan = nullptr, *d_band_of = nullptr;   // [K] complement; [c_out] source channel, band
+  int *d_band_ucol = nullptr, *d_band_ulist = nullptr;   // [c_out] place of the source channel in the list; [nu] the list, ascending
+  float* d_band_gather = nullptr;                // [G][B nu]: the source columns of the field in flight, side by side
+  double *d_band_F = nullptr, *d_band_coef = nullptr;    // [2][L][n_lat][B nu], [2][L m][L l][B nu]: its analysis
+  double* d_band_G = nullptr;                    // [2][L m][n_lat][B c_out]: the Legendre synthesis of every derived column
+  unsigned* d_band_flags = nullptr;              // [M + 1][B nu]: a value of the column of that field was not finite
+  size_t band_work_key[2] = {0, 0};              // (B nu, M + 1) the scratch and the flags are sized for
+  gci::Bracket band_time{events};                // of the last call
+  gci::Event ev_band_src{events};                // stream order behind the source handle
+  int64_t band_calls = 0, band_device_us = 0, band_invalid_columns = 0;
 
   // ensemble event verification (gc_ens_event_*, gc_events.hip): threshold fields and the tables scored from the member store
   gci::BufferGroup evt_allocs{groups};            // sized by T: thresholds, codes, weights; kept across gc_ens_reserve

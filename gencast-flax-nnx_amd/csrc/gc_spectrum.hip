@@ -161,6 +161,109 @@ __global__ __launch_bounds__(256) void gc_spec_ens_kernel(const double* __restri
   for (int k = 0; k < 6; ++k) sums[(size_t)k * plane + o] = p[k];
 }
 
+// ---- spectral band views (gc_ens_band_*) ---------------------------------------------------------------
+// One field (a member or the truth) at a time: the distinct source columns the plan reads are gathered side by side (the
+// same bits), analysed by the two kernels above, and every derived column (b, j) is synthesised back from the coefficients
+// of its source column weighted with the response of its band:
+//   Legendre synthesis  G[part][m][lat][col] = sum_{l >= m} S[m][lat][l] (w_k[l] a[part][m][l][u(col)])        l ascending
+//   Fourier synthesis   g[lat][j][col] = sum_m (cos_s[m][j] G[0][m][lat][col] + sin_s[m][j] G[1][m][lat][col])  m ascending
+//   epilogue            d = (float) g, or (float) ((double) f - g) with the band's complement flag; NaN for a flagged column
+// The layout is the one of the analysis: lane = column, a wave keeps 16 output rows (latitudes, then longitudes) in
+// registers, the table values of a row are wave-uniform and consecutive in the summed index.  The response is per lane (the
+// lanes of a wave own different bands): K L doubles that stay in the vector cache.
+
+// gathered [G][Nu] <- the source columns (b, ulist[u]) of a field [G][B c_src]; one thread per element
+__global__ __launch_bounds__(256) void gc_band_gather_kernel(const float* __restrict__ field, size_t G, int B, int c_src, int nu,
+                                                              const int* __restrict__ ulist, float* __restrict__ out) {
+  const int Nu = B * nu;
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= G * (size_t)Nu) return;
+  const size_t node = e / Nu;
+  const int col = (int)(e - node * Nu), b = col / nu, u = col - b * nu;
+  reinterpret_cast<unsigned*>(out)[e] = reinterpret_cast<const unsigned*>(field)[node * ((size_t)B * c_src) + (size_t)b * c_src + ulist[u]];
+}
+
+// Legendre synthesis.  grid = (L, 2 ceil(n_lat / 64), ceil(Nd / 64)): blockIdx.x = m, blockIdx.y = part + 2 (block of 64
+// latitudes); lane = derived column.  The loader forms b = w a, rounded, before it enters the fused multiply-adds.
+__global__ __launch_bounds__(256) void gc_band_legendre_kernel(const float* __restrict__ S,        // [L m][n_lat][L l]
+                                                                const double* __restrict__ coef,    // [2][L m][L l][Nu]
+                                                                const double* __restrict__ resp,    // [K][L]
+                                                                const int* __restrict__ band_of, const int* __restrict__ ucol,
+                                                                int L, int n_lat, int B, int c_d, int nu,
+                                                                double* __restrict__ Gs) {           // [2][L m][n_lat][Nd]
+  const int m = blockIdx.x, part = blockIdx.y & 1;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int Nd = B * c_d, Nu = B * nu;
+  const int col = blockIdx.z * 64 + lane;
+  const int lat0 = (blockIdx.y >> 1) * kSpecBlockRows + wave * kSpecRows;
+  if (lat0 >= n_lat) return;
+  const float* srow[kSpecRows];
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k) srow[k] = S + ((size_t)m * n_lat + min(lat0 + k, n_lat - 1)) * L;
+  double acc[kSpecRows];
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k) acc[k] = 0.0;
+  const int cc = min(col, Nd - 1), b = cc / c_d, j = cc - b * c_d;
+  const double* const w = resp + (size_t)band_of[j] * L;
+  const double* const a = coef + ((size_t)part * L + m) * L * Nu + (size_t)b * nu + ucol[j];
+  for (int l = m; l < L; ++l) {
+    const double x = w[l] * a[(size_t)l * Nu];
+#pragma unroll
+    for (int k = 0; k < kSpecRows; ++k) acc[k] = fma((double)srow[k][l], x, acc[k]);
+  }
+  if (col >= Nd) return;
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k)
+    if (lat0 + k < n_lat) Gs[(((size_t)part * L + m) * n_lat + lat0 + k) * Nd + col] = acc[k];
+}
+
+// Fourier synthesis and epilogue.  grid = (n_lat, ceil(n_lon / 64), ceil(Nd / 64)); lane = derived column, a wave keeps 16
+// longitudes.  tab [n_lon][L][2]: (cos_s, sin_s) of a longitude, consecutive in m.  The result goes straight to channel j of
+// the destination field; src is the field the complement subtracts from.
+__global__ __launch_bounds__(256) void gc_band_fourier_kernel(const float* __restrict__ tab, const double* __restrict__ Gs,
+                                                               const float* __restrict__ src,       // [G][B c_src]
+                                                               const unsigned* __restrict__ flags,  // [Nu] of this field
+                                                               const int* __restrict__ comp, const int* __restrict__ band_of,
+                                                               const int* __restrict__ chan, const int* __restrict__ ucol,
+                                                               int L, int n_lat, int n_lon, int B, int c_src, int c_d, int nu,
+                                                               float* __restrict__ dst) {            // [G][Nd]
+  const int lat = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int Nd = B * c_d;
+  const int col = blockIdx.z * 64 + lane;
+  const int j0 = blockIdx.y * kSpecBlockRows + wave * kSpecRows;
+  if (j0 >= n_lon) return;
+  const float* trow[kSpecRows];
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k) trow[k] = tab + (size_t)min(j0 + k, n_lon - 1) * 2 * L;
+  double acc[kSpecRows];
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k) acc[k] = 0.0;
+  const int cc = min(col, Nd - 1);
+  const size_t plane = (size_t)L * n_lat * Nd;
+  const double* const g0 = Gs + (size_t)lat * Nd + cc;
+  for (int m = 0; m < L; ++m) {
+    const double xc = g0[(size_t)m * n_lat * Nd], xs = g0[plane + (size_t)m * n_lat * Nd];
+#pragma unroll
+    for (int k = 0; k < kSpecRows; ++k) {
+      acc[k] = fma((double)trow[k][2 * m], xc, acc[k]);
+      acc[k] = fma((double)trow[k][2 * m + 1], xs, acc[k]);
+    }
+  }
+  if (col >= Nd) return;
+  const int b = col / c_d, j = col - b * c_d;
+  const bool bad = flags[b * nu + ucol[j]] != 0u, complement = comp[band_of[j]] != 0;
+  const float* const f = src + (size_t)b * c_src + chan[j];
+#pragma unroll
+  for (int k = 0; k < kSpecRows; ++k) {
+    if (j0 + k >= n_lon) continue;
+    const size_t node = (size_t)lat * n_lon + j0 + k;
+    float d = complement ? (float)((double)f[node * ((size_t)B * c_src)] - acc[k]) : (float)acc[k];
+    if (bad) d = __builtin_nanf("");
+    dst[node * Nd + col] = d;
+  }
+}
+
 static bool spec_grid_ok(int L, int n_lat, int N) {
   return L >= 1 && n_lat >= 1 && N >= 1 && n_lat <= 65535 && (N + 63) / 64 <= 65535 &&
          2 * ((L + kSpecBlockRows - 1) / kSpecBlockRows) <= 65535 && (long long)L * N < (1ll << 31) - 256;
@@ -192,6 +295,36 @@ static hipError_t launch_spec_ens(hipStream_t s, double* sets, size_t set, int M
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(gc_spec_ens_kernel, dim3((L * N + 255) / 256), dim3(256), 0, s, sets, set, M, flags, L, N, sums, member_power);
+  return hipGetLastError();
+}
+
+// the device side of a band plan (gc_ens_band_set) and the scratch of the field in flight
+struct BandPlan {
+  const double* resp;
+  const float *leg, *tab;
+  const int *comp, *chan, *band_of, *ucol, *ulist;
+  int L, n_lat, n_lon, B, c_src, c_d, nu;
+  float* gather;
+  double *F, *coef, *Gs;
+};
+
+// one field [G][B c_src] -> the band field [G][B c_d]; flags: the [B nu] of this field, zeroed by the caller
+static hipError_t launch_band_field(hipStream_t s, const BandPlan& p, const float* atab, const float* Q, const float* src, float* dst,
+                                    unsigned* flags) {
+  const int Nu = p.B * p.nu, Nd = p.B * p.c_d;
+  const size_t G = (size_t)p.n_lat * p.n_lon;
+  hipLaunchKernelGGL(gc_band_gather_kernel, dim3((unsigned)((G * Nu + 255) / 256)), dim3(256), 0, s, src, G, p.B, p.c_src, p.nu,
+                     p.ulist, p.gather);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if ((e = launch_spec_analysis(s, p.gather, atab, Q, p.L, p.n_lat, p.n_lon, Nu, p.F, p.coef, flags)) != hipSuccess) return e;
+  const unsigned cols = (unsigned)((Nd + 63) / 64);
+  hipLaunchKernelGGL(gc_band_legendre_kernel, dim3(p.L, 2 * ((p.n_lat + kSpecBlockRows - 1) / kSpecBlockRows), cols), dim3(256), 0, s,
+                     p.leg, p.coef, p.resp, p.band_of, p.ucol, p.L, p.n_lat, p.B, p.c_d, p.nu, p.Gs);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(gc_band_fourier_kernel, dim3(p.n_lat, (p.n_lon + kSpecBlockRows - 1) / kSpecBlockRows, cols), dim3(256), 0, s,
+                     p.tab, p.Gs, src, flags, p.comp, p.band_of, p.chan, p.ucol, p.L, p.n_lat, p.n_lon, p.B, p.c_src, p.c_d, p.nu,
+                     dst);
   return hipGetLastError();
 }
 
@@ -252,6 +385,10 @@ int gc_spec_set_tables(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t lmax,
   GC_HIP(h, hipSetDevice(h->device));
   GC_HIP(h, h->spec_allocs.drop(h->stream));       // nothing reads the old tables any more
   h->spec_work_allocs.free();
+  h->band_allocs.free();                           // a band plan is made for the grid and the band limit of the tables: it goes with them
+  h->band_work_allocs.free();
+  h->band_set = false;
+  h->band_work_key[0] = h->band_work_key[1] = 0;
   h->sp_L = h->sp_sets = 0;
   const size_t L = (size_t)lmax;
   std::vector<float> tab(2 * L * n_lon);
@@ -344,6 +481,142 @@ int gc_ens_spectrum(gc_handle* h, const float* truth, double* sums, double* memb
   GC_HIP(h, hipMemcpyAsync(flags.data(), h->d_sp_flags, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
   GC_HIP(h, hipStreamSynchronize(s));
   return spec_finish(h, flags);
+  });
+}
+
+int gc_ens_band_set(gc_handle* h, int32_t c_src, int32_t n_bands, const double* response, const int32_t* complement,
+                    const int32_t* src_channel, const int32_t* band, const float* legendre_synthesis, const float* cos_s,
+                    const float* sin_s) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  int rc = spec_ready(h);
+  if (rc) return rc;
+  if (n_bands < 1 || n_bands > 8) return fail(h, GC_ERR_UNSUPPORTED, "the number of bands must be in 1 .. 8");
+  if (!response || !complement || !src_channel || !band || !legendre_synthesis || !cos_s || !sin_s)
+    return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  if (c_src < 1) return fail(h, GC_ERR_INVALID_ARGUMENT, "c_src must be positive");
+  const int c_d = h->cfg.c_out, B = h->cfg.batch, K = n_bands;
+  const size_t L = (size_t)h->sp_L, n_lat = (size_t)h->sp_lat, n_lon = (size_t)h->sp_lon;
+  for (size_t i = 0; i < (size_t)K * L; ++i)
+    if (!std::isfinite(response[i])) return fail(h, GC_ERR_INVALID_ARGUMENT, "the response of band " + std::to_string(i / L) + " is not finite at l = " + std::to_string(i % L));
+  std::vector<int> ulist;                            // the distinct source channels, ascending
+  for (int j = 0; j < c_d; ++j) {
+    if (src_channel[j] < 0 || src_channel[j] >= c_src) return fail(h, GC_ERR_INVALID_ARGUMENT, "derived channel " + std::to_string(j) + ": source channel outside [0, c_src)");
+    if (band[j] < 0 || band[j] >= K) return fail(h, GC_ERR_INVALID_ARGUMENT, "derived channel " + std::to_string(j) + ": band outside [0, n_bands)");
+    ulist.push_back(src_channel[j]);
+  }
+  std::sort(ulist.begin(), ulist.end());
+  ulist.erase(std::unique(ulist.begin(), ulist.end()), ulist.end());
+  const int nu = (int)ulist.size();
+  if (!gc::spec_grid_ok(h->sp_L, h->sp_lat, B * nu) || !gc::spec_grid_ok(h->sp_L, h->sp_lat, B * c_d))
+    return fail(h, GC_ERR_UNSUPPORTED, "grid too large for the spectrum kernels");
+  GC_HIP(h, hipSetDevice(h->device));
+  // one blob.  doubles: response [K][L]; floats: the Legendre synthesis [L][n_lat][L], then (cos_s, sin_s) [n_lon][L][2];
+  // int32: complement [K], src_channel, band, place in the list [c_d], the list [nu]
+  const size_t n_d = (size_t)K * L, n_leg = L * n_lat * L, n_f = n_leg + 2 * n_lon * L, n_i = (size_t)K + 3 * (size_t)c_d + nu;
+  std::vector<double> blob(n_d + (n_f + 1) / 2 + (n_i + 1) / 2);
+  std::copy(response, response + n_d, blob.begin());
+  float* const fb = reinterpret_cast<float*>(blob.data() + n_d);
+  std::copy(legendre_synthesis, legendre_synthesis + n_leg, fb);
+  for (size_t m = 0; m < L; ++m)
+    for (size_t j = 0; j < n_lon; ++j) {
+      fb[n_leg + (j * L + m) * 2] = cos_s[m * n_lon + j];
+      fb[n_leg + (j * L + m) * 2 + 1] = sin_s[m * n_lon + j];
+    }
+  int32_t* const ib = reinterpret_cast<int32_t*>(blob.data() + n_d + (n_f + 1) / 2);
+  for (int k = 0; k < K; ++k) ib[k] = complement[k] ? 1 : 0;
+  for (int j = 0; j < c_d; ++j) {
+    ib[K + j] = src_channel[j];
+    ib[K + c_d + j] = band[j];
+    ib[K + 2 * c_d + j] = (int)(std::lower_bound(ulist.begin(), ulist.end(), src_channel[j]) - ulist.begin());
+  }
+  std::copy(ulist.begin(), ulist.end(), ib + K + 3 * (size_t)c_d);
+  GC_HIP(h, h->band_allocs.drop(h->stream));         // nothing reads the old plan any more
+  h->band_set = false;
+  double* d_blob = nullptr;
+  if ((rc = dev_alloc(h, &d_blob, blob.size(), &h->band_allocs))) return rc;
+  GC_HIP(h, h->band_time.ensure());
+  GC_HIP(h, h->ev_band_src.ensure());
+  if ((rc = store_upload(h, d_blob, blob.data(), blob.size() * sizeof(double)))) return rc;
+  h->d_band_resp = d_blob;
+  h->d_band_leg = reinterpret_cast<float*>(d_blob + n_d);
+  h->d_band_tab = h->d_band_leg + n_leg;
+  h->d_band_comp = reinterpret_cast<int*>(d_blob + n_d + (n_f + 1) / 2);
+  h->d_band_chan = h->d_band_comp + K;
+  h->d_band_of = h->d_band_chan + c_d;
+  h->d_band_ucol = h->d_band_of + c_d;
+  h->d_band_ulist = h->d_band_ucol + c_d;
+  h->band_c_src = c_src;
+  h->band_K = K;
+  h->band_nu = nu;
+  h->band_set = true;
+  return GC_OK;
+  });
+}
+
+int gc_ens_band(gc_handle* h, gc_handle* src, const float* truth) {
+  return guarded(h, [&]() -> int {
+  if (!h) return GC_ERR_INVALID_ARGUMENT;
+  if (!src || src == h) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source must be another handle");
+  int rc = spec_ready(h);
+  if (rc) return rc;
+  if (!h->band_set) return fail(h, GC_ERR_STATE, "no plan (gc_ens_band_set)");
+  if ((rc = check_peer(h, src, "source", false, h->band_c_src, "c_out == c_src of the plan"))) return rc;
+  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
+  if (src->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store on the source handle (gc_ens_reserve)");
+  if (src->ens_members != h->ens_members) return fail(h, GC_ERR_STATE, "the two member stores hold different numbers of members");
+  if ((rc = store_complete(h, src, "source "))) return rc;
+  GC_HIP(h, hipSetDevice(h->device));
+  if ((rc = take_truth(h, src, truth, "gc_ens_band"))) return rc;   // into the source's truth buffer, as gc_ens_derive does
+  const int B = h->cfg.batch, c_d = h->cfg.c_out, M = h->ens_members, nu = h->band_nu;
+  const size_t L = (size_t)h->sp_L, n_lat = (size_t)h->sp_lat, Nu = (size_t)B * nu, Nd = (size_t)B * c_d;
+  const size_t field = field_len(h), sfield = field_len(src);
+  if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
+  if (h->band_work_key[0] != Nu || h->band_work_key[1] != (size_t)M + 1) {   // the scratch of ONE field, and the flags of all
+    GC_HIP(h, h->band_work_allocs.drop(h->stream));
+    h->band_work_key[0] = h->band_work_key[1] = 0;
+    if ((rc = dev_alloc(h, &h->d_band_gather, (size_t)h->hg.G * Nu, &h->band_work_allocs)) ||
+        (rc = dev_alloc(h, &h->d_band_F, 2 * L * n_lat * Nu, &h->band_work_allocs)) ||
+        (rc = dev_alloc(h, &h->d_band_coef, 2 * L * L * Nu, &h->band_work_allocs)) ||
+        (rc = dev_alloc(h, &h->d_band_G, 2 * L * n_lat * Nd, &h->band_work_allocs)) ||
+        (rc = dev_alloc(h, &h->d_band_flags, ((size_t)M + 1) * Nu, &h->band_work_allocs))) {
+      h->band_work_allocs.free();
+      return rc;
+    }
+    h->band_work_key[0] = Nu;
+    h->band_work_key[1] = (size_t)M + 1;
+  }
+  hipStream_t s = h->stream;
+  // the source's store and truth are complete on ITS stream: this handle's stream goes on behind them
+  if ((rc = order_behind(h, h->ev_band_src, src->stream, s))) return rc;
+  h->evt_scored = false;
+  h->has_ens_fields = false;
+  h->ord_ready = false;
+  const gc::BandPlan p{h->d_band_resp, h->d_band_leg, h->d_band_tab, h->d_band_comp, h->d_band_chan, h->d_band_of, h->d_band_ucol,
+                       h->d_band_ulist, h->sp_L, h->sp_lat, h->sp_lon, B, src->cfg.c_out, c_d, nu, h->d_band_gather, h->d_band_F,
+                       h->d_band_coef, h->d_band_G};
+  GC_HIP(h, h->band_time.begin(s));
+  GC_HIP(h, hipMemsetAsync(h->d_band_flags, 0, ((size_t)M + 1) * Nu * sizeof(unsigned), s));
+  for (int z = 0; z <= M; ++z) {                     // the M members, then the truth: one field at a time through the scratch
+    const float* from = z < M ? src->d_ens + (size_t)z * sfield : src->d_ens_truth;
+    float* to = z < M ? h->d_ens + (size_t)z * field : h->d_ens_truth;
+    if ((rc = launch(h, gc::KC_PACK, [&] {
+           return gc::launch_band_field(s, p, h->d_sp_tab, h->d_sp_q, from, to, h->d_band_flags + (size_t)z * Nu);
+         })))
+      return rc;
+  }
+  GC_HIP(h, h->band_time.end(s));
+  std::vector<unsigned> flags(((size_t)M + 1) * Nu);
+  GC_HIP(h, hipMemcpyAsync(flags.data(), h->d_band_flags, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  GC_HIP(h, hipStreamSynchronize(s));
+  GC_HIP(h, h->band_time.microseconds(&h->band_device_us));
+  int64_t bad = 0;
+  for (unsigned f : flags) bad += f ? 1 : 0;
+  h->band_invalid_columns = bad;
+  std::fill(h->ens_filled.begin(), h->ens_filled.end(), 1);
+  h->has_ens_truth = true;
+  ++h->band_calls;
+  return GC_OK;
   });
 }
 

@@ -180,12 +180,14 @@ class Denoiser:
       views[c_d] = nd
     return nd
 
-  def climatology_handle(self, c_d: int, *, view: bool = False) -> _lib.NativeDenoiser:
+  def climatology_handle(self, c_d: int, *, view: bool = False, key: Optional[str] = None) -> _lib.NativeDenoiser:
     """A graph-only handle like `view_handle`'s, kept apart from those (a view of `c_d` channels and the climatology it is
     scored against are two stores): its member store takes the K climatological samples of `c_d` channels that
     `NativeDenoiser.ens_clim_score` reads next to the members -- pushed with `ens_push_host`, or derived from another
     climatology handle with `ens_derive` (`view=True`: the handle of such derived samples, apart from the plain one of the
-    same width).  One per (`c_d`, `view`), created once and kept; `close` releases them."""
+    same width; `key`: a handle of its own under that name -- the climatology of a band view holds analysis tables and a
+    band plan, which two entries must not share).  One per (`c_d`, `view`[, `key`]), created once and kept; `close`
+    releases them."""
     if not self._initialized:
       raise RuntimeError("climatology_handle: the denoiser has not been initialised by a first call / init_for")
     c_d = int(c_d)
@@ -194,7 +196,8 @@ class Denoiser:
     clims = getattr(self, "_climatologies", None)
     if clims is None:
       clims = self._climatologies = {}
-    nd = clims.get((c_d, bool(view)))
+    slot = (c_d, bool(view)) if key is None else (c_d, bool(view), str(key))
+    nd = clims.get(slot)
     if nd is None or nd.closed:
       nd = _lib.NativeDenoiser(latent_size=128, d_model=128, num_heads=2, ffw_hidden=256, num_layers=1, c_in=c_d, c_out=c_d,
                                batch=self._batch, device_id=self._device_id)
@@ -203,7 +206,7 @@ class Denoiser:
       except Exception:
         nd.close()
         raise
-      clims[(c_d, bool(view))] = nd
+      clims[slot] = nd
     return nd
 
   def window_handle(self, c_d: int, key: str) -> _lib.NativeDenoiser:
@@ -237,6 +240,12 @@ class Denoiser:
     strike fields and which keeps the lists of centres of its last call.  Kept with the window handles, one per (`c_d`,
     `key`): two entries never share one."""
     return self.window_handle(c_d, "feature:" + str(key))
+
+  def band_handle(self, c_d: int, key: str) -> _lib.NativeDenoiser:
+    """A graph-only handle like `view_handle`'s with `c_out = c_d`, for ONE `verification.BandSpec` (an entry of
+    `EnsembleRollout.run(derived=...)`): the destination of `NativeDenoiser.ens_band`.  It holds the analysis tables of the
+    entry's band limit and its plan, so two entries never share one.  Kept with the window handles, one per (`c_d`, `key`)."""
+    return self.window_handle(c_d, "band:" + str(key))
 
   def close(self) -> None:
     """Releases every library handle this denoiser made: the view, climatology and window handles, the member lanes and

@@ -110,7 +110,8 @@ class EnsembleSampler:
 
   def derived(self, inputs, targets, forcings, num_members: int, spec, events=None):
     """Runs the members as `scores` does, sends them and `targets` through `spec` (a `verification.DerivedSpec`: wind speed
-    from two components, fields pooled over a neighbourhood) on the device and scores the derived fields there:
+    from two components, fields pooled over a neighbourhood; or a `verification.BandSpec`: the fields low-, band- or high-pass
+    filtered per total wavenumber) on the device and scores the derived fields there:
     `verification.EnsembleScores` over the derived channels (`spec.template(targets)` names them), with `events` (an
     `EventSpec` keyed by the derived names) -> (EnsembleScores, EventScores).  No member is downloaded.  The members are
     taken as they are sampled, scale 1 and location 0: under a normalisation wrapper (`InputsAndResiduals`, `NaNCleaner`
@@ -261,9 +262,14 @@ class EnsembleSampler:
 
     def derived_scores():
       plan = dspec.plan(template)
-      view = verification.ScoredStore(self._denoiser.view_handle(len(plan["op"])), num_members, weights, events=dev,
+      if isinstance(dspec, verification.BandSpec):           # a band view: a handle with the analysis tables of its band limit
+        handle, how = self._denoiser.band_handle(len(plan["band"]), "single"), "band_plan"
+        _spectra.ensure_tables(handle, template, plan["response"].shape[1])
+      else:
+        handle, how = self._denoiser.view_handle(len(plan["op"])), "plan"
+      view = verification.ScoredStore(handle, num_members, weights, events=dev,
                                       thresholds=None if dev is None else dev.packed(dspec.template(template)), weight_q=wq,
-                                      plan=plan, source=native, set_per_score=True)
+                                      source=native, set_per_score=True, **{how: plan})
       view.setup()
       scores, event_scores = view.score(truth)
       return scores if dev is None else (scores, event_scores)

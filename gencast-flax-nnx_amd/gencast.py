@@ -177,7 +177,8 @@ class GenCast:
   def ensemble_derived(self, inputs, targets, forcings=None, *, num_members, spec, events=None, rngs=0, concurrent_members=1):
     """Samples `num_members` (2..64) members as `ensemble_scores` does and scores, on the GPU, what `spec`
     (`verification.DerivedSpec`) makes of them and of `targets`: wind speed from two components, fields max-, min- or
-    mean-pooled over a neighbourhood.  -> `verification.EnsembleScores` over the derived channels, with `events` (an
+    mean-pooled over a neighbourhood; or what a `verification.BandSpec` makes of them: every variable low-, band- or
+    high-pass filtered per total wavenumber.  -> `verification.EnsembleScores` over the derived channels, with `events` (an
     `EventSpec` keyed by the derived names) -> (EnsembleScores, EventScores).  No member leaves the device.  The members
     are taken in the units they are sampled in; the normalisation wrappers have no such method, because under them a
     single-step sample is a normalised residual and the norm of two residuals is no wind speed (`ensemble_rollout(...,

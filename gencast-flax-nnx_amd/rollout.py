@@ -1029,7 +1029,11 @@ class EnsembleRollout:
     in physical units from the normalised components, fields pooled over a neighbourhood -- and are scored there with the
     same node weights: `EnsembleRolloutResult.derived[name]`.  The thresholds of such an EventSpec are keyed by the derived
     names, in physical units, and take the map of `DerivedSpec.channel_stats`.  With `keep_members` the derived members
-    are downloaded too.
+    are downloaded too.  A `verification.BandSpec` goes wherever a DerivedSpec goes: the states and the truth are then
+    analysed, weighted per total wavenumber and synthesised back (`gc_ens_band`) into a handle of the
+    entry's own (`Denoiser.band_handle`) that holds the analysis tables of its band limit -- the scores of the planetary
+    waves, of the synoptic scales, of what is left without them; the members stay in the normalised units of their source
+    channel (`BandSpec.channel_stats`).
     `order`: probabilities (at most 8; an empty sequence: none): per lead time, after the scores, the member states are
     sorted point by point on the device (`gc_ens_order_score`, on the truth already there): `EnsembleRolloutResult.order`
     (`verification.OrderScores`: the reliability / potential split of the ensemble CRPS, pinball loss and coverage of the
@@ -1257,12 +1261,23 @@ class EnsembleRollout:
       dplan = dspec.plan(template0, scale, loc)
       dtemplate = dspec.template(template0)
       dscale, dloc = dspec.channel_stats(template0, scale, loc)
-      store = verification.ScoredStore(den.view_handle(len(dplan["op"])), M, weights, events=dev,
+      if isinstance(dspec, verification.BandSpec):
+        # a band view: a handle of its own (and a climatology view of its own) with the analysis tables of its band limit
+        width, how = len(dplan["band"]), "band_plan"
+        handle = den.band_handle(width, name)
+        clim_view = None if clim_handle is None else den.climatology_handle(width, view=True, key="band:" + name)
+        for h in (handle, clim_view):
+          if h is not None:
+            _spectra.ensure_tables(h, template0, dplan["response"].shape[1])
+      else:
+        width, how = len(dplan["op"]), "plan"
+        handle = den.view_handle(width)
+        clim_view = None if clim_handle is None else den.climatology_handle(width, view=True)
+      store = verification.ScoredStore(handle, M, weights, events=dev,
                                        thresholds=None if dev is None else packed(dev, dtemplate, dscale, dloc), weight_q=wq,
-                                       plan=dplan, source=native, order=order, energy=eplan(dtemplate), variogram=vplan,
-                                       climatology=None if clim_handle is None
-                                       else den.climatology_handle(len(dplan["op"]), view=True),
-                                       climatology_source=clim_handle, **per_store_args(name, dtemplate, dscale, dloc))
+                                       source=native, order=order, energy=eplan(dtemplate), variogram=vplan,
+                                       climatology=clim_view, climatology_source=clim_handle, **{how: dplan},
+                                       **per_store_args(name, dtemplate, dscale, dloc))
       run.views[name] = _StoreSeries(store, dscale, dtemplate, keep_members=keep_members, keep_quantiles=keep_quantiles)
     for store in (v.store for v in run.views.values()):
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time

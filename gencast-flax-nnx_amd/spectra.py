@@ -53,6 +53,7 @@ class SphericalAnalysis:
       raise ValueError(f"lmax must be in 1 .. n_lon / 2 = {self.n_lon // 2}, got {self.lmax}")
     L = self.lmax
     P = _normalized_legendre(np.sin(np.deg2rad(lat)), L)                       # [m, l, lat]
+    self.legendre = P                                                          # [m, l, lat]: N_lm P_l^m(sin lat), zero for l < m
     self.legendre_analysis = np.zeros((L, L, self.n_lat), np.float64)
     self.condition_numbers = np.zeros(L, np.float64)
     for m in range(L):
@@ -68,6 +69,9 @@ class SphericalAnalysis:
     amp = np.where(m == 0, 1.0, np.sqrt(2.0)) / self.n_lon
     self.cos_a = np.cos(m[:, None] * phi[None, :]) * amp[:, None]              # [m, lon]
     self.sin_a = np.sin(m[:, None] * phi[None, :]) * amp[:, None]              # [m, lon] (m = 0: zeros)
+    amp_s = np.where(m == 0, 1.0, np.sqrt(2.0))
+    self.cos_s = np.cos(m[:, None] * phi[None, :]) * amp_s[:, None]            # [m, lon]: amp_m cos(m phi_j), the synthesis rows
+    self.sin_s = np.sin(m[:, None] * phi[None, :]) * amp_s[:, None]
 
   @property
   def worst_condition(self) -> float:
@@ -78,6 +82,14 @@ class SphericalAnalysis:
     `gc_spec_set_tables` / `NativeDenoiser.spec_set_tables`."""
     return (np.ascontiguousarray(self.legendre_analysis, np.float32), np.ascontiguousarray(self.cos_a, np.float32),
             np.ascontiguousarray(self.sin_a, np.float32))
+
+  def synthesis_tables(self):
+    """(legendre_synthesis [lmax m, n_lat, lmax l] (the plain A_m, zero for l < m), cos_s [lmax, n_lon], sin_s [lmax, n_lon])
+    float32, for `gc_ens_band_set` / `NativeDenoiser.ens_band_set`: the way back from the coefficients of `device_tables`
+    onto the grid, cos_s[m, j] = amp_m cos(m phi_j)."""
+    leg = np.where((np.arange(self.lmax)[:, None] <= np.arange(self.lmax)[None, :])[:, :, None], self.legendre[:self.lmax, :self.lmax], 0.0)
+    return (np.ascontiguousarray(np.transpose(leg, (0, 2, 1)), np.float32), np.ascontiguousarray(self.cos_s, np.float32),
+            np.ascontiguousarray(self.sin_s, np.float32))
 
   @staticmethod
   def for_template(template, lmax: Optional[int] = None) -> "SphericalAnalysis":

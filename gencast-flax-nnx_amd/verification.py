@@ -28,6 +28,10 @@ scorer above works unchanged.  The same spec forms combinations across pressure 
 thickness, shear, column integrals, integrated vapour transport, one level of a variable) and horizontal derivatives on the
 sphere (relative vorticity, divergence), through `gc_ens_derive_set_expr`.
 
+Band views (`gc_ens_band`): `BandSpec` names bands of total wavenumbers; the device analyses the members
+and the truth of a store into spherical harmonics, weights the coefficients with the band's response and synthesises them back
+into the store of a second handle -- low-, band- and true high-pass fields, on which every scorer works unchanged.
+
 Order statistics (`gc_ens_order_score`): the device sorts the M members of every point and hands back,
 per (batch, channel), the bin sums `bins[k] = (sum w alpha_k, sum w beta_k)` of Hersbach's (2000) decomposition of the
 ensemble CRPS, the outlier weights, and for Q probabilities the pinball-loss sums and below-quantile counts of the quantile
@@ -1404,6 +1408,206 @@ class DerivedSpec:
 
 
 # ---------------------------------------------------------------------------------------------
+# spectral band views: the members and the truth, scale by scale (gc_ens_band_*)
+# ---------------------------------------------------------------------------------------------
+class BandSpec:
+  """What `gc_ens_band` makes of a member store: every chosen target variable low-, band- or
+  high-pass filtered per total wavenumber l of the spherical harmonics -- the route analysis -> response -> synthesis of
+  `spectra.SphericalAnalysis` -- as a derived variable `f"{variable}_{band}"` with the dims of the variable.  Every scorer
+  then works on the band-limited fields unchanged.
+
+  `bands`: {name: (l_lo, l_hi)} with inclusive bounds, `l_hi` None: up to lmax - 1; or {name: dict(l=(l_lo, l_hi),
+  complement=True)}: the field MINUS that band, f - synth(w a), which also keeps what the basis below lmax cannot
+  represent (a grid field is not band-limited: this is the true high-pass); or {name: response}, an array [lmax] of finite
+  weights (or dict(response=..., complement=...)).  1 to 8 bands.  `variables`: the target variables to filter (None: all).
+  `lmax`: the band limit (None: n_lon / 2).  `taper`: the half-width in wavenumbers of a raised-cosine edge around
+  l_lo - 1/2 and l_hi + 1/2 (0: sharp; no edge below l = 0 or above lmax - 1); two bands that meet at an edge still sum
+  to one there.
+
+  The filter is linear and Y_00 lies in the band with weight w[0]: a view of `x s + l` is `s view(x) + l w[0]`, with
+  `complement` `s view(x) + l (1 - w[0])` -- `channel_stats` returns the source scale and that location, and no affine
+  goes to the device.  With float32 tables a constant comes back within a few 1e-7 relative."""
+
+  MAX_BANDS = 8
+  EARTH_RADIUS_KM = 6371.0
+
+  def __init__(self, bands, variables: Optional[Sequence[str]] = None, lmax: Optional[int] = None, taper: float = 0):
+    if not isinstance(bands, Mapping) or not 1 <= len(bands) <= self.MAX_BANDS:
+      raise ValueError(f"bands must be a mapping of 1 .. {self.MAX_BANDS} named bands")
+    if lmax is not None and (isinstance(lmax, bool) or int(lmax) != lmax or int(lmax) < 1):
+      raise ValueError(f"lmax must be a positive integer or None, got {lmax!r}")
+    if not (math.isfinite(float(taper)) and float(taper) >= 0.0):
+      raise ValueError(f"taper must be finite and >= 0, got {taper!r}")
+    self.lmax = None if lmax is None else int(lmax)
+    self.taper = float(taper)
+    self.bands = {}                                        # name -> ("l", lo, hi or None, complement) | ("w", response, complement)
+    for name, b in bands.items():
+      if not isinstance(name, str) or not name:
+        raise ValueError(f"a band name must be a non-empty string, got {name!r}")
+      complement = False
+      if isinstance(b, Mapping):
+        extra = set(b) - {"l", "response", "complement"}
+        if extra or ("l" in b) == ("response" in b):
+          raise ValueError(f"band {name!r}: a dict takes either l=(lo, hi) or response=, and complement=; got {sorted(b)}")
+        complement = bool(b.get("complement", False))
+        b = b["l"] if "l" in b else np.asarray(b["response"], np.float64)
+      if isinstance(b, np.ndarray) or (isinstance(b, (list, tuple)) and len(b) != 2):
+        w = np.asarray(b, np.float64).reshape(-1)
+        if w.size < 1 or not np.isfinite(w).all():
+          raise ValueError(f"band {name!r}: a response is a non-empty array of finite weights")
+        if self.lmax is not None and w.size != self.lmax:
+          raise ValueError(f"band {name!r}: the response has {w.size} weights, lmax is {self.lmax}")
+        self.bands[name] = ("w", w.copy(), complement)
+        continue
+      try:
+        lo, hi = b
+      except (TypeError, ValueError):
+        raise ValueError(f"band {name!r}: a band is (l_lo, l_hi), a dict or a response array, got {b!r}") from None
+      for v in (lo, hi):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+          raise ValueError(f"band {name!r}: the bounds are wavenumbers (integers; l_hi may be None), got {b!r}")
+      if lo is None or int(lo) < 0 or (hi is not None and int(hi) < int(lo)):
+        raise ValueError(f"band {name!r}: 0 <= l_lo <= l_hi, got {b!r}")
+      if self.lmax is not None and (int(lo) >= self.lmax or (hi is not None and int(hi) >= self.lmax)):
+        raise ValueError(f"band {name!r}: the bounds {b!r} lie beyond lmax - 1 = {self.lmax - 1}")
+      self.bands[name] = ("l", int(lo), None if hi is None else int(hi), complement)
+    self.variables = None if variables is None else [str(v) for v in variables]
+    if self.variables is not None and (not self.variables or len(set(self.variables)) != len(self.variables)):
+      raise ValueError(f"variables must be distinct names, at least one, got {variables!r}")
+
+  @classmethod
+  def from_wavelengths_km(cls, bands, variables=None, lmax=None, taper=0) -> "BandSpec":
+    """`bands`: {name: (longest_km, shortest_km)} (or dict(km=(longest, shortest), complement=...)); a wavelength maps to
+    l = round(2 pi R / wavelength) with R = 6371 km; `longest_km` None: from l = 0, `shortest_km` None: up to lmax - 1."""
+    def wavenumber(km):
+      if km is None:
+        return None
+      if not (math.isfinite(float(km)) and float(km) > 0.0):
+        raise ValueError(f"a wavelength must be finite and > 0 km, got {km!r}")
+      return int(round(2.0 * math.pi * cls.EARTH_RADIUS_KM / float(km)))
+    out = {}
+    for name, b in bands.items():
+      complement = None
+      if isinstance(b, Mapping):
+        if set(b) - {"km", "complement"} or "km" not in b:
+          raise ValueError(f"band {name!r}: a dict takes km=(longest, shortest) and complement=, got {sorted(b)}")
+        complement, b = bool(b.get("complement", False)), b["km"]
+      longest, shortest = b
+      l = (wavenumber(longest) or 0, wavenumber(shortest))
+      out[name] = l if complement is None else dict(l=l, complement=complement)
+    return cls(out, variables, lmax, taper)
+
+  @property
+  def band_names(self) -> List[str]:
+    return list(self.bands)
+
+  @property
+  def names(self) -> List[str]:
+    """The derived variables, `f"{variable}_{band}"`, where `variables` were named; else the band names alone (the
+    variables are then those of the template: `template(template0)` has the full list)."""
+    if self.variables is None:
+      return self.band_names
+    return [f"{v}_{b}" for v in self.variables for b in self.bands]
+
+  def _lmax(self, template0) -> int:
+    n_lon = int(datasets.as_dataset(template0).sizes["lon"])
+    lmax = max(1, n_lon // 2) if self.lmax is None else self.lmax
+    if not 1 <= lmax <= n_lon // 2:
+      raise ValueError(f"lmax must be in 1 .. n_lon / 2 = {n_lon // 2}, got {lmax}")
+    return lmax
+
+  @staticmethod
+  def _edge(l, at, taper, rising):
+    """A raised-cosine step around `at` (between two wavenumbers) of half-width `taper`: 0 -> 1 when `rising`."""
+    if taper <= 0.0:
+      r = (l > at).astype(np.float64)
+    else:
+      r = 0.5 * (1.0 - np.cos(np.pi * np.clip((l - (at - taper)) / (2.0 * taper), 0.0, 1.0)))
+    return r if rising else 1.0 - r
+
+  def responses(self, lmax: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(response [K, lmax] float64, complement [K] int32), the bands in the order given."""
+    l = np.arange(lmax, dtype=np.float64)
+    w = np.ones((len(self.bands), lmax))
+    comp = np.zeros(len(self.bands), np.int32)
+    for k, (name, b) in enumerate(self.bands.items()):
+      comp[k] = int(b[-1])
+      if b[0] == "w":
+        if b[1].size != lmax:
+          raise ValueError(f"band {name!r}: the response has {b[1].size} weights, lmax is {lmax}")
+        w[k] = b[1]
+        continue
+      lo, hi = b[1], lmax - 1 if b[2] is None else b[2]
+      if lo >= lmax or hi >= lmax:
+        raise ValueError(f"band {name!r}: the bounds ({b[1]}, {b[2]}) lie beyond lmax - 1 = {lmax - 1}")
+      if lo > 0:
+        w[k] *= self._edge(l, lo - 0.5, self.taper, True)
+      if hi < lmax - 1:
+        w[k] *= self._edge(l, hi + 0.5, self.taper, False)
+    return w, comp
+
+  def _rows(self, template0):
+    """[(derived name, variable, band index, (offset, n) of the variable)] in the order given: variables, then bands."""
+    template0 = datasets.as_dataset(template0)
+    where = {name: (off, n) for name, off, n in datasets.channel_layout(template0)}
+    variables = list(where) if self.variables is None else self.variables
+    for v in variables:
+      if v not in where:
+        raise ValueError(f"{v!r} is not a target variable")
+    rows = [(f"{v}_{b}", v, k, where[v]) for v in variables for k, b in enumerate(self.bands)]
+    names = [r[0] for r in rows]
+    if len(set(names)) != len(names):
+      raise ValueError(f"the derived variable names are not distinct: {sorted(n for n in set(names) if names.count(n) > 1)}")
+    return rows
+
+  def template(self, template0) -> datasets.Dataset:
+    """A Dataset of the derived variables `f"{variable}_{band}"` (zeros) with the dims and coordinates of the variable."""
+    template0 = datasets.as_dataset(template0)
+    out = {}
+    for name, v, _, _ in self._rows(template0):
+      out[name] = datasets.Variable(template0[v].dims, np.zeros_like(np.asarray(template0[v].data)))
+    return datasets.Dataset(out, template0.coords)
+
+  def _per_channel(self, template0):
+    """(src_channel [c_d], band [c_d]) in the packed order of `template`."""
+    rows = {r[0]: r for r in self._rows(template0)}
+    src, band = [], []
+    for name, _, n in datasets.channel_layout(self.template(template0)):
+      _, _, k, (off, n_src) = rows[name]
+      assert n == n_src
+      src += [off + c for c in range(n)]
+      band += [k] * n
+    return np.asarray(src, np.int32), np.asarray(band, np.int32)
+
+  def plan(self, template0, scale=None, loc=None) -> Dict[str, object]:
+    """The keyword arguments of `NativeDenoiser.ens_band_set`, the synthesis tables of the template's grid among them.
+    `scale` and `loc` are taken for the interface of `DerivedSpec.plan` and not used: the filter is linear, the members stay
+    in their own units (`channel_stats`)."""
+    from . import spectra                                 # (spectra imports this module)
+    template0 = datasets.as_dataset(template0)
+    c_src = sum(n for _, _, n in datasets.channel_layout(template0))
+    lmax = self._lmax(template0)
+    response, complement = self.responses(lmax)
+    src, band = self._per_channel(template0)
+    leg, cos_s, sin_s = spectra.SphericalAnalysis.for_template(template0, lmax).synthesis_tables()
+    return dict(c_src=c_src, response=response, complement=complement, src_channel=src, band=band, legendre_synthesis=leg,
+                cos_s=cos_s, sin_s=sin_s)
+
+  def channel_stats(self, template0, scale=None, loc=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(scale_d, loc_d) [c_d]: the source channel's scale, and its location times w[0] (times 1 - w[0] with complement)."""
+    template0 = datasets.as_dataset(template0)
+    c_src = sum(n for _, _, n in datasets.channel_layout(template0))
+    scale = np.ones(c_src) if scale is None else np.asarray(scale, np.float64).reshape(-1)
+    loc = np.zeros(c_src) if loc is None else np.asarray(loc, np.float64).reshape(-1)
+    if scale.shape != (c_src,) or loc.shape != (c_src,):
+      raise ValueError(f"scale and loc must have shape ({c_src},)")
+    response, complement = self.responses(self._lmax(template0))
+    src, band = self._per_channel(template0)
+    w0 = np.where(complement[band] != 0, 1.0 - response[band, 0], response[band, 0])
+    return scale[src].copy(), loc[src] * w0
+
+
+# ---------------------------------------------------------------------------------------------
 # feature detection: cyclone centres, strike fields, tracks (gc_ens_feature_*)
 # ---------------------------------------------------------------------------------------------
 _EARTH_RADIUS_KM = 6371.0
@@ -2109,7 +2313,9 @@ class ScoredStore:
   (None: `ens_score` is not used on it), optionally the events counted on it -- an `EventSpec`, its packed `thresholds`
   in the members' units and `weight_q` = `quantize_node_weights(...)` -- and optionally the `plan` (`DerivedSpec.plan`) that
   fills it from the store of a `source` handle (`ens_derive`), or instead the `feature_plan` (`FeatureSpec.plan`) that fills
-  it with the strike fields of the centres found in the source's store (`ens_feature`; `centres()` has the lists), and optionally `order`: the probabilities of the quantile
+  it with the strike fields of the centres found in the source's store (`ens_feature`; `centres()` has the lists), or instead the
+  `band_plan` (`BandSpec.plan`) that fills it with the band-limited fields of the source's store (`ens_band`; the handle holds the
+  analysis tables already: `spectra.ensure_tables`), and optionally `order`: the probabilities of the quantile
   fields `score_order` leaves on the device next to its `OrderScores`, optionally `energy` and `variogram`: the plans
   (`EnergySpec.plan`, `VariogramSpec.plan`) of `score_energy` and `score_variogram`, and optionally `climatology`: a second handle of the
   same graph, batch and c_out (`Denoiser.climatology_handle`) whose member store takes the K climatological samples
@@ -2123,7 +2329,7 @@ class ScoredStore:
   a handle, or thresholds that change from call to call (assign `thresholds` before the call)."""
 
   def __init__(self, handle, n_members: int, node_weight=None, *, plan=None, source=None, set_per_score: bool = False,
-               climatology=None, climatology_source=None, feature_plan=None, **scorers):
+               climatology=None, climatology_source=None, feature_plan=None, band_plan=None, **scorers):
     """`scorers`: per row of `SCORERS` with a `score`, its name (what switches it on) and its settings, None by default."""
     for row in (r for r in SCORERS if r.score is not None):
       for key in (row.name,) + row.settings:
@@ -2132,17 +2338,19 @@ class ScoredStore:
       raise TypeError(f"ScoredStore() got an unexpected keyword argument {next(iter(scorers))!r}")
     if self.regions is not None and self.region_bits is None:
       raise ValueError("regions need their node bits (RegionSpec.node_bits)")
-    if climatology_source is not None and (climatology is None or plan is None):
-      raise ValueError("a climatology source goes with a climatology handle and a derive plan")
+    if climatology_source is not None and (climatology is None or (plan is None and band_plan is None)):
+      raise ValueError("a climatology source goes with a climatology handle and a derive plan (or a band plan)")
     if self.events is not None and self.weight_q is None:
       raise ValueError("events need the quantised node weights (quantize_node_weights)")
     if plan is not None and feature_plan is not None:
       raise ValueError("a store is filled by a derive plan or by a feature plan, not both")
-    if (plan is None and feature_plan is None) != (source is None):
-      raise ValueError("a derive plan (or a feature plan) and its source handle go together")
+    if band_plan is not None and (plan is not None or feature_plan is not None):
+      raise ValueError("a store is filled by one of a derive plan, a feature plan and a band plan, not two")
+    if (plan is None and feature_plan is None and band_plan is None) != (source is None):
+      raise ValueError("a derive plan (or a feature plan, or a band plan) and its source handle go together")
     self.handle, self.n_members, self.node_weight = handle, int(n_members), node_weight
     self.plan, self.source, self.set_per_score = plan, source, bool(set_per_score)
-    self.feature_plan = feature_plan
+    self.feature_plan, self.band_plan = feature_plan, band_plan
     if self.order is not None:
       self.order = tuple(float(p) for p in np.asarray(self.order, dtype=np.float64).reshape(-1))
     self.climatology, self.climatology_source = climatology, climatology_source
@@ -2159,6 +2367,8 @@ class ScoredStore:
       self.handle.ens_derive_set(**self.plan)
     if self.feature_plan is not None:
       self.handle.ens_feature_set(**self.feature_plan)
+    if self.band_plan is not None:
+      self.handle.ens_band_set(**self.band_plan)
 
   def configure(self) -> None:
     """The plan, then every scorer that is switched on, in the order of `SCORERS` -- the thresholds, the probabilities, the
@@ -2229,10 +2439,14 @@ class ScoredStore:
     if self.climatology_source is not None:
       K = int(n_samples)
       self._reserve_climatology(K)
+      band = self.band_plan is not None            # (the climatology handle of a band view holds the analysis tables already)
       if self.set_per_score or not self._clim_plan_set:
-        self.climatology.ens_derive_set(**self.plan)
+        if band:
+          self.climatology.ens_band_set(**self.band_plan)
+        else:
+          self.climatology.ens_derive_set(**self.plan)
         self._clim_plan_set = True
-      self.climatology.ens_derive(self.climatology_source, source_truth)
+      (self.climatology.ens_band if band else self.climatology.ens_derive)(self.climatology_source, source_truth)
     elif fields is not None:
       K = len(fields)
       self._reserve_climatology(K)
@@ -2256,7 +2470,7 @@ class ScoredStore:
 
   def score(self, truth=None, want_fields: bool = False) -> Tuple[EnsembleScores, Optional["EventScores"]]:
     """-> (raw `EnsembleScores`, `EventScores` or None).  `truth` [G, B, c_out] in the members' units, None: the truth
-    already on the device; with a plan (or a feature plan) the store is first filled from the source's (members and truth,
+    already on the device; with a plan (or a feature plan, or a band plan) the store is first filled from the source's (members and truth,
     device to device) and `truth` [G, B, c_src] is the SOURCE's."""
     if self.plan is not None:
       if self.set_per_score:
@@ -2267,6 +2481,11 @@ class ScoredStore:
       if self.set_per_score:
         self._set_plan()
       self.handle.ens_feature(self.source, truth)
+      truth = None
+    if self.band_plan is not None:
+      if self.set_per_score:
+        self._set_plan()
+      self.handle.ens_band(self.source, truth)
       truth = None
     sums, hist = self.handle.ens_score(truth, want_fields=want_fields)
     return EnsembleScores(sums, hist, self.n_members), self.score_events(None)

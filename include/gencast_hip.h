@@ -624,6 +624,55 @@ int gc_ens_derive_set_expr(gc_handle* dst, int32_t c_src, const int32_t* op, con
                            const int32_t* pole_row /* [n_lat] */);
 
 /*
+ * Spectral band views on the device: the members and the truth of one handle's gc_ens_* store,
+ * low-, band- or high-pass filtered per total wavenumber, left in the member store of a SECOND handle, on which every scorer
+ * of this library then works as it is -- the CRPS of the planetary waves, a wind event on the field without its small
+ * scales.  The reference project has no spectral diagnostics; the yardstick is the definition below in float64, restated in
+ * tests/band_reference.py.
+ * Grid, basis and analysis are those of gc_spec_set_tables on `dst` (n_lat x n_lon = G, lmax = L): the filter needs them.
+ * A plan has K bands (1 <= K <= 8), each a response w_k[l] (float64, l < L, finite) and a flag complement_k, and per derived
+ * channel j of dst (c_d = dst's c_out) a pair (src_channel[j], band[j]).  For one field -- a member or the truth -- and one
+ * source column with data f, k = band[j]:
+ *   1  a = analysis(f), the coefficients of gc_spec_field: once per DISTINCT source column, however many bands read it
+ *   2  b[part][m][l] = w_k[l] a[part][m][l]                                                      in binary64, rounded
+ *   3  G[part][m][lat] = sum_{l = m .. L-1} S[m][lat][l] b[part][m][l]                            l ascending, fused multiply-adds
+ *      S = legendre_synthesis = float32(N_lm P_l^m(sin lat)): the plain A_m of the analysis, zero for l < m
+ *   4  g(lat, j) = sum_m (cos_s[m][j] G[0][m][lat] + sin_s[m][j] G[1][m][lat])                    m ascending, the cosine term
+ *      before the sine term, fused; cos_s[m][j] = float32(amp_m cos(m phi_j)), sin_s likewise, amp_0 = 1, else sqrt 2
+ *   5  d = (float) g, or with complement_k d = (float) ((double) f - g): rounded once
+ * Tables are float32 (built in float64 on the host: spectra.py), every product and sum on the device is binary64, every sum
+ * has one writer and a fixed order, and the only atomics are the integer ORs of the analysis' flags: the same call twice
+ * returns identical bytes.  complement is what makes a true high-pass: a grid field is not band-limited below L, f - low(f)
+ * keeps the part of f outside the span of the basis, synth((1 - w) a) drops it.  The truth goes through the same map.
+ * A source column of a field that holds a value that is not finite makes every derived channel reading it NaN at every
+ * node of THAT field (a transform cannot skip points); other fields and columns are unaffected.  Counter
+ * "ens_band_invalid_columns": the (field, batch member, distinct source channel) triples of the last call that were so.
+ *   gc_ens_band_set  the plan.  Needs gc_set_graph and gc_spec_set_tables on dst (else GC_ERR_STATE).  Through pinned staging:
+ *                    the caller's arrays are free on return.  Replaces an earlier plan ("device_allocations" stays flat),
+ *                    survives gc_ens_reserve, released by gc_destroy; gc_spec_set_tables on dst drops it.
+ *                    GC_ERR_UNSUPPORTED: K outside 1..8.  GC_ERR_INVALID_ARGUMENT: a null pointer, c_src < 1, a source
+ *                    channel outside [0, c_src), a band index outside [0, K), a response value that is not finite.
+ *   gc_ens_band      the contract of gc_ens_derive: every slot of dst's store becomes the band field and counts as pushed;
+ *                    dst's truth buffer becomes the band truth; dst's event codes and mean / variance fields count as not
+ *                    computed.  truth: host [G, B, c_src], uploaded into and kept in src's truth buffer, or NULL = src's
+ *                    last truth.  The kernels run on dst's stream, ordered behind src's stream by an event.  Synchronous.
+ *                    GC_ERR_INVALID_ARGUMENT: src is NULL, dst itself or on another device; src has no graph, another G or
+ *                    batch, or c_out != c_src of the plan.  GC_ERR_STATE: no tables, no plan, no store on dst, no store on
+ *                    src, the two stores differ in M, a src slot not pushed since its gc_ens_reserve, no truth.
+ * Launches, per field (the M members, then the truth, one at a time): a gather of the distinct source columns, the two
+ * analysis kernels of gc_spec_field, a Legendre synthesis with the response multiply in its loader, and a Fourier synthesis
+ * whose epilogue subtracts, rounds and writes straight into dst's slot.  The scratch of ONE field (the gathered columns, the
+ * two analysis steps, [2][L][n_lat][B c_d] doubles of the Legendre synthesis) and the flags are handle-owned and made again
+ * only when their size changes.  Nothing else on either handle is touched.  Counters: "ens_band_calls" (calls so far),
+ * "ens_band_device_us" (HIP-event time of the last call's launches), "ens_band_invalid_columns".
+ */
+int gc_ens_band_set(gc_handle* dst, int32_t c_src, int32_t n_bands, const double* response /* [K][lmax] */,
+                    const int32_t* complement /* [K] */, const int32_t* src_channel /* [c_out] */,
+                    const int32_t* band /* [c_out] */, const float* legendre_synthesis /* [lmax m][n_lat][lmax l], zero for l < m */,
+                    const float* cos_s /* [lmax][n_lon] */, const float* sin_s /* [lmax][n_lon] */);
+int gc_ens_band(gc_handle* dst, gc_handle* src, const float* truth /* [G,B,c_src] host, NULL = src's last truth */);
+
+/*
  * Ensemble order statistics on the device: the M members of every point of the gc_ens_* store in
  * ascending order, and what follows from that order -- quantile fields (the median, a p10 / p90 band) and the bin sums of
  * Hersbach's (2000) decomposition of the ensemble CRPS into a reliability and a potential part (gencast-flax-nnx_amd/
