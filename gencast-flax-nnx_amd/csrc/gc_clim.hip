@@ -19,6 +19,7 @@
 //   C4 = sum w ae_c   C5 = sum w d_c
 // No atomics on floats: every accumulator has one writer and every sum a fixed order (a thread's nodes ascending, the
 // node lanes of a column in lane order, the blocks in index order), so the same call twice returns identical bytes.
+#include "gc_colsum.h"
 #include "gc_sort.h"
 #include "gc_store.h"
 
@@ -41,12 +42,10 @@ __device__ inline double clim_gap_sum(float (&v)[P], int n) {
   return d;
 }
 
-// The pass.  Thread layout of gc_ens_score_kernel: grid.y cuts W = B c_out into column tiles of at most 256; inside a tile
-// of wt columns thread t owns column t % wt of node lane t / wt, q = 256 / wt lanes; block x walks the contiguous node
-// range [x per, (x + 1) per) in steps of q.  Per point the K samples are read once from HBM (K loads of stride `field`,
-// each coalesced across the wave) into P registers padded with +inf; their slot-order sums are formed while loading, then
-// they are sorted for d_c.  The M members follow into the SAME registers: cbar is known by then, so q_x is formed while
-// loading as well.  A point with a non-finite value never enters the network.
+// The pass, on the 256-wide cut of gc_colsum.h.  Per point the K samples are read once from HBM into P padded registers
+// (load_padded); their slot-order sums are formed while loading, then they are sorted for d_c.  The M members follow into
+// the SAME registers: cbar is known by then, so q_x is formed while loading as well.  A point with a non-finite value
+// never enters the network.
 // Out, as plain stores: part[block x][12][W] (double), cpart[block x][W] (counted points), ipart[block x][tile] (skipped).
 template <int P>
 __global__ __launch_bounds__(256) void gc_ens_clim_kernel(const float* __restrict__ mem, int M,
@@ -58,62 +57,42 @@ __global__ __launch_bounds__(256) void gc_ens_clim_kernel(const float* __restric
   __shared__ double lane_sum[256];
   __shared__ unsigned lane_cnt[256];
   __shared__ unsigned skipped;
-  const int col0 = blockIdx.y * 256;
-  const int wt = min(256, W - col0);
-  const int q = 256 / wt;
-  const int tid = threadIdx.x;
-  const int lane = tid / wt;
-  const int cl = tid - lane * wt;
-  const int col = col0 + cl;
+  const ColTile ct(256, 256, W, blockIdx.y);
+  const int tid = threadIdx.x, col = ct.col;
   if (tid == 0) skipped = 0u;
   __syncthreads();
   double s[kClimSums];
 #pragma unroll
   for (int k = 0; k < kClimSums; ++k) s[k] = 0.0;
   unsigned cnt = 0, inv = 0;
-  if (lane < q) {
+  if (ct.active()) {
     const double dM = (double)M, dK = (double)K;
     const double pairs_x = 0.5 * dM * (dM - 1.0), pairs_c = 0.5 * dK * (dK - 1.0);
-    const int n_end = min(G, (int)(blockIdx.x + 1) * per);
-    for (int n = blockIdx.x * per + lane; n < n_end; n += q) {
+    const int n_end = ct.n_end(G, per);
+    for (int n = ct.n_begin(per); n < n_end; n += ct.q) {
       const size_t i = (size_t)n * W + col;
       const float y = truth[i];
       const double yd = (double)y;
       float v[P];
-      bool fin = isfinite(y);
       double csum = 0.0, ae_c = 0.0;
-#pragma unroll
-      for (int k = 0; k < P; ++k) {
-        v[k] = __builtin_inff();
-        if (k < K) {
-          const float c = clim[(size_t)k * field + i];
-          v[k] = c;
-          fin = fin && isfinite(c);
-          csum += (double)c;
-          ae_c += fabs((double)c - yd);
-        }
-      }
-      if (!fin) {                                  // (the members are not looked at: the point adds to `invalid` alone)
+      const bool cfin = load_padded<P>(v, clim, field, i, K, [&](float c) {
+        csum += (double)c;
+        ae_c += fabs((double)c - yd);
+      });
+      if (!(cfin && isfinite(y))) {                // (the members are not looked at: the point adds to `invalid` alone)
         ++inv;
         continue;
       }
       const double cbar = csum / dK;
       const double d_c = clim_gap_sum<P>(v, K) / pairs_c;
       double sum = 0.0, ae_x = 0.0, q_x = 0.0;
-#pragma unroll
-      for (int k = 0; k < P; ++k) {
-        v[k] = __builtin_inff();
-        if (k < M) {
-          const float x = mem[(size_t)k * field + i];
-          v[k] = x;
-          fin = fin && isfinite(x);
-          sum += (double)x;
-          ae_x += fabs((double)x - yd);
-          const double dx = (double)x - cbar;
-          q_x += dx * dx;
-        }
-      }
-      if (!fin) {
+      const bool xfin = load_padded<P>(v, mem, field, i, M, [&](float x) {
+        sum += (double)x;
+        ae_x += fabs((double)x - yd);
+        const double dx = (double)x - cbar;
+        q_x += dx * dx;
+      });
+      if (!xfin) {
         ++inv;
         continue;
       }
@@ -137,59 +116,33 @@ __global__ __launch_bounds__(256) void gc_ens_clim_kernel(const float* __restric
     }
   }
   if (inv) atomicAdd(&skipped, inv);               // (an integer: the order of these does not show)
-  // the q lanes of a column, added in lane order
 #pragma unroll
   for (int k = 0; k < kClimSums; ++k) {
-    lane_sum[tid] = s[k];
-    __syncthreads();
-    if (tid < wt) {
-      double t = lane_sum[tid];
-      for (int l = 1; l < q; ++l) t += lane_sum[l * wt + tid];
-      part[((size_t)blockIdx.x * kClimSums + k) * W + col] = t;
-    }
-    __syncthreads();
+    const double t = col_total(lane_sum, s[k], ct);
+    if (tid < ct.wt) part[((size_t)blockIdx.x * kClimSums + k) * W + col] = t;
   }
-  lane_cnt[tid] = cnt;
-  __syncthreads();
-  if (tid < wt) {
-    unsigned t = lane_cnt[tid];
-    for (int l = 1; l < q; ++l) t += lane_cnt[l * wt + tid];
-    cpart[(size_t)blockIdx.x * W + col] = t;
-  }
+  const unsigned t = col_total(lane_cnt, cnt, ct);
+  if (tid < ct.wt) cpart[(size_t)blockIdx.x * W + col] = t;
   if (tid == 0) ipart[(size_t)blockIdx.x * gridDim.y + blockIdx.y] = skipped;
 }
 
-// One thread per result: the blocks of a sum are added in ascending block order.  e < 12 W: sum j = e / W of column
-// e % W -> out [W][12]; then W counts -> outc [W]; then one thread for the skipped points -> outc[W].
-__global__ __launch_bounds__(256) void gc_ens_clim_finish_kernel(const double* __restrict__ part,
-                                                                  const unsigned* __restrict__ cpart,
-                                                                  const unsigned* __restrict__ ipart, int blocks, int tiles,
-                                                                  int W, double* __restrict__ out,
-                                                                  unsigned long long* __restrict__ outc) {
-  const int nd = kClimSums * W;
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e < nd) {
+// The ascending block finish: e < 12 W: sum j = e / W of column e % W, as the partials lie -> out [W][12]; then W counts
+// -> outc [W]; the skipped points -> outc[W].
+struct ClimFinishMap {
+  const double* part;
+  const unsigned* cpart;
+  int W;
+  SkippedSum skipped;
+  __host__ __device__ int sums() const { return kClimSums * W; }
+  __host__ __device__ int counts() const { return W; }
+  __device__ BlockSum<double> sum(int e) const {
     const int j = e / W, col = e - j * W;
-    double t = 0.0;
-#pragma unroll 8
-    for (int b = 0; b < blocks; ++b) t += part[((size_t)b * kClimSums + j) * W + col];
-    out[(size_t)col * kClimSums + j] = t;
-  } else if (e < nd + W) {
-    const int col = e - nd;
-    unsigned long long t = 0ull;
-#pragma unroll 8
-    for (int b = 0; b < blocks; ++b) t += cpart[(size_t)b * W + col];
-    outc[col] = t;
-  } else if (e == nd + W) {
-    unsigned long long t = 0ull;
-    for (int i = 0; i < blocks * tiles; ++i) t += ipart[i];
-    outc[W] = t;
+    return {part + e, (size_t)kClimSums * W, (size_t)col * kClimSums + j};
   }
-}
+  __device__ BlockSum<unsigned> count(int col) const { return {cpart + col, (size_t)W, (size_t)col}; }
+};
 
-static int clim_pad(int n) { return n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
-
-// ONE padded size for both samples, P = max(pad(M), pad(K)): six instantiations
+// ONE padded size for both samples, that of max(M, K): six instantiations
 static hipError_t launch_ens_clim(hipStream_t s, const float* mem, int M, const float* clim, int K, size_t field,
                                   const float* truth, const float* node_w, int G, int B, int c_out, double* part,
                                   unsigned* cpart, unsigned* ipart) {
@@ -197,29 +150,16 @@ static hipError_t launch_ens_clim(hipStream_t s, const float* mem, int M, const 
   const int blocks = loss_reduce_blocks(G, B, c_out);
   const int per = (G + blocks - 1) / blocks;
   const dim3 grid(blocks, (W + 255) / 256);
-#define GC_CLIM_CASE(P)                                                                                                     \
-  case P:                                                                                                                   \
-    hipLaunchKernelGGL((gc_ens_clim_kernel<P>), grid, dim3(256), 0, s, mem, M, clim, K, field, truth, node_w, G, W, per, part, \
-                       cpart, ipart);                                                                                       \
-    break
-  switch (std::max(clim_pad(M), clim_pad(K))) {
-    GC_CLIM_CASE(2);
-    GC_CLIM_CASE(4);
-    GC_CLIM_CASE(8);
-    GC_CLIM_CASE(16);
-    GC_CLIM_CASE(32);
-    GC_CLIM_CASE(64);
-  }
-#undef GC_CLIM_CASE
-  return hipGetLastError();
+  return pad_dispatch(std::max(M, K), [&](auto p) {
+    hipLaunchKernelGGL((gc_ens_clim_kernel<decltype(p)::value>), grid, dim3(256), 0, s, mem, M, clim, K, field, truth, node_w, G, W, per, part,
+                       cpart, ipart);
+    return hipGetLastError();
+  });
 }
 
 static hipError_t launch_ens_clim_finish(hipStream_t s, const double* part, const unsigned* cpart, const unsigned* ipart,
                                          int blocks, int tiles, int W, double* out, unsigned long long* outc) {
-  const int total = (kClimSums + 1) * W + 1;
-  hipLaunchKernelGGL(gc_ens_clim_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, part, cpart, ipart, blocks, tiles,
-                     W, out, outc);
-  return hipGetLastError();
+  return launch_block_finish(s, ClimFinishMap{part, cpart, W, {ipart, tiles, (size_t)W}}, blocks, out, outc);
 }
 
 }  // namespace gc

@@ -14,6 +14,7 @@
 //   S0 = sum w, S1 = sum w (m - y), S2 = sum w (m - y)^2, S3 = sum w s2, S4 = sum w ae, S5 = sum w d,  H[r] += 1
 // No atomics on floats: every partial has one writer and every sum a fixed order, so the result does not depend on how
 // the launch was scheduled.  The rank counts are integers; their LDS atomics commute.
+#include "gc_colsum.h"
 #include "gc_store.h"
 
 // the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
@@ -23,6 +24,7 @@ namespace gc {
 
 constexpr int kEnsMinMembers = 2, kEnsMaxMembers = 64;
 
+// (This kernel and its finish keep their own text: on the shared pieces of gc_colsum.h the pass timed slower.)
 // Thread layout of gc_loss_reduce_kernel: a grid node's B rows are W = B c_out consecutive floats; grid.y cuts W into
 // column tiles of at most 256; inside a tile of wt columns thread t owns column t % wt (ONE accumulator set) of node
 // lane t / wt, q = 256 / wt lanes; block x walks the contiguous node range [x per, (x + 1) per) in steps of q.
@@ -180,8 +182,6 @@ __global__ __launch_bounds__(256) void gc_ens_finish_kernel(const double* __rest
     if (tid == 0) hist[(size_t)W * bins] = skipped;
   }
 }
-
-static size_t ens_score_lds(int M, int W) { return (size_t)M * 256 * sizeof(float) + (size_t)std::min(256, W) * (M + 1) * sizeof(unsigned); }
 
 static hipError_t launch_ens_score(hipStream_t s, const float* mem, size_t field, int M, const float* truth, const float* node_w,
                                    int G, int B, int c_out, double* part, unsigned* hpart, unsigned* ipart, float* mean, float* var) {

@@ -13,6 +13,7 @@
 // per point and threshold (k | o << 7, 255 = not counted: the exceedance-probability map), the table pass reads those
 // bytes and the weights.  Fusing them would need [T][W][2 (M + 1)] 64-bit bins per workgroup (268 KB at T = 4, W = 82,
 // M = 50), which no workgroup has.
+#include "gc_colsum.h"
 #include "gc_store.h"
 
 namespace gc {
@@ -83,22 +84,20 @@ __global__ __launch_bounds__(256) void gc_ens_event_code_kernel(const float* __r
 
 // Column tiles of the table pass: as few as fit the LDS budget, of equal width.  A column's bins are padded to an ODD
 // stride 2 (M + 1) + 1: for a rare event nearly every point of a column lands in bin (o = 0, k = 0), the lanes of a wave
-// own different columns (thread layout of gc_ens_score_kernel), and an odd stride puts those bins on different banks.
+// own different columns (thread layout of gc_colsum.h), and an odd stride puts those bins on different banks.
 static int evt_stride(int M) { return 2 * (M + 1) + 1; }
 static int evt_tiles(int W, int M) {
   const int fit = std::max(1, std::min(256, (int)(kEvtTableLds / ((size_t)evt_stride(M) * 12))));
   return (W + fit - 1) / fit;
 }
 static int evt_tile_width(int W, int M) { const int tiles = evt_tiles(W, M); return (W + tiles - 1) / tiles; }
-// node-range blocks: 8 nodes per thread or more, as loss_reduce_blocks, within kEvtMaxWorkgroups for the whole grid
+// node-range blocks: within kEvtMaxWorkgroups for the whole grid
 static int evt_node_blocks(int G, int W, int M, int T) {
-  const int q = 256 / evt_tile_width(W, M);
-  return std::max(1, std::min((G + 8 * q - 1) / (8 * q), kEvtMaxWorkgroups / (T * evt_tiles(W, M))));
+  return node_blocks(G, 256 / evt_tile_width(W, M), kEvtMaxWorkgroups / (T * evt_tiles(W, M)));
 }
 
-// Table pass.  grid = (node-range blocks, thresholds, column tiles).  Inside a tile of wt columns thread t owns column
-// t % wt of node lane t / wt, q = 256 / wt lanes; block x walks the contiguous node range [x per, (x + 1) per) in steps
-// of q.  Dynamic LDS: unsigned long long[wt][stride] weighted, then unsigned[wt][stride] counts.  A block's non-zero bins
+// Table pass.  grid = (node-range blocks, thresholds, column tiles): equal-width tiles of gc_colsum.h, cap = 256.
+// Dynamic LDS: unsigned long long[wt][stride] weighted, then unsigned[wt][stride] counts.  A block's non-zero bins
 // leave by integer atomics into the zeroed global tables weighted / counts [T][W][2][M + 1] and invalid [T]: per-block
 // partials would be blocks x T x W x 2 (M + 1) x 12 bytes (hundreds of MB at the 1-degree size) for sums that need no order.
 __global__ __launch_bounds__(256) void gc_ens_event_table_kernel(const unsigned char* __restrict__ code, size_t field,
@@ -110,12 +109,9 @@ __global__ __launch_bounds__(256) void gc_ens_event_table_kernel(const unsigned 
   extern __shared__ __attribute__((aligned(16))) unsigned char evt_lds[];
   __shared__ unsigned skipped;
   const int t = blockIdx.y;
-  const int col0 = blockIdx.z * tile_w;
-  const int wt = min(tile_w, W - col0);
-  const int q = 256 / wt;
+  const ColTile ct(tile_w, 256, W, blockIdx.z);
+  const int col0 = ct.col0, wt = ct.wt, cl = ct.cl;
   const int tid = threadIdx.x;
-  const int lane = tid / wt;
-  const int cl = tid - lane * wt;
   const int bins = 2 * (M + 1), stride = bins + 1;
   unsigned long long* const wtab = reinterpret_cast<unsigned long long*>(evt_lds);
   unsigned* const ctab = reinterpret_cast<unsigned*>(wtab + (size_t)tile_w * stride);
@@ -126,11 +122,11 @@ __global__ __launch_bounds__(256) void gc_ens_event_table_kernel(const unsigned 
   if (tid == 0) skipped = 0u;
   __syncthreads();
   unsigned inv = 0;
-  if (lane < q) {
+  if (ct.active()) {
     const unsigned char* const my = code + (size_t)t * field + col0 + cl;
-    const int n_end = min(G, (int)(blockIdx.x + 1) * per);
+    const int n_end = ct.n_end(G, per);
 #pragma unroll 4
-    for (int n = blockIdx.x * per + lane; n < n_end; n += q) {
+    for (int n = ct.n_begin(per); n < n_end; n += ct.q) {
       const unsigned c = my[(size_t)n * W];
       if (c == 255u) {
         ++inv;

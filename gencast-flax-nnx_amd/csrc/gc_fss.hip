@@ -19,6 +19,7 @@
 // No atomics on floats and every sum in a fixed order: two calls give the same bytes.  The work buffer holds the row sums of
 // one threshold and one chunk of columns for every scale and every row (a window reaches any row, a column none but its own):
 // chunks of columns need no halo.
+#include "gc_colsum.h"
 #include "gc_store.h"
 
 // the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
@@ -164,28 +165,27 @@ __global__ __launch_bounds__(256) void gc_ens_fss_col_kernel(const unsigned char
 #pragma unroll
   for (int j = 0; j < 4; ++j) red[j][tid] = acc[j];
   __syncthreads();
-  for (int e = tid; e < 4 * wc; e += 256) {          // the q lanes of a column, in lane order
+  for (int e = tid; e < 4 * wc; e += 256) {          // the lane fold (gc_colsum.h) on each of the four rows
     const int j = e / wc, c = e - j * wc;
-    double v = red[j][c];
-    for (int l = 1; l < q; ++l) v += red[j][l * wc + c];
-    part[(((size_t)blockIdx.x * S + s) * 4 + j) * wc + c] = v;
+    part[(((size_t)blockIdx.x * S + s) * 4 + j) * wc + c] = lane_fold(red[j], c, wc, q);
   }
 }
 
-// One thread per result of the chunk: the blocks of a sum in ascending block order.  e = (s 4 + j) wc + c as the partials
-// lie; out [S][W][4] of the threshold.
-__global__ __launch_bounds__(256) void gc_ens_fss_finish_kernel(const double* __restrict__ part, int blocks, int S, int W,
-                                                                 int c0, int wc, double* __restrict__ out) {
-  const int nd = 4 * S * wc;
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= nd) return;
-  const int sj = e / wc, c = e - sj * wc, s = sj >> 2, j = sj & 3;
-  if (c0 + c >= W) return;
-  double v = 0.0;
-#pragma unroll 8
-  for (int b = 0; b < blocks; ++b) v += part[(size_t)b * nd + e];
-  out[((size_t)s * W + c0 + c) * 4 + j] = v;
-}
+// The ascending block finish (gc_colsum.h) of the chunk: e = (s 4 + j) wc + c as the partials lie -> out [S][W][4] of the
+// threshold; a column of the chunk past W stands for no result.  No counts, no skipped points.
+struct FssFinishMap {
+  const double* part;
+  int S, W, c0, wc;
+  SkippedSum skipped;
+  __host__ __device__ int sums() const { return 4 * S * wc; }
+  __host__ __device__ int counts() const { return 0; }
+  __device__ BlockSum<double> sum(int e) const {
+    const int sj = e / wc, c = e - sj * wc, s = sj >> 2, j = sj & 3;
+    if (c0 + c >= W) return {nullptr, 0, 0};
+    return {part + e, (size_t)sums(), ((size_t)s * W + c0 + c) * 4 + j};
+  }
+  __device__ BlockSum<unsigned> count(int) const { return {nullptr, 0, 0}; }
+};
 
 // Fields: the column pass of one scale (slab 0 of the work buffer), one thread per point of the chunk, writing
 // prob = (float) P and obs = (float) O into the chunk's [G][wc] arrays instead of reducing; NaN where the point does not count.
@@ -234,10 +234,7 @@ static int fss_chunk(int S, int G, int W, int wt) {
   return std::min(cap, gci::round_up(W, wt));
 }
 
-static int fss_blocks(int G, int wc) {
-  const int q = 256 / wc;
-  return std::max(1, std::min((G + 8 * q - 1) / (8 * q), kFssMaxBlocks));
-}
+static int fss_blocks(int G, int wc) { return node_blocks(G, 256 / wc, kFssMaxBlocks); }
 
 static hipError_t launch_ens_fss_row(hipStream_t s, const unsigned char* code, int n_lat, int n_lon, int W, int c0, int wc,
                                      int wt, int S, const int* r_lon, uint2* work) {
@@ -261,8 +258,7 @@ static hipError_t launch_ens_fss_col(hipStream_t s, const unsigned char* code, c
 }
 
 static hipError_t launch_ens_fss_finish(hipStream_t s, const double* part, int blocks, int S, int W, int c0, int wc, double* out) {
-  hipLaunchKernelGGL(gc_ens_fss_finish_kernel, dim3((4 * S * wc + 255) / 256), dim3(256), 0, s, part, blocks, S, W, c0, wc, out);
-  return hipGetLastError();
+  return launch_block_finish(s, FssFinishMap{part, S, W, c0, wc, {}}, blocks, out, nullptr);
 }
 
 static hipError_t launch_ens_fss_field(hipStream_t s, const unsigned char* code, const unsigned* row_wq, int r_lat,

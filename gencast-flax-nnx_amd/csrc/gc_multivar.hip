@@ -20,6 +20,7 @@
 // Per (b, c, o):  V0 = sum omega   V1 = sum omega (vy - vx)^2   V2 = sum omega vx   V3 = sum omega vy   and a pair count.
 // No atomics on floats: every accumulator has one writer and every sum a fixed order (a thread's points ascending, the
 // slices or node lanes in index order, the blocks in index order), so the same call twice returns identical bytes.
+#include "gc_colsum.h"
 #include "gc_store.h"
 
 // the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
@@ -166,32 +167,22 @@ __global__ __launch_bounds__(256) void gc_ens_energy_kernel(const float* __restr
   }
 }
 
-// One thread per result: the blocks of a sum are added in ascending block order.  e < BK P: D2; then BK sums S0 -> out
-// behind them; then one thread for the skipped points.
-__global__ __launch_bounds__(256) void gc_ens_energy_finish_kernel(const double* __restrict__ part,
-                                                                    const double* __restrict__ s0part,
-                                                                    const unsigned* __restrict__ ipart, int blocks, int BK,
-                                                                    int P, double* __restrict__ out,
-                                                                    unsigned long long* __restrict__ outc) {
-  const int nd = BK * P;
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e < nd) {
-    double t = 0.0;
-#pragma unroll 8
-    for (int x = 0; x < blocks; ++x) t += part[(size_t)x * nd + e];
-    out[e] = t;
-  } else if (e < nd + BK) {
-    const int y = e - nd;
-    double t = 0.0;
-#pragma unroll 8
-    for (int x = 0; x < blocks; ++x) t += s0part[(size_t)x * BK + y];
-    out[e] = t;
-  } else if (e == nd + BK) {
-    unsigned long long t = 0ull;
-    for (int i = 0; i < blocks * BK; ++i) t += ipart[i];
-    outc[0] = t;
+// The ascending block finish (gc_colsum.h): e < BK P: D2, as the partials lie; then BK sums S0 from their own array -> out
+// behind them; no counts; the skipped points -> outc[0].
+struct EnergyFinishMap {
+  const double* part;
+  const double* s0part;
+  int BK, P;
+  SkippedSum skipped;
+  __host__ __device__ int sums() const { return BK * P + BK; }
+  __host__ __device__ int counts() const { return 0; }
+  __device__ BlockSum<double> sum(int e) const {
+    const int nd = BK * P;
+    if (e < nd) return {part + e, (size_t)nd, (size_t)e};
+    return {s0part + (e - nd), (size_t)BK, (size_t)e};
   }
-}
+  __device__ BlockSum<unsigned> count(int) const { return {nullptr, 0, 0}; }
+};
 
 static hipError_t launch_ens_energy(hipStream_t s, const float* mem, size_t field, int M, const float* truth,
                                     const float* node_w, const double* scale, const int* gchan, const int* goff, int G, int B,
@@ -221,10 +212,7 @@ static hipError_t launch_ens_energy(hipStream_t s, const float* mem, size_t fiel
 
 static hipError_t launch_ens_energy_finish(hipStream_t s, const double* part, const double* s0part, const unsigned* ipart,
                                            int blocks, int BK, int P, double* out, unsigned long long* outc) {
-  const int total = BK * P + BK + 1;
-  hipLaunchKernelGGL(gc_ens_energy_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, part, s0part, ipart, blocks, BK, P,
-                     out, outc);
-  return hipGetLastError();
+  return launch_block_finish(s, EnergyFinishMap{part, s0part, BK, P, {ipart, BK, 0}}, blocks, out, outc);
 }
 
 // |u|^p for the three orders: PK = 0 sqrt, 1 identity, 2 a product
@@ -234,9 +222,7 @@ __device__ inline double mv_vpow(double u) {
   return PK == 0 ? sqrt(a) : PK == 1 ? a : a * a;
 }
 
-// The variogram pass.  Thread layout of gc_ens_score_kernel: grid.y cuts W = B c_out into column tiles of at most 256;
-// inside a tile of wt columns thread t owns column t % wt of node lane t / wt, q = 256 / wt lanes; block x walks the
-// contiguous node range [x per, (x + 1) per) in steps of q; grid.z is the offset.  The M + 1 values of the point and of its
+// The variogram pass, on the 256-wide cut of gc_colsum.h; grid.z is the offset.  The M + 1 values of the point and of its
 // partner are read from HBM, each load coalesced across the wave.
 // Out, as plain stores: part[block x][offset][4][W] (double), cpart[block x][offset][W] (valid pairs).
 template <int PK>
@@ -251,19 +237,14 @@ __global__ __launch_bounds__(256) void gc_ens_variogram_kernel(const float* __re
   const int G = n_lat * n_lon;
   const int o = blockIdx.z, O = gridDim.z;
   const int di = offs[2 * o], dj = offs[2 * o + 1];
-  const int col0 = blockIdx.y * 256;
-  const int wt = min(256, W - col0);
-  const int q = 256 / wt;
-  const int tid = threadIdx.x;
-  const int lane = tid / wt;
-  const int cl = tid - lane * wt;
-  const int col = col0 + cl;
+  const ColTile ct(256, 256, W, blockIdx.y);
+  const int tid = threadIdx.x, col = ct.col;
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   unsigned cnt = 0;
-  if (lane < q) {
+  if (ct.active()) {
     const double dM = (double)M;
-    const int n_end = min(G, (int)(blockIdx.x + 1) * per);
-    for (int n = blockIdx.x * per + lane; n < n_end; n += q) {
+    const int n_end = ct.n_end(G, per);
+    for (int n = ct.n_begin(per); n < n_end; n += ct.q) {
       const int i = n / n_lon, j = n - i * n_lon;
       const int i2 = i + di;
       if (i2 < 0 || i2 >= n_lat) continue;
@@ -291,50 +272,34 @@ __global__ __launch_bounds__(256) void gc_ens_variogram_kernel(const float* __re
       ++cnt;
     }
   }
-  // the q lanes of a column, added in lane order
   const size_t row = (size_t)blockIdx.x * O + o;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    lane_sum[tid] = s[k];
-    __syncthreads();
-    if (tid < wt) {
-      double t = lane_sum[tid];
-      for (int l = 1; l < q; ++l) t += lane_sum[l * wt + tid];
-      part[(row * 4 + k) * W + col] = t;
-    }
-    __syncthreads();
+    const double t = col_total(lane_sum, s[k], ct);
+    if (tid < ct.wt) part[(row * 4 + k) * W + col] = t;
   }
-  lane_cnt[tid] = cnt;
-  __syncthreads();
-  if (tid < wt) {
-    unsigned t = lane_cnt[tid];
-    for (int l = 1; l < q; ++l) t += lane_cnt[l * wt + tid];
-    cpart[row * W + col] = t;
-  }
+  const unsigned t = col_total(lane_cnt, cnt, ct);
+  if (tid < ct.wt) cpart[row * W + col] = t;
 }
 
-// One thread per result: the blocks of a sum are added in ascending block order.  e < 4 W O: sum k of column col at offset
-// o -> out [4][W][O]; then W O counts -> outc [W][O].
-__global__ __launch_bounds__(256) void gc_ens_variogram_finish_kernel(const double* __restrict__ part,
-                                                                       const unsigned* __restrict__ cpart, int blocks, int W,
-                                                                       int O, double* __restrict__ out,
-                                                                       unsigned long long* __restrict__ outc) {
-  const int nd = 4 * W * O;
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e < nd) {
+// The ascending block finish: e < 4 W O: sum k of column col at offset o, e = (k O + o) W + col -> out [4][W][O]; then W O
+// counts, as the partials lie -> outc [W][O].
+struct VariogramFinishMap {
+  const double* part;
+  const unsigned* cpart;
+  int W, O;
+  SkippedSum skipped;
+  __host__ __device__ int sums() const { return 4 * W * O; }
+  __host__ __device__ int counts() const { return W * O; }
+  __device__ BlockSum<double> sum(int e) const {
     const int k = e / (W * O), r = e - k * W * O, o = r / W, col = r - o * W;
-    double t = 0.0;
-#pragma unroll 8
-    for (int x = 0; x < blocks; ++x) t += part[(((size_t)x * O + o) * 4 + k) * W + col];
-    out[((size_t)k * W + col) * O + o] = t;
-  } else if (e < nd + W * O) {
-    const int r = e - nd, o = r / W, col = r - o * W;
-    unsigned long long t = 0ull;
-#pragma unroll 8
-    for (int x = 0; x < blocks; ++x) t += cpart[((size_t)x * O + o) * W + col];
-    outc[(size_t)col * O + o] = t;
+    return {part + ((size_t)o * 4 + k) * W + col, (size_t)sums(), ((size_t)k * W + col) * O + o};
   }
-}
+  __device__ BlockSum<unsigned> count(int r) const {
+    const int o = r / W, col = r - o * W;
+    return {cpart + r, (size_t)counts(), (size_t)col * O + o};
+  }
+};
 
 static hipError_t launch_ens_variogram(hipStream_t s, int pk, const float* mem, size_t field, int M, const float* truth,
                                        const float* node_w, const int* offs, int O, int n_lat, int n_lon, int B, int c_out,
@@ -359,10 +324,7 @@ static hipError_t launch_ens_variogram(hipStream_t s, int pk, const float* mem, 
 
 static hipError_t launch_ens_variogram_finish(hipStream_t s, const double* part, const unsigned* cpart, int blocks, int W, int O,
                                               double* out, unsigned long long* outc) {
-  const int total = 5 * W * O;
-  hipLaunchKernelGGL(gc_ens_variogram_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, part, cpart, blocks, W, O, out,
-                     outc);
-  return hipGetLastError();
+  return launch_block_finish(s, VariogramFinishMap{part, cpart, W, O, {}}, blocks, out, outc);
 }
 
 }  // namespace gc

@@ -13,6 +13,7 @@
 //   pinball[q] = sum w u (p_q - [u < 0]), u = y - Q_q          counts[q] = #{y < Q_q}, counts[Q] = counted points
 // No atomics on floats: every accumulator has one writer and every sum a fixed order (a thread's nodes ascending, the
 // node lanes of a column in lane order, the blocks in index order), so the same call twice returns identical bytes.
+#include "gc_colsum.h"
 #include "gc_sort.h"
 #include "gc_store.h"
 
@@ -39,11 +40,11 @@ static size_t ord_thread_bytes(int M, int Q) { return (size_t)ord_nacc(M, Q) * s
 static int ord_cap(int M, int Q) { return (int)std::min<size_t>(256, kOrdLds / ord_thread_bytes(M, Q)); }
 static int ord_tiles(int W, int cap) { return (W + cap - 1) / cap; }
 static int ord_tile_width(int W, int cap) { const int t = ord_tiles(W, cap); return (W + t - 1) / t; }
-// node-range blocks: 8 nodes per thread or more, at most two rounds of the workgroups the LDS lets a CU hold
+// node-range blocks: at most 1024 and two rounds of the workgroups the LDS lets a CU hold
 static int ord_blocks(int G, int W, int M, int Q) {
   const int cap = ord_cap(M, Q), q = cap / ord_tile_width(W, cap);
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / ((size_t)cap * ord_thread_bytes(M, Q))));
-  return std::max(1, std::min({(G + 8 * q - 1) / (8 * q), 1024, 2 * kOrdCuCount * per_cu}));
+  return node_blocks(G, q, std::min(1024, 2 * kOrdCuCount * per_cu));
 }
 
 // v[idx] for a wave-uniform idx in [0, P): a tree of selects on the bits of idx, lowest first, over compile-time
@@ -65,11 +66,9 @@ __device__ inline float ord_pick(const float (&v)[P], int idx) {
   return t[0];
 }
 
-// The pass.  Thread layout of gc_ens_score_kernel, on column tiles of tile_w <= cap columns: inside a tile of wt columns
-// thread t < q wt owns column t % wt of node lane t / wt, q = cap / wt lanes; block x walks the contiguous node range
-// [x per, (x + 1) per) in steps of q.  The M values of a point are read once from HBM (M loads of stride `field`, each
-// coalesced across the wave) into P registers, padded with +inf, and sorted there.  SCORE = false: the quantile fields
-// only -- no truth, no weights, no LDS.
+// The pass, on equal-width column tiles of tile_w <= cap columns (gc_colsum.h; cap < 256 where the LDS holds fewer
+// accumulator sets).  The M values of a point are read once from HBM into P padded registers (load_padded) and sorted
+// there.  SCORE = false: the quantile fields only -- no truth, no weights, no LDS.
 // Dynamic LDS (SCORE): double acc[nacc][cap], then unsigned cnt[Q + 1][cap]; accumulator j of thread t at [j][t], so the
 // threads of a wave touch consecutive words.
 // Out, as plain stores: qf [Q][field]; part[block x][nacc][W] (double), cpart[block x][Q + 1][W], ipart[block x][tile].
@@ -86,13 +85,9 @@ __global__ __launch_bounds__(256) void gc_ens_order_kernel(const float* __restri
   const int nacc = 2 * (M + 1) + 3 + Q;
   double* const acc = reinterpret_cast<double*>(ord_lds);
   unsigned* const cnt = reinterpret_cast<unsigned*>(acc + (size_t)nacc * cap);
-  const int col0 = blockIdx.y * tile_w;
-  const int wt = min(tile_w, W - col0);
-  const int q = cap / wt;
+  const ColTile ct(tile_w, cap, W, blockIdx.y);
+  const int col0 = ct.col0, wt = ct.wt, q = ct.q;
   const int tid = threadIdx.x;
-  const int lane = tid / wt;
-  const int cl = tid - lane * wt;
-  const int col = col0 + cl;
   if constexpr (SCORE) {
     for (int i = tid; i < nacc * cap; i += 256) acc[i] = 0.0;
     for (int i = tid; i < (Q + 1) * cap; i += 256) cnt[i] = 0u;
@@ -100,22 +95,14 @@ __global__ __launch_bounds__(256) void gc_ens_order_kernel(const float* __restri
     __syncthreads();
   }
   unsigned inv = 0;
-  if (lane < q) {
+  if (ct.active()) {
     double* const my = acc + tid;                  // accumulator j at my[j * cap]
     unsigned* const myc = cnt + tid;
-    const int n_end = min(G, (int)(blockIdx.x + 1) * per);
-    for (int n = blockIdx.x * per + lane; n < n_end; n += q) {
-      const size_t i = (size_t)n * W + col;
+    const int n_end = ct.n_end(G, per);
+    for (int n = ct.n_begin(per); n < n_end; n += q) {
+      const size_t i = (size_t)n * W + ct.col;
       float v[P];
-      bool xfin = true;
-#pragma unroll
-      for (int k = 0; k < P; ++k) {
-        v[k] = __builtin_inff();
-        if (k < M) {
-          v[k] = mem[(size_t)k * field + i];
-          xfin = xfin && isfinite(v[k]);
-        }
-      }
+      const bool xfin = load_padded<P>(v, mem, field, i, M);
       float qv[kOrdMaxQuantiles];
       if (xfin) {                                  // the network never sees a NaN
         ord_sort<P>(v);
@@ -171,57 +158,43 @@ __global__ __launch_bounds__(256) void gc_ens_order_kernel(const float* __restri
   if constexpr (SCORE) {
     if (inv) atomicAdd(&skipped, inv);
     __syncthreads();
-    // the q lanes of a column, added in lane order
+    // the lane fold, in place on the accumulator rows
     for (int e = tid; e < nacc * wt; e += 256) {
       const int j = e / wt, c = e - j * wt;
-      double t = acc[(size_t)j * cap + c];
-      for (int l = 1; l < q; ++l) t += acc[(size_t)j * cap + l * wt + c];
-      part[((size_t)blockIdx.x * nacc + j) * W + col0 + c] = t;
+      part[((size_t)blockIdx.x * nacc + j) * W + col0 + c] = lane_fold(acc + (size_t)j * cap, c, wt, q);
     }
     for (int e = tid; e < (Q + 1) * wt; e += 256) {
       const int j = e / wt, c = e - j * wt;
-      unsigned t = cnt[(size_t)j * cap + c];
-      for (int l = 1; l < q; ++l) t += cnt[(size_t)j * cap + l * wt + c];
-      cpart[((size_t)blockIdx.x * (Q + 1) + j) * W + col0 + c] = t;
+      cpart[((size_t)blockIdx.x * (Q + 1) + j) * W + col0 + c] = lane_fold(cnt + (size_t)j * cap, c, wt, q);
     }
     if (tid == 0) ipart[(size_t)blockIdx.x * gridDim.y + blockIdx.y] = skipped;
   }
 }
 
-// One thread per sum: the blocks of an accumulator are added in ascending block order.  e < nacc W: double sum j = e / W
-// of column e % W, stored where the result arrays want it -- out = bins [W][M + 1][2], extra [W][3], pinball [W][Q];
-// then (Q + 1) W counts -> outc [W][Q + 1]; then one thread for the skipped points -> outc[W (Q + 1)].
-__global__ __launch_bounds__(256) void gc_ens_order_finish_kernel(const double* __restrict__ part,
-                                                                   const unsigned* __restrict__ cpart,
-                                                                   const unsigned* __restrict__ ipart, int blocks, int tiles,
-                                                                   int W, int M, int Q, double* __restrict__ out,
-                                                                   unsigned long long* __restrict__ outc) {
-  const int nacc = 2 * (M + 1) + 3 + Q;
-  const int nd = nacc * W, nc = (Q + 1) * W;
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e < nd) {
+// The ascending block finish: e < nacc W: double sum j = e / W of column e % W, as the partials lie, stored where the
+// result arrays want it -- out = bins [W][M + 1][2], extra [W][3], pinball [W][Q]; then (Q + 1) W counts -> outc
+// [W][Q + 1]; the skipped points -> outc[W (Q + 1)].
+struct OrdFinishMap {
+  const double* part;
+  const unsigned* cpart;
+  int W, M, Q;
+  SkippedSum skipped;
+  __host__ __device__ int sums() const { return (2 * (M + 1) + 3 + Q) * W; }
+  __host__ __device__ int counts() const { return (Q + 1) * W; }
+  __device__ BlockSum<double> sum(int e) const {
     const int j = e / W, col = e - j * W;
-    double t = 0.0;
-#pragma unroll 8
-    for (int b = 0; b < blocks; ++b) t += part[((size_t)b * nacc + j) * W + col];
     const int nb = 2 * (M + 1);
     size_t at;
     if (j < nb) at = (size_t)col * nb + j;
     else if (j < nb + 3) at = (size_t)W * nb + (size_t)col * 3 + (j - nb);
     else at = (size_t)W * (nb + 3) + (size_t)col * Q + (j - nb - 3);
-    out[at] = t;
-  } else if (e < nd + nc) {
-    const int r = e - nd, j = r / W, col = r - j * W;
-    unsigned long long t = 0ull;
-#pragma unroll 8
-    for (int b = 0; b < blocks; ++b) t += cpart[((size_t)b * (Q + 1) + j) * W + col];
-    outc[(size_t)col * (Q + 1) + j] = t;
-  } else if (e == nd + nc) {
-    unsigned long long t = 0ull;
-    for (int i = 0; i < blocks * tiles; ++i) t += ipart[i];
-    outc[(size_t)W * (Q + 1)] = t;
+    return {part + e, (size_t)sums(), at};
   }
-}
+  __device__ BlockSum<unsigned> count(int e) const {
+    const int j = e / W, col = e - j * W;
+    return {cpart + e, (size_t)counts(), (size_t)col * (Q + 1) + j};
+  }
+};
 
 template <int P, bool SCORE>
 static hipError_t ord_launch(hipStream_t s, dim3 grid, size_t lds, const float* mem, size_t field, int M, const float* truth,
@@ -248,26 +221,18 @@ static hipError_t launch_ens_order(hipStream_t s, bool score, const float* mem, 
   const int per = (G + blocks - 1) / blocks;
   const size_t lds = score ? (size_t)cap * ord_thread_bytes(M, Q) : 0;
   const dim3 grid(blocks, tiles);
-#define GC_ORD_CASE(P)                                                                                                          \
-  return score ? ord_launch<P, true>(s, grid, lds, mem, field, M, truth, node_w, G, W, per, cap, tile_w, plan, qf, part, cpart, \
-                                     ipart)                                                                                     \
-               : ord_launch<P, false>(s, grid, lds, mem, field, M, truth, node_w, G, W, per, cap, tile_w, plan, qf, part, cpart, \
-                                      ipart)
-  if (M <= 2) { GC_ORD_CASE(2); }
-  if (M <= 4) { GC_ORD_CASE(4); }
-  if (M <= 8) { GC_ORD_CASE(8); }
-  if (M <= 16) { GC_ORD_CASE(16); }
-  if (M <= 32) { GC_ORD_CASE(32); }
-  GC_ORD_CASE(64);
-#undef GC_ORD_CASE
+  return pad_dispatch(M, [&](auto p) {
+    constexpr int P = decltype(p)::value;
+    return score ? ord_launch<P, true>(s, grid, lds, mem, field, M, truth, node_w, G, W, per, cap, tile_w, plan, qf, part, cpart,
+                                       ipart)
+                 : ord_launch<P, false>(s, grid, lds, mem, field, M, truth, node_w, G, W, per, cap, tile_w, plan, qf, part, cpart,
+                                        ipart);
+  });
 }
 
 static hipError_t launch_ens_order_finish(hipStream_t s, const double* part, const unsigned* cpart, const unsigned* ipart,
                                           int blocks, int tiles, int W, int M, int Q, double* out, unsigned long long* outc) {
-  const int total = (ord_nacc(M, Q) + Q + 1) * W + 1;
-  hipLaunchKernelGGL(gc_ens_order_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, part, cpart, ipart, blocks, tiles, W,
-                     M, Q, out, outc);
-  return hipGetLastError();
+  return launch_block_finish(s, OrdFinishMap{part, cpart, W, M, Q, {ipart, tiles, (size_t)W * (Q + 1)}}, blocks, out, outc);
 }
 
 }  // namespace gc

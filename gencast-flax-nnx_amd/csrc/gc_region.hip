@@ -24,6 +24,7 @@
 // rank counts are integers; their LDS atomics commute.
 #include <map>
 
+#include "gc_colsum.h"
 #include "gc_store.h"
 
 // the per-point arithmetic is the definition above, operation for operation: no fused multiply-adds
@@ -34,11 +35,10 @@ namespace gc {
 constexpr int kRegionMax = 32, kRegionMaxAtoms = 256;
 constexpr int kRegionMaxBlocks = kLossMaxBlocks + kRegionMaxAtoms;   // base + one ragged block per atom at the most
 
-// The geometry of gc_ens_score_kernel: grid.y cuts W = B c_out into column tiles of at most 256; inside a tile of wt
-// columns thread t owns column t % wt (ONE accumulator set) of node lane t / wt, q = 256 / wt lanes.  Block x walks
-// order[begin, end) of its table entry blk[2 x], blk[2 x + 1] in steps of q instead of a contiguous node range.
-// Dynamic LDS: float[M][256] (a point's members, a bank of its own for every lane), then unsigned[wt][M + 1] rank counts.
-// Out, as plain stores: part[block x][6][W] (double), hpart[block x][W][M + 1], ipart[block x][tile] (points skipped).
+// The scoring pass, on the 256-wide cut of gc_colsum.h, but block x walks order[begin, end) of its table entry blk[2 x],
+// blk[2 x + 1] in steps of q instead of a contiguous node range.  Dynamic LDS:
+// ens_score_lds (nothing scales with R).  Out, as plain stores: part[block x][6][W] (double), hpart[block x][W][M + 1],
+// ipart[block x][tile] (points skipped).
 __global__ __launch_bounds__(256) void gc_ens_region_kernel(const float* __restrict__ mem, size_t field, int M,
                                                              const float* __restrict__ truth,
                                                              const float* __restrict__ node_w,
@@ -50,26 +50,21 @@ __global__ __launch_bounds__(256) void gc_ens_region_kernel(const float* __restr
   __shared__ unsigned skipped;
   float* const tile = reinterpret_cast<float*>(reg_lds);
   unsigned* const hist = reinterpret_cast<unsigned*>(tile + (size_t)M * 256);
-  const int col0 = blockIdx.y * 256;
-  const int wt = min(256, W - col0);
-  const int q = 256 / wt;
+  const ColTile ct(256, 256, W, blockIdx.y);
   const int tid = threadIdx.x;
-  const int lane = tid / wt;
-  const int cl = tid - lane * wt;
-  const int col = col0 + cl;
   const int bins = M + 1;
-  for (int i = tid; i < wt * bins; i += 256) hist[i] = 0u;
+  for (int i = tid; i < ct.wt * bins; i += 256) hist[i] = 0u;
   if (tid == 0) skipped = 0u;
   __syncthreads();
   double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   unsigned inv = 0;
-  if (lane < q) {
+  if (ct.active()) {
     float* const my = tile + tid;                  // x_k at my[k * 256]
     const double dM = (double)M, pairs = 0.5 * dM * (dM - 1.0);
     const int p_end = blk[2 * blockIdx.x + 1];
-    for (int p = blk[2 * blockIdx.x] + lane; p < p_end; p += q) {
+    for (int p = blk[2 * blockIdx.x] + ct.lane; p < p_end; p += ct.q) {
       const int n = order[p];
-      const size_t i = (size_t)n * W + col;
+      const size_t i = (size_t)n * W + ct.col;
       const float y = truth[i];
       bool xfin = true;
       double sum = 0.0;
@@ -113,31 +108,23 @@ __global__ __launch_bounds__(256) void gc_ens_region_kernel(const float* __restr
       s[3] += w * s2;
       s[4] += w * (ae / dM);
       s[5] += w * ((d0 + d1) / pairs);
-      atomicAdd(&hist[cl * bins + r], 1u);
+      atomicAdd(&hist[ct.cl * bins + r], 1u);
     }
   }
   if (inv) atomicAdd(&skipped, inv);
-  // the q lanes of a column, added in lane order
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
-    lane_sum[tid] = s[k];
-    __syncthreads();
-    if (tid < wt) {
-      double t = lane_sum[tid];
-      for (int l = 1; l < q; ++l) t += lane_sum[l * wt + tid];
-      part[((size_t)blockIdx.x * 6 + k) * W + col] = t;
-    }
-    __syncthreads();
+    const double t = col_total(lane_sum, s[k], ct);
+    if (tid < ct.wt) part[((size_t)blockIdx.x * 6 + k) * W + ct.col] = t;
   }
-  unsigned* const hp = hpart + ((size_t)blockIdx.x * W + col0) * bins;
-  for (int i = tid; i < wt * bins; i += 256) hp[i] = hist[i];
+  unsigned* const hp = hpart + ((size_t)blockIdx.x * W + ct.col0) * bins;
+  for (int i = tid; i < ct.wt * bins; i += 256) hp[i] = hist[i];
   if (tid == 0) ipart[(size_t)blockIdx.x * gridDim.y + blockIdx.y] = skipped;
 }
 
 // One workgroup per (column tile, region r).  The blocks whose atom bits[b] has bit r are listed in LDS in ascending order
-// (blocks <= kRegionMaxBlocks) and then added the way gc_ens_finish_kernel adds all blocks: thread t owns column t % wt and
-// the contiguous range of the list of lane t / wt, the lanes are combined in lane order -- a fixed order, ascending in the
-// block index.  sums [R][6][W]; hist [R][W][M + 1], then [R] words: the points of each region the call skipped.
+// (blocks <= kRegionMaxBlocks); the six sums of a column are the lane-split block sum (gc_colsum.h) over that list.
+// sums [R][6][W]; hist [R][W][M + 1], then [R] words: the points of each region the call skipped.
 __global__ __launch_bounds__(256) void gc_ens_region_finish_kernel(const double* __restrict__ part,
                                                                     const unsigned* __restrict__ hpart,
                                                                     const unsigned* __restrict__ ipart,
@@ -150,12 +137,9 @@ __global__ __launch_bounds__(256) void gc_ens_region_finish_kernel(const double*
   __shared__ int sel_at[257];
   const int r = blockIdx.y, R = gridDim.y, tiles = gridDim.x;
   const unsigned bit = 1u << r;
-  const int col0 = blockIdx.x * 256;
-  const int wt = min(256, W - col0);
-  const int q = 256 / wt;
+  const ColTile ct(256, 256, W, blockIdx.x);
+  const int col0 = ct.col0, wt = ct.wt, col = ct.col;
   const int tid = threadIdx.x;
-  const int lane = tid / wt;
-  const int col = col0 + (tid - lane * wt);
   const int bins = M + 1;
   // The list first, so that the sums below are loops of independent loads: thread t looks at the contiguous blocks
   // [t chunk, (t + 1) chunk), the counts are added up in thread order, and every thread writes its own at its offset.
@@ -176,22 +160,9 @@ __global__ __launch_bounds__(256) void gc_ens_region_finish_kernel(const double*
     if (bits[b] & bit) sel[at++] = b;
   __syncthreads();
   const int n_sel = sel_at[256];
-  const int bper = (n_sel + q - 1) / q;
   for (int k = 0; k < 6; ++k) {
-    double t = 0.0;
-    if (lane < q) {
-      const int i_end = min(n_sel, (lane + 1) * bper);
-#pragma unroll 8
-      for (int i = lane * bper; i < i_end; ++i) t += part[((size_t)sel[i] * 6 + k) * W + col];
-    }
-    lane_sum[tid] = t;
-    __syncthreads();
-    if (tid < wt) {
-      double tot = lane_sum[tid];
-      for (int l = 1; l < q; ++l) tot += lane_sum[l * wt + tid];
-      sums[((size_t)r * 6 + k) * W + col] = tot;
-    }
-    __syncthreads();
+    const double tot = lane_split_block_sum(lane_sum, ct, part + (size_t)k * W + col, (size_t)6 * W, n_sel, ListedBlocks{sel});
+    if (tid < wt) sums[((size_t)r * 6 + k) * W + col] = tot;
   }
   for (int e = tid; e < wt * bins; e += 256) {
     unsigned long long t = 0ull;
@@ -208,13 +179,10 @@ __global__ __launch_bounds__(256) void gc_ens_region_finish_kernel(const double*
   }
 }
 
-// what ens_score_lds gives (gc_ensemble.hip): nothing here scales with R
-static size_t region_lds(int M, int W) { return (size_t)M * 256 * sizeof(float) + (size_t)std::min(256, W) * (M + 1) * sizeof(unsigned); }
-
 static hipError_t launch_ens_region(hipStream_t s, const float* mem, size_t field, int M, const float* truth, const float* node_w,
                                     const int* order, const int* blk, int blocks, int W, double* part, unsigned* hpart,
                                     unsigned* ipart) {
-  const size_t lds = region_lds(M, W);
+  const size_t lds = ens_score_lds(M, W);
   if (lds > 64 * 1024) {                           // (a per-device property of the kernel; setting it again is harmless)
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gc_ens_region_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

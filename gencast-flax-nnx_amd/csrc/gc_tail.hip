@@ -23,6 +23,7 @@
 // All of these are raw and additive over batches and dates.
 // No atomics on floats: every accumulator has one writer and every sum a fixed order (a thread's nodes ascending, the
 // node lanes of a column in lane order, the blocks in index order), so the same call twice returns identical bytes.
+#include "gc_colsum.h"
 #include "gc_sort.h"
 #include "gc_store.h"
 
@@ -34,18 +35,15 @@ namespace gc {
 constexpr int kTailMaxThresholds = 8;
 
 // column tiles of equal width, at most 256 columns each: a thread keeps its accumulators in registers, so every thread
-// of a workgroup may own a column (the `cap` of gc_order.hip is the workgroup size here)
+// of a workgroup may own a column (cap = 256)
 static int tail_tiles(int W) { return (W + 255) / 256; }
 static int tail_tile_width(int W) { const int t = tail_tiles(W); return (W + t - 1) / t; }
-// node-range blocks as ord_blocks: 8 nodes per thread or more, at most 1024.  (ord_blocks's third bound, two rounds of the
-// workgroups a CU holds, is 1024 or more here: the widest instance leaves room for two workgroups per CU.)
-static int tail_blocks(int G, int W) {
-  const int q = 256 / tail_tile_width(W);
-  return std::max(1, std::min((G + 8 * q - 1) / (8 * q), 1024));
-}
+// node-range blocks: at most 1024.  (Two rounds of the workgroups a CU holds would be 1024 or more: the widest instance
+// leaves room for two workgroups per CU.)
+static int tail_blocks(int G, int W) { return node_blocks(G, 256 / tail_tile_width(W), 1024); }
 
-// The pass.  Thread layout of gc_ens_order_kernel on column tiles of tile_w <= 256 columns: inside a tile of wt columns
-// thread t < q wt owns column t % wt of node lane t / wt, q = 256 / wt lanes; block x walks the contiguous node range
+// The pass.  The thread layout of gc_colsum.h, written out (this kernel keeps its own text: it timed slower on the shared
+// pieces), on column tiles of tile_w <= 256 columns: inside a tile of wt columns thread t < q wt owns column t % wt of node lane t / wt, q = 256 / wt lanes; block x walks the contiguous node range
 // [x per, (x + 1) per) in steps of q.  The M values of a point are read once from HBM (M loads of stride `field`, each
 // coalesced across the wave) into P registers, padded with +inf, and sorted there once; every threshold then costs one
 // more coalesced load and O(M) double operations.  Bit t of dir_up: threshold t is the upper tail.
@@ -147,7 +145,8 @@ __global__ __launch_bounds__(256) void gc_ens_tail_kernel(const float* __restric
   }
 }
 
-// One thread per result: the blocks of a sum are added in ascending block order.  e < 4 T W: sum j of column col of
+// One thread per result: the blocks of a sum are added in ascending block order (own text, as the pass: the shared finish
+// of gc_colsum.h timed slower here).  e < 4 T W: sum j of column col of
 // threshold t, e = (t 4 + j) W + col as the partials lie, stored at out [T][W][4]; then T W counts -> outc [T][W].
 __global__ __launch_bounds__(256) void gc_ens_tail_finish_kernel(const double* __restrict__ part,
                                                                   const unsigned* __restrict__ cpart, int blocks, int T,
@@ -170,30 +169,17 @@ __global__ __launch_bounds__(256) void gc_ens_tail_finish_kernel(const double* _
   }
 }
 
-template <int P>
-static hipError_t tail_launch(hipStream_t s, dim3 grid, const float* mem, size_t field, int M, const float* truth,
-                              const float* node_w, const float* thr, int T, unsigned dir_up, int G, int W, int per, int tile_w,
-                              double* part, unsigned* cpart) {
-  hipLaunchKernelGGL((gc_ens_tail_kernel<P>), grid, dim3(256), 0, s, mem, field, M, truth, node_w, thr, T, dir_up, G, W, per,
-                     tile_w, part, cpart);
-  return hipGetLastError();
-}
-
 static hipError_t launch_ens_tail(hipStream_t s, const float* mem, size_t field, int M, const float* truth,
                                   const float* node_w, const float* thr, int T, unsigned dir_up, int G, int W, double* part,
                                   unsigned* cpart) {
   const int blocks = tail_blocks(G, W), tile_w = tail_tile_width(W);
   const int per = (G + blocks - 1) / blocks;
   const dim3 grid(blocks, tail_tiles(W));
-#define GC_TAIL_CASE(P) \
-  return tail_launch<P>(s, grid, mem, field, M, truth, node_w, thr, T, dir_up, G, W, per, tile_w, part, cpart)
-  if (M <= 2) { GC_TAIL_CASE(2); }
-  if (M <= 4) { GC_TAIL_CASE(4); }
-  if (M <= 8) { GC_TAIL_CASE(8); }
-  if (M <= 16) { GC_TAIL_CASE(16); }
-  if (M <= 32) { GC_TAIL_CASE(32); }
-  GC_TAIL_CASE(64);
-#undef GC_TAIL_CASE
+  return pad_dispatch(M, [&](auto p) {
+    hipLaunchKernelGGL((gc_ens_tail_kernel<decltype(p)::value>), grid, dim3(256), 0, s, mem, field, M, truth, node_w, thr, T,
+                       dir_up, G, W, per, tile_w, part, cpart);
+    return hipGetLastError();
+  });
 }
 
 static hipError_t launch_ens_tail_finish(hipStream_t s, const double* part, const unsigned* cpart, int blocks, int T, int W,

@@ -106,6 +106,23 @@ def test_more_columns_than_one_tile(M, K):
     cl.close()
 
 
+def test_a_second_column_tile_of_one_column():
+  """(B, C) = (1, 257): the second column tile is one column wide, 256 node lanes for the 8 nodes of a block."""
+  gr = _graph()
+  G, B, C, M, K = gr.num_grid_nodes, 1, 257, 3, 3
+  members, clim, truth, w = _data(M, K, G, B, C, seed=257)
+  members[1, 17, 0, 256] = np.nan                          # an invalid point in the one-column tile
+  ref = R.reference(members, clim, truth, w)
+  nd, cl = _handle(gr, B, C), _handle(gr, B, C)
+  try:
+    _push_all(nd, members, w)
+    _push_all(cl, clim)
+    _check("W=257", nd.ens_clim_score(cl, truth), ref, G)
+  finally:
+    nd.close()
+    cl.close()
+
+
 def test_a_width_that_is_no_multiple_of_the_wave_size():
   gr = _graph()
   G, B, C, M, K = gr.num_grid_nodes, 1, 37, 5, 3           # 6 lanes of 37 columns: lanes straddle the waves, 34 idle threads

@@ -9,7 +9,7 @@ included.  The per-term values of the sums are then bit-equal and only the order
 Sizes, as in tests/test_gpu_derive.py: the 13 x 24 grid (G = 312) and the 11 x 15 grid (G = 165, odd everything), handles with
 set_graph only.  (B, C) = (2, 6): one partial row tile of 16 columns; (1, 82): three row tiles of 32, a chunk of 96 columns
 with 64 idle threads in the column pass; (4, 82): W = 328, two chunks of columns, the second partial; (1, 7) on the odd grid:
-a tile of 8.  S = 4 scales pair r_lat in {0, 1, 3, 12} (12 covers the whole column) with r_lon all 0, all 2, a 2500 km window
+a tile of 8; (1, 257): a second chunk with one live column.  S = 4 scales pair r_lat in {0, 1, 3, 12} (12 covers the whole column) with r_lon all 0, all 2, a 2500 km window
 (capped at the poles) and all (n_lon - 1) // 2; at 15 longitudes that is the whole row."""
 import functools
 
@@ -26,7 +26,7 @@ from tests.helpers import graph_handle as _handle
 pytestmark = pytest.mark.gpu
 
 GRIDS = {"even": (13, 24), "odd": (11, 15)}
-SHAPES = [("even", 2, 6, 9), ("even", 1, 82, 2), ("even", 4, 82, 2), ("odd", 1, 7, 2)]      # grid, B, C, M
+SHAPES = [("even", 2, 6, 9), ("even", 1, 82, 2), ("even", 4, 82, 2), ("odd", 1, 7, 2), ("even", 1, 257, 3)]   # grid, B, C, M
 R_LATS = np.array([0, 1, 3, 12], np.int32)
 
 

@@ -222,6 +222,21 @@ def test_variogram_more_columns_than_one_tile():
     nd.close()
 
 
+def test_variogram_a_second_column_tile_of_one_column():
+  """(B, C) = (1, 257): the second column tile is one column wide, 256 node lanes for the 8 nodes of a block."""
+  gr = _graph()
+  G, B, C, M = gr.num_grid_nodes, 1, 257, 3
+  members, truth, w = _data(M, G, B, C, seed=257)
+  ref = R.variogram(members, truth, w, N_LAT, N_LON, OFFSETS, 1.0)
+  nd = _handle(gr, B, C)
+  try:
+    _push_all(nd, members, w)
+    nd.ens_variogram_set(N_LAT, N_LON, OFFSETS, 1.0)
+    _check_variogram("W=257", nd.ens_variogram_score(truth), ref, G, M)
+  finally:
+    nd.close()
+
+
 def test_variogram_wraps_in_longitude_and_clips_in_latitude():
   """The truth is 1 in row 0 and in column 0 and 0 elsewhere, the members are 0: vx = 0 and vy = 1 exactly where one end of a
   pair lies on the cross, so V3 counts those pairs with their weights -- w = (row + 1) / 8 is dyadic and every expected

@@ -123,6 +123,22 @@ def test_more_columns_than_one_tile(M):
     nd.close()
 
 
+def test_two_equal_width_tiles_of_one_lane():
+  """(B, C) = (1, 257): two column tiles of 129 and 128 columns, one node lane in the first and two in the second."""
+  gr = _graph()
+  G, B, C, M = gr.num_grid_nodes, 1, 257, 3
+  members, truth, w = _data(M, G, B, C, seed=257)
+  ref = R.reference(members, truth, w, PROBS)
+  nd = _handle(gr, B, C)
+  try:
+    _push_all(nd, members, w)
+    nd.ens_order_set(PROBS)
+    _check("W=257", nd.ens_order_score(truth), ref, G)
+    _check_fields("W=257", nd, ref)
+  finally:
+    nd.close()
+
+
 # ---- 3. ties and invalid points ---------------------------------------------------------------------------------------------
 def test_ties_and_invalid_points():
   gr = _graph()

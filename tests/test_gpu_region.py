@@ -134,6 +134,27 @@ def test_every_region_matches_the_float64_reference_on_its_nodes(M, B, C):
     nd.close()
 
 
+def test_a_second_column_tile_of_one_column():
+  """(B, C) = (1, 257): the second column tile is one column wide -- 256 node lanes in the pass, and in the finish 256
+  lanes for the few blocks of a region.  `_data` needs B >= 2, so the data here are plain but for the NaN truth rows."""
+  gr = _graph()
+  G, B, C, M = gr.num_grid_nodes, 1, 257, 3
+  rng = np.random.default_rng(257)
+  scale = np.logspace(-3, 5, C)
+  members = (rng.standard_normal((M, G, B, C)) * scale).astype(np.float32)
+  truth = (rng.standard_normal((G, B, C)) * scale).astype(np.float32)
+  truth[NAN_TRUTH] = np.nan
+  w = (np.arange(G) % 7 + 1).astype(np.float32) / 8.0
+  bits, n_regions = _regions(B * C)
+  nd = _handle(gr, B, C)
+  try:
+    _push_all(nd, members, w)
+    nd.ens_region_set(bits, n_regions)
+    _check("W=257 M=3", nd.ens_region_score(truth), R.reference(members, truth, w, bits, n_regions), G, M)
+  finally:
+    nd.close()
+
+
 # ---- 2. R = 1, all nodes: gc_ens_score ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M", [3, 50])
 def test_one_region_of_all_nodes_is_ens_score(M):

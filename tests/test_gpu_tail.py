@@ -173,6 +173,28 @@ def test_more_columns_than_one_tile(M, T):
     nd.close()
 
 
+def test_two_equal_width_tiles_of_one_lane():
+  """(B, C) = (1, 257): two column tiles of 129 and 128 columns, one node lane in the first and two in the second.  `_data`
+  needs B >= 2, so the data here are plain: no special points but the NaN truth rows."""
+  gr = _graph()
+  G, B, C, M, T = gr.num_grid_nodes, 1, 257, 3, 2
+  rng = np.random.default_rng(257)
+  scale = np.logspace(-3, 5, C)
+  members = (rng.standard_normal((M, G, B, C)) * scale).astype(np.float32)
+  truth = (rng.standard_normal((G, B, C)) * scale).astype(np.float32)
+  truth[NAN_TRUTH] = np.nan
+  thr = (rng.standard_normal((T, G, B, C)) * 0.5 * scale).astype(np.float32)
+  w = rng.uniform(0.1, 2.0, G).astype(np.float32)
+  dirs = _directions(T)
+  nd = _handle(gr, B, C)
+  try:
+    _push_all(nd, members, w)
+    nd.ens_tail_set(thr, dirs)
+    _check("W=257", nd.ens_tail_score(truth), R.reference(members, truth, w, thr, dirs), G, M)
+  finally:
+    nd.close()
+
+
 # ---- 4. identities on the device ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M", [3, 50])
 def test_identities_with_ens_score_on_the_same_store(M):

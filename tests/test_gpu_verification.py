@@ -81,6 +81,23 @@ def test_scores_match_the_float64_definition_tiny(M):
     nd.close()
 
 
+def test_a_second_column_tile_of_one_column():
+  """(B, C) = (1, 257): the second column tile is one column wide, so it has 256 node lanes -- more than the 8 nodes of a
+  block, most lanes walk nothing -- and the finish folds 256 lanes of at most one block each."""
+  gr = _graph()
+  G, B, C, M = gr.num_grid_nodes, 1, 257, 3
+  members, truth, w = _data(M, G, B, C, seed=257)
+  ref = R.reference(members, truth, w)
+  nd = _handle(gr, B, C)
+  try:
+    _push_all(nd, members, w)
+    sums, hist = nd.ens_score(truth, want_fields=True)
+    _check_sums("W=257", sums, hist, ref, G, M)
+    _check_fields("W=257", *nd.ens_download_fields(), ref)
+  finally:
+    nd.close()
+
+
 # ---- 2. full-size grids, set_graph only ----------------------------------------------------------------------------
 @pytest.mark.parametrize("case", ["nano", "one_degree"])
 def test_scores_match_the_float64_definition_full_size(case):
