@@ -77,6 +77,39 @@ Rccl& rccl() {
     }                                                                                       \
   } while (0)
 
+// The counters of the units that keep a Meter.  A unit with a regular name has <prefix>_calls and <prefix>_device_us, and
+// <prefix>_invalid_points where it counts skipped points; the names that do not follow are rows of their own.
+const int64_t* meter_counter(const gc_handle* h, const std::string& n) {
+  struct Unit { const char* prefix; Meter gc_handle::*meter; bool invalid_points; };
+  static const Unit units[] = {
+      {"ens_event", &gc_handle::evt, true},     {"ens_derive", &gc_handle::drv, false}, {"ens_band", &gc_handle::band, false},
+      {"ens_order", &gc_handle::ord, true},     {"ens_clim", &gc_handle::clim, true},   {"ens_energy", &gc_handle::en, true},
+      {"ens_variogram", &gc_handle::vg, false}, {"ens_tail", &gc_handle::tail, true},   {"ens_region", &gc_handle::reg, true},
+      {"ens_feature", &gc_handle::feat, false}, {"ens_fss", &gc_handle::fss, false}};
+  struct Row { const char* name; Meter gc_handle::*meter; int64_t Meter::*field; };
+  static const Row rows[] = {
+      {"ens_scores", &gc_handle::ens, &Meter::calls},
+      {"ens_score_device_us", &gc_handle::ens, &Meter::device_us},
+      {"ens_invalid_points", &gc_handle::ens, &Meter::invalid},
+      {"spec_calls", &gc_handle::spec, &Meter::calls},
+      {"spec_device_us", &gc_handle::spec, &Meter::device_us},
+      {"spec_invalid_columns", &gc_handle::spec, &Meter::invalid},
+      {"ens_band_invalid_columns", &gc_handle::band, &Meter::invalid},
+      {"ens_window_emits", &gc_handle::win, &Meter::calls},
+      {"ens_window_device_us", &gc_handle::win, &Meter::device_us}};
+  for (const Row& r : rows)
+    if (n == r.name) return &(h->*r.meter.*r.field);
+  for (const Unit& u : units) {
+    const size_t len = std::strlen(u.prefix);
+    if (n.compare(0, len, u.prefix) != 0) continue;
+    const Meter& m = h->*u.meter;
+    if (n.compare(len, std::string::npos, "_calls") == 0) return &m.calls;
+    if (n.compare(len, std::string::npos, "_device_us") == 0) return &m.device_us;
+    if (u.invalid_points && n.compare(len, std::string::npos, "_invalid_points") == 0) return &m.invalid;
+  }
+  return nullptr;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -877,46 +910,12 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
   else if (n == "graph_captures") *value = h->graph_captures;
   else if (n == "loss_evaluations") *value = h->loss_evaluations;
   else if (n == "loss_device_us") *value = h->loss_device_us;
-  else if (n == "ens_scores") *value = h->ens_scores;
-  else if (n == "ens_score_device_us") *value = h->ens_score_device_us;
-  else if (n == "ens_invalid_points") *value = h->ens_invalid_points;
-  else if (n == "spec_calls") *value = h->spec_calls;
-  else if (n == "spec_device_us") *value = h->spec_device_us;
-  else if (n == "spec_invalid_columns") *value = h->spec_invalid_columns;
-  else if (n == "ens_event_calls") *value = h->evt_calls;
-  else if (n == "ens_event_device_us") *value = h->evt_device_us;
-  else if (n == "ens_event_invalid_points") *value = h->evt_invalid_points;
-  else if (n == "ens_derive_calls") *value = h->drv_calls;
-  else if (n == "ens_derive_device_us") *value = h->drv_device_us;
-  else if (n == "ens_band_calls") *value = h->band_calls;
-  else if (n == "ens_band_device_us") *value = h->band_device_us;
-  else if (n == "ens_band_invalid_columns") *value = h->band_invalid_columns;
-  else if (n == "ens_order_calls") *value = h->ord_calls;
-  else if (n == "ens_order_device_us") *value = h->ord_device_us;
-  else if (n == "ens_order_invalid_points") *value = h->ord_invalid_points;
-  else if (n == "ens_clim_calls") *value = h->clim_calls;
-  else if (n == "ens_clim_device_us") *value = h->clim_device_us;
-  else if (n == "ens_clim_invalid_points") *value = h->clim_invalid_points;
-  else if (n == "ens_energy_calls") *value = h->en_calls;
-  else if (n == "ens_energy_device_us") *value = h->en_device_us;
-  else if (n == "ens_energy_invalid_points") *value = h->en_invalid_points;
-  else if (n == "ens_variogram_calls") *value = h->vg_calls;
-  else if (n == "ens_variogram_device_us") *value = h->vg_device_us;
-  else if (n == "ens_tail_calls") *value = h->tail_calls;
-  else if (n == "ens_tail_device_us") *value = h->tail_device_us;
-  else if (n == "ens_tail_invalid_points") *value = h->tail_invalid_points;
-  else if (n == "ens_region_calls") *value = h->reg_calls;
-  else if (n == "ens_region_device_us") *value = h->reg_device_us;
-  else if (n == "ens_feature_calls") *value = h->feat_calls;
-  else if (n == "ens_feature_device_us") *value = h->feat_device_us;
-  else if (n == "ens_region_invalid_points") *value = h->reg_invalid_points;
-  else if (n == "ens_fss_calls") *value = h->fss_calls;
-  else if (n == "ens_fss_device_us") *value = h->fss_device_us;
+  else if (const int64_t* v = meter_counter(h, n)) *value = *v;
   else if (n == "ens_window_pushes") *value = h->win_pushes;
-  else if (n == "ens_window_emits") *value = h->win_emits;
-  else if (n == "ens_window_device_us") *value = h->win_device_us;
-  else if (n == "ens_window_ring_bytes")
-    *value = (int64_t)((size_t)h->win_ring_L * (((size_t)(h->win_ring_M + 1) * h->hg.G * h->cfg.batch * h->cfg.c_out + 3) / 4 * 4) * sizeof(float));
+  else if (n == "ens_window_ring_bytes") {
+    const size_t L = h->win_allocs.key[0], M = h->win_allocs.key[1];   // (0, 0): no ring
+    *value = (int64_t)(L * (((M + 1) * h->hg.G * h->cfg.batch * h->cfg.c_out + 3) / 4 * 4) * sizeof(float));
+  }
   else if (n == "noise_stream") *value = (int64_t)h->nz_stream;
   else if (n == "device_allocations") {
     *value = 0;

@@ -172,55 +172,50 @@ int gc_ens_clim_score(gc_handle* h, gc_handle* clim, const float* truth, double*
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
   if (!clim || clim == h) return fail(h, GC_ERR_INVALID_ARGUMENT, "the climatology must be another handle");
-  if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  int rc = check_peer(h, clim, "climatology", false, h->cfg.c_out);
-  if (rc) return rc;
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  if (clim->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store on the climatology handle (gc_ens_reserve)");
-  if ((rc = store_complete(h, h)) || (rc = store_complete(h, clim, "climatology "))) return rc;
-  if (!h->has_ens_w) return fail(h, GC_ERR_STATE, "no node weights (gc_ens_set_node_weight)");
+  int rc;
+  if ((rc = need_out(h, sums)) || (rc = need_graph(h)) || (rc = check_peer(h, clim, "climatology", false, h->cfg.c_out)) ||
+      (rc = need_store(h)) || (rc = need(h, clim->ens_members != 0, "no member store on the climatology handle (gc_ens_reserve)")) ||
+      (rc = store_complete(h, h)) || (rc = store_complete(h, clim, "climatology ")) || (rc = need_weights(h)))
+    return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, h, truth, "gc_ens_clim_score"))) return rc;
   const gc_config& c = h->cfg;
   const int G = h->hg.G, B = c.batch, W = B * c.c_out, M = h->ens_members, K = clim->ens_members;
   const int blocks = gc::loss_reduce_blocks(G, B, c.c_out), tiles = (W + 255) / 256;
   if (!h->d_clim_part) {                             // sized by G, B and c_out alone: made once
-    if ((rc = dev_alloc(h, &h->d_clim_part, (size_t)blocks * gc::kClimSums * W, &h->clim_allocs)) ||
-        (rc = dev_alloc(h, &h->d_clim_cpart, (size_t)blocks * W + (size_t)blocks * tiles, &h->clim_allocs)) ||
-        (rc = dev_alloc(h, &h->d_clim_out, (size_t)gc::kClimSums * W, &h->clim_allocs)) ||
-        (rc = dev_alloc(h, &h->d_clim_outc, (size_t)W + 1, &h->clim_allocs))) {
-      h->clim_allocs.free();
+    if ((rc = alloc_all(h, h->clim_allocs, buf(&h->d_clim_part, (size_t)blocks * gc::kClimSums * W),
+                        buf(&h->d_clim_cpart, (size_t)blocks * W + (size_t)blocks * tiles),
+                        buf(&h->d_clim_out, (size_t)gc::kClimSums * W), buf(&h->d_clim_outc, (size_t)W + 1)))) {
       h->d_clim_part = nullptr;
       return rc;
     }
-    GC_HIP(h, h->clim_time.ensure());
     GC_HIP(h, h->ev_clim_src.ensure());
   }
   hipStream_t s = h->stream;
   // the climatology's store is complete on ITS stream: this handle's stream goes on behind it
   if ((rc = order_behind(h, h->ev_clim_src, clim->stream, s))) return rc;
   unsigned* const ipart = h->d_clim_cpart + (size_t)blocks * W;
-  GC_HIP(h, h->clim_time.begin(s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_clim(s, h->d_ens, M, clim->d_ens, K, field_len(h), h->d_ens_truth, h->d_ens_w, G, B, c.c_out,
-                                    h->d_clim_part, h->d_clim_cpart, ipart);
-       })))
-    return rc;
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_clim_finish(s, h->d_clim_part, h->d_clim_cpart, ipart, blocks, tiles, W, h->d_clim_out,
-                                           h->d_clim_outc);
-       })))
-    return rc;
-  GC_HIP(h, h->clim_time.end(s));
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counts are copied out as they lie");
-  std::vector<unsigned long long> cnt((size_t)W + 1);
-  GC_HIP(h, hipMemcpyAsync(sums, h->d_clim_out, (size_t)gc::kClimSums * W * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(cnt.data(), h->d_clim_outc, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));                // (the pass has read the climatology's store: it may be pushed into again)
-  GC_HIP(h, h->clim_time.microseconds(&h->clim_device_us));
-  h->clim_invalid_points = (int64_t)cnt.back();
-  ++h->clim_calls;
+  std::vector<uint64_t> cnt((size_t)W + 1);
+  // (on return the pass has read the climatology's store: it may be pushed into again)
+  rc = timed(h, h->clim,
+             [&] {
+               return launch_each(h,
+                   [&] {
+                     return gc::launch_ens_clim(s, h->d_ens, M, clim->d_ens, K, field_len(h), h->d_ens_truth, h->d_ens_w, G, B, c.c_out,
+                                                h->d_clim_part, h->d_clim_cpart, ipart);
+                   },
+                   [&] {
+                     return gc::launch_ens_clim_finish(s, h->d_clim_part, h->d_clim_cpart, ipart, blocks, tiles, W, h->d_clim_out,
+                                                       h->d_clim_outc);
+                   });
+             },
+             [&]() -> int {
+               if ((rc = read_back(h, sums, h->d_clim_out, (size_t)gc::kClimSums * W)) || (rc = read_back(h, cnt.data(), h->d_clim_outc, cnt.size())))
+                 return rc;
+               return GC_OK;
+             });
+  if (rc) return rc;
+  h->clim.invalid = (int64_t)cnt.back();
   if (counts)
     for (size_t i = 0; i + 1 < cnt.size(); ++i) counts[i] = cnt[i];
   if (invalid) invalid[0] = cnt.back();

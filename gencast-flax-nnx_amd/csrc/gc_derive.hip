@@ -489,7 +489,7 @@ int gc_ens_derive_set(gc_handle* h, int32_t c_src, const int32_t* op, const int3
                       const double* row_weight) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (pool < gc::kPoolNone || pool > gc::kPoolMean) return fail(h, GC_ERR_UNSUPPORTED, "pool must be 0 (none), 1 (max), 2 (min) or 3 (mean)");
   if (!op || !src_a || !src_b || !affine || (pool != gc::kPoolNone && (!r_lon || !row_weight)))
     return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
@@ -528,7 +528,6 @@ int gc_ens_derive_set(gc_handle* h, int32_t c_src, const int32_t* op, const int3
   int rc;
   double* d_blob = nullptr;
   if ((rc = dev_alloc(h, &d_blob, blob.size(), &h->drv_allocs))) return rc;
-  GC_HIP(h, h->drv_time.ensure());
   GC_HIP(h, h->ev_drv_src.ensure());
   if ((rc = store_upload(h, d_blob, blob.data(), blob.size() * sizeof(double)))) return rc;
   h->d_drv_affine = d_blob;
@@ -556,7 +555,7 @@ int gc_ens_derive_set_expr(gc_handle* h, int32_t c_src, const int32_t* op, const
                            const int32_t* pole_row) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (pool < gc::kPoolNone || pool > gc::kPoolMean) return fail(h, GC_ERR_UNSUPPORTED, "pool must be 0 (none), 1 (max), 2 (min) or 3 (mean)");
   if (!op || !src_a || !src_b || !affine || !scale || !loc || (pool != gc::kPoolNone && (!r_lon || !row_weight)))
     return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
@@ -666,7 +665,6 @@ int gc_ens_derive_set_expr(gc_handle* h, int32_t c_src, const int32_t* op, const
   int rc;
   double* d_blob = nullptr;
   if ((rc = dev_alloc(h, &d_blob, blob.size(), &h->drv_allocs))) return rc;
-  GC_HIP(h, h->drv_time.ensure());
   GC_HIP(h, h->ev_drv_src.ensure());
   if ((rc = store_upload(h, d_blob, blob.data(), blob.size() * sizeof(double)))) return rc;
   int* const d_ib = reinterpret_cast<int*>(d_blob + n_d);
@@ -699,74 +697,56 @@ int gc_ens_derive_set_expr(gc_handle* h, int32_t c_src, const int32_t* op, const
 int gc_ens_derive(gc_handle* h, gc_handle* src, const float* truth) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!src || src == h) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source must be another handle");
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (!h->drv_set) return fail(h, GC_ERR_STATE, "no plan (gc_ens_derive_set)");
-  int rc = check_peer(h, src, "source", false, h->drv_c_src, "c_out == c_src of the plan");
-  if (rc) return rc;
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  if (src->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store on the source handle (gc_ens_reserve)");
-  if (src->ens_members != h->ens_members) return fail(h, GC_ERR_STATE, "the two member stores hold different numbers of members");
-  if ((rc = store_complete(h, src, "source "))) return rc;
-  GC_HIP(h, hipSetDevice(h->device));
-  if ((rc = take_truth(h, src, truth, "gc_ens_derive"))) return rc;   // into the source's truth buffer, as gc_ens_score(src, truth, ...) would
+  int rc;
+  if ((rc = need_source(h, src)) || (rc = need_graph(h)) || (rc = need(h, h->drv_set, "no plan (gc_ens_derive_set)"))) return rc;
   const gc_config& c = h->cfg;
   const int G = h->hg.G, B = c.batch, c_d = c.c_out, W = B * c_d, pool = h->drv_pool, M = h->ens_members;
   const size_t field = field_len(h);
-  if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
   const int chunk = std::min(gc::kDrvChunk, M + 1);
-  const size_t need = pool == gc::kPoolNone ? 0 : (size_t)gc::kDrvChunk * field * (pool == gc::kPoolMean ? gc::kDrvMeanBytes : 4);
-  if (need && need != h->drv_work_bytes) {         // sized by the pool kind and the field: made again only when they change
-    GC_HIP(h, h->drv_work_allocs.drop(h->stream));
-    h->drv_work_bytes = 0;
-    if ((rc = dev_alloc(h, &h->d_drv_work, need, &h->drv_work_allocs))) return rc;
-    h->drv_work_bytes = need;
-  }
+  // the intermediate of a pooled plan, sized by the pool kind and the field
+  const size_t bytes = pool == gc::kPoolNone ? 0 : (size_t)gc::kDrvChunk * field * (pool == gc::kPoolMean ? gc::kDrvMeanBytes : 4);
+  rc = fill_open(h, src, h->drv_c_src, truth, "gc_ens_derive", h->ev_drv_src,
+                 [&] { return bytes ? sized_for(h, h->drv_work_allocs, {bytes}, buf(&h->d_drv_work, bytes)) : GC_OK; });
+  if (rc) return rc;
   hipStream_t s = h->stream;
-  // the source's store and truth are complete on ITS stream: this handle's stream goes on behind them
-  if ((rc = order_behind(h, h->ev_drv_src, src->stream, s))) return rc;
-  h->evt_scored = false;
-  h->has_ens_fields = false;
-  h->ord_ready = false;
-  GC_HIP(h, h->drv_time.begin(s));
   const int n_lat = h->drv_n_lat;
   const gc::DrvExpr g{h->d_drv_op, h->d_drv_a, h->d_drv_b, h->d_drv_affine, h->d_drv_tstart, h->d_drv_tq, h->d_drv_ta, h->d_drv_tb,
                       h->d_drv_rows, h->d_drv_rows + n_lat, h->d_drv_rows + 2 * (size_t)n_lat, h->d_drv_pole, h->drv_inv_2dlam,
                       h->drv_n_terms, n_lat, h->drv_n_lon};      // read by the plans of gc_ens_derive_set_expr only
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         if (h->drv_expr)
-           return gc::launch_ens_derive_expr(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out,
-                                             c_d, g);
-         return gc::launch_ens_derive(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out, c_d,
-                                      h->d_drv_op, h->d_drv_a, h->d_drv_b, h->d_drv_affine);
-       })))
-    return rc;
-  if (h->drv_expr && h->drv_poles &&
-      (rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_derive_pole(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out, c_d, g);
-       })))
-    return rc;
-  if (pool != gc::kPoolNone) {
-    for (int z0 = 0; z0 <= M; z0 += chunk) {
-      const int nz = std::min(chunk, M + 1 - z0);
-      if ((rc = launch(h, gc::KC_PACK, [&] {
-             return gc::launch_ens_pool_row(s, pool, h->d_ens, h->d_ens_truth, field, M, z0, nz, h->drv_n_lat, h->drv_n_lon, W,
-                                            h->d_drv_rlon, h->d_drv_work);
-           })))
-        return rc;
-      if ((rc = launch(h, gc::KC_PACK, [&] {
-             return gc::launch_ens_pool_col(s, pool, h->d_ens, h->d_ens_truth, field, M, z0, nz, h->drv_n_lat, h->drv_n_lon, W,
-                                            h->drv_r_lat, h->d_drv_work, h->d_drv_roww);
-           })))
-        return rc;
-    }
-  }
-  GC_HIP(h, h->drv_time.end(s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->drv_time.microseconds(&h->drv_device_us));
-  std::fill(h->ens_filled.begin(), h->ens_filled.end(), 1);
-  h->has_ens_truth = true;
-  ++h->drv_calls;
+  rc = timed(h, h->drv,
+             [&]() -> int {
+               if ((rc = launch_each(h, [&] {
+                     if (h->drv_expr)
+                       return gc::launch_ens_derive_expr(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B,
+                                                         src->cfg.c_out, c_d, g);
+                     return gc::launch_ens_derive(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B, src->cfg.c_out,
+                                                  c_d, h->d_drv_op, h->d_drv_a, h->d_drv_b, h->d_drv_affine);
+                   })))
+                 return rc;
+               if (h->drv_expr && h->drv_poles && (rc = launch_each(h, [&] {
+                     return gc::launch_ens_derive_pole(s, src->d_ens, src->d_ens_truth, h->d_ens, h->d_ens_truth, M, G, B,
+                                                       src->cfg.c_out, c_d, g);
+                   })))
+                 return rc;
+               if (pool == gc::kPoolNone) return GC_OK;
+               for (int z0 = 0; z0 <= M; z0 += chunk) {
+                 const int nz = std::min(chunk, M + 1 - z0);
+                 if ((rc = launch_each(h,
+                          [&] {
+                            return gc::launch_ens_pool_row(s, pool, h->d_ens, h->d_ens_truth, field, M, z0, nz, h->drv_n_lat,
+                                                           h->drv_n_lon, W, h->d_drv_rlon, h->d_drv_work);
+                          },
+                          [&] {
+                            return gc::launch_ens_pool_col(s, pool, h->d_ens, h->d_ens_truth, field, M, z0, nz, h->drv_n_lat,
+                                                           h->drv_n_lon, W, h->drv_r_lat, h->d_drv_work, h->d_drv_roww);
+                          })))
+                   return rc;
+               }
+               return GC_OK;
+             },
+             no_readbacks);
+  if (rc) return rc;
+  fill_close(h);
   return GC_OK;
   });
 }

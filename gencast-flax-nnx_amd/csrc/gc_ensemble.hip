@@ -245,10 +245,9 @@ using namespace gci;
 namespace {
 
 // the entries that need G only: no weights, no gc_finalize
-int ens_ready(gc_handle* h, bool need_store) {
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (need_store && h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  return GC_OK;
+int ens_ready(gc_handle* h, bool store) {
+  const int rc = need_graph(h);
+  return rc || !store ? rc : need_store(h);
 }
 
 int ens_slot(gc_handle* h, int32_t slot) {
@@ -257,7 +256,7 @@ int ens_slot(gc_handle* h, int32_t slot) {
 }
 
 int ctx_ready(gc_handle* h, int32_t slot) {
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (h->ctx_slots == 0) return fail(h, GC_ERR_STATE, "no context store (gc_ctx_reserve)");
   if (slot < 0 || slot >= h->ctx_slots) return fail(h, GC_ERR_INVALID_ARGUMENT, "slot outside [0, n)");
   return GC_OK;
@@ -300,19 +299,13 @@ int gc_ens_reserve(gc_handle* h, int32_t n_members) {
   const gc_config& c = h->cfg;
   const int G = h->hg.G, W = c.batch * c.c_out, M = n_members;
   const size_t blocks = (size_t)gc::loss_reduce_blocks(G, c.batch, c.c_out), tiles = (size_t)(W + 255) / 256;
-  if ((rc = dev_alloc(h, &h->d_ens, (size_t)M * field_len(h), &h->ens_allocs)) ||
-      (rc = dev_alloc(h, &h->d_ens_part, blocks * 6 * W, &h->ens_allocs)) ||
-      (rc = dev_alloc(h, &h->d_ens_hpart, blocks * W * (M + 1) + blocks * tiles, &h->ens_allocs)) ||
-      (rc = dev_alloc(h, &h->d_ens_sums, (size_t)6 * W, &h->ens_allocs)) ||
-      (rc = dev_alloc(h, &h->d_ens_hist, (size_t)W * (M + 1) + 1, &h->ens_allocs)) ||
-      (rc = dev_alloc(h, &h->d_ens_state_src, (size_t)c.c_out, &h->ens_allocs))) {
-    h->ens_allocs.free();
+  if ((rc = alloc_all(h, h->ens_allocs, buf(&h->d_ens, (size_t)M * field_len(h)), buf(&h->d_ens_part, blocks * 6 * W),
+                      buf(&h->d_ens_hpart, blocks * W * (M + 1) + blocks * tiles), buf(&h->d_ens_sums, (size_t)6 * W),
+                      buf(&h->d_ens_hist, (size_t)W * (M + 1) + 1), buf(&h->d_ens_state_src, (size_t)c.c_out))))
     return rc;
-  }
   h->ens_state_src.clear();
   GC_HIP(h, h->ev_ens_free.ensure());
   GC_HIP(h, h->ev_ens_done.ensure());
-  GC_HIP(h, h->ens_time.ensure());
   h->ens_filled.assign((size_t)M, 0);
   h->ens_members = M;
   return GC_OK;
@@ -373,11 +366,9 @@ int gc_ens_push_host(gc_handle* h, int32_t slot, const float* field) {
 int gc_ens_score(gc_handle* h, const float* truth, int32_t want_fields, double* sums, uint64_t* rank_hist) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  int rc = ens_ready(h, true);
-  if (rc) return rc;
-  if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  if ((rc = store_complete(h, h))) return rc;
-  if (!h->has_ens_w) return fail(h, GC_ERR_STATE, "no node weights (gc_ens_set_node_weight)");
+  int rc;
+  if ((rc = need_graph(h)) || (rc = need_store(h)) || (rc = need_out(h, sums)) || (rc = store_complete(h, h)) || (rc = need_weights(h)))
+    return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, h, truth, "gc_ens_score"))) return rc;
   const gc_config& c = h->cfg;
@@ -389,26 +380,25 @@ int gc_ens_score(gc_handle* h, const float* truth, int32_t want_fields, double* 
   hipStream_t s = h->stream;
   const int blocks = gc::loss_reduce_blocks(G, B, c.c_out);
   unsigned* const ipart = h->d_ens_hpart + (size_t)blocks * W * (M + 1);
-  GC_HIP(h, h->ens_time.begin(s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_score(s, h->d_ens, field, M, h->d_ens_truth, h->d_ens_w, G, B, c.c_out, h->d_ens_part,
-                                     h->d_ens_hpart, ipart, want_fields ? h->d_ens_mean : nullptr,
-                                     want_fields ? h->d_ens_var : nullptr);
-       })))
-    return rc;
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_finish(s, h->d_ens_part, h->d_ens_hpart, ipart, blocks, W, M, h->d_ens_sums, h->d_ens_hist);
-       })))
-    return rc;
-  GC_HIP(h, h->ens_time.end(s));
-  if (want_fields) h->has_ens_fields = true;
-  std::vector<unsigned long long> hist((size_t)W * (M + 1) + 1);
-  GC_HIP(h, hipMemcpyAsync(sums, h->d_ens_sums, (size_t)6 * W * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(hist.data(), h->d_ens_hist, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->ens_time.microseconds(&h->ens_score_device_us));
-  h->ens_invalid_points = (int64_t)hist.back();
-  ++h->ens_scores;
+  std::vector<uint64_t> hist((size_t)W * (M + 1) + 1);
+  rc = timed(h, h->ens,
+             [&] {
+               return launch_each(h,
+                   [&] {
+                     return gc::launch_ens_score(s, h->d_ens, field, M, h->d_ens_truth, h->d_ens_w, G, B, c.c_out, h->d_ens_part,
+                                                 h->d_ens_hpart, ipart, want_fields ? h->d_ens_mean : nullptr,
+                                                 want_fields ? h->d_ens_var : nullptr);
+                   },
+                   [&] { return gc::launch_ens_finish(s, h->d_ens_part, h->d_ens_hpart, ipart, blocks, W, M, h->d_ens_sums, h->d_ens_hist); });
+             },
+             [&]() -> int {
+               if (want_fields) h->has_ens_fields = true;      // (enqueued: a download on this stream finds them)
+               if ((rc = read_back(h, sums, h->d_ens_sums, (size_t)6 * W)) || (rc = read_back(h, hist.data(), h->d_ens_hist, hist.size())))
+                 return rc;
+               return GC_OK;
+             });
+  if (rc) return rc;
+  h->ens.invalid = (int64_t)hist.back();
   if (rank_hist)
     for (size_t i = 0; i + 1 < hist.size(); ++i) rank_hist[i] = hist[i];
   return GC_OK;
@@ -491,7 +481,7 @@ int gc_ens_download_member(gc_handle* h, int32_t slot, float* out) {
 int gc_ctx_reserve(gc_handle* h, int32_t n) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (n < 1 || n > 64) return fail(h, GC_ERR_UNSUPPORTED, "n must be in 1..64");
   GC_HIP(h, hipSetDevice(h->device));
   for (gc_handle::CtxSlot& c : h->ctx) {             // no copy into or out of the old store is still running

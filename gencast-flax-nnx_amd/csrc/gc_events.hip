@@ -209,7 +209,7 @@ int gc_ens_event_set(gc_handle* h, int32_t n_thresholds, const float* thresholds
                      const uint32_t* node_weight_q) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (!thresholds || !direction || !node_weight_q) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   if (n_thresholds < 1 || n_thresholds > gc::kEvtMaxThresholds) return fail(h, GC_ERR_UNSUPPORTED, "n_thresholds must be in 1..8");
   unsigned up = 0;
@@ -225,14 +225,10 @@ int gc_ens_event_set(gc_handle* h, int32_t n_thresholds, const float* thresholds
   if (T != h->evt_T) {
     GC_HIP(h, h->evt_allocs.drop(h->stream));        // nothing reads the old buffers any more
     h->evt_table_allocs.free();
-    h->evt_T = h->evt_table_T = h->evt_table_M = 0;
-    if ((rc = dev_alloc(h, &h->d_evt_thr, (size_t)T * field, &h->evt_allocs)) ||
-        (rc = dev_alloc(h, &h->d_evt_code, (size_t)T * field, &h->evt_allocs)) ||
-        (rc = dev_alloc(h, &h->d_evt_wq, (size_t)h->hg.G, &h->evt_allocs))) {
-      h->evt_allocs.free();
+    h->evt_T = 0;
+    if ((rc = alloc_all(h, h->evt_allocs, buf(&h->d_evt_thr, (size_t)T * field), buf(&h->d_evt_code, (size_t)T * field),
+                        buf(&h->d_evt_wq, (size_t)h->hg.G))))
       return rc;
-    }
-    GC_HIP(h, h->evt_time.ensure());
   }
   // on the handle's stream, behind whatever still reads the old values; the caller's arrays are free on return
   for (int t = 0; t < T; ++t)
@@ -248,53 +244,43 @@ int gc_ens_event_set(gc_handle* h, int32_t n_thresholds, const float* thresholds
 int gc_ens_event_score(gc_handle* h, const float* truth, uint64_t* weighted, uint64_t* counts, uint64_t* invalid) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (h->evt_T == 0) return fail(h, GC_ERR_STATE, "no thresholds (gc_ens_event_set)");
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  if (!weighted) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = store_complete(h, h);
-  if (rc) return rc;
+  int rc;
+  if ((rc = need_graph(h)) || (rc = need(h, h->evt_T != 0, "no thresholds (gc_ens_event_set)")) || (rc = need_store(h)) ||
+      (rc = need_out(h, weighted)) || (rc = store_complete(h, h)))
+    return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, h, truth, "gc_ens_event_score"))) return rc;
   const gc_config& c = h->cfg;
   const int G = h->hg.G, W = c.batch * c.c_out, M = h->ens_members, T = h->evt_T;
   const size_t field = field_len(h), len = evt_table_len(h, T, M);
-  if (h->evt_table_T != T || h->evt_table_M != M) {   // sized by M: made again when M or T changed
-    GC_HIP(h, h->evt_table_allocs.drop(h->stream));
-    h->evt_table_T = h->evt_table_M = 0;
-    if ((rc = dev_alloc(h, &h->d_evt_table, 2 * len + (size_t)T, &h->evt_table_allocs))) return rc;
-    h->evt_table_T = T;
-    h->evt_table_M = M;
-  }
+  if ((rc = sized_for(h, h->evt_table_allocs, {(size_t)T, (size_t)M}, buf(&h->d_evt_table, 2 * len + (size_t)T)))) return rc;
   hipStream_t s = h->stream;
   unsigned long long* const d_w = h->d_evt_table;
   unsigned long long* const d_c = d_w + len;
   unsigned long long* const d_inv = d_c + len;
-  GC_HIP(h, h->evt_time.begin(s));
-  GC_HIP(h, hipMemsetAsync(d_w, 0, (2 * len + (size_t)T) * sizeof(unsigned long long), s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_event_code(s, h->d_ens, field, M, h->d_ens_truth, T, h->d_evt_thr, h->evt_dir_up, h->d_evt_code);
-       })))
-    return rc;
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_event_table(s, h->d_evt_code, field, h->d_evt_wq, G, W, M, T, d_w, d_c, d_inv);
-       })))
-    return rc;
-  GC_HIP(h, h->evt_time.end(s));
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the tables are copied out as they lie");
-  std::vector<unsigned long long> inv((size_t)T);
-  GC_HIP(h, hipMemcpyAsync(weighted, d_w, len * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  if (counts) GC_HIP(h, hipMemcpyAsync(counts, d_c, len * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(inv.data(), d_inv, inv.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->evt_time.microseconds(&h->evt_device_us));
+  std::vector<uint64_t> inv((size_t)T);
+  rc = timed(h, h->evt,
+             [&]() -> int {
+               GC_HIP(h, hipMemsetAsync(d_w, 0, (2 * len + (size_t)T) * sizeof(unsigned long long), s));
+               return launch_each(h,
+                   [&] {
+                     return gc::launch_ens_event_code(s, h->d_ens, field, M, h->d_ens_truth, T, h->d_evt_thr, h->evt_dir_up, h->d_evt_code);
+                   },
+                   [&] { return gc::launch_ens_event_table(s, h->d_evt_code, field, h->d_evt_wq, G, W, M, T, d_w, d_c, d_inv); });
+             },
+             [&]() -> int {
+               if ((rc = read_back(h, weighted, d_w, len)) || (counts && (rc = read_back(h, counts, d_c, len))) ||
+                   (rc = read_back(h, inv.data(), d_inv, inv.size())))
+                 return rc;
+               return GC_OK;
+             });
+  if (rc) return rc;
   int64_t total = 0;
   for (int t = 0; t < T; ++t) {
     total += (int64_t)inv[(size_t)t];
     if (invalid) invalid[t] = inv[(size_t)t];
   }
-  h->evt_invalid_points = total;
-  ++h->evt_calls;
+  h->evt.invalid = total;
   h->evt_scored = true;
   return GC_OK;
   });
@@ -303,7 +289,7 @@ int gc_ens_event_score(gc_handle* h, const float* truth, uint64_t* weighted, uin
 int gc_ens_event_download(gc_handle* h, int32_t threshold, uint8_t* code) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (h->evt_T == 0) return fail(h, GC_ERR_STATE, "no thresholds (gc_ens_event_set)");
   if (!code) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   if (threshold < 0 || threshold >= h->evt_T) return fail(h, GC_ERR_INVALID_ARGUMENT, "threshold outside [0, n_thresholds)");

@@ -253,7 +253,7 @@ int gc_ens_feature_set(gc_handle* h, int32_t c_src, int32_t D, const int32_t* ch
                        const int32_t* strike_lat, const int32_t* strike_lon, int32_t max_centres) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (!channel || !direction || !use_threshold || !threshold || !r_lat || !r_lon || !ring_lat || !ring_lon || !depth ||
       !strike_lat || !strike_lon)
     return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
@@ -308,7 +308,6 @@ int gc_ens_feature_set(gc_handle* h, int32_t c_src, int32_t D, const int32_t* ch
   int rc;
   double* d_blob = nullptr;
   if ((rc = dev_alloc(h, &d_blob, blob.size(), &h->feat_allocs))) return rc;
-  GC_HIP(h, h->feat_time.ensure());
   GC_HIP(h, h->ev_feat_src.ensure());
   if ((rc = store_upload(h, d_blob, blob.data(), blob.size() * sizeof(double)))) return rc;
   h->d_feat_depth = d_blob;
@@ -325,21 +324,10 @@ int gc_ens_feature_set(gc_handle* h, int32_t c_src, int32_t D, const int32_t* ch
 int gc_ens_feature(gc_handle* h, gc_handle* src, const float* truth) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!src || src == h) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source must be another handle");
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (!h->feat_set) return fail(h, GC_ERR_STATE, "no plan (gc_ens_feature_set)");
-  int rc = check_peer(h, src, "source", false, h->feat_c_src, "c_out == c_src of the plan");
-  if (rc) return rc;
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  if (src->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store on the source handle (gc_ens_reserve)");
-  if (src->ens_members != h->ens_members) return fail(h, GC_ERR_STATE, "the two member stores hold different numbers of members");
-  if ((rc = store_complete(h, src, "source "))) return rc;
-  GC_HIP(h, hipSetDevice(h->device));
-  if ((rc = take_truth(h, src, truth, "gc_ens_feature"))) return rc;   // into the source's truth buffer, as gc_ens_derive does
+  int rc;
+  if ((rc = need_source(h, src)) || (rc = need_graph(h)) || (rc = need(h, h->feat_set, "no plan (gc_ens_feature_set)"))) return rc;
   const int G = h->hg.G, B = h->cfg.batch, D = h->cfg.c_out, M = h->ens_members, c_src = h->feat_c_src;
   const int n_lat = h->feat_n_lat, n_lon = h->feat_n_lon, maxc = h->feat_max;
-  const size_t field = field_len(h);
-  if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
   const int chunk = std::min(gc::kFeatChunk, M + 1);
   const int nblk = (G + 255) / 256;
   // the work of a chunk: keys and row minima (8 bytes each), block counts (4 bytes per 256 nodes), flags (1 byte), per
@@ -347,14 +335,12 @@ int gc_ens_feature(gc_handle* h, gc_handle* src, const float* truth) {
   const size_t cols = (size_t)gc::kFeatChunk * B * D, per_list = (size_t)(M + 1) * B * D;
   const size_t o_row = cols * G * 8, o_bc = 2 * o_row, o_flag = o_bc + cols * nblk * 4;
   const size_t o_count = (o_flag + cols * G + 7) / 8 * 8, o_node = o_count + (per_list * 4 + 7) / 8 * 8;
-  const size_t o_value = o_node + per_list * maxc * 4, need = o_value + per_list * maxc * 4;
-  if (need != h->feat_work_bytes) {                // sized by the field, M and max_centres: made again only when they change
-    GC_HIP(h, h->feat_work_allocs.drop(h->stream));
-    h->feat_work_bytes = 0;
-    h->feat_listed = false;
-    if ((rc = dev_alloc(h, &h->d_feat_work, need, &h->feat_work_allocs))) return rc;
-    h->feat_work_bytes = need;
-  }
+  const size_t o_value = o_node + per_list * maxc * 4, bytes = o_value + per_list * maxc * 4;
+  rc = fill_open(h, src, c_src, truth, "gc_ens_feature", h->ev_feat_src, [&] {   // sized by the field, M and max_centres
+    if (h->feat_work_allocs.differs({bytes})) h->feat_listed = false;          // the lists go with the buffer
+    return sized_for(h, h->feat_work_allocs, {bytes}, buf(&h->d_feat_work, bytes));
+  });
+  if (rc) return rc;
   unsigned char* const wk = h->d_feat_work;
   unsigned long long* const key = reinterpret_cast<unsigned long long*>(wk);
   unsigned long long* const rowmin = reinterpret_cast<unsigned long long*>(wk + o_row);
@@ -364,52 +350,45 @@ int gc_ens_feature(gc_handle* h, gc_handle* src, const float* truth) {
   int* const l_node = reinterpret_cast<int*>(wk + o_node);
   float* const l_value = reinterpret_cast<float*>(wk + o_value);
   hipStream_t s = h->stream;
-  // the source's store and truth are complete on ITS stream: this handle's stream goes on behind them
-  if ((rc = order_behind(h, h->ev_feat_src, src->stream, s))) return rc;
-  h->evt_scored = false;
-  h->has_ens_fields = false;
-  h->ord_ready = false;
   h->feat_listed = false;
   const int* const tab = h->d_feat_tab;
-  GC_HIP(h, h->feat_time.begin(s));
-  for (int z0 = 0; z0 <= M; z0 += chunk) {
-    const int nc = std::min(chunk, M + 1 - z0) * B * D;
-    if ((rc = launch(h, gc::KC_PACK, [&] {
-           hipLaunchKernelGGL(gc::gc_feat_gather_kernel, dim3(std::min(nblk, 1024), nc), dim3(256), 0, s, src->d_ens, src->d_ens_truth,
-                              h->d_ens, h->d_ens_truth, M, z0, G, B, c_src, D, tab, key);
-           return hipGetLastError();
-         })))
-      return rc;
-    if ((rc = launch(h, gc::KC_PACK, [&] {
-           hipLaunchKernelGGL(gc::gc_feat_row_kernel, dim3(n_lat, nc), dim3(256), gc::feat_row_lds(n_lon), s, key, G, n_lat, n_lon, D,
-                              tab + gc::kFtTables * D, rowmin);
-           return hipGetLastError();
-         })))
-      return rc;
-    if ((rc = launch(h, gc::KC_PACK, [&] {
-           hipLaunchKernelGGL(gc::gc_feat_col_kernel, dim3(nblk, nc), dim3(256), 0, s, key, rowmin, h->d_ens, h->d_ens_truth, M, z0, G,
-                              n_lat, n_lon, B, D, tab, h->d_feat_depth, flag, bcount);
-           return hipGetLastError();
-         })))
-      return rc;
-    if ((rc = launch(h, gc::KC_PACK, [&] {
-           hipLaunchKernelGGL(gc::gc_feat_list_kernel, dim3(nc), dim3(256), 0, s, src->d_ens, src->d_ens_truth, M, z0, G, B, c_src, D, tab,
-                              flag, bcount, nblk, maxc, l_count, l_node, l_value);
-           return hipGetLastError();
-         })))
-      return rc;
-  }
-  GC_HIP(h, h->feat_time.end(s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->feat_time.microseconds(&h->feat_device_us));
-  std::fill(h->ens_filled.begin(), h->ens_filled.end(), 1);
-  h->has_ens_truth = true;
+  rc = timed(h, h->feat,
+             [&]() -> int {
+               for (int z0 = 0; z0 <= M; z0 += chunk) {
+                 const int nc = std::min(chunk, M + 1 - z0) * B * D;
+                 if ((rc = launch_each(h,
+                          [&] {
+                            hipLaunchKernelGGL(gc::gc_feat_gather_kernel, dim3(std::min(nblk, 1024), nc), dim3(256), 0, s, src->d_ens,
+                                               src->d_ens_truth, h->d_ens, h->d_ens_truth, M, z0, G, B, c_src, D, tab, key);
+                            return hipGetLastError();
+                          },
+                          [&] {
+                            hipLaunchKernelGGL(gc::gc_feat_row_kernel, dim3(n_lat, nc), dim3(256), gc::feat_row_lds(n_lon), s, key, G, n_lat,
+                                               n_lon, D, tab + gc::kFtTables * D, rowmin);
+                            return hipGetLastError();
+                          },
+                          [&] {
+                            hipLaunchKernelGGL(gc::gc_feat_col_kernel, dim3(nblk, nc), dim3(256), 0, s, key, rowmin, h->d_ens, h->d_ens_truth,
+                                               M, z0, G, n_lat, n_lon, B, D, tab, h->d_feat_depth, flag, bcount);
+                            return hipGetLastError();
+                          },
+                          [&] {
+                            hipLaunchKernelGGL(gc::gc_feat_list_kernel, dim3(nc), dim3(256), 0, s, src->d_ens, src->d_ens_truth, M, z0, G, B,
+                                               c_src, D, tab, flag, bcount, nblk, maxc, l_count, l_node, l_value);
+                            return hipGetLastError();
+                          })))
+                   return rc;
+               }
+               return GC_OK;
+             },
+             no_readbacks);
+  if (rc) return rc;
+  fill_close(h);
   h->d_feat_count = l_count;
   h->d_feat_node = l_node;
   h->d_feat_value = l_value;
   h->feat_list_M = M;
   h->feat_listed = true;
-  ++h->feat_calls;
   return GC_OK;
   });
 }

@@ -278,11 +278,9 @@ namespace {
 
 // what both calls need before they launch: a plan, codes that are those of the store as it stands
 int fss_ready(gc_handle* h) {
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (!h->fss_S) return fail(h, GC_ERR_STATE, "no plan (gc_ens_fss_set)");
-  if (h->evt_T == 0 || !h->evt_scored || h->ens_members == 0)
-    return fail(h, GC_ERR_STATE, "no valid event codes on the device (gc_ens_event_score)");
-  return GC_OK;
+  int rc;
+  if ((rc = need_graph(h)) || (rc = need(h, h->fss_S != 0, "no plan (gc_ens_fss_set)"))) return rc;
+  return need(h, h->evt_T != 0 && h->evt_scored && h->ens_members != 0, "no valid event codes on the device (gc_ens_event_score)");
 }
 
 // The work buffer (S + 1 slabs of [G][wc] 8-byte elements: the row sums of every scale; the last slab takes the two float
@@ -291,20 +289,8 @@ int fss_ready(gc_handle* h) {
 int fss_work(gc_handle* h, int wc, int blocks) {
   const int S = h->fss_S, T = h->evt_T, W = h->cfg.batch * h->cfg.c_out;
   const size_t n_work = (size_t)(S + 1) * h->hg.G * wc, n_part = (size_t)blocks * S * 4 * wc, n_out = (size_t)T * S * W * 4;
-  if (n_work == h->fss_work_len && n_part == h->fss_part_len && n_out == h->fss_out_len) return GC_OK;
-  GC_HIP(h, h->fss_work_allocs.drop(h->stream));
-  h->fss_work_len = h->fss_part_len = h->fss_out_len = 0;
-  int rc;
-  if ((rc = dev_alloc(h, &h->d_fss_work, n_work, &h->fss_work_allocs)) ||
-      (rc = dev_alloc(h, &h->d_fss_part, n_part, &h->fss_work_allocs)) ||
-      (rc = dev_alloc(h, &h->d_fss_out, n_out, &h->fss_work_allocs))) {
-    h->fss_work_allocs.free();
-    return rc;
-  }
-  h->fss_work_len = n_work;
-  h->fss_part_len = n_part;
-  h->fss_out_len = n_out;
-  return GC_OK;
+  return sized_for(h, h->fss_work_allocs, {n_work, n_part, n_out}, buf(&h->d_fss_work, n_work), buf(&h->d_fss_part, n_part),
+                   buf(&h->d_fss_out, n_out));
 }
 
 }  // namespace
@@ -315,7 +301,7 @@ int gc_ens_fss_set(gc_handle* h, int32_t n_scales, int32_t n_lat, int32_t n_lon,
                    const uint32_t* row_wq) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (!r_lat || !r_lon || !row_wq) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   if (n_scales < 1 || n_scales > gc::kFssMaxScales) return fail(h, GC_ERR_UNSUPPORTED, "n_scales must be in 1..8");
   if (n_lon > gc::kFssMaxLon) return fail(h, GC_ERR_UNSUPPORTED, "n_lon is too large for the packed row counts (n_lon > 16384)");
@@ -342,7 +328,6 @@ int gc_ens_fss_set(gc_handle* h, int32_t n_scales, int32_t n_lat, int32_t n_lon,
   int rc;
   int32_t* d_blob = nullptr;
   if ((rc = dev_alloc(h, &d_blob, blob.size(), &h->fss_allocs))) return rc;
-  GC_HIP(h, h->fss_time.ensure());
   if ((rc = store_upload(h, d_blob, blob.data(), blob.size() * sizeof(int32_t)))) return rc;
   h->d_fss_rlat = d_blob;
   h->d_fss_rlon = d_blob + S;
@@ -358,9 +343,8 @@ int gc_ens_fss_set(gc_handle* h, int32_t n_scales, int32_t n_lat, int32_t n_lon,
 int gc_ens_fss_score(gc_handle* h, double* sums) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  int rc = fss_ready(h);
-  if (rc) return rc;
-  if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  int rc;
+  if ((rc = fss_ready(h)) || (rc = need_out(h, sums))) return rc;
   GC_HIP(h, hipSetDevice(h->device));
   const gc_config& c = h->cfg;
   const int G = h->hg.G, W = c.batch * c.c_out, M = h->ens_members, T = h->evt_T, S = h->fss_S;
@@ -369,40 +353,34 @@ int gc_ens_fss_score(gc_handle* h, double* sums) {
   const int wt = gc::fss_tile(n_lon, W), wc = gc::fss_chunk(S, G, W, wt), blocks = gc::fss_blocks(G, wc);
   if ((rc = fss_work(h, wc, blocks))) return rc;
   hipStream_t s = h->stream;
-  GC_HIP(h, h->fss_time.begin(s));
-  for (int t = 0; t < T; ++t) {
-    const unsigned char* const code = h->d_evt_code + (size_t)t * field;
-    for (int c0 = 0; c0 < W; c0 += wc) {
-      if ((rc = launch(h, gc::KC_PACK, [&] {
-             return gc::launch_ens_fss_row(s, code, n_lat, n_lon, W, c0, wc, wt, S, h->d_fss_rlon, h->d_fss_work);
-           })))
-        return rc;
-      if ((rc = launch(h, gc::KC_PACK, [&] {
-             return gc::launch_ens_fss_col(s, code, h->d_evt_wq, h->d_fss_roww, h->d_fss_rlat, h->d_fss_work, G, n_lat, n_lon, W,
-                                           c0, wc, M, S, blocks, h->d_fss_part);
-           })))
-        return rc;
-      if ((rc = launch(h, gc::KC_PACK, [&] {
-             return gc::launch_ens_fss_finish(s, h->d_fss_part, blocks, S, W, c0, wc, h->d_fss_out + (size_t)t * S * W * 4);
-           })))
-        return rc;
-    }
-  }
-  GC_HIP(h, h->fss_time.end(s));
-  GC_HIP(h, hipMemcpyAsync(sums, h->d_fss_out, (size_t)T * S * W * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->fss_time.microseconds(&h->fss_device_us));
-  ++h->fss_calls;
-  return GC_OK;
+  return timed(h, h->fss,
+               [&]() -> int {
+                 for (int t = 0; t < T; ++t) {
+                   const unsigned char* const code = h->d_evt_code + (size_t)t * field;
+                   for (int c0 = 0; c0 < W; c0 += wc)
+                     if ((rc = launch_each(h,
+                              [&] { return gc::launch_ens_fss_row(s, code, n_lat, n_lon, W, c0, wc, wt, S, h->d_fss_rlon, h->d_fss_work); },
+                              [&] {
+                                return gc::launch_ens_fss_col(s, code, h->d_evt_wq, h->d_fss_roww, h->d_fss_rlat, h->d_fss_work, G, n_lat,
+                                                              n_lon, W, c0, wc, M, S, blocks, h->d_fss_part);
+                              },
+                              [&] {
+                                return gc::launch_ens_fss_finish(s, h->d_fss_part, blocks, S, W, c0, wc,
+                                                                 h->d_fss_out + (size_t)t * S * W * 4);
+                              })))
+                       return rc;
+                 }
+                 return GC_OK;
+               },
+               [&] { return read_back(h, sums, h->d_fss_out, (size_t)T * S * W * 4); });
   });
 }
 
 int gc_ens_fss_fields(gc_handle* h, int32_t threshold, int32_t scale, float* prob, float* obs) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  int rc = fss_ready(h);
-  if (rc) return rc;
-  if (!prob || !obs) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  int rc;
+  if ((rc = fss_ready(h)) || (rc = need_out(h, prob && obs))) return rc;
   if (threshold < 0 || threshold >= h->evt_T) return fail(h, GC_ERR_INVALID_ARGUMENT, "threshold outside [0, n_thresholds)");
   if (scale < 0 || scale >= h->fss_S) return fail(h, GC_ERR_INVALID_ARGUMENT, "scale outside [0, n_scales)");
   GC_HIP(h, hipSetDevice(h->device));

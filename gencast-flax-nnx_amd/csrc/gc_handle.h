@@ -15,12 +15,13 @@
 //   gc_tail.hip      gc_ens_tail_*
 //   gc_region.hip    gc_ens_region_*
 //   gc_feature.hip   gc_ens_feature_*
-// The last twelve are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
-// lead times of another, gc_feature.hip with the strike fields of the centres it finds in another).  What they share -- field length, upload through
-// the pinned staging buffer, "every slot has been pushed", intake of the truth, validation of a second handle and the
-// relay of its failures, the order between two handles' streams -- is in gc_store.h.  The device buffers of a feature
-// are a BufferGroup and its events an Event or a Bracket (below); declaring one as a member of the handle is all it takes
-// for gc_destroy to release it and for the "device_allocations" counter to see it.
+//   gc_fss.hip       gc_ens_fss_*
+// The last thirteen are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
+// lead times of another, gc_feature.hip with the strike fields of the centres it finds in another).  Their host side is two
+// protocols, "score a store" and "fill a store from a source handle", written once in gc_store.h.  What a unit keeps on the
+// handle is declared with the types below: its device buffers are a BufferGroup (a KeyedGroup where a call makes them
+// again for other sizes), its events an Event, and the bookkeeping of its timed calls a Meter; declaring one as a member of
+// the handle is all it takes for gc_destroy to release it and for gc_get_counter to see it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -138,13 +139,43 @@ struct Bracket {
     const hipError_t e = e0.ensure(true);
     return e != hipSuccess ? e : e1.ensure(true);
   }
-  hipError_t begin(hipStream_t s) { return hipEventRecord(e0.e, s); }
+  hipError_t begin(hipStream_t s) {                // (the events are made by the first call)
+    const hipError_t e = ensure();
+    return e != hipSuccess ? e : hipEventRecord(e0.e, s);
+  }
   hipError_t end(hipStream_t s) { return hipEventRecord(e1.e, s); }
   hipError_t microseconds(int64_t* us) {           // (after the stream has been synchronised)
     float ms = 0.f;
     const hipError_t e = hipEventElapsedTime(&ms, e0.e, e1.e);
     *us = (int64_t)(ms * 1000.0f);
     return e;
+  }
+};
+
+// What a unit keeps of its timed calls (gci::timed, gc_store.h): the events of the last one, and the three numbers
+// gc_get_counter reports -- calls made, device time of the last, and what the last skipped (points or columns; 0 in a
+// unit that counts none).
+struct Meter {
+  Bracket time;
+  int64_t calls = 0, device_us = 0, invalid = 0;
+  explicit Meter(std::vector<Event*>& of_handle) : time(of_handle) {}
+};
+
+// A BufferGroup whose buffers are sized by N numbers: `key` is what they were made for, all zero where there are none (no
+// unit has an all-zero key).  A call that finds `differs(its sizes)` makes them again (gci::sized_for below).  free and
+// drop forget the key; gc_destroy frees through the BufferGroup, where no key matters any more.
+template <size_t N>
+struct KeyedGroup : BufferGroup {
+  std::array<size_t, N> key{};
+  using BufferGroup::BufferGroup;
+  bool differs(const std::array<size_t, N>& k) const { return key != k; }
+  void free() {
+    key.fill(0);
+    BufferGroup::free();
+  }
+  hipError_t drop(hipStream_t s) {
+    key.fill(0);
+    return BufferGroup::drop(s);
   }
 };
 
@@ -310,8 +341,7 @@ struct gc_handle {
   float *d_ens_mean = nullptr, *d_ens_var = nullptr;           // [G, B, c_out] each: made by the first call that asks for fields
   bool has_ens_w = false, has_ens_truth = false, has_ens_fields = false;
   gci::Event ev_ens_free{events}, ev_ens_done{events};         // stream order of a push from another handle
-  gci::Bracket ens_time{events};                               // of the last scoring call
-  int64_t ens_scores = 0, ens_score_device_us = 0, ens_invalid_points = 0;
+  gci::Meter ens{events};                                      // of gc_ens_score
   // member STATES (gc_ens_push_state): output channel j of a member comes from conditioning channel ens_state_src[j]
   // (-1: from the sample); the device copy is uploaded again only when the table changes
   std::vector<int32_t> ens_state_src;
@@ -339,12 +369,11 @@ struct gc_handle {
   double* d_sp_coef = nullptr;                   // [sp_sets][2][L m][L l][B c_out]
   double* d_sp_out = nullptr;                    // [6 + sp_sets][B c_out][L]: the sums, then the member powers
   unsigned* d_sp_flags = nullptr;                // [B c_out]: a value of the column was not finite
-  gci::Bracket spec_time{events};                // of the last spectrum call
-  int64_t spec_calls = 0, spec_device_us = 0, spec_invalid_columns = 0;
+  gci::Meter spec{events};                       // of gc_spec_field and gc_ens_spectrum; invalid: columns
 
   // spectral band views (gc_ens_band_*, gc_spectrum.hip): the plan, and the scratch of the one field in flight
   gci::BufferGroup band_allocs{groups};           // the plan's tables, one buffer: freed and replaced by gc_ens_band_set, dropped by gc_spec_set_tables
-  gci::BufferGroup band_work_allocs{groups};      // the scratch and the flags: made again by the call that finds their size changed
+  gci::KeyedGroup<2> band_work_allocs{groups};    // the scratch and the flags, sized by (B nu, M + 1): made again by the call that finds either changed
   bool band_set = false;                         // a plan has been set
   int band_c_src = 0, band_K = 0, band_nu = 0;   // source channels, bands, DISTINCT source channels the plan reads
   double* d_band_resp = nullptr;                 // [K][L] responses
@@ -355,28 +384,24 @@ struct gc_handle {
   double *d_band_F = nullptr, *d_band_coef = nullptr;    // [2][L][n_lat][B nu], [2][L m][L l][B nu]: its analysis
   double* d_band_G = nullptr;                    // [2][L m][n_lat][B c_out]: the Legendre synthesis of every derived column
   unsigned* d_band_flags = nullptr;              // [M + 1][B nu]: a value of the column of that field was not finite
-  size_t band_work_key[2] = {0, 0};              // (B nu, M + 1) the scratch and the flags are sized for
-  gci::Bracket band_time{events};                // of the last call
+  gci::Meter band{events};                       // of gc_ens_band; invalid: columns
   gci::Event ev_band_src{events};                // stream order behind the source handle
-  int64_t band_calls = 0, band_device_us = 0, band_invalid_columns = 0;
 
   // ensemble event verification (gc_ens_event_*, gc_events.hip): threshold fields and the tables scored from the member store
   gci::BufferGroup evt_allocs{groups};            // sized by T: thresholds, codes, weights; kept across gc_ens_reserve
-  gci::BufferGroup evt_table_allocs{groups};      // sized by T and M: made again by the scoring call that finds either changed
+  gci::KeyedGroup<2> evt_table_allocs{groups};    // sized by (T, M): made again by the scoring call that finds either changed
   int evt_T = 0;                                 // thresholds set (0: none)
   unsigned evt_dir_up = 0;                       // bit t: the event of threshold t is `value > thr`
-  int evt_table_T = 0, evt_table_M = 0;          // what d_evt_table is sized for
   float* d_evt_thr = nullptr;                    // [T][G, B, c_out]
   unsigned char* d_evt_code = nullptr;           // [T][G, B, c_out]: k | o << 7, 255 = not counted
   unsigned* d_evt_wq = nullptr;                  // [G] integer node weights
   unsigned long long* d_evt_table = nullptr;     // weighted [T][B c_out][2][M + 1], counts (same), invalid [T]
   bool evt_scored = false;                       // a scoring call ran since gc_ens_event_set / gc_ens_reserve
-  gci::Bracket evt_time{events};                 // of the last scoring call
-  int64_t evt_calls = 0, evt_device_us = 0, evt_invalid_points = 0;
+  gci::Meter evt{events};                        // of gc_ens_event_score
 
   // derived and pooled ensemble fields (gc_ens_derive_*, gc_derive.hip): the plan, and the intermediate of the pooling passes
   gci::BufferGroup drv_allocs{groups};            // the plan's tables, one buffer: freed and replaced by gc_ens_derive_set
-  gci::BufferGroup drv_work_allocs{groups};       // the intermediate: made again by the call that finds its size changed
+  gci::KeyedGroup<1> drv_work_allocs{groups};     // the intermediate, sized by its bytes: made again by the call that finds them changed
   bool drv_set = false;                          // a plan has been set
   int drv_c_src = 0, drv_pool = 0, drv_n_lat = 0, drv_n_lon = 0, drv_r_lat = 0;
   double *d_drv_affine = nullptr, *d_drv_roww = nullptr;       // [c_out][4] (sa, la, sb, lb), [n_lat]
@@ -389,26 +414,22 @@ struct gc_handle {
   double *d_drv_tq = nullptr, *d_drv_rows = nullptr;           // [5][n_terms] (coef, sa, la, sb, lb), [3][n_lat] (cos, 1 / (R cos), 1 / dphi)
   int *d_drv_tstart = nullptr, *d_drv_ta = nullptr, *d_drv_tb = nullptr, *d_drv_pole = nullptr;   // [c_out][3], [n_terms] x 2, [n_lat]
   unsigned char* d_drv_work = nullptr;           // 8 fields of row-pooled values: a float (max, min), or a double and an int32 (mean), per point
-  size_t drv_work_bytes = 0;
-  gci::Bracket drv_time{events};                               // of the last call
+  gci::Meter drv{events};                                      // of gc_ens_derive
   gci::Event ev_drv_src{events};                               // stream order behind the source handle
-  int64_t drv_calls = 0, drv_device_us = 0;
 
   // ensemble order statistics (gc_ens_order_*, gc_order.hip): quantile fields and the bin sums of the CRPS decomposition
   gci::BufferGroup ord_allocs{groups};            // sized by Q: the quantile fields; kept across gc_ens_reserve
-  gci::BufferGroup ord_work_allocs{groups};       // sized by M and Q: made again by the scoring call that finds either changed
+  gci::KeyedGroup<2> ord_work_allocs{groups};     // the partial and result buffers, sized by (M, Q): made again by the scoring call that finds either changed
   bool ord_set = false;                          // probabilities have been set (Q = 0 is a setting)
   int ord_Q = 0;
   double ord_p[8] = {};                          // the probabilities: lo, hi and f are formed per call from the current M
-  int ord_work_M = 0, ord_work_Q = -1;           // what the partial and result buffers are sized for
   float* d_ord_q = nullptr;                      // [Q][G, B, c_out] quantile fields
   double* d_ord_part = nullptr;                  // [blocks][2 (M + 1) + 3 + Q][B c_out] per-block column sums
   unsigned* d_ord_cpart = nullptr;               // [blocks][Q + 1][B c_out] per-block counts, then [blocks][tiles] skipped points
   double* d_ord_out = nullptr;                   // bins [B c_out][M + 1][2], extra [B c_out][3], pinball [B c_out][Q]
   unsigned long long* d_ord_outc = nullptr;      // counts [B c_out][Q + 1], then the skipped points of the call
   bool ord_ready = false;                        // an order call ran since gc_ens_order_set / gc_ens_reserve / gc_ens_derive
-  gci::Bracket ord_time{events};                 // of the last call
-  int64_t ord_calls = 0, ord_device_us = 0, ord_invalid_points = 0;
+  gci::Meter ord{events};                        // of gc_ens_order_score and gc_ens_order_fields
 
   // an ensemble against a climatology (gc_ens_clim_score, gc_clim.hip): the sums of a pass over this handle's store and another's
   gci::BufferGroup clim_allocs{groups};           // sized by G, B and c_out alone: made by the first call, kept
@@ -416,36 +437,31 @@ struct gc_handle {
   unsigned* d_clim_cpart = nullptr;              // [blocks][B c_out] per-block counted points, then [blocks][tiles] skipped points
   double* d_clim_out = nullptr;                  // [B c_out][12]
   unsigned long long* d_clim_outc = nullptr;     // [B c_out] counted points, then the skipped points of the call
-  gci::Bracket clim_time{events};                // of the last call
+  gci::Meter clim{events};                       // of gc_ens_clim_score
   gci::Event ev_clim_src{events};                // stream order behind the climatology handle
-  int64_t clim_calls = 0, clim_device_us = 0, clim_invalid_points = 0;
 
   // time-window ensemble fields (gc_ens_window_*, gc_window.hip): the plan, and the ring of the last L pushed lead times
-  gci::BufferGroup win_allocs{groups};            // the ring, one buffer: made again by the push that finds L or M changed
+  gci::KeyedGroup<2> win_allocs{groups};          // the ring, one buffer sized by (L, M): made again by the push that finds either changed
   bool win_set = false;                          // a plan has been set
   int win_kind = 0, win_L = 0;                   // 0 linear, 1 max, 2 min; the window length
-  int win_ring_L = 0, win_ring_M = 0;            // what d_win_ring is sized for (0: no ring)
   float* d_win_ring = nullptr;                   // [L][(M + 1) [G, B, c_out] padded to whole float4s]: M members, then the truth
   double* d_win_coef = nullptr;                  // [64] coefficients of a linear window, oldest first: made once
   int64_t win_pushes = 0;                        // pushes since the last gc_ens_window_set / _reset: the next goes to slot win_pushes % L
-  gci::Bracket win_time{events};                 // of the last emit
+  gci::Meter win{events};                        // of gc_ens_window_emit
   gci::Event ev_win_src{events};                 // stream order behind the source handle
-  int64_t win_emits = 0, win_device_us = 0;
 
   // multivariate ensemble scores (gc_ens_energy_*, gc_ens_variogram_*, gc_multivar.hip): the two plans and their sums
   gci::BufferGroup en_allocs{groups};             // the energy plan's tables: freed and replaced by gc_ens_energy_set
-  gci::BufferGroup en_work_allocs{groups};        // sized by M and the plan: made again by the scoring call that finds either changed
+  gci::KeyedGroup<3> en_work_allocs{groups};      // the partial and result buffers, sized by (M, K, blocks): made again by the scoring call that finds one changed
   bool en_set = false;                           // an energy plan has been set
   int en_K = 0, en_nc_max = 0;                   // groups; channels of the largest
   int *d_en_gchan = nullptr, *d_en_goff = nullptr;   // the channels of the groups, group after group; [K + 1] where each starts
   double* d_en_scale = nullptr;                  // [c_out] a[c]
-  int en_work_M = 0, en_work_K = 0, en_work_blocks = 0;   // what the partial and result buffers are sized for
   double* d_en_part = nullptr;                   // [blocks][B K][P] per-block pair sums, then [blocks][B K] per-block S0
   unsigned* d_en_ipart = nullptr;                // [blocks][B K] skipped points
   double* d_en_out = nullptr;                    // D2 [B][K][P], then S0 [B][K]
   unsigned long long* d_en_outc = nullptr;       // the skipped points of the call
-  gci::Bracket en_time{events};                  // of the last energy call
-  int64_t en_calls = 0, en_device_us = 0, en_invalid_points = 0;
+  gci::Meter en{events};                         // of gc_ens_energy_score
   gci::BufferGroup vg_allocs{groups};             // the variogram plan and the buffers sized by it: replaced by gc_ens_variogram_set
   bool vg_set = false;                           // a variogram plan has been set
   int vg_O = 0, vg_pk = 0, vg_n_lat = 0, vg_n_lon = 0;   // offsets; order 0 (p = 0.5), 1, 2; the grid
@@ -454,56 +470,49 @@ struct gc_handle {
   unsigned* d_vg_cpart = nullptr;                // [blocks][O][B c_out] per-block valid pairs
   double* d_vg_out = nullptr;                    // [4][B c_out][O]
   unsigned long long* d_vg_outc = nullptr;       // [B c_out][O]
-  gci::Bracket vg_time{events};                  // of the last variogram call
-  int64_t vg_calls = 0, vg_device_us = 0;
+  gci::Meter vg{events};                         // of gc_ens_variogram_score
 
   // threshold-weighted CRPS (gc_ens_tail_*, gc_tail.hip): threshold fields of its own and the sums of one sort per point
   gci::BufferGroup tail_allocs{groups};           // sized by T: the thresholds; kept across gc_ens_reserve
-  gci::BufferGroup tail_work_allocs{groups};      // sized by T: made again by the scoring call that finds it changed
+  gci::KeyedGroup<1> tail_work_allocs{groups};    // the partial and result buffers, sized by T: made again by the scoring call that finds it changed
   int tail_T = 0;                                // thresholds set (0: none)
   unsigned tail_dir_up = 0;                      // bit t: threshold t is the upper tail, weight 1{z >= thr}
-  int tail_work_T = 0;                           // what the partial and result buffers are sized for
   float* d_tail_thr = nullptr;                   // [T][G, B, c_out]
   double* d_tail_part = nullptr;                 // [blocks][T][4][B c_out] per-block column sums
   unsigned* d_tail_cpart = nullptr;              // [blocks][T][B c_out] per-block counted points
   double* d_tail_out = nullptr;                  // [T][B c_out][4]
   unsigned long long* d_tail_outc = nullptr;     // [T][B c_out] counted points
-  gci::Bracket tail_time{events};                // of the last call
-  int64_t tail_calls = 0, tail_device_us = 0, tail_invalid_points = 0;
+  gci::Meter tail{events};                       // of gc_ens_tail_score
 
   // regional ensemble scores (gc_ens_region_*, gc_region.hip): the plan on the host, its device copy and the sums of one pass
-  gci::BufferGroup reg_allocs{groups};            // the plan's device copy and everything sized by it and by M: replaced as a whole
+  gci::KeyedGroup<1> reg_allocs{groups};          // the plan's device copy and everything sized by it and by M (the key): replaced as a whole
   int reg_R = 0;                                 // regions set (0: no plan)
   int reg_listed = 0, reg_blocks = 0;            // nodes that belong to a region; entries of the block table
   std::vector<int> reg_plan;                     // order [listed], {begin, end} [blocks], atom bits [blocks]: kept across gc_ens_reserve
-  int reg_dev_M = 0;                             // M the device buffers are sized for (0: none)
   int* d_reg_plan = nullptr;                     // reg_plan as it lies
   double* d_reg_part = nullptr;                  // [blocks][6][B c_out] per-block column sums
   unsigned* d_reg_hpart = nullptr;               // [blocks][B c_out][M + 1] per-block rank counts, then [blocks][tiles] skipped points
   double* d_reg_sums = nullptr;                  // [R][6][B][c_out]
   unsigned long long* d_reg_hist = nullptr;      // [R][B][c_out][M + 1], then [R] skipped points
-  gci::Bracket reg_time{events};                 // of the last call
-  int64_t reg_calls = 0, reg_device_us = 0, reg_invalid_points = 0;
+  gci::Meter reg{events};                        // of gc_ens_region_score
 
   // ensemble feature detection (gc_ens_feature_*, gc_feature.hip): the plan, the work of a chunk of fields, the centre lists
   gci::BufferGroup feat_allocs{groups};           // the plan's tables, one buffer: freed and replaced by gc_ens_feature_set
-  gci::BufferGroup feat_work_allocs{groups};      // the work buffers and the lists: made again by the call that finds their size changed
+  gci::KeyedGroup<1> feat_work_allocs{groups};    // the work buffers and the lists, one buffer sized by its bytes: made again by the call that finds them changed
   bool feat_set = false;                         // a plan has been set
   bool feat_listed = false;                      // the lists are those of a call under the current plan
   int feat_c_src = 0, feat_n_lat = 0, feat_n_lon = 0, feat_max = 0, feat_list_M = 0;
   double* d_feat_depth = nullptr;                // [c_out]
   int* d_feat_tab = nullptr;                     // [7][c_out] per-detector tables, then r_lon, ring_lon, strike_lon [c_out][n_lat]
   unsigned char* d_feat_work = nullptr;          // 8 fields of keys, row minima, flags and block counts; then the lists
-  size_t feat_work_bytes = 0;
   int *d_feat_count = nullptr, *d_feat_node = nullptr;   // [M + 1][B][c_out], [M + 1][B][c_out][max_centres]: inside d_feat_work
   float* d_feat_value = nullptr;                 // [M + 1][B][c_out][max_centres]
-  gci::Bracket feat_time{events};                // of the last call
+  gci::Meter feat{events};                       // of gc_ens_feature
   gci::Event ev_feat_src{events};                // stream order behind the source handle
-  int64_t feat_calls = 0, feat_device_us = 0;
 
   // fractions skill score (gc_ens_fss_*, gc_fss.hip): the plan of the scales, and the row sums of a chunk of columns
   gci::BufferGroup fss_allocs{groups};            // the plan's tables, one buffer: freed and replaced by gc_ens_fss_set; kept across gc_ens_reserve
-  gci::BufferGroup fss_work_allocs{groups};       // the work buffer, the partials and the sums: made again by the call that finds a size changed
+  gci::KeyedGroup<3> fss_work_allocs{groups};     // the work buffer, the partials and the sums, sized by their three lengths: made again by the call that finds one changed
   int fss_S = 0;                                 // scales set (0: no plan)
   int fss_n_lat = 0, fss_n_lon = 0;
   std::vector<int32_t> fss_rlat;                 // [S], as on the device (gc_ens_fss_fields passes one by value)
@@ -512,9 +521,7 @@ struct gc_handle {
   uint2* d_fss_work = nullptr;                   // [S + 1][G][chunk columns]: (k sum, o | counts << 16) of the row windows; last slab: two float fields
   double* d_fss_part = nullptr;                  // [blocks][S][4][chunk columns] per-block column sums
   double* d_fss_out = nullptr;                   // [T][S][B c_out][4]
-  size_t fss_work_len = 0, fss_part_len = 0, fss_out_len = 0;   // what the three are sized for
-  gci::Bracket fss_time{events};                 // of the last scoring call
-  int64_t fss_calls = 0, fss_device_us = 0;
+  gci::Meter fss{events};                        // of gc_ens_fss_score
 
   // HIP-graph replay of the sampler (gc_set_option "graphs"): one captured graph per sample signature
   struct SampleGraph {
@@ -607,6 +614,45 @@ int dev_upload(gc_handle* h, T** p, const std::vector<T>& v, BufferGroup* owner 
   int rc = dev_alloc(h, p, v.size(), owner);
   if (rc) return rc;
   if (!v.empty()) GC_HIP(h, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return GC_OK;
+}
+
+// `count` elements at *p, to be allocated into a group (alloc_all, sized_for); `from`: host values copied into them
+template <typename T>
+struct Buf {
+  T** p;
+  size_t count;
+  const T* from;
+};
+template <typename T>
+Buf<T> buf(T** p, size_t count, const T* from = nullptr) { return {p, count, from}; }
+template <typename T>
+Buf<T> buf(T** p, const std::vector<T>& v) { return {p, v.size(), v.data()}; }
+
+template <typename T>
+int alloc_one(gc_handle* h, BufferGroup& g, const Buf<T>& b) {
+  if (int rc = dev_alloc(h, b.p, b.count, &g)) return rc;
+  if (b.from && b.count) GC_HIP(h, hipMemcpy(*b.p, b.from, b.count * sizeof(T), hipMemcpyHostToDevice));
+  return GC_OK;
+}
+
+// These buffers into `g`, in order; the first failure frees the whole group and is returned.
+template <typename... T>
+int alloc_all(gc_handle* h, BufferGroup& g, Buf<T>... b) {
+  int rc = GC_OK;
+  ((rc = rc ? rc : alloc_one(h, g, b)), ...);
+  if (rc) g.free();
+  return rc;
+}
+
+// The buffers of `g` are those made for `key`, or the old ones are dropped (behind everything on the handle's stream) and
+// these made in their place.
+template <size_t N, typename... T>
+int sized_for(gc_handle* h, KeyedGroup<N>& g, const std::array<size_t, N>& key, Buf<T>... b) {
+  if (!g.differs(key)) return GC_OK;
+  GC_HIP(h, g.drop(h->stream));
+  if (int rc = alloc_all(h, g, b...)) return rc;
+  g.key = key;
   return GC_OK;
 }
 

@@ -334,14 +334,10 @@ using namespace gci;
 namespace {
 
 // validation shared by the two scoring entries: a graph, a plan, a complete store, weights
-int mv_ready(gc_handle* h, bool plan, const char* setter) {
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (!plan) return fail(h, GC_ERR_STATE, std::string("no plan (") + setter + ")");
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  int rc = store_complete(h, h);
-  if (rc) return rc;
-  if (!h->has_ens_w) return fail(h, GC_ERR_STATE, "no node weights (gc_ens_set_node_weight)");
-  return GC_OK;
+int mv_ready(gc_handle* h, bool plan, const char* no_plan) {
+  int rc;
+  if ((rc = need_graph(h)) || (rc = need(h, plan, no_plan)) || (rc = need_store(h)) || (rc = store_complete(h, h))) return rc;
+  return need_weights(h);
 }
 
 }  // namespace
@@ -351,7 +347,7 @@ extern "C" {
 int gc_ens_energy_set(gc_handle* h, int32_t n_groups, const int32_t* group, const double* scale) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (n_groups < 1 || n_groups > gc::kMvMaxGroups) return fail(h, GC_ERR_UNSUPPORTED, "n_groups must be in 1..32");
   if (!group || !scale) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   const int C = h->cfg.c_out, K = n_groups;
@@ -374,13 +370,7 @@ int gc_ens_energy_set(gc_handle* h, int32_t n_groups, const int32_t* group, cons
   GC_HIP(h, hipSetDevice(h->device));
   GC_HIP(h, h->en_allocs.drop(h->stream));            // nothing reads the old plan any more
   h->en_set = false;
-  int rc;
-  if ((rc = dev_upload(h, &h->d_en_gchan, gchan, &h->en_allocs)) || (rc = dev_upload(h, &h->d_en_goff, goff, &h->en_allocs)) ||
-      (rc = dev_upload(h, &h->d_en_scale, a, &h->en_allocs))) {
-    h->en_allocs.free();
-    return rc;
-  }
-  GC_HIP(h, h->en_time.ensure());
+  if (int rc = alloc_all(h, h->en_allocs, buf(&h->d_en_gchan, gchan), buf(&h->d_en_goff, goff), buf(&h->d_en_scale, a))) return rc;
   h->en_K = K;
   h->en_nc_max = 0;
   for (int k = 0; k < K; ++k) h->en_nc_max = std::max(h->en_nc_max, goff[(size_t)k + 1] - goff[(size_t)k]);
@@ -392,50 +382,40 @@ int gc_ens_energy_set(gc_handle* h, int32_t n_groups, const int32_t* group, cons
 int gc_ens_energy_score(gc_handle* h, const float* truth, double* d2, double* s0, uint64_t* invalid) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  int rc = mv_ready(h, h->en_set, "gc_ens_energy_set");
-  if (rc) return rc;
-  if (!d2 || !s0) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  int rc;
+  if ((rc = mv_ready(h, h->en_set, "no plan (gc_ens_energy_set)")) || (rc = need_out(h, d2 && s0))) return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, h, truth, "gc_ens_energy_score"))) return rc;
   const gc_config& c = h->cfg;
   const int G = h->hg.G, B = c.batch, M = h->ens_members, K = h->en_K, BK = B * K, P = gc::mv_pairs(M);
   const int blocks = gc::mv_energy_blocks(G, BK, P, h->en_nc_max);
   const size_t n_out = (size_t)BK * P + BK;
-  if (h->en_work_M != M || h->en_work_K != K || h->en_work_blocks != blocks) {   // sized by M and the plan
-    GC_HIP(h, h->en_work_allocs.drop(h->stream));
-    h->en_work_M = 0;
-    if ((rc = dev_alloc(h, &h->d_en_part, (size_t)blocks * n_out, &h->en_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_en_ipart, (size_t)blocks * BK, &h->en_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_en_out, n_out, &h->en_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_en_outc, 1, &h->en_work_allocs))) {
-      h->en_work_allocs.free();
-      return rc;
-    }
-    h->en_work_M = M;
-    h->en_work_K = K;
-    h->en_work_blocks = blocks;
-  }
+  // sized by M and the plan
+  if ((rc = sized_for(h, h->en_work_allocs, {(size_t)M, (size_t)K, (size_t)blocks}, buf(&h->d_en_part, (size_t)blocks * n_out),
+                      buf(&h->d_en_ipart, (size_t)blocks * BK), buf(&h->d_en_out, n_out), buf(&h->d_en_outc, 1))))
+    return rc;
   hipStream_t s = h->stream;
   double* const s0part = h->d_en_part + (size_t)blocks * BK * P;
-  GC_HIP(h, h->en_time.begin(s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_energy(s, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, h->d_en_scale, h->d_en_gchan,
-                                      h->d_en_goff, G, B, c.c_out, K, blocks, h->d_en_part, s0part, h->d_en_ipart);
-       })))
-    return rc;
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_energy_finish(s, h->d_en_part, s0part, h->d_en_ipart, blocks, BK, P, h->d_en_out, h->d_en_outc);
-       })))
-    return rc;
-  GC_HIP(h, h->en_time.end(s));
-  unsigned long long inv = 0;
-  GC_HIP(h, hipMemcpyAsync(d2, h->d_en_out, (size_t)BK * P * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(s0, h->d_en_out + (size_t)BK * P, (size_t)BK * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(&inv, h->d_en_outc, sizeof(inv), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->en_time.microseconds(&h->en_device_us));
-  h->en_invalid_points = (int64_t)inv;
-  ++h->en_calls;
+  uint64_t inv = 0;
+  rc = timed(h, h->en,
+             [&] {
+               return launch_each(h,
+                   [&] {
+                     return gc::launch_ens_energy(s, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, h->d_en_scale, h->d_en_gchan,
+                                                  h->d_en_goff, G, B, c.c_out, K, blocks, h->d_en_part, s0part, h->d_en_ipart);
+                   },
+                   [&] {
+                     return gc::launch_ens_energy_finish(s, h->d_en_part, s0part, h->d_en_ipart, blocks, BK, P, h->d_en_out, h->d_en_outc);
+                   });
+             },
+             [&]() -> int {
+               if ((rc = read_back(h, d2, h->d_en_out, (size_t)BK * P)) || (rc = read_back(h, s0, h->d_en_out + (size_t)BK * P, (size_t)BK)) ||
+                   (rc = read_back(h, &inv, h->d_en_outc, 1)))
+                 return rc;
+               return GC_OK;
+             });
+  if (rc) return rc;
+  h->en.invalid = (int64_t)inv;
   if (invalid) invalid[0] = inv;
   return GC_OK;
   });
@@ -444,7 +424,7 @@ int gc_ens_energy_score(gc_handle* h, const float* truth, double* d2, double* s0
 int gc_ens_variogram_set(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t n_offsets, const int32_t* offsets, double p) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (n_offsets < 1 || n_offsets > gc::kMvMaxOffsets) return fail(h, GC_ERR_UNSUPPORTED, "n_offsets must be in 1..16");
   const int pk = p == 0.5 ? 0 : p == 1.0 ? 1 : p == 2.0 ? 2 : -1;
   if (pk < 0) return fail(h, GC_ERR_UNSUPPORTED, "the order p must be 0.5, 1 or 2");
@@ -464,16 +444,9 @@ int gc_ens_variogram_set(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t n_o
   const int W = c.batch * c.c_out;
   const size_t blocks = (size_t)gc::loss_reduce_blocks(h->hg.G, c.batch, c.c_out);
   const std::vector<int> offs(offsets, offsets + 2 * O);
-  int rc;
-  if ((rc = dev_upload(h, &h->d_vg_offs, offs, &h->vg_allocs)) ||
-      (rc = dev_alloc(h, &h->d_vg_part, blocks * O * 4 * W, &h->vg_allocs)) ||
-      (rc = dev_alloc(h, &h->d_vg_cpart, blocks * O * W, &h->vg_allocs)) ||
-      (rc = dev_alloc(h, &h->d_vg_out, (size_t)4 * W * O, &h->vg_allocs)) ||
-      (rc = dev_alloc(h, &h->d_vg_outc, (size_t)W * O, &h->vg_allocs))) {
-    h->vg_allocs.free();
+  if (int rc = alloc_all(h, h->vg_allocs, buf(&h->d_vg_offs, offs), buf(&h->d_vg_part, blocks * O * 4 * W),
+                         buf(&h->d_vg_cpart, blocks * O * W), buf(&h->d_vg_out, (size_t)4 * W * O), buf(&h->d_vg_outc, (size_t)W * O)))
     return rc;
-  }
-  GC_HIP(h, h->vg_time.ensure());
   h->vg_O = O;
   h->vg_pk = pk;
   h->vg_n_lat = n_lat;
@@ -486,33 +459,29 @@ int gc_ens_variogram_set(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t n_o
 int gc_ens_variogram_score(gc_handle* h, const float* truth, double* sums, uint64_t* counts) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  int rc = mv_ready(h, h->vg_set, "gc_ens_variogram_set");
-  if (rc) return rc;
-  if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
+  int rc;
+  if ((rc = mv_ready(h, h->vg_set, "no plan (gc_ens_variogram_set)")) || (rc = need_out(h, sums))) return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, h, truth, "gc_ens_variogram_score"))) return rc;
   const gc_config& c = h->cfg;
   const int G = h->hg.G, B = c.batch, W = B * c.c_out, M = h->ens_members, O = h->vg_O;
   const int blocks = gc::loss_reduce_blocks(G, B, c.c_out);
   hipStream_t s = h->stream;
-  GC_HIP(h, h->vg_time.begin(s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_variogram(s, h->vg_pk, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, h->d_vg_offs, O,
-                                         h->vg_n_lat, h->vg_n_lon, B, c.c_out, h->d_vg_part, h->d_vg_cpart);
-       })))
-    return rc;
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_variogram_finish(s, h->d_vg_part, h->d_vg_cpart, blocks, W, O, h->d_vg_out, h->d_vg_outc);
-       })))
-    return rc;
-  GC_HIP(h, h->vg_time.end(s));
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counts are copied out as they lie");
-  GC_HIP(h, hipMemcpyAsync(sums, h->d_vg_out, (size_t)4 * W * O * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (counts) GC_HIP(h, hipMemcpyAsync(counts, h->d_vg_outc, (size_t)W * O * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->vg_time.microseconds(&h->vg_device_us));
-  ++h->vg_calls;
-  return GC_OK;
+  return timed(h, h->vg,
+               [&] {
+                 return launch_each(h,
+                     [&] {
+                       return gc::launch_ens_variogram(s, h->vg_pk, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, h->d_vg_offs, O,
+                                                       h->vg_n_lat, h->vg_n_lon, B, c.c_out, h->d_vg_part, h->d_vg_cpart);
+                     },
+                     [&] { return gc::launch_ens_variogram_finish(s, h->d_vg_part, h->d_vg_cpart, blocks, W, O, h->d_vg_out, h->d_vg_outc); });
+               },
+               [&]() -> int {
+                 if ((rc = read_back(h, sums, h->d_vg_out, (size_t)4 * W * O)) ||
+                     (counts && (rc = read_back(h, counts, h->d_vg_outc, (size_t)W * O))))
+                   return rc;
+                 return GC_OK;
+               });
   });
 }
 

@@ -243,9 +243,8 @@ namespace {
 
 // validation shared by the two passes: a graph, a setting, a complete store
 int ord_ready(gc_handle* h) {
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (!h->ord_set) return fail(h, GC_ERR_STATE, "no probabilities (gc_ens_order_set)");
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
+  int rc;
+  if ((rc = need_graph(h)) || (rc = need(h, h->ord_set, "no probabilities (gc_ens_order_set)")) || (rc = need_store(h))) return rc;
   return store_complete(h, h);
 }
 
@@ -272,7 +271,7 @@ extern "C" {
 int gc_ens_order_set(gc_handle* h, int32_t n_quantiles, const double* probs) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (n_quantiles < 0 || n_quantiles > gc::kOrdMaxQuantiles) return fail(h, GC_ERR_UNSUPPORTED, "n_quantiles must be in 0..8");
   if (n_quantiles > 0 && !probs) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   for (int q = 0; q < n_quantiles; ++q)
@@ -287,7 +286,6 @@ int gc_ens_order_set(gc_handle* h, int32_t n_quantiles, const double* probs) {
     h->d_ord_q = nullptr;
     int rc;
     if ((rc = dev_alloc(h, &h->d_ord_q, (size_t)Q * field_len(h), &h->ord_allocs))) return rc;
-    GC_HIP(h, h->ord_time.ensure());
   }
   for (int q = 0; q < Q; ++q) h->ord_p[q] = probs[q];
   h->ord_Q = Q;
@@ -306,16 +304,15 @@ int gc_ens_order_fields(gc_handle* h) {
   const int G = h->hg.G, W = c.batch * c.c_out, M = h->ens_members;
   const gc::OrdPlan plan = ord_plan(h);
   hipStream_t s = h->stream;
-  GC_HIP(h, h->ord_time.begin(s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_order(s, false, h->d_ens, field_len(h), M, nullptr, nullptr, G, W, plan, h->d_ord_q, nullptr,
-                                     nullptr, nullptr);
-       })))
-    return rc;
-  GC_HIP(h, h->ord_time.end(s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->ord_time.microseconds(&h->ord_device_us));
-  ++h->ord_calls;
+  rc = timed(h, h->ord,
+             [&] {
+               return launch_each(h, [&] {
+                 return gc::launch_ens_order(s, false, h->d_ens, field_len(h), M, nullptr, nullptr, G, W, plan, h->d_ord_q, nullptr,
+                                             nullptr, nullptr);
+               });
+             },
+             no_readbacks);
+  if (rc) return rc;
   h->ord_ready = true;
   return GC_OK;
   });
@@ -327,8 +324,7 @@ int gc_ens_order_score(gc_handle* h, const float* truth, double* bins, double* e
   if (!h) return GC_ERR_INVALID_ARGUMENT;
   int rc = ord_ready(h);
   if (rc) return rc;
-  if (!bins || !extra) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  if (!h->has_ens_w) return fail(h, GC_ERR_STATE, "no node weights (gc_ens_set_node_weight)");
+  if ((rc = need_out(h, bins && extra)) || (rc = need_weights(h))) return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, h, truth, "gc_ens_order_score"))) return rc;
   const gc_config& c = h->cfg;
@@ -336,47 +332,37 @@ int gc_ens_order_score(gc_handle* h, const float* truth, double* bins, double* e
   const int nacc = gc::ord_nacc(M, Q);
   const int blocks = gc::ord_blocks(G, W, M, Q), tiles = gc::ord_tiles(W, gc::ord_cap(M, Q));
   const size_t n_out = (size_t)nacc * W, n_outc = (size_t)(Q + 1) * W + 1;
-  if (h->ord_work_M != M || h->ord_work_Q != Q) {     // sized by M and Q: made again when either changed
-    GC_HIP(h, h->ord_work_allocs.drop(h->stream));
-    h->ord_work_M = 0;
-    h->ord_work_Q = -1;
-    if ((rc = dev_alloc(h, &h->d_ord_part, (size_t)blocks * n_out, &h->ord_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_ord_cpart, (size_t)blocks * (Q + 1) * W + (size_t)blocks * tiles, &h->ord_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_ord_out, n_out, &h->ord_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_ord_outc, n_outc, &h->ord_work_allocs))) {
-      h->ord_work_allocs.free();
-      return rc;
-    }
-    h->ord_work_M = M;
-    h->ord_work_Q = Q;
-  }
+  if ((rc = sized_for(h, h->ord_work_allocs, {(size_t)M, (size_t)Q}, buf(&h->d_ord_part, (size_t)blocks * n_out),
+                      buf(&h->d_ord_cpart, (size_t)blocks * (Q + 1) * W + (size_t)blocks * tiles), buf(&h->d_ord_out, n_out),
+                      buf(&h->d_ord_outc, n_outc))))
+    return rc;
   const gc::OrdPlan plan = ord_plan(h);
   hipStream_t s = h->stream;
   unsigned* const ipart = h->d_ord_cpart + (size_t)blocks * (Q + 1) * W;
-  GC_HIP(h, h->ord_time.begin(s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_order(s, true, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, G, W, plan, h->d_ord_q,
-                                     h->d_ord_part, h->d_ord_cpart, ipart);
-       })))
-    return rc;
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_order_finish(s, h->d_ord_part, h->d_ord_cpart, ipart, blocks, tiles, W, M, Q, h->d_ord_out,
-                                            h->d_ord_outc);
-       })))
-    return rc;
-  GC_HIP(h, h->ord_time.end(s));
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counts are copied out as they lie");
   const size_t n_bins = (size_t)W * 2 * (M + 1), n_extra = (size_t)W * 3;
-  std::vector<unsigned long long> cnt(n_outc);
-  GC_HIP(h, hipMemcpyAsync(bins, h->d_ord_out, n_bins * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(extra, h->d_ord_out + n_bins, n_extra * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (pinball && Q > 0)
-    GC_HIP(h, hipMemcpyAsync(pinball, h->d_ord_out + n_bins + n_extra, (size_t)W * Q * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(cnt.data(), h->d_ord_outc, n_outc * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->ord_time.microseconds(&h->ord_device_us));
-  h->ord_invalid_points = (int64_t)cnt.back();
-  ++h->ord_calls;
+  std::vector<uint64_t> cnt(n_outc);
+  rc = timed(h, h->ord,
+             [&] {
+               return launch_each(h,
+                   [&] {
+                     return gc::launch_ens_order(s, true, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, G, W, plan,
+                                                 h->d_ord_q, h->d_ord_part, h->d_ord_cpart, ipart);
+                   },
+                   [&] {
+                     return gc::launch_ens_order_finish(s, h->d_ord_part, h->d_ord_cpart, ipart, blocks, tiles, W, M, Q, h->d_ord_out,
+                                                        h->d_ord_outc);
+                   });
+             },
+             [&]() -> int {
+               const double* const out = h->d_ord_out;
+               if ((rc = read_back(h, bins, out, n_bins)) || (rc = read_back(h, extra, out + n_bins, n_extra)) ||
+                   (pinball && Q > 0 && (rc = read_back(h, pinball, out + n_bins + n_extra, (size_t)W * Q))) ||
+                   (rc = read_back(h, cnt.data(), h->d_ord_outc, n_outc)))
+                 return rc;
+               return GC_OK;
+             });
+  if (rc) return rc;
+  h->ord.invalid = (int64_t)cnt.back();
   h->ord_ready = true;
   if (counts)
     for (size_t i = 0; i + 1 < cnt.size(); ++i) counts[i] = cnt[i];
@@ -388,7 +374,7 @@ int gc_ens_order_score(gc_handle* h, const float* truth, double* bins, double* e
 int gc_ens_order_download(gc_handle* h, int32_t q, float* field) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (!h->ord_set) return fail(h, GC_ERR_STATE, "no probabilities (gc_ens_order_set)");
   if (!field) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   if (q < 0 || q >= h->ord_Q) return fail(h, GC_ERR_INVALID_ARGUMENT, "q outside [0, n_quantiles)");

@@ -211,24 +211,18 @@ namespace {
 // stays on the host (h->reg_plan), so a store of another M gets its buffers without a new gc_ens_region_set.
 int region_buffers(gc_handle* h, int M) {
   GC_HIP(h, h->reg_allocs.drop(h->stream));          // nothing reads the old ones any more
-  h->reg_dev_M = 0;
   const int W = h->cfg.batch * h->cfg.c_out, R = h->reg_R;
   const size_t blocks = (size_t)h->reg_blocks, tiles = (size_t)(W + 255) / 256, bins = (size_t)M + 1;
   int rc;
-  if ((rc = dev_alloc(h, &h->d_reg_plan, h->reg_plan.size(), &h->reg_allocs)) ||
-      (rc = dev_alloc(h, &h->d_reg_part, blocks * 6 * W, &h->reg_allocs)) ||
-      (rc = dev_alloc(h, &h->d_reg_hpart, blocks * W * bins + blocks * tiles, &h->reg_allocs)) ||
-      (rc = dev_alloc(h, &h->d_reg_sums, (size_t)R * 6 * W, &h->reg_allocs)) ||
-      (rc = dev_alloc(h, &h->d_reg_hist, (size_t)R * W * bins + R, &h->reg_allocs))) {
-    h->reg_allocs.free();
+  if ((rc = alloc_all(h, h->reg_allocs, buf(&h->d_reg_plan, h->reg_plan.size()), buf(&h->d_reg_part, blocks * 6 * W),
+                      buf(&h->d_reg_hpart, blocks * W * bins + blocks * tiles), buf(&h->d_reg_sums, (size_t)R * 6 * W),
+                      buf(&h->d_reg_hist, (size_t)R * W * bins + R))))
     return rc;
-  }
   if (!h->reg_plan.empty()) {
     GC_HIP(h, hipMemcpyAsync(h->d_reg_plan, h->reg_plan.data(), h->reg_plan.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     GC_HIP(h, hipStreamSynchronize(h->stream));
   }
-  GC_HIP(h, h->reg_time.ensure());
-  h->reg_dev_M = M;
+  h->reg_allocs.key = {(size_t)M};                   // (only now: a failed upload leaves buffers the next call replaces)
   return GC_OK;
 }
 
@@ -239,7 +233,7 @@ extern "C" {
 int gc_ens_region_set(gc_handle* h, int32_t n_regions, const uint32_t* node_bits) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (!node_bits) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   if (n_regions < 1 || n_regions > gc::kRegionMax) return fail(h, GC_ERR_UNSUPPORTED, "n_regions must be in 1..32");
   const int G = h->hg.G, R = n_regions;
@@ -273,7 +267,6 @@ int gc_ens_region_set(gc_handle* h, int32_t n_regions, const uint32_t* node_bits
   if (bits.size() > (size_t)gc::kRegionMaxBlocks) return fail(h, GC_ERR_INTERNAL, "the block table is longer than base + atoms");
   GC_HIP(h, hipSetDevice(h->device));
   GC_HIP(h, h->reg_allocs.drop(h->stream));          // the old plan is in force until here
-  h->reg_dev_M = 0;
   h->reg_R = R;
   h->reg_listed = (int)listed;
   h->reg_blocks = (int)bits.size();
@@ -288,49 +281,46 @@ int gc_ens_region_set(gc_handle* h, int32_t n_regions, const uint32_t* node_bits
 int gc_ens_region_score(gc_handle* h, const float* truth, double* sums, uint64_t* hist, uint64_t* invalid) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (h->reg_R == 0) return fail(h, GC_ERR_STATE, "no regions (gc_ens_region_set)");
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = store_complete(h, h);
-  if (rc) return rc;
-  if (!h->has_ens_w) return fail(h, GC_ERR_STATE, "no node weights (gc_ens_set_node_weight)");
+  int rc;
+  if ((rc = need_graph(h)) || (rc = need(h, h->reg_R != 0, "no regions (gc_ens_region_set)")) || (rc = need_store(h)) ||
+      (rc = need_out(h, sums)) || (rc = store_complete(h, h)) || (rc = need_weights(h)))
+    return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, h, truth, "gc_ens_region_score"))) return rc;
   const gc_config& c = h->cfg;
   const int W = c.batch * c.c_out, M = h->ens_members, R = h->reg_R, blocks = h->reg_blocks;
-  if (h->reg_dev_M != M && (rc = region_buffers(h, M))) return rc;   // a store of another M since the plan was set
+  if (h->reg_allocs.differs({(size_t)M}) && (rc = region_buffers(h, M))) return rc;   // a store of another M since the plan was set
   const int* const order = h->d_reg_plan;
   const int* const table = order + h->reg_listed;
   const unsigned* const bits = reinterpret_cast<const unsigned*>(table + 2 * (size_t)blocks);
   unsigned* const ipart = h->d_reg_hpart + (size_t)blocks * W * (M + 1);
   hipStream_t s = h->stream;
-  GC_HIP(h, h->reg_time.begin(s));
-  if (blocks > 0 && (rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_region(s, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, order, table, blocks, W,
-                                      h->d_reg_part, h->d_reg_hpart, ipart);
-       })))
-    return rc;
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_region_finish(s, h->d_reg_part, h->d_reg_hpart, ipart, bits, blocks, R, W, M, h->d_reg_sums,
-                                             h->d_reg_hist);
-       })))
-    return rc;
-  GC_HIP(h, h->reg_time.end(s));
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counts are copied out as they lie");
   const size_t n_hist = (size_t)R * W * (M + 1);
-  std::vector<unsigned long long> out(n_hist + R);
-  GC_HIP(h, hipMemcpyAsync(sums, h->d_reg_sums, (size_t)R * 6 * W * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(out.data(), h->d_reg_hist, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->reg_time.microseconds(&h->reg_device_us));
+  std::vector<uint64_t> out(n_hist + R);
+  rc = timed(h, h->reg,
+             [&]() -> int {
+               if (blocks > 0 && (rc = launch_each(h, [&] {
+                     return gc::launch_ens_region(s, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, order, table, blocks, W,
+                                                  h->d_reg_part, h->d_reg_hpart, ipart);
+                   })))
+                 return rc;
+               return launch_each(h, [&] {
+                 return gc::launch_ens_region_finish(s, h->d_reg_part, h->d_reg_hpart, ipart, bits, blocks, R, W, M, h->d_reg_sums,
+                                                     h->d_reg_hist);
+               });
+             },
+             [&]() -> int {
+               if ((rc = read_back(h, sums, h->d_reg_sums, (size_t)R * 6 * W)) || (rc = read_back(h, out.data(), h->d_reg_hist, out.size())))
+                 return rc;
+               return GC_OK;
+             });
+  if (rc) return rc;
   int64_t total = 0;
   for (int r = 0; r < R; ++r) {
     total += (int64_t)out[n_hist + r];
     if (invalid) invalid[r] = out[n_hist + r];
   }
-  h->reg_invalid_points = total;
-  ++h->reg_calls;
+  h->reg.invalid = total;
   if (hist)
     for (size_t i = 0; i < n_hist; ++i) hist[i] = out[i];
   return GC_OK;

@@ -337,9 +337,8 @@ namespace {
 size_t spec_set_len(const gc_handle* h) { return (size_t)2 * h->sp_L * h->sp_L * h->cfg.batch * h->cfg.c_out; }
 
 int spec_ready(gc_handle* h) {
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (h->sp_L == 0) return fail(h, GC_ERR_STATE, "no analysis tables (gc_spec_set_tables)");
-  return GC_OK;
+  const int rc = need_graph(h);
+  return rc ? rc : need(h, h->sp_L != 0, "no analysis tables (gc_spec_set_tables)");
 }
 
 // The buffers sized by the number of coefficient sets a call keeps: made again when a call needs more than there are.
@@ -348,23 +347,18 @@ int spec_reserve_sets(gc_handle* h, int sets) {
   GC_HIP(h, h->spec_work_allocs.drop(h->stream));
   h->sp_sets = 0;
   const size_t out = (size_t)h->cfg.batch * h->cfg.c_out * h->sp_L;
-  int rc;
-  if ((rc = dev_alloc(h, &h->d_sp_coef, (size_t)sets * spec_set_len(h), &h->spec_work_allocs)) ||
-      (rc = dev_alloc(h, &h->d_sp_out, (size_t)(6 + sets) * out, &h->spec_work_allocs))) {
-    h->spec_work_allocs.free();
+  if (int rc = alloc_all(h, h->spec_work_allocs, buf(&h->d_sp_coef, (size_t)sets * spec_set_len(h)),
+                         buf(&h->d_sp_out, (size_t)(6 + sets) * out)))
     return rc;
-  }
   h->sp_sets = sets;
   return GC_OK;
 }
 
-int spec_finish(gc_handle* h, const std::vector<unsigned>& flags) {
-  GC_HIP(h, h->spec_time.microseconds(&h->spec_device_us));
+// columns with a value that was not finite
+int64_t flagged(const std::vector<unsigned>& flags) {
   int64_t bad = 0;
   for (unsigned f : flags) bad += f ? 1 : 0;
-  h->spec_invalid_columns = bad;
-  ++h->spec_calls;
-  return GC_OK;
+  return bad;
 }
 
 }  // namespace
@@ -375,7 +369,7 @@ int gc_spec_set_tables(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t lmax,
                        const float* cos_a, const float* sin_a) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (!legendre_analysis || !cos_a || !sin_a) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   if (n_lat < 2 || n_lon < 2 || (int64_t)n_lat * n_lon != h->hg.G)
     return fail(h, GC_ERR_INVALID_ARGUMENT, "n_lat * n_lon must equal the number of grid nodes");
@@ -388,22 +382,14 @@ int gc_spec_set_tables(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t lmax,
   h->band_allocs.free();                           // a band plan is made for the grid and the band limit of the tables: it goes with them
   h->band_work_allocs.free();
   h->band_set = false;
-  h->band_work_key[0] = h->band_work_key[1] = 0;
   h->sp_L = h->sp_sets = 0;
   const size_t L = (size_t)lmax;
   std::vector<float> tab(2 * L * n_lon);
   std::copy(cos_a, cos_a + L * n_lon, tab.begin());
   std::copy(sin_a, sin_a + L * n_lon, tab.begin() + L * n_lon);
-  int rc;
-  if ((rc = dev_upload(h, &h->d_sp_q, std::vector<float>(legendre_analysis, legendre_analysis + L * L * n_lat), &h->spec_allocs)) ||
-      (rc = dev_upload(h, &h->d_sp_tab, tab, &h->spec_allocs)) ||
-      (rc = dev_alloc(h, &h->d_sp_F, 2 * L * n_lat * N, &h->spec_allocs)) ||
-      (rc = dev_alloc(h, &h->d_sp_field, field_len(h), &h->spec_allocs)) ||
-      (rc = dev_alloc(h, &h->d_sp_flags, (size_t)N, &h->spec_allocs))) {
-    h->spec_allocs.free();
+  if (int rc = alloc_all(h, h->spec_allocs, buf(&h->d_sp_q, L * L * n_lat, legendre_analysis), buf(&h->d_sp_tab, tab),
+                         buf(&h->d_sp_F, 2 * L * n_lat * N), buf(&h->d_sp_field, field_len(h)), buf(&h->d_sp_flags, (size_t)N)))
     return rc;
-  }
-  GC_HIP(h, h->spec_time.ensure());
   h->sp_L = lmax; h->sp_lat = n_lat; h->sp_lon = n_lon;
   return GC_OK;
   });
@@ -412,10 +398,10 @@ int gc_spec_set_tables(gc_handle* h, int32_t n_lat, int32_t n_lon, int32_t lmax,
 int gc_spec_field(gc_handle* h, const float* field, double* power) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  int rc = spec_ready(h);
-  if (rc) return rc;
-  if (!power) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  if (!field && (!h->finalized || !h->has_sample)) return fail(h, GC_ERR_STATE, "no sample on the device (gc_sample_resident)");
+  int rc;
+  if ((rc = spec_ready(h)) || (rc = need_out(h, power)) ||
+      (rc = need(h, field || (h->finalized && h->has_sample), "no sample on the device (gc_sample_resident)")))
+    return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if (!field && (rc = resolve_guard(h))) return rc;   // the spectrum is of the CHECKED sample (exact-f32 re-run included)
   if ((rc = spec_reserve_sets(h, 1))) return rc;
@@ -423,32 +409,33 @@ int gc_spec_field(gc_handle* h, const float* field, double* power) {
   const int L = h->sp_L, N = h->cfg.batch * h->cfg.c_out;
   hipStream_t s = h->stream;
   const float* src = field ? h->d_sp_field : h->d_sx;
-  GC_HIP(h, h->spec_time.begin(s));
-  GC_HIP(h, hipMemsetAsync(h->d_sp_flags, 0, (size_t)N * sizeof(unsigned), s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_spec_analysis(s, src, h->d_sp_tab, h->d_sp_q, L, h->sp_lat, h->sp_lon, N, h->d_sp_F, h->d_sp_coef,
-                                         h->d_sp_flags);
-       })))
-    return rc;
-  if ((rc = launch(h, gc::KC_PACK, [&] { return gc::launch_spec_power(s, h->d_sp_coef, h->d_sp_flags, L, N, h->d_sp_out); })))
-    return rc;
-  GC_HIP(h, h->spec_time.end(s));
   std::vector<unsigned> flags((size_t)N);
-  GC_HIP(h, hipMemcpyAsync(power, h->d_sp_out, (size_t)N * L * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(flags.data(), h->d_sp_flags, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  return spec_finish(h, flags);
+  rc = timed(h, h->spec,
+             [&]() -> int {
+               GC_HIP(h, hipMemsetAsync(h->d_sp_flags, 0, (size_t)N * sizeof(unsigned), s));
+               return launch_each(h,
+                   [&] {
+                     return gc::launch_spec_analysis(s, src, h->d_sp_tab, h->d_sp_q, L, h->sp_lat, h->sp_lon, N, h->d_sp_F, h->d_sp_coef,
+                                                     h->d_sp_flags);
+                   },
+                   [&] { return gc::launch_spec_power(s, h->d_sp_coef, h->d_sp_flags, L, N, h->d_sp_out); });
+             },
+             [&]() -> int {
+               if ((rc = read_back(h, power, h->d_sp_out, (size_t)N * L)) || (rc = read_back(h, flags.data(), h->d_sp_flags, flags.size())))
+                 return rc;
+               return GC_OK;
+             });
+  if (rc) return rc;
+  h->spec.invalid = flagged(flags);
+  return GC_OK;
   });
 }
 
 int gc_ens_spectrum(gc_handle* h, const float* truth, double* sums, double* member_power) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  int rc = spec_ready(h);
-  if (rc) return rc;
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  if ((rc = store_complete(h, h))) return rc;
+  int rc;
+  if ((rc = spec_ready(h)) || (rc = need_store(h)) || (rc = need_out(h, sums)) || (rc = store_complete(h, h))) return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, h, truth, "gc_ens_spectrum"))) return rc;
   const int M = h->ens_members;
@@ -459,28 +446,33 @@ int gc_ens_spectrum(gc_handle* h, const float* truth, double* sums, double* memb
   hipStream_t s = h->stream;
   double* const d_sums = h->d_sp_out;
   double* const d_mp = h->d_sp_out + 6 * plane;
-  GC_HIP(h, h->spec_time.begin(s));
-  GC_HIP(h, hipMemsetAsync(h->d_sp_flags, 0, (size_t)N * sizeof(unsigned), s));
-  // one field at a time through the Fourier scratch; set 0 = truth, 1 + i = member i, M + 1 = the mean coefficients
-  for (int k = 0; k <= M; ++k) {
-    const float* src = k == 0 ? h->d_ens_truth : h->d_ens + (size_t)(k - 1) * field;
-    if ((rc = launch(h, gc::KC_PACK, [&] {
-           return gc::launch_spec_analysis(s, src, h->d_sp_tab, h->d_sp_q, L, h->sp_lat, h->sp_lon, N, h->d_sp_F,
-                                           h->d_sp_coef + (size_t)k * set, h->d_sp_flags);
-         })))
-      return rc;
-  }
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_spec_ens(s, h->d_sp_coef, set, M, h->d_sp_flags, L, N, d_sums, member_power ? d_mp : nullptr);
-       })))
-    return rc;
-  GC_HIP(h, h->spec_time.end(s));
   std::vector<unsigned> flags((size_t)N);
-  GC_HIP(h, hipMemcpyAsync(sums, d_sums, 6 * plane * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (member_power) GC_HIP(h, hipMemcpyAsync(member_power, d_mp, (size_t)M * plane * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(flags.data(), h->d_sp_flags, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  return spec_finish(h, flags);
+  rc = timed(h, h->spec,
+             [&]() -> int {
+               GC_HIP(h, hipMemsetAsync(h->d_sp_flags, 0, (size_t)N * sizeof(unsigned), s));
+               // one field at a time through the Fourier scratch; set 0 = truth, 1 + i = member i, M + 1 = the mean coefficients
+               for (int k = 0; k <= M; ++k) {
+                 const float* src = k == 0 ? h->d_ens_truth : h->d_ens + (size_t)(k - 1) * field;
+                 if ((rc = launch_each(h, [&] {
+                       return gc::launch_spec_analysis(s, src, h->d_sp_tab, h->d_sp_q, L, h->sp_lat, h->sp_lon, N, h->d_sp_F,
+                                                       h->d_sp_coef + (size_t)k * set, h->d_sp_flags);
+                     })))
+                   return rc;
+               }
+               return launch_each(h, [&] {
+                 return gc::launch_spec_ens(s, h->d_sp_coef, set, M, h->d_sp_flags, L, N, d_sums, member_power ? d_mp : nullptr);
+               });
+             },
+             [&]() -> int {
+               if ((rc = read_back(h, sums, d_sums, 6 * plane)) ||
+                   (member_power && (rc = read_back(h, member_power, d_mp, (size_t)M * plane))) ||
+                   (rc = read_back(h, flags.data(), h->d_sp_flags, flags.size())))
+                 return rc;
+               return GC_OK;
+             });
+  if (rc) return rc;
+  h->spec.invalid = flagged(flags);
+  return GC_OK;
   });
 }
 
@@ -535,7 +527,6 @@ int gc_ens_band_set(gc_handle* h, int32_t c_src, int32_t n_bands, const double* 
   h->band_set = false;
   double* d_blob = nullptr;
   if ((rc = dev_alloc(h, &d_blob, blob.size(), &h->band_allocs))) return rc;
-  GC_HIP(h, h->band_time.ensure());
   GC_HIP(h, h->ev_band_src.ensure());
   if ((rc = store_upload(h, d_blob, blob.data(), blob.size() * sizeof(double)))) return rc;
   h->d_band_resp = d_blob;
@@ -557,65 +548,39 @@ int gc_ens_band_set(gc_handle* h, int32_t c_src, int32_t n_bands, const double* 
 int gc_ens_band(gc_handle* h, gc_handle* src, const float* truth) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!src || src == h) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source must be another handle");
-  int rc = spec_ready(h);
-  if (rc) return rc;
-  if (!h->band_set) return fail(h, GC_ERR_STATE, "no plan (gc_ens_band_set)");
-  if ((rc = check_peer(h, src, "source", false, h->band_c_src, "c_out == c_src of the plan"))) return rc;
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  if (src->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store on the source handle (gc_ens_reserve)");
-  if (src->ens_members != h->ens_members) return fail(h, GC_ERR_STATE, "the two member stores hold different numbers of members");
-  if ((rc = store_complete(h, src, "source "))) return rc;
-  GC_HIP(h, hipSetDevice(h->device));
-  if ((rc = take_truth(h, src, truth, "gc_ens_band"))) return rc;   // into the source's truth buffer, as gc_ens_derive does
+  int rc;
+  if ((rc = need_source(h, src)) || (rc = spec_ready(h)) || (rc = need(h, h->band_set, "no plan (gc_ens_band_set)"))) return rc;
   const int B = h->cfg.batch, c_d = h->cfg.c_out, M = h->ens_members, nu = h->band_nu;
   const size_t L = (size_t)h->sp_L, n_lat = (size_t)h->sp_lat, Nu = (size_t)B * nu, Nd = (size_t)B * c_d;
   const size_t field = field_len(h), sfield = field_len(src);
-  if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
-  if (h->band_work_key[0] != Nu || h->band_work_key[1] != (size_t)M + 1) {   // the scratch of ONE field, and the flags of all
-    GC_HIP(h, h->band_work_allocs.drop(h->stream));
-    h->band_work_key[0] = h->band_work_key[1] = 0;
-    if ((rc = dev_alloc(h, &h->d_band_gather, (size_t)h->hg.G * Nu, &h->band_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_band_F, 2 * L * n_lat * Nu, &h->band_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_band_coef, 2 * L * L * Nu, &h->band_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_band_G, 2 * L * n_lat * Nd, &h->band_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_band_flags, ((size_t)M + 1) * Nu, &h->band_work_allocs))) {
-      h->band_work_allocs.free();
-      return rc;
-    }
-    h->band_work_key[0] = Nu;
-    h->band_work_key[1] = (size_t)M + 1;
-  }
+  rc = fill_open(h, src, h->band_c_src, truth, "gc_ens_band", h->ev_band_src, [&] {   // the scratch of ONE field, and the flags of all
+    return sized_for(h, h->band_work_allocs, {Nu, (size_t)M + 1}, buf(&h->d_band_gather, (size_t)h->hg.G * Nu),
+                     buf(&h->d_band_F, 2 * L * n_lat * Nu), buf(&h->d_band_coef, 2 * L * L * Nu), buf(&h->d_band_G, 2 * L * n_lat * Nd),
+                     buf(&h->d_band_flags, ((size_t)M + 1) * Nu));
+  });
+  if (rc) return rc;
   hipStream_t s = h->stream;
-  // the source's store and truth are complete on ITS stream: this handle's stream goes on behind them
-  if ((rc = order_behind(h, h->ev_band_src, src->stream, s))) return rc;
-  h->evt_scored = false;
-  h->has_ens_fields = false;
-  h->ord_ready = false;
   const gc::BandPlan p{h->d_band_resp, h->d_band_leg, h->d_band_tab, h->d_band_comp, h->d_band_chan, h->d_band_of, h->d_band_ucol,
                        h->d_band_ulist, h->sp_L, h->sp_lat, h->sp_lon, B, src->cfg.c_out, c_d, nu, h->d_band_gather, h->d_band_F,
                        h->d_band_coef, h->d_band_G};
-  GC_HIP(h, h->band_time.begin(s));
-  GC_HIP(h, hipMemsetAsync(h->d_band_flags, 0, ((size_t)M + 1) * Nu * sizeof(unsigned), s));
-  for (int z = 0; z <= M; ++z) {                     // the M members, then the truth: one field at a time through the scratch
-    const float* from = z < M ? src->d_ens + (size_t)z * sfield : src->d_ens_truth;
-    float* to = z < M ? h->d_ens + (size_t)z * field : h->d_ens_truth;
-    if ((rc = launch(h, gc::KC_PACK, [&] {
-           return gc::launch_band_field(s, p, h->d_sp_tab, h->d_sp_q, from, to, h->d_band_flags + (size_t)z * Nu);
-         })))
-      return rc;
-  }
-  GC_HIP(h, h->band_time.end(s));
   std::vector<unsigned> flags(((size_t)M + 1) * Nu);
-  GC_HIP(h, hipMemcpyAsync(flags.data(), h->d_band_flags, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->band_time.microseconds(&h->band_device_us));
-  int64_t bad = 0;
-  for (unsigned f : flags) bad += f ? 1 : 0;
-  h->band_invalid_columns = bad;
-  std::fill(h->ens_filled.begin(), h->ens_filled.end(), 1);
-  h->has_ens_truth = true;
-  ++h->band_calls;
+  rc = timed(h, h->band,
+             [&]() -> int {
+               GC_HIP(h, hipMemsetAsync(h->d_band_flags, 0, ((size_t)M + 1) * Nu * sizeof(unsigned), s));
+               for (int z = 0; z <= M; ++z) {        // the M members, then the truth: one field at a time through the scratch
+                 const float* from = z < M ? src->d_ens + (size_t)z * sfield : src->d_ens_truth;
+                 float* to = z < M ? h->d_ens + (size_t)z * field : h->d_ens_truth;
+                 if ((rc = launch_each(h, [&] {
+                       return gc::launch_band_field(s, p, h->d_sp_tab, h->d_sp_q, from, to, h->d_band_flags + (size_t)z * Nu);
+                     })))
+                   return rc;
+               }
+               return GC_OK;
+             },
+             [&] { return read_back(h, flags.data(), h->d_band_flags, flags.size()); });
+  if (rc) return rc;
+  h->band.invalid = flagged(flags);
+  fill_close(h);
   return GC_OK;
   });
 }

@@ -199,7 +199,7 @@ extern "C" {
 int gc_ens_tail_set(gc_handle* h, int32_t n_thresholds, const float* thresholds, const int32_t* direction) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (!thresholds || !direction) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
   if (n_thresholds < 1 || n_thresholds > gc::kTailMaxThresholds) return fail(h, GC_ERR_UNSUPPORTED, "n_thresholds must be in 1..8");
   unsigned up = 0;
@@ -216,7 +216,6 @@ int gc_ens_tail_set(gc_handle* h, int32_t n_thresholds, const float* thresholds,
     h->tail_T = 0;
     h->d_tail_thr = nullptr;
     if ((rc = dev_alloc(h, &h->d_tail_thr, (size_t)T * field, &h->tail_allocs))) return rc;
-    GC_HIP(h, h->tail_time.ensure());
   }
   // on the handle's stream, behind whatever still reads the old values; the caller's arrays are free on return
   for (int t = 0; t < T; ++t)
@@ -231,49 +230,36 @@ int gc_ens_tail_set(gc_handle* h, int32_t n_thresholds, const float* thresholds,
 int gc_ens_tail_score(gc_handle* h, const float* truth, double* sums, uint64_t* counts, uint64_t* invalid) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (h->tail_T == 0) return fail(h, GC_ERR_STATE, "no thresholds (gc_ens_tail_set)");
-  if (h->ens_members == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  if (!sums) return fail(h, GC_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = store_complete(h, h);
-  if (rc) return rc;
-  if (!h->has_ens_w) return fail(h, GC_ERR_STATE, "no node weights (gc_ens_set_node_weight)");
+  int rc;
+  if ((rc = need_graph(h)) || (rc = need(h, h->tail_T != 0, "no thresholds (gc_ens_tail_set)")) || (rc = need_store(h)) ||
+      (rc = need_out(h, sums)) || (rc = store_complete(h, h)) || (rc = need_weights(h)))
+    return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, h, truth, "gc_ens_tail_score"))) return rc;
   const gc_config& c = h->cfg;
   const int G = h->hg.G, W = c.batch * c.c_out, M = h->ens_members, T = h->tail_T;
   const int blocks = gc::tail_blocks(G, W);
   const size_t n_out = (size_t)4 * T * W, n_outc = (size_t)T * W;
-  if (h->tail_work_T != T) {                          // sized by T (the layout does not depend on M): made again when T changed
-    GC_HIP(h, h->tail_work_allocs.drop(h->stream));
-    h->tail_work_T = 0;
-    if ((rc = dev_alloc(h, &h->d_tail_part, (size_t)blocks * n_out, &h->tail_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_tail_cpart, (size_t)blocks * n_outc, &h->tail_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_tail_out, n_out, &h->tail_work_allocs)) ||
-        (rc = dev_alloc(h, &h->d_tail_outc, n_outc, &h->tail_work_allocs))) {
-      h->tail_work_allocs.free();
-      return rc;
-    }
-    h->tail_work_T = T;
-  }
+  // sized by T (the layout does not depend on M)
+  if ((rc = sized_for(h, h->tail_work_allocs, {(size_t)T}, buf(&h->d_tail_part, (size_t)blocks * n_out),
+                      buf(&h->d_tail_cpart, (size_t)blocks * n_outc), buf(&h->d_tail_out, n_out), buf(&h->d_tail_outc, n_outc))))
+    return rc;
   hipStream_t s = h->stream;
-  GC_HIP(h, h->tail_time.begin(s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_tail(s, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, h->d_tail_thr, T, h->tail_dir_up, G,
-                                    W, h->d_tail_part, h->d_tail_cpart);
-       })))
-    return rc;
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_tail_finish(s, h->d_tail_part, h->d_tail_cpart, blocks, T, W, h->d_tail_out, h->d_tail_outc);
-       })))
-    return rc;
-  GC_HIP(h, h->tail_time.end(s));
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counts are copied out as they lie");
-  std::vector<unsigned long long> cnt(n_outc);
-  GC_HIP(h, hipMemcpyAsync(sums, h->d_tail_out, n_out * sizeof(double), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipMemcpyAsync(cnt.data(), h->d_tail_outc, n_outc * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->tail_time.microseconds(&h->tail_device_us));
+  std::vector<uint64_t> cnt(n_outc);
+  rc = timed(h, h->tail,
+             [&] {
+               return launch_each(h,
+                   [&] {
+                     return gc::launch_ens_tail(s, h->d_ens, field_len(h), M, h->d_ens_truth, h->d_ens_w, h->d_tail_thr, T,
+                                                h->tail_dir_up, G, W, h->d_tail_part, h->d_tail_cpart);
+                   },
+                   [&] { return gc::launch_ens_tail_finish(s, h->d_tail_part, h->d_tail_cpart, blocks, T, W, h->d_tail_out, h->d_tail_outc); });
+             },
+             [&]() -> int {
+               if ((rc = read_back(h, sums, h->d_tail_out, n_out)) || (rc = read_back(h, cnt.data(), h->d_tail_outc, n_outc))) return rc;
+               return GC_OK;
+             });
+  if (rc) return rc;
   // every point of the field is counted or skipped: the skipped ones are what the counts leave
   int64_t total = 0;
   for (int t = 0; t < T; ++t) {
@@ -283,8 +269,7 @@ int gc_ens_tail_score(gc_handle* h, const float* truth, double* sums, uint64_t* 
     total += (int64_t)skipped;
     if (invalid) invalid[t] = skipped;
   }
-  h->tail_invalid_points = total;
-  ++h->tail_calls;
+  h->tail.invalid = total;
   if (counts)
     for (size_t i = 0; i < cnt.size(); ++i) counts[i] = cnt[i];
   return GC_OK;

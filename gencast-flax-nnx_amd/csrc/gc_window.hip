@@ -114,7 +114,7 @@ extern "C" {
 int gc_ens_window_set(gc_handle* h, int32_t kind, int32_t length, const double* coef) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
+  if (int rc = need_graph(h)) return rc;
   if (kind < gc::kWinLinear || kind > gc::kWinMin) return fail(h, GC_ERR_UNSUPPORTED, "kind must be 0 (linear), 1 (max) or 2 (min)");
   if (length < 1) return fail(h, GC_ERR_INVALID_ARGUMENT, "length must be at least 1");
   if (length > gc::kWinMaxLength) return fail(h, GC_ERR_UNSUPPORTED, "length must be at most 64");
@@ -127,7 +127,6 @@ int gc_ens_window_set(gc_handle* h, int32_t kind, int32_t length, const double* 
   int rc;
   if (!h->d_win_coef) {                              // 64 doubles, made once
     if ((rc = dev_alloc(h, &h->d_win_coef, (size_t)gc::kWinMaxLength))) return rc;
-    GC_HIP(h, h->win_time.ensure());
     GC_HIP(h, h->ev_win_src.ensure());
   }
   h->win_set = false;
@@ -145,28 +144,21 @@ int gc_ens_window_set(gc_handle* h, int32_t kind, int32_t length, const double* 
 int gc_ens_window_push(gc_handle* h, gc_handle* src, const float* truth) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!src || src == h) return fail(h, GC_ERR_INVALID_ARGUMENT, "the source must be another handle");
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (!h->win_set) return fail(h, GC_ERR_STATE, "no plan (gc_ens_window_set)");
-  int rc = check_peer(h, src, "source", false, h->cfg.c_out);
-  if (rc) return rc;
+  int rc;
+  if ((rc = need_source(h, src)) || (rc = need_graph(h)) || (rc = need(h, h->win_set, "no plan (gc_ens_window_set)")) ||
+      (rc = check_peer(h, src, "source", false, h->cfg.c_out)))
+    return rc;
   const int M = src->ens_members, L = h->win_L;
-  if (M == 0) return fail(h, GC_ERR_STATE, "no member store on the source handle (gc_ens_reserve)");
-  if (h->win_pushes > 0 && M != h->win_ring_M)
-    return fail(h, GC_ERR_STATE, "the source holds " + std::to_string(M) + " members, the ring " + std::to_string(h->win_ring_M) +
+  const size_t ring_M = h->win_allocs.key[1];
+  if ((rc = need(h, M != 0, "no member store on the source handle (gc_ens_reserve)"))) return rc;
+  if (h->win_pushes > 0 && (size_t)M != ring_M)
+    return fail(h, GC_ERR_STATE, "the source holds " + std::to_string(M) + " members, the ring " + std::to_string(ring_M) +
                                      " (gc_ens_window_reset first)");
   if ((rc = store_complete(h, src, "source "))) return rc;
   GC_HIP(h, hipSetDevice(h->device));
   if ((rc = take_truth(h, src, truth, "gc_ens_window_push"))) return rc;   // into the source's truth buffer, as gc_ens_derive does
   const size_t field = field_len(h), stride = win_stride(h, M);
-  if (!h->d_win_ring || h->win_ring_L != L || h->win_ring_M != M) {     // sized by L and M: made again only when they change
-    GC_HIP(h, h->win_allocs.drop(h->stream));
-    h->d_win_ring = nullptr;
-    h->win_ring_L = h->win_ring_M = 0;
-    if ((rc = dev_alloc(h, &h->d_win_ring, (size_t)L * stride, &h->win_allocs))) return rc;
-    h->win_ring_L = L;
-    h->win_ring_M = M;
-  }
+  if ((rc = sized_for(h, h->win_allocs, {(size_t)L, (size_t)M}, buf(&h->d_win_ring, (size_t)L * stride)))) return rc;
   hipStream_t s = h->stream;
   // the source's store and truth are complete on ITS stream: this handle's stream goes on behind them
   if ((rc = order_behind(h, h->ev_win_src, src->stream, s))) return rc;
@@ -182,35 +174,30 @@ int gc_ens_window_push(gc_handle* h, gc_handle* src, const float* truth) {
 int gc_ens_window_emit(gc_handle* h) {
   return guarded(h, [&]() -> int {
   if (!h) return GC_ERR_INVALID_ARGUMENT;
-  if (!h->has_graph) return fail(h, GC_ERR_STATE, "gc_set_graph must be called first");
-  if (!h->win_set) return fail(h, GC_ERR_STATE, "no plan (gc_ens_window_set)");
+  int rc;
+  if ((rc = need_graph(h)) || (rc = need(h, h->win_set, "no plan (gc_ens_window_set)"))) return rc;
   const int L = h->win_L, M = h->ens_members;
   if (h->win_pushes < L)
     return fail(h, GC_ERR_STATE, "the window needs " + std::to_string(L) + " pushes, the ring holds " + std::to_string(h->win_pushes));
-  if (M == 0) return fail(h, GC_ERR_STATE, "no member store (gc_ens_reserve)");
-  if (M != h->win_ring_M || L != h->win_ring_L)
-    return fail(h, GC_ERR_STATE, "the member store holds " + std::to_string(M) + " members, the ring " + std::to_string(h->win_ring_M));
+  if ((rc = need_store(h))) return rc;
+  if (h->win_allocs.differs({(size_t)L, (size_t)M}))
+    return fail(h, GC_ERR_STATE, "the member store holds " + std::to_string(M) + " members, the ring " + std::to_string(h->win_allocs.key[1]));
   GC_HIP(h, hipSetDevice(h->device));
-  int rc;
   const size_t field = field_len(h), stride = win_stride(h, M);
-  if (!h->d_ens_truth && (rc = dev_alloc(h, &h->d_ens_truth, field))) return rc;
+  if ((rc = own_truth_buffer(h))) return rc;             // the source here is the ring: of fill_open, the parts that apply
   hipStream_t s = h->stream;
-  h->evt_scored = false;
-  h->has_ens_fields = false;
-  h->ord_ready = false;
+  store_rewritten(h);
   const int start = (int)((h->win_pushes - L) % L);
-  GC_HIP(h, h->win_time.begin(s));
-  if ((rc = launch(h, gc::KC_PACK, [&] {
-         return gc::launch_ens_window(s, h->win_kind, h->d_win_ring, stride, L, start, h->d_win_coef, h->d_ens, h->d_ens_truth,
-                                      (size_t)M * field, (size_t)(M + 1) * field);
-       })))
-    return rc;
-  GC_HIP(h, h->win_time.end(s));
-  GC_HIP(h, hipStreamSynchronize(s));
-  GC_HIP(h, h->win_time.microseconds(&h->win_device_us));
-  std::fill(h->ens_filled.begin(), h->ens_filled.end(), 1);
-  h->has_ens_truth = true;
-  ++h->win_emits;
+  rc = timed(h, h->win,
+             [&] {
+               return launch_each(h, [&] {
+                 return gc::launch_ens_window(s, h->win_kind, h->d_win_ring, stride, L, start, h->d_win_coef, h->d_ens, h->d_ens_truth,
+                                              (size_t)M * field, (size_t)(M + 1) * field);
+               });
+             },
+             no_readbacks);
+  if (rc) return rc;
+  fill_close(h);
   return GC_OK;
   });
 }

@@ -941,3 +941,225 @@ def test_one_degree_fp16_rollout_two_steps_compose_as_the_oracle_says():
       assert err < 2e-6 * scale
   assert all(bool(np.isfinite(np.asarray(v.data)).all()) for v in preds.data_vars.values())
   nd.close()
+
+
+# ---- the host protocol of the ensemble scorers: counter names and the order of the checks -------------------------------
+
+# every name gc_get_counter knows, but for device_allocations and noise_stream
+COUNTERS = (
+    "range_fallbacks", "static_embedding_fallbacks", "launches_per_call", "weights_f16_unsafe", "fp16_storage", "split_edge",
+    "attention_items", "m2g_fused_sum", "embed_cache", "edge_term_samples", "edge_term_cache_bytes", "graph_replays",
+    "graph_captures", "loss_evaluations", "loss_device_us",
+    "ens_scores", "ens_score_device_us", "ens_invalid_points",
+    "spec_calls", "spec_device_us", "spec_invalid_columns",
+    "ens_event_calls", "ens_event_device_us", "ens_event_invalid_points",
+    "ens_derive_calls", "ens_derive_device_us",
+    "ens_band_calls", "ens_band_device_us", "ens_band_invalid_columns",
+    "ens_order_calls", "ens_order_device_us", "ens_order_invalid_points",
+    "ens_clim_calls", "ens_clim_device_us", "ens_clim_invalid_points",
+    "ens_energy_calls", "ens_energy_device_us", "ens_energy_invalid_points",
+    "ens_variogram_calls", "ens_variogram_device_us",
+    "ens_tail_calls", "ens_tail_device_us", "ens_tail_invalid_points",
+    "ens_region_calls", "ens_region_device_us", "ens_region_invalid_points",
+    "ens_feature_calls", "ens_feature_device_us",
+    "ens_fss_calls", "ens_fss_device_us",
+    "ens_window_pushes", "ens_window_emits", "ens_window_device_us", "ens_window_ring_bytes")
+FRESH_ALLOCATIONS = 51        # device buffers of a graph-only handle on the 13 x 24 grid (B = 1, c_out = 2): those of gc_set_graph
+
+
+def test_every_counter_name_reads_zero_on_a_fresh_handle_and_other_names_are_refused():
+  """gc_get_counter on a handle that knows its graph and nothing else: every public name reads 0, `device_allocations` counts
+  the buffers of gc_set_graph, and a scorer that keeps no `invalid` counter has no such name."""
+  nd = helpers.graph_handle(helpers.small_graph(), 1, 2)
+  try:
+    for name in COUNTERS:
+      assert nd.counter(name) == 0, name
+    assert nd.counter("noise_stream") == 0
+    assert nd.counter("device_allocations") == FRESH_ALLOCATIONS
+    for name in ("ens_variogram_invalid_points", "ens_derive_invalid_points", "ens_fss_invalid_points",
+                 "ens_feature_invalid_points", "ens_tail", "no_such_counter"):
+      with pytest.raises(ValueError, match="unknown counter"):
+        nd.counter(name)
+  finally:
+    nd.close()
+
+
+def test_the_order_of_the_checks_of_every_scoring_and_filling_entry():
+  """Two faults at once, at every rung of the state ladder (graph only -> plans set -> store reserved -> one slot unpushed ->
+  all pushed, no weights -> weights, no truth): the rung's state fault and a null required output (for the entries that fill
+  a store from another handle, which have no output: a source of other dimensions, and a source whose own ladder is behind).
+  Which of the two is reported is the order of the checks in the entry: (return code, a fragment of gc_last_error) below,
+  as recorded before the scorers shared their host code.  Every call ends in a host-side refusal; nothing is launched."""
+  import ctypes
+  from gencast_flax_nnx_amd import _lib
+  lib = _lib.load_library()
+  ST, ARG = _lib.GC_ERR_STATE, _lib.GC_ERR_INVALID_ARGUMENT
+  gr = helpers.small_graph()
+  G, B, C, M = gr.num_grid_nodes, 1, 2, 2
+  n_lat, n_lon, L = 13, 24, 2
+  h, src, clim = (helpers.graph_handle(gr, B, C) for _ in range(3))
+  bad = helpers.graph_handle(gr, B, C + 1)                               # a peer of other dimensions
+  buf = np.zeros(4096)                                                   # stands for any output: nothing is ever written
+  dp, up, fp = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_float)
+  D, U, F = buf.ctypes.data_as(dp), buf.ctypes.data_as(up), buf.ctypes.data_as(fp)
+  p = h._h
+  null = {                                                               # every output null
+      "score": lambda: lib.gc_ens_score(p, None, 0, None, None),
+      "spectrum": lambda: lib.gc_ens_spectrum(p, None, None, None),
+      "spec_field": lambda: lib.gc_spec_field(p, None, None),
+      "event": lambda: lib.gc_ens_event_score(p, None, None, None, None),
+      "fss": lambda: lib.gc_ens_fss_score(p, None),
+      "fss_fields": lambda: lib.gc_ens_fss_fields(p, 0, 0, None, None),
+      "order": lambda: lib.gc_ens_order_score(p, None, None, None, None, None, None),
+      "clim": lambda: lib.gc_ens_clim_score(p, clim._h, None, None, None, None),
+      "energy": lambda: lib.gc_ens_energy_score(p, None, None, None, None),
+      "variogram": lambda: lib.gc_ens_variogram_score(p, None, None, None),
+      "tail": lambda: lib.gc_ens_tail_score(p, None, None, None, None),
+      "region": lambda: lib.gc_ens_region_score(p, None, None, None, None),
+  }
+  full = {                                                               # every output given, no truth
+      "score": lambda: lib.gc_ens_score(p, None, 0, D, U),
+      "spectrum": lambda: lib.gc_ens_spectrum(p, None, D, D),
+      "spec_field": lambda: lib.gc_spec_field(p, None, D),
+      "event": lambda: lib.gc_ens_event_score(p, None, U, U, U),
+      "order": lambda: lib.gc_ens_order_score(p, None, D, D, D, U, U),
+      "clim": lambda: lib.gc_ens_clim_score(p, clim._h, None, D, U, U),
+      "energy": lambda: lib.gc_ens_energy_score(p, None, D, D, U),
+      "variogram": lambda: lib.gc_ens_variogram_score(p, None, D, U),
+      "tail": lambda: lib.gc_ens_tail_score(p, None, D, U, U),
+      "region": lambda: lib.gc_ens_region_score(p, None, D, U, U),
+  }
+  fill = {
+      "derive": lambda s: lib.gc_ens_derive(p, s, None),
+      "band": lambda s: lib.gc_ens_band(p, s, None),
+      "feature": lambda s: lib.gc_ens_feature(p, s, None),
+      "window_push": lambda s: lib.gc_ens_window_push(p, s, None),
+  }
+
+  wrong = []
+
+  def expect(what, call, code, fragment):
+    rc = call()
+    err = lib.gc_last_error(p).decode()
+    print(f"{what}: {rc} {err!r}")
+    if rc != code or fragment not in err:
+      wrong.append((what, rc, err, code, fragment))
+
+  NULL, STORE, SRC_STORE, DIMS = "null argument", "no member store (gc_ens_reserve)", "no member store on the source handle", "has other dimensions"
+  slot = lambda i: f"member slot {i} has not been pushed"
+  try:
+    # ---- rung 0: the graph only
+    rung = "graph only"
+    for name, frag in (("score", STORE), ("spectrum", "no analysis tables"), ("spec_field", "no analysis tables"),
+                       ("event", "no thresholds (gc_ens_event_set)"), ("fss", "no plan (gc_ens_fss_set)"),
+                       ("fss_fields", "no plan (gc_ens_fss_set)"), ("order", "no probabilities (gc_ens_order_set)"),
+                       ("energy", "no plan (gc_ens_energy_set)"), ("variogram", "no plan (gc_ens_variogram_set)"),
+                       ("tail", "no thresholds (gc_ens_tail_set)"), ("region", "no regions (gc_ens_region_set)")):
+      expect(f"{rung}: {name}", null[name], ST, frag)
+    expect(f"{rung}: clim", null["clim"], ARG, NULL)
+    expect(f"{rung}: clim, no handle", lambda: lib.gc_ens_clim_score(p, None, None, None, None, None), ARG, "the climatology must be another handle")
+    expect(f"{rung}: order_fields", lambda: lib.gc_ens_order_fields(p), ST, "no probabilities")
+    expect(f"{rung}: window_emit", lambda: lib.gc_ens_window_emit(p), ST, "no plan (gc_ens_window_set)")
+    for name, frag in (("derive", "no plan (gc_ens_derive_set)"), ("band", "no analysis tables"), ("feature", "no plan (gc_ens_feature_set)"),
+                       ("window_push", "no plan (gc_ens_window_set)")):
+      expect(f"{rung}: {name}, itself", lambda: fill[name](p), ARG, "the source must be another handle")
+      expect(f"{rung}: {name}, no source", lambda: fill[name](None), ARG, "the source must be another handle")
+      expect(f"{rung}: {name}, other dimensions", lambda: fill[name](bad._h), ST, frag)
+      expect(f"{rung}: {name}, empty source", lambda: fill[name](src._h), ST, frag)
+    # ---- rung 1: every plan
+    rung = "plans set"
+    thr = np.zeros((1, G, B, C), np.float32)
+    zlat = np.zeros((C, n_lat), np.int32)
+    h.spec_set_tables(np.zeros((L, L, n_lat), np.float32), np.zeros((L, n_lon), np.float32), np.zeros((L, n_lon), np.float32))
+    expect(f"{rung}: band, tables only", lambda: fill["band"](bad._h), ST, "no plan (gc_ens_band_set)")
+    h.ens_band_set(C, np.ones((1, L)), [0], [0, 1], [0, 0], np.zeros((L, n_lat, L), np.float32), np.zeros((L, n_lon), np.float32),
+                   np.zeros((L, n_lon), np.float32))
+    h.ens_event_set(thr, (+1,), np.ones(G, np.uint32))
+    h.ens_fss_set(np.zeros(1, np.int32), np.zeros((1, n_lat), np.int32), np.ones(n_lat, np.uint32))
+    h.ens_order_set([0.5])
+    h.ens_energy_set(1, np.zeros(C, np.int32), np.ones(C))
+    h.ens_variogram_set(n_lat, n_lon, np.array([[0, 1]], np.int32), 1.0)
+    h.ens_tail_set(thr, (+1,))
+    h.ens_region_set(np.ones(G, np.uint32), 1)
+    h.ens_derive_set(C, [0, 0], [0, 1], [0, 0], np.tile([1.0, 0.0, 1.0, 0.0], (C, 1)), n_lat=n_lat, n_lon=n_lon)
+    h.ens_feature_set(C, [0, 1], [-1, +1], [0, 0], [0.0, 0.0], n_lat, n_lon, [1, 1], zlat + 1, [0, 0], zlat, [0.0, 0.0], [0, 0], zlat)
+    h.ens_window_set(1, 2)
+    for name in ("score", "spectrum", "event", "order", "energy", "variogram", "tail", "region"):
+      expect(f"{rung}: {name}", null[name], ST, STORE)
+    expect(f"{rung}: order_fields", lambda: lib.gc_ens_order_fields(p), ST, STORE)
+    for name in ("derive", "band", "feature"):
+      expect(f"{rung}: {name}, other dimensions", lambda: fill[name](bad._h), ARG, DIMS)
+      expect(f"{rung}: {name}, empty source", lambda: fill[name](src._h), ST, STORE)
+
+    def same_at_every_later_rung(rung):
+      expect(f"{rung}: spec_field", null["spec_field"], ARG, NULL)
+      expect(f"{rung}: spec_field, no sample", full["spec_field"], ST, "no sample on the device")
+      expect(f"{rung}: fss", null["fss"], ST, "no valid event codes")
+      expect(f"{rung}: fss_fields", null["fss_fields"], ST, "no valid event codes")
+      expect(f"{rung}: clim", null["clim"], ARG, NULL)
+      expect(f"{rung}: window_emit", lambda: lib.gc_ens_window_emit(p), ST, "the window needs 2 pushes, the ring holds 0")
+      expect(f"{rung}: window_push, other dimensions", lambda: fill["window_push"](bad._h), ARG, DIMS)
+      expect(f"{rung}: window_push, empty source", lambda: fill["window_push"](src._h), ST, SRC_STORE)
+
+    same_at_every_later_rung(rung)
+    expect(f"{rung}: clim, outputs", full["clim"], ST, STORE)
+    # ---- rungs 2 to 4: the store reserved, one slot unpushed, all pushed
+    field = np.zeros((G, B, C), np.float32)
+    for rung, unpushed in (("store reserved", 0), ("one slot unpushed", 1), ("all pushed, no weights", None)):
+      if unpushed == 0:
+        h.ens_reserve(M)
+      else:
+        h.ens_push_host(0 if unpushed == 1 else 1, field)
+      same_at_every_later_rung(rung)
+      for name in ("score", "spectrum", "event", "tail", "region"):         # the null output is tested before the slots
+        expect(f"{rung}: {name}", null[name], ARG, NULL)
+      for name in ("order", "energy", "variogram"):                         # ... and here behind them
+        if unpushed is not None:
+          expect(f"{rung}: {name}", null[name], ST, slot(unpushed))
+      if unpushed is not None:
+        expect(f"{rung}: order_fields", lambda: lib.gc_ens_order_fields(p), ST, slot(unpushed))
+        expect(f"{rung}: clim, outputs", full["clim"], ST, "no member store on the climatology handle")
+      for name in ("derive", "band", "feature"):
+        expect(f"{rung}: {name}, other dimensions", lambda: fill[name](bad._h), ARG, DIMS)
+        expect(f"{rung}: {name}, empty source", lambda: fill[name](src._h), ST, SRC_STORE)
+    expect(f"{rung}: order", null["order"], ARG, NULL)                      # behind the slots, in front of the weights
+    for name in ("energy", "variogram"):                                    # behind both
+      expect(f"{rung}: {name}", null[name], ST, "no node weights")
+    for name in ("score", "order", "tail", "region"):
+      expect(f"{rung}: {name}, outputs", full[name], ST, "no node weights")
+    # ---- rung 5: weights, no truth
+    rung = "weights, no truth"
+    h.ens_set_node_weight(np.ones(G, np.float32))
+    same_at_every_later_rung(rung)
+    for name in ("score", "spectrum", "event", "order", "energy", "variogram", "tail", "region"):
+      expect(f"{rung}: {name}", null[name], ARG, NULL)
+      expect(f"{rung}: {name}, outputs", full[name], ST, f"no truth on the device (pass one to gc_ens_{name}" if name in ("score", "spectrum")
+             else f"no truth on the device (pass one to gc_ens_{name}_score)")
+    # the climatology's own ladder, behind this handle's
+    expect(f"{rung}: clim, outputs", full["clim"], ST, "no member store on the climatology handle")
+    clim.ens_reserve(3)
+    expect(f"{rung}: clim, an unpushed climatology", full["clim"], ST, "climatology member slot 0 has not been pushed")
+    for i in range(3):
+      clim.ens_push_host(i, field)
+    expect(f"{rung}: clim, complete", full["clim"], ST, "no truth on the device (pass one to gc_ens_clim_score)")
+    expect(f"{rung}: clim, other dimensions", lambda: lib.gc_ens_clim_score(p, bad._h, None, D, U, U), ARG, DIMS)
+    # ---- the source's ladder, behind this handle's
+    src.ens_reserve(M + 1)
+    for name in ("derive", "band", "feature"):
+      expect(f"source of {M + 1}: {name}", lambda: fill[name](src._h), ST, "the two member stores hold different numbers of members")
+    expect(f"source of {M + 1}: window_push", lambda: fill["window_push"](src._h), ST, "source " + slot(0))
+    src.ens_reserve(M)
+    for i in range(M):
+      for name in fill:
+        expect(f"source slot {i} unpushed: {name}", lambda: fill[name](src._h), ST, "source " + slot(i))
+      src.ens_push_host(i, field)
+    for name in fill:
+      expect(f"source complete: {name}", lambda: fill[name](src._h), ST, f"no truth on the source handle (pass one to gc_ens_{name})")
+    for nd in (h, src, clim, bad):
+      for name in COUNTERS:
+        if name != "launches_per_call":
+          assert nd.counter(name) == 0, name
+    assert not wrong, wrong
+  finally:
+    for nd in (h, src, clim, bad):
+      nd.close()
