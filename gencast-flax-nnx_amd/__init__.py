@@ -21,6 +21,8 @@ Public surface (mirrors the reference's call contracts):
                       on the GPU (GenCast.ensemble_order, EnsembleRollout.run(order=...))
                       ClimatologyScores: anomaly correlation and CRPS skill score of an ensemble against K climatological
                       samples held by a second handle (GenCast.ensemble_climatology, EnsembleRollout.run(climatology=...))
+                      EfiSpec / EfiScores: the Extreme Forecast Index -- the members ranked, on the GPU, in the K samples of
+                      that second handle -- and its verification (GenCast.ensemble_efi, EnsembleRollout.run(efi=...))
                       WindowSpec: accumulations, means, changes and extremes over the last lead times of a rollout, formed
                       on the GPU from a ring of member stores (EnsembleRollout.run(windows=...))
                       EnergySpec / VariogramSpec: the energy score over groups of variables and the variogram score over
@@ -56,9 +58,9 @@ from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, Ense
                       InputsAndResiduals, WindowRolloutResult, autoregressive_rollout, state_channels)
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
-from .verification import (BandSpec, ClimatologyScores, DerivedSpec, EnergyScores, EnergySpec, EnsembleScores, EventScores,  # noqa: F401
+from .verification import (BandSpec, ClimatologyScores, DerivedSpec, EfiScores, EfiSpec, EnergyScores, EnergySpec, EnsembleScores, EventScores,  # noqa: F401
                            EventSpec, FeatureScores, FeatureSpec, FractionsScores, OrderScores, RegionScores, RegionSpec,
-                           TailScores, VariogramScores, VariogramSpec, WindowSpec, link_tracks)
+                           TailScores, VariogramScores, VariogramSpec, WindowSpec, efi_table, link_tracks)
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
@@ -68,4 +70,4 @@ __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_
            "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores",
            "WindowSpec", "WindowRolloutResult", "EnergySpec", "EnergyScores", "VariogramSpec", "VariogramScores", "TailScores",
            "RegionSpec", "RegionScores", "FeatureSpec", "FeatureScores", "FeatureRolloutResult", "link_tracks",
-           "FractionsScores", "BandSpec"]
+           "FractionsScores", "BandSpec", "EfiSpec", "EfiScores", "efi_table"]

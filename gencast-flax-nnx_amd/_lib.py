@@ -143,6 +143,12 @@ SIGNATURES = {
     "gc_ens_order_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
     "gc_ens_clim_score": (ctypes.c_int, [_hp, _hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
                                          ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_efi_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
+    "gc_ens_efi_score": (ctypes.c_int, [_hp, _hp, ctypes.POINTER(ctypes.c_double), _f32p, ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                        ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_efi_fields": (ctypes.c_int, [_hp, _hp, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_efi_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
     "gc_ens_window_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
     "gc_ens_window_push": (ctypes.c_int, [_hp, _hp, _f32p]),
     "gc_ens_window_emit": (ctypes.c_int, [_hp]),
@@ -265,6 +271,7 @@ class NativeDenoiser:
     self._variogram_offsets = None             # offsets of the variogram plan this object set (None: ens_variogram_set not called)
     self._tail_thresholds = 0                  # tail threshold fields this object handed to the handle
     self._regions = 0                          # regions of the plan this object handed to the handle (0: ens_region_set not called)
+    self._efi_plan = None                      # (T, E) of the events and bins this object set (None: ens_efi_set not called)
     self._window_length = 0                    # length of the window plan this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
@@ -1073,6 +1080,77 @@ class NativeDenoiser:
     self._check(self._lib.gc_ens_clim_score(self._h, clim._h, None if t is None else _ptr(t, _f32p),  # pylint: disable=protected-access
                                             _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(counts, u64), _ptr(invalid, u64)))
     return sums, counts, int(invalid[0])
+
+  # -- extreme forecast index (the members ranked in the samples of a climatology handle) ----------------
+  def ens_efi_set(self, ranks=(), directions=(), n_bins: int = 20, node_weight_q=None) -> None:
+    """The events and bins of `ens_efi_score` (gc_ens_efi_set; needs `set_graph` only and survives `ens_reserve`): `ranks` [T]
+    int and `directions` [T] (> 0: the truth's event is lt(y) >= rank, < 0: le(y) <= rank), T in 0..4; `n_bins` E in 2..32
+    equal EFI bins; `node_weight_q` [G] uint32 (`verification.quantize_node_weights`), not needed when T == 0.
+    `verification.EfiSpec` builds the ranks from quantiles."""
+    r, d = _i32(ranks).reshape(-1), _i32(directions).reshape(-1)
+    T = int(r.shape[0])
+    if d.shape != (T,):
+      raise ValueError(f"directions must have shape ({T},)")
+    if isinstance(n_bins, bool) or int(n_bins) != n_bins:
+      raise ValueError(f"n_bins must be an integer in 2..32, got {n_bins!r}")
+    w = None
+    if T:
+      w = np.asarray(node_weight_q)
+      if w.shape != (self.num_grid_nodes,) or w.dtype.kind not in "ui" or (w.size and (w.min() < 0 or w.max() > 0xFFFFFFFF)):
+        raise ValueError(f"node_weight_q must be unsigned 32-bit integers of shape ({self.num_grid_nodes},)")
+      w = np.ascontiguousarray(w, dtype=np.uint32)
+    self._check(self._lib.gc_ens_efi_set(self._h, T, _ptr(r, _i32p) if T else None, _ptr(d, _i32p) if T else None, int(n_bins),
+                                         None if w is None else _ptr(w, ctypes.POINTER(ctypes.c_uint32))))
+    self._efi_plan = (T, int(n_bins))
+
+  def _efi_args(self, clim, table):
+    if not isinstance(clim, NativeDenoiser):
+      raise TypeError("clim must be a NativeDenoiser")
+    if clim is self:
+      raise ValueError("the climatology must be another handle")
+    if not self._ens_members:
+      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    K = clim._ens_members  # pylint: disable=protected-access
+    if not K:
+      raise GencastHipError("libgencast_hip error 4: no member store on the climatology handle (ens_reserve has not been "
+                            "called on that object)")
+    a = np.ascontiguousarray(table, dtype=np.float64)
+    if a.shape != (K + 1,):
+      raise ValueError(f"table must have shape ({K + 1},) for the {K} samples of the climatology handle, got {a.shape}")
+    return a
+
+  def ens_efi_score(self, clim: "NativeDenoiser", table, truth=None):
+    """-> (sums [B, c_out, 6] float64, weighted [T, B, c_out, 2, E] uint64, counts (same shape), invalid int): the raw,
+    additive results of gc_ens_efi_score over this handle's member store and the K samples in the store of `clim`
+    (`Denoiser.climatology_handle`); `table` [K + 1] float64 is `verification.efi_table(K)`.  The EFI and the observed index
+    stay on the device (`ens_efi_field`).  `truth` [G, B, c_out], or None = the truth uploaded last."""
+    a = self._efi_args(clim, table)
+    if self._efi_plan is None:
+      raise GencastHipError("libgencast_hip error 4: no events and bins (ens_efi_set has not been called on this object)")
+    t = self._truth_arg(truth)
+    (T, E), B, C = self._efi_plan, self.cfg.batch, self.cfg.c_out
+    dp, u64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)
+    sums = np.empty((B, C, 6), dtype=np.float64)
+    weighted = np.zeros((T, B, C, 2, E), dtype=np.uint64)
+    counts = np.zeros_like(weighted)
+    invalid = np.zeros(1, dtype=np.uint64)
+    self._check(self._lib.gc_ens_efi_score(self._h, clim._h, _ptr(a, dp), None if t is None else _ptr(t, _f32p),  # pylint: disable=protected-access
+                                           _ptr(sums, dp), _ptr(weighted, u64) if T else None, _ptr(counts, u64) if T else None,
+                                           _ptr(invalid, u64)))
+    return sums, weighted, counts, int(invalid[0])
+
+  def ens_efi_fields(self, clim: "NativeDenoiser", table) -> None:
+    """The EFI field of the member store against the samples of `clim`, without truth, weights or events
+    (gc_ens_efi_fields); `ens_efi_field(0)` downloads it."""
+    a = self._efi_args(clim, table)
+    self._check(self._lib.gc_ens_efi_fields(self._h, clim._h, _ptr(a, ctypes.POINTER(ctypes.c_double))))  # pylint: disable=protected-access
+
+  def ens_efi_field(self, which: int = 0) -> np.ndarray:
+    """Field `which` [G, B, c_out] float32 of the last `ens_efi_score` / `ens_efi_fields`: 0 the EFI, 1 the observed index
+    (gc_ens_efi_download; the observed index only after `ens_efi_score`)."""
+    out = np.empty(self._shape_out(), dtype=np.float32)
+    self._check(self._lib.gc_ens_efi_download(self._h, int(which), _ptr(out, _f32p)))
+    return out
 
   # -- multivariate ensemble scores (energy over channel groups, variogram over grid offsets) -----------
   def _truth_arg(self, truth):

@@ -85,7 +85,7 @@ const int64_t* meter_counter(const gc_handle* h, const std::string& n) {
       {"ens_event", &gc_handle::evt, true},     {"ens_derive", &gc_handle::drv, false}, {"ens_band", &gc_handle::band, false},
       {"ens_order", &gc_handle::ord, true},     {"ens_clim", &gc_handle::clim, true},   {"ens_energy", &gc_handle::en, true},
       {"ens_variogram", &gc_handle::vg, false}, {"ens_tail", &gc_handle::tail, true},   {"ens_region", &gc_handle::reg, true},
-      {"ens_feature", &gc_handle::feat, false}, {"ens_fss", &gc_handle::fss, false}};
+      {"ens_feature", &gc_handle::feat, false}, {"ens_fss", &gc_handle::fss, false},  {"ens_efi", &gc_handle::efi, true}};
   struct Row { const char* name; Meter gc_handle::*meter; int64_t Meter::*field; };
   static const Row rows[] = {
       {"ens_scores", &gc_handle::ens, &Meter::calls},

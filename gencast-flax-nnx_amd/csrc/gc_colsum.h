@@ -1,4 +1,4 @@
-// Column sums of the ensemble scorers (gc_ensemble.hip, gc_region.hip, gc_clim.hip, gc_order.hip, gc_tail.hip,
+// Column sums of the ensemble scorers (gc_ensemble.hip, gc_region.hip, gc_clim.hip, gc_efi.hip, gc_order.hip, gc_tail.hip,
 // gc_multivar.hip, gc_fss.hip, gc_events.hip): the thread layout over column tiles, the fold of a column's node lanes,
 // the two sums over the per-block partials, and the host helpers that size the grids.  DESIGN.md section 8r.  Every sum formed here has ONE order, so the same call twice returns identical bytes.
 //

@@ -294,6 +294,7 @@ int gc_ens_reserve(gc_handle* h, int32_t n_members) {
   h->has_ens_fields = false;
   h->evt_scored = false;                           // (gc_events.hip: the codes were of the old store)
   h->ord_ready = false;                            // (gc_order.hip: so were the quantile fields)
+  h->efi_fields = 0;                               // (gc_efi.hip: and the index fields)
   h->d_ens = nullptr;
   h->d_ens_state_src = nullptr;
   const gc_config& c = h->cfg;

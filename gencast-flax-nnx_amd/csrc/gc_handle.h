@@ -10,13 +10,14 @@
 //   gc_derive.hip    gc_ens_derive_*
 //   gc_order.hip     gc_ens_order_*
 //   gc_clim.hip      gc_ens_clim_score
+//   gc_efi.hip       gc_ens_efi_*
 //   gc_window.hip    gc_ens_window_*
 //   gc_multivar.hip  gc_ens_energy_*, gc_ens_variogram_*
 //   gc_tail.hip      gc_ens_tail_*
 //   gc_region.hip    gc_ens_region_*
 //   gc_feature.hip   gc_ens_feature_*
 //   gc_fss.hip       gc_ens_fss_*
-// The last thirteen are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
+// The last fourteen are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
 // lead times of another, gc_feature.hip with the strike fields of the centres it finds in another).  Their host side is two
 // protocols, "score a store" and "fill a store from a source handle", written once in gc_store.h.  What a unit keeps on the
 // handle is declared with the types below: its device buffers are a BufferGroup (a KeyedGroup where a call makes them
@@ -439,6 +440,25 @@ struct gc_handle {
   unsigned long long* d_clim_outc = nullptr;     // [B c_out] counted points, then the skipped points of the call
   gci::Meter clim{events};                       // of gc_ens_clim_score
   gci::Event ev_clim_src{events};                // stream order behind the climatology handle
+
+  // extreme forecast index (gc_ens_efi_*, gc_efi.hip): the members of this handle's store ranked in the samples of another's
+  gci::BufferGroup efi_allocs{groups};            // sized by G, B and c_out alone: made by the first call, kept across gc_ens_reserve
+  gci::KeyedGroup<2> efi_table_allocs{groups};    // the integer tables, sized by (T + 1, E): made again by the scoring call that finds either changed
+  bool efi_set = false;                          // events and bins have been set (T = 0 is a setting)
+  int efi_T = 0, efi_E = 0;                      // events, EFI bins
+  int efi_rank[4] = {}, efi_dir[4] = {};         // per event: the rank n, and +1 (lt_y >= n) or -1 (le_y <= n)
+  int efi_fields = 0;                            // of this store: 0 no fields on the device, 1 the EFI alone, 2 the observed index too
+  float* d_efi_field = nullptr;                  // [2][G, B, c_out]: the EFI, the observed index
+  unsigned short* d_efi_code = nullptr;          // [G, B, c_out]: bin | event bits << 8, 0xFFFF = not counted
+  unsigned* d_efi_wq = nullptr;                  // [G] integer node weights
+  double* d_efi_tab = nullptr;                   // [65] the table a[0 .. K] of the call in flight
+  double* d_efi_part = nullptr;                  // [blocks][6][B c_out] per-block column sums
+  unsigned* d_efi_ipart = nullptr;               // [blocks][tiles] skipped points
+  double* d_efi_out = nullptr;                   // [B c_out][6]
+  unsigned long long* d_efi_outc = nullptr;      // the skipped points of the call
+  unsigned long long* d_efi_table = nullptr;     // weighted [T][B c_out][2][E], then counts (same)
+  gci::Meter efi{events};                        // of gc_ens_efi_score and gc_ens_efi_fields
+  gci::Event ev_efi_src{events};                 // stream order behind the climatology handle
 
   // time-window ensemble fields (gc_ens_window_*, gc_window.hip): the plan, and the ring of the last L pushed lead times
   gci::KeyedGroup<2> win_allocs{groups};          // the ring, one buffer sized by (L, M): made again by the push that finds either changed

@@ -1,7 +1,7 @@
 // The two host protocols of the units over the member store (gc_ens_reserve).  Host code only.
 //
 // Scoring a store (gc_ens_score, gc_ens_spectrum, gc_ens_event_score, gc_ens_fss_score, gc_ens_order_*, gc_ens_clim_score,
-// gc_ens_energy_score, gc_ens_variogram_score, gc_ens_tail_score, gc_ens_region_score):
+// gc_ens_efi_score, gc_ens_energy_score, gc_ens_variogram_score, gc_ens_tail_score, gc_ens_region_score):
 //   1. the state checks, one `||` chain of need_graph / need(plan) / need_store / need_out / store_complete / need_weights /
 //      check_peer in the order THIS entry reports them (the orders differ, and tests pin them);
 //   2. hipSetDevice, take_truth;
@@ -134,6 +134,7 @@ inline void store_rewritten(gc_handle* h) {
   h->evt_scored = false;
   h->has_ens_fields = false;
   h->ord_ready = false;
+  h->efi_fields = 0;
 }
 
 // The opening, behind need_source and the entry's plan check: the source has c_out == c_src of the plan and a complete

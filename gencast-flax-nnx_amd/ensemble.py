@@ -152,6 +152,20 @@ class EnsembleSampler:
       raise ValueError(f"climatology must be 2..64 Datasets shaped like the targets, got {len(climatology)}")
     return self._run(inputs, targets, forcings, num_members, None, climatology=climatology)
 
+  def efi(self, inputs, targets, forcings, num_members: int, climatology, spec=None, fields: bool = True):
+    """Runs the members as `scores` does and ranks them, point by point on the device, in `climatology` (K Datasets as in
+    `climatology`): the Extreme Forecast Index, verified against `targets` by `spec` (a `verification.EfiSpec`; None: its
+    defaults) -> `verification.EfiScores`, with `fields` -> (EfiScores, EFI Dataset, observed-index Dataset), both shaped
+    like `targets`.  `targets` None (a forecast without an analysis): -> the EFI Dataset alone, shaped like a sample.  The
+    index has no unit.  No member is downloaded."""
+    self._one_rank("efi")
+    climatology = list(climatology)
+    if not 2 <= len(climatology) <= 64:
+      raise ValueError(f"climatology must be 2..64 Datasets shaped like the targets, got {len(climatology)}")
+    spec = verification.EfiSpec() if spec is None else spec
+    return self._run(inputs, climatology[0] if targets is None else targets, forcings, num_members, None,
+                     efi=(climatology, spec, bool(fields), targets is not None))
+
   def multivariate(self, inputs, targets, forcings, num_members: int, energy=None, variogram=None):
     """Runs the members as `scores` does and forms, on the device, the two proper scores of a JOINT forecast: with `energy`
     (a `verification.EnergySpec`: groups of variables) the energy score of every group, with `variogram` (a
@@ -191,11 +205,13 @@ class EnsembleSampler:
     EnergySpec or None, a VariogramSpec or None), only their energy and variogram scores, or, with `tails` (an EventSpec), only
     their threshold-weighted CRPS sums, or, with `regions` (a RegionSpec), only their sums per region, or, with `derived` (a
     DerivedSpec, an EventSpec or None), only the scores of the derived fields, or, with `features` (a FeatureSpec), only the
-    centres and the scores of their strike fields; else they are scored (`scores`), with
+    centres and the scores of their strike fields, or, with `efi` (K Datasets, an EfiSpec, want fields, has a truth), only their
+    extreme forecast index; else they are scored (`scores`), with
     `spectral` both.  `asked`: at most one of these keywords (one that is None was not asked for)."""
     asked = {what: arg for what, arg in asked.items() if arg is not None}
     events, order, climatology, tails, regions = (asked.get(k) for k in ("events", "order", "climatology", "tails", "regions"))
     fspec = asked.get("features")
+    eclim, espec, efields, etruth = asked.get("efi", (None, None, False, False))
     (dspec, dev), (energy, variogram) = asked.get("derived", (None, None)), asked.get("multivariate", (None, None))
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
@@ -226,14 +242,16 @@ class EnsembleSampler:
     main = None                                            # lane 0's member store, where anything is scored at all
     if scoring or spectral or asked:
       weights = None if spectral and not scoring else verification.node_weights(template)
-      wq = None if events is None and dev is None and fspec is None else verification.quantize_node_weights(weights)
+      wq = (None if events is None and dev is None and fspec is None and not (espec is not None and etruth and espec.n_events)
+            else verification.quantize_node_weights(weights))
       # (scored once: the thresholds are set by that call, after the members are in; events and derived fields alone need no
       # node weights on the main store)
       main = verification.ScoredStore(native, num_members, weights if scoring or asked.keys() - {"events", "derived", "features"} else None,
                                       events=events, thresholds=None if events is None else events.packed(template), weight_q=wq,
                                       set_per_score=True, order=None if order is None else order[0],
-                                      climatology=None if climatology is None
+                                      climatology=None if climatology is None and eclim is None
                                       else self._denoiser.climatology_handle(self._denoiser.dims.c_out),
+                                      efi=None if espec is None else espec if wq is not None else verification.EfiSpec((), (), espec.bins),
                                       energy=None if energy is None else energy.plan(template),
                                       variogram=None if variogram is None else variogram.plan(template),
                                       tails=tails, tail_thresholds=None if tails is None else tails.packed(template),
@@ -290,6 +308,13 @@ class EnsembleSampler:
       en = main.score_energy(truth)
       return en, main.score_variogram(truth if en is None else None)      # (the truth is on the device after the first)
 
+    def efi_scores():
+      main.load_climatology([pack(c) for c in eclim])
+      if not etruth:                                       # a forecast without an analysis: the field alone
+        return as_given([main.efi_field_without_truth()])[0]
+      scores = main.score_efi(truth)
+      return (scores,) + tuple(as_given(main.efi_fields())) if efields else scores
+
     def order_scores():
       scores = main.score_order(truth)
       return (scores, as_given(main.quantile_fields())) if order[1] else scores
@@ -298,7 +323,7 @@ class EnsembleSampler:
       return {"derived": derived_scores, "features": feature_scores, "events": lambda: main.score_events(truth),
               "climatology": lambda: main.score_climatology([pack(c) for c in climatology], truth),
               "tails": lambda: main.score_tails(truth), "regions": lambda: main.score_regions(truth),
-              "multivariate": multivariate_scores, "order": order_scores}[next(iter(asked))]()
+              "multivariate": multivariate_scores, "order": order_scores, "efi": efi_scores}[next(iter(asked))]()
     if not scoring:
       return _spectra.EnsembleSpectra(native.ens_spectrum(truth), num_members)
     result = (main.score(truth, want_fields=score_fields)[0],)

@@ -174,6 +174,17 @@ class GenCast:
     runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.climatology(inputs, targets, forcings, num_members, climatology)
 
+  def ensemble_efi(self, inputs, targets, forcings=None, *, num_members, climatology, spec=None, fields=True, rngs=0,
+                   concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and ranks them on the GPU, point by point, in
+    `climatology` (K Datasets, as in `ensemble_climatology`): the Extreme Forecast Index (Lalaurette 2003), in [-1, 1], how
+    far the forecast distribution is shifted against the climatological one, weighted towards the tails.
+    -> (`verification.EfiScores`, EFI Dataset, observed-index Dataset); `fields=False`: the scores alone.  `spec`: a
+    `verification.EfiSpec` (the climatological events of `targets` the index is verified against, the EFI bins).
+    `targets=None` -- a real forecast, no analysis yet -- gives the EFI Dataset alone.  No member leaves the device."""
+    runner = self._ensemble_sampler(rngs, concurrent_members)
+    return runner.efi(inputs, targets, forcings, num_members, climatology, spec, fields)
+
   def ensemble_derived(self, inputs, targets, forcings=None, *, num_members, spec, events=None, rngs=0, concurrent_members=1):
     """Samples `num_members` (2..64) members as `ensemble_scores` does and scores, on the GPU, what `spec`
     (`verification.DerivedSpec`) makes of them and of `targets`: wind speed from two components, fields max-, min- or

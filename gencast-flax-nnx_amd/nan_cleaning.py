@@ -138,6 +138,12 @@ class NaNCleaner:
     the device does not count (`ClimatologyScores.invalid`)."""
     return self.predictor.ensemble_climatology(*self._cleaned(inputs, targets, forcings, False), **kwargs)
 
+  def ensemble_efi(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """Inputs and forcings are cleaned; the targets (None: a forecast without an analysis) and the climatology pass through
+    unchanged: their NaNs are points the device does not count (`EfiScores.invalid`) and NaNs of both index fields."""
+    inputs, _, forcings = self._cleaned(inputs, inputs if targets is None else targets, forcings, False)
+    return self.predictor.ensemble_efi(inputs, targets, forcings, **kwargs)
+
   def ensemble_events(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """Inputs and forcings are cleaned; the targets pass through unchanged, as in `ensemble_scores`: their NaNs are
     points the device does not count (`EventScores.invalid`)."""

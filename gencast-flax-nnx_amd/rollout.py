@@ -249,6 +249,17 @@ class InputsAndResiduals:
       nclim.append(Dataset({k: self._subtract_input_and_normalize_target(raw, k, v) for k, v in c.items()}, c.coords))
     return self.predictor.ensemble_climatology(ni, nt, forcings=nf, climatology=nclim, **kwargs).scaled(scale)
 
+  def ensemble_efi(self, inputs, targets, forcings=None, *, climatology, **kwargs):
+    """`ensemble_efi` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets, passed
+    through as it is: every sample goes through the SAME map as the targets (as in `ensemble_climatology`), that map is
+    increasing per point, and ranks -- hence the index, its fields and its tables -- do not change under it.  With
+    `targets=None` the first sample stands in where the shape of the targets is needed."""
+    climatology = [datasets.as_dataset(c) for c in climatology]
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, climatology[0] if targets is None else targets, forcings)
+    nclim = [Dataset({k: self._subtract_input_and_normalize_target(raw, k, v) for k, v in c.items()}, c.coords)
+             for c in climatology]
+    return self.predictor.ensemble_efi(ni, None if targets is None else nt, forcings=nf, climatology=nclim, **kwargs)
+
   def ensemble_events(self, inputs, targets, forcings=None, *, spec, **kwargs):
     """`ensemble_events` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets.
     The thresholds of `spec` (physical units) go through the SAME map as the targets
@@ -653,10 +664,32 @@ class _SeriesResult:
   def _carries(cls) -> List[str]:
     return [name for row in cls._rows() for name in row.series]
 
+  @classmethod
+  def _carries_efi(cls) -> bool:
+    return cls._carried_as in verification.EFI_SCORER.carried_by
+
   def __getattr__(self, name):
     if any(row.optional and name in row.series for row in self._rows()):
       return None
+    if name in ("efi", "efi_fields") and self._carries_efi():    # of `run(efi=...)`: absent from `vars(result)` unless asked for
+      return None
     raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+  def _set_efi(self, efi, efi_fields) -> None:
+    """`efi`: one `verification.EfiScores` per lead time; `efi_fields`: per lead time (EFI, observed index) [G, B, c]."""
+    word = verification.EFI_SCORER.word
+    if efi is not None:
+      self.efi = list(efi)
+      if len(self.efi) != len(self.scores):
+        raise ValueError(f"scores and the {word} must cover the same lead times")
+    if efi_fields is not None:
+      self.efi_fields = efi_fields
+
+  def _merged_efi(self, other) -> Optional[list]:
+    """The index tables and sums of both results added entry by entry (None: neither has them); the fields belong to one date."""
+    if (self.efi is None) != (other.efi is None):
+      raise ValueError(f"merge: only one of the two {self._kind} carries the {verification.EFI_SCORER.word}")
+    return None if self.efi is None else [type(x).merge([x, y]) for x, y in zip(self.efi, other.efi)]
 
   def _set_series(self, named, series) -> None:
     """Copies the series into lists (the scores first) and checks that the others cover the lead times of the scores.
@@ -708,12 +741,14 @@ class DerivedRolloutResult(_SeriesResult):
 
   _carried_as, _kind = "derived", "derived results"
 
-  def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, quantiles=None, **series):
+  def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, quantiles=None, efi=None,
+               efi_fields=None, **series):
     self._set_series(locals(), series)
+    self._set_efi(efi, efi_fields)
     self.members, self.template, self.quantiles = members, template, quantiles
 
   def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
-    return DerivedRolloutResult(template=self.template, **self._merged_series(other))
+    return DerivedRolloutResult(template=self.template, efi=self._merged_efi(other), **self._merged_series(other))
 
 
 class FeatureRolloutResult(_SeriesResult):
@@ -793,8 +828,9 @@ class EnsembleRolloutResult(_SeriesResult):
   _carried_as = "ensemble"
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
-               derived=None, quantiles=None, windows=None, features=None, **series):
+               derived=None, quantiles=None, windows=None, features=None, efi=None, efi_fields=None, **series):
     self._set_series(locals(), series)
+    self._set_efi(efi, efi_fields)
     self.derived = None if derived is None else dict(derived)
     self.windows = None if windows is None else dict(windows)
     if features is not None:                              # (as an optional series: absent from `vars(result)` unless asked for)
@@ -820,7 +856,7 @@ class EnsembleRolloutResult(_SeriesResult):
     if other.n_members != self.n_members:
       raise ValueError(f"merge: member counts differ ({self.n_members} and {other.n_members})")
     series = self._merged_series(other)
-    return EnsembleRolloutResult(n_members=self.n_members, **series,
+    return EnsembleRolloutResult(n_members=self.n_members, **series, efi=self._merged_efi(other),
                                  derived=_merge_named(self.derived, other.derived, "derived scores", "derived"),
                                  windows=_merge_named(self.windows, other.windows, "windows", "window"),
                                  features=_merge_named(self.features, other.features, "features", "feature"))
@@ -831,8 +867,12 @@ class _StoreSeries:
   as a `verification.ScoredStore`, the scale and the template of its channels, and what the lead times have yielded so far:
   every series the store and the `keep_*` flags call for is a list, the others are None."""
 
-  def __init__(self, store, scale, template, *, keep_members: bool = False, keep_quantiles: bool = False):
+  def __init__(self, store, scale, template, *, keep_members: bool = False, keep_quantiles: bool = False,
+               keep_efi: bool = False):
     self.store, self.scale, self.template = store, scale, template
+    # the extreme forecast index of a store with an `EfiSpec` (`verification.EFI_SCORER`: beside the table) and its two fields
+    self.efi = [] if getattr(store, "efi", None) is not None else None
+    self.efi_fields = [] if self.efi is not None and keep_efi else None
     # {series, by the name a result has it under: its list} of the scores and of every row the store has switched on
     self.lists = {name: [] for row in verification.SCORERS
                   if row.name == "scores" or getattr(store, row.name, None) is not None for name in row.series}
@@ -879,6 +919,10 @@ class _StoreSeries:
       lists[row.name].append(raw)                           # (without `scaled`: in the store's own units)
       if row.name == "order" and self.quantiles is not None:
         self.quantiles.append(self.store.quantile_fields())
+    if self.efi is not None:                                # (behind the climatology row, which has filled the second handle)
+      self.efi.append(verification.EFI_SCORER.score(self.store, None))
+      if self.efi_fields is not None:
+        self.efi_fields.append(self.store.efi_fields())
     if self.members is not None:
       self.members.append([self.store.handle.ens_download_member(m) for m in range(self.store.n_members)])
 
@@ -891,8 +935,8 @@ class _StoreSeries:
                                 template=self.template, quantiles=self.quantiles, **self.carried(FeatureRolloutResult))
 
   def derived_result(self) -> DerivedRolloutResult:
-    return DerivedRolloutResult(members=self.members, template=self.template, quantiles=self.quantiles,
-                                **self.carried(DerivedRolloutResult))
+    return DerivedRolloutResult(members=self.members, template=self.template, quantiles=self.quantiles, efi=self.efi,
+                                efi_fields=self.efi_fields, **self.carried(DerivedRolloutResult))
 
 
 class _WindowEntry:
@@ -1015,7 +1059,8 @@ class EnsembleRollout:
           init_noise=None, spectra: bool = False, lmax: Optional[int] = None, fields: bool = False,
           keep_members: bool = False, events=None, derived=None, order=None,
           keep_quantiles: bool = False, climatology=None, windows=None, energy=None,
-          variogram=None, tails=None, regions=None, features=None) -> EnsembleRolloutResult:
+          variogram=None, tails=None, regions=None, features=None, efi=None,
+          keep_efi: bool = False) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -1090,6 +1135,14 @@ class EnsembleRollout:
     `variogram` and `climatology` do not.  A window may name it as its source: `WindowSpec("max", L, source=name)` is a strike
     within L steps, the track-probability map.  `verification.link_tracks` links the centres of a member over the lead times.
     Without `features` nothing changes.
+    `efi`: a `verification.EfiSpec`, together with `climatology` (without it a ValueError): per lead time, behind the
+    climatology scores, the member states are ranked point by point in the K samples already in the second handle's store
+    (`gc_ens_efi_score`, on the truth already there): `EnsembleRolloutResult.efi` (`verification.EfiScores`: mean index, its
+    correlation with the observed index, the ROC of the index against the climatological events of the spec), and the same
+    for every `derived` entry -- a band view included -- on its derived members and derived samples.  The index has no
+    unit, so there is no normalised twin.  `keep_efi`: also the two fields, downloaded: `efi_fields[k]` = (EFI, observed
+    index), [G, B, c] each.  It does not reach the windows (`climatology` does not) nor the `features`.  Without `efi` nothing
+    changes.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -1129,7 +1182,7 @@ class EnsembleRollout:
     run = self._setup(inputs, targets, forcings, horizon, M, context_steps=context_steps, init_noise=init_noise,
                       spectra=spectra, lmax=lmax, fields=fields, keep_members=keep_members, events=events, derived=derived,
                       order=order, keep_quantiles=keep_quantiles, climatology=climatology, windows=windows, energy=energy,
-                      variogram=variogram, per_store=per_store, features=features)
+                      variogram=variogram, per_store=per_store, features=features, efi=efi, keep_efi=keep_efi)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -1143,11 +1196,12 @@ class EnsembleRollout:
                                  derived=None if derived is None else {k: v.derived_result() for k, v in run.views.items()},
                                  windows=None if windows is None else {k: v.result() for k, v in run.windows.items()},
                                  features=None if features is None else {k: v.feature_result() for k, v in run.features.items()},
-                                 spectra=run.spectra, spectra_normalized=run.raw_spectra, **main.carried(EnsembleRolloutResult))
+                                 spectra=run.spectra, spectra_normalized=run.raw_spectra, efi=main.efi,
+                                 efi_fields=main.efi_fields, **main.carried(EnsembleRolloutResult))
 
   def _setup(self, inputs, targets, forcings, horizon, M, *, context_steps, init_noise, spectra, lmax, fields, keep_members,
              events, derived, order, keep_quantiles, climatology, windows, energy, variogram, per_store,
-             features=None) -> "_EnsembleRun":
+             features=None, efi=None, keep_efi=False) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views.  The
     keywords are `run`'s own; `per_store`: {argument given per store ("tails", "regions"): {store name: spec} or None}."""
     run = _EnsembleRun()
@@ -1204,8 +1258,10 @@ class EnsembleRollout:
 
     weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
     wq = None
+    if efi is not None and climatology is None:
+      raise ValueError("efi: the extreme forecast index ranks the members in the samples of `climatology`, which was not given")
     if (events is not None or features or any(dev is not None for _, dev in entries.values())
-        or any(wev is not None for _, wev in wentries.values())):
+        or any(wev is not None for _, wev in wentries.values()) or (efi is not None and efi.n_events)):
       wq = verification.quantize_node_weights(weights)
     specs = None
     if events is not None:
@@ -1223,8 +1279,9 @@ class EnsembleRollout:
     main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
                                     thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
                                     set_per_score=specs is not None and len(specs) > 1, order=order, climatology=clim_handle,
-                                    energy=eplan(template0), variogram=vplan, **per_store_args(None, template0, scale, loc))
-    run.main = _StoreSeries(main, scale, template0, keep_members=keep_members, keep_quantiles=keep_quantiles)
+                                    energy=eplan(template0), variogram=vplan, efi=efi,
+                                    **per_store_args(None, template0, scale, loc))
+    run.main = _StoreSeries(main, scale, template0, keep_members=keep_members, keep_quantiles=keep_quantiles, keep_efi=keep_efi)
     main.reserve()
     if spectra:
       _spectra.ensure_tables(native, template0, lmax)
@@ -1276,9 +1333,10 @@ class EnsembleRollout:
       store = verification.ScoredStore(handle, M, weights, events=dev,
                                        thresholds=None if dev is None else packed(dev, dtemplate, dscale, dloc), weight_q=wq,
                                        source=native, order=order, energy=eplan(dtemplate), variogram=vplan,
-                                       climatology=clim_view, climatology_source=clim_handle, **{how: dplan},
+                                       climatology=clim_view, climatology_source=clim_handle, efi=efi, **{how: dplan},
                                        **per_store_args(name, dtemplate, dscale, dloc))
-      run.views[name] = _StoreSeries(store, dscale, dtemplate, keep_members=keep_members, keep_quantiles=keep_quantiles)
+      run.views[name] = _StoreSeries(store, dscale, dtemplate, keep_members=keep_members, keep_quantiles=keep_quantiles,
+                                     keep_efi=keep_efi)
     for store in (v.store for v in run.views.values()):
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
       store.set_per_score = sum(1 for v in run.views.values() if v.store.handle is store.handle) > 1

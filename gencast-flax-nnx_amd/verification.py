@@ -57,6 +57,12 @@ also gets, from the code bytes of the events, the neighbourhood ensemble probabi
 eight radii; `FractionsScores` keeps the four raw sums per (threshold, scale, batch, channel) and derives the fractions skill
 score and the smallest skilful scale.  It rides on `EventScores.fractions`.
 
+The Extreme Forecast Index (`gc_ens_efi_*`): the members ranked, point by point, in the K samples of that
+second handle -- how far the forecast distribution is shifted against the climatological one, weighted towards the tails.
+`efi_table` makes the table the device looks up, `EfiSpec` names the climatological events of the truth the index is verified
+against, `EfiScores` keeps the raw sums and integer tables and derives the mean index, its correlation with the observed
+index and the ROC.
+
 Regions (`gc_ens_region_score`): the sums of `EnsembleScores` per named set of grid nodes -- tropics,
 extratropics, land, sea, boxes -- every region from one pass over the nodes that belong to any.  `RegionSpec` holds the masks
 and builds boxes from bounds; `RegionScores[name]` is the region's `EnsembleScores`.
@@ -2208,6 +2214,178 @@ class VariogramScores(AdditiveScores):
 
 
 # ---------------------------------------------------------------------------------------------
+# extreme forecast index: the members ranked in the climatological samples (gc_ens_efi_*)
+# ---------------------------------------------------------------------------------------------
+def efi_table(n_climatology: int) -> np.ndarray:
+  """a[n] = asin(2 n / K - 1) / pi for n = 0 .. K, float64 [K + 1]: the table `gc_ens_efi_score` looks up.  The upper half
+  is formed with `np.arcsin` and mirrored, so a[K - n] == -a[n] to the bit, a[K / 2] == 0 for even K, a[0] = -0.5 and
+  a[K] = 0.5 exactly: a member above every sample adds a[K] + a[K] = 1."""
+  K = int(n_climatology)
+  if not 2 <= K <= 64:
+    raise ValueError(f"the number of climatological samples must be in 2..64, got {n_climatology}")
+  a = np.zeros(K + 1, dtype=np.float64)
+  upper = np.arange(K // 2 + 1, K + 1)
+  a[upper] = np.arcsin((2.0 * upper - K) / K) / np.pi
+  a[K - upper] = -a[upper]
+  return a
+
+
+class EfiSpec:
+  """What `gc_ens_efi_score` verifies the index against: T (0..4) climatological events of the truth and E (2..32) equal EFI
+  bins.  `quantiles` [T] in (0, 1) with `directions` [T]: +1 is "the truth lies above the q-quantile of the samples"
+  (lt(y) >= ceil(q K - 1e-9)), -1 "below it" (le(y) <= floor(q K + 1e-9)); or `ranks` [T], the integers themselves, for every
+  K.  No units: ranks are unchanged by any increasing map applied to members, samples and truth alike."""
+
+  def __init__(self, quantiles: Optional[Sequence[float]] = (0.9, 0.1), directions: Sequence[int] = (+1, -1), bins: int = 20, *,
+               ranks: Optional[Sequence[int]] = None):
+    if ranks is not None:
+      if any(isinstance(r, bool) or int(r) != r for r in ranks):
+        raise ValueError("ranks must be integers")
+      self.ranks, self.quantiles = tuple(int(r) for r in ranks), None
+    else:
+      self.ranks, self.quantiles = None, tuple(float(q) for q in quantiles)
+      if not all(0.0 < q < 1.0 for q in self.quantiles):
+        raise ValueError("quantiles must lie in (0, 1)")
+    self.directions = tuple(int(np.sign(d)) for d in directions)
+    T = len(self.ranks if self.quantiles is None else self.quantiles)
+    if T > 4:
+      raise ValueError(f"at most 4 events, got {T}")
+    if len(self.directions) != T or any(d == 0 for d in self.directions):
+      raise ValueError(f"directions must be {T} non-zero signs")
+    if isinstance(bins, bool) or int(bins) != bins or not 2 <= int(bins) <= 32:
+      raise ValueError(f"bins must be an integer in 2..32, got {bins!r}")
+    self.bins = int(bins)
+
+  @property
+  def n_events(self) -> int:
+    return len(self.directions)
+
+  def ranks_for(self, n_climatology: int) -> Tuple[int, ...]:
+    """The integer rank of every event for K samples: ceil(q K - 1e-9) upwards, floor(q K + 1e-9) downwards (0.9 * 30 is 27,
+    whatever the product rounds to)."""
+    if self.quantiles is None:
+      return self.ranks
+    K = int(n_climatology)
+    return tuple(int(math.ceil(q * K - 1e-9)) if d > 0 else int(math.floor(q * K + 1e-9))
+                 for q, d in zip(self.quantiles, self.directions))
+
+
+class EfiScores(AdditiveScores):
+  """The raw results of `gc_ens_efi_score`: `sums` [B, c_out, 6] float64 = sum w (1, f, o, f o, f^2, o^2) over the counted
+  nodes -- f the EFI, o the observed index -- and the integer tables `weighted` / `counts` [T, B, c_out, 2, E] uint64 (axis -2:
+  the truth outside / inside event t, axis -1: the EFI bin [-1 + 2 e / E, -1 + 2 (e + 1) / E), f = 1 in the last), with M,
+  K, the ranks and directions of the events, the `scale` of the quantised node weights and the points `invalid`.  All of
+  it adds over dates.  Scores of the sums are [B, c_out], scores of the tables [T, B, c_out]; a zero denominator gives NaN.
+  The ROC is that of the warning "f >= threshold" for an upper event (direction +1) and "f < threshold" for a lower one."""
+  _adds = ("sums", "weighted", "counts", "invalid")
+  _same = {"n_members": "members", "n_climatology": "climatological samples", "ranks": "ranks", "directions": "directions",
+           "scale": "scale"}
+  _listed = ("efi_mean", "observed_mean", "correlation", "valid_weight")
+  _what = "EFI scores"
+
+  def __init__(self, sums, weighted, counts, n_members: int, n_climatology: int, ranks: Sequence[int] = (),
+               directions: Sequence[int] = (), scale: float = 1.0, invalid: int = 0):
+    self.sums = np.asarray(sums, dtype=np.float64)
+    self.weighted = np.asarray(weighted, dtype=np.uint64)
+    self.counts = np.asarray(counts, dtype=np.uint64)
+    self.n_members, self.n_climatology, self.invalid = int(n_members), int(n_climatology), int(invalid)
+    self.ranks, self.directions = tuple(int(r) for r in ranks), tuple(int(np.sign(d)) for d in directions)
+    self.scale = float(scale)
+    if self.n_members < 2 or self.n_climatology < 2:
+      raise ValueError("n_members and n_climatology must be >= 2")
+    if self.sums.ndim != 3 or self.sums.shape[-1] != 6:
+      raise ValueError(f"sums must be [batch, channels, 6], got {self.sums.shape}")
+    T = len(self.ranks)
+    if len(self.directions) != T or any(d == 0 for d in self.directions):
+      raise ValueError(f"directions must be {T} non-zero signs")
+    if (self.weighted.ndim != 5 or self.weighted.shape[:4] != (T,) + self.sums.shape[:2] + (2,)
+        or not 2 <= self.weighted.shape[4] <= 32):
+      raise ValueError(f"weighted must be [{T}, {self.sums.shape[0]}, {self.sums.shape[1]}, 2, E] with E in 2..32, "
+                       f"got {self.weighted.shape}")
+    if self.counts.shape != self.weighted.shape:
+      raise ValueError(f"counts must be {self.weighted.shape}, got {self.counts.shape}")
+    if not (self.scale > 0.0 and math.isfinite(self.scale)):
+      raise ValueError("scale must be positive and finite")
+
+  _ratio = staticmethod(ClimatologyScores._ratio)
+
+  @property
+  def n_bins(self) -> int:
+    return int(self.weighted.shape[-1])
+
+  @property
+  def valid_weight(self) -> np.ndarray:
+    return self.sums[..., 0]
+
+  @property
+  def efi_mean(self) -> np.ndarray:
+    """The weighted mean EFI over the counted nodes."""
+    return self._ratio(self.sums[..., 1], self.sums[..., 0])
+
+  @property
+  def observed_mean(self) -> np.ndarray:
+    return self._ratio(self.sums[..., 2], self.sums[..., 0])
+
+  @property
+  def correlation(self) -> np.ndarray:
+    """The weighted (centred) correlation of the EFI and the observed index."""
+    s0 = self.sums[..., 0]
+    mf, mo = self.efi_mean, self.observed_mean
+    cov = self._ratio(self.sums[..., 3], s0) - mf * mo
+    vf, vo = self._ratio(self.sums[..., 4], s0) - mf * mf, self._ratio(self.sums[..., 5], s0) - mo * mo
+    prod = vf * vo
+    return self._ratio(cov, np.sqrt(np.where(prod > 0.0, prod, np.nan)))
+
+  # -- the tables in float64 (exact: see quantize_node_weights), the bins in the order of rising alarm ---------
+  def _tables(self) -> Tuple[np.ndarray, np.ndarray]:
+    """(o_e, n_e - o_e) [T, B, c_out, E]: the weight of the truth inside / outside the event per bin, the bins of a lower
+    event reversed so that the warning is always "bin >= j"."""
+    inside = self.weighted[..., 1, :].astype(np.float64) / self.scale
+    outside = self.weighted[..., 0, :].astype(np.float64) / self.scale
+    for t, d in enumerate(self.directions):
+      if d < 0:
+        inside[t], outside[t] = inside[t, ..., ::-1].copy(), outside[t, ..., ::-1].copy()
+    return inside, outside
+
+  @property
+  def base_rate(self) -> np.ndarray:
+    """How often the truth lay in the event, [T, B, c_out]."""
+    inside, outside = self._tables()
+    return self._ratio(inside.sum(-1), inside.sum(-1) + outside.sum(-1))
+
+  def _rates(self) -> Tuple[np.ndarray, np.ndarray]:
+    """Hit rate and false-alarm rate of the warnings j = 0 .. E ("bin >= j" in the order of rising alarm): [T, B, c_out, E + 1]."""
+    inside, outside = self._tables()
+    zero = np.zeros(inside.shape[:-1] + (1,))
+    tail = lambda a: np.concatenate([np.cumsum(a[..., ::-1], axis=-1)[..., ::-1], zero], axis=-1)
+    return self._ratio(tail(inside), inside.sum(-1)[..., None]), self._ratio(tail(outside), outside.sum(-1)[..., None])
+
+  def _level(self, threshold: float) -> np.ndarray:
+    """The warning level j [T] of an EFI threshold, which must be a bin edge -1 + 2 j / E."""
+    E = self.n_bins
+    edge = (float(threshold) + 1.0) * 0.5 * E
+    j = int(round(edge))
+    if abs(edge - j) > 1e-9 or not 0 <= j <= E:
+      raise ValueError(f"threshold must be a bin edge -1 + 2 j / {E}, j = 0 .. {E}, got {threshold}")
+    return np.array([j if d > 0 else E - j for d in self.directions], dtype=np.int64)   # (a lower event: bins reversed)
+
+  def hit_rate(self, threshold: float) -> np.ndarray:
+    """Of the warning at EFI `threshold` (a bin edge): the weight of the warned events over that of all events, [T, B, c_out]."""
+    h, _ = self._rates()
+    return np.stack([h[t, ..., j] for t, j in enumerate(self._level(threshold))]) if len(self.ranks) else h[..., 0]
+
+  def false_alarm_rate(self, threshold: float) -> np.ndarray:
+    _, f = self._rates()
+    return np.stack([f[t, ..., j] for t, j in enumerate(self._level(threshold))]) if len(self.ranks) else f[..., 0]
+
+  @property
+  def roc_area(self) -> np.ndarray:
+    """The trapezoid rule through the E + 1 points (false-alarm rate, hit rate) of the bin edges, [T, B, c_out]."""
+    h, f = self._rates()
+    return (0.5 * (f[..., :-1] - f[..., 1:]) * (h[..., :-1] + h[..., 1:])).sum(axis=-1)
+
+
+# ---------------------------------------------------------------------------------------------
 # the scorers of a member store, each declared once
 # ---------------------------------------------------------------------------------------------
 class Scorer(NamedTuple):
@@ -2301,8 +2479,24 @@ SCORERS = [
 ]
 
 
+def _set_efi(store):
+  store._efi_set_for = None                     # (the ranks need K: the next `score_efi` hands them over)  pylint: disable=protected-access
+
+
+def _score_efi(store, truth):
+  return store.score_efi(truth)
+
+
+# The extreme forecast index, scored next to the climatology row (it reads the same second handle, after that row has
+# filled it).  It stands beside the table, not in it: the series of the table's rows are a recorded public surface
+# (tests/test_scorer_table.py) that a new name would change, so the results carry `efi` as they carry `features` -- an
+# attribute that exists only on the result of a run that asked for it.
+EFI_SCORER = Scorer("efi", "extreme forecast index", set=_set_efi, score=_score_efi, scaled=False,
+                    carried_by=("ensemble", "derived"))
+
+
 def scorer(name: str) -> Scorer:
-  return next(row for row in SCORERS if row.name == name)
+  return next(row for row in SCORERS + [EFI_SCORER] if row.name == name)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2329,8 +2523,9 @@ class ScoredStore:
   a handle, or thresholds that change from call to call (assign `thresholds` before the call)."""
 
   def __init__(self, handle, n_members: int, node_weight=None, *, plan=None, source=None, set_per_score: bool = False,
-               climatology=None, climatology_source=None, feature_plan=None, band_plan=None, **scorers):
-    """`scorers`: per row of `SCORERS` with a `score`, its name (what switches it on) and its settings, None by default."""
+               climatology=None, climatology_source=None, feature_plan=None, band_plan=None, efi=None, **scorers):
+    """`scorers`: per row of `SCORERS` with a `score`, its name (what switches it on) and its settings, None by default.
+    `efi`: an `EfiSpec` for `score_efi` (it needs the `climatology` handle, and `weight_q` where it has events)."""
     for row in (r for r in SCORERS if r.score is not None):
       for key in (row.name,) + row.settings:
         setattr(self, key, scorers.pop(key, None))
@@ -2342,6 +2537,14 @@ class ScoredStore:
       raise ValueError("a climatology source goes with a climatology handle and a derive plan (or a band plan)")
     if self.events is not None and self.weight_q is None:
       raise ValueError("events need the quantised node weights (quantize_node_weights)")
+    if efi is not None:
+      if not isinstance(efi, EfiSpec):
+        raise TypeError("efi must be an EfiSpec")
+      if climatology is None:
+        raise ValueError("the extreme forecast index needs a climatology handle")
+      if efi.n_events and self.weight_q is None:
+        raise ValueError("the events of an EfiSpec need the quantised node weights (quantize_node_weights)")
+    self.efi, self._efi_set_for = efi, None      # (K the events and bins were last handed over for)
     if plan is not None and feature_plan is not None:
       raise ValueError("a store is filled by a derive plan or by a feature plan, not both")
     if band_plan is not None and (plan is not None or feature_plan is not None):
@@ -2374,7 +2577,7 @@ class ScoredStore:
     """The plan, then every scorer that is switched on, in the order of `SCORERS` -- the thresholds, the probabilities, the
     multivariate plans, the tails and the regions: all survive `ens_reserve` and every score."""
     self._set_plan()
-    for row in SCORERS:
+    for row in SCORERS + [EFI_SCORER]:
       if row.set is not None and getattr(self, row.name) is not None:
         row.set(self)
 
@@ -2426,6 +2629,15 @@ class ScoredStore:
       self.climatology.ens_reserve(K)
       self._clim_reserved = K
 
+  def load_climatology(self, fields) -> int:
+    """The K (2..64) samples [G, B, c_out], in the members' units, into the climatology handle's store (reserved again only
+    when K changes) -> K."""
+    K = len(fields)
+    self._reserve_climatology(K)
+    for j, f in enumerate(fields):
+      self.climatology.ens_push_host(j, f)
+    return K
+
   def score_climatology(self, fields=None, truth=None, *, n_samples: Optional[int] = None,
                         source_truth=None) -> Optional["ClimatologyScores"]:
     """The members against a climatology (None without a climatology handle).  `fields`: the K (2..64) samples
@@ -2448,14 +2660,37 @@ class ScoredStore:
         self._clim_plan_set = True
       (self.climatology.ens_band if band else self.climatology.ens_derive)(self.climatology_source, source_truth)
     elif fields is not None:
-      K = len(fields)
-      self._reserve_climatology(K)
-      for j, f in enumerate(fields):
-        self.climatology.ens_push_host(j, f)
+      K = self.load_climatology(fields)
     else:
       K = self._clim_reserved
     sums, counts, invalid = self.handle.ens_clim_score(self.climatology, truth)
     return ClimatologyScores(sums, counts, self.n_members, K, invalid)
+
+  def score_efi(self, truth=None, *, n_samples: Optional[int] = None) -> Optional["EfiScores"]:
+    """The extreme forecast index of the members against the samples in the climatology handle's store, verified against
+    the truth (None without an `EfiSpec`): call it after `score_climatology`, which fills that store.  `n_samples`: K of a
+    store somebody else filled; `truth` None: the truth already on the device.  Both fields stay on the device
+    (`efi_fields`)."""
+    if self.efi is None:
+      return None
+    K = self._clim_reserved if n_samples is None else int(n_samples)
+    ranks = self.efi.ranks_for(K)
+    if self.set_per_score or self._efi_set_for != K:
+      self.handle.ens_efi_set(ranks, self.efi.directions, self.efi.bins, None if self.weight_q is None else self.weight_q[0])
+      self._efi_set_for = K
+    sums, weighted, counts, invalid = self.handle.ens_efi_score(self.climatology, efi_table(K), truth)
+    return EfiScores(sums, weighted, counts, self.n_members, K, ranks, self.efi.directions,
+                     1.0 if self.weight_q is None else self.weight_q[1], invalid)
+
+  def efi_field_without_truth(self) -> np.ndarray:
+    """The EFI field [G, B, c_out] of the members against the samples in the climatology handle's store, downloaded: no truth,
+    no weights, no events (`gc_ens_efi_fields`) -- what a real forecast, one without an analysis, can ask."""
+    self.handle.ens_efi_fields(self.climatology, efi_table(self._clim_reserved))
+    return self.handle.ens_efi_field(0)
+
+  def efi_fields(self, *, observed: bool = True) -> Tuple[np.ndarray, ...]:
+    """The EFI field [G, B, c_out] of the last `score_efi`, downloaded, and with `observed` the observed index too."""
+    return tuple(self.handle.ens_efi_field(i) for i in range(2 if observed else 1))
 
   def centres(self) -> Dict[str, list]:
     """The centres the last `score` found on a store with a `feature_plan` (`ens_feature_centres`), as `unpack_centres`

@@ -766,6 +766,54 @@ int gc_ens_clim_score(gc_handle* h, gc_handle* clim, const float* truth /* NULL 
                       uint64_t* invalid /* [1], NULL allowed */);
 
 /*
+ * The Extreme Forecast Index on the device (Lalaurette 2003, Zsoter 2006): at every point, how far
+ * the M members of `h` are shifted against the K climatological samples in the store of `clim` (the second handle of
+ * gc_ens_clim_score: same device, G, batch and c_out; 2 <= M, K <= 64), weighted towards the tails
+ * (gencast-flax-nnx_amd/verification.py EfiScores).  The reference project has no verification code; the yardstick is the
+ * definition below, restated in float64 in tests/efi_reference.py.  Per point, comparisons on the float32 values:
+ *   le(v) = #{j : c_j <= v}     lt(v) = #{j : c_j < v}
+ *   f = (sum_i (a[le(x_i)] + a[lt(x_i)])) / M        i ascending, in double: the EFI, in [-1, 1]
+ *   o = a[le(y)] + a[lt(y)]                          the observed index: the same expression for the truth alone
+ * `table` is a[0 .. K] = asin(2 n / K - 1) / pi, made on the host (verification.efi_table): this is the integral
+ * (2 / pi) int_0^1 (p - F_f(p)) / sqrt(p (1 - p)) dp in closed form, ties counted half.  The device does comparisons, integer
+ * counts, lookups, double additions in slot order and one division, so both fields (float32, rounded once) equal the
+ * float64 reference byte for byte.  A point counts when y, all M members and all K samples are finite; elsewhere both
+ * fields are NaN and the point adds to `invalid` alone.  Per column (b, c), over the counted nodes, w [G] the node weights:
+ *   sums[b][c][0..5] = sum w, sum w f, sum w o, sum w f o, sum w f^2, sum w o^2        (f in double, before rounding)
+ * in double, every sum in one fixed order (no atomics on floats): the same call twice returns identical bytes.  For event
+ * t < T of the truth -- direction > 0: lt(y) >= rank_t, direction < 0: le(y) <= rank_t -- and the EFI bin
+ * e = min(E - 1, (int)((f + 1) E / 2)):
+ *   weighted[t][b][c][o_t][e] += wq[g]      counts[t][b][c][o_t][e] += 1              (wq: the integer weights of gc_ens_event_set)
+ * integers, compared with ==.  Everything is raw and additive over batches and dates; mean EFI, the correlation of f and o
+ * and the ROC of the index against the event are formed on the host.
+ *   gc_ens_efi_set       the events and the bins.  Needs gc_set_graph only; survives gc_ens_reserve; replaces an earlier
+ *                        setting; wq [G] may be NULL when n_events == 0.
+ *                        GC_ERR_INVALID_ARGUMENT: n_events outside 0..4, n_bins outside 2..32, a direction of 0, a NULL array.
+ *   gc_ens_efi_score     truth: host [G, B, c_out], uploaded and kept, or NULL = the truth uploaded last.  sums is required,
+ *                        weighted where T > 0; counts (the shape of weighted) and invalid [1] may be NULL.  Three launches on
+ *                        h's stream, ordered behind clim's stream by an event: the index pass (the K samples of a point
+ *                        in registers, the M members streamed past them; fields, one 16-bit code per point, per-block
+ *                        column sums), the ascending block finish, the table pass over the codes.  Synchronous.
+ *   gc_ens_efi_fields    the EFI field alone: no truth, no weights and no gc_ens_efi_set needed, nothing returned.
+ *   gc_ens_efi_download  field 0 (the EFI) or 1 (the observed index) of the last of the two calls on this store.
+ *   GC_ERR_STATE: no gc_set_graph, no member store on either handle, a slot of either not pushed (of clim's: "climatology
+ *   member slot ..."), no gc_ens_efi_set, no node weights, no truth; download: no fields of this store on the device
+ *   (gc_ens_reserve and every call that rewrites the store forget them), or the observed index after gc_ens_efi_fields.
+ *   GC_ERR_INVALID_ARGUMENT: clim NULL or == h, table or sums NULL, clim on another device or with another G, batch or
+ *   c_out, a table that is not antisymmetric (a[K - n] == -a[n]) and non-decreasing, `which` outside 0..1.
+ * Counters (on h): "ens_efi_calls", "ens_efi_device_us" (HIP-event time of the last call's launches),
+ * "ens_efi_invalid_points" (of the last gc_ens_efi_score).
+ */
+int gc_ens_efi_set(gc_handle* h, int32_t n_events /* T, 0..4 */, const int32_t* rank /* [T] */, const int32_t* direction /* [T] */,
+                   int32_t n_bins /* E, 2..32 */, const uint32_t* wq /* [G]; NULL allowed when T == 0 */);
+int gc_ens_efi_score(gc_handle* h, gc_handle* clim, const double* table /* [K + 1] */,
+                     const float* truth /* NULL = the truth uploaded last */, double* sums /* [B][c_out][6] */,
+                     uint64_t* weighted /* [T][B][c_out][2][E] */, uint64_t* counts /* as weighted, NULL allowed */,
+                     uint64_t* invalid /* [1], NULL allowed */);
+int gc_ens_efi_fields(gc_handle* h, gc_handle* clim, const double* table /* [K + 1] */);
+int gc_ens_efi_download(gc_handle* h, int32_t which /* 0 EFI, 1 observed index */, float* field /* [G,B,c_out] */);
+
+/*
  * Time-window ensemble fields on the device: accumulations, means, changes and extremes over the
  * last L lead times of a rollout -- 24 h precipitation from 12 h steps, a weekly mean, the highest wind speed within three
  * days -- formed from the members and the truths that one handle's gc_ens_* store held at those lead times and left in the
