@@ -77,8 +77,9 @@ Rccl& rccl() {
     }                                                                                       \
   } while (0)
 
-// The counters of the units that keep a Meter.  A unit with a regular name has <prefix>_calls and <prefix>_device_us, and
-// <prefix>_invalid_points where it counts skipped points; the names that do not follow are rows of their own.
+// The counters of the units that keep a Meter.  A unit with a regular name has <prefix>_calls, <prefix>_device_us and
+// <prefix>_blocks (Meter, gc_handle.h), and <prefix>_invalid_points where it counts skipped points; the names that do not
+// follow are rows of their own.
 const int64_t* meter_counter(const gc_handle* h, const std::string& n) {
   struct Unit { const char* prefix; Meter gc_handle::*meter; bool invalid_points; };
   static const Unit units[] = {
@@ -91,6 +92,8 @@ const int64_t* meter_counter(const gc_handle* h, const std::string& n) {
       {"ens_scores", &gc_handle::ens, &Meter::calls},
       {"ens_score_device_us", &gc_handle::ens, &Meter::device_us},
       {"ens_invalid_points", &gc_handle::ens, &Meter::invalid},
+      {"ens_score_blocks", &gc_handle::ens, &Meter::blocks},
+      {"ens_fss_chunks", &gc_handle::fss, &Meter::chunks},
       {"spec_calls", &gc_handle::spec, &Meter::calls},
       {"spec_device_us", &gc_handle::spec, &Meter::device_us},
       {"spec_invalid_columns", &gc_handle::spec, &Meter::invalid},
@@ -105,6 +108,7 @@ const int64_t* meter_counter(const gc_handle* h, const std::string& n) {
     const Meter& m = h->*u.meter;
     if (n.compare(len, std::string::npos, "_calls") == 0) return &m.calls;
     if (n.compare(len, std::string::npos, "_device_us") == 0) return &m.device_us;
+    if (n.compare(len, std::string::npos, "_blocks") == 0) return &m.blocks;
     if (u.invalid_points && n.compare(len, std::string::npos, "_invalid_points") == 0) return &m.invalid;
   }
   return nullptr;

@@ -216,6 +216,7 @@ int gc_ens_clim_score(gc_handle* h, gc_handle* clim, const float* truth, double*
              });
   if (rc) return rc;
   h->clim.invalid = (int64_t)cnt.back();
+  h->clim.blocks = blocks;
   if (counts)
     for (size_t i = 0; i + 1 < cnt.size(); ++i) counts[i] = cnt[i];
   if (invalid) invalid[0] = cnt.back();

@@ -414,12 +414,17 @@ static int drv_tile(int pool, int n_lon, int W) {
   return wt;
 }
 
+// node blocks of the point pass: q nodes each per trip of its grid-stride walk, at most 1024
+static int drv_point_blocks(int G, int W) {
+  const int q = 256 / std::min(256, W);
+  return std::max(1, std::min(1024, (G + q - 1) / q));
+}
+
 static hipError_t launch_ens_derive(hipStream_t s, const float* smem, const float* struth, float* dmem, float* dtruth, int M,
                                     int G, int B, int c_src, int c_d, const int* op, const int* src_a, const int* src_b,
                                     const double* affine) {
   const int W = B * c_d;
-  const int q = 256 / std::min(256, W);
-  const int blocks = std::max(1, std::min(1024, (G + q - 1) / q));
+  const int blocks = drv_point_blocks(G, W);
   hipLaunchKernelGGL(gc_ens_derive_kernel, dim3(blocks, (W + 255) / 256, M + 1), dim3(256), 0, s, smem, struth, dmem, dtruth, M,
                      G, B, c_src, c_d, op, src_a, src_b, affine);
   return hipGetLastError();
@@ -428,8 +433,7 @@ static hipError_t launch_ens_derive(hipStream_t s, const float* smem, const floa
 static hipError_t launch_ens_derive_expr(hipStream_t s, const float* smem, const float* struth, float* dmem, float* dtruth, int M,
                                          int G, int B, int c_src, int c_d, const DrvExpr& g) {
   const int W = B * c_d;
-  const int q = 256 / std::min(256, W);
-  const int blocks = std::max(1, std::min(1024, (G + q - 1) / q));
+  const int blocks = drv_point_blocks(G, W);
   hipLaunchKernelGGL(gc_ens_derive_expr_kernel, dim3(blocks, (W + 255) / 256, M + 1), dim3(256), (size_t)g.n_terms * kDrvTermBytes,
                      s, smem, struth, dmem, dtruth, M, G, B, c_src, c_d, g);
   return hipGetLastError();
@@ -746,6 +750,7 @@ int gc_ens_derive(gc_handle* h, gc_handle* src, const float* truth) {
              },
              no_readbacks);
   if (rc) return rc;
+  h->drv.blocks = gc::drv_point_blocks(G, W);
   fill_close(h);
   return GC_OK;
   });

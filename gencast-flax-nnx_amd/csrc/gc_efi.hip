@@ -222,10 +222,15 @@ static hipError_t launch_ens_efi(hipStream_t s, const float* mem, int M, const f
   });
 }
 
+// node-range blocks of the table pass: within kEfiMaxWorkgroups for the whole grid
+static int efi_table_blocks(int G, int W, int T, int E) {
+  return node_blocks(G, 256 / efi_tile_width(W, E), kEfiMaxWorkgroups / (T * efi_tiles(W, E)));
+}
+
 static hipError_t launch_ens_efi_table(hipStream_t s, const unsigned short* code, const unsigned* wq, int G, int W, int T, int E,
                                        unsigned long long* weighted, unsigned long long* counts) {
   const int tiles = efi_tiles(W, E), tile_w = efi_tile_width(W, E);
-  const int blocks = node_blocks(G, 256 / tile_w, kEfiMaxWorkgroups / (T * tiles));
+  const int blocks = efi_table_blocks(G, W, T, E);
   const int per = (G + blocks - 1) / blocks;
   const size_t lds = (size_t)tile_w * efi_stride(E) * (sizeof(unsigned long long) + sizeof(unsigned));
   hipLaunchKernelGGL(gc_ens_efi_table_kernel, dim3(blocks, T, tiles), dim3(256), lds, s, code, wq, G, W, E, tile_w, per, weighted,
@@ -363,6 +368,7 @@ int gc_ens_efi_score(gc_handle* h, gc_handle* clim, const double* table, const f
              });
   if (rc) return rc;
   h->efi.invalid = (int64_t)inv;
+  h->efi.blocks = T > 0 ? gc::efi_table_blocks(G, W, T, E) : blocks;
   h->efi_fields = 2;
   if (invalid) invalid[0] = inv;
   return GC_OK;
@@ -391,6 +397,7 @@ int gc_ens_efi_fields(gc_handle* h, gc_handle* clim, const double* table) {
              },
              no_readbacks);
   if (rc) return rc;
+  h->efi.blocks = blocks;
   h->efi_fields = 1;
   return GC_OK;
   });

@@ -400,6 +400,7 @@ int gc_ens_score(gc_handle* h, const float* truth, int32_t want_fields, double* 
              });
   if (rc) return rc;
   h->ens.invalid = (int64_t)hist.back();
+  h->ens.blocks = blocks;
   if (rank_hist)
     for (size_t i = 0; i + 1 < hist.size(); ++i) rank_hist[i] = hist[i];
   return GC_OK;

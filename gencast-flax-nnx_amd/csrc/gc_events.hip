@@ -281,6 +281,7 @@ int gc_ens_event_score(gc_handle* h, const float* truth, uint64_t* weighted, uin
     if (invalid) invalid[t] = inv[(size_t)t];
   }
   h->evt.invalid = total;
+  h->evt.blocks = gc::evt_node_blocks(G, W, M, T);
   h->evt_scored = true;
   return GC_OK;
   });

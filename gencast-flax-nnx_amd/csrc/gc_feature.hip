@@ -383,6 +383,7 @@ int gc_ens_feature(gc_handle* h, gc_handle* src, const float* truth) {
              },
              no_readbacks);
   if (rc) return rc;
+  h->feat.blocks = std::min(nblk, 1024);             // of the gather, the one pass that walks the nodes grid-stride
   fill_close(h);
   h->d_feat_count = l_count;
   h->d_feat_node = l_node;

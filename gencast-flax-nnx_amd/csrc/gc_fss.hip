@@ -353,6 +353,8 @@ int gc_ens_fss_score(gc_handle* h, double* sums) {
   const int wt = gc::fss_tile(n_lon, W), wc = gc::fss_chunk(S, G, W, wt), blocks = gc::fss_blocks(G, wc);
   if ((rc = fss_work(h, wc, blocks))) return rc;
   hipStream_t s = h->stream;
+  h->fss.blocks = blocks;                            // of the column pass
+  h->fss.chunks = (W + wc - 1) / wc;                 // column chunks every threshold goes through
   return timed(h, h->fss,
                [&]() -> int {
                  for (int t = 0; t < T; ++t) {

@@ -153,12 +153,22 @@ struct Bracket {
   }
 };
 
-// What a unit keeps of its timed calls (gci::timed, gc_store.h): the events of the last one, and the three numbers
-// gc_get_counter reports -- calls made, device time of the last, and what the last skipped (points or columns; 0 in a
-// unit that counts none).
+// What a unit keeps of its timed calls (gci::timed, gc_store.h): the events of the last one, and the numbers
+// gc_get_counter reports -- calls made, device time of the last, what the last skipped (points or columns; 0 in a
+// unit that counts none), and the launch geometry of the last: `blocks` is grid.x of its main pass, the node-range
+// workgroups (the regime a call ran in: below a unit's block cap every workgroup has nodes, above it `per` grows and the
+// trailing ones may have none); `chunks` the column chunks it went through (gc_ens_fss_score alone; 0 elsewhere).  A
+// call with two passes of different geometry reports the pass that has a cap of its own:
+//   gc_ens_efi_score    the table pass (kEfiMaxWorkgroups / (T tiles)) where T > 0, else the index pass;
+//   gc_ens_efi_fields   the index pass (loss_reduce_blocks), the only one it has;
+//   gc_ens_order_score  the sorting pass (ord_blocks);   gc_ens_order_fields  its field pass (loss_reduce_blocks of one tile);
+//   gc_ens_derive       the point pass (launch_ens_derive / launch_ens_derive_expr), not the pooling passes;
+//   gc_ens_fss_score    the column pass (fss_blocks);
+//   gc_ens_feature, gc_ens_band  their gather (grid-stride by gridDim.x * 256; one thread per gathered value): neither
+//                       has a node-range pass or a cap that bites below 262 144 nodes.
 struct Meter {
   Bracket time;
-  int64_t calls = 0, device_us = 0, invalid = 0;
+  int64_t calls = 0, device_us = 0, invalid = 0, blocks = 0, chunks = 0;
   explicit Meter(std::vector<Event*>& of_handle) : time(of_handle) {}
 };
 

@@ -35,16 +35,16 @@ constexpr int kMvTile = 256;                     // points of a tile: one per th
 // 32-lane half own consecutive pairs, so their rows i are consecutive but for one wrap (pair (j - 1, j) is followed by
 // (0, j + 1)): at most a 2-way conflict on the lanes around the wrap, none elsewhere
 constexpr int kMvLd = kMvTile + 1;
-constexpr size_t kMvPartBytes = (size_t)64 << 20;   // cap of the per-block partials of the energy pass
+constexpr int kMvMaxWorkgroups = 2048;           // of the energy pass, over all (b, k): about eight per CU
 
 static int mv_pairs(int M) { return M * (M + 1) / 2; }
 // pairs a thread owns: 1 (P <= 256, the spare threads then take slices of the tile), 3 or 9 (P <= 2080 at M = 64)
 static int mv_npp(int P) { return P <= 256 ? 1 : P <= 768 ? 3 : 9; }
-// node-range blocks of one (b, k): a tile of work each or more, about eight workgroups per CU in all, the partials capped
-static int mv_energy_blocks(int G, int BK, int P, int nc_max) {
+// node-range blocks of one (b, k): a tile of work each or more, kMvMaxWorkgroups in all.  That cap also bounds the
+// per-block partials: blocks BK <= 2048 rows of P <= 2080 doubles, 32.5 MB at the most.
+static int mv_energy_blocks(int G, int BK, int nc_max) {
   const long tiles = ((long)G * nc_max + kMvTile - 1) / kMvTile;
-  const long cap = (long)std::max<size_t>(1, kMvPartBytes / ((size_t)BK * P * sizeof(double)));
-  return (int)std::max<long>(1, std::min({tiles, (long)std::max(1, 2048 / BK), cap, (long)G}));
+  return (int)std::max<long>(1, std::min({tiles, (long)std::max(1, kMvMaxWorkgroups / BK), (long)G}));
 }
 
 // The energy pass.  Workgroup (x, y): node range [x per, (x + 1) per) of batch member b = y / K and group k = y % K; its
@@ -388,7 +388,7 @@ int gc_ens_energy_score(gc_handle* h, const float* truth, double* d2, double* s0
   if ((rc = take_truth(h, h, truth, "gc_ens_energy_score"))) return rc;
   const gc_config& c = h->cfg;
   const int G = h->hg.G, B = c.batch, M = h->ens_members, K = h->en_K, BK = B * K, P = gc::mv_pairs(M);
-  const int blocks = gc::mv_energy_blocks(G, BK, P, h->en_nc_max);
+  const int blocks = gc::mv_energy_blocks(G, BK, h->en_nc_max);
   const size_t n_out = (size_t)BK * P + BK;
   // sized by M and the plan
   if ((rc = sized_for(h, h->en_work_allocs, {(size_t)M, (size_t)K, (size_t)blocks}, buf(&h->d_en_part, (size_t)blocks * n_out),
@@ -416,6 +416,7 @@ int gc_ens_energy_score(gc_handle* h, const float* truth, double* d2, double* s0
              });
   if (rc) return rc;
   h->en.invalid = (int64_t)inv;
+  h->en.blocks = blocks;
   if (invalid) invalid[0] = inv;
   return GC_OK;
   });
@@ -467,6 +468,7 @@ int gc_ens_variogram_score(gc_handle* h, const float* truth, double* sums, uint6
   const int G = h->hg.G, B = c.batch, W = B * c.c_out, M = h->ens_members, O = h->vg_O;
   const int blocks = gc::loss_reduce_blocks(G, B, c.c_out);
   hipStream_t s = h->stream;
+  h->vg.blocks = blocks;
   return timed(h, h->vg,
                [&] {
                  return launch_each(h,

@@ -46,6 +46,8 @@ static int ord_blocks(int G, int W, int M, int Q) {
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / ((size_t)cap * ord_thread_bytes(M, Q))));
   return node_blocks(G, q, std::min(1024, 2 * kOrdCuCount * per_cu));
 }
+// ... of the field pass, which holds no accumulators: those of a pass over one 256-wide column tile
+static int ord_field_blocks(int G, int W) { return loss_reduce_blocks(G, 1, std::min(256, W)); }
 
 // v[idx] for a wave-uniform idx in [0, P): a tree of selects on the bits of idx, lowest first, over compile-time
 // indices -- P - 1 selects on log2 P conditions, and the array stays in registers
@@ -217,7 +219,7 @@ static hipError_t launch_ens_order(hipStream_t s, bool score, const float* mem, 
   const int Q = plan.Q;
   const int cap = score ? ord_cap(M, Q) : 256;
   const int tiles = ord_tiles(W, cap), tile_w = ord_tile_width(W, cap);
-  const int blocks = score ? ord_blocks(G, W, M, Q) : loss_reduce_blocks(G, 1, std::min(256, W));
+  const int blocks = score ? ord_blocks(G, W, M, Q) : ord_field_blocks(G, W);
   const int per = (G + blocks - 1) / blocks;
   const size_t lds = score ? (size_t)cap * ord_thread_bytes(M, Q) : 0;
   const dim3 grid(blocks, tiles);
@@ -313,6 +315,7 @@ int gc_ens_order_fields(gc_handle* h) {
              },
              no_readbacks);
   if (rc) return rc;
+  h->ord.blocks = gc::ord_field_blocks(G, W);
   h->ord_ready = true;
   return GC_OK;
   });
@@ -363,6 +366,7 @@ int gc_ens_order_score(gc_handle* h, const float* truth, double* bins, double* e
              });
   if (rc) return rc;
   h->ord.invalid = (int64_t)cnt.back();
+  h->ord.blocks = blocks;
   h->ord_ready = true;
   if (counts)
     for (size_t i = 0; i + 1 < cnt.size(); ++i) counts[i] = cnt[i];

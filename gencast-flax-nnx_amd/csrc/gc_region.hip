@@ -321,6 +321,7 @@ int gc_ens_region_score(gc_handle* h, const float* truth, double* sums, uint64_t
     if (invalid) invalid[r] = out[n_hist + r];
   }
   h->reg.invalid = total;
+  h->reg.blocks = blocks;                            // (the entries of the block table: one workgroup row each)
   if (hist)
     for (size_t i = 0; i < n_hist; ++i) hist[i] = out[i];
   return GC_OK;

@@ -580,6 +580,7 @@ int gc_ens_band(gc_handle* h, gc_handle* src, const float* truth) {
              [&] { return read_back(h, flags.data(), h->d_band_flags, flags.size()); });
   if (rc) return rc;
   h->band.invalid = flagged(flags);
+  h->band.blocks = (int64_t)(((size_t)h->hg.G * Nu + 255) / 256);   // of the gather, the one pass laid out over the nodes
   fill_close(h);
   return GC_OK;
   });

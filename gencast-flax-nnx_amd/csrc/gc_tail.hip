@@ -270,6 +270,7 @@ int gc_ens_tail_score(gc_handle* h, const float* truth, double* sums, uint64_t* 
     if (invalid) invalid[t] = skipped;
   }
   h->tail.invalid = total;
+  h->tail.blocks = blocks;
   if (counts)
     for (size_t i = 0; i < cnt.size(); ++i) counts[i] = cnt[i];
   return GC_OK;

@@ -1175,6 +1175,17 @@ int gc_algorithmic_work(gc_handle* h, double* flops, double* bytes);
  * gc_set_option "edge_term_cache_mb"), "edge_term_cache_bytes" (device bytes that cache holds now; 0: not built),
  * "loss_evaluations" (denoising-loss evaluations so far: gc_loss_resident / gc_loss), "loss_device_us" (HIP-event time of
  * the evaluations of the last gc_loss_resident call, microseconds). */
+/* Launch geometry of the last call of an ensemble unit (0 before its first call): "<prefix>_blocks" for the prefixes
+ * ens_event, ens_derive, ens_band, ens_order, ens_clim, ens_efi, ens_energy, ens_variogram, ens_tail, ens_region,
+ * ens_feature and ens_fss, and "ens_score_blocks" for gc_ens_score -- the node-range workgroups (grid.x) of the call's main
+ * pass.  Every pass caps that number (2048, 1024, 1024 / (thresholds x column tiles), 2048 / (batch x groups), 256 ...);
+ * above the cap a workgroup walks more nodes and the trailing workgroups may have none, so the counter says which regime
+ * a call ran in.  Where a call has two passes of different geometry it is the pass with a cap of its own:
+ * gc_ens_efi_score with events reports its table pass, without events (and gc_ens_efi_fields) the index pass;
+ * gc_ens_order_score the sorting pass, gc_ens_order_fields its field pass; gc_ens_derive the point pass, not the pooling
+ * passes; gc_ens_fss_score the column pass; gc_ens_region_score the entries of the plan's block table; gc_ens_feature and
+ * gc_ens_band, which have no node-range pass, the workgroups of their gather.  "ens_fss_chunks": the column chunks every
+ * threshold of the last gc_ens_fss_score went through (the work buffer's byte budget or the 256-column limit cut them). */
 /* ... and "device_allocations" (device buffers the handle holds now: gc_finalize and gc_set_noisy_slots replace theirs, they do not add),
  * "noise_stream" (the Philox stream the next drawn field will use: gc_noise_seed sets it, every initial-noise and churn field adds one). */
 int gc_get_counter(gc_handle* h, const char* name, int64_t* value);

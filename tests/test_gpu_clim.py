@@ -355,6 +355,9 @@ def test_full_size(case):
     _push_all(cl, clim)
     out = nd.ens_clim_score(cl, truth)
     print(f"{case}: ens_clim_device_us {nd.counter('ens_clim_device_us')}")
+    # the regime: loss_reduce_blocks = min(kLossMaxBlocks = 2048, ceil(G / (8 q))) -- nano: W = 32, q = 8, ceil(10512 / 64) =
+    # 165; one degree: W = 82, q = 3, 2715 -> 2048 (per = 32, 11 trailing workgroups without nodes)
+    assert nd.counter("ens_clim_blocks") == (165 if case == "nano" else 2048)
     _check(case, out, ref, G)
   finally:
     nd.close()

@@ -963,7 +963,11 @@ COUNTERS = (
     "ens_region_calls", "ens_region_device_us", "ens_region_invalid_points",
     "ens_feature_calls", "ens_feature_device_us",
     "ens_fss_calls", "ens_fss_device_us",
-    "ens_window_pushes", "ens_window_emits", "ens_window_device_us", "ens_window_ring_bytes")
+    "ens_window_pushes", "ens_window_emits", "ens_window_device_us", "ens_window_ring_bytes",
+    # the launch geometry of the last call: node-range workgroups of the main pass, column chunks of the fractions sums
+    "ens_score_blocks", "ens_event_blocks", "ens_derive_blocks", "ens_band_blocks", "ens_order_blocks", "ens_clim_blocks",
+    "ens_energy_blocks", "ens_variogram_blocks", "ens_tail_blocks", "ens_region_blocks", "ens_feature_blocks", "ens_fss_blocks",
+    "ens_efi_blocks", "ens_fss_chunks")
 FRESH_ALLOCATIONS = 51        # device buffers of a graph-only handle on the 13 x 24 grid (B = 1, c_out = 2): those of gc_set_graph
 
 

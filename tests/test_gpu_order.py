@@ -371,6 +371,10 @@ def test_full_size(case):
     nd.ens_order_set(probs)
     out = nd.ens_order_score(truth)
     print(f"{case}: ens_order_device_us {nd.counter('ens_order_device_us')}")
+    # the regime: ord_blocks = min(ceil(G / (8 q)), min(1024, 2 * kOrdCuCount * per_cu)), W = 82, Q = 3.  nano, M = 50: a thread's
+    # accumulators take 880 bytes, so 167 threads get a set (q = 2) and one workgroup fits a CU: ceil(10512 / 16) = 657 -> 512.
+    # One degree, M = 8: 208 bytes, 256 threads (q = 3), three workgroups per CU: ceil(65160 / 24) = 2715 -> 1024.
+    assert nd.counter("ens_order_blocks") == (512 if case == "nano" else 1024)
     _check(case, out, ref, G)
     _check_fields(case, nd, ref)
   finally:

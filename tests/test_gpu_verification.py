@@ -118,6 +118,9 @@ def test_scores_match_the_float64_definition_full_size(case):
     _check_sums(case, sums, hist, ref, G, M)
     _check_fields(case, *nd.ens_download_fields(), ref)
     print(f"{case}: ens_score_device_us {nd.counter('ens_score_device_us')}")
+    # the regime: loss_reduce_blocks with W = 82, q = 3 node lanes: min(kLossMaxBlocks = 2048, ceil(G / (8 q))) -- below the
+    # cap at nano (ceil(10512 / 24) = 438), capped at one degree (2715 -> 2048, per = 32, 11 trailing workgroups without nodes)
+    assert nd.counter("ens_score_blocks") == (438 if case == "nano" else 2048)
   finally:
     nd.close()
 
