@@ -41,6 +41,9 @@ Public surface (mirrors the reference's call contracts):
                       BandSpec: the members and the truth low-, band- or high-pass filtered per total wavenumber on
                       the GPU (analysis, a response per wavenumber, synthesis) in front of every scorer: scores scale by
                       scale (GenCast.ensemble_derived, EnsembleRollout.run(derived=...))
+                      MapSpec / ScoreMaps / EventMaps: WHERE the forecast is good -- bias, RMSE, spread/skill, CRPS, outlier
+                      frequency and Brier score per grid point, added up over dates on the GPU, one set of planes per lead
+                      time (GenCast.ensemble_maps, EnsembleRollout.run(maps=...))
   NaNCleaner          gencast/nan_cleaning.py:27-156
   rollout             common/normalization.py:31-238 (InputsAndResiduals), training/train_helpers.py:485-622
                       (autoregressive_rollout); DeviceRollout keeps the context in HBM; EnsembleRollout keeps one
@@ -59,8 +62,8 @@ from .rollout import (DerivedRolloutResult, DeviceRollout, EnsembleRollout, Ense
 from .sampler import Sampler, noise_schedule, stochastic_churn_rate_schedule  # noqa: F401
 from .spectra import EnsembleSpectra, SphericalAnalysis  # noqa: F401
 from .verification import (BandSpec, ClimatologyScores, DerivedSpec, EfiScores, EfiSpec, EnergyScores, EnergySpec, EnsembleScores, EventScores,  # noqa: F401
-                           EventSpec, FeatureScores, FeatureSpec, FractionsScores, OrderScores, RegionScores, RegionSpec,
-                           TailScores, VariogramScores, VariogramSpec, WindowSpec, efi_table, link_tracks)
+                           EventMaps, EventSpec, FeatureScores, FeatureSpec, FractionsScores, MapSpec, OrderScores, RegionScores,
+                           RegionSpec, ScoreMaps, TailScores, VariogramScores, VariogramSpec, WindowSpec, efi_table, link_tracks)
 
 __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_model",
            "noise_schedule", "config", "datasets", "geometry", "synthetic", "weights", "rollout",
@@ -70,4 +73,5 @@ __all__ = ["Denoiser", "Sampler", "GenCast", "EnsembleSampler", "create_gencast_
            "DerivedSpec", "DerivedRolloutResult", "OrderScores", "ClimatologyScores",
            "WindowSpec", "WindowRolloutResult", "EnergySpec", "EnergyScores", "VariogramSpec", "VariogramScores", "TailScores",
            "RegionSpec", "RegionScores", "FeatureSpec", "FeatureScores", "FeatureRolloutResult", "link_tracks",
-           "FractionsScores", "BandSpec", "EfiSpec", "EfiScores", "efi_table"]
+           "FractionsScores", "BandSpec", "EfiSpec", "EfiScores", "efi_table",
+           "MapSpec", "ScoreMaps", "EventMaps"]

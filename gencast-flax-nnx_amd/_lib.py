@@ -149,6 +149,12 @@ SIGNATURES = {
                                         ctypes.POINTER(ctypes.c_uint64)]),
     "gc_ens_efi_fields": (ctypes.c_int, [_hp, _hp, ctypes.POINTER(ctypes.c_double)]),
     "gc_ens_efi_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
+    "gc_ens_map_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32]),
+    "gc_ens_map_accumulate": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
+    "gc_ens_map_accumulate_events": (ctypes.c_int, [_hp, ctypes.c_int32]),
+    "gc_ens_map_download": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int64)]),
+    "gc_ens_map_reset": (ctypes.c_int, [_hp, ctypes.c_int32]),
     "gc_ens_window_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
     "gc_ens_window_push": (ctypes.c_int, [_hp, _hp, _f32p]),
     "gc_ens_window_emit": (ctypes.c_int, [_hp]),
@@ -272,6 +278,7 @@ class NativeDenoiser:
     self._tail_thresholds = 0                  # tail threshold fields this object handed to the handle
     self._regions = 0                          # regions of the plan this object handed to the handle (0: ens_region_set not called)
     self._efi_plan = None                      # (T, E) of the events and bins this object set (None: ens_efi_set not called)
+    self._map_plan = None                      # (C', L, T) of the map plan this object set (None: ens_map_set not called)
     self._window_length = 0                    # length of the window plan this object handed to the handle
 
   # -- plumbing ------------------------------------------------------------------------------
@@ -1230,6 +1237,53 @@ class NativeDenoiser:
                                                  _ptr(sums, ctypes.POINTER(ctypes.c_double)),
                                                  _ptr(counts, ctypes.POINTER(ctypes.c_uint64))))
     return sums, counts
+
+  # -- score maps (the marginal scores per grid point, added up over dates on the device) ----------------
+  def ens_map_set(self, channels=None, n_slots: int = 1, n_event_thresholds: int = 0) -> None:
+    """The plan of the score maps (gc_ens_map_set; needs `set_graph` only, survives `ens_reserve`): `channels` [C'] ascending and
+    distinct (None = all c_out), `n_slots` in 1..128 (a slot is a lead time), `n_event_thresholds` in 0..8 (0: no event
+    planes).  Allocates and zeroes the accumulators; a repeated call replaces and zeroes them."""
+    if channels is None:
+      n, ptr = self.cfg.c_out, None
+    else:
+      ch = _i32(channels)
+      if ch.ndim != 1 or ch.size < 1:
+        raise ValueError("channels must be a non-empty list of channel indices (or None for all)")
+      n, ptr = int(ch.size), _ptr(ch, _i32p)
+    self._check(self._lib.gc_ens_map_set(self._h, n, ptr, int(n_slots), int(n_event_thresholds)))
+    self._map_plan = (n, int(n_slots), int(n_event_thresholds))
+
+  def ens_map_accumulate(self, slot: int, truth=None) -> None:
+    """Adds the date in the member store into the planes of `slot` (gc_ens_map_accumulate).  `truth` [G, B, c_out], or None =
+    the truth uploaded last (shared with `ens_score`)."""
+    t = None if truth is None else self._truth_arg(truth)
+    self._check(self._lib.gc_ens_map_accumulate(self._h, int(slot), None if t is None else _ptr(t, _f32p)))
+
+  def ens_map_accumulate_events(self, slot: int) -> None:
+    """Adds the codes of the last `ens_event_score` into the event planes of `slot` (gc_ens_map_accumulate_events)."""
+    self._check(self._lib.gc_ens_map_accumulate_events(self._h, int(slot)))
+
+  def ens_map_download(self, slot: int, events: bool = None):
+    """-> (sums [6, G, B, C'] float64, counts [3, G, B, C'] uint32, events [T, 5, G, B, C'] uint32 or None, dates [2] int64: field
+    and event calls added): the planes of `slot` (gc_ens_map_download; `verification.ScoreMaps` / `EventMaps` derive the
+    scores).  `events`: None = where the plan has event planes."""
+    dp, u32 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32)
+    if self._map_plan is None:                   # the library says what is missing, in its order
+      self._check(self._lib.gc_ens_map_download(self._h, int(slot), None, None, None, None))
+      raise GencastHipError("libgencast_hip error 4: no map plan (ens_map_set has not been called on this object)")
+    (C, _, T), G, B = self._map_plan, self.num_grid_nodes, self.cfg.batch
+    want = T > 0 if events is None else bool(events)
+    sums = np.empty((6, G, B, C), dtype=np.float64)
+    counts = np.empty((3, G, B, C), dtype=np.uint32)
+    ev = np.empty((T, 5, G, B, C), dtype=np.uint32) if want else None
+    dates = np.zeros(2, dtype=np.int64)
+    self._check(self._lib.gc_ens_map_download(self._h, int(slot), _ptr(sums, dp), _ptr(counts, u32),
+                                              None if ev is None else _ptr(ev, u32), _ptr(dates, ctypes.POINTER(ctypes.c_int64))))
+    return sums, counts, ev, dates
+
+  def ens_map_reset(self, slot: int = -1) -> None:
+    """Zeroes the planes of `slot` (-1: of every slot) and forgets its M and its dates (gc_ens_map_reset)."""
+    self._check(self._lib.gc_ens_map_reset(self._h, int(slot)))
 
   # -- threshold-weighted CRPS (one sort of the members per point, T thresholds) -------------------------
   def ens_tail_set(self, thresholds, directions) -> None:

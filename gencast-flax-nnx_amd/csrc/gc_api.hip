@@ -86,7 +86,8 @@ const int64_t* meter_counter(const gc_handle* h, const std::string& n) {
       {"ens_event", &gc_handle::evt, true},     {"ens_derive", &gc_handle::drv, false}, {"ens_band", &gc_handle::band, false},
       {"ens_order", &gc_handle::ord, true},     {"ens_clim", &gc_handle::clim, true},   {"ens_energy", &gc_handle::en, true},
       {"ens_variogram", &gc_handle::vg, false}, {"ens_tail", &gc_handle::tail, true},   {"ens_region", &gc_handle::reg, true},
-      {"ens_feature", &gc_handle::feat, false}, {"ens_fss", &gc_handle::fss, false},  {"ens_efi", &gc_handle::efi, true}};
+      {"ens_feature", &gc_handle::feat, false}, {"ens_fss", &gc_handle::fss, false},  {"ens_efi", &gc_handle::efi, true},
+      {"ens_map", &gc_handle::map, true}};
   struct Row { const char* name; Meter gc_handle::*meter; int64_t Meter::*field; };
   static const Row rows[] = {
       {"ens_scores", &gc_handle::ens, &Meter::calls},
@@ -920,6 +921,7 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
     const size_t L = h->win_allocs.key[0], M = h->win_allocs.key[1];   // (0, 0): no ring
     *value = (int64_t)(L * (((M + 1) * h->hg.G * h->cfg.batch * h->cfg.c_out + 3) / 4 * 4) * sizeof(float));
   }
+  else if (n == "ens_map_bytes") *value = h->map_set ? h->map_bytes : 0;
   else if (n == "noise_stream") *value = (int64_t)h->nz_stream;
   else if (n == "device_allocations") {
     *value = 0;

@@ -11,13 +11,14 @@
 //   gc_order.hip     gc_ens_order_*
 //   gc_clim.hip      gc_ens_clim_score
 //   gc_efi.hip       gc_ens_efi_*
+//   gc_map.hip       gc_ens_map_*
 //   gc_window.hip    gc_ens_window_*
 //   gc_multivar.hip  gc_ens_energy_*, gc_ens_variogram_*
 //   gc_tail.hip      gc_ens_tail_*
 //   gc_region.hip    gc_ens_region_*
 //   gc_feature.hip   gc_ens_feature_*
 //   gc_fss.hip       gc_ens_fss_*
-// The last fourteen are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
+// The last fifteen are scorers over the member store of gc_ens_reserve (gc_window.hip fills one from a ring of the last
 // lead times of another, gc_feature.hip with the strike fields of the centres it finds in another).  Their host side is two
 // protocols, "score a store" and "fill a store from a source handle", written once in gc_store.h.  What a unit keeps on the
 // handle is declared with the types below: its device buffers are a BufferGroup (a KeyedGroup where a call makes them
@@ -469,6 +470,21 @@ struct gc_handle {
   unsigned long long* d_efi_table = nullptr;     // weighted [T][B c_out][2][E], then counts (same)
   gci::Meter efi{events};                        // of gc_ens_efi_score and gc_ens_efi_fields
   gci::Event ev_efi_src{events};                 // stream order behind the climatology handle
+
+  // score maps (gc_ens_map_*, gc_map.hip): per-point accumulators of the marginal scores, one set of planes per slot
+  gci::BufferGroup map_allocs{groups};            // everything sized by the plan: freed and replaced by gc_ens_map_set; not sized by M, kept across gc_ens_reserve
+  bool map_set = false;                          // a plan has been set
+  bool map_all = false;                          // ... that selects every channel (the kernels read no channel list)
+  int map_C = 0, map_L = 0, map_T = 0;           // selected channels C', slots, event thresholds (0: no event planes)
+  std::vector<int> map_M;                        // [L] the M of the dates a slot holds (0: none)
+  std::vector<int64_t> map_dates;                // [L][2] field / event calls added into a slot
+  int* d_map_chan = nullptr;                     // [C'] the selected channels, ascending
+  double* d_map_sums = nullptr;                  // [L][6][G, B, C']
+  unsigned* d_map_counts = nullptr;              // [L][3][G, B, C']
+  unsigned* d_map_events = nullptr;              // [L][T][5][G, B, C']
+  unsigned* d_map_ipart = nullptr;               // [kMapMaxBlocks][tiles] selected points a workgroup skipped
+  int64_t map_bytes = 0;                         // bytes of the three accumulator arrays ("ens_map_bytes")
+  gci::Meter map{events};                        // of gc_ens_map_accumulate and gc_ens_map_accumulate_events
 
   // time-window ensemble fields (gc_ens_window_*, gc_window.hip): the plan, and the ring of the last L pushed lead times
   gci::KeyedGroup<2> win_allocs{groups};          // the ring, one buffer sized by (L, M): made again by the push that finds either changed

@@ -186,6 +186,18 @@ class EnsembleSampler:
     self._one_rank("tails")
     return self._run(inputs, targets, forcings, num_members, None, tails=spec)
 
+  def maps(self, inputs, targets, forcings, num_members: int, spec, events=None):
+    """Runs the members as `scores` does and forms, on the device, the score maps of this one date for the channels of `spec`
+    (a `verification.MapSpec`): `verification.ScoreMaps` -- the per-point planes of bias, RMSE, spread, CRPS and the outlier
+    counts, in the units of `targets`, additive over dates (`ScoreMaps.merge`).  With `MapSpec(events=True)` and `events` (an
+    `EventSpec`) -> (ScoreMaps, `verification.EventMaps`).  Only the planes are downloaded, no member."""
+    self._one_rank("maps")
+    if not isinstance(spec, verification.MapSpec):
+      raise TypeError("spec must be a verification.MapSpec")
+    if spec.events and events is None:
+      raise ValueError("maps: MapSpec(events=True) needs an EventSpec (events=...)")
+    return self._run(inputs, targets, forcings, num_members, None, maps=(spec, events if spec.events else None))
+
   def regions(self, inputs, targets, forcings, num_members: int, spec):
     """Runs the members as `scores` does and forms, on the device, the sums of `scores` for every region of `spec` (a
     `verification.RegionSpec`) from one pass over the nodes of all regions: `verification.RegionScores`, whose `[name]` is the
@@ -206,12 +218,16 @@ class EnsembleSampler:
     their threshold-weighted CRPS sums, or, with `regions` (a RegionSpec), only their sums per region, or, with `derived` (a
     DerivedSpec, an EventSpec or None), only the scores of the derived fields, or, with `features` (a FeatureSpec), only the
     centres and the scores of their strike fields, or, with `efi` (K Datasets, an EfiSpec, want fields, has a truth), only their
-    extreme forecast index; else they are scored (`scores`), with
+    extreme forecast index, or, with `maps` (a MapSpec, an EventSpec or None), only their score maps of this date; else they
+    are scored (`scores`), with
     `spectral` both.  `asked`: at most one of these keywords (one that is None was not asked for)."""
     asked = {what: arg for what, arg in asked.items() if arg is not None}
     events, order, climatology, tails, regions = (asked.get(k) for k in ("events", "order", "climatology", "tails", "regions"))
     fspec = asked.get("features")
     eclim, espec, efields, etruth = asked.get("efi", (None, None, False, False))
+    mspec, mev = asked.get("maps", (None, None))
+    if mev is not None:                                    # the events a MapSpec(events=True) counts: those of the main store
+      events = mev
     (dspec, dev), (energy, variogram) = asked.get("derived", (None, None)), asked.get("multivariate", (None, None))
     template = datasets.as_dataset(targets_template)
     # every rank packs its (possibly stale) local copy to size buffers; rank 0's data wins
@@ -248,7 +264,8 @@ class EnsembleSampler:
       # node weights on the main store)
       main = verification.ScoredStore(native, num_members, weights if scoring or asked.keys() - {"events", "derived", "features"} else None,
                                       events=events, thresholds=None if events is None else events.packed(template), weight_q=wq,
-                                      set_per_score=True, order=None if order is None else order[0],
+                                      set_per_score=mspec is None, order=None if order is None else order[0],
+                                      maps=mspec, map_channels=None if mspec is None else mspec.channels(template),
                                       climatology=None if climatology is None and eclim is None
                                       else self._denoiser.climatology_handle(self._denoiser.dims.c_out),
                                       efi=None if espec is None else espec if wq is not None else verification.EfiSpec((), (), espec.bins),
@@ -319,8 +336,14 @@ class EnsembleSampler:
       scores = main.score_order(truth)
       return (scores, as_given(main.quantile_fields())) if order[1] else scores
 
+    def map_scores():                                      # one date into slot 0 of accumulators made for this call
+      if mev is not None:
+        main.score_events(truth)                             # (leaves the codes and the truth on the device)
+      main.accumulate_maps(0, None if mev is not None else truth)
+      return main.download_maps(0)
+
     if asked:                                              # (what was asked for is scored alone)
-      return {"derived": derived_scores, "features": feature_scores, "events": lambda: main.score_events(truth),
+      return {"derived": derived_scores, "maps": map_scores, "features": feature_scores, "events": lambda: main.score_events(truth),
               "climatology": lambda: main.score_climatology([pack(c) for c in climatology], truth),
               "tails": lambda: main.score_tails(truth), "regions": lambda: main.score_regions(truth),
               "multivariate": multivariate_scores, "order": order_scores, "efi": efi_scores}[next(iter(asked))]()

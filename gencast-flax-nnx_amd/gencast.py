@@ -136,6 +136,16 @@ class GenCast:
     runner = self._ensemble_sampler(rngs, concurrent_members)
     return runner.tails(inputs, targets, forcings, num_members, spec)
 
+  def ensemble_maps(self, inputs, targets, forcings=None, *, num_members, spec, events=None, rngs=0, concurrent_members=1):
+    """Samples `num_members` (2..64) members as `ensemble_scores` does and forms on the GPU the score maps of this date:
+    `verification.ScoreMaps` -- per grid point and per channel of `spec` (`verification.MapSpec`) the raw planes from which
+    `.bias`, `.rmse`, `.spread_skill_ratio`, `.crps`, `.crps_stderr`, `.outlier_low` / `.outlier_high` follow; the planes of
+    several dates add (`ScoreMaps.merge`), and any region chosen afterwards is a weighted sum of them (`.region`).  With
+    `MapSpec(events=True)` and `events` (an `EventSpec`) -> (ScoreMaps, `verification.EventMaps`: per-point Brier score, base
+    rate and forecast probability).  No member leaves the device."""
+    runner = self._ensemble_sampler(rngs, concurrent_members)
+    return runner.maps(inputs, targets, forcings, num_members, spec, events)
+
   def ensemble_regions(self, inputs, targets, forcings=None, *, num_members, spec, rngs=0, concurrent_members=1):
     """Samples `num_members` (2..64) members as `ensemble_scores` does and forms on the GPU the sums of `ensemble_scores` for
     every region of `spec` (`verification.RegionSpec`: named boolean masks over the grid, overlapping or not) from ONE pass

@@ -154,6 +154,11 @@ class NaNCleaner:
     points the device does not count (`TailScores.invalid`)."""
     return self.predictor.ensemble_tails(*self._cleaned(inputs, targets, forcings, False), **kwargs)
 
+  def ensemble_maps(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
+    """Inputs and forcings are cleaned; the targets pass through unchanged, as in `ensemble_scores`: their NaNs are
+    points that add nothing to any plane (`ScoreMaps.valid_dates` is 0 there)."""
+    return self.predictor.ensemble_maps(*self._cleaned(inputs, targets, forcings, False), **kwargs)
+
   def ensemble_regions(self, inputs, targets, forcings: Optional[Dataset] = None, **kwargs):
     """Inputs and forcings are cleaned; the targets pass through unchanged, as in `ensemble_scores`: their NaNs are
     points the device does not count (`RegionScores.invalid`, per region)."""

@@ -280,6 +280,20 @@ class InputsAndResiduals:
     nspec = spec.mapped(datasets.as_dataset(targets), lambda name, v: self._subtract_input_and_normalize_target(raw, name, v))
     return self.predictor.ensemble_tails(ni, nt, forcings=nf, spec=nspec, **kwargs).scaled(scale)
 
+  def ensemble_maps(self, inputs, targets, forcings=None, *, spec, events=None, **kwargs):
+    """`ensemble_maps` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets, returned in
+    physical units: the planes are rescaled per selected channel (`ScoreMaps.scaled`: b drops out of every term), nothing is
+    recomputed.  The thresholds of `events` (physical units) go through the SAME map as the targets, as in `ensemble_events`;
+    the event planes are integers and carry no unit."""
+    raw, ni, nt, nf = self._normalized_loss_args(inputs, targets, forcings)
+    scale = self._target_scale(raw, targets)[spec.channels(targets)]
+    nev = None if events is None else events.mapped(datasets.as_dataset(targets),
+                                                     lambda name, v: self._subtract_input_and_normalize_target(raw, name, v))
+    out = self.predictor.ensemble_maps(ni, nt, forcings=nf, spec=spec, events=nev, **kwargs)
+    if not isinstance(out, tuple):
+      return out.scaled(scale)
+    return out[0].scaled(scale), out[1]
+
   def ensemble_regions(self, inputs, targets, forcings=None, **kwargs):
     """`ensemble_regions` of the wrapped predictor on normalised inputs and forcings and residual-normalised targets, returned
     in physical units: every region's raw sums are rescaled as in `ensemble_scores` (`RegionScores.scaled`)."""
@@ -673,6 +687,8 @@ class _SeriesResult:
       return None
     if name in ("efi", "efi_fields") and self._carries_efi():    # of `run(efi=...)`: absent from `vars(result)` unless asked for
       return None
+    if name in ("maps", "maps_normalized", "event_maps"):        # of `run(maps=...)`: likewise
+      return None
     raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
   def _set_efi(self, efi, efi_fields) -> None:
@@ -690,6 +706,26 @@ class _SeriesResult:
     if (self.efi is None) != (other.efi is None):
       raise ValueError(f"merge: only one of the two {self._kind} carries the {verification.EFI_SCORER.word}")
     return None if self.efi is None else [type(x).merge([x, y]) for x, y in zip(self.efi, other.efi)]
+
+  _MAP_SERIES = ("maps", "maps_normalized", "event_maps")
+
+  def _set_maps(self, maps, maps_normalized, event_maps) -> None:
+    """Of `run(maps=...)`, per slot (a lead time; on a window result a window): `maps[k]` (`verification.ScoreMaps` in physical
+    units), `maps_normalized[k]` (as the device holds them), `event_maps[k]` (`verification.EventMaps`, with
+    `MapSpec(events=True)`).  Absent from `vars(result)` unless asked for (`verification.MAP_SCORER`: beside the table)."""
+    for name, given in zip(self._MAP_SERIES, (maps, maps_normalized, event_maps)):
+      if given is not None:
+        setattr(self, name, list(given))
+
+  def _merged_maps(self, other) -> Dict[str, Optional[list]]:
+    """The planes of both results added slot by slot (`ScoreMaps.merge`, `EventMaps.merge`: a left fold, self first)."""
+    out = {}
+    for name in self._MAP_SERIES:
+      a, b = getattr(self, name), getattr(other, name)
+      if (a is None) != (b is None):
+        raise ValueError(f"merge: only one of the two {self._kind} carries {verification.MAP_SCORER.word}")
+      out[name] = None if a is None else [type(x).merge([x, y]) for x, y in zip(a, b)]
+    return out
 
   def _set_series(self, named, series) -> None:
     """Copies the series into lists (the scores first) and checks that the others cover the lead times of the scores.
@@ -742,13 +778,15 @@ class DerivedRolloutResult(_SeriesResult):
   _carried_as, _kind = "derived", "derived results"
 
   def __init__(self, scores, scores_normalized, events=None, members=None, template=None, *, quantiles=None, efi=None,
-               efi_fields=None, **series):
+               efi_fields=None, maps=None, maps_normalized=None, event_maps=None, **series):
     self._set_series(locals(), series)
     self._set_efi(efi, efi_fields)
+    self._set_maps(maps, maps_normalized, event_maps)
     self.members, self.template, self.quantiles = members, template, quantiles
 
   def merge(self, other: "DerivedRolloutResult") -> "DerivedRolloutResult":
-    return DerivedRolloutResult(template=self.template, efi=self._merged_efi(other), **self._merged_series(other))
+    return DerivedRolloutResult(template=self.template, efi=self._merged_efi(other), **self._merged_maps(other),
+                                **self._merged_series(other))
 
 
 class FeatureRolloutResult(_SeriesResult):
@@ -790,9 +828,10 @@ class WindowRolloutResult(_SeriesResult):
   _carried_as, _kind = "window", "window results"
 
   def __init__(self, leads, steps: int, scores, scores_normalized, events=None, order=None, members=None, template=None,
-               **series):
+               *, maps=None, maps_normalized=None, event_maps=None, **series):
     self.leads, self.steps = [int(k) for k in leads], int(steps)
     self._set_series(locals(), series)
+    self._set_maps(maps, maps_normalized, event_maps)
     if len(self.scores) != len(self.leads) or len(self.scores_normalized) != len(self.leads):
       raise ValueError("a window result needs one score per window lead time")
     self.members, self.template = members, template
@@ -801,7 +840,8 @@ class WindowRolloutResult(_SeriesResult):
     """The result over the union of the start dates, window by window: raw sums add; members belong to one date."""
     if self.leads != other.leads or self.steps != other.steps:
       raise ValueError(f"merge: the windows differ (steps {self.steps} and {other.steps}, leads {self.leads} and {other.leads})")
-    return WindowRolloutResult(self.leads, self.steps, template=self.template, **self._merged_series(other))
+    return WindowRolloutResult(self.leads, self.steps, template=self.template, **self._merged_maps(other),
+                               **self._merged_series(other))
 
 
 class EnsembleRolloutResult(_SeriesResult):
@@ -828,9 +868,11 @@ class EnsembleRolloutResult(_SeriesResult):
   _carried_as = "ensemble"
 
   def __init__(self, scores, spectra=None, mean=None, variance=None, members=None, n_members: Optional[int] = None, *,
-               derived=None, quantiles=None, windows=None, features=None, efi=None, efi_fields=None, **series):
+               derived=None, quantiles=None, windows=None, features=None, efi=None, efi_fields=None, maps=None,
+               maps_normalized=None, event_maps=None, **series):
     self._set_series(locals(), series)
     self._set_efi(efi, efi_fields)
+    self._set_maps(maps, maps_normalized, event_maps)
     self.derived = None if derived is None else dict(derived)
     self.windows = None if windows is None else dict(windows)
     if features is not None:                              # (as an optional series: absent from `vars(result)` unless asked for)
@@ -856,7 +898,7 @@ class EnsembleRolloutResult(_SeriesResult):
     if other.n_members != self.n_members:
       raise ValueError(f"merge: member counts differ ({self.n_members} and {other.n_members})")
     series = self._merged_series(other)
-    return EnsembleRolloutResult(n_members=self.n_members, **series, efi=self._merged_efi(other),
+    return EnsembleRolloutResult(n_members=self.n_members, **series, efi=self._merged_efi(other), **self._merged_maps(other),
                                  derived=_merge_named(self.derived, other.derived, "derived scores", "derived"),
                                  windows=_merge_named(self.windows, other.windows, "windows", "window"),
                                  features=_merge_named(self.features, other.features, "features", "feature"))
@@ -878,6 +920,9 @@ class _StoreSeries:
                   if row.name == "scores" or getattr(store, row.name, None) is not None for name in row.series}
     self.quantiles = [] if store.order is not None and keep_quantiles else None
     self.members = [] if keep_members else None
+    # the score maps of a store with a `MapSpec`: the slot the next scored lead (or window) is added into, and what
+    # `collect_maps` downloads at the end of a run that does not keep them resident
+    self.map_slot, self.map_series = 0, {}
     # a store with a feature plan: per lead time the centres and the strike-probability map
     self.centres, self.probabilities = ([], []) if getattr(store, "feature_plan", None) is not None else (None, None)
 
@@ -923,8 +968,22 @@ class _StoreSeries:
       self.efi.append(verification.EFI_SCORER.score(self.store, None))
       if self.efi_fields is not None:
         self.efi_fields.append(self.store.efi_fields())
+    if getattr(self.store, "maps", None) is not None:       # (the events ran with the scores: their codes are on the device)
+      self.store.accumulate_maps(self.map_slot)
+      self.map_slot += 1
     if self.members is not None:
       self.members.append([self.store.handle.ens_download_member(m) for m in range(self.store.n_members)])
+
+  def collect_maps(self) -> Dict[str, Optional[list]]:
+    """Downloads every slot of the store's accumulators: {"maps": physical units, "maps_normalized": as the device holds them,
+    "event_maps": with `MapSpec(events=True)`, else None}; kept as `map_series` for the results."""
+    store = self.store
+    got = [store.download_maps(slot) for slot in range(store.map_slots)]
+    raw = [g[0] if store.maps.events else g for g in got]
+    scale = np.asarray(self.scale, np.float64)[list(raw[0].channels)]
+    self.map_series = {"maps": [r.scaled(scale) for r in raw], "maps_normalized": raw,
+                       "event_maps": [g[1] for g in got] if store.maps.events else None}
+    return self.map_series
 
   def carried(self, result) -> Dict[str, list]:
     """The series of the store that a result of class `result` carries, as the keywords of its constructor."""
@@ -936,7 +995,7 @@ class _StoreSeries:
 
   def derived_result(self) -> DerivedRolloutResult:
     return DerivedRolloutResult(members=self.members, template=self.template, quantiles=self.quantiles, efi=self.efi,
-                                efi_fields=self.efi_fields, **self.carried(DerivedRolloutResult))
+                                efi_fields=self.efi_fields, **self.map_series, **self.carried(DerivedRolloutResult))
 
 
 class _WindowEntry:
@@ -965,7 +1024,7 @@ class _WindowEntry:
 
   def result(self) -> WindowRolloutResult:
     s = self.series
-    return WindowRolloutResult(self.leads, self.spec.steps, members=s.members, template=s.template,
+    return WindowRolloutResult(self.leads, self.spec.steps, members=s.members, template=s.template, **s.map_series,
                                **s.carried(WindowRolloutResult))
 
 
@@ -1060,7 +1119,7 @@ class EnsembleRollout:
           keep_members: bool = False, events=None, derived=None, order=None,
           keep_quantiles: bool = False, climatology=None, windows=None, energy=None,
           variogram=None, tails=None, regions=None, features=None, efi=None,
-          keep_efi: bool = False) -> EnsembleRolloutResult:
+          keep_efi: bool = False, maps=None, maps_resident: bool = False) -> EnsembleRolloutResult:
     """Rolls `num_members` (2..64) members out `horizon` steps and scores them against `targets[k]` at every lead time
     k.  `init_noise[m][k]`: a given initial state [G, B, c_out] for member m, step k.  `spectra` / `lmax`: also the
     spherical-harmonic spectra per lead time (`targets` must then be finite).  `fields`: also the ensemble mean and
@@ -1143,6 +1202,16 @@ class EnsembleRollout:
     unit, so there is no normalised twin.  `keep_efi`: also the two fields, downloaded: `efi_fields[k]` = (EFI, observed
     index), [G, B, c] each.  It does not reach the windows (`climatology` does not) nor the `features`.  Without `efi` nothing
     changes.
+    `maps`: a `verification.MapSpec` for the main store, or a mapping {None: spec, name: spec, ...} whose other keys name
+    entries of `derived` / `windows`: per lead time (per window, on a window entry), behind everything else that is scored, the
+    date is added into the store's score maps on the device (`gc_ens_map_accumulate`; slot = lead index, or the index of the
+    window) -- per grid point the planes of bias, RMSE, spread, CRPS and the outlier counts, with `MapSpec(events=True)` also
+    the event planes of the store's EventSpec.  By default a run zeroes its slots, adds its one date and downloads them at the
+    end: `EnsembleRolloutResult.maps[k]` (`verification.ScoreMaps` in physical units), `maps_normalized[k]`, `event_maps[k]`,
+    and the same on the results of the named entries; `merge` adds them over start dates.  With `maps_resident` a run neither
+    zeroes nor downloads: the sums stay in HBM over any number of runs with the same plan and horizon (another plan or horizon
+    is a ValueError), `download_maps()` fetches them once and `reset_maps()` clears them.  A store that shares its handle with
+    another (two `derived` entries of equal width, one EventSpec per lead time) cannot keep maps.  Without `maps` nothing changes.
 
     Units: scores and spectra are returned in the units of `targets` through `EnsembleScores.scaled(s)` /
     `EnsembleSpectra.scaled(s)`, s the input scale per channel; the location offset l cancels in every score and in the
@@ -1179,10 +1248,14 @@ class EnsembleRollout:
       raise ValueError("init_noise must be [num_members][horizon] fields")
     known = set(derived or {}) | set(windows or {}) | set(features or {})
     per_store = {arg: _per_store(arg, spec, known) for arg, spec in (("tails", tails), ("regions", regions))}
+    map_specs = _per_store("maps", maps, set(derived or {}) | set(windows or {}))
+    if maps_resident and map_specs is None:
+      raise ValueError("maps_resident goes with maps=...")
     run = self._setup(inputs, targets, forcings, horizon, M, context_steps=context_steps, init_noise=init_noise,
                       spectra=spectra, lmax=lmax, fields=fields, keep_members=keep_members, events=events, derived=derived,
                       order=order, keep_quantiles=keep_quantiles, climatology=climatology, windows=windows, energy=energy,
-                      variogram=variogram, per_store=per_store, features=features, efi=efi, keep_efi=keep_efi)
+                      variogram=variogram, per_store=per_store, features=features, efi=efi, keep_efi=keep_efi,
+                      map_specs=map_specs, maps_resident=maps_resident)
     self.last_lead_ms = []
     for k in range(horizon):
       t0 = _time.perf_counter()
@@ -1190,6 +1263,11 @@ class EnsembleRollout:
       self._score_lead(run, k, targets)
       self.last_lead_ms.append(1e3 * (_time.perf_counter() - t0))
     main = run.main
+    if map_specs is not None:
+      self._map_run = run                                  # (what `download_maps` / `reset_maps` reach)
+      if not maps_resident:
+        for series in self._map_stores(run).values():
+          series.collect_maps()
     return EnsembleRolloutResult(mean=_on_time_axis(run.means, given, horizon) if fields else None,
                                  variance=_on_time_axis(run.variances, given, horizon) if fields else None,
                                  members=main.members, n_members=M, quantiles=main.quantiles,
@@ -1197,11 +1275,35 @@ class EnsembleRollout:
                                  windows=None if windows is None else {k: v.result() for k, v in run.windows.items()},
                                  features=None if features is None else {k: v.feature_result() for k, v in run.features.items()},
                                  spectra=run.spectra, spectra_normalized=run.raw_spectra, efi=main.efi,
-                                 efi_fields=main.efi_fields, **main.carried(EnsembleRolloutResult))
+                                 efi_fields=main.efi_fields, **main.map_series, **main.carried(EnsembleRolloutResult))
+
+  @staticmethod
+  def _map_stores(run: "_EnsembleRun") -> Dict[Optional[str], "_StoreSeries"]:
+    """{store name (None: the main store): its series} of the stores of a run that keep score maps."""
+    named = [(None, run.main)] + list(run.views.items()) + [(name, w.series) for name, w in run.windows.items()]
+    return {name: series for name, series in named if getattr(series.store, "maps", None) is not None}
+
+  def download_maps(self) -> Dict[Optional[str], Dict[str, Optional[list]]]:
+    """The score maps the last `run(maps=...)` left on the device -- with `maps_resident` the sums over every run since they
+    were last cleared -- as {store name (None: the main store): {"maps": [slots] `ScoreMaps` in physical units,
+    "maps_normalized": as the device holds them, "event_maps": `EventMaps` or None}}: per store the series the result of a
+    run without `maps_resident` carries."""
+    run = getattr(self, "_map_run", None)
+    if run is None:
+      raise ValueError("download_maps: no run with maps=... has been made")
+    return {name: dict(series.collect_maps()) for name, series in self._map_stores(run).items()}
+
+  def reset_maps(self) -> None:
+    """Zeroes the score maps of every store of the last `run(maps=...)`; the next run may bring another plan or horizon."""
+    run = getattr(self, "_map_run", None)
+    if run is None:
+      raise ValueError("reset_maps: no run with maps=... has been made")
+    for series in self._map_stores(run).values():
+      series.store.forget_maps()
 
   def _setup(self, inputs, targets, forcings, horizon, M, *, context_steps, init_noise, spectra, lmax, fields, keep_members,
              events, derived, order, keep_quantiles, climatology, windows, energy, variogram, per_store,
-             features=None, efi=None, keep_efi=False) -> "_EnsembleRun":
+             features=None, efi=None, keep_efi=False, map_specs=None, maps_resident=False) -> "_EnsembleRun":
     """Everything `run` does before the first sample: lanes, context store, the main store and the derived views.  The
     keywords are `run`'s own; `per_store`: {argument given per store ("tails", "regions"): {store name: spec} or None}."""
     run = _EnsembleRun()
@@ -1256,6 +1358,15 @@ class EnsembleRollout:
           out.update({arg: spec}, **verification.scorer(arg).from_spec(spec, template, lambda sp, t: packed(sp, t, s, l)))
       return out
 
+    def map_args(name, template, slots):
+      """The `ScoredStore` keywords of the score maps of the store `name`: one slot per scored lead time (or window)."""
+      spec = (map_specs or {}).get(name)
+      if spec is None:
+        return {}
+      if not 1 <= slots <= 128:
+        raise ValueError(f"maps: {slots} slots (lead times or windows) -- the accumulators hold 1..128")
+      return dict(maps=spec, map_channels=spec.channels(template), map_slots=slots, maps_resident=maps_resident)
+
     weights = verification.node_weights(template0)        # the same nodes everywhere: quantised once, too
     wq = None
     if efi is not None and climatology is None:
@@ -1279,7 +1390,7 @@ class EnsembleRollout:
     main = verification.ScoredStore(native, M, weights, events=None if specs is None else specs[0],
                                     thresholds=None if specs is None else run.thresholds[0], weight_q=wq,
                                     set_per_score=specs is not None and len(specs) > 1, order=order, climatology=clim_handle,
-                                    energy=eplan(template0), variogram=vplan, efi=efi,
+                                    energy=eplan(template0), variogram=vplan, efi=efi, **map_args(None, template0, horizon),
                                     **per_store_args(None, template0, scale, loc))
     run.main = _StoreSeries(main, scale, template0, keep_members=keep_members, keep_quantiles=keep_quantiles, keep_efi=keep_efi)
     main.reserve()
@@ -1334,12 +1445,15 @@ class EnsembleRollout:
                                        thresholds=None if dev is None else packed(dev, dtemplate, dscale, dloc), weight_q=wq,
                                        source=native, order=order, energy=eplan(dtemplate), variogram=vplan,
                                        climatology=clim_view, climatology_source=clim_handle, efi=efi, **{how: dplan},
-                                       **per_store_args(name, dtemplate, dscale, dloc))
+                                       **map_args(name, dtemplate, horizon), **per_store_args(name, dtemplate, dscale, dloc))
       run.views[name] = _StoreSeries(store, dscale, dtemplate, keep_members=keep_members, keep_quantiles=keep_quantiles,
                                      keep_efi=keep_efi)
     for store in (v.store for v in run.views.values()):
       # entries of equal width share a handle: their plan and thresholds are then set again at every lead time
       store.set_per_score = sum(1 for v in run.views.values() if v.store.handle is store.handle) > 1
+      if store.set_per_score and store.maps is not None:
+        raise ValueError("maps: a derived entry that shares its handle with another of equal width cannot keep score maps -- "
+                         "two views must not add into one accumulator")
       store.setup()
 
     for name, fspec in (features or {}).items():
@@ -1368,6 +1482,7 @@ class EnsembleRollout:
       store = verification.ScoredStore(den.window_handle(len(wscale), name), M, weights, events=wev,
                                        thresholds=None if wev is None else packed(wev, stemplate, wscale, wloc), weight_q=wq,
                                        order=order, energy=eplan(stemplate), variogram=vplan,
+                                       **map_args(name, stemplate, len(wspec.leads(horizon))),
                                        **per_store_args(name, stemplate, wscale, wloc))
       run.windows[name] = _WindowEntry(wspec, _StoreSeries(store, wscale, stemplate, keep_members=keep_members), source, horizon)
       run.windows[name].start()

@@ -63,6 +63,11 @@ second handle -- how far the forecast distribution is shifted against the climat
 against, `EfiScores` keeps the raw sums and integer tables and derives the mean index, its correlation with the observed
 index and the ROC.
 
+Score maps (`gc_ens_map_*`): the marginal scores kept per grid point and added up over dates on the
+device, one set of planes per slot (a lead time).  `MapSpec` selects the channels, `ScoreMaps` keeps the raw planes and
+derives bias, RMSE, spread/skill, the fair CRPS with its standard error and the outlier frequencies per point, `EventMaps`
+the Brier score, base rate and forecast probability per point; both merge over dates and reduce to any region after the fact.
+
 Regions (`gc_ens_region_score`): the sums of `EnsembleScores` per named set of grid nodes -- tropics,
 extratropics, land, sea, boxes -- every region from one pass over the nodes that belong to any.  `RegionSpec` holds the masks
 and builds boxes from bounds; `RegionScores[name]` is the region's `EnsembleScores`.
@@ -2386,6 +2391,329 @@ class EfiScores(AdditiveScores):
 
 
 # ---------------------------------------------------------------------------------------------
+# score maps: the marginal scores per grid point, added up over dates (gc_ens_map_*)
+# ---------------------------------------------------------------------------------------------
+class MapSpec:
+  """What the score maps of a store cover: `variables` (None: every target variable), `levels` (None: every level; else the
+  values of the `level` coordinate to keep, for the variables that have levels), and with `events` the event planes of the
+  store's `EventSpec` (its T thresholds, from the codes its event score leaves on the device)."""
+
+  def __init__(self, variables: Optional[Sequence[str]] = None, levels: Optional[Sequence[float]] = None, events: bool = False):
+    if isinstance(variables, str):
+      variables = (variables,)
+    self.variables = None if variables is None else tuple(str(v) for v in variables)
+    self.levels = None if levels is None else tuple(float(v) for v in np.asarray(levels, dtype=np.float64).reshape(-1))
+    self.events = bool(events)
+    if self.variables is not None and (not self.variables or len(set(self.variables)) != len(self.variables)):
+      raise ValueError("variables must be a non-empty list of distinct names (or None for all)")
+    if self.levels is not None and (not self.levels or len(set(self.levels)) != len(self.levels)):
+      raise ValueError("levels must be a non-empty list of distinct values (or None for all)")
+
+  def __eq__(self, other):
+    return isinstance(other, MapSpec) and (self.variables, self.levels, self.events) == (other.variables, other.levels, other.events)
+
+  def __hash__(self):
+    return hash((self.variables, self.levels, self.events))
+
+  def channels(self, template) -> np.ndarray:
+    """The selected channels [C'] int32, ascending, in the channel order of `datasets.channel_layout(template)`."""
+    template = datasets.as_dataset(template)
+    layout = {name: (off, n) for name, off, n in datasets.channel_layout(template)}
+    for name in self.variables or ():
+      if name not in layout:
+        raise ValueError(f"{name!r} is not a target variable")
+    level_idx = None
+    if self.levels is not None:
+      if "level" not in template.coords:
+        raise ValueError("levels given, but the template has no 'level' coordinate")
+      coord = np.asarray(template.coords["level"], dtype=np.float64).reshape(-1)
+      level_idx = []
+      for v in self.levels:
+        at = np.flatnonzero(coord == v)
+        if at.size != 1:
+          raise ValueError(f"level {v:g} is not one of the template's levels {coord.tolist()}")
+        level_idx.append(int(at[0]))
+    out = []
+    for name in sorted(layout):
+      if self.variables is not None and name not in self.variables:
+        continue
+      off, n = layout[name]
+      var = template[name]
+      stack = [d for d in var.dims if d not in datasets.PRESERVED]
+      idx = np.arange(n).reshape([var.sizes[d] for d in stack])
+      if level_idx is not None and "level" in stack:
+        idx = np.take(idx, level_idx, axis=stack.index("level"))
+      out.extend(int(off + i) for i in idx.reshape(-1))
+    if not out:
+      raise ValueError("the map spec selects no channel")
+    return np.array(sorted(out), dtype=np.int32)
+
+
+def _map_channels(channels, n: int) -> Tuple[int, ...]:
+  ch = tuple(range(n)) if channels is None else tuple(int(c) for c in np.asarray(channels).reshape(-1))
+  if len(ch) != n:
+    raise ValueError(f"channels must name the {n} channels of the planes, got {len(ch)}")
+  return ch
+
+
+def _map_field(values, counted, template, channels, name: Optional[str]):
+  """[G, B, C'] -> a Dataset on the template's grid: the selected channels of the template's variables, NaN elsewhere and
+  where the point never counted; `name`: a prefix of the variable names (None: as in the template)."""
+  template = datasets.as_dataset(template)
+  sizes = template.sizes
+  n_lat, n_lon = int(sizes["lat"]), int(sizes["lon"])
+  total = sum(n for _, _, n in datasets.channel_layout(template))
+  v = np.where(counted, values, np.nan)
+  G, B = v.shape[:2]
+  if G != n_lat * n_lon:
+    raise ValueError(f"the planes have {G} nodes, the template {n_lat} x {n_lon}")
+  full = np.full((G, B, total), np.nan)
+  full[:, :, list(channels)] = v
+  stacked = np.transpose(full.reshape(n_lat, n_lon, B, total), (2, 0, 1, 3))
+  like = datasets.Dataset({k: datasets.Variable(var.dims, np.broadcast_to(np.zeros(()), tuple(B if d == "batch" else n for d, n in
+                                                                                     zip(var.dims, np.shape(var.data)))))
+                           for k, var in template.items()}, template.coords)
+  ds = datasets.stacked_to_dataset(stacked, like)
+  if name is None:
+    return ds
+  return datasets.Dataset({f"{name}_{k}": var for k, var in ds.items()}, ds.coords)
+
+
+class MapRegionScores(EnsembleScores):
+  """`ScoreMaps.region`: the column sums of `EnsembleScores` formed from map planes.  Of the rank histogram the planes hold
+  the two end bins alone; the bins between them are zero here, and `valid_points` comes from the N0 plane."""
+  _listed = tuple(x for x in EnsembleScores._listed if x != "rank_histogram") + ("outlier_low", "outlier_high")
+
+  def __init__(self, sums, rank_histogram, n_members: int, points=None):
+    super().__init__(sums, rank_histogram, n_members)
+    self.points = self.rank_histogram.sum(axis=-1) if points is None else np.asarray(points, dtype=np.uint64)
+
+  @property
+  def valid_points(self) -> np.ndarray:
+    return self.points
+
+  @property
+  def outlier_low(self) -> np.ndarray:
+    return self.rank_histogram[..., 0] / self.points.astype(np.float64)
+
+  @property
+  def outlier_high(self) -> np.ndarray:
+    return self.rank_histogram[..., -1] / self.points.astype(np.float64)
+
+
+class ScoreMaps:
+  """The raw planes of `gc_ens_map_download` for one slot: `sums` [6, G, B, C'] float64 (P0 .. P5: the per-date e, e^2, s2, ae, d
+  and c^2 of a point, added date after date), `counts` [3, G, B, C'] uint32 (N0 dates counted, N1 dates with the truth below
+  every member, N2 above every member), with the member count M, the `channels` [C'] the planes cover and `dates`, the
+  calls that were added.  Every score is [G, B, C'] float64, NaN where the point never counted.  The planes add over dates
+  (`merge`); scores do not."""
+
+  def __init__(self, sums, counts, n_members: int, channels=None, dates: int = 0):
+    self.sums = np.asarray(sums, dtype=np.float64)
+    self.counts = np.asarray(counts, dtype=np.uint32)
+    self.n_members = int(n_members)
+    if self.n_members < 2:
+      raise ValueError("n_members must be >= 2")
+    if self.sums.ndim != 4 or self.sums.shape[0] != 6:
+      raise ValueError(f"sums must be [6, G, batch, channels], got {self.sums.shape}")
+    if self.counts.shape != (3,) + self.sums.shape[1:]:
+      raise ValueError(f"counts must be {(3,) + self.sums.shape[1:]}, got {self.counts.shape}")
+    self.channels = _map_channels(channels, self.sums.shape[-1])
+    self.dates = int(dates)
+
+  # -- the planes
+  def _p(self, k: int) -> np.ndarray:
+    return self.sums[k]
+
+  @property
+  def valid_dates(self) -> np.ndarray:
+    """N0: the dates on which the point counted."""
+    return self.counts[0]
+
+  @property
+  def _n(self) -> np.ndarray:
+    n = self.counts[0].astype(np.float64)
+    return np.where(n > 0.0, n, np.nan)
+
+  @property
+  def bias(self) -> np.ndarray:
+    return self._p(0) / self._n
+
+  @property
+  def rmse(self) -> np.ndarray:
+    """Of the ensemble mean."""
+    return np.sqrt(self._p(1) / self._n)
+
+  @property
+  def spread(self) -> np.ndarray:
+    return np.sqrt(self._p(2) / self._n)
+
+  @property
+  def spread_skill_ratio(self) -> np.ndarray:
+    """sqrt((M+1)/M) spread / rmse: 1 for a calibrated ensemble of any size."""
+    m = float(self.n_members)
+    with np.errstate(divide="ignore", invalid="ignore"):
+      return np.sqrt((m + 1.0) / m) * self.spread / self.rmse
+
+  @property
+  def crps(self) -> np.ndarray:
+    """The fair CRPS."""
+    return (self._p(3) - 0.5 * self._p(4)) / self._n
+
+  @property
+  def crps_ensemble(self) -> np.ndarray:
+    """The CRPS of the M-member empirical distribution (pair term normalised by M^2)."""
+    m = float(self.n_members)
+    return (self._p(3) - 0.5 * (m - 1.0) / m * self._p(4)) / self._n
+
+  @property
+  def crps_stderr(self) -> np.ndarray:
+    """The standard error of `crps` over the dates: sqrt((P5 / N0 - crps^2) / (N0 - 1)); NaN with fewer than two dates."""
+    n = self._n
+    crps = self.crps
+    with np.errstate(divide="ignore", invalid="ignore"):
+      var = (self._p(5) / n - crps * crps) / np.where(n > 1.0, n - 1.0, np.nan)
+    return np.sqrt(np.maximum(var, 0.0))
+
+  @property
+  def outlier_low(self) -> np.ndarray:
+    """The frequency of the truth below every member (1 / (M + 1) for a calibrated ensemble)."""
+    return self.counts[1] / self._n
+
+  @property
+  def outlier_high(self) -> np.ndarray:
+    return self.counts[2] / self._n
+
+  # -- algebra
+  def scaled(self, channel_scale) -> "ScoreMaps":
+    """The planes of a x + b in place of x (members and truth alike), a = channel_scale [C'], any b: P0 scales with a, P3 and
+    P4 with |a|, P1, P2 and P5 with a^2; for a < 0 the two outlier counts change places."""
+    a = np.asarray(channel_scale, dtype=np.float64).reshape(-1)
+    if a.shape != (self.sums.shape[-1],):
+      raise ValueError(f"channel_scale must have shape ({self.sums.shape[-1]},)")
+    if np.any(a == 0.0) or not np.all(np.isfinite(a)):
+      raise ValueError("channel_scale must be finite and non-zero")
+    f = np.stack([a, a * a, a * a, np.abs(a), np.abs(a), a * a])
+    counts = self.counts.copy()
+    neg = a < 0.0
+    counts[1][..., neg], counts[2][..., neg] = self.counts[2][..., neg], self.counts[1][..., neg]
+    return ScoreMaps(self.sums * f[:, None, None, :], counts, self.n_members, self.channels, self.dates)
+
+  @staticmethod
+  def merge(parts: Sequence["ScoreMaps"]) -> "ScoreMaps":
+    """The planes over the dates of all parts: a left fold of plane additions, in the order of `parts` -- what the device
+    holds after the same dates were accumulated in that order."""
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    sums, counts, dates = first.sums.copy(), first.counts.copy(), first.dates
+    for p in parts[1:]:
+      if p.n_members != first.n_members or p.channels != first.channels or p.sums.shape != first.sums.shape:
+        raise ValueError("merge: the score maps differ in members, channels or shape")
+      sums = sums + p.sums
+      counts = counts + p.counts
+      dates += p.dates
+    return ScoreMaps(sums, counts, first.n_members, first.channels, dates)
+
+  def region(self, weights) -> MapRegionScores:
+    """The column sums of `EnsembleScores` over the nodes: S0 = sum_g w N0, S1 .. S5 = sum_g w P0 .. P4, per (batch, channel);
+    `weights` [G] (a mask, or node weights times a mask).  Any region chosen after the fact is such a weighted sum of planes."""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape != (self.sums.shape[1],):
+      raise ValueError(f"weights must have shape ({self.sums.shape[1]},)")
+    planes = np.concatenate([self.counts[:1].astype(np.float64), self.sums[:5]])
+    sums = np.moveaxis(np.tensordot(w, planes, axes=([0], [1])), 0, -1)          # [B, C', 6]
+    inside = w != 0.0
+    hist = np.zeros(sums.shape[:2] + (self.n_members + 1,), np.uint64)
+    hist[..., 0] = self.counts[1][inside].sum(axis=0, dtype=np.uint64)
+    hist[..., -1] = self.counts[2][inside].sum(axis=0, dtype=np.uint64)
+    return MapRegionScores(sums, hist, self.n_members, self.counts[0][inside].sum(axis=0, dtype=np.uint64))
+
+  def to_dataset(self, template, name: str = "crps"):
+    """The score `name` (a property of this class) as a Dataset on the lat / lon of `template`: the variables of the template,
+    NaN at the points that never counted and in the channels the maps do not cover."""
+    if name.startswith("_") or not isinstance(getattr(type(self), name, None), property):
+      raise ValueError(f"{name!r} is not a score of {type(self).__name__}")
+    return _map_field(getattr(self, name), self.counts[0] > 0, template, self.channels, None)
+
+
+class EventMaps:
+  """The event planes of `gc_ens_map_download` for one slot: `events` [T, 5, G, B, C'] uint32 (E0 dates counted, E1 sum k,
+  E2 sum k^2, E3 sum k o, E4 sum o; k members in the event, o the truth in it), with M, the `directions` [T] of the events,
+  the `channels` and the `dates` added.  Scores are [T, G, B, C'] float64, NaN where the point never counted."""
+
+  def __init__(self, events, n_members: int, directions=None, channels=None, dates: int = 0):
+    self.events = np.asarray(events, dtype=np.uint32)
+    self.n_members = int(n_members)
+    if self.n_members < 2:
+      raise ValueError("n_members must be >= 2")
+    if self.events.ndim != 5 or self.events.shape[1] != 5:
+      raise ValueError(f"events must be [T, 5, G, batch, channels], got {self.events.shape}")
+    self.directions = None if directions is None else tuple(int(np.sign(d)) for d in directions)
+    if self.directions is not None and len(self.directions) != self.events.shape[0]:
+      raise ValueError(f"directions must be {self.events.shape[0]} signs")
+    self.channels = _map_channels(channels, self.events.shape[-1])
+    self.dates = int(dates)
+
+  @staticmethod
+  def _brier(e, m: float) -> np.ndarray:
+    """(E2 / M^2 - 2 E3 / M + E4) / E0 from planes (or weighted sums of planes) in float64: the numerator as the integer
+    E2 - 2 M E3 + M^2 E4, so nothing cancels in rounded numbers."""
+    e0 = np.where(e[:, 0] > 0.0, e[:, 0], np.nan)
+    return (e[:, 2] - 2.0 * m * e[:, 3] + m * m * e[:, 4]) / (m * m * e0)
+
+  @property
+  def valid_dates(self) -> np.ndarray:
+    return self.events[:, 0]
+
+  @property
+  def brier(self) -> np.ndarray:
+    return self._brier(self.events.astype(np.float64), float(self.n_members))
+
+  @property
+  def base_rate(self) -> np.ndarray:
+    e = self.events.astype(np.float64)
+    return e[:, 4] / np.where(e[:, 0] > 0.0, e[:, 0], np.nan)
+
+  @property
+  def forecast_probability(self) -> np.ndarray:
+    e = self.events.astype(np.float64)
+    return e[:, 1] / (float(self.n_members) * np.where(e[:, 0] > 0.0, e[:, 0], np.nan))
+
+  @staticmethod
+  def merge(parts: Sequence["EventMaps"]) -> "EventMaps":
+    parts = list(parts)
+    if not parts:
+      raise ValueError("merge: nothing to merge")
+    first = parts[0]
+    events, dates = first.events.copy(), first.dates
+    for p in parts[1:]:
+      if (p.n_members != first.n_members or p.channels != first.channels or p.events.shape != first.events.shape
+          or p.directions != first.directions):
+        raise ValueError("merge: the event maps differ in members, channels, directions or shape")
+      events = events + p.events
+      dates += p.dates
+    return EventMaps(events, first.n_members, first.directions, first.channels, dates)
+
+  def region(self, weights) -> Dict[str, np.ndarray]:
+    """{"brier", "base_rate", "forecast_probability", "valid_weight"}: [T, B, C'] over the nodes with `weights` [G] -- with the
+    integer weights of `quantize_node_weights` the sums are exact below 2^53, as the tables of `EventScores` are."""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape != (self.events.shape[2],):
+      raise ValueError(f"weights must have shape ({self.events.shape[2]},)")
+    e = np.tensordot(self.events.astype(np.float64), w, axes=([2], [0]))             # [T, 5, B, C']
+    e0 = np.where(e[:, 0] > 0.0, e[:, 0], np.nan)
+    return {"brier": self._brier(e, float(self.n_members)), "base_rate": e[:, 4] / e0,
+            "forecast_probability": e[:, 1] / (float(self.n_members) * e0), "valid_weight": e[:, 0]}
+
+  def to_dataset(self, template, name: str = "brier", threshold: int = 0):
+    if name.startswith("_") or not isinstance(getattr(type(self), name, None), property):
+      raise ValueError(f"{name!r} is not a score of {type(self).__name__}")
+    return _map_field(getattr(self, name)[threshold], self.events[threshold, 0] > 0, template, self.channels, None)
+
+
+# ---------------------------------------------------------------------------------------------
 # the scorers of a member store, each declared once
 # ---------------------------------------------------------------------------------------------
 class Scorer(NamedTuple):
@@ -2495,8 +2823,29 @@ EFI_SCORER = Scorer("efi", "extreme forecast index", set=_set_efi, score=_score_
                     carried_by=("ensemble", "derived"))
 
 
+def _set_maps(store):
+  """Makes (and zeroes) the accumulators of the store's handle.  A store with `maps_resident` keeps what the handle holds
+  when it was made for the same channels, slots and thresholds -- the sums of earlier runs -- and refuses another plan."""
+  T = store.events.n_thresholds if store.maps.events else 0
+  key = (None if store.map_channels is None else tuple(int(c) for c in store.map_channels), store.map_slots, T)
+  held = getattr(store.handle, "_resident_map_plan", None)
+  if store.maps_resident and held is not None:
+    if held != key:
+      raise ValueError(f"maps_resident: the handle holds sums of another plan or horizon (channels, slots, thresholds {held}, now "
+                       f"{key}): download them and call reset_maps(), or run without maps_resident")
+    return
+  store.handle.ens_map_set(store.map_channels, store.map_slots, T)
+  store.handle._resident_map_plan = key if store.maps_resident else None   # pylint: disable=protected-access
+
+
+# The score maps (gc_ens_map_*): per-point accumulators over dates.  Beside the table for the reason the index is: the
+# table's series are a recorded surface.  `set` makes (and zeroes) the accumulators; a store adds a date with
+# `accumulate_maps`, so the row has no `score` of the per-lead kind.
+MAP_SCORER = Scorer("maps", "score maps", ("map_channels", "map_slots"), set=_set_maps, scaled=True)
+
+
 def scorer(name: str) -> Scorer:
-  return next(row for row in SCORERS + [EFI_SCORER] if row.name == name)
+  return next(row for row in SCORERS + [EFI_SCORER, MAP_SCORER] if row.name == name)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2523,9 +2872,13 @@ class ScoredStore:
   a handle, or thresholds that change from call to call (assign `thresholds` before the call)."""
 
   def __init__(self, handle, n_members: int, node_weight=None, *, plan=None, source=None, set_per_score: bool = False,
-               climatology=None, climatology_source=None, feature_plan=None, band_plan=None, efi=None, **scorers):
+               climatology=None, climatology_source=None, feature_plan=None, band_plan=None, efi=None, maps=None,
+               map_channels=None, map_slots: int = 1, maps_resident: bool = False, **scorers):
     """`scorers`: per row of `SCORERS` with a `score`, its name (what switches it on) and its settings, None by default.
-    `efi`: an `EfiSpec` for `score_efi` (it needs the `climatology` handle, and `weight_q` where it has events)."""
+    `efi`: an `EfiSpec` for `score_efi` (it needs the `climatology` handle, and `weight_q` where it has events).
+    `maps`: a `MapSpec` for `accumulate_maps` / `download_maps` / `reset_maps`, with `map_channels` = `maps.channels(template)`
+    (None: every channel of the store) and `map_slots` (1..128) the slots the accumulators get; `maps_resident`: `configure`
+    keeps the sums the handle already holds for the same plan (`forget_maps` ends that)."""
     for row in (r for r in SCORERS if r.score is not None):
       for key in (row.name,) + row.settings:
         setattr(self, key, scorers.pop(key, None))
@@ -2545,6 +2898,21 @@ class ScoredStore:
       if efi.n_events and self.weight_q is None:
         raise ValueError("the events of an EfiSpec need the quantised node weights (quantize_node_weights)")
     self.efi, self._efi_set_for = efi, None      # (K the events and bins were last handed over for)
+    if maps is not None:
+      if not isinstance(maps, MapSpec):
+        raise TypeError("maps must be a MapSpec")
+      if set_per_score:
+        raise ValueError("maps: a store that shares its handle with another (set_per_score) cannot keep score maps -- two "
+                         "views must not add into one accumulator")
+      if maps.events and self.events is None:
+        raise ValueError("maps: event planes (MapSpec(events=True)) need the store's EventSpec (events=...)")
+      if not 1 <= int(map_slots) <= 128:
+        raise ValueError("map_slots must be in 1..128")
+      if map_channels is None and (maps.variables is not None or maps.levels is not None):
+        raise ValueError("maps: a MapSpec that selects variables or levels needs map_channels = maps.channels(template)")
+    self.maps = maps
+    self.map_channels = None if map_channels is None else np.asarray(map_channels, dtype=np.int32).reshape(-1)
+    self.map_slots, self.maps_resident = int(map_slots), bool(maps_resident)
     if plan is not None and feature_plan is not None:
       raise ValueError("a store is filled by a derive plan or by a feature plan, not both")
     if band_plan is not None and (plan is not None or feature_plan is not None):
@@ -2577,7 +2945,7 @@ class ScoredStore:
     """The plan, then every scorer that is switched on, in the order of `SCORERS` -- the thresholds, the probabilities, the
     multivariate plans, the tails and the regions: all survive `ens_reserve` and every score."""
     self._set_plan()
-    for row in SCORERS + [EFI_SCORER]:
+    for row in SCORERS + [EFI_SCORER, MAP_SCORER]:
       if row.set is not None and getattr(self, row.name) is not None:
         row.set(self)
 
@@ -2691,6 +3059,40 @@ class ScoredStore:
   def efi_fields(self, *, observed: bool = True) -> Tuple[np.ndarray, ...]:
     """The EFI field [G, B, c_out] of the last `score_efi`, downloaded, and with `observed` the observed index too."""
     return tuple(self.handle.ens_efi_field(i) for i in range(2 if observed else 1))
+
+  def _need_maps(self, who: str) -> None:
+    if self.maps is None:
+      raise ValueError(f"{who}: the store has no MapSpec (maps=...)")
+
+  def accumulate_maps(self, slot: int, truth=None) -> None:
+    """Adds the date in the store into the planes of `slot` (`gc_ens_map_accumulate`), and with `MapSpec(events=True)` the
+    codes of the store's last event score into its event planes: call it after `score`, which fills a derived view and
+    counts the events.  `truth` None: the truth already on the device."""
+    self._need_maps("accumulate_maps")
+    self.handle.ens_map_accumulate(slot, truth)
+    if self.maps.events:
+      self.handle.ens_map_accumulate_events(slot)
+
+  def download_maps(self, slot: int):
+    """-> `ScoreMaps` of `slot`, raw (in the members' units); with `MapSpec(events=True)` -> (`ScoreMaps`, `EventMaps`)."""
+    self._need_maps("download_maps")
+    sums, counts, events, dates = self.handle.ens_map_download(slot, self.maps.events)
+    C = sums.shape[-1]
+    channels = tuple(range(C)) if self.map_channels is None else tuple(int(c) for c in self.map_channels)
+    maps = ScoreMaps(sums, counts, self.n_members, channels, int(dates[0]))
+    if not self.maps.events:
+      return maps
+    return maps, EventMaps(events, self.n_members, self.events.directions, channels, int(dates[1]))
+
+  def reset_maps(self, slot: Optional[int] = None) -> None:
+    """Zeroes the planes of `slot` (None: of every slot)."""
+    self._need_maps("reset_maps")
+    self.handle.ens_map_reset(-1 if slot is None else int(slot))
+
+  def forget_maps(self) -> None:
+    """Zeroes every slot and lets the next `configure` make accumulators for another plan (the end of `maps_resident`)."""
+    self.reset_maps()
+    self.handle._resident_map_plan = None          # pylint: disable=protected-access
 
   def centres(self) -> Dict[str, list]:
     """The centres the last `score` found on a store with a `feature_plan` (`ens_feature_centres`), as `unpack_centres`

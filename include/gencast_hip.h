@@ -814,6 +814,63 @@ int gc_ens_efi_fields(gc_handle* h, gc_handle* clim, const double* table /* [K +
 int gc_ens_efi_download(gc_handle* h, int32_t which /* 0 EFI, 1 observed index */, float* field /* [G,B,c_out] */);
 
 /*
+ * Score maps on the device: every unit above ends in a table per batch member and channel; this one
+ * says WHERE the forecast is good.  The marginal scores of gc_ens_score are kept per grid point and added up over dates on
+ * the device, one set of planes per slot (a slot is a lead time).  The reference project has no verification code; the
+ * yardstick is the definition below, restated in tests/map_reference.py.
+ * Store, truth and validity are those of gc_ens_score: members x_0 .. x_{M-1} and truth y are [G, B, c_out] float32; a point
+ * counts when y and all M members are finite there.  No node weight is read.  The plan selects C' channels (ascending,
+ * distinct; NULL = all), L slots and T event thresholds.
+ * Per counted point, in double from the float32 values, each operation rounded once and nothing contracted:
+ *   m  = (sum_i x_i) / M                                i ascending (slot order)
+ *   s2 = (sum_i (x_i - m) (x_i - m)) / (M - 1)          the same order
+ *   e  = m - y
+ *   with the members sorted ascending x_(0) <= .. <= x_(M-1):
+ *   ae = (sum_k |x_(k) - y|) / M                        k ascending
+ *   d  = (sum_{k=1}^{M-1} (double)(k (M - k)) (x_(k) - x_(k-1))) / (M (M - 1) / 2)     k ascending; no term cancels
+ *   c  = ae - 0.5 d                                     the fair CRPS of the point
+ *   r  = #{i : x_i < y}                                 a member equal to y is not below it
+ * The planes of a slot, per point (g, b, c'); dates add in call order, so a plane is the left fold of the per-date doubles:
+ *   sums   [6]: P0 += e   P1 += e e   P2 += s2   P3 += ae   P4 += d   P5 += c c          (double)
+ *   counts [3]: N0 += 1   N1 += [r == 0]   N2 += [r == M]                                 (uint32)
+ * A point that does not count on a date adds nothing to any plane.  Event planes, from the byte per point and threshold
+ * that gc_ens_event_score leaves (code = k | o << 7, 255 = not counted), uint32:
+ *   events [T][5]: E0 += 1   E1 += k   E2 += k k   E3 += k o   E4 += o
+ * Every point has one owner thread: no partials, no finish pass, no atomics; the planes equal the definition byte for byte.
+ * Scores are formed on the host from the planes (bias = P0 / N0, fair crps = (P3 - P4 / 2) / N0,
+ * brier = (E2 / M^2 - 2 E3 / M + E4) / E0 ...); the planes add over dates and merge over runs, scores do not.
+ *   gc_ens_map_set                the plan; allocates and zeroes [L][6 + 3 + 5 T] planes of G B C' values.  A repeated call
+ *                                 replaces and zeroes ("device_allocations" stays flat).  The planes are not sized by M and
+ *                                 survive gc_ens_reserve; released by gc_destroy.  GC_ERR_UNSUPPORTED: n_slots outside
+ *                                 1..128, n_event_thresholds outside 0..8.  GC_ERR_INVALID_ARGUMENT: n_channels outside
+ *                                 1..c_out, a channel outside [0, c_out), channels not ascending or repeated.
+ *   gc_ens_map_accumulate         adds the date in the store into `slot`.  Synchronous.  A slot remembers the M of its first
+ *                                 date.  Faults, in this order: no graph; no plan; slot outside [0, L)
+ *                                 (GC_ERR_INVALID_ARGUMENT); no member store; a member slot not pushed; no truth; another M
+ *                                 than the slot holds ("reset the slot first").  All but the slot are GC_ERR_STATE.
+ *   gc_ens_map_accumulate_events  adds the codes of the last gc_ens_event_score into `slot`.  Faults, in this order: no
+ *                                 graph; no plan; a plan without event planes; slot outside [0, L); no member store; the T
+ *                                 of gc_ens_event_set differs from the plan's; no event score since gc_ens_event_set /
+ *                                 gc_ens_reserve / the last rewrite of the store; another M than the slot holds.
+ *   gc_ens_map_download           the planes of one slot and the number of field / event calls added into it.
+ *                                 GC_ERR_INVALID_ARGUMENT: a bad slot, sums or counts NULL, events given for a plan with T = 0.
+ *   gc_ens_map_reset              zeroes a slot (-1: every slot) and forgets its M and its dates.
+ * All five need gc_set_graph only; download and reset report no graph, no plan, the slot, in that order.  None of them
+ * touches the member store, the truth (beyond storing the one passed), the mean / variance, quantile, EFI or code fields,
+ * the conditioning, the last sample or the captured graphs.
+ * Counters: "ens_map_calls", "ens_map_device_us" (HIP-event time of the last accumulate), "ens_map_invalid_points" (selected
+ * points the last gc_ens_map_accumulate skipped), "ens_map_blocks" (grid.x of the last pass: one point per thread up to
+ * 1024 workgroups, which then stride), "ens_map_bytes" (the accumulator bytes of the plan).
+ */
+int gc_ens_map_set(gc_handle* h, int32_t n_channels, const int32_t* channel /* [C'] or NULL = all */,
+                   int32_t n_slots /* 1..128 */, int32_t n_event_thresholds /* 0..8, 0 = no event planes */);
+int gc_ens_map_accumulate(gc_handle* h, int32_t slot, const float* truth /* NULL = the truth uploaded last */);
+int gc_ens_map_accumulate_events(gc_handle* h, int32_t slot);   /* the codes of the last gc_ens_event_score */
+int gc_ens_map_download(gc_handle* h, int32_t slot, double* sums /* [6][G][B][C'] */, uint32_t* counts /* [3][G][B][C'] */,
+                        uint32_t* events /* [T][5][G][B][C'], NULL allowed */, int64_t* dates /* [2]: field / event calls, NULL allowed */);
+int gc_ens_map_reset(gc_handle* h, int32_t slot /* -1 = every slot */);
+
+/*
  * Time-window ensemble fields on the device: accumulations, means, changes and extremes over the
  * last L lead times of a rollout -- 24 h precipitation from 12 h steps, a weekly mean, the highest wind speed within three
  * days -- formed from the members and the truths that one handle's gc_ens_* store held at those lead times and left in the
@@ -1177,7 +1234,7 @@ int gc_algorithmic_work(gc_handle* h, double* flops, double* bytes);
  * the evaluations of the last gc_loss_resident call, microseconds). */
 /* Launch geometry of the last call of an ensemble unit (0 before its first call): "<prefix>_blocks" for the prefixes
  * ens_event, ens_derive, ens_band, ens_order, ens_clim, ens_efi, ens_energy, ens_variogram, ens_tail, ens_region,
- * ens_feature and ens_fss, and "ens_score_blocks" for gc_ens_score -- the node-range workgroups (grid.x) of the call's main
+ * ens_feature, ens_fss and ens_map, and "ens_score_blocks" for gc_ens_score -- the node-range workgroups (grid.x) of the call's main
  * pass.  Every pass caps that number (2048, 1024, 1024 / (thresholds x column tiles), 2048 / (batch x groups), 256 ...);
  * above the cap a workgroup walks more nodes and the trailing workgroups may have none, so the counter says which regime
  * a call ran in.  Where a call has two passes of different geometry it is the pass with a cap of its own:
