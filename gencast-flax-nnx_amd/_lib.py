@@ -1502,7 +1502,8 @@ class NativeDenoiser:
     self._check(self._lib.gc_comm_destroy(self._h))
 
   def counter(self, name: str) -> int:
-    """Named counters: range_fallbacks, launches_per_call, weights_f16_unsafe, loss_evaluations, ... (gc_get_counter)."""
+    """Named counters: range_fallbacks, launches_per_call, weights_f16_unsafe, loss_evaluations, ... (gc_get_counter);
+    poison_allocs and poison_bytes: the device buffers GC_DEBUG_POISON=1 has filled on this handle (0 without it)."""
     v = ctypes.c_int64()
     self._check(self._lib.gc_get_counter(self._h, name.encode(), ctypes.byref(v)))
     return v.value

@@ -148,7 +148,8 @@ const char* gc_last_error(const gc_handle* h) { return h ? h->err.c_str() : g_cr
 // The environment switches, all read here, once per handle (gc_create).  GC_PRECISION and GC_TUNE_GRAPH set the
 // defaults of gc_set_option's "precision" and "graphs"; M2G_FUSE_SUM, EMBED_CACHE, ATTN_ITEMS, MLP_PAIR, EDGE_TERMS and A16 select
 // the other form of a fused path (the tests' bit-identity references); GRAPH_SERIALIZE and GRAPH_VERBOSE are the
-// graph-replay safety valve and its diagnostics (run_sampler).
+// graph-replay safety valve and its diagnostics (run_sampler).  GC_DEBUG_POISON=1 makes dev_alloc fill every new buffer
+// (gc_handle.h; never timed).
 static void read_switches(gc_handle* h) {
   auto is = [](const char* name, const char* value) { const char* v = std::getenv(name); return v && std::string(v) == value; };
   auto off = [](const char* name) { const char* v = std::getenv(name); return v && *v && std::atoi(v) == 0; };
@@ -163,6 +164,7 @@ static void read_switches(gc_handle* h) {
   h->a16 = !off("GC_TUNE_A16");
   h->graph_serialize = on("GC_TUNE_GRAPH_SERIALIZE");
   h->graph_verbose = on("GC_TUNE_GRAPH_VERBOSE");
+  h->poison = on("GC_DEBUG_POISON");
 }
 
 int gc_create(const gc_config* cfg, int device_id, gc_handle** out) {
@@ -402,7 +404,7 @@ int gc_set_graph(gc_handle* h, int32_t G, int32_t M, int32_t E1, const int32_t* 
     return rc;
   {
     uint16_t* kv = nullptr;
-    if ((rc = dev_alloc(h, &kv, MB * 4 * D))) return rc;
+    if ((rc = dev_alloc(h, &kv, MB * 4 * D, nullptr, true))) return rc;   // fp16 planes: poisoned as NaN
     h->d_kv16 = kv;
   }
   if ((rc = dev_alloc(h, &h->d_u, MB * F))) return rc;
@@ -451,8 +453,8 @@ int gc_set_graph(gc_handle* h, int32_t G, int32_t M, int32_t E1, const int32_t* 
   if ((rc = dev_alloc(h, &h->d_slots, (size_t)c.c_out))) return rc;
   if ((rc = alloc_all({{&h->d_m0_hat, (size_t)M * L}, {&h->d_e0_hat, (size_t)E1 * L}, {&h->d_f0_hat, (size_t)E2 * L}}))) return rc;
   GC_HIP(h, hipMemset(h->d_xp, 0, GB * h->kp * sizeof(float)));
-  GC_HIP(h, hipHostMalloc((void**)&h->pin_cond, GB * c.c_in * sizeof(float), hipHostMallocDefault));
-  GC_HIP(h, hipHostMalloc((void**)&h->pin_noise, GB * c.c_out * sizeof(float), hipHostMallocDefault));
+  GC_HIP(h, pinned_alloc(h, &h->pin_cond, GB * c.c_in));
+  GC_HIP(h, pinned_alloc(h, &h->pin_noise, GB * c.c_out));
   h->has_graph = true;
   h->finalized = false;
   return GC_OK;
@@ -750,7 +752,7 @@ int gc_rollout_plan(gc_handle* h, const int32_t* kind, const int32_t* src, const
     GC_HIP(h, hipEventSynchronize(h->ev_pin));
     if (h->pin_forc) GC_HIP(h, hipHostFree(h->pin_forc));
     h->pin_forc = nullptr;
-    GC_HIP(h, hipHostMalloc((void**)&h->pin_forc, GB * n_forcing * sizeof(float), hipHostMallocDefault));
+    GC_HIP(h, pinned_alloc(h, &h->pin_forc, GB * n_forcing));
     h->ro_forc_cap = n_forcing;
   }
   h->ro_nforc = n_forcing;
@@ -922,6 +924,8 @@ int gc_get_counter(gc_handle* h, const char* name, int64_t* value) {
     *value = (int64_t)(L * (((M + 1) * h->hg.G * h->cfg.batch * h->cfg.c_out + 3) / 4 * 4) * sizeof(float));
   }
   else if (n == "ens_map_bytes") *value = h->map_set ? h->map_bytes : 0;
+  else if (n == "poison_allocs") *value = h->poison_allocs;
+  else if (n == "poison_bytes") *value = h->poison_bytes;
   else if (n == "noise_stream") *value = (int64_t)h->nz_stream;
   else if (n == "device_allocations") {
     *value = 0;
@@ -1100,7 +1104,7 @@ int gc_loss_resident(gc_handle* h, const float* sigmas, int32_t n_eval, int32_t 
       return rc;
     unsigned* pin = nullptr;                     // the new block first: a failure leaves the old one and loss_cap = 0
     h->loss_cap = 0;
-    GC_HIP(h, hipHostMalloc((void**)&pin, (size_t)cap * sizeof(unsigned), hipHostMallocDefault));
+    GC_HIP(h, pinned_alloc(h, &pin, (size_t)cap));
     if (h->pin_lguard) (void)hipHostFree(h->pin_lguard);
     h->pin_lguard = pin;
     h->loss_cap = cap;

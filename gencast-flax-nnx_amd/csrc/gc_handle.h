@@ -37,6 +37,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <rccl/rccl.h>   // types and enums only: librccl.so.1 is dlopen'ed on first use (gc_comm_*)
@@ -310,6 +311,8 @@ struct gc_handle {
   bool attn_items = true;                    // GC_TUNE_ATTN_ITEMS=0: the plain (tile, split) attention launch
   bool graph_serialize = false;              // GC_TUNE_GRAPH_SERIALIZE=1: every hipGraphLaunch also takes the capture mutex (run_sampler)
   bool graph_verbose = false;                // GC_TUNE_GRAPH_VERBOSE=1: graph capture progress on stderr
+  bool poison = false;                       // GC_DEBUG_POISON=1: dev_alloc fills every new buffer (NaN / 0x01 bytes), the pinned staging buffers get 0xFF
+  int64_t poison_allocs = 0, poison_bytes = 0;   // device buffers filled so far, and their bytes (gc_get_counter)
   // sampler state
   int* d_slots = nullptr;
   float *d_sx = nullptr, *d_sden = nullptr, *d_smid = nullptr, *d_noise = nullptr;
@@ -645,14 +648,38 @@ inline int fail(gc_handle* h, int code, const std::string& msg) {
   return code;
 }
 
-// owner: the list that frees the buffer (default h->allocs: freed in destroy)
+// Poison mode (GC_DEBUG_POISON=1, DESIGN.md "Poisoned allocations"): the bytes a fresh buffer is filled with.  0xFF makes
+// every float, double and fp16 word a NaN.  0x01 makes a stray count 16 843 009 and a stray event code (k = 1, o = 0), both
+// of which the `==` assertions see, and keeps a stray index or loop bound bounded (0xFF would read as "not counted" in the
+// event codes and as 4 294 967 295 in a bound).
+constexpr int kPoisonFloat = 0xFF, kPoisonInt = 0x01;
+
+// owner: the list that frees the buffer (default h->allocs: freed in destroy).  as_float: the buffer holds floating-point
+// values (what its poison pattern follows): by default what T says; an fp16 plane behind an integer container passes true.
 template <typename T>
-int dev_alloc(gc_handle* h, T** p, size_t count, BufferGroup* owner = nullptr) {
+int dev_alloc(gc_handle* h, T** p, size_t count, BufferGroup* owner = nullptr, bool as_float = std::is_floating_point<T>::value) {
   void* q = nullptr;
-  GC_HIP(h, hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+  GC_HIP(h, hipMalloc(&q, bytes));
   (owner ? owner : &h->allocs)->ptrs.push_back(q);
+  if (h->poison) {
+    // a synchronous fill, complete before anything on the handle's non-blocking streams (which the null stream does not
+    // order) or a `from` copy of the caller can touch the buffer; this mode is never timed
+    GC_HIP(h, hipMemset(q, as_float ? kPoisonFloat : kPoisonInt, bytes));
+    GC_HIP(h, hipDeviceSynchronize());
+    ++h->poison_allocs;
+    h->poison_bytes += (int64_t)bytes;
+  }
   *p = reinterpret_cast<T*>(q);
   return GC_OK;
+}
+
+// A pinned staging buffer of the handle; poison mode fills it with 0xFF on the host.
+template <typename T>
+hipError_t pinned_alloc(gc_handle* h, T** p, size_t count) {
+  const hipError_t e = hipHostMalloc((void**)p, count * sizeof(T), hipHostMallocDefault);
+  if (e == hipSuccess && h->poison) std::memset(*p, kPoisonFloat, count * sizeof(T));
+  return e;
 }
 
 template <typename T>

@@ -1245,6 +1245,12 @@ int gc_algorithmic_work(gc_handle* h, double* flops, double* bytes);
  * threshold of the last gc_ens_fss_score went through (the work buffer's byte budget or the 256-column limit cut them). */
 /* ... and "device_allocations" (device buffers the handle holds now: gc_finalize and gc_set_noisy_slots replace theirs, they do not add),
  * "noise_stream" (the Philox stream the next drawn field will use: gc_noise_seed sets it, every initial-noise and churn field adds one). */
+/* Poison mode, a debugging aid that is never timed: with GC_DEBUG_POISON=1 in the environment when gc_create runs, every
+ * device buffer the handle allocates from then on is filled before anything else touches it -- bytes 0xFF where it holds
+ * floating-point values (float, double, the fp16 K / V planes: every word a NaN), bytes 0x01 where it holds integers or
+ * mixed work bytes (a stray count reads 16 843 009, a stray index stays small) -- and the pinned staging buffers are filled
+ * with 0xFF on the host.  A result that depends on a word the library never wrote then differs from the result without
+ * the switch.  "poison_allocs" (device buffers filled so far) and "poison_bytes" (their bytes) read 0 without the switch. */
 int gc_get_counter(gc_handle* h, const char* name, int64_t* value);
 
 #ifdef __cplusplus

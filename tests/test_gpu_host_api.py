@@ -949,7 +949,7 @@ def test_one_degree_fp16_rollout_two_steps_compose_as_the_oracle_says():
 COUNTERS = (
     "range_fallbacks", "static_embedding_fallbacks", "launches_per_call", "weights_f16_unsafe", "fp16_storage", "split_edge",
     "attention_items", "m2g_fused_sum", "embed_cache", "edge_term_samples", "edge_term_cache_bytes", "graph_replays",
-    "graph_captures", "loss_evaluations", "loss_device_us",
+    "graph_captures", "loss_evaluations", "loss_device_us", "poison_allocs", "poison_bytes",
     "ens_scores", "ens_score_device_us", "ens_invalid_points",
     "spec_calls", "spec_device_us", "spec_invalid_columns",
     "ens_event_calls", "ens_event_device_us", "ens_event_invalid_points",
