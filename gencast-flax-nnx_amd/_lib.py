@@ -46,7 +46,12 @@ class GencastHipError(RuntimeError):
 _f32p = ctypes.POINTER(ctypes.c_float)
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _i64p = ctypes.POINTER(ctypes.c_int64)
+_f64p = ctypes.POINTER(ctypes.c_double)
+_u64p = ctypes.POINTER(ctypes.c_uint64)
+_u32p = ctypes.POINTER(ctypes.c_uint32)
+_u8p = ctypes.POINTER(ctypes.c_uint8)
 _hp = ctypes.c_void_p
+_hpp = ctypes.POINTER(_hp)
 
 # name -> (restype, argtypes); every symbol include/gencast_hip.h (+ _debug.h) declares.
 SIGNATURES = {
@@ -55,24 +60,21 @@ SIGNATURES = {
     "gc_device_count": (ctypes.c_int, []),
     "gc_device_pci_bus_id": (ctypes.c_int, [ctypes.c_int32, ctypes.c_char_p, ctypes.c_int64]),
     "gc_last_error": (ctypes.c_char_p, [_hp]),
-    "gc_create": (ctypes.c_int, [ctypes.POINTER(GcConfig), ctypes.c_int, ctypes.POINTER(_hp)]),
+    "gc_create": (ctypes.c_int, [ctypes.POINTER(GcConfig), ctypes.c_int, _hpp]),
     "gc_destroy": (None, [_hp]),
     "gc_set_option": (ctypes.c_int, [_hp, ctypes.c_char_p, ctypes.c_char_p]),
-    "gc_set_graph": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p,
-                                    ctypes.c_int32, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p, _f32p,
-                                    _f32p, _f32p]),
+    "gc_set_graph": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, ctypes.c_int32, _i32p,
+                                    _i32p, _i32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "gc_load_weight": (ctypes.c_int, [_hp, ctypes.c_char_p, _f32p, _i64p, ctypes.c_int32]),
     "gc_missing_weights": (ctypes.c_int, [_hp, _i32p]),
     "gc_finalize": (ctypes.c_int, [_hp]),
     "gc_denoise": (ctypes.c_int, [_hp, _f32p, _f32p, _f32p]),
     "gc_set_noisy_slots": (ctypes.c_int, [_hp, _i32p]),
-    "gc_sample": (ctypes.c_int, [_hp, _f32p, _f32p, _f32p, ctypes.c_int32, ctypes.c_int32, _f32p,
-                                 ctypes.POINTER(GcSampleStats)]),
+    "gc_sample": (ctypes.c_int, [_hp, _f32p, _f32p, _f32p, ctypes.c_int32, ctypes.c_int32, _f32p, ctypes.POINTER(GcSampleStats)]),
     "gc_upload_cond": (ctypes.c_int, [_hp, _f32p]),
     "gc_upload_cond_dev": (ctypes.c_int, [_hp, ctypes.c_void_p]),
     "gc_upload_noise": (ctypes.c_int, [_hp, _f32p]),
-    "gc_sample_resident": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, ctypes.c_int32,
-                                          ctypes.POINTER(GcSampleStats)]),
+    "gc_sample_resident": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GcSampleStats)]),
     "gc_download_sample": (ctypes.c_int, [_hp, _f32p]),
     "gc_stash_sample": (ctypes.c_int, [_hp]),
     "gc_download_stash": (ctypes.c_int, [_hp, _f32p]),
@@ -80,15 +82,14 @@ SIGNATURES = {
     "gc_rollout_advance": (ctypes.c_int, [_hp, _f32p]),
     "gc_download_cond": (ctypes.c_int, [_hp, _f32p]),
     "gc_sync": (ctypes.c_int, [_hp]),
-    "gc_cond_device_ptr": (ctypes.c_int, [_hp, ctypes.POINTER(ctypes.c_void_p), _i64p]),
+    "gc_cond_device_ptr": (ctypes.c_int, [_hp, _hpp, _i64p]),
     "gc_commit_cond": (ctypes.c_int, [_hp]),
     "gc_num_kernel_classes": (ctypes.c_int, []),
     "gc_kernel_class_name": (ctypes.c_char_p, [ctypes.c_int]),
     "gc_profile_enable": (ctypes.c_int, [_hp, ctypes.c_int]),
     "gc_profile_set_stride": (ctypes.c_int, [_hp, ctypes.c_int]),
     "gc_profile_read": (ctypes.c_int, [_hp, _i32p, _f32p]),
-    "gc_algorithmic_work": (ctypes.c_int, [_hp, ctypes.POINTER(ctypes.c_double),
-                                           ctypes.POINTER(ctypes.c_double)]),
+    "gc_algorithmic_work": (ctypes.c_int, [_hp, _f64p, _f64p]),
     "gc_get_counter": (ctypes.c_int, [_hp, ctypes.c_char_p, _i64p]),
     "gc_noise_set_tables": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p, _f32p]),
     "gc_noise_seed": (ctypes.c_int, [_hp, ctypes.c_uint64, ctypes.c_uint64]),
@@ -104,8 +105,7 @@ SIGNATURES = {
     "gc_ens_set_node_weight": (ctypes.c_int, [_hp, _f32p]),
     "gc_ens_push": (ctypes.c_int, [_hp, ctypes.c_int32, _hp]),
     "gc_ens_push_host": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
-    "gc_ens_score": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, ctypes.POINTER(ctypes.c_double),
-                                    ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_score": (ctypes.c_int, [_hp, _f32p, ctypes.c_int32, _f64p, _u64p]),
     "gc_ens_download_fields": (ctypes.c_int, [_hp, _f32p, _f32p]),
     "gc_ctx_reserve": (ctypes.c_int, [_hp, ctypes.c_int32]),
     "gc_ctx_save": (ctypes.c_int, [_hp, ctypes.c_int32, _hp]),
@@ -114,72 +114,57 @@ SIGNATURES = {
     "gc_ens_push_state": (ctypes.c_int, [_hp, ctypes.c_int32, _hp, _i32p]),
     "gc_ens_download_member": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
     "gc_spec_set_tables": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p, _f32p]),
-    "gc_spec_field": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double)]),
-    "gc_ens_spectrum": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
-    "gc_ens_event_set": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p, _i32p, ctypes.POINTER(ctypes.c_uint32)]),
-    "gc_ens_event_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
-                                          ctypes.POINTER(ctypes.c_uint64)]),
-    "gc_ens_event_download": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint8)]),
-    "gc_ens_fss_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p,
-                                      ctypes.POINTER(ctypes.c_uint32)]),
-    "gc_ens_fss_score": (ctypes.c_int, [_hp, ctypes.POINTER(ctypes.c_double)]),
+    "gc_spec_field": (ctypes.c_int, [_hp, _f32p, _f64p]),
+    "gc_ens_spectrum": (ctypes.c_int, [_hp, _f32p, _f64p, _f64p]),
+    "gc_ens_event_set": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p, _i32p, _u32p]),
+    "gc_ens_event_score": (ctypes.c_int, [_hp, _f32p, _u64p, _u64p, _u64p]),
+    "gc_ens_event_download": (ctypes.c_int, [_hp, ctypes.c_int32, _u8p]),
+    "gc_ens_fss_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _u32p]),
+    "gc_ens_fss_score": (ctypes.c_int, [_hp, _f64p]),
     "gc_ens_fss_fields": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, _f32p, _f32p]),
-    "gc_ens_derive_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int32,
-                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.POINTER(ctypes.c_double)]),
-    "gc_ens_derive_set_expr": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double), ctypes.c_int32,
-                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.POINTER(ctypes.c_double),
-                                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _i32p, ctypes.c_int32,
-                                              ctypes.POINTER(ctypes.c_double), _i32p, _i32p, ctypes.POINTER(ctypes.c_double),
-                                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.c_double, _i32p]),
+    "gc_ens_derive_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, _i32p, _f64p, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_int32, _i32p, _f64p]),
+    "gc_ens_derive_set_expr": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, _i32p, _f64p, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, _i32p, _f64p, _f64p, _f64p, _i32p, ctypes.c_int32,
+                                              _f64p, _i32p, _i32p, _f64p, _f64p, _f64p, ctypes.c_double, _i32p]),
     "gc_ens_derive": (ctypes.c_int, [_hp, _hp, _f32p]),
-    "gc_ens_band_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), _i32p, _i32p, _i32p,
-                                       _f32p, _f32p, _f32p]),
+    "gc_ens_band_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, _f64p, _i32p, _i32p, _i32p, _f32p, _f32p, _f32p]),
     "gc_ens_band": (ctypes.c_int, [_hp, _hp, _f32p]),
-    "gc_ens_order_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
-    "gc_ens_order_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
-                                          ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_order_set": (ctypes.c_int, [_hp, ctypes.c_int32, _f64p]),
+    "gc_ens_order_score": (ctypes.c_int, [_hp, _f32p, _f64p, _f64p, _f64p, _u64p, _u64p]),
     "gc_ens_order_fields": (ctypes.c_int, [_hp]),
     "gc_ens_order_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
-    "gc_ens_clim_score": (ctypes.c_int, [_hp, _hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
-                                         ctypes.POINTER(ctypes.c_uint64)]),
-    "gc_ens_efi_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
-    "gc_ens_efi_score": (ctypes.c_int, [_hp, _hp, ctypes.POINTER(ctypes.c_double), _f32p, ctypes.POINTER(ctypes.c_double),
-                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
-                                        ctypes.POINTER(ctypes.c_uint64)]),
-    "gc_ens_efi_fields": (ctypes.c_int, [_hp, _hp, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_clim_score": (ctypes.c_int, [_hp, _hp, _f32p, _f64p, _u64p, _u64p]),
+    "gc_ens_efi_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _i32p, ctypes.c_int32, _u32p]),
+    "gc_ens_efi_score": (ctypes.c_int, [_hp, _hp, _f64p, _f32p, _f64p, _u64p, _u64p, _u64p]),
+    "gc_ens_efi_fields": (ctypes.c_int, [_hp, _hp, _f64p]),
     "gc_ens_efi_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
     "gc_ens_map_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, ctypes.c_int32, ctypes.c_int32]),
     "gc_ens_map_accumulate": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p]),
     "gc_ens_map_accumulate_events": (ctypes.c_int, [_hp, ctypes.c_int32]),
-    "gc_ens_map_download": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32),
-                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int64)]),
+    "gc_ens_map_download": (ctypes.c_int, [_hp, ctypes.c_int32, _f64p, _u32p, _u32p, _i64p]),
     "gc_ens_map_reset": (ctypes.c_int, [_hp, ctypes.c_int32]),
-    "gc_ens_window_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
+    "gc_ens_window_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, _f64p]),
     "gc_ens_window_push": (ctypes.c_int, [_hp, _hp, _f32p]),
     "gc_ens_window_emit": (ctypes.c_int, [_hp]),
     "gc_ens_window_reset": (ctypes.c_int, [_hp]),
-    "gc_ens_energy_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, ctypes.POINTER(ctypes.c_double)]),
-    "gc_ens_energy_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                           ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_energy_set": (ctypes.c_int, [_hp, ctypes.c_int32, _i32p, _f64p]),
+    "gc_ens_energy_score": (ctypes.c_int, [_hp, _f32p, _f64p, _f64p, _u64p]),
     "gc_ens_variogram_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _i32p, ctypes.c_double]),
-    "gc_ens_variogram_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_variogram_score": (ctypes.c_int, [_hp, _f32p, _f64p, _u64p]),
     "gc_ens_tail_set": (ctypes.c_int, [_hp, ctypes.c_int32, _f32p, _i32p]),
-    "gc_ens_tail_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
-                                         ctypes.POINTER(ctypes.c_uint64)]),
-    "gc_ens_region_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
-    "gc_ens_region_score": (ctypes.c_int, [_hp, _f32p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
-                                           ctypes.POINTER(ctypes.c_uint64)]),
+    "gc_ens_tail_score": (ctypes.c_int, [_hp, _f32p, _f64p, _u64p, _u64p]),
+    "gc_ens_region_set": (ctypes.c_int, [_hp, ctypes.c_int32, _u32p]),
+    "gc_ens_region_score": (ctypes.c_int, [_hp, _f32p, _f64p, _u64p, _u64p]),
     "gc_ens_feature_set": (ctypes.c_int, [_hp, ctypes.c_int32, ctypes.c_int32, _i32p, _i32p, _i32p, _f32p, ctypes.c_int32,
-                                          ctypes.c_int32, _i32p, _i32p, _i32p, _i32p, ctypes.POINTER(ctypes.c_double), _i32p, _i32p,
-                                          ctypes.c_int32]),
+                                          ctypes.c_int32, _i32p, _i32p, _i32p, _i32p, _f64p, _i32p, _i32p, ctypes.c_int32]),
     "gc_ens_feature": (ctypes.c_int, [_hp, _hp, _f32p]),
     "gc_ens_feature_centres": (ctypes.c_int, [_hp, _i32p, _i32p, _f32p]),
     "gc_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "gc_comm_init": (ctypes.c_int, [_hp, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]),
     "gc_comm_info": (ctypes.c_int, [_hp, _i32p, _i32p]),
     "gc_comm_broadcast_cond": (ctypes.c_int, [_hp, ctypes.c_int32]),
-    "gc_comm_allreduce_max": (ctypes.c_int, [_hp, ctypes.POINTER(ctypes.c_double)]),
+    "gc_comm_allreduce_max": (ctypes.c_int, [_hp, _f64p]),
     "gc_comm_destroy": (ctypes.c_int, [_hp]),
     # include/gencast_hip_debug.h (tests only)
     "gc_debug_fetch": (ctypes.c_int, [_hp, ctypes.c_char_p, _f32p, ctypes.c_int64, _i64p, _i64p]),
@@ -233,8 +218,42 @@ def _i32(a) -> np.ndarray:
   return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _f64(a) -> np.ndarray:
+  return np.ascontiguousarray(a, dtype=np.float64)
+
+
 def _ptr(a: np.ndarray, ty):
   return a.ctypes.data_as(ty)
+
+
+def _opt(a: Optional[np.ndarray], ty):
+  """The pointer argument of an optional array: NULL for None."""
+  return None if a is None else a.ctypes.data_as(ty)
+
+
+def _handle_of(other):
+  """The C handle argument for another object; NULL for None, which the entries that allow it read as this handle itself."""
+  return None if other is None else other._h  # pylint: disable=protected-access
+
+
+def _need(have, missing: str, call: Optional[str] = None, why: Optional[str] = None) -> None:
+  """A state guard: what a C entry would answer with GC_ERR_STATE, said before its result buffers are sized from that state.
+  `missing` is what the object lacks and `call` the method that supplies it (`why`: the text in brackets, where it is another)."""
+  if not have:
+    raise GencastHipError(f"libgencast_hip error 4: no {missing} ({why or call + ' has not been called on this object'})")
+
+
+def _directions(directions, n: int) -> np.ndarray:
+  d = _i32(directions)
+  if d.shape != (n,):
+    raise ValueError(f"directions must have shape ({n},)")
+  return d
+
+
+def _check_r_lon(r: np.ndarray, n_lon: int, name: str = "r_lon") -> None:
+  """A window reaches at most half way round a row of `n_lon` longitudes."""
+  if np.any((r < 0) | (r > (n_lon - 1) // 2)):
+    raise ValueError(f"{name} must lie in 0 .. {(n_lon - 1) // 2}")
 
 
 class NativeDenoiser:
@@ -333,7 +352,7 @@ class NativeDenoiser:
         len(arrs["m2g_s"]), _ptr(arrs["m2g_s"], _i32p), _ptr(arrs["m2g_r"], _i32p),
         _ptr(arrs["rowptr"], _i32p), _ptr(arrs["cols"], _i32p), _ptr(arrs["gs"], _f32p),
         _ptr(arrs["ms"], _f32p), _ptr(arrs["e1"], _f32p), _ptr(arrs["e2"], _f32p),
-        None if xyz is None else _ptr(xyz, _f32p)))
+        _opt(xyz, _f32p)))
     self.num_grid_nodes, self.num_mesh_nodes = G, M
 
   def load_weights(self, params: Dict[str, np.ndarray]) -> None:
@@ -363,6 +382,53 @@ class NativeDenoiser:
   def _shape_out(self):
     return (self.num_grid_nodes, self.cfg.batch, self.cfg.c_out)
 
+  def _field(self, dtype=np.float32) -> np.ndarray:
+    """An output buffer for one [G, B, c_out] field."""
+    return np.empty(self._shape_out(), dtype=dtype)
+
+  def _download(self, entry, *args, shape=None) -> np.ndarray:
+    """`entry(handle, *args, out)` into a fresh float32 field ([G, B, c_out] unless `shape` says otherwise), which it returns."""
+    out = self._field() if shape is None else np.empty(shape, dtype=np.float32)
+    self._check(entry(self._h, *args, _ptr(out, _f32p)))
+    return out
+
+  def _need_store(self) -> None:
+    _need(self._ens_members, "member store", "ens_reserve")
+
+  def _truth_arg(self, truth, channels: Optional[int] = None) -> Optional[np.ndarray]:
+    """The optional truth of a scorer as float32 [G, B, c_out] ([G, B, `channels`] for the source of a view), or None."""
+    if truth is None:
+      return None
+    t = _f32(truth)
+    want = self._shape_out() if channels is None else (self.num_grid_nodes, self.cfg.batch, channels)
+    if t.shape != want:
+      raise ValueError(f"truth must be {want}, got {t.shape}")
+    return t
+
+  def _check_src(self, src) -> None:
+    """`src` is the object whose store a view of this one reads."""
+    if not isinstance(src, NativeDenoiser) or src is self:
+      raise ValueError("src must be another NativeDenoiser")
+
+  def _check_clim(self, clim) -> None:
+    """`clim` is the object that holds the climatological samples."""
+    if not isinstance(clim, NativeDenoiser):
+      raise TypeError("clim must be a NativeDenoiser")
+    if clim is self:
+      raise ValueError("the climatology must be another handle")
+
+  def _weights_q_arg(self, node_weight_q) -> np.ndarray:
+    w = np.asarray(node_weight_q)
+    if w.shape != (self.num_grid_nodes,) or w.dtype.kind not in "ui" or (w.size and (w.min() < 0 or w.max() > 0xFFFFFFFF)):
+      raise ValueError(f"node_weight_q must be unsigned 32-bit integers of shape ({self.num_grid_nodes},)")
+    return np.ascontiguousarray(w, dtype=np.uint32)
+
+  def _thresholds_arg(self, thresholds) -> np.ndarray:
+    thr = _f32(thresholds)
+    if thr.ndim != 4 or thr.shape[1:] != self._shape_out():
+      raise ValueError(f"thresholds must be [T, {', '.join(str(n) for n in self._shape_out())}], got {thr.shape}")
+    return thr
+
   def denoise(self, grid_feats, sigma) -> np.ndarray:
     x = _f32(grid_feats)
     s = _f32(sigma).reshape(-1)
@@ -370,7 +436,7 @@ class NativeDenoiser:
       raise ValueError(f"grid_feats must be {self._shape_in()}, got {x.shape}")
     if s.shape != (self.cfg.batch,):
       raise ValueError("noise_levels expected to be shape (batch,).")
-    out = np.empty(self._shape_out(), dtype=np.float32)
+    out = self._field()
     self._check(self._lib.gc_denoise(self._h, _ptr(x, _f32p), _ptr(s, _f32p), _ptr(out, _f32p)))
     return out
 
@@ -380,7 +446,7 @@ class NativeDenoiser:
       raise ValueError(f"cond_feats must be {self._shape_in()}, got {c.shape}")
     if z.shape != self._shape_out():
       raise ValueError(f"init_noise must be {self._shape_out()}, got {z.shape}")
-    out = np.empty(self._shape_out(), dtype=np.float32)
+    out = self._field()
     st = GcSampleStats()
     self._check(self._lib.gc_sample(self._h, _ptr(c, _f32p), _ptr(z, _f32p), _ptr(sg, _f32p),
                                     len(sg) - 1, int(bool(skip_dead_call)), _ptr(out, _f32p),
@@ -419,9 +485,7 @@ class NativeDenoiser:
     return dict(denoiser_calls=st.denoiser_calls, device_ms=st.device_ms) if want_stats else None
 
   def download_sample(self) -> np.ndarray:
-    out = np.empty(self._shape_out(), dtype=np.float32)
-    self._check(self._lib.gc_download_sample(self._h, _ptr(out, _f32p)))
-    return out
+    return self._download(self._lib.gc_download_sample)
 
   def stash_sample(self) -> None:
     """Waits for the last sample and snapshots it on the device (gc_stash_sample): the handle is free for the next step."""
@@ -429,17 +493,11 @@ class NativeDenoiser:
 
   def download_stash(self) -> np.ndarray:
     """Copies the snapshot to the host on a side stream while the main stream keeps running (gc_download_stash)."""
-    out = np.empty(self._shape_out(), dtype=np.float32)
-    self._check(self._lib.gc_download_stash(self._h, _ptr(out, _f32p)))
-    return out
+    return self._download(self._lib.gc_download_stash)
 
   def rollout_plan(self, kind, src, sidx, a, b, n_forcing: int):
     """Per-channel context-update plan (gc_rollout_plan; kinds documented in gencast_hip.h)."""
-    kind = np.ascontiguousarray(kind, dtype=np.int32)
-    src = np.ascontiguousarray(src, dtype=np.int32)
-    sidx = np.ascontiguousarray(sidx, dtype=np.int32)
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    b = np.ascontiguousarray(b, dtype=np.float32)
+    kind, src, sidx, a, b = _i32(kind), _i32(src), _i32(sidx), _f32(a), _f32(b)
     for arr in (kind, src, sidx, a, b):
       if arr.shape != (self.cfg.c_in,):
         raise ValueError(f"plan arrays must have shape ({self.cfg.c_in},)")
@@ -452,16 +510,14 @@ class NativeDenoiser:
     if forcings is None:
       self._check(self._lib.gc_rollout_advance(self._h, None))
       return
-    forcings = np.ascontiguousarray(forcings, dtype=np.float32)
+    forcings = _f32(forcings)
     want = (self.num_grid_nodes, self.cfg.batch, getattr(self, "_n_forcing", -1))
     if forcings.shape != want:
       raise ValueError(f"forcings must have shape {want}")
     self._check(self._lib.gc_rollout_advance(self._h, _ptr(forcings, _f32p)))
 
   def download_cond(self) -> np.ndarray:
-    out = np.empty((self.num_grid_nodes, self.cfg.batch, self.cfg.c_in), dtype=np.float32)
-    self._check(self._lib.gc_download_cond(self._h, _ptr(out, _f32p)))
-    return out
+    return self._download(self._lib.gc_download_cond, shape=self._shape_in())
 
   def sync(self):
     self._check(self._lib.gc_sync(self._h))
@@ -505,9 +561,7 @@ class NativeDenoiser:
     self._check(self._lib.gc_noise_draw(self._h))
 
   def download_noise(self) -> np.ndarray:
-    out = np.empty(self._shape_out(), dtype=np.float32)
-    self._check(self._lib.gc_download_noise(self._h, _ptr(out, _f32p)))
-    return out
+    return self._download(self._lib.gc_download_noise)
 
   def set_churn(self, rates, noise_level_inflation_factor: float = 1.0) -> None:
     """Per-step churn rates for the following sample calls (None / all zero: off)."""
@@ -535,8 +589,7 @@ class NativeDenoiser:
 
   def _need_loss_groups(self) -> int:
     """The result buffers are sized by the group count: the weights must have gone through `loss_set_weights`."""
-    if not self._loss_groups:
-      raise GencastHipError("libgencast_hip error 4: no loss weights (loss_set_weights has not been called on this object)")
+    _need(self._loss_groups, "loss weights", "loss_set_weights")
     return self._loss_groups
 
   def upload_targets(self, targets) -> None:
@@ -561,9 +614,7 @@ class NativeDenoiser:
 
   def download_denoised(self) -> np.ndarray:
     """The preconditioned prediction D of the last loss evaluation (gc_download_denoised)."""
-    out = np.empty(self._shape_out(), dtype=np.float32)
-    self._check(self._lib.gc_download_denoised(self._h, _ptr(out, _f32p)))
-    return out
+    return self._download(self._lib.gc_download_denoised)
 
   def loss(self, cond_feats, targets, noise, sigma, want_denoised: bool = False):
     """One evaluation from host arrays (gc_loss) -> (loss [B], per_group [B, n_groups][, D [G, B, c_out]])."""
@@ -577,9 +628,9 @@ class NativeDenoiser:
     ng = self._need_loss_groups()
     loss = np.empty((self.cfg.batch,), dtype=np.float32)
     per_group = np.empty((self.cfg.batch, ng), dtype=np.float32)
-    den = np.empty(self._shape_out(), dtype=np.float32) if want_denoised else None
+    den = self._field() if want_denoised else None
     self._check(self._lib.gc_loss(self._h, _ptr(c, _f32p), _ptr(t, _f32p), _ptr(z, _f32p), _ptr(sg, _f32p),
-                                  _ptr(loss, _f32p), _ptr(per_group, _f32p), None if den is None else _ptr(den, _f32p)))
+                                  _ptr(loss, _f32p), _ptr(per_group, _f32p), _opt(den, _f32p)))
     return (loss, per_group, den) if want_denoised else (loss, per_group)
 
   # -- ensemble verification (scored on the device) -------------------------------------------------
@@ -596,7 +647,7 @@ class NativeDenoiser:
 
   def ens_push(self, slot: int, src: Optional["NativeDenoiser"] = None) -> None:
     """Slot <- the last sample of `src` (None: of this handle), device to device (gc_ens_push)."""
-    self._check(self._lib.gc_ens_push(self._h, int(slot), None if src is None else src._h))  # pylint: disable=protected-access
+    self._check(self._lib.gc_ens_push(self._h, int(slot), _handle_of(src)))
 
   def ens_push_host(self, slot: int, field) -> None:
     x = _f32(field)
@@ -607,25 +658,17 @@ class NativeDenoiser:
   def ens_score(self, truth=None, want_fields: bool = False):
     """-> (sums [B, c_out, 6] float64, rank_hist [B, c_out, M + 1] uint64): the raw, additive sums of gc_ens_score
     (`verification.EnsembleScores` derives the scores).  `truth` [G, B, c_out], or None = the truth uploaded last."""
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
-    t = None
-    if truth is not None:
-      t = _f32(truth)
-      if t.shape != self._shape_out():
-        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    self._need_store()
+    t = self._truth_arg(truth)
     B, C = self.cfg.batch, self.cfg.c_out
     sums = np.empty((6, B, C), dtype=np.float64)
     hist = np.empty((B, C, self._ens_members + 1), dtype=np.uint64)
-    self._check(self._lib.gc_ens_score(self._h, None if t is None else _ptr(t, _f32p), int(bool(want_fields)),
-                                       _ptr(sums, ctypes.POINTER(ctypes.c_double)),
-                                       _ptr(hist, ctypes.POINTER(ctypes.c_uint64))))
+    self._check(self._lib.gc_ens_score(self._h, _opt(t, _f32p), int(bool(want_fields)), _ptr(sums, _f64p), _ptr(hist, _u64p)))
     return np.ascontiguousarray(np.moveaxis(sums, 0, -1)), hist
 
   def ens_download_fields(self):
     """(mean, variance) [G, B, c_out] of the last `ens_score(want_fields=True)` (gc_ens_download_fields)."""
-    mean = np.empty(self._shape_out(), dtype=np.float32)
-    var = np.empty(self._shape_out(), dtype=np.float32)
+    mean, var = self._field(), self._field()
     self._check(self._lib.gc_ens_download_fields(self._h, _ptr(mean, _f32p), _ptr(var, _f32p)))
     return mean, var
 
@@ -635,62 +678,44 @@ class NativeDenoiser:
     t = _i32(state_src)
     if t.shape != (self.cfg.c_out,):
       raise ValueError(f"state_src must have shape ({self.cfg.c_out},)")
-    self._check(self._lib.gc_ens_push_state(self._h, int(slot), None if src is None else src._h, _ptr(t, _i32p)))  # pylint: disable=protected-access
+    self._check(self._lib.gc_ens_push_state(self._h, int(slot), _handle_of(src), _ptr(t, _i32p)))
 
   def ens_download_member(self, slot: int) -> np.ndarray:
     """One stored member [G, B, c_out] (gc_ens_download_member)."""
-    out = np.empty(self._shape_out(), dtype=np.float32)
-    self._check(self._lib.gc_ens_download_member(self._h, int(slot), _ptr(out, _f32p)))
-    return out
+    return self._download(self._lib.gc_ens_download_member, int(slot))
 
   # -- ensemble event verification (exceedance tables formed on the device) ---------------------------
   def ens_event_set(self, thresholds, directions, node_weight_q) -> None:
     """`thresholds` [T, G, B, c_out] float32 (T in 1..8; NaN = not evaluated there), `directions` [T] (> 0: the event is
     `value > threshold`, < 0: `value < threshold`), `node_weight_q` [G] uint32 (`verification.quantize_node_weights`):
     gc_ens_event_set; needs `set_graph` only and survives `ens_reserve`."""
-    thr = _f32(thresholds)
-    if thr.ndim != 4 or thr.shape[1:] != self._shape_out():
-      raise ValueError(f"thresholds must be [T, {', '.join(str(n) for n in self._shape_out())}], got {thr.shape}")
-    d = _i32(directions)
-    if d.shape != (thr.shape[0],):
-      raise ValueError(f"directions must have shape ({thr.shape[0]},)")
-    w = np.asarray(node_weight_q)
-    if w.shape != (self.num_grid_nodes,) or w.dtype.kind not in "ui" or (w.size and (w.min() < 0 or w.max() > 0xFFFFFFFF)):
-      raise ValueError(f"node_weight_q must be unsigned 32-bit integers of shape ({self.num_grid_nodes},)")
-    w = np.ascontiguousarray(w, dtype=np.uint32)
-    self._check(self._lib.gc_ens_event_set(self._h, thr.shape[0], _ptr(thr, _f32p), _ptr(d, _i32p),
-                                           _ptr(w, ctypes.POINTER(ctypes.c_uint32))))
+    thr = self._thresholds_arg(thresholds)
+    d = _directions(directions, thr.shape[0])
+    w = self._weights_q_arg(node_weight_q)
+    self._check(self._lib.gc_ens_event_set(self._h, thr.shape[0], _ptr(thr, _f32p), _ptr(d, _i32p), _ptr(w, _u32p)))
     self._event_thresholds = int(thr.shape[0])
 
   def ens_event_score(self, truth=None):
     """-> (weighted [T, B, c_out, 2, M + 1] uint64, counts (same shape), invalid [T] uint64): the integer tables of
     gc_ens_event_score over the member store (`verification.EventScores` derives the scores).  `truth` [G, B, c_out], or
     None = the truth uploaded last (shared with `ens_score` / `ens_spectrum`)."""
-    if not self._event_thresholds:
-      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_event_set has not been called on this object)")
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
-    t = None
-    if truth is not None:
-      t = _f32(truth)
-      if t.shape != self._shape_out():
-        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    _need(self._event_thresholds, "thresholds", "ens_event_set")
+    self._need_store()
+    t = self._truth_arg(truth)
     T, B, C = self._event_thresholds, self.cfg.batch, self.cfg.c_out
-    u64 = ctypes.POINTER(ctypes.c_uint64)
     weighted = np.empty((T, B, C, 2, self._ens_members + 1), dtype=np.uint64)
     counts = np.empty_like(weighted)
     invalid = np.empty(T, dtype=np.uint64)
-    self._check(self._lib.gc_ens_event_score(self._h, None if t is None else _ptr(t, _f32p), _ptr(weighted, u64),
-                                             _ptr(counts, u64), _ptr(invalid, u64)))
+    self._check(self._lib.gc_ens_event_score(self._h, _opt(t, _f32p), _ptr(weighted, _u64p), _ptr(counts, _u64p),
+                                             _ptr(invalid, _u64p)))
     return weighted, counts, invalid
 
   def ens_event_codes(self, t: int) -> np.ndarray:
     """uint8 [G, B, c_out] of threshold `t` from the last `ens_event_score`: k | (o << 7), 255 where the point did not
     count (gc_ens_event_download; `verification.event_probability` decodes)."""
-    if not self._event_thresholds:
-      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_event_set has not been called on this object)")
-    code = np.empty(self._shape_out(), dtype=np.uint8)
-    self._check(self._lib.gc_ens_event_download(self._h, int(t), _ptr(code, ctypes.POINTER(ctypes.c_uint8))))
+    _need(self._event_thresholds, "thresholds", "ens_event_set")
+    code = self._field(np.uint8)
+    self._check(self._lib.gc_ens_event_download(self._h, int(t), _ptr(code, _u8p)))
     return code
 
   # -- fractions skill score (neighbourhood fractions of the event codes, S scales from one pass) -------
@@ -711,41 +736,34 @@ class NativeDenoiser:
       raise ValueError(f"n_lat * n_lon = {n_lat} * {n_lon} must equal the number of grid nodes {self.num_grid_nodes}")
     if np.any(rl < 0):
       raise ValueError("r_lat must be >= 0")
-    if np.any((ro < 0) | (ro > (n_lon - 1) // 2)):
-      raise ValueError(f"r_lon must lie in 0 .. {(n_lon - 1) // 2}")
+    _check_r_lon(ro, n_lon)
     w = np.asarray(row_wq)
     if w.shape != (n_lat,) or w.dtype.kind not in "ui" or np.any(w < 1) or np.any(w > 2 ** 24 - 1):
       raise ValueError(f"row_wq must be integers in 1 .. 2^24 - 1 of shape ({n_lat},)")
     w = np.ascontiguousarray(w, dtype=np.uint32)
-    self._check(self._lib.gc_ens_fss_set(self._h, rl.shape[0], n_lat, n_lon, _ptr(rl, _i32p), _ptr(ro, _i32p),
-                                         _ptr(w, ctypes.POINTER(ctypes.c_uint32))))
+    self._check(self._lib.gc_ens_fss_set(self._h, rl.shape[0], n_lat, n_lon, _ptr(rl, _i32p), _ptr(ro, _i32p), _ptr(w, _u32p)))
     self._fss_scales = int(rl.shape[0])
 
   def ens_fss_score(self) -> np.ndarray:
     """-> sums [T, S, B, c_out, 4] float64 of gc_ens_fss_score: sum w (P - O)^2, sum w (P^2 + O^2), sum w P, sum w O over the
     counted centres, from the event codes the last `ens_event_score` left on the device (`verification.FractionsScores`
     derives the scores)."""
-    if not self._fss_scales:
-      raise GencastHipError("libgencast_hip error 4: no plan (ens_fss_set has not been called on this object)")
-    if not self._event_thresholds:
-      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_event_set has not been called on this object)")
+    _need(self._fss_scales, "plan", "ens_fss_set")
+    _need(self._event_thresholds, "thresholds", "ens_event_set")
     sums = np.empty((self._event_thresholds, self._fss_scales, self.cfg.batch, self.cfg.c_out, 4), dtype=np.float64)
-    self._check(self._lib.gc_ens_fss_score(self._h, _ptr(sums, ctypes.POINTER(ctypes.c_double))))
+    self._check(self._lib.gc_ens_fss_score(self._h, _ptr(sums, _f64p)))
     return sums
 
   def ens_fss_fields(self, t: int, s: int):
     """-> (prob, obs), float32 [G, B, c_out] each: the neighbourhood ensemble probability P and the observed fraction O of
     threshold `t` at scale `s`, NaN where the point did not count (gc_ens_fss_fields)."""
-    if not self._fss_scales:
-      raise GencastHipError("libgencast_hip error 4: no plan (ens_fss_set has not been called on this object)")
-    if not self._event_thresholds:
-      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_event_set has not been called on this object)")
+    _need(self._fss_scales, "plan", "ens_fss_set")
+    _need(self._event_thresholds, "thresholds", "ens_event_set")
     if not 0 <= int(t) < self._event_thresholds:
       raise ValueError(f"t must lie in [0, {self._event_thresholds})")
     if not 0 <= int(s) < self._fss_scales:
       raise ValueError(f"s must lie in [0, {self._fss_scales})")
-    prob = np.empty(self._shape_out(), dtype=np.float32)
-    obs = np.empty(self._shape_out(), dtype=np.float32)
+    prob, obs = self._field(), self._field()
     self._check(self._lib.gc_ens_fss_fields(self._h, int(t), int(s), _ptr(prob, _f32p), _ptr(obs, _f32p)))
     return prob, obs
 
@@ -784,7 +802,7 @@ class NativeDenoiser:
     lists = (o == 2) | (o == 3)
     if np.any(~lists & ((a < 0) | (a >= c_src))) or np.any(~lists & (o != 0) & ((b < 0) | (b >= c_src))):
       raise ValueError(f"a source channel lies outside [0, {int(c_src)})")
-    aff = np.ascontiguousarray(affine, dtype=np.float64)
+    aff = _f64(affine)
     if aff.shape != (c_d, 4):
       raise ValueError(f"affine must have shape ({c_d}, 4)")
     if int(pool) not in (0, 1, 2, 3):
@@ -793,31 +811,29 @@ class NativeDenoiser:
       raise ValueError(f"n_lat * n_lon must equal the number of grid nodes ({self.num_grid_nodes})")
     if int(r_lat) < 0:
       raise ValueError("r_lat must be >= 0")
-    dp = ctypes.POINTER(ctypes.c_double)
     r = w = None
     if int(pool) != 0:
       if r_lon is None or row_weight is None:
         raise ValueError("a pooled plan needs r_lon and row_weight")
       r = _i32(r_lon)
-      w = np.ascontiguousarray(row_weight, dtype=np.float64)
+      w = _f64(row_weight)
       if r.shape != (int(n_lat),) or w.shape != (int(n_lat),):
         raise ValueError(f"r_lon and row_weight must have shape ({int(n_lat)},)")
-      if np.any((r < 0) | (r > (int(n_lon) - 1) // 2)):
-        raise ValueError(f"r_lon must lie in 0 .. {(int(n_lon) - 1) // 2}")
+      _check_r_lon(r, int(n_lon))
       if not np.all(np.isfinite(w) & (w > 0.0)):
         raise ValueError("row_weight must be finite and > 0")
+    plain = (self._h, int(c_src), _ptr(o, _i32p), _ptr(a, _i32p), _ptr(b, _i32p), _ptr(aff, _f64p), int(pool), int(n_lat),
+             int(n_lon), int(r_lat), _opt(r, _i32p), _opt(w, _f64p))         # (the expression form takes these first)
     if not expr:
-      self._check(self._lib.gc_ens_derive_set(self._h, int(c_src), _ptr(o, _i32p), _ptr(a, _i32p), _ptr(b, _i32p), _ptr(aff, dp),
-                                              int(pool), int(n_lat), int(n_lon), int(r_lat),
-                                              None if r is None else _ptr(r, _i32p), None if w is None else _ptr(w, dp)))
+      self._check(self._lib.gc_ens_derive_set(*plain))
       self._derive_c_src = int(c_src)
       return
     if scale is None or loc is None:
       raise ValueError("scale and loc go together")
-    sc, lo = (np.ascontiguousarray(v, dtype=np.float64) for v in (scale, loc))
+    sc, lo = _f64(scale), _f64(loc)
     if sc.shape != (int(c_src),) or lo.shape != (int(c_src),) or not (np.isfinite(sc).all() and np.isfinite(lo).all()):
       raise ValueError(f"scale and loc must be finite and have shape ({int(c_src)},)")
-    tc = np.ascontiguousarray(np.zeros(0) if term_coef is None else term_coef, dtype=np.float64).reshape(-1)
+    tc = _f64(np.zeros(0) if term_coef is None else term_coef).reshape(-1)
     ta, tb = (_i32(np.zeros(0, np.int32) if v is None else v).reshape(-1) for v in (term_a, term_b))
     if not tc.shape == ta.shape == tb.shape:
       raise ValueError("term_coef, term_a and term_b must have one entry per term")
@@ -841,15 +857,12 @@ class NativeDenoiser:
         raise ValueError("vorticity and divergence need coslat, inv_rcos, inv_dphi, inv_2dlam and pole_row")
       if int(n_lon) < 3 or int(n_lat) < 2:
         raise ValueError("vorticity and divergence need n_lon >= 3 and n_lat >= 2")
-      rows = [np.ascontiguousarray(v, dtype=np.float64) for v in (coslat, inv_rcos, inv_dphi)] + [_i32(pole_row)]
+      rows = [_f64(coslat), _f64(inv_rcos), _f64(inv_dphi), _i32(pole_row)]
       if any(v.shape != (int(n_lat),) for v in rows):
         raise ValueError(f"coslat, inv_rcos, inv_dphi and pole_row must have shape ({int(n_lat)},)")
     self._check(self._lib.gc_ens_derive_set_expr(
-        self._h, int(c_src), _ptr(o, _i32p), _ptr(a, _i32p), _ptr(b, _i32p), _ptr(aff, dp), int(pool), int(n_lat), int(n_lon),
-        int(r_lat), None if r is None else _ptr(r, _i32p), None if w is None else _ptr(w, dp), _ptr(sc, dp), _ptr(lo, dp),
-        None if ts is None else _ptr(ts, _i32p), int(tc.size), _ptr(tc, dp), _ptr(ta, _i32p), _ptr(tb, _i32p),
-        *(None if v is None else _ptr(v, dp) for v in rows[:3]), 0.0 if inv_2dlam is None else float(inv_2dlam),
-        None if rows[3] is None else _ptr(rows[3], _i32p)))
+        *plain, _ptr(sc, _f64p), _ptr(lo, _f64p), _opt(ts, _i32p), int(tc.size), _ptr(tc, _f64p), _ptr(ta, _i32p), _ptr(tb, _i32p),
+        *(_opt(v, _f64p) for v in rows[:3]), 0.0 if inv_2dlam is None else float(inv_2dlam), _opt(rows[3], _i32p)))
     self._derive_c_src = int(c_src)
 
   def ens_derive(self, src: "NativeDenoiser", truth=None) -> None:
@@ -857,17 +870,10 @@ class NativeDenoiser:
     the derived truth of `src` (gc_ens_derive): afterwards `ens_score(None)`, `ens_event_score(None)`, `ens_spectrum(None)`
     and `ens_download_member` of THIS handle see the derived fields.  `truth` [G, B, c_src] is uploaded into `src`, or
     None = the truth `src` holds."""
-    if not self._derive_c_src:
-      raise GencastHipError("libgencast_hip error 4: no plan (ens_derive_set has not been called on this object)")
-    if not isinstance(src, NativeDenoiser) or src is self:
-      raise ValueError("src must be another NativeDenoiser")
-    t = None
-    if truth is not None:
-      t = _f32(truth)
-      want = (self.num_grid_nodes, self.cfg.batch, self._derive_c_src)
-      if t.shape != want:
-        raise ValueError(f"truth must be {want}, got {t.shape}")
-    self._check(self._lib.gc_ens_derive(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
+    _need(self._derive_c_src, "plan", "ens_derive_set")
+    self._check_src(src)
+    t = self._truth_arg(truth, self._derive_c_src)
+    self._check(self._lib.gc_ens_derive(self._h, _handle_of(src), _opt(t, _f32p)))
 
   # -- spectral band views (band-limited members and truth, into this handle's member store) -----------------
   def ens_band_set(self, c_src: int, response, complement, src_channel, band, legendre_synthesis, cos_s, sin_s) -> None:
@@ -877,12 +883,11 @@ class NativeDenoiser:
     synth(w a); derived channel j is band `band[j]` of source channel `src_channel[j]`.  `legendre_synthesis` [lmax, n_lat,
     lmax], `cos_s`, `sin_s` [lmax, n_lon]: `spectra.SphericalAnalysis.synthesis_tables()`.  `verification.BandSpec` builds
     these arrays from variable names."""
-    if not self._spec_lmax:
-      raise GencastHipError("libgencast_hip error 4: no analysis tables (spec_set_tables has not been called on this object)")
+    _need(self._spec_lmax, "analysis tables", "spec_set_tables")
     c_d, L = self.cfg.c_out, self._spec_lmax
     if int(c_src) < 1:
       raise ValueError("c_src must be positive")
-    w = np.ascontiguousarray(response, dtype=np.float64)
+    w = _f64(response)
     if w.ndim != 2 or not 1 <= w.shape[0] <= 8 or w.shape[1] != L:
       raise ValueError(f"response must be [K, {L}] with K in 1..8, got {w.shape}")
     if not np.isfinite(w).all():
@@ -902,9 +907,8 @@ class NativeDenoiser:
       raise ValueError(f"legendre_synthesis must be [{L}, n_lat, {L}] with n_lat * n_lon = {self.num_grid_nodes}, got {leg.shape}")
     if cs.shape != (L, cs.shape[-1]) or sn.shape != cs.shape:
       raise ValueError(f"cos_s and sin_s must be [{L}, n_lon], got {cs.shape} and {sn.shape}")
-    self._check(self._lib.gc_ens_band_set(self._h, int(c_src), int(w.shape[0]), _ptr(w, ctypes.POINTER(ctypes.c_double)),
-                                          _ptr(comp, _i32p), _ptr(ch, _i32p), _ptr(bd, _i32p), _ptr(leg, _f32p), _ptr(cs, _f32p),
-                                          _ptr(sn, _f32p)))
+    self._check(self._lib.gc_ens_band_set(self._h, int(c_src), int(w.shape[0]), _ptr(w, _f64p), _ptr(comp, _i32p), _ptr(ch, _i32p),
+                                          _ptr(bd, _i32p), _ptr(leg, _f32p), _ptr(cs, _f32p), _ptr(sn, _f32p)))
     self._band_c_src = int(c_src)
 
   def ens_band(self, src: "NativeDenoiser", truth=None) -> None:
@@ -913,17 +917,10 @@ class NativeDenoiser:
     `truth` [G, B, c_src] is uploaded into `src`, or None = the truth `src` holds.  A band is linear: a view of `x s + l` is
     `s view(x) + l w[0]` (`l (1 - w[0])` with complement); with float32 tables a constant comes back within a few 1e-7
     relative."""
-    if not self._band_c_src:
-      raise GencastHipError("libgencast_hip error 4: no plan (ens_band_set has not been called on this object)")
-    if not isinstance(src, NativeDenoiser) or src is self:
-      raise ValueError("src must be another NativeDenoiser")
-    t = None
-    if truth is not None:
-      t = _f32(truth)
-      want = (self.num_grid_nodes, self.cfg.batch, self._band_c_src)
-      if t.shape != want:
-        raise ValueError(f"truth must be {want}, got {t.shape}")
-    self._check(self._lib.gc_ens_band(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
+    _need(self._band_c_src, "plan", "ens_band_set")
+    self._check_src(src)
+    t = self._truth_arg(truth, self._band_c_src)
+    self._check(self._lib.gc_ens_band(self._h, _handle_of(src), _opt(t, _f32p)))
 
   # -- ensemble feature detection (centres and strike fields, into this handle's member store) -------------
   def ens_feature_set(self, c_src: int, channel, direction, use_threshold, threshold, n_lat: int, n_lon: int, r_lat, r_lon,
@@ -943,7 +940,7 @@ class NativeDenoiser:
     n_lat, n_lon = int(n_lat), int(n_lon)
     ch, di, ut = _i32(channel), _i32(direction), _i32(use_threshold)
     rl, gl, sl = _i32(r_lat), _i32(ring_lat), _i32(strike_lat)
-    th, de = _f32(threshold), np.ascontiguousarray(depth, dtype=np.float64)
+    th, de = _f32(threshold), _f64(depth)
     for name, a in (("channel", ch), ("direction", di), ("use_threshold", ut), ("threshold", th), ("r_lat", rl), ("ring_lat", gl),
                     ("depth", de), ("strike_lat", sl)):
       if a.shape != (D,):
@@ -963,15 +960,13 @@ class NativeDenoiser:
       a = _i32(a)
       if a.shape != (D, n_lat):
         raise ValueError(f"{name} must have shape ({D}, {n_lat}), got {a.shape}")
-      if np.any((a < 0) | (a > (n_lon - 1) // 2)):
-        raise ValueError(f"{name} must lie in 0 .. {(n_lon - 1) // 2}")
+      _check_r_lon(a, n_lon, name)
       lons.append(a)
     if isinstance(max_centres, bool) or int(max_centres) != max_centres or not 1 <= int(max_centres) <= 1024:
       raise ValueError(f"max_centres must be an integer in 1 .. 1024, got {max_centres!r}")
     self._check(self._lib.gc_ens_feature_set(self._h, int(c_src), D, _ptr(ch, _i32p), _ptr(di, _i32p), _ptr(ut, _i32p), _ptr(th, _f32p),
                                              n_lat, n_lon, _ptr(rl, _i32p), _ptr(lons[0], _i32p), _ptr(gl, _i32p), _ptr(lons[1], _i32p),
-                                             _ptr(de, ctypes.POINTER(ctypes.c_double)), _ptr(sl, _i32p), _ptr(lons[2], _i32p),
-                                             int(max_centres)))
+                                             _ptr(de, _f64p), _ptr(sl, _i32p), _ptr(lons[2], _i32p), int(max_centres)))
     self._feature_c_src, self._feature_max, self._feature_members = int(c_src), int(max_centres), -1
 
   def ens_feature(self, src: "NativeDenoiser", truth=None) -> None:
@@ -979,17 +974,10 @@ class NativeDenoiser:
     this handle's truth <- those of the truth of `src` (gc_ens_feature): afterwards every scorer of THIS handle sees the
     0 / 1 fields (truth None) and `ens_feature_centres` returns the lists.  `truth` [G, B, c_src] is uploaded into `src`, or
     None = the truth `src` holds."""
-    if not self._feature_c_src:
-      raise GencastHipError("libgencast_hip error 4: no plan (ens_feature_set has not been called on this object)")
-    if not isinstance(src, NativeDenoiser) or src is self:
-      raise ValueError("src must be another NativeDenoiser")
-    t = None
-    if truth is not None:
-      t = _f32(truth)
-      want = (self.num_grid_nodes, self.cfg.batch, self._feature_c_src)
-      if t.shape != want:
-        raise ValueError(f"truth must be {want}, got {t.shape}")
-    self._check(self._lib.gc_ens_feature(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
+    _need(self._feature_c_src, "plan", "ens_feature_set")
+    self._check_src(src)
+    t = self._truth_arg(truth, self._feature_c_src)
+    self._check(self._lib.gc_ens_feature(self._h, _handle_of(src), _opt(t, _f32p)))
     self._feature_members = self._ens_members
 
   def ens_feature_centres(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -997,8 +985,7 @@ class NativeDenoiser:
     last `ens_feature` (gc_ens_feature_centres): field M is the truth; `count` is the true number of centres, of which the
     first min(count, max_centres) in ascending node index are listed (`value`: the source value, the same bits); the entries
     behind them read node -1, value 0."""
-    if self._feature_members < 0:
-      raise GencastHipError("libgencast_hip error 4: no centre lists (ens_feature has not run since ens_feature_set)")
+    _need(self._feature_members >= 0, "centre lists", why="ens_feature has not run since ens_feature_set")
     shape = (self._feature_members + 1, self.cfg.batch, self.cfg.c_out)
     count = np.empty(shape, np.int32)
     node = np.empty(shape + (self._feature_max,), np.int32)
@@ -1010,20 +997,17 @@ class NativeDenoiser:
   def ens_order_set(self, probs) -> None:
     """`probs` [Q] in [0, 1], Q in 0..8: the quantile fields `ens_order_score` / `ens_order_fields` leave on the device
     (gc_ens_order_set; needs `set_graph` only and survives `ens_reserve`).  Q = 0: the bin sums only."""
-    p = np.ascontiguousarray([] if probs is None else probs, dtype=np.float64)
+    p = _f64([] if probs is None else probs)
     if p.ndim != 1 or p.shape[0] > 8:
       raise ValueError(f"probs must be a sequence of at most 8 probabilities, got shape {p.shape}")
     if not np.all((p >= 0.0) & (p <= 1.0)):                # (NaN fails both comparisons)
       raise ValueError("probs must lie in [0, 1]")
-    self._check(self._lib.gc_ens_order_set(self._h, p.shape[0],
-                                           _ptr(p, ctypes.POINTER(ctypes.c_double)) if p.shape[0] else None))
+    self._check(self._lib.gc_ens_order_set(self._h, p.shape[0], _ptr(p, _f64p) if p.shape[0] else None))
     self._order_quantiles = int(p.shape[0])
 
   def _order_need_set(self) -> int:
-    if self._order_quantiles is None:
-      raise GencastHipError("libgencast_hip error 4: no probabilities (ens_order_set has not been called on this object)")
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    _need(self._order_quantiles is not None, "probabilities", "ens_order_set")
+    self._need_store()
     return self._order_quantiles
 
   def ens_order_score(self, truth=None):
@@ -1032,20 +1016,15 @@ class NativeDenoiser:
     the scores); the Q quantile fields stay on the device (`ens_order_quantile`).  `truth` [G, B, c_out], or None = the
     truth uploaded last (shared with `ens_score`)."""
     Q = self._order_need_set()
-    t = None
-    if truth is not None:
-      t = _f32(truth)
-      if t.shape != self._shape_out():
-        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    t = self._truth_arg(truth)
     B, C, M = self.cfg.batch, self.cfg.c_out, self._ens_members
-    dp, u64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)
     bins = np.empty((B, C, M + 1, 2), dtype=np.float64)
     extra = np.empty((B, C, 3), dtype=np.float64)
     pinball = np.empty((B, C, Q), dtype=np.float64)
     counts = np.empty((B, C, Q + 1), dtype=np.uint64)
     invalid = np.zeros(1, dtype=np.uint64)
-    self._check(self._lib.gc_ens_order_score(self._h, None if t is None else _ptr(t, _f32p), _ptr(bins, dp), _ptr(extra, dp),
-                                             _ptr(pinball, dp) if Q else None, _ptr(counts, u64), _ptr(invalid, u64)))
+    self._check(self._lib.gc_ens_order_score(self._h, _opt(t, _f32p), _ptr(bins, _f64p), _ptr(extra, _f64p),
+                                             _ptr(pinball, _f64p) if Q else None, _ptr(counts, _u64p), _ptr(invalid, _u64p)))
     return bins, extra, pinball, counts, int(invalid[0])
 
   def ens_order_fields(self) -> None:
@@ -1055,11 +1034,8 @@ class NativeDenoiser:
 
   def ens_order_quantile(self, q: int) -> np.ndarray:
     """Quantile field `q` [G, B, c_out] of the last `ens_order_score` / `ens_order_fields` (gc_ens_order_download)."""
-    if self._order_quantiles is None:
-      raise GencastHipError("libgencast_hip error 4: no probabilities (ens_order_set has not been called on this object)")
-    out = np.empty(self._shape_out(), dtype=np.float32)
-    self._check(self._lib.gc_ens_order_download(self._h, int(q), _ptr(out, _f32p)))
-    return out
+    _need(self._order_quantiles is not None, "probabilities", "ens_order_set")
+    return self._download(self._lib.gc_ens_order_download, int(q))
 
   # -- an ensemble against a climatology (two member stores, one pass) -----------------------------------
   def ens_clim_score(self, clim: "NativeDenoiser", truth=None):
@@ -1068,24 +1044,15 @@ class NativeDenoiser:
     handle with the same graph, batch and c_out (`Denoiser.climatology_handle`; filled with `ens_reserve(K)` and
     `ens_push_host`).  `verification.ClimatologyScores` derives ACC, CRPSS and the rest.  `truth` [G, B, c_out], or None =
     the truth uploaded last (shared with `ens_score`)."""
-    if not isinstance(clim, NativeDenoiser):
-      raise TypeError("clim must be a NativeDenoiser")
-    if clim is self:
-      raise ValueError("the climatology must be another handle")
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
-    t = None
-    if truth is not None:
-      t = _f32(truth)
-      if t.shape != self._shape_out():
-        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    self._check_clim(clim)
+    self._need_store()
+    t = self._truth_arg(truth)
     B, C = self.cfg.batch, self.cfg.c_out
     sums = np.empty((B, C, 12), dtype=np.float64)
     counts = np.empty((B, C), dtype=np.uint64)
     invalid = np.zeros(1, dtype=np.uint64)
-    u64 = ctypes.POINTER(ctypes.c_uint64)
-    self._check(self._lib.gc_ens_clim_score(self._h, clim._h, None if t is None else _ptr(t, _f32p),  # pylint: disable=protected-access
-                                            _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(counts, u64), _ptr(invalid, u64)))
+    self._check(self._lib.gc_ens_clim_score(self._h, _handle_of(clim), _opt(t, _f32p), _ptr(sums, _f64p), _ptr(counts, _u64p),
+                                            _ptr(invalid, _u64p)))
     return sums, counts, int(invalid[0])
 
   # -- extreme forecast index (the members ranked in the samples of a climatology handle) ----------------
@@ -1094,34 +1061,23 @@ class NativeDenoiser:
     int and `directions` [T] (> 0: the truth's event is lt(y) >= rank, < 0: le(y) <= rank), T in 0..4; `n_bins` E in 2..32
     equal EFI bins; `node_weight_q` [G] uint32 (`verification.quantize_node_weights`), not needed when T == 0.
     `verification.EfiSpec` builds the ranks from quantiles."""
-    r, d = _i32(ranks).reshape(-1), _i32(directions).reshape(-1)
+    r = _i32(ranks).reshape(-1)
     T = int(r.shape[0])
-    if d.shape != (T,):
-      raise ValueError(f"directions must have shape ({T},)")
+    d = _directions(_i32(directions).reshape(-1), T)
     if isinstance(n_bins, bool) or int(n_bins) != n_bins:
       raise ValueError(f"n_bins must be an integer in 2..32, got {n_bins!r}")
-    w = None
-    if T:
-      w = np.asarray(node_weight_q)
-      if w.shape != (self.num_grid_nodes,) or w.dtype.kind not in "ui" or (w.size and (w.min() < 0 or w.max() > 0xFFFFFFFF)):
-        raise ValueError(f"node_weight_q must be unsigned 32-bit integers of shape ({self.num_grid_nodes},)")
-      w = np.ascontiguousarray(w, dtype=np.uint32)
+    w = self._weights_q_arg(node_weight_q) if T else None
     self._check(self._lib.gc_ens_efi_set(self._h, T, _ptr(r, _i32p) if T else None, _ptr(d, _i32p) if T else None, int(n_bins),
-                                         None if w is None else _ptr(w, ctypes.POINTER(ctypes.c_uint32))))
+                                         _opt(w, _u32p)))
     self._efi_plan = (T, int(n_bins))
 
   def _efi_args(self, clim, table):
-    if not isinstance(clim, NativeDenoiser):
-      raise TypeError("clim must be a NativeDenoiser")
-    if clim is self:
-      raise ValueError("the climatology must be another handle")
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    """-> `table` as float64 [K + 1] for the K samples in the store of `clim`, after the guards the two EFI calls share."""
+    self._check_clim(clim)
+    self._need_store()
     K = clim._ens_members  # pylint: disable=protected-access
-    if not K:
-      raise GencastHipError("libgencast_hip error 4: no member store on the climatology handle (ens_reserve has not been "
-                            "called on that object)")
-    a = np.ascontiguousarray(table, dtype=np.float64)
+    _need(K, "member store on the climatology handle", why="ens_reserve has not been called on that object")
+    a = _f64(table)
     if a.shape != (K + 1,):
       raise ValueError(f"table must have shape ({K + 1},) for the {K} samples of the climatology handle, got {a.shape}")
     return a
@@ -1132,49 +1088,36 @@ class NativeDenoiser:
     (`Denoiser.climatology_handle`); `table` [K + 1] float64 is `verification.efi_table(K)`.  The EFI and the observed index
     stay on the device (`ens_efi_field`).  `truth` [G, B, c_out], or None = the truth uploaded last."""
     a = self._efi_args(clim, table)
-    if self._efi_plan is None:
-      raise GencastHipError("libgencast_hip error 4: no events and bins (ens_efi_set has not been called on this object)")
+    _need(self._efi_plan is not None, "events and bins", "ens_efi_set")
     t = self._truth_arg(truth)
     (T, E), B, C = self._efi_plan, self.cfg.batch, self.cfg.c_out
-    dp, u64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)
     sums = np.empty((B, C, 6), dtype=np.float64)
     weighted = np.zeros((T, B, C, 2, E), dtype=np.uint64)
     counts = np.zeros_like(weighted)
     invalid = np.zeros(1, dtype=np.uint64)
-    self._check(self._lib.gc_ens_efi_score(self._h, clim._h, _ptr(a, dp), None if t is None else _ptr(t, _f32p),  # pylint: disable=protected-access
-                                           _ptr(sums, dp), _ptr(weighted, u64) if T else None, _ptr(counts, u64) if T else None,
-                                           _ptr(invalid, u64)))
+    self._check(self._lib.gc_ens_efi_score(self._h, _handle_of(clim), _ptr(a, _f64p), _opt(t, _f32p), _ptr(sums, _f64p),
+                                           _ptr(weighted, _u64p) if T else None, _ptr(counts, _u64p) if T else None,
+                                           _ptr(invalid, _u64p)))
     return sums, weighted, counts, int(invalid[0])
 
   def ens_efi_fields(self, clim: "NativeDenoiser", table) -> None:
     """The EFI field of the member store against the samples of `clim`, without truth, weights or events
     (gc_ens_efi_fields); `ens_efi_field(0)` downloads it."""
     a = self._efi_args(clim, table)
-    self._check(self._lib.gc_ens_efi_fields(self._h, clim._h, _ptr(a, ctypes.POINTER(ctypes.c_double))))  # pylint: disable=protected-access
+    self._check(self._lib.gc_ens_efi_fields(self._h, _handle_of(clim), _ptr(a, _f64p)))
 
   def ens_efi_field(self, which: int = 0) -> np.ndarray:
     """Field `which` [G, B, c_out] float32 of the last `ens_efi_score` / `ens_efi_fields`: 0 the EFI, 1 the observed index
     (gc_ens_efi_download; the observed index only after `ens_efi_score`)."""
-    out = np.empty(self._shape_out(), dtype=np.float32)
-    self._check(self._lib.gc_ens_efi_download(self._h, int(which), _ptr(out, _f32p)))
-    return out
+    return self._download(self._lib.gc_ens_efi_download, int(which))
 
   # -- multivariate ensemble scores (energy over channel groups, variogram over grid offsets) -----------
-  def _truth_arg(self, truth):
-    if truth is None:
-      return None
-    t = _f32(truth)
-    if t.shape != self._shape_out():
-      raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
-    return t
-
   def ens_energy_set(self, n_groups: int, group, scale) -> None:
     """The plan of `ens_energy_score` (gc_ens_energy_set; needs `set_graph` only and survives `ens_reserve`): `group` [c_out]
     int, the group 0 .. n_groups - 1 of every channel or -1 for none; `scale` [c_out] float64, a[c] > 0 of the grouped
     channels.  `verification.EnergySpec` builds these arguments."""
     K = int(n_groups)
-    g = np.ascontiguousarray(group, dtype=np.int32)
-    a = np.ascontiguousarray(scale, dtype=np.float64)
+    g, a = _i32(group), _f64(scale)
     C = self.cfg.c_out
     if g.shape != (C,) or a.shape != (C,):
       raise ValueError(f"group and scale must be [{C}], got {g.shape} and {a.shape}")
@@ -1184,31 +1127,27 @@ class NativeDenoiser:
       raise ValueError("group must map every channel to -1 or 0 .. n_groups - 1 and leave no group empty")
     if not np.all(np.isfinite(a[g >= 0]) & (a[g >= 0] > 0.0)):
       raise ValueError("scale must be finite and > 0 for grouped channels")
-    self._check(self._lib.gc_ens_energy_set(self._h, K, _ptr(g, _i32p), _ptr(a, ctypes.POINTER(ctypes.c_double))))
+    self._check(self._lib.gc_ens_energy_set(self._h, K, _ptr(g, _i32p), _ptr(a, _f64p)))
     self._energy_groups = K
 
   def ens_energy_score(self, truth=None):
     """-> (d2 [B, K, P] float64, s0 [B, K] float64, invalid int): the raw sums of gc_ens_energy_score over the member store,
     P = M (M + 1) / 2 pairs (i < j, index j (j - 1) / 2 + i, slot M the truth); `verification.EnergyScores` derives the
     scores.  `truth` [G, B, c_out], or None = the truth uploaded last (shared with `ens_score`)."""
-    if self._energy_groups is None:
-      raise GencastHipError("libgencast_hip error 4: no plan (ens_energy_set has not been called on this object)")
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    _need(self._energy_groups is not None, "plan", "ens_energy_set")
+    self._need_store()
     t = self._truth_arg(truth)
     B, K, M = self.cfg.batch, self._energy_groups, self._ens_members
-    dp, u64 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)
     d2 = np.empty((B, K, M * (M + 1) // 2), dtype=np.float64)
     s0 = np.empty((B, K), dtype=np.float64)
     invalid = np.zeros(1, dtype=np.uint64)
-    self._check(self._lib.gc_ens_energy_score(self._h, None if t is None else _ptr(t, _f32p), _ptr(d2, dp), _ptr(s0, dp),
-                                              _ptr(invalid, u64)))
+    self._check(self._lib.gc_ens_energy_score(self._h, _opt(t, _f32p), _ptr(d2, _f64p), _ptr(s0, _f64p), _ptr(invalid, _u64p)))
     return d2, s0, int(invalid[0])
 
   def ens_variogram_set(self, n_lat: int, n_lon: int, offsets, p: float) -> None:
     """The plan of `ens_variogram_score` (gc_ens_variogram_set; needs `set_graph` only and survives `ens_reserve`): the grid
     `n_lat` x `n_lon` (node = i n_lon + j), `offsets` [O, 2] int (di, dj), O in 1..16, and the order `p` in {0.5, 1, 2}."""
-    o = np.ascontiguousarray(offsets, dtype=np.int32)
+    o = _i32(offsets)
     if o.ndim != 2 or o.shape[1] != 2 or not 1 <= o.shape[0] <= 16:
       raise ValueError(f"offsets must be [O, 2] with O in 1..16, got {o.shape}")
     if float(p) not in (0.5, 1.0, 2.0):
@@ -1225,17 +1164,13 @@ class NativeDenoiser:
     """-> (sums [4, B, c_out, O] float64: V0 .. V3, counts [B, c_out, O] uint64): the raw, additive sums of
     gc_ens_variogram_score over the member store; `verification.VariogramScores` derives the scores.  `truth` [G, B, c_out],
     or None = the truth uploaded last (shared with `ens_score`)."""
-    if self._variogram_offsets is None:
-      raise GencastHipError("libgencast_hip error 4: no plan (ens_variogram_set has not been called on this object)")
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    _need(self._variogram_offsets is not None, "plan", "ens_variogram_set")
+    self._need_store()
     t = self._truth_arg(truth)
     B, C, O = self.cfg.batch, self.cfg.c_out, self._variogram_offsets
     sums = np.empty((4, B, C, O), dtype=np.float64)
     counts = np.empty((B, C, O), dtype=np.uint64)
-    self._check(self._lib.gc_ens_variogram_score(self._h, None if t is None else _ptr(t, _f32p),
-                                                 _ptr(sums, ctypes.POINTER(ctypes.c_double)),
-                                                 _ptr(counts, ctypes.POINTER(ctypes.c_uint64))))
+    self._check(self._lib.gc_ens_variogram_score(self._h, _opt(t, _f32p), _ptr(sums, _f64p), _ptr(counts, _u64p)))
     return sums, counts
 
   # -- score maps (the marginal scores per grid point, added up over dates on the device) ----------------
@@ -1243,21 +1178,18 @@ class NativeDenoiser:
     """The plan of the score maps (gc_ens_map_set; needs `set_graph` only, survives `ens_reserve`): `channels` [C'] ascending and
     distinct (None = all c_out), `n_slots` in 1..128 (a slot is a lead time), `n_event_thresholds` in 0..8 (0: no event
     planes).  Allocates and zeroes the accumulators; a repeated call replaces and zeroes them."""
-    if channels is None:
-      n, ptr = self.cfg.c_out, None
-    else:
-      ch = _i32(channels)
-      if ch.ndim != 1 or ch.size < 1:
-        raise ValueError("channels must be a non-empty list of channel indices (or None for all)")
-      n, ptr = int(ch.size), _ptr(ch, _i32p)
-    self._check(self._lib.gc_ens_map_set(self._h, n, ptr, int(n_slots), int(n_event_thresholds)))
+    ch = None if channels is None else _i32(channels)
+    if ch is not None and (ch.ndim != 1 or ch.size < 1):
+      raise ValueError("channels must be a non-empty list of channel indices (or None for all)")
+    n = self.cfg.c_out if ch is None else int(ch.size)
+    self._check(self._lib.gc_ens_map_set(self._h, n, _opt(ch, _i32p), int(n_slots), int(n_event_thresholds)))
     self._map_plan = (n, int(n_slots), int(n_event_thresholds))
 
   def ens_map_accumulate(self, slot: int, truth=None) -> None:
     """Adds the date in the member store into the planes of `slot` (gc_ens_map_accumulate).  `truth` [G, B, c_out], or None =
     the truth uploaded last (shared with `ens_score`)."""
-    t = None if truth is None else self._truth_arg(truth)
-    self._check(self._lib.gc_ens_map_accumulate(self._h, int(slot), None if t is None else _ptr(t, _f32p)))
+    t = self._truth_arg(truth)
+    self._check(self._lib.gc_ens_map_accumulate(self._h, int(slot), _opt(t, _f32p)))
 
   def ens_map_accumulate_events(self, slot: int) -> None:
     """Adds the codes of the last `ens_event_score` into the event planes of `slot` (gc_ens_map_accumulate_events)."""
@@ -1267,18 +1199,17 @@ class NativeDenoiser:
     """-> (sums [6, G, B, C'] float64, counts [3, G, B, C'] uint32, events [T, 5, G, B, C'] uint32 or None, dates [2] int64: field
     and event calls added): the planes of `slot` (gc_ens_map_download; `verification.ScoreMaps` / `EventMaps` derive the
     scores).  `events`: None = where the plan has event planes."""
-    dp, u32 = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32)
     if self._map_plan is None:                   # the library says what is missing, in its order
       self._check(self._lib.gc_ens_map_download(self._h, int(slot), None, None, None, None))
-      raise GencastHipError("libgencast_hip error 4: no map plan (ens_map_set has not been called on this object)")
+      _need(False, "map plan", "ens_map_set")
     (C, _, T), G, B = self._map_plan, self.num_grid_nodes, self.cfg.batch
     want = T > 0 if events is None else bool(events)
     sums = np.empty((6, G, B, C), dtype=np.float64)
     counts = np.empty((3, G, B, C), dtype=np.uint32)
     ev = np.empty((T, 5, G, B, C), dtype=np.uint32) if want else None
     dates = np.zeros(2, dtype=np.int64)
-    self._check(self._lib.gc_ens_map_download(self._h, int(slot), _ptr(sums, dp), _ptr(counts, u32),
-                                              None if ev is None else _ptr(ev, u32), _ptr(dates, ctypes.POINTER(ctypes.c_int64))))
+    self._check(self._lib.gc_ens_map_download(self._h, int(slot), _ptr(sums, _f64p), _ptr(counts, _u32p), _opt(ev, _u32p),
+                                              _ptr(dates, _i64p)))
     return sums, counts, ev, dates
 
   def ens_map_reset(self, slot: int = -1) -> None:
@@ -1290,14 +1221,10 @@ class NativeDenoiser:
     """`thresholds` [T, G, B, c_out] float32 (T in 1..8; NaN = not evaluated there), `directions` [T] (> 0: the upper tail,
     weight 1{z >= threshold}; < 0: the lower tail, 1{z <= threshold}): gc_ens_tail_set; needs `set_graph` only, survives
     `ens_reserve` and is independent of `ens_event_set`."""
-    thr = _f32(thresholds)
-    if thr.ndim != 4 or thr.shape[1:] != self._shape_out():
-      raise ValueError(f"thresholds must be [T, {', '.join(str(n) for n in self._shape_out())}], got {thr.shape}")
+    thr = self._thresholds_arg(thresholds)
     if not 1 <= thr.shape[0] <= 8:
       raise ValueError(f"thresholds must hold 1..8 fields, got {thr.shape[0]}")
-    d = _i32(directions)
-    if d.shape != (thr.shape[0],):
-      raise ValueError(f"directions must have shape ({thr.shape[0]},)")
+    d = _directions(directions, thr.shape[0])
     if np.any(d == 0):
       raise ValueError("directions must be non-zero")
     self._check(self._lib.gc_ens_tail_set(self._h, thr.shape[0], _ptr(thr, _f32p), _ptr(d, _i32p)))
@@ -1307,18 +1234,14 @@ class NativeDenoiser:
     """-> (sums [T, B, c_out, 4] float64: sum w, sum w ae, sum w d, sum w o; counts [T, B, c_out] uint64; invalid [T] uint64):
     the raw, additive sums of gc_ens_tail_score over the member store (`verification.TailScores` derives the scores).
     `truth` [G, B, c_out], or None = the truth uploaded last (shared with `ens_score`)."""
-    if not self._tail_thresholds:
-      raise GencastHipError("libgencast_hip error 4: no thresholds (ens_tail_set has not been called on this object)")
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    _need(self._tail_thresholds, "thresholds", "ens_tail_set")
+    self._need_store()
     t = self._truth_arg(truth)
     T, B, C = self._tail_thresholds, self.cfg.batch, self.cfg.c_out
-    u64 = ctypes.POINTER(ctypes.c_uint64)
     sums = np.empty((T, B, C, 4), dtype=np.float64)
     counts = np.empty((T, B, C), dtype=np.uint64)
     invalid = np.empty(T, dtype=np.uint64)
-    self._check(self._lib.gc_ens_tail_score(self._h, None if t is None else _ptr(t, _f32p),
-                                            _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(counts, u64), _ptr(invalid, u64)))
+    self._check(self._lib.gc_ens_tail_score(self._h, _opt(t, _f32p), _ptr(sums, _f64p), _ptr(counts, _u64p), _ptr(invalid, _u64p)))
     return sums, counts, invalid
 
   # -- regional ensemble scores (the sums of ens_score per region of grid nodes, from one pass) ---------
@@ -1335,25 +1258,21 @@ class NativeDenoiser:
     if raw.dtype.kind not in "ui" or (raw.size and (int(raw.min()) < 0 or int(raw.max()) >> R)):
       raise ValueError(f"node_bits must be unsigned integers below 2^{R}")
     bits = np.ascontiguousarray(raw, dtype=np.uint32)
-    self._check(self._lib.gc_ens_region_set(self._h, R, _ptr(bits, ctypes.POINTER(ctypes.c_uint32))))
+    self._check(self._lib.gc_ens_region_set(self._h, R, _ptr(bits, _u32p)))
     self._regions = R
 
   def ens_region_score(self, truth=None):
     """-> (sums [R, B, c_out, 6] float64, hist [R, B, c_out, M + 1] uint64, invalid [R] uint64): per region the raw, additive
     sums, rank histogram and skipped points of `ens_score` restricted to the region's nodes (gc_ens_region_score;
     `verification.RegionScores` derives the scores).  `truth` [G, B, c_out], or None = the truth uploaded last."""
-    if not self._regions:
-      raise GencastHipError("libgencast_hip error 4: no regions (ens_region_set has not been called on this object)")
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
+    _need(self._regions, "regions", "ens_region_set")
+    self._need_store()
     t = self._truth_arg(truth)
     R, B, C = self._regions, self.cfg.batch, self.cfg.c_out
-    u64 = ctypes.POINTER(ctypes.c_uint64)
     sums = np.empty((R, 6, B, C), dtype=np.float64)
     hist = np.empty((R, B, C, self._ens_members + 1), dtype=np.uint64)
     invalid = np.empty(R, dtype=np.uint64)
-    self._check(self._lib.gc_ens_region_score(self._h, None if t is None else _ptr(t, _f32p),
-                                              _ptr(sums, ctypes.POINTER(ctypes.c_double)), _ptr(hist, u64), _ptr(invalid, u64)))
+    self._check(self._lib.gc_ens_region_score(self._h, _opt(t, _f32p), _ptr(sums, _f64p), _ptr(hist, _u64p), _ptr(invalid, _u64p)))
     return np.ascontiguousarray(np.moveaxis(sums, 1, -1)), hist, invalid
 
   # -- time-window ensemble fields (a ring of the last lead times, reduced into this handle's member store) --
@@ -1371,38 +1290,30 @@ class NativeDenoiser:
     if kind == 0:
       if coef is None:
         raise ValueError("a linear window needs its coefficients")
-      a = np.ascontiguousarray(coef, dtype=np.float64)
+      a = _f64(coef)
       if a.shape != (length,):
         raise ValueError(f"coef must have shape ({length},)")
       if not np.all(np.isfinite(a)):
         raise ValueError("coef must be finite")
     elif coef is not None:
       raise ValueError("only a linear window takes coefficients")
-    self._check(self._lib.gc_ens_window_set(self._h, kind, length,
-                                            None if a is None else _ptr(a, ctypes.POINTER(ctypes.c_double))))
+    self._check(self._lib.gc_ens_window_set(self._h, kind, length, _opt(a, _f64p)))
     self._window_length = length
 
   def ens_window_push(self, src: "NativeDenoiser", truth=None) -> None:
     """The ring of this handle <- the M members and the truth of `src`'s store as they stand, device to device
     (gc_ens_window_push).  `truth` [G, B, c_out] is uploaded into `src`, or None = the truth `src` holds.  On return `src`'s
     store may be overwritten."""
-    if not self._window_length:
-      raise GencastHipError("libgencast_hip error 4: no plan (ens_window_set has not been called on this object)")
-    if not isinstance(src, NativeDenoiser) or src is self:
-      raise ValueError("src must be another NativeDenoiser")
-    t = None
-    if truth is not None:
-      t = _f32(truth)
-      if t.shape != self._shape_out():
-        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
-    self._check(self._lib.gc_ens_window_push(self._h, src._h, None if t is None else _ptr(t, _f32p)))  # pylint: disable=protected-access
+    _need(self._window_length, "plan", "ens_window_set")
+    self._check_src(src)
+    t = self._truth_arg(truth)
+    self._check(self._lib.gc_ens_window_push(self._h, _handle_of(src), _opt(t, _f32p)))
 
   def ens_window_emit(self) -> None:
     """Every slot of this handle's member store and its truth <- the window over the last `length` pushes
     (gc_ens_window_emit): afterwards `ens_score(None)`, `ens_event_score(None)`, `ens_order_score(None)` and
     `ens_download_member` of THIS handle see the windowed fields.  The ring is unchanged."""
-    if not self._window_length:
-      raise GencastHipError("libgencast_hip error 4: no plan (ens_window_set has not been called on this object)")
+    _need(self._window_length, "plan", "ens_window_set")
     self._check(self._lib.gc_ens_window_emit(self._h))
 
   def ens_window_reset(self) -> None:
@@ -1416,16 +1327,14 @@ class NativeDenoiser:
 
   def ctx_save(self, slot: int, src: Optional["NativeDenoiser"] = None) -> None:
     """Slot <- the current conditioning of `src` (None: of this handle), device to device (gc_ctx_save)."""
-    self._check(self._lib.gc_ctx_save(self._h, int(slot), None if src is None else src._h))  # pylint: disable=protected-access
+    self._check(self._lib.gc_ctx_save(self._h, int(slot), _handle_of(src)))
 
   def ctx_load(self, slot: int, dst: Optional["NativeDenoiser"] = None) -> None:
     """The conditioning of `dst` (None: of this handle) <- slot, re-packed like `upload_cond_dev` (gc_ctx_load)."""
-    self._check(self._lib.gc_ctx_load(self._h, int(slot), None if dst is None else dst._h))  # pylint: disable=protected-access
+    self._check(self._lib.gc_ctx_load(self._h, int(slot), _handle_of(dst)))
 
   def ctx_download(self, slot: int) -> np.ndarray:
-    out = np.empty(self._shape_in(), dtype=np.float32)
-    self._check(self._lib.gc_ctx_download(self._h, int(slot), _ptr(out, _f32p)))
-    return out
+    return self._download(self._lib.gc_ctx_download, int(slot), shape=self._shape_in())
 
   # -- spherical-harmonic power spectra (analysed on the device) -------------------------------------
   def spec_set_tables(self, legendre_analysis, cos_a, sin_a) -> None:
@@ -1439,41 +1348,29 @@ class NativeDenoiser:
     self._spec_lmax = int(q.shape[0])
     self._band_c_src = 0                       # (a band plan goes with the tables it was made for)
 
-  def _spec_need_tables(self):
-    if not self._spec_lmax:
-      raise GencastHipError("libgencast_hip error 4: no analysis tables (spec_set_tables has not been called on this object)")
-
   def spec_field(self, field=None) -> np.ndarray:
     """-> power [B, c_out, lmax] float64 of `field` [G, B, c_out], or of the last resident sample (None): gc_spec_field."""
-    self._spec_need_tables()
+    _need(self._spec_lmax, "analysis tables", "spec_set_tables")
     x = None
     if field is not None:
       x = _f32(field)
       if x.shape != self._shape_out():
         raise ValueError(f"field must be {self._shape_out()}, got {x.shape}")
     power = np.empty((self.cfg.batch, self.cfg.c_out, self._spec_lmax), dtype=np.float64)
-    self._check(self._lib.gc_spec_field(self._h, None if x is None else _ptr(x, _f32p),
-                                        _ptr(power, ctypes.POINTER(ctypes.c_double))))
+    self._check(self._lib.gc_spec_field(self._h, _opt(x, _f32p), _ptr(power, _f64p)))
     return power
 
   def ens_spectrum(self, truth=None, want_member_power: bool = False):
     """-> sums [B, c_out, lmax, 6] float64, the raw additive sums of gc_ens_spectrum over the member store
     (`spectra.EnsembleSpectra` derives the rest); with `want_member_power` also [M, B, c_out, lmax].
     `truth` [G, B, c_out], or None = the truth uploaded last (shared with `ens_score`)."""
-    self._spec_need_tables()
-    if not self._ens_members:
-      raise GencastHipError("libgencast_hip error 4: no member store (ens_reserve has not been called on this object)")
-    t = None
-    if truth is not None:
-      t = _f32(truth)
-      if t.shape != self._shape_out():
-        raise ValueError(f"truth must be {self._shape_out()}, got {t.shape}")
+    _need(self._spec_lmax, "analysis tables", "spec_set_tables")
+    self._need_store()
+    t = self._truth_arg(truth)
     B, C, L = self.cfg.batch, self.cfg.c_out, self._spec_lmax
-    dp = ctypes.POINTER(ctypes.c_double)
     sums = np.empty((6, B, C, L), dtype=np.float64)
     mp = np.empty((self._ens_members, B, C, L), dtype=np.float64) if want_member_power else None
-    self._check(self._lib.gc_ens_spectrum(self._h, None if t is None else _ptr(t, _f32p), _ptr(sums, dp),
-                                          None if mp is None else _ptr(mp, dp)))
+    self._check(self._lib.gc_ens_spectrum(self._h, _opt(t, _f32p), _ptr(sums, _f64p), _opt(mp, _f64p)))
     sums = np.ascontiguousarray(np.moveaxis(sums, 0, -1))
     return (sums, mp) if want_member_power else sums
 
